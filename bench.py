@@ -20,6 +20,13 @@ as a child process (one rank per GPU over RCCL), relays rank 0's JSON line and a
 leg from another child -- `mgh_compress_multi`, one process driving N devices -- as
 `native_multi`. Under `torch.distributed.run` (WORLD_SIZE set) it is a rank.
 
+A plain run sets up, warms up, times `--steps` steps, writes the outputs of the last step when
+`--dump-outputs DIR` is given, and prints the line: metric, value, unit, higher_is_better, dtype,
+ms_per_step. Everything else it can measure or check -- per-kernel breakdown and roofline,
+decompression, 16-bit, two-stream and end-to-end legs, the other configurations, the CPU baseline
+and its parity check, the N > 1 native_multi / capi_dist legs -- runs after the timed steps with
+`--full`.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -34,6 +41,9 @@ sys.path.insert(0, ROOT)
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (/opt/skills/guides/MI355X_MICROARCH.md)
 TOL = 1e-3
 SHAPE = (512, 512, 512)
+# --dump-outputs: at most 2^22 quantized coefficients and 2^20 outliers, float64: 48 MB in all
+DUMP_SAMPLE = 1 << 22
+DUMP_OUTLIERS = 1 << 20
 
 
 def algorithmic_bytes_per_step(h, esz):
@@ -269,7 +279,7 @@ def launch_ranks(args, argv):
     if p.returncode != 0 or res is None:
         sys.stdout.write(p.stdout[-4000:])
         raise SystemExit(p.returncode or 1)
-    if not args.dist_dry_run and not args.no_native_multi:
+    if args.full and not args.dist_dry_run and not args.no_native_multi:
         cmd2 = [sys.executable, os.path.abspath(__file__), "--native-multi", "--gpus", str(args.gpus)]
         try:
             p2 = subprocess.run(cmd2, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
@@ -483,7 +493,7 @@ def gpu_field(torch, shape, dtype, dev, seed=20260101):
 
 def config_leg(torch, mgard_amd, name, dev, local_rank, steps=5, end_to_end=False, dist=None, world=1,
                rank=0, host_e2e=False):
-    """One of the other BASELINE.json configurations as a step-only leg of the default run
+    """One of the other BASELINE.json configurations as a step-only leg of the --full run
     (`other_configs`): input generated on the device, `steps` timed steps after 2 warm-ups."""
     import numpy as np
     from tests.util import nonuniform_coords
@@ -1016,16 +1026,52 @@ def scatter_gather_leg(torch, mgard_amd, dist, dev, local_rank, rank, world, sla
     return out
 
 
+def dump_outputs(path, torch, bufs, prefix=""):
+    """--dump-outputs: what the caller of the timed step holds after its last step, as float64 .npy
+    (exact for these integers), so that two builds can be compared output for output:
+    quantized.npy    the quantized coefficients, flattened; beyond DUMP_SAMPLE of them, the values at
+                     a fixed seeded sample of flat positions (the same positions for the same shape)
+    outlier_count.npy
+    outlier_idx.npy, outlier_val.npy   the outliers sorted by position (the library appends them in
+                     atomic order); beyond DUMP_OUTLIERS of them, a fixed seeded sample of that list"""
+    import numpy as np
+    q, cnt, oidx, oval = bufs
+
+    def sample(x, k, seed):
+        if x.numel() <= k:
+            return x
+        pos = np.unique(np.random.default_rng(seed).integers(0, x.numel(), k))
+        return x[torch.from_numpy(pos).to(x.device)]
+    n = min(int(cnt.item()), oidx.numel())
+    idx, order = torch.sort(oidx[:n])
+    out = {"quantized": sample(q.reshape(-1), DUMP_SAMPLE, 20260201), "outlier_count": cnt[:1],
+           "outlier_idx": sample(idx, DUMP_OUTLIERS, 20260202),
+           "outlier_val": sample(oval[:n][order], DUMP_OUTLIERS, 20260202)}
+    os.makedirs(path, exist_ok=True)
+    for name, t in out.items():
+        np.save(os.path.join(path, prefix + name + ".npy"), t.cpu().numpy().astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     # (defaults: a timed window of ~90 ms -- a fresh box was seen to run its first 25 ms at 2/3 speed once)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run everything beyond the headline figure: per-kernel "
+                         "breakdown and roofline, decompression / 16-bit / two-stream / end-to-end legs, the other "
+                         "configurations, the CPU baseline and parity check, and for N > 1 the native_multi / "
+                         "capi_dist legs (a plain run sets up, warms up, times the steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step gave its caller to DIR/<name>.npy "
+                         "(float64; a fixed seeded sample of the quantized coefficients when they exceed "
+                         "%d values)" % DUMP_SAMPLE)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--only-step", action="store_true",
-                    help="time the step only: no decompression / 16-bit / end-to-end legs, no CPU "
-                         "baseline (profiling runs: every launch of the trace belongs to the metric)")
+                    help="with --full: the per-kernel breakdown and roofline of the step only, no decompression "
+                         "/ 16-bit / end-to-end legs, no CPU baseline (profiling runs: every launch of the trace "
+                         "belongs to the metric)")
     ap.add_argument("--shape", type=str, default=None, help="override, e.g. 256,256,256")
     ap.add_argument("--config", choices=sorted(CONFIGS), default="512f32",
                     help="BASELINE.json configuration: 512f32 = configs[1] (the metric's, default), "
@@ -1033,7 +1079,7 @@ def main():
     ap.add_argument("--no-host-leg", action="store_true",
                     help="skip the host-buffer end-to-end leg (end_to_end_host)")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the step-only legs of configs[2], [3], [4] in the default run")
+                    help="skip the step-only legs of configs[2], [3], [4] in the --full run")
     ap.add_argument("--no-native-multi", action="store_true",
                     help="N > 1 launcher: skip the one-process / N-devices leg (mgh_compress_multi)")
     ap.add_argument("--native-multi", action="store_true",
@@ -1048,6 +1094,8 @@ def main():
                     help="exercise the N>1 code path (process group + norm all-reduce) with any "
                          "world size, e.g. 1 (developer check)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # ---- N > 1 as the driver calls it (`python3 bench.py --gpus N ...`): become the launcher
     # BEFORE anything imports torch or touches a GPU ----
@@ -1126,46 +1174,29 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    # ---- warm-up (untimed), then 3 untimed steady-state steps with every kernel bracketed by
-    # HIP events: per-kernel breakdown + which kernel dominates ----
+    # ---- warm-up (untimed) ----
     for _ in range(max(args.warmup, 1)):
-        nrm = step()
+        step()
     torch.cuda.synchronize()
     n_out = int(cnt.item())
     assert n_out <= cap, "outlier buffer too small: %d > %d" % (n_out, cap)
-    NPROF = 3
-    h.profile(True)
-    for _ in range(NPROF):
-        step()
-    torch.cuda.synchronize()
-    prof = h.profile_read(reset=True)
-    dominant = max(prof.items(), key=lambda kv: kv[1][0])[0]
 
-    # ---- timed region: K steps, HIP events on the dominant kernel's launches only ----
-    h.profile(True, only=dominant)
+    # ---- timed region: K steps ----
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
         step()
     barrier()
     elapsed = time.perf_counter() - t0
-    dom = h.profile_read(reset=True)[dominant]
-    h.profile(False)
     if dist is not None:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, torch, bufs, "" if dist is None else "rank%d_" % rank)
 
-    # HBM traffic of the dominant kernel from the committed PMC passes (same workload only)
-    # (a file taken on other kernel sources than the ones this run loads is refused)
-    traffic, traffic_note = (None, "no PMC traffic file for this configuration") if args.shape else \
-        pmc_traffic(args.config, dominant)
     in_bytes = N * esz
     value = in_bytes * args.steps * world / elapsed / 1e9
-    alg = algorithmic_bytes_per_step(h, esz)
-    dom_ms, dom_launches = dom
-    dom_bytes = alg.get(dominant, 0) * args.steps
-    achieved = dom_bytes / (dom_ms * 1e-3) / 1e9 if dom_ms > 0 else 0.0
     result = {
         "metric": "compress GB/s (input) at rel-Linf 1e-3, 3D 512^3 f32, decompose+quantize on "
                   "device-resident data" if args.config == "512f32" else
@@ -1183,17 +1214,42 @@ def main():
                    "parallelism": "1 subdomain per GPU%s" % (
                        "" if dist is None else ", scalar norm all-reduce over RCCL")},
         "hbm_frac_whole_step": round((esz + 8.0) * N / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS, 4),
-        "roofline": {"bound": "hbm", "kernel": dominant,
-                     "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
-                     "traffic_source": traffic_note,
-                     "avg_launch_ms": round(dom_ms / max(dom_launches, 1), 5),
-                     "launches": dom_launches,
-                     "algorithmic_bytes_per_step": alg.get(dominant, 0),
-                     "kernel_ms_per_step_all": {k: round(v[0] / NPROF, 4)
-                                                for k, v in sorted(prof.items())}},
     }
-    if dist is None and not args.only_step and len(shape) == 3:
+    if args.full:
+        # ---- after the timed region: 3 untimed steps with every kernel bracketed by HIP events
+        # (per-kernel breakdown + which kernel dominates), then K more steps with HIP events on the
+        # dominant kernel's launches only (its time for the roofline) ----
+        NPROF = 3
+        h.profile(True)
+        for _ in range(NPROF):
+            step()
+        torch.cuda.synchronize()
+        prof = h.profile_read(reset=True)
+        dominant = max(prof.items(), key=lambda kv: kv[1][0])[0]
+        h.profile(True, only=dominant)
+        barrier()
+        for _ in range(args.steps):
+            step()
+        barrier()
+        dom_ms, dom_launches = h.profile_read(reset=True)[dominant]
+        h.profile(False)
+        # HBM traffic of the dominant kernel from the committed PMC passes (same workload only)
+        # (a file taken on other kernel sources than the ones this run loads is refused)
+        traffic, traffic_note = (None, "no PMC traffic file for this configuration") if args.shape else \
+            pmc_traffic(args.config, dominant)
+        alg = algorithmic_bytes_per_step(h, esz)
+        dom_bytes = alg.get(dominant, 0) * args.steps
+        achieved = dom_bytes / (dom_ms * 1e-3) / 1e9 if dom_ms > 0 else 0.0
+        result["roofline"] = {"bound": "hbm", "kernel": dominant,
+                              "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                              "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
+                              "traffic_source": traffic_note,
+                              "avg_launch_ms": round(dom_ms / max(dom_launches, 1), 5),
+                              "launches": dom_launches,
+                              "algorithmic_bytes_per_step": alg.get(dominant, 0),
+                              "kernel_ms_per_step_all": {k: round(v[0] / NPROF, 4)
+                                                         for k, v in sorted(prof.items())}}
+    if args.full and dist is None and not args.only_step and len(shape) == 3:
         # How fast does THIS device move the dominant pass's bytes when nothing else is going on?
         # A pure stream with the same read/write mix (N elements read, N int64 written with
         # streaming stores, N/4 elements of side output), no halo, no arithmetic. `frac` above stays
@@ -1216,7 +1272,7 @@ def main():
                 "frac_of_peak": round(srate / HBM_PEAK_GBS, 4),
                 "kernel_vs_stream_time": round((dom_ms / max(dom_launches, 1)) / ms.value, 3)}
         del side, qcal
-    if dist is None and not args.only_step and args.config == "512f32":
+    if args.full and dist is None and not args.only_step and args.config == "512f32":
         # Informational, never `value`: two volumes in flight on two streams (two hierarchies, two
         # sets of buffers) -- what a pipeline over many subdomains / time steps does. The chain
         # below the top level is latency-bound and leaves the chip idle; the other stream's norm
@@ -1255,7 +1311,7 @@ def main():
             result["two_streams"] = {"error": str(e)}
     if args.only_step:
         args.no_cpu_baseline = True
-    if dist is None and not args.only_step:
+    if args.full and dist is None and not args.only_step:
         # decompression side (BASELINE.json configs[4] asks for the round trip): dequantize +
         # recompose of the same volume, error against the requested tolerance
         n_keep = int(cnt.item())
@@ -1367,7 +1423,7 @@ def main():
     q_host = None
     # ---- the other BASELINE.json configurations, on the driver's line (step-only legs; `value`
     # stays configs[1]) ----
-    if args.config == "512f32" and not args.shape and not args.only_step and not args.no_other_configs:
+    if args.full and args.config == "512f32" and not args.shape and not args.only_step and not args.no_other_configs:
         q_host = q.cpu().numpy() if (rank == 0 and dist is None and not args.no_cpu_baseline) else None
         del q, oidx, oval, bufs, d_u
         h.close()
@@ -1407,11 +1463,11 @@ def main():
             except (mgard_amd.MgardHipError, RuntimeError, AssertionError) as e:
                 oc["scatter_gather"] = {"error": str(e)[:300]}
         result["other_configs"] = oc
-    if dist is not None:
+    if args.full and dist is not None:
         seen = torch.ones(1, dtype=torch.int64, device=dev)
         dist.all_reduce(seen, op=dist.ReduceOp.SUM)
         result["rccl_ranks_seen"] = int(seen.item())
-    if rank == 0 and dist is None and not args.no_cpu_baseline and args.config not in ("1024f32", "4d"):
+    if args.full and rank == 0 and dist is None and not args.no_cpu_baseline and args.config not in ("1024f32", "4d"):
         base, rq = cpu_baseline(u, TOL, S, coords)
         result["cpu_baseline"] = base
         # parity spot check on the bench workload itself: quantized integers are bit-exact

@@ -1,6 +1,6 @@
 #!/bin/bash
 # SQ / TCC counters + FETCH/WRITE traffic of the decompression side (dequantize + recompose leg of
-# bench.py): PMC passes of the default legs without the other configurations.
+# bench.py): PMC passes of the `--full` legs without the other configurations.
 # usage (through gpurun): tools/decomp_counters.sh TAG
 TAG=$1; shift
 R=$PWD
@@ -14,7 +14,7 @@ P4="WRITE_SIZE"
 i=0
 for P in "$P1" "$P2" "$P3" "$P4"; do
   i=$((i+1))
-  timeout 600 rocprofv3 --kernel-trace --pmc $P -d $O/p$i -- python3 $R/bench.py --steps 3 --warmup 1 --no-other-configs --no-cpu-baseline "$@" > $O/p$i.log 2>&1
+  timeout 600 rocprofv3 --kernel-trace --pmc $P -d $O/p$i -- python3 $R/bench.py --full --steps 3 --warmup 1 --no-other-configs --no-cpu-baseline "$@" > $O/p$i.log 2>&1
   echo "pass $i rc=$?" >> $O/passes.txt
 done
 cd $R

@@ -9,7 +9,7 @@ mkdir -p $O
 python -m pytest tests -q -m gpu -rf 2>&1 | grep -E "^FAILED|^ERROR|passed|failed" | tail -12 > $O/pytest_gpu.txt
 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.txt 2>&1
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 $R/bench.py --steps 10 --warmup 3 --no-other-configs > $O/stats.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 $R/bench.py --full --steps 10 --warmup 3 --no-other-configs > $O/stats.log 2>&1
 # the same with the timed steps only (no decompress / sym16 / two-stream / end-to-end legs, whose
 # launches of the same kernels -- some of them overlapped on two streams -- enter the averages above)
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_step -- python3 $R/bench.py --steps 10 --warmup 3 --only-step > $O/stats_step.log 2>&1
@@ -52,7 +52,7 @@ tools/trace_step.sh $TAG/tlf64 --config 512f64nu
 tools/chain_counters.sh $TAG/chain > /dev/null 2>&1
 cp $O/chain/chain_counters.json $O/sq_counters_chain.json 2>/dev/null
 cp $O/chain/chain_counters.txt $O/sq_counters_chain.txt 2>/dev/null
-python bench.py > $O/bench_with_traffic.log 2>&1
-python bench.py --config 1024f32 --only-step > $O/bench_1024.log 2>&1
+python bench.py --full > $O/bench_with_traffic.log 2>&1
+python bench.py --full --config 1024f32 --only-step > $O/bench_1024.log 2>&1
 rm -rf $O/fetch $O/write $O/fetch1024 $O/write1024
 cat $O/pytest_gpu.txt $O/smoke.txt; tail -1 $O/bench_with_traffic.log | cut -c1-400

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Step time and per-kernel times under developer switches, same box: tools/sweep_env.sh (through gpurun)
-run() { env "$@" python bench.py --only-step --steps 40 --warmup 5 2>/dev/null | tail -1 | python -c "
+run() { env "$@" python bench.py --full --only-step --steps 40 --warmup 5 2>/dev/null | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); k=d['roofline']['kernel_ms_per_step_all']
 print('%-34s' % ' '.join(sys.argv[1:]), d['ms_per_step'], {a:round(b*1000) for a,b in k.items()})" "$@"; }
