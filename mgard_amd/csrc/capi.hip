@@ -83,7 +83,6 @@ struct mgh_hierarchy {
   // (kernels_ipk_dma.hpp: LDS-DMA front end, everything requested up front; default), 0 = never
   int ipk_dma = 1;
   long ipk_dma_min_env = -1;
-  int inline_qp = 0;   // MGH_INLINE_QP: the finest level's kernel computes its quantizer itself (no k_make_qparams launch in front of it)
   int ipk_dma_rounds = 4;  // MGH_IPK_DMA_ROUNDS: k_ipk_dma also for levels whose tiles need up to this many rounds of resident workgroups
   size_t ipk_dma_min = 512;  // MGH_IPK_DMA_MIN: fewest tiles of a level for k_ipk_dma (two per CU; set in mgh_hierarchy_create)
   int absmax_warm_mb = 192;  // MGH_ABSMAX_WARM_MB: the norm pass reads all but the last so many MB of the input with nontemporal loads
@@ -91,7 +90,7 @@ struct mgh_hierarchy {
   int fused_faces = 1;
   int fused_tall = 1;  // MGH_FUSED_TALL: 64 x 4 tiles for levels with a short fastest extent (default 1)
   int slice_batch = 1;  // MGH_SLICE_BATCH: D = 4 decompression, all t-slices of a kind in one launch (default 1)
-  int fused_xcd = 1;  // MGH_FUSED_XCD: tiles of a level in contiguous ranges per XCD (default 1; 2: the equal ranges of rounds 2-5 from 32 tiles on)
+  int fused_xcd = 1;  // MGH_FUSED_XCD: tiles of a level in contiguous ranges per XCD (default 1)
   int fused_fixed = 1; // MGH_FUSED_FIXED: the int64 + dictionary variant of the level kernel (default 1)
   int fused_wide = 1; // MGH_FUSED_WIDE: 4 x 64 tiles for 0 = no level, 1 = long marches, 2 = all (unset: 1 for floats, 0 for doubles)
   int fused4 = 1;     // MGH_FUSED4: D = 4 through the 3-D tile code, slice by slice (default 1)
@@ -108,19 +107,16 @@ struct mgh_hierarchy {
   uint32_t ipk_spec_max = 16384;  // MGH_IPK_SPEC_MAX: most pencils of a solve whose pencils do not fit LDS that still run in verified chunks
   int ipk_spec_k = 0;   // MGH_IPK_SPEC_K: warm-up length of a chunk (0 = 64 floats / 128 doubles; tiny values make the verification fail and exercise the repair)
   int sym16_mixed = 1;  // MGH_SYM16_MIXED: 16-bit symbols for the finest level only, int64 below it (default), 0 = 16-bit symbols on every level
-  int restore_v = 3;  // MGH_RESTORE_V: 3 = marching node restore (kernels_recompose2.hpp), 2 = one wave per pair of fine rows
   int tail_solves = 1;  // MGH_TAIL_SOLVES: the tail kernel runs the Thomas solves of the level above it
   // (the rest of the developer switches, env.hpp; all read when the hierarchy is created)
   size_t cls1 = 256, cls2 = 2048;  // MGH_CLS1 / MGH_CLS2: tile-count thresholds of the march classes
   int rch[3] = {1, 4, 16};         // MGH_RCH=a,b,c: coarse planes per workgroup of the three classes
   uint32_t ipk_w = 64;             // MGH_IPK_W: widest solver wave of the streaming Thomas solves
-  int ipk_pd = 1;                  // MGH_IPK_PD: their load-pipeline depth
   size_t ipk_contig_rounds = 4;    // MGH_IPK_CONTIG: rounds of the LDS-staged contiguous solve from which the streaming one takes over
   int ipk_range_mb = 128;          // MGH_IPK_RANGE_MB: f- and c-solve of a load vector bigger than twice this run in r-plane ranges of this size (0 = off)
   int ipk_kr16 = 1;                // MGH_IPK_KR16: 16 register-resident batches for float pencils of 512+ elements
   size_t ipk_wpc = 8;              // MGH_IPK_WPC: most one-wave solver workgroups per CU the host plans with
   bool no_head = false;            // MGH_NO_RECOMPOSE_HEAD
-  bool restore_rows = false;       // MGH_RESTORE_ROWS
   bool debug_sync = false;         // MGH_DEBUG_SYNC: name every launch on stderr and synchronise behind it
   std::map<std::string, ProfileEntry> prof;
   size_t device_bytes = 0;
@@ -211,10 +207,6 @@ template <typename T> struct DeviceState {
   // mgh_norm_stream_begin/add: the slot of the NEXT fused call already holds the reduction of its
   // input (accumulated slab by slab while the input was arriving from the host)
   bool norm_streamed = false;
-  // MGH_INLINE_QP: quantizer constants of the last inline call, on the device and as uploaded
-  QParamArgs<T> *qinl_dev = nullptr;
-  QParamArgs<T> qinl_host;
-  bool qinl_valid = false;
   T *normval = nullptr;                  // norm as T, written by k_make_qparams
   unsigned long long *oh_key = nullptr;  // outlier table of the 16-bit symbol path (grown on demand)
   long long *oh_val = nullptr;
@@ -475,7 +467,6 @@ template <typename T> void destroy_state(mgh_hierarchy *h) {
     (void)hipFree(ds->t2);
     (void)hipFree(ds->t3);
     (void)hipFree(ds->scratch_full);
-    (void)hipFree(ds->qinl_dev);
     (void)hipFree(ds->pack_in);
     (void)hipFree(ds->pack_out);
     (void)hipFree(ds->nd_w);
@@ -742,21 +733,18 @@ int ipk_launch(mgh_hierarchy *h, int axis, const uint32_t *m, T *x, const T *tt,
         if (axis == 2) { n_inner = npencil; outer_stride = 0; inner_stride = n; stride = 1; }
         else if (axis == 1) { n_inner = m[2]; outer_stride = (size_t)m[1] * m[2]; inner_stride = 1; stride = m[2]; }
         else { n_inner = m[1] * m[2]; outer_stride = batch_stride; inner_stride = 1; stride = (size_t)m[1] * m[2]; }
-#define MGH_STREAM(CONTIG, PD)                                                                \
+#define MGH_STREAM(CONTIG)                                                                    \
   {                                                                                           \
     static std::atomic<uint64_t> once{0};                                                     \
-    TRY(allow_big_lds_once(k_ipk_stream<T, U, KR, PD, CONTIG, false>, once));                 \
+    TRY(allow_big_lds_once(k_ipk_stream<T, U, KR, 1, CONTIG, false>, once));                  \
     return launch(h, name, s, [&] {                                                           \
-      k_ipk_stream<T, U, KR, PD, CONTIG, false><<<blocks, 64, lds, s>>>(                      \
+      k_ipk_stream<T, U, KR, 1, CONTIG, false><<<blocks, 64, lds, s>>>(                       \
           npencil, n_inner, outer_stride, inner_stride, stride, n, W, n_glob, x, tt, add_to,  \
           sign);                                                                              \
     });                                                                                       \
   }
-        const int pd = h->ipk_pd;
-        if (axis == 2) MGH_STREAM(true, 1)
-        if (pd == 4) MGH_STREAM(false, 4)
-        if (pd == 2) MGH_STREAM(false, 2)
-        MGH_STREAM(false, 1)
+        if (axis == 2) MGH_STREAM(true)
+        MGH_STREAM(false)
 #undef MGH_STREAM
       }
     }
@@ -910,11 +898,6 @@ template <typename T> struct QuantParams {
   int64_t *oval = nullptr;
   unsigned long long ocap = 0;
   const T *d_qp = nullptr;  // device table [2 * (L + 1)] (k_make_qparams) instead of qz / vol
-  // MGH_INLINE_QP: the call's quantizer constants in device memory + the reduction scalar; a finest
-  // level that runs k_level_fused2 computes its quantizer itself and `after_first` is not called
-  const QParamArgs<T> *d_qinl = nullptr;
-  const unsigned long long *d_qslot = nullptr;
-  std::function<int()> inline_done;  // host bookkeeping of the skipped launch
 };
 
 template <typename T>
@@ -982,7 +965,7 @@ int launch_fused2_t(mgh_hierarchy *h, const FusedArgs<T> &A, const Box3 &b, int 
   // (contiguous tile ranges per XCD only where there are tiles to hand out -- a cross-section of three
   // tiles padded to eight put every workgroup that had work on XCDs 0..2 -- 16395 x 39 x 39 f64: top
   // level 778 us; without the ranges the r-chunks rotate the tiles over the XCDs)
-  G.xcd_ranges = ntile >= (h->fused_xcd == 2 ? 32u : kXcdRangeMinTiles) ? h->fused_xcd : 0;
+  G.xcd_ranges = ntile >= kXcdRangeMinTiles ? h->fused_xcd : 0;
   const dim3 grid(G.xcd_ranges ? (ntile + 7) / 8 * 8 : ntile, (unsigned)G.nchunk, 1);
   const bool faces = G.n_ff || G.n_cf;
 #define MGH_F2(RCH)                                                                           \
@@ -1116,41 +1099,33 @@ int decompose_fused(mgh_hierarchy *h, const T *data, T *coeff, const QuantParams
       A.volume = qp->vol[l];
     }
     const int cls = level_class(h, b);
-    {
-      const bool inl = OUT == OUT_Q && l == L && qp->d_qinl && !(cls < h->box);
-      A.qinl = inl ? qp->d_qinl : nullptr;
-      A.qslot = inl ? qp->d_qslot : nullptr;
-      if (l == L) {
-        if (inl) TRY(qp->inline_done());
-        else TRY(after_first());
-      }
-      // (the level kernels test the dictionary range in 32 bits: the entry points send larger
-      // dictionaries through decompose + quantize)
-      if (OUT == OUT_Q && !(qp->dict_size >= 0 && qp->dict_size <= ((int64_t)1 << 30)))
-        return fail(MGH_ERR_INVALID_ARGUMENT, "fused path: dict_size must be at most 2^30");
-      if (cls < h->box) {
-        // small level: no march (kernels_box.hpp)
-        constexpr int BR = 4, BC = 4, BF = 8;
-        const int bx = ((int)b.m[2] + BF - 1) / BF, by = ((int)b.m[1] + BC - 1) / BC,
-                  bz = ((int)b.m[0] + BR - 1) / BR;
-        TRY(launch(h, OUT == OUT_Q ? "level_box_q" : "level_box", s, [&] {
-          k_level_box<T, OUT, BR, BC, BF><<<(unsigned)(bx * by * bz), 256, 0, s>>>(A, bx, by);
-        }));
-      } else {
-        // long marches (RCH = 16: 9% r-halo) when there are plenty of tiles, short ones
-        // (RCH = 4) on the small levels where the march length is pure latency
-        const char *nm = cls == 2 ? (OUT == OUT_Q ? "level_fused_q" : "level_fused")
-                                  : (OUT == OUT_Q ? "level_fused_q_small" : "level_fused_small");
-        if (OUT == OUT_Q && agg) {  // (many outliers last time: slot requests per workgroup)
-          if (A.prep_huffman && !A.q16 && h->fused_fixed)
-            TRY((launch_fused2<T, OUT == OUT_Q ? OUT_QH : OUT, OUT == OUT_Q>(h, A, b, cls, nm, s)));
-          else
-            TRY((launch_fused2<T, OUT, OUT == OUT_Q>(h, A, b, cls, nm, s)));
-        } else if (OUT == OUT_Q && A.prep_huffman && !A.q16 && h->fused_fixed)
-          TRY((launch_fused2<T, OUT == OUT_Q ? OUT_QH : OUT>(h, A, b, cls, nm, s)));
+    if (l == L) TRY(after_first());
+    // (the level kernels test the dictionary range in 32 bits: the entry points send larger
+    // dictionaries through decompose + quantize)
+    if (OUT == OUT_Q && !(qp->dict_size >= 0 && qp->dict_size <= ((int64_t)1 << 30)))
+      return fail(MGH_ERR_INVALID_ARGUMENT, "fused path: dict_size must be at most 2^30");
+    if (cls < h->box) {
+      // small level: no march (kernels_box.hpp)
+      constexpr int BR = 4, BC = 4, BF = 8;
+      const int bx = ((int)b.m[2] + BF - 1) / BF, by = ((int)b.m[1] + BC - 1) / BC,
+                bz = ((int)b.m[0] + BR - 1) / BR;
+      TRY(launch(h, OUT == OUT_Q ? "level_box_q" : "level_box", s, [&] {
+        k_level_box<T, OUT, BR, BC, BF><<<(unsigned)(bx * by * bz), 256, 0, s>>>(A, bx, by);
+      }));
+    } else {
+      // long marches (RCH = 16: 9% r-halo) when there are plenty of tiles, short ones
+      // (RCH = 4) on the small levels where the march length is pure latency
+      const char *nm = cls == 2 ? (OUT == OUT_Q ? "level_fused_q" : "level_fused")
+                                : (OUT == OUT_Q ? "level_fused_q_small" : "level_fused_small");
+      if (OUT == OUT_Q && agg) {  // (many outliers last time: slot requests per workgroup)
+        if (A.prep_huffman && !A.q16 && h->fused_fixed)
+          TRY((launch_fused2<T, OUT == OUT_Q ? OUT_QH : OUT, OUT == OUT_Q>(h, A, b, cls, nm, s)));
         else
-          TRY((launch_fused2<T, OUT>(h, A, b, cls, nm, s)));
-      }
+          TRY((launch_fused2<T, OUT, OUT == OUT_Q>(h, A, b, cls, nm, s)));
+      } else if (OUT == OUT_Q && A.prep_huffman && !A.q16 && h->fused_fixed)
+        TRY((launch_fused2<T, OUT == OUT_Q ? OUT_QH : OUT>(h, A, b, cls, nm, s)));
+      else
+        TRY((launch_fused2<T, OUT>(h, A, b, cls, nm, s)));
     }
     // (the level right above the tail leaves its three solves to the tail kernel, which needs the
     // box in LDS anyway)
@@ -1263,7 +1238,7 @@ int launch_fused4_t(mgh_hierarchy *h, const FusedArgs<T> &A, const Fused4<T> &Q,
     G.nchunk = fused_nchunk(mri, RCHv);
     G.chunk_hi = G.nchunk;
     const unsigned ntile = (unsigned)(G.n_main + G.n_ff + G.n_cf);
-    G.xcd_ranges = ntile >= (h->fused_xcd == 2 ? 32u : kXcdRangeMinTiles) ? h->fused_xcd : 0;  // (see launch_fused2_t)
+    G.xcd_ranges = ntile >= kXcdRangeMinTiles ? h->fused_xcd : 0;  // (see launch_fused2_t)
     const unsigned gx = G.xcd_ranges ? (ntile + 7) / 8 * 8 : ntile;
     const bool faces = G.n_ff || G.n_cf;
     const unsigned n_even = (unsigned)m_t, n_odd = (unsigned)(n_t - m_t);
@@ -1900,8 +1875,7 @@ int recompose_impl(mgh_hierarchy *h, const T *coeff, T *data, hipStream_t s) {
 // (Compressor::Decompress lines 256-257 = Dequantize + Recompose). With QT = T the same level
 // loop runs on floating-point coefficients (Compressor::Recompose on its own).
 // Node restore of one level (or one t-slice of a 4-D level): the marching kernel
-// (kernels_recompose2.hpp), or the row-pair / row kernels of kernels_recompose.hpp
-// (MGH_RESTORE_V=2, MGH_RESTORE_ROWS=1: cross-checks).
+// (kernels_recompose2.hpp).
 // (TC x TF coarse nodes per workgroup: 4 x 64, or 64 x 4 where the fastest extent is short -- fused_tall_tiles)
 template <typename T, typename QT, bool TODD, int TC, int TF>
 int launch_restore3(mgh_hierarchy *h, const RecomposeArgs<T> &A, const Box3 &b, const char *nm, hipStream_t st) {
@@ -1920,16 +1894,8 @@ int launch_restore3(mgh_hierarchy *h, const RecomposeArgs<T> &A, const Box3 &b, 
 
 template <typename T, typename QT, bool TODD>
 int launch_restore(mgh_hierarchy *h, const RecomposeArgs<T> &A, const Box3 &b, const char *nm, hipStream_t st) {
-  if (h->restore_v == 3 && !h->restore_rows && fused_tall_tiles(h, b))
-    return launch_restore3<T, QT, TODD, 64, 4>(h, A, b, nm, st);
-  if (h->restore_v == 3 && !h->restore_rows) return launch_restore3<T, QT, TODD, 4, 64>(h, A, b, nm, st);
-  const dim3 blk(64, 4, 1);
-  if (h->restore_rows && !TODD)
-    return launch(h, nm, st, [&] {
-      k_level_restore_q<T, QT><<<dim3(1, (b.n[1] + 3) / 4, b.n[0]), blk, 0, st>>>(A);
-    });
-  const dim3 grid(1, ((b.n[1] + 1) / 2 + 3) / 4, b.n[0]);
-  return launch(h, nm, st, [&] { k_level_restore2_q<T, QT, TODD><<<grid, blk, 0, st>>>(A); });
+  if (fused_tall_tiles(h, b)) return launch_restore3<T, QT, TODD, 64, 4>(h, A, b, nm, st);
+  return launch_restore3<T, QT, TODD, 4, 64>(h, A, b, nm, st);
 }
 // Load-vector pass of the decompression side (one level, or one t-slice of a 4-D level):
 // one plane per step, march length by the number of tiles.
@@ -2101,7 +2067,7 @@ int recompose_levels4(mgh_hierarchy *h, RecomposeArgs<T> A0, const std::vector<T
     const int n_t = (int)N[0], m_t = (int)Mc[0];
     // ---- load vectors of the padded t positions: one launch for all of them (grid.z limit
     // permitting; MGH_SLICE_BATCH=0: a launch per slice)
-    const bool batch = h->slice_batch && h->restore_v == 3 && !h->restore_rows &&
+    const bool batch = h->slice_batch &&
                        (size_t)(2 * m_t - 1) * ((Mc[1] + 15) / 16) < 65536;  // (grid.z of the load-vector launch)
     if (n_t % 2 == 0)  // ghost slice
       HIP_TRY(hipMemsetAsync(ds->load4 + (size_t)(n_t - 1) * M, 0, M * sizeof(T), st));
@@ -2446,7 +2412,7 @@ inline unsigned ld_grid(const LdView &V) { return (unsigned)std::min<uint64_t>((
 // The norm reduction of `data` (dense, or pitched with the strides of `view`) accumulated into `slot`.
 template <typename T>
 int norm_reduce(mgh_hierarchy *h, const T *data, double s, unsigned long long *slot, const LdView *view,
-                size_t n_cold, hipStream_t st, unsigned long long *zero_a = nullptr, unsigned long long *zero_b = nullptr) {
+                size_t n_cold, hipStream_t st) {
   const bool inf = (T)s == std::numeric_limits<T>::infinity();
   if (view) {
     if (inf) return launch(h, "absmax", st, [&] { k_norm_ld<T, false><<<ld_grid(*view), 256, 0, st>>>(data, *view, slot); });
@@ -2454,8 +2420,8 @@ int norm_reduce(mgh_hierarchy *h, const T *data, double s, unsigned long long *s
   }
   const size_t total = h->total;
   const unsigned grid = (unsigned)std::min<size_t>((total + 1023) / 1024, 256 * 8);
-  if (inf) return launch(h, "absmax", st, [&] { k_absmax<T><<<grid, 256, 0, st>>>(data, total, slot, n_cold, zero_a, zero_b); });
-  return launch(h, "sqsum", st, [&] { k_sqsum<T><<<grid, 256, 0, st>>>(data, total, (double *)slot, n_cold, zero_a, zero_b); });
+  if (inf) return launch(h, "absmax", st, [&] { k_absmax<T><<<grid, 256, 0, st>>>(data, total, slot, n_cold); });
+  return launch(h, "sqsum", st, [&] { k_sqsum<T><<<grid, 256, 0, st>>>(data, total, (double *)slot, n_cold); });
 }
 
 // Launch the norm reduction; the result stays in ds->scalar (absmax bits or double sum).
@@ -2586,7 +2552,6 @@ int fused_q_entry_device(mgh_hierarchy *h, const T *data, int ebtype, double tol
   const bool streamed = ds->norm_streamed && !d_norm && ebtype == MGH_REL;
   ds->norm_streamed = false;
   const bool need_norm = !d_norm && ebtype == MGH_REL && !streamed;
-  bool inline_qp = false;
   // The norm scalar has two slots used alternately: this call reduces into scalar[slot] (zero on
   // entry) and k_make_qparams zeroes the other one for the next call, together with the outlier
   // counter -- two memset launches less per step.
@@ -2604,31 +2569,8 @@ int fused_q_entry_device(mgh_hierarchy *h, const T *data, int ebtype, double tol
       const LdView V = ld_view(h, 0);
       TRY(norm_reduce<T>(h, data, s, slot, &V, 0, st));
     } else {
-      inline_qp = h->inline_qp && h->D == 3 && !decomposed;
-      TRY(norm_reduce<T>(h, data, s, slot, nullptr, total > warm ? total - warm : 0, st,
-                         inline_qp ? (unsigned long long *)ocount : nullptr, inline_qp ? other : nullptr));
+      TRY(norm_reduce<T>(h, data, s, slot, nullptr, total > warm ? total - warm : 0, st));
     }
-  }
-  QuantParams<T> qp;
-  if (inline_qp) {
-    // the call's constants in device memory (uploaded when they change: per hierarchy they are a
-    // function of bound type, tolerance and s)
-    QParamArgs<T> P;
-    TRY(fill_qparam_args<T>(h, d_norm, ebtype, tol, s, decomposed, nsub, nullptr, P));
-    P.scalar = nullptr;  // (the slot alternates: it travels in FusedArgs::qslot)
-    if (!ds->qinl_dev) TRY(dev_alloc(h, &ds->qinl_dev, (size_t)1));
-    if (!ds->qinl_valid || std::memcmp(&ds->qinl_host, &P, sizeof(P)) != 0) {
-      std::memcpy(&ds->qinl_host, &P, sizeof(P));
-      HIP_TRY(hipMemcpyAsync(ds->qinl_dev, &ds->qinl_host, sizeof(P), hipMemcpyHostToDevice, st));
-      ds->qinl_valid = true;
-    }
-    qp.d_qinl = ds->qinl_dev;
-    qp.d_qslot = slot;
-    qp.inline_done = [ds] {
-      ds->scalar_slot = 1 - ds->scalar_slot;
-      ds->fscal_dirty = false;
-      return (int)MGH_SUCCESS;
-    };
   }
   auto qparams = [&] {
     QParamArgs<T> P;
@@ -2640,6 +2582,7 @@ int fused_q_entry_device(mgh_hierarchy *h, const T *data, int ebtype, double tol
     ds->fscal_dirty = false;
     return (int)MGH_SUCCESS;
   };
+  QuantParams<T> qp;
   qp.d_qp = ds->qz;
   qp.dict_size = (int64_t)dict_size;
   qp.prep_huffman = prep_huffman;
@@ -2828,7 +2771,6 @@ int mgh_hierarchy_create(mgh_hierarchy **out, int D, const uint64_t *shape, int 
     h->fused_wide = (int)env_get("MGH_FUSED_WIDE", -1);  // (-1: by data type, below)
     h->fused4 = (int)env_get("MGH_FUSED4", h->fused4);
     h->box = (int)env_get("MGH_BOX", h->box);
-    h->restore_v = (int)env_get("MGH_RESTORE_V", h->restore_v);
     h->sym16_mixed = (int)env_get("MGH_SYM16_MIXED", h->sym16_mixed);
     h->ipk_spec = (int)env_get("MGH_IPK_SPEC", h->ipk_spec);
     h->ipk_spec_k = (int)env_get("MGH_IPK_SPEC_K", h->ipk_spec_k);
@@ -2839,19 +2781,16 @@ int mgh_hierarchy_create(mgh_hierarchy **out, int D, const uint64_t *shape, int 
     h->ipk_chunk_k = (int)env_get("MGH_IPK_CHUNK_K", h->ipk_chunk_k);
     h->tail_solves = (int)env_get("MGH_TAIL_SOLVES", h->tail_solves);
     h->ipk_dma_rounds = (int)env_get("MGH_IPK_DMA_ROUNDS", h->ipk_dma_rounds);
-    h->inline_qp = (int)env_get("MGH_INLINE_QP", h->inline_qp);
     h->nd_rows = (int)env_get("MGH_ND_ROWS", h->nd_rows);
     h->cls1 = (size_t)env_get("MGH_CLS1", (long)h->cls1);
     h->cls2 = (size_t)env_get("MGH_CLS2", (long)h->cls2);
     if (const char *e = std::getenv("MGH_RCH")) std::sscanf(e, "%d,%d,%d", &h->rch[0], &h->rch[1], &h->rch[2]);
     h->ipk_w = (uint32_t)env_get("MGH_IPK_W", h->ipk_w);
-    h->ipk_pd = (int)env_get("MGH_IPK_PD", h->ipk_pd);
     h->ipk_wpc = (size_t)env_get("MGH_IPK_WPC", (long)h->ipk_wpc);
     h->ipk_kr16 = (int)env_get("MGH_IPK_KR16", h->ipk_kr16);
     h->ipk_range_mb = (int)env_get("MGH_IPK_RANGE_MB", h->ipk_range_mb);
     h->ipk_contig_rounds = (size_t)env_get("MGH_IPK_CONTIG", (long)h->ipk_contig_rounds);
     h->no_head = env_get("MGH_NO_RECOMPOSE_HEAD", 0) != 0;
-    h->restore_rows = env_get("MGH_RESTORE_ROWS", 0) != 0;
     h->debug_sync = env_get("MGH_DEBUG_SYNC", 0) != 0;
     if (h->force_nd) h->force_v1 = true;  // keeps the fused entry points off
   }

@@ -22,14 +22,13 @@ struct EnvSwitch {
 inline const EnvSwitch *env_switches(size_t *count) {
   static const EnvSwitch k[] = {
       {"MGH_FORCE_V1", 0, 1},       {"MGH_FORCE_ND", 0, 1},        {"MGH_IPK_STREAM", 0, 1},      {"MGH_IPK_DMA", 0, 1},  {"MGH_IPK_DMA_MIN", 0, 1 << 30},  {"MGH_MULTI_FORCE_PEER", 0, 1},  {"MGH_ABSMAX_WARM_MB", 0, 1 << 20},      {"MGH_FUSED_FACES", 0, 1},
-      {"MGH_FUSED_XCD", 0, 2},      {"MGH_FUSED_FIXED", 0, 1},     {"MGH_FUSED_WIDE", 0, 2},
+      {"MGH_FUSED_XCD", 0, 1},      {"MGH_FUSED_FIXED", 0, 1},     {"MGH_FUSED_WIDE", 0, 2},
       {"MGH_SLICE_BATCH", 0, 1},      {"MGH_FUSED_TALL", 0, 1},
       {"MGH_FUSED4", 0, 1},         {"MGH_CLS1", 0, 1 << 30},     {"MGH_CLS2", 0, 1 << 30},      {"MGH_RCH", 1, 16},
-      {"MGH_IPK_W", 16, 64},        {"MGH_IPK_PD", 1, 4},          {"MGH_NO_RECOMPOSE_HEAD", 0, 1}, {"MGH_RESTORE_ROWS", 0, 1}, {"MGH_DEBUG_SYNC", 0, 1},
+      {"MGH_IPK_W", 16, 64},        {"MGH_NO_RECOMPOSE_HEAD", 0, 1}, {"MGH_DEBUG_SYNC", 0, 1},
       {"MGH_HL_TIMING", 0, 1},      {"MGH_HUFF_TB", 8, 15},        {"MGH_HUFF_SERIAL_DECODE", 0, 1},
       {"MGH_HUFF_PAR_DECODE", 0, 1}, {"MGH_SYM16_DECODE", 0, 1},   {"MGH_BOX", 0, 3},            {"MGH_IPK_WPC", 1, 16},
       {"MGH_TAIL_SOLVES", 0, 1},    {"MGH_IPK_CONTIG", 2, 1 << 20},
-      {"MGH_RESTORE_V", 2, 3},
       {"MGH_IPK_KR16", 0, 1},
       {"MGH_IPK_RANGE_MB", 0, 1 << 20},
       {"MGH_HL_PIPELINE", 0, 1},
@@ -52,10 +51,6 @@ inline const EnvSwitch *env_switches(size_t *count) {
       {"MGH_HL_DECODE_FOLLOWS", 0, 1},
       {"MGH_HL_COPY_AFFINITY", 0, 1},
       {"MGH_IPK_DMA_ROUNDS", 1, 64},
-      {"MGH_HL_COPY_PARTS", 1, 64},
-      {"MGH_HUFF_LEAN", 0, 1},
-      {"MGH_INLINE_QP", 0, 1},
-      {"MGH_HUFF_DBG", 0, 7},
   };
   *count = sizeof(k) / sizeof(k[0]);
   return k;

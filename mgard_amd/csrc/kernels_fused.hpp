@@ -48,12 +48,6 @@ template <typename T> struct FusedArgs {
   // never left the device -- read from qp[level] / qp[nlev + level] (k_make_qparams)
   T quantizer, volume;
   const T *qp;
-  // ... or (round 6, MGH_INLINE_QP: the finest level of a REL call whose norm was just reduced)
-  // computed by every workgroup itself from the reduction scalar `qslot` and the call's constants
-  // `qinl` in device memory -- the k_make_qparams launch between the norm pass and this kernel
-  // is gone; workgroup 0 leaves the table for the levels below
-  const QParamArgs<T> *qinl;
-  const unsigned long long *qslot;
   int level, nlev;
   int64_t dict_size;
   int prep_huffman;
@@ -260,25 +254,6 @@ __device__ __forceinline__ void make_qparams_body(const QParamArgs<T> &P) {
   }
   if (P.reset_count) *P.reset_count = 0;
   if (P.zero_next) *P.zero_next = 0;
-}
-
-// The finest level's own quantizer inside the level kernel (FusedArgs::qinl): every workgroup the
-// same single IEEE operations on the same inputs as make_qparams_body -- the same bits; the first
-// thread of the launch also leaves the table and the norm for the kernels behind it.
-template <typename T>
-__device__ __forceinline__ void inline_qparams(FusedArgs<T> &A, bool first_thread) {
-  const QParamArgs<T> &P = *A.qinl;
-  const T norm = qparams_norm<T>(P, A.qslot);
-  const double abs_tol = qparams_abs_tol2<T>(P, norm);
-  A.quantizer = qparams_level<T>(abs_tol, P.den[A.level]);
-  A.volume = P.vol[A.level];
-  if (first_thread) {
-    *P.norm_out = norm;
-    for (int l = 0; l < P.nlev; l++) {
-      P.qp[l] = qparams_level<T>(abs_tol, P.den[l]);
-      P.qp[P.nlev + l] = P.vol[l];
-    }
-  }
 }
 
 template <typename T> __global__ void k_make_qparams(QParamArgs<T> P) {

@@ -787,9 +787,7 @@ k_level_fused2(FusedArgs<T> A, Fused2Grid G, Fused4<T> Q) {
   __shared__ uint32_t ol_off[kLists ? 8 * kOutlierStashOf<T> : 1];
   if (kLists && threadIdx.x == 0) ol_flag = 0;  // (no pair has sequence number 0; visible behind the tile's first barrier)
   const OutlierShared<T> OS{ol_cnt, &ol_base, &ol_flag, ol_val, ol_off};
-  if ((OUT == OUT_Q || OUT == OUT_QH) && A.qinl) {
-    inline_qparams<T>(A, threadIdx.x == 0 && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0);
-  } else if ((OUT == OUT_Q || OUT == OUT_QH) && A.qp) {
+  if ((OUT == OUT_Q || OUT == OUT_QH) && A.qp) {
     A.quantizer = A.qp[A.level];
     A.volume = A.qp[A.nlev + A.level];
   }
@@ -825,14 +823,9 @@ k_level_fused2(FusedArgs<T> A, Fused2Grid G, Fused4<T> Q) {
   int b = blockIdx.x;
   if (G.xcd_ranges) {
     const int n = G.n_main + G.n_ff + G.n_cf, k = b % 8, j = b / 8;
-    if (G.xcd_ranges == 2) {  // (MGH_FUSED_XCD=2: the equal ranges of rounds 2-5, for A/B runs)
-      b = k * (int)(gridDim.x / 8) + j;
-      if (b >= n) return;
-    } else {
-      const int lo = k * n / 8, hi = (k + 1) * n / 8;
-      if (j >= hi - lo) return;
-      b = lo + j;
-    }
+    const int lo = k * n / 8, hi = (k + 1) * n / 8;
+    if (j >= hi - lo) return;
+    b = lo + j;
   }
   const int f_main_end = G.n_ff ? G.ff_F0 : A.m[2], c_main_end = G.n_cf ? G.cf_C0 : A.m[1];
   if (!FACES || b < G.n_main) {

@@ -4,13 +4,10 @@
 //                       coefficients (dequantized on the fly, never materialised as floats);
 //                       same marching / sweep structure as k_level_fused (kernels_fused.hpp),
 //                       minus the coefficient computation.
-//   k_level_restore_q : fine nodal array from the corrected coarse nodes and the quantized
-//                       coefficients: even nodes are copies, odd nodes = coefficient +
-//                       interpolant (GpkRev3D, GridProcessingKernel3D.hpp:1231-2352), with the
-//                       dequantizer of LinearQuantization.hpp:246-264 fused in.
 //   k_head_in_q       : level-0 nodal values out of the head of the quantized array.
-// Between the two, the Thomas solves of kernels_ipk.hpp subtract the correction from the
-// coarse nodes. Bit-identical to dequantize + recompose with kernels_v1.hpp.
+// Between the load vector and the node restore (k_level_restore3_q, kernels_recompose2.hpp), the
+// Thomas solves of kernels_ipk.hpp subtract the correction from the coarse nodes. Bit-identical
+// to dequantize + recompose with kernels_v1.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -253,225 +250,6 @@ k_level_loadvec_q(RecomposeArgs<T> A) {
     for (int k = 0; k < NL; k++) cur[k] = nxt[k];
   }
 #undef LI
-}
-
-// One wave per fine row (rp, cp); a lane handles the node PAIRS (fp = 2t, 2t + 1) for
-// t = lane, lane + 64, ...: consecutive lanes read consecutive quantized values in both the
-// coarse-f and the coefficient-f part of the reordered row and consecutive coarse nodes, and
-// write 8 contiguous bytes each. Row-level index math is done once per wave.
-template <typename T, typename QT>
-__global__ void __launch_bounds__(256)
-k_level_restore_q(RecomposeArgs<T> A) {
-  const int nr = A.n[0], nc = A.n[1], nf = A.n[2];
-  const int mr = A.m[0], mc = A.m[1], mf = A.m[2];
-  const int cp = blockIdx.y * blockDim.y + threadIdx.y;
-  const int rp = blockIdx.z;
-  if (cp >= nc || rp >= nr) return;
-  // coarse index of an even fine position (or of the real last node of an even-sized dim),
-  // else the node is a coefficient node at odd position p
-  auto split = [](int p, int n, int m, bool &odd) -> int {
-    odd = (p & 1) && !(n % 2 == 0 && p == n - 1);
-    return odd ? m + (p - 1) / 2 : (p == n - 1 ? m - 1 : p / 2);
-  };
-  bool ro, co;
-  const int i = split(rp, nr, mr, ro), j = split(cp, nc, mc, co);
-  const size_t mJ = mf, mI = (size_t)mc * mf;
-  const int r0 = ro ? (rp - 1) / 2 : i, c0 = co ? (cp - 1) / 2 : j;
-  const T rr = ro ? A.ratio[0][rp - 1] : (T)0, rc = co ? A.ratio[1][cp - 1] : (T)0;
-  const size_t qlin = A.lin_base + (size_t)i * A.dI + (size_t)j * A.dJ;  // (lin_base: the t-slice of a 4-D level)
-  const QT *qrow = qsrc<T>(A, QT()) + qlin;
-  T *out = A.fine + (size_t)rp * A.fI + (size_t)cp * A.fJ;
-  const bool pure_coarse = !ro && !co;
-  const T *rows[2][2];
-#pragma unroll
-  for (int a = 0; a < 2; a++)
-#pragma unroll
-    for (int b = 0; b < 2; b++)
-      rows[a][b] = A.coarse + (size_t)(r0 + (ro ? a : 0)) * mI + (size_t)(c0 + (co ? b : 0)) * mJ;
-  const bool pair_aligned = (reinterpret_cast<uintptr_t>(out) & (2 * sizeof(T) - 1)) == 0;
-  const int npair = (nf + 1) / 2;
-  for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < npair; t += gridDim.x * blockDim.x) {
-    // node E = fine 2t (coarse-f index t); node O = fine 2t+1: a coefficient node in f, or
-    // -- last node of an even-sized dim -- the coarse-f node t+1 = mf-1
-    const int fpO = 2 * t + 1;
-    const bool hasO = fpO < nf;
-    const bool fo = hasO && !(nf % 2 == 0 && fpO == nf - 1);
-    const T rf = fo ? A.ratio[2][fpO - 1] : (T)0;
-    const int t1 = min(t + 1, mf - 1);
-    // interpolants of both nodes from the (up to) 4 coarse rows, f innermost, then c, then r
-    T hE[2], hO[2];
-#pragma unroll
-    for (int a = 0; a < 2; a++) {
-      if (a == 1 && !ro) break;
-      T gE[2], gO[2];
-#pragma unroll
-      for (int b = 0; b < 2; b++) {
-        if (b == 1 && !co) break;
-        const T v0 = rows[a][b][t], v1 = rows[a][b][t1];
-        gE[b] = v0;
-        gO[b] = fo ? lerp_ref(v0, v1, rf) : v1;
-      }
-      hE[a] = co ? lerp_ref(gE[0], gE[1], rc) : gE[0];
-      hO[a] = co ? lerp_ref(gO[0], gO[1], rc) : gO[0];
-    }
-    const T iE = ro ? lerp_ref(hE[0], hE[1], rr) : hE[0];
-    const T iO = ro ? lerp_ref(hO[0], hO[1], rr) : hO[0];
-    // E: coarse node (pure copy) unless r or c is odd
-    T vE = iE;
-    if (!pure_coarse) vE = qdecode(A, qload<T>(A, qrow + t), qlin + t) + iE;
-    T vO = iO;  // (pure coarse last node of an even-sized dim: iO = row[mf-1])
-    if (hasO) {
-      if (fo)
-        vO = qdecode(A, qload<T>(A, qrow + mf + t), qlin + mf + t) + iO;
-      else if (!pure_coarse)
-        vO = qdecode(A, qload<T>(A, qrow + mf - 1), qlin + mf - 1) + iO;
-    }
-    // the pair is contiguous: one 2-element store when the row start allows it
-    T *dst = out + 2 * t;
-    if (hasO && pair_aligned) {
-      struct alignas(2 * sizeof(T)) Pair { T a, b; };
-      *reinterpret_cast<Pair *>(dst) = Pair{vE, vO};
-    } else {
-      dst[0] = vE;
-      if (hasO) dst[1] = vO;
-    }
-  }
-}
-
-// The same for a PAIR of fine rows (cp = 2J, 2J + 1) per wave: both rows interpolate from the
-// coarse rows J (and J + 1), so the coarse values and their f-interpolants are loaded / formed
-// once for the two, and the row-level set-up is paid once (466 instead of 565 us over the levels
-// of 512^3). Every output is computed with the operations of k_level_restore_q, in the same
-// order. (A 2 x 2 group -- two planes x two rows per wave -- was slower again: 570 us.)
-//
-// TODD (D = 4, an ODD slice of the slowest dimension t): every node of the slice is a coefficient
-// node of the level -- value = coefficient + lerp_t(X_a, X_b), X = the 3-D interpolant (f, then c,
-// then r) of the coarse slice below (A.coarse) / above (A.coarse_b), the mirror of the TODD tiles
-// of kernels_fused2.hpp (CalcCoefficientsND.hpp:25-236: nested lerps, fastest dim innermost).
-template <typename T, typename QT, bool TODD = false>
-__global__ void __launch_bounds__(256)
-k_level_restore2_q(RecomposeArgs<T> A) {
-  const int nr = A.n[0], nc = A.n[1], nf = A.n[2];
-  const int mr = A.m[0], mc = A.m[1], mf = A.m[2];
-  const int J = blockIdx.y * blockDim.y + threadIdx.y;  // pair index: rows 2J and 2J + 1
-  const int rp = blockIdx.z;
-  const int cpE = 2 * J, cpO = 2 * J + 1;
-  if (cpE >= nc || rp >= nr) return;
-  const bool hasRowO = cpO < nc;
-  const bool ro = (rp & 1) && !(nr % 2 == 0 && rp == nr - 1);
-  const int i = ro ? mr + (rp - 1) / 2 : (rp == nr - 1 ? mr - 1 : rp / 2);
-  const int r0 = ro ? (rp - 1) / 2 : i;
-  // row E is a coarse row in c (even position); row O is a coefficient row unless it is the real
-  // last node of an even-sized dim (then it is the coarse row mc - 1 = J + 1)
-  const bool coO = hasRowO && !(nc % 2 == 0 && cpO == nc - 1);
-  const int jE = J;
-  const int jO = coO ? mc + J : mc - 1;
-  const T rr = ro ? A.ratio[0][rp - 1] : (T)0, rc = coO ? A.ratio[1][cpO - 1] : (T)0;
-  const size_t mJ = mf, mI = (size_t)mc * mf;
-  const size_t qlinE = A.lin_base + (size_t)i * A.dI + (size_t)jE * A.dJ,
-               qlinO = A.lin_base + (size_t)i * A.dI + (size_t)jO * A.dJ;
-  const QT *qrowE = qsrc<T>(A, QT()) + qlinE, *qrowO = qsrc<T>(A, QT()) + qlinO;
-  T *outE = A.fine + (size_t)rp * A.fI + (size_t)cpE * A.fJ;
-  T *outO = outE + A.fJ;
-  const bool pureE = !TODD && !ro;          // row E: coarse in c; a pure copy unless r is odd
-  const bool pureO = !TODD && !ro && !coO;  // (row O as the coarse last row of an even-sized dim)
-  const int cJ1 = min(J + 1, mc - 1);
-  const T *rowJ[2], *rowJ1[2];
-#pragma unroll
-  for (int a = 0; a < 2; a++) {
-    rowJ[a] = A.coarse + (size_t)(r0 + (ro ? a : 0)) * mI + (size_t)J * mJ;
-    rowJ1[a] = A.coarse + (size_t)(r0 + (ro ? a : 0)) * mI + (size_t)cJ1 * mJ;
-  }
-  const ptrdiff_t to_b = TODD ? A.coarse_b - A.coarse : 0;
-  const T rt = TODD ? A.ratio_t[A.tpos - 1] : (T)0;
-  const bool alE = (reinterpret_cast<uintptr_t>(outE) & (2 * sizeof(T) - 1)) == 0;
-  const bool alO = (reinterpret_cast<uintptr_t>(outO) & (2 * sizeof(T) - 1)) == 0;
-  const int npair = (nf + 1) / 2;
-  struct alignas(2 * sizeof(T)) Pair { T a, b; };
-  for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < npair; t += gridDim.x * blockDim.x) {
-    const int fpO = 2 * t + 1;
-    const bool hasO = fpO < nf;
-    const bool fo = hasO && !(nf % 2 == 0 && fpO == nf - 1);
-    const T rf = fo ? A.ratio[2][fpO - 1] : (T)0;
-    const int t1 = min(t + 1, mf - 1);
-    // the four interpolants (row E: nodes E, O; row O: nodes E, O) from one coarse slice
-    // (`off` = element offset of the slice relative to A.coarse)
-    auto interp = [&](ptrdiff_t off, T &iEE, T &iEO, T &iOE, T &iOO) {
-      // f-level values of the coarse rows J and J+1 at the (up to) two r-planes
-      T eJ[2], oJ[2], eJ1[2], oJ1[2];
-#pragma unroll
-      for (int a = 0; a < 2; a++) {
-        if (a == 1 && !ro) break;
-        const T v0 = rowJ[a][off + t], v1 = rowJ[a][off + t1];
-        eJ[a] = v0;
-        oJ[a] = fo ? lerp_ref(v0, v1, rf) : v1;
-        if (hasRowO) {
-          const T w0 = rowJ1[a][off + t], w1 = rowJ1[a][off + t1];
-          eJ1[a] = w0;
-          oJ1[a] = fo ? lerp_ref(w0, w1, rf) : w1;
-        }
-      }
-      // row E (c even): the row-J values, then r
-      iEE = ro ? lerp_ref(eJ[0], eJ[1], rr) : eJ[0];
-      iEO = ro ? lerp_ref(oJ[0], oJ[1], rr) : oJ[0];
-      // row O: c-interpolation between rows J and J+1 (or the coarse last row J+1), then r
-      if (hasRowO) {
-        T hE[2], hO[2];
-#pragma unroll
-        for (int a = 0; a < 2; a++) {
-          if (a == 1 && !ro) break;
-          hE[a] = coO ? lerp_ref(eJ[a], eJ1[a], rc) : eJ1[a];
-          hO[a] = coO ? lerp_ref(oJ[a], oJ1[a], rc) : oJ1[a];
-        }
-        iOE = ro ? lerp_ref(hE[0], hE[1], rr) : hE[0];
-        iOO = ro ? lerp_ref(hO[0], hO[1], rr) : hO[0];
-      }
-    };
-    T iEE, iEO, iOE = 0, iOO = 0;
-    interp(0, iEE, iEO, iOE, iOO);
-    if (TODD) {
-      T bEE, bEO, bOE = 0, bOO = 0;
-      interp(to_b, bEE, bEO, bOE, bOO);
-      iEE = lerp_ref(iEE, bEE, rt);
-      iEO = lerp_ref(iEO, bEO, rt);
-      iOE = lerp_ref(iOE, bOE, rt);
-      iOO = lerp_ref(iOO, bOO, rt);
-    }
-    // ---- row E
-    {
-      T vE = iEE;
-      if (!pureE) vE = qdecode(A, qload<T>(A, qrowE + t), qlinE + t) + iEE;
-      T vO = iEO;
-      if (hasO) {
-        if (fo) vO = qdecode(A, qload<T>(A, qrowE + mf + t), qlinE + mf + t) + iEO;
-        else if (!pureE) vO = qdecode(A, qload<T>(A, qrowE + mf - 1), qlinE + mf - 1) + iEO;
-      }
-      T *dst = outE + 2 * t;
-      if (hasO && alE) {
-        *reinterpret_cast<Pair *>(dst) = Pair{vE, vO};
-      } else {
-        dst[0] = vE;
-        if (hasO) dst[1] = vO;
-      }
-    }
-    // ---- row O
-    if (hasRowO) {
-      T vE = iOE;
-      if (!pureO) vE = qdecode(A, qload<T>(A, qrowO + t), qlinO + t) + iOE;
-      T vO = iOO;
-      if (hasO) {
-        if (fo) vO = qdecode(A, qload<T>(A, qrowO + mf + t), qlinO + mf + t) + iOO;
-        else if (!pureO) vO = qdecode(A, qload<T>(A, qrowO + mf - 1), qlinO + mf - 1) + iOO;
-      }
-      T *dst = outO + 2 * t;
-      if (hasO && alO) {
-        *reinterpret_cast<Pair *>(dst) = Pair{vE, vO};
-      } else {
-        dst[0] = vE;
-        if (hasO) dst[1] = vO;
-      }
-    }
-  }
 }
 
 // D = 4: level-0 nodal values (compact (m0, m1, m2, m3)) out of the head of the quantized array;

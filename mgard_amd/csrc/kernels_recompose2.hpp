@@ -13,18 +13,17 @@ namespace mgh {
 // coefficients (GpkRev3D, GridProcessingKernel3D.hpp:1231-2352; dequantizer of
 // LinearQuantization.hpp:246-264 fused in).
 //
-// k_level_restore2_q hands one wave a pair of fine rows of ONE plane: the four (node, f, c, fc)
-// interpolants of a coarse plane are formed again for the odd plane below and the odd plane above
-// it, and every wave pays the row set-up. Here a thread owns one CELL column -- coarse node
-// (Jc, Jf) and its three odd neighbours -- and marches along r over a chunk of coarse planes,
-// the mirror of the compression side's pair step (kernels_fused2.hpp): the interpolants G(R) of
+// A thread owns one CELL column -- coarse node (Jc, Jf) and its three odd neighbours -- and
+// marches along r over a chunk of coarse planes, the mirror of the compression side's pair step
+// (kernels_fused2.hpp): the interpolants G(R) of
 // coarse plane R serve the even plane 2R directly and, r-lerped with G(R + 1), the odd plane
 // 2R + 1; G(R + 1) is then carried on. 4 coarse loads, 12 lerps and 7 coefficient loads per cell
 // and plane pair; no LDS, no barrier; a wave reads and writes whole 512-byte rows (64 cells of a
 // row: 64 consecutive 8-byte coefficients of each parity class in, 64 consecutive node pairs
 // out). Loads of the next pair are requested before the current one is finished.
 // Padded coordinates as everywhere (even size: real last node at P = n, ghost at P = n - 1, which
-// has no output). Per value the operations of k_level_restore_q in the same order.
+// has no output). Per value the operations of the element code (gpk_rev_elem, kernels_v1.hpp, on
+// the dequantized coefficient) in the same order.
 //
 // TODD (D = 4, an ODD slice of t): every node of the slice is a coefficient node:
 // value = coefficient + lerp_t(X_a, X_b), X = the 3-D interpolant from the coarse slice below /

@@ -273,7 +273,7 @@ k_tail(TailArgs<T> A) {
 // launch -- level-0 nodal values out of the head of the coefficient array, then per level the
 // dequantized coefficient field, the three mass/restriction sweeps, the three Thomas solves, the
 // subtraction of the correction from the coarse nodes and the node restore (kernels_v1.hpp
-// element code; k_level_loadvec_q / k_level_restore_q compute the same values). Without it
+// element code; k_level_loadvec_q / k_level_restore3_q compute the same values). Without it
 // every one of these levels costs four dependent launches of a few microseconds each.
 // ---------------------------------------------------------------------------------------
 template <typename T> struct HeadLevel {

@@ -425,9 +425,9 @@ def test_huffman_parameters_roundtrip(dict_size, block, where):
 
 
 def test_alternative_kernels_give_the_same_result():
-    """The developer switches select the previous / simpler kernels (one fine row per wave in the
-    node restore, every level with its own launches, the parallel decoder without rings, 16-bit
-    symbols on the decompression side): same container size, bit-identical reconstruction."""
+    """The developer switches select the previous / simpler kernels (every level with its own
+    launches, the parallel decoder without rings, 16-bit symbols on the decompression side, the
+    one-thread-per-element kernels): same container size, bit-identical reconstruction."""
     import os
     import subprocess
     import sys
@@ -443,7 +443,7 @@ def test_alternative_kernels_give_the_same_result():
         return line[-1]
 
     ref = run({})
-    assert run({"MGH_RESTORE_ROWS": "1", "MGH_NO_RECOMPOSE_HEAD": "1", "MGH_HUFF_PAR_DECODE": "1"}) == ref
+    assert run({"MGH_NO_RECOMPOSE_HEAD": "1", "MGH_HUFF_PAR_DECODE": "1"}) == ref
     assert run({"MGH_SYM16_DECODE": "1", "MGH_HUFF_SERIAL_DECODE": "1"}) == ref
     # int64 between decoder and dequantizer / 16-bit symbols on every level (not only the finest)
     assert run({"MGH_SYM16_DECODE": "0"}) == ref
@@ -455,10 +455,10 @@ def test_alternative_kernels_give_the_same_result():
     assert run({"MGH_FUSED_WIDE": "0", "MGH_FUSED4": "0", "MGH_IPK_W": "32"}) == ref
     # round 3: no box kernel / box kernel on every level, tail kernel without the solves of the
     # level above it, other residency plans of the streaming Thomas solves
-    assert run({"MGH_BOX": "0", "MGH_TAIL_SOLVES": "0", "MGH_RESTORE_V": "2", "MGH_IPK_CONTIG": "2"}) == ref
+    assert run({"MGH_BOX": "0", "MGH_TAIL_SOLVES": "0", "MGH_IPK_CONTIG": "2"}) == ref
     assert run({"MGH_BOX": "3", "MGH_IPK_WPC": "16"}) == ref
     # round 6: tile placement and shapes, slice batching, chunked strided solves, the N-D row kernels
-    assert run({"MGH_FUSED_XCD": "2", "MGH_FUSED_TALL": "0", "MGH_SLICE_BATCH": "0"}) == ref
+    assert run({"MGH_FUSED_TALL": "0", "MGH_SLICE_BATCH": "0"}) == ref
     assert run({"MGH_IPK_SPEC_LONG": "0", "MGH_ND_ROWS": "0", "MGH_FUSED_XCD": "0"}) == ref
 
 
@@ -1134,15 +1134,13 @@ def test_synchronisation_points_behind_the_huffman_record(kind, n, chunk, monkey
     assert rec[:len(plain)] == plain
     # (MGH_HUFF_PAIR: records with the section go through k_decode_sync -- two codes per table slot
     # where they fit: 2 always, 1 for short codes only -- or, 0, through k_decode_ring's single-symbol steps)
-    # MGH_HUFF_LEAN=1: the writing pass without divergent control flow (k_decode_lean) instead of k_decode_ring's
-    for sync_decode, pair, lean in (("1", "2", "0"), ("1", "0", "1"), ("1", "0", "0"), ("1", "1", "0"), ("0", "1", "0")):
+    for sync_decode, pair in (("1", "2"), ("1", "0"), ("1", "1"), ("0", "1")):
         monkeypatch.setenv("MGH_HUFF_SYNC_DECODE", sync_decode)
         monkeypatch.setenv("MGH_HUFF_PAIR", pair)
-        monkeypatch.setenv("MGH_HUFF_LEAN", lean)
         for payload in (rec, plain, torch.frombuffer(bytearray(rec), dtype=torch.uint8).cuda(),
                         torch.frombuffer(bytearray(b"xyz" + rec), dtype=torch.uint8).cuda()[3:]):
             back, bi, bv = ctx.decompress(payload, n, hl.HUFFMAN)
-            assert np.array_equal(back.cpu().numpy(), q), (kind, sync_decode, pair, lean)
+            assert np.array_equal(back.cpu().numpy(), q), (kind, sync_decode, pair)
             assert np.array_equal(bi.cpu().numpy(), oi) and np.array_equal(bv.cpu().numpy(), ov)
     ctx.close()
 
