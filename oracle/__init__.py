@@ -30,6 +30,12 @@ def build(force=False):
     return _LIB_PATH
 
 
+def build_ref(verbose=True):
+    """oracle/_ref/libmgx_ref.so, the reference's own SERIAL path (oracle/build_ref.py)."""
+    from .build_ref import build_ref as _build_ref
+    return _build_ref(verbose=verbose)
+
+
 def lib():
     global _lib
     if _lib is None:
