@@ -123,6 +123,30 @@ inline compress_status_type decompress(const void *compressed_data, size_t compr
   return decompress(compressed_data, compressed_size, decompressed_data, HighLevelConfig(),
                     output_pre_allocated);
 }
+// EXTENSION (the reference's decompress has no level argument): the array at `level` of the
+// hierarchy (0 = coarsest), dense in the shape infer_level_shape gives; containers with one
+// subdomain only (mgh_decompress_level).
+inline compress_status_type decompress_level(const void *compressed_data, size_t compressed_size, int level,
+                                             void *&decompressed_data, HighLevelConfig config,
+                                             bool output_pre_allocated) {
+  const mgh_config c = detail::to_c(config);
+  return detail::status(mgh_decompress_level(compressed_data, compressed_size, level, &decompressed_data, &c,
+                                             output_pre_allocated ? 1 : 0));
+}
+// shape of `level` and l_target of the container's hierarchy; level < 0: only l_target (shape left
+// empty). The status tells a failure from that query.
+inline compress_status_type infer_level_shape(const void *compressed_data, size_t compressed_size, int level,
+                                              HighLevelConfig config, std::vector<SIZE> &shape, int &l_target) {
+  const mgh_config c = detail::to_c(config);
+  int D = 0, lt = 0;
+  uint64_t shp[MGH_MAX_DIM];
+  shape.clear();
+  const int rc = mgh_infer_level_shape(compressed_data, compressed_size, &c, level, &D, shp, &lt);
+  if (rc != MGH_SUCCESS) return detail::status(rc);
+  l_target = lt;
+  if (level >= 0) shape.assign(shp, shp + D);
+  return compress_status_type::Success;
+}
 inline compress_status_type decompress(const void *compressed_data, size_t compressed_size,
                                        void *&decompressed_data, std::vector<SIZE> &shape,
                                        data_type &dtype, HighLevelConfig config, bool output_pre_allocated) {

@@ -253,6 +253,17 @@ inline enum compress_status_type decompress(const void *compressed_data, size_t 
   return detail::status(mgh_decompress(compressed_data, compressed_size, &decompressed_data, &c,
                                        output_pre_allocated ? 1 : 0));
 }
+// EXTENSION (no counterpart in compress_x.hpp): the array at `level` of the hierarchy (0 = coarsest),
+// dense in the shape mgh_infer_level_shape gives; containers with one subdomain only.
+inline enum compress_status_type decompress_level(const void *compressed_data, size_t compressed_size, int level,
+                                                  void *&decompressed_data, Config config,
+                                                  bool output_pre_allocated) {
+  const compress_status_type ok = detail::check(config);
+  if (ok != compress_status_type::Success) return ok;
+  const mgh_config c = detail::to_c(config);
+  return detail::status(mgh_decompress_level(compressed_data, compressed_size, level, &decompressed_data, &c,
+                                             output_pre_allocated ? 1 : 0));
+}
 inline enum compress_status_type decompress(const void *compressed_data, size_t compressed_size,
                                             void *&decompressed_data, bool output_pre_allocated) {
   return decompress(compressed_data, compressed_size, decompressed_data, Config(), output_pre_allocated);

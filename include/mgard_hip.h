@@ -224,6 +224,41 @@ int mgh_dequantize_recompose(mgh_hierarchy *h, int64_t *d_quantized, int error_b
                              const int64_t *d_outlier_val, uint64_t outlier_count, void *d_data,
                              void *stream);
 
+/* ---- Reconstruction at a coarser level of the hierarchy (reduced resolution) ----------------
+ * EXTENSIONS of the compression-level interface: the reference has the operation one layer down,
+ * DataRefactor::Recompose(data, start_level, stop_level, queue)
+ * (include/mgard-x/DataRefactoring/DataRefactor.hpp:108-124; loop
+ * MultiDimension/DataRefactoring.hpp:233,274); these calls fix the range to 0 ... level.
+ * Levels are the hierarchy's: 0 = coarsest grid, mgh_l_target(h) = the full array. The result is
+ * what the recompose loop holds at the nodes of `level` after the passes l = 1 ... level and none
+ * above: the corrected nodal values of that level, written to d_out as a DENSE array of
+ * mgh_level_shape(h, level) (MGH_LD_OUT does not apply to these calls; MGH_LD_IN is honoured for
+ * d_coeff as mgh_recompose honours it). d_out must not alias the input.
+ * d_coeff / d_quantized / d_symbols are the FULL arrays the calls without a level take (full-array
+ * strides, outlier indices = positions in the full array). Only the corner box
+ * [0, m_0) x ... x [0, m_{D-1}), m = level_shape(level), is read, outliers outside it are ignored,
+ * and no work is done that scales with the full array. d_quantized is modified INSIDE the box only
+ * (outliers written back), so one buffer serves level 2, then 3, ... then the full call.
+ * The quantizers are those of the full hierarchy. level == l_target: the bits of the call without
+ * a level; level outside 0 ... l_target: MGH_ERR_INVALID_ARGUMENT, nothing launched. */
+int mgh_recompose_to_level(mgh_hierarchy *h, const void *d_coeff, int level, void *d_out, void *stream);
+int mgh_dequantize_recompose_to_level(mgh_hierarchy *h, int64_t *d_quantized, int error_bound_type,
+                                      double tol, double s, double norm, uint64_t dict_size,
+                                      int prep_huffman, const uint64_t *d_outlier_idx,
+                                      const int64_t *d_outlier_val, uint64_t outlier_count, int level,
+                                      void *d_out, void *stream);
+/* (where mgh_sym16_supported(h), like mgh_dequantize_recompose_sym16) */
+int mgh_dequantize_recompose_sym16_to_level(mgh_hierarchy *h, const uint16_t *d_symbols,
+                                            int error_bound_type, double tol, double s, double norm,
+                                            uint64_t dict_size, const uint64_t *d_outlier_idx,
+                                            const int64_t *d_outlier_val, uint64_t outlier_count,
+                                            int level, void *d_out, void *stream);
+/* HOST only: index in the finest grid of every node of `level` along `dim`, ascending
+ * (level_shape(level)[dim] entries; returns their number, or a negative status). The rule is the
+ * hierarchy's own coarsening, level by level: keep every second node and always the last one. With
+ * it a caller builds the coordinates of the coarse grid of a non-uniform array. */
+int mgh_level_nodes(const mgh_hierarchy *h, int level, int dim, uint64_t *h_idx_out, uint64_t cap);
+
 /* OutlierRestore (LinearQuantization.hpp:304-350) on its own: d_q[idx[i]] = val[i]; indices
  * outside [0, n) are ignored. */
 int mgh_outlier_restore(int64_t *d_q, uint64_t n, const uint64_t *d_outlier_idx,

@@ -206,6 +206,31 @@ public:
           "DequantizeRecompose");
   }
 
+  // Extensions (mgh_*_to_level; the reference has DataRefactor::Recompose(data, start_level,
+  // stop_level, queue), DataRefactor.hpp:108-124, and no level argument at this layer): the nodal
+  // values of `level` of the hierarchy (0 = coarsest, hierarchy.l_target() = full) as a DENSE array
+  // of hierarchy.level_shape(level) in `level_data`, which must not be the input.
+  void RecomposeToLevel(const T *coefficients, int level, T *level_data, void *queue = nullptr) {
+    check(mgh_recompose_to_level(hierarchy_->handle(), coefficients, level, level_data, queue),
+          "RecomposeToLevel");
+  }
+  void DequantizeRecomposeToLevel(T *level_data, int level, error_bound_type ebtype, T tol, T s, T norm,
+                                  SIZE outlier_count, void *queue = nullptr) {
+    check(mgh_dequantize_recompose_to_level(hierarchy_->handle(), quantized_, (int)ebtype, (double)tol,
+                                            (double)s, (double)norm, config_.huff_dict_size,
+                                            config_.prep_huffman ? 1 : 0, outlier_idx_, outliers_,
+                                            outlier_count, level, level_data, queue),
+          "DequantizeRecomposeToLevel");
+  }
+  void DequantizeRecomposeSym16ToLevel(T *level_data, int level, error_bound_type ebtype, T tol, T s, T norm,
+                                       const uint16_t *symbols, SIZE outlier_count, void *queue = nullptr) {
+    check(mgh_dequantize_recompose_sym16_to_level(hierarchy_->handle(), symbols, (int)ebtype, (double)tol,
+                                                  (double)s, (double)norm, config_.huff_dict_size,
+                                                  outlier_idx_, outliers_, outlier_count, level, level_data,
+                                                  queue),
+          "DequantizeRecomposeSym16ToLevel");
+  }
+
   // Extension (mgh_*_sym16): the same two calls with the quantized values as 16-bit dictionary
   // symbols in a caller-provided device buffer of hierarchy.total_num_elems() uint16_t
   // (prep_huffman semantics; only where SupportsSym16(), i.e. on the fused 3-D path).

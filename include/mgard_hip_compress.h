@@ -159,6 +159,35 @@ int mgh_infer_shape(const void *compressed_data, size_t compressed_size, int *D_
                     uint64_t *shape_out /* [MGH_MAX_DIM] */);
 int mgh_infer_data_type(const void *compressed_data, size_t compressed_size, int *dtype_out);
 
+/* ---- Reconstruction at a coarser level of the hierarchy (EXTENSIONS: the reference's public
+ * decompress has no level argument; its refactoring layer has DataRefactor::Recompose(data,
+ * start_level, stop_level, queue), DataRefactor.hpp:108-124) ------------------------------------
+ * Levels are the hierarchy's: 0 = coarsest grid, l_target = the full array. `config` carries
+ * max_larget_level as it does for mgh_decompress (the container does not record it; NULL =
+ * defaults). Containers with ONE subdomain only: a domain-decomposed container answers
+ * MGH_ERR_INVALID_ARGUMENT (every subdomain has its own hierarchy and l_target).
+ *
+ * mgh_infer_level_shape: shape of `level` and l_target of the container's hierarchy; level < 0:
+ * only l_target (D_out / shape_out untouched). mgh_infer_level_nodes: index in the finest grid of
+ * every node of `level` along `dim`, ascending (keep every second node and always the last one, per
+ * coarsening); returns their number, or l_target for level < 0, or a negative status. With it a
+ * caller picks the coordinates of the coarse grid of a non-uniform array. compressed_data: host or device
+ * like mgh_infer_shape; with a host buffer neither call needs a device.
+ *
+ * mgh_decompress_level: like mgh_decompress (same memory-space rules: host or device stream, output
+ * allocated in the stream's space unless pre-allocated), the output being the dense array of
+ * mgh_infer_level_shape(level): mgh_dequantize_recompose_to_level of the decoded integers.
+ * level == l_target returns the bytes of mgh_decompress. The lossless stage still decodes the whole
+ * record. A record that was stored RAW (the data itself, because the lossless stage did not shrink
+ * it) is returned as it is at l_target; below l_target it costs a full decomposition and
+ * quantization with the header's bound first, so that the level is the one a Huffman record gives. */
+int mgh_infer_level_shape(const void *compressed_data, size_t compressed_size, const mgh_config *config,
+                          int level, int *D_out, uint64_t *shape_out /* [MGH_MAX_DIM] */, int *l_target_out);
+int mgh_infer_level_nodes(const void *compressed_data, size_t compressed_size, const mgh_config *config,
+                          int level, int dim, uint64_t *h_idx_out, uint64_t cap);
+int mgh_decompress_level(const void *compressed_data, size_t compressed_size, int level,
+                         void **decompressed_data, const mgh_config *config, int output_pre_allocated);
+
 /* Stream contract of mgh_compress / mgh_decompress: the calls return when the result is
  * complete (they synchronise their own pipeline streams before returning). The pipeline streams
  * are created with default (blocking) flags like the reference's queues

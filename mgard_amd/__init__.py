@@ -29,6 +29,8 @@ SYMBOLS = [
     "mgh_profile_enable", "mgh_profile_filter", "mgh_profile_read", "mgh_stream_calibrate",
     "mgh_level_linearize", "mgh_outlier_restore", "mgh_norm_stream_begin", "mgh_norm_stream_add",
     "mgh_set_ld",
+    "mgh_recompose_to_level", "mgh_dequantize_recompose_to_level",
+    "mgh_dequantize_recompose_sym16_to_level", "mgh_level_nodes",
 ]
 
 
@@ -94,6 +96,12 @@ def load_library():
                                    C.c_int, C.c_int]
     L.mgh_outlier_restore.argtypes = [vp, u64, vp, vp, u64, vp]
     L.mgh_level_linearize.argtypes = [vp, vp, vp, C.c_int, vp, vp, u64, u64, vp]
+    L.mgh_recompose_to_level.argtypes = [vp, vp, C.c_int, vp, vp]
+    L.mgh_dequantize_recompose_to_level.argtypes = [vp, vp, C.c_int, C.c_double, C.c_double, C.c_double,
+                                                    u64, C.c_int, vp, vp, u64, C.c_int, vp, vp]
+    L.mgh_dequantize_recompose_sym16_to_level.argtypes = [vp, vp, C.c_int, C.c_double, C.c_double,
+                                                          C.c_double, u64, vp, vp, u64, C.c_int, vp, vp]
+    L.mgh_level_nodes.argtypes = [vp, C.c_int, C.c_int, u64p, u64]
     L.mgh_stream_calibrate.argtypes = [C.c_int, vp, vp, vp, u64, C.c_int, C.POINTER(C.c_double), vp]
     _lib = L
     return L
@@ -161,6 +169,13 @@ class Hierarchy:
         _check(load_library().mgh_level_shape(self._h, l, out))
         return tuple(int(x) for x in out)
 
+    def level_nodes(self, level, dim):
+        """mgh_level_nodes: index in the finest grid of every node of `level` along `dim`."""
+        n = self.shape[dim] if 0 <= dim < self.D else 1
+        out = (C.c_uint64 * n)()
+        k = _check(load_library().mgh_level_nodes(self._h, int(level), int(dim), out, n))
+        return np.array(out[:k], dtype=np.int64)
+
     def device_bytes(self):
         return int(load_library().mgh_device_bytes(self._h))
 
@@ -205,7 +220,26 @@ class Hierarchy:
         _check(load_library().mgh_decompose(self._h, self._chk(data), self._chk(out), _stream()))
         return out
 
-    def recompose(self, coeff, out=None):
+    def _level_out(self, level, out, device):
+        """The dense array of level_shape(level) the *_to_level calls write (LD_OUT does not apply)."""
+        import torch
+        if out is None:
+            shape = self.level_shape(level)  # (raises on a level outside 0 .. l_target)
+            return torch.empty(shape, dtype=self.torch_dtype, device=device)
+        assert out.is_cuda and out.is_contiguous() and out.dtype == self.torch_dtype, "bad tensor"
+        assert out.device.index == self.device
+        if 0 <= level <= self.l_target:
+            assert out.numel() == int(np.prod(self.level_shape(level))), "bad tensor"
+        return out
+
+    def recompose(self, coeff, out=None, level=None):
+        """level = None: the full array. Else mgh_recompose_to_level: the nodal values of that level
+        of the hierarchy (0 = coarsest), a dense array of level_shape(level)."""
+        if level is not None:
+            out = self._level_out(level, out, coeff.device)
+            _check(load_library().mgh_recompose_to_level(self._h, self._chk(coeff), int(level),
+                                                         C.c_void_p(out.data_ptr()), _stream()))
+            return out
         out = self._new_out(coeff.device) if out is None else out
         _check(load_library().mgh_recompose(self._h, self._chk(coeff), self._chk(out), _stream()))
         return out
@@ -333,10 +367,17 @@ class Hierarchy:
         return sym, idx[:k], val[:k], n, nout.value
 
     def dequantize_recompose_sym16(self, sym, ebtype, tol, s, norm, dict_size=8192, outlier_idx=None,
-                                   outlier_val=None, out=None):
+                                   outlier_val=None, out=None, level=None):
         import torch
-        out = self._new_out(sym.device) if out is None else out
         n = 0 if outlier_idx is None else int(outlier_idx.numel())
+        if level is not None:
+            out = self._level_out(level, out, sym.device)
+            _check(load_library().mgh_dequantize_recompose_sym16_to_level(
+                self._h, C.c_void_p(sym.data_ptr()), ebtype, tol, s, norm, dict_size,
+                C.c_void_p(outlier_idx.data_ptr() if n else 0), C.c_void_p(outlier_val.data_ptr() if n else 0),
+                n, int(level), C.c_void_p(out.data_ptr()), _stream()))
+            return out
+        out = self._new_out(sym.device) if out is None else out
         _check(load_library().mgh_dequantize_recompose_sym16(
             self._h, C.c_void_p(sym.data_ptr()), ebtype, tol, s, norm, dict_size,
             C.c_void_p(outlier_idx.data_ptr() if n else 0), C.c_void_p(outlier_val.data_ptr() if n else 0),
@@ -344,10 +385,18 @@ class Hierarchy:
         return out
 
     def dequantize_recompose(self, q, ebtype, tol, s, norm, dict_size=8192, prep_huffman=True,
-                             outlier_idx=None, outlier_val=None, out=None):
+                             outlier_idx=None, outlier_val=None, out=None, level=None):
         import torch
-        out = self._new_out(q.device) if out is None else out
         n = 0 if outlier_idx is None else int(outlier_idx.numel())
+        if level is not None:
+            out = self._level_out(level, out, q.device)
+            _check(load_library().mgh_dequantize_recompose_to_level(
+                self._h, self._chk(q, torch.int64), ebtype, tol, s, norm, dict_size, int(prep_huffman),
+                C.c_void_p(outlier_idx.data_ptr() if n else 0),
+                C.c_void_p(outlier_val.data_ptr() if n else 0), n, int(level),
+                C.c_void_p(out.data_ptr()), _stream()))
+            return out
+        out = self._new_out(q.device) if out is None else out
         _check(load_library().mgh_dequantize_recompose(
             self._h, self._chk(q, torch.int64), ebtype, tol, s, norm, dict_size, int(prep_huffman),
             C.c_void_p(outlier_idx.data_ptr() if n else 0),

@@ -34,6 +34,7 @@
 #include "kernels_recompose.hpp"
 #include "kernels_recompose2.hpp"
 #include "kernels_nd.hpp"
+#include "kernels_level.hpp"
 
 namespace {
 
@@ -189,6 +190,7 @@ template <typename T> struct DeviceState {
   };
   std::vector<NdLevel> nd;         // [l], l >= 1 (all D dims; used by the D > 3 path)
   T *nd_w = nullptr, *nd_a = nullptr, *nd_b = nullptr;  // N-D scratch (lazily allocated)
+  size_t nd_cap = 0;               // ... elements of each (a stop below the finest level needs that level's box only)
   // fused D = 4 path (lazily allocated): compact coarse arrays per level, per-slice load vectors
   // of the biggest level (padded slice positions), t-swept load vector / correction
   std::vector<T *> nodal4;
@@ -196,6 +198,9 @@ template <typename T> struct DeviceState {
   bool state4_ready = false;       // set only once every allocation of ensure_state4 succeeded
   std::vector<T *> nodal;          // [l] compact nodal buffers, l = 0..L-1
   T *t1 = nullptr, *t2 = nullptr, *t3 = nullptr;
+  int t12_level = 0;               // t1 / t2 hold the sweeps of levels up to this one (0: not allocated)
+  T *level_box = nullptr;          // compact coefficients of the corner box of a stop level (mgh_*_to_level; grown on demand)
+  size_t level_box_elems = 0;
   T *scratch_full = nullptr;       // lazily allocated full-size copy
   T *qz = nullptr;                 // 2*(L+1): quantizers, volumes
   unsigned long long *scalar = nullptr;  // 8-byte device scalar (norm / counters)
@@ -482,6 +487,7 @@ template <typename T> void destroy_state(mgh_hierarchy *h) {
     (void)hipFree(ds->oh_key);
     (void)hipFree(ds->oh_val);
     (void)hipFree(ds->qbox);
+    (void)hipFree(ds->level_box);
     (void)hipFree(ds->spec_y);
     (void)hipFree(ds->spec_a);
     (void)hipFree(ds->spec_b);
@@ -844,15 +850,33 @@ int ipk_fc_launch(mgh_hierarchy *h, const uint32_t *m, T *x, const T *tt_f, cons
 // CalcCorrection3D (Correction/CalcCorrection3D.hpp:26-185) + AddND/SubtractND.
 template <typename T>
 int correction(mgh_hierarchy *h, int l, const T *coef, size_t cI, size_t cJ, T *target, int sign,
-               hipStream_t s) {
+               hipStream_t s, int top_level = -1) {
   auto *ds = DS<T>(h);
   const LevelTables<T> &t = ds->lt[l];
   const Box3 &b = t.box;
   const dim3 blk(64, 4, 1);
-  if (!ds->t1) {
-    const Box3 &tb = ds->lt[h->L].box;
-    TRY(dev_alloc(h, &ds->t1, (size_t)tb.n[0] * tb.n[1] * tb.m[2]));
-    TRY(dev_alloc(h, &ds->t2, (size_t)tb.n[0] * tb.m[1] * tb.m[2]));
+  // (top_level: the last level this call's loop runs -- a stop below the finest level sizes the
+  // sweeps by its own box; -1: the finest)
+  const int tl = top_level < 0 ? h->L : top_level;
+  if (ds->t12_level < tl) {
+    if (ds->t12_level >= 1) {
+      const Box3 &ob = ds->lt[ds->t12_level].box;
+      dev_free(h, &ds->t1, (size_t)ob.n[0] * ob.n[1] * ob.m[2]);
+      dev_free(h, &ds->t2, (size_t)ob.n[0] * ob.m[1] * ob.m[2]);
+      ds->t12_level = 0;
+    }
+    // (growing frees buffers that earlier launches on the caller's stream may still read: safe
+    // because hipFree waits for the device; a failed attempt leaves nothing behind)
+    const Box3 &tb = ds->lt[tl].box;
+    const size_t c1 = (size_t)tb.n[0] * tb.n[1] * tb.m[2], c2 = (size_t)tb.n[0] * tb.m[1] * tb.m[2];
+    int rc = dev_alloc(h, &ds->t1, c1);
+    if (rc == MGH_SUCCESS) rc = dev_alloc(h, &ds->t2, c2);
+    if (rc != MGH_SUCCESS) {
+      dev_free(h, &ds->t1, c1);
+      dev_free(h, &ds->t2, c2);
+      return rc;
+    }
+    ds->t12_level = tl;
   }
   // LPK1 along f: (nr, nc, nf) -> (nr, nc, ff)
   TRY(launch(h, "lpk_f", s, [&] {
@@ -1445,17 +1469,32 @@ inline bool fusedc_ok(const mgh_hierarchy *h) { return fused_ok(h) || fused4_ok(
 
 
 // ---- N-D path (D = 4, 5): in place on `v` (full array, reordered as levels proceed) -------
-template <typename T> int nd_ensure(mgh_hierarchy *h) {
+// (count: elements of the array the level loop runs on -- the full one, or the dense box of a stop level)
+template <typename T> int nd_ensure(mgh_hierarchy *h, size_t count = 0) {
   auto *ds = DS<T>(h);
-  if (!ds->nd_w) {
-    TRY(dev_alloc(h, &ds->nd_w, (size_t)h->total));
-    TRY(dev_alloc(h, &ds->nd_a, (size_t)h->total));
-    TRY(dev_alloc(h, &ds->nd_b, (size_t)h->total));
+  if (!count) count = (size_t)h->total;
+  if (ds->nd_cap < count) {
+    dev_free(h, &ds->nd_w, ds->nd_cap);
+    dev_free(h, &ds->nd_a, ds->nd_cap);
+    dev_free(h, &ds->nd_b, ds->nd_cap);
+    ds->nd_cap = 0;
+    int rc = dev_alloc(h, &ds->nd_w, count);
+    if (rc == MGH_SUCCESS) rc = dev_alloc(h, &ds->nd_a, count);
+    if (rc == MGH_SUCCESS) rc = dev_alloc(h, &ds->nd_b, count);
+    if (rc != MGH_SUCCESS) {
+      dev_free(h, &ds->nd_w, count);
+      dev_free(h, &ds->nd_a, count);
+      dev_free(h, &ds->nd_b, count);
+      return rc;
+    }
+    ds->nd_cap = count;
   }
   return MGH_SUCCESS;
 }
 
-template <typename T> NdBox nd_box(mgh_hierarchy *h, int l) {
+// (array_level: the array the box lies in is the dense array of that level's shape -- the compact
+// corner box of a stop level; -1: the full array)
+template <typename T> NdBox nd_box(mgh_hierarchy *h, int l, int array_level = -1) {
   auto *hh = HH<T>(h);
   NdBox b{};
   b.D = h->D;
@@ -1464,7 +1503,7 @@ template <typename T> NdBox nd_box(mgh_hierarchy *h, int l) {
     b.n[d] = (uint32_t)hh->level_shape[l][d];
     b.m[d] = (uint32_t)hh->level_shape[l - 1][d];
     b.fs[d] = sacc;
-    sacc *= hh->shape[d];
+    sacc *= array_level < 0 ? hh->shape[d] : hh->level_shape[array_level][d];
   }
   return b;
 }
@@ -1709,11 +1748,17 @@ template <typename T> int decompose_nd(mgh_hierarchy *h, T *v, hipStream_t st, c
   return MGH_SUCCESS;
 }
 
-template <typename T> int recompose_nd(mgh_hierarchy *h, T *v, hipStream_t st) {
+// (stop >= 0: `v` is the dense corner box of level `stop`, and the loop ends there)
+template <typename T> int recompose_nd(mgh_hierarchy *h, T *v, hipStream_t st, int stop = -1) {
   auto *ds = DS<T>(h);
-  TRY(nd_ensure<T>(h));
-  for (int l = 1; l <= h->L; l++) {
-    const NdBox b = nd_box<T>(h, l);
+  size_t count = 0;
+  if (stop >= 0) {
+    count = 1;
+    for (int d = 0; d < h->D; d++) count *= HH<T>(h)->level_shape[stop][d];
+  }
+  TRY(nd_ensure<T>(h, count));
+  for (int l = 1; l <= (stop < 0 ? h->L : stop); l++) {
+    const NdBox b = nd_box<T>(h, l, stop);
     NdTables<T> tb{};
     uint64_t nn = 1, mm = 1;
     for (int d = 0; d < h->D; d++) {
@@ -1796,12 +1841,45 @@ int decompose_impl(mgh_hierarchy *h, const T *data, T *coeff, hipStream_t s) {
 
 template <typename T, typename QT, typename QTL = QT>
 int recompose_levels(mgh_hierarchy *h, RecomposeArgs<T> A, const std::vector<T> &level_qv, T *data,
-                     hipStream_t st, const RecomposeArgs<T> *AL = nullptr, int ntop = 1);
+                     hipStream_t st, const RecomposeArgs<T> *AL = nullptr, int ntop = 1, int stop = -1);
 
 template <typename T, typename QT, typename QTL = QT>
 int recompose_levels4(mgh_hierarchy *h, RecomposeArgs<T> A, const std::vector<T> &level_qv, T *data,
-                      hipStream_t st, const RecomposeArgs<T> *AL = nullptr, size_t A_sT = 0, int ntop = 1);
+                      hipStream_t st, const RecomposeArgs<T> *AL = nullptr, size_t A_sT = 0, int ntop = 1,
+                      int stop = -1);
 inline bool fused4_ok(const mgh_hierarchy *h);
+
+// The level loop of the one-thread-per-element kernels (D <= 3): coefficients C with strides
+// (cI, cJ, 1) in the 3-D view, levels 1 .. Ls. Ls == L: `data` has the full array's strides;
+// below (mgh_*_to_level) it is the dense array of level Ls.
+template <typename T>
+int recompose_v1_levels(mgh_hierarchy *h, const T *C, size_t cI, size_t cJ, T *data, int Ls, hipStream_t s) {
+  auto *ds = DS<T>(h);
+  const int L = h->L;
+  const dim3 blk(64, 4, 1);
+  {
+    const Box3 &b = ds->lt[1].box;
+    TRY(launch(h, "copy_box", s, [&] {
+      k_copy_box<T><<<grid3(b.m[0], b.m[1], b.m[2], blk), blk, 0, s>>>(
+          b.m[0], b.m[1], b.m[2], C, cI, cJ, Ls == 0 ? data : ds->nodal[0], (size_t)b.m[1] * b.m[2],
+          (size_t)b.m[2]);
+    }));
+  }
+  for (int l = 1; l <= Ls; l++) {
+    const LevelTables<T> &t = ds->lt[l];
+    const Box3 &b = t.box;
+    T *coarse = ds->nodal[l - 1];
+    TRY(correction<T>(h, l, C, cI, cJ, coarse, -1, s, Ls));
+    T *out = (l == Ls) ? data : ds->nodal[l];
+    const size_t oJ = (l == L) ? ds->full_J : b.n[2];
+    const size_t oI = (l == L) ? ds->full_I : (size_t)b.n[1] * b.n[2];
+    TRY(launch(h, "gpk_rev", s, [&] {
+      k_gpk_rev<T><<<grid3(b.n[0], b.n[1], b.n[2], blk), blk, 0, s>>>(
+          b, coarse, C, cI, cJ, out, oI, oJ, t.ratio[0], t.ratio[1], t.ratio[2]);
+    }));
+  }
+  return MGH_SUCCESS;
+}
 
 template <typename T>
 int recompose_impl(mgh_hierarchy *h, const T *coeff, T *data, hipStream_t s) {
@@ -1844,30 +1922,36 @@ int recompose_impl(mgh_hierarchy *h, const T *coeff, T *data, hipStream_t s) {
     A.dJ = fJ;
     return recompose_levels<T, T>(h, A, std::vector<T>(L + 1, (T)1), data, s);
   }
-  const dim3 blk(64, 4, 1);
-  {
-    const Box3 &b = ds->lt[1].box;
-    TRY(launch(h, "copy_box", s, [&] {
-      k_copy_box<T><<<grid3(b.m[0], b.m[1], b.m[2], blk), blk, 0, s>>>(
-          b.m[0], b.m[1], b.m[2], C, fI, fJ, ds->nodal[0], (size_t)b.m[1] * b.m[2], (size_t)b.m[2]);
-    }));
-  }
-  for (int l = 1; l <= L; l++) {
-    const LevelTables<T> &t = ds->lt[l];
-    const Box3 &b = t.box;
-    T *coarse = ds->nodal[l - 1];
-    TRY(correction<T>(h, l, C, fI, fJ, coarse, -1, s));
-    T *out = (l == L) ? data : ds->nodal[l];
-    const size_t oJ = (l == L) ? fJ : b.n[2];
-    const size_t oI = (l == L) ? fI : (size_t)b.n[1] * b.n[2];
-    TRY(launch(h, "gpk_rev", s, [&] {
-      k_gpk_rev<T><<<grid3(b.n[0], b.n[1], b.n[2], blk), blk, 0, s>>>(
-          b, coarse, C, fI, fJ, out, oI, oJ, t.ratio[0], t.ratio[1], t.ratio[2]);
-    }));
-  }
-  return MGH_SUCCESS;
+  return recompose_v1_levels<T>(h, C, fI, fJ, data, L, s);
 }
 
+
+// ---- reconstruction at a coarser level (mgh_*_to_level) -----------------------------------------
+// The corner box of `level` in the full array: extents, and the element strides of the source --
+// the caller's pitched coefficients (mgh_set_ld(MGH_LD_IN)) where `pitched_in`, else the dense array.
+template <typename T> LevelBox level_box_of(const mgh_hierarchy *h, int level, bool pitched_in) {
+  auto *hh = HH<T>(h);
+  LevelBox b{};
+  b.D = h->D;
+  uint64_t sacc = 1;
+  for (int d = h->D - 1; d >= 0; d--) {
+    b.m[d] = (uint32_t)hh->level_shape[level][d];
+    b.n[d] = (uint32_t)hh->shape[d];
+    b.ss[d] = sacc;
+    sacc *= (pitched_in && h->has_ld[0] && d >= 1) ? h->ld[0][d] : hh->shape[d];
+  }
+  return b;
+}
+inline uint64_t level_box_rows(const LevelBox &b) {
+  uint64_t rows = 1;
+  for (int d = 0; d < b.D - 1; d++) rows *= b.m[d];
+  return rows;
+}
+// (one wave per piece of a row, four waves a workgroup: kernels_level.hpp)
+inline unsigned level_box_grid(const LevelBox &b) {
+  const uint64_t units = level_box_rows(b) * ((b.m[b.D - 1] + kLevelBoxPiece - 1) / kLevelBoxPiece);
+  return (unsigned)std::min<uint64_t>((units + 3) / 4, 256 * 32);
+}
 
 // Fused decompression: outlier restore, then per level (coarse to fine) the load vector
 // straight from the quantized coefficients, three Thomas solves subtracting the correction
@@ -1936,17 +2020,20 @@ int launch_loadvec(mgh_hierarchy *h, const RecomposeArgs<T> &A, const Box3 &b, h
 // QTL / AL: coefficient source of the `ntop` FINEST levels when it differs from that of the levels
 // below (16-bit symbols for the finest levels, int64 of the coarse corner box for the rest:
 // dequantize_recompose_fused16); AL == nullptr: one source for all levels.
+// stop >= 0 (mgh_*_to_level): the loop ends at that level and `data` is the DENSE array of its
+// shape -- the strides of the compact nodal buffer it stands in for.
 template <typename T, typename QT, typename QTL>
 int recompose_levels(mgh_hierarchy *h, RecomposeArgs<T> A, const std::vector<T> &level_qv, T *data,
-                     hipStream_t st, const RecomposeArgs<T> *AL, int ntop) {
+                     hipStream_t st, const RecomposeArgs<T> *AL, int ntop, int stop) {
   auto *ds = DS<T>(h);
   const int L = h->L;
+  const int Ls = stop < 0 ? L : stop;  // the last level run
   // levels 1 .. l_head run inside ONE single-workgroup kernel (their working set fits in LDS);
   // MGH_NO_RECOMPOSE_HEAD=1: every level with its own launches (cross-check)
   const bool no_head = h->no_head;
   int l_head = 0;
   if (!no_head) {
-    for (int l = 1; l <= std::min(AL ? L - ntop : L, kTailMaxLevels); l++) {
+    for (int l = 1; l <= std::min(std::min(AL ? L - ntop : L, Ls), kTailMaxLevels); l++) {
       if ((head_lds_elems(ds->lt[l].box) + ds->lt_end[l]) * sizeof(T) > 150 * 1024) break;
       l_head = l;
     }
@@ -1968,7 +2055,7 @@ int recompose_levels(mgh_hierarchy *h, RecomposeArgs<T> A, const std::vector<T> 
     HA.qv0 = level_qv[0];
     HA.in = A;
     const Box3 &bl = ds->lt[l_head].box;
-    HA.out = (l_head == L) ? data : ds->nodal[l_head];
+    HA.out = (l_head == Ls) ? data : ds->nodal[l_head];
     HA.oJ = (l_head == L) ? (ds->dst_J ? ds->dst_J : ds->full_J) : bl.n[2];
     HA.oI = (l_head == L) ? (ds->dst_I ? ds->dst_I : ds->full_I) : (size_t)bl.n[1] * bl.n[2];
     HA.tab_base = ds->tables;
@@ -1983,10 +2070,10 @@ int recompose_levels(mgh_hierarchy *h, RecomposeArgs<T> A, const std::vector<T> 
     TRY(launch(h, "head_in", st, [&] {
       const size_t tot = (size_t)b.m[0] * b.m[1] * b.m[2];
       k_head_in_q<T, QT><<<(unsigned)std::min<size_t>((tot + 255) / 256, 1024), 256, 0, st>>>(
-          (int)b.m[0], (int)b.m[1], (int)b.m[2], A, ds->nodal[0]);
+          (int)b.m[0], (int)b.m[1], (int)b.m[2], A, Ls == 0 ? data : ds->nodal[0]);
     }));
   }
-  for (int l = l_head + 1; l <= L; l++) {
+  for (int l = l_head + 1; l <= Ls; l++) {
     const LevelTables<T> &t = ds->lt[l];
     const Box3 &b = t.box;
     const bool top = AL && l > L - ntop;
@@ -2004,7 +2091,7 @@ int recompose_levels(mgh_hierarchy *h, RecomposeArgs<T> A, const std::vector<T> 
     else TRY((launch_loadvec<T, QT>(h, B, b, st)));
     TRY(ipk_fc_launch<T>(h, b.m, ds->t3, t.thomas[2], t.thomas[1], st));
     TRY(ipk_launch<T>(h, 0, b.m, ds->t3, t.thomas[0], ds->nodal[l - 1], -1, st));
-    B.fine = (l == L) ? data : ds->nodal[l];
+    B.fine = (l == Ls) ? data : ds->nodal[l];
     B.fJ = (l == L) ? (ds->dst_J ? ds->dst_J : ds->full_J) : b.n[2];
     B.fI = (l == L) ? (ds->dst_I ? ds->dst_I : ds->full_I) : (size_t)b.n[1] * b.n[2];
     if (top) TRY((launch_restore<T, QTL, false>(h, B, b, "restore_q", st)));
@@ -2021,10 +2108,11 @@ int recompose_levels(mgh_hierarchy *h, RecomposeArgs<T> A, const std::vector<T> 
 // recompose_levels (the finest level's source has the full array's strides).
 template <typename T, typename QT, typename QTL>
 int recompose_levels4(mgh_hierarchy *h, RecomposeArgs<T> A0, const std::vector<T> &level_qv, T *data,
-                      hipStream_t st, const RecomposeArgs<T> *AL, size_t A_sT, int ntop) {
+                      hipStream_t st, const RecomposeArgs<T> *AL, size_t A_sT, int ntop, int stop) {
   auto *ds = DS<T>(h);
   auto *hh = HH<T>(h);
   const int L = h->L;
+  const int Ls = stop < 0 ? L : stop;  // the last level run; below L, `data` is dense in its shape
   const auto &sh = hh->level_shape;
   const size_t full[4] = {(size_t)sh[L][1] * sh[L][2] * sh[L][3], (size_t)sh[L][2] * sh[L][3],
                           (size_t)sh[L][3], 1};
@@ -2040,10 +2128,10 @@ int recompose_levels4(mgh_hierarchy *h, RecomposeArgs<T> A0, const std::vector<T
     A0.qv = level_qv[0];
     TRY(launch(h, "head_in", st, [&] {
       k_head_in4_q<T, QT><<<(unsigned)std::min<size_t>((tot + 255) / 256, 1024), 256, 0, st>>>(
-          (int)M0[0], (int)M0[1], (int)M0[2], (int)M0[3], A0, A_sT, ds->nodal4[0]);
+          (int)M0[0], (int)M0[1], (int)M0[2], (int)M0[3], A0, A_sT, Ls == 0 ? data : ds->nodal4[0]);
     }));
   }
-  for (int l = 1; l <= L; l++) {
+  for (int l = 1; l <= Ls; l++) {
     const bool top = AL && l > L - ntop;
     RecomposeArgs<T> A = top ? *AL : A0;
     const size_t sT = top ? full[0] : A_sT;
@@ -2102,7 +2190,7 @@ int recompose_levels4(mgh_hierarchy *h, RecomposeArgs<T> A0, const std::vector<T
     TRY(ipk_launch<T>(h, 0, b.m, ds->corr4, ds->nd[l].thomas[1], nullptr, +1, st, (uint32_t)m_t, M));
     TRY((tsolve_apply<T>(h, ds->corr4, ds->nodal4[l - 1], M, m_t, Mc[1] * Mc[2], Mc[3], ds->nd[l].thomas[0], -1, st)));
     // ---- node restore, slice by slice
-    T *fine = (l == L) ? data : ds->nodal4[l];
+    T *fine = (l == Ls) ? data : ds->nodal4[l];
     const size_t fT = (l == L) ? full[0] : (size_t)N[1] * N[2] * N[3];
     A.fI = (l == L) ? full[1] : (size_t)N[2] * N[3];
     A.fJ = (l == L) ? full[2] : (size_t)N[3];
@@ -2151,11 +2239,17 @@ template <typename T>
 int dequantize_recompose_fused(mgh_hierarchy *h, int64_t *q, int ebtype, double tol, double s,
                                double norm, uint64_t dict_size, int prep_huffman,
                                const uint64_t *oidx, const int64_t *oval, uint64_t ocount, T *data,
-                               hipStream_t st) {
+                               hipStream_t st, int stop = -1) {
   auto *ds = DS<T>(h);
   auto *hh = HH<T>(h);
   const int L = h->L;
   if (prep_huffman && ocount) {
+    if (stop >= 0) {  // (only what the stop level reads: the rest of the caller's integers stays as it is)
+      const LevelBox lb = level_box_of<T>(h, stop, false);
+      TRY(launch(h, "outlier_restore", st, [&] {
+        k_outlier_restore_in_box<<<(unsigned)((ocount + 255) / 256), 256, 0, st>>>(q, lb, oidx, oval, ocount);
+      }));
+    } else
     TRY(launch(h, "outlier_restore", st, [&] {
       k_outlier_restore<<<(unsigned)((ocount + 255) / 256), 256, 0, st>>>(q, h->total, oidx, oval, ocount);
     }));
@@ -2170,8 +2264,8 @@ int dequantize_recompose_fused(mgh_hierarchy *h, int64_t *q, int ebtype, double 
   A.half = prep_huffman ? (int64_t)(dict_size / 2) : 0;
   std::vector<T> level_qv(L + 1);
   for (int l = 0; l <= L; l++) level_qv[l] = qz[l] * (calc_vol ? hh->level_volume(l, true) : (T)1);
-  if (h->D == 4) return recompose_levels4<T, int64_t>(h, A, level_qv, data, st);
-  return recompose_levels<T, int64_t>(h, A, level_qv, data, st);
+  if (h->D == 4) return recompose_levels4<T, int64_t>(h, A, level_qv, data, st, nullptr, 0, 1, stop);
+  return recompose_levels<T, int64_t>(h, A, level_qv, data, st, nullptr, 1, stop);
 }
 
 // The same from 16-bit dictionary symbols (what the Huffman decoder of the high-level path
@@ -2179,12 +2273,17 @@ int dequantize_recompose_fused(mgh_hierarchy *h, int64_t *q, int ebtype, double 
 template <typename T>
 int dequantize_recompose_fused16(mgh_hierarchy *h, const uint16_t *sym, int ebtype, double tol, double s,
                                  double norm, uint64_t dict_size, const uint64_t *oidx,
-                                 const int64_t *oval, uint64_t ocount, T *data, hipStream_t st) {
+                                 const int64_t *oval, uint64_t ocount, T *data, hipStream_t st, int stop = -1) {
   auto *ds = DS<T>(h);
   auto *hh = HH<T>(h);
   const int L = h->L;
   RecomposeArgs<T> A{};
-  if (ocount) {
+  const bool mixed = h->sym16_mixed && L >= 2 && h->total >= ((uint64_t)1 << 18);
+  const int ntop = L >= 4 ? 2 : 1;
+  // a stop at or below the levels that run on the widened box (mgh_*_to_level): the box of the stop
+  // level is all there is to read -- no table, no symbol of the finest levels
+  const bool box_only = mixed && stop >= 0 && stop <= L - ntop;
+  if (ocount && !box_only) {
     size_t slots = 16;
     while (slots < 2 * ocount) slots *= 2;
     if (slots > ((size_t)1 << 31)) return fail(MGH_ERR_INVALID_ARGUMENT, "too many outliers");
@@ -2224,9 +2323,8 @@ int dequantize_recompose_fused16(mgh_hierarchy *h, const uint16_t *sym, int ebty
   // written over them, and those levels run the int64 kernels on it. Two levels stay on symbols
   // where the hierarchy is deep enough: the box is then 1/64 (D = 3) of the array instead of 1/8
   // (512^3: widening the 257^3 box cost 51 us, almost all of it the 136 MB of int64 stores).
-  if (h->sym16_mixed && L >= 2 && h->total >= ((uint64_t)1 << 18)) {
-    const int ntop = L >= 4 ? 2 : 1;
-    const auto &Mc = hh->level_shape[L - ntop];
+  if (mixed) {
+    const auto &Mc = hh->level_shape[box_only ? stop : L - ntop];
     const auto &N = hh->level_shape[L];
     BoxMap bm{};
     for (int k = 0; k < 4; k++) bm.m[k] = bm.n[k] = 1;
@@ -2235,11 +2333,10 @@ int dequantize_recompose_fused16(mgh_hierarchy *h, const uint16_t *sym, int ebty
       bm.n[4 - h->D + d] = (uint32_t)N[d];
     }
     const size_t box = (size_t)bm.m[0] * bm.m[1] * bm.m[2] * bm.m[3];
-    if (box > ds->qbox_elems) {
-      (void)hipFree(ds->qbox);
-      ds->qbox = nullptr;
+    if (box > ds->qbox_elems) {  // (counted in mgh_device_bytes: a stop level's box is a fraction of the full call's)
+      dev_free(h, &ds->qbox, ds->qbox_elems);
       ds->qbox_elems = 0;
-      HIP_TRY(hipMalloc(&ds->qbox, box * sizeof(int64_t)));
+      TRY(dev_alloc(h, &ds->qbox, box));
       ds->qbox_elems = box;
     }
     const size_t rows = box / bm.m[3];
@@ -2256,12 +2353,17 @@ int dequantize_recompose_fused16(mgh_hierarchy *h, const uint16_t *sym, int ebty
     A64.dJ = bm.m[3];
     A64.dI = (size_t)bm.m[2] * bm.m[3];
     A64.half = A.half;
+    if (box_only) {
+      if (h->D == 4)
+        return recompose_levels4<T, int64_t>(h, A64, level_qv, data, st, nullptr, (size_t)bm.m[1] * bm.m[2] * bm.m[3], 1, stop);
+      return recompose_levels<T, int64_t>(h, A64, level_qv, data, st, nullptr, 1, stop);
+    }
     if (h->D == 4)
-      return recompose_levels4<T, int64_t, uint16_t>(h, A64, level_qv, data, st, &A, (size_t)bm.m[1] * bm.m[2] * bm.m[3], ntop);
-    return recompose_levels<T, int64_t, uint16_t>(h, A64, level_qv, data, st, &A, ntop);
+      return recompose_levels4<T, int64_t, uint16_t>(h, A64, level_qv, data, st, &A, (size_t)bm.m[1] * bm.m[2] * bm.m[3], ntop, stop);
+    return recompose_levels<T, int64_t, uint16_t>(h, A64, level_qv, data, st, &A, ntop, stop);
   }
-  if (h->D == 4) return recompose_levels4<T, uint16_t>(h, A, level_qv, data, st);
-  return recompose_levels<T, uint16_t>(h, A, level_qv, data, st);
+  if (h->D == 4) return recompose_levels4<T, uint16_t>(h, A, level_qv, data, st, nullptr, 0, 1, stop);
+  return recompose_levels<T, uint16_t>(h, A, level_qv, data, st, nullptr, 1, stop);
 }
 
 template <typename T>
@@ -2324,6 +2426,92 @@ int dequantize_impl(mgh_hierarchy *h, int64_t *q, int ebtype, double tol, double
                                           coeff);
   }));
   return MGH_SUCCESS;
+}
+
+// Compact buffer for the corner box of a stop level on the one-thread-per-element path, whose
+// node restore reads the coefficients while it writes the output.
+template <typename T> int ensure_level_box(mgh_hierarchy *h, size_t count) {
+  auto *ds = DS<T>(h);
+  if (count > ds->level_box_elems) {
+    dev_free(h, &ds->level_box, ds->level_box_elems);
+    ds->level_box_elems = 0;
+    TRY(dev_alloc(h, &ds->level_box, count));
+    ds->level_box_elems = count;
+  }
+  return MGH_SUCCESS;
+}
+
+// The level loop on a COMPACT corner box (dense array of level_shape(level)) for the shapes the
+// fused kernels do not take: `fill(dst)` puts the box's coefficients there. The generic N-D kernels
+// work in place, so the box is filled into the output itself.
+template <typename T, typename Fill>
+int recompose_box_to_level(mgh_hierarchy *h, int level, T *out, hipStream_t st, Fill &&fill) {
+  auto *ds = DS<T>(h);
+  auto *hh = HH<T>(h);
+  const int D = h->D;
+  if (D > 3 || h->force_nd) {
+    TRY(fill(out));
+    return level == 0 ? (int)MGH_SUCCESS : recompose_nd<T>(h, out, st, level);
+  }
+  const auto &m = hh->level_shape[level];
+  size_t count = 1;
+  for (int d = 0; d < D; d++) count *= m[d];
+  if (level == 0) return fill(out);
+  TRY(ensure_level_box<T>(h, count));
+  TRY(fill(ds->level_box));
+  const size_t cJ = m[D - 1], cI = (D >= 2 ? m[D - 2] : 1) * cJ;
+  return recompose_v1_levels<T>(h, ds->level_box, cI, cJ, out, level, st);
+}
+
+// mgh_recompose_to_level, level < l_target. The fused kernels read the corner box in place, with
+// the strides of the caller's array; the other paths gather it first (k_box_gather).
+template <typename T>
+int recompose_to_level_impl(mgh_hierarchy *h, const T *coeff, int level, T *out, hipStream_t st) {
+  const LevelBox lb = level_box_of<T>(h, level, true);
+  if (fused_ok(h) && !h->force_v1 && lb.ss[0] < ((uint64_t)1 << 30)) {
+    RecomposeArgs<T> A{};
+    A.coef = coeff;
+    A.dI = (size_t)lb.ss[0];
+    A.dJ = (size_t)lb.ss[1];
+    return recompose_levels<T, T>(h, A, std::vector<T>(h->L + 1, (T)1), out, st, nullptr, 1, level);
+  }
+  if (fused4_ok(h) && !h->force_v1) {
+    RecomposeArgs<T> A{};
+    A.coef = coeff;
+    A.dI = (size_t)lb.ss[1];
+    A.dJ = (size_t)lb.ss[2];
+    return recompose_levels4<T, T>(h, A, std::vector<T>(h->L + 1, (T)1), out, st, nullptr, (size_t)lb.ss[0], 1, level);
+  }
+  const uint64_t rows = level_box_rows(lb);
+  return recompose_box_to_level<T>(h, level, out, st, [&](T *dst) {
+    return launch(h, "box_gather", st, [&] {
+      k_box_gather<T><<<level_box_grid(lb), 256, 0, st>>>(lb, coeff, dst, rows);
+    });
+  });
+}
+
+// mgh_dequantize_recompose_to_level, level < l_target, on the shapes the fused kernels do not take:
+// outliers of the box written back, the box dequantized into a compact array, the level loop on it.
+template <typename T>
+int dequantize_recompose_box_to_level(mgh_hierarchy *h, int64_t *q, int ebtype, double tol, double s, double norm,
+                                      uint64_t dict_size, int prep_huffman, const uint64_t *oidx,
+                                      const int64_t *oval, uint64_t ocount, int level, T *out, hipStream_t st) {
+  auto *ds = DS<T>(h);
+  TRY(upload_quantizers<T>(h, ebtype, tol, s, norm, false, st));
+  const LevelBox lb = level_box_of<T>(h, level, false);
+  if (prep_huffman && ocount) {
+    TRY(launch(h, "outlier_restore", st, [&] {
+      k_outlier_restore_in_box<<<(unsigned)((ocount + 255) / 256), 256, 0, st>>>(q, lb, oidx, oval, ocount);
+    }));
+  }
+  const uint64_t rows = level_box_rows(lb);
+  return recompose_box_to_level<T>(h, level, out, st, [&](T *dst) {
+    return launch(h, "box_dequantize", st, [&] {
+      k_box_dequantize<T><<<level_box_grid(lb), 256, 0, st>>>(lb, ds->qmeta, q, ds->marks, ds->qz,
+                                                                 ds->qz + (h->L + 1), (int64_t)dict_size,
+                                                                 prep_huffman, dst, rows);
+    });
+  });
 }
 
 // ---- pitched caller arrays (mgh_set_ld; mgard_x::Array::ld, Array.hpp:70-84: hipMallocPitch pads the
@@ -3218,6 +3406,112 @@ int mgh_dequantize_recompose(mgh_hierarchy *h, int64_t *d_quantized, int ebtype,
                           d_outlier_idx, d_outlier_val, outlier_count, d_data, stream);
   if (rc != MGH_SUCCESS) return rc;
   return mgh_recompose(h, d_data, d_data, stream);
+}
+
+int mgh_level_nodes(const mgh_hierarchy *h, int level, int dim, uint64_t *h_idx_out, uint64_t cap) {
+  if (!h || !h_idx_out) return fail(MGH_ERR_INVALID_ARGUMENT, "null argument");
+  if (level < 0 || level > h->L) return fail(MGH_ERR_INVALID_ARGUMENT, "level outside 0 .. l_target");
+  if (dim < 0 || dim >= h->D) return fail(MGH_ERR_INVALID_ARGUMENT, "dim");
+  std::vector<uint64_t> idx;
+  level_nodes(h->shape[dim], h->L - level, idx);
+  if (idx.size() > cap) return fail(MGH_ERR_INVALID_ARGUMENT, "mgh_level_nodes: capacity too small");
+  std::copy(idx.begin(), idx.end(), h_idx_out);
+  return (int)idx.size();
+}
+
+namespace {
+// level == l_target is the existing call with a DENSE output: MGH_LD_OUT is set aside for its duration.
+// dense_in: MGH_LD_IN as well, for the calls that read no T array (integers and symbols are always dense;
+// on the staged path mgh_dequantize_recompose hands its own dense coefficients to mgh_recompose, which
+// would take them for the caller's pitched array).
+struct DenseOutScope {
+  mgh_hierarchy *h;
+  bool saved, saved_in;
+  explicit DenseOutScope(mgh_hierarchy *hh, bool dense_in = false)
+      : h(hh), saved(hh->has_ld[1]), saved_in(hh->has_ld[0]) {
+    h->has_ld[1] = false;
+    if (dense_in) h->has_ld[0] = false;
+  }
+  ~DenseOutScope() {
+    h->has_ld[1] = saved;
+    h->has_ld[0] = saved_in;
+  }
+  DenseOutScope(const DenseOutScope &) = delete;
+  DenseOutScope &operator=(const DenseOutScope &) = delete;
+};
+int level_arg(const mgh_hierarchy *h, int level) {
+  if (level < 0 || level > h->L) return fail(MGH_ERR_INVALID_ARGUMENT, "level outside 0 .. l_target");
+  return MGH_SUCCESS;
+}
+} // namespace
+
+int mgh_recompose_to_level(mgh_hierarchy *h, const void *d_coeff, int level, void *d_out, void *stream) {
+  if (!h || !d_out || !d_coeff) return fail(MGH_ERR_INVALID_ARGUMENT, "null argument");
+  if (d_out == d_coeff) return fail(MGH_ERR_INVALID_ARGUMENT, "mgh_recompose_to_level: d_out must not be d_coeff");
+  TRY(level_arg(h, level));
+  if (level == h->L) {
+    DenseOutScope dense(h);
+    return mgh_recompose(h, d_coeff, d_out, stream);
+  }
+  HIP_TRY(hipSetDevice(h->device));
+  return DISPATCH(h, recompose_to_level_impl<float>(h, (const float *)d_coeff, level, (float *)d_out, (hipStream_t)stream),
+                  recompose_to_level_impl<double>(h, (const double *)d_coeff, level, (double *)d_out, (hipStream_t)stream));
+}
+
+int mgh_dequantize_recompose_to_level(mgh_hierarchy *h, int64_t *d_quantized, int ebtype, double tol, double s,
+                                      double norm, uint64_t dict_size, int prep_huffman,
+                                      const uint64_t *d_outlier_idx, const int64_t *d_outlier_val,
+                                      uint64_t outlier_count, int level, void *d_out, void *stream) {
+  if (!h || !d_out || !d_quantized) return fail(MGH_ERR_INVALID_ARGUMENT, "null argument");
+  if (prep_huffman && outlier_count && (!d_outlier_idx || !d_outlier_val))
+    return fail(MGH_ERR_INVALID_ARGUMENT, "null outlier list");
+  TRY(level_arg(h, level));
+  if (level == h->L) {
+    DenseOutScope dense(h, true);
+    return mgh_dequantize_recompose(h, d_quantized, ebtype, tol, s, norm, dict_size, prep_huffman,
+                                            d_outlier_idx, d_outlier_val, outlier_count, d_out, stream);
+  }
+  HIP_TRY(hipSetDevice(h->device));
+  if (fusedc_ok(h) && !h->force_v1)
+    return DISPATCH(h,
+                    dequantize_recompose_fused<float>(h, d_quantized, ebtype, tol, s, norm, dict_size, prep_huffman,
+                                                      d_outlier_idx, d_outlier_val, outlier_count, (float *)d_out,
+                                                      (hipStream_t)stream, level),
+                    dequantize_recompose_fused<double>(h, d_quantized, ebtype, tol, s, norm, dict_size, prep_huffman,
+                                                       d_outlier_idx, d_outlier_val, outlier_count, (double *)d_out,
+                                                       (hipStream_t)stream, level));
+  return DISPATCH(h,
+                  dequantize_recompose_box_to_level<float>(h, d_quantized, ebtype, tol, s, norm, dict_size,
+                                                           prep_huffman, d_outlier_idx, d_outlier_val, outlier_count,
+                                                           level, (float *)d_out, (hipStream_t)stream),
+                  dequantize_recompose_box_to_level<double>(h, d_quantized, ebtype, tol, s, norm, dict_size,
+                                                            prep_huffman, d_outlier_idx, d_outlier_val, outlier_count,
+                                                            level, (double *)d_out, (hipStream_t)stream));
+}
+
+int mgh_dequantize_recompose_sym16_to_level(mgh_hierarchy *h, const uint16_t *d_symbols, int error_bound_type,
+                                            double tol, double s, double norm, uint64_t dict_size,
+                                            const uint64_t *d_outlier_idx, const int64_t *d_outlier_val,
+                                            uint64_t outlier_count, int level, void *d_out, void *stream) {
+  if (!h || !d_symbols || !d_out || (outlier_count && (!d_outlier_idx || !d_outlier_val)))
+    return fail(MGH_ERR_INVALID_ARGUMENT, "null argument");
+  if (dict_size == 0 || dict_size > 65536) return fail(MGH_ERR_INVALID_ARGUMENT, "dict_size must be in 1..65536");
+  TRY(level_arg(h, level));
+  if (!mgh_sym16_supported(h))
+    return fail(MGH_ERR_UNSUPPORTED_DIMENSION, "16-bit symbols: only on the fused 3-D / 4-D path");
+  if (level == h->L) {
+    DenseOutScope dense(h, true);
+    return mgh_dequantize_recompose_sym16(h, d_symbols, error_bound_type, tol, s, norm, dict_size,
+                                                  d_outlier_idx, d_outlier_val, outlier_count, d_out, stream);
+  }
+  HIP_TRY(hipSetDevice(h->device));
+  return DISPATCH(h,
+                  dequantize_recompose_fused16<float>(h, d_symbols, error_bound_type, tol, s, norm, dict_size,
+                                                      d_outlier_idx, d_outlier_val, outlier_count, (float *)d_out,
+                                                      (hipStream_t)stream, level),
+                  dequantize_recompose_fused16<double>(h, d_symbols, error_bound_type, tol, s, norm, dict_size,
+                                                       d_outlier_idx, d_outlier_val, outlier_count, (double *)d_out,
+                                                       (hipStream_t)stream, level));
 }
 
 #ifdef MGH_PHASE_TIMING

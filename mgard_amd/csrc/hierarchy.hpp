@@ -8,6 +8,7 @@
 // are bit-identical to what mgard_x::Hierarchy holds
 // (reference: include/mgard-x/Hierarchy/Hierarchy.hpp:23-190, 193-418, 689-708).
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <limits>
@@ -16,6 +17,35 @@
 namespace mgh {
 
 constexpr int kMaxDim = 5;
+
+// Indices in the finest grid of the nodes that are left of a dimension of n nodes after `steps`
+// coarsenings, ascending. One coarsening keeps every second node and always the last one
+// (n -> n/2 + 1; Hierarchy.hpp:712-757 builds its level shapes and coordinates by the same rule).
+inline void level_nodes(uint64_t n, int steps, std::vector<uint64_t> &idx) {
+  idx.resize(n);
+  for (uint64_t i = 0; i < n; i++) idx[i] = i;
+  for (int k = 0; k < steps; k++) {
+    const uint64_t cur = idx.size(), m = cur / 2 + 1;
+    for (uint64_t j = 0; j + 1 < m; j++) idx[j] = idx[2 * j];
+    idx[m - 1] = idx[cur - 1];
+    idx.resize(m);
+  }
+}
+
+// l_target of a shape: the levels its shortest coarsening sequence has (n -> n/2 + 1 down to 2), cut
+// by max_level -- what HostHierarchy::init computes, without the tables.
+inline int hierarchy_l_target(size_t D, const uint64_t *shape, uint64_t max_level) {
+  uint64_t lt = std::numeric_limits<uint64_t>::max();
+  for (size_t d = 0; d < D; d++) {
+    uint64_t n = shape[d], steps = 0;
+    while (n > 2) {
+      n = n / 2 + 1;
+      steps++;
+    }
+    lt = std::min(lt, steps);
+  }
+  return (int)std::min(lt, max_level);
+}
 
 template <typename T> struct DimLevel {
   uint64_t n = 1;        // nodes of this dim on this level

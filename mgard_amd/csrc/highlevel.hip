@@ -35,6 +35,7 @@
 #include "format.hpp"
 #include "huffman.hpp"
 #include "env.hpp"
+#include "hierarchy.hpp"
 
 extern "C" void mgh_set_last_error_(const char *msg);  // capi.hip
 
@@ -2534,9 +2535,33 @@ int read_header(const void *data, size_t size, fmt::Header &hd, size_t &meta_siz
   return MGH_SUCCESS;
 }
 
+// Level shapes of the array a container holds, from its header and the caller's configuration alone
+// (max_larget_level is not recorded: INTEGRATION.md). level < 0: only l_target.
+int header_level_shape(const fmt::Header &hd, const mgh_config &cfg, int level, int *l_target_out,
+                       std::vector<uint64_t> *shape_out) {
+  if (hd.shape.empty() || hd.shape.size() > MGH_MAX_DIM) return hl_fail(MGH_ERR_UNSUPPORTED_DIMENSION, "header: dimension");
+  if (hd.dd_method != fmt::DD_NOOP)
+    return hl_fail(MGH_ERR_INVALID_ARGUMENT,
+                   "reconstruction at a coarser level: the container is domain-decomposed (every subdomain has its "
+                   "own hierarchy and l_target); only containers with one subdomain are supported");
+  for (uint64_t e : hd.shape)
+    if (e < 3) return hl_fail(MGH_ERR_FORMAT, "header: extent below 3");
+  const int L = mgh::hierarchy_l_target(hd.shape.size(), hd.shape.data(), cfg.max_larget_level);
+  if (l_target_out) *l_target_out = L;
+  if (level < 0 && !shape_out) return MGH_SUCCESS;
+  if (level < 0 || level > L) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "level outside 0 .. l_target");
+  if (shape_out) {
+    shape_out->assign(hd.shape.begin(), hd.shape.end());
+    for (uint64_t &e : *shape_out)
+      for (int k = 0; k < L - level; k++) e = e / 2 + 1;
+  }
+  return MGH_SUCCESS;
+}
+
+// level >= 0: mgh_decompress_level -- the output is the dense array of that level of the hierarchy
 template <typename T>
 int decompress_impl(const fmt::Header &hd, size_t meta_size, const void *compressed, size_t csize_total,
-                    void **out, const mgh_config &cfg_in, bool prealloc) {
+                    void **out, const mgh_config &cfg_in, bool prealloc, int level = -1) {
   mgh_config cfg = cfg_in;
   HL_TRY(cache_prepare(cfg.dev_id));
   HL_TRY(trim_hierarchy_cache());
@@ -2544,6 +2569,12 @@ int decompress_impl(const fmt::Header &hd, size_t meta_size, const void *compres
   const size_t elem = sizeof(T);
   size_t total = 1;
   for (uint64_t e : hd.shape) total *= e;
+  if (level >= 0) {  // (refuses a decomposed container and a level outside the hierarchy)
+    std::vector<uint64_t> lshape;
+    HL_TRY(header_level_shape(hd, cfg, level, nullptr, &lshape));
+    total = 1;
+    for (uint64_t e : lshape) total *= e;
+  }
   Decomposer dd;
   HL_TRY(decomposer_from_header(hd, cfg, dd));
   for (uint64_t id = 0; id < dd.num; id++)
@@ -2594,13 +2625,14 @@ int decompress_impl(const fmt::Header &hd, size_t meta_size, const void *compres
     return rc;
   };
   const uint64_t max_elems = dd.max_subdomain_elems();
+  const uint64_t sub_elems = level >= 0 ? total : max_elems;  // (dense reconstruction of a subdomain)
   int rc;
   // device-resident output whose subdomains are contiguous slabs: reconstruct them in place
   const bool zero_copy = is_device_pointer(*out) && dd.all_contiguous();
   auto ensure_all = [&]() -> int {
     for (int l = 0; l < nlanes; l++) {
       Lane &L = g_cache.lane[l];
-      if (!zero_copy) HL_TRY(L.sub.ensure(max_elems * elem));
+      if (!zero_copy) HL_TRY(L.sub.ensure(sub_elems * elem));
       HL_TRY(L.q.ensure(max_elems * 8));
       if (hd.reorder) HL_TRY(L.q2.ensure(max_elems * 8));
     }
@@ -2673,9 +2705,10 @@ int decompress_impl(const fmt::Header &hd, size_t meta_size, const void *compres
     const char *rec = (const char *)compressed + byte_offset;
     void *sub = zero_copy ? (void *)((char *)*out + dd.linear_offset(id) * elem) : L.sub.p;
     byte_offset += csize;
-    if (!((double)(n * elem) / (double)csize > 1.0)) {  // GPUPipelines.hpp:414-417
+    const bool raw = !((double)(n * elem) / (double)csize > 1.0);  // GPUPipelines.hpp:414-417
+    if (raw) {
       if (csize != n * elem) return hl_fail(MGH_ERR_FORMAT, "raw subdomain record has the wrong size");
-      return copy_any(sub, rec, csize, st);
+      if (level < 0) return copy_any(sub, rec, csize, st);
     }
     const uint8_t *payload = (const uint8_t *)rec;
     uint64_t ocount = 0;
@@ -2683,6 +2716,19 @@ int decompress_impl(const fmt::Header &hd, size_t meta_size, const void *compres
     bool owned = false;
     HL_TRY(get_hierarchy(&h, &owned, dtype, sshape, cptr, dd.subdomain_offset(id), cfg, lane));
     if (owned) owned_h[lane] = h;
+    if (level >= 0 && level > mgh_l_target(h)) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "level outside 0 .. l_target");
+    if (raw) {
+      // a record that holds the data itself (the lossless stage did not pay): the finest level is the
+      // data; a coarser one is what a Huffman record of this subdomain would have given -- the
+      // integers of the header's bound, made here (no dictionary: prep_huffman = 0)
+      if (level == mgh_l_target(h)) return copy_any(sub, rec, csize, st);
+      HL_TRY(L.q2.ensure(n * elem));
+      HL_TRY(copy_any(L.q2.p, rec, csize, st));
+      HL_TRY(mgh_decompose_quantize(h, L.q2.p, local_eb, (double)local_tol, (double)s, (double)norm, nullptr,
+                                    hd.huff_dict_size, 0, (int64_t *)L.q.p, nullptr, nullptr, nullptr, 0, nullptr, st));
+      return mgh_dequantize_recompose_to_level(h, (int64_t *)L.q.p, local_eb, (double)local_tol, (double)s,
+                                               (double)norm, hd.huff_dict_size, 0, nullptr, nullptr, 0, level, sub, st);
+    }
     // 16-bit symbols between decoder and dequantizer (a quarter of the bytes the decoder writes and
     // the two passes over the finest level read). The symbol width is chosen PER LEVEL inside
     // mgh_dequantize_recompose_sym16: the finest level reads the symbols, the levels below --
@@ -2695,6 +2741,11 @@ int decompress_impl(const fmt::Header &hd, size_t meta_size, const void *compres
     bool sym16 = sym16_decode && !hd.reorder && mgh_sym16_supported(h) && hd.huff_dict_size <= 65536;
     HL_TRY(lossless_decompress(L.ll, payload, csize, lossless, (int64_t *)L.q.p, n, &ocount, st, &sym16,
                                /*sync_end=*/false));
+    if (sym16 && level >= 0)
+      return mgh_dequantize_recompose_sym16_to_level(h, (const uint16_t *)L.q.p, local_eb, (double)local_tol,
+                                                     (double)s, (double)norm, hd.huff_dict_size,
+                                                     (const uint64_t *)L.ll->oidx.p, (const int64_t *)L.ll->oval.p,
+                                                     ocount, level, sub, st);
     if (sym16)
       return mgh_dequantize_recompose_sym16(h, (const uint16_t *)L.q.p, local_eb, (double)local_tol, (double)s,
                                             (double)norm, hd.huff_dict_size, (const uint64_t *)L.ll->oidx.p,
@@ -2705,9 +2756,16 @@ int decompress_impl(const fmt::Header &hd, size_t meta_size, const void *compres
       HL_TRY(mgh_outlier_restore((int64_t *)L.q.p, n, (const uint64_t *)L.ll->oidx.p,
                                  (const int64_t *)L.ll->oval.p, ocount, st));
       HL_TRY(mgh_level_linearize(h, (const int64_t *)L.q.p, (int64_t *)L.q2.p, 1, nullptr, nullptr, 0, 0, st));
+      if (level >= 0)
+        return mgh_dequantize_recompose_to_level(h, (int64_t *)L.q2.p, local_eb, (double)local_tol, (double)s,
+                                                 (double)norm, hd.huff_dict_size, 1, nullptr, nullptr, 0, level, sub, st);
       return mgh_dequantize_recompose(h, (int64_t *)L.q2.p, local_eb, (double)local_tol, (double)s, (double)norm,
                                       hd.huff_dict_size, 1, nullptr, nullptr, 0, sub, st);
     }
+    if (level >= 0)
+      return mgh_dequantize_recompose_to_level(h, (int64_t *)L.q.p, local_eb, (double)local_tol, (double)s,
+                                               (double)norm, hd.huff_dict_size, 1, (const uint64_t *)L.ll->oidx.p,
+                                               (const int64_t *)L.ll->oval.p, ocount, level, sub, st);
     return mgh_dequantize_recompose(h, (int64_t *)L.q.p, local_eb, (double)local_tol, (double)s, (double)norm,
                                     hd.huff_dict_size, 1, (const uint64_t *)L.ll->oidx.p,
                                     (const int64_t *)L.ll->oval.p, ocount, sub, st);
@@ -2716,6 +2774,7 @@ int decompress_impl(const fmt::Header &hd, size_t meta_size, const void *compres
     if (zero_copy) return MGH_SUCCESS;
     pretouch.join();
     Lane &L = g_cache.lane[id % nlanes];
+    if (level >= 0) return copy_any(*out, L.sub.p, total * elem, L.st);  // (one subdomain, dense in the level's shape)
     return copy_subdomain(dd, id, elem, L.sub.p, nullptr, *out, false, L.st);
   };
   if ((rc = issue(0)) != MGH_SUCCESS) return cleanup(rc);
@@ -2802,7 +2861,14 @@ int mgh_compress(int D, int dtype, const uint64_t *shape, double tol, double s, 
 }
 
 static int decompress_entry(const void *compressed_data, size_t compressed_size, void **decompressed_data,
-                            const mgh_config *config, int output_pre_allocated, size_t expect_bytes, int expect_dtype);
+                            const mgh_config *config, int output_pre_allocated, size_t expect_bytes, int expect_dtype,
+                            int level = -1);
+
+int mgh_decompress_level(const void *compressed_data, size_t compressed_size, int level, void **decompressed_data,
+                         const mgh_config *config, int output_pre_allocated) {
+  if (level < 0) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "level outside 0 .. l_target");
+  return decompress_entry(compressed_data, compressed_size, decompressed_data, config, output_pre_allocated, 0, -1, level);
+}
 
 int mgh_decompress(const void *compressed_data, size_t compressed_size, void **decompressed_data,
                    const mgh_config *config, int output_pre_allocated) {
@@ -2820,7 +2886,8 @@ int mgh_decompress_into(const void *compressed_data, size_t compressed_size, voi
 // expect_dtype >= 0: the caller's buffer holds expect_bytes bytes of that type -- checked against the
 // header the call reads anyway, before anything is written (mgh_decompress_into)
 static int decompress_entry(const void *compressed_data, size_t compressed_size, void **decompressed_data,
-                            const mgh_config *config, int output_pre_allocated, size_t expect_bytes, int expect_dtype) {
+                            const mgh_config *config, int output_pre_allocated, size_t expect_bytes, int expect_dtype,
+                            int level) {
   if (!compressed_data || !decompressed_data) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "NULL argument");
   if (output_pre_allocated && !*decompressed_data) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "pre-allocated output is NULL");
   {
@@ -2853,9 +2920,9 @@ static int decompress_entry(const void *compressed_data, size_t compressed_size,
   try {
     if (hd.is_double)
       return decompress_impl<double>(hd, meta_size, compressed_data, compressed_size, decompressed_data,
-                                     *config, output_pre_allocated != 0);
+                                     *config, output_pre_allocated != 0, level);
     return decompress_impl<float>(hd, meta_size, compressed_data, compressed_size, decompressed_data,
-                                  *config, output_pre_allocated != 0);
+                                  *config, output_pre_allocated != 0, level);
   } catch (const std::exception &e) {
     return hl_fail(MGH_ERR_DEVICE, e.what());
   }
@@ -3751,6 +3818,51 @@ int mgh_infer_shape(const void *data, size_t size, int *D_out, uint64_t *shape_o
   *D_out = (int)hd.shape.size();
   for (size_t d = 0; d < hd.shape.size(); d++) shape_out[d] = hd.shape[d];
   return MGH_SUCCESS;
+}
+
+namespace {
+int infer_level(const void *data, size_t size, const mgh_config *config, int level, int *L_out,
+                std::vector<uint64_t> *shape_out, std::vector<uint64_t> *full_out) {
+  if (!data) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "NULL argument");
+  mgh_config def;
+  if (!config) {
+    mgh_config_default(&def);
+    config = &def;
+  }
+  fmt::Header hd;
+  size_t ms = 0;
+  HL_TRY(read_header(data, size, hd, ms));
+  if (full_out) full_out->assign(hd.shape.begin(), hd.shape.end());
+  return header_level_shape(hd, *config, level, L_out, shape_out);
+}
+} // namespace
+
+int mgh_infer_level_shape(const void *data, size_t size, const mgh_config *config, int level, int *D_out,
+                          uint64_t *shape_out, int *l_target_out) {
+  std::vector<uint64_t> shp;
+  int L = 0;
+  HL_TRY(infer_level(data, size, config, level, &L, level < 0 ? nullptr : &shp, nullptr));
+  if (l_target_out) *l_target_out = L;
+  if (level >= 0) {
+    if (D_out) *D_out = (int)shp.size();
+    if (shape_out) std::copy(shp.begin(), shp.end(), shape_out);
+  }
+  return MGH_SUCCESS;
+}
+
+int mgh_infer_level_nodes(const void *data, size_t size, const mgh_config *config, int level, int dim,
+                          uint64_t *h_idx_out, uint64_t cap) {
+  std::vector<uint64_t> full;
+  int L = 0;
+  HL_TRY(infer_level(data, size, config, -1, &L, nullptr, &full));
+  if (level < 0) return L;
+  if (level > L) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "level outside 0 .. l_target");
+  if (dim < 0 || dim >= (int)full.size() || !h_idx_out) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "dim / NULL argument");
+  std::vector<uint64_t> idx;
+  mgh::level_nodes(full[dim], L - level, idx);
+  if (idx.size() > cap) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "mgh_infer_level_nodes: capacity too small");
+  std::copy(idx.begin(), idx.end(), h_idx_out);
+  return (int)idx.size();
 }
 
 int mgh_infer_data_type(const void *data, size_t size, int *dtype_out) {

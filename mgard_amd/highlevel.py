@@ -24,6 +24,7 @@ HL_SYMBOLS = [
     "mgh_compress_multi", "mgh_decompress_multi", "mgh_pin_memory", "mgh_check_memory_pinned",
     "mgh_unpin_memory", "mgh_dist_use_library", "mgh_compress_dist", "mgh_decompress_dist",
     "mgh_decompress_into",
+    "mgh_infer_level_shape", "mgh_infer_level_nodes", "mgh_decompress_level",
 ]
 
 
@@ -103,6 +104,9 @@ def _hl():
                                C.POINTER(Config), C.c_int]
     L.mgh_decompress.argtypes = [vp, C.c_size_t, C.POINTER(vp), C.POINTER(Config), C.c_int]
     L.mgh_decompress_into.argtypes = [vp, C.c_size_t, vp, C.c_size_t, C.c_int, vp]
+    L.mgh_infer_level_shape.argtypes = [vp, C.c_size_t, vp, C.c_int, vp, vp, vp]
+    L.mgh_infer_level_nodes.argtypes = [vp, C.c_size_t, vp, C.c_int, C.c_int, vp, u64]
+    L.mgh_decompress_level.argtypes = [vp, C.c_size_t, C.c_int, C.POINTER(vp), vp, C.c_int]
     L.mgh_dist_use_library.argtypes = [C.c_char_p]
     L.mgh_compress_dist.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(u64), C.c_double,
                                     C.c_double, C.c_int, vp, C.POINTER(vp), C.POINTER(C.c_size_t), vp, vp, C.c_int]
@@ -274,17 +278,79 @@ def infer(buf):
     return tuple(int(shp[d]) for d in range(D.value)), dt.value
 
 
-def decompress(buf, config=None, out=None):
+def infer_level(buf, level, config=None):
+    """mgh_infer_level_shape: (shape of `level`, l_target) of the hierarchy of a compressed stream;
+    level = None or < 0: (None, l_target). `config` carries max_larget_level as for decompress."""
+    import torch
+    L = _hl()
+    cfg = config if config is not None else Config()
+    if isinstance(buf, torch.Tensor):
+        p, n = C.c_void_p(buf.data_ptr()), buf.numel()
+    else:
+        buf = np.ascontiguousarray(buf)
+        p, n = C.c_void_p(buf.ctypes.data), buf.size
+    level = -1 if level is None else int(level)
+    D, lt = C.c_int(), C.c_int()
+    shp = (C.c_uint64 * MAX_DIM)()
+    _check(L.mgh_infer_level_shape(p, n, C.byref(cfg), level, C.byref(D), shp, C.byref(lt)))
+    if level < 0:
+        return None, lt.value
+    return tuple(int(shp[d]) for d in range(D.value)), lt.value
+
+
+def infer_level_nodes(buf, level, dim, config=None):
+    """mgh_infer_level_nodes: index in the finest grid of every node of `level` along `dim`."""
+    import torch
+    L = _hl()
+    if level < 0:
+        raise ValueError("level must be >= 0 (infer_level(buf, None) gives l_target)")
+    cfg = config if config is not None else Config()
+    if isinstance(buf, torch.Tensor):
+        p, n = C.c_void_p(buf.data_ptr()), buf.numel()
+    else:
+        buf = np.ascontiguousarray(buf)
+        p, n = C.c_void_p(buf.ctypes.data), buf.size
+    shape, _ = infer(buf)
+    cap = shape[dim] if 0 <= dim < len(shape) else 1
+    out = (C.c_uint64 * cap)()
+    k = _check(L.mgh_infer_level_nodes(p, n, C.byref(cfg), int(level), int(dim), out, cap))
+    return np.array(out[:k], dtype=np.int64)
+
+
+def decompress(buf, config=None, out=None, level=None):
     """mgard_x::decompress. Returns a numpy array (host stream) or a cuda tensor (device stream).
     `out`: optional pre-allocated buffer -- a contiguous cuda tensor (device streams) or a
     C-contiguous numpy array (host streams). Its size and type are checked by the library against the
-    header it reads anyway (mgh_decompress_into: ValueError on a mismatch, nothing written)."""
+    header it reads anyway (mgh_decompress_into: ValueError on a mismatch, nothing written).
+    `level` (extension): mgh_decompress_level -- the array at that level of the hierarchy (0 =
+    coarsest, infer_level(buf, None)[1] = full), of shape infer_level(buf, level)[0]."""
     import torch
     L = _hl()
     cfg = config if config is not None else Config()
     on_dev = isinstance(buf, torch.Tensor) and buf.is_cuda
     if not on_dev:
         buf = np.ascontiguousarray(buf)
+    if level is not None:
+        shape, _ = infer_level(buf, int(level), cfg)
+        _, dt = infer(buf)
+        want = torch.float32 if dt == FLOAT else torch.float64
+        if on_dev:
+            if out is None:
+                out = torch.empty(shape, dtype=want, device=buf.device)
+            if not (isinstance(out, torch.Tensor) and out.is_cuda and out.is_contiguous() and out.dtype == want and
+                    out.device == buf.device and out.numel() == int(np.prod(shape))):
+                raise ValueError("`out` must be a contiguous cuda tensor of the level's shape and the stream's type")
+            p, n, optr = C.c_void_p(buf.data_ptr()), buf.numel(), C.c_void_p(out.data_ptr())
+        else:
+            npdt = np.float32 if dt == FLOAT else np.float64
+            if out is None:
+                out = np.empty(shape, dtype=npdt)
+            if not (isinstance(out, np.ndarray) and out.flags.c_contiguous and out.flags.writeable and
+                    out.dtype == npdt and out.size == int(np.prod(shape))):
+                raise ValueError("`out` must be a writeable C-contiguous numpy array of the level's shape and type")
+            p, n, optr = C.c_void_p(buf.ctypes.data), buf.size, C.c_void_p(out.ctypes.data)
+        _check(L.mgh_decompress_level(p, n, int(level), C.byref(optr), C.byref(cfg), 1))
+        return out
     if out is None:
         shape, dt = infer(buf)
         if on_dev:
