@@ -125,7 +125,6 @@ struct mgh_hierarchy {
   // mgh_set_ld: leading dimensions of the caller's T arrays, [MGH_LD_IN / MGH_LD_OUT][dim]
   uint64_t ld[2][MGH_MAX_DIM] = {};
   bool has_ld[2] = {false, false};
-  bool ld_guard = false;  // inside an entry point that has already dealt with the leading dimensions
 };
 
 namespace {
@@ -227,10 +226,6 @@ template <typename T> struct DeviceState {
   unsigned long long *outliers_seen = nullptr;
   QuantMeta qmeta;
   size_t full_I = 0, full_J = 0;   // strides of the full array in the 3-D view
-  // Strides of a PITCHED caller array for the one call that set them (mgh_set_ld; 0 = full_I /
-  // full_J): the finest level's input of the fused decomposition, the finest level's output of the
-  // fused recomposition. Every other path sees dense copies (ld_pack / ld_unpack).
-  size_t src_I = 0, src_J = 0, dst_I = 0, dst_J = 0;
   T *pack_in = nullptr, *pack_out = nullptr;  // dense copies of pitched arrays (lazily allocated)
 };
 
@@ -1060,19 +1055,81 @@ template <typename T> bool outlier_agg_now(mgh_hierarchy *h, const QuantParams<T
 
 __global__ void k_publish_count(const unsigned long long *count, unsigned long long *seen) { *seen = *count; }
 
+// The fused kernels index inside an r-plane with 32-bit offsets (and the emit pass with 32-bit
+// byte offsets): planes of 2^29 elements or more go through the one-thread-per-element kernels.
+inline bool fused_ok(const mgh_hierarchy *h) {
+  return h->D == 3 && h->L >= 1 && h->plane_elems < ((uint64_t)1 << 29);
+}
+// compression side: also D = 4 (decompose_fused4); arrays of < 2^32 elements per t-slice
+inline bool fused4_ok(const mgh_hierarchy *h) {
+  return h->D == 4 && h->fused4 && !h->force_nd && h->L >= 1 && h->plane_elems < ((uint64_t)1 << 29);
+}
+inline bool fusedc_ok(const mgh_hierarchy *h) { return fused_ok(h) || fused4_ok(h); }
+
+// ---- layouts of T arrays (mgh_set_ld; mgard_x::Array::ld, Array.hpp:70-84: hipMallocPitch pads the
+// fastest dimension; SubArray.hpp:136-139 carries one ld per dimension) ------------------------
+// Rows of the array (all dimensions but the fastest, right-aligned, leading 1s) and the element
+// strides of those dimensions.
+struct LdView {
+  uint32_t ext[MGH_MAX_DIM];
+  uint64_t stride[MGH_MAX_DIM];
+  uint64_t rows;
+};
+// How a T array of the full shape lies in memory. A layout belongs to an ARGUMENT: it is made where
+// the caller's pointer enters the library (caller_layout, in the extern "C" entry points) and passed
+// down beside the pointer; the buffers of the hierarchy are dense (dense_layout). A function without
+// a layout parameter takes dense arrays; one with it says which layouts it takes in place, and
+// ld_pack / LdOut make a dense copy for the rest.
+struct Layout {
+  LdView view{};         // for the row-wise kernels (k_ld_copy, k_norm_ld) and level_box_of
+  size_t I = 0, J = 0;   // strides of the two slower dimensions of the 3-D view (fused kernels)
+  bool pitched = false;  // false: dense
+  // pitched, and the fused 3-D kernels can read / write it in place: D = 3 on the fused path, planes
+  // addressable in 32 bits like the dense ones
+  bool native3 = false;
+};
+// ext[d]: elements between two steps of dimension d - 1 (the extent, or a leading dimension)
+inline Layout make_layout(const mgh_hierarchy *h, const uint64_t *ext, bool pitched) {
+  Layout lay;
+  const int D = h->D;
+  uint64_t st = 1, str[MGH_MAX_DIM] = {};
+  for (int d = D - 1; d >= 0; d--) {
+    str[d] = st;
+    st *= ext[d];
+  }
+  lay.view.rows = 1;
+  for (int k = 0; k < MGH_MAX_DIM; k++) {
+    const int d = k - (MGH_MAX_DIM - D);
+    lay.view.ext[k] = d >= 0 ? (uint32_t)h->shape[d] : 1u;
+    lay.view.stride[k] = d >= 0 ? str[d] : 0;
+    if (k < MGH_MAX_DIM - 1) lay.view.rows *= lay.view.ext[k];
+  }
+  lay.J = (size_t)ext[D - 1];
+  lay.I = (size_t)((D >= 2 ? ext[D - 2] : 1) * ext[D - 1]);
+  lay.pitched = pitched;
+  lay.native3 = pitched && fused_ok(h) && !h->force_v1 && lay.I < ((size_t)1 << 30);
+  return lay;
+}
+inline Layout dense_layout(const mgh_hierarchy *h) { return make_layout(h, h->shape, false); }
+// The layout mgh_set_ld gave the T arrays an entry point reads (MGH_LD_IN) or writes (MGH_LD_OUT).
+inline Layout caller_layout(const mgh_hierarchy *h, int which) {
+  return h->has_ld[which] ? make_layout(h, h->ld[which], true) : dense_layout(h);
+}
+
 template <typename T, int OUT, typename AfterFirst>
 int decompose_fused4(mgh_hierarchy *h, const T *data, T *coeff, const QuantParams<T> *qp,
                      hipStream_t s, AfterFirst &&after_first);
 
+// in: dense, or a pitched array the kernels of the finest level read in place (Layout::native3)
 template <typename T, int OUT, typename AfterFirst>
-int decompose_fused(mgh_hierarchy *h, const T *data, T *coeff, const QuantParams<T> *qp,
+int decompose_fused(mgh_hierarchy *h, const T *data, const Layout &in, T *coeff, const QuantParams<T> *qp,
                     hipStream_t s, AfterFirst &&after_first) {
   if (h->D == 4) return decompose_fused4<T, OUT>(h, data, coeff, qp, s, after_first);
   auto *ds = DS<T>(h);
   const int L = h->L;
   const size_t fI = ds->full_I, fJ = ds->full_J;
   const T *src = data;
-  size_t sI = ds->src_I ? ds->src_I : fI, sJ = ds->src_J ? ds->src_J : fJ;  // (pitched input: mgh_set_ld)
+  size_t sI = in.I, sJ = in.J;
 
   FusedArgs<T> A{};
   A.coef = coeff;
@@ -1451,22 +1508,10 @@ int decompose_fused4(mgh_hierarchy *h, const T *data, T *coeff, const QuantParam
 }
 
 template <typename T, int OUT>
-int decompose_fused(mgh_hierarchy *h, const T *data, T *coeff, const QuantParams<T> *qp,
+int decompose_fused(mgh_hierarchy *h, const T *data, const Layout &in, T *coeff, const QuantParams<T> *qp,
                     hipStream_t s) {
-  return decompose_fused<T, OUT>(h, data, coeff, qp, s, [] { return (int)MGH_SUCCESS; });
+  return decompose_fused<T, OUT>(h, data, in, coeff, qp, s, [] { return (int)MGH_SUCCESS; });
 }
-
-// The fused kernels index inside an r-plane with 32-bit offsets (and the emit pass with 32-bit
-// byte offsets): planes of 2^29 elements or more go through the one-thread-per-element kernels.
-inline bool fused_ok(const mgh_hierarchy *h) {
-  return h->D == 3 && h->L >= 1 && h->plane_elems < ((uint64_t)1 << 29);
-}
-// compression side: also D = 4 (decompose_fused4); arrays of < 2^32 elements per t-slice
-inline bool fused4_ok(const mgh_hierarchy *h) {
-  return h->D == 4 && h->fused4 && !h->force_nd && h->L >= 1 && h->plane_elems < ((uint64_t)1 << 29);
-}
-inline bool fusedc_ok(const mgh_hierarchy *h) { return fused_ok(h) || fused4_ok(h); }
-
 
 // ---- N-D path (D = 4, 5): in place on `v` (full array, reordered as levels proceed) -------
 // (count: elements of the array the level loop runs on -- the full one, or the dense box of a stop level)
@@ -1787,7 +1832,7 @@ template <typename T> int recompose_nd(mgh_hierarchy *h, T *v, hipStream_t st, i
 }
 
 template <typename T>
-int decompose_impl(mgh_hierarchy *h, const T *data, T *coeff, hipStream_t s) {
+int decompose_dense(mgh_hierarchy *h, const T *data, T *coeff, hipStream_t s) {
   auto *ds = DS<T>(h);
   if (fused4_ok(h) && !h->force_v1) {
     const T *src4 = data;
@@ -1796,7 +1841,7 @@ int decompose_impl(mgh_hierarchy *h, const T *data, T *coeff, hipStream_t s) {
       HIP_TRY(hipMemcpyAsync(ds->scratch_full, data, h->total * sizeof(T), hipMemcpyDeviceToDevice, s));
       src4 = ds->scratch_full;
     }
-    return decompose_fused<T, OUT_T>(h, src4, coeff, nullptr, s);
+    return decompose_fused<T, OUT_T>(h, src4, dense_layout(h), coeff, nullptr, s);
   }
   if (h->D > 3 || h->force_nd)
     return decompose_nd<T>(h, coeff, s, (const void *)data != (const void *)coeff ? data : nullptr);
@@ -1809,7 +1854,7 @@ int decompose_impl(mgh_hierarchy *h, const T *data, T *coeff, hipStream_t s) {
     HIP_TRY(hipMemcpyAsync(ds->scratch_full, data, h->total * sizeof(T), hipMemcpyDeviceToDevice, s));
     src = ds->scratch_full;
   }
-  if (fused_ok(h) && !h->force_v1) return decompose_fused<T, OUT_T>(h, src, coeff, nullptr, s);
+  if (fused_ok(h) && !h->force_v1) return decompose_fused<T, OUT_T>(h, src, dense_layout(h), coeff, nullptr, s);
   const dim3 blk(64, 4, 1);
   for (int l = L; l >= 1; l--) {
     const LevelTables<T> &t = ds->lt[l];
@@ -1840,14 +1885,13 @@ int decompose_impl(mgh_hierarchy *h, const T *data, T *coeff, hipStream_t s) {
 
 
 template <typename T, typename QT, typename QTL = QT>
-int recompose_levels(mgh_hierarchy *h, RecomposeArgs<T> A, const std::vector<T> &level_qv, T *data,
+int recompose_levels(mgh_hierarchy *h, RecomposeArgs<T> A, const std::vector<T> &level_qv, T *data, const Layout &out,
                      hipStream_t st, const RecomposeArgs<T> *AL = nullptr, int ntop = 1, int stop = -1);
 
 template <typename T, typename QT, typename QTL = QT>
 int recompose_levels4(mgh_hierarchy *h, RecomposeArgs<T> A, const std::vector<T> &level_qv, T *data,
                       hipStream_t st, const RecomposeArgs<T> *AL = nullptr, size_t A_sT = 0, int ntop = 1,
                       int stop = -1);
-inline bool fused4_ok(const mgh_hierarchy *h);
 
 // The level loop of the one-thread-per-element kernels (D <= 3): coefficients C with strides
 // (cI, cJ, 1) in the 3-D view, levels 1 .. Ls. Ls == L: `data` has the full array's strides;
@@ -1882,7 +1926,7 @@ int recompose_v1_levels(mgh_hierarchy *h, const T *C, size_t cI, size_t cJ, T *d
 }
 
 template <typename T>
-int recompose_impl(mgh_hierarchy *h, const T *coeff, T *data, hipStream_t s) {
+int recompose_dense(mgh_hierarchy *h, const T *coeff, T *data, hipStream_t s) {
   auto *ds = DS<T>(h);
   if (fused4_ok(h) && !h->force_v1) {
     // D = 4 on the slice-by-slice level loop, reading floating-point coefficients
@@ -1920,25 +1964,22 @@ int recompose_impl(mgh_hierarchy *h, const T *coeff, T *data, hipStream_t s) {
     A.coef = C;
     A.dI = fI;
     A.dJ = fJ;
-    return recompose_levels<T, T>(h, A, std::vector<T>(L + 1, (T)1), data, s);
+    return recompose_levels<T, T>(h, A, std::vector<T>(L + 1, (T)1), data, dense_layout(h), s);
   }
   return recompose_v1_levels<T>(h, C, fI, fJ, data, L, s);
 }
 
 
 // ---- reconstruction at a coarser level (mgh_*_to_level) -----------------------------------------
-// The corner box of `level` in the full array: extents, and the element strides of the source --
-// the caller's pitched coefficients (mgh_set_ld(MGH_LD_IN)) where `pitched_in`, else the dense array.
-template <typename T> LevelBox level_box_of(const mgh_hierarchy *h, int level, bool pitched_in) {
+// The corner box of `level` in the full array: extents, and the element strides of the source array.
+template <typename T> LevelBox level_box_of(const mgh_hierarchy *h, int level, const Layout &src) {
   auto *hh = HH<T>(h);
   LevelBox b{};
   b.D = h->D;
-  uint64_t sacc = 1;
-  for (int d = h->D - 1; d >= 0; d--) {
+  for (int d = 0; d < h->D; d++) {
     b.m[d] = (uint32_t)hh->level_shape[level][d];
     b.n[d] = (uint32_t)hh->shape[d];
-    b.ss[d] = sacc;
-    sacc *= (pitched_in && h->has_ld[0] && d >= 1) ? h->ld[0][d] : hh->shape[d];
+    b.ss[d] = src.view.stride[MGH_MAX_DIM - h->D + d];
   }
   return b;
 }
@@ -2020,10 +2061,12 @@ int launch_loadvec(mgh_hierarchy *h, const RecomposeArgs<T> &A, const Box3 &b, h
 // QTL / AL: coefficient source of the `ntop` FINEST levels when it differs from that of the levels
 // below (16-bit symbols for the finest levels, int64 of the coarse corner box for the rest:
 // dequantize_recompose_fused16); AL == nullptr: one source for all levels.
+// out: the layout of `data` as the full array -- dense, or a pitched array the finest level's
+// kernels write in place (Layout::native3).
 // stop >= 0 (mgh_*_to_level): the loop ends at that level and `data` is the DENSE array of its
 // shape -- the strides of the compact nodal buffer it stands in for.
 template <typename T, typename QT, typename QTL>
-int recompose_levels(mgh_hierarchy *h, RecomposeArgs<T> A, const std::vector<T> &level_qv, T *data,
+int recompose_levels(mgh_hierarchy *h, RecomposeArgs<T> A, const std::vector<T> &level_qv, T *data, const Layout &out,
                      hipStream_t st, const RecomposeArgs<T> *AL, int ntop, int stop) {
   auto *ds = DS<T>(h);
   const int L = h->L;
@@ -2056,8 +2099,8 @@ int recompose_levels(mgh_hierarchy *h, RecomposeArgs<T> A, const std::vector<T> 
     HA.in = A;
     const Box3 &bl = ds->lt[l_head].box;
     HA.out = (l_head == Ls) ? data : ds->nodal[l_head];
-    HA.oJ = (l_head == L) ? (ds->dst_J ? ds->dst_J : ds->full_J) : bl.n[2];
-    HA.oI = (l_head == L) ? (ds->dst_I ? ds->dst_I : ds->full_I) : (size_t)bl.n[1] * bl.n[2];
+    HA.oJ = (l_head == L) ? out.J : bl.n[2];
+    HA.oI = (l_head == L) ? out.I : (size_t)bl.n[1] * bl.n[2];
     HA.tab_base = ds->tables;
     HA.tab_count = (uint32_t)ds->lt_end[l_head];
     const size_t lds = (head_lds_elems(bl) + ds->lt_end[l_head]) * sizeof(T);
@@ -2092,8 +2135,8 @@ int recompose_levels(mgh_hierarchy *h, RecomposeArgs<T> A, const std::vector<T> 
     TRY(ipk_fc_launch<T>(h, b.m, ds->t3, t.thomas[2], t.thomas[1], st));
     TRY(ipk_launch<T>(h, 0, b.m, ds->t3, t.thomas[0], ds->nodal[l - 1], -1, st));
     B.fine = (l == Ls) ? data : ds->nodal[l];
-    B.fJ = (l == L) ? (ds->dst_J ? ds->dst_J : ds->full_J) : b.n[2];
-    B.fI = (l == L) ? (ds->dst_I ? ds->dst_I : ds->full_I) : (size_t)b.n[1] * b.n[2];
+    B.fJ = (l == L) ? out.J : b.n[2];
+    B.fI = (l == L) ? out.I : (size_t)b.n[1] * b.n[2];
     if (top) TRY((launch_restore<T, QTL, false>(h, B, b, "restore_q", st)));
     else TRY((launch_restore<T, QT, false>(h, B, b, "restore_q", st)));
   }
@@ -2239,13 +2282,13 @@ template <typename T>
 int dequantize_recompose_fused(mgh_hierarchy *h, int64_t *q, int ebtype, double tol, double s,
                                double norm, uint64_t dict_size, int prep_huffman,
                                const uint64_t *oidx, const int64_t *oval, uint64_t ocount, T *data,
-                               hipStream_t st, int stop = -1) {
+                               const Layout &out, hipStream_t st, int stop = -1) {
   auto *ds = DS<T>(h);
   auto *hh = HH<T>(h);
   const int L = h->L;
   if (prep_huffman && ocount) {
     if (stop >= 0) {  // (only what the stop level reads: the rest of the caller's integers stays as it is)
-      const LevelBox lb = level_box_of<T>(h, stop, false);
+      const LevelBox lb = level_box_of<T>(h, stop, dense_layout(h));
       TRY(launch(h, "outlier_restore", st, [&] {
         k_outlier_restore_in_box<<<(unsigned)((ocount + 255) / 256), 256, 0, st>>>(q, lb, oidx, oval, ocount);
       }));
@@ -2265,7 +2308,7 @@ int dequantize_recompose_fused(mgh_hierarchy *h, int64_t *q, int ebtype, double 
   std::vector<T> level_qv(L + 1);
   for (int l = 0; l <= L; l++) level_qv[l] = qz[l] * (calc_vol ? hh->level_volume(l, true) : (T)1);
   if (h->D == 4) return recompose_levels4<T, int64_t>(h, A, level_qv, data, st, nullptr, 0, 1, stop);
-  return recompose_levels<T, int64_t>(h, A, level_qv, data, st, nullptr, 1, stop);
+  return recompose_levels<T, int64_t>(h, A, level_qv, data, out, st, nullptr, 1, stop);
 }
 
 // The same from 16-bit dictionary symbols (what the Huffman decoder of the high-level path
@@ -2273,7 +2316,8 @@ int dequantize_recompose_fused(mgh_hierarchy *h, int64_t *q, int ebtype, double 
 template <typename T>
 int dequantize_recompose_fused16(mgh_hierarchy *h, const uint16_t *sym, int ebtype, double tol, double s,
                                  double norm, uint64_t dict_size, const uint64_t *oidx,
-                                 const int64_t *oval, uint64_t ocount, T *data, hipStream_t st, int stop = -1) {
+                                 const int64_t *oval, uint64_t ocount, T *data, const Layout &out, hipStream_t st,
+                                 int stop = -1) {
   auto *ds = DS<T>(h);
   auto *hh = HH<T>(h);
   const int L = h->L;
@@ -2356,14 +2400,14 @@ int dequantize_recompose_fused16(mgh_hierarchy *h, const uint16_t *sym, int ebty
     if (box_only) {
       if (h->D == 4)
         return recompose_levels4<T, int64_t>(h, A64, level_qv, data, st, nullptr, (size_t)bm.m[1] * bm.m[2] * bm.m[3], 1, stop);
-      return recompose_levels<T, int64_t>(h, A64, level_qv, data, st, nullptr, 1, stop);
+      return recompose_levels<T, int64_t>(h, A64, level_qv, data, out, st, nullptr, 1, stop);
     }
     if (h->D == 4)
       return recompose_levels4<T, int64_t, uint16_t>(h, A64, level_qv, data, st, &A, (size_t)bm.m[1] * bm.m[2] * bm.m[3], ntop, stop);
-    return recompose_levels<T, int64_t, uint16_t>(h, A64, level_qv, data, st, &A, ntop, stop);
+    return recompose_levels<T, int64_t, uint16_t>(h, A64, level_qv, data, out, st, &A, ntop, stop);
   }
   if (h->D == 4) return recompose_levels4<T, uint16_t>(h, A, level_qv, data, st, nullptr, 0, 1, stop);
-  return recompose_levels<T, uint16_t>(h, A, level_qv, data, st, nullptr, 1, stop);
+  return recompose_levels<T, uint16_t>(h, A, level_qv, data, out, st, nullptr, 1, stop);
 }
 
 template <typename T>
@@ -2400,15 +2444,7 @@ int quantize_launch(mgh_hierarchy *h, const T *coeff, uint64_t dict_size, int pr
 }
 
 template <typename T>
-int quantize_impl(mgh_hierarchy *h, const T *coeff, int ebtype, double tol, double s, double norm,
-                  uint64_t dict_size, int prep_huffman, int64_t *q, uint64_t *ocount,
-                  uint64_t *oidx, int64_t *oval, uint64_t ocap, hipStream_t st) {
-  TRY(upload_quantizers<T>(h, ebtype, tol, s, norm, true, st));
-  return quantize_launch<T>(h, coeff, dict_size, prep_huffman, q, ocount, oidx, oval, ocap, st);
-}
-
-template <typename T>
-int dequantize_impl(mgh_hierarchy *h, int64_t *q, int ebtype, double tol, double s, double norm,
+int dequantize_dense(mgh_hierarchy *h, int64_t *q, int ebtype, double tol, double s, double norm,
                     uint64_t dict_size, int prep_huffman, const uint64_t *oidx,
                     const int64_t *oval, uint64_t ocount, T *coeff, hipStream_t st) {
   auto *ds = DS<T>(h);
@@ -2464,16 +2500,16 @@ int recompose_box_to_level(mgh_hierarchy *h, int level, T *out, hipStream_t st, 
 }
 
 // mgh_recompose_to_level, level < l_target. The fused kernels read the corner box in place, with
-// the strides of the caller's array; the other paths gather it first (k_box_gather).
+// the strides of the caller's array (any layout); the other paths gather it first (k_box_gather).
 template <typename T>
-int recompose_to_level_impl(mgh_hierarchy *h, const T *coeff, int level, T *out, hipStream_t st) {
-  const LevelBox lb = level_box_of<T>(h, level, true);
+int recompose_to_level_impl(mgh_hierarchy *h, const T *coeff, const Layout &in, int level, T *out, hipStream_t st) {
+  const LevelBox lb = level_box_of<T>(h, level, in);
   if (fused_ok(h) && !h->force_v1 && lb.ss[0] < ((uint64_t)1 << 30)) {
     RecomposeArgs<T> A{};
     A.coef = coeff;
     A.dI = (size_t)lb.ss[0];
     A.dJ = (size_t)lb.ss[1];
-    return recompose_levels<T, T>(h, A, std::vector<T>(h->L + 1, (T)1), out, st, nullptr, 1, level);
+    return recompose_levels<T, T>(h, A, std::vector<T>(h->L + 1, (T)1), out, dense_layout(h), st, nullptr, 1, level);
   }
   if (fused4_ok(h) && !h->force_v1) {
     RecomposeArgs<T> A{};
@@ -2498,7 +2534,7 @@ int dequantize_recompose_box_to_level(mgh_hierarchy *h, int64_t *q, int ebtype, 
                                       const int64_t *oval, uint64_t ocount, int level, T *out, hipStream_t st) {
   auto *ds = DS<T>(h);
   TRY(upload_quantizers<T>(h, ebtype, tol, s, norm, false, st));
-  const LevelBox lb = level_box_of<T>(h, level, false);
+  const LevelBox lb = level_box_of<T>(h, level, dense_layout(h));
   if (prep_huffman && ocount) {
     TRY(launch(h, "outlier_restore", st, [&] {
       k_outlier_restore_in_box<<<(unsigned)((ocount + 255) / 256), 256, 0, st>>>(q, lb, oidx, oval, ocount);
@@ -2514,31 +2550,7 @@ int dequantize_recompose_box_to_level(mgh_hierarchy *h, int64_t *q, int ebtype, 
   });
 }
 
-// ---- pitched caller arrays (mgh_set_ld; mgard_x::Array::ld, Array.hpp:70-84: hipMallocPitch pads the
-// fastest dimension; SubArray.hpp:136-139 carries one ld per dimension) ------------------------
-// Rows of the array (all dimensions but the fastest, right-aligned, leading 1s) and the element
-// strides of those dimensions in the pitched array.
-struct LdView {
-  uint32_t ext[MGH_MAX_DIM];
-  uint64_t stride[MGH_MAX_DIM];
-  uint64_t rows;
-};
-inline LdView ld_view(const mgh_hierarchy *h, int which) {
-  LdView V{};
-  uint64_t st = 1, str[MGH_MAX_DIM] = {};
-  for (int d = h->D - 1; d >= 0; d--) {
-    str[d] = st;
-    st *= h->has_ld[which] ? h->ld[which][d] : h->shape[d];
-  }
-  V.rows = 1;
-  for (int k = 0; k < MGH_MAX_DIM; k++) {
-    const int d = k - (MGH_MAX_DIM - h->D);
-    V.ext[k] = d >= 0 ? (uint32_t)h->shape[d] : 1u;
-    V.stride[k] = d >= 0 ? str[d] : 0;
-    if (k < MGH_MAX_DIM - 1) V.rows *= V.ext[k];
-  }
-  return V;
-}
+// ---- kernels on pitched arrays (Layout::view) ----------------------------------------------------
 __device__ __forceinline__ uint64_t ld_row_offset(const LdView &V, uint64_t row) {
   uint64_t r = row, off = 0;
 #pragma unroll
@@ -2612,15 +2624,12 @@ int norm_reduce(mgh_hierarchy *h, const T *data, double s, unsigned long long *s
   return launch(h, "sqsum", st, [&] { k_sqsum<T><<<grid, 256, 0, st>>>(data, total, (double *)slot, n_cold); });
 }
 
-// Launch the norm reduction; the result stays in ds->scalar (absmax bits or double sum).
-template <typename T> int norm_launch(mgh_hierarchy *h, const T *data, double s, hipStream_t st) {
+// Launch the norm reduction (any layout: a pitched array row by row); the result stays in
+// ds->scalar (absmax bits or double sum).
+template <typename T> int norm_launch(mgh_hierarchy *h, const T *data, const Layout &in, double s, hipStream_t st) {
   auto *ds = DS<T>(h);
   HIP_TRY(hipMemsetAsync(ds->scalar, 0, 8, st));
-  if (h->has_ld[0] && !h->ld_guard) {
-    const LdView V = ld_view(h, 0);
-    return norm_reduce<T>(h, data, s, ds->scalar, &V, 0, st);
-  }
-  return norm_reduce<T>(h, data, s, ds->scalar, nullptr, 0, st);
+  return norm_reduce<T>(h, data, s, ds->scalar, in.pitched ? &in.view : nullptr, 0, st);
 }
 
 // Quantizer table on the device from a device-resident norm (no host round trip).
@@ -2658,11 +2667,11 @@ int make_qparams_launch(mgh_hierarchy *h, const T *d_norm, int ebtype, double to
 }
 
 template <typename T>
-int norm_impl(mgh_hierarchy *h, const T *data, double s, double *out, hipStream_t st) {
+int norm_impl(mgh_hierarchy *h, const T *data, const Layout &in, double s, double *out, hipStream_t st) {
   auto *ds = DS<T>(h);
   auto *hh = HH<T>(h);
   const size_t total = h->total;
-  TRY(norm_launch<T>(h, data, s, st));
+  TRY(norm_launch<T>(h, data, in, s, st));
   T norm;
   if ((T)s == std::numeric_limits<T>::infinity()) {
     unsigned long long bits = 0;
@@ -2711,10 +2720,84 @@ int64_t table_impl(const mgh_hierarchy *h, int kind, int level, int dim, void *o
   return (int64_t)v->size();
 }
 
+// Dense view of a pitched array for the paths that do not take strides. ld_pack: the input copied
+// into a dense buffer of the hierarchy (p then points there, and `lay` says so); LdOut: the kernels
+// write a dense buffer, finish() spreads it into the caller's pitched array. native_ok: the callee
+// runs the fused 3-D kernels, which take a Layout::native3 array as it is. Dense arrays pay nothing.
+template <typename T> int ld_pack(mgh_hierarchy *h, const T *&p, Layout &lay, bool native_ok, hipStream_t st) {
+  if (!lay.pitched || (native_ok && lay.native3)) return MGH_SUCCESS;
+  auto *ds = DS<T>(h);
+  if (!ds->pack_in) TRY(dev_alloc(h, &ds->pack_in, (size_t)h->total));
+  const LdView V = lay.view;
+  TRY(launch(h, "ld_pack", st, [&] { k_ld_copy<T><<<ld_grid(V), 256, 0, st>>>(ds->pack_in, const_cast<T *>(p), V, 1); }));
+  p = ds->pack_in;
+  lay = dense_layout(h);
+  return MGH_SUCCESS;
+}
+template <typename T> struct LdOut {
+  T *user = nullptr;
+  LdView view{};
+  int begin(mgh_hierarchy *h, T *&p, Layout &lay, bool native_ok) {  // (p == nullptr: no such argument)
+    if (!p || !lay.pitched || (native_ok && lay.native3)) return MGH_SUCCESS;
+    auto *ds = DS<T>(h);
+    if (!ds->pack_out) TRY(dev_alloc(h, &ds->pack_out, (size_t)h->total));
+    user = p;
+    view = lay.view;
+    p = ds->pack_out;
+    lay = dense_layout(h);
+    return MGH_SUCCESS;
+  }
+  int finish(mgh_hierarchy *h, hipStream_t st) {
+    if (!user) return MGH_SUCCESS;
+    auto *ds = DS<T>(h);
+    return launch(h, "ld_unpack", st, [&] { k_ld_copy<T><<<ld_grid(view), 256, 0, st>>>(ds->pack_out, user, view, 0); });
+  }
+};
+
+// ---- the stages on arrays of any layout ---------------------------------------------------------
 template <typename T>
-int fused_q_entry(mgh_hierarchy *h, const T *data, int ebtype, double tol, double s, double norm,
+int decompose_impl(mgh_hierarchy *h, const T *data, Layout in, T *coeff, Layout out, hipStream_t st) {
+  TRY(ld_pack<T>(h, data, in, false, st));
+  LdOut<T> o;
+  TRY(o.begin(h, coeff, out, false));
+  TRY(decompose_dense<T>(h, data, coeff, st));
+  return o.finish(h, st);
+}
+
+template <typename T>
+int recompose_impl(mgh_hierarchy *h, const T *coeff, Layout in, T *data, Layout out, hipStream_t st) {
+  TRY(ld_pack<T>(h, coeff, in, false, st));
+  LdOut<T> o;
+  TRY(o.begin(h, data, out, false));
+  TRY(recompose_dense<T>(h, coeff, data, st));
+  return o.finish(h, st);
+}
+
+// (the integers are always dense)
+template <typename T>
+int quantize_impl(mgh_hierarchy *h, const T *coeff, Layout in, int ebtype, double tol, double s, double norm,
                   uint64_t dict_size, int prep_huffman, int64_t *q, uint64_t *ocount,
                   uint64_t *oidx, int64_t *oval, uint64_t ocap, hipStream_t st) {
+  TRY(ld_pack<T>(h, coeff, in, false, st));
+  TRY(upload_quantizers<T>(h, ebtype, tol, s, norm, true, st));
+  return quantize_launch<T>(h, coeff, dict_size, prep_huffman, q, ocount, oidx, oval, ocap, st);
+}
+
+template <typename T>
+int dequantize_impl(mgh_hierarchy *h, int64_t *q, int ebtype, double tol, double s, double norm,
+                    uint64_t dict_size, int prep_huffman, const uint64_t *oidx,
+                    const int64_t *oval, uint64_t ocount, T *coeff, Layout out, hipStream_t st) {
+  LdOut<T> o;
+  TRY(o.begin(h, coeff, out, false));
+  TRY(dequantize_dense<T>(h, q, ebtype, tol, s, norm, dict_size, prep_huffman, oidx, oval, ocount, coeff, st));
+  return o.finish(h, st);
+}
+
+template <typename T>
+int fused_q_entry(mgh_hierarchy *h, const T *data, Layout in, int ebtype, double tol, double s, double norm,
+                  uint64_t dict_size, int prep_huffman, int64_t *q, uint64_t *ocount,
+                  uint64_t *oidx, int64_t *oval, uint64_t ocap, hipStream_t st) {
+  TRY(ld_pack<T>(h, data, in, true, st));
   QuantParams<T> qp = make_quant_params<T>(h, ebtype, tol, s, norm, true);
   qp.dict_size = (int64_t)dict_size;
   qp.prep_huffman = prep_huffman;
@@ -2723,18 +2806,19 @@ int fused_q_entry(mgh_hierarchy *h, const T *data, int ebtype, double tol, doubl
   qp.oidx = oidx;
   qp.oval = oval;
   qp.ocap = ocap;
-  return decompose_fused<T, OUT_Q>(h, data, nullptr, &qp, st);
+  return decompose_fused<T, OUT_Q>(h, data, in, nullptr, &qp, st);
 }
 
 // Same with the norm (and hence the quantizers) never leaving the device: d_norm given, or
 // computed here (REL). h_norm_out != NULL costs one synchronisation at the END of the call.
 template <typename T>
-int fused_q_entry_device(mgh_hierarchy *h, const T *data, int ebtype, double tol, double s,
+int fused_q_entry_device(mgh_hierarchy *h, const T *data, Layout in, int ebtype, double tol, double s,
                          const T *d_norm, int decomposed, uint64_t nsub, double *h_norm_out,
                          uint64_t dict_size, int prep_huffman, int64_t *q, uint64_t *ocount,
                          uint64_t *oidx, int64_t *oval, uint64_t ocap, hipStream_t st,
                          uint16_t *q16 = nullptr) {
   auto *ds = DS<T>(h);
+  TRY(ld_pack<T>(h, data, in, true, st));
   // (mgh_norm_stream_*: the reduction is in the slot already; anything else the caller passes
   // alongside -- a given norm, an ABS bound -- overrides it)
   const bool streamed = ds->norm_streamed && !d_norm && ebtype == MGH_REL;
@@ -2753,12 +2837,10 @@ int fused_q_entry_device(mgh_hierarchy *h, const T *data, int ebtype, double tol
     // the 256 MB memory-side cache (512^3 f32, same box, 60 steps each: absmax 109 -> 93 us,
     // top-level pass 384 -> 397 us, step 0.894 -> 0.889 ms)
     const size_t total = h->total, warm = ((size_t)h->absmax_warm_mb << 20) / sizeof(T);
-    if (ds->src_J) {  // (pitched input read in place: row by row)
-      const LdView V = ld_view(h, 0);
-      TRY(norm_reduce<T>(h, data, s, slot, &V, 0, st));
-    } else {
+    if (in.pitched)  // (read in place: row by row)
+      TRY(norm_reduce<T>(h, data, s, slot, &in.view, 0, st));
+    else
       TRY(norm_reduce<T>(h, data, s, slot, nullptr, total > warm ? total - warm : 0, st));
-    }
   }
   auto qparams = [&] {
     QParamArgs<T> P;
@@ -2780,7 +2862,7 @@ int fused_q_entry_device(mgh_hierarchy *h, const T *data, int ebtype, double tol
   qp.oidx = oidx;
   qp.oval = oval;
   qp.ocap = ocap;
-  TRY((decompose_fused<T, OUT_Q>(h, data, nullptr, &qp, st, qparams)));
+  TRY((decompose_fused<T, OUT_Q>(h, data, in, nullptr, &qp, st, qparams)));
   if (h_norm_out) {
     T nv = 0;
     HIP_TRY(hipMemcpyAsync(&nv, ds->normval, sizeof(T), hipMemcpyDeviceToHost, st));
@@ -2790,38 +2872,92 @@ int fused_q_entry_device(mgh_hierarchy *h, const T *data, int ebtype, double tol
   return MGH_SUCCESS;
 }
 
-// Dense view of the caller's pitched arrays for the paths that do not take strides. ld_pack: the
-// input copied into a dense buffer of the hierarchy (p then points there); LdOut: the kernels write
-// a dense buffer, finish() spreads it into the caller's pitched array. Dense callers pay nothing.
-template <typename T> int ld_pack(mgh_hierarchy *h, const T *&p, hipStream_t st) {
-  if (!h->has_ld[0] || !p) return MGH_SUCCESS;
+// REL bound without a norm on the shapes the fused level kernels do not take (D = 5, thin boxes ...):
+// norm, quantizer table, decomposition and quantizer queued one behind the other -- the norm and the
+// table stay on the device as in fused_q_entry_device (mgh_norm + mgh_quantize were two host round
+// trips, 35 us each on the 5-D step). h_norm_out != NULL: one synchronisation at the END.
+template <typename T>
+int staged_q_entry_device(mgh_hierarchy *h, const T *data, int ebtype, double tol, double s, double *h_norm_out,
+                          uint64_t dict_size, int prep_huffman, int64_t *q, uint64_t *ocount, uint64_t *oidx,
+                          int64_t *oval, uint64_t ocap, T *coeff, hipStream_t st) {
   auto *ds = DS<T>(h);
-  if (!ds->pack_in) TRY(dev_alloc(h, &ds->pack_in, (size_t)h->total));
-  const LdView V = ld_view(h, 0);
-  TRY(launch(h, "ld_pack", st, [&] { k_ld_copy<T><<<ld_grid(V), 256, 0, st>>>(ds->pack_in, const_cast<T *>(p), V, 1); }));
-  p = ds->pack_in;
+  TRY(norm_launch<T>(h, data, dense_layout(h), s, st));
+  TRY(make_qparams_launch<T>(h, nullptr, ebtype, tol, s, 0, 1, nullptr, st));
+  ds->qmeta.calc_vol = ((T)s == std::numeric_limits<T>::infinity()) ? 0 : 1;
+  TRY(decompose_dense<T>(h, data, coeff, st));
+  TRY(quantize_launch<T>(h, coeff, dict_size, prep_huffman, q, ocount, oidx, oval, ocap, st));
+  if (h_norm_out) {
+    T nv;
+    HIP_TRY(hipMemcpyAsync(&nv, ds->normval, sizeof(T), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    *h_norm_out = (double)nv;
+  }
   return MGH_SUCCESS;
 }
-template <typename T> struct LdOut {
-  T *user = nullptr;
-  int begin(mgh_hierarchy *h, T *&p) {
-    if (!h->has_ld[1] || !p) return MGH_SUCCESS;
-    auto *ds = DS<T>(h);
-    if (!ds->pack_out) TRY(dev_alloc(h, &ds->pack_out, (size_t)h->total));
-    user = p;
-    p = ds->pack_out;
-    return MGH_SUCCESS;
+
+inline int outlier_args(int prep_huffman, const uint64_t *ocount, const uint64_t *oidx, const int64_t *oval,
+                        uint64_t ocap) {
+  if (prep_huffman && (!ocount || (ocap && (!oidx || !oval))))
+    return fail(MGH_ERR_INVALID_ARGUMENT, "outlier buffers required with prep_huffman");
+  return MGH_SUCCESS;
+}
+
+// mgh_decompose_quantize. Without a coefficient output, on the shapes the fused level kernels take:
+// one fused pass. Else staged on dense arrays: the coefficients go to `coeff` (through a dense copy
+// if it is pitched) or to scratch_full, and the quantizer reads them there.
+template <typename T>
+int decompose_quantize(mgh_hierarchy *h, const T *data, Layout in, int ebtype, double tol, double s, double norm,
+                       double *h_norm_out, uint64_t dict_size, int prep_huffman, int64_t *q, uint64_t *ocount,
+                       uint64_t *oidx, int64_t *oval, uint64_t ocap, T *coeff, Layout out, hipStream_t st) {
+  TRY(outlier_args(prep_huffman, ocount, oidx, oval, ocap));
+  // REL without a norm: the norm and the quantizers stay on the device, no host round trip inside the call
+  const bool device_norm = ebtype == MGH_REL && !(norm > 0);
+  if (!device_norm && h_norm_out) *h_norm_out = norm;
+  // (the fused level kernels test the dictionary range in 32 bits: larger dictionaries are staged)
+  if (!coeff && fusedc_ok(h) && !h->force_v1 && dict_size <= ((uint64_t)1 << 30)) {
+    if (device_norm)
+      return fused_q_entry_device<T>(h, data, in, ebtype, tol, s, nullptr, 0, 1, h_norm_out, dict_size, prep_huffman,
+                                     q, ocount, oidx, oval, ocap, st);
+    if (ocount) HIP_TRY(hipMemsetAsync(ocount, 0, sizeof(uint64_t), st));
+    return fused_q_entry<T>(h, data, in, ebtype, tol, s, norm, dict_size, prep_huffman, q, ocount, oidx, oval, ocap, st);
   }
-  int finish(mgh_hierarchy *h, hipStream_t st) {
-    if (!user) return MGH_SUCCESS;
-    auto *ds = DS<T>(h);
-    const LdView V = ld_view(h, 1);
-    return launch(h, "ld_unpack", st, [&] { k_ld_copy<T><<<ld_grid(V), 256, 0, st>>>(ds->pack_out, user, V, 0); });
+  TRY(ld_pack<T>(h, data, in, false, st));
+  LdOut<T> o;
+  TRY(o.begin(h, coeff, out, false));
+  if (!coeff) {
+    TRY(ensure_scratch<T>(h));
+    coeff = DS<T>(h)->scratch_full;
+    if (coeff == data) return fail(MGH_ERR_INVALID_ARGUMENT, "aliasing");
   }
-};
-// Strides of a pitched array in the 3-D view of the fused kernels, when they can read / write it in
-// place: D <= 3 on the fused path, planes addressable in 32 bits like the dense ones.
-inline bool ld_native3(const mgh_hierarchy *h, int which, size_t &sI, size_t &sJ);
+  if (device_norm) {
+    TRY(staged_q_entry_device<T>(h, data, ebtype, tol, s, h_norm_out, dict_size, prep_huffman, q, ocount, oidx, oval,
+                                 ocap, coeff, st));
+  } else {
+    TRY(decompose_dense<T>(h, data, coeff, st));
+    TRY(quantize_impl<T>(h, coeff, dense_layout(h), ebtype, tol, s, norm, dict_size, prep_huffman, q, ocount, oidx,
+                         oval, ocap, st));
+  }
+  return o.finish(h, st);
+}
+
+// mgh_dequantize_recompose: the fused level loop, or dequantizer and recomposition in place on the
+// (dense) output.
+template <typename T>
+int dequantize_recompose(mgh_hierarchy *h, int64_t *q, int ebtype, double tol, double s, double norm,
+                         uint64_t dict_size, int prep_huffman, const uint64_t *oidx, const int64_t *oval,
+                         uint64_t ocount, T *data, Layout out, hipStream_t st) {
+  const bool fused = fusedc_ok(h) && !h->force_v1;
+  LdOut<T> o;
+  TRY(o.begin(h, data, out, fused));
+  if (fused) {
+    TRY(dequantize_recompose_fused<T>(h, q, ebtype, tol, s, norm, dict_size, prep_huffman, oidx, oval, ocount, data,
+                                      out, st));
+  } else {
+    TRY(dequantize_dense<T>(h, q, ebtype, tol, s, norm, dict_size, prep_huffman, oidx, oval, ocount, data, st));
+    TRY(recompose_dense<T>(h, data, data, st));
+  }
+  return o.finish(h, st);
+}
 
 // Norm accumulated over parts of the input (mgh_norm_stream_begin / _add): the same reduction
 // kernels on a range, into the slot the next fused call reads.
@@ -2844,75 +2980,12 @@ int norm_stream_add(mgh_hierarchy *h, const T *part, size_t count, double s, int
   return launch(h, "sqsum", st, [&] { k_sqsum<T><<<grid, 256, 0, st>>>(part, count, (double *)slot, cold ? count : 0); });
 }
 
-#define DISPATCH(h, call_f, call_d)                                              \
-  ((h)->dtype == MGH_FLOAT ? (call_f) : (call_d))
-
-inline bool ld_native3(const mgh_hierarchy *h, int which, size_t &sI, size_t &sJ) {
-  if (!h->has_ld[which] || !fused_ok(h) || h->force_v1) return false;
-  const uint64_t lf = h->ld[which][2], lc = h->ld[which][1];
-  if (lf * lc >= ((uint64_t)1 << 30)) return false;
-  sJ = (size_t)lf;
-  sI = (size_t)(lf * lc);
-  return true;
-}
-
-// An entry point with a pitched T input and / or output (mgh_set_ld): `call(in, out)` is the entry
-// point itself, run once more under the guard with pointers it can take as dense ones -- copies
-// (ld_pack / LdOut), or the caller's own arrays where the fused 3-D kernels take the strides
-// (native_ok: the call is one that runs them).
-template <typename T, typename F>
-int ld_entry_t(mgh_hierarchy *h, const void *in, void *out, bool native_ok, hipStream_t st, F &&call) {
-  auto *ds = DS<T>(h);
-  const T *pin = (const T *)in;
-  T *pout = (T *)out;
-  size_t sI = 0, sJ = 0, oI = 0, oJ = 0;
-  const bool nat_in = pin && native_ok && ld_native3(h, 0, sI, sJ);
-  const bool nat_out = pout && native_ok && ld_native3(h, 1, oI, oJ);
-  if (pin && h->has_ld[0] && !nat_in) TRY(ld_pack<T>(h, pin, st));
-  LdOut<T> o;
-  if (pout && h->has_ld[1] && !nat_out) TRY(o.begin(h, pout));
-  if (nat_in) ds->src_I = sI, ds->src_J = sJ;
-  if (nat_out) ds->dst_I = oI, ds->dst_J = oJ;
-  h->ld_guard = true;
-  const int rc = call((const void *)pin, (void *)pout);
-  h->ld_guard = false;
-  ds->src_I = ds->src_J = ds->dst_I = ds->dst_J = 0;
-  if (rc != MGH_SUCCESS) return rc;
-  return o.finish(h, st);
-}
-template <typename F>
-int ld_entry(mgh_hierarchy *h, const void *in, void *out, bool native_ok, void *stream, F &&call) {
-  if (h->dtype == MGH_FLOAT) return ld_entry_t<float>(h, in, out, native_ok, (hipStream_t)stream, call);
-  return ld_entry_t<double>(h, in, out, native_ok, (hipStream_t)stream, call);
-}
-inline bool ld_wanted(const mgh_hierarchy *h, const void *in, const void *out) {
-  return !h->ld_guard && ((in && h->has_ld[0]) || (out && h->has_ld[1]));
+// One body for both element types: f(T()) with the T of the hierarchy.
+template <typename F> auto with_type(const mgh_hierarchy *h, F &&f) {
+  return h->dtype == MGH_FLOAT ? f(float()) : f(double());
 }
 
 } // namespace
-
-// REL bound without a norm on the shapes the fused level kernels do not take (D = 5, thin boxes ...):
-// norm, quantizer table, decomposition and quantizer queued one behind the other -- the norm and the
-// table stay on the device as in fused_q_entry_device (mgh_norm + mgh_quantize were two host round
-// trips, 35 us each on the 5-D step). h_norm_out != NULL: one synchronisation at the END.
-template <typename T>
-int staged_q_entry_device(mgh_hierarchy *h, const T *data, int ebtype, double tol, double s, double *h_norm_out,
-                          uint64_t dict_size, int prep_huffman, int64_t *q, uint64_t *ocount, uint64_t *oidx,
-                          int64_t *oval, uint64_t ocap, T *coeff, hipStream_t st) {
-  auto *ds = DS<T>(h);
-  TRY(norm_launch<T>(h, data, s, st));
-  TRY(make_qparams_launch<T>(h, nullptr, ebtype, tol, s, 0, 1, nullptr, st));
-  ds->qmeta.calc_vol = ((T)s == std::numeric_limits<T>::infinity()) ? 0 : 1;
-  TRY(mgh_decompose(h, data, coeff, (void *)st));
-  TRY(quantize_launch<T>(h, coeff, dict_size, prep_huffman, q, ocount, oidx, oval, ocap, st));
-  if (h_norm_out) {
-    T nv;
-    HIP_TRY(hipMemcpyAsync(&nv, ds->normval, sizeof(T), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    *h_norm_out = (double)nv;
-  }
-  return MGH_SUCCESS;
-}
 
 extern "C" {
 
@@ -3032,7 +3105,7 @@ int mgh_hierarchy_create(mgh_hierarchy **out, int D, const uint64_t *shape, int 
     if (h->fused_tall && m2 <= 16 && m1 >= 48) tiles = (double)((m1 + 63) / 64) * (double)((m2 + 3) / 4);
     if ((double)(m1 * m2) < 0.125 * tiles * 256.0) h->force_v1 = true;
   }
-  int rc = DISPATCH(h, build_device_state<float>(h), build_device_state<double>(h));
+  int rc = with_type(h, [&](auto t) { return build_device_state<decltype(t)>(h); });
   if (rc != MGH_SUCCESS) {
     mgh_hierarchy_destroy(h);
     return rc;
@@ -3049,7 +3122,7 @@ void mgh_hierarchy_destroy(mgh_hierarchy *h) {
       (void)hipEventDestroy(ev.first);
       (void)hipEventDestroy(ev.second);
     }
-  if (h->dtype == MGH_FLOAT) destroy_state<float>(h); else destroy_state<double>(h);
+  with_type(h, [&](auto t) { destroy_state<decltype(t)>(h); return 0; });
   delete h;
 }
 
@@ -3057,25 +3130,24 @@ int mgh_l_target(const mgh_hierarchy *h) { return h ? h->L : MGH_ERR_INVALID_ARG
 
 int mgh_level_shape(const mgh_hierarchy *h, int level, uint64_t *out_shape) {
   if (!h || !out_shape || level < 0 || level > h->L) return fail(MGH_ERR_INVALID_ARGUMENT, "level");
-  for (int d = 0; d < h->D; d++)
-    out_shape[d] = h->dtype == MGH_FLOAT ? HH<float>(h)->level_shape[level][d]
-                                         : HH<double>(h)->level_shape[level][d];
-  return MGH_SUCCESS;
+  return with_type(h, [&](auto t) {
+    for (int d = 0; d < h->D; d++) out_shape[d] = HH<decltype(t)>(h)->level_shape[level][d];
+    return (int)MGH_SUCCESS;
+  });
 }
 
 uint64_t mgh_total_num_elems(const mgh_hierarchy *h) { return h ? h->total : 0; }
 size_t mgh_device_bytes(const mgh_hierarchy *h) { return h ? h->device_bytes : 0; }
 const void *mgh_norm_device_ptr(const mgh_hierarchy *h) {
   if (!h) return nullptr;
-  return h->dtype == MGH_FLOAT ? (const void *)DS<float>(h)->normval : (const void *)DS<double>(h)->normval;
+  return with_type(h, [&](auto t) { return (const void *)DS<decltype(t)>(h)->normval; });
 }
 
 
 int64_t mgh_hierarchy_table(const mgh_hierarchy *h, int kind, int level, int dim, void *h_out,
                             uint64_t cap) {
   if (!h || !h_out) return fail(MGH_ERR_INVALID_ARGUMENT, "null argument");
-  return DISPATCH(h, table_impl<float>(h, kind, level, dim, h_out, cap),
-                  table_impl<double>(h, kind, level, dim, h_out, cap));
+  return with_type(h, [&](auto t) { return table_impl<decltype(t)>(h, kind, level, dim, h_out, cap); });
 }
 
 int mgh_set_ld(mgh_hierarchy *h, int which, const uint64_t *ld) {
@@ -3094,29 +3166,36 @@ int mgh_set_ld(mgh_hierarchy *h, int which, const uint64_t *ld) {
   return MGH_SUCCESS;
 }
 
+// The stage entry points: arguments checked, the layouts of their OWN T arguments taken from the
+// setting (caller_layout), one internal template called. The stages reach each other through the
+// templates, never through these.
 int mgh_norm(mgh_hierarchy *h, const void *d_data, double s, double *h_norm_out, void *stream) {
   if (!h || !d_data || !h_norm_out) return fail(MGH_ERR_INVALID_ARGUMENT, "null argument");
   HIP_TRY(hipSetDevice(h->device));
-  return DISPATCH(h, norm_impl<float>(h, (const float *)d_data, s, h_norm_out, (hipStream_t)stream),
-                  norm_impl<double>(h, (const double *)d_data, s, h_norm_out, (hipStream_t)stream));
+  return with_type(h, [&](auto t) {
+    using T = decltype(t);
+    return norm_impl<T>(h, (const T *)d_data, caller_layout(h, MGH_LD_IN), s, h_norm_out, (hipStream_t)stream);
+  });
 }
 
 int mgh_decompose(mgh_hierarchy *h, const void *d_data, void *d_coeff, void *stream) {
   if (!h || !d_data || !d_coeff) return fail(MGH_ERR_INVALID_ARGUMENT, "null argument");
   HIP_TRY(hipSetDevice(h->device));
-  if (ld_wanted(h, d_data, d_coeff))
-    return ld_entry(h, d_data, d_coeff, false, stream, [&](const void *i, void *o) { return mgh_decompose(h, i, o, stream); });
-  return DISPATCH(h, decompose_impl<float>(h, (const float *)d_data, (float *)d_coeff, (hipStream_t)stream),
-                  decompose_impl<double>(h, (const double *)d_data, (double *)d_coeff, (hipStream_t)stream));
+  return with_type(h, [&](auto t) {
+    using T = decltype(t);
+    return decompose_impl<T>(h, (const T *)d_data, caller_layout(h, MGH_LD_IN), (T *)d_coeff,
+                             caller_layout(h, MGH_LD_OUT), (hipStream_t)stream);
+  });
 }
 
 int mgh_recompose(mgh_hierarchy *h, const void *d_coeff, void *d_data, void *stream) {
   if (!h || !d_data || !d_coeff) return fail(MGH_ERR_INVALID_ARGUMENT, "null argument");
   HIP_TRY(hipSetDevice(h->device));
-  if (ld_wanted(h, d_coeff, d_data))
-    return ld_entry(h, d_coeff, d_data, false, stream, [&](const void *i, void *o) { return mgh_recompose(h, i, o, stream); });
-  return DISPATCH(h, recompose_impl<float>(h, (const float *)d_coeff, (float *)d_data, (hipStream_t)stream),
-                  recompose_impl<double>(h, (const double *)d_coeff, (double *)d_data, (hipStream_t)stream));
+  return with_type(h, [&](auto t) {
+    using T = decltype(t);
+    return recompose_impl<T>(h, (const T *)d_coeff, caller_layout(h, MGH_LD_IN), (T *)d_data,
+                             caller_layout(h, MGH_LD_OUT), (hipStream_t)stream);
+  });
 }
 
 int mgh_quantize(mgh_hierarchy *h, const void *d_coeff, int ebtype, double tol, double s,
@@ -3124,21 +3203,14 @@ int mgh_quantize(mgh_hierarchy *h, const void *d_coeff, int ebtype, double tol, 
                  uint64_t *d_outlier_count, uint64_t *d_outlier_idx, int64_t *d_outlier_val,
                  uint64_t outlier_capacity, void *stream) {
   if (!h || !d_coeff || !d_quantized) return fail(MGH_ERR_INVALID_ARGUMENT, "null argument");
-  if (prep_huffman && (!d_outlier_count || (outlier_capacity && (!d_outlier_idx || !d_outlier_val))))
-    return fail(MGH_ERR_INVALID_ARGUMENT, "outlier buffers required with prep_huffman");
+  TRY(outlier_args(prep_huffman, d_outlier_count, d_outlier_idx, d_outlier_val, outlier_capacity));
   HIP_TRY(hipSetDevice(h->device));
-  if (ld_wanted(h, d_coeff, nullptr))  // (pitched coefficients: quantized from a dense copy; the integers are always dense)
-    return ld_entry(h, d_coeff, nullptr, false, stream, [&](const void *i, void *) {
-      return mgh_quantize(h, i, ebtype, tol, s, norm, dict_size, prep_huffman, d_quantized, d_outlier_count,
-                          d_outlier_idx, d_outlier_val, outlier_capacity, stream);
-    });
-  return DISPATCH(h,
-                  quantize_impl<float>(h, (const float *)d_coeff, ebtype, tol, s, norm, dict_size,
-                                       prep_huffman, d_quantized, d_outlier_count, d_outlier_idx,
-                                       d_outlier_val, outlier_capacity, (hipStream_t)stream),
-                  quantize_impl<double>(h, (const double *)d_coeff, ebtype, tol, s, norm, dict_size,
-                                        prep_huffman, d_quantized, d_outlier_count, d_outlier_idx,
-                                        d_outlier_val, outlier_capacity, (hipStream_t)stream));
+  return with_type(h, [&](auto t) {
+    using T = decltype(t);
+    return quantize_impl<T>(h, (const T *)d_coeff, caller_layout(h, MGH_LD_IN), ebtype, tol, s, norm, dict_size,
+                            prep_huffman, d_quantized, d_outlier_count, d_outlier_idx, d_outlier_val,
+                            outlier_capacity, (hipStream_t)stream);
+  });
 }
 
 int mgh_dequantize(mgh_hierarchy *h, int64_t *d_quantized, int ebtype, double tol, double s,
@@ -3147,18 +3219,12 @@ int mgh_dequantize(mgh_hierarchy *h, int64_t *d_quantized, int ebtype, double to
                    uint64_t outlier_count, void *d_coeff, void *stream) {
   if (!h || !d_coeff || !d_quantized) return fail(MGH_ERR_INVALID_ARGUMENT, "null argument");
   HIP_TRY(hipSetDevice(h->device));
-  if (ld_wanted(h, nullptr, d_coeff))  // (pitched coefficients out: dequantized densely, then spread)
-    return ld_entry(h, nullptr, d_coeff, false, stream, [&](const void *, void *o) {
-      return mgh_dequantize(h, d_quantized, ebtype, tol, s, norm, dict_size, prep_huffman, d_outlier_idx,
-                            d_outlier_val, outlier_count, o, stream);
-    });
-  return DISPATCH(h,
-                  dequantize_impl<float>(h, d_quantized, ebtype, tol, s, norm, dict_size,
-                                         prep_huffman, d_outlier_idx, d_outlier_val, outlier_count,
-                                         (float *)d_coeff, (hipStream_t)stream),
-                  dequantize_impl<double>(h, d_quantized, ebtype, tol, s, norm, dict_size,
-                                          prep_huffman, d_outlier_idx, d_outlier_val, outlier_count,
-                                          (double *)d_coeff, (hipStream_t)stream));
+  return with_type(h, [&](auto t) {
+    using T = decltype(t);
+    return dequantize_impl<T>(h, d_quantized, ebtype, tol, s, norm, dict_size, prep_huffman, d_outlier_idx,
+                              d_outlier_val, outlier_count, (T *)d_coeff, caller_layout(h, MGH_LD_OUT),
+                              (hipStream_t)stream);
+  });
 }
 
 int mgh_decompose_quantize_sym16(mgh_hierarchy *h, const void *d_data, int error_bound_type, double tol,
@@ -3172,41 +3238,23 @@ int mgh_decompose_quantize_sym16(mgh_hierarchy *h, const void *d_data, int error
   HIP_TRY(hipSetDevice(h->device));
   if (!(fusedc_ok(h) && !h->force_v1))
     return fail(MGH_ERR_UNSUPPORTED_DIMENSION, "16-bit symbols: only on the fused 3-D / 4-D path");
-  if (ld_wanted(h, d_data, nullptr))
-    return ld_entry(h, d_data, nullptr, true, stream, [&](const void *i, void *) {
-      return mgh_decompose_quantize_sym16(h, i, error_bound_type, tol, s, norm, h_norm_out, dict_size, d_symbols,
-                                          d_outlier_count, d_outlier_idx, d_outlier_val, outlier_capacity, stream);
-    });
-  // (the norm and the quantizers stay on the device; a given norm is uploaded first)
-  const void *d_norm = nullptr;
-  if (!(error_bound_type == MGH_REL && !(norm > 0)) && error_bound_type == MGH_REL) {
-    if (h->dtype == MGH_FLOAT) {
-      const float nv = (float)norm;
-      HIP_TRY(hipMemcpyAsync(DS<float>(h)->normval, &nv, sizeof(float), hipMemcpyHostToDevice, (hipStream_t)stream));
-      HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-      d_norm = DS<float>(h)->normval;
-    } else {
-      const double nv = norm;
-      HIP_TRY(hipMemcpyAsync(DS<double>(h)->normval, &nv, sizeof(double), hipMemcpyHostToDevice, (hipStream_t)stream));
-      HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-      d_norm = DS<double>(h)->normval;
+  hipStream_t st = (hipStream_t)stream;
+  return with_type(h, [&](auto t) -> int {
+    using T = decltype(t);
+    // (the norm and the quantizers stay on the device; a given norm is uploaded first)
+    const bool device_norm = error_bound_type == MGH_REL && !(norm > 0);
+    const T *d_norm = nullptr;
+    if (error_bound_type == MGH_REL && !device_norm) {
+      const T nv = (T)norm;
+      HIP_TRY(hipMemcpyAsync(DS<T>(h)->normval, &nv, sizeof(T), hipMemcpyHostToDevice, st));
+      HIP_TRY(hipStreamSynchronize(st));
+      d_norm = DS<T>(h)->normval;
     }
-    if (h_norm_out) *h_norm_out = norm;
-    h_norm_out = nullptr;
-  }
-  if (error_bound_type != MGH_REL) {  // (no norm involved)
-    if (h_norm_out) *h_norm_out = norm;
-    h_norm_out = nullptr;
-  }
-  return DISPATCH(h,
-                  fused_q_entry_device<float>(h, (const float *)d_data, error_bound_type, tol, s,
-                                              (const float *)d_norm, 0, 1, h_norm_out, dict_size, 1, nullptr,
-                                              d_outlier_count, d_outlier_idx, d_outlier_val,
-                                              outlier_capacity, (hipStream_t)stream, d_symbols),
-                  fused_q_entry_device<double>(h, (const double *)d_data, error_bound_type, tol, s,
-                                               (const double *)d_norm, 0, 1, h_norm_out, dict_size, 1, nullptr,
-                                               d_outlier_count, d_outlier_idx, d_outlier_val,
-                                               outlier_capacity, (hipStream_t)stream, d_symbols));
+    if (!device_norm && h_norm_out) *h_norm_out = norm;  // (given, or none involved)
+    return fused_q_entry_device<T>(h, (const T *)d_data, caller_layout(h, MGH_LD_IN), error_bound_type, tol, s,
+                                   d_norm, 0, 1, device_norm ? h_norm_out : nullptr, dict_size, 1, nullptr,
+                                   d_outlier_count, d_outlier_idx, d_outlier_val, outlier_capacity, st, d_symbols);
+  });
 }
 
 int mgh_sym16_supported(const mgh_hierarchy *h) {
@@ -3223,18 +3271,17 @@ int mgh_dequantize_recompose_sym16(mgh_hierarchy *h, const uint16_t *d_symbols, 
   HIP_TRY(hipSetDevice(h->device));
   if (!mgh_sym16_supported(h))
     return fail(MGH_ERR_UNSUPPORTED_DIMENSION, "16-bit symbols: only on the fused 3-D / 4-D path");
-  if (ld_wanted(h, nullptr, d_data_out))
-    return ld_entry(h, nullptr, d_data_out, true, stream, [&](const void *, void *o) {
-      return mgh_dequantize_recompose_sym16(h, d_symbols, error_bound_type, tol, s, norm, dict_size, d_outlier_idx,
-                                            d_outlier_val, outlier_count, o, stream);
-    });
-  return DISPATCH(h,
-                  dequantize_recompose_fused16<float>(h, d_symbols, error_bound_type, tol, s, norm, dict_size,
-                                                      d_outlier_idx, d_outlier_val, outlier_count,
-                                                      (float *)d_data_out, (hipStream_t)stream),
-                  dequantize_recompose_fused16<double>(h, d_symbols, error_bound_type, tol, s, norm, dict_size,
-                                                       d_outlier_idx, d_outlier_val, outlier_count,
-                                                       (double *)d_data_out, (hipStream_t)stream));
+  hipStream_t st = (hipStream_t)stream;
+  return with_type(h, [&](auto t) -> int {
+    using T = decltype(t);
+    T *data = (T *)d_data_out;
+    Layout out = caller_layout(h, MGH_LD_OUT);
+    LdOut<T> o;
+    TRY(o.begin(h, data, out, true));
+    TRY(dequantize_recompose_fused16<T>(h, d_symbols, error_bound_type, tol, s, norm, dict_size, d_outlier_idx,
+                                        d_outlier_val, outlier_count, data, out, st));
+    return o.finish(h, st);
+  });
 }
 
 int mgh_decompose_quantize(mgh_hierarchy *h, const void *d_data, int error_bound_type, double tol, double s,
@@ -3244,76 +3291,13 @@ int mgh_decompose_quantize(mgh_hierarchy *h, const void *d_data, int error_bound
                            uint64_t outlier_capacity, void *d_coeff_opt, void *stream) {
   if (!h || !d_data || !d_quantized) return fail(MGH_ERR_INVALID_ARGUMENT, "null argument");
   HIP_TRY(hipSetDevice(h->device));
-  // (the fused level kernels test the dictionary range in 32 bits: larger dictionaries are staged)
-  const bool fused = !d_coeff_opt && fusedc_ok(h) && !h->force_v1 && dict_size <= ((uint64_t)1 << 30);
-  if (ld_wanted(h, d_data, d_coeff_opt))
-    return ld_entry(h, d_data, d_coeff_opt, fused, stream, [&](const void *i, void *o) {
-      return mgh_decompose_quantize(h, i, error_bound_type, tol, s, norm, h_norm_out, dict_size, prep_huffman,
-                                    d_quantized, d_outlier_count, d_outlier_idx, d_outlier_val, outlier_capacity, o,
-                                    stream);
-    });
-  if (fused && error_bound_type == MGH_REL && !(norm > 0)) {
-    // the norm and the quantizers stay on the device: no host round trip inside the call
-    if (prep_huffman && (!d_outlier_count || (outlier_capacity && (!d_outlier_idx || !d_outlier_val))))
-      return fail(MGH_ERR_INVALID_ARGUMENT, "outlier buffers required with prep_huffman");
-    return DISPATCH(h,
-                    fused_q_entry_device<float>(h, (const float *)d_data, error_bound_type, tol, s,
-                                                nullptr, 0, 1, h_norm_out, dict_size, prep_huffman,
-                                                d_quantized, d_outlier_count, d_outlier_idx,
-                                                d_outlier_val, outlier_capacity, (hipStream_t)stream),
-                    fused_q_entry_device<double>(h, (const double *)d_data, error_bound_type, tol, s,
-                                                 nullptr, 0, 1, h_norm_out, dict_size, prep_huffman,
-                                                 d_quantized, d_outlier_count, d_outlier_idx,
-                                                 d_outlier_val, outlier_capacity, (hipStream_t)stream));
-  }
-  if (!fused && error_bound_type == MGH_REL && !(norm > 0)) {
-    void *coeff = d_coeff_opt;
-    if (!coeff) {
-      int rc = DISPATCH(h, ensure_scratch<float>(h), ensure_scratch<double>(h));
-      if (rc != MGH_SUCCESS) return rc;
-      coeff = h->dtype == MGH_FLOAT ? (void *)DS<float>(h)->scratch_full : (void *)DS<double>(h)->scratch_full;
-      if (coeff == d_data) return fail(MGH_ERR_INVALID_ARGUMENT, "aliasing");
-    }
-    return DISPATCH(h,
-                    staged_q_entry_device<float>(h, (const float *)d_data, error_bound_type, tol, s, h_norm_out,
-                                                 dict_size, prep_huffman, d_quantized, d_outlier_count, d_outlier_idx,
-                                                 d_outlier_val, outlier_capacity, (float *)coeff, (hipStream_t)stream),
-                    staged_q_entry_device<double>(h, (const double *)d_data, error_bound_type, tol, s, h_norm_out,
-                                                  dict_size, prep_huffman, d_quantized, d_outlier_count, d_outlier_idx,
-                                                  d_outlier_val, outlier_capacity, (double *)coeff, (hipStream_t)stream));
-  }
-  if (error_bound_type == MGH_REL && !(norm > 0)) {
-    int rc = mgh_norm(h, d_data, s, &norm, stream);
-    if (rc != MGH_SUCCESS) return rc;
-  }
-  if (h_norm_out) *h_norm_out = norm;
-  if (fused) {
-    if (prep_huffman && (!d_outlier_count || (outlier_capacity && (!d_outlier_idx || !d_outlier_val))))
-      return fail(MGH_ERR_INVALID_ARGUMENT, "outlier buffers required with prep_huffman");
-    if (d_outlier_count) HIP_TRY(hipMemsetAsync(d_outlier_count, 0, sizeof(uint64_t), (hipStream_t)stream));
-    return DISPATCH(h,
-                    fused_q_entry<float>(h, (const float *)d_data, error_bound_type, tol, s, norm,
-                                         dict_size, prep_huffman, d_quantized, d_outlier_count,
-                                         d_outlier_idx, d_outlier_val, outlier_capacity,
-                                         (hipStream_t)stream),
-                    fused_q_entry<double>(h, (const double *)d_data, error_bound_type, tol, s, norm,
-                                          dict_size, prep_huffman, d_quantized, d_outlier_count,
-                                          d_outlier_idx, d_outlier_val, outlier_capacity,
-                                          (hipStream_t)stream));
-  }
-  void *coeff = d_coeff_opt;
-  if (!coeff) {
-    int rc = DISPATCH(h, ensure_scratch<float>(h), ensure_scratch<double>(h));
-    if (rc != MGH_SUCCESS) return rc;
-    coeff = h->dtype == MGH_FLOAT ? (void *)DS<float>(h)->scratch_full
-                                  : (void *)DS<double>(h)->scratch_full;
-    if (coeff == d_data) return fail(MGH_ERR_INVALID_ARGUMENT, "aliasing");
-  }
-  int rc = mgh_decompose(h, d_data, coeff, stream);
-  if (rc != MGH_SUCCESS) return rc;
-  return mgh_quantize(h, coeff, error_bound_type, tol, s, norm, dict_size, prep_huffman,
-                      d_quantized, d_outlier_count, d_outlier_idx, d_outlier_val,
-                      outlier_capacity, stream);
+  return with_type(h, [&](auto t) {
+    using T = decltype(t);
+    return decompose_quantize<T>(h, (const T *)d_data, caller_layout(h, MGH_LD_IN), error_bound_type, tol, s, norm,
+                                 h_norm_out, dict_size, prep_huffman, d_quantized, d_outlier_count, d_outlier_idx,
+                                 d_outlier_val, outlier_capacity, (T *)d_coeff_opt, caller_layout(h, MGH_LD_OUT),
+                                 (hipStream_t)stream);
+  });
 }
 
 int mgh_norm_device(mgh_hierarchy *h, const void *d_data, double s, void *d_norm_out,
@@ -3321,17 +3305,14 @@ int mgh_norm_device(mgh_hierarchy *h, const void *d_data, double s, void *d_norm
   if (!h || !d_data || !d_norm_out) return fail(MGH_ERR_INVALID_ARGUMENT, "null argument");
   HIP_TRY(hipSetDevice(h->device));
   hipStream_t st = (hipStream_t)stream;
-  if (h->dtype == MGH_FLOAT) {
-    TRY(norm_launch<float>(h, (const float *)d_data, s, st));
+  return with_type(h, [&](auto t) -> int {
+    using T = decltype(t);
+    TRY(norm_launch<T>(h, (const T *)d_data, caller_layout(h, MGH_LD_IN), s, st));
     // ABS/undecomposed parameters are irrelevant here: only the norm conversion is wanted
-    TRY(make_qparams_launch<float>(h, nullptr, MGH_ABS, 1.0, s, 0, 1, nullptr, st));
-    HIP_TRY(hipMemcpyAsync(d_norm_out, DS<float>(h)->normval, sizeof(float), hipMemcpyDeviceToDevice, st));
-  } else {
-    TRY(norm_launch<double>(h, (const double *)d_data, s, st));
-    TRY(make_qparams_launch<double>(h, nullptr, MGH_ABS, 1.0, s, 0, 1, nullptr, st));
-    HIP_TRY(hipMemcpyAsync(d_norm_out, DS<double>(h)->normval, sizeof(double), hipMemcpyDeviceToDevice, st));
-  }
-  return MGH_SUCCESS;
+    TRY(make_qparams_launch<T>(h, nullptr, MGH_ABS, 1.0, s, 0, 1, nullptr, st));
+    HIP_TRY(hipMemcpyAsync(d_norm_out, DS<T>(h)->normval, sizeof(T), hipMemcpyDeviceToDevice, st));
+    return MGH_SUCCESS;
+  });
 }
 
 int mgh_norm_stream_begin(mgh_hierarchy *h, void *stream) {
@@ -3339,15 +3320,17 @@ int mgh_norm_stream_begin(mgh_hierarchy *h, void *stream) {
   if (!fusedc_ok(h) || h->force_v1)
     return fail(MGH_ERR_UNSUPPORTED_DIMENSION, "streamed norm: only in front of the fused 3-D / 4-D path");
   HIP_TRY(hipSetDevice(h->device));
-  return DISPATCH(h, norm_stream_begin<float>(h, (hipStream_t)stream), norm_stream_begin<double>(h, (hipStream_t)stream));
+  return with_type(h, [&](auto t) { return norm_stream_begin<decltype(t)>(h, (hipStream_t)stream); });
 }
 
 int mgh_norm_stream_add(mgh_hierarchy *h, const void *d_part, uint64_t count, double s, int cold, void *stream) {
   if (!h || (!d_part && count)) return fail(MGH_ERR_INVALID_ARGUMENT, "null argument");
   if (h->has_ld[0]) return fail(MGH_ERR_INVALID_ARGUMENT, "mgh_norm_stream_add takes parts of a dense array (mgh_set_ld is set)");
   HIP_TRY(hipSetDevice(h->device));
-  return DISPATCH(h, norm_stream_add<float>(h, (const float *)d_part, count, s, cold, (hipStream_t)stream),
-                  norm_stream_add<double>(h, (const double *)d_part, count, s, cold, (hipStream_t)stream));
+  return with_type(h, [&](auto t) {
+    using T = decltype(t);
+    return norm_stream_add<T>(h, (const T *)d_part, count, s, cold, (hipStream_t)stream);
+  });
 }
 
 int mgh_decompose_quantize_dn(mgh_hierarchy *h, const void *d_data, int error_bound_type,
@@ -3358,26 +3341,15 @@ int mgh_decompose_quantize_dn(mgh_hierarchy *h, const void *d_data, int error_bo
   if (!h || !d_data || !d_quantized || !d_norm) return fail(MGH_ERR_INVALID_ARGUMENT, "null argument");
   if (!fusedc_ok(h) || h->force_v1)
     return fail(MGH_ERR_UNSUPPORTED_DIMENSION, "device-norm entry point needs the fused 3-D / 4-D path");
-  if (prep_huffman && (!d_outlier_count || (outlier_capacity && (!d_outlier_idx || !d_outlier_val))))
-    return fail(MGH_ERR_INVALID_ARGUMENT, "outlier buffers required with prep_huffman");
+  TRY(outlier_args(prep_huffman, d_outlier_count, d_outlier_idx, d_outlier_val, outlier_capacity));
   HIP_TRY(hipSetDevice(h->device));
-  if (ld_wanted(h, d_data, nullptr))
-    return ld_entry(h, d_data, nullptr, true, stream, [&](const void *i, void *) {
-      return mgh_decompose_quantize_dn(h, i, error_bound_type, tol, s, d_norm, num_subdomains, dict_size,
-                                       prep_huffman, d_quantized, d_outlier_count, d_outlier_idx, d_outlier_val,
-                                       outlier_capacity, stream);
-    });
-  return DISPATCH(h,
-                  fused_q_entry_device<float>(h, (const float *)d_data, error_bound_type, tol, s,
-                                              (const float *)d_norm, 1, num_subdomains, nullptr,
-                                              dict_size, prep_huffman, d_quantized, d_outlier_count,
-                                              d_outlier_idx, d_outlier_val, outlier_capacity,
-                                              (hipStream_t)stream),
-                  fused_q_entry_device<double>(h, (const double *)d_data, error_bound_type, tol, s,
-                                               (const double *)d_norm, 1, num_subdomains, nullptr,
-                                               dict_size, prep_huffman, d_quantized, d_outlier_count,
-                                               d_outlier_idx, d_outlier_val, outlier_capacity,
-                                               (hipStream_t)stream));
+  return with_type(h, [&](auto t) {
+    using T = decltype(t);
+    return fused_q_entry_device<T>(h, (const T *)d_data, caller_layout(h, MGH_LD_IN), error_bound_type, tol, s,
+                                   (const T *)d_norm, 1, num_subdomains, nullptr, dict_size, prep_huffman,
+                                   d_quantized, d_outlier_count, d_outlier_idx, d_outlier_val, outlier_capacity,
+                                   (hipStream_t)stream);
+  });
 }
 
 int mgh_dequantize_recompose(mgh_hierarchy *h, int64_t *d_quantized, int ebtype, double tol,
@@ -3385,27 +3357,13 @@ int mgh_dequantize_recompose(mgh_hierarchy *h, int64_t *d_quantized, int ebtype,
                              const uint64_t *d_outlier_idx, const int64_t *d_outlier_val,
                              uint64_t outlier_count, void *d_data, void *stream) {
   if (!h || !d_data || !d_quantized) return fail(MGH_ERR_INVALID_ARGUMENT, "null argument");
-  if (ld_wanted(h, nullptr, d_data))
-    return ld_entry(h, nullptr, d_data, fusedc_ok(h) && !h->force_v1, stream, [&](const void *, void *o) {
-      return mgh_dequantize_recompose(h, d_quantized, ebtype, tol, s, norm, dict_size, prep_huffman, d_outlier_idx,
-                                      d_outlier_val, outlier_count, o, stream);
-    });
-  if (fusedc_ok(h) && !h->force_v1) {
-    HIP_TRY(hipSetDevice(h->device));
-    return DISPATCH(h,
-                    dequantize_recompose_fused<float>(h, d_quantized, ebtype, tol, s, norm, dict_size,
-                                                      prep_huffman, d_outlier_idx, d_outlier_val,
-                                                      outlier_count, (float *)d_data,
-                                                      (hipStream_t)stream),
-                    dequantize_recompose_fused<double>(h, d_quantized, ebtype, tol, s, norm,
-                                                       dict_size, prep_huffman, d_outlier_idx,
-                                                       d_outlier_val, outlier_count,
-                                                       (double *)d_data, (hipStream_t)stream));
-  }
-  int rc = mgh_dequantize(h, d_quantized, ebtype, tol, s, norm, dict_size, prep_huffman,
-                          d_outlier_idx, d_outlier_val, outlier_count, d_data, stream);
-  if (rc != MGH_SUCCESS) return rc;
-  return mgh_recompose(h, d_data, d_data, stream);
+  HIP_TRY(hipSetDevice(h->device));
+  return with_type(h, [&](auto t) {
+    using T = decltype(t);
+    return dequantize_recompose<T>(h, d_quantized, ebtype, tol, s, norm, dict_size, prep_huffman, d_outlier_idx,
+                                   d_outlier_val, outlier_count, (T *)d_data, caller_layout(h, MGH_LD_OUT),
+                                   (hipStream_t)stream);
+  });
 }
 
 int mgh_level_nodes(const mgh_hierarchy *h, int level, int dim, uint64_t *h_idx_out, uint64_t cap) {
@@ -3420,42 +3378,26 @@ int mgh_level_nodes(const mgh_hierarchy *h, int level, int dim, uint64_t *h_idx_
 }
 
 namespace {
-// level == l_target is the existing call with a DENSE output: MGH_LD_OUT is set aside for its duration.
-// dense_in: MGH_LD_IN as well, for the calls that read no T array (integers and symbols are always dense;
-// on the staged path mgh_dequantize_recompose hands its own dense coefficients to mgh_recompose, which
-// would take them for the caller's pitched array).
-struct DenseOutScope {
-  mgh_hierarchy *h;
-  bool saved, saved_in;
-  explicit DenseOutScope(mgh_hierarchy *hh, bool dense_in = false)
-      : h(hh), saved(hh->has_ld[1]), saved_in(hh->has_ld[0]) {
-    h->has_ld[1] = false;
-    if (dense_in) h->has_ld[0] = false;
-  }
-  ~DenseOutScope() {
-    h->has_ld[1] = saved;
-    h->has_ld[0] = saved_in;
-  }
-  DenseOutScope(const DenseOutScope &) = delete;
-  DenseOutScope &operator=(const DenseOutScope &) = delete;
-};
 int level_arg(const mgh_hierarchy *h, int level) {
   if (level < 0 || level > h->L) return fail(MGH_ERR_INVALID_ARGUMENT, "level outside 0 .. l_target");
   return MGH_SUCCESS;
 }
 } // namespace
 
+// The output of these calls is the dense array of level_shape(level): MGH_LD_OUT does not apply.
+// level == l_target is the body of the call without a level, with a dense layout for the output.
 int mgh_recompose_to_level(mgh_hierarchy *h, const void *d_coeff, int level, void *d_out, void *stream) {
   if (!h || !d_out || !d_coeff) return fail(MGH_ERR_INVALID_ARGUMENT, "null argument");
   if (d_out == d_coeff) return fail(MGH_ERR_INVALID_ARGUMENT, "mgh_recompose_to_level: d_out must not be d_coeff");
   TRY(level_arg(h, level));
-  if (level == h->L) {
-    DenseOutScope dense(h);
-    return mgh_recompose(h, d_coeff, d_out, stream);
-  }
   HIP_TRY(hipSetDevice(h->device));
-  return DISPATCH(h, recompose_to_level_impl<float>(h, (const float *)d_coeff, level, (float *)d_out, (hipStream_t)stream),
-                  recompose_to_level_impl<double>(h, (const double *)d_coeff, level, (double *)d_out, (hipStream_t)stream));
+  return with_type(h, [&](auto t) {
+    using T = decltype(t);
+    const Layout in = caller_layout(h, MGH_LD_IN);
+    if (level == h->L)
+      return recompose_impl<T>(h, (const T *)d_coeff, in, (T *)d_out, dense_layout(h), (hipStream_t)stream);
+    return recompose_to_level_impl<T>(h, (const T *)d_coeff, in, level, (T *)d_out, (hipStream_t)stream);
+  });
 }
 
 int mgh_dequantize_recompose_to_level(mgh_hierarchy *h, int64_t *d_quantized, int ebtype, double tol, double s,
@@ -3466,27 +3408,20 @@ int mgh_dequantize_recompose_to_level(mgh_hierarchy *h, int64_t *d_quantized, in
   if (prep_huffman && outlier_count && (!d_outlier_idx || !d_outlier_val))
     return fail(MGH_ERR_INVALID_ARGUMENT, "null outlier list");
   TRY(level_arg(h, level));
-  if (level == h->L) {
-    DenseOutScope dense(h, true);
-    return mgh_dequantize_recompose(h, d_quantized, ebtype, tol, s, norm, dict_size, prep_huffman,
-                                            d_outlier_idx, d_outlier_val, outlier_count, d_out, stream);
-  }
   HIP_TRY(hipSetDevice(h->device));
-  if (fusedc_ok(h) && !h->force_v1)
-    return DISPATCH(h,
-                    dequantize_recompose_fused<float>(h, d_quantized, ebtype, tol, s, norm, dict_size, prep_huffman,
-                                                      d_outlier_idx, d_outlier_val, outlier_count, (float *)d_out,
-                                                      (hipStream_t)stream, level),
-                    dequantize_recompose_fused<double>(h, d_quantized, ebtype, tol, s, norm, dict_size, prep_huffman,
-                                                       d_outlier_idx, d_outlier_val, outlier_count, (double *)d_out,
-                                                       (hipStream_t)stream, level));
-  return DISPATCH(h,
-                  dequantize_recompose_box_to_level<float>(h, d_quantized, ebtype, tol, s, norm, dict_size,
-                                                           prep_huffman, d_outlier_idx, d_outlier_val, outlier_count,
-                                                           level, (float *)d_out, (hipStream_t)stream),
-                  dequantize_recompose_box_to_level<double>(h, d_quantized, ebtype, tol, s, norm, dict_size,
-                                                            prep_huffman, d_outlier_idx, d_outlier_val, outlier_count,
-                                                            level, (double *)d_out, (hipStream_t)stream));
+  hipStream_t st = (hipStream_t)stream;
+  return with_type(h, [&](auto t) {
+    using T = decltype(t);
+    if (level == h->L)
+      return dequantize_recompose<T>(h, d_quantized, ebtype, tol, s, norm, dict_size, prep_huffman, d_outlier_idx,
+                                     d_outlier_val, outlier_count, (T *)d_out, dense_layout(h), st);
+    if (fusedc_ok(h) && !h->force_v1)
+      return dequantize_recompose_fused<T>(h, d_quantized, ebtype, tol, s, norm, dict_size, prep_huffman,
+                                           d_outlier_idx, d_outlier_val, outlier_count, (T *)d_out, dense_layout(h),
+                                           st, level);
+    return dequantize_recompose_box_to_level<T>(h, d_quantized, ebtype, tol, s, norm, dict_size, prep_huffman,
+                                                d_outlier_idx, d_outlier_val, outlier_count, level, (T *)d_out, st);
+  });
 }
 
 int mgh_dequantize_recompose_sym16_to_level(mgh_hierarchy *h, const uint16_t *d_symbols, int error_bound_type,
@@ -3499,19 +3434,13 @@ int mgh_dequantize_recompose_sym16_to_level(mgh_hierarchy *h, const uint16_t *d_
   TRY(level_arg(h, level));
   if (!mgh_sym16_supported(h))
     return fail(MGH_ERR_UNSUPPORTED_DIMENSION, "16-bit symbols: only on the fused 3-D / 4-D path");
-  if (level == h->L) {
-    DenseOutScope dense(h, true);
-    return mgh_dequantize_recompose_sym16(h, d_symbols, error_bound_type, tol, s, norm, dict_size,
-                                                  d_outlier_idx, d_outlier_val, outlier_count, d_out, stream);
-  }
   HIP_TRY(hipSetDevice(h->device));
-  return DISPATCH(h,
-                  dequantize_recompose_fused16<float>(h, d_symbols, error_bound_type, tol, s, norm, dict_size,
-                                                      d_outlier_idx, d_outlier_val, outlier_count, (float *)d_out,
-                                                      (hipStream_t)stream, level),
-                  dequantize_recompose_fused16<double>(h, d_symbols, error_bound_type, tol, s, norm, dict_size,
-                                                       d_outlier_idx, d_outlier_val, outlier_count, (double *)d_out,
-                                                       (hipStream_t)stream, level));
+  return with_type(h, [&](auto t) {
+    using T = decltype(t);
+    return dequantize_recompose_fused16<T>(h, d_symbols, error_bound_type, tol, s, norm, dict_size, d_outlier_idx,
+                                           d_outlier_val, outlier_count, (T *)d_out, dense_layout(h),
+                                           (hipStream_t)stream, level == h->L ? -1 : level);
+  });
 }
 
 #ifdef MGH_PHASE_TIMING

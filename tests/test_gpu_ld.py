@@ -146,6 +146,135 @@ def test_every_stage_on_pitched_arrays_equals_the_dense_result(shape, dt, pad_mi
     h.close()
 
 
+def _nan_array(torch, u, ld):
+    """A pitched allocation for a call to write: all NaN."""
+    return torch.full([u.shape[0]] + list(ld[1:]), float("nan"), dtype=u.dtype, device=u.device)
+
+
+def _same_q(torch, a, b):
+    """Two decompose_quantize results (q, outlier_idx, outlier_val, count, norm): the same integers,
+    the same SET of outliers (the list is filled by atomics), the same count and norm."""
+    return (torch.equal(a[0], b[0]) and a[3] == b[3] and a[4] == b[4]
+            and sorted(zip(a[1].tolist(), a[2].tolist())) == sorted(zip(b[1].tolist(), b[2].tolist())))
+
+
+def _bounds(mg, nrm):
+    """decompose_quantize with a REL bound and no norm, a REL bound and the norm, an ABS bound:
+    (error_bound_type, tol, norm)."""
+    return [(mg.REL, 1e-3, 0.0), (mg.REL, 1e-3, nrm), (mg.ABS, 1e-3 * nrm, 0.0)]
+
+
+@pytest.mark.parametrize("pad_mid", [False, True])
+@pytest.mark.parametrize("dt", [np.float32, np.float64])
+@pytest.mark.parametrize("shape", [s for s, _ in SHAPES], ids=[n for _, n in SHAPES])
+def test_one_role_pitched_the_other_dense_on_the_combined_calls(shape, dt, pad_mid):
+    """Only MGH_LD_IN or only MGH_LD_OUT set: the combined calls run stages on buffers of the
+    hierarchy (coefficients between decomposition and quantizer, the in-place array of the staged
+    decompression), and those are dense whatever the caller's arrays are."""
+    torch, mg = _mods()
+    inf = float("inf")
+    u = torch.from_numpy(smooth_field(shape, dt, noise=1e-3)).cuda()
+    ld = _ld(shape, np.dtype(dt).itemsize, pad_mid)
+    h = mg.Hierarchy(shape, dt)
+    nrm = h.norm(u, inf)
+    dense = [h.decompose_quantize(u, eb, tol, inf, norm=n, dict_size=64) for eb, tol, n in _bounds(mg, nrm)]
+    fq, foi, fov, _, fn = dense[0]
+    back = h.dequantize_recompose(fq.clone(), mg.REL, 1e-3, inf, fn, dict_size=64, outlier_idx=foi, outlier_val=fov)
+
+    # ---- pitched input, dense output ----
+    up = _pitched(torch, u, ld)
+    h.set_ld(mg.LD_IN, ld)
+    for (eb, tol, n), want in zip(_bounds(mg, nrm), dense):
+        assert _same_q(torch, h.decompose_quantize(up, eb, tol, inf, norm=n, dict_size=64), want)
+    out = torch.empty_like(u)
+    h.dequantize_recompose(fq.clone(), mg.REL, 1e-3, inf, fn, dict_size=64, outlier_idx=foi, outlier_val=fov, out=out)
+    assert torch.equal(out, back)
+    assert _padding_untouched(torch, up, shape)
+    h.set_ld(mg.LD_IN, None)
+
+    # ---- dense input, pitched output (decompose_quantize has no T output here) ----
+    h.set_ld(mg.LD_OUT, ld)
+    for (eb, tol, n), want in zip(_bounds(mg, nrm), dense):
+        assert _same_q(torch, h.decompose_quantize(u, eb, tol, inf, norm=n, dict_size=64), want)
+    op = _nan_array(torch, u, ld)
+    h.dequantize_recompose(fq.clone(), mg.REL, 1e-3, inf, fn, dict_size=64, outlier_idx=foi, outlier_val=fov, out=op)
+    assert torch.equal(_valid(op, shape), back) and _padding_untouched(torch, op, shape)
+
+    # ---- and dense again ----
+    h.set_ld(mg.LD_OUT, None)
+    assert _same_q(torch, h.decompose_quantize(u, mg.REL, 1e-3, inf, dict_size=64), dense[0])
+    assert torch.equal(h.dequantize_recompose(fq.clone(), mg.REL, 1e-3, inf, fn, dict_size=64, outlier_idx=foi,
+                                              outlier_val=fov), back)
+    h.close()
+
+
+@pytest.mark.parametrize("pad_mid", [False, True])
+@pytest.mark.parametrize("dt", [np.float32, np.float64])
+@pytest.mark.parametrize("shape", [s for s, _ in SHAPES], ids=[n for _, n in SHAPES])
+def test_both_roles_with_different_pitches_and_the_setting_survives(shape, dt, pad_mid):
+    """Input and output pitched differently (dimension D-2 padded in one of them only), every call
+    out of place. Then: a refused call leaves nothing behind -- the next pitched call honours the
+    setting, and a handle set back to dense gives the dense results."""
+    torch, mg = _mods()
+    inf = float("inf")
+    u = torch.from_numpy(smooth_field(shape, dt, noise=1e-3)).cuda()
+    ld_in = _ld(shape, np.dtype(dt).itemsize, pad_mid)
+    ld_out = _ld(shape, np.dtype(dt).itemsize, not pad_mid)
+    h = mg.Hierarchy(shape, dt)
+    coef = h.decompose(u)
+    rec = h.recompose(coef)
+    staged_coef = torch.empty_like(u)
+    staged = h.decompose_quantize(u, mg.REL, 1e-3, inf, dict_size=64, coeff_out=staged_coef)
+    fused = h.decompose_quantize(u, mg.REL, 1e-3, inf, dict_size=64)
+    fq, foi, fov, _, fn = fused
+    back = h.dequantize_recompose(fq.clone(), mg.REL, 1e-3, inf, fn, dict_size=64, outlier_idx=foi, outlier_val=fov)
+
+    up = _pitched(torch, u, ld_in)
+    cp = _pitched(torch, coef, ld_in)
+    h.set_ld(mg.LD_IN, ld_in)
+    h.set_ld(mg.LD_OUT, ld_out)
+
+    def written(op, want):
+        return torch.equal(_valid(op, shape), want) and _padding_untouched(torch, op, shape)
+
+    op = _nan_array(torch, u, ld_out)
+    h.decompose(up, out=op)
+    assert written(op, coef)
+    op = _nan_array(torch, u, ld_out)
+    h.recompose(cp, out=op)
+    assert written(op, rec)
+    op = _nan_array(torch, u, ld_out)
+    g = h.decompose_quantize(up, mg.REL, 1e-3, inf, dict_size=64, coeff_out=op)
+    assert _same_q(torch, g, staged) and written(op, staged_coef)
+    assert _same_q(torch, h.decompose_quantize(up, mg.REL, 1e-3, inf, dict_size=64), fused)
+    op = _nan_array(torch, u, ld_out)
+    h.dequantize_recompose(fq.clone(), mg.REL, 1e-3, inf, fn, dict_size=64, outlier_idx=foi, outlier_val=fov, out=op)
+    assert written(op, back)
+    assert _padding_untouched(torch, up, shape) and _padding_untouched(torch, cp, shape)
+
+    # ---- refused calls (MGH_ERR_INVALID_ARGUMENT = -1) with both roles set ----
+    with pytest.raises(mg.MgardHipError, match="error -1:"):
+        h.decompose_quantize_sym16(up, mg.REL, 1e-3, inf, dict_size=70000)
+    with pytest.raises(mg.MgardHipError, match="error -1:"):   # (parts of a pitched array)
+        mg._check(mg.load_library().mgh_norm_stream_add(h._h, up.data_ptr(), up.numel(), inf, 0, mg._stream()))
+    op = _nan_array(torch, u, ld_out)
+    h.decompose(up, out=op)
+    assert written(op, coef)
+    op = _nan_array(torch, u, ld_out)
+    h.dequantize_recompose(fq.clone(), mg.REL, 1e-3, inf, fn, dict_size=64, outlier_idx=foi, outlier_val=fov, out=op)
+    assert written(op, back)
+    assert _same_q(torch, h.decompose_quantize(up, mg.REL, 1e-3, inf, dict_size=64), fused)
+
+    # ---- and dense again ----
+    h.set_ld(mg.LD_IN, None)
+    h.set_ld(mg.LD_OUT, None)
+    assert torch.equal(h.decompose(u), coef) and torch.equal(h.recompose(coef), rec)
+    assert _same_q(torch, h.decompose_quantize(u, mg.REL, 1e-3, inf, dict_size=64), fused)
+    assert torch.equal(h.dequantize_recompose(fq.clone(), mg.REL, 1e-3, inf, fn, dict_size=64, outlier_idx=foi,
+                                              outlier_val=fov), back)
+    h.close()
+
+
 def test_set_ld_arguments():
     torch, mg = _mods()
     h = mg.Hierarchy((20, 30, 40), np.float32)
