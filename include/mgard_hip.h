@@ -253,6 +253,26 @@ int mgh_dequantize_recompose_sym16_to_level(mgh_hierarchy *h, const uint16_t *d_
                                             uint64_t dict_size, const uint64_t *d_outlier_idx,
                                             const int64_t *d_outlier_val, uint64_t outlier_count,
                                             int level, void *d_out, void *stream);
+/* The same from the HEAD of a level-linearised array (mgh_level_linearize; what a reorder = 1 record
+ * holds): its first N_level = prod(level_shape(level)) integers ARE the corner box of `level`, level
+ * by level, so nothing behind them is needed.
+ * mgh_level_box_from_linear: the permutation on its own -- d_linear [at least N_level] to the compact
+ * corner box d_box_out [N_level], reordered layout, dense in level_shape(level); nothing at or behind
+ * position N_level is read. level = 0 ... l_target; at l_target the result is
+ * mgh_level_linearize(inverse = 1). d_box_out must not be d_linear.
+ * mgh_dequantize_recompose_linear_to_level: d_linear holds at least the first N_level integers and no
+ * other is read. The outlier indices are LINEARISED positions (as a reorder = 1 record carries them):
+ * those at positions >= N_level are skipped, the others are written into d_linear in place before the
+ * box is made. d_out is the dense array of level_shape(level), bit-identical to
+ * mgh_level_linearize(inverse) + mgh_dequantize_recompose_to_level on the full array. No work scales
+ * with the full array; the box buffer is counted in mgh_device_bytes. */
+int mgh_level_box_from_linear(mgh_hierarchy *h, const int64_t *d_linear, int level, int64_t *d_box_out,
+                              void *stream);
+int mgh_dequantize_recompose_linear_to_level(mgh_hierarchy *h, int64_t *d_linear, int error_bound_type,
+                                             double tol, double s, double norm, uint64_t dict_size,
+                                             int prep_huffman, const uint64_t *d_outlier_idx,
+                                             const int64_t *d_outlier_val, uint64_t outlier_count,
+                                             int level, void *d_out, void *stream);
 /* HOST only: index in the finest grid of every node of `level` along `dim`, ascending
  * (level_shape(level)[dim] entries; returns their number, or a negative status). The rule is the
  * hierarchy's own coarsening, level by level: keep every second node and always the last one. With

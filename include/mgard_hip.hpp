@@ -222,6 +222,19 @@ public:
                                             outlier_count, level, level_data, queue),
           "DequantizeRecomposeToLevel");
   }
+  // ... from the head of a level-linearised array (reorder = 1): `linear` holds at least the first
+  // prod(level_shape(level)) integers, the outlier indices are linearised positions.
+  void DequantizeRecomposeLinearToLevel(T *level_data, int level, int64_t *linear, error_bound_type ebtype, T tol,
+                                        T s, T norm, SIZE outlier_count, void *queue = nullptr) {
+    check(mgh_dequantize_recompose_linear_to_level(hierarchy_->handle(), linear, (int)ebtype, (double)tol,
+                                                   (double)s, (double)norm, config_.huff_dict_size,
+                                                   config_.prep_huffman ? 1 : 0, outlier_idx_, outliers_,
+                                                   outlier_count, level, level_data, queue),
+          "DequantizeRecomposeLinearToLevel");
+  }
+  void LevelBoxFromLinear(const int64_t *linear, int level, int64_t *box, void *queue = nullptr) {
+    check(mgh_level_box_from_linear(hierarchy_->handle(), linear, level, box, queue), "LevelBoxFromLinear");
+  }
   void DequantizeRecomposeSym16ToLevel(T *level_data, int level, error_bound_type ebtype, T tol, T s, T norm,
                                        const uint16_t *symbols, SIZE outlier_count, void *queue = nullptr) {
     check(mgh_dequantize_recompose_sym16_to_level(hierarchy_->handle(), symbols, (int)ebtype, (double)tol,

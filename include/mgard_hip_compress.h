@@ -177,8 +177,13 @@ int mgh_infer_data_type(const void *compressed_data, size_t compressed_size, int
  * mgh_decompress_level: like mgh_decompress (same memory-space rules: host or device stream, output
  * allocated in the stream's space unless pre-allocated), the output being the dense array of
  * mgh_infer_level_shape(level): mgh_dequantize_recompose_to_level of the decoded integers.
- * level == l_target returns the bytes of mgh_decompress. The lossless stage still decodes the whole
- * record. A record that was stored RAW (the data itself, because the lossless stage did not shrink
+ * level == l_target returns the bytes of mgh_decompress. For a reorder = 0 record the lossless stage
+ * decodes the whole record (the box of a level is spread over every chunk). A reorder = 1 record is
+ * level-linearised: below l_target only its leading ceil(N_level / huff_block_size) Huffman chunks are
+ * decoded (mgh_lossless_decompress_prefix) and the level is made from that head
+ * (mgh_dequantize_recompose_linear_to_level) -- of a record in host memory only the head, the code
+ * units of those chunks, the outlier lists and the synchronisation entries of those chunks are moved.
+ * mgh_last_decompress_stats tells what the last call did. A record that was stored RAW (the data itself, because the lossless stage did not shrink
  * it) is returned as it is at l_target; below l_target it costs a full decomposition and
  * quantization with the header's bound first, so that the level is the one a Huffman record gives. */
 int mgh_infer_level_shape(const void *compressed_data, size_t compressed_size, const mgh_config *config,
@@ -187,6 +192,20 @@ int mgh_infer_level_nodes(const void *compressed_data, size_t compressed_size, c
                           int level, int dim, uint64_t *h_idx_out, uint64_t cap);
 int mgh_decompress_level(const void *compressed_data, size_t compressed_size, int level,
                          void **decompressed_data, const mgh_config *config, int output_pre_allocated);
+
+/* What the last mgh_decompress* call of the calling thread did in its lossless stage (thread-local;
+ * zeros before the first call; a failed call leaves what it had counted). Raw records count in
+ * subdomains and record_bytes only. */
+typedef struct mgh_decompress_stats {
+  uint64_t subdomains;
+  uint64_t chunks_total;       /* Huffman chunks of the records */
+  uint64_t chunks_decoded;     /* ... of which decoded */
+  uint64_t symbols_decoded;    /* integers the decoders wrote */
+  uint64_t record_bytes;       /* bytes of the records (Huffman_Zstd: of the frames) */
+  uint64_t record_bytes_moved; /* bytes of the records copied to the device or within it; code
+                                  units decoded in place count 0 */
+} mgh_decompress_stats;
+int mgh_last_decompress_stats(mgh_decompress_stats *out);
 
 /* Stream contract of mgh_compress / mgh_decompress: the calls return when the result is
  * complete (they synchronise their own pipeline streams before returning). The pipeline streams
@@ -271,6 +290,19 @@ int mgh_lossless_decompress(mgh_lossless_ctx *ctx, const uint8_t *h_payload, uin
                             int lossless, int64_t *d_quantized, uint64_t n,
                             const uint64_t **d_outlier_idx_out, const int64_t **d_outlier_val_out,
                             uint64_t *outlier_count_out, void *stream);
+
+/* The same for the first n_prefix integers only: chunks 0 ... ceil(n_prefix / chunk) - 1 are decoded,
+ * d_quantized[0 ... min(n, chunks * chunk)) is written and nothing behind it (the buffer need not be
+ * larger). The record's head is validated as a whole; the chunk-table entries are checked for the
+ * chunks decoded. The outlier lists are delivered whole (they are not sorted). Of a record in HOST
+ * memory only the head, the code units up to the end of the last needed chunk (plus the one unit the
+ * decoders peek at), the outlier lists and the synchronisation entries of the needed chunks are
+ * moved; a record on the decoding device is read in place; a Huffman_Zstd frame is inflated whole on
+ * the host. n_prefix = n (or larger) is mgh_lossless_decompress; n_prefix = 0 is an error. */
+int mgh_lossless_decompress_prefix(mgh_lossless_ctx *ctx, const uint8_t *payload, uint64_t size,
+                                   int lossless, int64_t *d_quantized, uint64_t n, uint64_t n_prefix,
+                                   const uint64_t **d_outlier_idx_out, const int64_t **d_outlier_val_out,
+                                   uint64_t *outlier_count_out, void *stream);
 
 #ifdef __cplusplus
 }

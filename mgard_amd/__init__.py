@@ -31,6 +31,7 @@ SYMBOLS = [
     "mgh_set_ld",
     "mgh_recompose_to_level", "mgh_dequantize_recompose_to_level",
     "mgh_dequantize_recompose_sym16_to_level", "mgh_level_nodes",
+    "mgh_level_box_from_linear", "mgh_dequantize_recompose_linear_to_level",
 ]
 
 
@@ -101,6 +102,9 @@ def load_library():
                                                     u64, C.c_int, vp, vp, u64, C.c_int, vp, vp]
     L.mgh_dequantize_recompose_sym16_to_level.argtypes = [vp, vp, C.c_int, C.c_double, C.c_double,
                                                           C.c_double, u64, vp, vp, u64, C.c_int, vp, vp]
+    L.mgh_level_box_from_linear.argtypes = [vp, vp, C.c_int, vp, vp]
+    L.mgh_dequantize_recompose_linear_to_level.argtypes = [vp, vp, C.c_int, C.c_double, C.c_double, C.c_double,
+                                                           u64, C.c_int, vp, vp, u64, C.c_int, vp, vp]
     L.mgh_level_nodes.argtypes = [vp, C.c_int, C.c_int, u64p, u64]
     L.mgh_stream_calibrate.argtypes = [C.c_int, vp, vp, vp, u64, C.c_int, C.POINTER(C.c_double), vp]
     _lib = L
@@ -412,6 +416,45 @@ class Hierarchy:
         _check(load_library().mgh_level_linearize(
             self._h, self._chk(q, torch.int64), C.c_void_p(out.data_ptr()), int(inverse),
             C.c_void_p(outlier_idx.data_ptr() if n else 0), None, n, 0, _stream()))
+        return out
+
+    def _linear_head(self, lin, level):
+        import torch
+        need = 1
+        for e in self.level_shape(level):
+            need *= int(e)
+        if not (lin.is_cuda and lin.dtype == torch.int64 and lin.is_contiguous() and lin.numel() >= need):
+            raise ValueError("expected a contiguous cuda int64 tensor of at least %d elements "
+                             "(the head of the level-linearised array)" % need)
+        return need
+
+    def level_box_from_linear(self, lin, level, out=None):
+        """mgh_level_box_from_linear: the compact corner box of `level` (reordered layout, dense in
+        level_shape(level)) out of the first prod(level_shape(level)) integers of a level-linearised
+        array; `lin` need not be longer than that."""
+        import torch
+        need = self._linear_head(lin, level)
+        if out is None:
+            out = torch.empty(tuple(int(e) for e in self.level_shape(level)), dtype=torch.int64, device=lin.device)
+        elif not (out.is_cuda and out.dtype == torch.int64 and out.is_contiguous() and out.numel() >= need):
+            raise ValueError("out: expected a contiguous cuda int64 tensor of at least %d elements" % need)
+        _check(load_library().mgh_level_box_from_linear(
+            self._h, C.c_void_p(lin.data_ptr()), int(level), C.c_void_p(out.data_ptr()), _stream()))
+        return out
+
+    def dequantize_recompose_linear(self, lin, ebtype, tol, s, norm, dict_size=8192, prep_huffman=True,
+                                    outlier_idx=None, outlier_val=None, out=None, level=None):
+        """mgh_dequantize_recompose_linear_to_level: `lin` holds (at least) the head of the
+        level-linearised array that is the box of `level` (default: l_target); the outlier indices are
+        linearised positions, those inside the head are written into `lin`."""
+        level = self.l_target if level is None else int(level)
+        self._linear_head(lin, level)
+        n = 0 if outlier_idx is None else int(outlier_idx.numel())
+        out = self._level_out(level, out, lin.device)
+        _check(load_library().mgh_dequantize_recompose_linear_to_level(
+            self._h, C.c_void_p(lin.data_ptr()), ebtype, tol, s, norm, dict_size, int(prep_huffman),
+            C.c_void_p(outlier_idx.data_ptr() if n else 0), C.c_void_p(outlier_val.data_ptr() if n else 0),
+            n, level, C.c_void_p(out.data_ptr()), _stream()))
         return out
 
     # ---- per-kernel timing (HIP events on the launch stream) ----

@@ -2282,7 +2282,9 @@ template <typename T>
 int dequantize_recompose_fused(mgh_hierarchy *h, int64_t *q, int ebtype, double tol, double s,
                                double norm, uint64_t dict_size, int prep_huffman,
                                const uint64_t *oidx, const int64_t *oval, uint64_t ocount, T *data,
-                               const Layout &out, hipStream_t st, int stop = -1) {
+                               const Layout &out, hipStream_t st, int stop = -1, const size_t *box_m = nullptr) {
+  // box_m (with stop >= 0): q is the COMPACT corner box of the stop level, dense in these extents
+  // (mgh_dequantize_recompose_linear_to_level), not the full array
   auto *ds = DS<T>(h);
   auto *hh = HH<T>(h);
   const int L = h->L;
@@ -2307,7 +2309,14 @@ int dequantize_recompose_fused(mgh_hierarchy *h, int64_t *q, int ebtype, double 
   A.half = prep_huffman ? (int64_t)(dict_size / 2) : 0;
   std::vector<T> level_qv(L + 1);
   for (int l = 0; l <= L; l++) level_qv[l] = qz[l] * (calc_vol ? hh->level_volume(l, true) : (T)1);
-  if (h->D == 4) return recompose_levels4<T, int64_t>(h, A, level_qv, data, st, nullptr, 0, 1, stop);
+  size_t sT = 0;
+  if (box_m) {
+    const int D = h->D;
+    A.dJ = box_m[D - 1];
+    A.dI = box_m[D - 2] * box_m[D - 1];
+    if (D == 4) sT = box_m[1] * box_m[2] * box_m[3];
+  }
+  if (h->D == 4) return recompose_levels4<T, int64_t>(h, A, level_qv, data, st, nullptr, sT, 1, stop);
   return recompose_levels<T, int64_t>(h, A, level_qv, data, out, st, nullptr, 1, stop);
 }
 
@@ -2531,11 +2540,21 @@ int recompose_to_level_impl(mgh_hierarchy *h, const T *coeff, const Layout &in, 
 template <typename T>
 int dequantize_recompose_box_to_level(mgh_hierarchy *h, int64_t *q, int ebtype, double tol, double s, double norm,
                                       uint64_t dict_size, int prep_huffman, const uint64_t *oidx,
-                                      const int64_t *oval, uint64_t ocount, int level, T *out, hipStream_t st) {
+                                      const int64_t *oval, uint64_t ocount, int level, T *out, hipStream_t st,
+                                      bool compact = false) {
+  // compact: q is the compact corner box of the level itself (dense in level_shape(level), outliers
+  // already in it), read with its own strides
   auto *ds = DS<T>(h);
   TRY(upload_quantizers<T>(h, ebtype, tol, s, norm, false, st));
-  const LevelBox lb = level_box_of<T>(h, level, dense_layout(h));
-  if (prep_huffman && ocount) {
+  LevelBox lb = level_box_of<T>(h, level, dense_layout(h));
+  if (compact) {
+    uint64_t bs = 1;
+    for (int d = h->D - 1; d >= 0; d--) {
+      lb.ss[d] = bs;
+      bs *= lb.m[d];
+    }
+  }
+  if (prep_huffman && ocount && !compact) {
     TRY(launch(h, "outlier_restore", st, [&] {
       k_outlier_restore_in_box<<<(unsigned)((ocount + 255) / 256), 256, 0, st>>>(q, lb, oidx, oval, ocount);
     }));
@@ -3378,6 +3397,59 @@ int mgh_level_nodes(const mgh_hierarchy *h, int level, int dim, uint64_t *h_idx_
 }
 
 namespace {
+// the level shapes and level marks the linearisation kernels read (kernels_v1.hpp)
+const int *lin_meta(mgh_hierarchy *h, mgh::LinMeta &m) {
+  const int *marks = nullptr;
+  auto fill = [&](auto *hh, auto *ds) {
+    m.D = hh->D;
+    m.L = hh->L;
+    for (int d = 0; d < hh->D; d++) {
+      m.shape[d] = (uint32_t)hh->shape[d];
+      m.markoff[d] = ds->qmeta.markoff[d];
+      for (int l = 0; l <= hh->L; l++) m.lshape[l][d] = (uint32_t)hh->level_shape[l][d];
+    }
+    marks = ds->marks;
+  };
+  if (h->dtype == MGH_FLOAT) fill(HH<float>(h), DS<float>(h));
+  else fill(HH<double>(h), DS<double>(h));
+  return marks;
+}
+
+// The compact corner box of `level` (dense in level_shape(level)) out of the first N_level integers
+// of a level-linearised array: k_box_from_linear, one wave per piece of a run of the stream.
+int box_from_linear(mgh_hierarchy *h, const int64_t *lin, int level, int64_t *box, hipStream_t st) {
+  if (h->L + 1 > mgh::kLinMaxLevels + 1) return fail(MGH_ERR_INVALID_ARGUMENT, "too many levels");
+  mgh::LinMeta m{};
+  (void)lin_meta(h, m);
+  mgh::LinBox B{};
+  B.level = level;
+  const int D = h->D;
+  uint64_t bs = 1;
+  for (int d = D - 1; d >= 0; d--) {
+    B.bs[d] = bs;
+    bs *= m.lshape[level][d];
+  }
+  for (int j = 0; j <= level; j++) {
+    uint64_t rows = 1;
+    for (int d = 0; d < D - 1; d++) rows *= m.lshape[j][d];
+    const uint64_t units = rows * ((m.lshape[j][D - 1] + kLevelBoxPiece - 1) / kLevelBoxPiece);
+    if (units >= ((uint64_t)1 << 32)) return fail(MGH_ERR_INVALID_ARGUMENT, "level box too large");
+    B.unit0[j + 1] = B.unit0[j] + units;
+  }
+  const unsigned grid = (unsigned)std::min<uint64_t>((B.unit0[level + 1] + 3) / 4, 256 * 32);
+  return launch(h, "box_from_linear", st, [&] { mgh::k_box_from_linear<<<grid, 256, 0, st>>>(m, B, lin, box); });
+}
+
+uint64_t level_elems(const mgh_hierarchy *h, int level) {
+  uint64_t n = 1;
+  auto f = [&](auto *hh) {
+    for (int d = 0; d < h->D; d++) n *= hh->level_shape[level][d];
+  };
+  if (h->dtype == MGH_FLOAT) f(HH<float>(h));
+  else f(HH<double>(h));
+  return n;
+}
+
 int level_arg(const mgh_hierarchy *h, int level) {
   if (level < 0 || level > h->L) return fail(MGH_ERR_INVALID_ARGUMENT, "level outside 0 .. l_target");
   return MGH_SUCCESS;
@@ -3421,6 +3493,56 @@ int mgh_dequantize_recompose_to_level(mgh_hierarchy *h, int64_t *d_quantized, in
                                            st, level);
     return dequantize_recompose_box_to_level<T>(h, d_quantized, ebtype, tol, s, norm, dict_size, prep_huffman,
                                                 d_outlier_idx, d_outlier_val, outlier_count, level, (T *)d_out, st);
+  });
+}
+
+int mgh_level_box_from_linear(mgh_hierarchy *h, const int64_t *d_linear, int level, int64_t *d_box_out, void *stream) {
+  if (!h || !d_linear || !d_box_out || d_linear == d_box_out)
+    return fail(MGH_ERR_INVALID_ARGUMENT, "mgh_level_box_from_linear: null or aliasing argument");
+  TRY(level_arg(h, level));
+  HIP_TRY(hipSetDevice(h->device));
+  return box_from_linear(h, d_linear, level, d_box_out, (hipStream_t)stream);
+}
+
+// The head of a level-linearised array (a reorder = 1 record) to the dense array of `level`: the
+// outliers of the head written in place, the compact box of the level made from it (ds->qbox), and
+// the level loops of mgh_dequantize_recompose_to_level on that box with the box's own strides.
+int mgh_dequantize_recompose_linear_to_level(mgh_hierarchy *h, int64_t *d_linear, int ebtype, double tol, double s,
+                                             double norm, uint64_t dict_size, int prep_huffman,
+                                             const uint64_t *d_outlier_idx, const int64_t *d_outlier_val,
+                                             uint64_t outlier_count, int level, void *d_out, void *stream) {
+  if (!h || !d_out || !d_linear) return fail(MGH_ERR_INVALID_ARGUMENT, "null argument");
+  if (prep_huffman && outlier_count && (!d_outlier_idx || !d_outlier_val))
+    return fail(MGH_ERR_INVALID_ARGUMENT, "null outlier list");
+  TRY(level_arg(h, level));
+  HIP_TRY(hipSetDevice(h->device));
+  hipStream_t st = (hipStream_t)stream;
+  return with_type(h, [&](auto t) {
+    using T = decltype(t);
+    auto *ds = DS<T>(h);
+    const uint64_t n_level = level_elems(h, level);
+    if (prep_huffman && outlier_count) {  // (linearised positions: those behind the head are skipped)
+      TRY(launch(h, "outlier_restore", st, [&] {
+        k_outlier_restore<<<(unsigned)((outlier_count + 255) / 256), 256, 0, st>>>(d_linear, n_level, d_outlier_idx,
+                                                                                  d_outlier_val, outlier_count);
+      }));
+    }
+    if (n_level > ds->qbox_elems) {  // (counted in mgh_device_bytes)
+      dev_free(h, &ds->qbox, ds->qbox_elems);
+      ds->qbox_elems = 0;
+      TRY(dev_alloc(h, &ds->qbox, n_level));
+      ds->qbox_elems = n_level;
+    }
+    TRY(box_from_linear(h, d_linear, level, ds->qbox, st));
+    if (level == h->L)
+      return dequantize_recompose<T>(h, ds->qbox, ebtype, tol, s, norm, dict_size, prep_huffman, nullptr, nullptr, 0,
+                                     (T *)d_out, dense_layout(h), st);
+    const auto &m = HH<T>(h)->level_shape[level];
+    if (fusedc_ok(h) && !h->force_v1)
+      return dequantize_recompose_fused<T>(h, ds->qbox, ebtype, tol, s, norm, dict_size, prep_huffman, nullptr,
+                                           nullptr, 0, (T *)d_out, dense_layout(h), st, level, m.data());
+    return dequantize_recompose_box_to_level<T>(h, ds->qbox, ebtype, tol, s, norm, dict_size, prep_huffman, nullptr,
+                                                nullptr, 0, level, (T *)d_out, st, /*compact=*/true);
   });
 }
 
@@ -3526,19 +3648,7 @@ int mgh_level_linearize(mgh_hierarchy *h, const int64_t *d_in, int64_t *d_out, i
   HIP_TRY(hipSetDevice(h->device));
   hipStream_t st = (hipStream_t)stream;
   mgh::LinMeta m{};
-  const int *marks = nullptr;
-  auto fill = [&](auto *hh, auto *ds) {
-    m.D = hh->D;
-    m.L = hh->L;
-    for (int d = 0; d < hh->D; d++) {
-      m.shape[d] = (uint32_t)hh->shape[d];
-      m.markoff[d] = ds->qmeta.markoff[d];
-      for (int l = 0; l <= hh->L; l++) m.lshape[l][d] = (uint32_t)hh->level_shape[l][d];
-    }
-    marks = ds->marks;
-  };
-  if (h->dtype == MGH_FLOAT) fill(HH<float>(h), DS<float>(h));
-  else fill(HH<double>(h), DS<double>(h));
+  const int *marks = lin_meta(h, m);
   const size_t total = h->total;
   const unsigned grid = (unsigned)std::min<size_t>((total + 255) / 256, 256 * 32);
   TRY(launch(h, "level_linearize", st, [&] {

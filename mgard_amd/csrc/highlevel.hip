@@ -788,9 +788,21 @@ int lossless_tag_check(mgh_lossless_ctx *c) {
   return MGH_SUCCESS;
 }
 
+// What the lossless stage of the last mgh_decompress* call of this thread did (mgh_last_decompress_stats).
+inline mgh_decompress_stats &decompress_stats() {
+  static thread_local mgh_decompress_stats s{};
+  return s;
+}
+
+// n_prefix < n (mgh_lossless_decompress_prefix): only the chunks that hold the first n_prefix
+// integers are decoded -- d_q[0 .. min(n, chunks * chunk)) is written, nothing behind it -- and of a
+// record that has to be copied only what those chunks need is moved. q_cap: elements d_q holds (the
+// record's own chunk length decides what is written; one that needs more is refused).
 int lossless_decompress(mgh_lossless_ctx *c, const uint8_t *payload, uint64_t size, int lossless,
                         int64_t *d_q, uint64_t n, uint64_t *ocount_out, hipStream_t st,
-                        bool *sym16 = nullptr, bool sync_end = true) {
+                        bool *sym16 = nullptr, bool sync_end = true, uint64_t n_prefix = ~(uint64_t)0,
+                        uint64_t q_cap = ~(uint64_t)0) {
+  if (n_prefix == 0) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "lossless_decompress: empty prefix");
   const uint8_t *p = payload;
   uint64_t psize = size;
   bool on_dev = is_device_pointer(payload);
@@ -842,6 +854,10 @@ int lossless_decompress(mgh_lossless_ctx *c, const uint8_t *payload, uint64_t si
       huffmeta_size != 2 * ((n - 1) / (uint64_t)chunk + 1))
     return hl_fail(MGH_ERR_FORMAT, "Huffman record: header does not match the subdomain");
   const size_t nchunk = huffmeta_size / 2;
+  // the chunks decoded, and the integers they hold
+  const size_t ndec = std::min<size_t>(nchunk, (size_t)((std::min<uint64_t>(n_prefix, n) - 1) / (uint64_t)chunk + 1));
+  const size_t n_dec = (size_t)std::min<uint64_t>(n, (uint64_t)ndec * (uint64_t)chunk);
+  if (n_dec > q_cap) return hl_fail(MGH_ERR_FORMAT, "Huffman record: chunk length does not match the header");
   PayloadLayout L;
   L.compute(nchunk, (size_t)dict, 0, 0);
   if (!need(0, L.ddata)) return hl_fail(MGH_ERR_FORMAT, "Huffman record truncated");
@@ -878,14 +894,23 @@ int lossless_decompress(mgh_lossless_ctx *c, const uint8_t *payload, uint64_t si
   }
   if (env_get("MGH_HUFF_SYNC_DECODE", 1) == 0) has_sync = false;  // cross-check: decode without them
   // the chunk entries must stay inside the unit array (they index it in the decoder)
+  size_t units_need = 0;  // code units up to the end of the last chunk decoded
   {
     const uint64_t *bits = reinterpret_cast<const uint64_t *>(head.data() + L.huffmeta);
     const uint64_t *ent = bits + nchunk;
-    for (size_t k = 0; k < nchunk; k++)
+    for (size_t k = 0; k < nchunk; k++) {
       if (ent[k] > units || (bits[k] + 63) / 64 > units - ent[k])
         return hl_fail(MGH_ERR_FORMAT, "Huffman record: chunk outside the code stream");
+      if (k < ndec) units_need = std::max<size_t>(units_need, ent[k] + (bits[k] + 63) / 64);
+    }
   }
+  if (ndec == nchunk) units_need = units;
   hl_debug("lossless_decompress: record head parsed");
+  mgh_decompress_stats &stats = decompress_stats();
+  stats.chunks_total += nchunk;
+  stats.chunks_decoded += ndec;
+  stats.symbols_decoded += n_dec;
+  stats.record_bytes += size;
   HL_TRY(c->bits.ensure(nchunk * 8));
   HL_TRY(c->entry.ensure(nchunk * 8));
   HL_TRY(c->tables.ensure(dbsize));
@@ -906,8 +931,8 @@ int lossless_decompress(mgh_lossless_ctx *c, const uint8_t *payload, uint64_t si
       P.bytes[P.n] = bytes;
       P.n++;
     };
-    piece(p + L.huffmeta, c->bits.p, nchunk * 8);
-    piece(p + L.huffmeta + nchunk * 8, c->entry.p, nchunk * 8);
+    piece(p + L.huffmeta, c->bits.p, ndec * 8);
+    piece(p + L.huffmeta + nchunk * 8, c->entry.p, ndec * 8);
     piece(p + L.decodebook, c->tables.p, dbsize);
     piece(p + o_oidx, c->oidx.p, ocount * 8);
     piece(p + o_oval, c->oval.p, ocount * 8);
@@ -930,12 +955,14 @@ int lossless_decompress(mgh_lossless_ctx *c, const uint8_t *payload, uint64_t si
     }
     size_t tot = 0;
     for (int i = 0; i < P.n; i++) tot += P.bytes[i];
+    stats.record_bytes_moved += tot;
     k_record_pieces<<<(unsigned)std::min<size_t>(std::max<size_t>(tot / (256 * 64), 1), 512), 256, 0, st>>>(P);
     HL_HIP(hipGetLastError());
   } else {
-    HL_HIP(hipMemcpyAsync(c->bits.p, meta_src + L.huffmeta, nchunk * 8, hipMemcpyDefault, st));
-    HL_HIP(hipMemcpyAsync(c->entry.p, meta_src + L.huffmeta + nchunk * 8, nchunk * 8, hipMemcpyDefault, st));
+    HL_HIP(hipMemcpyAsync(c->bits.p, meta_src + L.huffmeta, ndec * 8, hipMemcpyDefault, st));
+    HL_HIP(hipMemcpyAsync(c->entry.p, meta_src + L.huffmeta + nchunk * 8, ndec * 8, hipMemcpyDefault, st));
     HL_HIP(hipMemcpyAsync(c->tables.p, meta_src + L.decodebook, dbsize, hipMemcpyDefault, st));
+    stats.record_bytes_moved += 2 * ndec * 8 + dbsize;
   }
   static const bool serial_decode = env_get("MGH_HUFF_SERIAL_DECODE", 0) != 0;  // cross-check
   static const bool par_decode = env_get("MGH_HUFF_PAR_DECODE", 0) != 0;           // cross-check
@@ -961,17 +988,19 @@ int lossless_decompress(mgh_lossless_ctx *c, const uint8_t *payload, uint64_t si
   if (units_in_place) {
     d_units = (const unsigned long long *)(p + L.ddata);
   } else {
-    HL_TRY(c->units.ensure((units + 1) * 8));  // (not for units decoded in place: 8 N bytes a lane would hold for nothing)
+    HL_TRY(c->units.ensure((units_need + 1) * 8));  // (not for units decoded in place: 8 N bytes a lane would hold for nothing)
     d_units = (const unsigned long long *)c->units.p;
     // A large record in HOST memory is decoded while it arrives (below: the ring decoder's launches
     // follow the pieces of the copy, which runs on the cache's copy stream); everything else is
     // copied here, in stream order. (A record in pageable memory travels through the pinned ring.)
-    units_follow = !on_dev && ring_decode && units * 8 >= ((size_t)32 << 20) && cache_copy_stream(c->dev) &&
+    units_follow = !on_dev && ring_decode && units_need * 8 >= ((size_t)32 << 20) && cache_copy_stream(c->dev) &&
                    env_get("MGH_HL_DECODE_FOLLOWS", 1) != 0;
-    if (units && !units_follow) HL_TRY(copy_any(c->units.p, p + L.ddata, units * 8, st));
-    HL_HIP(hipMemsetAsync((char *)c->units.p + units * 8, 0, 8, st));  // (the decoder peeks one unit ahead)
+    if (units_need && !units_follow) HL_TRY(copy_any(c->units.p, p + L.ddata, units_need * 8, st));
+    HL_HIP(hipMemsetAsync((char *)c->units.p + units_need * 8, 0, 8, st));  // (the decoder peeks one unit ahead)
+    stats.record_bytes_moved += units_need * 8;
   }
   if (ocount && !pieces) {
+    stats.record_bytes_moved += 16 * ocount;
     HL_HIP(hipMemcpyAsync(c->oidx.p, p + o_oidx, ocount * 8, hipMemcpyDefault, st));
     HL_HIP(hipMemcpyAsync(c->oval.p, p + o_oval, ocount * 8, hipMemcpyDefault, st));
   }
@@ -1038,8 +1067,11 @@ int lossless_decompress(mgh_lossless_ctx *c, const uint8_t *payload, uint64_t si
           HL_TRY(aux_read(&tag, p + o_sync - 8, 8));
           if (tag != PayloadLayout::kSyncTag) return hl_fail(MGH_ERR_FORMAT, "Huffman record: outlier lists");
         }
-        HL_TRY(c->sync.ensure(sync_bytes - 8));
-        HL_HIP(hipMemcpyAsync(c->sync.p, p + o_sync, sync_bytes - 8, hipMemcpyDefault, st));
+        // (the entries of the chunks decoded)
+        const size_t sync_need = 4 * (size_t)huff::kSyncLanes * ndec;
+        HL_TRY(c->sync.ensure(sync_need));
+        HL_HIP(hipMemcpyAsync(c->sync.p, p + o_sync, sync_need, hipMemcpyDefault, st));
+        stats.record_bytes_moved += sync_need;
         d_sync = (const unsigned *)c->sync.p;
       }
     }
@@ -1060,7 +1092,7 @@ int lossless_decompress(mgh_lossless_ctx *c, const uint8_t *payload, uint64_t si
     // the per-chunk arrays, the output and the symbol count moved up by c0 chunks
     auto launch_range = [&](size_t c0, size_t c1) -> int {
       if (c1 <= c0) return MGH_SUCCESS;
-      const size_t cnt = c1 - c0, n_r = n - c0 * (size_t)chunk;
+      const size_t cnt = c1 - c0, n_r = n_dec - c0 * (size_t)chunk;
       const unsigned grid = (unsigned)((cnt + waves - 1) / waves);
       const unsigned long long *bits_r = (const unsigned long long *)c->bits.p + c0;
       const unsigned long long *ent_r = (const unsigned long long *)c->entry.p + c0;
@@ -1094,14 +1126,14 @@ int lossless_decompress(mgh_lossless_ctx *c, const uint8_t *payload, uint64_t si
       const uint64_t *h_bits = reinterpret_cast<const uint64_t *>(head.data() + L.huffmeta);
       const uint64_t *h_ent = h_bits + nchunk;
       size_t c_done = 0;
-      const size_t total_b = units * 8;
+      const size_t total_b = units_need * 8;
       const ChunkFn on_piece = [&](size_t off, size_t nb, hipEvent_t landed) -> int {
         const uint64_t have = (off + nb) / 8;  // units of the record on the device
         size_t c_hi = c_done;
         if (off + nb >= total_b) {
-          c_hi = nchunk;
+          c_hi = ndec;
         } else {
-          while (c_hi < nchunk && h_ent[c_hi] + (h_bits[c_hi] + 63) / 64 + 1 <= have) c_hi++;
+          while (c_hi < ndec && h_ent[c_hi] + (h_bits[c_hi] + 63) / 64 + 1 <= have) c_hi++;
         }
         if (c_hi > c_done) {
           HL_HIP(hipStreamWaitEvent(st, landed, 0));
@@ -1113,9 +1145,9 @@ int lossless_decompress(mgh_lossless_ctx *c, const uint8_t *payload, uint64_t si
       // (the copy stream must not run ahead of what st has queued in front: the small uploads above
       // are independent of the units; the units buffer itself is free -- the caller drained st)
       HL_TRY(copy_any(c->units.p, p + L.ddata, total_b, cache_copy_stream(c->dev), &on_piece));
-      if (c_done < nchunk) return hl_fail(MGH_ERR_DEVICE, "lossless_decompress: chunks left behind the last piece");
+      if (c_done < ndec) return hl_fail(MGH_ERR_DEVICE, "lossless_decompress: chunks left behind the last piece");
     } else {
-      HL_TRY(launch_range(0, nchunk));
+      HL_TRY(launch_range(0, ndec));
     }
     HL_HIP(hipGetLastError());
   } else if (!serial_decode && (size_t)chunk >= 1024) {
@@ -1132,15 +1164,15 @@ int lossless_decompress(mgh_lossless_ctx *c, const uint8_t *payload, uint64_t si
                          150 * 1024)
       tb--;
     const size_t lds_par = ((size_t)4 << tb) + ((size_t)dict + 3) / 4 * 8 + huff::kParWaves * 64 * huff::kParBatch * 2;
-    huff::k_decode_par<<<(unsigned)((nchunk + huff::kParWaves - 1) / huff::kParWaves),
+    huff::k_decode_par<<<(unsigned)((ndec + huff::kParWaves - 1) / huff::kParWaves),
                          64 * huff::kParWaves, lds_par, st>>>(
         d_units, (const unsigned long long *)c->bits.p,
-        (const unsigned long long *)c->entry.p, nchunk, chunk, n, dict, tb, tab, tab + 64, tab + 128, d_q);
+        (const unsigned long long *)c->entry.p, ndec, chunk, n_dec, dict, tb, tab, tab + 64, tab + 128, d_q);
   } else {
     if (sym16) *sym16 = false;
-    huff::k_decode<<<(unsigned)((nchunk + 63) / 64), 64, lds, st>>>(
+    huff::k_decode<<<(unsigned)((ndec + 63) / 64), 64, lds, st>>>(
         d_units, (const unsigned long long *)c->bits.p,
-        (const unsigned long long *)c->entry.p, nchunk, chunk, n, dict, tb, tab, tab + 64, tab + 128, d_q);
+        (const unsigned long long *)c->entry.p, ndec, chunk, n_dec, dict, tb, tab, tab + 64, tab + 128, d_q);
   }
   HL_HIP(hipGetLastError());
   hl_debug("lossless_decompress: decode launched");
@@ -2626,6 +2658,17 @@ int decompress_impl(const fmt::Header &hd, size_t meta_size, const void *compres
   };
   const uint64_t max_elems = dd.max_subdomain_elems();
   const uint64_t sub_elems = level >= 0 ? total : max_elems;  // (dense reconstruction of a subdomain)
+  // A level below l_target of a level-linearised (reorder = 1) record: its first `total` integers are
+  // the box of the level -- only the chunks that hold them are decoded, and the level is made from
+  // that head; nothing on the way is sized by the subdomain.
+  bool linear_head = false;
+  if (level >= 0 && hd.reorder) {
+    int l_target = 0;
+    HL_TRY(header_level_shape(hd, cfg, -1, &l_target, nullptr));
+    linear_head = level < l_target;
+  }
+  const uint64_t hblock = std::max<uint64_t>(hd.huff_block_size, 1);
+  const uint64_t q_elems = linear_head ? std::min<uint64_t>(max_elems, ((total - 1) / hblock + 1) * hblock) : max_elems;
   int rc;
   // device-resident output whose subdomains are contiguous slabs: reconstruct them in place
   const bool zero_copy = is_device_pointer(*out) && dd.all_contiguous();
@@ -2633,8 +2676,8 @@ int decompress_impl(const fmt::Header &hd, size_t meta_size, const void *compres
     for (int l = 0; l < nlanes; l++) {
       Lane &L = g_cache.lane[l];
       if (!zero_copy) HL_TRY(L.sub.ensure(sub_elems * elem));
-      HL_TRY(L.q.ensure(max_elems * 8));
-      if (hd.reorder) HL_TRY(L.q2.ensure(max_elems * 8));
+      HL_TRY(L.q.ensure(q_elems * 8));
+      if (hd.reorder && !linear_head) HL_TRY(L.q2.ensure(max_elems * 8));
     }
     return MGH_SUCCESS;
   };
@@ -2706,7 +2749,9 @@ int decompress_impl(const fmt::Header &hd, size_t meta_size, const void *compres
     void *sub = zero_copy ? (void *)((char *)*out + dd.linear_offset(id) * elem) : L.sub.p;
     byte_offset += csize;
     const bool raw = !((double)(n * elem) / (double)csize > 1.0);  // GPUPipelines.hpp:414-417
+    decompress_stats().subdomains++;
     if (raw) {
+      decompress_stats().record_bytes += csize;
       if (csize != n * elem) return hl_fail(MGH_ERR_FORMAT, "raw subdomain record has the wrong size");
       if (level < 0) return copy_any(sub, rec, csize, st);
     }
@@ -2722,6 +2767,7 @@ int decompress_impl(const fmt::Header &hd, size_t meta_size, const void *compres
       // data; a coarser one is what a Huffman record of this subdomain would have given -- the
       // integers of the header's bound, made here (no dictionary: prep_huffman = 0)
       if (level == mgh_l_target(h)) return copy_any(sub, rec, csize, st);
+      HL_TRY(L.q.ensure(n * 8));  // (the head of a reorder = 1 record is all the lane holds otherwise)
       HL_TRY(L.q2.ensure(n * elem));
       HL_TRY(copy_any(L.q2.p, rec, csize, st));
       HL_TRY(mgh_decompose_quantize(h, L.q2.p, local_eb, (double)local_tol, (double)s, (double)norm, nullptr,
@@ -2739,6 +2785,15 @@ int decompress_impl(const fmt::Header &hd, size_t meta_size, const void *compres
     static const long sym16_env = env_get("MGH_SYM16_DECODE", -1);
     const bool sym16_decode = sym16_env < 0 ? n >= ((uint64_t)1 << 25) : sym16_env != 0;
     bool sym16 = sym16_decode && !hd.reorder && mgh_sym16_supported(h) && hd.huff_dict_size <= 65536;
+    if (linear_head) {
+      if (level >= mgh_l_target(h)) return hl_fail(MGH_ERR_FORMAT, "header: the hierarchy of the subdomain is not the header's");
+      HL_TRY(lossless_decompress(L.ll, payload, csize, lossless, (int64_t *)L.q.p, n, &ocount, st, nullptr,
+                                 /*sync_end=*/false, /*n_prefix=*/total, /*q_cap=*/q_elems));
+      return mgh_dequantize_recompose_linear_to_level(h, (int64_t *)L.q.p, local_eb, (double)local_tol, (double)s,
+                                                      (double)norm, hd.huff_dict_size, 1,
+                                                      (const uint64_t *)L.ll->oidx.p, (const int64_t *)L.ll->oval.p,
+                                                      ocount, level, sub, st);
+    }
     HL_TRY(lossless_decompress(L.ll, payload, csize, lossless, (int64_t *)L.q.p, n, &ocount, st, &sym16,
                                /*sync_end=*/false));
     if (sym16 && level >= 0)
@@ -2888,6 +2943,7 @@ int mgh_decompress_into(const void *compressed_data, size_t compressed_size, voi
 static int decompress_entry(const void *compressed_data, size_t compressed_size, void **decompressed_data,
                             const mgh_config *config, int output_pre_allocated, size_t expect_bytes, int expect_dtype,
                             int level) {
+  decompress_stats() = mgh_decompress_stats{};
   if (!compressed_data || !decompressed_data) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "NULL argument");
   if (output_pre_allocated && !*decompressed_data) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "pre-allocated output is NULL");
   {
@@ -4082,6 +4138,29 @@ int mgh_lossless_decompress(mgh_lossless_ctx *ctx, const uint8_t *payload, uint6
   }
   if (oidx_out) *oidx_out = (const uint64_t *)ctx->oidx.p;
   if (oval_out) *oval_out = (const int64_t *)ctx->oval.p;
+  return MGH_SUCCESS;
+}
+
+int mgh_lossless_decompress_prefix(mgh_lossless_ctx *ctx, const uint8_t *payload, uint64_t size, int lossless,
+                                   int64_t *d_q, uint64_t n, uint64_t n_prefix, const uint64_t **oidx_out,
+                                   const int64_t **oval_out, uint64_t *ocount_out, void *stream) {
+  if (!ctx || !payload || !d_q || !ocount_out) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (n_prefix == 0) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "mgh_lossless_decompress_prefix: n_prefix is 0");
+  if (hipSetDevice(ctx->dev) != hipSuccess) return hl_fail(MGH_ERR_DEVICE, "hipSetDevice");
+  try {
+    HL_TRY(lossless_decompress(ctx, payload, size, lossless, d_q, n, ocount_out, (hipStream_t)stream, nullptr, true,
+                               n_prefix));
+  } catch (const std::exception &e) {
+    return hl_fail(MGH_ERR_DEVICE, e.what());
+  }
+  if (oidx_out) *oidx_out = (const uint64_t *)ctx->oidx.p;
+  if (oval_out) *oval_out = (const int64_t *)ctx->oval.p;
+  return MGH_SUCCESS;
+}
+
+int mgh_last_decompress_stats(mgh_decompress_stats *out) {
+  if (!out) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "NULL argument");
+  *out = decompress_stats();
   return MGH_SUCCESS;
 }
 

@@ -106,4 +106,96 @@ k_outlier_restore_in_box(int64_t *__restrict__ q, LevelBox B, const uint64_t *__
   if (inside) q[lin0] = val[k];
 }
 
+// ---- the box of a level straight out of the head of a level-linearised array --------------------
+// k_box_from_linear: the first N_level = prod(level_shape(level)) integers of a level-linearised
+// array (config.reorder == 1, linearized_position in kernels_v1.hpp) are the corner box of `level`,
+// level by level: level 0 in natural order, then for j = 1 .. level the fine grid of level j in
+// natural order with its coarse nodes left out. In that order a natural row of level j whose slow
+// indices include a level-j node is ONE contiguous run (coarse-f and odd-f nodes interleaved); a
+// row whose slow indices are all coarse keeps only its odd-f nodes, again one run. So the inverse
+// permutation restricted to the box streams: one wave per piece of a run, the run's first stream
+// position and its row of the box computed once (scalar work), the lanes read the stream with unit
+// stride and store the de-interleaved halves to the one or two row pieces of the box they belong
+// to. Every element of the box is written exactly once, nothing at or behind N_level is read.
+struct LinBox {
+  int level;
+  uint64_t bs[5];                       // element strides of the box (dense in level_shape(level))
+  uint64_t unit0[kLinMaxLevels + 2];    // first unit of level j (units: pieces of runs); [level + 1]: all
+};
+
+typedef int64_t lin_pair_t __attribute__((ext_vector_type(2), aligned(8)));
+
+__global__ void __launch_bounds__(256)
+k_box_from_linear(LinMeta m, LinBox B, const int64_t *__restrict__ lin, int64_t *__restrict__ box) {
+  const int lane = threadIdx.x & 63;
+  const int D = m.D;
+  const uint64_t units = B.unit0[B.level + 1];
+  const uint64_t wave0 = __builtin_amdgcn_readfirstlane((uint32_t)(blockIdx.x * 4 + (threadIdx.x >> 6)));
+  for (uint64_t u = wave0; u < units; u += (uint64_t)gridDim.x * 4) {
+    int j = 0;
+    while (u >= B.unit0[j + 1]) j++;
+    const uint32_t *F = m.lshape[j];
+    const uint32_t Ff = F[D - 1];
+    const uint32_t npiece = (Ff + kLevelBoxPiece - 1) / kLevelBoxPiece;
+    const uint32_t ul = (uint32_t)(u - B.unit0[j]);
+    uint32_t row = ul / npiece;
+    const uint32_t e0 = (ul - row * npiece) * kLevelBoxPiece;  // first stream element of the piece in its run
+    if (j == 0) {
+      // level 0: the first N_0 integers in natural order, row by row into the box
+      uint64_t off = 0;
+      const uint64_t src = (uint64_t)row * Ff;
+      for (int d = D - 2; d >= 0; d--) {
+        off += (uint64_t)(row % F[d]) * B.bs[d];
+        row /= F[d];
+      }
+      const uint32_t e1 = min(Ff, e0 + kLevelBoxPiece);
+      for (uint32_t f = e0 + lane; f < e1; f += 64) box[off + f] = lin[src + f];
+      continue;
+    }
+    const uint32_t *C = m.lshape[j - 1];
+    const uint32_t Cf = C[D - 1];
+    // natural slow coordinates of the row in level j's fine grid: its row of the box, and the part of
+    // linearized_position's sums that does not depend on the fastest coordinate
+    uint64_t off = 0, stride = Ff, cstride = Ff / 2 + 1, to = 0, co = 0, base = Cf;
+    bool mixed = false;
+    for (int d = D - 2; d >= 0; d--) {
+      const uint32_t g = row % F[d];
+      row /= F[d];
+      const bool odd = (g & 1u) && g != F[d] - 1;  // a level-j node along d
+      mixed |= odd;
+      const uint32_t idx = odd ? C[d] + (g - 1) / 2 : (g == F[d] - 1 && F[d] % 2 == 0 ? F[d] / 2 : g / 2);
+      off += (uint64_t)idx * B.bs[d];
+      to += (uint64_t)g * stride;
+      stride *= F[d];
+      if (odd) co = 0;
+      if (g) co += (uint64_t)((g - 1) / 2 + 1) * cstride;
+      cstride *= F[d] / 2 + 1;
+      base *= C[d];
+    }
+    // (an all-coarse row starts at its first odd-f node, g = 1: one element on, one coarse node before it)
+    const int64_t *s = lin + (base + to - co);
+    int64_t *dst = box + off;
+    if (mixed) {
+      // the whole natural row: nodes 2k and 2k + 1 side by side in the stream
+      const uint32_t e1 = min(Ff, e0 + kLevelBoxPiece);
+      const bool even_last = Ff % 2 == 0;  // node Ff - 1 of an even extent is the last COARSE node
+      for (uint32_t g = e0 + 2 * lane; g < e1; g += 128) {
+        const uint32_t k = g / 2;
+        if (g + 1 < e1) {
+          const lin_pair_t v = *reinterpret_cast<const lin_pair_t *>(s + g);
+          dst[k] = v.x;
+          dst[(even_last && g + 1 == Ff - 1) ? Ff / 2 : Cf + k] = v.y;
+        } else {
+          dst[k] = s[g];
+        }
+      }
+    } else {
+      // only the odd-f nodes: Ff - Cf of them in a row
+      const uint32_t cnt = Ff - Cf;
+      const uint32_t e1 = min(cnt, e0 + kLevelBoxPiece);
+      for (uint32_t k = e0 + lane; k < e1; k += 64) dst[Cf + k] = s[k];
+    }
+  }
+}
+
 } // namespace mgh

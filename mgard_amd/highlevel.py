@@ -25,6 +25,7 @@ HL_SYMBOLS = [
     "mgh_unpin_memory", "mgh_dist_use_library", "mgh_compress_dist", "mgh_decompress_dist",
     "mgh_decompress_into",
     "mgh_infer_level_shape", "mgh_infer_level_nodes", "mgh_decompress_level",
+    "mgh_lossless_decompress_prefix", "mgh_last_decompress_stats",
 ]
 
 
@@ -61,6 +62,13 @@ class Config(C.Structure):
                 self.num_domain_decomposition_sizes = len(v)
             else:
                 setattr(self, k, v)
+
+
+class DecompressStats(C.Structure):
+    """mgh_decompress_stats: what the lossless stage of the last decompress* call of this thread did."""
+    _fields_ = [("subdomains", C.c_uint64), ("chunks_total", C.c_uint64), ("chunks_decoded", C.c_uint64),
+                ("symbols_decoded", C.c_uint64), ("record_bytes", C.c_uint64),
+                ("record_bytes_moved", C.c_uint64)]
 
 
 class HeaderInfo(C.Structure):
@@ -136,6 +144,9 @@ def _hl():
     L.mgh_lossless_compress_device.argtypes = [vp, vp, u64, u64, u64, vp, vp, u64, vp, u64, C.POINTER(u64), vp]
     L.mgh_lossless_decompress.argtypes = [vp, vp, u64, C.c_int, vp, u64, C.POINTER(vp), C.POINTER(vp),
                                           C.POINTER(u64), vp]
+    L.mgh_lossless_decompress_prefix.argtypes = [vp, vp, u64, C.c_int, vp, u64, u64, C.POINTER(vp), C.POINTER(vp),
+                                                 C.POINTER(u64), vp]
+    L.mgh_last_decompress_stats.argtypes = [C.POINTER(DecompressStats)]
     L.mgh_memcpy.argtypes = [vp, vp, C.c_size_t]
     L.mgh_huffman_codebook.argtypes = [vp, u64, vp, vp, vp, vp]
     _declared = True
@@ -432,6 +443,14 @@ def compress_multi(data, tol, s=INF, mode=REL, devices=(0,), coords=None, config
     return out[:size.value]
 
 
+def last_decompress_stats():
+    """mgh_last_decompress_stats as a dict: subdomains, chunks_total, chunks_decoded, symbols_decoded,
+    record_bytes, record_bytes_moved of the last decompress* call of this thread."""
+    st = DecompressStats()
+    _check(_hl().mgh_last_decompress_stats(C.byref(st)))
+    return {k: int(getattr(st, k)) for k, _ in DecompressStats._fields_}
+
+
 def decompress_multi(buf, devices=(0,), config=None):
     """mgh_decompress_multi: host stream in, host numpy array out."""
     L = _hl()
@@ -546,11 +565,22 @@ class Lossless:
             out.numel(), C.byref(size), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
         return out[:size.value]
 
-    def decompress(self, payload, n, lossless=HUFFMAN):
+    def decompress(self, payload, n, lossless=HUFFMAN, prefix=None, out=None):
         """payload: bytes, or a cuda uint8 tensor (decoded where it lies). Returns (q, outlier_idx,
-        outlier_val) as cuda tensors."""
+        outlier_val) as cuda tensors.
+        prefix: decode only the chunks that hold the first `prefix` integers
+        (mgh_lossless_decompress_prefix): q[0 : min(n, ceil(prefix / chunk) * chunk)] is written and
+        nothing behind it; the outlier lists come whole. out: a cuda int64 tensor to decode into (with
+        a prefix it need only hold what is written); default: a new one of n elements."""
         import torch
-        q = torch.empty(n, dtype=torch.int64, device="cuda")
+        if out is None:
+            q = torch.empty(n, dtype=torch.int64, device="cuda")
+        else:
+            if not (out.is_cuda and out.dtype == torch.int64 and out.is_contiguous()):
+                raise ValueError("out: expected a contiguous cuda int64 tensor")
+            if prefix is None and out.numel() < n:
+                raise ValueError("out: %d elements, the record holds %d" % (out.numel(), n))
+            q = out
         if isinstance(payload, torch.Tensor):
             if not (payload.is_cuda and payload.dtype == torch.uint8 and payload.dim() == 1 and
                     payload.is_contiguous()):
@@ -561,9 +591,14 @@ class Lossless:
         else:
             raw, nbytes = (C.c_uint8 * len(payload)).from_buffer_copy(payload), len(payload)
         oi, ov, cnt = C.c_void_p(), C.c_void_p(), C.c_uint64()
-        _check(_hl().mgh_lossless_decompress(
-            self._c, raw, nbytes, lossless, C.c_void_p(q.data_ptr()), n, C.byref(oi), C.byref(ov),
-            C.byref(cnt), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        if prefix is None:
+            _check(_hl().mgh_lossless_decompress(
+                self._c, raw, nbytes, lossless, C.c_void_p(q.data_ptr()), n, C.byref(oi), C.byref(ov),
+                C.byref(cnt), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        else:
+            _check(_hl().mgh_lossless_decompress_prefix(
+                self._c, raw, nbytes, lossless, C.c_void_p(q.data_ptr()), n, int(prefix), C.byref(oi), C.byref(ov),
+                C.byref(cnt), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
         k = cnt.value
         idx = torch.empty(k, dtype=torch.int64, device="cuda")
         val = torch.empty(k, dtype=torch.int64, device="cuda")

@@ -1,6 +1,9 @@
 """Reconstruction at a coarser level against the FULL call, in the same run on the same box: HIP events,
 warm-up, several alternations (full, l_target-1, -2, -3, full, ...). For n^3 f32 (default 512; 1024):
-dequantize_recompose from int64 and from 16-bit symbols, highlevel.decompress device to device, and the
+dequantize_recompose from int64 and from 16-bit symbols, highlevel.decompress device to device and host to
+host of a reorder = 0 and of a reorder = 1 (level-linearised) container -- below l_target only the head of the
+latter is decoded; where the library has mgh_last_decompress_stats the chunks decoded are printed, so the
+tool runs on an older tree too -- the box_from_linear kernel on its own, and the
 full call's top-level kernels (profile) -- the structural claim is
     time(level = l_target - 1) < time(full) - time(top-level kernels of the full call) + spread.
 Dev tool; the table goes into DESIGN.md section 6 and profiles/NOTES.md."""
@@ -26,8 +29,12 @@ INF = float("inf")
 q, oi, ov, cnt, nrm = h.decompose_quantize(d, mg.REL, 1e-3, INF)
 sym, si, sv, scnt, _ = h.decompose_quantize_sym16(d, mg.REL, 1e-3, INF, nrm)
 stream = hl.compress(d, 1e-3, INF, mg.REL)
+cfg1 = hl.Config(reorder=1)
+stream1 = hl.compress(d, 1e-3, INF, mg.REL, config=cfg1)
+host0, host1 = stream.cpu().numpy(), stream1.cpu().numpy()
 levels = [None, L - 1, L - 2, L - 3]
 outs = {lv: torch.empty(h.shape if lv is None else h.level_shape(lv), dtype=torch.float32, device=dev) for lv in levels}
+houts = {lv: np.empty(h.shape if lv is None else h.level_shape(lv), dtype=np.float32) for lv in levels}
 
 
 def timed(f):
@@ -46,6 +53,9 @@ legs = {
     "sym16": lambda lv: h.dequantize_recompose_sym16(sym, mg.REL, 1e-3, INF, nrm, outlier_idx=si, outlier_val=sv,
                                                      out=outs[lv], level=lv),
     "decompress": lambda lv: hl.decompress(stream, out=outs[lv], level=lv),
+    "decompress r1": lambda lv: hl.decompress(stream1, config=cfg1, out=outs[lv], level=lv),
+    "decompress h2h": lambda lv: hl.decompress(host0, out=houts[lv], level=lv),
+    "decompress r1 h2h": lambda lv: hl.decompress(host1, config=cfg1, out=houts[lv], level=lv),
 }
 print("%d^3 f32, l_target %d, %d alternations x %d calls; ms per call: min / median / max" % (n, L, rounds, reps))
 for name, f in legs.items():
@@ -58,9 +68,13 @@ for name, f in legs.items():
             t[lv].append(timed(lambda: f(lv)))
     for lv in levels:
         v = sorted(t[lv])
-        print("  %-10s %-14s %8.3f / %8.3f / %8.3f" % (name, "full" if lv is None else "l_target-%d" % (L - lv),
+        print("  %-18s %-14s %8.3f / %8.3f / %8.3f" % (name, "full" if lv is None else "l_target-%d" % (L - lv),
                                                           v[0], v[len(v) // 2], v[-1]))
-    if name == "decompress":
+    if name.startswith("decompress"):
+        if hasattr(hl, "last_decompress_stats"):
+            for lv in levels:
+                f(lv)
+                print("     %-14s %s" % ("full" if lv is None else "l_target-%d" % (L - lv), hl.last_decompress_stats()))
         continue
     # per-kernel events of the full call and of level l_target - 1 (3 calls each): every kernel of both, their
     # sums, and the kernel time of the full call beyond that level. Beside the whole-call times above, the sums
@@ -91,3 +105,14 @@ for name, f in legs.items():
     print("     not kernel time (whole call - kernel sum): full %.3f ms, l_target-1 %.3f ms" % (
         med[None] - sums[None], med[L - 1] - sums[L - 1]))
     print("     structural check: l_target-1 %.3f ms against full - beyond = %.3f ms" % (med[L - 1], med[None] - top))
+
+# k_box_from_linear on its own: the box of level l_target - 1 (and - 2) from the head of the linearised integers
+if hasattr(h, "level_box_from_linear"):
+    lin = h.level_linearize(q).reshape(-1)
+    for lv in (L - 1, L - 2):
+        n_l = int(np.prod(h.level_shape(lv)))
+        head, box = lin[:n_l].clone(), torch.empty(n_l, dtype=torch.int64, device=dev)
+        h.level_box_from_linear(head, lv, out=box)
+        v = sorted(timed(lambda: h.level_box_from_linear(head, lv, out=box)) for _ in range(rounds))
+        print("  box_from_linear %s: %.4f / %.4f / %.4f ms, %.0f GB/s at the median (16 bytes per element)" % (
+            "x".join(map(str, h.level_shape(lv))), v[0], v[len(v) // 2], v[-1], 16 * n_l / v[len(v) // 2] / 1e6))
