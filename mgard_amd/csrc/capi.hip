@@ -22,6 +22,7 @@
 
 #include "env.hpp"
 #include "hierarchy.hpp"
+#include "ipk_plan.hpp"
 #include "kernels_v1.hpp"
 #include "kernels_ipk.hpp"
 #include "kernels_ipk_stream.hpp"
@@ -77,15 +78,7 @@ struct mgh_hierarchy {
   int force_v1_env = -1;
   bool force_nd = false;  // MGH_FORCE_ND=1: run the generic N-D kernels also for D <= 3 (cross-check)
   std::string prof_filter;  // empty = every kernel
-  // MGH_IPK_STREAM: 1 = streaming Thomas solves (kernels_ipk_stream.hpp) on the levels whose
-  // LDS-staged solve needs more than one round of resident workgroups (default), 0 = never
-  int ipk_stream = 1;
-  // MGH_IPK_DMA: 1 = strided float pencils whose tiles are all resident at once run k_ipk_dma
-  // (kernels_ipk_dma.hpp: LDS-DMA front end, everything requested up front; default), 0 = never
-  int ipk_dma = 1;
-  long ipk_dma_min_env = -1;
-  int ipk_dma_rounds = 4;  // MGH_IPK_DMA_ROUNDS: k_ipk_dma also for levels whose tiles need up to this many rounds of resident workgroups
-  size_t ipk_dma_min = 512;  // MGH_IPK_DMA_MIN: fewest tiles of a level for k_ipk_dma (two per CU; set in mgh_hierarchy_create)
+  mgh::IpkTuning ipk;  // MGH_IPK_*: what the Thomas-solve planner goes by (ipk_plan.hpp)
   int absmax_warm_mb = 192;  // MGH_ABSMAX_WARM_MB: the norm pass reads all but the last so many MB of the input with nontemporal loads
   // MGH_FUSED_FACES: 1 = face tiles for the remainder columns / rows of a level (default), 0 = off
   int fused_faces = 1;
@@ -99,24 +92,13 @@ struct mgh_hierarchy {
   // the box kernel (kernels_box.hpp: no march, every phase once over a 4 x 4 x 8 box) instead of
   // the marching tile kernel; 0 = none, 1 = class 0 (default), 2 = classes 0-1, 3 = every level
   int box = 1;
-  int ipk_spec = 1;     // MGH_IPK_SPEC: few long contiguous pencils (1-D arrays) are solved in chunks, each verified against the sequential sweep (kernels_ipk_spec.hpp); 0 = one lane per pencil
   int outlier_agg = 2;  // MGH_OUTLIER_AGG: the level kernel asks for outlier slots once per workgroup and pair step instead of once per wave and plane (kernels_fused2.hpp: OutlierShared): 0 never, 1 always, 2 when the previous call on this hierarchy left more than 0.5 % of its values (and more than 200 000) in the outlier list
-  int ipk_chunk = 1;    // MGH_IPK_CHUNK: the LDS-staged solve of contiguous pencils shares a tile's sweeps between the four waves (thomas_chunked: chunks verified against the sequential sweep)
-  int ipk_chunk_k = 0;  // MGH_IPK_CHUNK_K: warm-up length of a chunk (0 = from the tables, chunk_warmup_need; small values make the verification fail and exercise the fall-back)
-  int ipk_chunk_need = 0;  // warm-up length that the Thomas tables of this hierarchy need (set with the tables)
-  int ipk_spec_long = 1024;  // MGH_IPK_SPEC_LONG: strided pencils of this length and more, one round of tiles at most, run in verified chunks too (0: never)
-  uint32_t ipk_spec_max = 16384;  // MGH_IPK_SPEC_MAX: most pencils of a solve whose pencils do not fit LDS that still run in verified chunks
-  int ipk_spec_k = 0;   // MGH_IPK_SPEC_K: warm-up length of a chunk (0 = 64 floats / 128 doubles; tiny values make the verification fail and exercise the repair)
   int sym16_mixed = 1;  // MGH_SYM16_MIXED: 16-bit symbols for the finest level only, int64 below it (default), 0 = 16-bit symbols on every level
   int tail_solves = 1;  // MGH_TAIL_SOLVES: the tail kernel runs the Thomas solves of the level above it
   // (the rest of the developer switches, env.hpp; all read when the hierarchy is created)
   size_t cls1 = 256, cls2 = 2048;  // MGH_CLS1 / MGH_CLS2: tile-count thresholds of the march classes
   int rch[3] = {1, 4, 16};         // MGH_RCH=a,b,c: coarse planes per workgroup of the three classes
-  uint32_t ipk_w = 64;             // MGH_IPK_W: widest solver wave of the streaming Thomas solves
-  size_t ipk_contig_rounds = 4;    // MGH_IPK_CONTIG: rounds of the LDS-staged contiguous solve from which the streaming one takes over
   int ipk_range_mb = 128;          // MGH_IPK_RANGE_MB: f- and c-solve of a load vector bigger than twice this run in r-plane ranges of this size (0 = off)
-  int ipk_kr16 = 1;                // MGH_IPK_KR16: 16 register-resident batches for float pencils of 512+ elements
-  size_t ipk_wpc = 8;              // MGH_IPK_WPC: most one-wave solver workgroups per CU the host plans with
   bool no_head = false;            // MGH_NO_RECOMPOSE_HEAD
   bool debug_sync = false;         // MGH_DEBUG_SYNC: name every launch on stderr and synchronise behind it
   std::map<std::string, ProfileEntry> prof;
@@ -387,7 +369,7 @@ template <typename T> int build_device_state(mgh_hierarchy *h) {
       offs[l].ratio[k] = push(hh->lv[l][d].ratio);
       offs[l].mass[k] = push(hh->mass_table(l, d));
       const std::vector<T> tt = hh->thomas_table(l - 1, d);
-      h->ipk_chunk_need = std::max(h->ipk_chunk_need, chunk_warmup_need(tt));
+      h->ipk.chunk_need = std::max(h->ipk.chunk_need, chunk_warmup_need(tt));
       offs[l].thomas[k] = push(tt);
     }
   }
@@ -499,9 +481,6 @@ template <typename T> int ensure_scratch(mgh_hierarchy *h) {
   return MGH_SUCCESS;
 }
 
-// LDS budget for the IPK tiles: whole pencils of 64 (or 32) lanes must fit.
-constexpr size_t kLdsPerCU = 160 * 1024;
-
 // (`bytes`: the dynamic part; a kernel with static LDS of its own asks for that much less)
 template <typename K> int allow_big_lds(K kernel, size_t bytes = kLdsPerCU) {
   HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
@@ -520,306 +499,158 @@ template <typename K> int allow_big_lds_once(K kernel, std::atomic<uint64_t> &do
   return MGH_SUCCESS;
 }
 
-// Thomas solve along `axis` of the compact (m[0], m[1], m[2]) box.
+// ---- Thomas solves: one launcher per family of ipk_plan.hpp ------------------
+// A run-time value as a compile-time one: f(std::integral_constant<int, V>) with the V that equals v.
+template <int... V, typename F> int with_value(int v, F &&f) {
+  int rc = MGH_ERR_INVALID_ARGUMENT;
+  (void)((v == V ? (rc = f(std::integral_constant<int, V>{}), true) : false) || ...);
+  return rc;
+}
+
+// What every launcher is given beside the plan: pointers, sign and where to launch.
+template <typename T> struct IpkArgs {
+  mgh_hierarchy *h;
+  const char *name;  // profile name of the axis
+  T *x;
+  const T *tt;
+  T *add_to;
+  int sign;
+  hipStream_t s;
+  int add() const { return add_to ? (sign > 0 ? 1 : -1) : 0; }
+};
+
+// Scratch of the verified-chunk solve, grown on demand: forward results of `total` elements,
+// two arrays of `edges` chunk-edge values, the repair counter and mismatch flags.
+template <typename T> int spec_scratch(mgh_hierarchy *h, size_t total, size_t edges, hipStream_t s) {
+  auto *ds = DS<T>(h);
+  if (total > ds->spec_y_elems) {
+    (void)hipFree(ds->spec_y);
+    ds->spec_y = nullptr;
+    ds->spec_y_elems = 0;
+    HIP_TRY(hipMalloc(&ds->spec_y, total * sizeof(T)));
+    ds->spec_y_elems = total;
+  }
+  if (edges > ds->spec_edge_elems) {
+    (void)hipFree(ds->spec_a);
+    (void)hipFree(ds->spec_b);
+    ds->spec_a = ds->spec_b = nullptr;
+    ds->spec_edge_elems = 0;
+    HIP_TRY(hipMalloc(&ds->spec_a, edges * sizeof(T)));
+    HIP_TRY(hipMalloc(&ds->spec_b, edges * sizeof(T)));
+    ds->spec_edge_elems = edges;
+  }
+  if (!ds->spec_fixed) {  // [0]: chunks repaired so far, [1]: mismatch flags of the two sweeps of a call
+    HIP_TRY(hipMalloc(&ds->spec_fixed, 16));
+    HIP_TRY(hipMemsetAsync(ds->spec_fixed, 0, 16, s));
+  }
+  return MGH_SUCCESS;
+}
+
+template <typename T> int ipk_launch_spec(const IpkPlan &p, const IpkArgs<T> &a, int axis) {
+  const IpkGeom &g = p.geom;
+  const SpecGeom G{g.n, p.S, p.K, p.nchunk, g.npencil, g.n_inner, g.outer_stride, g.inner_stride, g.stride, axis != 2};
+  const size_t total = (size_t)g.npencil * g.n;
+  TRY(spec_scratch<T>(a.h, total, (size_t)g.npencil * p.nchunk, a.s));
+  auto *ds = DS<T>(a.h);
+  T *x = a.x, *y = ds->spec_y, *ea = ds->spec_a, *eb = ds->spec_b;
+  unsigned long long *fx = ds->spec_fixed;
+  unsigned *mm = reinterpret_cast<unsigned *>(ds->spec_fixed + 1);
+  hipStream_t s = a.s;
+  HIP_TRY(hipMemsetAsync(mm, 0, 8, s));
+  return launch(a.h, a.name, s, [&] {
+    k_ipk_spec_fwd<T><<<p.grid, 64, 0, s>>>(G, x, y, a.tt, ea, eb);
+    k_ipk_spec_check<T><<<p.check_grid, 256, 0, s>>>(p.nchunk, g.npencil, ea, eb, +1, mm);
+    k_ipk_spec_fix<T><<<p.fix_grid, 64, 0, s>>>(G, x, y, a.tt, ea, eb, +1, fx, mm);
+    k_ipk_spec_bwd<T><<<p.grid, 64, 0, s>>>(G, y, x, a.tt, ea, eb);
+    k_ipk_spec_check<T><<<p.check_grid, 256, 0, s>>>(p.nchunk, g.npencil, ea, eb, -1, mm + 1);
+    k_ipk_spec_fix<T><<<p.fix_grid, 64, 0, s>>>(G, y, x, a.tt, ea, eb, -1, fx, mm + 1);
+    if (a.add_to) k_ipk_spec_apply<T><<<p.apply_grid, 256, 0, s>>>(total, a.add_to, x, a.sign);
+  });
+}
+
+template <typename T, bool CHUNKED> int ipk_launch_lds_contig(const IpkPlan &p, const IpkArgs<T> &a) {
+  static std::atomic<uint64_t> once{0};
+  TRY(allow_big_lds_once(k_ipk_lds_contig<T, CHUNKED>, once, p.lds_attr));
+  return launch(a.h, a.name, a.s, [&] {
+    k_ipk_lds_contig<T, CHUNKED><<<p.grid, p.block, p.lds, a.s>>>(p.geom.npencil, p.geom.n, p.pad, p.magic, p.P,
+                                                                  a.x, a.tt, a.add_to, a.sign, p.K);
+  });
+}
+
+template <typename T, int ADD> int ipk_launch_dma(const IpkPlan &p, const IpkArgs<T> &a) {
+  constexpr uint32_t U = 64 / sizeof(T), KR = 10;
+  const IpkGeom &g = p.geom;
+  static std::atomic<uint64_t> once{0};
+  TRY(allow_big_lds_once(k_ipk_dma<T, U, KR, ADD>, once, p.lds_attr));
+  return launch(a.h, a.name, a.s, [&] {
+    k_ipk_dma<T, U, KR, ADD><<<p.grid, p.block, p.lds, a.s>>>(g.npencil, g.n_inner, g.outer_stride, 1, g.stride,
+                                                              g.n, a.x, a.tt, a.add_to);
+  });
+}
+
+template <typename T, int KR, bool CONTIG> int ipk_launch_stream(const IpkPlan &p, const IpkArgs<T> &a) {
+  constexpr uint32_t U = 64 / sizeof(T);
+  const IpkGeom &g = p.geom;
+  static std::atomic<uint64_t> once{0};
+  TRY(allow_big_lds_once(k_ipk_stream<T, U, KR, 1, CONTIG, false>, once, p.lds_attr));
+  return launch(a.h, a.name, a.s, [&] {
+    k_ipk_stream<T, U, KR, 1, CONTIG, false><<<p.grid, p.block, p.lds, a.s>>>(
+        g.npencil, g.n_inner, g.outer_stride, g.inner_stride, g.stride, g.n, p.W, p.n_glob, a.x, a.tt, a.add_to,
+        a.sign);
+  });
+}
+
+template <typename T, int W> int ipk_launch_lds_strided(const IpkPlan &p, const IpkArgs<T> &a) {
+  const IpkGeom &g = p.geom;
+  static std::atomic<uint64_t> once{0};
+  TRY(allow_big_lds_once(k_ipk_lds_strided<T, W>, once, p.lds_attr));
+  return launch(a.h, a.name, a.s, [&] {
+    k_ipk_lds_strided<T, W><<<p.grid, p.block, p.lds, a.s>>>(g.npencil / g.n_inner, g.n_inner, g.outer_stride,
+                                                             g.stride, g.n, a.x, a.tt, a.add_to, a.sign);
+  });
+}
+
+template <typename T, int AXIS> int ipk_launch_thread(const IpkPlan &p, const IpkArgs<T> &a, const uint32_t *m) {
+  return launch(a.h, a.name, a.s, [&] {
+    k_ipk<T, AXIS><<<dim3(p.grid, p.grid_y, 1), dim3(p.block, 1, 1), 0, a.s>>>(m[0], m[1], m[2], a.x, a.tt,
+                                                                             a.add_to, a.sign);
+  });
+}
+
+// Thomas solve along `axis` of the compact (m[0], m[1], m[2]) box, by the kernel ipk_plan() picks.
 // axis 0 only: `nbatch` boxes `batch_stride` elements apart in ONE launch (the slices of a 4-D level).
 template <typename T>
 int ipk_launch(mgh_hierarchy *h, int axis, const uint32_t *m, T *x, const T *tt, T *add_to,
                int sign, hipStream_t s, uint32_t nbatch = 1, size_t batch_stride = 0) {
   if (nbatch > 1 && axis != 0) return fail(MGH_ERR_INVALID_ARGUMENT, "ipk_launch: batches along the slowest axis only");
-  const uint32_t n = m[axis];
   static const char *names[3] = {"ipk_r", "ipk_c", "ipk_f"};
-  const char *name = names[axis];
-  // tile width (pencils per workgroup): whole pencils must fit in LDS; among the fitting
-  // widths take the one that needs the fewest "rounds" of resident workgroups
-  const size_t pencil_bytes = (size_t)(n + (axis == 2 && n % 2 == 0 ? 1 : 0)) * sizeof(T);
-  const uint32_t npencil = axis == 2 ? m[0] * m[1] : (axis == 1 ? m[0] * m[2] : nbatch * m[1] * m[2]);
-  // Few long pencils (a 1-D array: ONE pencil per level): parallel inside the pencil, every chunk
-  // verified against the sequential sweep (kernels_ipk_spec.hpp)
-  auto spec_solve = [&]() -> int {
-    auto *ds = DS<T>(h);
-    SpecGeom G{};
-    G.n = n;
-    G.K = h->ipk_spec_k > 0 ? (uint32_t)h->ipk_spec_k : (sizeof(T) == 4 ? 64u : 128u);
-    uint32_t S = std::max<uint32_t>(128, std::min<uint32_t>(1024, n / 16384));
-    G.S = (S + 7) / 8 * 8;
-    G.nchunk = (n + G.S - 1) / G.S;
-    G.npencil = npencil;
-    if (axis == 2) { G.n_inner = npencil; G.outer_stride = 0; G.inner_stride = n; G.stride = 1; G.along_p = 0; }
-    else if (axis == 1) { G.n_inner = m[2]; G.outer_stride = (size_t)m[1] * m[2]; G.inner_stride = 1; G.stride = m[2]; G.along_p = 1; }
-    else { G.n_inner = m[1] * m[2]; G.outer_stride = batch_stride; G.inner_stride = 1; G.stride = (size_t)m[1] * m[2]; G.along_p = 1; }  // (batches: boxes back to back, spec_ok)
-    const uint32_t nchunk = G.nchunk;
-    const size_t total = (size_t)npencil * n, edges = (size_t)npencil * nchunk;
-    if (total > ds->spec_y_elems) {
-      (void)hipFree(ds->spec_y);
-      ds->spec_y = nullptr;
-      ds->spec_y_elems = 0;
-      HIP_TRY(hipMalloc(&ds->spec_y, total * sizeof(T)));
-      ds->spec_y_elems = total;
+  const IpkArgs<T> a{h, names[axis], x, tt, add_to, sign, s};
+  const IpkPlan p = ipk_plan(h->ipk, sizeof(T), axis, m, nbatch, batch_stride);
+  switch (p.kernel) {
+  case IpkKernel::Spec: return ipk_launch_spec<T>(p, a, axis);
+  case IpkKernel::LdsContigChunked: return ipk_launch_lds_contig<T, true>(p, a);
+  case IpkKernel::Dma:
+    if constexpr (sizeof(T) == 4)
+      return with_value<0, 1, -1>(a.add(), [&](auto add) { return ipk_launch_dma<T, add()>(p, a); });
+    break;  // (planned for 4-byte elements only)
+  case IpkKernel::Stream:
+    if constexpr (sizeof(T) == 4)
+      if (p.KR == 16)
+        return axis == 2 ? ipk_launch_stream<T, 16, true>(p, a) : ipk_launch_stream<T, 16, false>(p, a);
+    return axis == 2 ? ipk_launch_stream<T, 8, true>(p, a) : ipk_launch_stream<T, 8, false>(p, a);
+  case IpkKernel::LdsContig: return ipk_launch_lds_contig<T, false>(p, a);
+  case IpkKernel::LdsStrided:
+    return with_value<64, 48, 32, 16>((int)p.W, [&](auto w) { return ipk_launch_lds_strided<T, w()>(p, a); });
+  case IpkKernel::Thread:
+    if (p.per_batch) {
+      for (uint32_t bi = 0; bi < nbatch; bi++)
+        TRY(ipk_launch<T>(h, axis, m, x + (size_t)bi * batch_stride, tt,
+                          add_to ? add_to + (size_t)bi * batch_stride : nullptr, sign, s));
+      return MGH_SUCCESS;
     }
-    if (edges > ds->spec_edge_elems) {
-      (void)hipFree(ds->spec_a);
-      (void)hipFree(ds->spec_b);
-      ds->spec_a = ds->spec_b = nullptr;
-      ds->spec_edge_elems = 0;
-      HIP_TRY(hipMalloc(&ds->spec_a, edges * sizeof(T)));
-      HIP_TRY(hipMalloc(&ds->spec_b, edges * sizeof(T)));
-      ds->spec_edge_elems = edges;
-    }
-    if (!ds->spec_fixed) {  // [0]: chunks repaired so far, [1]: mismatch flags of the two sweeps of a call
-      HIP_TRY(hipMalloc(&ds->spec_fixed, 16));
-      HIP_TRY(hipMemsetAsync(ds->spec_fixed, 0, 16, s));
-    }
-    const unsigned grid = (unsigned)((edges + 63) / 64);
-    const unsigned pgrid = (npencil + 63) / 64;
-    T *y = ds->spec_y, *ea = ds->spec_a, *eb = ds->spec_b;
-    unsigned long long *fx = ds->spec_fixed;
-    unsigned *mm = reinterpret_cast<unsigned *>(ds->spec_fixed + 1);
-    const unsigned cgrid = (unsigned)((edges + 255) / 256);
-    HIP_TRY(hipMemsetAsync(mm, 0, 8, s));
-    TRY(launch(h, name, s, [&] {
-      k_ipk_spec_fwd<T><<<grid, 64, 0, s>>>(G, x, y, tt, ea, eb);
-      k_ipk_spec_check<T><<<cgrid, 256, 0, s>>>(nchunk, npencil, ea, eb, +1, mm);
-      k_ipk_spec_fix<T><<<pgrid, 64, 0, s>>>(G, x, y, tt, ea, eb, +1, fx, mm);
-      k_ipk_spec_bwd<T><<<grid, 64, 0, s>>>(G, y, x, tt, ea, eb);
-      k_ipk_spec_check<T><<<cgrid, 256, 0, s>>>(nchunk, npencil, ea, eb, -1, mm + 1);
-      k_ipk_spec_fix<T><<<pgrid, 64, 0, s>>>(G, y, x, tt, ea, eb, -1, fx, mm + 1);
-      if (add_to)
-        k_ipk_spec_apply<T><<<(unsigned)std::min<size_t>((total + 255) / 256, 4096), 256, 0, s>>>(total, add_to, x, sign);
-    }));
-    return MGH_SUCCESS;
-  };
-  // (the batches of a 4-D level: only back to back -- the chunk buffers and the add-to pass see one array)
-  const bool spec_ok = h->ipk_spec && (nbatch == 1 || batch_stride == (size_t)m[0] * m[1] * m[2]);
-  if (axis == 2 && nbatch == 1 && h->ipk_spec && npencil <= 64 && n >= 2048) return spec_solve();
-  int best_w = 0;
-  size_t best_rounds = ~(size_t)0;
-  for (int w : {64, 48, 32, 16}) {
-    const size_t lds = w * pencil_bytes;
-    if (lds > kLdsPerCU) continue;
-    const size_t per_cu = std::min<size_t>(kLdsPerCU / lds, 8);
-    const size_t blocks = (npencil + w - 1) / w;
-    const size_t rounds = (blocks + per_cu * h->num_cu - 1) / (per_cu * h->num_cu);
-    if (rounds < best_rounds) {
-      best_rounds = rounds;
-      best_w = w;
-    }
+    return with_value<0, 1, 2>(axis, [&](auto ax) { return ipk_launch_thread<T, ax()>(p, a, m); });
   }
-  // Long strided pencils, few enough of them to be one round of tiles with most of the chip idle
-  // (16395 x 64 x 64: the r-solve of the 2051 x 9 x 9 level is 6 tiles and a chain of 2051 steps down
-  // and 2051 back at ~40 ns each in LDS -- 161 us for 0.7 MB; the levels above it 91 and 53 us): the
-  // verified chunks put a wave on every piece of every pencil. MGH_IPK_SPEC_LONG: the pencil length
-  // from which on (default 1024; 0: never).
-  if (axis != 2 && spec_ok && h->ipk_spec_long && n >= (uint32_t)h->ipk_spec_long &&
-      npencil <= 64u * (uint32_t)h->num_cu && npencil <= h->ipk_spec_max)
-    return spec_solve();
-  // Contiguous pencils, LDS-staged tiles whose sweeps are shared by the four waves (thomas_chunked;
-  // warm-up length from the tables, ipk_chunk_need), ahead of the streaming kernels: 512^3 f32 top
-  // level 53 -> 44 us, f64 120 -> 109 us, 1024^3 554 -> 543 us. (The same for strided pencils and
-  // for the plane kernel of the small levels was measured and dropped: profiles/NOTES.md.)
-  if (h->ipk_chunk && axis == 2 && best_w && n >= 64 && best_w * pencil_bytes + 8192 <= kLdsPerCU) {
-    const uint32_t K = h->ipk_chunk_k > 0 ? (uint32_t)h->ipk_chunk_k : (uint32_t)h->ipk_chunk_need;
-    if (K > 0 && K <= n / 2) {
-      const uint32_t pad = (n % 2 == 0) ? 1u : 0u;
-      const uint32_t magic = (uint32_t)((((uint64_t)1 << 32) + n - 1) / n);
-      const uint32_t P = (uint32_t)best_w;
-      static std::atomic<uint64_t> once{0};
-      TRY(allow_big_lds_once(k_ipk_lds_contig<T, true>, once, kLdsPerCU - 8192));
-      return launch(h, name, s, [&] {
-        k_ipk_lds_contig<T, true><<<(npencil + P - 1) / P, 256, P * pencil_bytes, s>>>(
-            npencil, n, pad, magic, P, x, tt, add_to, sign, K);
-      });
-    }
-  }
-  // Streaming solves: every wave a solver, forward results parked in registers + LDS +
-  // (the leading n_glob elements) in place in global memory. Where the forward results are parked
-  // decides how many pencils a CU works on at once, and residency is the throughput of these
-  // latency-bound chains: the host picks the tile width W and n_glob that need the FEWEST rounds
-  // of resident workgroups (up to ipk_wpc one-wave workgroups per CU), then the least global
-  // parking. Used when the LDS-staged tiles need more than one round (strided pencils), or --
-  // contiguous pencils, where the LDS-staged kernel is the better one at one or two rounds --
-  // from four rounds on (1024^3: 2 KB pencils leave ONE staged tile per CU, 16 rounds).
-  // batches of 64 bytes per lane: 16 floats / 8 doubles; the last KR batches stay in registers.
-  // KR = 8 (a third of the register file: two or more waves per SIMD), or -- float pencils of
-  // 512+ elements, MGH_IPK_KR16 -- KR = 16: 256 values of every pencil in registers, one wave per
-  // SIMD, so that most of the rest fits in LDS and little is parked in global memory (1024^3:
-  // PMC traffic of a solve 2.0-2.5 GB for 1.08 GB algorithmic with KR = 8).
-  constexpr int kNotApplicable = 1 << 20;
-  constexpr uint32_t U = sizeof(T) == 4 ? 16 : 8;
-  // Strided float pencils, every tile of the level resident at once: the LDS-DMA variant
-  // (kernels_ipk_dma.hpp). KR register-resident batches: as many as keep two waves per SIMD.
-  if constexpr (sizeof(T) == 4) {
-    const size_t box_bytes = (nbatch > 1 ? nbatch * batch_stride : (size_t)m[0] * m[1] * m[2]) * sizeof(T);
-    if (h->ipk_dma && axis != 2 && box_bytes < ((size_t)1 << 32)) {
-      auto try_kr = [&](auto KRc) -> int {
-        constexpr uint32_t KR = decltype(KRc)::value;
-        if (n < KR * U) return kNotApplicable;
-        const uint32_t nl = n - KR * U;
-        const size_t lds = (size_t)nl * 64 * sizeof(T);
-        if (lds > kLdsPerCU - 4096) return kNotApplicable;
-        const size_t per_cu = lds ? std::min<size_t>((kLdsPerCU - 4096) / lds, 8) : 8;
-        const size_t tiles = ((size_t)npencil + 63) / 64;
-        // (a level with fewer than two tiles per CU is served better by the LDS-staged kernels, whose
-        // four waves per tile stream it in and out: 129^3, 261 tiles, 18.8 vs 16.1 us)
-        // (MGH_IPK_DMA_MIN: that threshold in tiles, 0 in the tests that run this kernel on small shapes)
-        // (round 6: short pencils -- four or more tiles per CU -- also when the level needs up to
-        // MGH_IPK_DMA_ROUNDS rounds of resident workgroups: the 8 x 512^3 slab's 5168 tiles of
-        // 257-element pencils, ipk_c 242 -> 213 us, ipk_r 204 -> 190 us against k_ipk_stream; long
-        // pencils with ONE tile per CU lose badly that way -- 1024^3's 513-element pencils 430 -> 850 us)
-        const size_t rounds = per_cu >= 4 ? (size_t)h->ipk_dma_rounds : 1;
-        if (tiles > per_cu * h->num_cu * rounds || tiles < h->ipk_dma_min) return kNotApplicable;
-        const unsigned blocks = (unsigned)((tiles + 7) / 8 * 8);
-        uint32_t n_inner;
-        size_t outer_stride, stride;
-        if (axis == 1) { n_inner = m[2]; outer_stride = (size_t)m[1] * m[2]; stride = m[2]; }
-        else { n_inner = m[1] * m[2]; outer_stride = batch_stride; stride = (size_t)m[1] * m[2]; }
-#define MGH_DMA(ADD)                                                                          \
-  {                                                                                           \
-    static std::atomic<uint64_t> once{0};                                                     \
-    TRY(allow_big_lds_once(k_ipk_dma<T, U, KR, ADD>, once));                                  \
-    return launch(h, name, s, [&] {                                                           \
-      k_ipk_dma<T, U, KR, ADD><<<blocks, 64, lds, s>>>(npencil, n_inner, outer_stride, 1,     \
-                                                       stride, n, x, tt, add_to);             \
-    });                                                                                       \
-  }
-        if (!add_to) MGH_DMA(0)
-        if (sign > 0) MGH_DMA(1)
-        MGH_DMA(-1)
-#undef MGH_DMA
-      };
-      const int rc = try_kr(std::integral_constant<uint32_t, 10>{});
-      if (rc != kNotApplicable) return rc;
-    }
-  }
-  auto stream_plan = [&](auto KRc, size_t wpc_cap) -> int {
-    constexpr uint32_t KR = decltype(KRc)::value;
-    const size_t wpc = std::min(h->ipk_wpc, wpc_cap);
-    const uint32_t nb = n / U;
-    const size_t box_bytes = (nbatch > 1 ? nbatch * batch_stride : (size_t)m[0] * m[1] * m[2]) * sizeof(T);
-    // (strided pencils: measured inside the step at 512^3, ipk_c 59 -> 52 us, ipk_r of
-    // all levels 128 -> 103 us, but the contiguous solve 60 -> 65 us)
-    const size_t min_rounds = axis == 2 ? h->ipk_contig_rounds : 2;
-    if (h->ipk_stream && best_w && best_rounds >= min_rounds && nb >= KR &&
-        box_bytes < ((size_t)1 << 32)) {
-      const uint32_t parked = (nb - KR) * U;  // elements per pencil outside the registers
-      uint32_t W = 0, n_glob = 0;
-      size_t w_rounds = ~(size_t)0;
-      const uint32_t w_max = h->ipk_w;
-      for (uint32_t ng = 0; ng <= parked; ng += U) {
-        for (uint32_t w : {64u, 60u, 56u, 48u, 40u, 32u, 24u, 16u}) {
-          if (w > w_max) continue;
-          const size_t lds = (size_t)w * (parked - ng) * sizeof(T) +
-                             (axis == 2 ? TileIO<T, U>::stage_elems * sizeof(T) : 0);
-          // ~230 VGPRs (KR = 8): two waves per SIMD = 8 one-wave workgroups per CU; KR = 16:
-          // ~400 VGPRs, one wave per SIMD = 4 per CU (the caps the host plans with)
-          // (five 32 KB allocations do not fit one CU although 5 * 32 KB = 160 KB: leave a margin)
-          const size_t per_cu = lds ? std::min<size_t>((kLdsPerCU - 4096) / lds, wpc) : wpc;
-          if (!per_cu) continue;
-          const size_t blocks = ((size_t)npencil + w - 1) / w;
-          const size_t rounds = (blocks + per_cu * h->num_cu - 1) / (per_cu * h->num_cu);
-          if (rounds < w_rounds) {
-            w_rounds = rounds;
-            W = w;
-            n_glob = ng;
-          }
-        }
-        if (w_rounds == 1) break;
-      }
-      if (W && w_rounds < best_rounds) {
-        // (contiguous pencils: + the staging area of the wave-cooperative loads and stores)
-        const size_t lds = (size_t)W * (parked - n_glob) * sizeof(T) +
-                           (axis == 2 ? TileIO<T, U>::stage_elems * sizeof(T) : 0);
-        const unsigned blocks = ((npencil + W - 1) / W + 7) / 8 * 8;
-        uint32_t n_inner;
-        size_t outer_stride, inner_stride, stride;
-        if (axis == 2) { n_inner = npencil; outer_stride = 0; inner_stride = n; stride = 1; }
-        else if (axis == 1) { n_inner = m[2]; outer_stride = (size_t)m[1] * m[2]; inner_stride = 1; stride = m[2]; }
-        else { n_inner = m[1] * m[2]; outer_stride = batch_stride; inner_stride = 1; stride = (size_t)m[1] * m[2]; }
-#define MGH_STREAM(CONTIG)                                                                    \
-  {                                                                                           \
-    static std::atomic<uint64_t> once{0};                                                     \
-    TRY(allow_big_lds_once(k_ipk_stream<T, U, KR, 1, CONTIG, false>, once));                  \
-    return launch(h, name, s, [&] {                                                           \
-      k_ipk_stream<T, U, KR, 1, CONTIG, false><<<blocks, 64, lds, s>>>(                       \
-          npencil, n_inner, outer_stride, inner_stride, stride, n, W, n_glob, x, tt, add_to,  \
-          sign);                                                                              \
-    });                                                                                       \
-  }
-        if (axis == 2) MGH_STREAM(true)
-        MGH_STREAM(false)
-#undef MGH_STREAM
-      }
-    }
-    return kNotApplicable;
-  };
-  if constexpr (sizeof(T) == 4) {
-    if (h->ipk_kr16 && n / U >= 32) {
-      const int rc = stream_plan(std::integral_constant<uint32_t, 16>{}, 4);
-      if (rc != kNotApplicable) return rc;
-    }
-  }
-  {
-    const int rc = stream_plan(std::integral_constant<uint32_t, 8>{}, 16);
-    if (rc != kNotApplicable) return rc;
-  }
-  if (axis == 2 && best_w) {
-    const uint32_t pad = (n % 2 == 0) ? 1u : 0u;
-    const uint32_t magic = (uint32_t)((((uint64_t)1 << 32) + n - 1) / n);  // e/n for e < 2^17
-    static std::atomic<uint64_t> once{0};
-    TRY(allow_big_lds_once(k_ipk_lds_contig<T>, once));
-    const uint32_t P = (uint32_t)best_w;
-    return launch(h, name, s, [&] {
-      k_ipk_lds_contig<T><<<(npencil + P - 1) / P, 256, P * pencil_bytes, s>>>(
-          npencil, n, pad, magic, P, x, tt, add_to, sign, 0u);
-    });
-  }
-  if (axis != 2 && best_w) {
-    const uint32_t n_outer = axis == 1 ? m[0] : nbatch;
-    const uint32_t n_inner = axis == 1 ? m[2] : m[1] * m[2];
-    const size_t outer_stride = axis == 1 ? (size_t)m[1] * m[2] : batch_stride;
-    const size_t stride = axis == 1 ? (size_t)m[2] : (size_t)m[1] * m[2];
-    const size_t lds = best_w * pencil_bytes;
-    const unsigned blocks = ((npencil + best_w - 1) / best_w + 7) / 8 * 8;  // XCD-contiguous tile ranges
-#define MGH_STRIDED(W)                                                                        \
-  {                                                                                           \
-    static std::atomic<uint64_t> once{0};                                                                 \
-    TRY(allow_big_lds_once(k_ipk_lds_strided<T, W>, once));                  \
-    return launch(h, name, s, [&] {                                                           \
-      k_ipk_lds_strided<T, W><<<blocks, 256, lds, s>>>(n_outer, n_inner, outer_stride,        \
-                                                       stride, n, x, tt, add_to, sign);       \
-    });                                                                                       \
-  }
-    if (best_w == 64) MGH_STRIDED(64)
-    if (best_w == 48) MGH_STRIDED(48)
-    if (best_w == 32) MGH_STRIDED(32)
-    MGH_STRIDED(16)
-#undef MGH_STRIDED
-  }
-  // pencils too long for LDS. Not too many of them (a 4194304 x 9 array: 9 strided pencils of
-  // 2^21 elements per level; 100 x 100 x 6000: 2601 contiguous ones of 3001): in verified chunks
-  if (spec_ok && n >= 2048 && npencil <= h->ipk_spec_max) return spec_solve();
-  // ... else one thread per pencil straight from global memory
-  if (nbatch > 1) {
-    for (uint32_t bi = 0; bi < nbatch; bi++)
-      TRY(ipk_launch<T>(h, axis, m, x + (size_t)bi * batch_stride, tt,
-                        add_to ? add_to + (size_t)bi * batch_stride : nullptr, sign, s));
-    return MGH_SUCCESS;
-  }
-  const dim3 pb(64, 1, 1);
-  if (axis == 2) {
-    const dim3 g((m[1] + 63) / 64, m[0], 1);
-    return launch(h, name, s, [&] {
-      k_ipk<T, 2><<<g, pb, 0, s>>>(m[0], m[1], m[2], x, tt, add_to, sign);
-    });
-  } else if (axis == 1) {
-    const dim3 g((m[2] + 63) / 64, m[0], 1);
-    return launch(h, name, s, [&] {
-      k_ipk<T, 1><<<g, pb, 0, s>>>(m[0], m[1], m[2], x, tt, add_to, sign);
-    });
-  }
-  const dim3 g((m[2] + 63) / 64, m[1], 1);
-  return launch(h, name, s, [&] {
-    k_ipk<T, 0><<<g, pb, 0, s>>>(m[0], m[1], m[2], x, tt, add_to, sign);
-  });
+  return fail(MGH_ERR_INVALID_ARGUMENT, "ipk_launch: no kernel for this plan");
 }
 
 // f-solve and c-solve of a compact (m0, m1, m2) box: one launch when a coarse plane fits in LDS
@@ -828,7 +659,7 @@ template <typename T>
 int ipk_fc_launch(mgh_hierarchy *h, const uint32_t *m, T *x, const T *tt_f, const T *tt_c,
                   hipStream_t s) {
   const uint32_t pitch = m[2] | 1u;
-  if ((size_t)m[1] * pitch * sizeof(T) <= 150 * 1024 && m[1] <= 1024 && m[2] <= 1024) {
+  if (ipk_plane_fits_lds(sizeof(T), m)) {
     static std::atomic<uint64_t> once{0};
     TRY(allow_big_lds_once(k_ipk_plane_fc<T>, once));
     const uint32_t magic = (uint32_t)((((uint64_t)1 << 32) + m[2] - 1) / m[2]);  // e / m2, e < 2^32 / m2
@@ -2999,6 +2830,27 @@ int norm_stream_add(mgh_hierarchy *h, const T *part, size_t count, double s, int
   return launch(h, "sqsum", st, [&] { k_sqsum<T><<<grid, 256, 0, st>>>(part, count, (double *)slot, cold ? count : 0); });
 }
 
+// The switches as set in the environment (validated by env_validate) on a device of `num_cu` CUs.
+inline IpkTuning ipk_tuning_from_env(size_t num_cu) {
+  IpkTuning t;
+  t.num_cu = num_cu;
+  t.stream = (int)env_get("MGH_IPK_STREAM", t.stream);
+  t.dma = (int)env_get("MGH_IPK_DMA", t.dma);
+  t.dma_min = (size_t)env_get("MGH_IPK_DMA_MIN", (long)(2 * num_cu));
+  t.dma_rounds = (int)env_get("MGH_IPK_DMA_ROUNDS", t.dma_rounds);
+  t.spec = (int)env_get("MGH_IPK_SPEC", t.spec);
+  t.spec_k = (int)env_get("MGH_IPK_SPEC_K", t.spec_k);
+  t.spec_long = (int)env_get("MGH_IPK_SPEC_LONG", t.spec_long);
+  t.spec_max = (uint32_t)env_get("MGH_IPK_SPEC_MAX", (long)t.spec_max);
+  t.chunk = (int)env_get("MGH_IPK_CHUNK", t.chunk);
+  t.chunk_k = (int)env_get("MGH_IPK_CHUNK_K", t.chunk_k);
+  t.w = (uint32_t)env_get("MGH_IPK_W", t.w);
+  t.wpc = (size_t)env_get("MGH_IPK_WPC", (long)t.wpc);
+  t.kr16 = (int)env_get("MGH_IPK_KR16", t.kr16);
+  t.contig_rounds = (size_t)env_get("MGH_IPK_CONTIG", (long)t.contig_rounds);
+  return t;
+}
+
 // One body for both element types: f(T()) with the T of the hierarchy.
 template <typename F> auto with_type(const mgh_hierarchy *h, F &&f) {
   return h->dtype == MGH_FLOAT ? f(float()) : f(double());
@@ -3039,9 +2891,6 @@ int mgh_hierarchy_create(mgh_hierarchy **out, int D, const uint64_t *shape, int 
     h->force_v1 = h->force_v1_env == 1;
     h->force_nd = env_get("MGH_FORCE_ND", 0) != 0;
     h->force_nd_ipk = env_get("MGH_ND_IPK", 0) != 0;
-    h->ipk_stream = (int)env_get("MGH_IPK_STREAM", h->ipk_stream);
-    h->ipk_dma = (int)env_get("MGH_IPK_DMA", h->ipk_dma);
-    h->ipk_dma_min_env = env_get("MGH_IPK_DMA_MIN", -1);
     h->absmax_warm_mb = (int)env_get("MGH_ABSMAX_WARM_MB", h->absmax_warm_mb);
     h->fused_faces = (int)env_get("MGH_FUSED_FACES", h->fused_faces);
     h->fused_xcd = (int)env_get("MGH_FUSED_XCD", h->fused_xcd);
@@ -3052,24 +2901,13 @@ int mgh_hierarchy_create(mgh_hierarchy **out, int D, const uint64_t *shape, int 
     h->fused4 = (int)env_get("MGH_FUSED4", h->fused4);
     h->box = (int)env_get("MGH_BOX", h->box);
     h->sym16_mixed = (int)env_get("MGH_SYM16_MIXED", h->sym16_mixed);
-    h->ipk_spec = (int)env_get("MGH_IPK_SPEC", h->ipk_spec);
-    h->ipk_spec_k = (int)env_get("MGH_IPK_SPEC_K", h->ipk_spec_k);
-    h->ipk_spec_long = (int)env_get("MGH_IPK_SPEC_LONG", h->ipk_spec_long);
-    h->ipk_spec_max = (uint32_t)env_get("MGH_IPK_SPEC_MAX", (long)h->ipk_spec_max);
-    h->ipk_chunk = (int)env_get("MGH_IPK_CHUNK", h->ipk_chunk);
     h->outlier_agg = (int)env_get("MGH_OUTLIER_AGG", h->outlier_agg);
-    h->ipk_chunk_k = (int)env_get("MGH_IPK_CHUNK_K", h->ipk_chunk_k);
     h->tail_solves = (int)env_get("MGH_TAIL_SOLVES", h->tail_solves);
-    h->ipk_dma_rounds = (int)env_get("MGH_IPK_DMA_ROUNDS", h->ipk_dma_rounds);
     h->nd_rows = (int)env_get("MGH_ND_ROWS", h->nd_rows);
     h->cls1 = (size_t)env_get("MGH_CLS1", (long)h->cls1);
     h->cls2 = (size_t)env_get("MGH_CLS2", (long)h->cls2);
     if (const char *e = std::getenv("MGH_RCH")) std::sscanf(e, "%d,%d,%d", &h->rch[0], &h->rch[1], &h->rch[2]);
-    h->ipk_w = (uint32_t)env_get("MGH_IPK_W", h->ipk_w);
-    h->ipk_wpc = (size_t)env_get("MGH_IPK_WPC", (long)h->ipk_wpc);
-    h->ipk_kr16 = (int)env_get("MGH_IPK_KR16", h->ipk_kr16);
     h->ipk_range_mb = (int)env_get("MGH_IPK_RANGE_MB", h->ipk_range_mb);
-    h->ipk_contig_rounds = (size_t)env_get("MGH_IPK_CONTIG", (long)h->ipk_contig_rounds);
     h->no_head = env_get("MGH_NO_RECOMPOSE_HEAD", 0) != 0;
     h->debug_sync = env_get("MGH_DEBUG_SYNC", 0) != 0;
     if (h->force_nd) h->force_v1 = true;  // keeps the fused entry points off
@@ -3085,7 +2923,7 @@ int mgh_hierarchy_create(mgh_hierarchy **out, int D, const uint64_t *shape, int 
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0)
       h->num_cu = (size_t)cus;
   }
-  h->ipk_dma_min = h->ipk_dma_min_env >= 0 ? (size_t)h->ipk_dma_min_env : 2 * h->num_cu;
+  h->ipk = ipk_tuning_from_env(h->num_cu);
   h->D = D;
   bool ok;
   if (dtype == MGH_FLOAT) {

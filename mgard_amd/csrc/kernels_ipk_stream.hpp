@@ -35,6 +35,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "ipk_plan.hpp"
 #include "kernels_ipk.hpp"
 
 namespace mgh {
@@ -127,6 +128,7 @@ template <typename T, int U> struct TileIO {
   static constexpr int NI = 64 / RP;       // instructions per batch
   static constexpr int PITCH = U + 1;
   static constexpr int stage_elems = 64 * PITCH;
+  static_assert(stage_elems == (int)ipk_stream_stage_elems(U), "the host plans the LDS of a launch with ipk_plan.hpp's size");
   // x: first element of the tile; rows: rows of the tile that exist; i: first column.
   // issue(): the global loads only -- v holds RAW vectors (instruction m, element k at
   // v[m * VN + k]: 16 bytes of row lane / QL + m * RP) and nothing waits for them;
