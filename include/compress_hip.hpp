@@ -43,6 +43,7 @@ struct HighLevelConfig : Config {
   int zstd_compress_level = 3;
   SIZE max_memory_footprint = std::numeric_limits<SIZE>::max();
   bool auto_pin_host_buffers = false;  // (reference: true; see mgh_config_default in highlevel.hip)
+  int reorder = 0;                     // Config::reorder: 1 = level-linearised records (what ProgressiveReader reads)
 };
 
 namespace detail {
@@ -64,6 +65,7 @@ inline mgh_config to_c(const HighLevelConfig &c) {
   m.max_larget_level = c.max_larget_level;
   m.max_memory_footprint = c.max_memory_footprint;
   m.auto_pin_host_buffers = c.auto_pin_host_buffers ? 1 : 0;
+  m.reorder = c.reorder;
   return m;
 }
 inline compress_status_type status(int rc) {
@@ -147,6 +149,40 @@ inline compress_status_type infer_level_shape(const void *compressed_data, size_
   if (level >= 0) shape.assign(shp, shp + D);
   return compress_status_type::Success;
 }
+// where the coefficients of `level` lie in a reorder = 1 record (mgh_infer_level_range)
+inline compress_status_type infer_level_range(const void *compressed_data, size_t compressed_size, int level,
+                                              HighLevelConfig config, SIZE &first_elem, SIZE &num_elems,
+                                              SIZE &first_chunk, SIZE &num_chunks) {
+  const mgh_config c = detail::to_c(config);
+  uint64_t v[4] = {0, 0, 0, 0};
+  const int rc = mgh_infer_level_range(compressed_data, compressed_size, &c, level, &v[0], &v[1], &v[2], &v[3]);
+  if (rc != MGH_SUCCESS) return detail::status(rc);
+  first_elem = v[0];
+  num_elems = v[1];
+  first_chunk = v[2];
+  num_chunks = v[3];
+  return compress_status_type::Success;
+}
+// EXTENSION: a reduced-resolution reconstruction of a reorder = 1 container refined level by level
+// (mgh_progressive). The container is borrowed until the reader is destroyed.
+class ProgressiveReader {
+public:
+  ProgressiveReader(const void *compressed_data, size_t compressed_size, HighLevelConfig config = HighLevelConfig()) {
+    const mgh_config c = detail::to_c(config);
+    check(mgh_progressive_open(&p_, compressed_data, compressed_size, &c), "ProgressiveReader");
+  }
+  ~ProgressiveReader() { mgh_progressive_close(p_); }
+  ProgressiveReader(const ProgressiveReader &) = delete;
+  ProgressiveReader &operator=(const ProgressiveReader &) = delete;
+  int level() const { return mgh_progressive_level(p_); }  // -1 before the first refine
+  // the dense array of to_level (above level()), like decompress_level returns it
+  compress_status_type refine(int to_level, void *&data, bool output_pre_allocated) {
+    return detail::status(mgh_progressive_refine(p_, to_level, &data, output_pre_allocated ? 1 : 0));
+  }
+
+private:
+  mgh_progressive *p_ = nullptr;
+};
 inline compress_status_type decompress(const void *compressed_data, size_t compressed_size,
                                        void *&decompressed_data, std::vector<SIZE> &shape,
                                        data_type &dtype, HighLevelConfig config, bool output_pre_allocated) {
@@ -201,6 +237,16 @@ public:
     check(mgh_lossless_decompress(ctx_, data, size, (int)config_.lossless, c_->quantized_array(), n,
                                   &outlier_idx, &outliers, &cnt, queue),
           "LosslessDecompress");
+    outlier_count = cnt;
+  }
+  // ... of the chunks that hold integers [first, first + count) only, into `out` (mgh_lossless_decompress_range)
+  void LosslessDecompressRange(const Byte *data, SIZE size, SIZE n, SIZE first, SIZE count, QUANTIZED_INT *out,
+                               const ATOMIC_IDX *&outlier_idx, const QUANTIZED_INT *&outliers, SIZE &outlier_count,
+                               void *queue = nullptr) {
+    uint64_t cnt = 0;
+    check(mgh_lossless_decompress_range(ctx_, data, size, (int)config_.lossless, out, n, first, count, &outlier_idx,
+                                        &outliers, &cnt, queue),
+          "LosslessDecompressRange");
     outlier_count = cnt;
   }
 

@@ -273,6 +273,22 @@ int mgh_dequantize_recompose_linear_to_level(mgh_hierarchy *h, int64_t *d_linear
                                              int prep_huffman, const uint64_t *d_outlier_idx,
                                              const int64_t *d_outlier_val, uint64_t outlier_count,
                                              int level, void *d_out, void *stream);
+/* ONE LEVEL STEP of the same loop, for a caller that keeps the result of a coarser level and wants
+ * the next one (DataRefactor::Recompose(data, start_level, stop_level, queue) with
+ * start_level = level - 1, stop_level = level). level = 1 ... l_target.
+ * d_coarse: the dense array of level_shape(level - 1), as a *_to_level call or an earlier
+ * mgh_refine_level wrote it; NOT modified (the call works on a copy inside the hierarchy, 1/2^D of the
+ * output). d_segment: the N_level - N_{level-1} integers [N_{level-1}, N_level) of the level-linearised
+ * array -- the coefficients of that level and nothing else. The outlier indices are linearised
+ * positions of the WHOLE array, as above: those inside the segment are written into d_segment in
+ * place, all others are skipped. d_out: dense in level_shape(level) (MGH_LD_OUT does not apply); it
+ * must alias neither input. Bit-identical to mgh_dequantize_recompose_linear_to_level(level) on the
+ * head [0, N_level) of the same array; no work scales with anything but the box of `level`, and none
+ * of the levels below is run again. */
+int mgh_refine_level(mgh_hierarchy *h, const void *d_coarse, int64_t *d_segment, int error_bound_type,
+                     double tol, double s, double norm, uint64_t dict_size, int prep_huffman,
+                     const uint64_t *d_outlier_idx, const int64_t *d_outlier_val, uint64_t outlier_count,
+                     int level, void *d_out, void *stream);
 /* HOST only: index in the finest grid of every node of `level` along `dim`, ascending
  * (level_shape(level)[dim] entries; returns their number, or a negative status). The rule is the
  * hierarchy's own coarsening, level by level: keep every second node and always the last one. With

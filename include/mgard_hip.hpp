@@ -232,6 +232,15 @@ public:
                                                    outlier_count, level, level_data, queue),
           "DequantizeRecomposeLinearToLevel");
   }
+  // One level step (mgh_refine_level): the dense array of level - 1 and the level's own segment of the
+  // level-linearised array to the dense array of `level`; `coarse` is not modified.
+  void RefineLevel(T *level_data, int level, const T *coarse, int64_t *segment, error_bound_type ebtype, T tol, T s,
+                   T norm, SIZE outlier_count, void *queue = nullptr) {
+    check(mgh_refine_level(hierarchy_->handle(), coarse, segment, (int)ebtype, (double)tol, (double)s, (double)norm,
+                           config_.huff_dict_size, config_.prep_huffman ? 1 : 0, outlier_idx_, outliers_,
+                           outlier_count, level, level_data, queue),
+          "RefineLevel");
+  }
   void LevelBoxFromLinear(const int64_t *linear, int level, int64_t *box, void *queue = nullptr) {
     check(mgh_level_box_from_linear(hierarchy_->handle(), linear, level, box, queue), "LevelBoxFromLinear");
   }

@@ -304,6 +304,50 @@ int mgh_lossless_decompress_prefix(mgh_lossless_ctx *ctx, const uint8_t *payload
                                    const uint64_t **d_outlier_idx_out, const int64_t **d_outlier_val_out,
                                    uint64_t *outlier_count_out, void *stream);
 
+/* The same for a RANGE of integers: chunks first / chunk ... (first + count - 1) / chunk are decoded;
+ * d_quantized[0 ...) receives the integers from (first / chunk) * chunk to the end of the last decoded
+ * chunk (or n), and nothing behind that. The head is validated as for the prefix call. Of a record in
+ * host memory only the head, the code units and the synchronisation entries of the decoded chunks and
+ * the (whole) outlier lists are moved. first = 0 is the prefix call; count = 0 or a range that leaves
+ * [0, n) is an error. */
+int mgh_lossless_decompress_range(mgh_lossless_ctx *ctx, const uint8_t *payload, uint64_t size, int lossless,
+                                  int64_t *d_quantized, uint64_t n, uint64_t first, uint64_t count,
+                                  const uint64_t **d_outlier_idx_out, const int64_t **d_outlier_val_out,
+                                  uint64_t *outlier_count_out, void *stream);
+
+/* HOST only (like mgh_infer_level_shape): where the coefficients of `level` lie in a level-linearised
+ * (reorder = 1) record -- integers [first_elem, first_elem + num_elems) with first_elem = N_{level-1}
+ * (0 for level 0) and N_l = prod(level_shape(l)) -- and the Huffman chunks that hold them, by the
+ * header's huff_block_size. Any out pointer may be NULL. Decomposed containers and levels outside
+ * 0 ... l_target are refused like mgh_infer_level_shape refuses them. */
+int mgh_infer_level_range(const void *compressed_data, size_t compressed_size, const mgh_config *config,
+                          int level, uint64_t *first_elem, uint64_t *num_elems, uint64_t *first_chunk,
+                          uint64_t *num_chunks);
+
+/* ---- Progressive reader (EXTENSION; DataRefactor::Recompose(data, start_level, stop_level, queue),
+ * DataRefactor.hpp:108-124, is the reference's notion of a partial walk): a coarse level now, finer
+ * ones when they are wanted, without starting over.
+ * open: parses and validates the head once, uploads decode tables, chunk table and outlier lists once
+ * (a Huffman_Zstd frame is inflated once; a RAW record is turned into its level-linearised integers
+ * once, by the route of mgh_decompress_level). The container is BORROWED: the caller keeps it alive
+ * and unchanged until close. Host and device containers as for mgh_decompress. Needs a container with
+ * ONE subdomain (else MGH_ERR_INVALID_ARGUMENT, as mgh_decompress_level) written with reorder = 1
+ * (else MGH_ERR_INVALID_ARGUMENT: the levels of a reorder = 0 record are spread over every chunk).
+ * refine: to_level must be ABOVE mgh_progressive_level (-1 before the first call), else
+ * MGH_ERR_INVALID_ARGUMENT. Decodes only chunks not decoded before (the tail of a boundary chunk stays
+ * on the device: every chunk is decoded at most once over any sequence of calls), runs
+ * mgh_refine_level per level (the first call: mgh_dequantize_recompose_linear_to_level) and returns
+ * the dense array of to_level like mgh_decompress_level returns it (in the container's memory space,
+ * or in the caller's buffer). Bit-identical to mgh_decompress_level(to_level); at l_target to
+ * mgh_decompress. The nodal array of the current level stays on the device as the state.
+ * mgh_last_decompress_stats reports each refine's own chunks. */
+typedef struct mgh_progressive mgh_progressive;
+int mgh_progressive_open(mgh_progressive **out, const void *compressed_data, size_t compressed_size,
+                         const mgh_config *config);
+int mgh_progressive_level(const mgh_progressive *p);
+int mgh_progressive_refine(mgh_progressive *p, int to_level, void **data, int output_pre_allocated);
+void mgh_progressive_close(mgh_progressive *p);
+
 #ifdef __cplusplus
 }
 #endif

@@ -32,6 +32,7 @@ SYMBOLS = [
     "mgh_recompose_to_level", "mgh_dequantize_recompose_to_level",
     "mgh_dequantize_recompose_sym16_to_level", "mgh_level_nodes",
     "mgh_level_box_from_linear", "mgh_dequantize_recompose_linear_to_level",
+    "mgh_refine_level",
 ]
 
 
@@ -105,6 +106,8 @@ def load_library():
     L.mgh_level_box_from_linear.argtypes = [vp, vp, C.c_int, vp, vp]
     L.mgh_dequantize_recompose_linear_to_level.argtypes = [vp, vp, C.c_int, C.c_double, C.c_double, C.c_double,
                                                            u64, C.c_int, vp, vp, u64, C.c_int, vp, vp]
+    L.mgh_refine_level.argtypes = [vp, vp, vp, C.c_int, C.c_double, C.c_double, C.c_double, u64, C.c_int, vp, vp, u64,
+                                   C.c_int, vp, vp]
     L.mgh_level_nodes.argtypes = [vp, C.c_int, C.c_int, u64p, u64]
     L.mgh_stream_calibrate.argtypes = [C.c_int, vp, vp, vp, u64, C.c_int, C.POINTER(C.c_double), vp]
     _lib = L
@@ -455,6 +458,35 @@ class Hierarchy:
             self._h, C.c_void_p(lin.data_ptr()), ebtype, tol, s, norm, dict_size, int(prep_huffman),
             C.c_void_p(outlier_idx.data_ptr() if n else 0), C.c_void_p(outlier_val.data_ptr() if n else 0),
             n, level, C.c_void_p(out.data_ptr()), _stream()))
+        return out
+
+    def refine_level(self, coarse, segment, ebtype, tol, s, norm, level, dict_size=8192, prep_huffman=True,
+                     outlier_idx=None, outlier_val=None, out=None):
+        """mgh_refine_level: one level step. `coarse`: the dense array of level_shape(level - 1) (not
+        modified); `segment`: the prod(level_shape(level)) - prod(level_shape(level - 1)) integers of
+        `level` in the level-linearised array (outliers of the level are written into it; the indices
+        are linearised positions of the whole array). Returns the dense array of `level`."""
+        import torch
+        level = int(level)
+        if not 1 <= level <= self.l_target:
+            raise ValueError("level must be in 1 .. l_target")
+        lo = hi = 1
+        for e in self.level_shape(level - 1):
+            lo *= int(e)
+        for e in self.level_shape(level):
+            hi *= int(e)
+        if not (coarse.is_cuda and coarse.is_contiguous() and coarse.dtype == self.torch_dtype and
+                coarse.numel() == lo):
+            raise ValueError("coarse: expected the contiguous cuda array of level %d (%d elements)" % (level - 1, lo))
+        if not (segment.is_cuda and segment.dtype == torch.int64 and segment.is_contiguous() and
+                segment.numel() >= hi - lo):
+            raise ValueError("segment: expected a contiguous cuda int64 tensor of at least %d elements" % (hi - lo))
+        n = 0 if outlier_idx is None else int(outlier_idx.numel())
+        out = self._level_out(level, out, coarse.device)
+        _check(load_library().mgh_refine_level(
+            self._h, C.c_void_p(coarse.data_ptr()), C.c_void_p(segment.data_ptr()), ebtype, tol, s, norm, dict_size,
+            int(prep_huffman), C.c_void_p(outlier_idx.data_ptr() if n else 0),
+            C.c_void_p(outlier_val.data_ptr() if n else 0), n, level, C.c_void_p(out.data_ptr()), _stream()))
         return out
 
     # ---- per-kernel timing (HIP events on the launch stream) ----

@@ -1624,8 +1624,9 @@ template <typename T> int decompose_nd(mgh_hierarchy *h, T *v, hipStream_t st, c
   return MGH_SUCCESS;
 }
 
-// (stop >= 0: `v` is the dense corner box of level `stop`, and the loop ends there)
-template <typename T> int recompose_nd(mgh_hierarchy *h, T *v, hipStream_t st, int stop = -1) {
+// (stop >= 0: `v` is the dense corner box of level `stop`, and the loop ends there; start >= 1: the
+// corner box of level start - 1 inside `v` holds that level's nodal values, and the loop begins at start)
+template <typename T> int recompose_nd(mgh_hierarchy *h, T *v, hipStream_t st, int stop = -1, int start = 0) {
   auto *ds = DS<T>(h);
   size_t count = 0;
   if (stop >= 0) {
@@ -1633,7 +1634,7 @@ template <typename T> int recompose_nd(mgh_hierarchy *h, T *v, hipStream_t st, i
     for (int d = 0; d < h->D; d++) count *= HH<T>(h)->level_shape[stop][d];
   }
   TRY(nd_ensure<T>(h, count));
-  for (int l = 1; l <= (stop < 0 ? h->L : stop); l++) {
+  for (int l = std::max(1, start); l <= (stop < 0 ? h->L : stop); l++) {
     const NdBox b = nd_box<T>(h, l, stop);
     NdTables<T> tb{};
     uint64_t nn = 1, mm = 1;
@@ -1717,22 +1718,24 @@ int decompose_dense(mgh_hierarchy *h, const T *data, T *coeff, hipStream_t s) {
 
 template <typename T, typename QT, typename QTL = QT>
 int recompose_levels(mgh_hierarchy *h, RecomposeArgs<T> A, const std::vector<T> &level_qv, T *data, const Layout &out,
-                     hipStream_t st, const RecomposeArgs<T> *AL = nullptr, int ntop = 1, int stop = -1);
+                     hipStream_t st, const RecomposeArgs<T> *AL = nullptr, int ntop = 1, int stop = -1, int start = 0);
 
 template <typename T, typename QT, typename QTL = QT>
 int recompose_levels4(mgh_hierarchy *h, RecomposeArgs<T> A, const std::vector<T> &level_qv, T *data,
                       hipStream_t st, const RecomposeArgs<T> *AL = nullptr, size_t A_sT = 0, int ntop = 1,
-                      int stop = -1);
+                      int stop = -1, int start = 0);
 
 // The level loop of the one-thread-per-element kernels (D <= 3): coefficients C with strides
 // (cI, cJ, 1) in the 3-D view, levels 1 .. Ls. Ls == L: `data` has the full array's strides;
-// below (mgh_*_to_level) it is the dense array of level Ls.
+// below (mgh_*_to_level) it is the dense array of level Ls. start >= 1 (mgh_refine_level): levels
+// start .. Ls alone, with the nodal values of level start - 1 in ds->nodal[start - 1] already.
 template <typename T>
-int recompose_v1_levels(mgh_hierarchy *h, const T *C, size_t cI, size_t cJ, T *data, int Ls, hipStream_t s) {
+int recompose_v1_levels(mgh_hierarchy *h, const T *C, size_t cI, size_t cJ, T *data, int Ls, hipStream_t s,
+                        int start = 0) {
   auto *ds = DS<T>(h);
   const int L = h->L;
   const dim3 blk(64, 4, 1);
-  {
+  if (start < 1) {
     const Box3 &b = ds->lt[1].box;
     TRY(launch(h, "copy_box", s, [&] {
       k_copy_box<T><<<grid3(b.m[0], b.m[1], b.m[2], blk), blk, 0, s>>>(
@@ -1740,7 +1743,7 @@ int recompose_v1_levels(mgh_hierarchy *h, const T *C, size_t cI, size_t cJ, T *d
           (size_t)b.m[2]);
     }));
   }
-  for (int l = 1; l <= Ls; l++) {
+  for (int l = std::max(1, start); l <= Ls; l++) {
     const LevelTables<T> &t = ds->lt[l];
     const Box3 &b = t.box;
     T *coarse = ds->nodal[l - 1];
@@ -1896,9 +1899,11 @@ int launch_loadvec(mgh_hierarchy *h, const RecomposeArgs<T> &A, const Box3 &b, h
 // kernels write in place (Layout::native3).
 // stop >= 0 (mgh_*_to_level): the loop ends at that level and `data` is the DENSE array of its
 // shape -- the strides of the compact nodal buffer it stands in for.
+// start >= 1 (mgh_refine_level): the levels start .. Ls alone, each with its own launches -- the
+// corrected nodal values of level start - 1 are in ds->nodal[start - 1] already, nothing below is run.
 template <typename T, typename QT, typename QTL>
 int recompose_levels(mgh_hierarchy *h, RecomposeArgs<T> A, const std::vector<T> &level_qv, T *data, const Layout &out,
-                     hipStream_t st, const RecomposeArgs<T> *AL, int ntop, int stop) {
+                     hipStream_t st, const RecomposeArgs<T> *AL, int ntop, int stop, int start) {
   auto *ds = DS<T>(h);
   const int L = h->L;
   const int Ls = stop < 0 ? L : stop;  // the last level run
@@ -1906,7 +1911,7 @@ int recompose_levels(mgh_hierarchy *h, RecomposeArgs<T> A, const std::vector<T> 
   // MGH_NO_RECOMPOSE_HEAD=1: every level with its own launches (cross-check)
   const bool no_head = h->no_head;
   int l_head = 0;
-  if (!no_head) {
+  if (!no_head && start < 1) {
     for (int l = 1; l <= std::min(std::min(AL ? L - ntop : L, Ls), kTailMaxLevels); l++) {
       if ((head_lds_elems(ds->lt[l].box) + ds->lt_end[l]) * sizeof(T) > 150 * 1024) break;
       l_head = l;
@@ -1938,7 +1943,7 @@ int recompose_levels(mgh_hierarchy *h, RecomposeArgs<T> A, const std::vector<T> 
     static std::atomic<uint64_t> once{0};
     TRY(allow_big_lds_once(k_recompose_head<T, QT>, once));
     TRY(launch(h, "recompose_head", st, [&] { k_recompose_head<T, QT><<<1, 1024, lds, st>>>(HA); }));
-  } else {
+  } else if (start < 1) {
     const Box3 &b = ds->lt[1].box;
     A.qv = level_qv[0];
     TRY(launch(h, "head_in", st, [&] {
@@ -1947,7 +1952,7 @@ int recompose_levels(mgh_hierarchy *h, RecomposeArgs<T> A, const std::vector<T> 
           (int)b.m[0], (int)b.m[1], (int)b.m[2], A, Ls == 0 ? data : ds->nodal[0]);
     }));
   }
-  for (int l = l_head + 1; l <= Ls; l++) {
+  for (int l = std::max(l_head + 1, start); l <= Ls; l++) {
     const LevelTables<T> &t = ds->lt[l];
     const Box3 &b = t.box;
     const bool top = AL && l > L - ntop;
@@ -1979,10 +1984,11 @@ int recompose_levels(mgh_hierarchy *h, RecomposeArgs<T> A, const std::vector<T> 
 // solves subtracting the correction from the coarse nodes, then the node restore slice by slice
 // (odd slices interpolate across t between the two neighbouring coarse slices).
 // A_sT: element stride between two t-slices of A's source (0: the full array's). AL / QTL as in
-// recompose_levels (the finest level's source has the full array's strides).
+// recompose_levels (the finest level's source has the full array's strides). start as there: the
+// nodal values of level start - 1 are in ds->nodal4[start - 1].
 template <typename T, typename QT, typename QTL>
 int recompose_levels4(mgh_hierarchy *h, RecomposeArgs<T> A0, const std::vector<T> &level_qv, T *data,
-                      hipStream_t st, const RecomposeArgs<T> *AL, size_t A_sT, int ntop, int stop) {
+                      hipStream_t st, const RecomposeArgs<T> *AL, size_t A_sT, int ntop, int stop, int start) {
   auto *ds = DS<T>(h);
   auto *hh = HH<T>(h);
   const int L = h->L;
@@ -1996,7 +2002,7 @@ int recompose_levels4(mgh_hierarchy *h, RecomposeArgs<T> A0, const std::vector<T
     A0.dI = full[1];
     A0.dJ = full[2];
   }
-  {
+  if (start < 1) {
     const auto &M0 = sh[0];
     const size_t tot = (size_t)M0[0] * M0[1] * M0[2] * M0[3];
     A0.qv = level_qv[0];
@@ -2005,7 +2011,7 @@ int recompose_levels4(mgh_hierarchy *h, RecomposeArgs<T> A0, const std::vector<T
           (int)M0[0], (int)M0[1], (int)M0[2], (int)M0[3], A0, A_sT, Ls == 0 ? data : ds->nodal4[0]);
     }));
   }
-  for (int l = 1; l <= Ls; l++) {
+  for (int l = std::max(1, start); l <= Ls; l++) {
     const bool top = AL && l > L - ntop;
     RecomposeArgs<T> A = top ? *AL : A0;
     const size_t sT = top ? full[0] : A_sT;
@@ -3278,6 +3284,34 @@ int box_from_linear(mgh_hierarchy *h, const int64_t *lin, int level, int64_t *bo
   return launch(h, "box_from_linear", st, [&] { mgh::k_box_from_linear<<<grid, 256, 0, st>>>(m, B, lin, box); });
 }
 
+// The shell of the compact box of `level` (dense in level_shape(level)) out of the level's own segment
+// [N_{level-1}, N_level) of a level-linearised array: k_shell_from_linear. fill_inner: the inner box
+// of level - 1 gets `inner` (the fused node restore loads those positions).
+int shell_from_linear(mgh_hierarchy *h, const int64_t *seg, int level, int64_t *box, bool fill_inner, int64_t inner,
+                      hipStream_t st) {
+  if (h->L + 1 > mgh::kLinMaxLevels + 1) return fail(MGH_ERR_INVALID_ARGUMENT, "too many levels");
+  mgh::LinMeta m{};
+  (void)lin_meta(h, m);
+  mgh::LinBox B{};
+  B.level = level;
+  const int D = h->D;
+  uint64_t bs = 1;
+  for (int d = D - 1; d >= 0; d--) {
+    B.bs[d] = bs;
+    bs *= m.lshape[level][d];
+  }
+  for (int k = 0; k < 2; k++) {  // the runs of the level; the rows of the inner box
+    const uint32_t *e = m.lshape[level - k];
+    uint64_t rows = 1;
+    for (int d = 0; d < D - 1; d++) rows *= e[d];
+    const uint64_t units = k == 1 && !fill_inner ? 0 : rows * ((e[D - 1] + kLevelBoxPiece - 1) / kLevelBoxPiece);
+    if (units >= ((uint64_t)1 << 32)) return fail(MGH_ERR_INVALID_ARGUMENT, "level box too large");
+    B.unit0[k + 1] = B.unit0[k] + units;
+  }
+  const unsigned grid = (unsigned)std::min<uint64_t>((B.unit0[2] + 3) / 4, 256 * 32);
+  return launch(h, "shell_from_linear", st, [&] { mgh::k_shell_from_linear<<<grid, 256, 0, st>>>(m, B, seg, box, inner); });
+}
+
 uint64_t level_elems(const mgh_hierarchy *h, int level) {
   uint64_t n = 1;
   auto f = [&](auto *hh) {
@@ -3381,6 +3415,106 @@ int mgh_dequantize_recompose_linear_to_level(mgh_hierarchy *h, int64_t *d_linear
                                            nullptr, 0, (T *)d_out, dense_layout(h), st, level, m.data());
     return dequantize_recompose_box_to_level<T>(h, ds->qbox, ebtype, tol, s, norm, dict_size, prep_huffman, nullptr,
                                                 nullptr, 0, level, (T *)d_out, st, /*compact=*/true);
+  });
+}
+
+// One level step: the dense nodal array of level - 1 and the level's own segment of a level-linearised
+// array to the dense array of `level` -- one pass of the level loop of
+// mgh_dequantize_recompose_linear_to_level, with the box of the level made from the segment alone.
+extern "C++" {
+template <typename T>
+static int refine_level(mgh_hierarchy *h, const T *coarse, int64_t *seg, int ebtype, double tol, double s, double norm,
+                        uint64_t dict_size, int prep_huffman, const uint64_t *oidx, const int64_t *oval,
+                        uint64_t ocount, int level, T *out, hipStream_t st) {
+  auto *ds = DS<T>(h);
+  auto *hh = HH<T>(h);
+  const int D = h->D, L = h->L;
+  const uint64_t n_lo = level_elems(h, level - 1), n_hi = level_elems(h, level);
+  if (prep_huffman && ocount) {  // (linearised positions of the whole array: those of this level)
+    TRY(launch(h, "outlier_restore_window", st, [&] {
+      k_outlier_restore_window<<<(unsigned)((ocount + 255) / 256), 256, 0, st>>>(seg, n_lo, n_hi, oidx, oval, ocount);
+    }));
+  }
+  if (n_hi > ds->qbox_elems) {  // (counted in mgh_device_bytes)
+    dev_free(h, &ds->qbox, ds->qbox_elems);
+    ds->qbox_elems = 0;
+    TRY(dev_alloc(h, &ds->qbox, n_hi));
+    ds->qbox_elems = n_hi;
+  }
+  const bool fused = fusedc_ok(h) && !h->force_v1;
+  const int64_t half = prep_huffman ? (int64_t)(dict_size / 2) : 0;
+  TRY(shell_from_linear(h, seg, level, ds->qbox, fused, half, st));
+  const auto &m = hh->level_shape[level];
+  if (fused) {
+    // the r-solve subtracts the correction from the coarse nodes in place: on a copy
+    if (D == 4) TRY(ensure_state4<T>(h));
+    T *nodal = D == 4 ? ds->nodal4[level - 1] : ds->nodal[level - 1];
+    TRY(launch(h, "refine_coarse_in", st, [&] {
+      (void)hipMemcpyAsync(nodal, coarse, n_lo * sizeof(T), hipMemcpyDeviceToDevice, st);
+    }));
+    std::vector<T> qz(L + 1);
+    hh->quantizers(ebtype, (T)tol, (T)s, (T)norm, false, qz.data());
+    const bool calc_vol = !((T)s == std::numeric_limits<T>::infinity());
+    std::vector<T> level_qv(L + 1);
+    for (int l = 0; l <= L; l++) level_qv[l] = qz[l] * (calc_vol ? hh->level_volume(l, true) : (T)1);
+    RecomposeArgs<T> A{};
+    A.q = ds->qbox;
+    A.half = half;
+    A.dJ = m[D - 1];
+    A.dI = m[D - 2] * m[D - 1];
+    if (D == 4)
+      return recompose_levels4<T, int64_t>(h, A, level_qv, out, st, nullptr, (size_t)(m[1] * m[2] * m[3]), 1, level, level);
+    return recompose_levels<T, int64_t>(h, A, level_qv, out, dense_layout(h), st, nullptr, 1, level, level);
+  }
+  // the other shapes: a compact floating-point box -- inner box = the coarse array, shell dequantized
+  TRY(upload_quantizers<T>(h, ebtype, tol, s, norm, false, st));
+  LevelBox lb{};
+  lb.D = D;
+  for (int d = 0; d < D; d++) {
+    lb.m[d] = (uint32_t)m[d];
+    lb.n[d] = (uint32_t)hh->level_shape[level - 1][d];
+  }
+  uint64_t bs = 1;
+  for (int d = D - 1; d >= 0; d--) {
+    lb.ss[d] = bs;
+    bs *= lb.m[d];
+  }
+  const uint64_t rows = level_box_rows(lb);
+  auto fill = [&](T *dst) {
+    return launch(h, "box_refine_fill", st, [&] {
+      k_box_refine_fill<T><<<level_box_grid(lb), 256, 0, st>>>(lb, ds->qmeta, ds->qbox, coarse, ds->marks, ds->qz,
+                                                                  ds->qz + (L + 1), (int64_t)dict_size, prep_huffman,
+                                                                  dst, rows);
+    });
+  };
+  if (D > 3 || h->force_nd) {  // (the generic N-D kernels work in place: the box is the output)
+    TRY(fill(out));
+    return recompose_nd<T>(h, out, st, level, level);
+  }
+  TRY(ensure_level_box<T>(h, n_hi));
+  TRY(fill(ds->level_box));
+  TRY(launch(h, "refine_coarse_in", st, [&] {
+    (void)hipMemcpyAsync(ds->nodal[level - 1], coarse, n_lo * sizeof(T), hipMemcpyDeviceToDevice, st);
+  }));
+  const size_t cJ = m[D - 1], cI = (D >= 2 ? m[D - 2] : 1) * cJ;
+  return recompose_v1_levels<T>(h, ds->level_box, cI, cJ, out, level, st, level);
+}
+}  // extern "C++"
+
+int mgh_refine_level(mgh_hierarchy *h, const void *d_coarse, int64_t *d_segment, int ebtype, double tol, double s,
+                     double norm, uint64_t dict_size, int prep_huffman, const uint64_t *d_outlier_idx,
+                     const int64_t *d_outlier_val, uint64_t outlier_count, int level, void *d_out, void *stream) {
+  if (!h || !d_coarse || !d_segment || !d_out) return fail(MGH_ERR_INVALID_ARGUMENT, "null argument");
+  if (prep_huffman && outlier_count && (!d_outlier_idx || !d_outlier_val))
+    return fail(MGH_ERR_INVALID_ARGUMENT, "null outlier list");
+  if (level < 1 || level > h->L) return fail(MGH_ERR_INVALID_ARGUMENT, "mgh_refine_level: level outside 1 .. l_target");
+  if (d_out == d_coarse || d_out == (void *)d_segment)
+    return fail(MGH_ERR_INVALID_ARGUMENT, "mgh_refine_level: d_out must not alias an input");
+  HIP_TRY(hipSetDevice(h->device));
+  return with_type(h, [&](auto t) {
+    using T = decltype(t);
+    return refine_level<T>(h, (const T *)d_coarse, d_segment, ebtype, tol, s, norm, dict_size, prep_huffman,
+                           d_outlier_idx, d_outlier_val, outlier_count, level, (T *)d_out, (hipStream_t)stream);
   });
 }
 

@@ -287,6 +287,11 @@ struct mgh_lossless_ctx {
   // `direct`): record_write() does not move them again
   bool units_in_place = false;
   std::vector<uint32_t> h_dtable;  // decompression: two-level decode table (source of an asynchronous upload)
+  // A reader that comes back to ONE record (mgh_progressive). 1: the next lossless_decompress() parses
+  // the head, inflates a Zstd frame, uploads the decode tables, the whole chunk table and the outlier
+  // lists, and keeps them (-> 2); 2: all that is in place -- a call moves only the code units and
+  // synchronisation entries of the chunks it decodes.
+  int keep = 0;
   size_t record_size() const { return overflow ? ~(size_t)0 : (on_host ? host.size() : lay.total); }
 };
 
@@ -798,15 +803,26 @@ inline mgh_decompress_stats &decompress_stats() {
 // integers are decoded -- d_q[0 .. min(n, chunks * chunk)) is written, nothing behind it -- and of a
 // record that has to be copied only what those chunks need is moved. q_cap: elements d_q holds (the
 // record's own chunk length decides what is written; one that needs more is refused).
+// first > 0 (mgh_lossless_decompress_range): the chunks in front of the one that holds integer `first`
+// are left out as well -- d_q[0] is the first integer of chunk first / chunk, and the decoders run on
+// the chunk-table entries, synchronisation entries and code units of the range alone.
+// n_prefix == 0: nothing is decoded (a context with keep == 1 only: the reader's open).
 int lossless_decompress(mgh_lossless_ctx *c, const uint8_t *payload, uint64_t size, int lossless,
                         int64_t *d_q, uint64_t n, uint64_t *ocount_out, hipStream_t st,
                         bool *sym16 = nullptr, bool sync_end = true, uint64_t n_prefix = ~(uint64_t)0,
-                        uint64_t q_cap = ~(uint64_t)0) {
-  if (n_prefix == 0) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "lossless_decompress: empty prefix");
+                        uint64_t q_cap = ~(uint64_t)0, uint64_t first = 0) {
+  if (n_prefix == 0 && c->keep != 1) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "lossless_decompress: empty prefix");
+  if (n_prefix != 0 && first >= std::min<uint64_t>(n_prefix, n))
+    return hl_fail(MGH_ERR_INVALID_ARGUMENT, "lossless_decompress: empty range");
+  const bool kept = c->keep == 2;  // head, tables, lists (and the inflated frame) are those of this record already
   const uint8_t *p = payload;
   uint64_t psize = size;
   bool on_dev = is_device_pointer(payload);
-  if (lossless == MGH_LOSSLESS_HUFFMAN_ZSTD) {
+  if (lossless == MGH_LOSSLESS_HUFFMAN_ZSTD && kept) {
+    p = c->host2.data();
+    psize = c->host2.size();
+    on_dev = false;
+  } else if (lossless == MGH_LOSSLESS_HUFFMAN_ZSTD) {
     if (!g_zstd.load()) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "lossless: libzstd.so.1 not found");
     if (size < 8) return hl_fail(MGH_ERR_FORMAT, "zstd record truncated");
     const uint8_t *src = payload;
@@ -838,7 +854,7 @@ int lossless_decompress(mgh_lossless_ctx *c, const uint8_t *payload, uint64_t si
     else std::memcpy(head.data() + have, p + have, upto - have);
     return MGH_SUCCESS;
   };
-  head.clear();
+  if (!kept) head.clear();
   if (!need(0, 24)) return hl_fail(MGH_ERR_FORMAT, "Huffman record truncated");
   // (a record in device memory: one copy that covers the whole leading part for the default
   // parameters instead of one per field -- every synchronous copy costs tens of microseconds)
@@ -855,9 +871,13 @@ int lossless_decompress(mgh_lossless_ctx *c, const uint8_t *payload, uint64_t si
     return hl_fail(MGH_ERR_FORMAT, "Huffman record: header does not match the subdomain");
   const size_t nchunk = huffmeta_size / 2;
   // the chunks decoded, and the integers they hold
-  const size_t ndec = std::min<size_t>(nchunk, (size_t)((std::min<uint64_t>(n_prefix, n) - 1) / (uint64_t)chunk + 1));
+  // (chunks [cf, ndec); d_q[0] is integer cf * chunk)
+  const size_t ndec = n_prefix == 0 ? 0 : std::min<size_t>(nchunk, (size_t)((std::min<uint64_t>(n_prefix, n) - 1) / (uint64_t)chunk + 1));
+  const size_t cf = (size_t)(first / (uint64_t)chunk);
   const size_t n_dec = (size_t)std::min<uint64_t>(n, (uint64_t)ndec * (uint64_t)chunk);
-  if (n_dec > q_cap) return hl_fail(MGH_ERR_FORMAT, "Huffman record: chunk length does not match the header");
+  if (ndec && n_dec - cf * (size_t)chunk > q_cap) return hl_fail(MGH_ERR_FORMAT, "Huffman record: chunk length does not match the header");
+  // chunk-table entries on the device: those of the range, or (a kept context) the whole table
+  const size_t tb0 = c->keep ? 0 : cf, tb_cnt = c->keep ? nchunk : ndec - cf;
   PayloadLayout L;
   L.compute(nchunk, (size_t)dict, 0, 0);
   if (!need(0, L.ddata)) return hl_fail(MGH_ERR_FORMAT, "Huffman record truncated");
@@ -895,21 +915,25 @@ int lossless_decompress(mgh_lossless_ctx *c, const uint8_t *payload, uint64_t si
   if (env_get("MGH_HUFF_SYNC_DECODE", 1) == 0) has_sync = false;  // cross-check: decode without them
   // the chunk entries must stay inside the unit array (they index it in the decoder)
   size_t units_need = 0;  // code units up to the end of the last chunk decoded
+  size_t units_lo = 0;    // ... and the first one of the first chunk decoded
   {
     const uint64_t *bits = reinterpret_cast<const uint64_t *>(head.data() + L.huffmeta);
     const uint64_t *ent = bits + nchunk;
+    if (cf) units_lo = units;
     for (size_t k = 0; k < nchunk; k++) {
       if (ent[k] > units || (bits[k] + 63) / 64 > units - ent[k])
         return hl_fail(MGH_ERR_FORMAT, "Huffman record: chunk outside the code stream");
       if (k < ndec) units_need = std::max<size_t>(units_need, ent[k] + (bits[k] + 63) / 64);
+      if (cf && k >= cf && k < ndec) units_lo = std::min<size_t>(units_lo, ent[k]);
     }
   }
   if (ndec == nchunk) units_need = units;
+  units_lo = std::min(units_lo, units_need);
   hl_debug("lossless_decompress: record head parsed");
   mgh_decompress_stats &stats = decompress_stats();
   stats.chunks_total += nchunk;
-  stats.chunks_decoded += ndec;
-  stats.symbols_decoded += n_dec;
+  stats.chunks_decoded += ndec - std::min(cf, ndec);
+  stats.symbols_decoded += ndec ? n_dec - cf * (size_t)chunk : 0;
   stats.record_bytes += size;
   HL_TRY(c->bits.ensure(nchunk * 8));
   HL_TRY(c->entry.ensure(nchunk * 8));
@@ -931,12 +955,14 @@ int lossless_decompress(mgh_lossless_ctx *c, const uint8_t *payload, uint64_t si
       P.bytes[P.n] = bytes;
       P.n++;
     };
-    piece(p + L.huffmeta, c->bits.p, ndec * 8);
-    piece(p + L.huffmeta + nchunk * 8, c->entry.p, ndec * 8);
-    piece(p + L.decodebook, c->tables.p, dbsize);
-    piece(p + o_oidx, c->oidx.p, ocount * 8);
-    piece(p + o_oval, c->oval.p, ocount * 8);
-    if (has_sync) {
+    if (!kept) {
+      piece(p + L.huffmeta + tb0 * 8, c->bits.p, tb_cnt * 8);
+      piece(p + L.huffmeta + (nchunk + tb0) * 8, c->entry.p, tb_cnt * 8);
+      piece(p + L.decodebook, c->tables.p, dbsize);
+      piece(p + o_oidx, c->oidx.p, ocount * 8);
+      piece(p + o_oval, c->oval.p, ocount * 8);
+    }
+    if (has_sync && !kept) {
       // The section was recognised by the record's size alone (no host copy of its tag): the kernel
       // looks at the tag and clears a pinned word if it is not one; whoever synchronises the stream
       // next turns that into MGH_ERR_FORMAT (lossless_tag_check) -- a damaged record must not decode
@@ -956,13 +982,15 @@ int lossless_decompress(mgh_lossless_ctx *c, const uint8_t *payload, uint64_t si
     size_t tot = 0;
     for (int i = 0; i < P.n; i++) tot += P.bytes[i];
     stats.record_bytes_moved += tot;
-    k_record_pieces<<<(unsigned)std::min<size_t>(std::max<size_t>(tot / (256 * 64), 1), 512), 256, 0, st>>>(P);
-    HL_HIP(hipGetLastError());
-  } else {
-    HL_HIP(hipMemcpyAsync(c->bits.p, meta_src + L.huffmeta, ndec * 8, hipMemcpyDefault, st));
-    HL_HIP(hipMemcpyAsync(c->entry.p, meta_src + L.huffmeta + nchunk * 8, ndec * 8, hipMemcpyDefault, st));
+    if (!kept) {
+      k_record_pieces<<<(unsigned)std::min<size_t>(std::max<size_t>(tot / (256 * 64), 1), 512), 256, 0, st>>>(P);
+      HL_HIP(hipGetLastError());
+    }
+  } else if (!kept) {
+    HL_HIP(hipMemcpyAsync(c->bits.p, meta_src + L.huffmeta + tb0 * 8, tb_cnt * 8, hipMemcpyDefault, st));
+    HL_HIP(hipMemcpyAsync(c->entry.p, meta_src + L.huffmeta + (nchunk + tb0) * 8, tb_cnt * 8, hipMemcpyDefault, st));
     HL_HIP(hipMemcpyAsync(c->tables.p, meta_src + L.decodebook, dbsize, hipMemcpyDefault, st));
-    stats.record_bytes_moved += 2 * ndec * 8 + dbsize;
+    stats.record_bytes_moved += 2 * tb_cnt * 8 + dbsize;
   }
   static const bool serial_decode = env_get("MGH_HUFF_SERIAL_DECODE", 0) != 0;  // cross-check
   static const bool par_decode = env_get("MGH_HUFF_PAR_DECODE", 0) != 0;           // cross-check
@@ -988,18 +1016,21 @@ int lossless_decompress(mgh_lossless_ctx *c, const uint8_t *payload, uint64_t si
   if (units_in_place) {
     d_units = (const unsigned long long *)(p + L.ddata);
   } else {
-    HL_TRY(c->units.ensure((units_need + 1) * 8));  // (not for units decoded in place: 8 N bytes a lane would hold for nothing)
-    d_units = (const unsigned long long *)c->units.p;
+    // (not for units decoded in place: 8 N bytes a lane would hold for nothing. The entries of the
+    // chunk table count from the start of the stream: the pointer is moved down by what is left out)
+    HL_TRY(c->units.ensure((units_need - units_lo + 1) * 8));
+    d_units = (const unsigned long long *)c->units.p - units_lo;
     // A large record in HOST memory is decoded while it arrives (below: the ring decoder's launches
     // follow the pieces of the copy, which runs on the cache's copy stream); everything else is
     // copied here, in stream order. (A record in pageable memory travels through the pinned ring.)
-    units_follow = !on_dev && ring_decode && units_need * 8 >= ((size_t)32 << 20) && cache_copy_stream(c->dev) &&
+    units_follow = !on_dev && ring_decode && (units_need - units_lo) * 8 >= ((size_t)32 << 20) && cache_copy_stream(c->dev) &&
                    env_get("MGH_HL_DECODE_FOLLOWS", 1) != 0;
-    if (units_need && !units_follow) HL_TRY(copy_any(c->units.p, p + L.ddata, units_need * 8, st));
-    HL_HIP(hipMemsetAsync((char *)c->units.p + units_need * 8, 0, 8, st));  // (the decoder peeks one unit ahead)
-    stats.record_bytes_moved += units_need * 8;
+    if (units_need > units_lo && !units_follow)
+      HL_TRY(copy_any(c->units.p, p + L.ddata + units_lo * 8, (units_need - units_lo) * 8, st));
+    HL_HIP(hipMemsetAsync((char *)c->units.p + (units_need - units_lo) * 8, 0, 8, st));  // (the decoder peeks one unit ahead)
+    stats.record_bytes_moved += (units_need - units_lo) * 8;
   }
-  if (ocount && !pieces) {
+  if (ocount && !pieces && !kept) {
     stats.record_bytes_moved += 16 * ocount;
     HL_HIP(hipMemcpyAsync(c->oidx.p, p + o_oidx, ocount * 8, hipMemcpyDefault, st));
     HL_HIP(hipMemcpyAsync(c->oval.p, p + o_oval, ocount * 8, hipMemcpyDefault, st));
@@ -1038,15 +1069,19 @@ int lossless_decompress(mgh_lossless_ctx *c, const uint8_t *payload, uint64_t si
     const long pair_env = env_get("MGH_HUFF_PAIR", 1);
     const bool pair_decode = has_sync && (size_t)chunk <= 65535 &&
                              (pair_env == 2 || (pair_env == 1 && (double)units * 64.0 <= 6.5 * (double)n));
-    dt = huff::build_decode_table(book, book + 64, book + 128, (int)dict, rtb,
-                                  (lds_cap - 8 * per_wave) / 4 - (pair_decode ? ((size_t)1 << rtb) : 0));
-    if (pair_decode) dt = huff::make_pair_table(dt, rtb);
+    if (!kept) {
+      dt = huff::build_decode_table(book, book + 64, book + 128, (int)dict, rtb,
+                                    (lds_cap - 8 * per_wave) / 4 - (pair_decode ? ((size_t)1 << rtb) : 0));
+      if (pair_decode) dt = huff::make_pair_table(dt, rtb);
+    }
     const int waves = huff::decode_ring_lds(dt.size(), 16) <= lds_cap ? 16 : 8;
-    HL_TRY(c->dtable.ensure(dt.size() * 4));
-    // (out of pinned memory: a copy from pageable memory is staged synchronously, ~15 us)
-    HL_TRY(c->dpin.ensure(dt.size() * 4));
-    std::memcpy(c->dpin.p, dt.data(), dt.size() * 4);
-    HL_HIP(hipMemcpyAsync(c->dtable.p, c->dpin.p, dt.size() * 4, hipMemcpyHostToDevice, st));
+    if (!kept) {
+      HL_TRY(c->dtable.ensure(dt.size() * 4));
+      // (out of pinned memory: a copy from pageable memory is staged synchronously, ~15 us)
+      HL_TRY(c->dpin.ensure(dt.size() * 4));
+      std::memcpy(c->dpin.p, dt.data(), dt.size() * 4);
+      HL_HIP(hipMemcpyAsync(c->dtable.p, c->dpin.p, dt.size() * 4, hipMemcpyHostToDevice, st));
+    }
     static std::atomic<uint64_t> once3{0};
     if (hl_attr_pending(once3)) {
       HL_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(huff::k_decode_ring<int64_t>),
@@ -1058,6 +1093,7 @@ int lossless_decompress(mgh_lossless_ctx *c, const uint8_t *payload, uint64_t si
     // synchronisation points of the encoder, if the record has them: read where they lie in a
     // record on this device (any alignment), else from a copy
     const unsigned *d_sync = nullptr;
+    size_t sync0 = 0;  // chunk d_sync starts at
     if (has_sync && (size_t)chunk <= 65535) {
       if (on_dev && is_device_pointer_on(p, c->dev)) {
         d_sync = (const unsigned *)(p + o_sync);
@@ -1068,11 +1104,13 @@ int lossless_decompress(mgh_lossless_ctx *c, const uint8_t *payload, uint64_t si
           if (tag != PayloadLayout::kSyncTag) return hl_fail(MGH_ERR_FORMAT, "Huffman record: outlier lists");
         }
         // (the entries of the chunks decoded)
-        const size_t sync_need = 4 * (size_t)huff::kSyncLanes * ndec;
-        HL_TRY(c->sync.ensure(sync_need));
-        HL_HIP(hipMemcpyAsync(c->sync.p, p + o_sync, sync_need, hipMemcpyDefault, st));
+        const size_t sync_per = 4 * (size_t)huff::kSyncLanes;
+        const size_t sync_need = sync_per * (ndec - std::min(cf, ndec));
+        HL_TRY(c->sync.ensure(std::max<size_t>(sync_need, sync_per)));
+        if (sync_need) HL_HIP(hipMemcpyAsync(c->sync.p, p + o_sync + sync_per * cf, sync_need, hipMemcpyDefault, st));
         stats.record_bytes_moved += sync_need;
         d_sync = (const unsigned *)c->sync.p;
+        sync0 = cf;
       }
     }
     if (pair_decode && !d_sync) return hl_fail(MGH_ERR_DEVICE, "lossless_decompress: pair table without synchronisation points");
@@ -1094,11 +1132,11 @@ int lossless_decompress(mgh_lossless_ctx *c, const uint8_t *payload, uint64_t si
       if (c1 <= c0) return MGH_SUCCESS;
       const size_t cnt = c1 - c0, n_r = n_dec - c0 * (size_t)chunk;
       const unsigned grid = (unsigned)((cnt + waves - 1) / waves);
-      const unsigned long long *bits_r = (const unsigned long long *)c->bits.p + c0;
-      const unsigned long long *ent_r = (const unsigned long long *)c->entry.p + c0;
-      const unsigned *sync_r = d_sync ? reinterpret_cast<const unsigned *>(reinterpret_cast<const uint8_t *>(d_sync) + c0 * huff::kSyncLanes * 4) : nullptr;
-      int64_t *q64 = d_q + c0 * (size_t)chunk;
-      uint16_t *q16 = (uint16_t *)d_q + c0 * (size_t)chunk;
+      const unsigned long long *bits_r = (const unsigned long long *)c->bits.p + (c0 - tb0);
+      const unsigned long long *ent_r = (const unsigned long long *)c->entry.p + (c0 - tb0);
+      const unsigned *sync_r = d_sync ? reinterpret_cast<const unsigned *>(reinterpret_cast<const uint8_t *>(d_sync) + (c0 - sync0) * huff::kSyncLanes * 4) : nullptr;
+      int64_t *q64 = d_q + (c0 - cf) * (size_t)chunk;
+      uint16_t *q16 = (uint16_t *)d_q + (c0 - cf) * (size_t)chunk;
       if (pair_decode) {
         if (out16)
           huff::k_decode_sync<uint16_t><<<grid, 64 * waves, lds_b, st>>>(d_units, bits_r, ent_r, cnt, chunk, n_r, dict, rtb,
@@ -1125,10 +1163,10 @@ int lossless_decompress(mgh_lossless_ctx *c, const uint8_t *payload, uint64_t si
       // whose units (and the one unit the decoder peeks at behind them) have landed are decoded on st
       const uint64_t *h_bits = reinterpret_cast<const uint64_t *>(head.data() + L.huffmeta);
       const uint64_t *h_ent = h_bits + nchunk;
-      size_t c_done = 0;
-      const size_t total_b = units_need * 8;
+      size_t c_done = cf;
+      const size_t total_b = (units_need - units_lo) * 8;
       const ChunkFn on_piece = [&](size_t off, size_t nb, hipEvent_t landed) -> int {
-        const uint64_t have = (off + nb) / 8;  // units of the record on the device
+        const uint64_t have = units_lo + (off + nb) / 8;  // units of the record on the device
         size_t c_hi = c_done;
         if (off + nb >= total_b) {
           c_hi = ndec;
@@ -1144,12 +1182,14 @@ int lossless_decompress(mgh_lossless_ctx *c, const uint8_t *payload, uint64_t si
       };
       // (the copy stream must not run ahead of what st has queued in front: the small uploads above
       // are independent of the units; the units buffer itself is free -- the caller drained st)
-      HL_TRY(copy_any(c->units.p, p + L.ddata, total_b, cache_copy_stream(c->dev), &on_piece));
+      HL_TRY(copy_any(c->units.p, p + L.ddata + units_lo * 8, total_b, cache_copy_stream(c->dev), &on_piece));
       if (c_done < ndec) return hl_fail(MGH_ERR_DEVICE, "lossless_decompress: chunks left behind the last piece");
     } else {
-      HL_TRY(launch_range(0, ndec));
+      HL_TRY(launch_range(cf, ndec));
     }
     HL_HIP(hipGetLastError());
+  } else if (ndec <= cf) {
+    // (nothing to decode)
   } else if (!serial_decode && (size_t)chunk >= 1024) {
     if (sym16) *sym16 = false;
     // parallel decoding inside the chunks (one wave per chunk)
@@ -1164,21 +1204,24 @@ int lossless_decompress(mgh_lossless_ctx *c, const uint8_t *payload, uint64_t si
                          150 * 1024)
       tb--;
     const size_t lds_par = ((size_t)4 << tb) + ((size_t)dict + 3) / 4 * 8 + huff::kParWaves * 64 * huff::kParBatch * 2;
-    huff::k_decode_par<<<(unsigned)((ndec + huff::kParWaves - 1) / huff::kParWaves),
+    huff::k_decode_par<<<(unsigned)((ndec - cf + huff::kParWaves - 1) / huff::kParWaves),
                          64 * huff::kParWaves, lds_par, st>>>(
-        d_units, (const unsigned long long *)c->bits.p,
-        (const unsigned long long *)c->entry.p, ndec, chunk, n_dec, dict, tb, tab, tab + 64, tab + 128, d_q);
+        d_units, (const unsigned long long *)c->bits.p + (cf - tb0),
+        (const unsigned long long *)c->entry.p + (cf - tb0), ndec - cf, chunk, n_dec - cf * (size_t)chunk, dict, tb, tab,
+        tab + 64, tab + 128, d_q);
   } else {
     if (sym16) *sym16 = false;
-    huff::k_decode<<<(unsigned)((ndec + 63) / 64), 64, lds, st>>>(
-        d_units, (const unsigned long long *)c->bits.p,
-        (const unsigned long long *)c->entry.p, ndec, chunk, n_dec, dict, tb, tab, tab + 64, tab + 128, d_q);
+    huff::k_decode<<<(unsigned)((ndec - cf + 63) / 64), 64, lds, st>>>(
+        d_units, (const unsigned long long *)c->bits.p + (cf - tb0),
+        (const unsigned long long *)c->entry.p + (cf - tb0), ndec - cf, chunk, n_dec - cf * (size_t)chunk, dict, tb, tab,
+        tab + 64, tab + 128, d_q);
   }
   HL_HIP(hipGetLastError());
   hl_debug("lossless_decompress: decode launched");
   // the host payload may go away when we return (the subdomain pipeline keeps it, and the context's
   // host-side sources, alive until the lane has drained: sync_end = false)
   *ocount_out = ocount;
+  if (c->keep == 1) c->keep = 2;
   if (sync_end) {
     HL_HIP(hipStreamSynchronize(st));
     return lossless_tag_check(c);
@@ -4157,6 +4200,322 @@ int mgh_lossless_decompress_prefix(mgh_lossless_ctx *ctx, const uint8_t *payload
   if (oval_out) *oval_out = (const int64_t *)ctx->oval.p;
   return MGH_SUCCESS;
 }
+
+int mgh_lossless_decompress_range(mgh_lossless_ctx *ctx, const uint8_t *payload, uint64_t size, int lossless,
+                                  int64_t *d_q, uint64_t n, uint64_t first, uint64_t count, const uint64_t **oidx_out,
+                                  const int64_t **oval_out, uint64_t *ocount_out, void *stream) {
+  if (!ctx || !payload || !d_q || !ocount_out) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (count == 0 || first >= n || count > n - first)
+    return hl_fail(MGH_ERR_INVALID_ARGUMENT, "mgh_lossless_decompress_range: first / count outside the record");
+  if (hipSetDevice(ctx->dev) != hipSuccess) return hl_fail(MGH_ERR_DEVICE, "hipSetDevice");
+  try {
+    HL_TRY(lossless_decompress(ctx, payload, size, lossless, d_q, n, ocount_out, (hipStream_t)stream, nullptr, true,
+                               first + count, ~(uint64_t)0, first));
+  } catch (const std::exception &e) {
+    return hl_fail(MGH_ERR_DEVICE, e.what());
+  }
+  if (oidx_out) *oidx_out = (const uint64_t *)ctx->oidx.p;
+  if (oval_out) *oval_out = (const int64_t *)ctx->oval.p;
+  return MGH_SUCCESS;
+}
+
+int mgh_infer_level_range(const void *data, size_t size, const mgh_config *config, int level, uint64_t *first_elem,
+                          uint64_t *num_elems, uint64_t *first_chunk, uint64_t *num_chunks) {
+  if (!data) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "NULL argument");
+  mgh_config def;
+  if (!config) {
+    mgh_config_default(&def);
+    config = &def;
+  }
+  fmt::Header hd;
+  size_t ms = 0;
+  HL_TRY(read_header(data, size, hd, ms));
+  std::vector<uint64_t> shp;
+  HL_TRY(header_level_shape(hd, *config, level, nullptr, &shp));
+  uint64_t hi = 1, lo = 0;
+  for (uint64_t e : shp) hi *= e;
+  if (level > 0) {
+    HL_TRY(header_level_shape(hd, *config, level - 1, nullptr, &shp));
+    lo = 1;
+    for (uint64_t e : shp) lo *= e;
+  }
+  const uint64_t block = std::max<uint64_t>(hd.huff_block_size, 1);
+  if (first_elem) *first_elem = lo;
+  if (num_elems) *num_elems = hi - lo;
+  if (first_chunk) *first_chunk = lo / block;
+  if (num_chunks) *num_chunks = (hi - 1) / block - lo / block + 1;
+  return MGH_SUCCESS;
+}
+
+}  // extern "C"
+
+// ---- progressive reader: a reduced-resolution reconstruction refined level by level -----------------
+// State between the calls: the dense nodal array of the current level (what the next level step
+// reads), the integers decoded but not used yet (the tail of the boundary chunk), and a lossless
+// context that keeps the record's head, decode tables, chunk table and outlier lists on the device.
+struct mgh_progressive {
+  fmt::Header hd;
+  mgh_config cfg;
+  const uint8_t *rec = nullptr;  // the record inside the caller's container (borrowed)
+  uint64_t csize = 0;
+  bool in_dev = false, raw = false;
+  int lossless = MGH_LOSSLESS_HUFFMAN;
+  int dtype = MGH_FLOAT, eb = MGH_REL;
+  size_t elem = 4;
+  double tol = 0, s = 0, norm = 0;
+  uint64_t n = 0, block = 1, nchunk = 0, ocount = 0;
+  int L = 0, level = -1;
+  std::vector<uint64_t> N;  // N[l] = prod(level_shape(l))
+  mgh_hierarchy *h = nullptr;
+  mgh_lossless_ctx *ll = nullptr;
+  hipStream_t st = nullptr;
+  DevBuf q[2];             // q[qi]: integers [q_first, dec_end) of the level-linearised array
+  int qi = 0;
+  uint64_t q_first = 0, dec_end = 0;
+  DevBuf state[2];         // state[si]: the dense array of `level`
+  int si = 0;
+  DevBuf lin;              // a raw record: all its level-linearised integers (made at open)
+};
+
+namespace {
+void progressive_free(mgh_progressive *p) {
+  if (!p) return;
+  (void)hipSetDevice(p->cfg.dev_id);
+  if (p->st) (void)hipStreamSynchronize(p->st);
+  for (DevBuf *b : {&p->q[0], &p->q[1], &p->state[0], &p->state[1], &p->lin}) b->release();
+  if (p->h) mgh_hierarchy_destroy(p->h);
+  if (p->ll) mgh_lossless_destroy(p->ll);
+  if (p->st) (void)hipStreamDestroy(p->st);
+  delete p;
+}
+
+int progressive_open(mgh_progressive *p, const void *data, size_t size) {
+  std::unique_ptr<HostPrefix> prefix;
+  p->in_dev = is_device_pointer(data);
+  if (p->in_dev) prefix.reset(new HostPrefix(data, size));
+  size_t meta_size = 0;
+  fmt::Header &hd = p->hd;
+  HL_TRY(read_header(data, size, hd, meta_size));
+  if (hd.shape.empty() || hd.shape.size() > MGH_MAX_DIM) return hl_fail(MGH_ERR_UNSUPPORTED_DIMENSION, "header: dimension");
+  if (!hd.quantized) return hl_fail(MGH_ERR_FORMAT, "not a compressed (quantized) stream");
+  HL_TRY(header_level_shape(hd, p->cfg, -1, &p->L, nullptr));  // (refuses a decomposed container)
+  if (hd.compressor == fmt::COMP_X_HUFFMAN) p->lossless = MGH_LOSSLESS_HUFFMAN;
+  else if (hd.compressor == fmt::COMP_X_HUFFMAN_ZSTD) p->lossless = MGH_LOSSLESS_HUFFMAN_ZSTD;
+  else return hl_fail(MGH_ERR_FORMAT, "this lossless compressor is not supported");
+  if (hd.hierarchy != fmt::HIER_MULTIDIM) return hl_fail(MGH_ERR_FORMAT, "only the multi-dimensional decomposition is supported");
+  if (!hd.reorder)
+    return hl_fail(MGH_ERR_INVALID_ARGUMENT,
+                   "mgh_progressive_open: a reorder = 1 (level-linearised) container is needed: the levels of a "
+                   "reorder = 0 record are spread over every Huffman chunk");
+  p->dtype = hd.is_double ? MGH_DOUBLE : MGH_FLOAT;
+  p->elem = hd.is_double ? 8 : 4;
+  auto in_type = [&](double v) { return hd.is_double ? v : (double)(float)v; };
+  p->tol = in_type(hd.tol);
+  p->s = in_type(hd.s);
+  p->norm = in_type(hd.norm);
+  p->eb = hd.rel ? MGH_REL : MGH_ABS;
+  p->block = std::max<uint64_t>(hd.huff_block_size, 1);
+  p->N.resize(p->L + 1);
+  for (int l = 0; l <= p->L; l++) {
+    std::vector<uint64_t> shp;
+    HL_TRY(header_level_shape(hd, p->cfg, l, nullptr, &shp));
+    p->N[l] = 1;
+    for (uint64_t e : shp) p->N[l] *= e;
+  }
+  p->n = p->N[p->L];
+  // the one record
+  if (size - meta_size < 8) return hl_fail(MGH_ERR_FORMAT, "subdomain record truncated");
+  std::vector<uint8_t> sz;
+  HL_TRY(fetch_host((const char *)data + meta_size, 8, 8, sz));
+  std::memcpy(&p->csize, sz.data(), 8);
+  if (p->csize > size - meta_size - 8) return hl_fail(MGH_ERR_FORMAT, "subdomain record truncated");
+  p->rec = (const uint8_t *)data + meta_size + 8;
+  p->raw = !((double)(p->n * p->elem) / (double)p->csize > 1.0);
+  if (p->raw && p->csize != p->n * p->elem) return hl_fail(MGH_ERR_FORMAT, "raw subdomain record has the wrong size");
+  // hierarchy of the array (its own: it holds the state of the level loop between the calls)
+  {
+    const int D = (int)hd.shape.size();
+    std::vector<std::vector<float>> cf(D);
+    std::vector<std::vector<double>> cd(D);
+    const void *ptrs[MGH_MAX_DIM];
+    if (!hd.uniform)
+      for (int d = 0; d < D; d++) {
+        cd[d] = hd.coords[d];
+        if (p->cfg.mirror_reference_coord_cast)
+          for (double &x : cd[d]) x = (double)(float)x;
+        if (!hd.is_double) {
+          cf[d].assign(cd[d].begin(), cd[d].end());
+          ptrs[d] = cf[d].data();
+        } else {
+          ptrs[d] = cd[d].data();
+        }
+      }
+    HL_TRY(mgh_hierarchy_create(&p->h, D, hd.shape.data(), p->dtype, hd.uniform ? nullptr : ptrs,
+                                p->cfg.normalize_coordinates, p->cfg.max_larget_level, p->cfg.dev_id));
+    if (mgh_l_target(p->h) != p->L) return hl_fail(MGH_ERR_FORMAT, "header: the hierarchy of the subdomain is not the header's");
+  }
+  HL_HIP(hipStreamCreate(&p->st));
+  if (p->raw) {
+    // the integers a Huffman record of this array would have held (no dictionary), level-linearised:
+    // the route of mgh_decompress_level, once
+    if (p->L == 0) return MGH_SUCCESS;
+    DevBuf data_in, qfull;
+    HL_TRY(data_in.ensure(p->csize));
+    HL_TRY(qfull.ensure(p->n * 8));
+    HL_TRY(p->lin.ensure(p->n * 8));
+    int rc = copy_any(data_in.p, p->rec, p->csize, p->st);
+    if (rc == MGH_SUCCESS)
+      rc = mgh_decompose_quantize(p->h, data_in.p, p->eb, p->tol, p->s, p->norm, nullptr, hd.huff_dict_size, 0,
+                                  (int64_t *)qfull.p, nullptr, nullptr, nullptr, 0, nullptr, p->st);
+    if (rc == MGH_SUCCESS)
+      rc = mgh_level_linearize(p->h, (const int64_t *)qfull.p, (int64_t *)p->lin.p, 0, nullptr, nullptr, 0, 0, p->st);
+    (void)hipStreamSynchronize(p->st);
+    data_in.release();
+    qfull.release();
+    return rc;
+  }
+  // head parsed and validated, decode tables, chunk table and outlier lists uploaded, a Zstd frame
+  // inflated -- once
+  HL_TRY(mgh_lossless_create(&p->ll, p->cfg.dev_id));
+  p->ll->keep = 1;
+  decompress_stats() = mgh_decompress_stats{};
+  HL_TRY(lossless_decompress(p->ll, p->rec, p->csize, p->lossless, nullptr, p->n, &p->ocount, p->st, nullptr,
+                             /*sync_end=*/true, /*n_prefix=*/0));
+  p->nchunk = decompress_stats().chunks_total;
+  return MGH_SUCCESS;
+}
+
+int progressive_refine(mgh_progressive *p, int to, void **out, bool prealloc) {
+  const fmt::Header &hd = p->hd;
+  mgh_decompress_stats &stats = decompress_stats();
+  stats = mgh_decompress_stats{};
+  stats.subdomains = 1;
+  const int from = p->level;
+  hipStream_t st = p->st;
+  const uint64_t dict = hd.huff_dict_size;
+  const size_t out_bytes = p->N[to] * p->elem;
+  int at = p->si;
+  const bool raw_full = p->raw && to == p->L;  // (a raw record IS the finest level)
+  if (raw_full) stats.record_bytes = p->csize;
+  if (!raw_full) {
+    const int64_t *base = nullptr;  // integer `first` of the array
+    uint64_t first = 0;
+    const uint64_t *oidx = nullptr;
+    const int64_t *oval = nullptr;
+    if (p->raw) {
+      stats.record_bytes = p->csize;
+      base = (const int64_t *)p->lin.p;
+    } else {
+      // the integers [N_from, N_to): what is left of the boundary chunk, and the chunks not decoded yet
+      const uint64_t lo = from < 0 ? 0 : p->N[from];
+      const uint64_t carry = p->dec_end > lo ? p->dec_end - lo : 0;
+      const uint64_t new_end = std::max(p->dec_end, std::min(p->n, ((p->N[to] - 1) / p->block + 1) * p->block));
+      DevBuf &qn = p->q[p->qi ^ 1];
+      HL_TRY(qn.ensure(std::max<uint64_t>(carry + (new_end - p->dec_end), 1) * 8));
+      if (carry)
+        HL_HIP(hipMemcpyAsync(qn.p, (const int64_t *)p->q[p->qi].p + (lo - p->q_first), carry * 8, hipMemcpyDeviceToDevice, st));
+      if (new_end > p->dec_end) {
+        HL_TRY(lossless_decompress(p->ll, p->rec, p->csize, p->lossless, (int64_t *)qn.p + carry, p->n, &p->ocount, st,
+                                   nullptr, /*sync_end=*/false, /*n_prefix=*/new_end, /*q_cap=*/new_end - p->dec_end,
+                                   /*first=*/p->dec_end));
+      } else {  // (everything this refine reads was decoded with the boundary chunk of an earlier one)
+        stats.chunks_total = p->nchunk;
+        stats.record_bytes = p->csize;
+      }
+      p->qi ^= 1;
+      p->q_first = lo;
+      p->dec_end = new_end;
+      base = (const int64_t *)qn.p;
+      first = lo;
+      oidx = (const uint64_t *)p->ll->oidx.p;
+      oval = (const int64_t *)p->ll->oval.p;
+    }
+    const int prep = p->raw ? 0 : 1;
+    const uint64_t ocount = p->raw ? 0 : p->ocount;
+    int l = from;
+    if (from < 0) {
+      HL_TRY(p->state[at].ensure(out_bytes));
+      HL_TRY(mgh_dequantize_recompose_linear_to_level(p->h, (int64_t *)base, p->eb, p->tol, p->s, p->norm, dict, prep, oidx,
+                                                      oval, ocount, to, p->state[at].p, st));
+      l = to;
+    }
+    for (l = l + 1; l <= to; l++) {
+      HL_TRY(p->state[at ^ 1].ensure(p->N[l] * p->elem));
+      HL_TRY(mgh_refine_level(p->h, p->state[at].p, (int64_t *)base + (p->N[l - 1] - first), p->eb, p->tol, p->s, p->norm,
+                              dict, prep, oidx, oval, ocount, l, p->state[at ^ 1].p, st));
+      at ^= 1;
+    }
+  }
+  // the array of to_level out, in the container's memory space
+  if (!prealloc) {
+    if (p->in_dev) HL_HIP(hipMalloc(out, out_bytes));
+    else if (!(*out = host_alloc_large(out_bytes))) return hl_fail(MGH_ERR_OUT_OF_MEMORY, "malloc");
+  }
+  int rc = raw_full ? copy_any(*out, p->rec, out_bytes, st) : copy_any(*out, p->state[at].p, out_bytes, st);
+  if (rc == MGH_SUCCESS && hipStreamSynchronize(st) != hipSuccess) rc = hl_fail(MGH_ERR_DEVICE, "sync");
+  if (rc == MGH_SUCCESS && p->ll) rc = lossless_tag_check(p->ll);
+  if (rc != MGH_SUCCESS && !prealloc) {
+    if (p->in_dev) (void)hipFree(*out); else std::free(*out);
+    *out = nullptr;
+  }
+  if (rc == MGH_SUCCESS) {
+    p->si = at;
+    p->level = to;
+  }
+  return rc;
+}
+}  // namespace
+
+extern "C" {
+
+int mgh_progressive_open(mgh_progressive **out, const void *compressed_data, size_t compressed_size,
+                         const mgh_config *config) {
+  if (!out || !compressed_data) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "NULL argument");
+  *out = nullptr;
+  {
+    const std::string bad = env_validate();
+    if (!bad.empty()) return hl_fail(MGH_ERR_INVALID_ARGUMENT, bad);
+  }
+  mgh_config def;
+  if (!config) {
+    mgh_config_default(&def);
+    config = &def;
+  }
+  if (mgh_device_count() <= 0) return hl_fail(MGH_ERR_NO_DEVICE, "no HIP device");
+  if (hipSetDevice(config->dev_id) != hipSuccess) return hl_fail(MGH_ERR_DEVICE, "hipSetDevice");
+  mgh_progressive *p = new mgh_progressive();
+  p->cfg = *config;
+  int rc;
+  try {
+    rc = progressive_open(p, compressed_data, compressed_size);
+  } catch (const std::exception &e) {
+    rc = hl_fail(MGH_ERR_DEVICE, e.what());
+  }
+  if (rc != MGH_SUCCESS) {
+    progressive_free(p);
+    return rc;
+  }
+  *out = p;
+  return MGH_SUCCESS;
+}
+
+int mgh_progressive_level(const mgh_progressive *p) { return p ? p->level : -1; }
+
+int mgh_progressive_refine(mgh_progressive *p, int to_level, void **data, int output_pre_allocated) {
+  if (!p || !data) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (output_pre_allocated && !*data) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "pre-allocated output is NULL");
+  if (to_level < 0 || to_level > p->L) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "level outside 0 .. l_target");
+  if (to_level <= p->level)
+    return hl_fail(MGH_ERR_INVALID_ARGUMENT, "mgh_progressive_refine: to_level must be above the current level");
+  if (hipSetDevice(p->cfg.dev_id) != hipSuccess) return hl_fail(MGH_ERR_DEVICE, "hipSetDevice");
+  try {
+    return progressive_refine(p, to_level, data, output_pre_allocated != 0);
+  } catch (const std::exception &e) {
+    return hl_fail(MGH_ERR_DEVICE, e.what());
+  }
+}
+
+void mgh_progressive_close(mgh_progressive *p) { progressive_free(p); }
 
 int mgh_last_decompress_stats(mgh_decompress_stats *out) {
   if (!out) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "NULL argument");

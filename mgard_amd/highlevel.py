@@ -26,6 +26,8 @@ HL_SYMBOLS = [
     "mgh_decompress_into",
     "mgh_infer_level_shape", "mgh_infer_level_nodes", "mgh_decompress_level",
     "mgh_lossless_decompress_prefix", "mgh_last_decompress_stats",
+    "mgh_lossless_decompress_range", "mgh_infer_level_range", "mgh_progressive_open",
+    "mgh_progressive_level", "mgh_progressive_refine", "mgh_progressive_close",
 ]
 
 
@@ -146,6 +148,15 @@ def _hl():
                                           C.POINTER(u64), vp]
     L.mgh_lossless_decompress_prefix.argtypes = [vp, vp, u64, C.c_int, vp, u64, u64, C.POINTER(vp), C.POINTER(vp),
                                                  C.POINTER(u64), vp]
+    L.mgh_lossless_decompress_range.argtypes = [vp, vp, u64, C.c_int, vp, u64, u64, u64, C.POINTER(vp),
+                                                C.POINTER(vp), C.POINTER(u64), vp]
+    L.mgh_infer_level_range.argtypes = [vp, C.c_size_t, vp, C.c_int, C.POINTER(u64), C.POINTER(u64),
+                                        C.POINTER(u64), C.POINTER(u64)]
+    L.mgh_progressive_open.argtypes = [C.POINTER(vp), vp, C.c_size_t, vp]
+    L.mgh_progressive_level.argtypes = [vp]
+    L.mgh_progressive_refine.argtypes = [vp, C.c_int, C.POINTER(vp), C.c_int]
+    L.mgh_progressive_close.argtypes = [vp]
+    L.mgh_progressive_close.restype = None
     L.mgh_last_decompress_stats.argtypes = [C.POINTER(DecompressStats)]
     L.mgh_memcpy.argtypes = [vp, vp, C.c_size_t]
     L.mgh_huffman_codebook.argtypes = [vp, u64, vp, vp, vp, vp]
@@ -326,6 +337,93 @@ def infer_level_nodes(buf, level, dim, config=None):
     out = (C.c_uint64 * cap)()
     k = _check(L.mgh_infer_level_nodes(p, n, C.byref(cfg), int(level), int(dim), out, cap))
     return np.array(out[:k], dtype=np.int64)
+
+
+def infer_level_range(buf, level, config=None):
+    """mgh_infer_level_range: (first_elem, num_elems, first_chunk, num_chunks) of the coefficients of
+    `level` in a level-linearised (reorder = 1) record; host only."""
+    import torch
+    L = _hl()
+    cfg = config if config is not None else Config()
+    if isinstance(buf, torch.Tensor):
+        p, n = C.c_void_p(buf.data_ptr()), buf.numel()
+    else:
+        buf = np.ascontiguousarray(buf)
+        p, n = C.c_void_p(buf.ctypes.data), buf.size
+    v = [C.c_uint64() for _ in range(4)]
+    _check(L.mgh_infer_level_range(p, n, C.byref(cfg), int(level), *[C.byref(x) for x in v]))
+    return tuple(int(x.value) for x in v)
+
+
+class Progressive:
+    """mgh_progressive: a reduced-resolution reconstruction of a reorder = 1 container refined level by
+    level -- every Huffman chunk decoded once, every level's solves run once.
+
+        with Progressive(buf, config) as p:
+            preview = p.refine(2)
+            better = p.refine(3)
+
+    `buf` (numpy uint8 array or cuda uint8 tensor) is borrowed until close()."""
+
+    def __init__(self, buf, config=None):
+        import torch
+        self._p = C.c_void_p()
+        self._cfg = config if config is not None else Config()
+        self._on_dev = isinstance(buf, torch.Tensor) and buf.is_cuda
+        if not self._on_dev:
+            buf = np.ascontiguousarray(buf)
+        self._buf = buf
+        self._dt = infer(buf)[1]
+        p, n = (C.c_void_p(buf.data_ptr()), buf.numel()) if self._on_dev else (C.c_void_p(buf.ctypes.data), buf.size)
+        _check(_hl().mgh_progressive_open(C.byref(self._p), p, n, C.byref(self._cfg)))
+
+    @property
+    def level(self):
+        """The level of the last refine; -1 before the first one."""
+        return int(_hl().mgh_progressive_level(self._p)) if self._p else -1
+
+    def refine(self, level, out=None):
+        """The dense array of `level` (> self.level): a numpy array (host container) or a cuda tensor."""
+        import torch
+        if not self._p:
+            raise MgardHipError("the reader is closed")
+        shape, _ = infer_level(self._buf, int(level), self._cfg)
+        if self._on_dev:
+            want = torch.float32 if self._dt == FLOAT else torch.float64
+            if out is None:
+                out = torch.empty(shape, dtype=want, device=self._buf.device)
+            if not (isinstance(out, torch.Tensor) and out.is_cuda and out.is_contiguous() and out.dtype == want and
+                    out.numel() == int(np.prod(shape))):
+                raise ValueError("`out` must be a contiguous cuda tensor of the level's shape and the stream's type")
+            optr = C.c_void_p(out.data_ptr())
+        else:
+            npdt = np.float32 if self._dt == FLOAT else np.float64
+            if out is None:
+                out = np.empty(shape, dtype=npdt)
+            if not (isinstance(out, np.ndarray) and out.flags.c_contiguous and out.flags.writeable and
+                    out.dtype == npdt and out.size == int(np.prod(shape))):
+                raise ValueError("`out` must be a writeable C-contiguous numpy array of the level's shape and type")
+            optr = C.c_void_p(out.ctypes.data)
+        _check(_hl().mgh_progressive_refine(self._p, int(level), C.byref(optr), 1))
+        return out
+
+    def close(self):
+        if self._p:
+            _hl().mgh_progressive_close(self._p)
+            self._p = C.c_void_p()
+        self._buf = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def decompress(buf, config=None, out=None, level=None):
@@ -565,20 +663,25 @@ class Lossless:
             out.numel(), C.byref(size), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
         return out[:size.value]
 
-    def decompress(self, payload, n, lossless=HUFFMAN, prefix=None, out=None):
+    def decompress(self, payload, n, lossless=HUFFMAN, prefix=None, out=None, first=None, count=None):
         """payload: bytes, or a cuda uint8 tensor (decoded where it lies). Returns (q, outlier_idx,
         outlier_val) as cuda tensors.
         prefix: decode only the chunks that hold the first `prefix` integers
         (mgh_lossless_decompress_prefix): q[0 : min(n, ceil(prefix / chunk) * chunk)] is written and
         nothing behind it; the outlier lists come whole. out: a cuda int64 tensor to decode into (with
-        a prefix it need only hold what is written); default: a new one of n elements."""
+        a prefix it need only hold what is written); default: a new one of n elements.
+        first, count: decode only the chunks that hold integers [first, first + count)
+        (mgh_lossless_decompress_range): q[0:] receives the integers from (first // chunk) * chunk to
+        the end of the last decoded chunk (or n), nothing behind them."""
         import torch
+        if (first is None) != (count is None) or (first is not None and prefix is not None):
+            raise ValueError("pass first and count together, and not with prefix")
         if out is None:
             q = torch.empty(n, dtype=torch.int64, device="cuda")
         else:
             if not (out.is_cuda and out.dtype == torch.int64 and out.is_contiguous()):
                 raise ValueError("out: expected a contiguous cuda int64 tensor")
-            if prefix is None and out.numel() < n:
+            if prefix is None and first is None and out.numel() < n:
                 raise ValueError("out: %d elements, the record holds %d" % (out.numel(), n))
             q = out
         if isinstance(payload, torch.Tensor):
@@ -591,7 +694,11 @@ class Lossless:
         else:
             raw, nbytes = (C.c_uint8 * len(payload)).from_buffer_copy(payload), len(payload)
         oi, ov, cnt = C.c_void_p(), C.c_void_p(), C.c_uint64()
-        if prefix is None:
+        if first is not None:
+            _check(_hl().mgh_lossless_decompress_range(
+                self._c, raw, nbytes, lossless, C.c_void_p(q.data_ptr()), n, int(first), int(count), C.byref(oi),
+                C.byref(ov), C.byref(cnt), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        elif prefix is None:
             _check(_hl().mgh_lossless_decompress(
                 self._c, raw, nbytes, lossless, C.c_void_p(q.data_ptr()), n, C.byref(oi), C.byref(ov),
                 C.byref(cnt), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
