@@ -113,11 +113,6 @@ namespace {
 
 using namespace mgh;
 
-struct DevBuf {
-  void *p = nullptr;
-  size_t bytes = 0;
-};
-
 // Warm-up length of the chunked sweeps (thomas_chunked) for one Thomas table: a chunk starts
 // from state 0 instead of the true state, an error of the size of the data; after K steps it is
 // that times the product of the K multipliers it passed. For the two runs to MEET (and not
@@ -896,6 +891,8 @@ inline bool fused4_ok(const mgh_hierarchy *h) {
   return h->D == 4 && h->fused4 && !h->force_nd && h->L >= 1 && h->plane_elems < ((uint64_t)1 << 29);
 }
 inline bool fusedc_ok(const mgh_hierarchy *h) { return fused_ok(h) || fused4_ok(h); }
+// ... and not switched off: the route of the fused level loops
+inline bool fused_route(const mgh_hierarchy *h) { return fusedc_ok(h) && !h->force_v1; }
 
 // ---- layouts of T arrays (mgh_set_ld; mgard_x::Array::ld, Array.hpp:70-84: hipMallocPitch pads the
 // fastest dimension; SubArray.hpp:136-139 carries one ld per dimension) ------------------------
@@ -1725,6 +1722,16 @@ int recompose_levels4(mgh_hierarchy *h, RecomposeArgs<T> A, const std::vector<T>
                       hipStream_t st, const RecomposeArgs<T> *AL = nullptr, size_t A_sT = 0, int ntop = 1,
                       int stop = -1, int start = 0);
 
+// The one D == 4 dispatch of the fused level loops. A_sT as in recompose_levels4, `out` as in
+// recompose_levels: each takes its own.
+template <typename T, typename QT, typename QTL = QT>
+int recompose_levels_any(mgh_hierarchy *h, const RecomposeArgs<T> &A, size_t A_sT, const std::vector<T> &level_qv,
+                         T *data, const Layout &out, hipStream_t st, const RecomposeArgs<T> *AL = nullptr,
+                         int ntop = 1, int stop = -1, int start = 0) {
+  if (h->D == 4) return recompose_levels4<T, QT, QTL>(h, A, level_qv, data, st, AL, A_sT, ntop, stop, start);
+  return recompose_levels<T, QT, QTL>(h, A, level_qv, data, out, st, AL, ntop, stop, start);
+}
+
 // The level loop of the one-thread-per-element kernels (D <= 3): coefficients C with strides
 // (cI, cJ, 1) in the 3-D view, levels 1 .. Ls. Ls == L: `data` has the full array's strides;
 // below (mgh_*_to_level) it is the dense array of level Ls. start >= 1 (mgh_refine_level): levels
@@ -2115,64 +2122,109 @@ int recompose_levels4(mgh_hierarchy *h, RecomposeArgs<T> A0, const std::vector<T
   return MGH_SUCCESS;
 }
 
-template <typename T>
-int dequantize_recompose_fused(mgh_hierarchy *h, int64_t *q, int ebtype, double tol, double s,
-                               double norm, uint64_t dict_size, int prep_huffman,
-                               const uint64_t *oidx, const int64_t *oval, uint64_t ocount, T *data,
-                               const Layout &out, hipStream_t st, int stop = -1, const size_t *box_m = nullptr) {
-  // box_m (with stop >= 0): q is the COMPACT corner box of the stop level, dense in these extents
-  // (mgh_dequantize_recompose_linear_to_level), not the full array
-  auto *ds = DS<T>(h);
+// ---- what a reconstruction reads and makes: the descriptors of reconstruct() below ----------------
+// Quantization parameters, and the out-of-dictionary values of the record.
+struct QuantSpec {
+  int ebtype;
+  double tol, s, norm;
+  uint64_t dict_size;
+  int prep_huffman;
+  const uint64_t *oidx;
+  const int64_t *oval;
+  uint64_t ocount;
+};
+inline int64_t dict_half(const QuantSpec &qs) { return qs.prep_huffman ? (int64_t)(qs.dict_size / 2) : 0; }
+
+// The integers.
+struct IntSource {
+  enum Kind {
+    Full,    // q: the full array, with the hierarchy's strides
+    Box,     // q: the COMPACT corner box of the target's stop level (dense in its shape), outliers in it
+    Linear,  // q: level-linearised -- its head up to the stop level, or (a level step) the stop level's segment
+    Sym16    // sym: 16-bit dictionary symbols of the full array
+  } kind;
+  int64_t *q;
+  const uint16_t *sym;
+};
+
+// What is made: the dense array of level `stop` (stop == l_target: the full array, in layout `lay`),
+// from level 0 (start == 0), or in one level step (start == stop) from `coarse`, the dense array of
+// level stop - 1.
+struct Target {
+  int stop, start;
+  const void *coarse;
+  void *out;
+  Layout lay;
+};
+
+// Quantum of every level: its quantizer, times its volume factor when s != inf.
+template <typename T> std::vector<T> level_quanta(const mgh_hierarchy *h, const QuantSpec &qs) {
   auto *hh = HH<T>(h);
-  const int L = h->L;
-  if (prep_huffman && ocount) {
-    if (stop >= 0) {  // (only what the stop level reads: the rest of the caller's integers stays as it is)
-      const LevelBox lb = level_box_of<T>(h, stop, dense_layout(h));
-      TRY(launch(h, "outlier_restore", st, [&] {
-        k_outlier_restore_in_box<<<(unsigned)((ocount + 255) / 256), 256, 0, st>>>(q, lb, oidx, oval, ocount);
-      }));
-    } else
-    TRY(launch(h, "outlier_restore", st, [&] {
-      k_outlier_restore<<<(unsigned)((ocount + 255) / 256), 256, 0, st>>>(q, h->total, oidx, oval, ocount);
-    }));
-  }
-  std::vector<T> qz(L + 1);
-  hh->quantizers(ebtype, (T)tol, (T)s, (T)norm, false, qz.data());
-  const bool calc_vol = !((T)s == std::numeric_limits<T>::infinity());
-  RecomposeArgs<T> A{};
-  A.q = q;
-  A.dI = ds->full_I;
-  A.dJ = ds->full_J;
-  A.half = prep_huffman ? (int64_t)(dict_size / 2) : 0;
-  std::vector<T> level_qv(L + 1);
-  for (int l = 0; l <= L; l++) level_qv[l] = qz[l] * (calc_vol ? hh->level_volume(l, true) : (T)1);
-  size_t sT = 0;
-  if (box_m) {
-    const int D = h->D;
-    A.dJ = box_m[D - 1];
-    A.dI = box_m[D - 2] * box_m[D - 1];
-    if (D == 4) sT = box_m[1] * box_m[2] * box_m[3];
-  }
-  if (h->D == 4) return recompose_levels4<T, int64_t>(h, A, level_qv, data, st, nullptr, sT, 1, stop);
-  return recompose_levels<T, int64_t>(h, A, level_qv, data, out, st, nullptr, 1, stop);
+  std::vector<T> qv(h->L + 1);
+  hh->quantizers(qs.ebtype, (T)qs.tol, (T)qs.s, (T)qs.norm, false, qv.data());
+  if (!((T)qs.s == std::numeric_limits<T>::infinity()))
+    for (int l = 0; l <= h->L; l++) qv[l] = qv[l] * hh->level_volume(l, true);
+  return qv;
 }
 
-// The same from 16-bit dictionary symbols (what the Huffman decoder of the high-level path
-// delivers): no int64 array, the out-of-dictionary values are found through a hash table.
+// A device buffer of the handle grown to `count` elements (never shrunk; counted in mgh_device_bytes:
+// a stop level's box is a fraction of the full call's).
+template <typename U> int grow(mgh_hierarchy *h, U **p, size_t *elems, size_t count) {
+  if (count <= *elems) return MGH_SUCCESS;
+  dev_free(h, p, *elems);
+  *elems = 0;
+  TRY(dev_alloc(h, p, count));
+  *elems = count;
+  return MGH_SUCCESS;
+}
+
+// Row-major element strides of a dense box of extents m[0 .. D); returns its element count.
+template <typename E, typename S> uint64_t compact_strides(int D, const E *m, S *ss) {
+  uint64_t bs = 1;
+  for (int d = D - 1; d >= 0; d--) {
+    ss[d] = (S)bs;
+    bs *= m[d];
+  }
+  return bs;
+}
+// ... as the source of the fused level loops (D = 3, 4): A.dI / A.dJ; returns the t-slice stride (D = 4)
+template <typename T, typename E> size_t box_source(RecomposeArgs<T> &A, int D, const E *m) {
+  size_t ss[MGH_MAX_DIM];
+  compact_strides(D, m, ss);
+  A.dJ = ss[D - 2];
+  A.dI = ss[D - 3];
+  return D == 4 ? ss[0] : 0;
+}
+
+// Out-of-dictionary values written over the integers that are about to be read. `kernel`: the one of
+// k_outlier_restore (an array or its head), _in_box (corner box inside the full array), _box (widened
+// compact box), _window (a segment of a linearised array) for what q holds; `where`: its arguments
+// between q and the list.
+template <typename K, typename... W>
+int outliers_back(mgh_hierarchy *h, const QuantSpec &qs, const char *name, hipStream_t st, K kernel, int64_t *q,
+                  W... where) {
+  if (!qs.prep_huffman || !qs.ocount) return MGH_SUCCESS;
+  return launch(h, name, st, [&] {
+    kernel<<<(unsigned)((qs.ocount + 255) / 256), 256, 0, st>>>(q, where..., qs.oidx, qs.oval, qs.ocount);
+  });
+}
+
+// The fused level loops from 16-bit dictionary symbols (what the Huffman decoder of the high-level
+// path delivers; qs.prep_huffman is 1): no int64 array, the out-of-dictionary values are found
+// through a hash table.
 template <typename T>
-int dequantize_recompose_fused16(mgh_hierarchy *h, const uint16_t *sym, int ebtype, double tol, double s,
-                                 double norm, uint64_t dict_size, const uint64_t *oidx,
-                                 const int64_t *oval, uint64_t ocount, T *data, const Layout &out, hipStream_t st,
-                                 int stop = -1) {
+int dequantize_recompose_fused16(mgh_hierarchy *h, const QuantSpec &qs, const uint16_t *sym, T *data,
+                                 const Layout &out, hipStream_t st, int stop) {
   auto *ds = DS<T>(h);
   auto *hh = HH<T>(h);
   const int L = h->L;
+  const uint64_t ocount = qs.ocount;
   RecomposeArgs<T> A{};
   const bool mixed = h->sym16_mixed && L >= 2 && h->total >= ((uint64_t)1 << 18);
   const int ntop = L >= 4 ? 2 : 1;
   // a stop at or below the levels that run on the widened box (mgh_*_to_level): the box of the stop
   // level is all there is to read -- no table, no symbol of the finest levels
-  const bool box_only = mixed && stop >= 0 && stop <= L - ntop;
+  const bool box_only = mixed && stop <= L - ntop;
   if (ocount && !box_only) {
     size_t slots = 16;
     while (slots < 2 * ocount) slots *= 2;
@@ -2190,21 +2242,17 @@ int dequantize_recompose_fused16(mgh_hierarchy *h, const uint16_t *sym, int ebty
     HIP_TRY(hipMemsetAsync(ds->oh_key, 0, slots * 8, st));
     TRY(launch(h, "outlier_table", st, [&] {
       k_outlier_hash_build<<<(unsigned)((ocount + 255) / 256), 256, 0, st>>>(
-          oidx, oval, ocount, h->total, ds->oh_key, ds->oh_val, (uint32_t)(slots - 1));
+          qs.oidx, qs.oval, ocount, h->total, ds->oh_key, ds->oh_val, (uint32_t)(slots - 1));
     }));
     A.oh_key = ds->oh_key;
     A.oh_val = ds->oh_val;
     A.oh_mask = (uint32_t)(slots - 1);
   }
-  std::vector<T> qz(L + 1);
-  hh->quantizers(ebtype, (T)tol, (T)s, (T)norm, false, qz.data());
-  const bool calc_vol = !((T)s == std::numeric_limits<T>::infinity());
   A.q16 = sym;
   A.dI = ds->full_I;
   A.dJ = ds->full_J;
-  A.half = (int64_t)(dict_size / 2);
-  std::vector<T> level_qv(L + 1);
-  for (int l = 0; l <= L; l++) level_qv[l] = qz[l] * (calc_vol ? hh->level_volume(l, true) : (T)1);
+  A.half = dict_half(qs);
+  const std::vector<T> level_qv = level_quanta<T>(h, qs);
   // Symbol width PER LEVEL: the finest levels -- where out-of-dictionary values are rare -- are
   // read as 16-bit symbols with the table look-up behind symbol 0. The levels below hold nearly
   // all the outliers, and a look-up there is a dependent global load inside latency-bound
@@ -2213,47 +2261,29 @@ int dequantize_recompose_fused16(mgh_hierarchy *h, const uint16_t *sym, int ebty
   // written over them, and those levels run the int64 kernels on it. Two levels stay on symbols
   // where the hierarchy is deep enough: the box is then 1/64 (D = 3) of the array instead of 1/8
   // (512^3: widening the 257^3 box cost 51 us, almost all of it the 136 MB of int64 stores).
-  if (mixed) {
-    const auto &Mc = hh->level_shape[box_only ? stop : L - ntop];
-    const auto &N = hh->level_shape[L];
-    BoxMap bm{};
-    for (int k = 0; k < 4; k++) bm.m[k] = bm.n[k] = 1;
-    for (int d = 0; d < h->D; d++) {
-      bm.m[4 - h->D + d] = (uint32_t)Mc[d];
-      bm.n[4 - h->D + d] = (uint32_t)N[d];
-    }
-    const size_t box = (size_t)bm.m[0] * bm.m[1] * bm.m[2] * bm.m[3];
-    if (box > ds->qbox_elems) {  // (counted in mgh_device_bytes: a stop level's box is a fraction of the full call's)
-      dev_free(h, &ds->qbox, ds->qbox_elems);
-      ds->qbox_elems = 0;
-      TRY(dev_alloc(h, &ds->qbox, box));
-      ds->qbox_elems = box;
-    }
-    const size_t rows = box / bm.m[3];
-    if (rows >= ((size_t)1 << 32)) return fail(MGH_ERR_INVALID_ARGUMENT, "coarse box too large");
-    TRY(launch(h, "widen_box", st, [&] {
-      k_widen_box<<<(unsigned)std::min<size_t>((rows + 3) / 4, 256 * 32), 256, 0, st>>>(sym, ds->qbox, bm, (uint32_t)rows);
-    }));
-    if (ocount)
-      TRY(launch(h, "outlier_restore", st, [&] {
-        k_outlier_restore_box<<<(unsigned)((ocount + 255) / 256), 256, 0, st>>>(ds->qbox, bm, oidx, oval, ocount);
-      }));
-    RecomposeArgs<T> A64{};
-    A64.q = ds->qbox;
-    A64.dJ = bm.m[3];
-    A64.dI = (size_t)bm.m[2] * bm.m[3];
-    A64.half = A.half;
-    if (box_only) {
-      if (h->D == 4)
-        return recompose_levels4<T, int64_t>(h, A64, level_qv, data, st, nullptr, (size_t)bm.m[1] * bm.m[2] * bm.m[3], 1, stop);
-      return recompose_levels<T, int64_t>(h, A64, level_qv, data, out, st, nullptr, 1, stop);
-    }
-    if (h->D == 4)
-      return recompose_levels4<T, int64_t, uint16_t>(h, A64, level_qv, data, st, &A, (size_t)bm.m[1] * bm.m[2] * bm.m[3], ntop, stop);
-    return recompose_levels<T, int64_t, uint16_t>(h, A64, level_qv, data, out, st, &A, ntop, stop);
+  if (!mixed) return recompose_levels_any<T, uint16_t>(h, A, 0, level_qv, data, out, st, nullptr, 1, stop);
+  const auto &Mc = hh->level_shape[box_only ? stop : L - ntop];
+  const auto &N = hh->level_shape[L];
+  BoxMap bm{};
+  for (int k = 0; k < 4; k++) bm.m[k] = bm.n[k] = 1;
+  for (int d = 0; d < h->D; d++) {
+    bm.m[4 - h->D + d] = (uint32_t)Mc[d];
+    bm.n[4 - h->D + d] = (uint32_t)N[d];
   }
-  if (h->D == 4) return recompose_levels4<T, uint16_t>(h, A, level_qv, data, st, nullptr, 0, 1, stop);
-  return recompose_levels<T, uint16_t>(h, A, level_qv, data, out, st, nullptr, 1, stop);
+  RecomposeArgs<T> A64{};
+  const size_t sT = box_source(A64, 4, bm.m);
+  const size_t box = sT * bm.m[0];
+  TRY(grow(h, &ds->qbox, &ds->qbox_elems, box));
+  const size_t rows = box / bm.m[3];
+  if (rows >= ((size_t)1 << 32)) return fail(MGH_ERR_INVALID_ARGUMENT, "coarse box too large");
+  TRY(launch(h, "widen_box", st, [&] {
+    k_widen_box<<<(unsigned)std::min<size_t>((rows + 3) / 4, 256 * 32), 256, 0, st>>>(sym, ds->qbox, bm, (uint32_t)rows);
+  }));
+  TRY(outliers_back(h, qs, "outlier_restore", st, k_outlier_restore_box, ds->qbox, bm));
+  A64.q = ds->qbox;
+  A64.half = A.half;
+  if (box_only) return recompose_levels_any<T, int64_t>(h, A64, sT, level_qv, data, out, st, nullptr, 1, stop);
+  return recompose_levels_any<T, int64_t, uint16_t>(h, A64, sT, level_qv, data, out, st, &A, ntop, stop);
 }
 
 template <typename T>
@@ -2290,59 +2320,61 @@ int quantize_launch(mgh_hierarchy *h, const T *coeff, uint64_t dict_size, int pr
 }
 
 template <typename T>
-int dequantize_dense(mgh_hierarchy *h, int64_t *q, int ebtype, double tol, double s, double norm,
-                    uint64_t dict_size, int prep_huffman, const uint64_t *oidx,
-                    const int64_t *oval, uint64_t ocount, T *coeff, hipStream_t st) {
+int dequantize_dense(mgh_hierarchy *h, int64_t *q, const QuantSpec &qs, T *coeff, hipStream_t st) {
   auto *ds = DS<T>(h);
-  TRY(upload_quantizers<T>(h, ebtype, tol, s, norm, false, st));
+  TRY(upload_quantizers<T>(h, qs.ebtype, qs.tol, qs.s, qs.norm, false, st));
   const size_t total = h->total;
-  if (prep_huffman && ocount) {
-    TRY(launch(h, "outlier_restore", st, [&] {
-      k_outlier_restore<<<(unsigned)((ocount + 255) / 256), 256, 0, st>>>(q, h->total, oidx, oval, ocount);
-    }));
-  }
+  TRY(outliers_back(h, qs, "outlier_restore", st, k_outlier_restore, q, h->total));
   const unsigned grid = (unsigned)std::min<size_t>((total + 255) / 256, 256 * 32);
   TRY(launch(h, "dequantize", st, [&] {
     k_dequantize<T><<<grid, 256, 0, st>>>(ds->qmeta, total, q, ds->marks, ds->qz,
-                                          ds->qz + (h->L + 1), (int64_t)dict_size, prep_huffman,
+                                          ds->qz + (h->L + 1), (int64_t)qs.dict_size, qs.prep_huffman,
                                           coeff);
   }));
   return MGH_SUCCESS;
 }
 
-// Compact buffer for the corner box of a stop level on the one-thread-per-element path, whose
-// node restore reads the coefficients while it writes the output.
-template <typename T> int ensure_level_box(mgh_hierarchy *h, size_t count) {
-  auto *ds = DS<T>(h);
-  if (count > ds->level_box_elems) {
-    dev_free(h, &ds->level_box, ds->level_box_elems);
-    ds->level_box_elems = 0;
-    TRY(dev_alloc(h, &ds->level_box, count));
-    ds->level_box_elems = count;
-  }
-  return MGH_SUCCESS;
+uint64_t level_elems(const mgh_hierarchy *h, int level) {
+  uint64_t n = 1;
+  auto f = [&](auto *hh) {
+    for (int d = 0; d < h->D; d++) n *= hh->level_shape[level][d];
+  };
+  if (h->dtype == MGH_FLOAT) f(HH<float>(h));
+  else f(HH<double>(h));
+  return n;
+}
+
+// A level step (Target::start >= 1) starts from the caller's dense array of `level`: the solves
+// subtract the correction from the coarse nodes in place, so on a copy in the level loop's own buffer.
+template <typename T> int coarse_in(mgh_hierarchy *h, T *nodal, const void *coarse, int level, hipStream_t st) {
+  return launch(h, "refine_coarse_in", st, [&] {
+    (void)hipMemcpyAsync(nodal, coarse, level_elems(h, level) * sizeof(T), hipMemcpyDeviceToDevice, st);
+  });
 }
 
 // The level loop on a COMPACT corner box (dense array of level_shape(level)) for the shapes the
 // fused kernels do not take: `fill(dst)` puts the box's coefficients there. The generic N-D kernels
-// work in place, so the box is filled into the output itself.
+// work in place, so the box is filled into the output itself; the node restore of the
+// one-thread-per-element kernels reads the coefficients while it writes the output, so theirs is
+// ds->level_box. start >= 1: the levels start .. level alone, on top of `coarse` (coarse_in).
 template <typename T, typename Fill>
-int recompose_box_to_level(mgh_hierarchy *h, int level, T *out, hipStream_t st, Fill &&fill) {
+int recompose_box_to_level(mgh_hierarchy *h, int level, T *out, hipStream_t st, Fill &&fill, int start = 0,
+                           const void *coarse = nullptr) {
   auto *ds = DS<T>(h);
-  auto *hh = HH<T>(h);
   const int D = h->D;
   if (D > 3 || h->force_nd) {
     TRY(fill(out));
-    return level == 0 ? (int)MGH_SUCCESS : recompose_nd<T>(h, out, st, level);
+    return level == 0 ? (int)MGH_SUCCESS : recompose_nd<T>(h, out, st, level, start);
   }
-  const auto &m = hh->level_shape[level];
-  size_t count = 1;
-  for (int d = 0; d < D; d++) count *= m[d];
   if (level == 0) return fill(out);
-  TRY(ensure_level_box<T>(h, count));
+  size_t ss[3];
+  const size_t count = compact_strides(D, HH<T>(h)->level_shape[level].data(), ss);
+  TRY(grow(h, &ds->level_box, &ds->level_box_elems, count));
   TRY(fill(ds->level_box));
-  const size_t cJ = m[D - 1], cI = (D >= 2 ? m[D - 2] : 1) * cJ;
-  return recompose_v1_levels<T>(h, ds->level_box, cI, cJ, out, level, st);
+  if (start) TRY(coarse_in<T>(h, ds->nodal[start - 1], coarse, start - 1, st));
+  // (the 3-D view: a dimension the array does not have steps over all of it)
+  return recompose_v1_levels<T>(h, ds->level_box, D >= 3 ? ss[D - 3] : count, D >= 2 ? ss[D - 2] : count, out, level,
+                                st, start);
 }
 
 // mgh_recompose_to_level, level < l_target. The fused kernels read the corner box in place, with
@@ -2350,58 +2382,19 @@ int recompose_box_to_level(mgh_hierarchy *h, int level, T *out, hipStream_t st, 
 template <typename T>
 int recompose_to_level_impl(mgh_hierarchy *h, const T *coeff, const Layout &in, int level, T *out, hipStream_t st) {
   const LevelBox lb = level_box_of<T>(h, level, in);
-  if (fused_ok(h) && !h->force_v1 && lb.ss[0] < ((uint64_t)1 << 30)) {
+  const int D = h->D;
+  if (fused_route(h) && (D == 4 || lb.ss[0] < ((uint64_t)1 << 30))) {
     RecomposeArgs<T> A{};
     A.coef = coeff;
-    A.dI = (size_t)lb.ss[0];
-    A.dJ = (size_t)lb.ss[1];
-    return recompose_levels<T, T>(h, A, std::vector<T>(h->L + 1, (T)1), out, dense_layout(h), st, nullptr, 1, level);
-  }
-  if (fused4_ok(h) && !h->force_v1) {
-    RecomposeArgs<T> A{};
-    A.coef = coeff;
-    A.dI = (size_t)lb.ss[1];
-    A.dJ = (size_t)lb.ss[2];
-    return recompose_levels4<T, T>(h, A, std::vector<T>(h->L + 1, (T)1), out, st, nullptr, (size_t)lb.ss[0], 1, level);
+    A.dI = (size_t)lb.ss[D - 3];
+    A.dJ = (size_t)lb.ss[D - 2];
+    return recompose_levels_any<T, T>(h, A, (size_t)lb.ss[0], std::vector<T>(h->L + 1, (T)1), out, dense_layout(h), st,
+                                      nullptr, 1, level);
   }
   const uint64_t rows = level_box_rows(lb);
   return recompose_box_to_level<T>(h, level, out, st, [&](T *dst) {
     return launch(h, "box_gather", st, [&] {
       k_box_gather<T><<<level_box_grid(lb), 256, 0, st>>>(lb, coeff, dst, rows);
-    });
-  });
-}
-
-// mgh_dequantize_recompose_to_level, level < l_target, on the shapes the fused kernels do not take:
-// outliers of the box written back, the box dequantized into a compact array, the level loop on it.
-template <typename T>
-int dequantize_recompose_box_to_level(mgh_hierarchy *h, int64_t *q, int ebtype, double tol, double s, double norm,
-                                      uint64_t dict_size, int prep_huffman, const uint64_t *oidx,
-                                      const int64_t *oval, uint64_t ocount, int level, T *out, hipStream_t st,
-                                      bool compact = false) {
-  // compact: q is the compact corner box of the level itself (dense in level_shape(level), outliers
-  // already in it), read with its own strides
-  auto *ds = DS<T>(h);
-  TRY(upload_quantizers<T>(h, ebtype, tol, s, norm, false, st));
-  LevelBox lb = level_box_of<T>(h, level, dense_layout(h));
-  if (compact) {
-    uint64_t bs = 1;
-    for (int d = h->D - 1; d >= 0; d--) {
-      lb.ss[d] = bs;
-      bs *= lb.m[d];
-    }
-  }
-  if (prep_huffman && ocount && !compact) {
-    TRY(launch(h, "outlier_restore", st, [&] {
-      k_outlier_restore_in_box<<<(unsigned)((ocount + 255) / 256), 256, 0, st>>>(q, lb, oidx, oval, ocount);
-    }));
-  }
-  const uint64_t rows = level_box_rows(lb);
-  return recompose_box_to_level<T>(h, level, out, st, [&](T *dst) {
-    return launch(h, "box_dequantize", st, [&] {
-      k_box_dequantize<T><<<level_box_grid(lb), 256, 0, st>>>(lb, ds->qmeta, q, ds->marks, ds->qz,
-                                                                 ds->qz + (h->L + 1), (int64_t)dict_size,
-                                                                 prep_huffman, dst, rows);
     });
   });
 }
@@ -2640,12 +2633,10 @@ int quantize_impl(mgh_hierarchy *h, const T *coeff, Layout in, int ebtype, doubl
 }
 
 template <typename T>
-int dequantize_impl(mgh_hierarchy *h, int64_t *q, int ebtype, double tol, double s, double norm,
-                    uint64_t dict_size, int prep_huffman, const uint64_t *oidx,
-                    const int64_t *oval, uint64_t ocount, T *coeff, Layout out, hipStream_t st) {
+int dequantize_impl(mgh_hierarchy *h, int64_t *q, const QuantSpec &qs, T *coeff, Layout out, hipStream_t st) {
   LdOut<T> o;
   TRY(o.begin(h, coeff, out, false));
-  TRY(dequantize_dense<T>(h, q, ebtype, tol, s, norm, dict_size, prep_huffman, oidx, oval, ocount, coeff, st));
+  TRY(dequantize_dense<T>(h, q, qs, coeff, st));
   return o.finish(h, st);
 }
 
@@ -2796,23 +2787,146 @@ int decompose_quantize(mgh_hierarchy *h, const T *data, Layout in, int ebtype, d
   return o.finish(h, st);
 }
 
-// mgh_dequantize_recompose: the fused level loop, or dequantizer and recomposition in place on the
-// (dense) output.
+// the level shapes and level marks the linearisation kernels read (kernels_v1.hpp)
+const int *lin_meta(mgh_hierarchy *h, mgh::LinMeta &m) {
+  const int *marks = nullptr;
+  auto fill = [&](auto *hh, auto *ds) {
+    m.D = hh->D;
+    m.L = hh->L;
+    for (int d = 0; d < hh->D; d++) {
+      m.shape[d] = (uint32_t)hh->shape[d];
+      m.markoff[d] = ds->qmeta.markoff[d];
+      for (int l = 0; l <= hh->L; l++) m.lshape[l][d] = (uint32_t)hh->level_shape[l][d];
+    }
+    marks = ds->marks;
+  };
+  if (h->dtype == MGH_FLOAT) fill(HH<float>(h), DS<float>(h));
+  else fill(HH<double>(h), DS<double>(h));
+  return marks;
+}
+
+// What box_from_linear and shell_from_linear share: the level shapes, and the strides of the compact
+// box of `level` ...
+int lin_box_begin(mgh_hierarchy *h, int level, mgh::LinMeta &m, mgh::LinBox &B) {
+  if (h->L + 1 > mgh::kLinMaxLevels + 1) return fail(MGH_ERR_INVALID_ARGUMENT, "too many levels");
+  (void)lin_meta(h, m);
+  B.level = level;
+  compact_strides(h->D, m.lshape[level], B.bs);
+  return MGH_SUCCESS;
+}
+// ... and B.unit0[k + 1]: the units (pieces of rows, one wave each) of a box of extents e behind B.unit0[k]
+int lin_box_units(const mgh_hierarchy *h, mgh::LinBox &B, int k, const uint32_t *e, bool none = false) {
+  const int D = h->D;
+  uint64_t rows = 1;
+  for (int d = 0; d < D - 1; d++) rows *= e[d];
+  const uint64_t units = none ? 0 : rows * ((e[D - 1] + kLevelBoxPiece - 1) / kLevelBoxPiece);
+  if (units >= ((uint64_t)1 << 32)) return fail(MGH_ERR_INVALID_ARGUMENT, "level box too large");
+  B.unit0[k + 1] = B.unit0[k] + units;
+  return MGH_SUCCESS;
+}
+
+// The compact corner box of `level` (dense in level_shape(level)) out of the first N_level integers
+// of a level-linearised array: k_box_from_linear, one wave per piece of a run of the stream.
+int box_from_linear(mgh_hierarchy *h, const int64_t *lin, int level, int64_t *box, hipStream_t st) {
+  mgh::LinMeta m{};
+  mgh::LinBox B{};
+  TRY(lin_box_begin(h, level, m, B));
+  for (int j = 0; j <= level; j++) TRY(lin_box_units(h, B, j, m.lshape[j]));
+  const unsigned grid = (unsigned)std::min<uint64_t>((B.unit0[level + 1] + 3) / 4, 256 * 32);
+  return launch(h, "box_from_linear", st, [&] { mgh::k_box_from_linear<<<grid, 256, 0, st>>>(m, B, lin, box); });
+}
+
+// The shell of the compact box of `level` (dense in level_shape(level)) out of the level's own segment
+// [N_{level-1}, N_level) of a level-linearised array: k_shell_from_linear. fill_inner: the inner box
+// of level - 1 gets `inner` (the fused node restore loads those positions).
+int shell_from_linear(mgh_hierarchy *h, const int64_t *seg, int level, int64_t *box, bool fill_inner, int64_t inner,
+                      hipStream_t st) {
+  mgh::LinMeta m{};
+  mgh::LinBox B{};
+  TRY(lin_box_begin(h, level, m, B));
+  for (int k = 0; k < 2; k++)  // the runs of the level; the rows of the inner box
+    TRY(lin_box_units(h, B, k, m.lshape[level - k], k == 1 && !fill_inner));
+  const unsigned grid = (unsigned)std::min<uint64_t>((B.unit0[2] + 3) / 4, 256 * 32);
+  return launch(h, "shell_from_linear", st, [&] { mgh::k_shell_from_linear<<<grid, 256, 0, st>>>(m, B, seg, box, inner); });
+}
+
+// ---- the reconstruction core ---------------------------------------------------------------------
+// Everything behind mgh_dequantize_recompose{,_to_level,_linear_to_level,_sym16,_sym16_to_level} and
+// mgh_refine_level: integers `src` with the parameters `qs` to the array `tg`. The route:
+//   - the fused level loops (3-D, 4-D) read the integers where they are, with the source's strides;
+//   - the other shapes, whole array: dequantizer and recomposition in place on the (dense) output;
+//   - the other shapes, a stop level or a level step: the box dequantized into a compact
+//     floating-point array, then the one-thread-per-element or N-D levels (recompose_box_to_level).
 template <typename T>
-int dequantize_recompose(mgh_hierarchy *h, int64_t *q, int ebtype, double tol, double s, double norm,
-                         uint64_t dict_size, int prep_huffman, const uint64_t *oidx, const int64_t *oval,
-                         uint64_t ocount, T *data, Layout out, hipStream_t st) {
-  const bool fused = fusedc_ok(h) && !h->force_v1;
+int reconstruct(mgh_hierarchy *h, QuantSpec qs, IntSource src, const Target &tg, hipStream_t st) {
+  auto *ds = DS<T>(h);
+  const int D = h->D, L = h->L, stop = tg.stop, start = tg.start;
+  const bool fused = fused_route(h);
+  T *out = (T *)tg.out;
+  Layout lay = tg.lay;
   LdOut<T> o;
-  TRY(o.begin(h, data, out, fused));
-  if (fused) {
-    TRY(dequantize_recompose_fused<T>(h, q, ebtype, tol, s, norm, dict_size, prep_huffman, oidx, oval, ocount, data,
-                                      out, st));
-  } else {
-    TRY(dequantize_dense<T>(h, q, ebtype, tol, s, norm, dict_size, prep_huffman, oidx, oval, ocount, data, st));
-    TRY(recompose_dense<T>(h, data, data, st));
+  TRY(o.begin(h, out, lay, fused));
+  if (src.kind == IntSource::Sym16) {
+    TRY(dequantize_recompose_fused16<T>(h, qs, src.sym, out, lay, st, stop));
+    return o.finish(h, st);
   }
-  return o.finish(h, st);
+  if (src.kind == IntSource::Linear) {
+    // outliers at their linearised positions (those behind the head, or outside the segment, are
+    // skipped), then the compact box of the stop level in ds->qbox: nothing left to restore
+    const uint64_t n = level_elems(h, stop);
+    if (start) TRY(outliers_back(h, qs, "outlier_restore_window", st, k_outlier_restore_window, src.q,
+                                 level_elems(h, stop - 1), n));
+    else TRY(outliers_back(h, qs, "outlier_restore", st, k_outlier_restore, src.q, n));
+    TRY(grow(h, &ds->qbox, &ds->qbox_elems, n));
+    if (start) TRY(shell_from_linear(h, src.q, stop, ds->qbox, fused, dict_half(qs), st));
+    else TRY(box_from_linear(h, src.q, stop, ds->qbox, st));
+    src = IntSource{IntSource::Box, ds->qbox, nullptr};
+    qs.ocount = 0;
+  }
+  // (the box of l_target is the full array)
+  const bool compact = src.kind == IntSource::Box && stop < L;
+  LevelBox lb = level_box_of<T>(h, stop, dense_layout(h));  // what is read of src.q
+  if (compact) compact_strides(D, lb.m, lb.ss);
+  if (fused) {
+    if (stop < L) TRY(outliers_back(h, qs, "outlier_restore", st, k_outlier_restore_in_box, src.q, lb));
+    else TRY(outliers_back(h, qs, "outlier_restore", st, k_outlier_restore, src.q, h->total));
+    if (start) {
+      if (D == 4) TRY(ensure_state4<T>(h));
+      TRY(coarse_in<T>(h, D == 4 ? ds->nodal4[start - 1] : ds->nodal[start - 1], tg.coarse, start - 1, st));
+    }
+    RecomposeArgs<T> A{};
+    A.q = src.q;
+    A.half = dict_half(qs);
+    A.dI = ds->full_I;
+    A.dJ = ds->full_J;
+    const size_t sT = compact ? box_source(A, D, lb.m) : 0;
+    TRY((recompose_levels_any<T, int64_t>(h, A, sT, level_quanta<T>(h, qs), out, lay, st, nullptr, 1, stop, start)));
+    return o.finish(h, st);
+  }
+  if (stop == L && !start) {
+    TRY(dequantize_dense<T>(h, src.q, qs, out, st));
+    TRY(recompose_dense<T>(h, out, out, st));
+    return o.finish(h, st);
+  }
+  TRY(upload_quantizers<T>(h, qs.ebtype, qs.tol, qs.s, qs.norm, false, st));
+  TRY(outliers_back(h, qs, "outlier_restore", st, k_outlier_restore_in_box, src.q, lb));
+  if (start)  // (k_box_refine_fill: the inner box is the coarse array, the shell is dequantized)
+    for (int d = 0; d < D; d++) lb.n[d] = (uint32_t)HH<T>(h)->level_shape[stop - 1][d];
+  const uint64_t rows = level_box_rows(lb);
+  const T *coarse = (const T *)tg.coarse;
+  return recompose_box_to_level<T>(h, stop, out, st, [&](T *dst) {
+    if (start)
+      return launch(h, "box_refine_fill", st, [&] {
+        k_box_refine_fill<T><<<level_box_grid(lb), 256, 0, st>>>(lb, ds->qmeta, src.q, coarse, ds->marks, ds->qz,
+                                                                    ds->qz + (L + 1), (int64_t)qs.dict_size,
+                                                                    qs.prep_huffman, dst, rows);
+      });
+    return launch(h, "box_dequantize", st, [&] {
+      k_box_dequantize<T><<<level_box_grid(lb), 256, 0, st>>>(lb, ds->qmeta, src.q, ds->marks, ds->qz,
+                                                                 ds->qz + (L + 1), (int64_t)qs.dict_size,
+                                                                 qs.prep_huffman, dst, rows);
+    });
+  }, start, tg.coarse);
 }
 
 // Norm accumulated over parts of the input (mgh_norm_stream_begin / _add): the same reduction
@@ -3082,11 +3196,10 @@ int mgh_dequantize(mgh_hierarchy *h, int64_t *d_quantized, int ebtype, double to
                    uint64_t outlier_count, void *d_coeff, void *stream) {
   if (!h || !d_coeff || !d_quantized) return fail(MGH_ERR_INVALID_ARGUMENT, "null argument");
   HIP_TRY(hipSetDevice(h->device));
+  const QuantSpec qs{ebtype, tol, s, norm, dict_size, prep_huffman, d_outlier_idx, d_outlier_val, outlier_count};
   return with_type(h, [&](auto t) {
     using T = decltype(t);
-    return dequantize_impl<T>(h, d_quantized, ebtype, tol, s, norm, dict_size, prep_huffman, d_outlier_idx,
-                              d_outlier_val, outlier_count, (T *)d_coeff, caller_layout(h, MGH_LD_OUT),
-                              (hipStream_t)stream);
+    return dequantize_impl<T>(h, d_quantized, qs, (T *)d_coeff, caller_layout(h, MGH_LD_OUT), (hipStream_t)stream);
   });
 }
 
@@ -3124,6 +3237,12 @@ int mgh_sym16_supported(const mgh_hierarchy *h) {
   return h && fusedc_ok(h) && !h->force_v1 ? 1 : 0;
 }
 
+// The body of the reconstruction entry points: the core in the hierarchy's data type, on its device.
+static int reconstruct_entry(mgh_hierarchy *h, const QuantSpec &qs, const IntSource &src, const Target &tg, void *stream) {
+  HIP_TRY(hipSetDevice(h->device));
+  return with_type(h, [&](auto t) { return reconstruct<decltype(t)>(h, qs, src, tg, (hipStream_t)stream); });
+}
+
 int mgh_dequantize_recompose_sym16(mgh_hierarchy *h, const uint16_t *d_symbols, int error_bound_type,
                                    double tol, double s, double norm, uint64_t dict_size,
                                    const uint64_t *d_outlier_idx, const int64_t *d_outlier_val,
@@ -3131,20 +3250,11 @@ int mgh_dequantize_recompose_sym16(mgh_hierarchy *h, const uint16_t *d_symbols, 
   if (!h || !d_symbols || !d_data_out || (outlier_count && (!d_outlier_idx || !d_outlier_val)))
     return fail(MGH_ERR_INVALID_ARGUMENT, "null argument");
   if (dict_size == 0 || dict_size > 65536) return fail(MGH_ERR_INVALID_ARGUMENT, "dict_size must be in 1..65536");
-  HIP_TRY(hipSetDevice(h->device));
   if (!mgh_sym16_supported(h))
     return fail(MGH_ERR_UNSUPPORTED_DIMENSION, "16-bit symbols: only on the fused 3-D / 4-D path");
-  hipStream_t st = (hipStream_t)stream;
-  return with_type(h, [&](auto t) -> int {
-    using T = decltype(t);
-    T *data = (T *)d_data_out;
-    Layout out = caller_layout(h, MGH_LD_OUT);
-    LdOut<T> o;
-    TRY(o.begin(h, data, out, true));
-    TRY(dequantize_recompose_fused16<T>(h, d_symbols, error_bound_type, tol, s, norm, dict_size, d_outlier_idx,
-                                        d_outlier_val, outlier_count, data, out, st));
-    return o.finish(h, st);
-  });
+  return reconstruct_entry(h, {error_bound_type, tol, s, norm, dict_size, 1, d_outlier_idx, d_outlier_val, outlier_count},
+                           {IntSource::Sym16, nullptr, d_symbols},
+                           {h->L, 0, nullptr, d_data_out, caller_layout(h, MGH_LD_OUT)}, stream);
 }
 
 int mgh_decompose_quantize(mgh_hierarchy *h, const void *d_data, int error_bound_type, double tol, double s,
@@ -3220,13 +3330,9 @@ int mgh_dequantize_recompose(mgh_hierarchy *h, int64_t *d_quantized, int ebtype,
                              const uint64_t *d_outlier_idx, const int64_t *d_outlier_val,
                              uint64_t outlier_count, void *d_data, void *stream) {
   if (!h || !d_data || !d_quantized) return fail(MGH_ERR_INVALID_ARGUMENT, "null argument");
-  HIP_TRY(hipSetDevice(h->device));
-  return with_type(h, [&](auto t) {
-    using T = decltype(t);
-    return dequantize_recompose<T>(h, d_quantized, ebtype, tol, s, norm, dict_size, prep_huffman, d_outlier_idx,
-                                   d_outlier_val, outlier_count, (T *)d_data, caller_layout(h, MGH_LD_OUT),
-                                   (hipStream_t)stream);
-  });
+  return reconstruct_entry(h, {ebtype, tol, s, norm, dict_size, prep_huffman, d_outlier_idx, d_outlier_val, outlier_count},
+                           {IntSource::Full, d_quantized, nullptr},
+                           {h->L, 0, nullptr, d_data, caller_layout(h, MGH_LD_OUT)}, stream);
 }
 
 int mgh_level_nodes(const mgh_hierarchy *h, int level, int dim, uint64_t *h_idx_out, uint64_t cap) {
@@ -3241,87 +3347,6 @@ int mgh_level_nodes(const mgh_hierarchy *h, int level, int dim, uint64_t *h_idx_
 }
 
 namespace {
-// the level shapes and level marks the linearisation kernels read (kernels_v1.hpp)
-const int *lin_meta(mgh_hierarchy *h, mgh::LinMeta &m) {
-  const int *marks = nullptr;
-  auto fill = [&](auto *hh, auto *ds) {
-    m.D = hh->D;
-    m.L = hh->L;
-    for (int d = 0; d < hh->D; d++) {
-      m.shape[d] = (uint32_t)hh->shape[d];
-      m.markoff[d] = ds->qmeta.markoff[d];
-      for (int l = 0; l <= hh->L; l++) m.lshape[l][d] = (uint32_t)hh->level_shape[l][d];
-    }
-    marks = ds->marks;
-  };
-  if (h->dtype == MGH_FLOAT) fill(HH<float>(h), DS<float>(h));
-  else fill(HH<double>(h), DS<double>(h));
-  return marks;
-}
-
-// The compact corner box of `level` (dense in level_shape(level)) out of the first N_level integers
-// of a level-linearised array: k_box_from_linear, one wave per piece of a run of the stream.
-int box_from_linear(mgh_hierarchy *h, const int64_t *lin, int level, int64_t *box, hipStream_t st) {
-  if (h->L + 1 > mgh::kLinMaxLevels + 1) return fail(MGH_ERR_INVALID_ARGUMENT, "too many levels");
-  mgh::LinMeta m{};
-  (void)lin_meta(h, m);
-  mgh::LinBox B{};
-  B.level = level;
-  const int D = h->D;
-  uint64_t bs = 1;
-  for (int d = D - 1; d >= 0; d--) {
-    B.bs[d] = bs;
-    bs *= m.lshape[level][d];
-  }
-  for (int j = 0; j <= level; j++) {
-    uint64_t rows = 1;
-    for (int d = 0; d < D - 1; d++) rows *= m.lshape[j][d];
-    const uint64_t units = rows * ((m.lshape[j][D - 1] + kLevelBoxPiece - 1) / kLevelBoxPiece);
-    if (units >= ((uint64_t)1 << 32)) return fail(MGH_ERR_INVALID_ARGUMENT, "level box too large");
-    B.unit0[j + 1] = B.unit0[j] + units;
-  }
-  const unsigned grid = (unsigned)std::min<uint64_t>((B.unit0[level + 1] + 3) / 4, 256 * 32);
-  return launch(h, "box_from_linear", st, [&] { mgh::k_box_from_linear<<<grid, 256, 0, st>>>(m, B, lin, box); });
-}
-
-// The shell of the compact box of `level` (dense in level_shape(level)) out of the level's own segment
-// [N_{level-1}, N_level) of a level-linearised array: k_shell_from_linear. fill_inner: the inner box
-// of level - 1 gets `inner` (the fused node restore loads those positions).
-int shell_from_linear(mgh_hierarchy *h, const int64_t *seg, int level, int64_t *box, bool fill_inner, int64_t inner,
-                      hipStream_t st) {
-  if (h->L + 1 > mgh::kLinMaxLevels + 1) return fail(MGH_ERR_INVALID_ARGUMENT, "too many levels");
-  mgh::LinMeta m{};
-  (void)lin_meta(h, m);
-  mgh::LinBox B{};
-  B.level = level;
-  const int D = h->D;
-  uint64_t bs = 1;
-  for (int d = D - 1; d >= 0; d--) {
-    B.bs[d] = bs;
-    bs *= m.lshape[level][d];
-  }
-  for (int k = 0; k < 2; k++) {  // the runs of the level; the rows of the inner box
-    const uint32_t *e = m.lshape[level - k];
-    uint64_t rows = 1;
-    for (int d = 0; d < D - 1; d++) rows *= e[d];
-    const uint64_t units = k == 1 && !fill_inner ? 0 : rows * ((e[D - 1] + kLevelBoxPiece - 1) / kLevelBoxPiece);
-    if (units >= ((uint64_t)1 << 32)) return fail(MGH_ERR_INVALID_ARGUMENT, "level box too large");
-    B.unit0[k + 1] = B.unit0[k] + units;
-  }
-  const unsigned grid = (unsigned)std::min<uint64_t>((B.unit0[2] + 3) / 4, 256 * 32);
-  return launch(h, "shell_from_linear", st, [&] { mgh::k_shell_from_linear<<<grid, 256, 0, st>>>(m, B, seg, box, inner); });
-}
-
-uint64_t level_elems(const mgh_hierarchy *h, int level) {
-  uint64_t n = 1;
-  auto f = [&](auto *hh) {
-    for (int d = 0; d < h->D; d++) n *= hh->level_shape[level][d];
-  };
-  if (h->dtype == MGH_FLOAT) f(HH<float>(h));
-  else f(HH<double>(h));
-  return n;
-}
-
 int level_arg(const mgh_hierarchy *h, int level) {
   if (level < 0 || level > h->L) return fail(MGH_ERR_INVALID_ARGUMENT, "level outside 0 .. l_target");
   return MGH_SUCCESS;
@@ -3352,20 +3377,8 @@ int mgh_dequantize_recompose_to_level(mgh_hierarchy *h, int64_t *d_quantized, in
   if (prep_huffman && outlier_count && (!d_outlier_idx || !d_outlier_val))
     return fail(MGH_ERR_INVALID_ARGUMENT, "null outlier list");
   TRY(level_arg(h, level));
-  HIP_TRY(hipSetDevice(h->device));
-  hipStream_t st = (hipStream_t)stream;
-  return with_type(h, [&](auto t) {
-    using T = decltype(t);
-    if (level == h->L)
-      return dequantize_recompose<T>(h, d_quantized, ebtype, tol, s, norm, dict_size, prep_huffman, d_outlier_idx,
-                                     d_outlier_val, outlier_count, (T *)d_out, dense_layout(h), st);
-    if (fusedc_ok(h) && !h->force_v1)
-      return dequantize_recompose_fused<T>(h, d_quantized, ebtype, tol, s, norm, dict_size, prep_huffman,
-                                           d_outlier_idx, d_outlier_val, outlier_count, (T *)d_out, dense_layout(h),
-                                           st, level);
-    return dequantize_recompose_box_to_level<T>(h, d_quantized, ebtype, tol, s, norm, dict_size, prep_huffman,
-                                                d_outlier_idx, d_outlier_val, outlier_count, level, (T *)d_out, st);
-  });
+  return reconstruct_entry(h, {ebtype, tol, s, norm, dict_size, prep_huffman, d_outlier_idx, d_outlier_val, outlier_count},
+                           {IntSource::Full, d_quantized, nullptr}, {level, 0, nullptr, d_out, dense_layout(h)}, stream);
 }
 
 int mgh_level_box_from_linear(mgh_hierarchy *h, const int64_t *d_linear, int level, int64_t *d_box_out, void *stream) {
@@ -3387,120 +3400,13 @@ int mgh_dequantize_recompose_linear_to_level(mgh_hierarchy *h, int64_t *d_linear
   if (prep_huffman && outlier_count && (!d_outlier_idx || !d_outlier_val))
     return fail(MGH_ERR_INVALID_ARGUMENT, "null outlier list");
   TRY(level_arg(h, level));
-  HIP_TRY(hipSetDevice(h->device));
-  hipStream_t st = (hipStream_t)stream;
-  return with_type(h, [&](auto t) {
-    using T = decltype(t);
-    auto *ds = DS<T>(h);
-    const uint64_t n_level = level_elems(h, level);
-    if (prep_huffman && outlier_count) {  // (linearised positions: those behind the head are skipped)
-      TRY(launch(h, "outlier_restore", st, [&] {
-        k_outlier_restore<<<(unsigned)((outlier_count + 255) / 256), 256, 0, st>>>(d_linear, n_level, d_outlier_idx,
-                                                                                  d_outlier_val, outlier_count);
-      }));
-    }
-    if (n_level > ds->qbox_elems) {  // (counted in mgh_device_bytes)
-      dev_free(h, &ds->qbox, ds->qbox_elems);
-      ds->qbox_elems = 0;
-      TRY(dev_alloc(h, &ds->qbox, n_level));
-      ds->qbox_elems = n_level;
-    }
-    TRY(box_from_linear(h, d_linear, level, ds->qbox, st));
-    if (level == h->L)
-      return dequantize_recompose<T>(h, ds->qbox, ebtype, tol, s, norm, dict_size, prep_huffman, nullptr, nullptr, 0,
-                                     (T *)d_out, dense_layout(h), st);
-    const auto &m = HH<T>(h)->level_shape[level];
-    if (fusedc_ok(h) && !h->force_v1)
-      return dequantize_recompose_fused<T>(h, ds->qbox, ebtype, tol, s, norm, dict_size, prep_huffman, nullptr,
-                                           nullptr, 0, (T *)d_out, dense_layout(h), st, level, m.data());
-    return dequantize_recompose_box_to_level<T>(h, ds->qbox, ebtype, tol, s, norm, dict_size, prep_huffman, nullptr,
-                                                nullptr, 0, level, (T *)d_out, st, /*compact=*/true);
-  });
+  return reconstruct_entry(h, {ebtype, tol, s, norm, dict_size, prep_huffman, d_outlier_idx, d_outlier_val, outlier_count},
+                           {IntSource::Linear, d_linear, nullptr}, {level, 0, nullptr, d_out, dense_layout(h)}, stream);
 }
 
 // One level step: the dense nodal array of level - 1 and the level's own segment of a level-linearised
 // array to the dense array of `level` -- one pass of the level loop of
 // mgh_dequantize_recompose_linear_to_level, with the box of the level made from the segment alone.
-extern "C++" {
-template <typename T>
-static int refine_level(mgh_hierarchy *h, const T *coarse, int64_t *seg, int ebtype, double tol, double s, double norm,
-                        uint64_t dict_size, int prep_huffman, const uint64_t *oidx, const int64_t *oval,
-                        uint64_t ocount, int level, T *out, hipStream_t st) {
-  auto *ds = DS<T>(h);
-  auto *hh = HH<T>(h);
-  const int D = h->D, L = h->L;
-  const uint64_t n_lo = level_elems(h, level - 1), n_hi = level_elems(h, level);
-  if (prep_huffman && ocount) {  // (linearised positions of the whole array: those of this level)
-    TRY(launch(h, "outlier_restore_window", st, [&] {
-      k_outlier_restore_window<<<(unsigned)((ocount + 255) / 256), 256, 0, st>>>(seg, n_lo, n_hi, oidx, oval, ocount);
-    }));
-  }
-  if (n_hi > ds->qbox_elems) {  // (counted in mgh_device_bytes)
-    dev_free(h, &ds->qbox, ds->qbox_elems);
-    ds->qbox_elems = 0;
-    TRY(dev_alloc(h, &ds->qbox, n_hi));
-    ds->qbox_elems = n_hi;
-  }
-  const bool fused = fusedc_ok(h) && !h->force_v1;
-  const int64_t half = prep_huffman ? (int64_t)(dict_size / 2) : 0;
-  TRY(shell_from_linear(h, seg, level, ds->qbox, fused, half, st));
-  const auto &m = hh->level_shape[level];
-  if (fused) {
-    // the r-solve subtracts the correction from the coarse nodes in place: on a copy
-    if (D == 4) TRY(ensure_state4<T>(h));
-    T *nodal = D == 4 ? ds->nodal4[level - 1] : ds->nodal[level - 1];
-    TRY(launch(h, "refine_coarse_in", st, [&] {
-      (void)hipMemcpyAsync(nodal, coarse, n_lo * sizeof(T), hipMemcpyDeviceToDevice, st);
-    }));
-    std::vector<T> qz(L + 1);
-    hh->quantizers(ebtype, (T)tol, (T)s, (T)norm, false, qz.data());
-    const bool calc_vol = !((T)s == std::numeric_limits<T>::infinity());
-    std::vector<T> level_qv(L + 1);
-    for (int l = 0; l <= L; l++) level_qv[l] = qz[l] * (calc_vol ? hh->level_volume(l, true) : (T)1);
-    RecomposeArgs<T> A{};
-    A.q = ds->qbox;
-    A.half = half;
-    A.dJ = m[D - 1];
-    A.dI = m[D - 2] * m[D - 1];
-    if (D == 4)
-      return recompose_levels4<T, int64_t>(h, A, level_qv, out, st, nullptr, (size_t)(m[1] * m[2] * m[3]), 1, level, level);
-    return recompose_levels<T, int64_t>(h, A, level_qv, out, dense_layout(h), st, nullptr, 1, level, level);
-  }
-  // the other shapes: a compact floating-point box -- inner box = the coarse array, shell dequantized
-  TRY(upload_quantizers<T>(h, ebtype, tol, s, norm, false, st));
-  LevelBox lb{};
-  lb.D = D;
-  for (int d = 0; d < D; d++) {
-    lb.m[d] = (uint32_t)m[d];
-    lb.n[d] = (uint32_t)hh->level_shape[level - 1][d];
-  }
-  uint64_t bs = 1;
-  for (int d = D - 1; d >= 0; d--) {
-    lb.ss[d] = bs;
-    bs *= lb.m[d];
-  }
-  const uint64_t rows = level_box_rows(lb);
-  auto fill = [&](T *dst) {
-    return launch(h, "box_refine_fill", st, [&] {
-      k_box_refine_fill<T><<<level_box_grid(lb), 256, 0, st>>>(lb, ds->qmeta, ds->qbox, coarse, ds->marks, ds->qz,
-                                                                  ds->qz + (L + 1), (int64_t)dict_size, prep_huffman,
-                                                                  dst, rows);
-    });
-  };
-  if (D > 3 || h->force_nd) {  // (the generic N-D kernels work in place: the box is the output)
-    TRY(fill(out));
-    return recompose_nd<T>(h, out, st, level, level);
-  }
-  TRY(ensure_level_box<T>(h, n_hi));
-  TRY(fill(ds->level_box));
-  TRY(launch(h, "refine_coarse_in", st, [&] {
-    (void)hipMemcpyAsync(ds->nodal[level - 1], coarse, n_lo * sizeof(T), hipMemcpyDeviceToDevice, st);
-  }));
-  const size_t cJ = m[D - 1], cI = (D >= 2 ? m[D - 2] : 1) * cJ;
-  return recompose_v1_levels<T>(h, ds->level_box, cI, cJ, out, level, st, level);
-}
-}  // extern "C++"
-
 int mgh_refine_level(mgh_hierarchy *h, const void *d_coarse, int64_t *d_segment, int ebtype, double tol, double s,
                      double norm, uint64_t dict_size, int prep_huffman, const uint64_t *d_outlier_idx,
                      const int64_t *d_outlier_val, uint64_t outlier_count, int level, void *d_out, void *stream) {
@@ -3510,12 +3416,8 @@ int mgh_refine_level(mgh_hierarchy *h, const void *d_coarse, int64_t *d_segment,
   if (level < 1 || level > h->L) return fail(MGH_ERR_INVALID_ARGUMENT, "mgh_refine_level: level outside 1 .. l_target");
   if (d_out == d_coarse || d_out == (void *)d_segment)
     return fail(MGH_ERR_INVALID_ARGUMENT, "mgh_refine_level: d_out must not alias an input");
-  HIP_TRY(hipSetDevice(h->device));
-  return with_type(h, [&](auto t) {
-    using T = decltype(t);
-    return refine_level<T>(h, (const T *)d_coarse, d_segment, ebtype, tol, s, norm, dict_size, prep_huffman,
-                           d_outlier_idx, d_outlier_val, outlier_count, level, (T *)d_out, (hipStream_t)stream);
-  });
+  return reconstruct_entry(h, {ebtype, tol, s, norm, dict_size, prep_huffman, d_outlier_idx, d_outlier_val, outlier_count},
+                           {IntSource::Linear, d_segment, nullptr}, {level, level, d_coarse, d_out, dense_layout(h)}, stream);
 }
 
 int mgh_dequantize_recompose_sym16_to_level(mgh_hierarchy *h, const uint16_t *d_symbols, int error_bound_type,
@@ -3528,13 +3430,8 @@ int mgh_dequantize_recompose_sym16_to_level(mgh_hierarchy *h, const uint16_t *d_
   TRY(level_arg(h, level));
   if (!mgh_sym16_supported(h))
     return fail(MGH_ERR_UNSUPPORTED_DIMENSION, "16-bit symbols: only on the fused 3-D / 4-D path");
-  HIP_TRY(hipSetDevice(h->device));
-  return with_type(h, [&](auto t) {
-    using T = decltype(t);
-    return dequantize_recompose_fused16<T>(h, d_symbols, error_bound_type, tol, s, norm, dict_size, d_outlier_idx,
-                                           d_outlier_val, outlier_count, (T *)d_out, dense_layout(h),
-                                           (hipStream_t)stream, level == h->L ? -1 : level);
-  });
+  return reconstruct_entry(h, {error_bound_type, tol, s, norm, dict_size, 1, d_outlier_idx, d_outlier_val, outlier_count},
+                           {IntSource::Sym16, nullptr, d_symbols}, {level, 0, nullptr, d_out, dense_layout(h)}, stream);
 }
 
 #ifdef MGH_PHASE_TIMING

@@ -2064,16 +2064,17 @@ int trim_hierarchy_cache() {
 }
 
 // A hierarchy owns the workspace of the subdomain that runs on it, so the two lanes of the
-// pipeline keep separate ones (`lane` is part of the key).
+// pipeline keep separate ones (`lane` is part of the key). cached = false: one of the caller's own,
+// always owned (the progressive reader keeps the state of its level loop in it between the calls).
 int get_hierarchy(mgh_hierarchy **out, bool *owned, int dtype, const std::vector<uint64_t> &shape,
                   const std::vector<std::vector<double>> *coords, const std::vector<uint64_t> &off,
-                  const mgh_config &cfg, int lane = 0) {
+                  const mgh_config &cfg, int lane = 0, bool cached = true) {
   const int D = (int)shape.size();
   if (!coords) {
     std::vector<uint64_t> key = {(uint64_t)lane, (uint64_t)dtype, (uint64_t)cfg.normalize_coordinates,
                                  cfg.max_larget_level};
     key.insert(key.end(), shape.begin(), shape.end());
-    auto it = g_cache.hier.find(key);
+    auto it = cached ? g_cache.hier.find(key) : g_cache.hier.end();
     if (it != g_cache.hier.end()) {
       *out = it->second;
       *owned = false;
@@ -2086,7 +2087,7 @@ int get_hierarchy(mgh_hierarchy **out, bool *owned, int dtype, const std::vector
     // A full cache is emptied between calls only (trim_hierarchy_cache): inside a call a cached
     // hierarchy may be at work on the other lane. A shape that does not fit any more is built for
     // its subdomain alone.
-    *owned = g_cache.hier.size() >= kHierCacheMax;
+    *owned = !cached || g_cache.hier.size() >= kHierCacheMax;
     if (!*owned) g_cache.hier[key] = h;
     return MGH_SUCCESS;
   }
@@ -2633,6 +2634,122 @@ int header_level_shape(const fmt::Header &hd, const mgh_config &cfg, int level, 
   return MGH_SUCCESS;
 }
 
+// ---- what the decoders (mgh_decompress*, mgh_progressive_*) share ------------------------------------
+// One subdomain record inside a container.
+struct RecordView {
+  int lossless = MGH_LOSSLESS_HUFFMAN;  // the header's compressor as a lossless mode
+  const uint8_t *rec = nullptr;         // the record, behind its 8-byte size prefix (borrowed from the container)
+  uint64_t csize = 0;
+  bool raw = false;                     // it holds the data itself (the lossless stage did not pay)
+};
+// ... its part from the header: refuses the containers no decoder here reads
+int record_view_header(const fmt::Header &hd, RecordView &rv) {
+  if (hd.compressor == fmt::COMP_X_HUFFMAN) rv.lossless = MGH_LOSSLESS_HUFFMAN;
+  else if (hd.compressor == fmt::COMP_X_HUFFMAN_ZSTD) rv.lossless = MGH_LOSSLESS_HUFFMAN_ZSTD;
+  else return hl_fail(MGH_ERR_FORMAT, "this lossless compressor is not supported");
+  if (hd.hierarchy != fmt::HIER_MULTIDIM) return hl_fail(MGH_ERR_FORMAT, "only the multi-dimensional decomposition is supported");
+  return MGH_SUCCESS;
+}
+// ... and the record whose size prefix is at byte `at` of the container; data_bytes: the subdomain as data
+int record_view_at(const void *container, size_t size, size_t at, uint64_t data_bytes, RecordView &rv) {
+  if (size - at < 8) return hl_fail(MGH_ERR_FORMAT, "subdomain record truncated");
+  std::vector<uint8_t> sz;
+  HL_TRY(fetch_host((const char *)container + at, 8, 8, sz));
+  std::memcpy(&rv.csize, sz.data(), 8);
+  if (rv.csize > size - at - 8) return hl_fail(MGH_ERR_FORMAT, "subdomain record truncated");
+  rv.rec = (const uint8_t *)container + at + 8;
+  rv.raw = !((double)data_bytes / (double)rv.csize > 1.0);  // GPUPipelines.hpp:414-417
+  if (rv.raw && rv.csize != data_bytes) return hl_fail(MGH_ERR_FORMAT, "raw subdomain record has the wrong size");
+  return MGH_SUCCESS;
+}
+
+// The coordinates a decoder builds its hierarchies from (get_hierarchy converts them to the data
+// type); nullptr: a uniform grid.
+// The reference rebuilds the coordinates of a non-uniform grid through `(float)` when it
+// decompresses, for double data as well (CompressionHighLevel.hpp:455-462). Mirrored on request
+// only: with it an f64 non-uniform stream reconstructs exactly like stock MGARD-X does, without
+// it the coordinates the compressor used are taken at full precision.
+const std::vector<std::vector<double>> *decoder_coords(const fmt::Header &hd, const mgh_config &cfg,
+                                                       std::vector<std::vector<double>> &mirrored) {
+  if (hd.uniform) return nullptr;
+  if (!cfg.mirror_reference_coord_cast) return &hd.coords;
+  mirrored = hd.coords;
+  for (auto &c : mirrored)
+    for (double &x : c) x = (double)(float)x;
+  return &mirrored;
+}
+
+// The quantization a record was made with (the header's, per subdomain), in the data type's precision.
+struct RecordQuant {
+  int eb;
+  double tol, s, norm;
+  uint64_t dict;
+  bool reorder;
+};
+
+// A record that holds the data itself, below l_target: a coarser level is what a Huffman record of
+// this subdomain would have given -- the integers of the header's bound, made here (no dictionary:
+// prep_huffman = 0) into q, through `data`.
+int raw_record_integers(mgh_hierarchy *h, const RecordView &rv, const RecordQuant &qp, DevBuf &data, DevBuf &q,
+                        uint64_t n, hipStream_t st) {
+  HL_TRY(q.ensure(n * 8));
+  HL_TRY(data.ensure(rv.csize));
+  HL_TRY(copy_any(data.p, rv.rec, rv.csize, st));
+  return mgh_decompose_quantize(h, data.p, qp.eb, qp.tol, qp.s, qp.norm, nullptr, qp.dict, 0, (int64_t *)q.p, nullptr,
+                                nullptr, nullptr, 0, nullptr, st);
+}
+
+// A Huffman record of n integers to the dense subdomain at `dst`, queued on st: the whole array
+// (level < 0), the dense array of `level`, or -- linear_head -- that array from the first n_head
+// integers of a reorder = 1 record alone (q holds q_cap).
+int reconstruct_record(mgh_hierarchy *h, mgh_lossless_ctx *ll, DevBuf &q, DevBuf &q2, const RecordQuant &qp,
+                       const RecordView &rv, uint64_t n, int level, bool linear_head, uint64_t n_head, uint64_t q_cap,
+                       void *dst, hipStream_t st) {
+  uint64_t ocount = 0;
+  // 16-bit symbols between decoder and dequantizer (a quarter of the bytes the decoder writes and
+  // the two passes over the finest level read). The symbol width is chosen PER LEVEL inside
+  // mgh_dequantize_recompose_sym16: the finest level reads the symbols, the levels below --
+  // where the out-of-dictionary values live -- an int64 copy of the coarse corner box.
+  // Subdomains below 2^25 elements keep int64: the box copy and the outlier table are three more
+  // launches in a latency-bound chain (256^3: 0.86 ms with int64, 0.89 ms with symbols; 512^3: 2.16
+  // vs 2.03 ms). MGH_SYM16_DECODE=0 / 1: never / always (cross-checks).
+  static const long sym16_env = env_get("MGH_SYM16_DECODE", -1);
+  const bool sym16_decode = sym16_env < 0 ? n >= ((uint64_t)1 << 25) : sym16_env != 0;
+  bool sym16 = sym16_decode && !qp.reorder && mgh_sym16_supported(h) && qp.dict <= 65536;
+  int64_t *src = (int64_t *)q.p;
+  if (linear_head) {
+    if (level >= mgh_l_target(h)) return hl_fail(MGH_ERR_FORMAT, "header: the hierarchy of the subdomain is not the header's");
+    HL_TRY(lossless_decompress(ll, rv.rec, rv.csize, rv.lossless, src, n, &ocount, st, nullptr, /*sync_end=*/false,
+                               /*n_prefix=*/n_head, /*q_cap=*/q_cap));
+    return mgh_dequantize_recompose_linear_to_level(h, src, qp.eb, qp.tol, qp.s, qp.norm, qp.dict, 1,
+                                                    (const uint64_t *)ll->oidx.p, (const int64_t *)ll->oval.p, ocount,
+                                                    level, dst, st);
+  }
+  HL_TRY(lossless_decompress(ll, rv.rec, rv.csize, rv.lossless, src, n, &ocount, st, &sym16, /*sync_end=*/false));
+  const uint64_t *oidx = (const uint64_t *)ll->oidx.p;
+  const int64_t *oval = (const int64_t *)ll->oval.p;
+  if (sym16 && level >= 0)
+    return mgh_dequantize_recompose_sym16_to_level(h, (const uint16_t *)q.p, qp.eb, qp.tol, qp.s, qp.norm, qp.dict, oidx,
+                                                   oval, ocount, level, dst, st);
+  if (sym16)
+    return mgh_dequantize_recompose_sym16(h, (const uint16_t *)q.p, qp.eb, qp.tol, qp.s, qp.norm, qp.dict, oidx, oval,
+                                          ocount, dst, st);
+  if (qp.reorder) {
+    // level-linearised integers: outliers back at their linearised positions, the
+    // permutation undone, then the ordinary path with nothing left to restore
+    HL_TRY(mgh_outlier_restore(src, n, oidx, oval, ocount, st));
+    HL_TRY(mgh_level_linearize(h, src, (int64_t *)q2.p, 1, nullptr, nullptr, 0, 0, st));
+    src = (int64_t *)q2.p;
+    oidx = nullptr;
+    oval = nullptr;
+    ocount = 0;
+  }
+  if (level >= 0)
+    return mgh_dequantize_recompose_to_level(h, src, qp.eb, qp.tol, qp.s, qp.norm, qp.dict, 1, oidx, oval, ocount, level,
+                                             dst, st);
+  return mgh_dequantize_recompose(h, src, qp.eb, qp.tol, qp.s, qp.norm, qp.dict, 1, oidx, oval, ocount, dst, st);
+}
+
 // level >= 0: mgh_decompress_level -- the output is the dense array of that level of the hierarchy
 template <typename T>
 int decompress_impl(const fmt::Header &hd, size_t meta_size, const void *compressed, size_t csize_total,
@@ -2655,11 +2772,8 @@ int decompress_impl(const fmt::Header &hd, size_t meta_size, const void *compres
   for (uint64_t id = 0; id < dd.num; id++)
     for (uint64_t e : dd.subdomain_shape(id))
       if (e < 3) return hl_fail(MGH_ERR_FORMAT, "header: subdomain with fewer than 3 nodes");
-  int lossless;
-  if (hd.compressor == fmt::COMP_X_HUFFMAN) lossless = MGH_LOSSLESS_HUFFMAN;
-  else if (hd.compressor == fmt::COMP_X_HUFFMAN_ZSTD) lossless = MGH_LOSSLESS_HUFFMAN_ZSTD;
-  else return hl_fail(MGH_ERR_FORMAT, "this lossless compressor is not supported");
-  if (hd.hierarchy != fmt::HIER_MULTIDIM) return hl_fail(MGH_ERR_FORMAT, "only the multi-dimensional decomposition is supported");
+  RecordView rv_hd;
+  HL_TRY(record_view_header(hd, rv_hd));
   const bool in_dev = is_device_pointer(compressed);
   Pretouch pretouch;  // (joined before the first byte of the output is written, and on every way out)
   if (!prealloc) {
@@ -2732,18 +2846,9 @@ int decompress_impl(const fmt::Header &hd, size_t meta_size, const void *compres
     local_tol = local_abs_tol<T>(local_eb, norm, tol, s, dd.num);
     local_eb = MGH_ABS;
   }
-  const std::vector<std::vector<double>> *cptr = hd.uniform ? nullptr : &hd.coords;
-  // The reference rebuilds the coordinates of a non-uniform grid through `(float)` when it
-  // decompresses, for double data as well (CompressionHighLevel.hpp:455-462). Mirrored on request
-  // only: with it an f64 non-uniform stream reconstructs exactly like stock MGARD-X does, without
-  // it the coordinates the compressor used are taken at full precision.
-  std::vector<std::vector<double>> coords_f32;
-  if (cptr && cfg.mirror_reference_coord_cast) {
-    coords_f32 = hd.coords;
-    for (auto &c : coords_f32)
-      for (double &x : c) x = (double)(float)x;
-    cptr = &coords_f32;
-  }
+  const RecordQuant qp{local_eb, (double)local_tol, (double)s, (double)norm, hd.huff_dict_size, hd.reorder};
+  std::vector<std::vector<double>> mirrored;
+  const std::vector<std::vector<double>> *cptr = decoder_coords(hd, cfg, mirrored);
   // ---- subdomain pipeline (decompress_pipeline_gpu, GPUPipelines.hpp:330-520) ----
   // issue(k): everything of subdomain k up to the reconstructed dense subdomain, queued on lane
   // k % nlanes without a host synchronisation (the decoder of k + 1 runs beside the recomposition
@@ -2760,8 +2865,7 @@ int decompress_impl(const fmt::Header &hd, size_t meta_size, const void *compres
     HL_TRY(lossless_tag_check(L.ll));
     if (owned_h[lane]) mgh_hierarchy_destroy(owned_h[lane]);
     owned_h[lane] = nullptr;
-    if (csize_total - byte_offset < 8) return hl_fail(MGH_ERR_FORMAT, "subdomain record truncated");
-    if (in_dev) {
+    if (in_dev && csize_total - byte_offset >= 8) {
       // ONE device -> host read per subdomain: the size prefix and what the lossless stage will want
       // of the record's head (chunk table for the largest subdomain, decodebook) -- every further
       // read of this subdomain is served from it (dev_to_host). A read is a queued copy plus a
@@ -2779,94 +2883,31 @@ int decompress_impl(const fmt::Header &hd, size_t meta_size, const void *compres
         hp.base = at;
       }
     }
-    std::vector<uint8_t> sz;
-    HL_TRY(fetch_host((const char *)compressed + byte_offset, 8, 8, sz));
-    uint64_t csize = 0;
-    std::memcpy(&csize, sz.data(), 8);
-    byte_offset += 8;
-    if (csize > csize_total - byte_offset) return hl_fail(MGH_ERR_FORMAT, "subdomain record truncated");
     const auto sshape = dd.subdomain_shape(id);
     uint64_t n = 1;
     for (uint64_t e : sshape) n *= e;
-    const char *rec = (const char *)compressed + byte_offset;
+    RecordView rv = rv_hd;
+    HL_TRY(record_view_at(compressed, csize_total, byte_offset, n * elem, rv));
+    byte_offset += 8 + rv.csize;
     void *sub = zero_copy ? (void *)((char *)*out + dd.linear_offset(id) * elem) : L.sub.p;
-    byte_offset += csize;
-    const bool raw = !((double)(n * elem) / (double)csize > 1.0);  // GPUPipelines.hpp:414-417
     decompress_stats().subdomains++;
-    if (raw) {
-      decompress_stats().record_bytes += csize;
-      if (csize != n * elem) return hl_fail(MGH_ERR_FORMAT, "raw subdomain record has the wrong size");
-      if (level < 0) return copy_any(sub, rec, csize, st);
+    if (rv.raw) {
+      decompress_stats().record_bytes += rv.csize;
+      if (level < 0) return copy_any(sub, rv.rec, rv.csize, st);
     }
-    const uint8_t *payload = (const uint8_t *)rec;
-    uint64_t ocount = 0;
     mgh_hierarchy *h = nullptr;
     bool owned = false;
     HL_TRY(get_hierarchy(&h, &owned, dtype, sshape, cptr, dd.subdomain_offset(id), cfg, lane));
     if (owned) owned_h[lane] = h;
     if (level >= 0 && level > mgh_l_target(h)) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "level outside 0 .. l_target");
-    if (raw) {
-      // a record that holds the data itself (the lossless stage did not pay): the finest level is the
-      // data; a coarser one is what a Huffman record of this subdomain would have given -- the
-      // integers of the header's bound, made here (no dictionary: prep_huffman = 0)
-      if (level == mgh_l_target(h)) return copy_any(sub, rec, csize, st);
-      HL_TRY(L.q.ensure(n * 8));  // (the head of a reorder = 1 record is all the lane holds otherwise)
-      HL_TRY(L.q2.ensure(n * elem));
-      HL_TRY(copy_any(L.q2.p, rec, csize, st));
-      HL_TRY(mgh_decompose_quantize(h, L.q2.p, local_eb, (double)local_tol, (double)s, (double)norm, nullptr,
-                                    hd.huff_dict_size, 0, (int64_t *)L.q.p, nullptr, nullptr, nullptr, 0, nullptr, st));
-      return mgh_dequantize_recompose_to_level(h, (int64_t *)L.q.p, local_eb, (double)local_tol, (double)s,
-                                               (double)norm, hd.huff_dict_size, 0, nullptr, nullptr, 0, level, sub, st);
+    if (rv.raw) {  // (the finest level is the data)
+      if (level == mgh_l_target(h)) return copy_any(sub, rv.rec, rv.csize, st);
+      // (q: the head of a reorder = 1 record is all the lane holds otherwise)
+      HL_TRY(raw_record_integers(h, rv, qp, L.q2, L.q, n, st));
+      return mgh_dequantize_recompose_to_level(h, (int64_t *)L.q.p, qp.eb, qp.tol, qp.s, qp.norm, qp.dict, 0, nullptr,
+                                               nullptr, 0, level, sub, st);
     }
-    // 16-bit symbols between decoder and dequantizer (a quarter of the bytes the decoder writes and
-    // the two passes over the finest level read). The symbol width is chosen PER LEVEL inside
-    // mgh_dequantize_recompose_sym16: the finest level reads the symbols, the levels below --
-    // where the out-of-dictionary values live -- an int64 copy of the coarse corner box.
-    // Subdomains below 2^25 elements keep int64: the box copy and the outlier table are three more
-    // launches in a latency-bound chain (256^3: 0.86 ms with int64, 0.89 ms with symbols; 512^3: 2.16
-    // vs 2.03 ms). MGH_SYM16_DECODE=0 / 1: never / always (cross-checks).
-    static const long sym16_env = env_get("MGH_SYM16_DECODE", -1);
-    const bool sym16_decode = sym16_env < 0 ? n >= ((uint64_t)1 << 25) : sym16_env != 0;
-    bool sym16 = sym16_decode && !hd.reorder && mgh_sym16_supported(h) && hd.huff_dict_size <= 65536;
-    if (linear_head) {
-      if (level >= mgh_l_target(h)) return hl_fail(MGH_ERR_FORMAT, "header: the hierarchy of the subdomain is not the header's");
-      HL_TRY(lossless_decompress(L.ll, payload, csize, lossless, (int64_t *)L.q.p, n, &ocount, st, nullptr,
-                                 /*sync_end=*/false, /*n_prefix=*/total, /*q_cap=*/q_elems));
-      return mgh_dequantize_recompose_linear_to_level(h, (int64_t *)L.q.p, local_eb, (double)local_tol, (double)s,
-                                                      (double)norm, hd.huff_dict_size, 1,
-                                                      (const uint64_t *)L.ll->oidx.p, (const int64_t *)L.ll->oval.p,
-                                                      ocount, level, sub, st);
-    }
-    HL_TRY(lossless_decompress(L.ll, payload, csize, lossless, (int64_t *)L.q.p, n, &ocount, st, &sym16,
-                               /*sync_end=*/false));
-    if (sym16 && level >= 0)
-      return mgh_dequantize_recompose_sym16_to_level(h, (const uint16_t *)L.q.p, local_eb, (double)local_tol,
-                                                     (double)s, (double)norm, hd.huff_dict_size,
-                                                     (const uint64_t *)L.ll->oidx.p, (const int64_t *)L.ll->oval.p,
-                                                     ocount, level, sub, st);
-    if (sym16)
-      return mgh_dequantize_recompose_sym16(h, (const uint16_t *)L.q.p, local_eb, (double)local_tol, (double)s,
-                                            (double)norm, hd.huff_dict_size, (const uint64_t *)L.ll->oidx.p,
-                                            (const int64_t *)L.ll->oval.p, ocount, sub, st);
-    if (hd.reorder) {
-      // level-linearised integers: outliers back at their linearised positions, the
-      // permutation undone, then the ordinary path with nothing left to restore
-      HL_TRY(mgh_outlier_restore((int64_t *)L.q.p, n, (const uint64_t *)L.ll->oidx.p,
-                                 (const int64_t *)L.ll->oval.p, ocount, st));
-      HL_TRY(mgh_level_linearize(h, (const int64_t *)L.q.p, (int64_t *)L.q2.p, 1, nullptr, nullptr, 0, 0, st));
-      if (level >= 0)
-        return mgh_dequantize_recompose_to_level(h, (int64_t *)L.q2.p, local_eb, (double)local_tol, (double)s,
-                                                 (double)norm, hd.huff_dict_size, 1, nullptr, nullptr, 0, level, sub, st);
-      return mgh_dequantize_recompose(h, (int64_t *)L.q2.p, local_eb, (double)local_tol, (double)s, (double)norm,
-                                      hd.huff_dict_size, 1, nullptr, nullptr, 0, sub, st);
-    }
-    if (level >= 0)
-      return mgh_dequantize_recompose_to_level(h, (int64_t *)L.q.p, local_eb, (double)local_tol, (double)s,
-                                               (double)norm, hd.huff_dict_size, 1, (const uint64_t *)L.ll->oidx.p,
-                                               (const int64_t *)L.ll->oval.p, ocount, level, sub, st);
-    return mgh_dequantize_recompose(h, (int64_t *)L.q.p, local_eb, (double)local_tol, (double)s, (double)norm,
-                                    hd.huff_dict_size, 1, (const uint64_t *)L.ll->oidx.p,
-                                    (const int64_t *)L.ll->oval.p, ocount, sub, st);
+    return reconstruct_record(h, L.ll, L.q, L.q2, qp, rv, n, level, linear_head, total, q_elems, sub, st);
   };
   auto finish = [&](uint64_t id) -> int {
     if (zero_copy) return MGH_SUCCESS;
@@ -4256,13 +4297,11 @@ int mgh_infer_level_range(const void *data, size_t size, const mgh_config *confi
 struct mgh_progressive {
   fmt::Header hd;
   mgh_config cfg;
-  const uint8_t *rec = nullptr;  // the record inside the caller's container (borrowed)
-  uint64_t csize = 0;
-  bool in_dev = false, raw = false;
-  int lossless = MGH_LOSSLESS_HUFFMAN;
-  int dtype = MGH_FLOAT, eb = MGH_REL;
+  RecordView rv;  // the record inside the caller's container (borrowed)
+  RecordQuant qp{};
+  bool in_dev = false;
+  int dtype = MGH_FLOAT;
   size_t elem = 4;
-  double tol = 0, s = 0, norm = 0;
   uint64_t n = 0, block = 1, nchunk = 0, ocount = 0;
   int L = 0, level = -1;
   std::vector<uint64_t> N;  // N[l] = prod(level_shape(l))
@@ -4299,10 +4338,7 @@ int progressive_open(mgh_progressive *p, const void *data, size_t size) {
   if (hd.shape.empty() || hd.shape.size() > MGH_MAX_DIM) return hl_fail(MGH_ERR_UNSUPPORTED_DIMENSION, "header: dimension");
   if (!hd.quantized) return hl_fail(MGH_ERR_FORMAT, "not a compressed (quantized) stream");
   HL_TRY(header_level_shape(hd, p->cfg, -1, &p->L, nullptr));  // (refuses a decomposed container)
-  if (hd.compressor == fmt::COMP_X_HUFFMAN) p->lossless = MGH_LOSSLESS_HUFFMAN;
-  else if (hd.compressor == fmt::COMP_X_HUFFMAN_ZSTD) p->lossless = MGH_LOSSLESS_HUFFMAN_ZSTD;
-  else return hl_fail(MGH_ERR_FORMAT, "this lossless compressor is not supported");
-  if (hd.hierarchy != fmt::HIER_MULTIDIM) return hl_fail(MGH_ERR_FORMAT, "only the multi-dimensional decomposition is supported");
+  HL_TRY(record_view_header(hd, p->rv));
   if (!hd.reorder)
     return hl_fail(MGH_ERR_INVALID_ARGUMENT,
                    "mgh_progressive_open: a reorder = 1 (level-linearised) container is needed: the levels of a "
@@ -4310,10 +4346,7 @@ int progressive_open(mgh_progressive *p, const void *data, size_t size) {
   p->dtype = hd.is_double ? MGH_DOUBLE : MGH_FLOAT;
   p->elem = hd.is_double ? 8 : 4;
   auto in_type = [&](double v) { return hd.is_double ? v : (double)(float)v; };
-  p->tol = in_type(hd.tol);
-  p->s = in_type(hd.s);
-  p->norm = in_type(hd.norm);
-  p->eb = hd.rel ? MGH_REL : MGH_ABS;
+  p->qp = RecordQuant{hd.rel ? MGH_REL : MGH_ABS, in_type(hd.tol), in_type(hd.s), in_type(hd.norm), hd.huff_dict_size, true};
   p->block = std::max<uint64_t>(hd.huff_block_size, 1);
   p->N.resize(p->L + 1);
   for (int l = 0; l <= p->L; l++) {
@@ -4323,50 +4356,21 @@ int progressive_open(mgh_progressive *p, const void *data, size_t size) {
     for (uint64_t e : shp) p->N[l] *= e;
   }
   p->n = p->N[p->L];
-  // the one record
-  if (size - meta_size < 8) return hl_fail(MGH_ERR_FORMAT, "subdomain record truncated");
-  std::vector<uint8_t> sz;
-  HL_TRY(fetch_host((const char *)data + meta_size, 8, 8, sz));
-  std::memcpy(&p->csize, sz.data(), 8);
-  if (p->csize > size - meta_size - 8) return hl_fail(MGH_ERR_FORMAT, "subdomain record truncated");
-  p->rec = (const uint8_t *)data + meta_size + 8;
-  p->raw = !((double)(p->n * p->elem) / (double)p->csize > 1.0);
-  if (p->raw && p->csize != p->n * p->elem) return hl_fail(MGH_ERR_FORMAT, "raw subdomain record has the wrong size");
+  HL_TRY(record_view_at(data, size, meta_size, p->n * p->elem, p->rv));  // the one record
   // hierarchy of the array (its own: it holds the state of the level loop between the calls)
-  {
-    const int D = (int)hd.shape.size();
-    std::vector<std::vector<float>> cf(D);
-    std::vector<std::vector<double>> cd(D);
-    const void *ptrs[MGH_MAX_DIM];
-    if (!hd.uniform)
-      for (int d = 0; d < D; d++) {
-        cd[d] = hd.coords[d];
-        if (p->cfg.mirror_reference_coord_cast)
-          for (double &x : cd[d]) x = (double)(float)x;
-        if (!hd.is_double) {
-          cf[d].assign(cd[d].begin(), cd[d].end());
-          ptrs[d] = cf[d].data();
-        } else {
-          ptrs[d] = cd[d].data();
-        }
-      }
-    HL_TRY(mgh_hierarchy_create(&p->h, D, hd.shape.data(), p->dtype, hd.uniform ? nullptr : ptrs,
-                                p->cfg.normalize_coordinates, p->cfg.max_larget_level, p->cfg.dev_id));
-    if (mgh_l_target(p->h) != p->L) return hl_fail(MGH_ERR_FORMAT, "header: the hierarchy of the subdomain is not the header's");
-  }
+  std::vector<std::vector<double>> mirrored;
+  bool owned = true;
+  HL_TRY(get_hierarchy(&p->h, &owned, p->dtype, hd.shape, decoder_coords(hd, p->cfg, mirrored),
+                       std::vector<uint64_t>(hd.shape.size(), 0), p->cfg, 0, /*cached=*/false));
+  if (mgh_l_target(p->h) != p->L) return hl_fail(MGH_ERR_FORMAT, "header: the hierarchy of the subdomain is not the header's");
   HL_HIP(hipStreamCreate(&p->st));
-  if (p->raw) {
-    // the integers a Huffman record of this array would have held (no dictionary), level-linearised:
-    // the route of mgh_decompress_level, once
+  if (p->rv.raw) {
+    // the integers a Huffman record of this array would have held, level-linearised: the route of
+    // mgh_decompress_level, once
     if (p->L == 0) return MGH_SUCCESS;
     DevBuf data_in, qfull;
-    HL_TRY(data_in.ensure(p->csize));
-    HL_TRY(qfull.ensure(p->n * 8));
-    HL_TRY(p->lin.ensure(p->n * 8));
-    int rc = copy_any(data_in.p, p->rec, p->csize, p->st);
-    if (rc == MGH_SUCCESS)
-      rc = mgh_decompose_quantize(p->h, data_in.p, p->eb, p->tol, p->s, p->norm, nullptr, hd.huff_dict_size, 0,
-                                  (int64_t *)qfull.p, nullptr, nullptr, nullptr, 0, nullptr, p->st);
+    int rc = p->lin.ensure(p->n * 8);
+    if (rc == MGH_SUCCESS) rc = raw_record_integers(p->h, p->rv, p->qp, data_in, qfull, p->n, p->st);
     if (rc == MGH_SUCCESS)
       rc = mgh_level_linearize(p->h, (const int64_t *)qfull.p, (int64_t *)p->lin.p, 0, nullptr, nullptr, 0, 0, p->st);
     (void)hipStreamSynchronize(p->st);
@@ -4379,7 +4383,7 @@ int progressive_open(mgh_progressive *p, const void *data, size_t size) {
   HL_TRY(mgh_lossless_create(&p->ll, p->cfg.dev_id));
   p->ll->keep = 1;
   decompress_stats() = mgh_decompress_stats{};
-  HL_TRY(lossless_decompress(p->ll, p->rec, p->csize, p->lossless, nullptr, p->n, &p->ocount, p->st, nullptr,
+  HL_TRY(lossless_decompress(p->ll, p->rv.rec, p->rv.csize, p->rv.lossless, nullptr, p->n, &p->ocount, p->st, nullptr,
                              /*sync_end=*/true, /*n_prefix=*/0));
   p->nchunk = decompress_stats().chunks_total;
   return MGH_SUCCESS;
@@ -4395,15 +4399,15 @@ int progressive_refine(mgh_progressive *p, int to, void **out, bool prealloc) {
   const uint64_t dict = hd.huff_dict_size;
   const size_t out_bytes = p->N[to] * p->elem;
   int at = p->si;
-  const bool raw_full = p->raw && to == p->L;  // (a raw record IS the finest level)
-  if (raw_full) stats.record_bytes = p->csize;
+  const bool raw_full = p->rv.raw && to == p->L;  // (a raw record IS the finest level)
+  if (raw_full) stats.record_bytes = p->rv.csize;
   if (!raw_full) {
     const int64_t *base = nullptr;  // integer `first` of the array
     uint64_t first = 0;
     const uint64_t *oidx = nullptr;
     const int64_t *oval = nullptr;
-    if (p->raw) {
-      stats.record_bytes = p->csize;
+    if (p->rv.raw) {
+      stats.record_bytes = p->rv.csize;
       base = (const int64_t *)p->lin.p;
     } else {
       // the integers [N_from, N_to): what is left of the boundary chunk, and the chunks not decoded yet
@@ -4415,12 +4419,12 @@ int progressive_refine(mgh_progressive *p, int to, void **out, bool prealloc) {
       if (carry)
         HL_HIP(hipMemcpyAsync(qn.p, (const int64_t *)p->q[p->qi].p + (lo - p->q_first), carry * 8, hipMemcpyDeviceToDevice, st));
       if (new_end > p->dec_end) {
-        HL_TRY(lossless_decompress(p->ll, p->rec, p->csize, p->lossless, (int64_t *)qn.p + carry, p->n, &p->ocount, st,
+        HL_TRY(lossless_decompress(p->ll, p->rv.rec, p->rv.csize, p->rv.lossless, (int64_t *)qn.p + carry, p->n, &p->ocount, st,
                                    nullptr, /*sync_end=*/false, /*n_prefix=*/new_end, /*q_cap=*/new_end - p->dec_end,
                                    /*first=*/p->dec_end));
       } else {  // (everything this refine reads was decoded with the boundary chunk of an earlier one)
         stats.chunks_total = p->nchunk;
-        stats.record_bytes = p->csize;
+        stats.record_bytes = p->rv.csize;
       }
       p->qi ^= 1;
       p->q_first = lo;
@@ -4430,18 +4434,18 @@ int progressive_refine(mgh_progressive *p, int to, void **out, bool prealloc) {
       oidx = (const uint64_t *)p->ll->oidx.p;
       oval = (const int64_t *)p->ll->oval.p;
     }
-    const int prep = p->raw ? 0 : 1;
-    const uint64_t ocount = p->raw ? 0 : p->ocount;
+    const int prep = p->rv.raw ? 0 : 1;
+    const uint64_t ocount = p->rv.raw ? 0 : p->ocount;
     int l = from;
     if (from < 0) {
       HL_TRY(p->state[at].ensure(out_bytes));
-      HL_TRY(mgh_dequantize_recompose_linear_to_level(p->h, (int64_t *)base, p->eb, p->tol, p->s, p->norm, dict, prep, oidx,
+      HL_TRY(mgh_dequantize_recompose_linear_to_level(p->h, (int64_t *)base, p->qp.eb, p->qp.tol, p->qp.s, p->qp.norm, dict, prep, oidx,
                                                       oval, ocount, to, p->state[at].p, st));
       l = to;
     }
     for (l = l + 1; l <= to; l++) {
       HL_TRY(p->state[at ^ 1].ensure(p->N[l] * p->elem));
-      HL_TRY(mgh_refine_level(p->h, p->state[at].p, (int64_t *)base + (p->N[l - 1] - first), p->eb, p->tol, p->s, p->norm,
+      HL_TRY(mgh_refine_level(p->h, p->state[at].p, (int64_t *)base + (p->N[l - 1] - first), p->qp.eb, p->qp.tol, p->qp.s, p->qp.norm,
                               dict, prep, oidx, oval, ocount, l, p->state[at ^ 1].p, st));
       at ^= 1;
     }
@@ -4451,7 +4455,7 @@ int progressive_refine(mgh_progressive *p, int to, void **out, bool prealloc) {
     if (p->in_dev) HL_HIP(hipMalloc(out, out_bytes));
     else if (!(*out = host_alloc_large(out_bytes))) return hl_fail(MGH_ERR_OUT_OF_MEMORY, "malloc");
   }
-  int rc = raw_full ? copy_any(*out, p->rec, out_bytes, st) : copy_any(*out, p->state[at].p, out_bytes, st);
+  int rc = raw_full ? copy_any(*out, p->rv.rec, out_bytes, st) : copy_any(*out, p->state[at].p, out_bytes, st);
   if (rc == MGH_SUCCESS && hipStreamSynchronize(st) != hipSuccess) rc = hl_fail(MGH_ERR_DEVICE, "sync");
   if (rc == MGH_SUCCESS && p->ll) rc = lossless_tag_check(p->ll);
   if (rc != MGH_SUCCESS && !prealloc) {

@@ -101,6 +101,57 @@ def test_refine_level_under_developer_switches(monkeypatch, env):
     _refine_chain(Setup(((33, 40, 65), np.float32, dict(s=0.0), "")), mg.REL, 64)
 
 
+@pytest.mark.parametrize("shape", [(65, 70, 129), (9, 8, 10, 17), (5000, 5, 7)], ids=lambda s: "x".join(map(str, s)))
+def test_entry_points_interleaved_on_one_handle(shape):
+    """Every reconstruction entry shares the handle's compact boxes (qbox, level_box), nodal buffers and the
+    helper that grows them: one call of each kind in turn on ONE handle -- the boxes asked for shrink, then
+    grow; the second round starts with every buffer at its largest -- gives what the same call gives on a
+    fresh handle, bit for bit. (65 x 70 x 129: fused 3-D, mixed symbol widths, a stop on the widened box
+    alone; 9 x 8 x 10 x 17: the N-D kernels in place; 5000 x 5 x 7: the one-thread-per-element kernels on a
+    compact box.)"""
+    import torch
+    import mgard_amd as mg
+    dt, dict_size, tol, s = np.float32, 64, 1e-3, float("inf")
+    u = smooth_field(shape, dt, seed=int(np.prod(shape)) % 100003, noise=1e-2)
+    norm = float(dt(oracle.norm(u, s, True)))
+    du = torch.from_numpy(u).cuda()
+    prep = mg.Hierarchy(shape, dt)
+    L = prep.l_target
+    assert L >= 2
+    q, oi, ov, n, _ = prep.decompose_quantize(du, mg.REL, tol, s, norm, dict_size=dict_size)
+    assert n > 0
+    coef = prep.decompose(du)
+    oi_lin = oi.clone()
+    lin = prep.level_linearize(q, outlier_idx=oi_lin).reshape(-1)
+    N = [_n(prep.level_shape(l)) for l in range(L + 1)]
+    kw = dict(dict_size=dict_size, outlier_idx=oi, outlier_val=ov)
+    kwl = dict(dict_size=dict_size, outlier_idx=oi_lin, outlier_val=ov)
+    a = (mg.REL, tol, s, norm)
+    level1 = prep.dequantize_recompose_linear(lin[:N[1]].clone(), *a, level=1, **kwl)
+    calls = [
+        ("dequantize_recompose(level=L-1)", lambda h: h.dequantize_recompose(q.clone(), *a, level=L - 1, **kw)),
+        ("linear(level=1)", lambda h: h.dequantize_recompose_linear(lin[:N[1]].clone(), *a, level=1, **kwl)),
+        ("refine_level(2)", lambda h: h.refine_level(level1, lin[N[1]:N[2]].clone(), *a, 2, **kwl)),
+    ]
+    if prep.sym16_supported():
+        sym, oi16, ov16, _, _ = prep.decompose_quantize_sym16(du, mg.REL, tol, s, norm, dict_size=dict_size)
+        kw16 = dict(dict_size=dict_size, outlier_idx=oi16, outlier_val=ov16)
+        calls += [("sym16(level=L-3)", lambda h: h.dequantize_recompose_sym16(sym, *a, level=max(L - 3, 0), **kw16)),
+                  ("sym16()", lambda h: h.dequantize_recompose_sym16(sym, *a, **kw16))]
+    else:
+        assert shape != (65, 70, 129)
+    calls += [
+        ("recompose(level=0)", lambda h: h.recompose(coef, level=0)),
+        ("dequantize_recompose()", lambda h: h.dequantize_recompose(q.clone(), *a, **kw)),
+        ("linear(level=L)", lambda h: h.dequantize_recompose_linear(lin.clone(), *a, level=L, **kwl)),
+    ]
+    want = [_cpu(call(mg.Hierarchy(shape, dt))) for _, call in calls]
+    shared = mg.Hierarchy(shape, dt)
+    for round_ in (1, 2):
+        for (name, call), w in zip(calls, want):
+            assert_bit_equal(_cpu(call(shared)), w, "%s on the shared handle, round %d" % (name, round_))
+
+
 # ---- the lossless stage: decode a chunk range ------------------------------------------------------
 def test_lossless_decompress_range():
     import torch
