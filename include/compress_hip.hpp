@@ -149,6 +149,48 @@ inline compress_status_type infer_level_shape(const void *compressed_data, size_
   if (level >= 0) shape.assign(shp, shp + D);
   return compress_status_type::Success;
 }
+// EXTENSION: reduced resolution of any container, domain-decomposed ones included. `halvings` counts
+// coarsenings of the grid (n -> n/2 + 1), the same in every subdomain; the result is the subdomains'
+// level arrays stitched into one dense array of the shape infer_coarsened_shape gives
+// (mgh_decompress_coarsened).
+inline compress_status_type decompress_coarsened(const void *compressed_data, size_t compressed_size, int halvings,
+                                                 void *&decompressed_data, HighLevelConfig config,
+                                                 bool output_pre_allocated) {
+  const mgh_config c = detail::to_c(config);
+  return detail::status(mgh_decompress_coarsened(compressed_data, compressed_size, halvings, &decompressed_data, &c,
+                                                 output_pre_allocated ? 1 : 0));
+}
+// shape of the stitched array and the largest number of halvings; halvings < 0: only the latter
+// (shape left empty)
+inline compress_status_type infer_coarsened_shape(const void *compressed_data, size_t compressed_size, int halvings,
+                                                  HighLevelConfig config, std::vector<SIZE> &shape,
+                                                  int &max_halvings) {
+  const mgh_config c = detail::to_c(config);
+  int D = 0, K = 0;
+  uint64_t shp[MGH_MAX_DIM];
+  shape.clear();
+  const int rc = mgh_infer_coarsened_shape(compressed_data, compressed_size, &c, halvings, &D, shp, &K);
+  if (rc != MGH_SUCCESS) return detail::status(rc);
+  max_halvings = K;
+  if (halvings >= 0) shape.assign(shp, shp + D);
+  return compress_status_type::Success;
+}
+// index in the full array of every node of the stitched grid along `dim` (mgh_infer_coarsened_nodes)
+inline compress_status_type infer_coarsened_nodes(const void *compressed_data, size_t compressed_size, int halvings,
+                                                  int dim, HighLevelConfig config, std::vector<SIZE> &nodes) {
+  const mgh_config c = detail::to_c(config);
+  int D = 0;
+  uint64_t shp[MGH_MAX_DIM];
+  nodes.clear();
+  int rc = mgh_infer_shape(compressed_data, compressed_size, &D, shp);
+  if (rc != MGH_SUCCESS) return detail::status(rc);
+  if (halvings < 0 || dim < 0 || dim >= D) return compress_status_type::Failure;
+  std::vector<uint64_t> idx(shp[dim]);
+  rc = mgh_infer_coarsened_nodes(compressed_data, compressed_size, &c, halvings, dim, idx.data(), idx.size());
+  if (rc < 0) return detail::status(rc);
+  nodes.assign(idx.begin(), idx.begin() + rc);
+  return compress_status_type::Success;
+}
 // where the coefficients of `level` lie in a reorder = 1 record (mgh_infer_level_range)
 inline compress_status_type infer_level_range(const void *compressed_data, size_t compressed_size, int level,
                                               HighLevelConfig config, SIZE &first_elem, SIZE &num_elems,

@@ -264,6 +264,51 @@ inline enum compress_status_type decompress_level(const void *compressed_data, s
   return detail::status(mgh_decompress_level(compressed_data, compressed_size, level, &decompressed_data, &c,
                                              output_pre_allocated ? 1 : 0));
 }
+// EXTENSION: reduced resolution of any container, domain-decomposed ones included. `halvings` counts
+// coarsenings of the grid (n -> n/2 + 1), the same in every subdomain; the result is the subdomains'
+// level arrays stitched into one dense array of the shape infer_coarsened_shape gives.
+inline enum compress_status_type decompress_coarsened(const void *compressed_data, size_t compressed_size,
+                                                      int halvings, void *&decompressed_data, Config config,
+                                                      bool output_pre_allocated) {
+  const compress_status_type ok = detail::check(config);
+  if (ok != compress_status_type::Success) return ok;
+  const mgh_config c = detail::to_c(config);
+  return detail::status(mgh_decompress_coarsened(compressed_data, compressed_size, halvings, &decompressed_data, &c,
+                                                 output_pre_allocated ? 1 : 0));
+}
+// shape of the stitched array and the largest number of halvings; halvings < 0: only the latter
+// (shape left empty)
+inline enum compress_status_type infer_coarsened_shape(const void *compressed_data, size_t compressed_size,
+                                                       int halvings, Config config, std::vector<SIZE> &shape,
+                                                       int &max_halvings) {
+  const mgh_config c = detail::to_c(config);
+  int D = 0, K = 0;
+  uint64_t shp[MGH_MAX_DIM];
+  shape.clear();
+  const int rc = mgh_infer_coarsened_shape(compressed_data, compressed_size, &c, halvings, &D, shp, &K);
+  if (rc != MGH_SUCCESS) return detail::status(rc);
+  max_halvings = K;
+  if (halvings >= 0) shape.assign(shp, shp + D);
+  return compress_status_type::Success;
+}
+// index in the full array of every node of the stitched grid along `dim`: the coordinates of the
+// coarse grid are the full grid's at these indices
+inline enum compress_status_type infer_coarsened_nodes(const void *compressed_data, size_t compressed_size,
+                                                       int halvings, int dim, Config config,
+                                                       std::vector<SIZE> &nodes) {
+  const mgh_config c = detail::to_c(config);
+  int D = 0;
+  uint64_t shp[MGH_MAX_DIM];
+  nodes.clear();
+  int rc = mgh_infer_shape(compressed_data, compressed_size, &D, shp);
+  if (rc != MGH_SUCCESS) return detail::status(rc);
+  if (halvings < 0 || dim < 0 || dim >= D) return compress_status_type::Failure;
+  std::vector<uint64_t> idx(shp[dim]);
+  rc = mgh_infer_coarsened_nodes(compressed_data, compressed_size, &c, halvings, dim, idx.data(), idx.size());
+  if (rc < 0) return detail::status(rc);
+  nodes.assign(idx.begin(), idx.begin() + rc);
+  return compress_status_type::Success;
+}
 inline enum compress_status_type decompress(const void *compressed_data, size_t compressed_size,
                                             void *&decompressed_data, bool output_pre_allocated) {
   return decompress(compressed_data, compressed_size, decompressed_data, Config(), output_pre_allocated);

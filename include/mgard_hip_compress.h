@@ -165,7 +165,9 @@ int mgh_infer_data_type(const void *compressed_data, size_t compressed_size, int
  * Levels are the hierarchy's: 0 = coarsest grid, l_target = the full array. `config` carries
  * max_larget_level as it does for mgh_decompress (the container does not record it; NULL =
  * defaults). Containers with ONE subdomain only: a domain-decomposed container answers
- * MGH_ERR_INVALID_ARGUMENT (every subdomain has its own hierarchy and l_target).
+ * MGH_ERR_INVALID_ARGUMENT (every subdomain has its own hierarchy and l_target); for those, see
+ * mgh_infer_coarsened_shape / mgh_infer_coarsened_nodes / mgh_decompress_coarsened below, which count
+ * halvings of the grid instead of levels.
  *
  * mgh_infer_level_shape: shape of `level` and l_target of the container's hierarchy; level < 0:
  * only l_target (D_out / shape_out untouched). mgh_infer_level_nodes: index in the finest grid of
@@ -192,6 +194,45 @@ int mgh_infer_level_nodes(const void *compressed_data, size_t compressed_size, c
                           int level, int dim, uint64_t *h_idx_out, uint64_t cap);
 int mgh_decompress_level(const void *compressed_data, size_t compressed_size, int level,
                          void **decompressed_data, const mgh_config *config, int output_pre_allocated);
+
+/* ---- Reduced resolution of ANY container, domain-decomposed ones included (EXTENSION) ---------------
+ * `level` counts from the coarsest grid, and every subdomain has its own hierarchy and l_target, so
+ * one level number means a different resolution in each subdomain. The number that means the same in
+ * all of them is how often the grid has been halved: halvings = k >= 0. One halving turns an extent
+ * n into n / 2 + 1 (keep every second node and always the last one -- the hierarchy's own rule).
+ *
+ * Subdomain i (shape and offset as mgh_decompress sees them; a Variable decomposition takes its sizes
+ * from `config`) has l_target_i = the l_target of a hierarchy of its shape under
+ * config->max_larget_level. K = min_i l_target_i is the largest k; k > K answers
+ * MGH_ERR_INVALID_ARGUMENT (no subdomain is clamped: a block with fewer halvings than its neighbours
+ * would break the tensor-product grid). Subdomain i is reconstructed at level l_target_i - k, bit for bit
+ * what mgh_dequantize_recompose[_linear|_sym16]_to_level gives for it alone with the quantization
+ * mgh_decompress uses for it, and the level arrays are stitched in decomposition-grid order into ONE
+ * dense array: along dimension d the block at grid position j has the extent of n_{j,d} after k
+ * halvings, its offset is the sum of the extents before it, the stitched extent the sum of all.
+ * k = 0 returns the bytes of mgh_decompress; on a container with one subdomain k returns the bytes of
+ * mgh_decompress_level(l_target - k).
+ *
+ * mgh_infer_coarsened_shape: shape of the stitched array and K; halvings < 0: only K (D_out /
+ * shape_out untouched). mgh_infer_coarsened_nodes: index in the FULL array of every node of the
+ * stitched grid along `dim`, ascending -- per block, its offset in the full array plus the nodes its
+ * k halvings keep. The stitched grid is NOT uniform even for a uniform array (between two blocks the
+ * step is one fine spacing), so coordinates of the result are always read through this list. Returns
+ * the number of nodes, or K for halvings < 0, or a negative status. compressed_data: host or device;
+ * with a host buffer neither call needs a device.
+ *
+ * mgh_decompress_coarsened: memory-space rules of mgh_decompress_level. A reorder = 1 container with
+ * k > 0 decodes only the head of every record (mgh_last_decompress_stats accumulates over the
+ * subdomains); a reorder = 0 container decodes every record whole; a RAW record costs, for k > 0, a
+ * decomposition and quantization with the subdomain's bound first. A device output whose blocks are
+ * whole slabs of dimension 0 is written in place. */
+int mgh_infer_coarsened_shape(const void *compressed_data, size_t compressed_size, const mgh_config *config,
+                              int halvings, int *D_out, uint64_t *shape_out /* [MGH_MAX_DIM] */,
+                              int *max_halvings_out);
+int mgh_infer_coarsened_nodes(const void *compressed_data, size_t compressed_size, const mgh_config *config,
+                              int halvings, int dim, uint64_t *h_idx_out, uint64_t cap);
+int mgh_decompress_coarsened(const void *compressed_data, size_t compressed_size, int halvings,
+                             void **decompressed_data, const mgh_config *config, int output_pre_allocated);
 
 /* What the last mgh_decompress* call of the calling thread did in its lossless stage (thread-local;
  * zeros before the first call; a failed call leaves what it had counted). Raw records count in

@@ -1241,6 +1241,7 @@ struct Decomposer {
 
   std::vector<uint64_t> dim_num_subdomain() const {  // DomainDecomposer.hpp:90-103
     std::vector<uint64_t> r(D, 1);
+    if (!decomposed) return r;
     if (method == MGH_DD_MAXDIM || method == MGH_DD_VARIABLE) r[dim] = num;
     else for (int d = 0; d < D; d++) r[d] = (shape[d] - 1) / size + 1;
     return r;
@@ -1814,11 +1815,18 @@ k_copy_box(W *__restrict__ dense, W *__restrict__ full, BoxCopy B, int to_dense)
 // full array (host or device). Device to device on one GPU: ONE kernel launch. Otherwise as few
 // strided copies as the box allows -- one hipMemcpy3DAsync per 3-D sub-box (round 5; a 2-D copy per
 // r-plane was 129 calls of ~5 us for a 129^3 block, more than the block's compression).
-int copy_subdomain(const Decomposer &dd, uint64_t id, size_t elem, void *sub, const void *full_c,
-                   void *full_m, bool to_sub, hipStream_t st) {
+// copy_box is the general form: a dense buffer of extents `ext` <-> the box at offset `off` of a
+// dense array of shape `shape` (a subdomain in the full array; a level array of a subdomain in the
+// stitched array of mgh_decompress_coarsened).
+int copy_box(const std::vector<uint64_t> &ext, const std::vector<uint64_t> &off, const std::vector<uint64_t> &shape,
+             size_t elem, void *sub, const void *full_c, void *full_m, bool to_sub, hipStream_t st) {
   hl_debug(to_sub ? "copy_subdomain: to subdomain" : "copy_subdomain: to original");
-  const int D = dd.D;
-  const auto ext = dd.subdomain_shape(id), off = dd.subdomain_offset(id);
+  const int D = (int)shape.size();
+  if ((int)ext.size() != D || (int)off.size() != D || D < 1 || D > MGH_MAX_DIM)
+    return hl_fail(MGH_ERR_INVALID_ARGUMENT, "copy_box: dimension");
+  for (int d = 0; d < D; d++)
+    if (ext[d] == 0 || off[d] > shape[d] || ext[d] > shape[d] - off[d])
+      return hl_fail(MGH_ERR_INVALID_ARGUMENT, "copy_box: the box leaves the array");
   {
     int dev = 0;
     (void)hipGetDevice(&dev);
@@ -1829,7 +1837,7 @@ int copy_subdomain(const Decomposer &dd, uint64_t id, size_t elem, void *sub, co
       std::vector<uint64_t> fstr(D);
       for (int d = D - 1; d >= 0; d--) {
         fstr[d] = fs;
-        fs *= dd.shape[d];
+        fs *= shape[d];
       }
       B.rows = 1;
       for (int k = 0; k < MGH_MAX_DIM; k++) {
@@ -1851,12 +1859,12 @@ int copy_subdomain(const Decomposer &dd, uint64_t id, size_t elem, void *sub, co
   }
   // merge trailing dimensions the box spans completely
   int k = D - 1;
-  while (k > 0 && ext[k] == dd.shape[k]) k--;
+  while (k > 0 && ext[k] == shape[k]) k--;
   // width = ext[k] * prod(shape[k+1:]) contiguous elements; rows along dim k-1
   size_t inner = 1;
-  for (int d = k + 1; d < D; d++) inner *= dd.shape[d];
+  for (int d = k + 1; d < D; d++) inner *= shape[d];
   const size_t width = ext[k] * inner * elem;        // bytes per contiguous run
-  const size_t full_pitch = dd.shape[k] * inner * elem;  // distance between runs (dim k-1)
+  const size_t full_pitch = shape[k] * inner * elem;  // distance between runs (dim k-1)
   const size_t rows = k >= 1 ? ext[k - 1] : 1;
   // outer dims 0 .. k-2
   std::vector<uint64_t> idx(std::max(k - 1, 0), 0);
@@ -1865,7 +1873,7 @@ int copy_subdomain(const Decomposer &dd, uint64_t id, size_t elem, void *sub, co
     size_t s = 1;
     for (int d = D - 1; d >= 0; d--) {
       fstride[d] = s;
-      s *= dd.shape[d];
+      s *= shape[d];
     }
   }
   if (k == 0) {  // one contiguous run
@@ -1891,7 +1899,7 @@ int copy_subdomain(const Decomposer &dd, uint64_t id, size_t elem, void *sub, co
       hipMemcpy3DParms pr{};
       // (pitched pointers: pitch in bytes, then the allocation's width in bytes and height in rows)
       const hipPitchedPtr dense = make_hipPitchedPtr(sp, width, width, rows);
-      const hipPitchedPtr whole = make_hipPitchedPtr(fp, full_pitch, full_pitch, dd.shape[k - 1]);
+      const hipPitchedPtr whole = make_hipPitchedPtr(fp, full_pitch, full_pitch, shape[k - 1]);
       pr.srcPtr = to_sub ? whole : dense;
       pr.dstPtr = to_sub ? dense : whole;
       pr.extent = make_hipExtent(width, rows, depth);
@@ -1912,6 +1920,11 @@ int copy_subdomain(const Decomposer &dd, uint64_t id, size_t elem, void *sub, co
     if (d < 0) break;
   }
   return MGH_SUCCESS;
+}
+
+int copy_subdomain(const Decomposer &dd, uint64_t id, size_t elem, void *sub, const void *full_c,
+                   void *full_m, bool to_sub, hipStream_t st) {
+  return copy_box(dd.subdomain_shape(id), dd.subdomain_offset(id), dd.shape, elem, sub, full_c, full_m, to_sub, st);
 }
 
 // ---- per-thread cache: hierarchies, device buffers, lossless context
@@ -2634,6 +2647,60 @@ int header_level_shape(const fmt::Header &hd, const mgh_config &cfg, int level, 
   return MGH_SUCCESS;
 }
 
+// ---- a decomposed container after `halvings` coarsenings of every subdomain (host only) -------------
+// Every subdomain has its own hierarchy and l_target, so a level number means a different resolution in
+// each; the number of halvings (n -> n/2 + 1, the hierarchy's rule) means the same in all of them.
+// Subdomain i is taken at level l_target_i - halvings, and because every block gets exactly `halvings`
+// coarsenings its extent along d depends on its extent along d alone: the level arrays stitch into a
+// tensor-product array for MaxDim, Block and Variable decompositions alike.
+struct StitchedLayout {
+  int K = 0;                                 // min over the subdomains of l_target: the most halvings possible
+  std::vector<uint64_t> shape;               // of the stitched array
+  std::vector<std::vector<uint64_t>> ext;    // [d][j]: extent of the block at grid position j after the halvings
+  std::vector<std::vector<uint64_t>> off;    // [d][j]: its offset in the stitched array
+  std::vector<std::vector<uint64_t>> nodes;  // [d]: index in the FULL array of every node of the stitched grid
+};
+// halvings < 0: only K. Extents are validated here (a header is untrusted). The node list is made for
+// nodes_of_dim alone (it is as long as the extent of the full array).
+int stitched_layout(const Decomposer &dd, uint64_t max_level, int halvings, StitchedLayout &sl,
+                    int nodes_of_dim = -1) {
+  const int D = dd.D;
+  if (D < 1 || D > MGH_MAX_DIM) return hl_fail(MGH_ERR_UNSUPPORTED_DIMENSION, "header: dimension");
+  sl.K = std::numeric_limits<int>::max();
+  for (uint64_t id = 0; id < dd.num; id++) {
+    const auto s = dd.subdomain_shape(id);
+    for (uint64_t e : s)
+      if (e < 3) return hl_fail(MGH_ERR_FORMAT, "header: subdomain with fewer than 3 nodes");
+    sl.K = std::min(sl.K, mgh::hierarchy_l_target(s.size(), s.data(), max_level));
+  }
+  if (halvings < 0) return MGH_SUCCESS;
+  if (halvings > sl.K)
+    return hl_fail(MGH_ERR_INVALID_ARGUMENT, "halvings outside 0 .. the smallest l_target of the subdomains");
+  const auto nd = dd.dim_num_subdomain();
+  sl.shape.assign(D, 0);
+  sl.ext.assign(D, {});
+  sl.off.assign(D, {});
+  sl.nodes.assign(D, {});
+  std::vector<uint64_t> idx;
+  for (int d = 0; d < D; d++) {
+    uint64_t stride = 1;  // subdomain ids are row-major over the decomposition grid
+    for (int e = d + 1; e < D; e++) stride *= nd[e];
+    for (uint64_t j = 0; j < nd[d]; j++) {
+      const uint64_t id = j * stride;  // (grid position j along d, 0 elsewhere)
+      const uint64_t n = dd.subdomain_shape(id)[d], at = dd.subdomain_offset(id)[d];
+      uint64_t m = n;
+      for (int k = 0; k < halvings; k++) m = m / 2 + 1;
+      sl.ext[d].push_back(m);
+      sl.off[d].push_back(sl.shape[d]);
+      sl.shape[d] += m;
+      if (d != nodes_of_dim) continue;
+      mgh::level_nodes(n, halvings, idx);
+      for (uint64_t i : idx) sl.nodes[d].push_back(at + i);
+    }
+  }
+  return MGH_SUCCESS;
+}
+
 // ---- what the decoders (mgh_decompress*, mgh_progressive_*) share ------------------------------------
 // One subdomain record inside a container.
 struct RecordView {
@@ -2750,28 +2817,79 @@ int reconstruct_record(mgh_hierarchy *h, mgh_lossless_ctx *ll, DevBuf &q, DevBuf
   return mgh_dequantize_recompose(h, src, qp.eb, qp.tol, qp.s, qp.norm, qp.dict, 1, oidx, oval, ocount, dst, st);
 }
 
-// level >= 0: mgh_decompress_level -- the output is the dense array of that level of the hierarchy
+// What one subdomain becomes in the output: the level it is reconstructed at (-1: the whole
+// subdomain) and the box its dense array fills in the output array.
+struct SubdomainPlan {
+  int level = -1;
+  std::vector<uint64_t> ext, off;
+  uint64_t n = 0, n_out = 0;  // elements of the subdomain and of its box
+  bool linear_head = false;   // the level is made from the head of a reorder = 1 record alone
+};
+
+// level >= 0: mgh_decompress_level -- the output is the dense array of that level of the hierarchy.
+// halvings > 0: mgh_decompress_coarsened -- every subdomain at its level l_target_i - halvings, stitched.
 template <typename T>
 int decompress_impl(const fmt::Header &hd, size_t meta_size, const void *compressed, size_t csize_total,
-                    void **out, const mgh_config &cfg_in, bool prealloc, int level = -1) {
+                    void **out, const mgh_config &cfg_in, bool prealloc, int level = -1, int halvings = -1) {
   mgh_config cfg = cfg_in;
-  HL_TRY(cache_prepare(cfg.dev_id));
-  HL_TRY(trim_hierarchy_cache());
   const int dtype = hd.is_double ? MGH_DOUBLE : MGH_FLOAT;
   const size_t elem = sizeof(T);
-  size_t total = 1;
-  for (uint64_t e : hd.shape) total *= e;
-  if (level >= 0) {  // (refuses a decomposed container and a level outside the hierarchy)
-    std::vector<uint64_t> lshape;
-    HL_TRY(header_level_shape(hd, cfg, level, nullptr, &lshape));
-    total = 1;
-    for (uint64_t e : lshape) total *= e;
-  }
+  std::vector<uint64_t> dshape = hd.shape;  // of the output array
+  int l_target = 0;
+  // (refuses a decomposed container and a level outside the hierarchy)
+  if (level >= 0) HL_TRY(header_level_shape(hd, cfg, level, &l_target, &dshape));
   Decomposer dd;
   HL_TRY(decomposer_from_header(hd, cfg, dd));
   for (uint64_t id = 0; id < dd.num; id++)
     for (uint64_t e : dd.subdomain_shape(id))
       if (e < 3) return hl_fail(MGH_ERR_FORMAT, "header: subdomain with fewer than 3 nodes");
+  std::vector<SubdomainPlan> plan(dd.num);
+  if (level >= 0) {
+    plan[0].level = level;
+    plan[0].ext = dshape;
+    plan[0].off.assign(dshape.size(), 0);
+    plan[0].linear_head = hd.reorder && level < l_target;
+  } else if (halvings >= 0) {  // (refuses more halvings than the shallowest subdomain has levels)
+    StitchedLayout sl;
+    HL_TRY(stitched_layout(dd, cfg.max_larget_level, halvings, sl));
+    if (halvings > 0) {
+      dshape = sl.shape;
+      for (uint64_t id = 0; id < dd.num; id++) {
+        const auto sid = dd.dim_subdomain_id(id), sshape = dd.subdomain_shape(id);
+        SubdomainPlan &P = plan[id];
+        P.level = mgh::hierarchy_l_target(sshape.size(), sshape.data(), cfg.max_larget_level) - halvings;
+        for (int d = 0; d < dd.D; d++) {
+          P.ext.push_back(sl.ext[d][sid[d]]);
+          P.off.push_back(sl.off[d][sid[d]]);
+        }
+        P.linear_head = hd.reorder != 0;  // (level < l_target)
+      }
+    }
+  }
+  size_t total = 1;
+  for (uint64_t e : dshape) total *= e;
+  uint64_t sub_elems = 0, q_elems = 0, q2_elems = 0;  // what a lane's buffers hold: the maxima over the subdomains
+  bool all_slabs = true;  // every box spans every dimension but the slowest: a contiguous run of the output
+  const uint64_t hblock = std::max<uint64_t>(hd.huff_block_size, 1);
+  for (uint64_t id = 0; id < dd.num; id++) {
+    SubdomainPlan &P = plan[id];
+    if (P.level < 0) {
+      P.ext = dd.subdomain_shape(id);
+      P.off = dd.subdomain_offset(id);
+    }
+    P.n = P.n_out = 1;
+    for (uint64_t e : dd.subdomain_shape(id)) P.n *= e;
+    for (uint64_t e : P.ext) P.n_out *= e;
+    for (int d = 1; d < dd.D; d++) all_slabs = all_slabs && P.ext[d] == dshape[d];
+    sub_elems = std::max(sub_elems, P.n_out);
+    // A level below l_target of a level-linearised (reorder = 1) record: its first n_out integers are
+    // the box of the level -- only the chunks that hold them are decoded, and the level is made from
+    // that head; nothing on the way is sized by the subdomain.
+    q_elems = std::max(q_elems, P.linear_head ? std::min<uint64_t>(P.n, ((P.n_out - 1) / hblock + 1) * hblock) : P.n);
+    if (hd.reorder && !P.linear_head) q2_elems = std::max(q2_elems, P.n);
+  }
+  HL_TRY(cache_prepare(cfg.dev_id));
+  HL_TRY(trim_hierarchy_cache());
   RecordView rv_hd;
   HL_TRY(record_view_header(hd, rv_hd));
   const bool in_dev = is_device_pointer(compressed);
@@ -2814,27 +2932,17 @@ int decompress_impl(const fmt::Header &hd, size_t meta_size, const void *compres
     return rc;
   };
   const uint64_t max_elems = dd.max_subdomain_elems();
-  const uint64_t sub_elems = level >= 0 ? total : max_elems;  // (dense reconstruction of a subdomain)
-  // A level below l_target of a level-linearised (reorder = 1) record: its first `total` integers are
-  // the box of the level -- only the chunks that hold them are decoded, and the level is made from
-  // that head; nothing on the way is sized by the subdomain.
-  bool linear_head = false;
-  if (level >= 0 && hd.reorder) {
-    int l_target = 0;
-    HL_TRY(header_level_shape(hd, cfg, -1, &l_target, nullptr));
-    linear_head = level < l_target;
-  }
-  const uint64_t hblock = std::max<uint64_t>(hd.huff_block_size, 1);
-  const uint64_t q_elems = linear_head ? std::min<uint64_t>(max_elems, ((total - 1) / hblock + 1) * hblock) : max_elems;
   int rc;
   // device-resident output whose subdomains are contiguous slabs: reconstruct them in place
-  const bool zero_copy = is_device_pointer(*out) && dd.all_contiguous();
+  const bool zero_copy = is_device_pointer(*out) && all_slabs;
+  uint64_t slab_inner = 1;  // elements of one plane of the slowest dimension of the output
+  for (size_t d = 1; d < dshape.size(); d++) slab_inner *= dshape[d];
   auto ensure_all = [&]() -> int {
     for (int l = 0; l < nlanes; l++) {
       Lane &L = g_cache.lane[l];
       if (!zero_copy) HL_TRY(L.sub.ensure(sub_elems * elem));
       HL_TRY(L.q.ensure(q_elems * 8));
-      if (hd.reorder && !linear_head) HL_TRY(L.q2.ensure(max_elems * 8));
+      if (q2_elems) HL_TRY(L.q2.ensure(q2_elems * 8));
     }
     return MGH_SUCCESS;
   };
@@ -2884,12 +2992,13 @@ int decompress_impl(const fmt::Header &hd, size_t meta_size, const void *compres
       }
     }
     const auto sshape = dd.subdomain_shape(id);
-    uint64_t n = 1;
-    for (uint64_t e : sshape) n *= e;
+    const SubdomainPlan &P = plan[id];
+    const uint64_t n = P.n;
+    const int level = P.level;
     RecordView rv = rv_hd;
     HL_TRY(record_view_at(compressed, csize_total, byte_offset, n * elem, rv));
     byte_offset += 8 + rv.csize;
-    void *sub = zero_copy ? (void *)((char *)*out + dd.linear_offset(id) * elem) : L.sub.p;
+    void *sub = zero_copy ? (void *)((char *)*out + P.off[0] * slab_inner * elem) : L.sub.p;
     decompress_stats().subdomains++;
     if (rv.raw) {
       decompress_stats().record_bytes += rv.csize;
@@ -2900,6 +3009,8 @@ int decompress_impl(const fmt::Header &hd, size_t meta_size, const void *compres
     HL_TRY(get_hierarchy(&h, &owned, dtype, sshape, cptr, dd.subdomain_offset(id), cfg, lane));
     if (owned) owned_h[lane] = h;
     if (level >= 0 && level > mgh_l_target(h)) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "level outside 0 .. l_target");
+    if (halvings > 0 && level != mgh_l_target(h) - halvings)
+      return hl_fail(MGH_ERR_FORMAT, "header: the hierarchy of the subdomain is not the header's");
     if (rv.raw) {  // (the finest level is the data)
       if (level == mgh_l_target(h)) return copy_any(sub, rv.rec, rv.csize, st);
       // (q: the head of a reorder = 1 record is all the lane holds otherwise)
@@ -2907,14 +3018,13 @@ int decompress_impl(const fmt::Header &hd, size_t meta_size, const void *compres
       return mgh_dequantize_recompose_to_level(h, (int64_t *)L.q.p, qp.eb, qp.tol, qp.s, qp.norm, qp.dict, 0, nullptr,
                                                nullptr, 0, level, sub, st);
     }
-    return reconstruct_record(h, L.ll, L.q, L.q2, qp, rv, n, level, linear_head, total, q_elems, sub, st);
+    return reconstruct_record(h, L.ll, L.q, L.q2, qp, rv, n, level, P.linear_head, P.n_out, q_elems, sub, st);
   };
   auto finish = [&](uint64_t id) -> int {
     if (zero_copy) return MGH_SUCCESS;
     pretouch.join();
     Lane &L = g_cache.lane[id % nlanes];
-    if (level >= 0) return copy_any(*out, L.sub.p, total * elem, L.st);  // (one subdomain, dense in the level's shape)
-    return copy_subdomain(dd, id, elem, L.sub.p, nullptr, *out, false, L.st);
+    return copy_box(plan[id].ext, plan[id].off, dshape, elem, L.sub.p, nullptr, *out, false, L.st);
   };
   if ((rc = issue(0)) != MGH_SUCCESS) return cleanup(rc);
   for (uint64_t id = 0; id < dd.num; id++) {
@@ -3001,7 +3111,15 @@ int mgh_compress(int D, int dtype, const uint64_t *shape, double tol, double s, 
 
 static int decompress_entry(const void *compressed_data, size_t compressed_size, void **decompressed_data,
                             const mgh_config *config, int output_pre_allocated, size_t expect_bytes, int expect_dtype,
-                            int level = -1);
+                            int level = -1, int halvings = -1);
+
+int mgh_decompress_coarsened(const void *compressed_data, size_t compressed_size, int halvings, void **decompressed_data,
+                             const mgh_config *config, int output_pre_allocated) {
+  if (halvings < 0)
+    return hl_fail(MGH_ERR_INVALID_ARGUMENT, "halvings outside 0 .. the smallest l_target of the subdomains");
+  return decompress_entry(compressed_data, compressed_size, decompressed_data, config, output_pre_allocated, 0, -1, -1,
+                          halvings);
+}
 
 int mgh_decompress_level(const void *compressed_data, size_t compressed_size, int level, void **decompressed_data,
                          const mgh_config *config, int output_pre_allocated) {
@@ -3026,7 +3144,7 @@ int mgh_decompress_into(const void *compressed_data, size_t compressed_size, voi
 // header the call reads anyway, before anything is written (mgh_decompress_into)
 static int decompress_entry(const void *compressed_data, size_t compressed_size, void **decompressed_data,
                             const mgh_config *config, int output_pre_allocated, size_t expect_bytes, int expect_dtype,
-                            int level) {
+                            int level, int halvings) {
   decompress_stats() = mgh_decompress_stats{};
   if (!compressed_data || !decompressed_data) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "NULL argument");
   if (output_pre_allocated && !*decompressed_data) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "pre-allocated output is NULL");
@@ -3060,9 +3178,9 @@ static int decompress_entry(const void *compressed_data, size_t compressed_size,
   try {
     if (hd.is_double)
       return decompress_impl<double>(hd, meta_size, compressed_data, compressed_size, decompressed_data,
-                                     *config, output_pre_allocated != 0, level);
+                                     *config, output_pre_allocated != 0, level, halvings);
     return decompress_impl<float>(hd, meta_size, compressed_data, compressed_size, decompressed_data,
-                                  *config, output_pre_allocated != 0, level);
+                                  *config, output_pre_allocated != 0, level, halvings);
   } catch (const std::exception &e) {
     return hl_fail(MGH_ERR_DEVICE, e.what());
   }
@@ -4001,6 +4119,54 @@ int mgh_infer_level_nodes(const void *data, size_t size, const mgh_config *confi
   std::vector<uint64_t> idx;
   mgh::level_nodes(full[dim], L - level, idx);
   if (idx.size() > cap) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "mgh_infer_level_nodes: capacity too small");
+  std::copy(idx.begin(), idx.end(), h_idx_out);
+  return (int)idx.size();
+}
+
+namespace {
+int infer_coarsened(const void *data, size_t size, const mgh_config *config, int halvings, int nodes_of_dim,
+                    StitchedLayout &sl) {
+  if (!data) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "NULL argument");
+  mgh_config def;
+  if (!config) {
+    mgh_config_default(&def);
+    config = &def;
+  }
+  fmt::Header hd;
+  size_t ms = 0;
+  HL_TRY(read_header(data, size, hd, ms));
+  if (hd.shape.empty() || hd.shape.size() > MGH_MAX_DIM) return hl_fail(MGH_ERR_UNSUPPORTED_DIMENSION, "header: dimension");
+  Decomposer dd;
+  HL_TRY(decomposer_from_header(hd, *config, dd));
+  if (halvings >= 0 && nodes_of_dim != -1 && (nodes_of_dim < 0 || nodes_of_dim >= dd.D))
+    return hl_fail(MGH_ERR_INVALID_ARGUMENT, "dim / NULL argument");
+  return stitched_layout(dd, config->max_larget_level, halvings, sl, nodes_of_dim);
+}
+} // namespace
+
+int mgh_infer_coarsened_shape(const void *data, size_t size, const mgh_config *config, int halvings, int *D_out,
+                              uint64_t *shape_out, int *max_halvings_out) {
+  StitchedLayout sl;
+  HL_TRY(infer_coarsened(data, size, config, halvings, -1, sl));
+  if (max_halvings_out) *max_halvings_out = sl.K;
+  if (halvings >= 0) {
+    if (D_out) *D_out = (int)sl.shape.size();
+    if (shape_out) std::copy(sl.shape.begin(), sl.shape.end(), shape_out);
+  }
+  return MGH_SUCCESS;
+}
+
+int mgh_infer_coarsened_nodes(const void *data, size_t size, const mgh_config *config, int halvings, int dim,
+                              uint64_t *h_idx_out, uint64_t cap) {
+  StitchedLayout sl;
+  if (halvings < 0) {
+    HL_TRY(infer_coarsened(data, size, config, -1, -1, sl));
+    return sl.K;
+  }
+  if (dim < 0 || !h_idx_out) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "dim / NULL argument");
+  HL_TRY(infer_coarsened(data, size, config, halvings, dim, sl));
+  const std::vector<uint64_t> &idx = sl.nodes[dim];
+  if (idx.size() > cap) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "mgh_infer_coarsened_nodes: capacity too small");
   std::copy(idx.begin(), idx.end(), h_idx_out);
   return (int)idx.size();
 }

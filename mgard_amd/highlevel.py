@@ -28,6 +28,7 @@ HL_SYMBOLS = [
     "mgh_lossless_decompress_prefix", "mgh_last_decompress_stats",
     "mgh_lossless_decompress_range", "mgh_infer_level_range", "mgh_progressive_open",
     "mgh_progressive_level", "mgh_progressive_refine", "mgh_progressive_close",
+    "mgh_infer_coarsened_shape", "mgh_infer_coarsened_nodes", "mgh_decompress_coarsened",
 ]
 
 
@@ -117,6 +118,9 @@ def _hl():
     L.mgh_infer_level_shape.argtypes = [vp, C.c_size_t, vp, C.c_int, vp, vp, vp]
     L.mgh_infer_level_nodes.argtypes = [vp, C.c_size_t, vp, C.c_int, C.c_int, vp, u64]
     L.mgh_decompress_level.argtypes = [vp, C.c_size_t, C.c_int, C.POINTER(vp), vp, C.c_int]
+    L.mgh_infer_coarsened_shape.argtypes = [vp, C.c_size_t, vp, C.c_int, vp, vp, vp]
+    L.mgh_infer_coarsened_nodes.argtypes = [vp, C.c_size_t, vp, C.c_int, C.c_int, vp, u64]
+    L.mgh_decompress_coarsened.argtypes = [vp, C.c_size_t, C.c_int, C.POINTER(vp), vp, C.c_int]
     L.mgh_dist_use_library.argtypes = [C.c_char_p]
     L.mgh_compress_dist.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(u64), C.c_double,
                                     C.c_double, C.c_int, vp, C.POINTER(vp), C.POINTER(C.c_size_t), vp, vp, C.c_int]
@@ -339,6 +343,48 @@ def infer_level_nodes(buf, level, dim, config=None):
     return np.array(out[:k], dtype=np.int64)
 
 
+def infer_coarsened(buf, halvings, config=None):
+    """mgh_infer_coarsened_shape: (shape of the array after `halvings` coarsenings of every subdomain, K) with
+    K the largest number of halvings the container allows; halvings = None or < 0: (None, K). Works on
+    domain-decomposed containers; `config` carries max_larget_level and the sizes of a Variable decomposition."""
+    import torch
+    L = _hl()
+    cfg = config if config is not None else Config()
+    if isinstance(buf, torch.Tensor):
+        p, n = C.c_void_p(buf.data_ptr()), buf.numel()
+    else:
+        buf = np.ascontiguousarray(buf)
+        p, n = C.c_void_p(buf.ctypes.data), buf.size
+    halvings = -1 if halvings is None else int(halvings)
+    D, K = C.c_int(), C.c_int()
+    shp = (C.c_uint64 * MAX_DIM)()
+    _check(L.mgh_infer_coarsened_shape(p, n, C.byref(cfg), halvings, C.byref(D), shp, C.byref(K)))
+    if halvings < 0:
+        return None, K.value
+    return tuple(int(shp[d]) for d in range(D.value)), K.value
+
+
+def infer_coarsened_nodes(buf, halvings, dim, config=None):
+    """mgh_infer_coarsened_nodes: index in the FULL array of every node along `dim` of the array that
+    decompress(buf, coarsen=halvings) returns. The coordinates of that array are the full grid's at these
+    indices (the stitched grid of a decomposed container is not uniform)."""
+    import torch
+    L = _hl()
+    if halvings < 0:
+        raise ValueError("halvings must be >= 0 (infer_coarsened(buf, None) gives the largest number)")
+    cfg = config if config is not None else Config()
+    if isinstance(buf, torch.Tensor):
+        p, n = C.c_void_p(buf.data_ptr()), buf.numel()
+    else:
+        buf = np.ascontiguousarray(buf)
+        p, n = C.c_void_p(buf.ctypes.data), buf.size
+    shape, _ = infer(buf)
+    cap = shape[dim] if 0 <= dim < len(shape) else 1
+    out = (C.c_uint64 * cap)()
+    k = _check(L.mgh_infer_coarsened_nodes(p, n, C.byref(cfg), int(halvings), int(dim), out, cap))
+    return np.array(out[:k], dtype=np.int64)
+
+
 def infer_level_range(buf, level, config=None):
     """mgh_infer_level_range: (first_elem, num_elems, first_chunk, num_chunks) of the coefficients of
     `level` in a level-linearised (reorder = 1) record; host only."""
@@ -426,21 +472,32 @@ class Progressive:
             pass
 
 
-def decompress(buf, config=None, out=None, level=None):
+def decompress(buf, config=None, out=None, level=None, coarsen=None):
     """mgard_x::decompress. Returns a numpy array (host stream) or a cuda tensor (device stream).
     `out`: optional pre-allocated buffer -- a contiguous cuda tensor (device streams) or a
     C-contiguous numpy array (host streams). Its size and type are checked by the library against the
     header it reads anyway (mgh_decompress_into: ValueError on a mismatch, nothing written).
     `level` (extension): mgh_decompress_level -- the array at that level of the hierarchy (0 =
-    coarsest, infer_level(buf, None)[1] = full), of shape infer_level(buf, level)[0]."""
+    coarsest, infer_level(buf, None)[1] = full), of shape infer_level(buf, level)[0]. Containers with one
+    subdomain only.
+    `coarsen` (extension): mgh_decompress_coarsened -- every subdomain after that many halvings of its grid,
+    stitched into one array of shape infer_coarsened(buf, coarsen)[0]; domain-decomposed containers included.
+    infer_coarsened_nodes tells which nodes of the full grid the result holds."""
     import torch
+    if level is not None and coarsen is not None:
+        raise ValueError("pass either `level` or `coarsen`, not both")
     L = _hl()
     cfg = config if config is not None else Config()
     on_dev = isinstance(buf, torch.Tensor) and buf.is_cuda
     if not on_dev:
         buf = np.ascontiguousarray(buf)
-    if level is not None:
-        shape, _ = infer_level(buf, int(level), cfg)
+    if level is not None or coarsen is not None:
+        if level is not None:
+            shape, _ = infer_level(buf, int(level), cfg)
+        else:
+            if int(coarsen) < 0:
+                raise ValueError("coarsen must be >= 0")
+            shape, _ = infer_coarsened(buf, int(coarsen), cfg)
         _, dt = infer(buf)
         want = torch.float32 if dt == FLOAT else torch.float64
         if on_dev:
@@ -458,7 +515,10 @@ def decompress(buf, config=None, out=None, level=None):
                     out.dtype == npdt and out.size == int(np.prod(shape))):
                 raise ValueError("`out` must be a writeable C-contiguous numpy array of the level's shape and type")
             p, n, optr = C.c_void_p(buf.ctypes.data), buf.size, C.c_void_p(out.ctypes.data)
-        _check(L.mgh_decompress_level(p, n, int(level), C.byref(optr), C.byref(cfg), 1))
+        if level is not None:
+            _check(L.mgh_decompress_level(p, n, int(level), C.byref(optr), C.byref(cfg), 1))
+        else:
+            _check(L.mgh_decompress_coarsened(p, n, int(coarsen), C.byref(optr), C.byref(cfg), 1))
         return out
     if out is None:
         shape, dt = infer(buf)
