@@ -327,6 +327,16 @@ int mgh_profile_filter(mgh_hierarchy *h, const char *kernel_name_or_null);
 int mgh_profile_read(mgh_hierarchy *h, const char **names, double *total_ms, uint64_t *launches,
                      int cap, int reset);
 
+/* Test aid (no reference counterpart): while profiling is enabled on a hierarchy, every Thomas
+ * solve that goes through the solver's planner (mgard_amd/csrc/ipk_plan.hpp) leaves one record, the
+ * first 512 of them since the last reset. A record is MGH_IPK_PLAN_FIELDS values: family (position in
+ * IpkKernel: 0 Spec, 1 LdsContigChunked, 2 Dma, 3 Stream, 4 LdsContig, 5 LdsStrided, 6 Thread), axis
+ * of the compact box, element size, m[0], m[1], m[2], boxes of the launch, pencil length n, pencils,
+ * W, n_glob, KR, P, K, add (0: plain, +1 / -1: added to / subtracted from the coarse nodes), element
+ * stride between the boxes. Writes up to cap records to out; returns the number recorded. */
+#define MGH_IPK_PLAN_FIELDS 16
+int mgh_debug_ipk_plans_read(mgh_hierarchy *h, long long *out, int cap, int reset);
+
 /* Measurement aid for the roofline line (no reference counterpart): a PURE stream with the
  * read/write mix of the top-level pass of the hot path -- n elements of `dtype` read once,
  * n int64 written once with streaming stores, two side arrays of n/8 elements written -- and

@@ -32,7 +32,7 @@ SYMBOLS = [
     "mgh_recompose_to_level", "mgh_dequantize_recompose_to_level",
     "mgh_dequantize_recompose_sym16_to_level", "mgh_level_nodes",
     "mgh_level_box_from_linear", "mgh_dequantize_recompose_linear_to_level",
-    "mgh_refine_level",
+    "mgh_refine_level", "mgh_debug_ipk_plans_read",
 ]
 
 
@@ -96,6 +96,7 @@ def load_library():
     L.mgh_profile_filter.argtypes = [vp, C.c_char_p]
     L.mgh_profile_read.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(C.c_double), u64p,
                                    C.c_int, C.c_int]
+    L.mgh_debug_ipk_plans_read.argtypes = [vp, i64p, C.c_int, C.c_int]
     L.mgh_outlier_restore.argtypes = [vp, u64, vp, vp, u64, vp]
     L.mgh_level_linearize.argtypes = [vp, vp, vp, C.c_int, vp, vp, u64, u64, vp]
     L.mgh_recompose_to_level.argtypes = [vp, vp, C.c_int, vp, vp]
@@ -501,3 +502,22 @@ class Hierarchy:
         cnt = (C.c_uint64 * cap)()
         n = _check(load_library().mgh_profile_read(self._h, names, ms, cnt, cap, int(reset)))
         return {names[i].decode(): (ms[i], int(cnt[i])) for i in range(min(n, cap))}
+
+    IPK_FAMILIES = ("Spec", "LdsContigChunked", "Dma", "Stream", "LdsContig", "LdsStrided", "Thread")
+    IPK_PLAN_FIELDS = ("family", "axis", "elem", "m0", "m1", "m2", "nbatch", "n", "npencil", "W", "n_glob", "KR",
+                       "P", "K", "add", "batch_stride")
+
+    def ipk_plans(self, reset=True):
+        """The Thomas solves that went through the planner (csrc/ipk_plan.hpp) while profile() was
+        on, in launch order: one dict per solve with the keys IPK_PLAN_FIELDS (`family` by name, `m`
+        as a tuple instead of m0..m2)."""
+        cap, nf = 512, len(self.IPK_PLAN_FIELDS)
+        buf = (C.c_int64 * (cap * nf))()
+        n = _check(load_library().mgh_debug_ipk_plans_read(self._h, buf, cap, int(reset)))
+        out = []
+        for i in range(min(n, cap)):
+            r = dict(zip(self.IPK_PLAN_FIELDS, buf[i * nf:(i + 1) * nf]))
+            r["family"] = self.IPK_FAMILIES[r["family"]]
+            r["m"] = (r.pop("m0"), r.pop("m1"), r.pop("m2"))
+            out.append(r)
+        return out

@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
+#include <array>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -102,6 +103,9 @@ struct mgh_hierarchy {
   bool no_head = false;            // MGH_NO_RECOMPOSE_HEAD
   bool debug_sync = false;         // MGH_DEBUG_SYNC: name every launch on stderr and synchronise behind it
   std::map<std::string, ProfileEntry> prof;
+  // while `profiling`: one record per Thomas solve that went through ipk_launch, the first
+  // kIpkLogCap of them (mgh_debug_ipk_plans_read; MGH_IPK_PLAN_FIELDS values each, in its order)
+  std::vector<std::array<long long, MGH_IPK_PLAN_FIELDS>> ipk_log;
   size_t device_bytes = 0;
   uint64_t shape[MGH_MAX_DIM] = {};
   // mgh_set_ld: leading dimensions of the caller's T arrays, [MGH_LD_IN / MGH_LD_OUT][dim]
@@ -612,6 +616,8 @@ template <typename T, int AXIS> int ipk_launch_thread(const IpkPlan &p, const Ip
   });
 }
 
+constexpr size_t kIpkLogCap = 512;  // records mgh_hierarchy::ipk_log keeps
+
 // Thomas solve along `axis` of the compact (m[0], m[1], m[2]) box, by the kernel ipk_plan() picks.
 // axis 0 only: `nbatch` boxes `batch_stride` elements apart in ONE launch (the slices of a 4-D level).
 template <typename T>
@@ -621,6 +627,10 @@ int ipk_launch(mgh_hierarchy *h, int axis, const uint32_t *m, T *x, const T *tt,
   static const char *names[3] = {"ipk_r", "ipk_c", "ipk_f"};
   const IpkArgs<T> a{h, names[axis], x, tt, add_to, sign, s};
   const IpkPlan p = ipk_plan(h->ipk, sizeof(T), axis, m, nbatch, batch_stride);
+  // (the boxes of a Thread plan with batches come back here one by one: a record each, none for the whole)
+  if (h->profiling && !p.per_batch && h->ipk_log.size() < kIpkLogCap)
+    h->ipk_log.push_back({(long long)p.kernel, axis, (long long)sizeof(T), m[0], m[1], m[2], nbatch, p.geom.n,
+                          p.geom.npencil, p.W, p.n_glob, p.KR, p.P, p.K, a.add(), (long long)batch_stride});
   switch (p.kernel) {
   case IpkKernel::Spec: return ipk_launch_spec<T>(p, a, axis);
   case IpkKernel::LdsContigChunked: return ipk_launch_lds_contig<T, true>(p, a);
@@ -1050,6 +1060,7 @@ int decompose_fused(mgh_hierarchy *h, const T *data, const Layout &in, T *coeff,
         const uint32_t nrange = (uint32_t)((box_b + range_b - 1) / range_b);
         for (uint32_t k = 0; k < nrange; k++) {
           const uint32_t R_lo = (uint32_t)((uint64_t)b.m[0] * k / nrange), R_hi = (uint32_t)((uint64_t)b.m[0] * (k + 1) / nrange);
+          if (R_hi == R_lo) continue;  // (fewer planes than ranges: 3 x 16385 x 16385)
           const uint32_t ms[3] = {R_hi - R_lo, b.m[1], b.m[2]};
           TRY(ipk_fc_launch<T>(h, ms, ds->t3 + (size_t)R_lo * b.m[1] * b.m[2], t.thomas[2], t.thomas[1], s));
         }
@@ -2951,8 +2962,11 @@ int norm_stream_add(mgh_hierarchy *h, const T *part, size_t count, double s, int
 }
 
 // The switches as set in the environment (validated by env_validate) on a device of `num_cu` CUs.
+// MGH_IPK_PLAN_CU: the CU count the planner plans with instead (a plan is a performance choice:
+// every value gives the same bits; a small one puts small boxes on the kernels of the big ones).
 inline IpkTuning ipk_tuning_from_env(size_t num_cu) {
   IpkTuning t;
+  num_cu = (size_t)env_get("MGH_IPK_PLAN_CU", (long)num_cu);
   t.num_cu = num_cu;
   t.stream = (int)env_get("MGH_IPK_STREAM", t.stream);
   t.dma = (int)env_get("MGH_IPK_DMA", t.dma);
@@ -3452,6 +3466,15 @@ int mgh_debug_phase_read(unsigned long long *out16, int reset) {
   return MGH_SUCCESS;
 }
 #endif
+
+int mgh_debug_ipk_plans_read(mgh_hierarchy *h, long long *out, int cap, int reset) {
+  if (!h || (cap > 0 && !out) || cap < 0) return fail(MGH_ERR_INVALID_ARGUMENT, "null argument");
+  const int n = (int)h->ipk_log.size();
+  for (int i = 0; i < std::min(n, cap); i++)
+    std::copy(h->ipk_log[i].begin(), h->ipk_log[i].end(), out + (size_t)i * MGH_IPK_PLAN_FIELDS);
+  if (reset) h->ipk_log.clear();
+  return n;
+}
 
 int mgh_profile_enable(mgh_hierarchy *h, int enable) {
   if (!h) return fail(MGH_ERR_INVALID_ARGUMENT, "null argument");

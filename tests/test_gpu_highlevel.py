@@ -742,6 +742,12 @@ def test_developer_switches_are_validated(monkeypatch):
         mg.Hierarchy((9, 9, 9), np.float32)
     monkeypatch.setenv("MGH_RCH", "2,3,8")
     mg.Hierarchy((9, 9, 9), np.float32).close()
+    for bad in ("0", "1025"):
+        monkeypatch.setenv("MGH_IPK_PLAN_CU", bad)
+        with pytest.raises(mg.MgardHipError, match="MGH_IPK_PLAN_CU"):
+            mg.Hierarchy((9, 9, 9), np.float32)
+    monkeypatch.setenv("MGH_IPK_PLAN_CU", "1")
+    mg.Hierarchy((9, 9, 9), np.float32).close()
 
 
 def _records_on_device(torch, stream, metadata_size):
