@@ -741,31 +741,47 @@ int correction(mgh_hierarchy *h, int l, const T *coef, size_t cI, size_t cJ, T *
   return MGH_SUCCESS;
 }
 
-// Quantizer constants on the host (LinearQuantization.hpp:495-545 + volumes :186-195)
+// What a quantizer makes: the integers (always dense), and the out-of-dictionary values.
+struct QuantOut {
+  uint64_t dict_size;
+  int prep_huffman;
+  int64_t *q;
+  uint16_t *sym16;  // instead of q: 16-bit dictionary symbols (mgh_decompose_quantize_sym16)
+  uint64_t *ocount, *oidx;
+  int64_t *oval;
+  uint64_t ocap;
+};
+
+// What the fused kernels quantize with: the output, and the table -- built on the host
+// (LinearQuantization.hpp:495-545 + volumes :186-195) or left on the device by k_make_qparams.
 template <typename T> struct QuantParams {
-  std::vector<T> qz, vol;  // per level
-  int64_t dict_size = 0;
-  int prep_huffman = 0;
-  int64_t *q = nullptr;
-  uint16_t *q16 = nullptr;  // instead of q: 16-bit dictionary symbols (mgh_decompose_quantize_sym16)
-  unsigned long long *ocount = nullptr;
-  uint64_t *oidx = nullptr;
-  int64_t *oval = nullptr;
-  unsigned long long ocap = 0;
-  const T *d_qp = nullptr;  // device table [2 * (L + 1)] (k_make_qparams) instead of qz / vol
+  QuantOut out{};
+  std::vector<T> qz, vol;   // per level
+  const T *d_qp = nullptr;  // device table [2 * (L + 1)] instead of qz / vol
 };
 
 template <typename T>
-QuantParams<T> make_quant_params(mgh_hierarchy *h, int ebtype, double tol, double s, double norm,
-                                 bool reciprocal) {
+void host_quant_table(mgh_hierarchy *h, int ebtype, double tol, double s, double norm, QuantParams<T> &qp) {
   auto *hh = HH<T>(h);
-  QuantParams<T> qp;
   qp.qz.resize(h->L + 1);
   qp.vol.resize(h->L + 1);
-  hh->quantizers(ebtype, (T)tol, (T)s, (T)norm, reciprocal, qp.qz.data());
+  hh->quantizers(ebtype, (T)tol, (T)s, (T)norm, true, qp.qz.data());
   const bool calc_vol = !((T)s == std::numeric_limits<T>::infinity());
-  for (int l = 0; l <= h->L; l++) qp.vol[l] = calc_vol ? hh->level_volume(l, !reciprocal) : (T)1;
-  return qp;
+  for (int l = 0; l <= h->L; l++) qp.vol[l] = calc_vol ? hh->level_volume(l, false) : (T)1;
+}
+
+// The quantizer fields of the fused kernels' argument block.
+template <typename T> void fused_quant_args(const mgh_hierarchy *h, const QuantParams<T> &qp, FusedArgs<T> &A) {
+  A.q = qp.out.q;
+  A.q16 = qp.out.sym16;
+  A.dict_size = (int64_t)qp.out.dict_size;
+  A.prep_huffman = qp.out.prep_huffman;
+  A.outlier_count = (unsigned long long *)qp.out.ocount;
+  A.outlier_idx = qp.out.oidx;
+  A.outlier_val = qp.out.oval;
+  A.outlier_cap = qp.out.ocap;
+  A.qp = qp.d_qp;
+  A.nlev = h->L + 1;
 }
 
 // Size class of a level for the fused kernels: 2 = plenty of tiles (long marches, RCH = 16),
@@ -873,7 +889,7 @@ int launch_fused2(mgh_hierarchy *h, const FusedArgs<T> &A, const Box3 &b, int cl
 // -- decides.
 template <typename T> bool outlier_agg_now(mgh_hierarchy *h, const QuantParams<T> *qp) {
   auto *ds = DS<T>(h);
-  if (!qp || !qp->prep_huffman || !qp->ocount) return false;
+  if (!qp || !qp->out.prep_huffman || !qp->out.ocount) return false;
   if (!ds->outliers_seen && h->outlier_agg == 2) {
     if (hipHostMalloc(&ds->outliers_seen, sizeof(unsigned long long), hipHostMallocDefault) == hipSuccess)
       *ds->outliers_seen = 0;
@@ -973,18 +989,7 @@ int decompose_fused(mgh_hierarchy *h, const T *data, const Layout &in, T *coeff,
   A.coef = coeff;
   A.dI = fI;
   A.dJ = fJ;
-  if (OUT == OUT_Q) {
-    A.q = qp->q;
-    A.q16 = qp->q16;
-    A.dict_size = qp->dict_size;
-    A.prep_huffman = qp->prep_huffman;
-    A.outlier_count = qp->ocount;
-    A.outlier_idx = qp->oidx;
-    A.outlier_val = qp->oval;
-    A.outlier_cap = qp->ocap;
-    A.qp = qp->d_qp;
-    A.nlev = L + 1;
-  }
+  if (OUT == OUT_Q) fused_quant_args(h, *qp, A);
   const bool agg = OUT == OUT_Q && outlier_agg_now<T>(h, qp);
   // levels whose working set fits in one workgroup's LDS run inside the tail kernel
   constexpr size_t kTailLdsMax = 150 * 1024;
@@ -1021,7 +1026,7 @@ int decompose_fused(mgh_hierarchy *h, const T *data, const Layout &in, T *coeff,
     if (l == L) TRY(after_first());
     // (the level kernels test the dictionary range in 32 bits: the entry points send larger
     // dictionaries through decompose + quantize)
-    if (OUT == OUT_Q && !(qp->dict_size >= 0 && qp->dict_size <= ((int64_t)1 << 30)))
+    if (OUT == OUT_Q && qp->out.dict_size > ((uint64_t)1 << 30))
       return fail(MGH_ERR_INVALID_ARGUMENT, "fused path: dict_size must be at most 2^30");
     if (cls < h->box) {
       // small level: no march (kernels_box.hpp)
@@ -1253,18 +1258,7 @@ int decompose_fused4(mgh_hierarchy *h, const T *data, T *coeff, const QuantParam
   A.coef = coeff;
   A.dI = full[1];
   A.dJ = full[2];
-  if (OUT == OUT_Q) {
-    A.q = qp->q;
-    A.q16 = qp->q16;
-    A.dict_size = qp->dict_size;
-    A.prep_huffman = qp->prep_huffman;
-    A.outlier_count = qp->ocount;
-    A.outlier_idx = qp->oidx;
-    A.outlier_val = qp->oval;
-    A.outlier_cap = qp->ocap;
-    A.qp = qp->d_qp;
-    A.nlev = L + 1;
-  }
+  if (OUT == OUT_Q) fused_quant_args(h, *qp, A);
   TRY(after_first());
   const bool agg = OUT == OUT_Q && outlier_agg_now<T>(h, qp);
   const T *src = data;
@@ -2316,17 +2310,16 @@ int upload_quantizers(mgh_hierarchy *h, int ebtype, double tol, double s, double
 
 // the stand-alone quantizer with the table already in ds->qz (uploaded, or made on the device)
 template <typename T>
-int quantize_launch(mgh_hierarchy *h, const T *coeff, uint64_t dict_size, int prep_huffman, int64_t *q,
-                    uint64_t *ocount, uint64_t *oidx, int64_t *oval, uint64_t ocap, hipStream_t st) {
+int quantize_launch(mgh_hierarchy *h, const T *coeff, const QuantOut &qo, hipStream_t st) {
   auto *ds = DS<T>(h);
-  if (ocount) HIP_TRY(hipMemsetAsync(ocount, 0, sizeof(uint64_t), st));
+  if (qo.ocount) HIP_TRY(hipMemsetAsync(qo.ocount, 0, sizeof(uint64_t), st));
   const size_t total = h->total;
   const unsigned grid = (unsigned)std::min<size_t>((total + kQuantPerRound - 1) / kQuantPerRound, 256 * 32);
   return launch(h, "quantize", st, [&] {
     k_quantize<T><<<grid, 256, 0, st>>>(ds->qmeta, total, coeff, ds->marks, ds->qz,
-                                        ds->qz + (h->L + 1), (int64_t)dict_size, prep_huffman, q,
-                                        (unsigned long long *)ocount, oidx, oval,
-                                        (unsigned long long)ocap);
+                                        ds->qz + (h->L + 1), (int64_t)qo.dict_size, qo.prep_huffman, qo.q,
+                                        (unsigned long long *)qo.ocount, qo.oidx, qo.oval,
+                                        (unsigned long long)qo.ocap);
   });
 }
 
@@ -2614,6 +2607,41 @@ template <typename T> struct LdOut {
   }
 };
 
+// ---- what a decomposition + quantization reads and makes: the descriptors of decompose_quantize()
+// below (QuantOut, the integers: beside QuantParams) --------------------------------------------------
+// The error bound.
+struct Bound {
+  int ebtype;
+  double tol, s;
+};
+
+// The norm a REL bound is relative to.
+struct NormSource {
+  enum Kind {
+    None,    // ABS bound: none involved
+    Host,    // host: given by the caller (> 0)
+    Device,  // device: the caller's pointer (T), never read on the host
+    Compute  // REL without a norm: reduced here, or taken from the streamed slot (mgh_norm_stream_*)
+  } kind;
+  double host;
+  const void *device;
+  int decomposed;      // Device: the norm of a decomposed domain of nsub subdomains (a global norm)
+  uint64_t nsub;
+  double *h_norm_out;  // or NULL: the norm that was used (Compute: one synchronisation at the end)
+};
+
+// Where the coefficients go as well, if anywhere (coeff == nullptr: nowhere).
+struct CoeffOut {
+  void *coeff;
+  Layout lay;
+};
+
+inline int outlier_args(const QuantOut &qo) {
+  if (qo.prep_huffman && (!qo.ocount || (qo.ocap && (!qo.oidx || !qo.oval))))
+    return fail(MGH_ERR_INVALID_ARGUMENT, "outlier buffers required with prep_huffman");
+  return MGH_SUCCESS;
+}
+
 // ---- the stages on arrays of any layout ---------------------------------------------------------
 template <typename T>
 int decompose_impl(mgh_hierarchy *h, const T *data, Layout in, T *coeff, Layout out, hipStream_t st) {
@@ -2635,12 +2663,11 @@ int recompose_impl(mgh_hierarchy *h, const T *coeff, Layout in, T *data, Layout 
 
 // (the integers are always dense)
 template <typename T>
-int quantize_impl(mgh_hierarchy *h, const T *coeff, Layout in, int ebtype, double tol, double s, double norm,
-                  uint64_t dict_size, int prep_huffman, int64_t *q, uint64_t *ocount,
-                  uint64_t *oidx, int64_t *oval, uint64_t ocap, hipStream_t st) {
+int quantize_impl(mgh_hierarchy *h, const T *coeff, Layout in, const Bound &b, double norm, const QuantOut &qo,
+                  hipStream_t st) {
   TRY(ld_pack<T>(h, coeff, in, false, st));
-  TRY(upload_quantizers<T>(h, ebtype, tol, s, norm, true, st));
-  return quantize_launch<T>(h, coeff, dict_size, prep_huffman, q, ocount, oidx, oval, ocap, st);
+  TRY(upload_quantizers<T>(h, b.ebtype, b.tol, b.s, norm, true, st));
+  return quantize_launch<T>(h, coeff, qo, st);
 }
 
 template <typename T>
@@ -2651,151 +2678,122 @@ int dequantize_impl(mgh_hierarchy *h, int64_t *q, const QuantSpec &qs, T *coeff,
   return o.finish(h, st);
 }
 
-template <typename T>
-int fused_q_entry(mgh_hierarchy *h, const T *data, Layout in, int ebtype, double tol, double s, double norm,
-                  uint64_t dict_size, int prep_huffman, int64_t *q, uint64_t *ocount,
-                  uint64_t *oidx, int64_t *oval, uint64_t ocap, hipStream_t st) {
-  TRY(ld_pack<T>(h, data, in, true, st));
-  QuantParams<T> qp = make_quant_params<T>(h, ebtype, tol, s, norm, true);
-  qp.dict_size = (int64_t)dict_size;
-  qp.prep_huffman = prep_huffman;
-  qp.q = q;
-  qp.ocount = (unsigned long long *)ocount;
-  qp.oidx = oidx;
-  qp.oval = oval;
-  qp.ocap = ocap;
-  return decompose_fused<T, OUT_Q>(h, data, in, nullptr, &qp, st);
+// The norm k_make_qparams left in ds->normval, on the host: one synchronisation.
+template <typename T> int read_back_norm(mgh_hierarchy *h, double *out, hipStream_t st) {
+  T nv = 0;
+  HIP_TRY(hipMemcpyAsync(&nv, DS<T>(h)->normval, sizeof(T), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  *out = (double)nv;
+  return MGH_SUCCESS;
 }
 
-// Same with the norm (and hence the quantizers) never leaving the device: d_norm given, or
-// computed here (REL). h_norm_out != NULL costs one synchronisation at the END of the call.
+// ---- the decomposition + quantization core --------------------------------------------------------
+// Everything behind mgh_decompose_quantize{,_sym16,_dn}: `data` to the integers `qo` within `b`, the
+// coefficients to `co` as well if wanted. The route:
+//   - no coefficient output, a shape the fused level kernels take, dict_size <= 2^30 (they test the
+//     dictionary range in 32 bits): one fused pass;
+//   - else staged on dense arrays: the coefficients go to `co` (through a dense copy if it is pitched)
+//     or to scratch_full, and the quantizer reads them there.
+// The quantizer table: built on the host from a norm the host has (none, or given) for the int64
+// output; made on the device by k_make_qparams when the norm is there (computed here, the caller's
+// pointer) and for 16-bit symbols (a given norm is uploaded first) -- no host round trip inside the
+// call, ns.h_norm_out costs one synchronisation at the END (mgh_norm + mgh_quantize were two round
+// trips, 35 us each on the 5-D step).
 template <typename T>
-int fused_q_entry_device(mgh_hierarchy *h, const T *data, Layout in, int ebtype, double tol, double s,
-                         const T *d_norm, int decomposed, uint64_t nsub, double *h_norm_out,
-                         uint64_t dict_size, int prep_huffman, int64_t *q, uint64_t *ocount,
-                         uint64_t *oidx, int64_t *oval, uint64_t ocap, hipStream_t st,
-                         uint16_t *q16 = nullptr) {
+int decompose_quantize(mgh_hierarchy *h, const T *data, Layout in, const Bound &b, const NormSource &ns,
+                       const QuantOut &qo, const CoeffOut &co, hipStream_t st) {
   auto *ds = DS<T>(h);
-  TRY(ld_pack<T>(h, data, in, true, st));
-  // (mgh_norm_stream_*: the reduction is in the slot already; anything else the caller passes
-  // alongside -- a given norm, an ABS bound -- overrides it)
-  const bool streamed = ds->norm_streamed && !d_norm && ebtype == MGH_REL;
+  const bool inf = (T)b.s == std::numeric_limits<T>::infinity();
+  TRY(outlier_args(qo));
+  if (qo.sym16 && (qo.dict_size == 0 || qo.dict_size > 65536))
+    return fail(MGH_ERR_INVALID_ARGUMENT, "dict_size must be in 1..65536");
+  if (qo.sym16 && !fused_route(h))
+    return fail(MGH_ERR_UNSUPPORTED_DIMENSION, "16-bit symbols: only on the fused 3-D / 4-D path");
+  if (ns.kind == NormSource::Device && !fused_route(h))
+    return fail(MGH_ERR_UNSUPPORTED_DIMENSION, "device-norm entry point needs the fused 3-D / 4-D path");
+  const bool fused = !co.coeff && fused_route(h) && qo.dict_size <= ((uint64_t)1 << 30);
+  if (ns.kind == NormSource::Device && !fused)
+    return fail(MGH_ERR_INVALID_ARGUMENT, "fused path: dict_size must be at most 2^30");
+  // mgh_norm_stream_*: the reduction is in the slot already, for a fused call that would reduce by
+  // itself. Any other call drops it (fscal_dirty stays set: the next fused call zeroes the slots).
+  const bool streamed = ds->norm_streamed && fused && ns.kind == NormSource::Compute;
   ds->norm_streamed = false;
-  const bool need_norm = !d_norm && ebtype == MGH_REL && !streamed;
-  // The norm scalar has two slots used alternately: this call reduces into scalar[slot] (zero on
-  // entry) and k_make_qparams zeroes the other one for the next call, together with the outlier
-  // counter -- two memset launches less per step.
-  if (ds->fscal_dirty && !streamed) HIP_TRY(hipMemsetAsync(ds->fscal, 0, 16, st));
-  ds->fscal_dirty = true;
-  unsigned long long *slot = ds->fscal + ds->scalar_slot;
-  unsigned long long *other = ds->fscal + (1 - ds->scalar_slot);
-  if (need_norm) {
-    // all but the last MGH_ABSMAX_WARM_MB of the input with nontemporal loads: the level pass
-    // re-reads the input from its end, and only what the norm pass read last can still be in
-    // the 256 MB memory-side cache (512^3 f32, same box, 60 steps each: absmax 109 -> 93 us,
-    // top-level pass 384 -> 397 us, step 0.894 -> 0.889 ms)
-    const size_t total = h->total, warm = ((size_t)h->absmax_warm_mb << 20) / sizeof(T);
-    if (in.pitched)  // (read in place: row by row)
-      TRY(norm_reduce<T>(h, data, s, slot, &in.view, 0, st));
-    else
-      TRY(norm_reduce<T>(h, data, s, slot, nullptr, total > warm ? total - warm : 0, st));
-  }
-  auto qparams = [&] {
-    QParamArgs<T> P;
-    TRY(fill_qparam_args<T>(h, d_norm, ebtype, tol, s, decomposed, nsub, ocount, P));
-    P.scalar = slot;
-    P.zero_next = other;
-    TRY(launch(h, "make_qparams", st, [&] { k_make_qparams<T><<<1, 64, 0, st>>>(P); }));
-    ds->scalar_slot = 1 - ds->scalar_slot;
-    ds->fscal_dirty = false;
-    return (int)MGH_SUCCESS;
-  };
-  QuantParams<T> qp;
-  qp.d_qp = ds->qz;
-  qp.dict_size = (int64_t)dict_size;
-  qp.prep_huffman = prep_huffman;
-  qp.q = q;
-  qp.q16 = q16;
-  qp.ocount = (unsigned long long *)ocount;
-  qp.oidx = oidx;
-  qp.oval = oval;
-  qp.ocap = ocap;
-  TRY((decompose_fused<T, OUT_Q>(h, data, in, nullptr, &qp, st, qparams)));
-  if (h_norm_out) {
-    T nv = 0;
-    HIP_TRY(hipMemcpyAsync(&nv, ds->normval, sizeof(T), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    *h_norm_out = (double)nv;
-  }
-  return MGH_SUCCESS;
-}
+  const bool device_table = ns.kind == NormSource::Compute || ns.kind == NormSource::Device || qo.sym16;
+  if (ns.kind != NormSource::Compute && ns.h_norm_out) *ns.h_norm_out = ns.host;  // (given, or none involved)
 
-// REL bound without a norm on the shapes the fused level kernels do not take (D = 5, thin boxes ...):
-// norm, quantizer table, decomposition and quantizer queued one behind the other -- the norm and the
-// table stay on the device as in fused_q_entry_device (mgh_norm + mgh_quantize were two host round
-// trips, 35 us each on the 5-D step). h_norm_out != NULL: one synchronisation at the END.
-template <typename T>
-int staged_q_entry_device(mgh_hierarchy *h, const T *data, int ebtype, double tol, double s, double *h_norm_out,
-                          uint64_t dict_size, int prep_huffman, int64_t *q, uint64_t *ocount, uint64_t *oidx,
-                          int64_t *oval, uint64_t ocap, T *coeff, hipStream_t st) {
-  auto *ds = DS<T>(h);
-  TRY(norm_launch<T>(h, data, dense_layout(h), s, st));
-  TRY(make_qparams_launch<T>(h, nullptr, ebtype, tol, s, 0, 1, nullptr, st));
-  ds->qmeta.calc_vol = ((T)s == std::numeric_limits<T>::infinity()) ? 0 : 1;
-  TRY(decompose_dense<T>(h, data, coeff, st));
-  TRY(quantize_launch<T>(h, coeff, dict_size, prep_huffman, q, ocount, oidx, oval, ocap, st));
-  if (h_norm_out) {
-    T nv;
-    HIP_TRY(hipMemcpyAsync(&nv, ds->normval, sizeof(T), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    *h_norm_out = (double)nv;
-  }
-  return MGH_SUCCESS;
-}
-
-inline int outlier_args(int prep_huffman, const uint64_t *ocount, const uint64_t *oidx, const int64_t *oval,
-                        uint64_t ocap) {
-  if (prep_huffman && (!ocount || (ocap && (!oidx || !oval))))
-    return fail(MGH_ERR_INVALID_ARGUMENT, "outlier buffers required with prep_huffman");
-  return MGH_SUCCESS;
-}
-
-// mgh_decompose_quantize. Without a coefficient output, on the shapes the fused level kernels take:
-// one fused pass. Else staged on dense arrays: the coefficients go to `coeff` (through a dense copy
-// if it is pitched) or to scratch_full, and the quantizer reads them there.
-template <typename T>
-int decompose_quantize(mgh_hierarchy *h, const T *data, Layout in, int ebtype, double tol, double s, double norm,
-                       double *h_norm_out, uint64_t dict_size, int prep_huffman, int64_t *q, uint64_t *ocount,
-                       uint64_t *oidx, int64_t *oval, uint64_t ocap, T *coeff, Layout out, hipStream_t st) {
-  TRY(outlier_args(prep_huffman, ocount, oidx, oval, ocap));
-  // REL without a norm: the norm and the quantizers stay on the device, no host round trip inside the call
-  const bool device_norm = ebtype == MGH_REL && !(norm > 0);
-  if (!device_norm && h_norm_out) *h_norm_out = norm;
-  // (the fused level kernels test the dictionary range in 32 bits: larger dictionaries are staged)
-  if (!coeff && fusedc_ok(h) && !h->force_v1 && dict_size <= ((uint64_t)1 << 30)) {
-    if (device_norm)
-      return fused_q_entry_device<T>(h, data, in, ebtype, tol, s, nullptr, 0, 1, h_norm_out, dict_size, prep_huffman,
-                                     q, ocount, oidx, oval, ocap, st);
-    if (ocount) HIP_TRY(hipMemsetAsync(ocount, 0, sizeof(uint64_t), st));
-    return fused_q_entry<T>(h, data, in, ebtype, tol, s, norm, dict_size, prep_huffman, q, ocount, oidx, oval, ocap, st);
-  }
-  TRY(ld_pack<T>(h, data, in, false, st));
-  LdOut<T> o;
-  TRY(o.begin(h, coeff, out, false));
-  if (!coeff) {
-    TRY(ensure_scratch<T>(h));
-    coeff = DS<T>(h)->scratch_full;
-    if (coeff == data) return fail(MGH_ERR_INVALID_ARGUMENT, "aliasing");
-  }
-  if (device_norm) {
-    TRY(staged_q_entry_device<T>(h, data, ebtype, tol, s, h_norm_out, dict_size, prep_huffman, q, ocount, oidx, oval,
-                                 ocap, coeff, st));
+  if (fused) {
+    TRY(ld_pack<T>(h, data, in, true, st));
+    QuantParams<T> qp;
+    qp.out = qo;
+    const T *d_norm = (const T *)ns.device;
+    unsigned long long *slot = nullptr, *other = nullptr;
+    if (!device_table) {
+      if (qo.ocount) HIP_TRY(hipMemsetAsync(qo.ocount, 0, sizeof(uint64_t), st));  // (else k_make_qparams does it)
+      host_quant_table<T>(h, b.ebtype, b.tol, b.s, ns.host, qp);
+    } else {
+      if (ns.kind == NormSource::Host) {
+        const T nv = (T)ns.host;
+        HIP_TRY(hipMemcpyAsync(ds->normval, &nv, sizeof(T), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        d_norm = ds->normval;
+      }
+      qp.d_qp = ds->qz;
+      // The norm scalar has two slots used alternately: this call reduces into scalar[slot] (zero on
+      // entry) and k_make_qparams zeroes the other one for the next call, together with the outlier
+      // counter -- two memset launches less per step.
+      if (ds->fscal_dirty && !streamed) HIP_TRY(hipMemsetAsync(ds->fscal, 0, 16, st));
+      ds->fscal_dirty = true;
+      slot = ds->fscal + ds->scalar_slot;
+      other = ds->fscal + (1 - ds->scalar_slot);
+    }
+    if (ns.kind == NormSource::Compute && !streamed) {
+      // all but the last MGH_ABSMAX_WARM_MB of the input with nontemporal loads: the level pass
+      // re-reads the input from its end, and only what the norm pass read last can still be in
+      // the 256 MB memory-side cache (512^3 f32, same box, 60 steps each: absmax 109 -> 93 us,
+      // top-level pass 384 -> 397 us, step 0.894 -> 0.889 ms)
+      const size_t total = h->total, warm = ((size_t)h->absmax_warm_mb << 20) / sizeof(T);
+      if (in.pitched)  // (read in place: row by row)
+        TRY(norm_reduce<T>(h, data, b.s, slot, &in.view, 0, st));
+      else
+        TRY(norm_reduce<T>(h, data, b.s, slot, nullptr, total > warm ? total - warm : 0, st));
+    }
+    // (issued right in front of the first launch that reads the table)
+    auto table = [&]() -> int {
+      if (!device_table) return MGH_SUCCESS;
+      QParamArgs<T> P;
+      TRY(fill_qparam_args<T>(h, d_norm, b.ebtype, b.tol, b.s, ns.decomposed, ns.nsub, qo.ocount, P));
+      P.scalar = slot;
+      P.zero_next = other;
+      TRY(launch(h, "make_qparams", st, [&] { k_make_qparams<T><<<1, 64, 0, st>>>(P); }));
+      ds->scalar_slot = 1 - ds->scalar_slot;
+      ds->fscal_dirty = false;
+      return MGH_SUCCESS;
+    };
+    TRY((decompose_fused<T, OUT_Q>(h, data, in, nullptr, &qp, st, table)));
   } else {
+    TRY(ld_pack<T>(h, data, in, false, st));
+    T *coeff = (T *)co.coeff;
+    Layout out = co.lay;
+    LdOut<T> o;
+    TRY(o.begin(h, coeff, out, false));
+    if (!coeff) {
+      TRY(ensure_scratch<T>(h));
+      coeff = ds->scratch_full;
+      if (coeff == data) return fail(MGH_ERR_INVALID_ARGUMENT, "aliasing");
+    }
+    if (device_table) {
+      TRY(norm_launch<T>(h, data, in, b.s, st));
+      TRY(make_qparams_launch<T>(h, nullptr, b.ebtype, b.tol, b.s, 0, 1, nullptr, st));
+      ds->qmeta.calc_vol = inf ? 0 : 1;
+    } else {
+      TRY(upload_quantizers<T>(h, b.ebtype, b.tol, b.s, ns.host, true, st));
+    }
     TRY(decompose_dense<T>(h, data, coeff, st));
-    TRY(quantize_impl<T>(h, coeff, dense_layout(h), ebtype, tol, s, norm, dict_size, prep_huffman, q, ocount, oidx,
-                         oval, ocap, st));
+    TRY(quantize_launch<T>(h, coeff, qo, st));
+    TRY(o.finish(h, st));
   }
-  return o.finish(h, st);
+  if (ns.kind == NormSource::Compute && ns.h_norm_out) return read_back_norm<T>(h, ns.h_norm_out, st);
+  return MGH_SUCCESS;
 }
 
 // the level shapes and level marks the linearisation kernels read (kernels_v1.hpp)
@@ -3194,13 +3192,14 @@ int mgh_quantize(mgh_hierarchy *h, const void *d_coeff, int ebtype, double tol, 
                  uint64_t *d_outlier_count, uint64_t *d_outlier_idx, int64_t *d_outlier_val,
                  uint64_t outlier_capacity, void *stream) {
   if (!h || !d_coeff || !d_quantized) return fail(MGH_ERR_INVALID_ARGUMENT, "null argument");
-  TRY(outlier_args(prep_huffman, d_outlier_count, d_outlier_idx, d_outlier_val, outlier_capacity));
+  const QuantOut qo{dict_size, prep_huffman, d_quantized, nullptr, d_outlier_count, d_outlier_idx, d_outlier_val,
+                    outlier_capacity};
+  TRY(outlier_args(qo));
   HIP_TRY(hipSetDevice(h->device));
   return with_type(h, [&](auto t) {
     using T = decltype(t);
-    return quantize_impl<T>(h, (const T *)d_coeff, caller_layout(h, MGH_LD_IN), ebtype, tol, s, norm, dict_size,
-                            prep_huffman, d_quantized, d_outlier_count, d_outlier_idx, d_outlier_val,
-                            outlier_capacity, (hipStream_t)stream);
+    return quantize_impl<T>(h, (const T *)d_coeff, caller_layout(h, MGH_LD_IN), {ebtype, tol, s}, norm, qo,
+                            (hipStream_t)stream);
   });
 }
 
@@ -3217,6 +3216,22 @@ int mgh_dequantize(mgh_hierarchy *h, int64_t *d_quantized, int ebtype, double to
   });
 }
 
+// The body of mgh_decompose_quantize{,_sym16,_dn}: the core in the hierarchy's data type, on its device.
+static int decompose_quantize_entry(mgh_hierarchy *h, const void *d_data, const Bound &b, const NormSource &ns,
+                                    const QuantOut &qo, void *d_coeff_opt, void *stream) {
+  HIP_TRY(hipSetDevice(h->device));
+  return with_type(h, [&](auto t) {
+    using T = decltype(t);
+    return decompose_quantize<T>(h, (const T *)d_data, caller_layout(h, MGH_LD_IN), b, ns, qo,
+                                 {d_coeff_opt, caller_layout(h, MGH_LD_OUT)}, (hipStream_t)stream);
+  });
+}
+// The norm argument of the host entries: REL with norm > 0 is a given norm, REL without one asks for it.
+static NormSource norm_source(int ebtype, double norm, double *h_norm_out) {
+  const NormSource::Kind k = ebtype != MGH_REL ? NormSource::None : norm > 0 ? NormSource::Host : NormSource::Compute;
+  return {k, norm, nullptr, 0, 1, h_norm_out};
+}
+
 int mgh_decompose_quantize_sym16(mgh_hierarchy *h, const void *d_data, int error_bound_type, double tol,
                                  double s, double norm, double *h_norm_out, uint64_t dict_size,
                                  uint16_t *d_symbols, uint64_t *d_outlier_count,
@@ -3224,32 +3239,13 @@ int mgh_decompose_quantize_sym16(mgh_hierarchy *h, const void *d_data, int error
                                  uint64_t outlier_capacity, void *stream) {
   if (!h || !d_data || !d_symbols || !d_outlier_count || (outlier_capacity && (!d_outlier_idx || !d_outlier_val)))
     return fail(MGH_ERR_INVALID_ARGUMENT, "null argument");
-  if (dict_size == 0 || dict_size > 65536) return fail(MGH_ERR_INVALID_ARGUMENT, "dict_size must be in 1..65536");
-  HIP_TRY(hipSetDevice(h->device));
-  if (!(fusedc_ok(h) && !h->force_v1))
-    return fail(MGH_ERR_UNSUPPORTED_DIMENSION, "16-bit symbols: only on the fused 3-D / 4-D path");
-  hipStream_t st = (hipStream_t)stream;
-  return with_type(h, [&](auto t) -> int {
-    using T = decltype(t);
-    // (the norm and the quantizers stay on the device; a given norm is uploaded first)
-    const bool device_norm = error_bound_type == MGH_REL && !(norm > 0);
-    const T *d_norm = nullptr;
-    if (error_bound_type == MGH_REL && !device_norm) {
-      const T nv = (T)norm;
-      HIP_TRY(hipMemcpyAsync(DS<T>(h)->normval, &nv, sizeof(T), hipMemcpyHostToDevice, st));
-      HIP_TRY(hipStreamSynchronize(st));
-      d_norm = DS<T>(h)->normval;
-    }
-    if (!device_norm && h_norm_out) *h_norm_out = norm;  // (given, or none involved)
-    return fused_q_entry_device<T>(h, (const T *)d_data, caller_layout(h, MGH_LD_IN), error_bound_type, tol, s,
-                                   d_norm, 0, 1, device_norm ? h_norm_out : nullptr, dict_size, 1, nullptr,
-                                   d_outlier_count, d_outlier_idx, d_outlier_val, outlier_capacity, st, d_symbols);
-  });
+  return decompose_quantize_entry(h, d_data, {error_bound_type, tol, s}, norm_source(error_bound_type, norm, h_norm_out),
+                                  {dict_size, 1, nullptr, d_symbols, d_outlier_count, d_outlier_idx, d_outlier_val,
+                                   outlier_capacity},
+                                  nullptr, stream);
 }
 
-int mgh_sym16_supported(const mgh_hierarchy *h) {
-  return h && fusedc_ok(h) && !h->force_v1 ? 1 : 0;
-}
+int mgh_sym16_supported(const mgh_hierarchy *h) { return h && fused_route(h) ? 1 : 0; }
 
 // The body of the reconstruction entry points: the core in the hierarchy's data type, on its device.
 static int reconstruct_entry(mgh_hierarchy *h, const QuantSpec &qs, const IntSource &src, const Target &tg, void *stream) {
@@ -3277,14 +3273,10 @@ int mgh_decompose_quantize(mgh_hierarchy *h, const void *d_data, int error_bound
                            uint64_t *d_outlier_idx, int64_t *d_outlier_val,
                            uint64_t outlier_capacity, void *d_coeff_opt, void *stream) {
   if (!h || !d_data || !d_quantized) return fail(MGH_ERR_INVALID_ARGUMENT, "null argument");
-  HIP_TRY(hipSetDevice(h->device));
-  return with_type(h, [&](auto t) {
-    using T = decltype(t);
-    return decompose_quantize<T>(h, (const T *)d_data, caller_layout(h, MGH_LD_IN), error_bound_type, tol, s, norm,
-                                 h_norm_out, dict_size, prep_huffman, d_quantized, d_outlier_count, d_outlier_idx,
-                                 d_outlier_val, outlier_capacity, (T *)d_coeff_opt, caller_layout(h, MGH_LD_OUT),
-                                 (hipStream_t)stream);
-  });
+  return decompose_quantize_entry(h, d_data, {error_bound_type, tol, s}, norm_source(error_bound_type, norm, h_norm_out),
+                                  {dict_size, prep_huffman, d_quantized, nullptr, d_outlier_count, d_outlier_idx,
+                                   d_outlier_val, outlier_capacity},
+                                  d_coeff_opt, stream);
 }
 
 int mgh_norm_device(mgh_hierarchy *h, const void *d_data, double s, void *d_norm_out,
@@ -3304,7 +3296,7 @@ int mgh_norm_device(mgh_hierarchy *h, const void *d_data, double s, void *d_norm
 
 int mgh_norm_stream_begin(mgh_hierarchy *h, void *stream) {
   if (!h) return fail(MGH_ERR_INVALID_ARGUMENT, "null argument");
-  if (!fusedc_ok(h) || h->force_v1)
+  if (!fused_route(h))
     return fail(MGH_ERR_UNSUPPORTED_DIMENSION, "streamed norm: only in front of the fused 3-D / 4-D path");
   HIP_TRY(hipSetDevice(h->device));
   return with_type(h, [&](auto t) { return norm_stream_begin<decltype(t)>(h, (hipStream_t)stream); });
@@ -3326,17 +3318,11 @@ int mgh_decompose_quantize_dn(mgh_hierarchy *h, const void *d_data, int error_bo
                               uint64_t *d_outlier_count, uint64_t *d_outlier_idx,
                               int64_t *d_outlier_val, uint64_t outlier_capacity, void *stream) {
   if (!h || !d_data || !d_quantized || !d_norm) return fail(MGH_ERR_INVALID_ARGUMENT, "null argument");
-  if (!fusedc_ok(h) || h->force_v1)
-    return fail(MGH_ERR_UNSUPPORTED_DIMENSION, "device-norm entry point needs the fused 3-D / 4-D path");
-  TRY(outlier_args(prep_huffman, d_outlier_count, d_outlier_idx, d_outlier_val, outlier_capacity));
-  HIP_TRY(hipSetDevice(h->device));
-  return with_type(h, [&](auto t) {
-    using T = decltype(t);
-    return fused_q_entry_device<T>(h, (const T *)d_data, caller_layout(h, MGH_LD_IN), error_bound_type, tol, s,
-                                   (const T *)d_norm, 1, num_subdomains, nullptr, dict_size, prep_huffman,
-                                   d_quantized, d_outlier_count, d_outlier_idx, d_outlier_val, outlier_capacity,
-                                   (hipStream_t)stream);
-  });
+  return decompose_quantize_entry(h, d_data, {error_bound_type, tol, s},
+                                  {NormSource::Device, 0, d_norm, 1, num_subdomains, nullptr},
+                                  {dict_size, prep_huffman, d_quantized, nullptr, d_outlier_count, d_outlier_idx,
+                                   d_outlier_val, outlier_capacity},
+                                  nullptr, stream);
 }
 
 int mgh_dequantize_recompose(mgh_hierarchy *h, int64_t *d_quantized, int ebtype, double tol,
