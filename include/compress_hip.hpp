@@ -160,6 +160,16 @@ inline compress_status_type decompress_coarsened(const void *compressed_data, si
   return detail::status(mgh_decompress_coarsened(compressed_data, compressed_size, halvings, &decompressed_data, &c,
                                                  output_pre_allocated ? 1 : 0));
 }
+// EXTENSION: full-grid preview (mgh_decompress_preview). The container after `halvings` coarsenings,
+// every subdomain prolonged back to its own grid: an array of the container's shape and type, placed
+// like decompress places it. halvings = 0 is decompress.
+inline compress_status_type decompress_preview(const void *compressed_data, size_t compressed_size, int halvings,
+                                               void *&decompressed_data, HighLevelConfig config,
+                                               bool output_pre_allocated) {
+  const mgh_config c = detail::to_c(config);
+  return detail::status(mgh_decompress_preview(compressed_data, compressed_size, halvings, &decompressed_data, &c,
+                                               output_pre_allocated ? 1 : 0));
+}
 // shape of the stitched array and the largest number of halvings; halvings < 0: only the latter
 // (shape left empty)
 inline compress_status_type infer_coarsened_shape(const void *compressed_data, size_t compressed_size, int halvings,
@@ -220,6 +230,10 @@ public:
   // the dense array of to_level (above level()), like decompress_level returns it
   compress_status_type refine(int to_level, void *&data, bool output_pre_allocated) {
     return detail::status(mgh_progressive_refine(p_, to_level, &data, output_pre_allocated ? 1 : 0));
+  }
+  // the current level prolonged to the container's own grid (mgh_progressive_preview); the state stays
+  compress_status_type preview(void *&data, bool output_pre_allocated) {
+    return detail::status(mgh_progressive_preview(p_, &data, output_pre_allocated ? 1 : 0));
   }
 
 private:

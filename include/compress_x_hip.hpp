@@ -276,6 +276,17 @@ inline enum compress_status_type decompress_coarsened(const void *compressed_dat
   return detail::status(mgh_decompress_coarsened(compressed_data, compressed_size, halvings, &decompressed_data, &c,
                                                  output_pre_allocated ? 1 : 0));
 }
+// EXTENSION: full-grid preview. The container after `halvings` coarsenings, every subdomain prolonged
+// back to its own grid: an array of the container's shape and type, placed like decompress places it.
+inline enum compress_status_type decompress_preview(const void *compressed_data, size_t compressed_size,
+                                                    int halvings, void *&decompressed_data, Config config,
+                                                    bool output_pre_allocated) {
+  const compress_status_type ok = detail::check(config);
+  if (ok != compress_status_type::Success) return ok;
+  const mgh_config c = detail::to_c(config);
+  return detail::status(mgh_decompress_preview(compressed_data, compressed_size, halvings, &decompressed_data, &c,
+                                               output_pre_allocated ? 1 : 0));
+}
 // shape of the stitched array and the largest number of halvings; halvings < 0: only the latter
 // (shape left empty)
 inline enum compress_status_type infer_coarsened_shape(const void *compressed_data, size_t compressed_size,

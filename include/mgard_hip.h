@@ -289,6 +289,28 @@ int mgh_refine_level(mgh_hierarchy *h, const void *d_coarse, int64_t *d_segment,
                      double tol, double s, double norm, uint64_t dict_size, int prep_huffman,
                      const uint64_t *d_outlier_idx, const int64_t *d_outlier_val, uint64_t outlier_count,
                      int level, void *d_out, void *stream);
+/* Full-grid preview: the dense array of `level` (level_shape(level), as mgh_recompose_to_level and
+ * its siblings write it) prolonged to the hierarchy's own grid. The result is, bit for bit, what
+ * mgh_recompose gives for the reordered array that holds d_level in the corner box of `level` and
+ * zeros everywhere else: with zero coefficients the load vector, the Thomas solves and the
+ * correction are zero, and only the interpolation f, then c, then r of every level above `level`
+ * is left. level in 0 ... l_target (else MGH_ERR_INVALID_ARGUMENT, like a NULL pointer);
+ * level == l_target is a copy. One exception to "bit for bit", on the kernel route below only: a
+ * -0.0 in d_level at a node the finer levels keep is copied, where mgh_recompose subtracts a zero
+ * correction that is -0.0 away from the corners of the level and so gives +0.0 -- the sign of a
+ * zero, nothing else. d_level is NOT modified. d_out: DENSE in the hierarchy's shape --
+ * MGH_LD_OUT is not honoured --, and not d_level.
+ * D = 3 on the fused route: one launch of the prolongation kernel per level above `level`, the
+ * intermediates in the hierarchy's own level buffers; the only pass of the size of the array is
+ * the last launch's streaming write. Every other shape (D <= 2, thin shapes, D = 4, 5,
+ * MGH_FORCE_V1, MGH_FORCE_ND): the level loops of mgh_recompose from level + 1 on over an array of
+ * zeros -- full-sized work, there so that the call has one meaning on every shape. */
+int mgh_prolong(mgh_hierarchy *h, int level, const void *d_level, void *d_out, void *stream);
+/* Developer aid: the launch plan of mgh_prolong's kernel for the level step level - 1 -> level
+ * (1 ... l_target) as six ints: tile TC, TF (coarse nodes along c, f), tiles along f, tiles of an
+ * r-plane, coarse r-planes per workgroup, chunks of the march (the last takes what is left).
+ * MGH_ERR_UNSUPPORTED_DIMENSION where mgh_prolong runs no kernel of its own. */
+int mgh_debug_prolong_plan(const mgh_hierarchy *h, int level, int *out6);
 /* HOST only: index in the finest grid of every node of `level` along `dim`, ascending
  * (level_shape(level)[dim] entries; returns their number, or a negative status). The rule is the
  * hierarchy's own coarsening, level by level: keep every second node and always the last one. With

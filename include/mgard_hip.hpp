@@ -241,6 +241,12 @@ public:
                            outlier_count, level, level_data, queue),
           "RefineLevel");
   }
+  // Full-grid preview (mgh_prolong): the dense array of `level` prolonged to the array's own grid --
+  // Recompose of the coefficient array with everything outside the level's corner box zero.
+  // `full_data` is dense (no leading dimensions); `level_data` is not modified.
+  void Prolong(T *full_data, int level, const T *level_data, void *queue = nullptr) {
+    check(mgh_prolong(hierarchy_->handle(), level, level_data, full_data, queue), "Prolong");
+  }
   void LevelBoxFromLinear(const int64_t *linear, int level, int64_t *box, void *queue = nullptr) {
     check(mgh_level_box_from_linear(hierarchy_->handle(), linear, level, box, queue), "LevelBoxFromLinear");
   }

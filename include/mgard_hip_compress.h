@@ -234,6 +234,22 @@ int mgh_infer_coarsened_nodes(const void *compressed_data, size_t compressed_siz
 int mgh_decompress_coarsened(const void *compressed_data, size_t compressed_size, int halvings,
                              void **decompressed_data, const mgh_config *config, int output_pre_allocated);
 
+/* EXTENSION: full-grid preview. The container after `halvings` coarsenings -- halvings, its range
+ * check, one-subdomain containers and the records decoded exactly as in mgh_decompress_coarsened --
+ * put back on the grid of the data: the output has the shape and type of mgh_infer_shape /
+ * mgh_infer_data_type, in host or device memory like mgh_decompress. Every subdomain is reconstructed
+ * at its level l_target_i - halvings, prolonged inside its own hierarchy to its full shape
+ * (mgh_prolong) and placed where mgh_decompress places it; a device output whose subdomains are
+ * whole slabs of dimension 0 is prolonged into in place. The contract is per subdomain: the result
+ * there is, bit for bit, the recomposition of the subdomain's (dequantized) coefficient array with
+ * everything outside the corner box of that level set to zero -- with the one exception mgh_prolong
+ * has on 3-D subdomains of the fused route: a -0.0 of the level array at a node the next level keeps
+ * stays -0.0 where the recomposition gives +0.0 (the sign of a zero, nothing else). Nothing is interpolated across
+ * subdomain borders. halvings = 0 is mgh_decompress. Of a reorder = 1 container only the heads are
+ * decoded (mgh_last_decompress_stats). */
+int mgh_decompress_preview(const void *compressed_data, size_t compressed_size, int halvings,
+                           void **decompressed_data, const mgh_config *config, int output_pre_allocated);
+
 /* What the last mgh_decompress* call of the calling thread did in its lossless stage (thread-local;
  * zeros before the first call; a failed call leaves what it had counted). Raw records count in
  * subdomains and record_bytes only. */
@@ -387,6 +403,11 @@ int mgh_progressive_open(mgh_progressive **out, const void *compressed_data, siz
                          const mgh_config *config);
 int mgh_progressive_level(const mgh_progressive *p);
 int mgh_progressive_refine(mgh_progressive *p, int to_level, void **data, int output_pre_allocated);
+/* The reader's current level prolonged to the full grid (mgh_prolong): an array of the container's
+ * shape, in the container's memory space or in the caller's buffer. Equal to
+ * mgh_decompress_preview(l_target - level). Needs one refine before it; does not change the reader's
+ * state -- a later refine gives what it would have given. */
+int mgh_progressive_preview(mgh_progressive *p, void **data, int output_pre_allocated);
 void mgh_progressive_close(mgh_progressive *p);
 
 #ifdef __cplusplus

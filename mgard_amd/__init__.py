@@ -33,6 +33,7 @@ SYMBOLS = [
     "mgh_dequantize_recompose_sym16_to_level", "mgh_level_nodes",
     "mgh_level_box_from_linear", "mgh_dequantize_recompose_linear_to_level",
     "mgh_refine_level", "mgh_debug_ipk_plans_read",
+    "mgh_prolong", "mgh_debug_prolong_plan",
 ]
 
 
@@ -110,6 +111,8 @@ def load_library():
     L.mgh_refine_level.argtypes = [vp, vp, vp, C.c_int, C.c_double, C.c_double, C.c_double, u64, C.c_int, vp, vp, u64,
                                    C.c_int, vp, vp]
     L.mgh_level_nodes.argtypes = [vp, C.c_int, C.c_int, u64p, u64]
+    L.mgh_prolong.argtypes = [vp, C.c_int, vp, vp, vp]
+    L.mgh_debug_prolong_plan.argtypes = [vp, C.c_int, C.POINTER(C.c_int)]
     L.mgh_stream_calibrate.argtypes = [C.c_int, vp, vp, vp, u64, C.c_int, C.POINTER(C.c_double), vp]
     _lib = L
     return L
@@ -489,6 +492,36 @@ class Hierarchy:
             int(prep_huffman), C.c_void_p(outlier_idx.data_ptr() if n else 0),
             C.c_void_p(outlier_val.data_ptr() if n else 0), n, level, C.c_void_p(out.data_ptr()), _stream()))
         return out
+
+    def prolong(self, level_array, level, out=None):
+        """mgh_prolong: the dense array of `level` (level_shape(level), not modified) prolonged to the
+        full grid -- recompose() of the coefficient array with everything outside the level's corner
+        box zero. Returns the dense array of the hierarchy's shape (LD_OUT does not apply)."""
+        import torch
+        level = int(level)
+        if 0 <= level <= self.l_target:
+            need = int(np.prod(self.level_shape(level)))
+            if not (level_array.is_cuda and level_array.is_contiguous() and level_array.dtype == self.torch_dtype
+                    and level_array.numel() == need):
+                raise ValueError("level_array: expected the contiguous cuda array of level %d (%d elements)"
+                                 % (level, need))
+        if out is None:
+            out = torch.empty(self.shape, dtype=self.torch_dtype, device=level_array.device)
+        elif not (out.is_cuda and out.is_contiguous() and out.dtype == self.torch_dtype and
+                  out.numel() == self.total):
+            raise ValueError("out: expected a contiguous cuda array of the hierarchy's shape")
+        _check(load_library().mgh_prolong(self._h, level, C.c_void_p(level_array.data_ptr()),
+                                          C.c_void_p(out.data_ptr()), _stream()))
+        return out
+
+    PROLONG_PLAN_FIELDS = ("TC", "TF", "tiles_f", "tiles", "rch", "nchunk")
+
+    def prolong_plan(self, level):
+        """The launch plan of prolong()'s kernel for the level step level - 1 -> level
+        (mgh_debug_prolong_plan): a dict with the keys PROLONG_PLAN_FIELDS."""
+        out = (C.c_int * 6)()
+        _check(load_library().mgh_debug_prolong_plan(self._h, int(level), out))
+        return dict(zip(self.PROLONG_PLAN_FIELDS, [int(x) for x in out]))
 
     # ---- per-kernel timing (HIP events on the launch stream) ----
     def profile(self, enable=True, only=None):

@@ -37,6 +37,8 @@
 #include "kernels_recompose2.hpp"
 #include "kernels_nd.hpp"
 #include "kernels_level.hpp"
+#include "kernels_prolong.hpp"
+#include "prolong_plan.hpp"
 
 namespace {
 
@@ -2403,6 +2405,102 @@ int recompose_to_level_impl(mgh_hierarchy *h, const T *coeff, const Layout &in, 
   });
 }
 
+// ---- prolongation of a level to the full grid (mgh_prolong) ---------------------------------------
+// The plan of the level step l - 1 -> l (prolong_plan.hpp) for this hierarchy's switches.
+template <typename T> ProlongPlan prolong_plan_of(const mgh_hierarchy *h, int l) {
+  return prolong_plan(DS<T>(h)->lt[l].box.m, h->fused_tall != 0);
+}
+
+template <typename T, int TC, int TF>
+int launch_prolong3_t(mgh_hierarchy *h, const ProlongArgs<T> &A, hipStream_t st) {
+  const dim3 grid((unsigned)(A.gxm * ((A.m[1] + TC - 1) / TC)), (unsigned)A.nchunk, 1);
+  return launch(h, "prolong3", st, [&] { k_prolong3<T, TC, TF><<<grid, TC * TF, 0, st>>>(A); });
+}
+
+// Fused 3-D route: one launch per level level + 1 .. l_target, the intermediates in the compact
+// nodal buffers of the level loops, the last launch into `out` (dense, the full array's strides).
+template <typename T>
+int prolong_fused3(mgh_hierarchy *h, int level, const T *lvl, T *out, hipStream_t st) {
+  auto *ds = DS<T>(h);
+  const int L = h->L;
+  const T *coarse = lvl;
+  for (int l = level + 1; l <= L; l++) {
+    const LevelTables<T> &t = ds->lt[l];
+    const Box3 &b = t.box;
+    const ProlongPlan p = prolong_plan_of<T>(h, l);
+    if (p.nchunk > 65535) return fail(MGH_ERR_INVALID_ARGUMENT, "mgh_prolong: slowest extent too long");
+    ProlongArgs<T> A{};
+    for (int k = 0; k < 3; k++) {
+      A.n[k] = (int)b.n[k];
+      A.m[k] = (int)b.m[k];
+      A.ratio[k] = t.ratio[k];
+    }
+    A.coarse = coarse;
+    A.fine = l == L ? out : ds->nodal[l];
+    A.fJ = l == L ? ds->full_J : (size_t)b.n[2];
+    A.fI = l == L ? ds->full_I : (size_t)b.n[1] * b.n[2];
+    A.gxm = p.gxm;
+    A.rch = p.rch;
+    A.nchunk = p.nchunk;
+    if (p.TC == 64) TRY((launch_prolong3_t<T, 64, 4>(h, A, st)));
+    else TRY((launch_prolong3_t<T, 4, 64>(h, A, st)));
+    coarse = A.fine;
+  }
+  return MGH_SUCCESS;
+}
+
+// Every other shape: the level loops the full calls run, from level + 1 on, over coefficients that
+// are all zero. Full-sized (a memset and every pass of the finest levels), there so that the call
+// means the same on every shape.
+template <typename T>
+int prolong_fallback(mgh_hierarchy *h, int level, const T *lvl, T *out, hipStream_t st) {
+  auto *ds = DS<T>(h);
+  auto *hh = HH<T>(h);
+  const int D = h->D, L = h->L;
+  if (D > 3 || h->force_nd) {
+    // the generic N-D loop works in place: zero coefficients, the level's nodal values in its
+    // corner box (in the reordered layout the corner box of a level IS its nodal array)
+    HIP_TRY(hipMemsetAsync(out, 0, h->total * sizeof(T), st));
+    size_t ms[MGH_MAX_DIM], fs[MGH_MAX_DIM];
+    uint64_t m5[MGH_MAX_DIM], n5[MGH_MAX_DIM];
+    for (int k = 0; k < MGH_MAX_DIM; k++) {
+      const int d = k - (MGH_MAX_DIM - D);
+      m5[k] = d >= 0 ? hh->level_shape[level][d] : 1;
+      n5[k] = d >= 0 ? hh->shape[d] : 1;
+    }
+    compact_strides(MGH_MAX_DIM, m5, ms);
+    compact_strides(MGH_MAX_DIM, n5, fs);
+    const dim3 blk(64, 4, 1);
+    for (uint64_t a = 0; a < m5[0]; a++)
+      for (uint64_t b = 0; b < m5[1]; b++) {
+        const T *src = lvl + a * ms[0] + b * ms[1];
+        T *dst = out + a * fs[0] + b * fs[1];
+        TRY(launch(h, "copy_box", st, [&] {
+          k_copy_box<T><<<grid3((uint32_t)m5[2], (uint32_t)m5[3], (uint32_t)m5[4], blk), blk, 0, st>>>(
+              (uint32_t)m5[2], (uint32_t)m5[3], (uint32_t)m5[4], src, ms[2], ms[3], dst, fs[2], fs[3]);
+        }));
+      }
+    return recompose_nd<T>(h, out, st, -1, level + 1);
+  }
+  // one thread per element (D <= 3): the node restore reads the coefficients while it writes the
+  // output, so the zeros are an array of their own; the level's values go where the loop expects
+  // the corrected nodes of level `level`
+  TRY(ensure_scratch<T>(h));
+  HIP_TRY(hipMemsetAsync(ds->scratch_full, 0, h->total * sizeof(T), st));
+  TRY(coarse_in<T>(h, ds->nodal[level], lvl, level, st));
+  return recompose_v1_levels<T>(h, ds->scratch_full, ds->full_I, ds->full_J, out, L, st, level + 1);
+}
+
+template <typename T>
+int prolong_impl(mgh_hierarchy *h, int level, const T *lvl, T *out, hipStream_t st) {
+  if (level == h->L) {
+    HIP_TRY(hipMemcpyAsync(out, lvl, h->total * sizeof(T), hipMemcpyDeviceToDevice, st));
+    return MGH_SUCCESS;
+  }
+  if (fused_route(h) && h->D == 3) return prolong_fused3<T>(h, level, lvl, out, st);
+  return prolong_fallback<T>(h, level, lvl, out, st);
+}
+
 // ---- kernels on pitched arrays (Layout::view) ----------------------------------------------------
 __device__ __forceinline__ uint64_t ld_row_offset(const LdView &V, uint64_t row) {
   uint64_t r = row, off = 0;
@@ -3418,6 +3516,29 @@ int mgh_refine_level(mgh_hierarchy *h, const void *d_coarse, int64_t *d_segment,
     return fail(MGH_ERR_INVALID_ARGUMENT, "mgh_refine_level: d_out must not alias an input");
   return reconstruct_entry(h, {ebtype, tol, s, norm, dict_size, prep_huffman, d_outlier_idx, d_outlier_val, outlier_count},
                            {IntSource::Linear, d_segment, nullptr}, {level, level, d_coarse, d_out, dense_layout(h)}, stream);
+}
+
+// The dense array of `level` prolonged to the full grid: what mgh_recompose gives for the reordered
+// array that holds the level in its corner box and zeros everywhere else.
+int mgh_prolong(mgh_hierarchy *h, int level, const void *d_level, void *d_out, void *stream) {
+  if (!h || !d_level || !d_out) return fail(MGH_ERR_INVALID_ARGUMENT, "null argument");
+  if (d_out == d_level) return fail(MGH_ERR_INVALID_ARGUMENT, "mgh_prolong: d_out must not be d_level");
+  TRY(level_arg(h, level));
+  HIP_TRY(hipSetDevice(h->device));
+  return with_type(h, [&](auto t) {
+    using T = decltype(t);
+    return prolong_impl<T>(h, level, (const T *)d_level, (T *)d_out, (hipStream_t)stream);
+  });
+}
+
+int mgh_debug_prolong_plan(const mgh_hierarchy *h, int level, int *out6) {
+  if (!h || !out6) return fail(MGH_ERR_INVALID_ARGUMENT, "null argument");
+  if (level < 1 || level > h->L) return fail(MGH_ERR_INVALID_ARGUMENT, "level outside 1 .. l_target");
+  if (!(fused_route(h) && h->D == 3)) return fail(MGH_ERR_UNSUPPORTED_DIMENSION, "mgh_prolong runs no kernel of its own on this shape");
+  const ProlongPlan p = with_type(h, [&](auto t) { return prolong_plan_of<decltype(t)>(h, level); });
+  const int v[6] = {p.TC, p.TF, p.gxm, p.ntile, p.rch, p.nchunk};
+  std::copy(v, v + 6, out6);
+  return MGH_SUCCESS;
 }
 
 int mgh_dequantize_recompose_sym16_to_level(mgh_hierarchy *h, const uint16_t *d_symbols, int error_bound_type,

@@ -1938,6 +1938,7 @@ struct Lane {
   hipStream_t st = nullptr;
   DevBuf q, q2, ocount, oidx, oval;  // q2: level-linearised copy (config.reorder == 1)
   DevBuf sub;                        // decompression: the dense subdomain when the output is not written in place
+  DevBuf lvl;                        // full-grid preview: the dense array of the subdomain's level, before it is prolonged
   PinBuf pin;                        // [0, 8) size prefix of a raw record, [16, 24) norm read-back
   mgh_lossless_ctx *ll = nullptr;
   uint64_t ocap = 0;                 // elements oidx / oval hold
@@ -1948,6 +1949,7 @@ struct Lane {
     oidx.release();
     oval.release();
     sub.release();
+    lvl.release();
     pin.release();
     if (ll) mgh_lossless_destroy(ll);
     ll = nullptr;
@@ -2824,13 +2826,20 @@ struct SubdomainPlan {
   std::vector<uint64_t> ext, off;
   uint64_t n = 0, n_out = 0;  // elements of the subdomain and of its box
   bool linear_head = false;   // the level is made from the head of a reorder = 1 record alone
+  // full-grid preview: the level's dense array (n_level elements) is prolonged inside the subdomain's
+  // own hierarchy (mgh_prolong) to the whole subdomain, which is what fills the box
+  bool prolong = false;
+  uint64_t n_level = 0;
 };
 
 // level >= 0: mgh_decompress_level -- the output is the dense array of that level of the hierarchy.
 // halvings > 0: mgh_decompress_coarsened -- every subdomain at its level l_target_i - halvings, stitched.
+// ... and preview: mgh_decompress_preview -- every subdomain at that level, prolonged to its full shape and
+// placed where mgh_decompress places it; nothing is interpolated across subdomain borders.
 template <typename T>
 int decompress_impl(const fmt::Header &hd, size_t meta_size, const void *compressed, size_t csize_total,
-                    void **out, const mgh_config &cfg_in, bool prealloc, int level = -1, int halvings = -1) {
+                    void **out, const mgh_config &cfg_in, bool prealloc, int level = -1, int halvings = -1,
+                    bool preview = false) {
   mgh_config cfg = cfg_in;
   const int dtype = hd.is_double ? MGH_DOUBLE : MGH_FLOAT;
   const size_t elem = sizeof(T);
@@ -2853,14 +2862,22 @@ int decompress_impl(const fmt::Header &hd, size_t meta_size, const void *compres
     StitchedLayout sl;
     HL_TRY(stitched_layout(dd, cfg.max_larget_level, halvings, sl));
     if (halvings > 0) {
-      dshape = sl.shape;
+      if (!preview) dshape = sl.shape;
       for (uint64_t id = 0; id < dd.num; id++) {
         const auto sid = dd.dim_subdomain_id(id), sshape = dd.subdomain_shape(id);
         SubdomainPlan &P = plan[id];
         P.level = mgh::hierarchy_l_target(sshape.size(), sshape.data(), cfg.max_larget_level) - halvings;
-        for (int d = 0; d < dd.D; d++) {
-          P.ext.push_back(sl.ext[d][sid[d]]);
-          P.off.push_back(sl.off[d][sid[d]]);
+        P.n_level = 1;
+        for (int d = 0; d < dd.D; d++) P.n_level *= sl.ext[d][sid[d]];
+        if (preview) {
+          P.prolong = true;
+          P.ext = sshape;
+          P.off = dd.subdomain_offset(id);
+        } else {
+          for (int d = 0; d < dd.D; d++) {
+            P.ext.push_back(sl.ext[d][sid[d]]);
+            P.off.push_back(sl.off[d][sid[d]]);
+          }
         }
         P.linear_head = hd.reorder != 0;  // (level < l_target)
       }
@@ -2869,6 +2886,7 @@ int decompress_impl(const fmt::Header &hd, size_t meta_size, const void *compres
   size_t total = 1;
   for (uint64_t e : dshape) total *= e;
   uint64_t sub_elems = 0, q_elems = 0, q2_elems = 0;  // what a lane's buffers hold: the maxima over the subdomains
+  uint64_t lvl_elems = 0;
   bool all_slabs = true;  // every box spans every dimension but the slowest: a contiguous run of the output
   const uint64_t hblock = std::max<uint64_t>(hd.huff_block_size, 1);
   for (uint64_t id = 0; id < dd.num; id++) {
@@ -2882,10 +2900,12 @@ int decompress_impl(const fmt::Header &hd, size_t meta_size, const void *compres
     for (uint64_t e : P.ext) P.n_out *= e;
     for (int d = 1; d < dd.D; d++) all_slabs = all_slabs && P.ext[d] == dshape[d];
     sub_elems = std::max(sub_elems, P.n_out);
-    // A level below l_target of a level-linearised (reorder = 1) record: its first n_out integers are
+    if (!P.prolong) P.n_level = P.n_out;  // (the box IS the level's array)
+    else lvl_elems = std::max(lvl_elems, P.n_level);
+    // A level below l_target of a level-linearised (reorder = 1) record: its first n_level integers are
     // the box of the level -- only the chunks that hold them are decoded, and the level is made from
     // that head; nothing on the way is sized by the subdomain.
-    q_elems = std::max(q_elems, P.linear_head ? std::min<uint64_t>(P.n, ((P.n_out - 1) / hblock + 1) * hblock) : P.n);
+    q_elems = std::max(q_elems, P.linear_head ? std::min<uint64_t>(P.n, ((P.n_level - 1) / hblock + 1) * hblock) : P.n);
     if (hd.reorder && !P.linear_head) q2_elems = std::max(q2_elems, P.n);
   }
   HL_TRY(cache_prepare(cfg.dev_id));
@@ -2941,6 +2961,7 @@ int decompress_impl(const fmt::Header &hd, size_t meta_size, const void *compres
     for (int l = 0; l < nlanes; l++) {
       Lane &L = g_cache.lane[l];
       if (!zero_copy) HL_TRY(L.sub.ensure(sub_elems * elem));
+      if (lvl_elems) HL_TRY(L.lvl.ensure(lvl_elems * elem));
       HL_TRY(L.q.ensure(q_elems * 8));
       if (q2_elems) HL_TRY(L.q2.ensure(q2_elems * 8));
     }
@@ -3011,14 +3032,18 @@ int decompress_impl(const fmt::Header &hd, size_t meta_size, const void *compres
     if (level >= 0 && level > mgh_l_target(h)) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "level outside 0 .. l_target");
     if (halvings > 0 && level != mgh_l_target(h) - halvings)
       return hl_fail(MGH_ERR_FORMAT, "header: the hierarchy of the subdomain is not the header's");
+    // (full-grid preview: the level into the lane's own buffer, then prolonged to the dense subdomain)
+    void *made = P.prolong ? L.lvl.p : sub;
     if (rv.raw) {  // (the finest level is the data)
       if (level == mgh_l_target(h)) return copy_any(sub, rv.rec, rv.csize, st);
       // (q: the head of a reorder = 1 record is all the lane holds otherwise)
       HL_TRY(raw_record_integers(h, rv, qp, L.q2, L.q, n, st));
-      return mgh_dequantize_recompose_to_level(h, (int64_t *)L.q.p, qp.eb, qp.tol, qp.s, qp.norm, qp.dict, 0, nullptr,
-                                               nullptr, 0, level, sub, st);
+      HL_TRY(mgh_dequantize_recompose_to_level(h, (int64_t *)L.q.p, qp.eb, qp.tol, qp.s, qp.norm, qp.dict, 0, nullptr,
+                                               nullptr, 0, level, made, st));
+    } else {
+      HL_TRY(reconstruct_record(h, L.ll, L.q, L.q2, qp, rv, n, level, P.linear_head, P.n_level, q_elems, made, st));
     }
-    return reconstruct_record(h, L.ll, L.q, L.q2, qp, rv, n, level, P.linear_head, P.n_out, q_elems, sub, st);
+    return P.prolong ? mgh_prolong(h, level, made, sub, st) : (int)MGH_SUCCESS;
   };
   auto finish = [&](uint64_t id) -> int {
     if (zero_copy) return MGH_SUCCESS;
@@ -3111,7 +3136,15 @@ int mgh_compress(int D, int dtype, const uint64_t *shape, double tol, double s, 
 
 static int decompress_entry(const void *compressed_data, size_t compressed_size, void **decompressed_data,
                             const mgh_config *config, int output_pre_allocated, size_t expect_bytes, int expect_dtype,
-                            int level = -1, int halvings = -1);
+                            int level = -1, int halvings = -1, bool preview = false);
+
+int mgh_decompress_preview(const void *compressed_data, size_t compressed_size, int halvings, void **decompressed_data,
+                           const mgh_config *config, int output_pre_allocated) {
+  if (halvings < 0)
+    return hl_fail(MGH_ERR_INVALID_ARGUMENT, "halvings outside 0 .. the smallest l_target of the subdomains");
+  return decompress_entry(compressed_data, compressed_size, decompressed_data, config, output_pre_allocated, 0, -1, -1,
+                          halvings, true);
+}
 
 int mgh_decompress_coarsened(const void *compressed_data, size_t compressed_size, int halvings, void **decompressed_data,
                              const mgh_config *config, int output_pre_allocated) {
@@ -3144,7 +3177,7 @@ int mgh_decompress_into(const void *compressed_data, size_t compressed_size, voi
 // header the call reads anyway, before anything is written (mgh_decompress_into)
 static int decompress_entry(const void *compressed_data, size_t compressed_size, void **decompressed_data,
                             const mgh_config *config, int output_pre_allocated, size_t expect_bytes, int expect_dtype,
-                            int level, int halvings) {
+                            int level, int halvings, bool preview) {
   decompress_stats() = mgh_decompress_stats{};
   if (!compressed_data || !decompressed_data) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "NULL argument");
   if (output_pre_allocated && !*decompressed_data) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "pre-allocated output is NULL");
@@ -3178,9 +3211,9 @@ static int decompress_entry(const void *compressed_data, size_t compressed_size,
   try {
     if (hd.is_double)
       return decompress_impl<double>(hd, meta_size, compressed_data, compressed_size, decompressed_data,
-                                     *config, output_pre_allocated != 0, level, halvings);
+                                     *config, output_pre_allocated != 0, level, halvings, preview);
     return decompress_impl<float>(hd, meta_size, compressed_data, compressed_size, decompressed_data,
-                                  *config, output_pre_allocated != 0, level, halvings);
+                                  *config, output_pre_allocated != 0, level, halvings, preview);
   } catch (const std::exception &e) {
     return hl_fail(MGH_ERR_DEVICE, e.what());
   }
@@ -4480,6 +4513,7 @@ struct mgh_progressive {
   DevBuf state[2];         // state[si]: the dense array of `level`
   int si = 0;
   DevBuf lin;              // a raw record: all its level-linearised integers (made at open)
+  DevBuf full;             // mgh_progressive_preview into host memory: the full-grid array on its way out
 };
 
 namespace {
@@ -4487,7 +4521,7 @@ void progressive_free(mgh_progressive *p) {
   if (!p) return;
   (void)hipSetDevice(p->cfg.dev_id);
   if (p->st) (void)hipStreamSynchronize(p->st);
-  for (DevBuf *b : {&p->q[0], &p->q[1], &p->state[0], &p->state[1], &p->lin}) b->release();
+  for (DevBuf *b : {&p->q[0], &p->q[1], &p->state[0], &p->state[1], &p->lin, &p->full}) b->release();
   if (p->h) mgh_hierarchy_destroy(p->h);
   if (p->ll) mgh_lossless_destroy(p->ll);
   if (p->st) (void)hipStreamDestroy(p->st);
@@ -4634,6 +4668,34 @@ int progressive_refine(mgh_progressive *p, int to, void **out, bool prealloc) {
   }
   return rc;
 }
+
+// The current level prolonged to the full grid; reads the state, changes none of it (the level
+// buffers of the hierarchy it passes through are scratch between the calls).
+int progressive_preview(mgh_progressive *p, void **out, bool prealloc) {
+  hipStream_t st = p->st;
+  const size_t out_bytes = p->n * p->elem;
+  const bool raw_full = p->rv.raw && p->level == p->L;  // (a raw record IS the finest level: no state)
+  if (!prealloc) {
+    if (p->in_dev) HL_HIP(hipMalloc(out, out_bytes));
+    else if (!(*out = host_alloc_large(out_bytes))) return hl_fail(MGH_ERR_OUT_OF_MEMORY, "malloc");
+  }
+  int rc = MGH_SUCCESS;
+  if (raw_full) {
+    rc = copy_any(*out, p->rv.rec, out_bytes, st);
+  } else if (is_device_pointer(*out)) {
+    rc = mgh_prolong(p->h, p->level, p->state[p->si].p, *out, st);
+  } else {
+    rc = p->full.ensure(out_bytes);
+    if (rc == MGH_SUCCESS) rc = mgh_prolong(p->h, p->level, p->state[p->si].p, p->full.p, st);
+    if (rc == MGH_SUCCESS) rc = copy_any(*out, p->full.p, out_bytes, st);
+  }
+  if (rc == MGH_SUCCESS && hipStreamSynchronize(st) != hipSuccess) rc = hl_fail(MGH_ERR_DEVICE, "sync");
+  if (rc != MGH_SUCCESS && !prealloc) {
+    if (p->in_dev) (void)hipFree(*out); else std::free(*out);
+    *out = nullptr;
+  }
+  return rc;
+}
 }  // namespace
 
 extern "C" {
@@ -4680,6 +4742,19 @@ int mgh_progressive_refine(mgh_progressive *p, int to_level, void **data, int ou
   if (hipSetDevice(p->cfg.dev_id) != hipSuccess) return hl_fail(MGH_ERR_DEVICE, "hipSetDevice");
   try {
     return progressive_refine(p, to_level, data, output_pre_allocated != 0);
+  } catch (const std::exception &e) {
+    return hl_fail(MGH_ERR_DEVICE, e.what());
+  }
+}
+
+int mgh_progressive_preview(mgh_progressive *p, void **data, int output_pre_allocated) {
+  if (!p || !data) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (output_pre_allocated && !*data) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "pre-allocated output is NULL");
+  if (p->level < 0)
+    return hl_fail(MGH_ERR_INVALID_ARGUMENT, "mgh_progressive_preview: nothing refined yet (call mgh_progressive_refine first)");
+  if (hipSetDevice(p->cfg.dev_id) != hipSuccess) return hl_fail(MGH_ERR_DEVICE, "hipSetDevice");
+  try {
+    return progressive_preview(p, data, output_pre_allocated != 0);
   } catch (const std::exception &e) {
     return hl_fail(MGH_ERR_DEVICE, e.what());
   }

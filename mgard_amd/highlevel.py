@@ -29,6 +29,7 @@ HL_SYMBOLS = [
     "mgh_lossless_decompress_range", "mgh_infer_level_range", "mgh_progressive_open",
     "mgh_progressive_level", "mgh_progressive_refine", "mgh_progressive_close",
     "mgh_infer_coarsened_shape", "mgh_infer_coarsened_nodes", "mgh_decompress_coarsened",
+    "mgh_decompress_preview", "mgh_progressive_preview",
 ]
 
 
@@ -121,6 +122,7 @@ def _hl():
     L.mgh_infer_coarsened_shape.argtypes = [vp, C.c_size_t, vp, C.c_int, vp, vp, vp]
     L.mgh_infer_coarsened_nodes.argtypes = [vp, C.c_size_t, vp, C.c_int, C.c_int, vp, u64]
     L.mgh_decompress_coarsened.argtypes = [vp, C.c_size_t, C.c_int, C.POINTER(vp), vp, C.c_int]
+    L.mgh_decompress_preview.argtypes = [vp, C.c_size_t, C.c_int, C.POINTER(vp), vp, C.c_int]
     L.mgh_dist_use_library.argtypes = [C.c_char_p]
     L.mgh_compress_dist.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(u64), C.c_double,
                                     C.c_double, C.c_int, vp, C.POINTER(vp), C.POINTER(C.c_size_t), vp, vp, C.c_int]
@@ -159,6 +161,7 @@ def _hl():
     L.mgh_progressive_open.argtypes = [C.POINTER(vp), vp, C.c_size_t, vp]
     L.mgh_progressive_level.argtypes = [vp]
     L.mgh_progressive_refine.argtypes = [vp, C.c_int, C.POINTER(vp), C.c_int]
+    L.mgh_progressive_preview.argtypes = [vp, C.POINTER(vp), C.c_int]
     L.mgh_progressive_close.argtypes = [vp]
     L.mgh_progressive_close.restype = None
     L.mgh_last_decompress_stats.argtypes = [C.POINTER(DecompressStats)]
@@ -453,6 +456,33 @@ class Progressive:
         _check(_hl().mgh_progressive_refine(self._p, int(level), C.byref(optr), 1))
         return out
 
+    def preview(self, out=None):
+        """mgh_progressive_preview: the current level prolonged to the container's own grid -- an array
+        of infer(buf)[0], equal to decompress_preview(buf, l_target - level). Needs one
+        refine before it and leaves the reader's state as it is."""
+        import torch
+        if not self._p:
+            raise MgardHipError("the reader is closed")
+        shape, _ = infer(self._buf)
+        if self._on_dev:
+            want = torch.float32 if self._dt == FLOAT else torch.float64
+            if out is None:
+                out = torch.empty(shape, dtype=want, device=self._buf.device)
+            if not (isinstance(out, torch.Tensor) and out.is_cuda and out.is_contiguous() and out.dtype == want and
+                    out.numel() == int(np.prod(shape))):
+                raise ValueError("`out` must be a contiguous cuda tensor of the array's shape and the stream's type")
+            optr = C.c_void_p(out.data_ptr())
+        else:
+            npdt = np.float32 if self._dt == FLOAT else np.float64
+            if out is None:
+                out = np.empty(shape, dtype=npdt)
+            if not (isinstance(out, np.ndarray) and out.flags.c_contiguous and out.flags.writeable and
+                    out.dtype == npdt and out.size == int(np.prod(shape))):
+                raise ValueError("`out` must be a writeable C-contiguous numpy array of the array's shape and type")
+            optr = C.c_void_p(out.ctypes.data)
+        _check(_hl().mgh_progressive_preview(self._p, C.byref(optr), 1))
+        return out
+
     def close(self):
         if self._p:
             _hl().mgh_progressive_close(self._p)
@@ -482,7 +512,23 @@ def decompress(buf, config=None, out=None, level=None, coarsen=None):
     subdomain only.
     `coarsen` (extension): mgh_decompress_coarsened -- every subdomain after that many halvings of its grid,
     stitched into one array of shape infer_coarsened(buf, coarsen)[0]; domain-decomposed containers included.
-    infer_coarsened_nodes tells which nodes of the full grid the result holds."""
+    infer_coarsened_nodes tells which nodes of the full grid the result holds.
+    decompress_preview(buf, k) puts the coarsened subdomains back on the full grid."""
+    return _decompress(buf, config, out, level, coarsen, False)
+
+
+def decompress_preview(buf, coarsen, config=None, out=None):
+    """mgh_decompress_preview (extension): decompress(buf, coarsen=coarsen) with every coarsened subdomain
+    prolonged back to its own grid -- an array of infer(buf)[0], placed like the full decompression; per
+    subdomain the recomposition with every coefficient above its level zero. coarsen = 0 is decompress."""
+    if coarsen is None:
+        raise ValueError("decompress_preview needs `coarsen`")
+    return _decompress(buf, config, out, None, coarsen, True)
+
+
+def _decompress(buf, config, out, level, coarsen, full_grid):
+    """The body of decompress (full_grid = False) and decompress_preview (full_grid = True: mgh_decompress_preview
+    instead of mgh_decompress_coarsened, the output of the full array's shape)."""
     import torch
     if level is not None and coarsen is not None:
         raise ValueError("pass either `level` or `coarsen`, not both")
@@ -497,7 +543,9 @@ def decompress(buf, config=None, out=None, level=None, coarsen=None):
         else:
             if int(coarsen) < 0:
                 raise ValueError("coarsen must be >= 0")
-            shape, _ = infer_coarsened(buf, int(coarsen), cfg)
+            shape, _ = infer_coarsened(buf, int(coarsen), cfg)  # (also refuses more halvings than there are)
+            if full_grid:
+                shape = infer(buf)[0]
         _, dt = infer(buf)
         want = torch.float32 if dt == FLOAT else torch.float64
         if on_dev:
@@ -517,6 +565,8 @@ def decompress(buf, config=None, out=None, level=None, coarsen=None):
             p, n, optr = C.c_void_p(buf.ctypes.data), buf.size, C.c_void_p(out.ctypes.data)
         if level is not None:
             _check(L.mgh_decompress_level(p, n, int(level), C.byref(optr), C.byref(cfg), 1))
+        elif full_grid:
+            _check(L.mgh_decompress_preview(p, n, int(coarsen), C.byref(optr), C.byref(cfg), 1))
         else:
             _check(L.mgh_decompress_coarsened(p, n, int(coarsen), C.byref(optr), C.byref(cfg), 1))
         return out
