@@ -170,6 +170,16 @@ inline compress_status_type decompress_preview(const void *compressed_data, size
   return detail::status(mgh_decompress_preview(compressed_data, compressed_size, halvings, &decompressed_data, &c,
                                                output_pre_allocated ? 1 : 0));
 }
+// ... the box [lo_d, lo_d + ext_d) of it alone (mgh_decompress_preview_window): a dense array of shape ext;
+// subdomains the box does not meet are not opened. lo, ext: one entry per dimension of the array.
+inline compress_status_type decompress_preview_window(const void *compressed_data, size_t compressed_size, int halvings,
+                                                      const std::vector<uint64_t> &lo, const std::vector<uint64_t> &ext,
+                                                      void *&decompressed_data, HighLevelConfig config,
+                                                      bool output_pre_allocated) {
+  const mgh_config c = detail::to_c(config);
+  return detail::status(mgh_decompress_preview_window(compressed_data, compressed_size, halvings, lo.data(), ext.data(),
+                                                      &decompressed_data, &c, output_pre_allocated ? 1 : 0));
+}
 // shape of the stitched array and the largest number of halvings; halvings < 0: only the latter
 // (shape left empty)
 inline compress_status_type infer_coarsened_shape(const void *compressed_data, size_t compressed_size, int halvings,
@@ -234,6 +244,11 @@ public:
   // the current level prolonged to the container's own grid (mgh_progressive_preview); the state stays
   compress_status_type preview(void *&data, bool output_pre_allocated) {
     return detail::status(mgh_progressive_preview(p_, &data, output_pre_allocated ? 1 : 0));
+  }
+  // ... the box [lo_d, lo_d + ext_d) of it alone (mgh_progressive_preview_window)
+  compress_status_type preview_window(const std::vector<uint64_t> &lo, const std::vector<uint64_t> &ext, void *&data,
+                                      bool output_pre_allocated) {
+    return detail::status(mgh_progressive_preview_window(p_, lo.data(), ext.data(), &data, output_pre_allocated ? 1 : 0));
   }
 
 private:

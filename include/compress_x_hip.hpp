@@ -287,6 +287,19 @@ inline enum compress_status_type decompress_preview(const void *compressed_data,
   return detail::status(mgh_decompress_preview(compressed_data, compressed_size, halvings, &decompressed_data, &c,
                                                output_pre_allocated ? 1 : 0));
 }
+// ... the box [lo_d, lo_d + ext_d) of it alone (mgh_decompress_preview_window): a dense array of shape ext;
+// subdomains the box does not meet are not opened. lo, ext: one entry per dimension of the array.
+inline enum compress_status_type decompress_preview_window(const void *compressed_data, size_t compressed_size,
+                                                           int halvings, const std::vector<SIZE> &lo,
+                                                           const std::vector<SIZE> &ext, void *&decompressed_data,
+                                                           Config config, bool output_pre_allocated) {
+  const compress_status_type ok = detail::check(config);
+  if (ok != compress_status_type::Success) return ok;
+  const mgh_config c = detail::to_c(config);
+  const std::vector<uint64_t> l(lo.begin(), lo.end()), e(ext.begin(), ext.end());
+  return detail::status(mgh_decompress_preview_window(compressed_data, compressed_size, halvings, l.data(), e.data(),
+                                                      &decompressed_data, &c, output_pre_allocated ? 1 : 0));
+}
 // shape of the stitched array and the largest number of halvings; halvings < 0: only the latter
 // (shape left empty)
 inline enum compress_status_type infer_coarsened_shape(const void *compressed_data, size_t compressed_size,

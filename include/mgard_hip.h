@@ -311,6 +311,41 @@ int mgh_prolong(mgh_hierarchy *h, int level, const void *d_level, void *d_out, v
  * r-plane, coarse r-planes per workgroup, chunks of the march (the last takes what is left).
  * MGH_ERR_UNSUPPORTED_DIMENSION where mgh_prolong runs no kernel of its own. */
 int mgh_debug_prolong_plan(const mgh_hierarchy *h, int level, int *out6);
+/* Windowed full-grid preview: the box W = [lo_d, lo_d + ext_d) per dimension (indices of the full
+ * array; ext_d >= 1, lo_d + ext_d <= shape_d; lo and ext are uint64_t[D] on the HOST) of what
+ * mgh_prolong writes for the same h, level and d_level, bit for bit -- mgh_prolong's -0.0 exception
+ * included, the crop has it too. d_level: the WHOLE dense array of `level`, exactly what mgh_prolong
+ * takes; NOT modified. d_out: DENSE in ext (MGH_LD_OUT is not honoured), and not d_level. A NULL
+ * pointer, a level outside 0 ... l_target, ext_d == 0 or lo_d + ext_d > shape_d:
+ * MGH_ERR_INVALID_ARGUMENT, nothing launched, d_out untouched. level == l_target is a box copy.
+ * D = 3 on the fused route: prolongation is local (a node of level l depends on at most two nodes
+ * per dimension of level l - 1), so one launch of the window kernel per level above `level` runs
+ * over the cells under the window only. The first reads d_level in place, the intermediates live
+ * in window-sized buffers of the hierarchy (grown on demand, counted in mgh_device_bytes); no
+ * allocation, memset or pass is proportional to the array. Every other shape (D <= 2, thin shapes,
+ * D = 4, 5, MGH_FORCE_V1, MGH_FORCE_ND): mgh_prolong into a full-sized array of the hierarchy, and
+ * a box copy of the window out of it -- full-sized work, there so that the call has one meaning on
+ * every shape. */
+int mgh_prolong_window(mgh_hierarchy *h, int level, const void *d_level, const uint64_t *lo, const uint64_t *ext,
+                       void *d_out, void *stream);
+/* ... into a sub-box of a larger array: d_out points at the element the window's first node goes
+ * to, out_stride (uint64_t[D] on the host) are the element strides of that array; the fastest one
+ * must be 1. (mgh_decompress_preview_window writes a device-resident output this way.) */
+int mgh_prolong_window_strided(mgh_hierarchy *h, int level, const void *d_level, const uint64_t *lo,
+                               const uint64_t *ext, void *d_out, const uint64_t *out_stride, void *stream);
+/* HOST only, no device work: the nodes mgh_prolong_window's result depends on. For every level
+ * l = level ... l_target and every dimension d the closed range of real node indices of level l,
+ * out[(l - level) * 2 * D + 2 * d] = first, [... + 1] = last; the ranges of l_target are the window
+ * itself. Returns the number of integers written ((l_target - level + 1) * 2 * D <= cap) or a
+ * negative status. */
+int mgh_debug_prolong_window_ranges(const mgh_hierarchy *h, int level, const uint64_t *lo, const uint64_t *ext,
+                                    int64_t *out, uint64_t cap);
+/* Developer aid: the launch plan of the window kernel for the step l - 1 -> l
+ * (level < l <= l_target) of that window as twelve ints: the six of mgh_debug_prolong_plan, then
+ * the first cell and the number of cells per dimension (r, c, f).
+ * MGH_ERR_UNSUPPORTED_DIMENSION where mgh_prolong_window runs no kernel of its own. */
+int mgh_debug_prolong_window_plan(const mgh_hierarchy *h, int level, const uint64_t *lo, const uint64_t *ext, int l,
+                                  int *out12);
 /* HOST only: index in the finest grid of every node of `level` along `dim`, ascending
  * (level_shape(level)[dim] entries; returns their number, or a negative status). The rule is the
  * hierarchy's own coarsening, level by level: keep every second node and always the last one. With

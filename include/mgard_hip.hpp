@@ -247,6 +247,14 @@ public:
   void Prolong(T *full_data, int level, const T *level_data, void *queue = nullptr) {
     check(mgh_prolong(hierarchy_->handle(), level, level_data, full_data, queue), "Prolong");
   }
+  // ... the box [lo_d, lo_d + ext_d) of it alone (mgh_prolong_window): `window_data` is dense in ext;
+  // `level_data` is the whole level array, as for Prolong. On the fused 3-D route the work is the window's.
+  void ProlongWindow(T *window_data, int level, const T *level_data, const std::vector<SIZE> &lo,
+                     const std::vector<SIZE> &ext, void *queue = nullptr) {
+    const std::vector<uint64_t> l(lo.begin(), lo.end()), e(ext.begin(), ext.end());
+    check(mgh_prolong_window(hierarchy_->handle(), level, level_data, l.data(), e.data(), window_data, queue),
+          "ProlongWindow");
+  }
   void LevelBoxFromLinear(const int64_t *linear, int level, int64_t *box, void *queue = nullptr) {
     check(mgh_level_box_from_linear(hierarchy_->handle(), linear, level, box, queue), "LevelBoxFromLinear");
   }

@@ -250,6 +250,22 @@ int mgh_decompress_coarsened(const void *compressed_data, size_t compressed_size
 int mgh_decompress_preview(const void *compressed_data, size_t compressed_size, int halvings,
                            void **decompressed_data, const mgh_config *config, int output_pre_allocated);
 
+/* EXTENSION: windowed full-grid preview. The box W = [lo_d, lo_d + ext_d) per dimension (indices of
+ * the array of mgh_infer_shape; lo and ext hold one uint64_t per dimension on the host; ext_d >= 1,
+ * lo_d + ext_d <= shape_d, else MGH_ERR_INVALID_ARGUMENT) of what mgh_decompress_preview writes for the
+ * same container and halvings, bit for bit: a dense array of shape ext, in host or device memory by
+ * the rules of mgh_decompress_preview; the range check on halvings is the same. A subdomain whose box
+ * does not meet W is not opened: nothing of it is decoded, none of its record bytes are moved (its
+ * 8-byte size prefix is read, to find the next record), and it does not count in
+ * mgh_last_decompress_stats, whose `subdomains` is the number of subdomains reconstructed. A
+ * subdomain that meets W is reconstructed at l_target_i - halvings exactly as for the full preview,
+ * and its part of W is written by mgh_prolong_window of its own hierarchy -- straight into a
+ * device-resident output, else through a window-sized buffer. halvings = 0 is the crop of
+ * mgh_decompress, with the same skipping. Nothing is interpolated across subdomain borders. */
+int mgh_decompress_preview_window(const void *compressed_data, size_t compressed_size, int halvings, const uint64_t *lo,
+                                  const uint64_t *ext, void **decompressed_data, const mgh_config *config,
+                                  int output_pre_allocated);
+
 /* What the last mgh_decompress* call of the calling thread did in its lossless stage (thread-local;
  * zeros before the first call; a failed call leaves what it had counted). Raw records count in
  * subdomains and record_bytes only. */
@@ -408,6 +424,10 @@ int mgh_progressive_refine(mgh_progressive *p, int to_level, void **data, int ou
  * mgh_decompress_preview(l_target - level). Needs one refine before it; does not change the reader's
  * state -- a later refine gives what it would have given. */
 int mgh_progressive_preview(mgh_progressive *p, void **data, int output_pre_allocated);
+/* ... the box [lo_d, lo_d + ext_d) of it (mgh_prolong_window): a dense array of shape ext, bit for bit
+ * the crop of mgh_progressive_preview. The reader's state is untouched. */
+int mgh_progressive_preview_window(mgh_progressive *p, const uint64_t *lo, const uint64_t *ext, void **data,
+                                   int output_pre_allocated);
 void mgh_progressive_close(mgh_progressive *p);
 
 #ifdef __cplusplus

@@ -34,6 +34,8 @@ SYMBOLS = [
     "mgh_level_box_from_linear", "mgh_dequantize_recompose_linear_to_level",
     "mgh_refine_level", "mgh_debug_ipk_plans_read",
     "mgh_prolong", "mgh_debug_prolong_plan",
+    "mgh_prolong_window", "mgh_prolong_window_strided", "mgh_debug_prolong_window_ranges",
+    "mgh_debug_prolong_window_plan",
 ]
 
 
@@ -113,6 +115,10 @@ def load_library():
     L.mgh_level_nodes.argtypes = [vp, C.c_int, C.c_int, u64p, u64]
     L.mgh_prolong.argtypes = [vp, C.c_int, vp, vp, vp]
     L.mgh_debug_prolong_plan.argtypes = [vp, C.c_int, C.POINTER(C.c_int)]
+    L.mgh_prolong_window.argtypes = [vp, C.c_int, vp, u64p, u64p, vp, vp]
+    L.mgh_prolong_window_strided.argtypes = [vp, C.c_int, vp, u64p, u64p, vp, u64p, vp]
+    L.mgh_debug_prolong_window_ranges.argtypes = [vp, C.c_int, u64p, u64p, i64p, u64]
+    L.mgh_debug_prolong_window_plan.argtypes = [vp, C.c_int, u64p, u64p, C.c_int, C.POINTER(C.c_int)]
     L.mgh_stream_calibrate.argtypes = [C.c_int, vp, vp, vp, u64, C.c_int, C.POINTER(C.c_double), vp]
     _lib = L
     return L
@@ -493,10 +499,12 @@ class Hierarchy:
             C.c_void_p(outlier_val.data_ptr() if n else 0), n, level, C.c_void_p(out.data_ptr()), _stream()))
         return out
 
-    def prolong(self, level_array, level, out=None):
+    def prolong(self, level_array, level, out=None, window=None):
         """mgh_prolong: the dense array of `level` (level_shape(level), not modified) prolonged to the
         full grid -- recompose() of the coefficient array with everything outside the level's corner
-        box zero. Returns the dense array of the hierarchy's shape (LD_OUT does not apply)."""
+        box zero. Returns the dense array of the hierarchy's shape (LD_OUT does not apply).
+        window = (lo, ext): mgh_prolong_window -- the box [lo, lo + ext) of that array alone, a dense
+        array of shape ext; on the fused 3-D route the work is that of the window, not of the array."""
         import torch
         level = int(level)
         if 0 <= level <= self.l_target:
@@ -505,6 +513,17 @@ class Hierarchy:
                     and level_array.numel() == need):
                 raise ValueError("level_array: expected the contiguous cuda array of level %d (%d elements)"
                                  % (level, need))
+        if window is not None:
+            lo, ext = self._window(window)
+            shape = tuple(int(e) for e in ext)
+            if out is None:
+                out = torch.empty(shape, dtype=self.torch_dtype, device=level_array.device)
+            elif not (out.is_cuda and out.is_contiguous() and out.dtype == self.torch_dtype and
+                      out.numel() == int(np.prod(shape))):
+                raise ValueError("out: expected a contiguous cuda array of the window's shape")
+            _check(load_library().mgh_prolong_window(self._h, level, C.c_void_p(level_array.data_ptr()), lo, ext,
+                                                     C.c_void_p(out.data_ptr()), _stream()))
+            return out
         if out is None:
             out = torch.empty(self.shape, dtype=self.torch_dtype, device=level_array.device)
         elif not (out.is_cuda and out.is_contiguous() and out.dtype == self.torch_dtype and
@@ -513,6 +532,36 @@ class Hierarchy:
         _check(load_library().mgh_prolong(self._h, level, C.c_void_p(level_array.data_ptr()),
                                           C.c_void_p(out.data_ptr()), _stream()))
         return out
+
+    def _window(self, window):
+        """(lo, ext) as two uint64 arrays of the hierarchy's dimension (the library checks the values)."""
+        lo, ext = window
+        D = len(self.shape)
+        if len(lo) != D or len(ext) != D or min(lo) < 0 or min(ext) < 0:
+            raise ValueError("window: (lo, ext) with one non-negative integer per dimension each")
+        return (C.c_uint64 * D)(*[int(x) for x in lo]), (C.c_uint64 * D)(*[int(x) for x in ext])
+
+    def prolong_window_ranges(self, level, lo, ext):
+        """mgh_debug_prolong_window_ranges (host only): the nodes prolong(..., window=(lo, ext)) depends on --
+        a list over the levels level .. l_target of D pairs (first, last) of node indices of that level."""
+        lo, ext = self._window((lo, ext))
+        D = len(self.shape)
+        cap = (self.l_target + 1) * 2 * D
+        out = (C.c_int64 * cap)()
+        n = _check(load_library().mgh_debug_prolong_window_ranges(self._h, int(level), lo, ext, out, cap))
+        return [[(int(out[k * 2 * D + 2 * d]), int(out[k * 2 * D + 2 * d + 1])) for d in range(D)]
+                for k in range(n // (2 * D))]
+
+    PROLONG_WINDOW_PLAN_FIELDS = ("TC", "TF", "tiles_f", "tiles", "rch", "nchunk", "J0_r", "J0_c", "J0_f",
+                                  "cells_r", "cells_c", "cells_f")
+
+    def prolong_window_plan(self, level, lo, ext, step):
+        """The launch plan of the window kernel for the step `step` - 1 -> `step` of that window
+        (mgh_debug_prolong_window_plan): a dict with the keys PROLONG_WINDOW_PLAN_FIELDS."""
+        lo, ext = self._window((lo, ext))
+        out = (C.c_int * 12)()
+        _check(load_library().mgh_debug_prolong_window_plan(self._h, int(level), lo, ext, int(step), out))
+        return dict(zip(self.PROLONG_WINDOW_PLAN_FIELDS, [int(x) for x in out]))
 
     PROLONG_PLAN_FIELDS = ("TC", "TF", "tiles_f", "tiles", "rch", "nchunk")
 

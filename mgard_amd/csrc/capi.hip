@@ -38,7 +38,9 @@
 #include "kernels_nd.hpp"
 #include "kernels_level.hpp"
 #include "kernels_prolong.hpp"
+#include "kernels_prolong_win.hpp"
 #include "prolong_plan.hpp"
+#include "prolong_window_plan.hpp"
 
 namespace {
 
@@ -184,6 +186,12 @@ template <typename T> struct DeviceState {
   T *level_box = nullptr;          // compact coefficients of the corner box of a stop level (mgh_*_to_level; grown on demand)
   size_t level_box_elems = 0;
   T *scratch_full = nullptr;       // lazily allocated full-size copy
+  // mgh_prolong_window: the window's part of two consecutive levels (grown on demand, sized by the
+  // window), and on the shapes without a window kernel the full-grid array the window is cut from
+  T *win[2] = {nullptr, nullptr};
+  size_t win_elems[2] = {0, 0};
+  T *win_full = nullptr;
+  size_t win_full_elems = 0;
   T *qz = nullptr;                 // 2*(L+1): quantizers, volumes
   unsigned long long *scalar = nullptr;  // 8-byte device scalar (norm / counters)
   // fused device-norm path: fscal[slot] is zero on entry, the other slot is zeroed by
@@ -450,6 +458,9 @@ template <typename T> void destroy_state(mgh_hierarchy *h) {
     (void)hipFree(ds->t2);
     (void)hipFree(ds->t3);
     (void)hipFree(ds->scratch_full);
+    (void)hipFree(ds->win[0]);
+    (void)hipFree(ds->win[1]);
+    (void)hipFree(ds->win_full);
     (void)hipFree(ds->pack_in);
     (void)hipFree(ds->pack_out);
     (void)hipFree(ds->nd_w);
@@ -2501,6 +2512,131 @@ int prolong_impl(mgh_hierarchy *h, int level, const T *lvl, T *out, hipStream_t 
   return prolong_fallback<T>(h, level, lvl, out, st);
 }
 
+// ---- the window form (mgh_prolong_window) -----------------------------------------------------------
+template <typename T, int TC, int TF>
+int launch_prolong3_win_t(mgh_hierarchy *h, const ProlongWinArgs<T> &A, hipStream_t st) {
+  const dim3 grid((unsigned)(A.gxm * ((A.nJ[1] + TC - 1) / TC)), (unsigned)A.nchunk, 1);
+  return launch(h, "prolong3_win", st, [&] { k_prolong3_win<T, TC, TF><<<grid, TC * TF, 0, st>>>(A); });
+}
+
+// dst (element strides ds[0 .. D), a box of extents ext) <- the box at `lo` of the dense array src of
+// extents shape; D <= 5, the two slowest dimensions of the 5-D view on the host as in prolong_fallback
+template <typename T>
+int copy_window(mgh_hierarchy *h, int D, const uint64_t *shape, const T *src, const uint64_t *lo, const uint64_t *ext,
+                T *dst, const uint64_t *dstr, hipStream_t st) {
+  uint64_t n5[MGH_MAX_DIM], l5[MGH_MAX_DIM], e5[MGH_MAX_DIM], d5[MGH_MAX_DIM];
+  size_t ss[MGH_MAX_DIM];
+  for (int k = 0; k < MGH_MAX_DIM; k++) {
+    const int d = k - (MGH_MAX_DIM - D);
+    n5[k] = d >= 0 ? shape[d] : 1;
+    l5[k] = d >= 0 ? lo[d] : 0;
+    e5[k] = d >= 0 ? ext[d] : 1;
+    d5[k] = d >= 0 ? dstr[d] : 0;
+  }
+  compact_strides(MGH_MAX_DIM, n5, ss);
+  const dim3 blk(64, 4, 1);
+  for (uint64_t a = 0; a < e5[0]; a++)
+    for (uint64_t b = 0; b < e5[1]; b++) {
+      const T *sp = src + (l5[0] + a) * ss[0] + (l5[1] + b) * ss[1] + l5[2] * ss[2] + l5[3] * ss[3] + l5[4];
+      T *dp = dst + a * d5[0] + b * d5[1];
+      TRY(launch(h, "copy_box", st, [&] {
+        k_copy_box<T><<<grid3((uint32_t)e5[2], (uint32_t)e5[3], (uint32_t)e5[4], blk), blk, 0, st>>>(
+            (uint32_t)e5[2], (uint32_t)e5[3], (uint32_t)e5[4], sp, ss[2], ss[3], dp, (size_t)d5[2], (size_t)d5[3]);
+      }));
+    }
+  return MGH_SUCCESS;
+}
+
+// Fused 3-D route: one launch per level level + 1 .. l_target over the cells under the window. The
+// first reads the caller's level array in place, the last writes the box of `out`; in between the
+// window's part of a level lives in ds->win[l & 1].
+template <typename T>
+int prolong_window_fused3(mgh_hierarchy *h, int level, const T *lvl, const std::vector<int64_t> &chain, T *out,
+                          const uint64_t *ostr, hipStream_t st) {
+  auto *ds = DS<T>(h);
+  auto *hh = HH<T>(h);
+  const int L = h->L;
+  auto range = [&](int l, int k, int64_t *a, int64_t *b) {
+    *a = chain[(size_t)(l - level) * 6 + 2 * k];
+    *b = chain[(size_t)(l - level) * 6 + 2 * k + 1];
+  };
+  for (int l = level + 1; l < L; l++) {
+    size_t cnt = 1;
+    for (int k = 0; k < 3; k++) {
+      int64_t a, b;
+      range(l, k, &a, &b);
+      cnt *= (size_t)(b - a + 1);
+    }
+    TRY(grow(h, &ds->win[l & 1], &ds->win_elems[l & 1], cnt));
+  }
+  const T *src = lvl;
+  size_t sI = (size_t)(hh->level_shape[level][1] * hh->level_shape[level][2]), sJ = (size_t)hh->level_shape[level][2];
+  {
+    int64_t a[3], b[3];
+    for (int k = 0; k < 3; k++) range(level, k, &a[k], &b[k]);
+    src += (size_t)a[0] * sI + (size_t)a[1] * sJ + (size_t)a[2];
+  }
+  for (int l = level + 1; l <= L; l++) {
+    const LevelTables<T> &t = ds->lt[l];
+    int64_t ca[3], cb[3], fa[3], fb[3];
+    for (int k = 0; k < 3; k++) {
+      range(l - 1, k, &ca[k], &cb[k]);
+      range(l, k, &fa[k], &fb[k]);
+    }
+    const ProlongWinPlan w = prolong_window_plan(t.box.n, fa, fb, h->fused_tall != 0);
+    if (w.p.nchunk > 65535) return fail(MGH_ERR_INVALID_ARGUMENT, "mgh_prolong_window: slowest extent too long");
+    ProlongWinArgs<T> A{};
+    for (int k = 0; k < 3; k++) {
+      A.n[k] = (int)t.box.n[k];
+      A.m[k] = (int)t.box.m[k];
+      A.ratio[k] = t.ratio[k];
+      A.c0[k] = (int)ca[k];
+      A.sm[k] = (int)(cb[k] - ca[k] + 1);
+      A.d0[k] = (int)fa[k];
+      A.dn[k] = (int)(fb[k] - fa[k] + 1);
+      A.J0[k] = w.J0[k];
+      A.nJ[k] = w.nJ[k];
+    }
+    A.src = src;
+    A.sI = sI;
+    A.sJ = sJ;
+    A.dst = l == L ? out : ds->win[l & 1];
+    A.dI = l == L ? (size_t)ostr[0] : (size_t)A.dn[1] * A.dn[2];
+    A.dJ = l == L ? (size_t)ostr[1] : (size_t)A.dn[2];
+    A.gxm = w.p.gxm;
+    A.rch = w.p.rch;
+    A.nchunk = w.p.nchunk;
+    if (w.p.TC == 64) TRY((launch_prolong3_win_t<T, 64, 4>(h, A, st)));
+    else TRY((launch_prolong3_win_t<T, 4, 64>(h, A, st)));
+    src = A.dst;
+    sI = A.dI;
+    sJ = A.dJ;
+  }
+  return MGH_SUCCESS;
+}
+
+// out_stride == nullptr: dense in ext. On the fused 3-D route the fastest stride must be 1.
+template <typename T>
+int prolong_window_impl(mgh_hierarchy *h, int level, const T *lvl, const uint64_t *lo, const uint64_t *ext, T *out,
+                        const uint64_t *out_stride, hipStream_t st) {
+  auto *ds = DS<T>(h);
+  auto *hh = HH<T>(h);
+  const int D = h->D;
+  std::vector<int64_t> chain;
+  if (!prolong_window_chain(hh->level_shape, level, lo, ext, chain))
+    return fail(MGH_ERR_INVALID_ARGUMENT, "mgh_prolong_window: level or window outside the hierarchy");
+  uint64_t ostr[MGH_MAX_DIM];
+  if (out_stride) std::copy(out_stride, out_stride + D, ostr);
+  else compact_strides(D, ext, ostr);
+  if (ostr[D - 1] != 1) return fail(MGH_ERR_INVALID_ARGUMENT, "mgh_prolong_window: the fastest stride must be 1");
+  if (level == h->L) return copy_window<T>(h, D, hh->shape, lvl, lo, ext, out, ostr, st);
+  if (fused_route(h) && D == 3) return prolong_window_fused3<T>(h, level, lvl, chain, out, ostr, st);
+  // every other shape: the full call into an array of the hierarchy, and the window cut from it
+  TRY(grow(h, &ds->win_full, &ds->win_full_elems, (size_t)h->total));
+  TRY(prolong_impl<T>(h, level, lvl, ds->win_full, st));
+  return copy_window<T>(h, D, hh->shape, ds->win_full, lo, ext, out, ostr, st);
+}
+
 // ---- kernels on pitched arrays (Layout::view) ----------------------------------------------------
 __device__ __forceinline__ uint64_t ld_row_offset(const LdView &V, uint64_t row) {
   uint64_t r = row, off = 0;
@@ -3528,6 +3664,68 @@ int mgh_prolong(mgh_hierarchy *h, int level, const void *d_level, void *d_out, v
   return with_type(h, [&](auto t) {
     using T = decltype(t);
     return prolong_impl<T>(h, level, (const T *)d_level, (T *)d_out, (hipStream_t)stream);
+  });
+}
+
+namespace {
+int prolong_window_entry(mgh_hierarchy *h, int level, const void *d_level, const uint64_t *lo, const uint64_t *ext,
+                         void *d_out, const uint64_t *out_stride, void *stream) {
+  if (!h || !d_level || !d_out || !lo || !ext) return fail(MGH_ERR_INVALID_ARGUMENT, "null argument");
+  if (d_out == d_level) return fail(MGH_ERR_INVALID_ARGUMENT, "mgh_prolong_window: d_out must not be d_level");
+  TRY(level_arg(h, level));
+  HIP_TRY(hipSetDevice(h->device));
+  return with_type(h, [&](auto t) {
+    using T = decltype(t);
+    return prolong_window_impl<T>(h, level, (const T *)d_level, lo, ext, (T *)d_out, out_stride, (hipStream_t)stream);
+  });
+}
+} // namespace
+
+int mgh_prolong_window(mgh_hierarchy *h, int level, const void *d_level, const uint64_t *lo, const uint64_t *ext,
+                       void *d_out, void *stream) {
+  return prolong_window_entry(h, level, d_level, lo, ext, d_out, nullptr, stream);
+}
+
+int mgh_prolong_window_strided(mgh_hierarchy *h, int level, const void *d_level, const uint64_t *lo,
+                               const uint64_t *ext, void *d_out, const uint64_t *out_stride, void *stream) {
+  if (!out_stride) return fail(MGH_ERR_INVALID_ARGUMENT, "null argument");
+  return prolong_window_entry(h, level, d_level, lo, ext, d_out, out_stride, stream);
+}
+
+int mgh_debug_prolong_window_ranges(const mgh_hierarchy *h, int level, const uint64_t *lo, const uint64_t *ext,
+                                    int64_t *out, uint64_t cap) {
+  if (!h || !lo || !ext || !out) return fail(MGH_ERR_INVALID_ARGUMENT, "null argument");
+  std::vector<int64_t> chain;
+  const bool ok = with_type(h, [&](auto t) {
+    return prolong_window_chain(HH<decltype(t)>(h)->level_shape, level, lo, ext, chain);
+  });
+  if (!ok) return fail(MGH_ERR_INVALID_ARGUMENT, "mgh_debug_prolong_window_ranges: level or window outside the hierarchy");
+  if (cap < chain.size()) return fail(MGH_ERR_INVALID_ARGUMENT, "mgh_debug_prolong_window_ranges: out too small");
+  std::copy(chain.begin(), chain.end(), out);
+  return (int)chain.size();
+}
+
+int mgh_debug_prolong_window_plan(const mgh_hierarchy *h, int level, const uint64_t *lo, const uint64_t *ext, int l,
+                                  int *out12) {
+  if (!h || !lo || !ext || !out12) return fail(MGH_ERR_INVALID_ARGUMENT, "null argument");
+  if (!(fused_route(h) && h->D == 3))
+    return fail(MGH_ERR_UNSUPPORTED_DIMENSION, "mgh_prolong_window runs no kernel of its own on this shape");
+  if (l <= level || l > h->L) return fail(MGH_ERR_INVALID_ARGUMENT, "step outside level + 1 .. l_target");
+  return with_type(h, [&](auto t) {
+    using T = decltype(t);
+    std::vector<int64_t> chain;
+    if (!prolong_window_chain(HH<T>(h)->level_shape, level, lo, ext, chain))
+      return fail(MGH_ERR_INVALID_ARGUMENT, "level or window outside the hierarchy");
+    int64_t a[3], b[3];
+    for (int k = 0; k < 3; k++) {
+      a[k] = chain[(size_t)(l - level) * 6 + 2 * k];
+      b[k] = chain[(size_t)(l - level) * 6 + 2 * k + 1];
+    }
+    const ProlongWinPlan w = prolong_window_plan(DS<T>(h)->lt[l].box.n, a, b, h->fused_tall != 0);
+    const int v[12] = {w.p.TC, w.p.TF, w.p.gxm, w.p.ntile, w.p.rch, w.p.nchunk, w.J0[0], w.J0[1], w.J0[2],
+                       w.nJ[0], w.nJ[1], w.nJ[2]};
+    std::copy(v, v + 12, out12);
+    return (int)MGH_SUCCESS;
   });
 }
 

@@ -2830,16 +2830,28 @@ struct SubdomainPlan {
   // own hierarchy (mgh_prolong) to the whole subdomain, which is what fills the box
   bool prolong = false;
   uint64_t n_level = 0;
+  // windowed preview: the subdomain does not meet the window and is not opened; else `wlo` is where
+  // the window's part begins inside the subdomain (ext / off: that part and its place in the window)
+  bool skip = false;
+  std::vector<uint64_t> wlo;
+};
+
+// The box [lo, lo + ext) of the array a windowed preview writes (mgh_decompress_preview_window).
+struct Window {
+  std::vector<uint64_t> lo, ext;
 };
 
 // level >= 0: mgh_decompress_level -- the output is the dense array of that level of the hierarchy.
 // halvings > 0: mgh_decompress_coarsened -- every subdomain at its level l_target_i - halvings, stitched.
 // ... and preview: mgh_decompress_preview -- every subdomain at that level, prolonged to its full shape and
 // placed where mgh_decompress places it; nothing is interpolated across subdomain borders.
+// ... and win: mgh_decompress_preview_window -- the output is the window alone; only the subdomains that
+// meet it are opened, each reconstructed as for the preview and its part of the window written by
+// mgh_prolong_window of its own hierarchy (halvings = 0: the box copy of its finest level).
 template <typename T>
 int decompress_impl(const fmt::Header &hd, size_t meta_size, const void *compressed, size_t csize_total,
                     void **out, const mgh_config &cfg_in, bool prealloc, int level = -1, int halvings = -1,
-                    bool preview = false) {
+                    bool preview = false, const Window *win = nullptr) {
   mgh_config cfg = cfg_in;
   const int dtype = hd.is_double ? MGH_DOUBLE : MGH_FLOAT;
   const size_t elem = sizeof(T);
@@ -2883,6 +2895,35 @@ int decompress_impl(const fmt::Header &hd, size_t meta_size, const void *compres
       }
     }
   }
+  std::vector<uint64_t> order;  // the subdomains the call opens, ascending
+  if (win) {
+    dshape = win->ext;
+    for (uint64_t id = 0; id < dd.num; id++) {
+      SubdomainPlan &P = plan[id];
+      const auto soff = dd.subdomain_offset(id), sshape = dd.subdomain_shape(id);
+      std::vector<uint64_t> wext(dd.D), woff(dd.D);
+      P.wlo.resize(dd.D);
+      for (int d = 0; d < dd.D && !P.skip; d++) {
+        const uint64_t a = std::max(win->lo[d], soff[d]), b = std::min(win->lo[d] + win->ext[d], soff[d] + sshape[d]);
+        P.skip = a >= b;
+        if (P.skip) break;
+        P.wlo[d] = a - soff[d];
+        wext[d] = b - a;
+        woff[d] = a - win->lo[d];
+      }
+      if (P.skip) continue;
+      if (!P.prolong) {  // (halvings = 0: the finest level, whole, is what the window is cut from)
+        P.prolong = true;
+        P.n_level = 1;
+        for (uint64_t e : sshape) P.n_level *= e;
+      }
+      P.ext = wext;
+      P.off = woff;
+    }
+  }
+  for (uint64_t id = 0; id < dd.num; id++)
+    if (!plan[id].skip) order.push_back(id);
+  if (order.empty()) return hl_fail(MGH_ERR_FORMAT, "header: no subdomain under the window");
   size_t total = 1;
   for (uint64_t e : dshape) total *= e;
   uint64_t sub_elems = 0, q_elems = 0, q2_elems = 0;  // what a lane's buffers hold: the maxima over the subdomains
@@ -2891,7 +2932,8 @@ int decompress_impl(const fmt::Header &hd, size_t meta_size, const void *compres
   const uint64_t hblock = std::max<uint64_t>(hd.huff_block_size, 1);
   for (uint64_t id = 0; id < dd.num; id++) {
     SubdomainPlan &P = plan[id];
-    if (P.level < 0) {
+    if (P.skip) continue;
+    if (P.level < 0 && !win) {
       P.ext = dd.subdomain_shape(id);
       P.off = dd.subdomain_offset(id);
     }
@@ -2934,7 +2976,7 @@ int decompress_impl(const fmt::Header &hd, size_t meta_size, const void *compres
     }
   }
   const bool pipelined = env_get("MGH_HL_PIPELINE", 1) != 0;
-  const int nlanes = dd.num > 1 && pipelined ? kLanes : 1;
+  const int nlanes = order.size() > 1 && pipelined ? kLanes : 1;
   mgh_hierarchy *owned_h[kLanes] = {nullptr, nullptr};  // per-subdomain hierarchy (non-uniform grid) of the lane's last job
   auto cleanup = [&](int rc) {
     for (int l = 0; l < kLanes; l++) {
@@ -2954,13 +2996,15 @@ int decompress_impl(const fmt::Header &hd, size_t meta_size, const void *compres
   const uint64_t max_elems = dd.max_subdomain_elems();
   int rc;
   // device-resident output whose subdomains are contiguous slabs: reconstruct them in place
-  const bool zero_copy = is_device_pointer(*out) && all_slabs;
+  const bool zero_copy = !win && is_device_pointer(*out) && all_slabs;
+  // windowed preview into device memory: the window kernel writes the box of the output itself
+  const bool direct = win && is_device_pointer(*out);
   uint64_t slab_inner = 1;  // elements of one plane of the slowest dimension of the output
   for (size_t d = 1; d < dshape.size(); d++) slab_inner *= dshape[d];
   auto ensure_all = [&]() -> int {
     for (int l = 0; l < nlanes; l++) {
       Lane &L = g_cache.lane[l];
-      if (!zero_copy) HL_TRY(L.sub.ensure(sub_elems * elem));
+      if (!zero_copy && !direct) HL_TRY(L.sub.ensure(sub_elems * elem));
       if (lvl_elems) HL_TRY(L.lvl.ensure(lvl_elems * elem));
       HL_TRY(L.q.ensure(q_elems * 8));
       if (q2_elems) HL_TRY(L.q2.ensure(q2_elems * 8));
@@ -2984,10 +3028,20 @@ int decompress_impl(const fmt::Header &hd, size_t meta_size, const void *compres
   // of k); finish(k): the dense subdomain into its box of the output when it was not reconstructed
   // in place (for a pageable host output that copy occupies the host).
   size_t byte_offset = meta_size;
-  auto issue = [&](uint64_t id) -> int {
-    const int lane = (int)(id % nlanes);
+  uint64_t next_id = 0;  // the subdomain whose record begins at byte_offset
+  auto issue = [&](uint64_t k) -> int {
+    const uint64_t id = order[k];
+    const int lane = (int)(k % nlanes);
     Lane &L = g_cache.lane[lane];
     hipStream_t st = L.st;
+    for (; next_id < id; next_id++) {  // (records the window does not meet: their size prefix is all that is read)
+      RecordView skipped = rv_hd;
+      uint64_t sn = 1;
+      for (uint64_t e : dd.subdomain_shape(next_id)) sn *= e;
+      HL_TRY(record_view_at(compressed, csize_total, byte_offset, sn * elem, skipped));
+      byte_offset += 8 + skipped.csize;
+    }
+    next_id = id + 1;
     // what the lane's previous subdomain read from the host (decode tables, record head) and its
     // hierarchy are free again once the lane has drained
     HL_HIP(hipStreamSynchronize(st));
@@ -3023,7 +3077,7 @@ int decompress_impl(const fmt::Header &hd, size_t meta_size, const void *compres
     decompress_stats().subdomains++;
     if (rv.raw) {
       decompress_stats().record_bytes += rv.csize;
-      if (level < 0) return copy_any(sub, rv.rec, rv.csize, st);
+      if (level < 0 && !win) return copy_any(sub, rv.rec, rv.csize, st);
     }
     mgh_hierarchy *h = nullptr;
     bool owned = false;
@@ -3034,7 +3088,9 @@ int decompress_impl(const fmt::Header &hd, size_t meta_size, const void *compres
       return hl_fail(MGH_ERR_FORMAT, "header: the hierarchy of the subdomain is not the header's");
     // (full-grid preview: the level into the lane's own buffer, then prolonged to the dense subdomain)
     void *made = P.prolong ? L.lvl.p : sub;
-    if (rv.raw) {  // (the finest level is the data)
+    if (rv.raw && win && level < 0) {  // (the data, whole: the window is cut from it below)
+      HL_TRY(copy_any(made, rv.rec, rv.csize, st));
+    } else if (rv.raw) {  // (the finest level is the data)
       if (level == mgh_l_target(h)) return copy_any(sub, rv.rec, rv.csize, st);
       // (q: the head of a reorder = 1 record is all the lane holds otherwise)
       HL_TRY(raw_record_integers(h, rv, qp, L.q2, L.q, n, st));
@@ -3043,19 +3099,32 @@ int decompress_impl(const fmt::Header &hd, size_t meta_size, const void *compres
     } else {
       HL_TRY(reconstruct_record(h, L.ll, L.q, L.q2, qp, rv, n, level, P.linear_head, P.n_level, q_elems, made, st));
     }
-    return P.prolong ? mgh_prolong(h, level, made, sub, st) : (int)MGH_SUCCESS;
+    if (!P.prolong) return MGH_SUCCESS;
+    if (!win) return mgh_prolong(h, level, made, sub, st);
+    // the subdomain's part of the window: into its box of a device-resident output through that
+    // array's strides, else dense into the lane's buffer (finish copies it out)
+    uint64_t str[MGH_MAX_DIM];
+    const std::vector<uint64_t> &into = direct ? dshape : P.ext;
+    uint64_t run = 1, at = 0;
+    for (int d = dd.D - 1; d >= 0; d--) {
+      str[d] = run;
+      run *= into[d];
+      if (direct) at += P.off[d] * str[d];
+    }
+    return mgh_prolong_window_strided(h, level < 0 ? mgh_l_target(h) : level, made, P.wlo.data(), P.ext.data(),
+                                      direct ? (void *)((char *)*out + at * elem) : L.sub.p, str, st);
   };
-  auto finish = [&](uint64_t id) -> int {
-    if (zero_copy) return MGH_SUCCESS;
+  auto finish = [&](uint64_t k) -> int {
+    if (zero_copy || direct) return MGH_SUCCESS;
     pretouch.join();
-    Lane &L = g_cache.lane[id % nlanes];
-    return copy_box(plan[id].ext, plan[id].off, dshape, elem, L.sub.p, nullptr, *out, false, L.st);
+    Lane &L = g_cache.lane[k % nlanes];
+    return copy_box(plan[order[k]].ext, plan[order[k]].off, dshape, elem, L.sub.p, nullptr, *out, false, L.st);
   };
   if ((rc = issue(0)) != MGH_SUCCESS) return cleanup(rc);
-  for (uint64_t id = 0; id < dd.num; id++) {
-    if (nlanes > 1 && id + 1 < dd.num && (rc = issue(id + 1)) != MGH_SUCCESS) return cleanup(rc);
-    if ((rc = finish(id)) != MGH_SUCCESS) return cleanup(rc);
-    if (nlanes == 1 && id + 1 < dd.num && (rc = issue(id + 1)) != MGH_SUCCESS) return cleanup(rc);
+  for (uint64_t k = 0; k < order.size(); k++) {
+    if (nlanes > 1 && k + 1 < order.size() && (rc = issue(k + 1)) != MGH_SUCCESS) return cleanup(rc);
+    if ((rc = finish(k)) != MGH_SUCCESS) return cleanup(rc);
+    if (nlanes == 1 && k + 1 < order.size() && (rc = issue(k + 1)) != MGH_SUCCESS) return cleanup(rc);
   }
   for (int l = 0; l < nlanes; l++) {
     if (hipStreamSynchronize(g_cache.lane[l].st) != hipSuccess) return cleanup(hl_fail(MGH_ERR_DEVICE, "sync"));
@@ -3136,7 +3205,8 @@ int mgh_compress(int D, int dtype, const uint64_t *shape, double tol, double s, 
 
 static int decompress_entry(const void *compressed_data, size_t compressed_size, void **decompressed_data,
                             const mgh_config *config, int output_pre_allocated, size_t expect_bytes, int expect_dtype,
-                            int level = -1, int halvings = -1, bool preview = false);
+                            int level = -1, int halvings = -1, bool preview = false, const uint64_t *win_lo = nullptr,
+                            const uint64_t *win_ext = nullptr);
 
 int mgh_decompress_preview(const void *compressed_data, size_t compressed_size, int halvings, void **decompressed_data,
                            const mgh_config *config, int output_pre_allocated) {
@@ -3144,6 +3214,16 @@ int mgh_decompress_preview(const void *compressed_data, size_t compressed_size, 
     return hl_fail(MGH_ERR_INVALID_ARGUMENT, "halvings outside 0 .. the smallest l_target of the subdomains");
   return decompress_entry(compressed_data, compressed_size, decompressed_data, config, output_pre_allocated, 0, -1, -1,
                           halvings, true);
+}
+
+int mgh_decompress_preview_window(const void *compressed_data, size_t compressed_size, int halvings, const uint64_t *lo,
+                                  const uint64_t *ext, void **decompressed_data, const mgh_config *config,
+                                  int output_pre_allocated) {
+  if (!lo || !ext) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (halvings < 0)
+    return hl_fail(MGH_ERR_INVALID_ARGUMENT, "halvings outside 0 .. the smallest l_target of the subdomains");
+  return decompress_entry(compressed_data, compressed_size, decompressed_data, config, output_pre_allocated, 0, -1, -1,
+                          halvings, true, lo, ext);
 }
 
 int mgh_decompress_coarsened(const void *compressed_data, size_t compressed_size, int halvings, void **decompressed_data,
@@ -3177,7 +3257,7 @@ int mgh_decompress_into(const void *compressed_data, size_t compressed_size, voi
 // header the call reads anyway, before anything is written (mgh_decompress_into)
 static int decompress_entry(const void *compressed_data, size_t compressed_size, void **decompressed_data,
                             const mgh_config *config, int output_pre_allocated, size_t expect_bytes, int expect_dtype,
-                            int level, int halvings, bool preview) {
+                            int level, int halvings, bool preview, const uint64_t *win_lo, const uint64_t *win_ext) {
   decompress_stats() = mgh_decompress_stats{};
   if (!compressed_data || !decompressed_data) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "NULL argument");
   if (output_pre_allocated && !*decompressed_data) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "pre-allocated output is NULL");
@@ -3208,12 +3288,21 @@ static int decompress_entry(const void *compressed_data, size_t compressed_size,
     if (expect_bytes != need)
       return hl_fail(MGH_ERR_INVALID_ARGUMENT, "mgh_decompress_into: the buffer does not have the size of the array in the stream");
   }
+  Window window;
+  if (win_lo) {
+    window.lo.assign(win_lo, win_lo + hd.shape.size());
+    window.ext.assign(win_ext, win_ext + hd.shape.size());
+    for (size_t d = 0; d < hd.shape.size(); d++)
+      if (window.ext[d] == 0 || window.lo[d] > hd.shape[d] || window.ext[d] > hd.shape[d] - window.lo[d])
+        return hl_fail(MGH_ERR_INVALID_ARGUMENT, "the window leaves the array");
+  }
+  const Window *win = win_lo ? &window : nullptr;
   try {
     if (hd.is_double)
       return decompress_impl<double>(hd, meta_size, compressed_data, compressed_size, decompressed_data,
-                                     *config, output_pre_allocated != 0, level, halvings, preview);
+                                     *config, output_pre_allocated != 0, level, halvings, preview, win);
     return decompress_impl<float>(hd, meta_size, compressed_data, compressed_size, decompressed_data,
-                                  *config, output_pre_allocated != 0, level, halvings, preview);
+                                  *config, output_pre_allocated != 0, level, halvings, preview, win);
   } catch (const std::exception &e) {
     return hl_fail(MGH_ERR_DEVICE, e.what());
   }
@@ -4514,6 +4603,7 @@ struct mgh_progressive {
   int si = 0;
   DevBuf lin;              // a raw record: all its level-linearised integers (made at open)
   DevBuf full;             // mgh_progressive_preview into host memory: the full-grid array on its way out
+  DevBuf win;              // mgh_progressive_preview_window into host memory: the window on its way out
 };
 
 namespace {
@@ -4521,7 +4611,7 @@ void progressive_free(mgh_progressive *p) {
   if (!p) return;
   (void)hipSetDevice(p->cfg.dev_id);
   if (p->st) (void)hipStreamSynchronize(p->st);
-  for (DevBuf *b : {&p->q[0], &p->q[1], &p->state[0], &p->state[1], &p->lin, &p->full}) b->release();
+  for (DevBuf *b : {&p->q[0], &p->q[1], &p->state[0], &p->state[1], &p->lin, &p->full, &p->win}) b->release();
   if (p->h) mgh_hierarchy_destroy(p->h);
   if (p->ll) mgh_lossless_destroy(p->ll);
   if (p->st) (void)hipStreamDestroy(p->st);
@@ -4696,6 +4786,42 @@ int progressive_preview(mgh_progressive *p, void **out, bool prealloc) {
   }
   return rc;
 }
+
+// ... a window of it (mgh_prolong_window): the same reading of the state, window-sized work on the
+// fused 3-D route.
+int progressive_preview_window(mgh_progressive *p, const uint64_t *lo, const uint64_t *ext, void **out, bool prealloc) {
+  hipStream_t st = p->st;
+  size_t out_bytes = p->elem;
+  for (size_t d = 0; d < p->hd.shape.size(); d++) {
+    if (ext[d] == 0 || lo[d] > p->hd.shape[d] || ext[d] > p->hd.shape[d] - lo[d])
+      return hl_fail(MGH_ERR_INVALID_ARGUMENT, "the window leaves the array");
+    out_bytes *= ext[d];
+  }
+  const bool raw_full = p->rv.raw && p->level == p->L;  // (a raw record IS the finest level: no state)
+  if (!prealloc) {
+    if (p->in_dev) HL_HIP(hipMalloc(out, out_bytes));
+    else if (!(*out = host_alloc_large(out_bytes))) return hl_fail(MGH_ERR_OUT_OF_MEMORY, "malloc");
+  }
+  int rc = MGH_SUCCESS;
+  const void *lvl = p->state[p->si].p;
+  if (raw_full && is_device_pointer(p->rv.rec)) {
+    lvl = p->rv.rec;
+  } else if (raw_full) {
+    rc = p->full.ensure(p->n * p->elem);
+    if (rc == MGH_SUCCESS) rc = copy_any(p->full.p, p->rv.rec, p->n * p->elem, st);
+    lvl = p->full.p;
+  }
+  const bool out_dev = is_device_pointer(*out);
+  if (rc == MGH_SUCCESS && !out_dev) rc = p->win.ensure(out_bytes);
+  if (rc == MGH_SUCCESS) rc = mgh_prolong_window(p->h, p->level, lvl, lo, ext, out_dev ? *out : p->win.p, st);
+  if (rc == MGH_SUCCESS && !out_dev) rc = copy_any(*out, p->win.p, out_bytes, st);
+  if (rc == MGH_SUCCESS && hipStreamSynchronize(st) != hipSuccess) rc = hl_fail(MGH_ERR_DEVICE, "sync");
+  if (rc != MGH_SUCCESS && !prealloc) {
+    if (p->in_dev) (void)hipFree(*out); else std::free(*out);
+    *out = nullptr;
+  }
+  return rc;
+}
 }  // namespace
 
 extern "C" {
@@ -4755,6 +4881,21 @@ int mgh_progressive_preview(mgh_progressive *p, void **data, int output_pre_allo
   if (hipSetDevice(p->cfg.dev_id) != hipSuccess) return hl_fail(MGH_ERR_DEVICE, "hipSetDevice");
   try {
     return progressive_preview(p, data, output_pre_allocated != 0);
+  } catch (const std::exception &e) {
+    return hl_fail(MGH_ERR_DEVICE, e.what());
+  }
+}
+
+int mgh_progressive_preview_window(mgh_progressive *p, const uint64_t *lo, const uint64_t *ext, void **data,
+                                   int output_pre_allocated) {
+  if (!p || !data || !lo || !ext) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (output_pre_allocated && !*data) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "pre-allocated output is NULL");
+  if (p->level < 0)
+    return hl_fail(MGH_ERR_INVALID_ARGUMENT,
+                   "mgh_progressive_preview_window: nothing refined yet (call mgh_progressive_refine first)");
+  if (hipSetDevice(p->cfg.dev_id) != hipSuccess) return hl_fail(MGH_ERR_DEVICE, "hipSetDevice");
+  try {
+    return progressive_preview_window(p, lo, ext, data, output_pre_allocated != 0);
   } catch (const std::exception &e) {
     return hl_fail(MGH_ERR_DEVICE, e.what());
   }

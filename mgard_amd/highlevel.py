@@ -30,6 +30,7 @@ HL_SYMBOLS = [
     "mgh_progressive_level", "mgh_progressive_refine", "mgh_progressive_close",
     "mgh_infer_coarsened_shape", "mgh_infer_coarsened_nodes", "mgh_decompress_coarsened",
     "mgh_decompress_preview", "mgh_progressive_preview",
+    "mgh_decompress_preview_window", "mgh_progressive_preview_window",
 ]
 
 
@@ -123,6 +124,8 @@ def _hl():
     L.mgh_infer_coarsened_nodes.argtypes = [vp, C.c_size_t, vp, C.c_int, C.c_int, vp, u64]
     L.mgh_decompress_coarsened.argtypes = [vp, C.c_size_t, C.c_int, C.POINTER(vp), vp, C.c_int]
     L.mgh_decompress_preview.argtypes = [vp, C.c_size_t, C.c_int, C.POINTER(vp), vp, C.c_int]
+    L.mgh_decompress_preview_window.argtypes = [vp, C.c_size_t, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                                C.POINTER(vp), vp, C.c_int]
     L.mgh_dist_use_library.argtypes = [C.c_char_p]
     L.mgh_compress_dist.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(u64), C.c_double,
                                     C.c_double, C.c_int, vp, C.POINTER(vp), C.POINTER(C.c_size_t), vp, vp, C.c_int]
@@ -162,6 +165,8 @@ def _hl():
     L.mgh_progressive_level.argtypes = [vp]
     L.mgh_progressive_refine.argtypes = [vp, C.c_int, C.POINTER(vp), C.c_int]
     L.mgh_progressive_preview.argtypes = [vp, C.POINTER(vp), C.c_int]
+    L.mgh_progressive_preview_window.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(vp),
+                                                 C.c_int]
     L.mgh_progressive_close.argtypes = [vp]
     L.mgh_progressive_close.restype = None
     L.mgh_last_decompress_stats.argtypes = [C.POINTER(DecompressStats)]
@@ -456,14 +461,18 @@ class Progressive:
         _check(_hl().mgh_progressive_refine(self._p, int(level), C.byref(optr), 1))
         return out
 
-    def preview(self, out=None):
+    def preview(self, out=None, window=None):
         """mgh_progressive_preview: the current level prolonged to the container's own grid -- an array
         of infer(buf)[0], equal to decompress_preview(buf, l_target - level). Needs one
-        refine before it and leaves the reader's state as it is."""
+        refine before it and leaves the reader's state as it is.
+        window = (lo, ext): mgh_progressive_preview_window -- the box [lo, lo + ext) of that array alone."""
         import torch
         if not self._p:
             raise MgardHipError("the reader is closed")
         shape, _ = infer(self._buf)
+        if window is not None:
+            lo, ext = _window_args(window, len(shape))
+            shape = tuple(int(e) for e in ext)
         if self._on_dev:
             want = torch.float32 if self._dt == FLOAT else torch.float64
             if out is None:
@@ -480,7 +489,10 @@ class Progressive:
                     out.dtype == npdt and out.size == int(np.prod(shape))):
                 raise ValueError("`out` must be a writeable C-contiguous numpy array of the array's shape and type")
             optr = C.c_void_p(out.ctypes.data)
-        _check(_hl().mgh_progressive_preview(self._p, C.byref(optr), 1))
+        if window is not None:
+            _check(_hl().mgh_progressive_preview_window(self._p, lo, ext, C.byref(optr), 1))
+        else:
+            _check(_hl().mgh_progressive_preview(self._p, C.byref(optr), 1))
         return out
 
     def close(self):
@@ -517,18 +529,28 @@ def decompress(buf, config=None, out=None, level=None, coarsen=None):
     return _decompress(buf, config, out, level, coarsen, False)
 
 
-def decompress_preview(buf, coarsen, config=None, out=None):
+def _window_args(window, D):
+    """(lo, ext) as two uint64 arrays of D entries (the library checks them against the array)."""
+    lo, ext = window
+    if len(lo) != D or len(ext) != D or min(lo) < 0 or min(ext) < 0:
+        raise ValueError("window: (lo, ext) with one non-negative integer per dimension each")
+    return (C.c_uint64 * D)(*[int(x) for x in lo]), (C.c_uint64 * D)(*[int(x) for x in ext])
+
+
+def decompress_preview(buf, coarsen, config=None, out=None, window=None):
     """mgh_decompress_preview (extension): decompress(buf, coarsen=coarsen) with every coarsened subdomain
     prolonged back to its own grid -- an array of infer(buf)[0], placed like the full decompression; per
-    subdomain the recomposition with every coefficient above its level zero. coarsen = 0 is decompress."""
+    subdomain the recomposition with every coefficient above its level zero. coarsen = 0 is decompress.
+    window = (lo, ext): mgh_decompress_preview_window -- the box [lo, lo + ext) of that array alone, of shape
+    ext; subdomains the box does not meet are not opened."""
     if coarsen is None:
         raise ValueError("decompress_preview needs `coarsen`")
-    return _decompress(buf, config, out, None, coarsen, True)
+    return _decompress(buf, config, out, None, coarsen, True, window)
 
 
-def _decompress(buf, config, out, level, coarsen, full_grid):
+def _decompress(buf, config, out, level, coarsen, full_grid, window=None):
     """The body of decompress (full_grid = False) and decompress_preview (full_grid = True: mgh_decompress_preview
-    instead of mgh_decompress_coarsened, the output of the full array's shape)."""
+    instead of mgh_decompress_coarsened, the output of the full array's shape, or of the window's)."""
     import torch
     if level is not None and coarsen is not None:
         raise ValueError("pass either `level` or `coarsen`, not both")
@@ -546,6 +568,9 @@ def _decompress(buf, config, out, level, coarsen, full_grid):
             shape, _ = infer_coarsened(buf, int(coarsen), cfg)  # (also refuses more halvings than there are)
             if full_grid:
                 shape = infer(buf)[0]
+            if window is not None:
+                wlo, wext = _window_args(window, len(shape))
+                shape = tuple(int(e) for e in wext)
         _, dt = infer(buf)
         want = torch.float32 if dt == FLOAT else torch.float64
         if on_dev:
@@ -565,6 +590,8 @@ def _decompress(buf, config, out, level, coarsen, full_grid):
             p, n, optr = C.c_void_p(buf.ctypes.data), buf.size, C.c_void_p(out.ctypes.data)
         if level is not None:
             _check(L.mgh_decompress_level(p, n, int(level), C.byref(optr), C.byref(cfg), 1))
+        elif window is not None:
+            _check(L.mgh_decompress_preview_window(p, n, int(coarsen), wlo, wext, C.byref(optr), C.byref(cfg), 1))
         elif full_grid:
             _check(L.mgh_decompress_preview(p, n, int(coarsen), C.byref(optr), C.byref(cfg), 1))
         else:
