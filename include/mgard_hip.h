@@ -394,6 +394,19 @@ int mgh_profile_read(mgh_hierarchy *h, const char **names, double *total_ms, uin
 #define MGH_IPK_PLAN_FIELDS 16
 int mgh_debug_ipk_plans_read(mgh_hierarchy *h, long long *out, int cap, int reset);
 
+/* Test aid (no reference counterpart): while profiling is enabled on a hierarchy, every level that
+ * goes through the planner of the fused level passes (mgard_amd/csrc/fused_plan.hpp) leaves one
+ * record, the first 512 of them since the last reset. A record is MGH_FUSED_PLAN_FIELDS values: size
+ * class, element size, m[0], m[1], m[2] of the coarse box, TC, TF of the main tiles, 1 if the launch
+ * has face tiles, tiles, grid.x, march length (coarse planes per r-chunk), r-chunks, 1 if the march
+ * was chosen against the residency (0: the class's constant), slices of the first and the second
+ * launch (D = 4: even, odd; else 1, 0), workgroups of the two launches, resident workgroups
+ * (slots) of the first launch's kernel instance, rounds of resident workgroups (the larger of the
+ * two launches'), slots of the second launch's instance. Writes up to cap records to out; returns
+ * the number recorded. */
+#define MGH_FUSED_PLAN_FIELDS 20
+int mgh_debug_fused_plans_read(mgh_hierarchy *h, long long *out, int cap, int reset);
+
 /* Measurement aid for the roofline line (no reference counterpart): a PURE stream with the
  * read/write mix of the top-level pass of the hot path -- n elements of `dtype` read once,
  * n int64 written once with streaming stores, two side arrays of n/8 elements written -- and

@@ -32,7 +32,7 @@ SYMBOLS = [
     "mgh_recompose_to_level", "mgh_dequantize_recompose_to_level",
     "mgh_dequantize_recompose_sym16_to_level", "mgh_level_nodes",
     "mgh_level_box_from_linear", "mgh_dequantize_recompose_linear_to_level",
-    "mgh_refine_level", "mgh_debug_ipk_plans_read",
+    "mgh_refine_level", "mgh_debug_ipk_plans_read", "mgh_debug_fused_plans_read",
     "mgh_prolong", "mgh_debug_prolong_plan",
     "mgh_prolong_window", "mgh_prolong_window_strided", "mgh_debug_prolong_window_ranges",
     "mgh_debug_prolong_window_plan",
@@ -100,6 +100,7 @@ def load_library():
     L.mgh_profile_read.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(C.c_double), u64p,
                                    C.c_int, C.c_int]
     L.mgh_debug_ipk_plans_read.argtypes = [vp, i64p, C.c_int, C.c_int]
+    L.mgh_debug_fused_plans_read.argtypes = [vp, i64p, C.c_int, C.c_int]
     L.mgh_outlier_restore.argtypes = [vp, u64, vp, vp, u64, vp]
     L.mgh_level_linearize.argtypes = [vp, vp, vp, C.c_int, vp, vp, u64, u64, vp]
     L.mgh_recompose_to_level.argtypes = [vp, vp, C.c_int, vp, vp]
@@ -571,6 +572,23 @@ class Hierarchy:
         out = (C.c_int * 6)()
         _check(load_library().mgh_debug_prolong_plan(self._h, int(level), out))
         return dict(zip(self.PROLONG_PLAN_FIELDS, [int(x) for x in out]))
+
+    FUSED_PLAN_FIELDS = ("cls", "elem", "m0", "m1", "m2", "TC", "TF", "faces", "ntile", "grid_x", "rch", "nchunk",
+                         "by_policy", "nz0", "nz1", "workgroups0", "workgroups1", "slots", "rounds", "slots1")
+
+    def fused_plans(self, reset=True):
+        """The levels that went through the planner of the fused level passes (csrc/fused_plan.hpp)
+        while profile() was on, in launch order: one dict per level with the keys FUSED_PLAN_FIELDS
+        (`m` as a tuple instead of m0..m2)."""
+        cap, nf = 512, len(self.FUSED_PLAN_FIELDS)
+        buf = (C.c_int64 * (cap * nf))()
+        n = _check(load_library().mgh_debug_fused_plans_read(self._h, buf, cap, int(reset)))
+        out = []
+        for i in range(min(n, cap)):
+            r = dict(zip(self.FUSED_PLAN_FIELDS, buf[i * nf:(i + 1) * nf]))
+            r["m"] = (r.pop("m0"), r.pop("m1"), r.pop("m2"))
+            out.append(r)
+        return out
 
     # ---- per-kernel timing (HIP events on the launch stream) ----
     def profile(self, enable=True, only=None):

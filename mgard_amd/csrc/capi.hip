@@ -24,6 +24,7 @@
 #include "env.hpp"
 #include "hierarchy.hpp"
 #include "ipk_plan.hpp"
+#include "fused_plan.hpp"
 #include "kernels_v1.hpp"
 #include "kernels_ipk.hpp"
 #include "kernels_ipk_stream.hpp"
@@ -85,24 +86,19 @@ struct mgh_hierarchy {
   std::string prof_filter;  // empty = every kernel
   mgh::IpkTuning ipk;  // MGH_IPK_*: what the Thomas-solve planner goes by (ipk_plan.hpp)
   int absmax_warm_mb = 192;  // MGH_ABSMAX_WARM_MB: the norm pass reads all but the last so many MB of the input with nontemporal loads
-  // MGH_FUSED_FACES: 1 = face tiles for the remainder columns / rows of a level (default), 0 = off
-  int fused_faces = 1;
-  int fused_tall = 1;  // MGH_FUSED_TALL: 64 x 4 tiles for levels with a short fastest extent (default 1)
+  // MGH_FUSED_FACES / _TALL / _XCD / _WIDE, MGH_BOX, MGH_CLS1 / MGH_CLS2, MGH_RCH, MGH_FUSED_SLOTS: what
+  // the planner of the fused level passes goes by (fused_plan.hpp)
+  mgh::FusedTuning fused;
+  // workgroups per CU of the k_level_fused2 instances this hierarchy can launch, as the runtime
+  // reports them when the hierarchy is created (fused_residency_init; key: fused_instance_key)
+  std::map<int, int> fused_wg_per_cu;
   int slice_batch = 1;  // MGH_SLICE_BATCH: D = 4 decompression, all t-slices of a kind in one launch (default 1)
-  int fused_xcd = 1;  // MGH_FUSED_XCD: tiles of a level in contiguous ranges per XCD (default 1)
   int fused_fixed = 1; // MGH_FUSED_FIXED: the int64 + dictionary variant of the level kernel (default 1)
-  int fused_wide = 1; // MGH_FUSED_WIDE: 4 x 64 tiles for 0 = no level, 1 = long marches, 2 = all (unset: 1 for floats, 0 for doubles)
   int fused4 = 1;     // MGH_FUSED4: D = 4 through the 3-D tile code, slice by slice (default 1)
-  // MGH_BOX: levels up to this march class (0 = few tiles, 1 = mid-size, 2 = long marches) run
-  // the box kernel (kernels_box.hpp: no march, every phase once over a 4 x 4 x 8 box) instead of
-  // the marching tile kernel; 0 = none, 1 = class 0 (default), 2 = classes 0-1, 3 = every level
-  int box = 1;
   int outlier_agg = 2;  // MGH_OUTLIER_AGG: the level kernel asks for outlier slots once per workgroup and pair step instead of once per wave and plane (kernels_fused2.hpp: OutlierShared): 0 never, 1 always, 2 when the previous call on this hierarchy left more than 0.5 % of its values (and more than 200 000) in the outlier list
   int sym16_mixed = 1;  // MGH_SYM16_MIXED: 16-bit symbols for the finest level only, int64 below it (default), 0 = 16-bit symbols on every level
   int tail_solves = 1;  // MGH_TAIL_SOLVES: the tail kernel runs the Thomas solves of the level above it
   // (the rest of the developer switches, env.hpp; all read when the hierarchy is created)
-  size_t cls1 = 256, cls2 = 2048;  // MGH_CLS1 / MGH_CLS2: tile-count thresholds of the march classes
-  int rch[3] = {1, 4, 16};         // MGH_RCH=a,b,c: coarse planes per workgroup of the three classes
   int ipk_range_mb = 128;          // MGH_IPK_RANGE_MB: f- and c-solve of a load vector bigger than twice this run in r-plane ranges of this size (0 = off)
   bool no_head = false;            // MGH_NO_RECOMPOSE_HEAD
   bool debug_sync = false;         // MGH_DEBUG_SYNC: name every launch on stderr and synchronise behind it
@@ -110,6 +106,9 @@ struct mgh_hierarchy {
   // while `profiling`: one record per Thomas solve that went through ipk_launch, the first
   // kIpkLogCap of them (mgh_debug_ipk_plans_read; MGH_IPK_PLAN_FIELDS values each, in its order)
   std::vector<std::array<long long, MGH_IPK_PLAN_FIELDS>> ipk_log;
+  // while `profiling`: one record per level that went through the fused planner, the first
+  // kIpkLogCap of them (mgh_debug_fused_plans_read; MGH_FUSED_PLAN_FIELDS values each)
+  std::vector<std::array<long long, MGH_FUSED_PLAN_FIELDS>> fused_log;
   size_t device_bytes = 0;
   uint64_t shape[MGH_MAX_DIM] = {};
   // mgh_set_ld: leading dimensions of the caller's T arrays, [MGH_LD_IN / MGH_LD_OUT][dim]
@@ -797,101 +796,111 @@ template <typename T> void fused_quant_args(const mgh_hierarchy *h, const QuantP
   A.nlev = h->L + 1;
 }
 
-// Size class of a level for the fused kernels: 2 = plenty of tiles (long marches, RCH = 16),
-// 1 = mid-size (RCH = 4), 0 = few tiles (one coarse plane per workgroup).
-// nz: t-slices a launch of the D = 4 path covers (their workgroups count like tiles: 8 x 16395 x 39 x 39
-// f64 has 3 tiles a slice and ran its 16395 planes in marches of 4 -- 5.6 ms, 4.6 with marches of 16).
-inline int level_class(const mgh_hierarchy *h, const Box3 &b, size_t nz = 1) {
-  constexpr int TC = 8, TF = 32;
-  const size_t gx = (b.m[2] + TF - 1) / TF, gy = (b.m[1] + TC - 1) / TC;
-  if (gx * gy * nz * ((b.m[0] + 15) / 16) >= h->cls2) return 2;
-  if (gx * gy * nz * ((b.m[0] + 3) / 4) >= h->cls1) return 1;
-  return 0;
+// ---- the fused level passes: plan (fused_plan.hpp), residency, launch -----------------------
+inline bool fused_tall_tiles(const mgh_hierarchy *h, const Box3 &b) { return fused_tall_tiles(h->fused, b.m); }
+
+// The instance of k_level_fused2 a launch runs, as one number (RCH is 16 everywhere).
+constexpr int fused_instance_key(int out, int tc, int faces, int tmode, int agg) {
+  return (((out * 3 + (tc == 8 ? kShape8x32 : tc == 4 ? kShape4x64 : kShape64x4)) * 2 + faces) * 3 + tmode) * 2 + agg;
 }
 
-// Coarse planes per workgroup of the fused level kernel (the kernel is compiled for up to 16).
-inline int fused_rch(const mgh_hierarchy *h, int cls) { return h->rch[cls]; }
+// Workgroups per CU of one instance, asked of the runtime (256 threads, no dynamic LDS: the tile
+// lives in static LDS). Once per process, device and instance.
+template <typename T, int OUTK, int TC, int TF, bool FACES, int TMODE, bool AGG>
+int fused_residency_query(mgh_hierarchy *h) {
+  static std::mutex mu;
+  static std::map<int, int> per_device;
+  std::lock_guard<std::mutex> lock(mu);
+  auto it = per_device.find(h->device);
+  if (it == per_device.end()) {
+    int n = 0;
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(
+        &n, k_level_fused2<T, OUTK, TC, TF, kFusedMaxMarch, FACES, TMODE, AGG>, 256, 0));
+    if (n <= 0) return fail(MGH_ERR_DEVICE, "k_level_fused2: the runtime reports no resident workgroup");
+    it = per_device.emplace(h->device, n).first;
+  }
+  h->fused_wg_per_cu[fused_instance_key(OUTK, TC, FACES, TMODE, AGG)] = it->second;
+  return MGH_SUCCESS;
+}
+template <typename T, int OUTK, int TMODE, bool AGG> int fused_residency_shapes(mgh_hierarchy *h) {
+  TRY((fused_residency_query<T, OUTK, 8, 32, false, TMODE, AGG>(h)));
+  TRY((fused_residency_query<T, OUTK, 8, 32, true, TMODE, AGG>(h)));
+  TRY((fused_residency_query<T, OUTK, 4, 64, false, TMODE, AGG>(h)));
+  TRY((fused_residency_query<T, OUTK, 4, 64, true, TMODE, AGG>(h)));
+  TRY((fused_residency_query<T, OUTK, 64, 4, false, TMODE, AGG>(h)));
+  TRY((fused_residency_query<T, OUTK, 64, 4, true, TMODE, AGG>(h)));
+  return MGH_SUCCESS;
+}
+// Every instance decompose_fused (D <= 3) / decompose_fused4 (D = 4) can launch on this hierarchy.
+template <typename T> int fused_residency_init(mgh_hierarchy *h) {
+  if (h->D == 4) {
+    TRY((fused_residency_shapes<T, OUT_T, 1, false>(h)));
+    TRY((fused_residency_shapes<T, OUT_T, 2, false>(h)));
+    TRY((fused_residency_shapes<T, OUT_Q, 1, false>(h)));
+    TRY((fused_residency_shapes<T, OUT_Q, 2, false>(h)));
+    TRY((fused_residency_shapes<T, OUT_Q, 1, true>(h)));
+    TRY((fused_residency_shapes<T, OUT_Q, 2, true>(h)));
+  } else if (h->D <= 3) {
+    TRY((fused_residency_shapes<T, OUT_T, 0, false>(h)));
+    TRY((fused_residency_shapes<T, OUT_Q, 0, false>(h)));
+    TRY((fused_residency_shapes<T, OUT_QH, 0, false>(h)));
+    TRY((fused_residency_shapes<T, OUT_Q, 0, true>(h)));
+    TRY((fused_residency_shapes<T, OUT_QH, 0, true>(h)));
+  }
+  return MGH_SUCCESS;
+}
+// Workgroups the device holds at once of an instance (0: the hierarchy did not ask for it).
+inline long long fused_slots(const mgh_hierarchy *h, int key) {
+  auto it = h->fused_wg_per_cu.find(key);
+  return it == h->fused_wg_per_cu.end() ? 0 : (long long)it->second * (long long)h->num_cu;
+}
 
-// r-chunks of a level on the fused kernel: chunks of rch coarse planes, the last one takes what is
-// left (one plane more for sizes 2^k + 1)
-constexpr unsigned kXcdRangeMinTiles = 64;  // (below: at most 8 tiles an XCD, one more or less is 12 % and more)
-inline int fused_nchunk(int m_r, int rch) { return std::max(1, (m_r - 1 + rch - 1) / rch); }
+inline Fused2Grid fused_grid_of(const FusedPlan &p) {
+  Fused2Grid G{};
+  G.gxm = p.gxm; G.n_main = p.n_main;
+  G.ff_F0 = p.ff_F0; G.n_ff = p.n_ff;
+  G.cf_C0 = p.cf_C0; G.n_cf = p.n_cf;
+  G.rch = p.rch; G.nchunk = p.nchunk;
+  G.chunk_hi = p.nchunk;
+  G.xcd_ranges = p.xcd_ranges;
+  return G;
+}
+inline void fused_log_plan(mgh_hierarchy *h, const FusedPlan &p, int elem, const Box3 &b, const size_t nz[2]) {
+  if (!h->profiling || h->fused_log.size() >= kIpkLogCap) return;
+  std::array<long long, MGH_FUSED_PLAN_FIELDS> r;
+  static_assert(MGH_FUSED_PLAN_FIELDS == kFusedPlanFields, "mgard_hip.h and fused_plan.hpp agree on the record");
+  fused_plan_record(p, elem, b.m, nz, r.data());
+  h->fused_log.push_back(r);
+}
 
 // Level loop on the fused kernels (3 active dims): per level one fused
 // coefficient/quantize/load-vector pass, three Thomas solves (the last one adds
 // the correction into the coarse nodal array), then the head.
 // `after_first` (the quantizer set-up) is issued right in front of the first launch that needs it.
-// One level on the second-generation fused kernel (kernels_fused2.hpp). Tiles of the launch
-// (Fused2Grid): a remainder of up to 4 coarse columns / rows beyond the full tiles goes to face
-// tiles, the last r-chunk owns what is left of the planes (one more than the others for sizes
-// 2^k + 1).
+// One level on the second-generation fused kernel (kernels_fused2.hpp), as fused_plan.hpp plans it
+// (`p`: its tiles; the march is chosen here, against the residency of the instance that runs).
 template <typename T, int OUTK, int TC, int TF, bool AGG = false>
-int launch_fused2_t(mgh_hierarchy *h, const FusedArgs<T> &A, const Box3 &b, int cls, const char *nm,
+int launch_fused2_t(mgh_hierarchy *h, const FusedArgs<T> &A, const Box3 &b, FusedPlan p, const char *nm,
                     hipStream_t s) {
-  const int RCHv = fused_rch(h, cls);
-  Fused2Grid G{};
-  G.rch = RCHv;
-  const int mfi = (int)b.m[2], mci = (int)b.m[1], mri = (int)b.m[0];
-  const int nfull_f = (mfi - 1) / TF, rem_f = mfi - nfull_f * TF;
-  const int nfull_c = (mci - 1) / TC, rem_c = mci - nfull_c * TC;
-  const bool face_f = h->fused_faces && nfull_f >= 1 && rem_f <= 4;
-  const bool face_c = h->fused_faces && nfull_c >= 1 && rem_c <= 4;
-  G.gxm = face_f ? nfull_f : (mfi + TF - 1) / TF;
-  const int gym = face_c ? nfull_c : (mci + TC - 1) / TC;
-  G.n_main = G.gxm * gym;
-  G.ff_F0 = nfull_f * TF;
-  G.n_ff = face_f ? (mci + 63) / 64 : 0;
-  G.cf_C0 = nfull_c * TC;
-  G.n_cf = face_c ? ((face_f ? G.ff_F0 : mfi) + 63) / 64 : 0;
-  G.nchunk = fused_nchunk(mri, RCHv);
-  G.chunk_hi = G.nchunk;
-  const unsigned ntile = (unsigned)(G.n_main + G.n_ff + G.n_cf);
-  // (contiguous tile ranges per XCD only where there are tiles to hand out -- a cross-section of three
-  // tiles padded to eight put every workgroup that had work on XCDs 0..2 -- 16395 x 39 x 39 f64: top
-  // level 778 us; without the ranges the r-chunks rotate the tiles over the XCDs)
-  G.xcd_ranges = ntile >= kXcdRangeMinTiles ? h->fused_xcd : 0;
-  const dim3 grid(G.xcd_ranges ? (ntile + 7) / 8 * 8 : ntile, (unsigned)G.nchunk, 1);
-  const bool faces = G.n_ff || G.n_cf;
-#define MGH_F2(RCH)                                                                           \
-  if (faces)                                                                                  \
-    return launch_kernel(h, nm, s, k_level_fused2<T, OUTK, TC, TF, RCH, true, 0, AGG>, grid, dim3(256), 0, A, G, \
-                         Fused4<T>{});                                                        \
-  return launch_kernel(h, nm, s, k_level_fused2<T, OUTK, TC, TF, RCH, false, 0, AGG>, grid, dim3(256), 0, A, G, \
-                       Fused4<T>{});
-  MGH_F2(16)
-#undef MGH_F2
+  const size_t nz[2] = {1, 0};
+  const long long slots[2] = {fused_slots(h, fused_instance_key(OUTK, TC, p.faces, 0, AGG)), 0};
+  fused_plan_march(p, h->fused, (int)b.m[0], 1, nz, slots);
+  fused_log_plan(h, p, (int)sizeof(T), b, nz);
+  const Fused2Grid G = fused_grid_of(p);
+  const dim3 grid(p.grid_x, (unsigned)G.nchunk, 1);
+  if (p.faces)
+    return launch_kernel(h, nm, s, k_level_fused2<T, OUTK, TC, TF, kFusedMaxMarch, true, 0, AGG>, grid, dim3(256), 0,
+                         A, G, Fused4<T>{});
+  return launch_kernel(h, nm, s, k_level_fused2<T, OUTK, TC, TF, kFusedMaxMarch, false, 0, AGG>, grid, dim3(256), 0,
+                       A, G, Fused4<T>{});
 }
 
-// Tile shape: long marches (class 2) run 4 x 64 coarse nodes per tile -- every row a wave reads or
-// writes is 512 contiguous bytes instead of 256, which the memory system rewards more than the
-// larger halo (1.41 x instead of 1.24 x re-read) costs: top level of 512^3 f32 435 -> 383 us, same
-// box, alternating runs. The short marches of the lower levels are a few us faster on 8 x 32.
-// (... where the rows are long enough to fill them: 33 coarse nodes along f are one 8 x 32 tile and a
-// face tile, or half a 4 x 64 tile)
-inline bool fused_wide_tiles(const mgh_hierarchy *h, int cls, uint32_t mf) {
-  if (h->fused_wide >= 2) return true;
-  if (h->fused_wide != 1 || cls != 2) return false;
-  auto filled = [&](uint32_t tf) {  // share of a main tile's columns that hold nodes
-    const uint32_t nfull = (mf - 1) / tf, rem = mf - nfull * tf;
-    if (h->fused_faces && nfull >= 1 && rem <= 4) return 1.0;  // (the remainder goes to a face tile)
-    return (double)mf / (double)((mf + tf - 1) / tf * tf);
-  };
-  return filled(64) + 0.1 >= filled(32);
-}
-// A short FASTEST extent (AoS-like data: 2048 x 2048 x 17, 512^3 x 5): nine coarse nodes along f fill a
-// quarter of an 8 x 32 tile's lanes, three of them a tenth. Tiles of 64 x 4 coarse nodes there -- the face
-// tiles' shape as the main one (the (c, f) plane of such a level is nearly contiguous in memory, the short
-// rows cost little). MGH_FUSED_TALL=0: never.
-inline bool fused_tall_tiles(const mgh_hierarchy *h, const Box3 &b) {
-  return h->fused_tall && b.m[2] <= 16 && b.m[1] >= 48;
-}
 template <typename T, int OUTK, bool AGG = false>
-int launch_fused2(mgh_hierarchy *h, const FusedArgs<T> &A, const Box3 &b, int cls, const char *nm,
+int launch_fused2(mgh_hierarchy *h, const FusedArgs<T> &A, const Box3 &b, const FusedPlan &p, const char *nm,
                   hipStream_t s) {
-  if (fused_tall_tiles(h, b)) return launch_fused2_t<T, OUTK, 64, 4, AGG>(h, A, b, cls, nm, s);
-  if (fused_wide_tiles(h, cls, b.m[2]))
-    return launch_fused2_t<T, OUTK, 4, 64, AGG>(h, A, b, cls, nm, s);
-  return launch_fused2_t<T, OUTK, 8, 32, AGG>(h, A, b, cls, nm, s);
+  if (p.shape == kShape64x4) return launch_fused2_t<T, OUTK, 64, 4, AGG>(h, A, b, p, nm, s);
+  if (p.shape == kShape4x64) return launch_fused2_t<T, OUTK, 4, 64, AGG>(h, A, b, p, nm, s);
+  return launch_fused2_t<T, OUTK, 8, 32, AGG>(h, A, b, p, nm, s);
 }
 
 // Which variant of the level kernel: the one that asks for outlier slots per wave and plane
@@ -1035,13 +1044,14 @@ int decompose_fused(mgh_hierarchy *h, const T *data, const Layout &in, T *coeff,
       A.quantizer = qp->qz[l];
       A.volume = qp->vol[l];
     }
-    const int cls = level_class(h, b);
+    const FusedPlan plan = fused_plan_tiles(h->fused, b.m);
+    const int cls = plan.cls;
     if (l == L) TRY(after_first());
     // (the level kernels test the dictionary range in 32 bits: the entry points send larger
     // dictionaries through decompose + quantize)
     if (OUT == OUT_Q && qp->out.dict_size > ((uint64_t)1 << 30))
       return fail(MGH_ERR_INVALID_ARGUMENT, "fused path: dict_size must be at most 2^30");
-    if (cls < h->box) {
+    if (cls < h->fused.box) {
       // small level: no march (kernels_box.hpp)
       constexpr int BR = 4, BC = 4, BF = 8;
       const int bx = ((int)b.m[2] + BF - 1) / BF, by = ((int)b.m[1] + BC - 1) / BC,
@@ -1056,13 +1066,13 @@ int decompose_fused(mgh_hierarchy *h, const T *data, const Layout &in, T *coeff,
                                 : (OUT == OUT_Q ? "level_fused_q_small" : "level_fused_small");
       if (OUT == OUT_Q && agg) {  // (many outliers last time: slot requests per workgroup)
         if (A.prep_huffman && !A.q16 && h->fused_fixed)
-          TRY((launch_fused2<T, OUT == OUT_Q ? OUT_QH : OUT, OUT == OUT_Q>(h, A, b, cls, nm, s)));
+          TRY((launch_fused2<T, OUT == OUT_Q ? OUT_QH : OUT, OUT == OUT_Q>(h, A, b, plan, nm, s)));
         else
-          TRY((launch_fused2<T, OUT, OUT == OUT_Q>(h, A, b, cls, nm, s)));
+          TRY((launch_fused2<T, OUT, OUT == OUT_Q>(h, A, b, plan, nm, s)));
       } else if (OUT == OUT_Q && A.prep_huffman && !A.q16 && h->fused_fixed)
-        TRY((launch_fused2<T, OUT == OUT_Q ? OUT_QH : OUT>(h, A, b, cls, nm, s)));
+        TRY((launch_fused2<T, OUT == OUT_Q ? OUT_QH : OUT>(h, A, b, plan, nm, s)));
       else
-        TRY((launch_fused2<T, OUT>(h, A, b, cls, nm, s)));
+        TRY((launch_fused2<T, OUT>(h, A, b, plan, nm, s)));
     }
     // (the level right above the tail leaves its three solves to the tail kernel, which needs the
     // box in LDS anyway)
@@ -1156,30 +1166,17 @@ int decompose_fused(mgh_hierarchy *h, const T *data, const Layout &in, T *coeff,
 // CalcCorrectionND.hpp:25-267 (dims D-1 .. 0): bit-identical to the generic N-D kernels.
 // D = 4: the even and the odd slices of one level (kernels_fused2.hpp, TMODE 1 / 2)
 template <typename T, int OUT, int TC, int TF, bool AGG = false>
-int launch_fused4_t(mgh_hierarchy *h, const FusedArgs<T> &A, const Fused4<T> &Q, const Box3 &b, int cls,
+int launch_fused4_t(mgh_hierarchy *h, const FusedArgs<T> &A, const Fused4<T> &Q, const Box3 &b, FusedPlan p,
                     int n_t, int m_t, hipStream_t s) {
-    const int RCHv = fused_rch(h, cls);
-    Fused2Grid G{};
-    G.rch = RCHv;
-    const int mfi = (int)b.m[2], mci = (int)b.m[1], mri = (int)b.m[0];
-    const int nfull_f = (mfi - 1) / TF, rem_f = mfi - nfull_f * TF;
-    const int nfull_c = (mci - 1) / TC, rem_c = mci - nfull_c * TC;
-    const bool face_f = h->fused_faces && nfull_f >= 1 && rem_f <= 4;
-    const bool face_c = h->fused_faces && nfull_c >= 1 && rem_c <= 4;
-    G.gxm = face_f ? nfull_f : (mfi + TF - 1) / TF;
-    const int gym = face_c ? nfull_c : (mci + TC - 1) / TC;
-    G.n_main = G.gxm * gym;
-    G.ff_F0 = nfull_f * TF;
-    G.n_ff = face_f ? (mci + 63) / 64 : 0;
-    G.cf_C0 = nfull_c * TC;
-    G.n_cf = face_c ? ((face_f ? G.ff_F0 : mfi) + 63) / 64 : 0;
-    G.nchunk = fused_nchunk(mri, RCHv);
-    G.chunk_hi = G.nchunk;
-    const unsigned ntile = (unsigned)(G.n_main + G.n_ff + G.n_cf);
-    G.xcd_ranges = ntile >= kXcdRangeMinTiles ? h->fused_xcd : 0;  // (see launch_fused2_t)
-    const unsigned gx = G.xcd_ranges ? (ntile + 7) / 8 * 8 : ntile;
-    const bool faces = G.n_ff || G.n_cf;
-    const unsigned n_even = (unsigned)m_t, n_odd = (unsigned)(n_t - m_t);
+    const size_t nz[2] = {(size_t)m_t, (size_t)(n_t - m_t)};  // even, odd slices
+    const long long slots[2] = {fused_slots(h, fused_instance_key(OUT, TC, p.faces, 1, AGG)),
+                                fused_slots(h, fused_instance_key(OUT, TC, p.faces, 2, AGG))};
+    fused_plan_march(p, h->fused, (int)b.m[0], 2, nz, slots);
+    fused_log_plan(h, p, (int)sizeof(T), b, nz);
+    const Fused2Grid G = fused_grid_of(p);
+    const unsigned gx = p.grid_x;
+    const bool faces = p.faces;
+    const unsigned n_even = (unsigned)nz[0], n_odd = (unsigned)nz[1];
 #define MGH_F4(RCH, TMODE, NZ, NAME)                                                          \
   if ((NZ) > 0) {                                                                             \
     const dim3 grid(gx, (unsigned)G.nchunk, (NZ));                                            \
@@ -1188,8 +1185,8 @@ int launch_fused4_t(mgh_hierarchy *h, const FusedArgs<T> &A, const Fused4<T> &Q,
     else                                                                                      \
       TRY(launch_kernel(h, NAME, s, k_level_fused2<T, OUT, TC, TF, RCH, false, TMODE, AGG>, grid, dim3(256), 0, A, G, Q)); \
   }
-    MGH_F4(16, 1, n_even, "level4_even")
-    MGH_F4(16, 2, n_odd, "level4_odd")
+    MGH_F4(kFusedMaxMarch, 1, n_even, "level4_even")
+    MGH_F4(kFusedMaxMarch, 2, n_odd, "level4_odd")
 #undef MGH_F4
     return MGH_SUCCESS;
 }
@@ -1309,18 +1306,18 @@ int decompose_fused4(mgh_hierarchy *h, const T *data, T *coeff, const QuantParam
     // an even n_t has a ghost slice (padded position n_t - 1): its load vector is zero
     if (n_t % 2 == 0)
       HIP_TRY(hipMemsetAsync(ds->load4 + (size_t)(n_t - 1) * M, 0, M * sizeof(T), s));
-    const int cls = level_class(h, b, (size_t)std::max(1, n_t - m_t));
-    const bool wide = fused_wide_tiles(h, cls, b.m[2]), tall = fused_tall_tiles(h, b);
+    const FusedPlan plan = fused_plan_tiles(h->fused, b.m, (size_t)std::max(1, n_t - m_t));
+    const bool wide = plan.shape == kShape4x64, tall = plan.shape == kShape64x4;
     if (OUT == OUT_Q && agg) {
-      if (tall) TRY((launch_fused4_t<T, OUT, 64, 4, OUT == OUT_Q>(h, A, Q, b, cls, n_t, m_t, s)));
-      else if (wide) TRY((launch_fused4_t<T, OUT, 4, 64, OUT == OUT_Q>(h, A, Q, b, cls, n_t, m_t, s)));
-      else TRY((launch_fused4_t<T, OUT, 8, 32, OUT == OUT_Q>(h, A, Q, b, cls, n_t, m_t, s)));
+      if (tall) TRY((launch_fused4_t<T, OUT, 64, 4, OUT == OUT_Q>(h, A, Q, b, plan, n_t, m_t, s)));
+      else if (wide) TRY((launch_fused4_t<T, OUT, 4, 64, OUT == OUT_Q>(h, A, Q, b, plan, n_t, m_t, s)));
+      else TRY((launch_fused4_t<T, OUT, 8, 32, OUT == OUT_Q>(h, A, Q, b, plan, n_t, m_t, s)));
     } else if (tall)
-      TRY((launch_fused4_t<T, OUT, 64, 4>(h, A, Q, b, cls, n_t, m_t, s)));
+      TRY((launch_fused4_t<T, OUT, 64, 4>(h, A, Q, b, plan, n_t, m_t, s)));
     else if (wide)
-      TRY((launch_fused4_t<T, OUT, 4, 64>(h, A, Q, b, cls, n_t, m_t, s)));
+      TRY((launch_fused4_t<T, OUT, 4, 64>(h, A, Q, b, plan, n_t, m_t, s)));
     else
-      TRY((launch_fused4_t<T, OUT, 8, 32>(h, A, Q, b, cls, n_t, m_t, s)));
+      TRY((launch_fused4_t<T, OUT, 8, 32>(h, A, Q, b, plan, n_t, m_t, s)));
     // t-sweep, then the Thomas solves f, c, r, t on the coarse box (m_t, m_r, m_c, m_f)
     {
       TRY((tsweep_launch<T>(h, ds->load4, ds->corr4, M, m_t, ds->nd[l].mass[0], s)));
@@ -2419,7 +2416,7 @@ int recompose_to_level_impl(mgh_hierarchy *h, const T *coeff, const Layout &in, 
 // ---- prolongation of a level to the full grid (mgh_prolong) ---------------------------------------
 // The plan of the level step l - 1 -> l (prolong_plan.hpp) for this hierarchy's switches.
 template <typename T> ProlongPlan prolong_plan_of(const mgh_hierarchy *h, int l) {
-  return prolong_plan(DS<T>(h)->lt[l].box.m, h->fused_tall != 0);
+  return prolong_plan(DS<T>(h)->lt[l].box.m, h->fused.tall != 0);
 }
 
 template <typename T, int TC, int TF>
@@ -2583,7 +2580,7 @@ int prolong_window_fused3(mgh_hierarchy *h, int level, const T *lvl, const std::
       range(l - 1, k, &ca[k], &cb[k]);
       range(l, k, &fa[k], &fb[k]);
     }
-    const ProlongWinPlan w = prolong_window_plan(t.box.n, fa, fb, h->fused_tall != 0);
+    const ProlongWinPlan w = prolong_window_plan(t.box.n, fa, fb, h->fused.tall != 0);
     if (w.p.nchunk > 65535) return fail(MGH_ERR_INVALID_ARGUMENT, "mgh_prolong_window: slowest extent too long");
     ProlongWinArgs<T> A{};
     for (int k = 0; k < 3; k++) {
@@ -3258,21 +3255,25 @@ int mgh_hierarchy_create(mgh_hierarchy **out, int D, const uint64_t *shape, int 
     h->force_nd = env_get("MGH_FORCE_ND", 0) != 0;
     h->force_nd_ipk = env_get("MGH_ND_IPK", 0) != 0;
     h->absmax_warm_mb = (int)env_get("MGH_ABSMAX_WARM_MB", h->absmax_warm_mb);
-    h->fused_faces = (int)env_get("MGH_FUSED_FACES", h->fused_faces);
-    h->fused_xcd = (int)env_get("MGH_FUSED_XCD", h->fused_xcd);
+    h->fused.faces = (int)env_get("MGH_FUSED_FACES", h->fused.faces);
+    h->fused.xcd = (int)env_get("MGH_FUSED_XCD", h->fused.xcd);
     h->slice_batch = (int)env_get("MGH_SLICE_BATCH", h->slice_batch);
-    h->fused_tall = (int)env_get("MGH_FUSED_TALL", h->fused_tall);
+    h->fused.tall = (int)env_get("MGH_FUSED_TALL", h->fused.tall);
     h->fused_fixed = (int)env_get("MGH_FUSED_FIXED", h->fused_fixed);
-    h->fused_wide = (int)env_get("MGH_FUSED_WIDE", -1);  // (-1: by data type, below)
+    h->fused.wide = (int)env_get("MGH_FUSED_WIDE", -1);  // (-1: by data type, below)
     h->fused4 = (int)env_get("MGH_FUSED4", h->fused4);
-    h->box = (int)env_get("MGH_BOX", h->box);
+    h->fused.box = (int)env_get("MGH_BOX", h->fused.box);
     h->sym16_mixed = (int)env_get("MGH_SYM16_MIXED", h->sym16_mixed);
     h->outlier_agg = (int)env_get("MGH_OUTLIER_AGG", h->outlier_agg);
     h->tail_solves = (int)env_get("MGH_TAIL_SOLVES", h->tail_solves);
     h->nd_rows = (int)env_get("MGH_ND_ROWS", h->nd_rows);
-    h->cls1 = (size_t)env_get("MGH_CLS1", (long)h->cls1);
-    h->cls2 = (size_t)env_get("MGH_CLS2", (long)h->cls2);
-    if (const char *e = std::getenv("MGH_RCH")) std::sscanf(e, "%d,%d,%d", &h->rch[0], &h->rch[1], &h->rch[2]);
+    h->fused.cls1 = (size_t)env_get("MGH_CLS1", (long)h->fused.cls1);
+    h->fused.cls2 = (size_t)env_get("MGH_CLS2", (long)h->fused.cls2);
+    if (const char *e = std::getenv("MGH_RCH"))
+      std::sscanf(e, "%d,%d,%d", &h->fused.rch[0], &h->fused.rch[1], &h->fused.rch[2]);
+    // (any of the three set: the marches are the classes' constants, whatever the residency)
+    h->fused.pinned = std::getenv("MGH_RCH") || std::getenv("MGH_CLS1") || std::getenv("MGH_CLS2");
+    h->fused.slots_override = env_get("MGH_FUSED_SLOTS", 0);
     h->ipk_range_mb = (int)env_get("MGH_IPK_RANGE_MB", h->ipk_range_mb);
     h->no_head = env_get("MGH_NO_RECOMPOSE_HEAD", 0) != 0;
     h->debug_sync = env_get("MGH_DEBUG_SYNC", 0) != 0;
@@ -3283,7 +3284,7 @@ int mgh_hierarchy_create(mgh_hierarchy **out, int D, const uint64_t *shape, int 
   // tile shape of the long marches: 4 x 64 for floats, 8 x 32 for doubles -- fine rows of ~512 bytes
   // either way (512^3 f64 non-uniform, three alternating runs on one box: top-level pass
   // 612 -> 593 us, step 1.413 -> 1.384 ms)
-  if (h->fused_wide < 0) h->fused_wide = dtype == MGH_FLOAT ? 1 : 0;
+  if (h->fused.wide < 0) h->fused.wide = dtype == MGH_FLOAT ? 1 : 0;
   {
     int cus = 0;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0)
@@ -3325,10 +3326,13 @@ int mgh_hierarchy_create(mgh_hierarchy **out, int D, const uint64_t *shape, int 
     const uint64_t m1 = shape[1] / 2 + 1, m2 = shape[2] / 2 + 1;
     double tiles = (double)((m1 + 7) / 8) * (double)((m2 + 31) / 32);
     // (a short fastest extent under a long middle one: the 64 x 4 tiles -- fused_tall_tiles)
-    if (h->fused_tall && m2 <= 16 && m1 >= 48) tiles = (double)((m1 + 63) / 64) * (double)((m2 + 3) / 4);
+    if (h->fused.tall && m2 <= 16 && m1 >= 48) tiles = (double)((m1 + 63) / 64) * (double)((m2 + 3) / 4);
     if ((double)(m1 * m2) < 0.125 * tiles * 256.0) h->force_v1 = true;
   }
   int rc = with_type(h, [&](auto t) { return build_device_state<decltype(t)>(h); });
+  // what the device holds at once of every level-kernel instance this hierarchy can launch: the
+  // marches of the levels below the top are planned against it (fused_plan.hpp)
+  if (rc == MGH_SUCCESS) rc = with_type(h, [&](auto t) { return fused_residency_init<decltype(t)>(h); });
   if (rc != MGH_SUCCESS) {
     mgh_hierarchy_destroy(h);
     return rc;
@@ -3721,7 +3725,7 @@ int mgh_debug_prolong_window_plan(const mgh_hierarchy *h, int level, const uint6
       a[k] = chain[(size_t)(l - level) * 6 + 2 * k];
       b[k] = chain[(size_t)(l - level) * 6 + 2 * k + 1];
     }
-    const ProlongWinPlan w = prolong_window_plan(DS<T>(h)->lt[l].box.n, a, b, h->fused_tall != 0);
+    const ProlongWinPlan w = prolong_window_plan(DS<T>(h)->lt[l].box.n, a, b, h->fused.tall != 0);
     const int v[12] = {w.p.TC, w.p.TF, w.p.gxm, w.p.ntile, w.p.rch, w.p.nchunk, w.J0[0], w.J0[1], w.J0[2],
                        w.nJ[0], w.nJ[1], w.nJ[2]};
     std::copy(v, v + 12, out12);
@@ -3778,6 +3782,15 @@ int mgh_debug_ipk_plans_read(mgh_hierarchy *h, long long *out, int cap, int rese
   for (int i = 0; i < std::min(n, cap); i++)
     std::copy(h->ipk_log[i].begin(), h->ipk_log[i].end(), out + (size_t)i * MGH_IPK_PLAN_FIELDS);
   if (reset) h->ipk_log.clear();
+  return n;
+}
+
+int mgh_debug_fused_plans_read(mgh_hierarchy *h, long long *out, int cap, int reset) {
+  if (!h || (cap > 0 && !out) || cap < 0) return fail(MGH_ERR_INVALID_ARGUMENT, "null argument");
+  const int n = (int)h->fused_log.size();
+  for (int i = 0; i < std::min(n, cap); i++)
+    std::copy(h->fused_log[i].begin(), h->fused_log[i].end(), out + (size_t)i * MGH_FUSED_PLAN_FIELDS);
+  if (reset) h->fused_log.clear();
   return n;
 }
 

@@ -52,6 +52,7 @@ inline const EnvSwitch *env_switches(size_t *count) {
       {"MGH_HL_COPY_AFFINITY", 0, 1},
       {"MGH_IPK_DMA_ROUNDS", 1, 64},
       {"MGH_IPK_PLAN_CU", 1, 1024},
+      {"MGH_FUSED_SLOTS", 1, 1 << 20},
   };
   *count = sizeof(k) / sizeof(k[0]);
   return k;
