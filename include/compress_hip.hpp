@@ -25,6 +25,7 @@
 
 #include "mgard_hip.hpp"
 #include "mgard_hip_compress.h"
+#include "mgard_hip_errors.hpp"
 
 namespace mgard_hip {
 
@@ -169,6 +170,40 @@ inline compress_status_type decompress_preview(const void *compressed_data, size
   const mgh_config c = detail::to_c(config);
   return detail::status(mgh_decompress_preview(compressed_data, compressed_size, halvings, &decompressed_data, &c,
                                                output_pre_allocated ? 1 : 0));
+}
+// EXTENSION: mgh_verify. The error statistics of `original_data` (host or device memory) against what
+// decompress -- halvings = 0 -- or decompress_preview would write, subdomain by subdomain on the device,
+// without that array being made; result.within tells whether the container keeps its bound.
+inline compress_status_type verify(const void *compressed_data, size_t compressed_size, const void *original_data,
+                                   size_t original_bytes, data_type dtype, int halvings, HighLevelConfig config,
+                                   mgh_verify_result &result) {
+  const mgh_config c = detail::to_c(config);
+  return detail::status(mgh_verify(compressed_data, compressed_size, original_data, original_bytes, (int)dtype, halvings,
+                                   &c, &result));
+}
+// The figures of the reference's Utilities/ErrorCalculator.h (semantics: mgard_hip_errors.hpp), one pass
+// of mgh_compare on `device`; host or device pointers.
+template <typename T> double L_inf_norm(size_t n, const T *data, int device = 0) {
+  return mgard_hip_errors::L_inf_norm(n, data, device);
+}
+template <typename T> double L_2_norm(std::vector<SIZE> shape, const T *data, bool normalize_coordinates, int device = 0) {
+  return mgard_hip_errors::L_2_norm(mgard_hip_errors::count(shape), data, normalize_coordinates, device);
+}
+template <typename T>
+double L_inf_error(size_t n, const T *original_data, const T *decompressed_data, error_bound_type mode, int device = 0) {
+  return mgard_hip_errors::L_inf_error(n, original_data, decompressed_data, mode == error_bound_type::REL, device);
+}
+template <typename T>
+double L_2_error(std::vector<SIZE> shape, const T *original_data, const T *decompressed_data, error_bound_type mode,
+                 bool normalize_coordinates, int device = 0) {
+  return mgard_hip_errors::L_2_error(mgard_hip_errors::count(shape), original_data, decompressed_data,
+                                     mode == error_bound_type::REL, normalize_coordinates, device);
+}
+template <typename T> double MSE(size_t n, const T *original_data, const T *decompressed_data, int device = 0) {
+  return mgard_hip_errors::MSE(n, original_data, decompressed_data, device);
+}
+template <typename T> double PSNR(size_t n, const T *original_data, const T *decompressed_data, int device = 0) {
+  return mgard_hip_errors::PSNR(n, original_data, decompressed_data, device);
 }
 // ... the box [lo_d, lo_d + ext_d) of it alone (mgh_decompress_preview_window): a dense array of shape ext;
 // subdomains the box does not meet are not opened. lo, ext: one entry per dimension of the array.

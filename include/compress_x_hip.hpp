@@ -34,6 +34,7 @@
 #include <vector>
 
 #include "mgard_hip_compress.h"
+#include "mgard_hip_errors.hpp"
 
 namespace mgard_x {
 
@@ -355,6 +356,43 @@ decompress(const void *compressed_data, size_t compressed_size, void *&decompres
            std::vector<mgard_x::SIZE> &shape, data_type &dtype, bool output_pre_allocated) {
   return decompress(compressed_data, compressed_size, decompressed_data, shape, dtype, Config(),
                     output_pre_allocated);
+}
+
+// ---- error figures (Utilities/ErrorCalculator.h:22-121), the reference's names and signatures ----
+// Implemented on mgh_compare (one pass on device 0; the pointers may be host or device pointers);
+// mgard_hip_errors.hpp restates the semantics: REL divides by the norm of the original, a zero norm
+// is DBL_EPSILON, and PSNR's range is max(ref_max, 0) - ref_min because the reference's maximum
+// starts at 0 and its minimum at DBL_MAX.
+template <typename T> double L_inf_norm(size_t n, const T *data) { return mgard_hip_errors::L_inf_norm(n, data); }
+template <typename T> double L_2_norm(std::vector<SIZE> shape, const T *data, bool normalize_coordinates) {
+  return mgard_hip_errors::L_2_norm(mgard_hip_errors::count(shape), data, normalize_coordinates);
+}
+template <typename T>
+double L_inf_error(size_t n, const T *original_data, const T *decompressed_data, enum error_bound_type mode) {
+  return mgard_hip_errors::L_inf_error(n, original_data, decompressed_data, mode == error_bound_type::REL);
+}
+template <typename T>
+double L_2_error(std::vector<SIZE> shape, const T *original_data, const T *decompressed_data,
+                 enum error_bound_type mode, bool normalize_coordinates) {
+  return mgard_hip_errors::L_2_error(mgard_hip_errors::count(shape), original_data, decompressed_data,
+                                     mode == error_bound_type::REL, normalize_coordinates);
+}
+template <typename T> double MSE(size_t n, const T *original_data, const T *decompressed_data) {
+  return mgard_hip_errors::MSE(n, original_data, decompressed_data);
+}
+template <typename T> double PSNR(size_t n, const T *original_data, const T *decompressed_data) {
+  return mgard_hip_errors::PSNR(n, original_data, decompressed_data);
+}
+// EXTENSION: mgh_verify -- the statistics of `original` against what decompress (halvings = 0) or
+// decompress_preview would write, subdomain by subdomain, without that array being made.
+inline enum compress_status_type verify(const void *compressed_data, size_t compressed_size, const void *original_data,
+                                        size_t original_bytes, data_type dtype, int halvings, Config config,
+                                        mgh_verify_result &result) {
+  const compress_status_type ok = detail::check(config);
+  if (ok != compress_status_type::Success) return ok;
+  const mgh_config c = detail::to_c(config);
+  return detail::status(mgh_verify(compressed_data, compressed_size, original_data, original_bytes, (int)dtype, halvings,
+                                   &c, &result));
 }
 
 // ---- cache and pinned memory (compress_x.hpp:159-178) -------------------------------------------

@@ -407,6 +407,57 @@ int mgh_debug_ipk_plans_read(mgh_hierarchy *h, long long *out, int cap, int rese
 #define MGH_FUSED_PLAN_FIELDS 20
 int mgh_debug_fused_plans_read(mgh_hierarchy *h, long long *out, int cap, int reset);
 
+/* ---- Error statistics of two arrays ------------------------------------------------------------
+ * What include/mgard-x/Utilities/ErrorCalculator.h computes on the host with one loop per figure
+ * (L_inf_norm :22-33, L_2_norm :35-54, L_inf_error :56-72, L_2_error :74-97, MSE :99-107, PSNR
+ * :109-121), gathered in ONE pass over both arrays on the device. a = the reference (original)
+ * array, b = the other one. Fixed layout, 72 bytes: uint64_t and double fields only.
+ *  n            elements compared
+ *  nonfinite    positions where a[i] - b[i] is not finite (either value NaN or +-Inf, Inf - Inf, or
+ *               a difference that overflows). They are COUNTED HERE AND EXCLUDED FROM EVERY OTHER
+ *               FIELD. (The reference lets a NaN poison its sums and ignores it in its maxima.)
+ *  max_abs_err  max |a[i] - b[i]|: difference and fabs in the arrays' type, then widened (:57-64)
+ *  argmax       flat row-major index in the LOGICAL dense array of the lowest-indexed position that
+ *               attains max_abs_err; 0 when no position is finite
+ *  sum_sq_err   sum of (double)|a[i] - b[i]| squared, accumulated in double
+ *  ref_min, ref_max, ref_abs_max, ref_sum_sq   min a[i], max a[i], max |a[i]|, sum (double)a[i]^2
+ *               over the same positions (all 0 when there is none)
+ * Derived figures (csrc/compare_plan.hpp, and the C++ / Python mirrors): mse = sum_sq_err /
+ * (n - nonfinite), rmse, psnr = 20 log10((ref_max - ref_min) / rmse). */
+typedef struct mgh_error_stats {
+  uint64_t n;
+  uint64_t nonfinite;
+  double max_abs_err;
+  uint64_t argmax;
+  double sum_sq_err;
+  double ref_min;
+  double ref_max;
+  double ref_abs_max;
+  double ref_sum_sq;
+} mgh_error_stats;
+
+/* D = 1 ... MGH_MAX_DIM, shape[D] on the host. ld_a / ld_b: leading dimensions in mgh_set_ld's
+ * convention (D entries, ld[d] >= shape[d] for d >= 1, ld[0] not used), each array its own; NULL =
+ * dense. a and b may each be a DEVICE pointer (memory of `device`) or a HOST pointer -- the call
+ * finds out itself. Device arrays are read in place, once, by one launch of the reduction kernel
+ * (plus a one-workgroup launch that folds the per-workgroup results in a fixed order): no
+ * floating-point atomics, and the slabs of the workgroups depend on the number of elements only, so
+ * for the same shape and the same position of `a` relative to a 16-byte boundary (which decides the
+ * scalar head of a slab) the result is bit-reproducible from call to call and from device to device;
+ * at another alignment of `a` only the last bits of the two sums may differ. A host array travels
+ * through a device buffer in slabs of at most 64 MB whose results are folded in order (the sums
+ * then round differently from the one-launch sums; everything else is exact); with a host array in
+ * the call both arrays must be dense (MGH_ERR_INVALID_ARGUMENT otherwise).
+ * SYNCHRONOUS: *h_out is filled when the call returns. `stream`: the work is queued there. No
+ * hierarchy is needed. The scratch for the per-workgroup results is the call's own for as long as
+ * it runs (taken from a list of idle buffers of the device and put back on return), so calls in
+ * flight on different streams or threads never share one. The list holds as many buffers (147 KB
+ * each) as calls have run at the same time; mgh_release_cache (mgard_hip_compress.h) frees it. Errors (MGH_ERR_INVALID_ARGUMENT, message in mgh_last_error, nothing launched):
+ * D outside 1 ... MGH_MAX_DIM, an unknown dtype, a NULL shape / a / b / h_out, ld[d] < shape[d],
+ * a device that does not exist. */
+int mgh_compare(int D, int dtype, const uint64_t *shape, const void *a, const uint64_t *ld_a,
+                const void *b, const uint64_t *ld_b, mgh_error_stats *h_out, int device, void *stream);
+
 /* Measurement aid for the roofline line (no reference counterpart): a PURE stream with the
  * read/write mix of the top-level pass of the hot path -- n elements of `dtype` read once,
  * n int64 written once with streaming stores, two side arrays of n/8 elements written -- and

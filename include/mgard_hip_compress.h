@@ -266,6 +266,35 @@ int mgh_decompress_preview_window(const void *compressed_data, size_t compressed
                                   const uint64_t *ext, void **decompressed_data, const mgh_config *config,
                                   int output_pre_allocated);
 
+/* EXTENSION: how far is a container from the data it was made from? mgh_error_stats (mgard_hip.h)
+ * of `original` (the reference array, a) against what mgh_decompress -- halvings = 0 -- or
+ * mgh_decompress_preview -- halvings > 0, with its range check -- would write (b), WITHOUT that
+ * array ever existing. Every subdomain goes through the decoder's own path up to the dense
+ * subdomain in its lane's buffer (halvings > 0: mgh_prolong last) and is then compared with the
+ * same box of `original` by the kernel of mgh_compare: a device-resident original is read in place
+ * through the box's offset and the array's strides, the box of a host-resident one is uploaded into
+ * a second buffer of the lane. The partial results are folded in subdomain order (merge,
+ * csrc/compare_plan.hpp); stats.argmax is the flat index in the FULL array. Device memory: the
+ * lanes' buffers, plus one box per lane for a host original -- nothing of the size of the array.
+ * original_bytes / original_dtype are checked against the header before any work, as
+ * mgh_decompress_into checks its buffer (MGH_ERR_INVALID_ARGUMENT). Container and original may each
+ * be in host or device memory.
+ * The bound (halvings = 0 only): s = inf: bound_kind 0, achieved = stats.max_abs_err; s = 0:
+ * bound_kind 1, achieved = sqrt(sum_sq_err / (n - nonfinite)) with config->normalize_coordinates,
+ * else sqrt(sum_sq_err); bound = tol, or tol * the header's norm for a REL container; within =
+ * achieved <= bound, and 0 whenever stats.nonfinite > 0. Any other s: the bound is in the s-norm,
+ * which this call does not compute -- bound_kind = within = -1. halvings > 0: a preview carries no
+ * bound, within = -1 (bound_kind and bound are still the header's); stats is the point. */
+typedef struct mgh_verify_result {
+  mgh_error_stats stats;
+  int bound_kind;  /* 0: L-infinity (s = inf), 1: L2 (s = 0), -1: not evaluated */
+  double bound;    /* absolute: tol, or tol * the header's norm for REL */
+  double achieved; /* max_abs_err, or l2_error(config->normalize_coordinates) */
+  int within;      /* 1 / 0 / -1 */
+} mgh_verify_result;
+int mgh_verify(const void *compressed_data, size_t compressed_size, const void *original, size_t original_bytes,
+               int original_dtype, int halvings, const mgh_config *config, mgh_verify_result *out);
+
 /* What the last mgh_decompress* call of the calling thread did in its lossless stage (thread-local;
  * zeros before the first call; a failed call leaves what it had counted). Raw records count in
  * subdomains and record_bytes only. */
@@ -293,7 +322,8 @@ int mgh_pin_memory(void *ptr, size_t num_bytes);
 int mgh_check_memory_pinned(const void *ptr); /* 1 = pinned, 0 = not */
 int mgh_unpin_memory(void *ptr);
 void mgh_free_device(void *p);
-/* release_cache (compress_x.hpp:159): drops this thread's cached hierarchies and buffers. */
+/* release_cache (compress_x.hpp:159): drops this thread's cached hierarchies and buffers, and the
+ * idle scratch buffers of mgh_compare (those belong to the process, not to a thread). */
 void mgh_release_cache(void);
 /* Synchronous copy between any two of host / device memory (hipMemcpyDefault); lets a host
  * language without HIP bindings read the buffers the contexts own. */

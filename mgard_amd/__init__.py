@@ -36,11 +36,44 @@ SYMBOLS = [
     "mgh_prolong", "mgh_debug_prolong_plan",
     "mgh_prolong_window", "mgh_prolong_window_strided", "mgh_debug_prolong_window_ranges",
     "mgh_debug_prolong_window_plan",
+    "mgh_compare",
 ]
 
 
 class MgardHipError(RuntimeError):
     pass
+
+
+class ErrorStats(C.Structure):
+    """mgh_error_stats (include/mgard_hip.h): statistics of a reference array `a` against an array `b`.
+    Positions whose difference is not finite are counted in `nonfinite` and take part in nothing else."""
+    _fields_ = [("n", C.c_uint64), ("nonfinite", C.c_uint64), ("max_abs_err", C.c_double), ("argmax", C.c_uint64),
+                ("sum_sq_err", C.c_double), ("ref_min", C.c_double), ("ref_max", C.c_double),
+                ("ref_abs_max", C.c_double), ("ref_sum_sq", C.c_double)]
+
+    @property
+    def mse(self):
+        m = self.n - self.nonfinite
+        return self.sum_sq_err / m if m else 0.0
+
+    @property
+    def rmse(self):
+        return float(np.sqrt(self.mse))
+
+    @property
+    def psnr(self):
+        """20 log10((ref_max - ref_min) / rmse); +inf for a zero error."""
+        r = self.rmse
+        if r == 0:
+            return INF
+        with np.errstate(divide="ignore"):
+            return float(20.0 * np.log10(np.float64(self.ref_max - self.ref_min) / r))
+
+    def l2_error(self, normalize=True):
+        return float(np.sqrt(self.mse if normalize else self.sum_sq_err))
+
+    def __repr__(self):
+        return "ErrorStats(%s)" % ", ".join("%s=%r" % (k, getattr(self, k)) for k, _ in self._fields_)
 
 
 def lib_path():
@@ -121,6 +154,7 @@ def load_library():
     L.mgh_debug_prolong_window_ranges.argtypes = [vp, C.c_int, u64p, u64p, i64p, u64]
     L.mgh_debug_prolong_window_plan.argtypes = [vp, C.c_int, u64p, u64p, C.c_int, C.POINTER(C.c_int)]
     L.mgh_stream_calibrate.argtypes = [C.c_int, vp, vp, vp, u64, C.c_int, C.POINTER(C.c_double), vp]
+    L.mgh_compare.argtypes = [C.c_int, C.c_int, u64p, vp, u64p, vp, u64p, C.POINTER(ErrorStats), C.c_int, vp]
     _lib = L
     return L
 
@@ -137,6 +171,66 @@ def _stream():
 
 
 _NP = {FLOAT: np.float32, DOUBLE: np.float64}
+
+
+def _leading_dims(t):
+    """The leading dimensions (mgh_set_ld's convention) that describe the strides of a cuda tensor, or
+    None where they cannot (the caller then compares a contiguous copy)."""
+    shape, strides = tuple(t.shape), tuple(t.stride())
+    D = len(shape)
+    ld = list(shape)
+    for d in range(D - 1, 0, -1):
+        if shape[d - 1] > 1 and strides[d] > 0 and strides[d - 1] % strides[d] == 0:
+            ld[d] = strides[d - 1] // strides[d]
+    run = 1
+    for d in range(D - 1, -1, -1):
+        if shape[d] > 1 and strides[d] != run:
+            return None
+        if d > 0 and ld[d] < shape[d]:
+            return None
+        run *= ld[d]
+    return ld
+
+
+def compare(a, b, device=None):
+    """mgh_compare: ErrorStats of `a` (the reference) against `b`, in one pass on the device. Each of the
+    two is a cuda tensor or a NumPy array, float32 or float64 alike and of one shape. A cuda tensor whose
+    rows are padded (a slice of a larger allocation: strides that leading dimensions describe) is read in
+    place, its padding passed as `ld`; any other layout is compared through a contiguous copy. With a
+    NumPy array in the call both are compared dense."""
+    import torch
+    if tuple(a.shape) != tuple(b.shape):
+        raise ValueError("compare: the arrays have different shapes")
+    tensors = [x for x in (a, b) if isinstance(x, torch.Tensor)]
+    if any(not x.is_cuda for x in tensors):
+        raise ValueError("compare: tensors must be cuda tensors (pass host data as NumPy arrays)")
+    if device is None:
+        device = tensors[0].device.index if tensors else torch.cuda.current_device()
+    host = len(tensors) < 2
+    keep, ptrs, lds, dts = [], [], [], []
+    for x in (a, b):
+        if isinstance(x, torch.Tensor):
+            ld = None if host else _leading_dims(x)
+            if ld is None and not x.is_contiguous():
+                x = x.contiguous()
+            dts.append({torch.float32: FLOAT, torch.float64: DOUBLE}.get(x.dtype))
+            ptrs.append(C.c_void_p(x.data_ptr()))
+        else:
+            x = np.ascontiguousarray(x)
+            ld = None
+            dts.append({np.dtype(np.float32): FLOAT, np.dtype(np.float64): DOUBLE}.get(x.dtype))
+            ptrs.append(C.c_void_p(x.ctypes.data))
+        keep.append(x)
+        lds.append(None if ld is None or list(ld) == list(x.shape) else (C.c_uint64 * len(ld))(*ld))
+    if dts[0] is None or dts[0] != dts[1]:
+        raise ValueError("compare: float32 or float64 arrays of one type expected")
+    shape = tuple(int(e) for e in a.shape)
+    out = ErrorStats()
+    with torch.cuda.device(device):
+        stream = _stream()
+    _check(load_library().mgh_compare(len(shape), dts[0], (C.c_uint64 * max(len(shape), 1))(*shape), ptrs[0], lds[0],
+                                      ptrs[1], lds[1], C.byref(out), int(device), stream))
+    return out
 
 
 class Hierarchy:

@@ -23,6 +23,7 @@
 
 #include "env.hpp"
 #include "hierarchy.hpp"
+#include "ld_view.hpp"
 #include "ipk_plan.hpp"
 #include "fused_plan.hpp"
 #include "kernels_v1.hpp"
@@ -42,6 +43,8 @@
 #include "kernels_prolong_win.hpp"
 #include "prolong_plan.hpp"
 #include "prolong_window_plan.hpp"
+#include "compare_plan.hpp"
+#include "kernels_compare.hpp"
 
 namespace {
 
@@ -946,11 +949,7 @@ inline bool fused_route(const mgh_hierarchy *h) { return fusedc_ok(h) && !h->for
 // fastest dimension; SubArray.hpp:136-139 carries one ld per dimension) ------------------------
 // Rows of the array (all dimensions but the fastest, right-aligned, leading 1s) and the element
 // strides of those dimensions.
-struct LdView {
-  uint32_t ext[MGH_MAX_DIM];
-  uint64_t stride[MGH_MAX_DIM];
-  uint64_t rows;
-};
+// (struct LdView: ld_view.hpp)
 // How a T array of the full shape lies in memory. A layout belongs to an ARGUMENT: it is made where
 // the caller's pointer enters the library (caller_layout, in the extern "C" entry points) and passed
 // down beside the pointer; the buffers of the hierarchy are dense (dense_layout). A function without
@@ -2635,16 +2634,7 @@ int prolong_window_impl(mgh_hierarchy *h, int level, const T *lvl, const uint64_
 }
 
 // ---- kernels on pitched arrays (Layout::view) ----------------------------------------------------
-__device__ __forceinline__ uint64_t ld_row_offset(const LdView &V, uint64_t row) {
-  uint64_t r = row, off = 0;
-#pragma unroll
-  for (int d = MGH_MAX_DIM - 2; d >= 0; d--) {
-    const uint64_t q = r / V.ext[d];
-    off += (r - q * V.ext[d]) * V.stride[d];
-    r = q;
-  }
-  return off;
-}
+// (ld_row_offset: ld_view.hpp)
 // dense <-> pitched, one wave per row
 template <typename T>
 __global__ void __launch_bounds__(256) k_ld_copy(T *__restrict__ dense, T *__restrict__ pitched, LdView V, int to_dense) {
@@ -3907,6 +3897,228 @@ int mgh_stream_calibrate(int dtype, const void *d_in, int64_t *d_out, void *d_si
   HIP_TRY(hipGetLastError());
   *ms_out = (double)ms / reps;
   return MGH_SUCCESS;
+}
+
+// ---- mgh_compare ----------------------------------------------------------------------------------
+} // extern "C"
+
+namespace {
+
+// Device scratch of the reduction: the result, then one partial per workgroup.
+constexpr size_t kCompareScratchBytes = (size_t)(mgh::kCompareMaxGroups + 1) * sizeof(mgh_error_stats);
+// A host array travels to the device in slabs of this many bytes at most.
+constexpr size_t kCompareStageBytes = (size_t)64 << 20;
+
+// rows and strides of an array of `shape` with the element strides `str` (str[D - 1] == 1)
+LdView compare_view(int D, const uint64_t *shape, const uint64_t *str) {
+  LdView V{};
+  V.rows = 1;
+  for (int k = 0; k < MGH_MAX_DIM; k++) {
+    const int d = k - (MGH_MAX_DIM - D);
+    V.ext[k] = d >= 0 ? (uint32_t)shape[d] : 1u;
+    V.stride[k] = d >= 0 ? str[d] : 0;
+    if (k < MGH_MAX_DIM - 1) V.rows *= V.ext[k];
+  }
+  return V;
+}
+
+bool compare_is_dense(int D, const uint64_t *shape, const uint64_t *str) {
+  if (!str) return true;
+  uint64_t run = 1;
+  for (int d = D - 1; d >= 0; d--) {
+    if (shape[d] != 1 && str[d] != run) return false;
+    run *= shape[d];
+  }
+  return true;
+}
+
+template <typename T>
+int compare_launch(int D, const uint64_t *shape, const T *a, const uint64_t *str_a, const T *b, const uint64_t *str_b,
+                   mgh_error_stats *d_scratch, hipStream_t st) {
+  uint64_t n = 1;
+  for (int d = 0; d < D; d++) n *= shape[d];
+  const ComparePlan p = compare_plan(n, sizeof(T));
+  mgh_error_stats *partials = d_scratch + 1;
+  if (p.groups) {
+    if (compare_is_dense(D, shape, str_a) && compare_is_dense(D, shape, str_b)) {
+      k_compare<T><<<(unsigned)p.groups, 256, 0, st>>>(a, b, n, p.slab, partials);
+    } else {
+      uint64_t dense[MGH_MAX_DIM];
+      compact_strides(D, shape, dense);
+      const LdView Va = compare_view(D, shape, str_a ? str_a : dense), Vb = compare_view(D, shape, str_b ? str_b : dense);
+      k_compare_ld<T><<<(unsigned)p.groups, 256, 0, st>>>(a, Va, b, Vb, n, p.slab, partials);
+    }
+    HIP_TRY(hipGetLastError());
+  }
+  k_compare_final<<<1, 256, 0, st>>>(partials, (uint32_t)p.groups, d_scratch);
+  HIP_TRY(hipGetLastError());
+  return MGH_SUCCESS;
+}
+
+// Scratch of ONE call: taken from a per-device list of idle buffers (allocated when the list is empty)
+// and put back when the call returns, so two calls in flight -- on whatever streams and threads --
+// never share one, and the library holds as many buffers as calls have ever run at the same time,
+// however many threads come and go. Idle buffers stay until mgh_release_cache (release_idle) or the
+// end of the process.
+struct CompareScratch {
+  int device = -1;
+  void *p = nullptr;
+  hipStream_t st = nullptr;
+  bool drained = false;  // the call's last use of the buffer is known to be over
+  static std::mutex &lock() {
+    static std::mutex m;
+    return m;
+  }
+  static std::map<int, std::vector<void *>> &idle() {
+    static auto *m = new std::map<int, std::vector<void *>>();  // (never destroyed: no HIP call at exit)
+    return *m;
+  }
+  int acquire(int dev) {
+    device = dev;
+    {
+      std::lock_guard<std::mutex> g(lock());
+      auto &v = idle()[dev];
+      if (!v.empty()) {
+        p = v.back();
+        v.pop_back();
+        return MGH_SUCCESS;
+      }
+    }
+    HIP_TRY(hipMalloc(&p, kCompareScratchBytes));
+    return MGH_SUCCESS;
+  }
+  // frees the idle buffers of every device (buffers of calls in flight are not in the list)
+  static void release_idle() {
+    std::map<int, std::vector<void *>> gone;
+    {
+      std::lock_guard<std::mutex> g(lock());
+      gone.swap(idle());
+    }
+    for (auto &kv : gone)
+      for (void *q : kv.second) (void)hipFree(q);
+  }
+  ~CompareScratch() {
+    if (!p) return;
+    if (!drained) (void)hipStreamSynchronize(st);  // (a call that failed half way: nothing may still write to it)
+    std::lock_guard<std::mutex> g(lock());
+    idle()[device].push_back(p);
+  }
+};
+
+bool compare_on_device(const void *p) {
+  hipPointerAttribute_t at;
+  if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+    (void)hipGetLastError();
+    return false;
+  }
+  return at.type == hipMemoryTypeDevice;
+}
+
+struct CompareStage {
+  void *p = nullptr;
+  ~CompareStage() {
+    if (p) (void)hipFree(p);
+  }
+};
+
+template <typename T>
+int compare_host(uint64_t n, const T *a, bool a_dev, const T *b, bool b_dev, mgh_error_stats *d_scratch,
+                 mgh_error_stats *h_out, hipStream_t st) {
+  // slabs of whole 16-byte vectors, so that the alignment of every slab is that of the array
+  const uint64_t chunk = std::min<uint64_t>(std::max<uint64_t>(n, 1), kCompareStageBytes / sizeof(T));
+  CompareStage sa, sb;
+  if (!a_dev) HIP_TRY(hipMalloc(&sa.p, chunk * sizeof(T)));
+  if (!b_dev) HIP_TRY(hipMalloc(&sb.p, chunk * sizeof(T)));
+  mgh_error_stats total{};
+  for (uint64_t at = 0; at < n; at += chunk) {
+    const uint64_t len = std::min(chunk, n - at);
+    const T *pa = a + at, *pb = b + at;
+    if (!a_dev) {
+      HIP_TRY(hipMemcpyAsync(sa.p, pa, len * sizeof(T), hipMemcpyHostToDevice, st));
+      pa = (const T *)sa.p;
+    }
+    if (!b_dev) {
+      HIP_TRY(hipMemcpyAsync(sb.p, pb, len * sizeof(T), hipMemcpyHostToDevice, st));
+      pb = (const T *)sb.p;
+    }
+    TRY(compare_launch<T>(1, &len, pa, nullptr, pb, nullptr, d_scratch, st));
+    mgh_error_stats part;
+    HIP_TRY(hipMemcpyAsync(&part, d_scratch, sizeof(part), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    merge(total, part, at);
+  }
+  *h_out = total;
+  return MGH_SUCCESS;
+}
+
+template <typename T>
+int compare_entry(int D, const uint64_t *shape, const void *a, const uint64_t *ld_a, const void *b, const uint64_t *ld_b,
+                  mgh_error_stats *h_out, int device, hipStream_t st) {
+  CompareScratch scratch;
+  TRY(scratch.acquire(device));
+  scratch.st = st;
+  mgh_error_stats *d_scratch = (mgh_error_stats *)scratch.p;
+  const bool a_dev = compare_on_device(a), b_dev = compare_on_device(b);
+  uint64_t sa[MGH_MAX_DIM], sb[MGH_MAX_DIM];
+  if (ld_a) compact_strides(D, ld_a, sa);
+  if (ld_b) compact_strides(D, ld_b, sb);
+  const uint64_t *str_a = ld_a ? sa : nullptr, *str_b = ld_b ? sb : nullptr;
+  if (!a_dev || !b_dev) {
+    if (!compare_is_dense(D, shape, str_a) || !compare_is_dense(D, shape, str_b))
+      return fail(MGH_ERR_INVALID_ARGUMENT, "mgh_compare: with an array in host memory both arrays must be dense");
+    uint64_t n = 1;
+    for (int d = 0; d < D; d++) n *= shape[d];
+    const int rc = compare_host<T>(n, (const T *)a, a_dev, (const T *)b, b_dev, d_scratch, h_out, st);
+    scratch.drained = rc == MGH_SUCCESS;  // (its last step is a synchronise)
+    return rc;
+  }
+  TRY(compare_launch<T>(D, shape, (const T *)a, str_a, (const T *)b, str_b, d_scratch, st));
+  HIP_TRY(hipMemcpyAsync(h_out, d_scratch, sizeof(*h_out), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  scratch.drained = true;
+  return MGH_SUCCESS;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mgh_compare(int D, int dtype, const uint64_t *shape, const void *a, const uint64_t *ld_a, const void *b,
+                const uint64_t *ld_b, mgh_error_stats *h_out, int device, void *stream) {
+  if (D < 1 || D > MGH_MAX_DIM) return fail(MGH_ERR_INVALID_ARGUMENT, "mgh_compare: D must be 1 .. MGH_MAX_DIM");
+  if (dtype != MGH_FLOAT && dtype != MGH_DOUBLE) return fail(MGH_ERR_INVALID_ARGUMENT, "mgh_compare: unknown dtype");
+  if (!shape || !a || !b || !h_out) return fail(MGH_ERR_INVALID_ARGUMENT, "mgh_compare: NULL argument");
+  for (const uint64_t *ld : {ld_a, ld_b})
+    for (int d = 1; ld && d < D; d++)
+      if (ld[d] < shape[d]) return fail(MGH_ERR_INVALID_ARGUMENT, "mgh_compare: ld[d] < shape[d]");
+  for (int d = 0; d < D; d++)
+    if (shape[d] > 0xffffffffull && D > 1)
+      return fail(MGH_ERR_INVALID_ARGUMENT, "mgh_compare: an extent of 2^32 or more in an array of more than one dimension");
+  if (device < 0 || device >= mgh_device_count()) return fail(MGH_ERR_INVALID_ARGUMENT, "mgh_compare: no such device");
+  HIP_TRY(hipSetDevice(device));
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == MGH_FLOAT) return compare_entry<float>(D, shape, a, ld_a, b, ld_b, h_out, device, st);
+  return compare_entry<double>(D, shape, a, ld_a, b, ld_b, h_out, device, st);
+}
+
+// For highlevel.hip (mgh_verify): the same reduction of two DEVICE arrays given by element strides
+// (NULL: dense; the fastest stride is 1), ASYNCHRONOUS on `stream`. d_scratch: mgh_compare_scratch_bytes_()
+// bytes of the caller's; the result is the mgh_error_stats at its start.
+size_t mgh_compare_scratch_bytes_(void) { return kCompareScratchBytes; }
+// (mgh_release_cache: the idle scratch buffers of mgh_compare)
+void mgh_compare_release_(void) { CompareScratch::release_idle(); }
+int mgh_compare_device_(int D, int dtype, const uint64_t *shape, const void *d_a, const uint64_t *stride_a,
+                        const void *d_b, const uint64_t *stride_b, void *d_scratch, void *stream) {
+  if (D < 1 || D > MGH_MAX_DIM || !shape || !d_a || !d_b || !d_scratch || (dtype != MGH_FLOAT && dtype != MGH_DOUBLE))
+    return fail(MGH_ERR_INVALID_ARGUMENT, "mgh_compare_device_: bad argument");
+  for (const uint64_t *str : {stride_a, stride_b})
+    if (str && str[D - 1] != 1) return fail(MGH_ERR_INVALID_ARGUMENT, "mgh_compare_device_: the fastest stride must be 1");
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == MGH_FLOAT)
+    return compare_launch<float>(D, shape, (const float *)d_a, stride_a, (const float *)d_b, stride_b,
+                                 (mgh_error_stats *)d_scratch, st);
+  return compare_launch<double>(D, shape, (const double *)d_a, stride_a, (const double *)d_b, stride_b,
+                                (mgh_error_stats *)d_scratch, st);
 }
 
 } // extern "C"

@@ -36,8 +36,14 @@
 #include "huffman.hpp"
 #include "env.hpp"
 #include "hierarchy.hpp"
+#include "compare_plan.hpp"
 
 extern "C" void mgh_set_last_error_(const char *msg);  // capi.hip
+// (capi.hip: the reduction of mgh_compare on two device arrays given by element strides, asynchronous)
+extern "C" size_t mgh_compare_scratch_bytes_(void);
+extern "C" void mgh_compare_release_(void);
+extern "C" int mgh_compare_device_(int D, int dtype, const uint64_t *shape, const void *d_a, const uint64_t *stride_a,
+                                   const void *d_b, const uint64_t *stride_b, void *d_scratch, void *stream);
 
 namespace {
 constexpr int kOutlierOverflow = -1000;  // internal: more outliers than the buffers hold
@@ -1939,6 +1945,7 @@ struct Lane {
   DevBuf q, q2, ocount, oidx, oval;  // q2: level-linearised copy (config.reorder == 1)
   DevBuf sub;                        // decompression: the dense subdomain when the output is not written in place
   DevBuf lvl;                        // full-grid preview: the dense array of the subdomain's level, before it is prolonged
+  DevBuf cmp, orig;                  // mgh_verify: scratch of the reduction; the box of a host-resident original
   PinBuf pin;                        // [0, 8) size prefix of a raw record, [16, 24) norm read-back
   mgh_lossless_ctx *ll = nullptr;
   uint64_t ocap = 0;                 // elements oidx / oval hold
@@ -1950,6 +1957,8 @@ struct Lane {
     oval.release();
     sub.release();
     lvl.release();
+    cmp.release();
+    orig.release();
     pin.release();
     if (ll) mgh_lossless_destroy(ll);
     ll = nullptr;
@@ -1971,14 +1980,16 @@ struct HlCache {
   hipStream_t copy_st = nullptr;  // prefetch of the next subdomains (compression), strided write-back (decompression)
   hipStream_t aux_st = nullptr;   // small device -> host reads that must not wait for the lanes
   PinBuf aux_pin;
+  DevBuf vres;  // mgh_verify: one mgh_error_stats per subdomain, read back once at the end
   int dev = -1;
   // device bytes the cache holds now (they are reused, so they count as available to the next call)
   size_t held_bytes() const {
     size_t b = 0;
     for (auto &kv : hier) b += mgh_device_bytes(kv.second);
     for (auto &x : in) b += x.cap;
+    b += vres.cap;
     for (auto &l : lane) {
-      b += l.q.cap + l.q2.cap + l.oidx.cap + l.oval.cap + l.sub.cap;
+      b += l.q.cap + l.q2.cap + l.oidx.cap + l.oval.cap + l.sub.cap + l.orig.cap + l.cmp.cap;
       if (l.ll) b += l.ll->units.cap + l.ll->oidx.cap + l.ll->oval.cap;
     }
     return b;
@@ -1994,6 +2005,7 @@ struct HlCache {
       }
     hpin.release();
     aux_pin.release();
+    vres.release();
     for (auto &l : lane) l.release();
     for (hipStream_t *s : {&copy_st, &aux_st}) {
       if (*s) (void)hipStreamDestroy(*s);
@@ -2841,6 +2853,15 @@ struct Window {
   std::vector<uint64_t> lo, ext;
 };
 
+// mgh_verify: the array every reconstructed subdomain is compared with instead of being written out,
+// and the statistics of the whole array when the call is through.
+struct VerifyJob {
+  const void *original = nullptr;
+  mgh_error_stats stats{};
+  bool rel = false;  // the bound of the header
+  double tol = 0, s = 0, norm = 0;
+};
+
 // level >= 0: mgh_decompress_level -- the output is the dense array of that level of the hierarchy.
 // halvings > 0: mgh_decompress_coarsened -- every subdomain at its level l_target_i - halvings, stitched.
 // ... and preview: mgh_decompress_preview -- every subdomain at that level, prolonged to its full shape and
@@ -2848,10 +2869,12 @@ struct Window {
 // ... and win: mgh_decompress_preview_window -- the output is the window alone; only the subdomains that
 // meet it are opened, each reconstructed as for the preview and its part of the window written by
 // mgh_prolong_window of its own hierarchy (halvings = 0: the box copy of its finest level).
+// vfy: mgh_verify -- there is no output (prealloc, *out == NULL): where finish() would copy the dense
+// subdomain into its box of the output, it is compared with that box of vfy->original instead.
 template <typename T>
 int decompress_impl(const fmt::Header &hd, size_t meta_size, const void *compressed, size_t csize_total,
                     void **out, const mgh_config &cfg_in, bool prealloc, int level = -1, int halvings = -1,
-                    bool preview = false, const Window *win = nullptr) {
+                    bool preview = false, const Window *win = nullptr, VerifyJob *vfy = nullptr) {
   mgh_config cfg = cfg_in;
   const int dtype = hd.is_double ? MGH_DOUBLE : MGH_FLOAT;
   const size_t elem = sizeof(T);
@@ -2969,7 +2992,7 @@ int decompress_impl(const fmt::Header &hd, size_t meta_size, const void *compres
       if (hipHostRegister(const_cast<void *>(compressed), csize_total, hipHostRegisterDefault) == hipSuccess) in_pinned_here = true;
       else (void)hipGetLastError();
     }
-    if (!is_device_pointer(*out) && !is_registered_host(*out)) {
+    if (!vfy && !is_device_pointer(*out) && !is_registered_host(*out)) {
       pretouch.join();
       if (hipHostRegister(*out, total * elem, hipHostRegisterDefault) == hipSuccess) out_pinned_here = true;
       else (void)hipGetLastError();
@@ -2996,9 +3019,10 @@ int decompress_impl(const fmt::Header &hd, size_t meta_size, const void *compres
   const uint64_t max_elems = dd.max_subdomain_elems();
   int rc;
   // device-resident output whose subdomains are contiguous slabs: reconstruct them in place
-  const bool zero_copy = !win && is_device_pointer(*out) && all_slabs;
+  const bool zero_copy = !win && !vfy && is_device_pointer(*out) && all_slabs;
   // windowed preview into device memory: the window kernel writes the box of the output itself
   const bool direct = win && is_device_pointer(*out);
+  const bool vfy_in_place = vfy && is_device_pointer_on(vfy->original, cfg.dev_id);  // (the original is read where it lies)
   uint64_t slab_inner = 1;  // elements of one plane of the slowest dimension of the output
   for (size_t d = 1; d < dshape.size(); d++) slab_inner *= dshape[d];
   auto ensure_all = [&]() -> int {
@@ -3008,7 +3032,10 @@ int decompress_impl(const fmt::Header &hd, size_t meta_size, const void *compres
       if (lvl_elems) HL_TRY(L.lvl.ensure(lvl_elems * elem));
       HL_TRY(L.q.ensure(q_elems * 8));
       if (q2_elems) HL_TRY(L.q2.ensure(q2_elems * 8));
+      if (vfy) HL_TRY(L.cmp.ensure(mgh_compare_scratch_bytes_()));
+      if (vfy && !vfy_in_place) HL_TRY(L.orig.ensure(sub_elems * elem));
     }
+    if (vfy) HL_TRY(g_cache.vres.ensure(order.size() * sizeof(mgh_error_stats)));
     return MGH_SUCCESS;
   };
   if ((rc = ensure_all()) != MGH_SUCCESS) return cleanup(rc);
@@ -3118,6 +3145,27 @@ int decompress_impl(const fmt::Header &hd, size_t meta_size, const void *compres
     if (zero_copy || direct) return MGH_SUCCESS;
     pretouch.join();
     Lane &L = g_cache.lane[k % nlanes];
+    if (vfy) {
+      const SubdomainPlan &P = plan[order[k]];
+      const void *a = L.orig.p;
+      uint64_t astr[MGH_MAX_DIM];
+      if (vfy_in_place) {  // the box through its offset and the strides of the array
+        uint64_t run = 1, at = 0;
+        for (int d = dd.D - 1; d >= 0; d--) {
+          astr[d] = run;
+          at += P.off[d] * run;
+          run *= dshape[d];
+        }
+        a = (const char *)vfy->original + at * elem;
+      } else {
+        HL_TRY(copy_box(P.ext, P.off, dshape, elem, L.orig.p, vfy->original, nullptr, true, L.st));
+      }
+      HL_TRY(mgh_compare_device_(dd.D, dtype, P.ext.data(), a, vfy_in_place ? astr : nullptr, L.sub.p, nullptr, L.cmp.p,
+                                 L.st));
+      HL_HIP(hipMemcpyAsync((char *)g_cache.vres.p + k * sizeof(mgh_error_stats), L.cmp.p, sizeof(mgh_error_stats),
+                            hipMemcpyDeviceToDevice, L.st));
+      return MGH_SUCCESS;
+    }
     return copy_box(plan[order[k]].ext, plan[order[k]].off, dshape, elem, L.sub.p, nullptr, *out, false, L.st);
   };
   if ((rc = issue(0)) != MGH_SUCCESS) return cleanup(rc);
@@ -3129,6 +3177,25 @@ int decompress_impl(const fmt::Header &hd, size_t meta_size, const void *compres
   for (int l = 0; l < nlanes; l++) {
     if (hipStreamSynchronize(g_cache.lane[l].st) != hipSuccess) return cleanup(hl_fail(MGH_ERR_DEVICE, "sync"));
     if ((rc = lossless_tag_check(g_cache.lane[l].ll)) != MGH_SUCCESS) return cleanup(rc);
+  }
+  if (vfy) {
+    // the subdomains' results, in subdomain order; a box's argmax becomes the index in the whole array
+    std::vector<mgh_error_stats> parts(order.size());
+    if (hipMemcpy(parts.data(), g_cache.vres.p, parts.size() * sizeof(mgh_error_stats), hipMemcpyDeviceToHost) != hipSuccess)
+      return cleanup(hl_fail(MGH_ERR_DEVICE, "mgh_verify: reading the results back"));
+    vfy->stats = mgh_error_stats{};
+    for (uint64_t k = 0; k < order.size(); k++) {
+      const SubdomainPlan &P = plan[order[k]];
+      mgh_error_stats part = parts[k];
+      uint64_t rest = part.argmax, run = 1, at = 0;
+      for (int d = dd.D - 1; d >= 0; d--) {
+        at += (P.off[d] + rest % P.ext[d]) * run;
+        rest /= P.ext[d];
+        run *= dshape[d];
+      }
+      part.argmax = mgh::compare_finite(part) ? at : 0;
+      mgh::merge(vfy->stats, part, 0);
+    }
   }
   return cleanup(MGH_SUCCESS);
 }
@@ -3206,7 +3273,7 @@ int mgh_compress(int D, int dtype, const uint64_t *shape, double tol, double s, 
 static int decompress_entry(const void *compressed_data, size_t compressed_size, void **decompressed_data,
                             const mgh_config *config, int output_pre_allocated, size_t expect_bytes, int expect_dtype,
                             int level = -1, int halvings = -1, bool preview = false, const uint64_t *win_lo = nullptr,
-                            const uint64_t *win_ext = nullptr);
+                            const uint64_t *win_ext = nullptr, VerifyJob *vfy = nullptr);
 
 int mgh_decompress_preview(const void *compressed_data, size_t compressed_size, int halvings, void **decompressed_data,
                            const mgh_config *config, int output_pre_allocated) {
@@ -3255,12 +3322,17 @@ int mgh_decompress_into(const void *compressed_data, size_t compressed_size, voi
 
 // expect_dtype >= 0: the caller's buffer holds expect_bytes bytes of that type -- checked against the
 // header the call reads anyway, before anything is written (mgh_decompress_into)
+// vfy: mgh_verify -- the buffer is the ORIGINAL (vfy->original) and there is no output; the bound of
+// the header is left in vfy for the caller to evaluate
 static int decompress_entry(const void *compressed_data, size_t compressed_size, void **decompressed_data,
                             const mgh_config *config, int output_pre_allocated, size_t expect_bytes, int expect_dtype,
-                            int level, int halvings, bool preview, const uint64_t *win_lo, const uint64_t *win_ext) {
+                            int level, int halvings, bool preview, const uint64_t *win_lo, const uint64_t *win_ext,
+                            VerifyJob *vfy) {
+  const char *who = vfy ? "mgh_verify" : "mgh_decompress_into";
   decompress_stats() = mgh_decompress_stats{};
   if (!compressed_data || !decompressed_data) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "NULL argument");
-  if (output_pre_allocated && !*decompressed_data) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "pre-allocated output is NULL");
+  if (!vfy && output_pre_allocated && !*decompressed_data)
+    return hl_fail(MGH_ERR_INVALID_ARGUMENT, "pre-allocated output is NULL");
   {
     const std::string bad = env_validate();
     if (!bad.empty()) return hl_fail(MGH_ERR_INVALID_ARGUMENT, bad);
@@ -3284,9 +3356,16 @@ static int decompress_entry(const void *compressed_data, size_t compressed_size,
     size_t need = hd.is_double ? 8 : 4;
     for (uint64_t e : hd.shape) need *= e;
     if ((expect_dtype == MGH_DOUBLE) != hd.is_double)
-      return hl_fail(MGH_ERR_INVALID_ARGUMENT, "mgh_decompress_into: the stream holds the other data type");
+      return hl_fail(MGH_ERR_INVALID_ARGUMENT, std::string(who) + ": the stream holds the other data type");
     if (expect_bytes != need)
-      return hl_fail(MGH_ERR_INVALID_ARGUMENT, "mgh_decompress_into: the buffer does not have the size of the array in the stream");
+      return hl_fail(MGH_ERR_INVALID_ARGUMENT,
+                     std::string(who) + ": the buffer does not have the size of the array in the stream");
+  }
+  if (vfy) {
+    vfy->rel = hd.rel;
+    vfy->tol = hd.tol;
+    vfy->s = hd.s;
+    vfy->norm = hd.norm;
   }
   Window window;
   if (win_lo) {
@@ -3300,12 +3379,39 @@ static int decompress_entry(const void *compressed_data, size_t compressed_size,
   try {
     if (hd.is_double)
       return decompress_impl<double>(hd, meta_size, compressed_data, compressed_size, decompressed_data,
-                                     *config, output_pre_allocated != 0, level, halvings, preview, win);
+                                     *config, output_pre_allocated != 0, level, halvings, preview, win, vfy);
     return decompress_impl<float>(hd, meta_size, compressed_data, compressed_size, decompressed_data,
-                                  *config, output_pre_allocated != 0, level, halvings, preview, win);
+                                  *config, output_pre_allocated != 0, level, halvings, preview, win, vfy);
   } catch (const std::exception &e) {
     return hl_fail(MGH_ERR_DEVICE, e.what());
   }
+}
+
+
+int mgh_verify(const void *compressed_data, size_t compressed_size, const void *original, size_t original_bytes,
+               int original_dtype, int halvings, const mgh_config *config, mgh_verify_result *out) {
+  if (!original || !out) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (original_dtype != MGH_FLOAT && original_dtype != MGH_DOUBLE) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "mgh_verify: dtype");
+  if (halvings < 0)
+    return hl_fail(MGH_ERR_INVALID_ARGUMENT, "halvings outside 0 .. the smallest l_target of the subdomains");
+  VerifyJob job;
+  job.original = original;
+  void *none = nullptr;  // (there is no output: pre-allocated, and never looked at)
+  // (halvings = 0 goes the way of mgh_decompress_preview(0), which is mgh_decompress)
+  const int rc = decompress_entry(compressed_data, compressed_size, &none, config, 1, original_bytes, original_dtype, -1,
+                                  halvings, true, nullptr, nullptr, &job);
+  if (rc != MGH_SUCCESS) return rc;
+  const bool normalize = config ? config->normalize_coordinates != 0 : true;
+  mgh_verify_result r{};
+  r.stats = job.stats;
+  r.bound = job.rel ? job.tol * job.norm : job.tol;
+  r.bound_kind = std::isinf(job.s) ? 0 : job.s == 0 ? 1 : -1;
+  r.achieved = r.bound_kind == 0 ? r.stats.max_abs_err
+               : r.bound_kind == 1 ? mgh::l2_error(r.stats, normalize) : 0.0;
+  if (halvings > 0 || r.bound_kind < 0) r.within = -1;  // (a preview carries no bound)
+  else r.within = r.stats.nonfinite == 0 && r.achieved <= r.bound ? 1 : 0;
+  *out = r;
+  return MGH_SUCCESS;
 }
 
 }  // extern "C"
@@ -4326,6 +4432,7 @@ void mgh_free_device(void *p) {
 void mgh_release_cache(void) {
   if (g_cache_ptr) g_cache_ptr->release();
   release_host_transfer_state();  // pinned rings, copy threads
+  mgh_compare_release_();         // idle scratch buffers of mgh_compare (process-wide)
 }
 
 int mgh_memcpy(void *dst, const void *src, size_t bytes) {

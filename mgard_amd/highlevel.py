@@ -10,7 +10,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import ABS, DOUBLE, FLOAT, INF, REL, MgardHipError, _check, load_library  # noqa: F401
+from . import ABS, DOUBLE, FLOAT, INF, REL, ErrorStats, MgardHipError, _check, load_library  # noqa: F401
 
 MAX_DIM = 5
 DD_MAXDIM, DD_BLOCK, DD_VARIABLE = 0, 1, 2
@@ -31,6 +31,7 @@ HL_SYMBOLS = [
     "mgh_infer_coarsened_shape", "mgh_infer_coarsened_nodes", "mgh_decompress_coarsened",
     "mgh_decompress_preview", "mgh_progressive_preview",
     "mgh_decompress_preview_window", "mgh_progressive_preview_window",
+    "mgh_verify",
 ]
 
 
@@ -74,6 +75,18 @@ class DecompressStats(C.Structure):
     _fields_ = [("subdomains", C.c_uint64), ("chunks_total", C.c_uint64), ("chunks_decoded", C.c_uint64),
                 ("symbols_decoded", C.c_uint64), ("record_bytes", C.c_uint64),
                 ("record_bytes_moved", C.c_uint64)]
+
+
+class VerifyResult(C.Structure):
+    """mgh_verify_result: `stats` (ErrorStats) of the original against the container's reconstruction;
+    bound_kind 0: L-infinity, 1: L2, -1: not evaluated; `bound` absolute; `achieved` the matching figure
+    of stats; `within` 1 / 0 / -1 (not evaluated: a preview, or a bound in an s-norm)."""
+    _fields_ = [("stats", ErrorStats), ("bound_kind", C.c_int), ("bound", C.c_double), ("achieved", C.c_double),
+                ("within", C.c_int)]
+
+    def __repr__(self):
+        return "VerifyResult(stats=%r, bound_kind=%d, bound=%r, achieved=%r, within=%d)" % (
+            self.stats, self.bound_kind, self.bound, self.achieved, self.within)
 
 
 class HeaderInfo(C.Structure):
@@ -126,6 +139,7 @@ def _hl():
     L.mgh_decompress_preview.argtypes = [vp, C.c_size_t, C.c_int, C.POINTER(vp), vp, C.c_int]
     L.mgh_decompress_preview_window.argtypes = [vp, C.c_size_t, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
                                                 C.POINTER(vp), vp, C.c_int]
+    L.mgh_verify.argtypes = [vp, C.c_size_t, vp, C.c_size_t, C.c_int, C.c_int, vp, C.POINTER(VerifyResult)]
     L.mgh_dist_use_library.argtypes = [C.c_char_p]
     L.mgh_compress_dist.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(u64), C.c_double,
                                     C.c_double, C.c_int, vp, C.POINTER(vp), C.POINTER(C.c_size_t), vp, vp, C.c_int]
@@ -546,6 +560,28 @@ def decompress_preview(buf, coarsen, config=None, out=None, window=None):
     if coarsen is None:
         raise ValueError("decompress_preview needs `coarsen`")
     return _decompress(buf, config, out, None, coarsen, True, window)
+
+
+def verify(buf, original, config=None, coarsen=0):
+    """mgh_verify (extension): the error statistics of `original` (numpy array or cuda tensor, the data the
+    container was made from) against decompress(buf) -- coarsen = 0 -- or decompress_preview(buf, coarsen),
+    without that array being made: subdomain by subdomain, each compared on the device with its box of the
+    original. Returns a VerifyResult; container and original may each live on the host or the device."""
+    import torch
+    L = _hl()
+    cfg = config if config is not None else Config()
+    if isinstance(buf, torch.Tensor) and buf.is_cuda:
+        buf = buf.contiguous()
+        p, n = C.c_void_p(buf.data_ptr()), buf.numel()
+    else:
+        buf = np.ascontiguousarray(buf)
+        p, n = C.c_void_p(buf.ctypes.data), buf.size
+    optr, dt, shape, keep = _as_ptr(original)
+    nbytes = int(np.prod(shape)) * (4 if dt == FLOAT else 8)
+    out = VerifyResult()
+    _check(L.mgh_verify(p, n, optr, nbytes, dt, int(coarsen), C.byref(cfg), C.byref(out)))
+    del keep
+    return out
 
 
 def _decompress(buf, config, out, level, coarsen, full_grid, window=None):
