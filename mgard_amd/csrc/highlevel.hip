@@ -34,6 +34,7 @@
 
 #include "format.hpp"
 #include "huffman.hpp"
+#include "huffman_record.hpp"
 #include "env.hpp"
 #include "hierarchy.hpp"
 #include "compare_plan.hpp"
@@ -114,6 +115,15 @@ int hl_fail(int code, const std::string &msg) {
     int _rc = (expr);                      \
     if (_rc != MGH_SUCCESS) return _rc;    \
   } while (0)
+
+// the dynamic-LDS limit of some kernels, once per device (hl_attr_pending)
+template <typename... K> int hl_lds_limit(std::atomic<uint64_t> &once, int bytes, K... kernels) {
+  if (!hl_attr_pending(once)) return MGH_SUCCESS;
+  for (const void *k : {reinterpret_cast<const void *>(kernels)...})
+    HL_HIP(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+  hl_attr_done(once);
+  return MGH_SUCCESS;
+}
 
 // MemoryManager::IsDevicePointer
 bool is_device_pointer(const void *p) {
@@ -220,45 +230,6 @@ struct ZstdApi {
 };
 ZstdApi g_zstd;
 
-// ---- serialized Huffman record: offsets with natural alignment (Huffman.hpp:163-239) --------
-inline size_t align_up(size_t off, size_t a) { return (off + a - 1) / a * a; }
-
-struct PayloadLayout {
-  size_t primary_count = 0, huffmeta = 0, decodebook_size = 0, decodebook = 0, ddata_size = 0,
-         ddata = 0, outlier_count = 0, outlier_idx = 0, outliers = 0, total = 0;
-  // Behind the reference's payload (its reader stops at the outlier lists), optional: the decoder's
-  // synchronisation points (huffman.hpp: k_encode_chain), [u64 kSyncTag][u32 x 64 per chunk]. The
-  // section's size is 8 (mod 16) while the outlier lists' is 0: a reader that knows the record's
-  // size and where the lists start sees from the remainder whether it is there.
-  size_t sync_tag = 0, sync = 0;
-  static constexpr uint64_t kSyncTag = 0x31434e595348474dull;  // "MGHSYNC1"
-  static size_t sync_bytes(size_t nchunk) { return 8 + 4 * (size_t)huff::kSyncLanes * nchunk; }
-  // offsets of: primary_count, dict_size, chunk_size, huffmeta_size are fixed (0, 8, 12, 16)
-  void compute(size_t nchunk, size_t dict, size_t units, size_t noutlier, bool with_sync = false) {
-    size_t off = 0;
-    primary_count = off; off += 8;
-    off += 4;  // dict_size (int)
-    off += 4;  // chunk_size (int)
-    off = align_up(off, 8); off += 8;  // huffmeta_size
-    huffmeta = off; off += 8 * 2 * nchunk;
-    decodebook_size = off; off += 8;
-    decodebook = off; off += 8 * (2 * 64) + 8 * dict;
-    off = align_up(off, 8);
-    ddata_size = off; off += 8;
-    off = align_up(off, 8);
-    ddata = off; off += 8 * units;
-    outlier_count = off; off += 8;
-    outlier_idx = off; off += 8 * noutlier;
-    outliers = off; off += 8 * noutlier;
-    sync_tag = sync = 0;
-    if (with_sync) {
-      sync_tag = off; off += 8;
-      sync = off; off += 4 * (size_t)huff::kSyncLanes * nchunk;
-    }
-    total = off;
-  }
-};
-
 } // namespace
 
 // ---- lossless context ----------------------------------------------------------------------
@@ -305,11 +276,6 @@ namespace {
 
 using ChunkFn = std::function<int(size_t, size_t, hipEvent_t)>;
 int copy_any(void *dst, const void *src, size_t bytes, hipStream_t st, const ChunkFn *on_chunk = nullptr);  // (below)
-
-// The single-pass encoder stages code table and symbols of a chunk in LDS.
-inline bool lossless_sym16_ok(uint64_t dict, uint64_t chunk) {
-  return dict <= 65536 && dict * 8 + chunk * 2 <= 140 * 1024;
-}
 
 // Host copy of the first bytes of the device-resident stream a decompression call is reading:
 // header, record size and the leading part of the first record come out of ONE device-to-host
@@ -363,6 +329,18 @@ struct RecordPieces {
   const uint8_t *tag_src;
   unsigned long long tag_want;
   unsigned *tag_ok;
+  void add(const void *from, void *to, size_t nbytes) {
+    if (!nbytes) return;
+    src[n] = (const uint8_t *)from;
+    dst[n] = (uint8_t *)to;
+    bytes[n] = nbytes;
+    n++;
+  }
+  size_t total() const {
+    size_t t = 0;
+    for (int i = 0; i < n; i++) t += bytes[i];
+    return t;
+  }
 };
 __global__ void __launch_bounds__(256) k_record_pieces(RecordPieces P) {
   const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x, stride = (size_t)gridDim.x * 256;
@@ -382,6 +360,13 @@ __global__ void __launch_bounds__(256) k_record_pieces(RecordPieces P) {
     }
     for (size_t b = words * 8 + t; b < P.bytes[i]; b += stride) dp[b] = sp[b];
   }
+}
+
+int launch_record_pieces(const RecordPieces &P, hipStream_t st) {
+  const unsigned blocks = (unsigned)std::min<size_t>(std::max<size_t>(P.total() / (256 * 64), 1), 512);
+  k_record_pieces<<<blocks, 256, 0, st>>>(P);
+  HL_HIP(hipGetLastError());
+  return MGH_SUCCESS;
 }
 
 // Copy the record of the last lossless_compress() to dst (host or device memory, record_size()
@@ -407,27 +392,15 @@ int record_write(mgh_lossless_ctx *c, void *dst, hipStream_t st, const uint64_t 
     if (c->n_units && !c->units_in_place)
       HL_TRY(copy_any(d + L.ddata, c->units.p, c->n_units * 8, st));
     RecordPieces P{};
-    auto piece = [&](const void *src, void *to, size_t bytes) {
-      if (!bytes) return;
-      P.src[P.n] = (const uint8_t *)src;
-      P.dst[P.n] = (uint8_t *)to;
-      P.bytes[P.n] = bytes;
-      P.n++;
-    };
     const uint8_t *dh = (const uint8_t *)dev_head;
-    if (size_prefix) piece(dh, d - 8, 8 + L.ddata);
-    else piece(dh + 8, d, L.ddata);
+    if (size_prefix) P.add(dh, d - 8, 8 + L.ddata);
+    else P.add(dh + 8, d, L.ddata);
     // (the count out of the pinned buffer too: &c->pcounts[4] lies behind the head in the same allocation)
-    piece(dh + ((const uint8_t *)&c->pcounts[4] - (c->chead - 8)), d + L.outlier_count, 8);
-    piece(c->d_oidx, d + L.outlier_idx, c->n_outliers * 8);
-    piece(c->d_oval, d + L.outliers, c->n_outliers * 8);
-    if (c->use_sync) piece(c->sync.p, d + L.sync_tag, PayloadLayout::sync_bytes(c->n_chunks));
-    size_t total = 0;
-    for (int i = 0; i < P.n; i++) total += P.bytes[i];
-    const unsigned blocks = (unsigned)std::min<size_t>(std::max<size_t>(total / (256 * 64), 1), 512);
-    k_record_pieces<<<blocks, 256, 0, st>>>(P);
-    HL_HIP(hipGetLastError());
-    return MGH_SUCCESS;
+    P.add(dh + ((const uint8_t *)&c->pcounts[4] - (c->chead - 8)), d + L.outlier_count, 8);
+    P.add(c->d_oidx, d + L.outlier_idx, c->n_outliers * 8);
+    P.add(c->d_oval, d + L.outliers, c->n_outliers * 8);
+    if (c->use_sync) P.add(c->sync.p, d + L.sync_tag, PayloadLayout::sync_bytes(c->n_chunks));
+    return launch_record_pieces(P, st);
   }
   (void)hipGetLastError();
   if (size_prefix) {
@@ -653,18 +626,8 @@ int lossless_finish(mgh_lossless_ctx *c, const LosslessJob &J, hipStream_t st, u
       units_dst = (unsigned long long *)c->units.p;
     }
     static std::atomic<uint64_t> once{0};
-    if (hl_attr_pending(once)) {
-      const int lim = 144 * 1024;
-      HL_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(huff::k_encode_chain<int64_t, uint64_t>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-      HL_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(huff::k_encode_chain<uint16_t, uint64_t>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-      HL_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(huff::k_encode_chain<int64_t, uint32_t>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-      HL_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(huff::k_encode_chain<uint16_t, uint32_t>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-      hl_attr_done(once);
-    }
+    HL_TRY(hl_lds_limit(once, 144 * 1024, huff::k_encode_chain<int64_t, uint64_t>, huff::k_encode_chain<uint16_t, uint64_t>,
+                        huff::k_encode_chain<int64_t, uint32_t>, huff::k_encode_chain<uint16_t, uint32_t>));
     auto enc = [&](auto sym_tag, auto code_tag) {
       using SYM = decltype(sym_tag);
       using CODE = decltype(code_tag);
@@ -785,10 +748,6 @@ int lossless_compress(mgh_lossless_ctx *c, const int64_t *d_q, uint64_t n, uint6
   return lossless_finish(c, J, st, direct, direct_cap);
 }
 
-// `payload` may be host or device memory: only the small leading part of the record is brought
-// to the host, the code units and outlier lists go device-to-device (or host-to-device).
-// sym16: decode to uint16_t symbols at d_q (the ring decoder only; *sym16 is cleared when another
-// decoder had to be used and d_q holds int64 values).
 // After a synchronisation of the stream lossless_decompress() ran on: was the tag of the
 // synchronisation-point section of a device-resident record what it has to be?
 int lossless_tag_check(mgh_lossless_ctx *c) {
@@ -805,170 +764,56 @@ inline mgh_decompress_stats &decompress_stats() {
   return s;
 }
 
-// n_prefix < n (mgh_lossless_decompress_prefix): only the chunks that hold the first n_prefix
-// integers are decoded -- d_q[0 .. min(n, chunks * chunk)) is written, nothing behind it -- and of a
-// record that has to be copied only what those chunks need is moved. q_cap: elements d_q holds (the
-// record's own chunk length decides what is written; one that needs more is refused).
-// first > 0 (mgh_lossless_decompress_range): the chunks in front of the one that holds integer `first`
-// are left out as well -- d_q[0] is the first integer of chunk first / chunk, and the decoders run on
-// the chunk-table entries, synchronisation entries and code units of the range alone.
-// n_prefix == 0: nothing is decoded (a context with keep == 1 only: the reader's open).
-int lossless_decompress(mgh_lossless_ctx *c, const uint8_t *payload, uint64_t size, int lossless,
-                        int64_t *d_q, uint64_t n, uint64_t *ocount_out, hipStream_t st,
-                        bool *sym16 = nullptr, bool sync_end = true, uint64_t n_prefix = ~(uint64_t)0,
-                        uint64_t q_cap = ~(uint64_t)0, uint64_t first = 0) {
-  if (n_prefix == 0 && c->keep != 1) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "lossless_decompress: empty prefix");
-  if (n_prefix != 0 && first >= std::min<uint64_t>(n_prefix, n))
-    return hl_fail(MGH_ERR_INVALID_ARGUMENT, "lossless_decompress: empty range");
-  const bool kept = c->keep == 2;  // head, tables, lists (and the inflated frame) are those of this record already
-  const uint8_t *p = payload;
-  uint64_t psize = size;
-  bool on_dev = is_device_pointer(payload);
-  if (lossless == MGH_LOSSLESS_HUFFMAN_ZSTD && kept) {
-    p = c->host2.data();
-    psize = c->host2.size();
-    on_dev = false;
-  } else if (lossless == MGH_LOSSLESS_HUFFMAN_ZSTD) {
-    if (!g_zstd.load()) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "lossless: libzstd.so.1 not found");
-    if (size < 8) return hl_fail(MGH_ERR_FORMAT, "zstd record truncated");
-    const uint8_t *src = payload;
-    if (on_dev) {
-      c->host.resize(size);
-      HL_HIP(hipMemcpy(c->host.data(), payload, size, hipMemcpyDeviceToHost));
-      src = c->host.data();
-    }
-    uint64_t raw = 0;
-    std::memcpy(&raw, src, 8);
-    if (raw > ((uint64_t)1 << 40)) return hl_fail(MGH_ERR_FORMAT, "zstd record: implausible size");
-    c->host2.resize(raw);
-    const size_t got = g_zstd.decompress(c->host2.data(), raw, src + 8, size - 8);
-    if (g_zstd.isError(got) || got != raw) return hl_fail(MGH_ERR_FORMAT, "ZSTD_decompress failed");
-    p = c->host2.data();
-    psize = raw;
-    on_dev = false;
-  } else if (lossless != MGH_LOSSLESS_HUFFMAN) {
-    return hl_fail(MGH_ERR_INVALID_ARGUMENT, "lossless: only Huffman and Huffman_Zstd are supported");
-  }
-  // host copy of bytes [off, off + bytes) of the record
-  std::vector<uint8_t> &head = c->head;
-  auto need = [&](size_t off, size_t bytes) { return off <= psize && bytes <= psize - off; };
-  auto fetch = [&](size_t upto) -> int {  // make head cover [0, upto)
-    if (head.size() >= upto) return MGH_SUCCESS;
-    const size_t have = head.size();
-    head.resize(upto);
-    if (on_dev) HL_TRY(dev_to_host(head.data() + have, p + have, upto - have));
-    else std::memcpy(head.data() + have, p + have, upto - have);
-    return MGH_SUCCESS;
-  };
-  if (!kept) head.clear();
-  if (!need(0, 24)) return hl_fail(MGH_ERR_FORMAT, "Huffman record truncated");
-  // (a record in device memory: one copy that covers the whole leading part for the default
-  // parameters instead of one per field -- every synchronous copy costs tens of microseconds)
-  if (on_dev) HL_TRY(fetch(std::min<size_t>(psize, 24 + 16 * ((n - 1) / 20480 + 1) + 16 + 8 * 128 + 8 * 8192 + 16)));
-  else HL_TRY(fetch(24));
-  uint64_t primary = 0, huffmeta_size = 0;
-  int32_t dict = 0, chunk = 0;
-  std::memcpy(&primary, head.data(), 8);
-  std::memcpy(&dict, head.data() + 8, 4);
-  std::memcpy(&chunk, head.data() + 12, 4);
-  std::memcpy(&huffmeta_size, head.data() + 16, 8);
-  if (primary != n || dict <= 0 || dict > 16384 || chunk <= 0 ||
-      huffmeta_size != 2 * ((n - 1) / (uint64_t)chunk + 1))
-    return hl_fail(MGH_ERR_FORMAT, "Huffman record: header does not match the subdomain");
-  const size_t nchunk = huffmeta_size / 2;
-  // the chunks decoded, and the integers they hold
-  // (chunks [cf, ndec); d_q[0] is integer cf * chunk)
-  const size_t ndec = n_prefix == 0 ? 0 : std::min<size_t>(nchunk, (size_t)((std::min<uint64_t>(n_prefix, n) - 1) / (uint64_t)chunk + 1));
-  const size_t cf = (size_t)(first / (uint64_t)chunk);
-  const size_t n_dec = (size_t)std::min<uint64_t>(n, (uint64_t)ndec * (uint64_t)chunk);
-  if (ndec && n_dec - cf * (size_t)chunk > q_cap) return hl_fail(MGH_ERR_FORMAT, "Huffman record: chunk length does not match the header");
-  // chunk-table entries on the device: those of the range, or (a kept context) the whole table
-  const size_t tb0 = c->keep ? 0 : cf, tb_cnt = c->keep ? nchunk : ndec - cf;
-  PayloadLayout L;
-  L.compute(nchunk, (size_t)dict, 0, 0);
-  if (!need(0, L.ddata)) return hl_fail(MGH_ERR_FORMAT, "Huffman record truncated");
-  HL_TRY(fetch(L.ddata));
-  uint64_t dbsize = 0, units = 0;
-  std::memcpy(&dbsize, head.data() + L.decodebook_size, 8);
-  if (dbsize != 8 * 128 + 8 * (uint64_t)dict) return hl_fail(MGH_ERR_FORMAT, "Huffman record: decodebook size");
-  std::memcpy(&units, head.data() + L.ddata_size, 8);
-  if (units > (psize - L.ddata) / 8) return hl_fail(MGH_ERR_FORMAT, "Huffman record truncated");
-  const size_t o_oc = L.ddata + 8 * units;
-  if (!need(o_oc, 8)) return hl_fail(MGH_ERR_FORMAT, "Huffman record truncated");
-  uint64_t ocount = 0;
-  // Behind the outlier lists: nothing, or the synchronisation points of the decoder (PayloadLayout;
-  // 8 mod 16 bytes where the lists are 0 mod 16).
-  const size_t sync_bytes = PayloadLayout::sync_bytes(nchunk);
-  const size_t rem = psize - o_oc - 8;
-  bool has_sync = rem % 16 == 8 && rem >= sync_bytes;
+// The MGH_HUFF_* switches of the decoders (the two cross-check decoders are chosen once per process).
+inline DecodeSwitches decode_switches() {
+  static const bool serial = env_get("MGH_HUFF_SERIAL_DECODE", 0) != 0, par = env_get("MGH_HUFF_PAR_DECODE", 0) != 0;
+  return DecodeSwitches{serial, par, env_get("MGH_HUFF_SYNC_DECODE", 1) != 0, env_get("MGH_HUFF_PAIR", 1), env_get("MGH_HUFF_TB", DecodeSwitches::kNotSet)};
+}
+
+// The Huffman record inside a Huffman_Zstd record, inflated into the context (a kept context holds it already).
+int lossless_inflate(mgh_lossless_ctx *c, const uint8_t *payload, uint64_t size, bool on_dev) {
+  if (c->keep == 2) return MGH_SUCCESS;
+  if (!g_zstd.load()) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "lossless: libzstd.so.1 not found");
+  if (size < 8) return hl_fail(MGH_ERR_FORMAT, "zstd record truncated");
+  const uint8_t *src = payload;
   if (on_dev) {
-    // the record ends with the two outlier arrays (and that section): their length follows from
-    // the record size (saves a synchronous 8-byte copy from the device)
-    if (rem % 16 != 0 && !has_sync) return hl_fail(MGH_ERR_FORMAT, "Huffman record: outlier lists");
-    ocount = (rem - (has_sync ? sync_bytes : 0)) / 16;
-  } else {
-    std::memcpy(&ocount, p + o_oc, 8);
-    if (has_sync && (ocount > (rem - sync_bytes) / 16 || rem - 16 * ocount != sync_bytes)) has_sync = false;
+    c->host.resize(size);
+    HL_HIP(hipMemcpy(c->host.data(), payload, size, hipMemcpyDeviceToHost));
+    src = c->host.data();
   }
-  if (ocount > rem / 16) return hl_fail(MGH_ERR_FORMAT, "Huffman record truncated");
-  const size_t o_oidx = o_oc + 8, o_oval = o_oidx + 8 * ocount;
-  const size_t o_sync = o_oval + 8 * ocount + 8;  // (behind the tag)
-  if (has_sync && !on_dev) {
-    uint64_t tag = 0;
-    std::memcpy(&tag, p + o_sync - 8, 8);
-    if (tag != PayloadLayout::kSyncTag) has_sync = false;
-  }
-  if (env_get("MGH_HUFF_SYNC_DECODE", 1) == 0) has_sync = false;  // cross-check: decode without them
-  // the chunk entries must stay inside the unit array (they index it in the decoder)
-  size_t units_need = 0;  // code units up to the end of the last chunk decoded
-  size_t units_lo = 0;    // ... and the first one of the first chunk decoded
-  {
-    const uint64_t *bits = reinterpret_cast<const uint64_t *>(head.data() + L.huffmeta);
-    const uint64_t *ent = bits + nchunk;
-    if (cf) units_lo = units;
-    for (size_t k = 0; k < nchunk; k++) {
-      if (ent[k] > units || (bits[k] + 63) / 64 > units - ent[k])
-        return hl_fail(MGH_ERR_FORMAT, "Huffman record: chunk outside the code stream");
-      if (k < ndec) units_need = std::max<size_t>(units_need, ent[k] + (bits[k] + 63) / 64);
-      if (cf && k >= cf && k < ndec) units_lo = std::min<size_t>(units_lo, ent[k]);
-    }
-  }
-  if (ndec == nchunk) units_need = units;
-  units_lo = std::min(units_lo, units_need);
-  hl_debug("lossless_decompress: record head parsed");
+  uint64_t raw = 0;
+  std::memcpy(&raw, src, 8);
+  if (raw > ((uint64_t)1 << 40)) return hl_fail(MGH_ERR_FORMAT, "zstd record: implausible size");
+  c->host2.resize(raw);
+  const size_t got = g_zstd.decompress(c->host2.data(), raw, src + 8, size - 8);
+  if (g_zstd.isError(got) || got != raw) return hl_fail(MGH_ERR_FORMAT, "ZSTD_decompress failed");
+  return MGH_SUCCESS;
+}
+
+// Chunk table, decodebook and outlier lists of a parsed record into the context's device buffers
+// (a kept context has them). here: the record lies in memory of the context's device.
+int record_upload(mgh_lossless_ctx *c, const uint8_t *p, bool on_dev, bool here, const RecordPlan &R, hipStream_t st) {
+  const PayloadLayout &L = R.L;
+  const size_t nchunk = R.nchunk, ocount = R.ocount;
+  const bool kept = c->keep == 2;
   mgh_decompress_stats &stats = decompress_stats();
-  stats.chunks_total += nchunk;
-  stats.chunks_decoded += ndec - std::min(cf, ndec);
-  stats.symbols_decoded += ndec ? n_dec - cf * (size_t)chunk : 0;
-  stats.record_bytes += size;
   HL_TRY(c->bits.ensure(nchunk * 8));
   HL_TRY(c->entry.ensure(nchunk * 8));
-  HL_TRY(c->tables.ensure(dbsize));
+  HL_TRY(c->tables.ensure(R.dbsize));
   HL_TRY(c->oidx.ensure(std::max<size_t>(ocount, 1) * 8));
   HL_TRY(c->oval.ensure(std::max<size_t>(ocount, 1) * 8));
-  // (a record in device memory: these go device-to-device from the record itself, not back up
-  // from the pageable host copy)
-  const uint8_t *meta_src = on_dev ? p : head.data();
   // (a record on this device: chunk table, decodebook and outlier lists in ONE launch -- five
   // queued copies of ~5 us each stood in front of every decoder launch)
-  const bool pieces = on_dev && is_device_pointer_on(p, c->dev);
-  if (pieces) {
+  if (here) {
     RecordPieces P{};
-    auto piece = [&](const void *src, void *to, size_t bytes) {
-      if (!bytes) return;
-      P.src[P.n] = (const uint8_t *)src;
-      P.dst[P.n] = (uint8_t *)to;
-      P.bytes[P.n] = bytes;
-      P.n++;
-    };
     if (!kept) {
-      piece(p + L.huffmeta + tb0 * 8, c->bits.p, tb_cnt * 8);
-      piece(p + L.huffmeta + (nchunk + tb0) * 8, c->entry.p, tb_cnt * 8);
-      piece(p + L.decodebook, c->tables.p, dbsize);
-      piece(p + o_oidx, c->oidx.p, ocount * 8);
-      piece(p + o_oval, c->oval.p, ocount * 8);
+      P.add(p + L.huffmeta + R.tb0 * 8, c->bits.p, R.tb_cnt * 8);
+      P.add(p + L.huffmeta + (nchunk + R.tb0) * 8, c->entry.p, R.tb_cnt * 8);
+      P.add(p + L.decodebook, c->tables.p, R.dbsize);
+      P.add(p + R.o_oidx, c->oidx.p, ocount * 8);
+      P.add(p + R.o_oval, c->oval.p, ocount * 8);
     }
-    if (has_sync && !kept) {
+    if (R.has_sync && !kept) {
       // The section was recognised by the record's size alone (no host copy of its tag): the kernel
       // looks at the tag and clears a pinned word if it is not one; whoever synchronises the stream
       // next turns that into MGH_ERR_FORMAT (lossless_tag_check) -- a damaged record must not decode
@@ -977,7 +822,7 @@ int lossless_decompress(mgh_lossless_ctx *c, const uint8_t *payload, uint64_t si
       void *dev_word = nullptr;
       if (hipHostGetDevicePointer(&dev_word, c->tagpin.p, 0) == hipSuccess && dev_word) {
         *reinterpret_cast<volatile unsigned *>(c->tagpin.p) = 1;
-        P.tag_src = p + o_sync - 8;
+        P.tag_src = p + R.o_sync - 8;
         P.tag_want = PayloadLayout::kSyncTag;
         P.tag_ok = (unsigned *)dev_word;
         c->tag_pending = true;
@@ -985,242 +830,206 @@ int lossless_decompress(mgh_lossless_ctx *c, const uint8_t *payload, uint64_t si
         (void)hipGetLastError();
       }
     }
-    size_t tot = 0;
-    for (int i = 0; i < P.n; i++) tot += P.bytes[i];
-    stats.record_bytes_moved += tot;
-    if (!kept) {
-      k_record_pieces<<<(unsigned)std::min<size_t>(std::max<size_t>(tot / (256 * 64), 1), 512), 256, 0, st>>>(P);
-      HL_HIP(hipGetLastError());
-    }
+    stats.record_bytes_moved += P.total();
+    if (!kept) HL_TRY(launch_record_pieces(P, st));
   } else if (!kept) {
-    HL_HIP(hipMemcpyAsync(c->bits.p, meta_src + L.huffmeta + tb0 * 8, tb_cnt * 8, hipMemcpyDefault, st));
-    HL_HIP(hipMemcpyAsync(c->entry.p, meta_src + L.huffmeta + (nchunk + tb0) * 8, tb_cnt * 8, hipMemcpyDefault, st));
-    HL_HIP(hipMemcpyAsync(c->tables.p, meta_src + L.decodebook, dbsize, hipMemcpyDefault, st));
-    stats.record_bytes_moved += 2 * tb_cnt * 8 + dbsize;
+    // (a record in device memory: these go device-to-device from the record itself, not back up
+    // from the pageable host copy)
+    const uint8_t *meta_src = on_dev ? p : c->head.data();
+    HL_HIP(hipMemcpyAsync(c->bits.p, meta_src + L.huffmeta + R.tb0 * 8, R.tb_cnt * 8, hipMemcpyDefault, st));
+    HL_HIP(hipMemcpyAsync(c->entry.p, meta_src + L.huffmeta + (nchunk + R.tb0) * 8, R.tb_cnt * 8, hipMemcpyDefault, st));
+    HL_HIP(hipMemcpyAsync(c->tables.p, meta_src + L.decodebook, R.dbsize, hipMemcpyDefault, st));
+    stats.record_bytes_moved += 2 * R.tb_cnt * 8 + R.dbsize;
   }
-  static const bool serial_decode = env_get("MGH_HUFF_SERIAL_DECODE", 0) != 0;  // cross-check
-  static const bool par_decode = env_get("MGH_HUFF_PAR_DECODE", 0) != 0;           // cross-check
-  int book_max_len = 0;  // longest code of the decodebook (unused lengths carry first = 2^64-1)
-  {
-    const uint64_t *first = reinterpret_cast<const uint64_t *>(head.data() + L.decodebook);
-    for (int l = 1; l < 64; l++)
-      if (first[l] != ~(uint64_t)0) book_max_len = l;
+  if (ocount && !here && !kept) {
+    stats.record_bytes_moved += 16 * ocount;
+    HL_HIP(hipMemcpyAsync(c->oidx.p, p + R.o_oidx, ocount * 8, hipMemcpyDefault, st));
+    HL_HIP(hipMemcpyAsync(c->oval.p, p + R.o_oval, ocount * 8, hipMemcpyDefault, st));
   }
-  // (the ring decoder keeps more than 32 bits in its bit buffer: codes of up to 32 bits)
-  const bool ring_decode = !serial_decode && !par_decode && (size_t)chunk >= 1024 && (size_t)chunk <= (1u << 24) &&
-                           dict <= 65536 && book_max_len <= 32;
+  return MGH_SUCCESS;
+}
+
+// `payload` may be host or device memory: only the small leading part of the record is brought
+// to the host, the code units and outlier lists go device-to-device (or host-to-device). What the
+// record says is read by huffman_record.hpp (record_fixed, record_plan), which decoder takes it by
+// its decode_plan; this function fetches, uploads and launches.
+// sym16: decode to uint16_t symbols at d_q (the ring decoder only; *sym16 is cleared when another
+// decoder had to be used and d_q holds int64 values).
+// range (DecodeRange): a prefix or a range writes d_q[0 .. ) from the first integer of its first chunk
+// to the end of its last and nothing behind it, and of a record that has to be copied only what those
+// chunks need is moved; the decoders run on the chunk-table entries, synchronisation entries and code
+// units of the range alone. n_prefix == 0: a context with keep == 1 only (the reader's open).
+int lossless_decompress(mgh_lossless_ctx *c, const uint8_t *payload, uint64_t size, int lossless,
+                        int64_t *d_q, uint64_t n, uint64_t *ocount_out, hipStream_t st,
+                        bool *sym16 = nullptr, bool sync_end = true, const DecodeRange &range = DecodeRange()) {
+  if (range.n_prefix == 0 && c->keep != 1) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "lossless_decompress: empty prefix");
+  if (range.n_prefix != 0 && range.first >= std::min<uint64_t>(range.n_prefix, n))
+    return hl_fail(MGH_ERR_INVALID_ARGUMENT, "lossless_decompress: empty range");
+  const bool kept = c->keep == 2;  // head, tables, lists (and the inflated frame) are those of this record already
+  const uint8_t *p = payload;
+  uint64_t psize = size;
+  bool on_dev = is_device_pointer(payload);
+  if (lossless == MGH_LOSSLESS_HUFFMAN_ZSTD) {
+    HL_TRY(lossless_inflate(c, payload, size, on_dev));
+    p = c->host2.data();
+    psize = c->host2.size();
+    on_dev = false;
+  } else if (lossless != MGH_LOSSLESS_HUFFMAN) {
+    return hl_fail(MGH_ERR_INVALID_ARGUMENT, "lossless: only Huffman and Huffman_Zstd are supported");
+  }
+  std::vector<uint8_t> &head = c->head;
+  auto fetch = [&](size_t upto) -> int {  // make head a host copy of bytes [0, upto) of the record
+    if (head.size() >= upto) return MGH_SUCCESS;
+    const size_t have = head.size();
+    head.resize(upto);
+    if (on_dev) HL_TRY(dev_to_host(head.data() + have, p + have, upto - have));
+    else std::memcpy(head.data() + have, p + have, upto - have);
+    return MGH_SUCCESS;
+  };
+  if (!kept) head.clear();
+  // (a record in device memory: one copy that covers the whole leading part for the default
+  // parameters instead of one per field -- every synchronous copy costs tens of microseconds)
+  if (psize >= 24) HL_TRY(fetch(std::min<size_t>(psize, on_dev ? 24 + 16 * ((n - 1) / 20480 + 1) + 16 + 8 * 128 + 8 * 8192 + 16 : 24)));
+  const DecodeSwitches sw = decode_switches();
+  RecordPlan R;
+  if (const char *bad = record_fixed(head.data(), head.size(), psize, n, range, c->keep != 0, R))
+    return hl_fail(MGH_ERR_FORMAT, bad);
+  HL_TRY(fetch(R.L.ddata));
+  if (const char *bad = record_plan(head.data(), head.size(), on_dev ? nullptr : p, psize, sw, R))
+    return hl_fail(MGH_ERR_FORMAT, bad);
+  const DecodePlan D = decode_plan(R, n, sw);
+  const PayloadLayout &L = R.L;
+  const size_t nchunk = R.nchunk, ndec = R.ndec, cf = R.cf, ocount = R.ocount;
+  const size_t n_out = ndec ? R.n_dec - cf * (size_t)R.chunk : 0;  // integers the call writes
+  const size_t units_b = (R.units_need - R.units_lo) * 8;           // bytes of the code units it reads
+  hl_debug("lossless_decompress: record head parsed");
+  mgh_decompress_stats &stats = decompress_stats();
+  stats.chunks_total += nchunk;
+  stats.chunks_decoded += ndec - std::min(cf, ndec);
+  stats.symbols_decoded += n_out;
+  stats.record_bytes += size;
+  const bool here = on_dev && is_device_pointer_on(p, c->dev);
+  HL_TRY(record_upload(c, p, on_dev, here, R, st));
+  const bool ring = D.kind == DecodeKind::ring;
   // A device-resident record is decoded where it is (512^3: 150 MB not copied) -- by the ring
   // decoder wherever its code units start (load_unit), by the others when they start 8-byte
   // aligned. The decoders peek one unit past the stream; in the record that is the outlier count
   // -- the peeked bits lie beyond the last code of the last chunk and never reach a symbol (every
   // chunk stops at its bit count).
   // (only memory of the device the decoder runs on: a record on another GPU is copied over)
-  const bool units_in_place = on_dev && units && (ring_decode || ((uintptr_t)(p + L.ddata) & 7) == 0) &&
-                              is_device_pointer_on(p, c->dev);
-  const unsigned long long *d_units = (const unsigned long long *)c->units.p;
+  const bool units_in_place = here && R.units && (ring || ((uintptr_t)(p + L.ddata) & 7) == 0);
+  const unsigned long long *d_units = (const unsigned long long *)(p + L.ddata);
   bool units_follow = false;
-  if (units_in_place) {
-    d_units = (const unsigned long long *)(p + L.ddata);
-  } else {
+  if (!units_in_place) {
     // (not for units decoded in place: 8 N bytes a lane would hold for nothing. The entries of the
     // chunk table count from the start of the stream: the pointer is moved down by what is left out)
-    HL_TRY(c->units.ensure((units_need - units_lo + 1) * 8));
-    d_units = (const unsigned long long *)c->units.p - units_lo;
+    HL_TRY(c->units.ensure(units_b + 8));
+    d_units = (const unsigned long long *)c->units.p - R.units_lo;
     // A large record in HOST memory is decoded while it arrives (below: the ring decoder's launches
     // follow the pieces of the copy, which runs on the cache's copy stream); everything else is
     // copied here, in stream order. (A record in pageable memory travels through the pinned ring.)
-    units_follow = !on_dev && ring_decode && (units_need - units_lo) * 8 >= ((size_t)32 << 20) && cache_copy_stream(c->dev) &&
+    units_follow = !on_dev && ring && units_b >= ((size_t)32 << 20) && cache_copy_stream(c->dev) &&
                    env_get("MGH_HL_DECODE_FOLLOWS", 1) != 0;
-    if (units_need > units_lo && !units_follow)
-      HL_TRY(copy_any(c->units.p, p + L.ddata + units_lo * 8, (units_need - units_lo) * 8, st));
-    HL_HIP(hipMemsetAsync((char *)c->units.p + (units_need - units_lo) * 8, 0, 8, st));  // (the decoder peeks one unit ahead)
-    stats.record_bytes_moved += (units_need - units_lo) * 8;
-  }
-  if (ocount && !pieces && !kept) {
-    stats.record_bytes_moved += 16 * ocount;
-    HL_HIP(hipMemcpyAsync(c->oidx.p, p + o_oidx, ocount * 8, hipMemcpyDefault, st));
-    HL_HIP(hipMemcpyAsync(c->oval.p, p + o_oval, ocount * 8, hipMemcpyDefault, st));
+    if (units_b && !units_follow) HL_TRY(copy_any(c->units.p, p + L.ddata + R.units_lo * 8, units_b, st));
+    HL_HIP(hipMemsetAsync((char *)c->units.p + units_b, 0, 8, st));  // (the decoder peeks one unit ahead)
+    stats.record_bytes_moved += units_b;
   }
   hl_debug("lossless_decompress: uploads done");
-  const unsigned long long *tab = (const unsigned long long *)c->tables.p;
-  // prefix table as large as LDS allows next to the 16-bit keys (15 bits for dict = 8192)
-  int tb = 15;
-  const size_t lds_keys_ring = ((size_t)dict * 2 + 7) / 8 * 8 + 16 * 64 * 8;
-  while (tb > 8 && ((size_t)4 << tb) + lds_keys_ring > 154 * 1024) tb--;
-  tb = std::max(8, std::min(tb, (int)env_get("MGH_HUFF_TB", tb)));  // developer switch
-  const size_t lds = ((size_t)4 << tb) + lds_keys_ring;
-  static std::atomic<uint64_t> once{0};
-  if (hl_attr_pending(once)) {
-    HL_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(huff::k_decode),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024));
-    hl_attr_done(once);
-  }
+  static std::atomic<uint64_t> once{0}, once_ring{0}, once_pair{0}, once_par{0};
+  HL_TRY(hl_lds_limit(once, 156 * 1024, huff::k_decode));
   hl_debug("lossless_decompress: uploads done (units, tables, outliers)");
-  if (ring_decode) {
-    // parallel decoding inside the chunks: two-level table from the decodebook (host, microseconds),
-    // code units through per-lane LDS rings. 16 waves per workgroup when the table leaves room.
+  const unsigned long long *tab = (const unsigned long long *)c->tables.p;
+  if (ring) {
+    // two-level table from the decodebook (host, microseconds); 16 waves per workgroup when the
+    // table leaves room
     const uint64_t *book = reinterpret_cast<const uint64_t *>(head.data() + L.decodebook);
-    int rtb = 12;
-    rtb = std::max(8, std::min(14, (int)env_get("MGH_HUFF_TB", rtb)));  // developer switch
     const size_t lds_cap = 150 * 1024;
-    const size_t per_wave = huff::decode_ring_lds(0, 1);
     // (kept in the context: the upload below is asynchronous and must not outlive its source)
     std::vector<uint32_t> &dt = c->h_dtable;
-    // Records with synchronisation points and SHORT codes: the decoder that takes two codes per
-    // root-table slot where both fit its 12 bits (k_decode_sync). 512^3 f32, int64 output, same box:
-    // 5.7 bits per symbol 0.79 against 0.85 ms with k_decode_ring's single-symbol steps; 7.4 bits 0.98
-    // against 0.87, 9.1 bits (the benchmark's field at 1e-3) 0.97 against 0.79 -- pairs no longer fit
-    // and the wider entries only cost. MGH_HUFF_PAIR: 0 never, 1 up to 6.5 bits per symbol (default),
-    // 2 whenever the record has the points (cross-check).
-    const long pair_env = env_get("MGH_HUFF_PAIR", 1);
-    const bool pair_decode = has_sync && (size_t)chunk <= 65535 &&
-                             (pair_env == 2 || (pair_env == 1 && (double)units * 64.0 <= 6.5 * (double)n));
     if (!kept) {
-      dt = huff::build_decode_table(book, book + 64, book + 128, (int)dict, rtb,
-                                    (lds_cap - 8 * per_wave) / 4 - (pair_decode ? ((size_t)1 << rtb) : 0));
-      if (pair_decode) dt = huff::make_pair_table(dt, rtb);
-    }
-    const int waves = huff::decode_ring_lds(dt.size(), 16) <= lds_cap ? 16 : 8;
-    if (!kept) {
+      dt = huff::build_decode_table(book, book + 64, book + 128, R.dict, D.rtb,
+                                    (lds_cap - 8 * huff::decode_ring_lds(0, 1)) / 4 - (D.pair ? ((size_t)1 << D.rtb) : 0));
+      if (D.pair) dt = huff::make_pair_table(dt, D.rtb);
       HL_TRY(c->dtable.ensure(dt.size() * 4));
       // (out of pinned memory: a copy from pageable memory is staged synchronously, ~15 us)
       HL_TRY(c->dpin.ensure(dt.size() * 4));
       std::memcpy(c->dpin.p, dt.data(), dt.size() * 4);
       HL_HIP(hipMemcpyAsync(c->dtable.p, c->dpin.p, dt.size() * 4, hipMemcpyHostToDevice, st));
     }
-    static std::atomic<uint64_t> once3{0};
-    if (hl_attr_pending(once3)) {
-      HL_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(huff::k_decode_ring<int64_t>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024));
-      HL_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(huff::k_decode_ring<uint16_t>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024));
-      hl_attr_done(once3);
-    }
+    const int waves = huff::decode_ring_lds(dt.size(), 16) <= lds_cap ? 16 : 8;
+    HL_TRY(hl_lds_limit(once_ring, 156 * 1024, huff::k_decode_ring<int64_t>, huff::k_decode_ring<uint16_t>));
+    if (D.pair) HL_TRY(hl_lds_limit(once_pair, 156 * 1024, huff::k_decode_sync<int64_t>, huff::k_decode_sync<uint16_t>));
     // synchronisation points of the encoder, if the record has them: read where they lie in a
     // record on this device (any alignment), else from a copy
-    const unsigned *d_sync = nullptr;
+    const size_t sync_per = 4 * (size_t)huff::kSyncLanes;
+    const uint8_t *d_sync = nullptr;
     size_t sync0 = 0;  // chunk d_sync starts at
-    if (has_sync && (size_t)chunk <= 65535) {
-      if (on_dev && is_device_pointer_on(p, c->dev)) {
-        d_sync = (const unsigned *)(p + o_sync);
-      } else {
-        if (on_dev) {  // (a record on another device: its tag has not been looked at yet)
-          uint64_t tag = 0;
-          HL_TRY(aux_read(&tag, p + o_sync - 8, 8));
-          if (tag != PayloadLayout::kSyncTag) return hl_fail(MGH_ERR_FORMAT, "Huffman record: outlier lists");
-        }
-        // (the entries of the chunks decoded)
-        const size_t sync_per = 4 * (size_t)huff::kSyncLanes;
-        const size_t sync_need = sync_per * (ndec - std::min(cf, ndec));
-        HL_TRY(c->sync.ensure(std::max<size_t>(sync_need, sync_per)));
-        if (sync_need) HL_HIP(hipMemcpyAsync(c->sync.p, p + o_sync + sync_per * cf, sync_need, hipMemcpyDefault, st));
-        stats.record_bytes_moved += sync_need;
-        d_sync = (const unsigned *)c->sync.p;
-        sync0 = cf;
+    if (D.sync && here) {
+      d_sync = p + R.o_sync;
+    } else if (D.sync) {
+      if (on_dev) {  // (a record on another device: its tag has not been looked at yet)
+        uint64_t tag = 0;
+        HL_TRY(aux_read(&tag, p + R.o_sync - 8, 8));
+        if (tag != PayloadLayout::kSyncTag) return hl_fail(MGH_ERR_FORMAT, "Huffman record: outlier lists");
       }
-    }
-    if (pair_decode && !d_sync) return hl_fail(MGH_ERR_DEVICE, "lossless_decompress: pair table without synchronisation points");
-    if (pair_decode) {
-      static std::atomic<uint64_t> once4{0};
-      if (hl_attr_pending(once4)) {
-        HL_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(huff::k_decode_sync<int64_t>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024));
-        HL_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(huff::k_decode_sync<uint16_t>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024));
-        hl_attr_done(once4);
-      }
+      // (the entries of the chunks decoded)
+      const size_t sync_need = sync_per * (ndec - std::min(cf, ndec));
+      HL_TRY(c->sync.ensure(std::max<size_t>(sync_need, sync_per)));
+      if (sync_need) HL_HIP(hipMemcpyAsync(c->sync.p, p + R.o_sync + sync_per * cf, sync_need, hipMemcpyDefault, st));
+      stats.record_bytes_moved += sync_need;
+      d_sync = (const uint8_t *)c->sync.p;
+      sync0 = cf;
     }
     const size_t lds_b = huff::decode_ring_lds(dt.size(), waves);
-    const bool out16 = sym16 && *sym16;
     // chunks [c0, c1): the kernels index everything by chunk, so a range is the same launch with
     // the per-chunk arrays, the output and the symbol count moved up by c0 chunks
-    auto launch_range = [&](size_t c0, size_t c1) -> int {
+    auto launch_range = [&](size_t c0, size_t c1, auto *q) -> int {
       if (c1 <= c0) return MGH_SUCCESS;
-      const size_t cnt = c1 - c0, n_r = n_dec - c0 * (size_t)chunk;
-      const unsigned grid = (unsigned)((cnt + waves - 1) / waves);
-      const unsigned long long *bits_r = (const unsigned long long *)c->bits.p + (c0 - tb0);
-      const unsigned long long *ent_r = (const unsigned long long *)c->entry.p + (c0 - tb0);
-      const unsigned *sync_r = d_sync ? reinterpret_cast<const unsigned *>(reinterpret_cast<const uint8_t *>(d_sync) + (c0 - sync0) * huff::kSyncLanes * 4) : nullptr;
-      int64_t *q64 = d_q + (c0 - cf) * (size_t)chunk;
-      uint16_t *q16 = (uint16_t *)d_q + (c0 - cf) * (size_t)chunk;
-      if (pair_decode) {
-        if (out16)
-          huff::k_decode_sync<uint16_t><<<grid, 64 * waves, lds_b, st>>>(d_units, bits_r, ent_r, cnt, chunk, n_r, dict, rtb,
-                                                                         (const unsigned *)c->dtable.p, (unsigned)dt.size(),
-                                                                         tab, tab + 64, tab + 128, q16, sync_r);
-        else
-          huff::k_decode_sync<int64_t><<<grid, 64 * waves, lds_b, st>>>(d_units, bits_r, ent_r, cnt, chunk, n_r, dict, rtb,
-                                                                        (const unsigned *)c->dtable.p, (unsigned)dt.size(),
-                                                                        tab, tab + 64, tab + 128, q64, sync_r);
-      } else if (out16) {
-        huff::k_decode_ring<uint16_t><<<grid, 64 * waves, lds_b, st>>>(d_units, bits_r, ent_r, cnt, chunk, n_r, dict, rtb,
-                                                                       (const unsigned *)c->dtable.p, (unsigned)dt.size(),
-                                                                       tab, tab + 64, tab + 128, q16, sync_r);
-      } else {
-        huff::k_decode_ring<int64_t><<<grid, 64 * waves, lds_b, st>>>(d_units, bits_r, ent_r, cnt, chunk, n_r, dict, rtb,
-                                                                      (const unsigned *)c->dtable.p, (unsigned)dt.size(),
-                                                                      tab, tab + 64, tab + 128, q64, sync_r);
-      }
+      using OUT = std::remove_pointer_t<decltype(q)>;
+      const auto kernel = D.pair ? huff::k_decode_sync<OUT> : huff::k_decode_ring<OUT>;
+      const size_t cnt = c1 - c0;
+      kernel<<<(unsigned)((cnt + waves - 1) / waves), 64 * waves, lds_b, st>>>(
+          d_units, (const unsigned long long *)c->bits.p + (c0 - R.tb0), (const unsigned long long *)c->entry.p + (c0 - R.tb0),
+          cnt, R.chunk, R.n_dec - c0 * (size_t)R.chunk, R.dict, D.rtb, (const unsigned *)c->dtable.p, (unsigned)dt.size(),
+          tab, tab + 64, tab + 128, q + (c0 - cf) * (size_t)R.chunk,
+          d_sync ? reinterpret_cast<const unsigned *>(d_sync + (c0 - sync0) * sync_per) : nullptr);
       HL_HIP(hipGetLastError());
       return MGH_SUCCESS;
     };
+    auto launch = [&](size_t c0, size_t c1) -> int {
+      return sym16 && *sym16 ? launch_range(c0, c1, (uint16_t *)d_q) : launch_range(c0, c1, d_q);
+    };
     if (units_follow) {
       // the record's code units on the copy stream, piece by piece; behind every piece the chunks
-      // whose units (and the one unit the decoder peeks at behind them) have landed are decoded on st
+      // whose units have landed (chunks_landed) are decoded on st
       const uint64_t *h_bits = reinterpret_cast<const uint64_t *>(head.data() + L.huffmeta);
-      const uint64_t *h_ent = h_bits + nchunk;
       size_t c_done = cf;
-      const size_t total_b = (units_need - units_lo) * 8;
       const ChunkFn on_piece = [&](size_t off, size_t nb, hipEvent_t landed) -> int {
-        const uint64_t have = units_lo + (off + nb) / 8;  // units of the record on the device
-        size_t c_hi = c_done;
-        if (off + nb >= total_b) {
-          c_hi = ndec;
-        } else {
-          while (c_hi < ndec && h_ent[c_hi] + (h_bits[c_hi] + 63) / 64 + 1 <= have) c_hi++;
-        }
+        const size_t c_hi = chunks_landed(R, h_bits, h_bits + nchunk, c_done, R.units_lo + (off + nb) / 8, off + nb >= units_b);
         if (c_hi > c_done) {
           HL_HIP(hipStreamWaitEvent(st, landed, 0));
-          HL_TRY(launch_range(c_done, c_hi));
+          HL_TRY(launch(c_done, c_hi));
           c_done = c_hi;
         }
         return MGH_SUCCESS;
       };
       // (the copy stream must not run ahead of what st has queued in front: the small uploads above
       // are independent of the units; the units buffer itself is free -- the caller drained st)
-      HL_TRY(copy_any(c->units.p, p + L.ddata + units_lo * 8, total_b, cache_copy_stream(c->dev), &on_piece));
+      HL_TRY(copy_any(c->units.p, p + L.ddata + R.units_lo * 8, units_b, cache_copy_stream(c->dev), &on_piece));
       if (c_done < ndec) return hl_fail(MGH_ERR_DEVICE, "lossless_decompress: chunks left behind the last piece");
     } else {
-      HL_TRY(launch_range(cf, ndec));
+      HL_TRY(launch(cf, ndec));
     }
-    HL_HIP(hipGetLastError());
-  } else if (ndec <= cf) {
-    // (nothing to decode)
-  } else if (!serial_decode && (size_t)chunk >= 1024) {
+  } else if (D.kind != DecodeKind::none) {
     if (sym16) *sym16 = false;
-    // parallel decoding inside the chunks (one wave per chunk)
-    static std::atomic<uint64_t> once2{0};
-    if (hl_attr_pending(once2)) {
-      HL_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(huff::k_decode_par),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024));
-      hl_attr_done(once2);
-    }
-    // 14-bit prefix table at most, so that the write-out staging (4 KiB per wave) fits beside it
-    while (tb > 8 && ((size_t)4 << tb) + ((size_t)dict + 3) / 4 * 8 + huff::kParWaves * 64 * huff::kParBatch * 2 >
-                         150 * 1024)
-      tb--;
-    const size_t lds_par = ((size_t)4 << tb) + ((size_t)dict + 3) / 4 * 8 + huff::kParWaves * 64 * huff::kParBatch * 2;
-    huff::k_decode_par<<<(unsigned)((ndec - cf + huff::kParWaves - 1) / huff::kParWaves),
-                         64 * huff::kParWaves, lds_par, st>>>(
-        d_units, (const unsigned long long *)c->bits.p + (cf - tb0),
-        (const unsigned long long *)c->entry.p + (cf - tb0), ndec - cf, chunk, n_dec - cf * (size_t)chunk, dict, tb, tab,
-        tab + 64, tab + 128, d_q);
-  } else {
-    if (sym16) *sym16 = false;
-    huff::k_decode<<<(unsigned)((ndec - cf + 63) / 64), 64, lds, st>>>(
-        d_units, (const unsigned long long *)c->bits.p + (cf - tb0),
-        (const unsigned long long *)c->entry.p + (cf - tb0), ndec - cf, chunk, n_dec - cf * (size_t)chunk, dict, tb, tab,
-        tab + 64, tab + 128, d_q);
+    // parallel inside the chunks, one wave per chunk (k_decode_par), or one lane per chunk (k_decode)
+    const bool par = D.kind == DecodeKind::par;
+    if (par) HL_TRY(hl_lds_limit(once_par, 156 * 1024, huff::k_decode_par));
+    const auto kernel = par ? huff::k_decode_par : huff::k_decode;
+    const unsigned per_group = par ? huff::kParWaves : 64, threads = par ? 64 * huff::kParWaves : 64;
+    kernel<<<(unsigned)((ndec - cf + per_group - 1) / per_group), threads, D.lds, st>>>(
+        d_units, (const unsigned long long *)c->bits.p + (cf - R.tb0), (const unsigned long long *)c->entry.p + (cf - R.tb0),
+        ndec - cf, R.chunk, n_out, R.dict, D.tb, tab, tab + 64, tab + 128, d_q);
   }
   HL_HIP(hipGetLastError());
   hl_debug("lossless_decompress: decode launched");
@@ -2801,7 +2610,7 @@ int reconstruct_record(mgh_hierarchy *h, mgh_lossless_ctx *ll, DevBuf &q, DevBuf
   if (linear_head) {
     if (level >= mgh_l_target(h)) return hl_fail(MGH_ERR_FORMAT, "header: the hierarchy of the subdomain is not the header's");
     HL_TRY(lossless_decompress(ll, rv.rec, rv.csize, rv.lossless, src, n, &ocount, st, nullptr, /*sync_end=*/false,
-                               /*n_prefix=*/n_head, /*q_cap=*/q_cap));
+                               DecodeRange{/*n_prefix=*/n_head, q_cap}));
     return mgh_dequantize_recompose_linear_to_level(h, src, qp.eb, qp.tol, qp.s, qp.norm, qp.dict, 1,
                                                     (const uint64_t *)ll->oidx.p, (const int64_t *)ll->oval.p, ocount,
                                                     level, dst, st);
@@ -4628,7 +4437,7 @@ int mgh_lossless_decompress_prefix(mgh_lossless_ctx *ctx, const uint8_t *payload
   if (hipSetDevice(ctx->dev) != hipSuccess) return hl_fail(MGH_ERR_DEVICE, "hipSetDevice");
   try {
     HL_TRY(lossless_decompress(ctx, payload, size, lossless, d_q, n, ocount_out, (hipStream_t)stream, nullptr, true,
-                               n_prefix));
+                               DecodeRange{n_prefix}));
   } catch (const std::exception &e) {
     return hl_fail(MGH_ERR_DEVICE, e.what());
   }
@@ -4646,7 +4455,7 @@ int mgh_lossless_decompress_range(mgh_lossless_ctx *ctx, const uint8_t *payload,
   if (hipSetDevice(ctx->dev) != hipSuccess) return hl_fail(MGH_ERR_DEVICE, "hipSetDevice");
   try {
     HL_TRY(lossless_decompress(ctx, payload, size, lossless, d_q, n, ocount_out, (hipStream_t)stream, nullptr, true,
-                               first + count, ~(uint64_t)0, first));
+                               DecodeRange{first + count, ~(uint64_t)0, first}));
   } catch (const std::exception &e) {
     return hl_fail(MGH_ERR_DEVICE, e.what());
   }
@@ -4781,7 +4590,7 @@ int progressive_open(mgh_progressive *p, const void *data, size_t size) {
   p->ll->keep = 1;
   decompress_stats() = mgh_decompress_stats{};
   HL_TRY(lossless_decompress(p->ll, p->rv.rec, p->rv.csize, p->rv.lossless, nullptr, p->n, &p->ocount, p->st, nullptr,
-                             /*sync_end=*/true, /*n_prefix=*/0));
+                             /*sync_end=*/true, DecodeRange{/*n_prefix=*/0}));
   p->nchunk = decompress_stats().chunks_total;
   return MGH_SUCCESS;
 }
@@ -4817,8 +4626,8 @@ int progressive_refine(mgh_progressive *p, int to, void **out, bool prealloc) {
         HL_HIP(hipMemcpyAsync(qn.p, (const int64_t *)p->q[p->qi].p + (lo - p->q_first), carry * 8, hipMemcpyDeviceToDevice, st));
       if (new_end > p->dec_end) {
         HL_TRY(lossless_decompress(p->ll, p->rv.rec, p->rv.csize, p->rv.lossless, (int64_t *)qn.p + carry, p->n, &p->ocount, st,
-                                   nullptr, /*sync_end=*/false, /*n_prefix=*/new_end, /*q_cap=*/new_end - p->dec_end,
-                                   /*first=*/p->dec_end));
+                                   nullptr, /*sync_end=*/false,
+                                   DecodeRange{/*n_prefix=*/new_end, /*q_cap=*/new_end - p->dec_end, /*first=*/p->dec_end}));
       } else {  // (everything this refine reads was decoded with the boundary chunk of an earlier one)
         stats.chunks_total = p->nchunk;
         stats.record_bytes = p->rv.csize;

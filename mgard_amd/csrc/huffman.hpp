@@ -39,6 +39,8 @@
 #include <type_traits>
 #include <vector>
 
+#include "huffman_record.hpp"  // kSyncLanes, kParWaves, kParBatch: shared with the host-side plan
+
 namespace mgh {
 namespace huff {
 
@@ -436,7 +438,6 @@ inline size_t encode_chain_lds(size_t dict, size_t entry_bytes, size_t chunk) {
 // Code units at an address that need not be 8-byte aligned: a record inside a container starts
 // wherever the header and the records before it end, and the encoder / decoder work on the units
 // where they lie (gfx950 serves unaligned global dwordx2 accesses; atomics need alignment).
-constexpr int kSyncLanes = 64;  // synchronisation points per chunk = lanes of the decoder's wave
 __device__ __forceinline__ unsigned load_u32(const unsigned *p, size_t i) {  // (any byte alignment)
   unsigned v;
   __builtin_memcpy(&v, reinterpret_cast<const unsigned char *>(p) + 4 * i, 4);
@@ -879,9 +880,6 @@ k_decode(const unsigned long long *__restrict__ units, const unsigned long long 
 //   3. symbol counts are prefix-summed across the wave and every lane decodes its subsequence
 //      once more, now writing the symbols to their final positions.
 // Same tables and semantics as k_decode. Dynamic LDS as for k_decode without the unit ring.
-constexpr int kParWaves = 16;
-constexpr int kParBatch = 32;  // symbols a lane decodes between two write-outs
-
 __global__ void __launch_bounds__(64 * kParWaves)
 k_decode_par(const unsigned long long *__restrict__ units, const unsigned long long *__restrict__ bits,
              const unsigned long long *__restrict__ entry_of_chunk, size_t nchunk, int chunk, size_t n,
