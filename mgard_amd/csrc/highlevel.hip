@@ -38,6 +38,7 @@
 #include "env.hpp"
 #include "hierarchy.hpp"
 #include "compare_plan.hpp"
+#include "domain_plan.hpp"
 
 extern "C" void mgh_set_last_error_(const char *msg);  // capi.hip
 // (capi.hip: the reduction of mgh_compare on two device arrays given by element strides, asynchronous)
@@ -1044,217 +1045,18 @@ int lossless_decompress(mgh_lossless_ctx *c, const uint8_t *payload, uint64_t si
   return MGH_SUCCESS;
 }
 
-// ---- domain decomposition (host logic) ------------------------------------------------------
-struct Decomposer {
-  int D = 0;
-  std::vector<uint64_t> shape;
-  bool decomposed = false;
-  int method = MGH_DD_MAXDIM;
-  uint64_t dim = 0, size = 0;        // MaxDim: (dim, size); Block: size; Variable: dim
-  std::vector<uint64_t> var_sizes;   // Variable
-  uint64_t num = 1;
-
-  std::vector<uint64_t> dim_num_subdomain() const {  // DomainDecomposer.hpp:90-103
-    std::vector<uint64_t> r(D, 1);
-    if (!decomposed) return r;
-    if (method == MGH_DD_MAXDIM || method == MGH_DD_VARIABLE) r[dim] = num;
-    else for (int d = 0; d < D; d++) r[d] = (shape[d] - 1) / size + 1;
-    return r;
-  }
-  std::vector<uint64_t> dim_subdomain_id(uint64_t id) const {  // :105-113
-    const auto nd = dim_num_subdomain();
-    std::vector<uint64_t> r(D);
-    for (int d = D - 1; d >= 0; d--) {
-      r[d] = id % nd[d];
-      id /= nd[d];
-    }
-    return r;
-  }
-  std::vector<uint64_t> subdomain_shape(uint64_t id) const {  // :124-168
-    if (!decomposed) return shape;
-    std::vector<uint64_t> r = shape;
-    if (method == MGH_DD_MAXDIM) {
-      r[dim] = id < shape[dim] / size ? size : shape[dim] % size;
-    } else if (method == MGH_DD_BLOCK) {
-      const auto sid = dim_subdomain_id(id);
-      for (int d = 0; d < D; d++) r[d] = sid[d] < shape[d] / size ? size : shape[d] % size;
-    } else {
-      r[dim] = var_sizes[id];
-    }
-    return r;
-  }
-  std::vector<uint64_t> subdomain_offset(uint64_t id) const {  // :115-122, 690-700
-    std::vector<uint64_t> r(D, 0);
-    if (!decomposed) return r;
-    if (method == MGH_DD_MAXDIM) {
-      r[dim] = id * size;
-    } else if (method == MGH_DD_BLOCK) {
-      const auto sid = dim_subdomain_id(id);
-      for (int d = 0; d < D; d++) r[d] = sid[d] * size;
-    } else {
-      for (uint64_t k = 0; k < id; k++) r[dim] += var_sizes[k];
-    }
-    return r;
-  }
-  // A subdomain is one contiguous run of the full array when it spans every dimension but the
-  // slowest completely; then it can be used in place (no copy) if the array is device memory.
-  bool contiguous(uint64_t id) const {
-    const auto ext = subdomain_shape(id);
-    for (int d = 1; d < D; d++)
-      if (ext[d] != shape[d]) return false;
-    return true;
-  }
-  uint64_t linear_offset(uint64_t id) const {
-    uint64_t inner = 1;
-    for (int d = 1; d < D; d++) inner *= shape[d];
-    return subdomain_offset(id)[0] * inner;
-  }
-  bool all_contiguous() const {
-    for (uint64_t id = 0; id < num; id++)
-      if (!contiguous(id)) return false;
-    return true;
-  }
-  uint64_t max_subdomain_elems() const {
-    uint64_t m = 0;
-    for (uint64_t id = 0; id < num; id++) {
-      uint64_t c = 1;
-      for (uint64_t e : subdomain_shape(id)) c *= e;
-      m = std::max(m, c);
-    }
-    return m;
-  }
-};
-
-// Device bytes the REFERENCE plans for one subdomain of this shape -- its formula, so that the
-// MaxDim / Block auto-splits land on the reference's subdomain sizes
-// (DomainDecomposer::EstimateMemoryFootprint, DomainDecomposer.hpp:24-69, with
-// Hierarchy.hpp:420-, Compressor.hpp:84-116, DataRefactor.hpp:50-70, LinearQuantization.hpp:547-552,
-// Lossless.hpp:58-71, HuffmanWorkspace.hpp:58-92):
-//   [input N T + output N 8 + ratio 8 + hierarchy tables]  (x 2 with prefetch)
-//   + refactoring workspace prod(n_d + 2) T (twice for D > 3) + quantizers + Huffman workspace
-//     (outlier lists 16 N ratio, codes 8 N, chunk tables 24 nchunk, code-book scratch ~ 80 dict)
-//     + the int64 array 8 N when T is narrower than 8 bytes.
-// Left out, because they depend on the reference's runtime and are a few KB: the allocation pitch
-// of the fastest dimension (hipMallocPitch), the radix sort's temporary storage for `dict`
-// keys, 2 (warps-per-block x CUs + 1) status words. This implementation itself needs less
-// (no (n+2)^D workspace, 16-bit symbols), so following the reference only means splitting earlier.
-size_t estimate_footprint(const std::vector<uint64_t> &shape, size_t elem, const mgh_config &cfg,
-                          bool prefetch) {
-  const int D = (int)shape.size();
-  double n = 1, ws = 1;
-  for (uint64_t e : shape) {
-    n *= (double)e;
-    ws *= (double)(e + 2);
-  }
-  const double ratio = cfg.estimate_outlier_ratio;
-  // levels: every dim is halved until the smallest reaches 2 (Hierarchy.hpp:428-446)
-  int L = 64;
-  for (uint64_t e : shape) {
-    int k = 0;
-    for (uint64_t m = e; m > 2; m = m / 2 + 1) k++;
-    L = std::min(L, k);
-  }
-  double hier = 0;  // per level and dim: shape words, ranges, coordinates, dist, ratio, am, bm, volumes
-  for (int l = 0; l <= L; l++) {
-    for (uint64_t e : shape) {
-      uint64_t m = e;
-      for (int k = 0; k < L - l; k++) m = m / 2 + 1;
-      hier += 6.0 * (double)(m + 1) * elem;
-    }
-    hier += (double)D * 8 * 2;
-  }
-  double b = n * elem + n * 8 + ratio * 8 + hier;
-  if (prefetch) b *= 2;
-  const double dict = (double)cfg.huff_dict_size;
-  const double nchunk = std::floor((n - 1) / (double)cfg.huff_block_size) + 1;
-  double lossless = 8 + n * ratio * 16 + dict * 4 + dict * 8 + (8 * 128 + 8 * dict) + n * 8 + 3 * nchunk * 8 +
-                    4 + dict * 4 + dict * 8 + 4 * dict * 4 + 6 * dict * 4 + 8 * dict + 64;
-  double comp = ws * elem * (D > 3 ? 2 : 1) + elem + (L + 1) * (double)elem + lossless + elem;
-  if (8 > elem) comp += 8 * n;
-  return (size_t)(b + comp);
-}
-
-// Device bytes THIS implementation keeps for a compression with `nlanes` pipeline lanes and
-// `nbufs` input buffers (upper bound): per lane the quantized array (8 N: int64 where the 16-bit
-// symbols do not apply), its level-linearised copy, the outlier lists (16 per estimated outlier),
-// the hierarchy's workspace (levels below the top, per-slice vectors; the generic N-D path keeps
-// three whole arrays) and the lossless stage's code units (a subdomain that does not compress
-// below its own size is stored raw); per input buffer one dense subdomain.
-size_t own_resident_bytes(int D, uint64_t max_elems, size_t elem, const mgh_config &cfg, uint64_t ocap,
-                          int nlanes, int nbufs) {
-  const double n = (double)max_elems;
-  const double hier = (D <= 3 ? 0.5 : D == 4 ? 1.5 : 4.0) * n * (double)elem;
-  const double lane = 8 * n + (cfg.reorder ? 8 * n : 0) + 16.0 * (double)ocap + hier + (n * (double)elem + 4096) +
-                      (double)(64 << 20);  // (tables, chunk states, synchronisation points, allocator granularity)
-  return (size_t)(lane * nlanes + (double)nbufs * n * (double)elem);
-}
+// ---- domain decomposition: its host logic is domain_plan.hpp -------------------------------------
+// a refusal of domain_plan.hpp as a status of this file
+inline int hl_plan(const Refusal &r) { return r.msg ? hl_fail(r.code, r.msg) : MGH_SUCCESS; }
 
 int make_decomposer(Decomposer &dd, int D, const uint64_t *shape, size_t elem, const mgh_config &cfg) {
-  dd.D = D;
-  dd.shape.assign(shape, shape + D);
   size_t free_b = 0, total_b = 0;
   HL_HIP(hipMemGetInfo(&free_b, &total_b));
   const size_t avail = std::min<size_t>(free_b, cfg.max_memory_footprint);
-  auto need = [&](const std::vector<uint64_t> &s, bool prefetch) {
-    return estimate_footprint(s, elem, cfg, prefetch) >= avail;
-  };
-  dd.method = cfg.domain_decomposition;
-  if (!need(dd.shape, false) && dd.method != MGH_DD_BLOCK && dd.method != MGH_DD_VARIABLE) {
-    dd.decomposed = false;  // DomainDecomposer.hpp:303-311
-    dd.dim = 0;
-    dd.size = shape[0];
-    dd.num = 1;
-    return MGH_SUCCESS;
-  }
-  dd.decomposed = true;
-  if (dd.method == MGH_DD_MAXDIM) {  // :209-236
-    uint64_t mx = 0;
-    for (int d = 0; d < D; d++)
-      if (shape[d] > mx) {
-        mx = shape[d];
-        dd.dim = d;
-      }
-    std::vector<uint64_t> cs = dd.shape;
-    bool prefetch = false;
-    while (need(cs, prefetch)) {
-      if (cs[dd.dim] <= 3) return hl_fail(MGH_ERR_OUT_OF_MEMORY, "domain decomposition: not enough device memory");
-      cs[dd.dim] = (cs[dd.dim] - 1) / 2 + 1;
-      prefetch = (shape[dd.dim] - 1) / cs[dd.dim] + 1 > 1;
-    }
-    dd.size = cs[dd.dim];
-    dd.num = (shape[dd.dim] - 1) / dd.size + 1;
-  } else if (dd.method == MGH_DD_BLOCK) {  // :238-263, 335-349
-    dd.size = cfg.block_size;
-    if (dd.size < 3) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "block_size");
-    for (;;) {
-      std::vector<uint64_t> cs(D, dd.size);
-      uint64_t cnt = 1;
-      for (int d = 0; d < D; d++) cnt *= (shape[d] - 1) / dd.size + 1;
-      if (!need(cs, cnt > 1)) break;
-      if (dd.size <= 3) return hl_fail(MGH_ERR_OUT_OF_MEMORY, "domain decomposition: not enough device memory");
-      dd.size = (dd.size - 1) / 2 + 1;
-    }
-    dd.num = 1;
-    for (int d = 0; d < D; d++) dd.num *= (shape[d] - 1) / dd.size + 1;
-  } else if (dd.method == MGH_DD_VARIABLE) {  // :350-357
-    if (cfg.domain_decomposition_dim < 0 || cfg.domain_decomposition_dim >= D ||
-        !cfg.domain_decomposition_sizes || !cfg.num_domain_decomposition_sizes)
-      return hl_fail(MGH_ERR_INVALID_ARGUMENT, "Variable domain decomposition needs dim and sizes");
-    dd.dim = cfg.domain_decomposition_dim;
-    dd.var_sizes.assign(cfg.domain_decomposition_sizes,
-                        cfg.domain_decomposition_sizes + cfg.num_domain_decomposition_sizes);
-    uint64_t sum = 0;
-    for (uint64_t v : dd.var_sizes) sum += v;
-    if (sum != shape[dd.dim]) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "Variable sizes do not add up to the extent");
-    dd.num = dd.var_sizes.size();
-    dd.size = dd.var_sizes[0];
-  } else {
-    return hl_fail(MGH_ERR_INVALID_ARGUMENT, "domain_decomposition");
-  }
-  for (uint64_t id = 0; id < dd.num; id++)
-    for (uint64_t e : dd.subdomain_shape(id))
-      if (e < 3) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "domain decomposition leaves a subdomain with fewer than 3 nodes in a dimension");
-  return MGH_SUCCESS;
+  return hl_plan(split_domain(dd, D, shape, elem, avail, cfg.domain_decomposition, cfg.block_size,
+                              cfg.domain_decomposition_dim, cfg.domain_decomposition_sizes,
+                              cfg.num_domain_decomposition_sizes, cfg.estimate_outlier_ratio, cfg.huff_dict_size,
+                              cfg.huff_block_size));
 }
 
 // ---- host side of the host <-> device transfers ----------------------------------------------
@@ -1947,16 +1749,6 @@ int get_hierarchy(mgh_hierarchy **out, bool *owned, int dtype, const std::vector
   return MGH_SUCCESS;
 }
 
-// calc_local_abs_tol (ErrorToleranceCalculator.hpp:134-155), in the data type
-template <typename T> T local_abs_tol(int ebtype, T norm, T tol, T s, uint64_t nsub) {
-  if (ebtype == MGH_REL) {
-    if (s == std::numeric_limits<T>::infinity()) return tol * norm;
-    return std::sqrt((tol * norm) * (tol * norm) / (T)nsub);
-  }
-  if (s == std::numeric_limits<T>::infinity()) return tol;
-  return std::sqrt((tol * tol) / (T)nsub);
-}
-
 int header_from(const Decomposer &dd, int dtype, int ebtype, double tol, double s, double norm,
                 const std::vector<std::vector<double>> *coords, const mgh_config &cfg, fmt::Header &h) {
   h = fmt::Header();
@@ -2068,7 +1860,7 @@ int compress_impl(int D, int dtype, const uint64_t *shape, double tol_d, double 
     size_t free_b = 0, total_b = 0;
     HL_HIP(hipMemGetInfo(&free_b, &total_b));
     const size_t avail = std::min<size_t>(free_b + g_cache.held_bytes(), cfg.max_memory_footprint);
-    if (own_resident_bytes(D, max_elems, elem, cfg, ocap, nlanes, nbufs) > avail) {
+    if (own_resident_bytes(D, max_elems, elem, cfg.reorder != 0, ocap, nlanes, nbufs) > avail) {
       nlanes = 1;
       nbufs = zero_copy ? 0 : (int)std::min<uint64_t>(dd.num, 2);
     }
@@ -2140,16 +1932,13 @@ int compress_impl(int D, int dtype, const uint64_t *shape, double tol_d, double 
         return cleanup(hl_fail(MGH_ERR_DEVICE, "norms of the subdomains"));
       for (mgh_hierarchy *h : owned_alive) mgh_hierarchy_destroy(h);
       owned_alive.clear();
-      double acc = 0;
+      NormAccumulator na{s == std::numeric_limits<T>::infinity(), cfg.normalize_coordinates != 0};
       for (uint64_t id = 0; id < dd.num; id++) {
-        const double ln = (double)((const T *)g_cache.aux_pin.p)[id];
         uint64_t cnt = 1;
         for (uint64_t e : dd.subdomain_shape(id)) cnt *= e;
-        if (s == std::numeric_limits<T>::infinity()) acc = std::max(acc, ln);
-        else acc += ln * ln * (cfg.normalize_coordinates ? (double)cnt : 1.0);  // un-normalised square
+        na.add((double)((const T *)g_cache.aux_pin.p)[id], cnt);
       }
-      if (s == std::numeric_limits<T>::infinity()) norm = (T)acc;
-      else norm = (T)(cfg.normalize_coordinates ? std::sqrt(acc / (double)total) : std::sqrt(acc));
+      norm = (T)na.result(total);
     }
     local_tol = local_abs_tol<T>(ebtype, norm, tol, s, dd.num);
     local_eb = MGH_ABS;  // CompressionHighLevel.hpp:135-138
@@ -2389,36 +2178,7 @@ int compress_impl(int D, int dtype, const uint64_t *shape, double tol_d, double 
 }
 
 int decomposer_from_header(const fmt::Header &hd, const mgh_config &cfg, Decomposer &dd) {
-  dd.D = (int)hd.shape.size();
-  dd.shape = hd.shape;
-  dd.decomposed = hd.dd_method != fmt::DD_NOOP;
-  dd.dim = hd.dd_dim;
-  dd.size = hd.dd_size;
-  dd.num = 1;
-  if (!dd.decomposed) return MGH_SUCCESS;
-  if (dd.dim >= (uint64_t)dd.D || dd.size == 0) return hl_fail(MGH_ERR_FORMAT, "header: domain decomposition");
-  if (hd.dd_method == fmt::DD_MAX_DIMENSION) {
-    dd.method = MGH_DD_MAXDIM;
-    dd.num = (dd.shape[dd.dim] - 1) / dd.size + 1;
-  } else if (hd.dd_method == fmt::DD_BLOCK) {
-    dd.method = MGH_DD_BLOCK;
-    for (int d = 0; d < dd.D; d++) dd.num *= (dd.shape[d] - 1) / dd.size + 1;
-  } else if (hd.dd_method == fmt::DD_VARIABLE) {
-    // the header records one size only; like the reference the caller's config supplies the
-    // list (DomainDecomposer.hpp:448-452)
-    dd.method = MGH_DD_VARIABLE;
-    if (!cfg.domain_decomposition_sizes || !cfg.num_domain_decomposition_sizes)
-      return hl_fail(MGH_ERR_INVALID_ARGUMENT, "Variable domain decomposition: pass the sizes in the config");
-    dd.var_sizes.assign(cfg.domain_decomposition_sizes,
-                        cfg.domain_decomposition_sizes + cfg.num_domain_decomposition_sizes);
-    uint64_t sum = 0;
-    for (uint64_t v : dd.var_sizes) sum += v;
-    if (sum != dd.shape[dd.dim]) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "Variable sizes do not add up to the extent");
-    dd.num = dd.var_sizes.size();
-  } else {
-    return hl_fail(MGH_ERR_FORMAT, "header: unknown domain decomposition");
-  }
-  return MGH_SUCCESS;
+  return hl_plan(mgh::decomposer_from_header(hd, cfg.domain_decomposition_sizes, cfg.num_domain_decomposition_sizes, dd));
 }
 
 // first bytes of a (host or device) stream on the host
@@ -2470,60 +2230,6 @@ int header_level_shape(const fmt::Header &hd, const mgh_config &cfg, int level, 
   return MGH_SUCCESS;
 }
 
-// ---- a decomposed container after `halvings` coarsenings of every subdomain (host only) -------------
-// Every subdomain has its own hierarchy and l_target, so a level number means a different resolution in
-// each; the number of halvings (n -> n/2 + 1, the hierarchy's rule) means the same in all of them.
-// Subdomain i is taken at level l_target_i - halvings, and because every block gets exactly `halvings`
-// coarsenings its extent along d depends on its extent along d alone: the level arrays stitch into a
-// tensor-product array for MaxDim, Block and Variable decompositions alike.
-struct StitchedLayout {
-  int K = 0;                                 // min over the subdomains of l_target: the most halvings possible
-  std::vector<uint64_t> shape;               // of the stitched array
-  std::vector<std::vector<uint64_t>> ext;    // [d][j]: extent of the block at grid position j after the halvings
-  std::vector<std::vector<uint64_t>> off;    // [d][j]: its offset in the stitched array
-  std::vector<std::vector<uint64_t>> nodes;  // [d]: index in the FULL array of every node of the stitched grid
-};
-// halvings < 0: only K. Extents are validated here (a header is untrusted). The node list is made for
-// nodes_of_dim alone (it is as long as the extent of the full array).
-int stitched_layout(const Decomposer &dd, uint64_t max_level, int halvings, StitchedLayout &sl,
-                    int nodes_of_dim = -1) {
-  const int D = dd.D;
-  if (D < 1 || D > MGH_MAX_DIM) return hl_fail(MGH_ERR_UNSUPPORTED_DIMENSION, "header: dimension");
-  sl.K = std::numeric_limits<int>::max();
-  for (uint64_t id = 0; id < dd.num; id++) {
-    const auto s = dd.subdomain_shape(id);
-    for (uint64_t e : s)
-      if (e < 3) return hl_fail(MGH_ERR_FORMAT, "header: subdomain with fewer than 3 nodes");
-    sl.K = std::min(sl.K, mgh::hierarchy_l_target(s.size(), s.data(), max_level));
-  }
-  if (halvings < 0) return MGH_SUCCESS;
-  if (halvings > sl.K)
-    return hl_fail(MGH_ERR_INVALID_ARGUMENT, "halvings outside 0 .. the smallest l_target of the subdomains");
-  const auto nd = dd.dim_num_subdomain();
-  sl.shape.assign(D, 0);
-  sl.ext.assign(D, {});
-  sl.off.assign(D, {});
-  sl.nodes.assign(D, {});
-  std::vector<uint64_t> idx;
-  for (int d = 0; d < D; d++) {
-    uint64_t stride = 1;  // subdomain ids are row-major over the decomposition grid
-    for (int e = d + 1; e < D; e++) stride *= nd[e];
-    for (uint64_t j = 0; j < nd[d]; j++) {
-      const uint64_t id = j * stride;  // (grid position j along d, 0 elsewhere)
-      const uint64_t n = dd.subdomain_shape(id)[d], at = dd.subdomain_offset(id)[d];
-      uint64_t m = n;
-      for (int k = 0; k < halvings; k++) m = m / 2 + 1;
-      sl.ext[d].push_back(m);
-      sl.off[d].push_back(sl.shape[d]);
-      sl.shape[d] += m;
-      if (d != nodes_of_dim) continue;
-      mgh::level_nodes(n, halvings, idx);
-      for (uint64_t i : idx) sl.nodes[d].push_back(at + i);
-    }
-  }
-  return MGH_SUCCESS;
-}
-
 // ---- what the decoders (mgh_decompress*, mgh_progressive_*) share ------------------------------------
 // One subdomain record inside a container.
 struct RecordView {
@@ -2550,6 +2256,26 @@ int record_view_at(const void *container, size_t size, size_t at, uint64_t data_
   rv.rec = (const uint8_t *)container + at + 8;
   rv.raw = !((double)data_bytes / (double)rv.csize > 1.0);  // GPUPipelines.hpp:414-417
   if (rv.raw && rv.csize != data_bytes) return hl_fail(MGH_ERR_FORMAT, "raw subdomain record has the wrong size");
+  return MGH_SUCCESS;
+}
+
+// Where the `num` records of a (host or device) container lie behind its header of meta_size bytes: the
+// offset of every size prefix and the length of its frame, prefix included.
+int record_table(const void *container, size_t size, size_t meta_size, uint64_t num, std::vector<size_t> &off,
+                 std::vector<size_t> &len) {
+  off.assign(num, 0);
+  len.assign(num, 0);
+  size_t at = meta_size;
+  std::vector<uint8_t> sz;
+  for (uint64_t id = 0; id < num; id++) {
+    if (const char *bad = frame_prefix(size, at)) return hl_fail(MGH_ERR_FORMAT, bad);
+    uint64_t cs = 0;
+    HL_TRY(fetch_host((const char *)container + at, 8, 8, sz));
+    std::memcpy(&cs, sz.data(), 8);
+    off[id] = at;
+    if (const char *bad = frame_next(size, at, cs, &at)) return hl_fail(MGH_ERR_FORMAT, bad);
+    len[id] = at - off[id];
+  }
   return MGH_SUCCESS;
 }
 
@@ -2693,9 +2419,7 @@ int decompress_impl(const fmt::Header &hd, size_t meta_size, const void *compres
   if (level >= 0) HL_TRY(header_level_shape(hd, cfg, level, &l_target, &dshape));
   Decomposer dd;
   HL_TRY(decomposer_from_header(hd, cfg, dd));
-  for (uint64_t id = 0; id < dd.num; id++)
-    for (uint64_t e : dd.subdomain_shape(id))
-      if (e < 3) return hl_fail(MGH_ERR_FORMAT, "header: subdomain with fewer than 3 nodes");
+  if (const char *bad = check_extents(dd)) return hl_fail(MGH_ERR_FORMAT, bad);
   std::vector<SubdomainPlan> plan(dd.num);
   if (level >= 0) {
     plan[0].level = level;
@@ -2704,7 +2428,7 @@ int decompress_impl(const fmt::Header &hd, size_t meta_size, const void *compres
     plan[0].linear_head = hd.reorder && level < l_target;
   } else if (halvings >= 0) {  // (refuses more halvings than the shallowest subdomain has levels)
     StitchedLayout sl;
-    HL_TRY(stitched_layout(dd, cfg.max_larget_level, halvings, sl));
+    HL_TRY(hl_plan(stitched_layout(dd, cfg.max_larget_level, halvings, sl)));
     if (halvings > 0) {
       if (!preview) dshape = sl.shape;
       for (uint64_t id = 0; id < dd.num; id++) {
@@ -3251,14 +2975,6 @@ struct MultiErr {
   }
 };
 
-inline uint64_t multi_slab_size(uint64_t n0, int ndev) {
-  // ceil(n0 / ndev), grown until the last slab has at least 3 planes (a hierarchy needs them)
-  uint64_t size = (n0 + ndev - 1) / ndev;
-  size = std::max<uint64_t>(size, 3);
-  while (size < n0 && n0 % size != 0 && n0 % size < 3) size++;
-  return size;
-}
-
 void worker_thread_teardown();
 
 template <typename T>
@@ -3267,14 +2983,7 @@ int compress_multi_impl(int ndev, const int *devs, int D, int dtype, const uint6
                         void **compressed, size_t *compressed_size, const void *const *coords_in,
                         const mgh_config &cfg0, bool prealloc) {
   const size_t elem = sizeof(T);
-  Decomposer dd;
-  dd.D = D;
-  dd.shape.assign(shape, shape + D);
-  dd.method = MGH_DD_MAXDIM;
-  dd.dim = 0;
-  dd.size = multi_slab_size(shape[0], ndev);
-  dd.num = (shape[0] - 1) / dd.size + 1;
-  dd.decomposed = dd.num > 1;
+  const Decomposer dd = Decomposer::slabs_of_dim0(std::vector<uint64_t>(shape, shape + D), multi_slab_size(shape[0], ndev));
   if (!dd.decomposed) {  // nothing to share out
     mgh_config c = cfg0;
     c.dev_id = devs[0];
@@ -3330,14 +3039,9 @@ int compress_multi_impl(int ndev, const int *devs, int D, int dtype, const uint6
     std::unique_lock<std::mutex> lk(rv_m);
     if (++rv_arrived == nthr) {
       if (ebtype == MGH_REL && err.rc == MGH_SUCCESS) {
-        double acc = 0;
-        for (uint64_t id = 0; id < num; id++) {
-          const uint64_t cnt = inner * dd.subdomain_shape(id)[0];
-          if (s == std::numeric_limits<T>::infinity()) acc = std::max(acc, ln[id]);
-          else acc += ln[id] * ln[id] * (cfg0.normalize_coordinates ? (double)cnt : 1.0);
-        }
-        if (s == std::numeric_limits<T>::infinity()) norm = (T)acc;
-        else norm = (T)(cfg0.normalize_coordinates ? std::sqrt(acc / (double)total) : std::sqrt(acc));
+        NormAccumulator na{s == std::numeric_limits<T>::infinity(), cfg0.normalize_coordinates != 0};
+        for (uint64_t id = 0; id < num; id++) na.add(ln[id], inner * dd.subdomain_shape(id)[0]);
+        norm = (T)na.result(total);
       }
       local_tol = local_abs_tol<T>(ebtype, norm, tol, s, num);
       rv_cv.notify_all();
@@ -3543,17 +3247,8 @@ int decompress_multi_impl(int ndev, const int *devs, const fmt::Header &hd, size
   };
   // record offsets (the sizes are in the stream)
   const uint64_t num = dd.num;
-  std::vector<size_t> off(num), len(num);
-  size_t at = meta_size;
-  for (uint64_t id = 0; id < num; id++) {
-    if (at + 8 > compressed_size) return bail(hl_fail(MGH_ERR_FORMAT, "truncated stream"));
-    uint64_t cs = 0;
-    std::memcpy(&cs, (const char *)compressed + at, 8);
-    if (cs > compressed_size - at - 8) return bail(hl_fail(MGH_ERR_FORMAT, "truncated record"));
-    off[id] = at;
-    len[id] = 8 + (size_t)cs;
-    at += len[id];
-  }
+  std::vector<size_t> off, len;
+  if (const int rc = record_table(compressed, compressed_size, meta_size, num, off, len)) return bail(rc);
   const T norm = (T)hd.norm, tol = (T)hd.tol, s = (T)hd.s;
   const T local_tol = local_abs_tol<T>(hd.rel ? MGH_REL : MGH_ABS, norm, tol, s, num);
   const int nthr = (int)std::min<uint64_t>(num, (uint64_t)ndev);
@@ -3566,29 +3261,7 @@ int decompress_multi_impl(int ndev, const int *devs, const fmt::Header &hd, size
       c.dev_id = devs[k];
       for (uint64_t id = k; id < num && err.rc == MGH_SUCCESS; id += nthr) {
         // the record as a container of its own: header of the slab (ABS bound) + the record
-        Decomposer one;
-        one.D = dd.D;
-        one.shape = dd.subdomain_shape(id);
-        one.decomposed = false;
-        one.num = 1;
-        std::vector<std::vector<double>> sc;
-        if (!hd.uniform) {
-          sc = hd.coords;
-          const uint64_t o0 = dd.subdomain_offset(id)[0];
-          sc[0].assign(hd.coords[0].begin() + o0, hd.coords[0].begin() + o0 + one.shape[0]);
-        }
-        // everything the stream says about itself (reorder, lossless choice, dictionary, ...) comes
-        // from ITS header, never from the caller's config; only what describes the slab changes
-        fmt::Header sh = hd;
-        sh.shape = one.shape;
-        if (!hd.uniform) sh.coords = sc;
-        sh.rel = false;
-        sh.tol = (double)local_tol;
-        sh.norm = 0.0;
-        sh.dd_method = fmt::DD_NOOP;
-        sh.dd_dim = 0;
-        sh.dd_size = 0;
-        const std::vector<uint8_t> meta = fmt::serialize_metadata(sh);
+        const std::vector<uint8_t> meta = fmt::serialize_metadata(slab_header(hd, dd, id, (double)local_tol));
         std::vector<uint8_t> mini(meta.size() + len[id]);
         std::memcpy(mini.data(), meta.data(), meta.size());
         std::memcpy(mini.data() + meta.size(), (const char *)compressed + off[id], len[id]);
@@ -3762,16 +3435,6 @@ RcclApi g_rccl;
     if (_r != 0) return hl_fail(MGH_ERR_DEVICE, std::string(#expr) + ": " + g_rccl.GetErrorString(_r)); \
   } while (0)
 
-// slabs of dimension 0 in rank order as a MaxDim decomposition: all of one size, the last one
-// may be shorter
-int dist_slab_size(const std::vector<uint64_t> &n0, uint64_t *size) {
-  *size = n0[0];
-  for (size_t r = 0; r + 1 < n0.size(); r++)
-    if (n0[r] != *size) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "mgh_*_dist: every rank but the last must hold the same number of planes");
-  if (n0.back() > *size || n0.back() < 3) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "mgh_*_dist: the last rank holds more planes than the others, or fewer than 3");
-  return MGH_SUCCESS;
-}
-
 template <typename T>
 int compress_dist_impl(void *comm, int rank, int nranks, int root, int D, int dtype, const uint64_t *lshape,
                        double tol_d, double s_d, int ebtype, const void *d_local, void **compressed,
@@ -3804,17 +3467,12 @@ int compress_dist_impl(void *comm, int rank, int nranks, int root, int D, int dt
     return mgh_compress(D, dtype, lshape, tol_d, s_d, ebtype, d_local, compressed, compressed_size, coords_in, &cfg,
                         prealloc);
   uint64_t slab = 0;
-  HL_TRY(dist_slab_size(n0, &slab));
-  Decomposer dd;
-  dd.D = D;
-  dd.shape.assign(lshape, lshape + D);
-  dd.shape[0] = 0;
-  for (uint64_t e : n0) dd.shape[0] += e;
-  dd.method = MGH_DD_MAXDIM;
-  dd.dim = 0;
-  dd.size = slab;
-  dd.num = (uint64_t)nranks;
-  dd.decomposed = true;
+  if (const char *bad = dist_slab_size(n0, &slab)) return hl_fail(MGH_ERR_INVALID_ARGUMENT, bad);
+  std::vector<uint64_t> gshape(lshape, lshape + D);  // of the whole domain
+  gshape[0] = 0;
+  for (uint64_t e : n0) gshape[0] += e;
+  // (one slab per rank, nranks >= 2 of them: dist_slab_size saw to it)
+  const Decomposer dd = Decomposer::slabs_of_dim0(gshape, slab);
   size_t total = 1, cnt = 1;
   for (int d = 0; d < D; d++) {
     total *= dd.shape[d];
@@ -3834,14 +3492,13 @@ int compress_dist_impl(void *comm, int rank, int nranks, int root, int D, int dt
     const int rc = mgh_norm(h, d_local, s_d, &ln, st);
     if (owned) mgh_hierarchy_destroy(h);
     HL_TRY(rc);
-    const bool inf = s == std::numeric_limits<T>::infinity();
-    double acc = inf ? ln : ln * ln * (cfg.normalize_coordinates ? (double)cnt : 1.0);
-    HL_HIP(hipMemcpyAsync(dscal.p, &acc, 8, hipMemcpyHostToDevice, st));
-    HL_NCCL(g_rccl.AllReduce(dscal.p, (char *)dscal.p + 8, 1, RcclApi::kFloat64, inf ? RcclApi::kMax : RcclApi::kSum, comm, st));
-    HL_HIP(hipMemcpyAsync(&acc, (char *)dscal.p + 8, 8, hipMemcpyDeviceToHost, st));
+    NormAccumulator na{s == std::numeric_limits<T>::infinity(), cfg.normalize_coordinates != 0};
+    na.add(ln, cnt);  // this rank's contribution; the ranks' are reduced the way add() combines them
+    HL_HIP(hipMemcpyAsync(dscal.p, &na.acc, 8, hipMemcpyHostToDevice, st));
+    HL_NCCL(g_rccl.AllReduce(dscal.p, (char *)dscal.p + 8, 1, RcclApi::kFloat64, na.inf ? RcclApi::kMax : RcclApi::kSum, comm, st));
+    HL_HIP(hipMemcpyAsync(&na.acc, (char *)dscal.p + 8, 8, hipMemcpyDeviceToHost, st));
     HL_HIP(hipStreamSynchronize(st));
-    if (inf) norm = (T)acc;
-    else norm = (T)(cfg.normalize_coordinates ? std::sqrt(acc / (double)total) : std::sqrt(acc));
+    norm = (T)na.result(total);
   }
   const T local_tol = local_abs_tol<T>(ebtype, norm, tol, s, (uint64_t)nranks);
   // ---- this rank's slab as a stand-alone ABS compression; its body is the record ----
@@ -3943,15 +3600,11 @@ int decompress_dist_impl(void *comm, int rank, int nranks, int root, fmt::Header
   HL_TRY(dtab.ensure((size_t)nranks * 16));
   std::vector<uint64_t> tab((size_t)nranks * 2, 0);  // offset (of the size prefix), length (prefix included)
   if (rank == root) {
-    size_t at = meta_size;
+    std::vector<size_t> off, len;
+    HL_TRY(record_table(compressed, compressed_size, meta_size, (uint64_t)nranks, off, len));
     for (int r = 0; r < nranks; r++) {
-      if (at + 8 > compressed_size) return hl_fail(MGH_ERR_FORMAT, "truncated stream");
-      uint64_t cs = 0;
-      HL_TRY(aux_read(&cs, (const char *)compressed + at, 8));
-      if (cs > compressed_size - at - 8) return hl_fail(MGH_ERR_FORMAT, "truncated record");
-      tab[2 * r] = at;
-      tab[2 * r + 1] = 8 + cs;
-      at += 8 + cs;
+      tab[2 * r] = off[r];
+      tab[2 * r + 1] = len[r];
     }
     HL_HIP(hipMemcpyAsync(dtab.p, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, st));
   }
@@ -3961,19 +3614,7 @@ int decompress_dist_impl(void *comm, int rank, int nranks, int root, fmt::Header
   // this rank's record behind the header of its slab: a container of its own (decompress_multi_impl)
   const T norm = (T)hd.norm, tol = (T)hd.tol, s = (T)hd.s;
   const T local_tol = local_abs_tol<T>(hd.rel ? MGH_REL : MGH_ABS, norm, tol, s, (uint64_t)nranks);
-  fmt::Header sh = hd;
-  sh.shape = dd.subdomain_shape((uint64_t)rank);
-  if (!hd.uniform) {
-    const uint64_t o0 = dd.subdomain_offset((uint64_t)rank)[0];
-    sh.coords[0].assign(hd.coords[0].begin() + o0, hd.coords[0].begin() + o0 + sh.shape[0]);
-  }
-  sh.rel = false;
-  sh.tol = (double)local_tol;
-  sh.norm = 0.0;
-  sh.dd_method = fmt::DD_NOOP;
-  sh.dd_dim = 0;
-  sh.dd_size = 0;
-  const std::vector<uint8_t> meta = fmt::serialize_metadata(sh);
+  const std::vector<uint8_t> meta = fmt::serialize_metadata(slab_header(hd, dd, (uint64_t)rank, (double)local_tol));
   const size_t mylen = tab[2 * rank + 1];
   DevBuf mini;
   Rel rel_mini{mini};
@@ -4177,7 +3818,7 @@ int infer_coarsened(const void *data, size_t size, const mgh_config *config, int
   HL_TRY(decomposer_from_header(hd, *config, dd));
   if (halvings >= 0 && nodes_of_dim != -1 && (nodes_of_dim < 0 || nodes_of_dim >= dd.D))
     return hl_fail(MGH_ERR_INVALID_ARGUMENT, "dim / NULL argument");
-  return stitched_layout(dd, config->max_larget_level, halvings, sl, nodes_of_dim);
+  return hl_plan(stitched_layout(dd, config->max_larget_level, halvings, sl, nodes_of_dim));
 }
 } // namespace
 

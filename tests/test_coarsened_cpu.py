@@ -18,10 +18,9 @@ import re
 import numpy as np
 import pytest
 
-from tests.util import nonuniform_coords
+from tests.util import MAXDIM, BLOCK, VARIABLE, blocks, nonuniform_coords
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-MAXDIM, BLOCK, VARIABLE = 0, 1, 2
 
 
 def keep(n, k):
@@ -42,28 +41,6 @@ def steps_to_two(n):
         n = n // 2 + 1
         k += 1
     return k
-
-
-def blocks(shape, dd, sizes=None):
-    """Per dimension the list of (offset, extent) of the decomposition grid. dd = (method, dim, size) or None."""
-    out = [[(0, n)] for n in shape]
-    if dd is None:
-        return out
-    method, dim, size = dd
-
-    def cut(n):
-        full, rest = divmod(n, size)
-        ext = [size] * full + ([rest] if rest else [])
-        return [(j * size, e) for j, e in enumerate(ext)]
-
-    if method == MAXDIM:
-        out[dim] = cut(shape[dim])
-    elif method == BLOCK:
-        out = [cut(n) for n in shape]
-    else:
-        assert sum(sizes) == shape[dim]
-        out[dim] = [(int(sum(sizes[:j])), e) for j, e in enumerate(sizes)]
-    return out
 
 
 def expected(shape, dd, sizes, max_level):

@@ -7,7 +7,7 @@ import pytest
 
 import oracle
 from tests import payload as pl
-from tests.util import nonuniform_coords, smooth_field
+from tests.util import nonuniform_coords, reference_footprint as _reference_footprint, smooth_field
 
 pytestmark = pytest.mark.gpu
 
@@ -244,40 +244,6 @@ def test_outlier_estimate_too_small_is_retried():
         b = b if isinstance(b, np.ndarray) else b.cpu().numpy()
         assert np.array_equal(a, b)
         assert float(np.max(np.abs(a - u))) <= 1e-4 * float(np.max(np.abs(u))) * (1 + 1e-6)
-
-
-def _reference_footprint(shape, elem, ratio=1.0, dict_size=8192, block=20480, prefetch=False):
-    """DomainDecomposer::EstimateMemoryFootprint (DomainDecomposer.hpp:24-69 and the estimators it
-    calls), runtime-independent terms -- restated here independently of highlevel.hip."""
-    D = len(shape)
-    n = float(np.prod(shape, dtype=np.float64))
-    ws = float(np.prod([e + 2 for e in shape], dtype=np.float64))
-    def levels(e):
-        k = 0
-        while e > 2:
-            e = e // 2 + 1
-            k += 1
-        return k
-    L = min(levels(e) for e in shape)
-    hier = 0.0
-    for l in range(L + 1):
-        for e in shape:
-            m = e
-            for _ in range(L - l):
-                m = m // 2 + 1
-            hier += 6.0 * (m + 1) * elem
-        hier += D * 8 * 2
-    b = n * elem + n * 8 + ratio * 8 + hier
-    if prefetch:
-        b *= 2
-    nchunk = np.floor((n - 1) / block) + 1
-    lossless = (8 + n * ratio * 16 + dict_size * 4 + dict_size * 8 + (8 * 128 + 8 * dict_size) + n * 8 +
-                3 * nchunk * 8 + 4 + dict_size * 4 + dict_size * 8 + 16 * dict_size + 24 * dict_size +
-                8 * dict_size + 64)
-    comp = ws * elem * (2 if D > 3 else 1) + elem + (L + 1) * elem + lossless + elem
-    if 8 > elem:
-        comp += 8 * n
-    return int(b + comp)
 
 
 def test_maxdim_split_follows_the_reference_footprint():

@@ -42,3 +42,61 @@ def inside_field(shape, dtype=np.float32, seed=1):
     g = g + 1e-3 * np.random.default_rng(seed).uniform(-1, 1, size=shape)
     return np.ascontiguousarray(g.astype(dtype))
 
+
+MAXDIM, BLOCK, VARIABLE = 0, 1, 2  # mgh_domain_decomposition
+
+
+def blocks(shape, dd, sizes=None):
+    """Per dimension the list of (offset, extent) of the decomposition grid. dd = (method, dim, size) or None."""
+    out = [[(0, n)] for n in shape]
+    if dd is None:
+        return out
+    method, dim, size = dd
+
+    def cut(n):
+        full, rest = divmod(n, size)
+        ext = [size] * full + ([rest] if rest else [])
+        return [(j * size, e) for j, e in enumerate(ext)]
+
+    if method == MAXDIM:
+        out[dim] = cut(shape[dim])
+    elif method == BLOCK:
+        out = [cut(n) for n in shape]
+    else:
+        assert sum(sizes) == shape[dim]
+        out[dim] = [(int(sum(sizes[:j])), e) for j, e in enumerate(sizes)]
+    return out
+
+
+def reference_footprint(shape, elem, ratio=1.0, dict_size=8192, block=20480, prefetch=False):
+    """DomainDecomposer::EstimateMemoryFootprint (DomainDecomposer.hpp:24-69 and the estimators it
+    calls), runtime-independent terms -- restated here independently of the library."""
+    D = len(shape)
+    n = float(np.prod(shape, dtype=np.float64))
+    ws = float(np.prod([e + 2 for e in shape], dtype=np.float64))
+    def levels(e):
+        k = 0
+        while e > 2:
+            e = e // 2 + 1
+            k += 1
+        return k
+    L = min(levels(e) for e in shape)
+    hier = 0.0
+    for l in range(L + 1):
+        for e in shape:
+            m = e
+            for _ in range(L - l):
+                m = m // 2 + 1
+            hier += 6.0 * (m + 1) * elem
+        hier += D * 8 * 2
+    b = n * elem + n * 8 + ratio * 8 + hier
+    if prefetch:
+        b *= 2
+    nchunk = np.floor((n - 1) / block) + 1
+    lossless = (8 + n * ratio * 16 + dict_size * 4 + dict_size * 8 + (8 * 128 + 8 * dict_size) + n * 8 +
+                3 * nchunk * 8 + 4 + dict_size * 4 + dict_size * 8 + 16 * dict_size + 24 * dict_size +
+                8 * dict_size + 64)
+    comp = ws * elem * (2 if D > 3 else 1) + elem + (L + 1) * elem + lossless + elem
+    if 8 > elem:
+        comp += 8 * n
+    return int(b + comp)
