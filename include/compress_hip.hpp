@@ -181,6 +181,37 @@ inline compress_status_type verify(const void *compressed_data, size_t compresse
   return detail::status(mgh_verify(compressed_data, compressed_size, original_data, original_bytes, (int)dtype, halvings,
                                    &c, &result));
 }
+// EXTENSION: mgh_estimate_sizes. What compress(tol) would write for every tolerance of `tols` (1..64),
+// from one decomposition: estimates[k].bytes_min <= size <= bytes_max. Containers of one subdomain,
+// lossless_type::Huffman only (Failure otherwise; mgh_last_error() says which).
+inline compress_status_type estimate_sizes(DIM D, data_type dtype, std::vector<SIZE> shape,
+                                           const std::vector<double> &tols, double s, error_bound_type mode,
+                                           const void *original_data, std::vector<const Byte *> coords,
+                                           HighLevelConfig config, std::vector<mgh_size_estimate> &estimates) {
+  if (shape.size() != D) return compress_status_type::Failure;
+  const mgh_config c = detail::to_c(config);
+  std::vector<const void *> cp(coords.begin(), coords.end());
+  estimates.assign(tols.size(), mgh_size_estimate{});
+  return detail::status(mgh_estimate_sizes(D, (int)dtype, shape.data(), (int)tols.size(), tols.data(), s, (int)mode,
+                                           original_data, cp.empty() ? nullptr : cp.data(), &c, estimates.data()));
+}
+// EXTENSION: mgh_compress_budget. The most accurate container of at most max_bytes with a tolerance in
+// [tol_min, tol_max] (`rounds` in 1..8 rounds of the search): the container compress(tol_used) writes.
+// OutputTooLargeFailure when not even tol_max fits (nothing allocated).
+inline compress_status_type compress_budget(DIM D, data_type dtype, std::vector<SIZE> shape, size_t max_bytes,
+                                            double tol_min, double tol_max, int rounds, double s, error_bound_type mode,
+                                            const void *original_data, void *&compressed_data, size_t &compressed_size,
+                                            std::vector<const Byte *> coords, HighLevelConfig config,
+                                            bool output_pre_allocated, double &tol_used,
+                                            mgh_size_estimate *estimate_used = nullptr) {
+  if (shape.size() != D) return compress_status_type::Failure;
+  const mgh_config c = detail::to_c(config);
+  std::vector<const void *> cp(coords.begin(), coords.end());
+  return detail::status(mgh_compress_budget(D, (int)dtype, shape.data(), max_bytes, tol_min, tol_max, rounds, s, (int)mode,
+                                            original_data, &compressed_data, &compressed_size,
+                                            cp.empty() ? nullptr : cp.data(), &c, output_pre_allocated ? 1 : 0, &tol_used,
+                                            estimate_used));
+}
 // The figures of the reference's Utilities/ErrorCalculator.h (semantics: mgard_hip_errors.hpp), one pass
 // of mgh_compare on `device`; host or device pointers.
 template <typename T> double L_inf_norm(size_t n, const T *data, int device = 0) {

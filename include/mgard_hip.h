@@ -195,6 +195,23 @@ int mgh_set_ld(mgh_hierarchy *h, int which, const uint64_t *ld);
 int mgh_norm_stream_begin(mgh_hierarchy *h, void *stream);
 int mgh_norm_stream_add(mgh_hierarchy *h, const void *d_part, uint64_t count, double s, int cold,
                         void *stream);
+/* Instead of that one call: ends the accumulation and hands the norm back, converted exactly as the
+ * fused call would have converted it (so a later call that is GIVEN this norm quantizes with the same
+ * table). Synchronises the stream. */
+int mgh_norm_stream_end(mgh_hierarchy *h, double s, double *h_norm_out, void *stream);
+
+/* Histograms of the symbols mgh_quantize(..., prep_huffman = 1) would store, for `ntol` (1..64)
+ * tolerances at once, from ONE coefficient array (what mgh_decompose wrote; MGH_LD_IN applies as in
+ * mgh_quantize): d_freq[k * dict_size + q] counts the elements whose symbol at tols[k] is q, outliers
+ * counted in bin 0 (the quantizer stores 0 for them) and in d_outliers[k]. Both device arrays are
+ * zeroed by the call. The level quantizers of every tolerance are the ones mgh_quantize builds.
+ * 32-bit counters: arrays of 2^32 elements and more are refused (MGH_ERR_INVALID_ARGUMENT), as are
+ * dict_size outside 2..16384. ASYNCHRONOUS behind the upload of the quantizer tables. No reference
+ * counterpart. */
+int mgh_quantize_histograms(mgh_hierarchy *h, const void *d_coeff, int error_bound_type, int ntol,
+                            const double *tols, double s, double norm, uint64_t dict_size,
+                            uint32_t *d_freq /* [ntol][dict_size] */, uint64_t *d_outliers /* [ntol] */,
+                            void *stream);
 
 /* Norm that stays on the device: writes one value of the hierarchy's dtype to
  * d_norm_out (max|x| for s = +inf, else the L2 norm of this array as

@@ -86,6 +86,45 @@ int mgh_compress(int D, int dtype, const uint64_t *shape, double tol, double s,
                  size_t *compressed_size, const void *const *coords, const mgh_config *config,
                  int output_pre_allocated);
 
+/* ---- Sizes before compressing, and compression to a byte budget (extensions) -----------------------
+ * What mgh_compress(tol) WOULD write, for `ntol` (1..64) tolerances, from one decomposition and one
+ * read of the coefficients per launch of up to eight tolerances: the Huffman code is built from a
+ * histogram and the record's layout is a formula, so a container's size follows from the histogram of
+ * its symbols and its outlier count -- up to the padding of every Huffman chunk to a 64-bit unit,
+ * which the histogram does not know. Hence a bracket, bytes_min <= size <= bytes_max, at most 8 bytes
+ * per chunk (huff_block_size symbols) wide. code_bits: the bits of the Huffman codes; outliers: the
+ * record's count; raw: 1 the writer will store the array itself (the record would not be smaller), 0 it
+ * will not, -1 the bracket straddles that threshold.
+ * Contract: containers of ONE subdomain (a configuration that decomposes the domain is
+ * MGH_ERR_INVALID_ARGUMENT) and lossless = MGH_LOSSLESS_HUFFMAN (a Zstd frame's size is no function
+ * of the histogram: MGH_ERR_INVALID_ARGUMENT). Host or device input, coords and config as in
+ * mgh_compress. A REL bound with s != inf inherits the order dependence of the norm's last bits
+ * (mgh_norm_stream_*): the estimate uses the reduction mgh_compress uses. */
+typedef struct mgh_size_estimate {
+  double tol;
+  uint64_t bytes_min, bytes_max, outliers, code_bits;
+  int raw;
+} mgh_size_estimate;
+int mgh_estimate_sizes(int D, int dtype, const uint64_t *shape, int ntol, const double *tols, double s,
+                       int error_bound_type, const void *original_data, const void *const *coords,
+                       const mgh_config *config, mgh_size_estimate *out /* [ntol] */);
+
+/* The most accurate container of at most max_bytes: searches [tol_min, tol_max] on a logarithmic
+ * grid (tol_min if it fits; else `rounds` in 1..8 rounds of three candidates, which narrow the
+ * bracket to (tol_max / tol_min)^(1 / 4^rounds)), pricing candidates as mgh_estimate_sizes does -- a
+ * candidate fits when its bytes_max does, so the result fits by construction --, then calls
+ * mgh_compress with *tol_used: the container is the one mgh_compress(*tol_used) writes.
+ * estimate_used (may be NULL): the estimate of *tol_used. The search is double-precision arithmetic
+ * on the tolerances alone and reproducible bit for bit. MGH_ERR_OUTPUT_TOO_LARGE when not even
+ * tol_max fits: nothing is allocated and *compressed_data is left as it was. tol_min <= 0,
+ * tol_min > tol_max, rounds outside 1..8: MGH_ERR_INVALID_ARGUMENT. With output_pre_allocated,
+ * *compressed_size carries the capacity in as in mgh_compress (max_bytes is the budget either way). */
+int mgh_compress_budget(int D, int dtype, const uint64_t *shape, size_t max_bytes, double tol_min, double tol_max,
+                        int rounds, double s, int error_bound_type, const void *original_data,
+                        void **compressed_data, size_t *compressed_size, const void *const *coords,
+                        const mgh_config *config, int output_pre_allocated, double *tol_used,
+                        mgh_size_estimate *estimate_used /* may be NULL */);
+
 /* mgard_x::decompress. Shape and type come from the header (query them first with
  * mgh_infer_shape / mgh_infer_data_type to pre-allocate). */
 int mgh_decompress(const void *compressed_data, size_t compressed_size,

@@ -28,6 +28,7 @@ SYMBOLS = [
     "mgh_dequantize_recompose_sym16", "mgh_sym16_supported",
     "mgh_profile_enable", "mgh_profile_filter", "mgh_profile_read", "mgh_stream_calibrate",
     "mgh_level_linearize", "mgh_outlier_restore", "mgh_norm_stream_begin", "mgh_norm_stream_add",
+    "mgh_norm_stream_end", "mgh_quantize_histograms",
     "mgh_set_ld",
     "mgh_recompose_to_level", "mgh_dequantize_recompose_to_level",
     "mgh_dequantize_recompose_sym16_to_level", "mgh_level_nodes",
@@ -119,6 +120,9 @@ def load_library():
     L.mgh_norm_stream_begin.argtypes = [vp, vp]
     L.mgh_set_ld.argtypes = [vp, C.c_int, u64p]
     L.mgh_norm_stream_add.argtypes = [vp, vp, u64, C.c_double, C.c_int, vp]
+    L.mgh_norm_stream_end.argtypes = [vp, C.c_double, C.POINTER(C.c_double), vp]
+    L.mgh_quantize_histograms.argtypes = [vp, vp, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_double, C.c_double,
+                                          u64, vp, vp, vp]
     L.mgh_dequantize_recompose_sym16.argtypes = [vp, vp, C.c_int, C.c_double, C.c_double, C.c_double, u64,
                                                  vp, vp, u64, vp, vp]
     L.mgh_sym16_supported.argtypes = [vp]
@@ -462,6 +466,27 @@ class Hierarchy:
             _check(L.mgh_norm_stream_add(self._h, C.c_void_p(flat.data_ptr() + off * flat.element_size()),
                                          int(cnt), s, int(k + 1 < len(parts)), _stream()))
             off += cnt
+
+    def norm_stream_end(self, s):
+        """mgh_norm_stream_end: the norm accumulated by norm_stream(), instead of the fused call that
+        would have taken it."""
+        out = C.c_double()
+        _check(load_library().mgh_norm_stream_end(self._h, s, C.byref(out), _stream()))
+        return out.value
+
+    def quantize_histograms(self, coeff, tols, ebtype, s, norm, dict_size=8192):
+        """mgh_quantize_histograms: (freq int32 tensor [len(tols), dict_size], outliers int64 tensor
+        [len(tols)]) -- per tolerance the histogram of the symbols quantize(prep_huffman=True) would
+        store (outliers in bin 0) and its outlier count, from one read of `coeff`."""
+        import torch
+        tols = [float(t) for t in tols]
+        k = len(tols)
+        freq = torch.empty((k, int(dict_size)), dtype=torch.int32, device=coeff.device)
+        outl = torch.empty(k, dtype=torch.int64, device=coeff.device)
+        _check(load_library().mgh_quantize_histograms(
+            self._h, self._chk(coeff), ebtype, k, (C.c_double * k)(*tols), s, norm, int(dict_size),
+            C.c_void_p(freq.data_ptr()), C.c_void_p(outl.data_ptr()), _stream()))
+        return freq, outl
 
     def decompose_quantize_sym16(self, data, ebtype, tol, s, norm=0.0, dict_size=8192, outlier_cap=None):
         """mgh_decompose_quantize_sym16: (symbols uint16, outlier_idx, outlier_val, count, norm)."""

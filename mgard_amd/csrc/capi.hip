@@ -45,6 +45,8 @@
 #include "prolong_window_plan.hpp"
 #include "compare_plan.hpp"
 #include "kernels_compare.hpp"
+#include "size_plan.hpp"
+#include "kernels_qhist.hpp"
 
 namespace {
 
@@ -195,6 +197,8 @@ template <typename T> struct DeviceState {
   T *win_full = nullptr;
   size_t win_full_elems = 0;
   T *qz = nullptr;                 // 2*(L+1): quantizers, volumes
+  T *qh_tab = nullptr;             // mgh_quantize_histograms: [ntol][L+1] quantizers, [L+1] volumes (grown on demand)
+  size_t qh_tab_elems = 0;
   unsigned long long *scalar = nullptr;  // 8-byte device scalar (norm / counters)
   // fused device-norm path: fscal[slot] is zero on entry, the other slot is zeroed by
   // k_make_qparams for the next call; `fscal_dirty` marks a call that died in between
@@ -472,6 +476,7 @@ template <typename T> void destroy_state(mgh_hierarchy *h) {
     (void)hipFree(ds->load4);
     (void)hipFree(ds->corr4);
     (void)hipFree(ds->qz);
+    (void)hipFree(ds->qh_tab);
     (void)hipFree(ds->scalar);
     (void)hipFree(ds->fscal);
     (void)hipFree(ds->normval);
@@ -2899,6 +2904,57 @@ int dequantize_impl(mgh_hierarchy *h, int64_t *q, const QuantSpec &qs, T *coeff,
   return o.finish(h, st);
 }
 
+// mgh_quantize_histograms: the tables of every tolerance as upload_quantizers makes the one of
+// mgh_quantize (the volumes depend on s only), then the launches size_plan.hpp splits the tolerances into.
+template <typename T, int K>
+int qhist_launch(mgh_hierarchy *h, const QuantMeta &qm, const T *coeff, const T *qz, const T *vol, uint64_t dict,
+                 uint32_t *freq, uint64_t *outliers, hipStream_t st) {
+  static std::atomic<uint64_t> once{0};
+  const size_t lds = (size_t)K * dict * 4;
+  TRY(allow_big_lds_once(k_quantize_histograms<T, K>, once, kQhistLdsBytes));
+  // few persistent workgroups: as many per CU as its LDS holds beside the static tables, four at most
+  const size_t per_cu = std::max<size_t>(1, std::min<size_t>(4, kLdsPerCU / (lds + 4096)));
+  const size_t total = h->total, per_wg = (size_t)kQhThreads * Vec16<T>::N;
+  const unsigned grid = (unsigned)std::min<size_t>((total + per_wg - 1) / per_wg, per_cu * h->num_cu);
+  return launch(h, "quantize_histograms", st, [&] {
+    k_quantize_histograms<T, K><<<grid, kQhThreads, lds, st>>>(qm, total, coeff, DS<T>(h)->marks, qz, vol, h->L + 1,
+                                                              (int)dict, freq, (unsigned long long *)outliers);
+  });
+}
+
+template <typename T>
+int quantize_histograms_impl(mgh_hierarchy *h, const T *coeff, Layout in, int ebtype, int ntol, const double *tols,
+                             double s, double norm, uint64_t dict, uint32_t *freq, uint64_t *outliers, hipStream_t st) {
+  auto *ds = DS<T>(h);
+  auto *hh = HH<T>(h);
+  const int nlev = h->L + 1;
+  if (nlev > kMaxLevels) return fail(MGH_ERR_INVALID_ARGUMENT, "too many levels");
+  TRY(ld_pack<T>(h, coeff, in, false, st));
+  std::vector<T> tab((size_t)(ntol + 1) * nlev);
+  for (int k = 0; k < ntol; k++) hh->quantizers(ebtype, (T)tols[k], (T)s, (T)norm, true, tab.data() + (size_t)k * nlev);
+  const bool calc_vol = !((T)s == std::numeric_limits<T>::infinity());
+  for (int l = 0; l < nlev; l++) tab[(size_t)ntol * nlev + l] = calc_vol ? hh->level_volume(l, false) : (T)1;
+  TRY(grow(h, &ds->qh_tab, &ds->qh_tab_elems, tab.size()));
+  // pageable-memory async copies are staged by the runtime before returning
+  HIP_TRY(hipMemcpyAsync(ds->qh_tab, tab.data(), tab.size() * sizeof(T), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  HIP_TRY(hipMemsetAsync(freq, 0, (size_t)ntol * dict * sizeof(uint32_t), st));
+  HIP_TRY(hipMemsetAsync(outliers, 0, (size_t)ntol * sizeof(uint64_t), st));
+  QuantMeta qm = ds->qmeta;
+  qm.calc_vol = calc_vol ? 1 : 0;
+  const T *vol = ds->qh_tab + (size_t)ntol * nlev;
+  for (int k0 = 0; k0 < ntol;) {
+    const int kk = qhist_per_launch(dict, ntol - k0);
+    if (kk < 1) return fail(MGH_ERR_INVALID_ARGUMENT, "quantize_histograms: dict_size");
+    TRY((with_value<1, 2, 3, 4, 5, 6, 7, 8>(kk, [&](auto K) {
+      return qhist_launch<T, decltype(K)::value>(h, qm, coeff, ds->qh_tab + (size_t)k0 * nlev, vol, dict,
+                                                 freq + (size_t)k0 * dict, outliers + k0, st);
+    })));
+    k0 += kk;
+  }
+  return MGH_SUCCESS;
+}
+
 // The norm k_make_qparams left in ds->normval, on the host: one synchronisation.
 template <typename T> int read_back_norm(mgh_hierarchy *h, double *out, hipStream_t st) {
   T nv = 0;
@@ -3178,6 +3234,22 @@ int norm_stream_add(mgh_hierarchy *h, const T *part, size_t count, double s, int
   if ((T)s == std::numeric_limits<T>::infinity())
     return launch(h, "absmax", st, [&] { k_absmax<T><<<grid, 256, 0, st>>>(part, count, slot, cold ? count : 0); });
   return launch(h, "sqsum", st, [&] { k_sqsum<T><<<grid, 256, 0, st>>>(part, count, (double *)slot, cold ? count : 0); });
+}
+
+// mgh_norm_stream_end: the accumulated reduction through k_make_qparams -- the conversion the fused
+// call would have run -- and back to the host; the slots are left as that call leaves them.
+template <typename T> int norm_stream_end(mgh_hierarchy *h, double s, double *out, hipStream_t st) {
+  auto *ds = DS<T>(h);
+  if (!ds->norm_streamed) return fail(MGH_ERR_INVALID_ARGUMENT, "mgh_norm_stream_end without mgh_norm_stream_begin");
+  ds->norm_streamed = false;
+  QParamArgs<T> P;
+  TRY(fill_qparam_args<T>(h, nullptr, MGH_ABS, 1.0, s, 0, 1, nullptr, P));
+  P.scalar = ds->fscal + ds->scalar_slot;
+  P.zero_next = ds->fscal + (1 - ds->scalar_slot);
+  TRY(launch(h, "make_qparams", st, [&] { k_make_qparams<T><<<1, 64, 0, st>>>(P); }));
+  ds->scalar_slot = 1 - ds->scalar_slot;
+  ds->fscal_dirty = false;
+  return read_back_norm<T>(h, out, st);
 }
 
 // The switches as set in the environment (validated by env_validate) on a device of `num_cu` CUs.
@@ -3537,6 +3609,25 @@ int mgh_norm_stream_add(mgh_hierarchy *h, const void *d_part, uint64_t count, do
   return with_type(h, [&](auto t) {
     using T = decltype(t);
     return norm_stream_add<T>(h, (const T *)d_part, count, s, cold, (hipStream_t)stream);
+  });
+}
+
+int mgh_norm_stream_end(mgh_hierarchy *h, double s, double *h_norm_out, void *stream) {
+  if (!h || !h_norm_out) return fail(MGH_ERR_INVALID_ARGUMENT, "null argument");
+  HIP_TRY(hipSetDevice(h->device));
+  return with_type(h, [&](auto t) { return norm_stream_end<decltype(t)>(h, s, h_norm_out, (hipStream_t)stream); });
+}
+
+int mgh_quantize_histograms(mgh_hierarchy *h, const void *d_coeff, int error_bound_type, int ntol, const double *tols,
+                            double s, double norm, uint64_t dict_size, uint32_t *d_freq, uint64_t *d_outliers,
+                            void *stream) {
+  if (!h || !d_coeff || !tols || !d_freq || !d_outliers) return fail(MGH_ERR_INVALID_ARGUMENT, "null argument");
+  if (const char *bad = qhist_refusal(h->total, ntol, dict_size)) return fail(MGH_ERR_INVALID_ARGUMENT, bad);
+  HIP_TRY(hipSetDevice(h->device));
+  return with_type(h, [&](auto t) {
+    using T = decltype(t);
+    return quantize_histograms_impl<T>(h, (const T *)d_coeff, caller_layout(h, MGH_LD_IN), error_bound_type, ntol, tols,
+                                       s, norm, dict_size, d_freq, d_outliers, (hipStream_t)stream);
   });
 }
 

@@ -39,6 +39,7 @@
 #include "hierarchy.hpp"
 #include "compare_plan.hpp"
 #include "domain_plan.hpp"
+#include "size_plan.hpp"
 
 extern "C" void mgh_set_last_error_(const char *msg);  // capi.hip
 // (capi.hip: the reduction of mgh_compare on two device arrays given by element strides, asynchronous)
@@ -584,17 +585,11 @@ int lossless_finish(mgh_lossless_ctx *c, const LosslessJob &J, hipStream_t st, u
     std::memcpy(pinp + o_code, cb.code.data(), dict * 8);
     HL_HIP(hipMemcpyAsync(c->code.p, pinp + o_code, dict * 8, hipMemcpyHostToDevice, st));
   }
-  // Synchronisation points for the decoder behind the record (PayloadLayout): with the single-pass
-  // encoder, chunks of the size it keeps in registers, and streams of 4 bits per symbol or more
-  // -- 256 bytes per chunk are 1.1 % of a chunk of 20 480 nine-bit codes, and the short codes of
-  // a low-entropy stream re-synchronise within a symbol or two anyway. MGH_HUFF_SYNC=0: never.
-  c->use_sync = false;
+  // Synchronisation points for the decoder behind the record (PayloadLayout): when, is
+  // record_has_sync (size_plan.hpp, which prices a record from its histogram). MGH_HUFF_SYNC=0: never.
   c->n_chunks = nchunk;
-  if (lossless == MGH_LOSSLESS_HUFFMAN && lossless_sym16_ok(dict, chunk) && chunk >= 1024 &&
-      chunk <= (uint64_t)huff::kEncRun * huff::kEncThreads && env_get("MGH_HUFF_SYNC", 1) != 0) {
-    c->use_sync = cb.total_bits >= 4 * n;
-    if (c->use_sync) HL_TRY(c->sync.ensure(PayloadLayout::sync_bytes(nchunk)));
-  }
+  c->use_sync = record_has_sync(lossless, dict, chunk, cb.total_bits, n, env_get("MGH_HUFF_SYNC", 1));
+  if (c->use_sync) HL_TRY(c->sync.ensure(PayloadLayout::sync_bytes(nchunk)));
   const size_t sync_bytes = c->use_sync ? PayloadLayout::sync_bytes(nchunk) : 0;
   // ---- serialize (Huffman.hpp:163-239): the small leading part on the host, the code units
   // and the outlier lists stay where they are until record_write() ----
@@ -2746,6 +2741,141 @@ int check_config(const mgh_config *cfg) {
   return MGH_SUCCESS;
 }
 
+// ---- sizes from histograms: mgh_estimate_sizes, mgh_compress_budget (size_plan.hpp) ---------------
+// One array decomposed once, its coefficients kept on the device (lane 0's integer buffer, free
+// between calls) while tolerances are priced against them.
+struct SizeEstimator {
+  int D = 0, dtype = 0, ebtype = 0;
+  double s = 0, norm = 1;
+  uint64_t n = 0;
+  size_t elem = 0;
+  mgh_config cfg{};
+  Decomposer dd;
+  std::vector<std::vector<double>> coords;
+  const std::vector<std::vector<double>> *cptr = nullptr;
+  mgh_hierarchy *h = nullptr;
+  bool owned = false;
+  std::vector<uint32_t> freq;
+  std::vector<uint64_t> outl;
+  huff::Codebook cb;
+  ~SizeEstimator() {
+    if (h && owned) mgh_hierarchy_destroy(h);
+  }
+
+  int fail_drained(int rc) {
+    (void)hipStreamSynchronize(g_cache.lane[0].st);
+    (void)hipStreamSynchronize(g_cache.copy_st);
+    return rc;
+  }
+
+  // upload (host input), norm of a REL bound with the reduction compress_impl will use, decomposition
+  int begin(int D_, int dtype_, const uint64_t *shape, double s_, int ebtype_, const void *original,
+            const void *const *coords_in, const mgh_config &cfg_) {
+    D = D_, dtype = dtype_, ebtype = ebtype_, s = s_, cfg = cfg_;
+    elem = dtype == MGH_FLOAT ? 4 : 8;
+    if (cfg.lossless != MGH_LOSSLESS_HUFFMAN)
+      return hl_fail(MGH_ERR_INVALID_ARGUMENT, "size estimates: lossless must be Huffman (a Zstd frame's size is no function of the histogram)");
+    HL_TRY(cache_prepare(cfg.dev_id));
+    HL_TRY(trim_hierarchy_cache());
+    HL_TRY(make_decomposer(dd, D, shape, elem, cfg));
+    if (dd.decomposed || dd.num != 1)
+      return hl_fail(MGH_ERR_INVALID_ARGUMENT, "size estimates: the configuration decomposes the domain (containers of one subdomain only)");
+    n = 1;
+    for (int d = 0; d < D; d++) n *= shape[d];
+    if (coords_in) {
+      coords.resize(D);
+      for (int d = 0; d < D; d++) {
+        if (dtype == MGH_FLOAT) coords[d].assign((const float *)coords_in[d], (const float *)coords_in[d] + shape[d]);
+        else coords[d].assign((const double *)coords_in[d], (const double *)coords_in[d] + shape[d]);
+      }
+      cptr = &coords;
+    }
+    HL_TRY(get_hierarchy(&h, &owned, dtype, dd.subdomain_shape(0), cptr, dd.subdomain_offset(0), cfg, 0));
+    Lane &L = g_cache.lane[0];
+    hipStream_t st = L.st;
+    const size_t bytes = n * elem;
+    const void *d_in = original;
+    bool have_norm = ebtype != MGH_REL;
+    if (!is_device_pointer(original)) {
+      HL_TRY(g_cache.in[0].ensure(bytes));
+      d_in = g_cache.in[0].p;
+      int rc;
+      if (ebtype == MGH_REL && env_get("MGH_HL_STREAM_NORM", 1) != 0 && mgh_sym16_supported(h)) {
+        // (compress_impl reduces the norm of such an input piece by piece while it arrives: the same
+        // pieces here, so that a sum of squares has the same partial sums)
+        if ((rc = mgh_norm_stream_begin(h, st)) != MGH_SUCCESS) return fail_drained(rc);
+        const size_t warm = (size_t)192 << 20;
+        mgh_hierarchy *const hh = h;
+        const double sd = s;
+        const size_t el = elem;
+        const ChunkFn on_piece = [&, hh, st, sd, el](size_t off, size_t nb, hipEvent_t landed) -> int {
+          HL_HIP(hipStreamWaitEvent(st, landed, 0));
+          return mgh_norm_stream_add(hh, (const char *)g_cache.in[0].p + off, nb / el, sd, off + nb + warm < bytes ? 1 : 0, st);
+        };
+        if ((rc = copy_any(g_cache.in[0].p, original, bytes, g_cache.copy_st, &on_piece)) != MGH_SUCCESS) return fail_drained(rc);
+        have_norm = true;
+      } else if ((rc = copy_any(g_cache.in[0].p, original, bytes, g_cache.copy_st)) != MGH_SUCCESS) {
+        return fail_drained(rc);
+      }
+      if (hipEventRecord(g_cache.in_ready[0], g_cache.copy_st) != hipSuccess ||
+          hipStreamWaitEvent(st, g_cache.in_ready[0], 0) != hipSuccess)
+        return fail_drained(hl_fail(MGH_ERR_DEVICE, "hipEventRecord"));
+      if (have_norm && ebtype == MGH_REL && (rc = mgh_norm_stream_end(h, s, &norm, st)) != MGH_SUCCESS) return fail_drained(rc);
+    }
+    int rc;
+    if (!have_norm && (rc = mgh_norm(h, d_in, s, &norm, st)) != MGH_SUCCESS) return fail_drained(rc);
+    if ((rc = L.q.ensure(std::max<size_t>(bytes, n * 8))) != MGH_SUCCESS) return fail_drained(rc);
+    if ((rc = mgh_decompose(h, d_in, L.q.p, st)) != MGH_SUCCESS) return fail_drained(rc);
+    return MGH_SUCCESS;
+  }
+
+  // one histogram pass per launch group, the codes on the host, the brackets
+  int price(int ntol, const double *tols, mgh_size_estimate *out) {
+    Lane &L = g_cache.lane[0];
+    hipStream_t st = L.st;
+    const uint64_t dict = cfg.huff_dict_size, chunk = cfg.huff_block_size;
+    const size_t fbytes = (size_t)ntol * dict * 4, o_outl = (fbytes + 7) / 8 * 8;
+    HL_TRY(L.q2.ensure(o_outl + (size_t)ntol * 8));
+    uint32_t *d_freq = (uint32_t *)L.q2.p;
+    uint64_t *d_outl = (uint64_t *)((char *)L.q2.p + o_outl);
+    int rc = mgh_quantize_histograms(h, L.q.p, ebtype, ntol, tols, s, norm, dict, d_freq, d_outl, st);
+    if (rc != MGH_SUCCESS) return fail_drained(rc);
+    freq.resize((size_t)ntol * dict);
+    outl.resize(ntol);
+    if (hipMemcpyAsync(freq.data(), d_freq, fbytes, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipMemcpyAsync(outl.data(), d_outl, (size_t)ntol * 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess)
+      return fail_drained(hl_fail(MGH_ERR_DEVICE, "size estimates: reading the histograms back"));
+    const long sync_env = env_get("MGH_HUFF_SYNC", 1);
+    for (int k = 0; k < ntol; k++) {
+      try {
+        huff::build_codebook(freq.data() + (size_t)k * dict, (int)dict, cb);
+      } catch (const std::exception &e) {
+        return hl_fail(MGH_ERR_INVALID_ARGUMENT, e.what());
+      }
+      const bool with_sync = record_has_sync(cfg.lossless, dict, chunk, cb.total_bits, n, sync_env);
+      const ByteBracket rb = record_bytes_bracket(n, dict, chunk, cb.total_bits, outl[k], with_sync);
+      fmt::Header hdr;
+      header_from(dd, dtype, ebtype, tols[k], s, ebtype == MGH_REL ? norm : 0.0, cptr, cfg, hdr);
+      const ContainerBracket c = container_bytes_bracket(fmt::serialize_metadata(hdr).size(), n, elem, rb);
+      out[k] = mgh_size_estimate{tols[k], c.min, c.max, outl[k], cb.total_bits, c.raw};
+    }
+    return MGH_SUCCESS;
+  }
+};
+
+int size_call_args(int D, int dtype, const uint64_t *shape, int ebtype, const void *original, const mgh_config *config) {
+  if (!shape || !original) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (D < 1 || D > MGH_MAX_DIM) return hl_fail(MGH_ERR_UNSUPPORTED_DIMENSION, "D must be 1..5");
+  if (dtype != MGH_FLOAT && dtype != MGH_DOUBLE) return hl_fail(MGH_ERR_UNSUPPORTED_DTYPE, "dtype");
+  if (ebtype != MGH_REL && ebtype != MGH_ABS) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "error_bound_type");
+  const std::string bad = env_validate();  // MGH_* developer switches: a typo is an error
+  if (!bad.empty()) return hl_fail(MGH_ERR_INVALID_ARGUMENT, bad);
+  HL_TRY(check_config(config));
+  if (hipSetDevice(config->dev_id) != hipSuccess) return hl_fail(MGH_ERR_DEVICE, "hipSetDevice");
+  return MGH_SUCCESS;
+}
+
 } // namespace
 
 extern "C" {
@@ -2801,6 +2931,77 @@ int mgh_compress(int D, int dtype, const uint64_t *shape, double tol, double s, 
   } catch (const std::exception &e) {
     return hl_fail(MGH_ERR_DEVICE, e.what());
   }
+}
+
+int mgh_estimate_sizes(int D, int dtype, const uint64_t *shape, int ntol, const double *tols, double s, int ebtype,
+                       const void *original_data, const void *const *coords, const mgh_config *config,
+                       mgh_size_estimate *out) {
+  if (!tols || !out) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (ntol < 1 || ntol > kQhistMaxTols) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "ntol must be in 1..64");
+  HL_TRY(size_call_args(D, dtype, shape, ebtype, original_data, config));
+  try {
+    SizeEstimator E;
+    HL_TRY(E.begin(D, dtype, shape, s, ebtype, original_data, coords, *config));
+    return E.price(ntol, tols, out);
+  } catch (const std::exception &e) {
+    return hl_fail(MGH_ERR_DEVICE, e.what());
+  }
+}
+
+int mgh_compress_budget(int D, int dtype, const uint64_t *shape, size_t max_bytes, double tol_min, double tol_max,
+                        int rounds, double s, int ebtype, const void *original_data, void **compressed_data,
+                        size_t *compressed_size, const void *const *coords, const mgh_config *config,
+                        int output_pre_allocated, double *tol_used, mgh_size_estimate *estimate_used) {
+  if (!compressed_data || !compressed_size || !tol_used) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (output_pre_allocated && !*compressed_data) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "pre-allocated output is NULL");
+  if (!(tol_min > 0) || !(tol_min <= tol_max) || !std::isfinite(tol_max) || rounds < 1 || rounds > 8)
+    return hl_fail(MGH_ERR_INVALID_ARGUMENT, "compress_budget: 0 < tol_min <= tol_max (finite), rounds in 1..8");
+  HL_TRY(size_call_args(D, dtype, shape, ebtype, original_data, config));
+  mgh_size_estimate used{};
+  try {
+    SizeEstimator E;
+    HL_TRY(E.begin(D, dtype, shape, s, ebtype, original_data, coords, *config));
+    int rc = MGH_SUCCESS;
+    std::vector<mgh_size_estimate> seen;  // every candidate priced, in order
+    auto fits3 = [&](const double m[3], bool ok[3]) {
+      mgh_size_estimate e[3];
+      if (rc == MGH_SUCCESS) rc = E.price(3, m, e);
+      for (int k = 0; k < 3; k++) {
+        ok[k] = rc == MGH_SUCCESS && e[k].bytes_max <= max_bytes;
+        if (rc == MGH_SUCCESS) seen.push_back(e[k]);
+      }
+    };
+    auto fits1 = [&](double tol) {
+      mgh_size_estimate e;
+      if (rc == MGH_SUCCESS) rc = E.price(1, &tol, &e);
+      if (rc != MGH_SUCCESS) return false;
+      seen.push_back(e);
+      return e.bytes_max <= max_bytes;
+    };
+    const SearchResult r = budget_search(tol_min, tol_max, rounds, fits1, fits3);
+    HL_TRY(rc);
+    if (r.end == SearchEnd::bad_argument) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "compress_budget: tolerances or rounds");
+    if (r.end == SearchEnd::nothing_fits)
+      return hl_fail(MGH_ERR_OUTPUT_TOO_LARGE, "compress_budget: the container of tol_max is larger than max_bytes");
+    *tol_used = r.tol;
+    for (const mgh_size_estimate &e : seen)
+      if (e.tol == r.tol) used = e;
+  } catch (const std::exception &e) {
+    return hl_fail(MGH_ERR_DEVICE, e.what());
+  }
+  if (estimate_used) *estimate_used = used;
+  // the writer itself, untouched: a second decomposition (its fused pass) is the price
+  void *const given = *compressed_data;
+  HL_TRY(mgh_compress(D, dtype, shape, *tol_used, s, ebtype, original_data, compressed_data, compressed_size, coords,
+                      config, output_pre_allocated));
+  if (*compressed_size > max_bytes) {  // (the bracket is an invariant of the record's layout: never expected)
+    if (!output_pre_allocated) {
+      if (is_device_pointer(*compressed_data)) (void)hipFree(*compressed_data); else std::free(*compressed_data);
+      *compressed_data = given;
+    }
+    return hl_fail(MGH_ERR_FORMAT, "compress_budget: the container left the estimate's bracket");
+  }
+  return MGH_SUCCESS;
 }
 
 static int decompress_entry(const void *compressed_data, size_t compressed_size, void **decompressed_data,

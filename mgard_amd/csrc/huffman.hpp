@@ -375,8 +375,7 @@ k_encode(const int64_t *__restrict__ q, size_t n, int chunk, const uint64_t *__r
   if (room != kUnitBits) flush(true);
 }
 
-constexpr int kEncRun = 40;      // symbols per thread the single-pass encoder keeps in registers (default chunk: 20480 = 40 x 512)
-constexpr int kEncThreads = 512;  // threads of an encoder workgroup (two workgroups per CU with 32-bit code entries)
+// (kEncRun, kEncThreads: huffman_record.hpp)
 
 
 // One pass over the symbols instead of two (k_chunk_bits + k_encode): the unit offset of a

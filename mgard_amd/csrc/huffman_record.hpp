@@ -20,6 +20,8 @@ namespace huff {
 constexpr int kSyncLanes = 64;  // synchronisation points per chunk = lanes of the decoder's wave
 constexpr int kParWaves = 16;
 constexpr int kParBatch = 32;  // symbols a lane decodes between two write-outs
+constexpr int kEncRun = 40;      // symbols per thread the single-pass encoder keeps in registers (default chunk: 20480 = 40 x 512)
+constexpr int kEncThreads = 512;  // threads of an encoder workgroup (two workgroups per CU with 32-bit code entries)
 } // namespace huff
 
 // ---- offsets with natural alignment (Huffman.hpp:163-239) ---------------------------------------

@@ -32,6 +32,7 @@ HL_SYMBOLS = [
     "mgh_decompress_preview", "mgh_progressive_preview",
     "mgh_decompress_preview_window", "mgh_progressive_preview_window",
     "mgh_verify",
+    "mgh_estimate_sizes", "mgh_compress_budget",
 ]
 
 
@@ -89,6 +90,17 @@ class VerifyResult(C.Structure):
             self.stats, self.bound_kind, self.bound, self.achieved, self.within)
 
 
+class SizeEstimate(C.Structure):
+    """mgh_size_estimate: bytes_min <= len(compress(data, tol)) <= bytes_max; raw 1 / 0 / -1 (the
+    bracket straddles the threshold at which the writer stores the array itself)."""
+    _fields_ = [("tol", C.c_double), ("bytes_min", C.c_uint64), ("bytes_max", C.c_uint64), ("outliers", C.c_uint64),
+                ("code_bits", C.c_uint64), ("raw", C.c_int)]
+
+    def __repr__(self):
+        return "SizeEstimate(tol=%r, bytes_min=%d, bytes_max=%d, outliers=%d, code_bits=%d, raw=%d)" % (
+            self.tol, self.bytes_min, self.bytes_max, self.outliers, self.code_bits, self.raw)
+
+
 class HeaderInfo(C.Structure):
     """mgh_header_info."""
     _fields_ = [
@@ -140,6 +152,11 @@ def _hl():
     L.mgh_decompress_preview_window.argtypes = [vp, C.c_size_t, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
                                                 C.POINTER(vp), vp, C.c_int]
     L.mgh_verify.argtypes = [vp, C.c_size_t, vp, C.c_size_t, C.c_int, C.c_int, vp, C.POINTER(VerifyResult)]
+    L.mgh_estimate_sizes.argtypes = [C.c_int, C.c_int, C.POINTER(u64), C.c_int, C.POINTER(C.c_double), C.c_double,
+                                     C.c_int, vp, C.POINTER(vp), C.POINTER(Config), C.POINTER(SizeEstimate)]
+    L.mgh_compress_budget.argtypes = [C.c_int, C.c_int, C.POINTER(u64), C.c_size_t, C.c_double, C.c_double, C.c_int,
+                                      C.c_double, C.c_int, vp, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(vp),
+                                      C.POINTER(Config), C.c_int, C.POINTER(C.c_double), C.POINTER(SizeEstimate)]
     L.mgh_dist_use_library.argtypes = [C.c_char_p]
     L.mgh_compress_dist.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(u64), C.c_double,
                                     C.c_double, C.c_int, vp, C.POINTER(vp), C.POINTER(C.c_size_t), vp, vp, C.c_int]
@@ -307,6 +324,64 @@ def compress(data, tol, s=INF, mode=REL, coords=None, config=None, out_capacity=
     _check(L.mgh_compress(D, dt, shp, float(tol), float(s), int(mode), ptr, C.byref(optr), C.byref(size),
                           cptr, C.byref(cfg), 1))
     return out[:size.value]
+
+
+def _coords_ptr(coords, dt, D):
+    """(void*[D] of host arrays of the data type or None, keepalive)"""
+    if coords is None:
+        return None, []
+    npdt = np.float32 if dt == FLOAT else np.float64
+    arr = (C.c_void_p * D)()
+    keep = []
+    for d in range(D):
+        c = np.ascontiguousarray(coords[d], dtype=npdt)
+        keep.append(c)
+        arr[d] = c.ctypes.data
+    return arr, keep
+
+
+def estimate_sizes(data, tols, s=INF, mode=REL, coords=None, config=None):
+    """mgh_estimate_sizes: one SizeEstimate per tolerance (1..64 of them) of what compress(data, tol, ...)
+    would write, from one decomposition. Containers of one subdomain, Huffman only."""
+    L = _hl()
+    cfg = config if config is not None else Config()
+    ptr, dt, shape, keep = _as_ptr(data)
+    D = len(shape)
+    tols = [float(t) for t in tols]
+    k = len(tols)
+    cptr, ckeep = _coords_ptr(coords, dt, D)
+    out = (SizeEstimate * max(k, 1))()
+    _check(L.mgh_estimate_sizes(D, dt, (C.c_uint64 * D)(*shape), k, (C.c_double * max(k, 1))(*tols), float(s), int(mode),
+                                ptr, cptr, C.byref(cfg), out))
+    return list(out)[:k]
+
+
+def compress_budget(data, max_bytes, tol_min, tol_max, rounds=4, s=INF, mode=REL, coords=None, config=None):
+    """mgh_compress_budget: the most accurate container of at most max_bytes, searching
+    [tol_min, tol_max]. Returns (buf, tol_used, estimate): buf is compress(data, tol_used, ...) -- a numpy
+    uint8 array (host input) or a cuda uint8 tensor (device input). Raises (MGH_ERR_OUTPUT_TOO_LARGE) when
+    not even tol_max fits."""
+    import torch
+    L = _hl()
+    cfg = config if config is not None else Config()
+    ptr, dt, shape, keep = _as_ptr(data)
+    D = len(shape)
+    cptr, ckeep = _coords_ptr(coords, dt, D)
+    on_device = isinstance(data, torch.Tensor) and data.is_cuda
+    cap = int(np.prod(shape)) * (4 if dt == FLOAT else 8) + 1000000
+    if on_device:
+        out = torch.empty(cap, dtype=torch.uint8, device=data.device)
+        optr = C.c_void_p(out.data_ptr())
+    else:
+        out = np.empty(cap, dtype=np.uint8)
+        optr = C.c_void_p(out.ctypes.data)
+    size = C.c_size_t(cap)
+    used = C.c_double()
+    est = SizeEstimate()
+    _check(L.mgh_compress_budget(D, dt, (C.c_uint64 * D)(*shape), int(max_bytes), float(tol_min), float(tol_max),
+                                 int(rounds), float(s), int(mode), ptr, C.byref(optr), C.byref(size), cptr,
+                                 C.byref(cfg), 1, C.byref(used), C.byref(est)))
+    return out[:size.value], used.value, est
 
 
 def infer(buf):
