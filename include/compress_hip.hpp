@@ -212,6 +212,38 @@ inline compress_status_type compress_budget(DIM D, data_type dtype, std::vector<
                                             cp.empty() ? nullptr : cp.data(), &c, output_pre_allocated ? 1 : 0, &tol_used,
                                             estimate_used));
 }
+// EXTENSION: mgh_achieved_errors. What verify(compress(tol)) would report for every tolerance of `tols`
+// (1..64), from one decomposition and without writing a container. Containers of one subdomain (Failure
+// otherwise; mgh_last_error() says so); any supported lossless_type.
+enum class target_metric : int { MaxAbs = MGH_TARGET_MAX_ABS, RMSE = MGH_TARGET_RMSE, PSNR = MGH_TARGET_PSNR };
+inline compress_status_type achieved_errors(DIM D, data_type dtype, std::vector<SIZE> shape,
+                                            const std::vector<double> &tols, double s, error_bound_type mode,
+                                            const void *original_data, std::vector<const Byte *> coords,
+                                            HighLevelConfig config, std::vector<mgh_error_stats> &stats) {
+  if (shape.size() != D) return compress_status_type::Failure;
+  const mgh_config c = detail::to_c(config);
+  std::vector<const void *> cp(coords.begin(), coords.end());
+  stats.assign(tols.size(), mgh_error_stats{});
+  return detail::status(mgh_achieved_errors(D, (int)dtype, shape.data(), (int)tols.size(), tols.data(), s, (int)mode,
+                                            original_data, cp.empty() ? nullptr : cp.data(), &c, stats.data()));
+}
+// EXTENSION: mgh_compress_target. The container of the largest tolerance in [tol_min, tol_max] whose achieved
+// error meets `target` in `metric` (`rounds` in 1..16 bisections): the container compress(tol_used) writes.
+// Failure (MGH_ERR_TARGET_NOT_MET behind it) when not even tol_min meets the target (nothing allocated).
+inline compress_status_type compress_target(DIM D, data_type dtype, std::vector<SIZE> shape, target_metric metric,
+                                            double target, double tol_min, double tol_max, int rounds, double s,
+                                            error_bound_type mode, const void *original_data, void *&compressed_data,
+                                            size_t &compressed_size, std::vector<const Byte *> coords,
+                                            HighLevelConfig config, bool output_pre_allocated, double &tol_used,
+                                            mgh_error_stats *stats_used = nullptr, int *candidates = nullptr) {
+  if (shape.size() != D) return compress_status_type::Failure;
+  const mgh_config c = detail::to_c(config);
+  std::vector<const void *> cp(coords.begin(), coords.end());
+  return detail::status(mgh_compress_target(D, (int)dtype, shape.data(), (int)metric, target, tol_min, tol_max, rounds, s,
+                                            (int)mode, original_data, &compressed_data, &compressed_size,
+                                            cp.empty() ? nullptr : cp.data(), &c, output_pre_allocated ? 1 : 0, &tol_used,
+                                            stats_used, candidates));
+}
 // The figures of the reference's Utilities/ErrorCalculator.h (semantics: mgard_hip_errors.hpp), one pass
 // of mgh_compare on `device`; host or device pointers.
 template <typename T> double L_inf_norm(size_t n, const T *data, int device = 0) {

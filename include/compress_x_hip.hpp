@@ -108,6 +108,7 @@ inline compress_status_type status(int rc) {
   case MGH_ERR_UNSUPPORTED_DIMENSION: return compress_status_type::NotSupportHigherNumberOfDimensionsFailure;
   case MGH_ERR_UNSUPPORTED_DTYPE: return compress_status_type::NotSupportDataTypeFailure;
   case MGH_ERR_NO_DEVICE: return compress_status_type::BackendNotAvailableFailure;
+  case MGH_ERR_TARGET_NOT_MET: return compress_status_type::Failure;  // (the reference has no status for it)
   default: return compress_status_type::Failure;
   }
 }

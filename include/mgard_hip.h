@@ -213,6 +213,19 @@ int mgh_quantize_histograms(mgh_hierarchy *h, const void *d_coeff, int error_bou
                             uint32_t *d_freq /* [ntol][dict_size] */, uint64_t *d_outliers /* [ntol] */,
                             void *stream);
 
+/* What the decoder will see of ONE coefficient array at a tolerance, without the integers, the outlier
+ * lists or the lossless stage: d_coeff_out[i] is, bit for bit, what mgh_dequantize writes for the
+ * integers mgh_quantize makes from d_coeff[i] -- for either prep_huffman and any dict_size (the
+ * dictionary shift cancels in int64, and an out-of-dictionary value travels through the outlier list as
+ * the same int64, so neither is an argument). The tables are the ones those two calls build, the
+ * arithmetic is their kernels' own. MGH_LD_IN applies to d_coeff as in mgh_quantize; d_coeff_out is
+ * DENSE (MGH_LD_OUT is not honoured) and may be d_coeff (in place) when that is dense. One read and one
+ * write per element. Arrays of 2^32 elements and more are refused (MGH_ERR_INVALID_ARGUMENT; 32-bit index
+ * arithmetic, as in mgh_quantize_histograms). ASYNCHRONOUS behind the upload of the quantizer tables. No
+ * reference counterpart. */
+int mgh_quantize_roundtrip(mgh_hierarchy *h, const void *d_coeff, int error_bound_type, double tol,
+                           double s, double norm, void *d_coeff_out, void *stream);
+
 /* Norm that stays on the device: writes one value of the hierarchy's dtype to
  * d_norm_out (max|x| for s = +inf, else the L2 norm of this array as
  * norm_calculator defines it). ASYNCHRONOUS. For a decomposed domain the caller

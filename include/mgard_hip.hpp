@@ -67,6 +67,7 @@ inline compress_status_type to_status(int rc) {
     return compress_status_type::NotSupportHigherNumberOfDimensionsFailure;
   case MGH_ERR_UNSUPPORTED_DTYPE: return compress_status_type::NotSupportDataTypeFailure;
   case MGH_ERR_NO_DEVICE: return compress_status_type::BackendNotAvailableFailure;
+  // (MGH_ERR_TARGET_NOT_MET of mgard_hip_compress.h too: the reference has no status for it)
   default: return compress_status_type::Failure;
   }
 }

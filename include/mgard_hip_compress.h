@@ -38,6 +38,7 @@ extern "C" {
 
 #define MGH_ERR_OUTPUT_TOO_LARGE (-7) /* cf. compress_status_type::OutputTooLargeFailure */
 #define MGH_ERR_FORMAT (-8)           /* malformed / unsupported compressed stream */
+#define MGH_ERR_TARGET_NOT_MET (-9)   /* mgh_compress_target: not even tol_min meets the error target */
 
 typedef enum mgh_domain_decomposition { /* domain_decomposition_type, Utilities/Types.h:50 */
   MGH_DD_MAXDIM = 0,
@@ -124,6 +125,51 @@ int mgh_compress_budget(int D, int dtype, const uint64_t *shape, size_t max_byte
                         void **compressed_data, size_t *compressed_size, const void *const *coords,
                         const mgh_config *config, int output_pre_allocated, double *tol_used,
                         mgh_size_estimate *estimate_used /* may be NULL */);
+
+/* ---- Achieved errors before compressing, and compression to an error target (extensions) -----------
+ * A tolerance is a guaranteed bound, not the error a caller gets (mgh_verify exists because the two
+ * differ). mgh_achieved_errors: out[k] holds the statistics mgh_verify (halvings = 0) would report for
+ * the container mgh_compress(tols[k]) would write, for `ntol` (1..64) tolerances, from ONE
+ * decomposition and WITHOUT writing a container: per tolerance the coefficients are turned into the
+ * coefficients the decoder will see (mgh_quantize_roundtrip: one streaming pass, no integers, no
+ * outlier lists, no lossless stage), recomposed (mgh_recompose) and compared with the input by the
+ * kernel of mgh_compare. For a device-resident input every field equals mgh_verify's bit for bit; for a
+ * host-resident one the exact fields (n, nonfinite, max_abs_err, argmax, the reference's extremes) do
+ * and the two sums may round differently, as mgh_compare documents for host arrays.
+ * Contract: containers of ONE subdomain (a configuration that decomposes the domain is
+ * MGH_ERR_INVALID_ARGUMENT). The achieved error does not depend on the lossless stage: Huffman and
+ * Huffman_Zstd are both accepted, as is either reorder. Host or device input, coords and config as in
+ * mgh_compress. Device memory: the coefficient array and one more array of the input's size, both in
+ * buffers the compression pipeline owns anyway.
+ * Known limits. (1) A REL bound with finite s on float64 data inherits the order dependence of the
+ * last bits of the norm (mgh_norm_stream_*): there the candidate and the written container may differ
+ * in the last bits of their statistics. (2) Where mgh_compress stores the array itself because the
+ * record would not be smaller (a RAW record: tiny arrays, or tolerances near the resolution of the
+ * type) the container is exact, and the candidate's statistics -- the quantizer's -- are an upper bound
+ * of its error rather than equal to it. */
+typedef enum mgh_target_metric { MGH_TARGET_MAX_ABS = 0, MGH_TARGET_RMSE = 1, MGH_TARGET_PSNR = 2 } mgh_target_metric;
+int mgh_achieved_errors(int D, int dtype, const uint64_t *shape, int ntol, const double *tols, double s,
+                        int error_bound_type, const void *original_data, const void *const *coords,
+                        const mgh_config *config, mgh_error_stats *out /* [ntol] */);
+
+/* The LARGEST tolerance in [tol_min, tol_max] whose achieved error meets `target` in `metric`
+ * (max_abs_err <= target, rmse <= target, or psnr >= target; a result with non-finite positions meets
+ * nothing), on a logarithmic grid: tol_max if it meets the target (1 candidate); else tol_min must
+ * (2 candidates), and `rounds` (1..16) bisections in log, each one candidate evaluated as
+ * mgh_achieved_errors evaluates it, narrow the bracket to (tol_max / tol_min)^(1 / 2^rounds). The
+ * result meets the target BY MEASUREMENT, so an error curve that is not monotone costs compression at
+ * worst, never the target. Then mgh_compress is called with *tol_used: the container is the one
+ * mgh_compress(*tol_used) writes. stats_used (may be NULL): the statistics of the chosen candidate;
+ * candidates (may be NULL): how many were evaluated. The search is double-precision arithmetic on the
+ * tolerances alone and reproducible bit for bit. MGH_ERR_TARGET_NOT_MET when not even tol_min meets the
+ * target: nothing is allocated and *compressed_data is left as it was. metric outside 0..2, a NaN
+ * target, tol_min <= 0, tol_min > tol_max, rounds outside 1..16: MGH_ERR_INVALID_ARGUMENT. The limits
+ * of mgh_achieved_errors apply. */
+int mgh_compress_target(int D, int dtype, const uint64_t *shape, int metric, double target, double tol_min,
+                        double tol_max, int rounds, double s, int error_bound_type, const void *original_data,
+                        void **compressed_data, size_t *compressed_size, const void *const *coords,
+                        const mgh_config *config, int output_pre_allocated, double *tol_used,
+                        mgh_error_stats *stats_used /* may be NULL */, int *candidates /* may be NULL */);
 
 /* mgard_x::decompress. Shape and type come from the header (query them first with
  * mgh_infer_shape / mgh_infer_data_type to pre-allocate). */

@@ -28,7 +28,7 @@ SYMBOLS = [
     "mgh_dequantize_recompose_sym16", "mgh_sym16_supported",
     "mgh_profile_enable", "mgh_profile_filter", "mgh_profile_read", "mgh_stream_calibrate",
     "mgh_level_linearize", "mgh_outlier_restore", "mgh_norm_stream_begin", "mgh_norm_stream_add",
-    "mgh_norm_stream_end", "mgh_quantize_histograms",
+    "mgh_norm_stream_end", "mgh_quantize_histograms", "mgh_quantize_roundtrip",
     "mgh_set_ld",
     "mgh_recompose_to_level", "mgh_dequantize_recompose_to_level",
     "mgh_dequantize_recompose_sym16_to_level", "mgh_level_nodes",
@@ -123,6 +123,7 @@ def load_library():
     L.mgh_norm_stream_end.argtypes = [vp, C.c_double, C.POINTER(C.c_double), vp]
     L.mgh_quantize_histograms.argtypes = [vp, vp, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_double, C.c_double,
                                           u64, vp, vp, vp]
+    L.mgh_quantize_roundtrip.argtypes = [vp, vp, C.c_int, C.c_double, C.c_double, C.c_double, vp, vp]
     L.mgh_dequantize_recompose_sym16.argtypes = [vp, vp, C.c_int, C.c_double, C.c_double, C.c_double, u64,
                                                  vp, vp, u64, vp, vp]
     L.mgh_sym16_supported.argtypes = [vp]
@@ -487,6 +488,19 @@ class Hierarchy:
             self._h, self._chk(coeff), ebtype, k, (C.c_double * k)(*tols), s, norm, int(dict_size),
             C.c_void_p(freq.data_ptr()), C.c_void_p(outl.data_ptr()), _stream()))
         return freq, outl
+
+    def quantize_roundtrip(self, coeff, error_bound_type, tol, s, norm, out=None):
+        """mgh_quantize_roundtrip: what dequantize() gives for the integers quantize() makes from `coeff`,
+        bit for bit, in one pass and without the integers. `out`: a dense tensor of the hierarchy's shape and
+        type (LD_OUT does not apply); it may be `coeff` itself (in place)."""
+        import torch
+        if out is None:
+            out = torch.empty(self.shape, dtype=self.torch_dtype, device=coeff.device)
+        assert out.is_cuda and out.is_contiguous() and out.numel() == self.total, "bad tensor"
+        assert out.dtype == self.torch_dtype and out.device.index == self.device, "bad tensor"
+        _check(load_library().mgh_quantize_roundtrip(
+            self._h, self._chk(coeff), int(error_bound_type), tol, s, norm, C.c_void_p(out.data_ptr()), _stream()))
+        return out
 
     def decompose_quantize_sym16(self, data, ebtype, tol, s, norm=0.0, dict_size=8192, outlier_cap=None):
         """mgh_decompose_quantize_sym16: (symbols uint16, outlier_idx, outlier_val, count, norm)."""

@@ -47,6 +47,8 @@
 #include "kernels_compare.hpp"
 #include "size_plan.hpp"
 #include "kernels_qhist.hpp"
+#include "target_plan.hpp"
+#include "kernels_qround.hpp"
 
 namespace {
 
@@ -199,6 +201,8 @@ template <typename T> struct DeviceState {
   T *qz = nullptr;                 // 2*(L+1): quantizers, volumes
   T *qh_tab = nullptr;             // mgh_quantize_histograms: [ntol][L+1] quantizers, [L+1] volumes (grown on demand)
   size_t qh_tab_elems = 0;
+  T *qr_tab = nullptr;             // mgh_quantize_roundtrip: 4*(L+1): reciprocal quantizers, their volumes, quantizers, theirs
+  size_t qr_tab_elems = 0;
   unsigned long long *scalar = nullptr;  // 8-byte device scalar (norm / counters)
   // fused device-norm path: fscal[slot] is zero on entry, the other slot is zeroed by
   // k_make_qparams for the next call; `fscal_dirty` marks a call that died in between
@@ -477,6 +481,7 @@ template <typename T> void destroy_state(mgh_hierarchy *h) {
     (void)hipFree(ds->corr4);
     (void)hipFree(ds->qz);
     (void)hipFree(ds->qh_tab);
+    (void)hipFree(ds->qr_tab);
     (void)hipFree(ds->scalar);
     (void)hipFree(ds->fscal);
     (void)hipFree(ds->normval);
@@ -2955,6 +2960,40 @@ int quantize_histograms_impl(mgh_hierarchy *h, const T *coeff, Layout in, int eb
   return MGH_SUCCESS;
 }
 
+// mgh_quantize_roundtrip: the table of mgh_quantize (upload_quantizers, reciprocal) and the table of
+// mgh_dequantize (upload_quantizers, not reciprocal) side by side, made by the same host code, then one
+// streaming launch. The output is dense.
+template <typename T>
+int quantize_roundtrip_impl(mgh_hierarchy *h, const T *coeff, Layout in, const Bound &b, double norm, T *out,
+                            hipStream_t st) {
+  auto *ds = DS<T>(h);
+  auto *hh = HH<T>(h);
+  const int nlev = h->L + 1;
+  if (nlev > kMaxLevels) return fail(MGH_ERR_INVALID_ARGUMENT, "too many levels");
+  TRY(ld_pack<T>(h, coeff, in, false, st));
+  std::vector<T> tab((size_t)4 * nlev);
+  hh->quantizers(b.ebtype, (T)b.tol, (T)b.s, (T)norm, true, tab.data());
+  hh->quantizers(b.ebtype, (T)b.tol, (T)b.s, (T)norm, false, tab.data() + 2 * nlev);
+  const bool calc_vol = !((T)b.s == std::numeric_limits<T>::infinity());
+  for (int l = 0; l < nlev; l++) {
+    tab[nlev + l] = calc_vol ? hh->level_volume(l, false) : (T)1;
+    tab[3 * nlev + l] = calc_vol ? hh->level_volume(l, true) : (T)1;
+  }
+  TRY(grow(h, &ds->qr_tab, &ds->qr_tab_elems, tab.size()));
+  // pageable-memory async copies are staged by the runtime before returning
+  HIP_TRY(hipMemcpyAsync(ds->qr_tab, tab.data(), tab.size() * sizeof(T), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  QuantMeta qm = ds->qmeta;
+  qm.calc_vol = calc_vol ? 1 : 0;
+  // a pure stream: workgroups of 256 threads, one 16-byte vector per thread and trip, at most eight
+  // workgroups per compute unit, which stride over the rest
+  const size_t total = h->total, per_wg = (size_t)kQrThreads * Vec16<T>::N;
+  const unsigned grid = (unsigned)std::min<size_t>((total + per_wg - 1) / per_wg, 8 * h->num_cu);
+  return launch(h, "quantize_roundtrip", st, [&] {
+    k_quantize_roundtrip<T><<<grid, kQrThreads, 0, st>>>(qm, total, coeff, ds->marks, ds->qr_tab, nlev, out);
+  });
+}
+
 // The norm k_make_qparams left in ds->normval, on the host: one synchronisation.
 template <typename T> int read_back_norm(mgh_hierarchy *h, double *out, hipStream_t st) {
   T nv = 0;
@@ -3628,6 +3667,18 @@ int mgh_quantize_histograms(mgh_hierarchy *h, const void *d_coeff, int error_bou
     using T = decltype(t);
     return quantize_histograms_impl<T>(h, (const T *)d_coeff, caller_layout(h, MGH_LD_IN), error_bound_type, ntol, tols,
                                        s, norm, dict_size, d_freq, d_outliers, (hipStream_t)stream);
+  });
+}
+
+int mgh_quantize_roundtrip(mgh_hierarchy *h, const void *d_coeff, int error_bound_type, double tol, double s,
+                           double norm, void *d_coeff_out, void *stream) {
+  if (!h || !d_coeff || !d_coeff_out) return fail(MGH_ERR_INVALID_ARGUMENT, "null argument");
+  if (const char *bad = qround_refusal(h->total)) return fail(MGH_ERR_INVALID_ARGUMENT, bad);
+  HIP_TRY(hipSetDevice(h->device));
+  return with_type(h, [&](auto t) {
+    using T = decltype(t);
+    return quantize_roundtrip_impl<T>(h, (const T *)d_coeff, caller_layout(h, MGH_LD_IN), {error_bound_type, tol, s},
+                                      norm, (T *)d_coeff_out, (hipStream_t)stream);
   });
 }
 

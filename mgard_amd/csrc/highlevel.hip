@@ -40,6 +40,7 @@
 #include "compare_plan.hpp"
 #include "domain_plan.hpp"
 #include "size_plan.hpp"
+#include "target_plan.hpp"
 
 extern "C" void mgh_set_last_error_(const char *msg);  // capi.hip
 // (capi.hip: the reduction of mgh_compare on two device arrays given by element strides, asynchronous)
@@ -2742,10 +2743,17 @@ int check_config(const mgh_config *cfg) {
 }
 
 // ---- sizes from histograms: mgh_estimate_sizes, mgh_compress_budget (size_plan.hpp) ---------------
+// ---- errors from round trips: mgh_achieved_errors, mgh_compress_target (target_plan.hpp) ----------
 // One array decomposed once, its coefficients kept on the device (lane 0's integer buffer, free
-// between calls) while tolerances are priced against them.
+// between calls) while tolerances are priced against them (price) or their reconstructions compared
+// with the input (achieved).
 struct SizeEstimator {
+  // what the decomposition is for: a size is a function of the histogram under Huffman alone; an
+  // achieved error does not depend on the lossless stage at all
+  enum class Purpose { sizes, errors };
   int D = 0, dtype = 0, ebtype = 0;
+  std::vector<uint64_t> shape_v;
+  const void *d_in = nullptr;  // the input on the device: the caller's array, or its upload
   double s = 0, norm = 1;
   uint64_t n = 0;
   size_t elem = 0;
@@ -2770,16 +2778,20 @@ struct SizeEstimator {
 
   // upload (host input), norm of a REL bound with the reduction compress_impl will use, decomposition
   int begin(int D_, int dtype_, const uint64_t *shape, double s_, int ebtype_, const void *original,
-            const void *const *coords_in, const mgh_config &cfg_) {
+            const void *const *coords_in, const mgh_config &cfg_, Purpose purpose = Purpose::sizes) {
     D = D_, dtype = dtype_, ebtype = ebtype_, s = s_, cfg = cfg_;
     elem = dtype == MGH_FLOAT ? 4 : 8;
-    if (cfg.lossless != MGH_LOSSLESS_HUFFMAN)
+    shape_v.assign(shape, shape + D);
+    if (purpose == Purpose::sizes && cfg.lossless != MGH_LOSSLESS_HUFFMAN)
       return hl_fail(MGH_ERR_INVALID_ARGUMENT, "size estimates: lossless must be Huffman (a Zstd frame's size is no function of the histogram)");
     HL_TRY(cache_prepare(cfg.dev_id));
     HL_TRY(trim_hierarchy_cache());
     HL_TRY(make_decomposer(dd, D, shape, elem, cfg));
     if (dd.decomposed || dd.num != 1)
-      return hl_fail(MGH_ERR_INVALID_ARGUMENT, "size estimates: the configuration decomposes the domain (containers of one subdomain only)");
+      return hl_fail(MGH_ERR_INVALID_ARGUMENT,
+                     purpose == Purpose::sizes
+                         ? "size estimates: the configuration decomposes the domain (containers of one subdomain only)"
+                         : "achieved errors: the configuration decomposes the domain (containers of one subdomain only)");
     n = 1;
     for (int d = 0; d < D; d++) n *= shape[d];
     if (coords_in) {
@@ -2794,7 +2806,7 @@ struct SizeEstimator {
     Lane &L = g_cache.lane[0];
     hipStream_t st = L.st;
     const size_t bytes = n * elem;
-    const void *d_in = original;
+    d_in = original;
     bool have_norm = ebtype != MGH_REL;
     if (!is_device_pointer(original)) {
       HL_TRY(g_cache.in[0].ensure(bytes));
@@ -2826,6 +2838,29 @@ struct SizeEstimator {
     if (!have_norm && (rc = mgh_norm(h, d_in, s, &norm, st)) != MGH_SUCCESS) return fail_drained(rc);
     if ((rc = L.q.ensure(std::max<size_t>(bytes, n * 8))) != MGH_SUCCESS) return fail_drained(rc);
     if ((rc = mgh_decompose(h, d_in, L.q.p, st)) != MGH_SUCCESS) return fail_drained(rc);
+    return MGH_SUCCESS;
+  }
+
+  // Per tolerance: the coefficients as the decoder will see them into the lane's second buffer
+  // (mgh_quantize_roundtrip), recomposed there in place, compared with the input on the device by the
+  // kernel of mgh_compare -- the launch mgh_verify makes for a container of one subdomain (dense `a`
+  // read in place, dense `b`), so the sums add up in the same order.
+  int achieved(int ntol, const double *tols, mgh_error_stats *out) {
+    Lane &L = g_cache.lane[0];
+    hipStream_t st = L.st;
+    int rc;
+    if ((rc = L.q2.ensure(n * elem)) != MGH_SUCCESS) return fail_drained(rc);
+    if ((rc = L.cmp.ensure(mgh_compare_scratch_bytes_())) != MGH_SUCCESS) return fail_drained(rc);
+    for (int k = 0; k < ntol; k++) {
+      if ((rc = mgh_quantize_roundtrip(h, L.q.p, ebtype, tols[k], s, norm, L.q2.p, st)) != MGH_SUCCESS) return fail_drained(rc);
+      if ((rc = mgh_recompose(h, L.q2.p, L.q2.p, st)) != MGH_SUCCESS) return fail_drained(rc);
+      if ((rc = mgh_compare_device_(D, dtype, shape_v.data(), d_in, nullptr, L.q2.p, nullptr, L.cmp.p, st)) != MGH_SUCCESS)
+        return fail_drained(rc);
+      // (pageable destination: the copy has landed when the call returns, and L.cmp is free for the next)
+      if (hipMemcpyAsync(&out[k], L.cmp.p, sizeof(mgh_error_stats), hipMemcpyDeviceToHost, st) != hipSuccess ||
+          hipStreamSynchronize(st) != hipSuccess)
+        return fail_drained(hl_fail(MGH_ERR_DEVICE, "achieved errors: reading the statistics back"));
+    }
     return MGH_SUCCESS;
   }
 
@@ -3002,6 +3037,66 @@ int mgh_compress_budget(int D, int dtype, const uint64_t *shape, size_t max_byte
     return hl_fail(MGH_ERR_FORMAT, "compress_budget: the container left the estimate's bracket");
   }
   return MGH_SUCCESS;
+}
+
+int mgh_achieved_errors(int D, int dtype, const uint64_t *shape, int ntol, const double *tols, double s, int ebtype,
+                        const void *original_data, const void *const *coords, const mgh_config *config,
+                        mgh_error_stats *out) {
+  if (!tols || !out) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (ntol < 1 || ntol > kTargetMaxTols) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "achieved_errors: ntol must be in 1..64");
+  HL_TRY(size_call_args(D, dtype, shape, ebtype, original_data, config));
+  try {
+    SizeEstimator E;
+    HL_TRY(E.begin(D, dtype, shape, s, ebtype, original_data, coords, *config, SizeEstimator::Purpose::errors));
+    return E.achieved(ntol, tols, out);
+  } catch (const std::exception &e) {
+    return hl_fail(MGH_ERR_DEVICE, e.what());
+  }
+}
+
+int mgh_compress_target(int D, int dtype, const uint64_t *shape, int metric, double target, double tol_min,
+                        double tol_max, int rounds, double s, int ebtype, const void *original_data,
+                        void **compressed_data, size_t *compressed_size, const void *const *coords,
+                        const mgh_config *config, int output_pre_allocated, double *tol_used, mgh_error_stats *stats_used,
+                        int *candidates) {
+  if (!compressed_data || !compressed_size || !tol_used) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (output_pre_allocated && !*compressed_data) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "pre-allocated output is NULL");
+  if (!target_metric_valid(metric) || std::isnan(target))
+    return hl_fail(MGH_ERR_INVALID_ARGUMENT, "compress_target: metric in 0..2 (max_abs, rmse, psnr), target not NaN");
+  if (!(tol_min > 0) || !(tol_min <= tol_max) || !std::isfinite(tol_max) || rounds < 1 || rounds > kTargetMaxRounds)
+    return hl_fail(MGH_ERR_INVALID_ARGUMENT, "compress_target: 0 < tol_min <= tol_max (finite), rounds in 1..16");
+  HL_TRY(size_call_args(D, dtype, shape, ebtype, original_data, config));
+  mgh_error_stats used{};
+  int evaluated = 0;
+  try {
+    SizeEstimator E;
+    HL_TRY(E.begin(D, dtype, shape, s, ebtype, original_data, coords, *config, SizeEstimator::Purpose::errors));
+    int rc = MGH_SUCCESS;
+    std::vector<std::pair<double, mgh_error_stats>> seen;  // every candidate evaluated, in order
+    auto meets = [&](double tol) {
+      mgh_error_stats e{};
+      if (rc == MGH_SUCCESS) rc = E.achieved(1, &tol, &e);
+      if (rc != MGH_SUCCESS) return false;
+      seen.emplace_back(tol, e);
+      return target_meets(e, (TargetMetric)metric, target);
+    };
+    const TargetResult r = target_search(tol_min, tol_max, rounds, meets);
+    HL_TRY(rc);
+    if (r.end == TargetEnd::bad_argument) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "compress_target: tolerances or rounds");
+    if (r.end == TargetEnd::nothing_meets)
+      return hl_fail(MGH_ERR_TARGET_NOT_MET, "compress_target: not even tol_min meets the target");
+    *tol_used = r.tol;
+    evaluated = r.candidates;
+    for (const auto &c : seen)
+      if (c.first == r.tol) used = c.second;
+  } catch (const std::exception &e) {
+    return hl_fail(MGH_ERR_DEVICE, e.what());
+  }
+  if (stats_used) *stats_used = used;
+  if (candidates) *candidates = evaluated;
+  // the writer itself, untouched: a second decomposition (its fused pass) is the price
+  return mgh_compress(D, dtype, shape, *tol_used, s, ebtype, original_data, compressed_data, compressed_size, coords,
+                      config, output_pre_allocated);
 }
 
 static int decompress_entry(const void *compressed_data, size_t compressed_size, void **decompressed_data,

@@ -15,6 +15,7 @@ from . import ABS, DOUBLE, FLOAT, INF, REL, ErrorStats, MgardHipError, _check, l
 MAX_DIM = 5
 DD_MAXDIM, DD_BLOCK, DD_VARIABLE = 0, 1, 2
 HUFFMAN, HUFFMAN_LZ4, HUFFMAN_ZSTD, CPU_LOSSLESS = 0, 1, 2, 3
+TARGET_MAX_ABS, TARGET_RMSE, TARGET_PSNR = 0, 1, 2  # mgh_target_metric
 
 HL_SYMBOLS = [
     "mgh_config_default", "mgh_compress", "mgh_decompress", "mgh_infer_shape",
@@ -33,6 +34,7 @@ HL_SYMBOLS = [
     "mgh_decompress_preview_window", "mgh_progressive_preview_window",
     "mgh_verify",
     "mgh_estimate_sizes", "mgh_compress_budget",
+    "mgh_achieved_errors", "mgh_compress_target",
 ]
 
 
@@ -157,6 +159,12 @@ def _hl():
     L.mgh_compress_budget.argtypes = [C.c_int, C.c_int, C.POINTER(u64), C.c_size_t, C.c_double, C.c_double, C.c_int,
                                       C.c_double, C.c_int, vp, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(vp),
                                       C.POINTER(Config), C.c_int, C.POINTER(C.c_double), C.POINTER(SizeEstimate)]
+    L.mgh_achieved_errors.argtypes = [C.c_int, C.c_int, C.POINTER(u64), C.c_int, C.POINTER(C.c_double), C.c_double,
+                                      C.c_int, vp, C.POINTER(vp), C.POINTER(Config), C.POINTER(ErrorStats)]
+    L.mgh_compress_target.argtypes = [C.c_int, C.c_int, C.POINTER(u64), C.c_int, C.c_double, C.c_double, C.c_double,
+                                      C.c_int, C.c_double, C.c_int, vp, C.POINTER(vp), C.POINTER(C.c_size_t),
+                                      C.POINTER(vp), C.POINTER(Config), C.c_int, C.POINTER(C.c_double),
+                                      C.POINTER(ErrorStats), C.POINTER(C.c_int)]
     L.mgh_dist_use_library.argtypes = [C.c_char_p]
     L.mgh_compress_dist.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(u64), C.c_double,
                                     C.c_double, C.c_int, vp, C.POINTER(vp), C.POINTER(C.c_size_t), vp, vp, C.c_int]
@@ -382,6 +390,53 @@ def compress_budget(data, max_bytes, tol_min, tol_max, rounds=4, s=INF, mode=REL
                                  int(rounds), float(s), int(mode), ptr, C.byref(optr), C.byref(size), cptr,
                                  C.byref(cfg), 1, C.byref(used), C.byref(est)))
     return out[:size.value], used.value, est
+
+
+def achieved_errors(data, tols, s=INF, mode=REL, coords=None, config=None):
+    """mgh_achieved_errors: one ErrorStats per tolerance (1..64 of them) -- what verify(compress(data, tol, ...),
+    data).stats would report, from one decomposition and without writing a container. Containers of one
+    subdomain; any supported lossless type."""
+    L = _hl()
+    cfg = config if config is not None else Config()
+    ptr, dt, shape, keep = _as_ptr(data)
+    D = len(shape)
+    tols = [float(t) for t in tols]
+    k = len(tols)
+    cptr, ckeep = _coords_ptr(coords, dt, D)
+    out = (ErrorStats * max(k, 1))()
+    _check(L.mgh_achieved_errors(D, dt, (C.c_uint64 * D)(*shape), k, (C.c_double * max(k, 1))(*tols), float(s), int(mode),
+                                 ptr, cptr, C.byref(cfg), out))
+    return list(out)[:k]
+
+
+def compress_target(data, metric, target, tol_min, tol_max, rounds=8, s=INF, mode=REL, coords=None, config=None):
+    """mgh_compress_target: the container of the LARGEST tolerance in [tol_min, tol_max] whose achieved error
+    meets `target` in `metric` (TARGET_MAX_ABS / TARGET_RMSE: at most; TARGET_PSNR: at least). Returns
+    (buf, tol_used, stats, candidates): buf is compress(data, tol_used, ...) -- a numpy uint8 array (host input)
+    or a cuda uint8 tensor (device input) --, stats the ErrorStats of the chosen candidate, candidates the number
+    evaluated. Raises (MGH_ERR_TARGET_NOT_MET) when not even tol_min meets the target."""
+    import torch
+    L = _hl()
+    cfg = config if config is not None else Config()
+    ptr, dt, shape, keep = _as_ptr(data)
+    D = len(shape)
+    cptr, ckeep = _coords_ptr(coords, dt, D)
+    on_device = isinstance(data, torch.Tensor) and data.is_cuda
+    cap = int(np.prod(shape)) * (4 if dt == FLOAT else 8) + 1000000
+    if on_device:
+        out = torch.empty(cap, dtype=torch.uint8, device=data.device)
+        optr = C.c_void_p(out.data_ptr())
+    else:
+        out = np.empty(cap, dtype=np.uint8)
+        optr = C.c_void_p(out.ctypes.data)
+    size = C.c_size_t(cap)
+    used = C.c_double()
+    stats = ErrorStats()
+    cand = C.c_int()
+    _check(L.mgh_compress_target(D, dt, (C.c_uint64 * D)(*shape), int(metric), float(target), float(tol_min),
+                                 float(tol_max), int(rounds), float(s), int(mode), ptr, C.byref(optr), C.byref(size), cptr,
+                                 C.byref(cfg), 1, C.byref(used), C.byref(stats), C.byref(cand)))
+    return out[:size.value], used.value, stats, cand.value
 
 
 def infer(buf):
