@@ -212,6 +212,31 @@ inline compress_status_type compress_budget(DIM D, data_type dtype, std::vector<
                                             cp.empty() ? nullptr : cp.data(), &c, output_pre_allocated ? 1 : 0, &tol_used,
                                             estimate_used));
 }
+// EXTENSION: mgh_compress_ladder. compressed_data[k] / compressed_size[k]: the container compress(tols[k])
+// writes (up to the order of its outlier list), for every tolerance of `tols` (1..64) in order, from ONE
+// decomposition. Containers of one subdomain (Failure otherwise; mgh_last_error() says so). Without
+// output_pre_allocated both vectors are sized here and every container is the caller's to free as
+// compress's is; with it, they carry the buffers and their capacities in. When tolerance k fails the
+// status is that write's, the containers before k stay valid and the pointers from k on are null where
+// the call allocates them.
+inline compress_status_type compress_ladder(DIM D, data_type dtype, std::vector<SIZE> shape,
+                                            const std::vector<double> &tols, double s, error_bound_type mode,
+                                            const void *original_data, std::vector<void *> &compressed_data,
+                                            std::vector<size_t> &compressed_size, std::vector<const Byte *> coords,
+                                            HighLevelConfig config, bool output_pre_allocated) {
+  if (shape.size() != D) return compress_status_type::Failure;
+  if (output_pre_allocated && (compressed_data.size() != tols.size() || compressed_size.size() != tols.size()))
+    return compress_status_type::Failure;
+  if (!output_pre_allocated) {
+    compressed_data.assign(tols.size(), nullptr);
+    compressed_size.assign(tols.size(), 0);
+  }
+  const mgh_config c = detail::to_c(config);
+  std::vector<const void *> cp(coords.begin(), coords.end());
+  return detail::status(mgh_compress_ladder(D, (int)dtype, shape.data(), (int)tols.size(), tols.data(), s, (int)mode,
+                                            original_data, compressed_data.data(), compressed_size.data(),
+                                            cp.empty() ? nullptr : cp.data(), &c, output_pre_allocated ? 1 : 0));
+}
 // EXTENSION: mgh_achieved_errors. What verify(compress(tol)) would report for every tolerance of `tols`
 // (1..64), from one decomposition and without writing a container. Containers of one subdomain (Failure
 // otherwise; mgh_last_error() says so); any supported lossless_type.

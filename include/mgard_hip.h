@@ -226,6 +226,25 @@ int mgh_quantize_histograms(mgh_hierarchy *h, const void *d_coeff, int error_bou
 int mgh_quantize_roundtrip(mgh_hierarchy *h, const void *d_coeff, int error_bound_type, double tol,
                            double s, double norm, void *d_coeff_out, void *stream);
 
+/* ONE coefficient array (what mgh_decompose wrote; MGH_LD_IN applies as in mgh_quantize_roundtrip: a
+ * pitched array goes through a dense copy inside the hierarchy) to what the lossless stage reads, in one
+ * pass: d_symbols[i] (dense, uint16) is the integer mgh_quantize(..., prep_huffman = 1) stores at i, which
+ * lies in [0, dict_size) or is 0 at an outlier's position; the outlier list holds (linear index, the int64
+ * mgh_quantize puts into its list) in no particular order. The counter goes on counting past
+ * outlier_capacity and nothing is written past it, so a caller learns the size it needs, as with
+ * mgh_quantize. d_freq_or_null, when given, receives the histogram of the stored symbols (dict_size
+ * 32-bit bins, an outlier counted in bin 0): what a histogram pass over d_symbols would count.
+ * THE CALLER ZEROES d_freq_or_null AND *d_outlier_count (in stream order before the call): the call adds
+ * to both. The level quantizers are the ones mgh_quantize builds, by the same host code and upload. Every
+ * shape the stand-alone quantizer takes, 1-D to 5-D. Refused with MGH_ERR_INVALID_ARGUMENT: dict_size
+ * odd or outside 2..16384, NULL d_symbols or d_outlier_count, outlier_capacity > 0 with a NULL list, arrays
+ * of 2^32 elements and more (32-bit index arithmetic and counters, as in mgh_quantize_histograms).
+ * ASYNCHRONOUS behind the upload of the quantizer table. No reference counterpart. */
+int mgh_quantize_symbols(mgh_hierarchy *h, const void *d_coeff, int error_bound_type, double tol, double s,
+                         double norm, uint64_t dict_size, uint16_t *d_symbols, uint32_t *d_freq_or_null,
+                         uint64_t *d_outlier_count, uint64_t *d_outlier_idx, int64_t *d_outlier_val,
+                         uint64_t outlier_capacity, void *stream);
+
 /* Norm that stays on the device: writes one value of the hierarchy's dtype to
  * d_norm_out (max|x| for s = +inf, else the L2 norm of this array as
  * norm_calculator defines it). ASYNCHRONOUS. For a decomposed domain the caller

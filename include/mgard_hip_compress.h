@@ -113,8 +113,9 @@ int mgh_estimate_sizes(int D, int dtype, const uint64_t *shape, int ntol, const 
 /* The most accurate container of at most max_bytes: searches [tol_min, tol_max] on a logarithmic
  * grid (tol_min if it fits; else `rounds` in 1..8 rounds of three candidates, which narrow the
  * bracket to (tol_max / tol_min)^(1 / 4^rounds)), pricing candidates as mgh_estimate_sizes does -- a
- * candidate fits when its bytes_max does, so the result fits by construction --, then calls
- * mgh_compress with *tol_used: the container is the one mgh_compress(*tol_used) writes.
+ * candidate fits when its bytes_max does, so the result fits by construction --, then writes the
+ * container of *tol_used from the coefficients the candidates were priced on (no second decomposition):
+ * the container is the one mgh_compress(*tol_used) writes, up to the order of its outlier list.
  * estimate_used (may be NULL): the estimate of *tol_used. The search is double-precision arithmetic
  * on the tolerances alone and reproducible bit for bit. MGH_ERR_OUTPUT_TOO_LARGE when not even
  * tol_max fits: nothing is allocated and *compressed_data is left as it was. tol_min <= 0,
@@ -158,8 +159,9 @@ int mgh_achieved_errors(int D, int dtype, const uint64_t *shape, int ntol, const
  * (2 candidates), and `rounds` (1..16) bisections in log, each one candidate evaluated as
  * mgh_achieved_errors evaluates it, narrow the bracket to (tol_max / tol_min)^(1 / 2^rounds). The
  * result meets the target BY MEASUREMENT, so an error curve that is not monotone costs compression at
- * worst, never the target. Then mgh_compress is called with *tol_used: the container is the one
- * mgh_compress(*tol_used) writes. stats_used (may be NULL): the statistics of the chosen candidate;
+ * worst, never the target. Then the container of *tol_used is written from the coefficients the
+ * candidates share (no second decomposition): it is the one mgh_compress(*tol_used) writes, up to the
+ * order of its outlier list. stats_used (may be NULL): the statistics of the chosen candidate;
  * candidates (may be NULL): how many were evaluated. The search is double-precision arithmetic on the
  * tolerances alone and reproducible bit for bit. MGH_ERR_TARGET_NOT_MET when not even tol_min meets the
  * target: nothing is allocated and *compressed_data is left as it was. metric outside 0..2, a NaN
@@ -170,6 +172,45 @@ int mgh_compress_target(int D, int dtype, const uint64_t *shape, int metric, dou
                         void **compressed_data, size_t *compressed_size, const void *const *coords,
                         const mgh_config *config, int output_pre_allocated, double *tol_used,
                         mgh_error_stats *stats_used /* may be NULL */, int *candidates /* may be NULL */);
+
+/* ---- One array at several tolerances: a ladder of containers (extension) ---------------------------
+ * compressed_data[k] receives the container mgh_compress(tols[k]) writes for the same arguments (up to
+ * the order of its outlier list), for `ntol` (1..64) tolerances in the order given -- fidelity tiers of
+ * one array -- from ONE upload, ONE norm and ONE decomposition: the decomposition does not depend on the
+ * tolerance, so every further tier costs a quantizer pass over the coefficients and a lossless stage.
+ * Outputs live in the input's memory space and are allocated as mgh_compress allocates them (free them
+ * the same way); with output_pre_allocated, compressed_size[k] carries the capacity of
+ * compressed_data[k] in and the size out.
+ * On a failure at tolerance k the status is the failing write's (MGH_ERR_OUTPUT_TOO_LARGE for a
+ * pre-allocated buffer that is too small), containers 0 .. k-1 stay valid and stay the caller's, and
+ * compressed_data[k ..] are NULL when the call allocates them.
+ * Contract: containers of ONE subdomain (a configuration that decomposes the domain is
+ * MGH_ERR_INVALID_ARGUMENT), either lossless type, either reorder. ntol outside 1..64 and a tolerance
+ * that is not positive and finite: MGH_ERR_INVALID_ARGUMENT. Host buffers are not registered
+ * (config->auto_pin_host_buffers is not honoured). Limit (1) of mgh_achieved_errors applies: a REL bound
+ * with finite s on float64 data inherits the order dependence of the last bits of the norm, as two
+ * mgh_compress calls do. Device memory: the coefficient array, and the symbols (2 bytes an element; 8,
+ * and 8 more with reorder = 1, where the single-pass encoder does not run) in buffers of the pipeline. */
+int mgh_compress_ladder(int D, int dtype, const uint64_t *shape, int ntol, const double *tols, double s,
+                        int error_bound_type, const void *original_data, void **compressed_data /* [ntol] */,
+                        size_t *compressed_size /* [ntol] */, const void *const *coords, const mgh_config *config,
+                        int output_pre_allocated);
+
+/* What the last WRITING call of the calling thread did (mgh_compress, mgh_compress_budget,
+ * mgh_compress_target, mgh_compress_ladder; thread-local; zeros before the first call; a failed call
+ * leaves what it had counted). */
+typedef struct mgh_compress_stats {
+  uint64_t decompositions;     /* passes that turned data into coefficients (one per subdomain of
+                                  mgh_compress; the estimators' own single one for the other three) */
+  uint64_t quantize_passes;    /* passes that turned coefficients into integers or symbols for a record
+                                  (candidates that were only priced or measured do not count) */
+  uint64_t histogram_launches; /* launches of the lossless stage's own histogram kernel; a record whose
+                                  bins the quantizer filled (mgh_quantize_symbols) counts 0 */
+  uint64_t records;            /* records written, RAW ones included */
+  uint64_t raw_records;        /* ... of which store the array itself */
+  uint64_t outlier_retries;    /* quantizer passes repeated because the outlier lists overflowed */
+} mgh_compress_stats;
+int mgh_last_compress_stats(mgh_compress_stats *out);
 
 /* mgard_x::decompress. Shape and type come from the header (query them first with
  * mgh_infer_shape / mgh_infer_data_type to pre-allocate). */
@@ -449,6 +490,11 @@ int mgh_metadata_parse(const uint8_t *data, uint64_t size, mgh_header_info *info
 int mgh_huffman_codebook(const uint32_t *freq, uint64_t dict_size, uint64_t *code_out,
                          uint64_t *first_out /* [64] */, uint64_t *entry_out /* [64] */,
                          uint64_t *keys_out /* [dict_size] */);
+
+/* Histogram of 16-bit symbols (mgh_decompose_quantize_sym16, mgh_quantize_symbols) as the lossless stage
+ * counts them: d_freq[q] += the number of d_symbols[i] == q < dict_size (2..16384). THE CALLER ZEROES
+ * d_freq. 1 .. 2^32 - 1 symbols. ASYNCHRONOUS on `stream`, on the current device. */
+int mgh_histogram_sym16(const uint16_t *d_symbols, uint64_t n, uint64_t dict_size, uint32_t *d_freq, void *stream);
 
 typedef struct mgh_lossless_ctx mgh_lossless_ctx;
 int mgh_lossless_create(mgh_lossless_ctx **out, int dev_id);

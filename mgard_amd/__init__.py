@@ -29,6 +29,7 @@ SYMBOLS = [
     "mgh_profile_enable", "mgh_profile_filter", "mgh_profile_read", "mgh_stream_calibrate",
     "mgh_level_linearize", "mgh_outlier_restore", "mgh_norm_stream_begin", "mgh_norm_stream_add",
     "mgh_norm_stream_end", "mgh_quantize_histograms", "mgh_quantize_roundtrip",
+    "mgh_quantize_symbols",
     "mgh_set_ld",
     "mgh_recompose_to_level", "mgh_dequantize_recompose_to_level",
     "mgh_dequantize_recompose_sym16_to_level", "mgh_level_nodes",
@@ -124,6 +125,8 @@ def load_library():
     L.mgh_quantize_histograms.argtypes = [vp, vp, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_double, C.c_double,
                                           u64, vp, vp, vp]
     L.mgh_quantize_roundtrip.argtypes = [vp, vp, C.c_int, C.c_double, C.c_double, C.c_double, vp, vp]
+    L.mgh_quantize_symbols.argtypes = [vp, vp, C.c_int, C.c_double, C.c_double, C.c_double, u64, vp, vp, vp, vp, vp,
+                                       u64, vp]
     L.mgh_dequantize_recompose_sym16.argtypes = [vp, vp, C.c_int, C.c_double, C.c_double, C.c_double, u64,
                                                  vp, vp, u64, vp, vp]
     L.mgh_sym16_supported.argtypes = [vp]
@@ -501,6 +504,23 @@ class Hierarchy:
         _check(load_library().mgh_quantize_roundtrip(
             self._h, self._chk(coeff), int(error_bound_type), tol, s, norm, C.c_void_p(out.data_ptr()), _stream()))
         return out
+
+    def quantize_symbols(self, coeff, ebtype, tol, s, norm, dict_size=8192, histogram=True, outlier_cap=None):
+        """mgh_quantize_symbols: (symbols uint16, freq int32 [dict_size] or None, outlier_idx, outlier_val)
+        -- what quantize(prep_huffman=True) stores, as 16-bit symbols with 0 at the outliers' positions, the
+        outlier list (its length is the count; at most `outlier_cap` pairs, the whole array by default) and,
+        with `histogram`, the histogram of the stored symbols, all from one pass over `coeff`."""
+        import torch
+        cap = self.total if outlier_cap is None else int(outlier_cap)
+        sym = torch.empty(self.shape, dtype=torch.uint16, device=coeff.device)
+        freq = torch.zeros(int(dict_size), dtype=torch.int32, device=coeff.device) if histogram else None
+        cnt, idx, val = self._outlier_bufs(cap)
+        _check(load_library().mgh_quantize_symbols(
+            self._h, self._chk(coeff), int(ebtype), tol, s, norm, int(dict_size), C.c_void_p(sym.data_ptr()),
+            C.c_void_p(freq.data_ptr()) if histogram else None, C.c_void_p(cnt.data_ptr()),
+            C.c_void_p(idx.data_ptr()), C.c_void_p(val.data_ptr()), cap, _stream()))
+        k = min(int(cnt.item()), cap)
+        return sym, freq, idx[:k], val[:k]
 
     def decompose_quantize_sym16(self, data, ebtype, tol, s, norm=0.0, dict_size=8192, outlier_cap=None):
         """mgh_decompose_quantize_sym16: (symbols uint16, outlier_idx, outlier_val, count, norm)."""

@@ -49,6 +49,7 @@
 #include "kernels_qhist.hpp"
 #include "target_plan.hpp"
 #include "kernels_qround.hpp"
+#include "kernels_qsym.hpp"
 
 namespace {
 
@@ -2994,6 +2995,38 @@ int quantize_roundtrip_impl(mgh_hierarchy *h, const T *coeff, Layout in, const B
   });
 }
 
+// mgh_quantize_symbols: the table of mgh_quantize by its own upload (upload_quantizers, reciprocal), then
+// one launch of k_quantize_symbols. The caller has zeroed the counter and the bins.
+template <typename T>
+int quantize_symbols_impl(mgh_hierarchy *h, const T *coeff, Layout in, const Bound &b, double norm, uint64_t dict,
+                          uint16_t *sym, uint32_t *freq, const QuantOut &qo, hipStream_t st) {
+  auto *ds = DS<T>(h);
+  const int nlev = h->L + 1;
+  if (nlev > kMaxLevels) return fail(MGH_ERR_INVALID_ARGUMENT, "too many levels");
+  TRY(ld_pack<T>(h, coeff, in, false, st));
+  TRY(upload_quantizers<T>(h, b.ebtype, b.tol, b.s, norm, true, st));
+  // persistent workgroups of 256 threads, one 16-byte vector per thread and round: eight per compute
+  // unit for the plain stream, as many as the LDS holds beside the static tables with the bins
+  const size_t lds = freq ? (size_t)dict * 4 : 0;
+  const size_t per_cu = std::max<size_t>(1, std::min<size_t>(8, kLdsPerCU / (lds + 4096)));
+  const size_t total = h->total, per_wg = (size_t)kQsThreads * Vec16<T>::N;
+  const unsigned grid = (unsigned)std::min<size_t>((total + per_wg - 1) / per_wg, per_cu * h->num_cu);
+  if (freq) {
+    static std::atomic<uint64_t> once{0};
+    TRY(allow_big_lds_once(k_quantize_symbols<T, true>, once, kQsymLdsBytes));
+  }
+  return launch(h, "quantize_symbols", st, [&] {
+    if (freq)
+      k_quantize_symbols<T, true><<<grid, kQsThreads, lds, st>>>(
+          ds->qmeta, total, coeff, ds->marks, ds->qz, nlev, (int)dict, sym, freq, (unsigned long long *)qo.ocount,
+          qo.oidx, qo.oval, (unsigned long long)qo.ocap);
+    else
+      k_quantize_symbols<T, false><<<grid, kQsThreads, 0, st>>>(
+          ds->qmeta, total, coeff, ds->marks, ds->qz, nlev, (int)dict, sym, nullptr, (unsigned long long *)qo.ocount,
+          qo.oidx, qo.oval, (unsigned long long)qo.ocap);
+  });
+}
+
 // The norm k_make_qparams left in ds->normval, on the host: one synchronisation.
 template <typename T> int read_back_norm(mgh_hierarchy *h, double *out, hipStream_t st) {
   T nv = 0;
@@ -3679,6 +3712,22 @@ int mgh_quantize_roundtrip(mgh_hierarchy *h, const void *d_coeff, int error_boun
     using T = decltype(t);
     return quantize_roundtrip_impl<T>(h, (const T *)d_coeff, caller_layout(h, MGH_LD_IN), {error_bound_type, tol, s},
                                       norm, (T *)d_coeff_out, (hipStream_t)stream);
+  });
+}
+
+int mgh_quantize_symbols(mgh_hierarchy *h, const void *d_coeff, int error_bound_type, double tol, double s,
+                         double norm, uint64_t dict_size, uint16_t *d_symbols, uint32_t *d_freq_or_null,
+                         uint64_t *d_outlier_count, uint64_t *d_outlier_idx, int64_t *d_outlier_val,
+                         uint64_t outlier_capacity, void *stream) {
+  if (!h || !d_coeff || !d_symbols) return fail(MGH_ERR_INVALID_ARGUMENT, "null argument");
+  const QuantOut qo{dict_size, 1, nullptr, d_symbols, d_outlier_count, d_outlier_idx, d_outlier_val, outlier_capacity};
+  TRY(outlier_args(qo));
+  if (const char *bad = qsym_refusal(h->total, dict_size)) return fail(MGH_ERR_INVALID_ARGUMENT, bad);
+  HIP_TRY(hipSetDevice(h->device));
+  return with_type(h, [&](auto t) {
+    using T = decltype(t);
+    return quantize_symbols_impl<T>(h, (const T *)d_coeff, caller_layout(h, MGH_LD_IN), {error_bound_type, tol, s},
+                                    norm, dict_size, d_symbols, d_freq_or_null, qo, (hipStream_t)stream);
   });
 }
 

@@ -51,6 +51,7 @@ extern "C" int mgh_compare_device_(int D, int dtype, const uint64_t *shape, cons
 
 namespace {
 constexpr int kOutlierOverflow = -1000;  // internal: more outliers than the buffers hold
+constexpr int kLadderMaxTols = 64;       // mgh_compress_ladder: tolerances per call
 
 // Kernel attributes such as the dynamic-LDS limit belong to the function on the current device and
 // are set once per device ordinal: `if (hl_attr_pending(once)) { set ...; hl_attr_done(once); }`.
@@ -444,6 +445,7 @@ struct LosslessJob {
   const uint64_t *d_ocount = nullptr;
   uint64_t ocap = ~(uint64_t)0, cap_units = 0;
   bool sym16 = false;
+  bool bins_filled = false;  // the quantizer counted the symbols into the context's bins (mgh_quantize_symbols)
 };
 
 // Zeroing of the stage's device state (histogram bins, the encoder's chunk states, optionally a
@@ -500,10 +502,14 @@ int lossless_begin(mgh_lossless_ctx *c, const LosslessJob &J, hipStream_t st) {
   // decomposer never produces one, but the stand-alone entry point could be handed one)
   if (n >= ((uint64_t)1 << 32))
     return hl_fail(MGH_ERR_INVALID_ARGUMENT, "lossless stage: more than 2^32 - 1 symbols in one record");
+  // (bins_filled: lossless_prepare zeroed the bins in front of the quantizer that filled them)
+  if (J.bins_filled && !prepared) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "lossless: filled bins without lossless_prepare");
   if (!prepared) HL_HIP(hipMemsetAsync(c->freq.p, 0, dict * 4, st));
   const unsigned hblocks =
       (unsigned)std::min<size_t>((n + huff::kHistThreads - 1) / huff::kHistThreads, 2 * (size_t)hl_num_cu());
-  if (sym16)
+  if (J.bins_filled)
+    hl_debug("lossless_compress: bins filled by the quantizer");
+  else if (sym16)
     huff::k_histogram<uint16_t><<<hblocks, huff::kHistThreads, dict * 4, st>>>((const uint16_t *)d_q, n, (int)dict,
                                                                                (unsigned *)c->freq.p);
   else
@@ -1550,6 +1556,7 @@ int copy_subdomain(const Decomposer &dd, uint64_t id, size_t elem, void *sub, co
 struct Lane {
   hipStream_t st = nullptr;
   DevBuf q, q2, ocount, oidx, oval;  // q2: level-linearised copy (config.reorder == 1)
+  DevBuf q3;                         // writing from coefficients kept in q: the linearised copy of the integers in q2
   DevBuf sub;                        // decompression: the dense subdomain when the output is not written in place
   DevBuf lvl;                        // full-grid preview: the dense array of the subdomain's level, before it is prolonged
   DevBuf cmp, orig;                  // mgh_verify: scratch of the reduction; the box of a host-resident original
@@ -1559,6 +1566,7 @@ struct Lane {
   void release() {
     q.release();
     q2.release();
+    q3.release();
     ocount.release();
     oidx.release();
     oval.release();
@@ -1596,7 +1604,7 @@ struct HlCache {
     for (auto &x : in) b += x.cap;
     b += vres.cap;
     for (auto &l : lane) {
-      b += l.q.cap + l.q2.cap + l.oidx.cap + l.oval.cap + l.sub.cap + l.orig.cap + l.cmp.cap;
+      b += l.q.cap + l.q2.cap + l.q3.cap + l.oidx.cap + l.oval.cap + l.sub.cap + l.orig.cap + l.cmp.cap;
       if (l.ll) b += l.ll->units.cap + l.ll->oidx.cap + l.ll->oval.cap;
     }
     return b;
@@ -1774,10 +1782,98 @@ int header_from(const Decomposer &dd, int dtype, int ebtype, double tol, double 
   return MGH_SUCCESS;
 }
 
+// ---- what the two entries into the writer share (compress_impl from the caller's data, -------------
+// ---- SizeEstimator::write from coefficients already on the device) --------------------------------
+// What the last writing call of this thread did (mgh_last_compress_stats).
+inline mgh_compress_stats &compress_stats() {
+  thread_local mgh_compress_stats s{};
+  return s;
+}
+
+// Where the records of a writing call go: its output and how much of it is used.
+struct RecordSink {
+  void *out = nullptr;
+  size_t cap = 0, byte_offset = 0;
+  bool out_dev = false;
+};
+
+// The second half of a subdomain's lossless stage (lossless_begin is queued on the lane), with the retry
+// of an outlier overflow: estimate_outlier_ratio was too optimistic, so the lane's lists grow to what the
+// subdomain needs and `again()` quantizes it once more and queues lossless_begin for the job `lj` then
+// describes (LinearQuantization.hpp:621-676 re-launches the same way).
+template <typename Again>
+int encode_record(Lane &L, const LosslessJob &lj, const RecordSink &S, Again &&again) {
+  int frc = MGH_SUCCESS;
+  for (int attempt = 0; attempt < 2; attempt++) {
+    const bool direct_ok = S.out_dev && S.cap - S.byte_offset > 8;
+    frc = lossless_finish(L.ll, lj, L.st, direct_ok ? (uint8_t *)S.out + S.byte_offset + 8 : nullptr,
+                          direct_ok ? S.cap - S.byte_offset - 8 : 0);
+    if (frc != kOutlierOverflow) break;
+    if (attempt == 1) return hl_fail(MGH_ERR_DEVICE, "outlier lists overflowed twice");
+    const uint64_t need = L.ll->outliers_needed;
+    HL_TRY(L.oidx.ensure(need * 8));
+    HL_TRY(L.oval.ensure(need * 8));
+    L.ocap = need;
+    compress_stats().outlier_retries++;
+    HL_TRY(again());
+  }
+  return frc;
+}
+
+// The record encode_record left in the lane's context -- or the dense subdomain `dense_in` itself where
+// the record is not smaller (a RAW record) -- behind its size prefix at the sink's offset. `last_hdr`
+// (the container's last record): the metadata, of meta_size bytes, travels on the record's stream, in
+// front of the synchronisation that record needs anyway; it comes out of g_cache.hpin, which the
+// caller has sized. Ends with the lane synchronised.
+int write_record(Lane &L, uint64_t n, size_t elem, const void *dense_in, RecordSink &S, const fmt::Header *last_hdr,
+                 size_t meta_size) {
+  hipStream_t st = L.st;
+  uint64_t csize = L.ll->record_size();
+  const bool raw = (double)(n * elem) / (double)csize < 1.0;  // GPUPipelines.hpp:136-155
+  if (raw) csize = n * elem;
+  if (csize > S.cap - S.byte_offset || S.cap - S.byte_offset - csize < 8)
+    return hl_fail(MGH_ERR_OUTPUT_TOO_LARGE, "Output too large");
+  char *dst = (char *)S.out + S.byte_offset;
+  const bool prefix_with_record = S.out_dev && !raw;  // (one copy: size prefix + head of the record)
+  if (S.out_dev && raw) {
+    std::memcpy(L.pin.p, &csize, 8);
+    HL_HIP(hipMemcpyAsync(dst, L.pin.p, 8, hipMemcpyHostToDevice, st));
+  } else if (!S.out_dev) {
+    std::memcpy(dst, &csize, 8);
+  }
+  dst += 8;
+  if (raw) {
+    // the dense subdomain itself (the decomposition does not modify its input, so the buffer still
+    // holds it)
+    HL_TRY(copy_any(dst, dense_in, csize, st));
+  } else {
+    const uint64_t cs64 = csize;
+    HL_TRY(record_write(L.ll, dst, st, prefix_with_record ? &cs64 : nullptr));
+  }
+  if (last_hdr) {
+    const std::vector<uint8_t> meta = fmt::serialize_metadata(*last_hdr);
+    if (meta.size() != meta_size) return hl_fail(MGH_ERR_FORMAT, "metadata size changed");
+    if (S.out_dev) {
+      // (out of pinned memory: the copy is queued, not staged synchronously)
+      std::memcpy((char *)g_cache.hpin.p + 64, meta.data(), meta.size());
+      HL_HIP(hipMemcpyAsync(S.out, (char *)g_cache.hpin.p + 64, meta.size(), hipMemcpyHostToDevice, st));
+    } else {
+      std::memcpy(S.out, meta.data(), meta.size());
+    }
+  }
+  if (hipStreamSynchronize(st) != hipSuccess) return hl_fail(MGH_ERR_DEVICE, "writing the subdomain record");
+  hl_debug("compress: record written");
+  compress_stats().records++;
+  compress_stats().raw_records += raw ? 1 : 0;
+  S.byte_offset += 8 + csize;
+  return MGH_SUCCESS;
+}
+
 template <typename T>
 int compress_impl(int D, int dtype, const uint64_t *shape, double tol_d, double s_d, int ebtype,
                   const void *original, void **compressed, size_t *compressed_size,
                   const void *const *coords_in, const mgh_config &cfg, bool prealloc) {
+  compress_stats() = mgh_compress_stats{};
   HL_TRY(cache_prepare(cfg.dev_id));
   HL_TRY(trim_hierarchy_cache());
   const T tol = (T)tol_d, s = (T)s_d;
@@ -1944,12 +2040,12 @@ int compress_impl(int D, int dtype, const uint64_t *shape, double tol_d, double 
   // the norm of a non-decomposed REL run, whose encoding has a fixed length (a non-zero double)
   fmt::Header hdr;
   header_from(dd, dtype, ebtype, tol_d, s_d, ebtype == MGH_REL ? (dd.decomposed ? (double)norm : 1.0) : 0.0, cptr, cfg, hdr);
-  std::vector<uint8_t> meta;  // (outlives the asynchronous copy of the header below)
   const size_t meta_size = fmt::serialize_metadata(hdr).size();
   if (meta_size > cap) return cleanup(hl_fail(MGH_ERR_OUTPUT_TOO_LARGE, "output buffer too small for the header"));
   // (sized once, here: an asynchronous copy out of it must never meet a re-allocation)
   if ((rc = g_cache.hpin.ensure(64 + meta_size)) != MGH_SUCCESS) return cleanup(rc);
-  size_t byte_offset = meta_size;
+  RecordSink sink;
+  sink.out = *compressed, sink.cap = cap, sink.byte_offset = meta_size, sink.out_dev = out_dev;
 
   // ---- subdomain pipeline (compress_pipeline_gpu, GPUPipelines.hpp:69-207) ----
   // issue(k): decomposition + quantizer + histogram of subdomain k queued on lane k % nlanes, no
@@ -2012,6 +2108,9 @@ int compress_impl(int D, int dtype, const uint64_t *shape, double tol_d, double 
                                     (int64_t *)L.q.p, (uint64_t *)L.ocount.p, (uint64_t *)L.oidx.p,
                                     (int64_t *)L.oval.p, L.ocap, nullptr, st));
     hl_debug("compress: decompose + quantize done");
+    compress_stats().decompositions++;
+    compress_stats().quantize_passes++;
+    compress_stats().histogram_launches++;
     // REL on the fused device path (the 16-bit symbol call: the norm never left the device): it
     // is fetched behind the quantizer into pinned memory and read when the lossless stage has
     // synchronised anyway -- a read-back inside the call above would stall the queue in front of
@@ -2046,33 +2145,19 @@ int compress_impl(int D, int dtype, const uint64_t *shape, double tol_d, double 
   };
   auto finish = [&](SubJob &J) -> int {
     Lane &L = g_cache.lane[J.lane];
-    hipStream_t st = L.st;
     const uint64_t id = J.id, n = J.n;
-    int frc = MGH_SUCCESS;
-    for (int attempt = 0; attempt < 2; attempt++) {
-      const bool direct_ok = out_dev && cap - byte_offset > 8;
-      frc = lossless_finish(L.ll, J.lj, st, direct_ok ? (uint8_t *)*compressed + byte_offset + 8 : nullptr,
-                            direct_ok ? cap - byte_offset - 8 : 0);
-      if (frc != kOutlierOverflow) break;
-      if (attempt == 1) return hl_fail(MGH_ERR_DEVICE, "outlier lists overflowed twice");
-      // estimate_outlier_ratio was too optimistic: grow this lane's lists to what the subdomain
-      // needs and quantize it again (LinearQuantization.hpp:621-676 re-launches the same way)
-      const uint64_t need = L.ll->outliers_needed;
-      HL_TRY(L.oidx.ensure(need * 8));
-      HL_TRY(L.oval.ensure(need * 8));
-      L.ocap = need;
+    HL_TRY(encode_record(L, J.lj, sink, [&]() -> int {
       mgh_hierarchy *h = J.h;
-      const bool owned = J.owned;
       SubJob again;
       // (the hierarchy of the first attempt serves the second; issue() looks it up again)
-      if (owned) {
+      if (J.owned) {
         owned_alive.erase(std::remove(owned_alive.begin(), owned_alive.end(), h), owned_alive.end());
         mgh_hierarchy_destroy(h);
       }
       HL_TRY(issue(again, id));
       J = again;
-    }
-    HL_TRY(frc);
+      return MGH_SUCCESS;
+    }));
     if (J.norm_deferred) {  // (lossless_finish has synchronised the lane)
       T nv;
       std::memcpy(&nv, (const char *)L.pin.p + 16, sizeof(T));
@@ -2081,49 +2166,14 @@ int compress_impl(int D, int dtype, const uint64_t *shape, double tol_d, double 
       norm = (T)J.norm_out;
     }
     hl_debug("compress: lossless stage done");
-    uint64_t csize = L.ll->record_size();
-    const bool raw = (double)(n * elem) / (double)csize < 1.0;  // GPUPipelines.hpp:136-155
-    if (raw) csize = n * elem;
-    if (csize > cap - byte_offset || cap - byte_offset - csize < 8)
-      return hl_fail(MGH_ERR_OUTPUT_TOO_LARGE, "Output too large");
-    char *dst = (char *)*compressed + byte_offset;
-    const bool prefix_with_record = out_dev && !raw;  // (one copy: size prefix + head of the record)
-    if (out_dev && raw) {
-      std::memcpy(L.pin.p, &csize, 8);
-      HL_HIP(hipMemcpyAsync(dst, L.pin.p, 8, hipMemcpyHostToDevice, st));
-    } else if (!out_dev) {
-      std::memcpy(dst, &csize, 8);
-    }
-    dst += 8;
-    if (raw) {
-      // the dense subdomain itself (decompose_quantize does not modify its input, so the buffer
-      // still holds it)
-      HL_TRY(copy_any(dst, sub_in(id), csize, st));
-    } else {
-      const uint64_t cs64 = csize;
-      HL_TRY(record_write(L.ll, dst, st, prefix_with_record ? &cs64 : nullptr));
-    }
-    if (id + 1 == dd.num) {
-      // header (with the norm the pipeline computed for a non-decomposed REL run): it travels on the
-      // last record's stream, in front of the synchronisation that record needs anyway
-      header_from(dd, dtype, ebtype, tol_d, s_d, ebtype == MGH_REL ? (double)norm : 0.0, cptr, cfg, hdr);
-      meta = fmt::serialize_metadata(hdr);
-      if (meta.size() != meta_size) return hl_fail(MGH_ERR_FORMAT, "metadata size changed");
-      if (out_dev) {
-        // (out of pinned memory: the copy is queued, not staged synchronously)
-        std::memcpy((char *)g_cache.hpin.p + 64, meta.data(), meta.size());
-        HL_HIP(hipMemcpyAsync(*compressed, (char *)g_cache.hpin.p + 64, meta.size(), hipMemcpyHostToDevice, st));
-      } else {
-        std::memcpy(*compressed, meta.data(), meta.size());
-      }
-    }
-    if (hipStreamSynchronize(st) != hipSuccess) return hl_fail(MGH_ERR_DEVICE, "writing the subdomain record");
-    hl_debug("compress: record written");
+    // the last record takes the header along, with the norm the pipeline computed for a non-decomposed REL run
+    const bool last = id + 1 == dd.num;
+    if (last) header_from(dd, dtype, ebtype, tol_d, s_d, ebtype == MGH_REL ? (double)norm : 0.0, cptr, cfg, hdr);
+    HL_TRY(write_record(L, n, elem, sub_in(id), sink, last ? &hdr : nullptr, meta_size));
     if (J.owned) {
       owned_alive.erase(std::remove(owned_alive.begin(), owned_alive.end(), J.h), owned_alive.end());
       mgh_hierarchy_destroy(J.h);
     }
-    byte_offset += 8 + csize;
     return MGH_SUCCESS;
   };
 
@@ -2169,7 +2219,7 @@ int compress_impl(int D, int dtype, const uint64_t *shape, double tol_d, double 
     if ((rc = finish(jobs[id % nlanes])) != MGH_SUCCESS) return cleanup(rc);
     if (nlanes == 1 && id + 1 < dd.num && (rc = issue(jobs[0], id + 1)) != MGH_SUCCESS) return cleanup(rc);
   }
-  *compressed_size = byte_offset;
+  *compressed_size = sink.byte_offset;
   return cleanup(MGH_SUCCESS);
 }
 
@@ -2749,11 +2799,12 @@ int check_config(const mgh_config *cfg) {
 // with the input (achieved).
 struct SizeEstimator {
   // what the decomposition is for: a size is a function of the histogram under Huffman alone; an
-  // achieved error does not depend on the lossless stage at all
-  enum class Purpose { sizes, errors };
+  // achieved error does not depend on the lossless stage at all, and a ladder takes either
+  enum class Purpose { sizes, errors, ladder };
   int D = 0, dtype = 0, ebtype = 0;
   std::vector<uint64_t> shape_v;
   const void *d_in = nullptr;  // the input on the device: the caller's array, or its upload
+  bool in_dev = false;         // the caller's array is device memory (so is every output the call allocates)
   double s = 0, norm = 1;
   uint64_t n = 0;
   size_t elem = 0;
@@ -2791,7 +2842,9 @@ struct SizeEstimator {
       return hl_fail(MGH_ERR_INVALID_ARGUMENT,
                      purpose == Purpose::sizes
                          ? "size estimates: the configuration decomposes the domain (containers of one subdomain only)"
-                         : "achieved errors: the configuration decomposes the domain (containers of one subdomain only)");
+                     : purpose == Purpose::errors
+                         ? "achieved errors: the configuration decomposes the domain (containers of one subdomain only)"
+                         : "compress_ladder: the configuration decomposes the domain (containers of one subdomain only)");
     n = 1;
     for (int d = 0; d < D; d++) n *= shape[d];
     if (coords_in) {
@@ -2807,8 +2860,9 @@ struct SizeEstimator {
     hipStream_t st = L.st;
     const size_t bytes = n * elem;
     d_in = original;
+    in_dev = is_device_pointer(original);
     bool have_norm = ebtype != MGH_REL;
-    if (!is_device_pointer(original)) {
+    if (!in_dev) {
       HL_TRY(g_cache.in[0].ensure(bytes));
       d_in = g_cache.in[0].p;
       int rc;
@@ -2838,6 +2892,105 @@ struct SizeEstimator {
     if (!have_norm && (rc = mgh_norm(h, d_in, s, &norm, st)) != MGH_SUCCESS) return fail_drained(rc);
     if ((rc = L.q.ensure(std::max<size_t>(bytes, n * 8))) != MGH_SUCCESS) return fail_drained(rc);
     if ((rc = mgh_decompose(h, d_in, L.q.p, st)) != MGH_SUCCESS) return fail_drained(rc);
+    return MGH_SUCCESS;
+  }
+
+  // The second entry into the writer: the container mgh_compress(tol) writes for this array, from the
+  // coefficients begin() left in lane 0's buffer (they survive the call: the next tolerance reads them
+  // again). What compress_impl does for its one subdomain behind the decomposition, in its order:
+  // output, lists, header size, quantizer, lossless_begin, then encode_record / write_record, which
+  // both entries call. The quantizing step:
+  //   - reorder == 0 and the single-pass encoder (lossless_sym16_ok): mgh_quantize_symbols into the
+  //     lane's second buffer, with the histogram into the context's bins where kFusedSymbolHistogram
+  //     says so (DESIGN.md section 8 has the measurement);
+  //   - else mgh_quantize to int64 there and, for reorder == 1, mgh_level_linearize into a third buffer.
+  // Host buffers are not registered here (auto_pin_host_buffers: begin() has moved the input already).
+  static constexpr bool kFusedSymbolHistogram = true;
+  int write(double tol, void **compressed, size_t *compressed_size, bool prealloc) {
+    Lane &L = g_cache.lane[0];
+    hipStream_t st = L.st;
+    // output buffer, same memory space as the input, sized as compress_impl sizes it
+    size_t cap;
+    if (!prealloc) {
+      cap = n * elem + (size_t)1e6;
+      if (in_dev) HL_HIP(hipMalloc(compressed, cap));
+      else if (!(*compressed = host_alloc_large(cap))) return hl_fail(MGH_ERR_OUT_OF_MEMORY, "malloc");
+    } else {
+      cap = *compressed_size;
+    }
+    auto cleanup = [&](int rc) {
+      if (rc == MGH_SUCCESS) return rc;
+      fail_drained(rc);
+      if (!prealloc) {
+        if (in_dev) (void)hipFree(*compressed); else std::free(*compressed);
+        *compressed = nullptr;
+      }
+      return rc;
+    };
+    RecordSink sink;
+    sink.out = *compressed, sink.cap = cap, sink.out_dev = is_device_pointer(*compressed);
+    const uint64_t dict = cfg.huff_dict_size, chunk = cfg.huff_block_size;
+    const bool sym16 = !cfg.reorder && lossless_sym16_ok(dict, chunk) && !qsym_refusal(n, dict);
+    const uint64_t ocap = std::max<uint64_t>(1, (uint64_t)(cfg.estimate_outlier_ratio * (double)n));
+    int rc;
+    if ((rc = L.q2.ensure(sym16 ? n * 2 : n * 8)) != MGH_SUCCESS) return cleanup(rc);
+    if (cfg.reorder && (rc = L.q3.ensure(n * 8)) != MGH_SUCCESS) return cleanup(rc);
+    if ((rc = L.ocount.ensure(8)) != MGH_SUCCESS || (rc = L.oidx.ensure(ocap * 8)) != MGH_SUCCESS ||
+        (rc = L.oval.ensure(ocap * 8)) != MGH_SUCCESS || (rc = L.pin.ensure(64)) != MGH_SUCCESS)
+      return cleanup(rc);
+    L.ocap = std::max(L.ocap, ocap);  // (grow-only buffers: an earlier call may have left more)
+    fmt::Header hdr;
+    header_from(dd, dtype, ebtype, tol, s, ebtype == MGH_REL ? norm : 0.0, cptr, cfg, hdr);
+    const size_t meta_size = fmt::serialize_metadata(hdr).size();
+    if (meta_size > cap) return cleanup(hl_fail(MGH_ERR_OUTPUT_TOO_LARGE, "output buffer too small for the header"));
+    if ((rc = g_cache.hpin.ensure(64 + meta_size)) != MGH_SUCCESS) return cleanup(rc);
+    sink.byte_offset = meta_size;
+
+    LosslessJob lj;
+    auto quantize = [&]() -> int {
+      // (outlier counter of the lane + the lossless stage's bins and chunk states: one launch)
+      HL_TRY(lossless_prepare(L.ll, n, dict, chunk, st, (unsigned long long *)L.ocount.p));
+      if (!L.ll->prepared_n) HL_HIP(hipMemsetAsync(L.ocount.p, 0, 8, st));
+      const bool fused_bins = sym16 && kFusedSymbolHistogram && L.ll->prepared_n != 0;
+      const int64_t *q_enc = (const int64_t *)L.q2.p;
+      if (sym16) {
+        HL_TRY(mgh_quantize_symbols(h, L.q.p, ebtype, tol, s, norm, dict, (uint16_t *)L.q2.p,
+                                    fused_bins ? (uint32_t *)L.ll->freq.p : nullptr, (uint64_t *)L.ocount.p,
+                                    (uint64_t *)L.oidx.p, (int64_t *)L.oval.p, L.ocap, st));
+      } else {
+        HL_TRY(mgh_quantize(h, L.q.p, ebtype, tol, s, norm, dict, 1, (int64_t *)L.q2.p, (uint64_t *)L.ocount.p,
+                            (uint64_t *)L.oidx.p, (int64_t *)L.oval.p, L.ocap, st));
+        if (cfg.reorder) {
+          // config.reorder == 1: the lossless stage sees the integers level by level, outlier
+          // indices are positions in that array (as in compress_impl)
+          HL_TRY(mgh_level_linearize(h, (const int64_t *)L.q2.p, (int64_t *)L.q3.p, 0, (uint64_t *)L.oidx.p,
+                                     (const uint64_t *)L.ocount.p, 0, L.ocap, st));
+          q_enc = (const int64_t *)L.q3.p;
+        }
+      }
+      compress_stats().quantize_passes++;
+      if (!fused_bins) compress_stats().histogram_launches++;
+      lj = LosslessJob();
+      lj.d_q = q_enc;
+      lj.n = n;
+      lj.dict = dict;
+      lj.chunk = chunk;
+      lj.lossless = cfg.lossless;
+      lj.zstd_level = cfg.zstd_compress_level;
+      lj.d_oidx = (const uint64_t *)L.oidx.p;
+      lj.d_oval = (const int64_t *)L.oval.p;
+      lj.ocount = 0;  // (read back together with the encoder's results)
+      lj.d_ocount = (const uint64_t *)L.ocount.p;
+      lj.ocap = L.ocap;
+      lj.cap_units = n * elem / 8 + 1;
+      lj.sym16 = sym16;
+      lj.bins_filled = fused_bins;
+      return lossless_begin(L.ll, lj, st);
+    };
+    if ((rc = quantize()) != MGH_SUCCESS) return cleanup(rc);
+    if ((rc = encode_record(L, lj, sink, quantize)) != MGH_SUCCESS) return cleanup(rc);
+    if ((rc = write_record(L, n, elem, d_in, sink, &hdr, meta_size)) != MGH_SUCCESS) return cleanup(rc);
+    *compressed_size = sink.byte_offset;
     return MGH_SUCCESS;
   }
 
@@ -2995,7 +3148,9 @@ int mgh_compress_budget(int D, int dtype, const uint64_t *shape, size_t max_byte
   mgh_size_estimate used{};
   try {
     SizeEstimator E;
+    compress_stats() = mgh_compress_stats{};
     HL_TRY(E.begin(D, dtype, shape, s, ebtype, original_data, coords, *config));
+    compress_stats().decompositions++;
     int rc = MGH_SUCCESS;
     std::vector<mgh_size_estimate> seen;  // every candidate priced, in order
     auto fits3 = [&](const double m[3], bool ok[3]) {
@@ -3021,22 +3176,21 @@ int mgh_compress_budget(int D, int dtype, const uint64_t *shape, size_t max_byte
     *tol_used = r.tol;
     for (const mgh_size_estimate &e : seen)
       if (e.tol == r.tol) used = e;
+    if (estimate_used) *estimate_used = used;
+    // the container of tol_used from the coefficients the candidates were priced on (SizeEstimator::write)
+    void *const given = *compressed_data;
+    HL_TRY(E.write(*tol_used, compressed_data, compressed_size, output_pre_allocated != 0));
+    if (*compressed_size > max_bytes) {  // (the bracket is an invariant of the record's layout: never expected)
+      if (!output_pre_allocated) {
+        if (is_device_pointer(*compressed_data)) (void)hipFree(*compressed_data); else std::free(*compressed_data);
+        *compressed_data = given;
+      }
+      return hl_fail(MGH_ERR_FORMAT, "compress_budget: the container left the estimate's bracket");
+    }
+    return MGH_SUCCESS;
   } catch (const std::exception &e) {
     return hl_fail(MGH_ERR_DEVICE, e.what());
   }
-  if (estimate_used) *estimate_used = used;
-  // the writer itself, untouched: a second decomposition (its fused pass) is the price
-  void *const given = *compressed_data;
-  HL_TRY(mgh_compress(D, dtype, shape, *tol_used, s, ebtype, original_data, compressed_data, compressed_size, coords,
-                      config, output_pre_allocated));
-  if (*compressed_size > max_bytes) {  // (the bracket is an invariant of the record's layout: never expected)
-    if (!output_pre_allocated) {
-      if (is_device_pointer(*compressed_data)) (void)hipFree(*compressed_data); else std::free(*compressed_data);
-      *compressed_data = given;
-    }
-    return hl_fail(MGH_ERR_FORMAT, "compress_budget: the container left the estimate's bracket");
-  }
-  return MGH_SUCCESS;
 }
 
 int mgh_achieved_errors(int D, int dtype, const uint64_t *shape, int ntol, const double *tols, double s, int ebtype,
@@ -3070,7 +3224,9 @@ int mgh_compress_target(int D, int dtype, const uint64_t *shape, int metric, dou
   int evaluated = 0;
   try {
     SizeEstimator E;
+    compress_stats() = mgh_compress_stats{};
     HL_TRY(E.begin(D, dtype, shape, s, ebtype, original_data, coords, *config, SizeEstimator::Purpose::errors));
+    compress_stats().decompositions++;
     int rc = MGH_SUCCESS;
     std::vector<std::pair<double, mgh_error_stats>> seen;  // every candidate evaluated, in order
     auto meets = [&](double tol) {
@@ -3089,14 +3245,58 @@ int mgh_compress_target(int D, int dtype, const uint64_t *shape, int metric, dou
     evaluated = r.candidates;
     for (const auto &c : seen)
       if (c.first == r.tol) used = c.second;
+    if (stats_used) *stats_used = used;
+    if (candidates) *candidates = evaluated;
+    // the container of tol_used from the coefficients the candidates share (SizeEstimator::write)
+    return E.write(*tol_used, compressed_data, compressed_size, output_pre_allocated != 0);
   } catch (const std::exception &e) {
     return hl_fail(MGH_ERR_DEVICE, e.what());
   }
-  if (stats_used) *stats_used = used;
-  if (candidates) *candidates = evaluated;
-  // the writer itself, untouched: a second decomposition (its fused pass) is the price
-  return mgh_compress(D, dtype, shape, *tol_used, s, ebtype, original_data, compressed_data, compressed_size, coords,
-                      config, output_pre_allocated);
+}
+
+int mgh_compress_ladder(int D, int dtype, const uint64_t *shape, int ntol, const double *tols, double s, int ebtype,
+                        const void *original_data, void **compressed_data, size_t *compressed_size,
+                        const void *const *coords, const mgh_config *config, int output_pre_allocated) {
+  if (!tols || !compressed_data || !compressed_size) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (ntol < 1 || ntol > kLadderMaxTols) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "compress_ladder: ntol must be in 1..64");
+  for (int k = 0; k < ntol; k++) {
+    if (!(tols[k] > 0) || !std::isfinite(tols[k]))
+      return hl_fail(MGH_ERR_INVALID_ARGUMENT, "compress_ladder: every tolerance must be positive and finite");
+    if (output_pre_allocated && !compressed_data[k]) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "pre-allocated output is NULL");
+  }
+  HL_TRY(size_call_args(D, dtype, shape, ebtype, original_data, config));
+  if (!output_pre_allocated)
+    for (int k = 0; k < ntol; k++) compressed_data[k] = nullptr;
+  try {
+    SizeEstimator E;
+    compress_stats() = mgh_compress_stats{};
+    HL_TRY(E.begin(D, dtype, shape, s, ebtype, original_data, coords, *config, SizeEstimator::Purpose::ladder));
+    compress_stats().decompositions++;
+    // (a failure at tolerance k leaves containers 0 .. k-1 the caller's; write() has freed its own)
+    for (int k = 0; k < ntol; k++)
+      HL_TRY(E.write(tols[k], &compressed_data[k], &compressed_size[k], output_pre_allocated != 0));
+    return MGH_SUCCESS;
+  } catch (const std::exception &e) {
+    return hl_fail(MGH_ERR_DEVICE, e.what());
+  }
+}
+
+int mgh_last_compress_stats(mgh_compress_stats *out) {
+  if (!out) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "NULL argument");
+  *out = compress_stats();
+  return MGH_SUCCESS;
+}
+
+int mgh_histogram_sym16(const uint16_t *d_symbols, uint64_t n, uint64_t dict_size, uint32_t *d_freq, void *stream) {
+  if (!d_symbols || !d_freq) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (n == 0 || n >= ((uint64_t)1 << 32) || dict_size < 2 || dict_size > 16384)
+    return hl_fail(MGH_ERR_INVALID_ARGUMENT, "histogram_sym16: 1 .. 2^32 - 1 symbols, dict_size in 2..16384");
+  const unsigned hblocks =
+      (unsigned)std::min<size_t>((n + huff::kHistThreads - 1) / huff::kHistThreads, 2 * (size_t)hl_num_cu());
+  huff::k_histogram<uint16_t><<<hblocks, huff::kHistThreads, dict_size * 4, (hipStream_t)stream>>>(
+      d_symbols, n, (int)dict_size, (unsigned *)d_freq);
+  HL_HIP(hipGetLastError());
+  return MGH_SUCCESS;
 }
 
 static int decompress_entry(const void *compressed_data, size_t compressed_size, void **decompressed_data,

@@ -89,6 +89,15 @@ inline int qhist_per_launch(uint64_t dict, int k_left) {
   return (int)std::min<uint64_t>({(uint64_t)std::max(k_left, 0), fit, (uint64_t)kQhistMaxPerLaunch});
 }
 
+// k_quantize_symbols keeps one histogram in LDS, 64 KB at the largest dictionary; the symbols are 16 bits
+// wide and the dictionary is centred on dict / 2, so an odd one is refused. (nullptr: nothing refused)
+constexpr uint64_t kQsymLdsBytes = 64 * 1024;
+inline const char *qsym_refusal(uint64_t total, uint64_t dict) {
+  if (total == 0 || total >= ((uint64_t)1 << 32)) return "quantize_symbols: 1 .. 2^32 - 1 elements (32-bit index arithmetic and counters)";
+  if (dict < 2 || dict > 16384 || (dict & 1)) return "quantize_symbols: dict_size must be even and in 2..16384";
+  return nullptr;
+}
+
 // ---- the search ------------------------------------------------------------------------------------
 // The largest accuracy (smallest tolerance) in [tol_min, tol_max] that fits, on a logarithmic grid:
 // tol_min if it fits; else a bracket [a, b], a does not fit, b fits, narrowed `rounds` times to a

@@ -35,6 +35,7 @@ HL_SYMBOLS = [
     "mgh_verify",
     "mgh_estimate_sizes", "mgh_compress_budget",
     "mgh_achieved_errors", "mgh_compress_target",
+    "mgh_compress_ladder", "mgh_last_compress_stats", "mgh_histogram_sym16",
 ]
 
 
@@ -78,6 +79,13 @@ class DecompressStats(C.Structure):
     _fields_ = [("subdomains", C.c_uint64), ("chunks_total", C.c_uint64), ("chunks_decoded", C.c_uint64),
                 ("symbols_decoded", C.c_uint64), ("record_bytes", C.c_uint64),
                 ("record_bytes_moved", C.c_uint64)]
+
+
+class CompressStats(C.Structure):
+    """mgh_compress_stats: what the last compress / compress_budget / compress_target / compress_ladder call
+    of this thread did."""
+    _fields_ = [("decompositions", C.c_uint64), ("quantize_passes", C.c_uint64), ("histogram_launches", C.c_uint64),
+                ("records", C.c_uint64), ("raw_records", C.c_uint64), ("outlier_retries", C.c_uint64)]
 
 
 class VerifyResult(C.Structure):
@@ -209,6 +217,11 @@ def _hl():
     L.mgh_progressive_close.argtypes = [vp]
     L.mgh_progressive_close.restype = None
     L.mgh_last_decompress_stats.argtypes = [C.POINTER(DecompressStats)]
+    L.mgh_last_compress_stats.argtypes = [C.POINTER(CompressStats)]
+    L.mgh_compress_ladder.argtypes = [C.c_int, C.c_int, C.POINTER(u64), C.c_int, C.POINTER(C.c_double), C.c_double,
+                                      C.c_int, vp, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(vp),
+                                      C.POINTER(Config), C.c_int]
+    L.mgh_histogram_sym16.argtypes = [vp, u64, u64, vp, vp]
     L.mgh_memcpy.argtypes = [vp, vp, C.c_size_t]
     L.mgh_huffman_codebook.argtypes = [vp, u64, vp, vp, vp, vp]
     _declared = True
@@ -437,6 +450,41 @@ def compress_target(data, metric, target, tol_min, tol_max, rounds=8, s=INF, mod
                                  float(tol_max), int(rounds), float(s), int(mode), ptr, C.byref(optr), C.byref(size), cptr,
                                  C.byref(cfg), 1, C.byref(used), C.byref(stats), C.byref(cand)))
     return out[:size.value], used.value, stats, cand.value
+
+
+def compress_ladder(data, tols, s=INF, mode=REL, coords=None, config=None, outs=None):
+    """mgh_compress_ladder: [compress(data, tol, ...) for tol in tols] (1..64 tolerances, up to the order of
+    the outlier lists) from ONE decomposition of `data` -- numpy uint8 arrays (host input) or cuda uint8
+    tensors (device input). Containers of one subdomain. `outs`: optional pre-allocated uint8 buffers of
+    the same kind, one per tolerance (their sizes are the capacities); when a tolerance fails the call
+    raises, and the buffers of the tolerances before it hold their containers."""
+    import torch
+    L = _hl()
+    cfg = config if config is not None else Config()
+    ptr, dt, shape, keep = _as_ptr(data)
+    D = len(shape)
+    tols = [float(t) for t in tols]
+    k = len(tols)
+    cptr, ckeep = _coords_ptr(coords, dt, D)
+    on_device = isinstance(data, torch.Tensor) and data.is_cuda
+    cap = int(np.prod(shape)) * (4 if dt == FLOAT else 8) + 1000000
+    if outs is None:
+        outs = [torch.empty(cap, dtype=torch.uint8, device=data.device) if on_device else np.empty(cap, dtype=np.uint8)
+                for _ in range(k)]
+    assert len(outs) == k, "one output buffer per tolerance"
+    optr = (C.c_void_p * max(k, 1))(*[o.data_ptr() if on_device else o.ctypes.data for o in outs])
+    sizes = (C.c_size_t * max(k, 1))(*[int(o.numel()) if on_device else int(o.size) for o in outs])
+    _check(L.mgh_compress_ladder(D, dt, (C.c_uint64 * D)(*shape), k, (C.c_double * max(k, 1))(*tols), float(s),
+                                 int(mode), ptr, optr, sizes, cptr, C.byref(cfg), 1))
+    return [o[:sizes[i]] for i, o in enumerate(outs)]
+
+
+def last_compress_stats():
+    """mgh_last_compress_stats as a dict: decompositions, quantize_passes, histogram_launches, records,
+    raw_records, outlier_retries of the last writing call of this thread."""
+    st = CompressStats()
+    _check(_hl().mgh_last_compress_stats(C.byref(st)))
+    return {k: int(getattr(st, k)) for k, _ in CompressStats._fields_}
 
 
 def infer(buf):
