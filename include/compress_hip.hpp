@@ -237,6 +237,38 @@ inline compress_status_type compress_ladder(DIM D, data_type dtype, std::vector<
                                             original_data, compressed_data.data(), compressed_size.data(),
                                             cp.empty() ? nullptr : cp.data(), &c, output_pre_allocated ? 1 : 0));
 }
+// EXTENSION: mgh_compress_layers. compressed_data[k]: the layer of tols[k] (strictly decreasing, 1..64) --
+// what the layers before it left of the coefficients, quantized at tols[k]; layer 0 is compress(tols[0])'s
+// container. Vectors, allocation and the failure at layer k as in compress_ladder. Containers of one
+// subdomain, reorder = 0 (Failure otherwise; mgh_last_error() says so). The order of the layers is the
+// caller's to keep: the containers carry no index.
+inline compress_status_type compress_layers(DIM D, data_type dtype, std::vector<SIZE> shape,
+                                            const std::vector<double> &tols, double s, error_bound_type mode,
+                                            const void *original_data, std::vector<void *> &compressed_data,
+                                            std::vector<size_t> &compressed_size, std::vector<const Byte *> coords,
+                                            HighLevelConfig config, bool output_pre_allocated) {
+  if (shape.size() != D) return compress_status_type::Failure;
+  if (output_pre_allocated && (compressed_data.size() != tols.size() || compressed_size.size() != tols.size()))
+    return compress_status_type::Failure;
+  if (!output_pre_allocated) {
+    compressed_data.assign(tols.size(), nullptr);
+    compressed_size.assign(tols.size(), 0);
+  }
+  const mgh_config c = detail::to_c(config);
+  std::vector<const void *> cp(coords.begin(), coords.end());
+  return detail::status(mgh_compress_layers(D, (int)dtype, shape.data(), (int)tols.size(), tols.data(), s, (int)mode,
+                                            original_data, compressed_data.data(), compressed_size.data(),
+                                            cp.empty() ? nullptr : cp.data(), &c, output_pre_allocated ? 1 : 0));
+}
+// ... and its one-shot reader (mgh_decompress_layers): the array after layers 0 .. size() - 1, in order.
+inline compress_status_type decompress_layers(const std::vector<const void *> &compressed_data,
+                                              const std::vector<size_t> &compressed_size, void *&decompressed_data,
+                                              HighLevelConfig config, bool output_pre_allocated) {
+  if (compressed_data.size() != compressed_size.size()) return compress_status_type::Failure;
+  const mgh_config c = detail::to_c(config);
+  return detail::status(mgh_decompress_layers((int)compressed_data.size(), compressed_data.data(), compressed_size.data(),
+                                              &c, &decompressed_data, output_pre_allocated ? 1 : 0));
+}
 // EXTENSION: mgh_achieved_errors. What verify(compress(tol)) would report for every tolerance of `tols`
 // (1..64), from one decomposition and without writing a container. Containers of one subdomain (Failure
 // otherwise; mgh_last_error() says so); any supported lossless_type.
@@ -376,6 +408,27 @@ public:
 
 private:
   mgh_progressive *p_ = nullptr;
+};
+// EXTENSION: the stateful reader of precision layers (mgh_layers): layer 0 at construction, then add() per
+// layer in the writer's order, data() whenever an array is wanted. The containers are not kept.
+class LayersReader {
+public:
+  LayersReader(const void *layer0, size_t size, HighLevelConfig config = HighLevelConfig()) {
+    const mgh_config c = detail::to_c(config);
+    check(mgh_layers_open(&p_, layer0, size, &c), "LayersReader");
+  }
+  ~LayersReader() { mgh_layers_close(p_); }
+  LayersReader(const LayersReader &) = delete;
+  LayersReader &operator=(const LayersReader &) = delete;
+  int count() const { return mgh_layers_count(p_); }
+  double tolerance() const { return mgh_layers_tolerance(p_); }
+  compress_status_type add(const void *layer, size_t size) { return detail::status(mgh_layers_add(p_, layer, size)); }
+  compress_status_type data(void *&out, bool output_pre_allocated) {
+    return detail::status(mgh_layers_data(p_, &out, output_pre_allocated ? 1 : 0));
+  }
+
+private:
+  mgh_layers *p_ = nullptr;
 };
 inline compress_status_type decompress(const void *compressed_data, size_t compressed_size,
                                        void *&decompressed_data, std::vector<SIZE> &shape,

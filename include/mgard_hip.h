@@ -245,6 +245,31 @@ int mgh_quantize_symbols(mgh_hierarchy *h, const void *d_coeff, int error_bound_
                          uint64_t *d_outlier_count, uint64_t *d_outlier_idx, int64_t *d_outlier_val,
                          uint64_t outlier_capacity, void *stream);
 
+/* mgh_quantize_symbols with one more output (precision layers): everything
+ * mgh_quantize_symbols writes, for the same arguments and on the same terms (the caller zeroes the bins and
+ * the counter, the refusals, MGH_LD_IN), and in addition
+ *   d_residual_out[i] = d_coeff[i] - (what mgh_dequantize writes at i for these integers and this bound),
+ * bit for bit: the dequantizer's own expression on its own tables, then one IEEE subtraction. At an
+ * outlier's position the integer is the one in the list, not the symbol 0 stored in its place.
+ * d_residual_out is DENSE (MGH_LD_OUT is not honoured), of the hierarchy's type, never NULL, and may be
+ * d_coeff (in place) when that is dense. Quantizing d_residual_out at a smaller tolerance gives the next
+ * layer. ASYNCHRONOUS behind the upload of the quantizer tables. No reference counterpart. */
+int mgh_quantize_symbols_residual(mgh_hierarchy *h, const void *d_coeff, int error_bound_type, double tol, double s,
+                                  double norm, uint64_t dict_size, uint16_t *d_symbols, uint32_t *d_freq_or_null,
+                                  uint64_t *d_outlier_count, uint64_t *d_outlier_idx, int64_t *d_outlier_val,
+                                  uint64_t outlier_capacity, void *d_residual_out, void *stream);
+
+/* The reader's side of it: d_coeff_inout[i] = (first ? nothing : d_coeff_inout[i]) + what mgh_dequantize
+ * writes at i for d_quantized, the outlier list and this bound -- `first` STORES that value (bit for bit
+ * mgh_dequantize's output), otherwise it is added with one IEEE addition. d_quantized is int64 (a 16-bit
+ * symbol input is not taken); like mgh_dequantize the call writes the outliers back into it first, so it
+ * is modified. d_coeff_inout is DENSE (MGH_LD_OUT is not honoured). Arrays of 2^32 elements and more are
+ * refused (MGH_ERR_INVALID_ARGUMENT). ASYNCHRONOUS behind the upload of the quantizer table. */
+int mgh_dequantize_add(mgh_hierarchy *h, int64_t *d_quantized, int error_bound_type, double tol, double s,
+                       double norm, uint64_t dict_size, int prep_huffman, const uint64_t *d_outlier_idx,
+                       const int64_t *d_outlier_val, uint64_t outlier_count, int first, void *d_coeff_inout,
+                       void *stream);
+
 /* Norm that stays on the device: writes one value of the hierarchy's dtype to
  * d_norm_out (max|x| for s = +inf, else the L2 norm of this array as
  * norm_calculator defines it). ASYNCHRONOUS. For a decomposed domain the caller

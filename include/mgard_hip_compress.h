@@ -196,8 +196,38 @@ int mgh_compress_ladder(int D, int dtype, const uint64_t *shape, int ntol, const
                         size_t *compressed_size /* [ntol] */, const void *const *coords, const mgh_config *config,
                         int output_pre_allocated);
 
+/* ---- One array as precision LAYERS: containers that refine it, tolerance by tolerance (extension) -----
+ * The tiers of a ladder are independent: each stores again what the coarser ones hold. Here
+ * compressed_data[k] stores what layers 0 .. k-1 left: the decomposition is linear and does not depend on
+ * the tolerance, so with r_0 the coefficients,
+ *   q_k = quantize(r_k; tols[k])   (the level quantizers of tols[k], as mgh_quantize),
+ *   r_{k+1} = r_k - dequantize(q_k; tols[k]),
+ * and a reader adds dequantize(q_0) + ... + dequantize(q_k) before ONE recomposition (mgh_layers_*,
+ * mgh_decompress_layers). After k layers every coefficient is off by at most half the level quantum of
+ * tols[k] -- the error model of mgh_compress(tols[k]).
+ * Every layer is an ordinary container of one subdomain with the header of tols[k]: compressed_data[0]
+ * is the container mgh_compress(tols[0]) writes (up to the order of its outlier list), and a stock reader
+ * decodes a later layer to a correction field. The containers carry NO layer index: their order is the
+ * caller's to keep.
+ * Arguments, outputs and the failure at layer k (containers 0 .. k-1 stay valid and the caller's) as in
+ * mgh_compress_ladder. MGH_ERR_INVALID_ARGUMENT, before anything is allocated: ntol outside 1..64; a
+ * tolerance that is not positive and finite; tolerances that are not STRICTLY DECREASING; a configuration
+ * that decomposes the domain; config->reorder == 1; a huff_dict_size that is odd or outside 2..16384, or
+ * one that, with huff_block_size, the single-pass encoder does not take; arrays of 2^32 elements and more.
+ * A layer that would be stored RAW (the record is not smaller than the array: a tolerance below the
+ * noise of the data) ends the call with MGH_ERR_INVALID_ARGUMENT, "compress_layers: layer k would be
+ * stored raw". Either lossless type. Device memory: the coefficient array TWICE (a layer's residual must
+ * not overwrite the coefficients it was made from until its record is written: an outlier overflow
+ * quantizes them again) and the symbols (2 bytes an element), in buffers of the pipeline.
+ * mgh_last_compress_stats: decompositions 1, records ntol, raw_records 0, quantize_passes ntol +
+ * outlier_retries. */
+int mgh_compress_layers(int D, int dtype, const uint64_t *shape, int ntol, const double *tols, double s,
+                        int error_bound_type, const void *original_data, void **compressed_data /* [ntol] */,
+                        size_t *compressed_size /* [ntol] */, const void *const *coords, const mgh_config *config,
+                        int output_pre_allocated);
+
 /* What the last WRITING call of the calling thread did (mgh_compress, mgh_compress_budget,
- * mgh_compress_target, mgh_compress_ladder; thread-local; zeros before the first call; a failed call
+ * mgh_compress_target, mgh_compress_ladder, mgh_compress_layers; thread-local; zeros before the first call; a failed call
  * leaves what it had counted). */
 typedef struct mgh_compress_stats {
   uint64_t decompositions;     /* passes that turned data into coefficients (one per subdomain of
@@ -590,6 +620,30 @@ int mgh_progressive_preview(mgh_progressive *p, void **data, int output_pre_allo
 int mgh_progressive_preview_window(mgh_progressive *p, const uint64_t *lo, const uint64_t *ext, void **data,
                                    int output_pre_allocated);
 void mgh_progressive_close(mgh_progressive *p);
+
+/* ---- Reader of precision layers (EXTENSION; the containers of mgh_compress_layers) -------------------
+ * A handle keeps the coefficients of the array, as the layers added so far give them, on the device
+ * (one array of the data's type). open takes layer 0, add the NEXT layer -- the containers carry no
+ * index, the order is the caller's -- and each costs a decode and one stream over the coefficients
+ * (mgh_dequantize_add); nothing is recomposed until mgh_layers_data, which runs mgh_recompose into an
+ * array in the memory space of layer 0's container, or into the caller's buffer, and leaves the handle as
+ * it was: more layers may follow. The containers are not kept: they may go away when the call returns.
+ * add refuses with MGH_ERR_INVALID_ARGUMENT, and leaves the handle as it was, a container whose shape,
+ * data type, coordinates, bound type, s, header norm or decomposition are not layer 0's, whose tolerance
+ * is not below the last layer's, whose record is RAW, that was written with reorder = 1 or that has more
+ * than one subdomain (open refuses the last three). count: layers added (-1 for NULL); tolerance: the
+ * last layer's (the header's). mgh_decompress_layers is open, add ... add, data, close in one call;
+ * nlayers in 1..64. After one layer the data is mgh_decompress's of that container, bit for bit. */
+typedef struct mgh_layers mgh_layers;
+int mgh_layers_open(mgh_layers **out, const void *compressed_data, size_t compressed_size, const mgh_config *config);
+int mgh_layers_add(mgh_layers *p, const void *compressed_data, size_t compressed_size);
+int mgh_layers_count(const mgh_layers *p);
+double mgh_layers_tolerance(const mgh_layers *p);
+int mgh_layers_data(mgh_layers *p, void **data, int output_pre_allocated);
+void mgh_layers_close(mgh_layers *p);
+int mgh_decompress_layers(int nlayers, const void *const *compressed_data /* [nlayers] */,
+                          const size_t *compressed_size /* [nlayers] */, const mgh_config *config,
+                          void **decompressed_data, int output_pre_allocated);
 
 #ifdef __cplusplus
 }

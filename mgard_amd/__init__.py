@@ -29,7 +29,7 @@ SYMBOLS = [
     "mgh_profile_enable", "mgh_profile_filter", "mgh_profile_read", "mgh_stream_calibrate",
     "mgh_level_linearize", "mgh_outlier_restore", "mgh_norm_stream_begin", "mgh_norm_stream_add",
     "mgh_norm_stream_end", "mgh_quantize_histograms", "mgh_quantize_roundtrip",
-    "mgh_quantize_symbols",
+    "mgh_quantize_symbols", "mgh_quantize_symbols_residual", "mgh_dequantize_add",
     "mgh_set_ld",
     "mgh_recompose_to_level", "mgh_dequantize_recompose_to_level",
     "mgh_dequantize_recompose_sym16_to_level", "mgh_level_nodes",
@@ -127,6 +127,10 @@ def load_library():
     L.mgh_quantize_roundtrip.argtypes = [vp, vp, C.c_int, C.c_double, C.c_double, C.c_double, vp, vp]
     L.mgh_quantize_symbols.argtypes = [vp, vp, C.c_int, C.c_double, C.c_double, C.c_double, u64, vp, vp, vp, vp, vp,
                                        u64, vp]
+    L.mgh_quantize_symbols_residual.argtypes = [vp, vp, C.c_int, C.c_double, C.c_double, C.c_double, u64, vp, vp, vp, vp,
+                                                vp, u64, vp, vp]
+    L.mgh_dequantize_add.argtypes = [vp, vp, C.c_int, C.c_double, C.c_double, C.c_double, u64, C.c_int, vp, vp, u64,
+                                     C.c_int, vp, vp]
     L.mgh_dequantize_recompose_sym16.argtypes = [vp, vp, C.c_int, C.c_double, C.c_double, C.c_double, u64,
                                                  vp, vp, u64, vp, vp]
     L.mgh_sym16_supported.argtypes = [vp]
@@ -521,6 +525,46 @@ class Hierarchy:
             C.c_void_p(idx.data_ptr()), C.c_void_p(val.data_ptr()), cap, _stream()))
         k = min(int(cnt.item()), cap)
         return sym, freq, idx[:k], val[:k]
+
+    def quantize_symbols_residual(self, coeff, ebtype, tol, s, norm, dict_size=8192, histogram=True, outlier_cap=None,
+                                  out=None):
+        """mgh_quantize_symbols_residual: quantize_symbols' (symbols, freq or None, outlier_idx, outlier_val) and,
+        fifth, the residual `coeff - dequantize(those integers)`, bit for bit, from the same pass -- what the
+        next precision layer quantizes. `out`: a dense tensor of the hierarchy's shape and type for the
+        residual; it may be `coeff` itself (in place)."""
+        import torch
+        cap = self.total if outlier_cap is None else int(outlier_cap)
+        sym = torch.empty(self.shape, dtype=torch.uint16, device=coeff.device)
+        freq = torch.zeros(int(dict_size), dtype=torch.int32, device=coeff.device) if histogram else None
+        if out is None:
+            out = torch.empty(self.shape, dtype=self.torch_dtype, device=coeff.device)
+        assert out.is_cuda and out.is_contiguous() and out.numel() == self.total, "bad tensor"
+        assert out.dtype == self.torch_dtype and out.device.index == self.device, "bad tensor"
+        cnt, idx, val = self._outlier_bufs(cap)
+        _check(load_library().mgh_quantize_symbols_residual(
+            self._h, self._chk(coeff), int(ebtype), tol, s, norm, int(dict_size), C.c_void_p(sym.data_ptr()),
+            C.c_void_p(freq.data_ptr()) if histogram else None, C.c_void_p(cnt.data_ptr()),
+            C.c_void_p(idx.data_ptr()), C.c_void_p(val.data_ptr()), cap, C.c_void_p(out.data_ptr()), _stream()))
+        k = min(int(cnt.item()), cap)
+        return sym, freq, idx[:k], val[:k], out
+
+    def dequantize_add(self, q, ebtype, tol, s, norm, dict_size=8192, prep_huffman=True, outlier_idx=None,
+                       outlier_val=None, acc=None):
+        """mgh_dequantize_add: acc = None -- a new tensor that holds dequantize(q, ...), bit for bit; else
+        `acc` (dense, the hierarchy's shape and type) with that value added to it in place. Like dequantize
+        the call writes the outliers back into `q`."""
+        import torch
+        first = acc is None
+        if first:
+            acc = torch.empty(self.shape, dtype=self.torch_dtype, device=q.device)
+        assert acc.is_cuda and acc.is_contiguous() and acc.numel() == self.total, "bad tensor"
+        assert acc.dtype == self.torch_dtype and acc.device.index == self.device, "bad tensor"
+        n = 0 if outlier_idx is None else int(outlier_idx.numel())
+        _check(load_library().mgh_dequantize_add(
+            self._h, self._chk(q, torch.int64), int(ebtype), tol, s, norm, int(dict_size), int(prep_huffman),
+            C.c_void_p(outlier_idx.data_ptr() if n else 0), C.c_void_p(outlier_val.data_ptr() if n else 0), n,
+            int(first), C.c_void_p(acc.data_ptr()), _stream()))
+        return acc
 
     def decompose_quantize_sym16(self, data, ebtype, tol, s, norm=0.0, dict_size=8192, outlier_cap=None):
         """mgh_decompose_quantize_sym16: (symbols uint16, outlier_idx, outlier_val, count, norm)."""

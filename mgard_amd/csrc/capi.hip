@@ -50,6 +50,7 @@
 #include "target_plan.hpp"
 #include "kernels_qround.hpp"
 #include "kernels_qsym.hpp"
+#include "kernels_qres.hpp"
 
 namespace {
 
@@ -2961,17 +2962,16 @@ int quantize_histograms_impl(mgh_hierarchy *h, const T *coeff, Layout in, int eb
   return MGH_SUCCESS;
 }
 
-// mgh_quantize_roundtrip: the table of mgh_quantize (upload_quantizers, reciprocal) and the table of
-// mgh_dequantize (upload_quantizers, not reciprocal) side by side, made by the same host code, then one
-// streaming launch. The output is dense.
+// The table of mgh_quantize (upload_quantizers, reciprocal) and the table of mgh_dequantize
+// (upload_quantizers, not reciprocal) side by side in ds->qr_tab, made by the same host code: what the
+// kernels that quantize and dequantize in one pass read (k_quantize_roundtrip,
+// k_quantize_symbols_residual). `qm`: the hierarchy's quantizer metadata for this s.
 template <typename T>
-int quantize_roundtrip_impl(mgh_hierarchy *h, const T *coeff, Layout in, const Bound &b, double norm, T *out,
-                            hipStream_t st) {
+int upload_roundtrip_tables(mgh_hierarchy *h, const Bound &b, double norm, QuantMeta &qm, hipStream_t st) {
   auto *ds = DS<T>(h);
   auto *hh = HH<T>(h);
   const int nlev = h->L + 1;
   if (nlev > kMaxLevels) return fail(MGH_ERR_INVALID_ARGUMENT, "too many levels");
-  TRY(ld_pack<T>(h, coeff, in, false, st));
   std::vector<T> tab((size_t)4 * nlev);
   hh->quantizers(b.ebtype, (T)b.tol, (T)b.s, (T)norm, true, tab.data());
   hh->quantizers(b.ebtype, (T)b.tol, (T)b.s, (T)norm, false, tab.data() + 2 * nlev);
@@ -2984,8 +2984,21 @@ int quantize_roundtrip_impl(mgh_hierarchy *h, const T *coeff, Layout in, const B
   // pageable-memory async copies are staged by the runtime before returning
   HIP_TRY(hipMemcpyAsync(ds->qr_tab, tab.data(), tab.size() * sizeof(T), hipMemcpyHostToDevice, st));
   HIP_TRY(hipStreamSynchronize(st));
-  QuantMeta qm = ds->qmeta;
+  qm = ds->qmeta;
   qm.calc_vol = calc_vol ? 1 : 0;
+  return MGH_SUCCESS;
+}
+
+// mgh_quantize_roundtrip: the four tables, then one streaming launch. The output is dense.
+template <typename T>
+int quantize_roundtrip_impl(mgh_hierarchy *h, const T *coeff, Layout in, const Bound &b, double norm, T *out,
+                            hipStream_t st) {
+  auto *ds = DS<T>(h);
+  const int nlev = h->L + 1;
+  if (nlev > kMaxLevels) return fail(MGH_ERR_INVALID_ARGUMENT, "too many levels");
+  TRY(ld_pack<T>(h, coeff, in, false, st));
+  QuantMeta qm;
+  TRY(upload_roundtrip_tables<T>(h, b, norm, qm, st));
   // a pure stream: workgroups of 256 threads, one 16-byte vector per thread and trip, at most eight
   // workgroups per compute unit, which stride over the rest
   const size_t total = h->total, per_wg = (size_t)kQrThreads * Vec16<T>::N;
@@ -3024,6 +3037,59 @@ int quantize_symbols_impl(mgh_hierarchy *h, const T *coeff, Layout in, const Bou
       k_quantize_symbols<T, false><<<grid, kQsThreads, 0, st>>>(
           ds->qmeta, total, coeff, ds->marks, ds->qz, nlev, (int)dict, sym, nullptr, (unsigned long long *)qo.ocount,
           qo.oidx, qo.oval, (unsigned long long)qo.ocap);
+  });
+}
+
+// mgh_quantize_symbols_residual: the four tables of the round trip, then one launch of
+// k_quantize_symbols_residual, sized as quantize_symbols_impl sizes its own. The caller has zeroed the
+// counter and the bins. The residual is dense.
+template <typename T>
+int quantize_symbols_residual_impl(mgh_hierarchy *h, const T *coeff, Layout in, const Bound &b, double norm,
+                                   uint64_t dict, uint16_t *sym, uint32_t *freq, const QuantOut &qo, T *residual,
+                                   hipStream_t st) {
+  auto *ds = DS<T>(h);
+  const int nlev = h->L + 1;
+  if (nlev > kMaxLevels) return fail(MGH_ERR_INVALID_ARGUMENT, "too many levels");
+  TRY(ld_pack<T>(h, coeff, in, false, st));
+  QuantMeta qm;
+  TRY(upload_roundtrip_tables<T>(h, b, norm, qm, st));
+  const size_t lds = freq ? (size_t)dict * 4 : 0;
+  const size_t per_cu = std::max<size_t>(1, std::min<size_t>(8, kLdsPerCU / (lds + 4096)));
+  const size_t total = h->total, per_wg = (size_t)kQsThreads * Vec16<T>::N;
+  const unsigned grid = (unsigned)std::min<size_t>((total + per_wg - 1) / per_wg, per_cu * h->num_cu);
+  if (freq) {
+    static std::atomic<uint64_t> once{0};
+    TRY(allow_big_lds_once(k_quantize_symbols_residual<T, true>, once, kQsymLdsBytes));
+  }
+  return launch(h, "quantize_symbols_residual", st, [&] {
+    if (freq)
+      k_quantize_symbols_residual<T, true><<<grid, kQsThreads, lds, st>>>(
+          qm, total, coeff, ds->marks, ds->qr_tab, nlev, (int)dict, sym, freq, (unsigned long long *)qo.ocount, qo.oidx,
+          qo.oval, (unsigned long long)qo.ocap, residual);
+    else
+      k_quantize_symbols_residual<T, false><<<grid, kQsThreads, 0, st>>>(
+          qm, total, coeff, ds->marks, ds->qr_tab, nlev, (int)dict, sym, nullptr, (unsigned long long *)qo.ocount,
+          qo.oidx, qo.oval, (unsigned long long)qo.ocap, residual);
+  });
+}
+
+// mgh_dequantize_add: the table of mgh_dequantize by its own upload, the outliers back into the integers
+// (dequantize_dense's step), then one streaming launch of k_dequantize_add on the dense accumulator.
+template <typename T>
+int dequantize_add_impl(mgh_hierarchy *h, int64_t *q, const QuantSpec &qs, bool first, T *acc, hipStream_t st) {
+  auto *ds = DS<T>(h);
+  const int nlev = h->L + 1;
+  if (nlev > kMaxLevels) return fail(MGH_ERR_INVALID_ARGUMENT, "too many levels");
+  TRY(upload_quantizers<T>(h, qs.ebtype, qs.tol, qs.s, qs.norm, false, st));
+  TRY(outliers_back(h, qs, "outlier_restore", st, k_outlier_restore, q, h->total));
+  const size_t total = h->total, per_wg = (size_t)kQaThreads * Vec16<T>::N;
+  const unsigned grid = (unsigned)std::min<size_t>((total + per_wg - 1) / per_wg, 8 * h->num_cu);
+  const int64_t shift = qs.prep_huffman ? (int64_t)qs.dict_size / 2 : 0;
+  return launch(h, "dequantize_add", st, [&] {
+    if (first)
+      k_dequantize_add<T, true><<<grid, kQaThreads, 0, st>>>(ds->qmeta, total, q, ds->marks, ds->qz, nlev, shift, acc);
+    else
+      k_dequantize_add<T, false><<<grid, kQaThreads, 0, st>>>(ds->qmeta, total, q, ds->marks, ds->qz, nlev, shift, acc);
   });
 }
 
@@ -3728,6 +3794,40 @@ int mgh_quantize_symbols(mgh_hierarchy *h, const void *d_coeff, int error_bound_
     using T = decltype(t);
     return quantize_symbols_impl<T>(h, (const T *)d_coeff, caller_layout(h, MGH_LD_IN), {error_bound_type, tol, s},
                                     norm, dict_size, d_symbols, d_freq_or_null, qo, (hipStream_t)stream);
+  });
+}
+
+int mgh_quantize_symbols_residual(mgh_hierarchy *h, const void *d_coeff, int error_bound_type, double tol, double s,
+                                  double norm, uint64_t dict_size, uint16_t *d_symbols, uint32_t *d_freq_or_null,
+                                  uint64_t *d_outlier_count, uint64_t *d_outlier_idx, int64_t *d_outlier_val,
+                                  uint64_t outlier_capacity, void *d_residual_out, void *stream) {
+  if (!h || !d_coeff || !d_symbols || !d_residual_out) return fail(MGH_ERR_INVALID_ARGUMENT, "null argument");
+  const QuantOut qo{dict_size, 1, nullptr, d_symbols, d_outlier_count, d_outlier_idx, d_outlier_val, outlier_capacity};
+  TRY(outlier_args(qo));
+  if (const char *bad = qsym_refusal(h->total, dict_size)) return fail(MGH_ERR_INVALID_ARGUMENT, bad);
+  HIP_TRY(hipSetDevice(h->device));
+  return with_type(h, [&](auto t) {
+    using T = decltype(t);
+    return quantize_symbols_residual_impl<T>(h, (const T *)d_coeff, caller_layout(h, MGH_LD_IN),
+                                             {error_bound_type, tol, s}, norm, dict_size, d_symbols, d_freq_or_null, qo,
+                                             (T *)d_residual_out, (hipStream_t)stream);
+  });
+}
+
+int mgh_dequantize_add(mgh_hierarchy *h, int64_t *d_quantized, int error_bound_type, double tol, double s, double norm,
+                       uint64_t dict_size, int prep_huffman, const uint64_t *d_outlier_idx,
+                       const int64_t *d_outlier_val, uint64_t outlier_count, int first, void *d_coeff_inout,
+                       void *stream) {
+  if (!h || !d_quantized || !d_coeff_inout) return fail(MGH_ERR_INVALID_ARGUMENT, "null argument");
+  if (prep_huffman && outlier_count && (!d_outlier_idx || !d_outlier_val))
+    return fail(MGH_ERR_INVALID_ARGUMENT, "null outlier list");
+  if (h->total == 0 || h->total >= ((uint64_t)1 << 32))
+    return fail(MGH_ERR_INVALID_ARGUMENT, "dequantize_add: 1 .. 2^32 - 1 elements (32-bit index arithmetic)");
+  HIP_TRY(hipSetDevice(h->device));
+  const QuantSpec qs{error_bound_type, tol, s, norm, dict_size, prep_huffman, d_outlier_idx, d_outlier_val, outlier_count};
+  return with_type(h, [&](auto t) {
+    using T = decltype(t);
+    return dequantize_add_impl<T>(h, d_quantized, qs, first != 0, (T *)d_coeff_inout, (hipStream_t)stream);
   });
 }
 

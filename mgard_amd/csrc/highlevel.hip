@@ -1824,12 +1824,16 @@ int encode_record(Lane &L, const LosslessJob &lj, const RecordSink &S, Again &&a
 // the record is not smaller (a RAW record) -- behind its size prefix at the sink's offset. `last_hdr`
 // (the container's last record): the metadata, of meta_size bytes, travels on the record's stream, in
 // front of the synchronisation that record needs anyway; it comes out of g_cache.hpin, which the
-// caller has sized. Ends with the lane synchronised.
+// caller has sized. Ends with the lane synchronised. no_raw_layer >= 0 (mgh_compress_layers: a residual
+// layer's "data" is no array a reader could take in its place): a record the RAW rule would store raw
+// ends the call instead, with nothing written.
 int write_record(Lane &L, uint64_t n, size_t elem, const void *dense_in, RecordSink &S, const fmt::Header *last_hdr,
-                 size_t meta_size) {
+                 size_t meta_size, int no_raw_layer = -1) {
   hipStream_t st = L.st;
   uint64_t csize = L.ll->record_size();
   const bool raw = (double)(n * elem) / (double)csize < 1.0;  // GPUPipelines.hpp:136-155
+  if (raw && no_raw_layer >= 0)
+    return hl_fail(MGH_ERR_INVALID_ARGUMENT, "compress_layers: layer " + std::to_string(no_raw_layer) + " would be stored raw");
   if (raw) csize = n * elem;
   if (csize > S.cap - S.byte_offset || S.cap - S.byte_offset - csize < 8)
     return hl_fail(MGH_ERR_OUTPUT_TOO_LARGE, "Output too large");
@@ -2800,7 +2804,7 @@ int check_config(const mgh_config *cfg) {
 struct SizeEstimator {
   // what the decomposition is for: a size is a function of the histogram under Huffman alone; an
   // achieved error does not depend on the lossless stage at all, and a ladder takes either
-  enum class Purpose { sizes, errors, ladder };
+  enum class Purpose { sizes, errors, ladder, layers };
   int D = 0, dtype = 0, ebtype = 0;
   std::vector<uint64_t> shape_v;
   const void *d_in = nullptr;  // the input on the device: the caller's array, or its upload
@@ -2817,6 +2821,7 @@ struct SizeEstimator {
   std::vector<uint32_t> freq;
   std::vector<uint64_t> outl;
   huff::Codebook cb;
+  bool res_in_q3 = false;  // write(layer): the coefficients the next layer reads are in lane 0's q3, not its q
   ~SizeEstimator() {
     if (h && owned) mgh_hierarchy_destroy(h);
   }
@@ -2844,7 +2849,9 @@ struct SizeEstimator {
                          ? "size estimates: the configuration decomposes the domain (containers of one subdomain only)"
                      : purpose == Purpose::errors
                          ? "achieved errors: the configuration decomposes the domain (containers of one subdomain only)"
-                         : "compress_ladder: the configuration decomposes the domain (containers of one subdomain only)");
+                     : purpose == Purpose::ladder
+                         ? "compress_ladder: the configuration decomposes the domain (containers of one subdomain only)"
+                         : "compress_layers: the configuration decomposes the domain (containers of one subdomain only)");
     n = 1;
     for (int d = 0; d < D; d++) n *= shape[d];
     if (coords_in) {
@@ -2905,8 +2912,13 @@ struct SizeEstimator {
   //     says so (DESIGN.md section 8 has the measurement);
   //   - else mgh_quantize to int64 there and, for reorder == 1, mgh_level_linearize into a third buffer.
   // Host buffers are not registered here (auto_pin_host_buffers: begin() has moved the input already).
+  // layer >= 0 (mgh_compress_layers, which has refused everything but the first route): the quantizing step
+  // is mgh_quantize_symbols_residual, which leaves what this layer did not take of the coefficients in the
+  // OTHER of two buffers (lane 0's q and q3). encode_record may run the step again (outlier overflow), and
+  // that pass must read what the first read, so the two swap roles only when the record is written. A
+  // record the RAW rule would store raw ends the call (write_record).
   static constexpr bool kFusedSymbolHistogram = true;
-  int write(double tol, void **compressed, size_t *compressed_size, bool prealloc) {
+  int write(double tol, void **compressed, size_t *compressed_size, bool prealloc, int layer = -1) {
     Lane &L = g_cache.lane[0];
     hipStream_t st = L.st;
     // output buffer, same memory space as the input, sized as compress_impl sizes it
@@ -2935,6 +2947,9 @@ struct SizeEstimator {
     int rc;
     if ((rc = L.q2.ensure(sym16 ? n * 2 : n * 8)) != MGH_SUCCESS) return cleanup(rc);
     if (cfg.reorder && (rc = L.q3.ensure(n * 8)) != MGH_SUCCESS) return cleanup(rc);
+    if (layer >= 0 && (rc = L.q3.ensure(n * elem)) != MGH_SUCCESS) return cleanup(rc);
+    const void *const coef = layer >= 0 && res_in_q3 ? L.q3.p : L.q.p;
+    void *const residual = layer < 0 ? nullptr : res_in_q3 ? L.q.p : L.q3.p;
     if ((rc = L.ocount.ensure(8)) != MGH_SUCCESS || (rc = L.oidx.ensure(ocap * 8)) != MGH_SUCCESS ||
         (rc = L.oval.ensure(ocap * 8)) != MGH_SUCCESS || (rc = L.pin.ensure(64)) != MGH_SUCCESS)
       return cleanup(rc);
@@ -2953,7 +2968,11 @@ struct SizeEstimator {
       if (!L.ll->prepared_n) HL_HIP(hipMemsetAsync(L.ocount.p, 0, 8, st));
       const bool fused_bins = sym16 && kFusedSymbolHistogram && L.ll->prepared_n != 0;
       const int64_t *q_enc = (const int64_t *)L.q2.p;
-      if (sym16) {
+      if (layer >= 0) {
+        HL_TRY(mgh_quantize_symbols_residual(h, coef, ebtype, tol, s, norm, dict, (uint16_t *)L.q2.p,
+                                             fused_bins ? (uint32_t *)L.ll->freq.p : nullptr, (uint64_t *)L.ocount.p,
+                                             (uint64_t *)L.oidx.p, (int64_t *)L.oval.p, L.ocap, residual, st));
+      } else if (sym16) {
         HL_TRY(mgh_quantize_symbols(h, L.q.p, ebtype, tol, s, norm, dict, (uint16_t *)L.q2.p,
                                     fused_bins ? (uint32_t *)L.ll->freq.p : nullptr, (uint64_t *)L.ocount.p,
                                     (uint64_t *)L.oidx.p, (int64_t *)L.oval.p, L.ocap, st));
@@ -2989,7 +3008,8 @@ struct SizeEstimator {
     };
     if ((rc = quantize()) != MGH_SUCCESS) return cleanup(rc);
     if ((rc = encode_record(L, lj, sink, quantize)) != MGH_SUCCESS) return cleanup(rc);
-    if ((rc = write_record(L, n, elem, d_in, sink, &hdr, meta_size)) != MGH_SUCCESS) return cleanup(rc);
+    if ((rc = write_record(L, n, elem, d_in, sink, &hdr, meta_size, layer)) != MGH_SUCCESS) return cleanup(rc);
+    if (layer >= 0) res_in_q3 = !res_in_q3;
     *compressed_size = sink.byte_offset;
     return MGH_SUCCESS;
   }
@@ -3275,6 +3295,52 @@ int mgh_compress_ladder(int D, int dtype, const uint64_t *shape, int ntol, const
     // (a failure at tolerance k leaves containers 0 .. k-1 the caller's; write() has freed its own)
     for (int k = 0; k < ntol; k++)
       HL_TRY(E.write(tols[k], &compressed_data[k], &compressed_size[k], output_pre_allocated != 0));
+    return MGH_SUCCESS;
+  } catch (const std::exception &e) {
+    return hl_fail(MGH_ERR_DEVICE, e.what());
+  }
+}
+
+int mgh_compress_layers(int D, int dtype, const uint64_t *shape, int ntol, const double *tols, double s, int ebtype,
+                        const void *original_data, void **compressed_data, size_t *compressed_size,
+                        const void *const *coords, const mgh_config *config, int output_pre_allocated) {
+  if (!tols || !compressed_data || !compressed_size) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (ntol < 1 || ntol > kLadderMaxTols) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "compress_layers: ntol must be in 1..64");
+  for (int k = 0; k < ntol; k++) {
+    if (!(tols[k] > 0) || !std::isfinite(tols[k]))
+      return hl_fail(MGH_ERR_INVALID_ARGUMENT, "compress_layers: every tolerance must be positive and finite");
+    if (k > 0 && !(tols[k] < tols[k - 1]))
+      return hl_fail(MGH_ERR_INVALID_ARGUMENT, "compress_layers: the tolerances must be strictly decreasing");
+    if (output_pre_allocated && !compressed_data[k]) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "pre-allocated output is NULL");
+  }
+  HL_TRY(size_call_args(D, dtype, shape, ebtype, original_data, config));
+  {
+    // what the layer writer does not take, before anything is allocated
+    uint64_t n = 1;
+    for (int d = 0; d < D; d++) n *= shape[d];
+    Decomposer dd;
+    HL_TRY(make_decomposer(dd, D, shape, dtype == MGH_FLOAT ? 4 : 8, *config));
+    if (dd.decomposed || dd.num != 1)
+      return hl_fail(MGH_ERR_INVALID_ARGUMENT,
+                     "compress_layers: the configuration decomposes the domain (containers of one subdomain only)");
+    if (config->reorder)
+      return hl_fail(MGH_ERR_INVALID_ARGUMENT, "compress_layers: reorder = 1 is not supported (the layers are reorder = 0 records)");
+    if (!lossless_sym16_ok(config->huff_dict_size, config->huff_block_size))
+      return hl_fail(MGH_ERR_INVALID_ARGUMENT,
+                     "compress_layers: huff_dict_size / huff_block_size outside what the single-pass encoder takes");
+    if (const char *bad = qsym_refusal(n, config->huff_dict_size))
+      return hl_fail(MGH_ERR_INVALID_ARGUMENT, std::string("compress_layers: ") + bad);
+  }
+  if (!output_pre_allocated)
+    for (int k = 0; k < ntol; k++) compressed_data[k] = nullptr;
+  try {
+    SizeEstimator E;
+    compress_stats() = mgh_compress_stats{};
+    HL_TRY(E.begin(D, dtype, shape, s, ebtype, original_data, coords, *config, SizeEstimator::Purpose::layers));
+    compress_stats().decompositions++;
+    // (a failure at layer k leaves containers 0 .. k-1 the caller's; write() has freed its own)
+    for (int k = 0; k < ntol; k++)
+      HL_TRY(E.write(tols[k], &compressed_data[k], &compressed_size[k], output_pre_allocated != 0, k));
     return MGH_SUCCESS;
   } catch (const std::exception &e) {
     return hl_fail(MGH_ERR_DEVICE, e.what());
@@ -4960,6 +5026,217 @@ int mgh_last_decompress_stats(mgh_decompress_stats *out) {
   if (!out) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "NULL argument");
   *out = decompress_stats();
   return MGH_SUCCESS;
+}
+
+} // extern "C"
+
+// ---- precision layers, the reader: containers of mgh_compress_layers added up in the coefficients ------
+// State between the calls: the accumulator -- the coefficients of the array as the layers added so far
+// give them -- on the device, and the header of layer 0, which every later layer has to agree with. A
+// layer costs a decode and one stream over the accumulator (mgh_dequantize_add); the recomposition runs
+// when the data is asked for, on a copy (mgh_recompose is not in place here: the accumulator stays).
+struct mgh_layers {
+  fmt::Header hd;  // of layer 0
+  mgh_config cfg;
+  bool in_dev = false;
+  int dtype = MGH_FLOAT;
+  size_t elem = 4;
+  uint64_t n = 0;
+  int count = 0;
+  double tol = 0;  // of the last layer added
+  mgh_hierarchy *h = nullptr;
+  mgh_lossless_ctx *ll = nullptr;
+  hipStream_t st = nullptr;
+  DevBuf acc;  // n elements: the coefficients
+  DevBuf q;    // n int64: the integers of the layer being added
+  DevBuf out;  // n elements: the recomposed array on its way to host memory
+};
+
+namespace {
+void layers_free(mgh_layers *p) {
+  if (!p) return;
+  (void)hipSetDevice(p->cfg.dev_id);
+  if (p->st) (void)hipStreamSynchronize(p->st);
+  for (DevBuf *b : {&p->acc, &p->q, &p->out}) b->release();
+  if (p->h) mgh_hierarchy_destroy(p->h);
+  if (p->ll) mgh_lossless_destroy(p->ll);
+  if (p->st) (void)hipStreamDestroy(p->st);
+  delete p;
+}
+
+// What a later layer must share with layer 0 to be a layer of the same array.
+const char *layers_mismatch(const fmt::Header &a, const fmt::Header &b) {
+  if (a.shape != b.shape) return "the shape";
+  if (a.is_double != b.is_double) return "the data type";
+  if (a.uniform != b.uniform || (!a.uniform && a.coords != b.coords)) return "the coordinates";
+  if (a.rel != b.rel) return "the error bound type";
+  if (!(a.s == b.s)) return "s";
+  if (!(a.norm == b.norm)) return "the norm";
+  if (a.dd_method != b.dd_method || a.hierarchy != b.hierarchy) return "the decomposition";
+  return nullptr;
+}
+
+// One container into the accumulator: layer 0 (p->count == 0) opens it, every other one is added. Every
+// refusal comes before the accumulator is touched.
+int layers_add(mgh_layers *p, const void *data, size_t size) {
+  const bool first = p->count == 0;
+  const char *who = first ? "mgh_layers_open" : "mgh_layers_add";
+  std::unique_ptr<HostPrefix> prefix;
+  const bool in_dev = is_device_pointer(data);
+  if (in_dev) prefix.reset(new HostPrefix(data, size));
+  size_t meta_size = 0;
+  fmt::Header hd;
+  HL_TRY(read_header(data, size, hd, meta_size));
+  if (hd.shape.empty() || hd.shape.size() > MGH_MAX_DIM) return hl_fail(MGH_ERR_UNSUPPORTED_DIMENSION, "header: dimension");
+  if (!hd.quantized) return hl_fail(MGH_ERR_FORMAT, "not a compressed (quantized) stream");
+  RecordView rv;
+  HL_TRY(record_view_header(hd, rv));
+  if (hd.dd_method != fmt::DD_NOOP)
+    return hl_fail(MGH_ERR_INVALID_ARGUMENT, std::string(who) + ": the container is domain-decomposed (layers have one subdomain)");
+  if (hd.reorder) return hl_fail(MGH_ERR_INVALID_ARGUMENT, std::string(who) + ": a reorder = 1 container is no layer");
+  for (uint64_t e : hd.shape)
+    if (e < 3) return hl_fail(MGH_ERR_FORMAT, "header: extent below 3");
+  if (!first) {
+    if (const char *what = layers_mismatch(p->hd, hd))
+      return hl_fail(MGH_ERR_INVALID_ARGUMENT, std::string(who) + ": " + what + " is not layer 0's");
+    if (!(hd.tol < p->tol))
+      return hl_fail(MGH_ERR_INVALID_ARGUMENT, std::string(who) + ": the tolerance is not below the last layer's");
+  }
+  uint64_t n = 1;
+  for (uint64_t e : hd.shape) n *= e;
+  const size_t elem = hd.is_double ? 8 : 4;
+  HL_TRY(record_view_at(data, size, meta_size, n * elem, rv));
+  if (rv.raw) return hl_fail(MGH_ERR_INVALID_ARGUMENT, std::string(who) + ": the record is stored raw (no layer is)");
+  if (first) {
+    p->hd = hd;
+    p->in_dev = in_dev;
+    p->dtype = hd.is_double ? MGH_DOUBLE : MGH_FLOAT;
+    p->elem = elem;
+    p->n = n;
+    std::vector<std::vector<double>> mirrored;
+    bool owned = true;
+    HL_TRY(get_hierarchy(&p->h, &owned, p->dtype, hd.shape, decoder_coords(hd, p->cfg, mirrored),
+                         std::vector<uint64_t>(hd.shape.size(), 0), p->cfg, 0, /*cached=*/false));
+    HL_HIP(hipStreamCreate(&p->st));
+    HL_TRY(mgh_lossless_create(&p->ll, p->cfg.dev_id));
+    HL_TRY(p->acc.ensure(n * elem));
+    HL_TRY(p->q.ensure(n * 8));
+    decompress_stats() = mgh_decompress_stats{};
+  }
+  auto in_type = [&](double v) { return hd.is_double ? v : (double)(float)v; };
+  uint64_t ocount = 0;
+  int rc = lossless_decompress(p->ll, rv.rec, rv.csize, rv.lossless, (int64_t *)p->q.p, n, &ocount, p->st);
+  if (rc != MGH_SUCCESS) {
+    (void)hipStreamSynchronize(p->st);
+    return rc;
+  }
+  rc = mgh_dequantize_add(p->h, (int64_t *)p->q.p, hd.rel ? MGH_REL : MGH_ABS, in_type(hd.tol), in_type(hd.s),
+                          in_type(hd.norm), hd.huff_dict_size, 1, (const uint64_t *)p->ll->oidx.p,
+                          (const int64_t *)p->ll->oval.p, ocount, first ? 1 : 0, p->acc.p, p->st);
+  if (hipStreamSynchronize(p->st) != hipSuccess && rc == MGH_SUCCESS) rc = hl_fail(MGH_ERR_DEVICE, "sync");
+  HL_TRY(rc);
+  p->count++;
+  p->tol = hd.tol;
+  return MGH_SUCCESS;
+}
+
+// mgh_recompose of the accumulator into an array in the containers' memory space (or the caller's buffer).
+int layers_data(mgh_layers *p, void **out, bool prealloc) {
+  hipStream_t st = p->st;
+  const size_t out_bytes = p->n * p->elem;
+  if (!prealloc) {
+    if (p->in_dev) HL_HIP(hipMalloc(out, out_bytes));
+    else if (!(*out = host_alloc_large(out_bytes))) return hl_fail(MGH_ERR_OUT_OF_MEMORY, "malloc");
+  }
+  int rc = MGH_SUCCESS;
+  if (is_device_pointer(*out)) {
+    rc = mgh_recompose(p->h, p->acc.p, *out, st);
+  } else {
+    rc = p->out.ensure(out_bytes);
+    if (rc == MGH_SUCCESS) rc = mgh_recompose(p->h, p->acc.p, p->out.p, st);
+    if (rc == MGH_SUCCESS) rc = copy_any(*out, p->out.p, out_bytes, st);
+  }
+  if (hipStreamSynchronize(st) != hipSuccess && rc == MGH_SUCCESS) rc = hl_fail(MGH_ERR_DEVICE, "sync");
+  if (rc != MGH_SUCCESS && !prealloc) {
+    if (p->in_dev) (void)hipFree(*out); else std::free(*out);
+    *out = nullptr;
+  }
+  return rc;
+}
+}  // namespace
+
+extern "C" {
+
+int mgh_layers_open(mgh_layers **out, const void *compressed_data, size_t compressed_size, const mgh_config *config) {
+  if (!out || !compressed_data) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "NULL argument");
+  *out = nullptr;
+  {
+    const std::string bad = env_validate();
+    if (!bad.empty()) return hl_fail(MGH_ERR_INVALID_ARGUMENT, bad);
+  }
+  mgh_config def;
+  if (!config) {
+    mgh_config_default(&def);
+    config = &def;
+  }
+  if (mgh_device_count() <= 0) return hl_fail(MGH_ERR_NO_DEVICE, "no HIP device");
+  if (hipSetDevice(config->dev_id) != hipSuccess) return hl_fail(MGH_ERR_DEVICE, "hipSetDevice");
+  mgh_layers *p = new mgh_layers();
+  p->cfg = *config;
+  int rc;
+  try {
+    rc = layers_add(p, compressed_data, compressed_size);
+  } catch (const std::exception &e) {
+    rc = hl_fail(MGH_ERR_DEVICE, e.what());
+  }
+  if (rc != MGH_SUCCESS) {
+    layers_free(p);
+    return rc;
+  }
+  *out = p;
+  return MGH_SUCCESS;
+}
+
+int mgh_layers_add(mgh_layers *p, const void *compressed_data, size_t compressed_size) {
+  if (!p || !compressed_data) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (hipSetDevice(p->cfg.dev_id) != hipSuccess) return hl_fail(MGH_ERR_DEVICE, "hipSetDevice");
+  try {
+    return layers_add(p, compressed_data, compressed_size);
+  } catch (const std::exception &e) {
+    return hl_fail(MGH_ERR_DEVICE, e.what());
+  }
+}
+
+int mgh_layers_count(const mgh_layers *p) { return p ? p->count : -1; }
+
+double mgh_layers_tolerance(const mgh_layers *p) { return p ? p->tol : 0.0; }
+
+int mgh_layers_data(mgh_layers *p, void **data, int output_pre_allocated) {
+  if (!p || !data) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (output_pre_allocated && !*data) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "pre-allocated output is NULL");
+  if (hipSetDevice(p->cfg.dev_id) != hipSuccess) return hl_fail(MGH_ERR_DEVICE, "hipSetDevice");
+  try {
+    return layers_data(p, data, output_pre_allocated != 0);
+  } catch (const std::exception &e) {
+    return hl_fail(MGH_ERR_DEVICE, e.what());
+  }
+}
+
+void mgh_layers_close(mgh_layers *p) { layers_free(p); }
+
+int mgh_decompress_layers(int nlayers, const void *const *compressed_data, const size_t *compressed_size,
+                          const mgh_config *config, void **decompressed_data, int output_pre_allocated) {
+  if (!compressed_data || !compressed_size || !decompressed_data) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (nlayers < 1 || nlayers > kLadderMaxTols) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "decompress_layers: nlayers must be in 1..64");
+  for (int k = 0; k < nlayers; k++)
+    if (!compressed_data[k]) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (output_pre_allocated && !*decompressed_data) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "pre-allocated output is NULL");
+  mgh_layers *p = nullptr;
+  int rc = mgh_layers_open(&p, compressed_data[0], compressed_size[0], config);
+  for (int k = 1; k < nlayers && rc == MGH_SUCCESS; k++) rc = mgh_layers_add(p, compressed_data[k], compressed_size[k]);
+  if (rc == MGH_SUCCESS) rc = mgh_layers_data(p, decompressed_data, output_pre_allocated);
+  mgh_layers_close(p);
+  return rc;
 }
 
 } // extern "C"

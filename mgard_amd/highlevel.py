@@ -36,6 +36,8 @@ HL_SYMBOLS = [
     "mgh_estimate_sizes", "mgh_compress_budget",
     "mgh_achieved_errors", "mgh_compress_target",
     "mgh_compress_ladder", "mgh_last_compress_stats", "mgh_histogram_sym16",
+    "mgh_compress_layers", "mgh_layers_open", "mgh_layers_add", "mgh_layers_count", "mgh_layers_tolerance",
+    "mgh_layers_data", "mgh_layers_close", "mgh_decompress_layers",
 ]
 
 
@@ -82,7 +84,7 @@ class DecompressStats(C.Structure):
 
 
 class CompressStats(C.Structure):
-    """mgh_compress_stats: what the last compress / compress_budget / compress_target / compress_ladder call
+    """mgh_compress_stats: what the last compress / compress_budget / compress_target / compress_ladder / compress_layers call
     of this thread did."""
     _fields_ = [("decompositions", C.c_uint64), ("quantize_passes", C.c_uint64), ("histogram_launches", C.c_uint64),
                 ("records", C.c_uint64), ("raw_records", C.c_uint64), ("outlier_retries", C.c_uint64)]
@@ -222,6 +224,17 @@ def _hl():
                                       C.c_int, vp, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(vp),
                                       C.POINTER(Config), C.c_int]
     L.mgh_histogram_sym16.argtypes = [vp, u64, u64, vp, vp]
+    L.mgh_compress_layers.argtypes = L.mgh_compress_ladder.argtypes
+    L.mgh_layers_open.argtypes = [C.POINTER(vp), vp, C.c_size_t, vp]
+    L.mgh_layers_add.argtypes = [vp, vp, C.c_size_t]
+    L.mgh_layers_count.argtypes = [vp]
+    L.mgh_layers_tolerance.argtypes = [vp]
+    L.mgh_layers_tolerance.restype = C.c_double
+    L.mgh_layers_data.argtypes = [vp, C.POINTER(vp), C.c_int]
+    L.mgh_layers_close.argtypes = [vp]
+    L.mgh_layers_close.restype = None
+    L.mgh_decompress_layers.argtypes = [C.c_int, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(Config), C.POINTER(vp),
+                                        C.c_int]
     L.mgh_memcpy.argtypes = [vp, vp, C.c_size_t]
     L.mgh_huffman_codebook.argtypes = [vp, u64, vp, vp, vp, vp]
     _declared = True
@@ -452,7 +465,7 @@ def compress_target(data, metric, target, tol_min, tol_max, rounds=8, s=INF, mod
     return out[:size.value], used.value, stats, cand.value
 
 
-def compress_ladder(data, tols, s=INF, mode=REL, coords=None, config=None, outs=None):
+def compress_ladder(data, tols, s=INF, mode=REL, coords=None, config=None, outs=None, _call="mgh_compress_ladder"):
     """mgh_compress_ladder: [compress(data, tol, ...) for tol in tols] (1..64 tolerances, up to the order of
     the outlier lists) from ONE decomposition of `data` -- numpy uint8 arrays (host input) or cuda uint8
     tensors (device input). Containers of one subdomain. `outs`: optional pre-allocated uint8 buffers of
@@ -474,9 +487,133 @@ def compress_ladder(data, tols, s=INF, mode=REL, coords=None, config=None, outs=
     assert len(outs) == k, "one output buffer per tolerance"
     optr = (C.c_void_p * max(k, 1))(*[o.data_ptr() if on_device else o.ctypes.data for o in outs])
     sizes = (C.c_size_t * max(k, 1))(*[int(o.numel()) if on_device else int(o.size) for o in outs])
-    _check(L.mgh_compress_ladder(D, dt, (C.c_uint64 * D)(*shape), k, (C.c_double * max(k, 1))(*tols), float(s),
-                                 int(mode), ptr, optr, sizes, cptr, C.byref(cfg), 1))
+    _check(getattr(L, _call)(D, dt, (C.c_uint64 * D)(*shape), k, (C.c_double * max(k, 1))(*tols), float(s),
+                             int(mode), ptr, optr, sizes, cptr, C.byref(cfg), 1))
     return [o[:sizes[i]] for i, o in enumerate(outs)]
+
+
+def compress_layers(data, tols, s=INF, mode=REL, coords=None, config=None, outs=None):
+    """mgh_compress_layers: precision layers of `data` for the strictly decreasing tolerances `tols` (1..64) --
+    container k holds what containers 0 .. k-1 left of the coefficients, quantized at tols[k], so
+    decompress_layers(bufs[:k + 1]) is within tols[k] and the set is far smaller than a ladder. bufs[0] is
+    compress(data, tols[0], ...)'s container; every layer is an ordinary container of one subdomain. The
+    containers carry no layer index: keep them in order. Outputs, `outs` and a failure at layer k as in
+    compress_ladder. Refused: a configuration that decomposes the domain, reorder = 1, a layer that would be
+    stored raw."""
+    return compress_ladder(data, tols, s, mode, coords, config, outs, _call="mgh_compress_layers")
+
+
+def _container_ptr(buf):
+    """(pointer, size, on_device, keepalive) of a container: numpy uint8 array or cuda uint8 tensor."""
+    import torch
+    if isinstance(buf, torch.Tensor) and buf.is_cuda:
+        buf = buf.contiguous()
+        return C.c_void_p(buf.data_ptr()), int(buf.numel()), True, buf
+    buf = np.ascontiguousarray(buf)
+    return C.c_void_p(buf.ctypes.data), int(buf.size), False, buf
+
+
+def _layers_out(buf0, out):
+    """The array layers of `buf0` reconstruct, as (out, pointer): a cuda tensor for a device container, a numpy
+    array for a host one."""
+    import torch
+    shape, dt = infer(buf0)
+    on_dev = isinstance(buf0, torch.Tensor) and buf0.is_cuda
+    n = int(np.prod(shape))
+    if on_dev:
+        want = torch.float32 if dt == FLOAT else torch.float64
+        if out is None:
+            out = torch.empty(shape, dtype=want, device=buf0.device)
+        if not (isinstance(out, torch.Tensor) and out.is_cuda and out.is_contiguous() and out.dtype == want and
+                out.numel() == n):
+            raise ValueError("`out` must be a contiguous cuda tensor of the array's shape and the stream's type")
+        return out, C.c_void_p(out.data_ptr())
+    npdt = np.float32 if dt == FLOAT else np.float64
+    if out is None:
+        out = np.empty(shape, dtype=npdt)
+    if not (isinstance(out, np.ndarray) and out.flags.c_contiguous and out.flags.writeable and out.dtype == npdt and
+            out.size == n):
+        raise ValueError("`out` must be a writeable C-contiguous numpy array of the array's shape and type")
+    return out, C.c_void_p(out.ctypes.data)
+
+
+def decompress_layers(bufs, config=None, out=None):
+    """mgh_decompress_layers: the array after the layers `bufs` (compress_layers' containers, from layer 0 on, in
+    order): one decode and one stream over the coefficients per layer, then one recomposition. A numpy array
+    (host containers) or a cuda tensor. decompress_layers([b]) is decompress(b), bit for bit."""
+    L = _hl()
+    cfg = config if config is not None else Config()
+    bufs = list(bufs)
+    k = len(bufs)
+    ptrs = [_container_ptr(b) for b in bufs]
+    if k == 0:
+        raise ValueError("decompress_layers needs at least layer 0")
+    out, optr = _layers_out(bufs[0], out)
+    _check(L.mgh_decompress_layers(k, (C.c_void_p * k)(*[p[0].value for p in ptrs]), (C.c_size_t * k)(*[p[1] for p in ptrs]),
+                                   C.byref(cfg), C.byref(optr), 1))
+    return out
+
+
+class Layers:
+    """mgh_layers: the reader of precision layers -- the coefficients stay on the device, a layer is added when
+    it arrives, an array is recomposed when it is wanted.
+
+        with Layers(bufs[0], config) as r:
+            coarse = r.data()
+            fine = r.add(bufs[1]).add(bufs[2]).data()
+
+    The containers are read during the call only. Their order is the caller's: a layer whose tolerance is not
+    below the last one's, or that belongs to another array, raises and leaves the reader as it was."""
+
+    def __init__(self, buf0, config=None):
+        self._p = C.c_void_p()
+        self._cfg = config if config is not None else Config()
+        self._buf0 = buf0
+        p, n, _, keep = _container_ptr(buf0)
+        _check(_hl().mgh_layers_open(C.byref(self._p), p, n, C.byref(self._cfg)))
+
+    def _open(self):
+        if not self._p:
+            raise MgardHipError("the reader is closed")
+        return self._p
+
+    @property
+    def count(self):
+        """Layers added so far, layer 0 included."""
+        return int(_hl().mgh_layers_count(self._open()))
+
+    @property
+    def tolerance(self):
+        """The tolerance of the last layer added (its header's)."""
+        return float(_hl().mgh_layers_tolerance(self._open()))
+
+    def add(self, buf):
+        p, n, _, keep = _container_ptr(buf)
+        _check(_hl().mgh_layers_add(self._open(), p, n))
+        return self
+
+    def data(self, out=None):
+        """mgh_layers_data: the recomposition of the coefficients as they stand; the reader goes on."""
+        out, optr = _layers_out(self._buf0, out)
+        _check(_hl().mgh_layers_data(self._open(), C.byref(optr), 1))
+        return out
+
+    def close(self):
+        if self._p:
+            _hl().mgh_layers_close(self._p)
+            self._p = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def last_compress_stats():
