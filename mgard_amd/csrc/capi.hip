@@ -50,7 +50,6 @@
 #include "target_plan.hpp"
 #include "kernels_qround.hpp"
 #include "kernels_qsym.hpp"
-#include "kernels_qres.hpp"
 
 namespace {
 
@@ -2911,20 +2910,62 @@ int dequantize_impl(mgh_hierarchy *h, int64_t *q, const QuantSpec &qs, T *coeff,
   return o.finish(h, st);
 }
 
-// mgh_quantize_histograms: the tables of every tolerance as upload_quantizers makes the one of
-// mgh_quantize (the volumes depend on s only), then the launches size_plan.hpp splits the tolerances into.
+// ---- the streaming quantizer passes (kernels_qwalk.hpp) ---------------------------------------------
+// Their grid: persistent workgroups of `threads`, one vector of `vn` elements per thread and trip, as
+// many per compute unit as its LDS holds beside the static tables with `lds` dynamic bytes each, `cap` at
+// most; they stride over the rest. The kernels stage the level tables in LDS rows of kMaxLevels.
+inline int stream_grid(mgh_hierarchy *h, int threads, int vn, size_t lds, size_t cap, unsigned *grid) {
+  if (h->L + 1 > kMaxLevels) return fail(MGH_ERR_INVALID_ARGUMENT, "too many levels");
+  const size_t per_cu = std::max<size_t>(1, std::min<size_t>(cap, kLdsPerCU / (lds + 4096)));
+  const size_t per_wg = (size_t)threads * vn;
+  *grid = (unsigned)std::min<size_t>((h->total + per_wg - 1) / per_wg, per_cu * h->num_cu);
+  return MGH_SUCCESS;
+}
+
+// Level tables made by the host code of upload_quantizers (the volumes depend on s only), one row of
+// L + 1 values per entry of `rows` -- which table (QTab) and for what tolerance -- side by side in *buf.
+// `qm`: the hierarchy's quantizer metadata for this s.
+struct QRow {
+  QTab tab;
+  double tol;
+};
+
+template <typename T>
+int upload_level_rows(mgh_hierarchy *h, int ebtype, double s, double norm, const std::vector<QRow> &rows, T **buf,
+                      size_t *buf_elems, QuantMeta &qm, hipStream_t st) {
+  auto *hh = HH<T>(h);
+  const int nlev = h->L + 1;
+  const bool calc_vol = !((T)s == std::numeric_limits<T>::infinity());
+  std::vector<T> tab(rows.size() * nlev);
+  for (size_t r = 0; r < rows.size(); r++) {
+    T *row = tab.data() + r * nlev;
+    const bool dequant = rows[r].tab == kTabQz || rows[r].tab == kTabDvol;
+    if (rows[r].tab == kTabRqz || rows[r].tab == kTabQz)
+      hh->quantizers(ebtype, (T)rows[r].tol, (T)s, (T)norm, !dequant, row);
+    else
+      for (int l = 0; l < nlev; l++) row[l] = calc_vol ? hh->level_volume(l, dequant) : (T)1;
+  }
+  TRY(grow(h, buf, buf_elems, tab.size()));
+  // pageable-memory async copies are staged by the runtime before returning
+  HIP_TRY(hipMemcpyAsync(*buf, tab.data(), tab.size() * sizeof(T), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  qm = DS<T>(h)->qmeta;
+  qm.calc_vol = calc_vol ? 1 : 0;
+  return MGH_SUCCESS;
+}
+
+// mgh_quantize_histograms: the reciprocal quantizers of every tolerance and one row of volumes in
+// ds->qh_tab, then the launches size_plan.hpp splits the tolerances into.
 template <typename T, int K>
 int qhist_launch(mgh_hierarchy *h, const QuantMeta &qm, const T *coeff, const T *qz, const T *vol, uint64_t dict,
                  uint32_t *freq, uint64_t *outliers, hipStream_t st) {
   static std::atomic<uint64_t> once{0};
   const size_t lds = (size_t)K * dict * 4;
   TRY(allow_big_lds_once(k_quantize_histograms<T, K>, once, kQhistLdsBytes));
-  // few persistent workgroups: as many per CU as its LDS holds beside the static tables, four at most
-  const size_t per_cu = std::max<size_t>(1, std::min<size_t>(4, kLdsPerCU / (lds + 4096)));
-  const size_t total = h->total, per_wg = (size_t)kQhThreads * Vec16<T>::N;
-  const unsigned grid = (unsigned)std::min<size_t>((total + per_wg - 1) / per_wg, per_cu * h->num_cu);
+  unsigned grid;
+  TRY(stream_grid(h, kQhThreads, Vec16<T>::N, lds, 4, &grid));
   return launch(h, "quantize_histograms", st, [&] {
-    k_quantize_histograms<T, K><<<grid, kQhThreads, lds, st>>>(qm, total, coeff, DS<T>(h)->marks, qz, vol, h->L + 1,
+    k_quantize_histograms<T, K><<<grid, kQhThreads, lds, st>>>(qm, h->total, coeff, DS<T>(h)->marks, qz, vol, h->L + 1,
                                                               (int)dict, freq, (unsigned long long *)outliers);
   });
 }
@@ -2933,22 +2974,15 @@ template <typename T>
 int quantize_histograms_impl(mgh_hierarchy *h, const T *coeff, Layout in, int ebtype, int ntol, const double *tols,
                              double s, double norm, uint64_t dict, uint32_t *freq, uint64_t *outliers, hipStream_t st) {
   auto *ds = DS<T>(h);
-  auto *hh = HH<T>(h);
   const int nlev = h->L + 1;
-  if (nlev > kMaxLevels) return fail(MGH_ERR_INVALID_ARGUMENT, "too many levels");
   TRY(ld_pack<T>(h, coeff, in, false, st));
-  std::vector<T> tab((size_t)(ntol + 1) * nlev);
-  for (int k = 0; k < ntol; k++) hh->quantizers(ebtype, (T)tols[k], (T)s, (T)norm, true, tab.data() + (size_t)k * nlev);
-  const bool calc_vol = !((T)s == std::numeric_limits<T>::infinity());
-  for (int l = 0; l < nlev; l++) tab[(size_t)ntol * nlev + l] = calc_vol ? hh->level_volume(l, false) : (T)1;
-  TRY(grow(h, &ds->qh_tab, &ds->qh_tab_elems, tab.size()));
-  // pageable-memory async copies are staged by the runtime before returning
-  HIP_TRY(hipMemcpyAsync(ds->qh_tab, tab.data(), tab.size() * sizeof(T), hipMemcpyHostToDevice, st));
-  HIP_TRY(hipStreamSynchronize(st));
+  std::vector<QRow> rows;
+  for (int k = 0; k < ntol; k++) rows.push_back({kTabRqz, tols[k]});
+  rows.push_back({kTabQvol, 0});
+  QuantMeta qm;
+  TRY(upload_level_rows<T>(h, ebtype, s, norm, rows, &ds->qh_tab, &ds->qh_tab_elems, qm, st));
   HIP_TRY(hipMemsetAsync(freq, 0, (size_t)ntol * dict * sizeof(uint32_t), st));
   HIP_TRY(hipMemsetAsync(outliers, 0, (size_t)ntol * sizeof(uint64_t), st));
-  QuantMeta qm = ds->qmeta;
-  qm.calc_vol = calc_vol ? 1 : 0;
   const T *vol = ds->qh_tab + (size_t)ntol * nlev;
   for (int k0 = 0; k0 < ntol;) {
     const int kk = qhist_per_launch(dict, ntol - k0);
@@ -2963,114 +2997,81 @@ int quantize_histograms_impl(mgh_hierarchy *h, const T *coeff, Layout in, int eb
 }
 
 // The table of mgh_quantize (upload_quantizers, reciprocal) and the table of mgh_dequantize
-// (upload_quantizers, not reciprocal) side by side in ds->qr_tab, made by the same host code: what the
-// kernels that quantize and dequantize in one pass read (k_quantize_roundtrip,
-// k_quantize_symbols_residual). `qm`: the hierarchy's quantizer metadata for this s.
+// (upload_quantizers, not reciprocal) side by side in ds->qr_tab, in the order of QTab: what the kernels
+// that quantize and dequantize in one pass read (k_quantize_roundtrip, k_quantize_symbols_residual).
 template <typename T>
 int upload_roundtrip_tables(mgh_hierarchy *h, const Bound &b, double norm, QuantMeta &qm, hipStream_t st) {
   auto *ds = DS<T>(h);
-  auto *hh = HH<T>(h);
-  const int nlev = h->L + 1;
-  if (nlev > kMaxLevels) return fail(MGH_ERR_INVALID_ARGUMENT, "too many levels");
-  std::vector<T> tab((size_t)4 * nlev);
-  hh->quantizers(b.ebtype, (T)b.tol, (T)b.s, (T)norm, true, tab.data());
-  hh->quantizers(b.ebtype, (T)b.tol, (T)b.s, (T)norm, false, tab.data() + 2 * nlev);
-  const bool calc_vol = !((T)b.s == std::numeric_limits<T>::infinity());
-  for (int l = 0; l < nlev; l++) {
-    tab[nlev + l] = calc_vol ? hh->level_volume(l, false) : (T)1;
-    tab[3 * nlev + l] = calc_vol ? hh->level_volume(l, true) : (T)1;
-  }
-  TRY(grow(h, &ds->qr_tab, &ds->qr_tab_elems, tab.size()));
-  // pageable-memory async copies are staged by the runtime before returning
-  HIP_TRY(hipMemcpyAsync(ds->qr_tab, tab.data(), tab.size() * sizeof(T), hipMemcpyHostToDevice, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  qm = ds->qmeta;
-  qm.calc_vol = calc_vol ? 1 : 0;
-  return MGH_SUCCESS;
+  const std::vector<QRow> rows{{kTabRqz, b.tol}, {kTabQvol, b.tol}, {kTabQz, b.tol}, {kTabDvol, b.tol}};
+  return upload_level_rows<T>(h, b.ebtype, b.s, norm, rows, &ds->qr_tab, &ds->qr_tab_elems, qm, st);
 }
 
-// mgh_quantize_roundtrip: the four tables, then one streaming launch. The output is dense.
+// mgh_quantize_roundtrip: the four tables, then one streaming launch, at most eight workgroups per
+// compute unit. The output is dense.
 template <typename T>
 int quantize_roundtrip_impl(mgh_hierarchy *h, const T *coeff, Layout in, const Bound &b, double norm, T *out,
                             hipStream_t st) {
   auto *ds = DS<T>(h);
-  const int nlev = h->L + 1;
-  if (nlev > kMaxLevels) return fail(MGH_ERR_INVALID_ARGUMENT, "too many levels");
+  unsigned grid;
+  TRY(stream_grid(h, kQrThreads, Vec16<T>::N, 0, 8, &grid));
   TRY(ld_pack<T>(h, coeff, in, false, st));
   QuantMeta qm;
   TRY(upload_roundtrip_tables<T>(h, b, norm, qm, st));
-  // a pure stream: workgroups of 256 threads, one 16-byte vector per thread and trip, at most eight
-  // workgroups per compute unit, which stride over the rest
-  const size_t total = h->total, per_wg = (size_t)kQrThreads * Vec16<T>::N;
-  const unsigned grid = (unsigned)std::min<size_t>((total + per_wg - 1) / per_wg, 8 * h->num_cu);
   return launch(h, "quantize_roundtrip", st, [&] {
-    k_quantize_roundtrip<T><<<grid, kQrThreads, 0, st>>>(qm, total, coeff, ds->marks, ds->qr_tab, nlev, out);
+    k_quantize_roundtrip<T><<<grid, kQrThreads, 0, st>>>(qm, h->total, coeff, ds->marks, ds->qr_tab, h->L + 1, out);
   });
 }
 
-// mgh_quantize_symbols: the table of mgh_quantize by its own upload (upload_quantizers, reciprocal), then
-// one launch of k_quantize_symbols. The caller has zeroed the counter and the bins.
+// One launch of k_quantize_symbols, or with RES of k_quantize_symbols_residual, on tables that are
+// uploaded: eight workgroups per compute unit for the plain stream, as many as the LDS holds beside the
+// static tables with the bins. The caller has zeroed the counter and the bins.
+template <typename T, bool RES>
+int qsym_launch(mgh_hierarchy *h, const QuantMeta &qm, const T *coeff, const T *tab, uint64_t dict, uint16_t *sym,
+                uint32_t *freq, const QuantOut &qo, T *residual, hipStream_t st) {
+  const size_t lds = freq ? (size_t)dict * 4 : 0;
+  unsigned grid;
+  TRY(stream_grid(h, kQsThreads, Vec16<T>::N, lds, 8, &grid));
+  return with_value<0, 1>(freq ? 1 : 0, [&](auto hist) {
+    constexpr bool HIST = decltype(hist)::value != 0;
+    auto count = (unsigned long long *)qo.ocount;
+    const auto cap = (unsigned long long)qo.ocap;
+    if constexpr (HIST) {
+      static std::atomic<uint64_t> once{0};
+      if constexpr (RES)
+        TRY(allow_big_lds_once(k_quantize_symbols_residual<T, true>, once, kQsymLdsBytes));
+      else
+        TRY(allow_big_lds_once(k_quantize_symbols<T, true>, once, kQsymLdsBytes));
+    }
+    return launch(h, RES ? "quantize_symbols_residual" : "quantize_symbols", st, [&] {
+      if constexpr (RES)
+        k_quantize_symbols_residual<T, HIST><<<grid, kQsThreads, lds, st>>>(
+            qm, h->total, coeff, DS<T>(h)->marks, tab, h->L + 1, (int)dict, sym, freq, count, qo.oidx, qo.oval, cap, residual);
+      else
+        k_quantize_symbols<T, HIST><<<grid, kQsThreads, lds, st>>>(
+            qm, h->total, coeff, DS<T>(h)->marks, tab, h->L + 1, (int)dict, sym, freq, count, qo.oidx, qo.oval, cap);
+    });
+  });
+}
+
+// mgh_quantize_symbols: the table of mgh_quantize by its own upload (upload_quantizers, reciprocal).
 template <typename T>
 int quantize_symbols_impl(mgh_hierarchy *h, const T *coeff, Layout in, const Bound &b, double norm, uint64_t dict,
                           uint16_t *sym, uint32_t *freq, const QuantOut &qo, hipStream_t st) {
   auto *ds = DS<T>(h);
-  const int nlev = h->L + 1;
-  if (nlev > kMaxLevels) return fail(MGH_ERR_INVALID_ARGUMENT, "too many levels");
   TRY(ld_pack<T>(h, coeff, in, false, st));
   TRY(upload_quantizers<T>(h, b.ebtype, b.tol, b.s, norm, true, st));
-  // persistent workgroups of 256 threads, one 16-byte vector per thread and round: eight per compute
-  // unit for the plain stream, as many as the LDS holds beside the static tables with the bins
-  const size_t lds = freq ? (size_t)dict * 4 : 0;
-  const size_t per_cu = std::max<size_t>(1, std::min<size_t>(8, kLdsPerCU / (lds + 4096)));
-  const size_t total = h->total, per_wg = (size_t)kQsThreads * Vec16<T>::N;
-  const unsigned grid = (unsigned)std::min<size_t>((total + per_wg - 1) / per_wg, per_cu * h->num_cu);
-  if (freq) {
-    static std::atomic<uint64_t> once{0};
-    TRY(allow_big_lds_once(k_quantize_symbols<T, true>, once, kQsymLdsBytes));
-  }
-  return launch(h, "quantize_symbols", st, [&] {
-    if (freq)
-      k_quantize_symbols<T, true><<<grid, kQsThreads, lds, st>>>(
-          ds->qmeta, total, coeff, ds->marks, ds->qz, nlev, (int)dict, sym, freq, (unsigned long long *)qo.ocount,
-          qo.oidx, qo.oval, (unsigned long long)qo.ocap);
-    else
-      k_quantize_symbols<T, false><<<grid, kQsThreads, 0, st>>>(
-          ds->qmeta, total, coeff, ds->marks, ds->qz, nlev, (int)dict, sym, nullptr, (unsigned long long *)qo.ocount,
-          qo.oidx, qo.oval, (unsigned long long)qo.ocap);
-  });
+  return qsym_launch<T, false>(h, ds->qmeta, coeff, ds->qz, dict, sym, freq, qo, nullptr, st);
 }
 
-// mgh_quantize_symbols_residual: the four tables of the round trip, then one launch of
-// k_quantize_symbols_residual, sized as quantize_symbols_impl sizes its own. The caller has zeroed the
-// counter and the bins. The residual is dense.
+// mgh_quantize_symbols_residual: the four tables of the round trip. The residual is dense.
 template <typename T>
 int quantize_symbols_residual_impl(mgh_hierarchy *h, const T *coeff, Layout in, const Bound &b, double norm,
                                    uint64_t dict, uint16_t *sym, uint32_t *freq, const QuantOut &qo, T *residual,
                                    hipStream_t st) {
-  auto *ds = DS<T>(h);
-  const int nlev = h->L + 1;
-  if (nlev > kMaxLevels) return fail(MGH_ERR_INVALID_ARGUMENT, "too many levels");
   TRY(ld_pack<T>(h, coeff, in, false, st));
   QuantMeta qm;
   TRY(upload_roundtrip_tables<T>(h, b, norm, qm, st));
-  const size_t lds = freq ? (size_t)dict * 4 : 0;
-  const size_t per_cu = std::max<size_t>(1, std::min<size_t>(8, kLdsPerCU / (lds + 4096)));
-  const size_t total = h->total, per_wg = (size_t)kQsThreads * Vec16<T>::N;
-  const unsigned grid = (unsigned)std::min<size_t>((total + per_wg - 1) / per_wg, per_cu * h->num_cu);
-  if (freq) {
-    static std::atomic<uint64_t> once{0};
-    TRY(allow_big_lds_once(k_quantize_symbols_residual<T, true>, once, kQsymLdsBytes));
-  }
-  return launch(h, "quantize_symbols_residual", st, [&] {
-    if (freq)
-      k_quantize_symbols_residual<T, true><<<grid, kQsThreads, lds, st>>>(
-          qm, total, coeff, ds->marks, ds->qr_tab, nlev, (int)dict, sym, freq, (unsigned long long *)qo.ocount, qo.oidx,
-          qo.oval, (unsigned long long)qo.ocap, residual);
-    else
-      k_quantize_symbols_residual<T, false><<<grid, kQsThreads, 0, st>>>(
-          qm, total, coeff, ds->marks, ds->qr_tab, nlev, (int)dict, sym, nullptr, (unsigned long long *)qo.ocount,
-          qo.oidx, qo.oval, (unsigned long long)qo.ocap, residual);
-  });
+  return qsym_launch<T, true>(h, qm, coeff, DS<T>(h)->qr_tab, dict, sym, freq, qo, residual, st);
 }
 
 // mgh_dequantize_add: the table of mgh_dequantize by its own upload, the outliers back into the integers
@@ -3078,12 +3079,12 @@ int quantize_symbols_residual_impl(mgh_hierarchy *h, const T *coeff, Layout in, 
 template <typename T>
 int dequantize_add_impl(mgh_hierarchy *h, int64_t *q, const QuantSpec &qs, bool first, T *acc, hipStream_t st) {
   auto *ds = DS<T>(h);
-  const int nlev = h->L + 1;
-  if (nlev > kMaxLevels) return fail(MGH_ERR_INVALID_ARGUMENT, "too many levels");
+  unsigned grid;
+  TRY(stream_grid(h, kQaThreads, Vec16<T>::N, 0, 8, &grid));
   TRY(upload_quantizers<T>(h, qs.ebtype, qs.tol, qs.s, qs.norm, false, st));
   TRY(outliers_back(h, qs, "outlier_restore", st, k_outlier_restore, q, h->total));
-  const size_t total = h->total, per_wg = (size_t)kQaThreads * Vec16<T>::N;
-  const unsigned grid = (unsigned)std::min<size_t>((total + per_wg - 1) / per_wg, 8 * h->num_cu);
+  const size_t total = h->total;
+  const int nlev = h->L + 1;
   const int64_t shift = qs.prep_huffman ? (int64_t)qs.dict_size / 2 : 0;
   return launch(h, "dequantize_add", st, [&] {
     if (first)

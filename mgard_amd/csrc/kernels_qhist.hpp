@@ -10,16 +10,12 @@
 // the CU's 160), few persistent workgroups stride over the array, and a workgroup ends with one global
 // atomic per used bin and one per tolerance with outliers, like huff::k_histogram.
 //
-// The level of an element is the largest of its per-dimension marks (level_of). The array is walked in
-// 16-byte vectors of the fastest dimension where the pointer allows it: a vector divides its linear
-// index once (32-bit: the entry point refuses 2^32 elements and more, the counters are 32-bit), takes
-// the level of the slow dimensions from the row index, and moves on by one column per element.
+// The walk is stream_levels (kernels_qwalk.hpp).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "kernels_v1.hpp"
-#include "kernels_fused.hpp"  // kMaxLevels
+#include "kernels_qwalk.hpp"
 
 namespace mgh {
 
@@ -32,12 +28,12 @@ k_quantize_histograms(QuantMeta m, size_t total, const T *__restrict__ v, const 
                       int dict, unsigned *__restrict__ freq /* [K][dict] */,
                       unsigned long long *__restrict__ outliers /* [K] */) {
   extern __shared__ unsigned qh_bins[];  // [K][dict]
-  __shared__ T s_qz[K * kMaxLevels];
-  __shared__ T s_vol[kMaxLevels];
+  __shared__ T s_qz[K][kMaxLevels];
+  __shared__ T s_vol[1][kMaxLevels];
   __shared__ unsigned s_out[(kQhThreads / 64) * K];
   for (int i = threadIdx.x; i < K * dict; i += kQhThreads) qh_bins[i] = 0;
-  for (int i = threadIdx.x; i < K * nlev; i += kQhThreads) s_qz[i] = qz[i];
-  for (int i = threadIdx.x; i < nlev; i += kQhThreads) s_vol[i] = vol[i];
+  stage_tables<kQhThreads>(qz, nlev, s_qz);
+  stage_tables<kQhThreads>(vol, nlev, s_vol);
   __syncthreads();
 
   const int64_t half = (int64_t)dict / 2;
@@ -45,10 +41,10 @@ k_quantize_histograms(QuantMeta m, size_t total, const T *__restrict__ v, const 
 #pragma unroll
   for (int k = 0; k < K; k++) oc[k] = 0;
   auto count = [&](T t, int level) {
-    const T volume = m.calc_vol ? s_vol[level] : (T)1;
+    const T volume = m.calc_vol ? s_vol[0][level] : (T)1;
 #pragma unroll
     for (int k = 0; k < K; k++) {
-      int64_t q = quantize_one(t, s_qz[k * nlev + level], volume);
+      int64_t q = quantize_one(t, s_qz[k][level], volume);
       q += half;
       if (q >= 0 && q < (int64_t)dict) {
         atomicAdd(&qh_bins[k * dict + (int)q], 1u);
@@ -58,65 +54,16 @@ k_quantize_histograms(QuantMeta m, size_t total, const T *__restrict__ v, const 
       }
     }
   };
-  // rows of the fastest dimension: lin = row * nf + col
-  const int fd = m.D - 1;
-  const uint32_t nf = m.shape[fd];
-  const int *__restrict__ fmarks = marks + m.markoff[fd];
-  auto slow_level = [&](uint32_t row) {
-    int level = 0;
-    for (int d = fd - 1; d >= 0; d--) {
-      const uint32_t id = row % m.shape[d];
-      row /= m.shape[d];
-      const int lv = marks[m.markoff[d] + id];
-      level = lv > level ? lv : level;
-    }
-    return level;
-  };
-
   constexpr int VN = Vec16<T>::N;
   typedef T NV __attribute__((ext_vector_type(VN)));
-  const size_t tid = (size_t)blockIdx.x * kQhThreads + threadIdx.x;
-  const size_t nth = (size_t)gridDim.x * kQhThreads;
-  size_t done = 0;
-  if ((reinterpret_cast<uintptr_t>(v) & 15) == 0) {
-    const size_t nvec = total / VN;
-    const NV *vv = reinterpret_cast<const NV *>(v);
-    for (size_t i = tid; i < nvec; i += nth) {
-      const NV x = vv[i];
-      const uint32_t lin = (uint32_t)(i * VN);
-      uint32_t row = 0, col = 0;
-      int rl = 0;
-      if (m.calc_vol) {
-        row = lin / nf;
-        col = lin - row * nf;
-        rl = slow_level(row);
-      }
+  stream_levels<kQhThreads, VN>(
+      m, marks, total, aligned16(v),
+      [&](size_t i, LevelCursor &cur) {
+        const NV x = reinterpret_cast<const NV *>(v)[i];
 #pragma unroll
-      for (int u = 0; u < VN; u++) {
-        int level = 0;
-        if (m.calc_vol) {
-          const int lv = fmarks[col];
-          level = lv > rl ? lv : rl;
-          if (++col == nf) {  // (the vector runs on into the next row)
-            col = 0;
-            row++;
-            if (u + 1 < VN) rl = slow_level(row);
-          }
-        }
-        count(x[u], level);
-      }
-    }
-    done = nvec * VN;
-  }
-  for (size_t k = done + tid; k < total; k += nth) {
-    int level = 0;
-    if (m.calc_vol) {
-      const uint32_t lin = (uint32_t)k, row = lin / nf, col = lin - row * nf;
-      const int rl = slow_level(row), lv = fmarks[col];
-      level = lv > rl ? lv : rl;
-    }
-    count(v[k], level);
-  }
+        for (int u = 0; u < VN; u++) count(x[u], cur.next(u + 1 < VN));
+      },
+      [&](size_t k, int level) { count(v[k], level); });
 
   // outlier counts: wave, workgroup, one global atomic per tolerance
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;

@@ -1,83 +1,73 @@
 // A coefficient array to what the lossless stage reads, in one pass (mgh_quantize_symbols; the second
 // entry into the high-level writer): 16-bit symbols, the outlier list and,
-// optionally, the histogram of the symbols.
+// optionally, the histogram of the symbols. And the two kernels of the precision layers (DESIGN.md
+// sections 4 and 8), where tier k of a layer set stores the quantized residual the tiers before it left in
+// the COEFFICIENTS: that quantizer with one more output (writer, mgh_quantize_symbols_residual) and the
+// dequantizer that adds to what is there (reader, mgh_dequantize_add).
 //
-// For every element the kernel computes what k_quantize computes with prep_huffman = 1 --
+// For every element the symbol kernels compute what k_quantize computes with prep_huffman = 1 --
 // quantize_one() itself with the level's reciprocal quantizer and the level's volume, plus dict / 2 --
-// and stores it as uint16_t when it lies in [0, dict); else it stores symbol 0 and appends (linear
-// index, that int64) to the outlier list, as k_quantize does.
-//
-// Outlier slots are requested ONCE per workgroup and round (k_quantize's scheme: a request per wave
-// queues on the counter), and none in a round without outliers. The counter goes
-// on counting past `outlier_cap`; nothing is written past it.
+// and store it as uint16_t when it lies in [0, dict); else they store symbol 0 and append (linear
+// index, that int64) to the outlier list, as k_quantize does (append_outliers, kernels_qwalk.hpp).
 //
 // HIST: the stored symbols are counted in bins privatised in LDS (dict <= 16384: 64 KB); a workgroup
 // ends with one global atomic per used bin, like huff::k_histogram, which this replaces. An outlier
 // counts in bin 0, the symbol stored for it. The centre symbol dict / 2 -- most of a smooth field --
 // is counted in a register and reaches its bin once per wave.
 //
-// The walk is k_quantize_histograms's (kernels_qhist.hpp): persistent workgroups stride over the array
-// in groups of one 16-byte vector of the fastest dimension; a group divides its linear index once
-// (32-bit: the entry point refuses 2^32 elements and more), takes the level of the slow dimensions from
-// the row index and moves on by one column per element. A group is loaded as one vector where the
-// pointer is 16-byte aligned and the group is whole, element by element otherwise (a misaligned view,
-// the tail); its symbols leave as one plain vector store (8 bytes per 4 floats) on the same terms.
+// RES (k_quantize_symbols_residual): in addition, per element,
+//     r_out = r - (qz[level] * vol_d[level]) * (T)q
+// with q the exact int64 BEFORE the dictionary shift (for an outlier: the value that travels through the
+// list, never the symbol 0 stored in its place) and the subtrahend k_dequantize's own expression on
+// k_dequantize's own two tables: four tables in LDS (QTab) instead of the quantizer's two. Multiply,
+// multiply and subtract are three IEEE operations (the build has -ffp-contract=off). A thread reads its
+// vector before it writes it and no thread touches another's, so r_out == v (in place) is allowed; the
+// two pointers are therefore not __restrict__.
+//
+// The walk is the level cursor's (kernels_qwalk.hpp) over groups of one 16-byte vector. A group is loaded
+// as one vector where the pointer is 16-byte aligned and the group is whole, element by element otherwise
+// (a misaligned view, the tail); its symbols leave as one plain vector store (8 bytes per 4 floats), and
+// its residuals as one, on the same terms.
+//
+// k_dequantize_add is k_dequantize on int64 integers whose outliers are written back already
+// (k_outlier_restore), as a pure stream (stream_levels) with its two tables in LDS. FIRST stores
+// k_dequantize's value (it is not added to zero: -0.0 stays -0.0); otherwise acc = acc + that value, one
+// IEEE add. 8 + esz bytes read (2 esz with the accumulator) and esz written per element, no atomics.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "kernels_v1.hpp"
-#include "kernels_fused.hpp"  // kMaxLevels
+#include "kernels_qwalk.hpp"
 
 namespace mgh {
 
 constexpr int kQsThreads = 256;
 
-template <typename T, bool HIST>
-__global__ void __launch_bounds__(kQsThreads)
-k_quantize_symbols(QuantMeta m, size_t total, const T *__restrict__ v, const int *__restrict__ marks,
-                   const T *__restrict__ tab /* [2][nlev]: reciprocal quantizers, volumes */, int nlev, int dict,
-                   uint16_t *__restrict__ sym, unsigned *__restrict__ freq /* [dict], HIST only */,
-                   unsigned long long *outlier_count, uint64_t *__restrict__ outlier_idx,
-                   int64_t *__restrict__ outlier_val, unsigned long long outlier_cap) {
+template <typename T, bool HIST, bool RES>
+__device__ __forceinline__ void quantize_symbols_body(const QuantMeta &m, size_t total, const T *v,
+                                                      const int *__restrict__ marks, const T *__restrict__ tab, int nlev,
+                                                      int dict, uint16_t *__restrict__ sym, unsigned *__restrict__ freq,
+                                                      unsigned long long *outlier_count, uint64_t *__restrict__ outlier_idx,
+                                                      int64_t *__restrict__ outlier_val, unsigned long long outlier_cap,
+                                                      T *r_out /* RES only */) {
   extern __shared__ unsigned qs_bins[];  // [dict], HIST only
-  __shared__ T s_qz[kMaxLevels];
-  __shared__ T s_vol[kMaxLevels];
-  __shared__ unsigned wcnt[kQsThreads / 64];
-  __shared__ unsigned long long gbase;
+  __shared__ T s_tab[RES ? 4 : 2][kMaxLevels];
   if (HIST)
     for (int i = threadIdx.x; i < dict; i += kQsThreads) qs_bins[i] = 0;
-  for (int i = threadIdx.x; i < nlev; i += kQsThreads) {
-    s_qz[i] = tab[i];
-    s_vol[i] = tab[nlev + i];
-  }
+  stage_tables<kQsThreads>(tab, nlev, s_tab);
   __syncthreads();
 
   const int64_t half = (int64_t)dict / 2;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  // rows of the fastest dimension: lin = row * nf + col
-  const int fd = m.D - 1;
-  const uint32_t nf = m.shape[fd];
-  const int *__restrict__ fmarks = marks + m.markoff[fd];
-  auto slow_level = [&](uint32_t row) {
-    int level = 0;
-    for (int d = fd - 1; d >= 0; d--) {
-      const uint32_t id = row % m.shape[d];
-      row /= m.shape[d];
-      const int lv = marks[m.markoff[d] + id];
-      level = lv > level ? lv : level;
-    }
-    return level;
-  };
-
   constexpr int VN = Vec16<T>::N;
   typedef T NV __attribute__((ext_vector_type(VN)));
   typedef uint16_t SV __attribute__((ext_vector_type(VN)));
-  const bool vec_in = (reinterpret_cast<uintptr_t>(v) & 15) == 0;
+  const bool vec_in = aligned16(v);
   const bool vec_out = (reinterpret_cast<uintptr_t>(sym) & (sizeof(SV) - 1)) == 0;
+  const bool vec_res = RES && aligned16(r_out);
   const size_t ngroup = (total + VN - 1) / VN;
+  LevelCursor cur(m, marks);
   unsigned centre = 0;  // HIST: symbols dict / 2 this thread has seen
-  // (uniform trip count per workgroup: the barriers below are reached by every thread)
+  // (uniform trip count per workgroup: the barriers of append_outliers are reached by every thread)
   const size_t stride = (size_t)gridDim.x * kQsThreads;
   for (size_t gb = (size_t)blockIdx.x * kQsThreads; gb < ngroup; gb += stride) {
     const size_t g = gb + threadIdx.x;
@@ -96,66 +86,37 @@ k_quantize_symbols(QuantMeta m, size_t total, const T *__restrict__ v, const int
     }
     int64_t qd[VN];
     bool outl[VN];
+    NV res;
     unsigned mine = 0;
-    uint32_t row = 0, col = 0;
-    int rl = 0;
-    if (m.calc_vol && cnt > 0) {
-      const uint32_t lin = (uint32_t)lin0;
-      row = lin / nf;
-      col = lin - row * nf;
-      rl = slow_level(row);
-    }
+    if (cnt > 0) cur.seek((uint32_t)lin0);
 #pragma unroll
     for (int u = 0; u < VN; u++) {
       qd[u] = 0;
       outl[u] = false;
+      res[u] = (T)0;
       if (u < cnt) {
-        int level = 0;
-        if (m.calc_vol) {
-          const int lv = fmarks[col];
-          level = lv > rl ? lv : rl;
-          if (++col == nf) {  // (the group runs on into the next row)
-            col = 0;
-            row++;
-            if (u + 1 < cnt) rl = slow_level(row);
-          }
+        const int level = cur.next(u + 1 < cnt);
+        const int64_t q = quantize_one(x[u], s_tab[kTabRqz][level], m.calc_vol ? s_tab[kTabQvol][level] : (T)1);
+        if constexpr (RES) {
+          const T volume = m.calc_vol ? s_tab[kTabDvol][level] : (T)1;
+          const T back = (s_tab[kTabQz][level] * volume) * (T)q;  // (k_dequantize's value of this integer)
+          res[u] = x[u] - back;
         }
-        qd[u] = quantize_one(x[u], s_qz[level], m.calc_vol ? s_vol[level] : (T)1) + half;
+        qd[u] = q + half;
         outl[u] = !(qd[u] >= 0 && qd[u] < (int64_t)dict);
         mine += outl[u] ? 1u : 0u;
       }
     }
-    if (__syncthreads_or((int)mine)) {
-      unsigned incl = mine;  // inclusive scan of the counts inside the wave
-      for (int d = 1; d < 64; d <<= 1) {
-        const unsigned t = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += t;
-      }
-      if (lane == 63) wcnt[wave] = incl;
-      __syncthreads();
-      if (threadIdx.x == 0) {
-        unsigned tot = 0;
-        for (int w = 0; w < kQsThreads / 64; w++) {
-          const unsigned c = wcnt[w];
-          wcnt[w] = tot;
-          tot += c;
-        }
-        gbase = tot ? atomicAdd(outlier_count, (unsigned long long)tot) : 0ull;
-      }
-      __syncthreads();
-      unsigned long long o = gbase + wcnt[wave] + (incl - mine);
+    if constexpr (RES) {
+      if (whole && vec_res) {
+        reinterpret_cast<NV *>(r_out)[g] = res;
+      } else {
 #pragma unroll
-      for (int u = 0; u < VN; u++)
-        if (outl[u]) {
-          if (o < outlier_cap) {
-            outlier_idx[o] = lin0 + u;
-            outlier_val[o] = qd[u];
-          }
-          qd[u] = 0;
-          o++;
-        }
-      __syncthreads();  // (wcnt / gbase are rewritten by the next round)
+        for (int u = 0; u < VN; u++)
+          if (u < cnt) r_out[lin0 + u] = res[u];
+      }
     }
+    append_outliers<kQsThreads>(mine, outl, qd, lin0, outlier_count, outlier_idx, outlier_val, outlier_cap);
     SV s;
 #pragma unroll
     for (int u = 0; u < VN; u++) {
@@ -173,14 +134,72 @@ k_quantize_symbols(QuantMeta m, size_t total, const T *__restrict__ v, const int
         if (u < cnt) sym[lin0 + u] = s[u];
     }
   }
+  if (HIST) flush_bins<kQsThreads>(qs_bins, dict, centre, (int)half, freq);
+}
 
-  if (HIST) {
-    for (int off = 32; off > 0; off >>= 1) centre += __shfl_down(centre, off, 64);
-    if (lane == 0 && centre) atomicAdd(&qs_bins[(int)half], centre);
-    __syncthreads();  // (every count of the workgroup is in the bins)
-    for (int i = threadIdx.x; i < dict; i += kQsThreads)
-      if (qs_bins[i]) atomicAdd(&freq[i], qs_bins[i]);
-  }
+template <typename T, bool HIST>
+__global__ void __launch_bounds__(kQsThreads)
+k_quantize_symbols(QuantMeta m, size_t total, const T *__restrict__ v, const int *__restrict__ marks,
+                   const T *__restrict__ tab /* [2][nlev]: reciprocal quantizers, volumes */, int nlev, int dict,
+                   uint16_t *__restrict__ sym, unsigned *__restrict__ freq /* [dict], HIST only */,
+                   unsigned long long *outlier_count, uint64_t *__restrict__ outlier_idx,
+                   int64_t *__restrict__ outlier_val, unsigned long long outlier_cap) {
+  quantize_symbols_body<T, HIST, false>(m, total, v, marks, tab, nlev, dict, sym, freq, outlier_count, outlier_idx,
+                                        outlier_val, outlier_cap, nullptr);
+}
+
+template <typename T, bool HIST>
+__global__ void __launch_bounds__(kQsThreads)
+k_quantize_symbols_residual(QuantMeta m, size_t total, const T *v, const int *__restrict__ marks,
+                            const T *__restrict__ tab /* [4][nlev]: QTab */, int nlev, int dict,
+                            uint16_t *__restrict__ sym, unsigned *__restrict__ freq /* [dict], HIST only */,
+                            unsigned long long *outlier_count, uint64_t *__restrict__ outlier_idx,
+                            int64_t *__restrict__ outlier_val, unsigned long long outlier_cap, T *r_out) {
+  quantize_symbols_body<T, HIST, true>(m, total, v, marks, tab, nlev, dict, sym, freq, outlier_count, outlier_idx,
+                                       outlier_val, outlier_cap, r_out);
+}
+
+constexpr int kQaThreads = 256;
+
+template <typename T, bool FIRST>
+__global__ void __launch_bounds__(kQaThreads)
+k_dequantize_add(QuantMeta m, size_t total, const int64_t *__restrict__ q, const int *__restrict__ marks,
+                 const T *__restrict__ tab /* [2][nlev]: quantizers, dequantize volumes */, int nlev, int64_t shift,
+                 T *__restrict__ acc) {
+  __shared__ T s_tab[2][kMaxLevels];
+  stage_tables<kQaThreads>(tab, nlev, s_tab);
+  __syncthreads();
+
+  auto value = [&](int64_t qd, int level) -> T {
+    const T volume = m.calc_vol ? s_tab[1][level] : (T)1;
+    return (s_tab[0][level] * volume) * (T)(qd - shift);
+  };
+  constexpr int VN = Vec16<T>::N;
+  typedef T NV __attribute__((ext_vector_type(VN)));
+  typedef int64_t Q2 __attribute__((ext_vector_type(2)));  // (16 bytes: a vector of T takes VN / 2 of them)
+  stream_levels<kQaThreads, VN>(
+      m, marks, total, aligned16(q, acc),
+      [&](size_t i, LevelCursor &cur) {
+        int64_t qd[VN];
+#pragma unroll
+        for (int u = 0; u < VN; u += 2) {
+          const Q2 two = reinterpret_cast<const Q2 *>(q)[i * (VN / 2) + u / 2];
+          qd[u] = two[0];
+          qd[u + 1] = two[1];
+        }
+        NV y;
+        if (!FIRST) y = reinterpret_cast<NV *>(acc)[i];
+#pragma unroll
+        for (int u = 0; u < VN; u++) {
+          const T add = value(qd[u], cur.next(u + 1 < VN));
+          y[u] = FIRST ? add : y[u] + add;
+        }
+        reinterpret_cast<NV *>(acc)[i] = y;
+      },
+      [&](size_t k, int level) {
+        const T add = value(q[k], level);
+        acc[k] = FIRST ? add : acc[k] + add;
+      });
 }
 
 }  // namespace mgh

@@ -77,6 +77,14 @@ def test_histograms_are_the_quantizers(shape, dt, rel, s, dict_size, ntol, nonun
     if ntol >= 3:
         assert outl[0] > 0.9 * n                                       # nearly every value an outlier ...
         assert freq[-1, dict_size // 2] == n and outl[-1] == 0         # ... and every value in the middle bin
+    if shape in ((65, 40), SMALL):
+        # the misaligned scalar route: a view that starts one element into an allocation
+        store = torch.empty(n + 1, dtype=c.dtype, device=c.device)
+        off = store[1:].view(shape)
+        off.copy_(c)
+        assert off.data_ptr() % 16 != 0 and off.is_contiguous()
+        freq1, outl1 = h.quantize_histograms(off, tols, eb, s, norm, dict_size=dict_size)
+        assert np.array_equal(freq1.cpu().numpy(), freq) and np.array_equal(outl1.cpu().numpy(), outl)
     # a second call on the same handle zeroes its outputs itself
     freq2, outl2 = h.quantize_histograms(c, tols[:1], eb, s, norm, dict_size=dict_size)
     assert np.array_equal(freq2.cpu().numpy()[0], freq[0]) and int(outl2[0]) == int(outl[0])
