@@ -120,6 +120,15 @@ int hl_fail(int code, const std::string &msg) {
     if (_rc != MGH_SUCCESS) return _rc;    \
   } while (0)
 
+// The body of an extern "C" entry: no exception leaves the library, it becomes the entry's status.
+template <typename Body> int hl_guarded(Body &&body) {
+  try {
+    return body();
+  } catch (const std::exception &e) {
+    return hl_fail(MGH_ERR_DEVICE, e.what());
+  }
+}
+
 // the dynamic-LDS limit of some kernels, once per device (hl_attr_pending)
 template <typename... K> int hl_lds_limit(std::atomic<uint64_t> &once, int bytes, K... kernels) {
   if (!hl_attr_pending(once)) return MGH_SUCCESS;
@@ -1401,6 +1410,27 @@ struct Pretouch {
   ~Pretouch() { join(); }
 };
 
+// The output of a call that allocates it unless the caller brought it (prealloc): in the memory space of
+// the call's input (`dev`), device memory or host_alloc_large. A failed call goes out through fail(rc),
+// which frees and clears only what alloc() made.
+struct OutSlot {
+  void **slot;
+  bool dev, prealloc;
+  int alloc(size_t bytes) const {
+    if (prealloc) return MGH_SUCCESS;
+    if (dev) HL_HIP(hipMalloc(slot, bytes));
+    else if (!(*slot = host_alloc_large(bytes))) return hl_fail(MGH_ERR_OUT_OF_MEMORY, "malloc");
+    return MGH_SUCCESS;
+  }
+  int fail(int rc) const {
+    if (rc != MGH_SUCCESS && !prealloc) {
+      if (dev) (void)hipFree(*slot); else std::free(*slot);
+      *slot = nullptr;
+    }
+    return rc;
+  }
+};
+
 // A box of an array <-> a dense buffer, both in memory of the current device: one launch whatever
 // the dimension (the reference copies subdomains with its own N-D kernels too:
 // DomainDecomposer.hpp:649-845). One wave per row of the box; W = 4- or 8-byte words.
@@ -1783,7 +1813,7 @@ int header_from(const Decomposer &dd, int dtype, int ebtype, double tol, double 
 }
 
 // ---- what the two entries into the writer share (compress_impl from the caller's data, -------------
-// ---- SizeEstimator::write from coefficients already on the device) --------------------------------
+// ---- CoefficientSession::write from coefficients already on the device) ---------------------------
 // What the last writing call of this thread did (mgh_last_compress_stats).
 inline mgh_compress_stats &compress_stats() {
   thread_local mgh_compress_stats s{};
@@ -1796,6 +1826,84 @@ struct RecordSink {
   size_t cap = 0, byte_offset = 0;
   bool out_dev = false;
 };
+
+// The output of a writing call into `sink`: the caller's buffer of *size bytes, or one the call allocates
+// for an array of n elements stored raw (CompressionHighLevel.hpp:147-162).
+int writer_output(const OutSlot &o, size_t n, size_t elem, const size_t *size, RecordSink &sink) {
+  sink.cap = o.prealloc ? *size : n * elem + (size_t)1e6;
+  HL_TRY(o.alloc(sink.cap));
+  sink.out = *o.slot, sink.out_dev = is_device_pointer(*o.slot);
+  return MGH_SUCCESS;
+}
+
+// The lane's outlier lists for ocap pairs, their counter and the lane's pinned words.
+int ensure_lane_lists(Lane &L, uint64_t ocap) {
+  HL_TRY(L.ocount.ensure(8));
+  HL_TRY(L.oidx.ensure(ocap * 8));
+  HL_TRY(L.oval.ensure(ocap * 8));
+  L.ocap = std::max(L.ocap, ocap);  // (grow-only buffers: an earlier call may have left more)
+  HL_TRY(L.pin.ensure(64));
+  return MGH_SUCCESS;
+}
+
+// The header of a writing call and the size of its metadata, behind which the sink's records start. The
+// size is known up front: the header does not depend on the payloads, except for the norm of a
+// non-decomposed REL run, whose encoding has a fixed length (a non-zero double).
+int header_step(const Decomposer &dd, int dtype, int ebtype, double tol, double s, double norm,
+                const std::vector<std::vector<double>> *coords, const mgh_config &cfg, RecordSink &sink,
+                fmt::Header &hdr, size_t &meta_size) {
+  header_from(dd, dtype, ebtype, tol, s, norm, coords, cfg, hdr);
+  meta_size = fmt::serialize_metadata(hdr).size();
+  if (meta_size > sink.cap) return hl_fail(MGH_ERR_OUTPUT_TOO_LARGE, "output buffer too small for the header");
+  sink.byte_offset = meta_size;
+  // (sized once, here: an asynchronous copy out of it must never meet a re-allocation)
+  return g_cache.hpin.ensure(64 + meta_size);
+}
+
+// The lossless stage's job for one subdomain of n elements: the integers q_enc, the lane's outlier lists.
+LosslessJob subdomain_job(const Lane &L, const mgh_config &cfg, const int64_t *q_enc, uint64_t n, size_t elem,
+                          bool sym16, bool bins_filled) {
+  LosslessJob lj;
+  lj.d_q = q_enc;
+  lj.n = n;
+  lj.dict = cfg.huff_dict_size;
+  lj.chunk = cfg.huff_block_size;
+  lj.lossless = cfg.lossless;
+  lj.zstd_level = cfg.zstd_compress_level;
+  lj.d_oidx = (const uint64_t *)L.oidx.p;
+  lj.d_oval = (const int64_t *)L.oval.p;
+  lj.ocount = 0;  // (read back together with the encoder's results)
+  lj.d_ocount = (const uint64_t *)L.ocount.p;
+  lj.ocap = L.ocap;
+  lj.cap_units = n * elem / 8 + 1;
+  lj.sym16 = sym16;
+  lj.bins_filled = bins_filled;
+  return lj;
+}
+
+// Whether a host array under this bound has its norm reduced while it arrives (stream_in_with_norm), given
+// that the fused path, which takes the streamed norm, runs on its hierarchy (mgh_sym16_supported).
+// MGH_HL_STREAM_NORM=0: norm after arrival (cross-check).
+bool norm_streams_in(bool in_dev, int ebtype) {
+  return !in_dev && ebtype == MGH_REL && env_get("MGH_HL_STREAM_NORM", 1) != 0;
+}
+
+// One subdomain arriving from the host under a REL bound: into dst on the copy stream, in_ready[0] behind
+// it, its norm reduced piece by piece on the lane's stream lst while the following pieces are still on
+// the link (the norm pass is a pure reduction). For s != inf the norm is a sum over these pieces, so both
+// entries into the writer come through here: their headers hold the same bits.
+int stream_in_with_norm(mgh_hierarchy *h, void *dst, const void *src, size_t bytes, size_t elem, double s,
+                        hipStream_t lst) {
+  HL_TRY(mgh_norm_stream_begin(h, lst));
+  const size_t warm = (size_t)192 << 20;  // (what the level pass may still find cached)
+  const ChunkFn on_piece = [=](size_t off, size_t nb, hipEvent_t landed) -> int {
+    HL_HIP(hipStreamWaitEvent(lst, landed, 0));
+    return mgh_norm_stream_add(h, (const char *)dst + off, nb / elem, s, off + nb + warm < bytes ? 1 : 0, lst);
+  };
+  HL_TRY(copy_any(dst, src, bytes, g_cache.copy_st, &on_piece));
+  if (hipEventRecord(g_cache.in_ready[0], g_cache.copy_st) != hipSuccess) return hl_fail(MGH_ERR_DEVICE, "hipEventRecord");
+  return MGH_SUCCESS;
+}
 
 // The second half of a subdomain's lossless stage (lossless_begin is queued on the lane), with the retry
 // of an outlier overflow: estimate_outlier_ratio was too optimistic, so the lane's lists grow to what the
@@ -1896,16 +2004,10 @@ int compress_impl(int D, int dtype, const uint64_t *shape, double tol_d, double 
     }
   }
   const std::vector<std::vector<double>> *cptr = coords_in ? &coords : nullptr;
-  // output buffer, same memory space as the input (CompressionHighLevel.hpp:147-162)
-  size_t cap;
-  if (!prealloc) {
-    cap = total * elem + (size_t)1e6;
-    if (in_dev) HL_HIP(hipMalloc(compressed, cap));
-    else if (!(*compressed = host_alloc_large(cap))) return hl_fail(MGH_ERR_OUT_OF_MEMORY, "malloc");
-  } else {
-    cap = *compressed_size;
-  }
-  const bool out_dev = is_device_pointer(*compressed);
+  // output buffer, same memory space as the input
+  const OutSlot slot{compressed, in_dev, prealloc};
+  RecordSink sink;
+  HL_TRY(writer_output(slot, total, elem, compressed_size, sink));
   // pin the host buffers for asynchronous transfers (auto_pin_host_buffers,
   // CompressionHighLevel.hpp:164-189: input and output)
   bool pinned_here = false, out_pinned_here = false;
@@ -1915,8 +2017,8 @@ int compress_impl(int D, int dtype, const uint64_t *shape, double tol_d, double 
     else
       (void)hipGetLastError();
   }
-  if (!out_dev && cfg.auto_pin_host_buffers && !is_registered_host(*compressed)) {
-    if (hipHostRegister(*compressed, cap, hipHostRegisterDefault) == hipSuccess)
+  if (!sink.out_dev && cfg.auto_pin_host_buffers && !is_registered_host(*compressed)) {
+    if (hipHostRegister(*compressed, sink.cap, hipHostRegisterDefault) == hipSuccess)
       out_pinned_here = true;
     else
       (void)hipGetLastError();
@@ -1936,11 +2038,7 @@ int compress_impl(int D, int dtype, const uint64_t *shape, double tol_d, double 
     owned_alive.clear();
     if (pinned_here) (void)hipHostUnregister(const_cast<void *>(original));
     if (out_pinned_here) (void)hipHostUnregister(*compressed);
-    if (rc != MGH_SUCCESS && !prealloc) {
-      if (in_dev) (void)hipFree(*compressed); else std::free(*compressed);
-      *compressed = nullptr;
-    }
-    return rc;
+    return slot.fail(rc);
   };
   const uint64_t max_elems = dd.max_subdomain_elems();
   const uint64_t ocap = std::max<uint64_t>(1, (uint64_t)(cfg.estimate_outlier_ratio * (double)max_elems));
@@ -1980,11 +2078,7 @@ int compress_impl(int D, int dtype, const uint64_t *shape, double tol_d, double 
       Lane &L = g_cache.lane[l];
       HL_TRY(L.q.ensure(max_elems * 8));
       if (cfg.reorder) HL_TRY(L.q2.ensure(max_elems * 8));
-      HL_TRY(L.ocount.ensure(8));
-      HL_TRY(L.oidx.ensure(ocap * 8));
-      HL_TRY(L.oval.ensure(ocap * 8));
-      L.ocap = std::max(L.ocap, ocap);  // (grow-only buffers: an earlier call may have left more)
-      HL_TRY(L.pin.ensure(64));
+      HL_TRY(ensure_lane_lists(L, ocap));
     }
     return MGH_SUCCESS;
   };
@@ -2040,16 +2134,12 @@ int compress_impl(int D, int dtype, const uint64_t *shape, double tol_d, double 
     local_eb = MGH_ABS;  // CompressionHighLevel.hpp:135-138
   }
 
-  // metadata size is known up front: the header does not depend on the payloads, except for
-  // the norm of a non-decomposed REL run, whose encoding has a fixed length (a non-zero double)
+  // (the norm of a non-decomposed REL run is the pipeline's to compute: any non-zero double stands in)
   fmt::Header hdr;
-  header_from(dd, dtype, ebtype, tol_d, s_d, ebtype == MGH_REL ? (dd.decomposed ? (double)norm : 1.0) : 0.0, cptr, cfg, hdr);
-  const size_t meta_size = fmt::serialize_metadata(hdr).size();
-  if (meta_size > cap) return cleanup(hl_fail(MGH_ERR_OUTPUT_TOO_LARGE, "output buffer too small for the header"));
-  // (sized once, here: an asynchronous copy out of it must never meet a re-allocation)
-  if ((rc = g_cache.hpin.ensure(64 + meta_size)) != MGH_SUCCESS) return cleanup(rc);
-  RecordSink sink;
-  sink.out = *compressed, sink.cap = cap, sink.byte_offset = meta_size, sink.out_dev = out_dev;
+  size_t meta_size;
+  if ((rc = header_step(dd, dtype, ebtype, tol_d, s_d, ebtype == MGH_REL ? (dd.decomposed ? (double)norm : 1.0) : 0.0,
+                        cptr, cfg, sink, hdr, meta_size)) != MGH_SUCCESS)
+    return cleanup(rc);
 
   // ---- subdomain pipeline (compress_pipeline_gpu, GPUPipelines.hpp:69-207) ----
   // issue(k): decomposition + quantizer + histogram of subdomain k queued on lane k % nlanes, no
@@ -2131,21 +2221,8 @@ int compress_impl(int D, int dtype, const uint64_t *shape, double tol_d, double 
                                  (const uint64_t *)L.ocount.p, 0, L.ocap, st));
       q_enc = (const int64_t *)L.q2.p;
     }
-    LosslessJob &lj = J.lj;
-    lj.d_q = q_enc;
-    lj.n = J.n;
-    lj.dict = cfg.huff_dict_size;
-    lj.chunk = cfg.huff_block_size;
-    lj.lossless = cfg.lossless;
-    lj.zstd_level = cfg.zstd_compress_level;
-    lj.d_oidx = (const uint64_t *)L.oidx.p;
-    lj.d_oval = (const int64_t *)L.oval.p;
-    lj.ocount = 0;  // (read back together with the encoder's results)
-    lj.d_ocount = (const uint64_t *)L.ocount.p;
-    lj.ocap = L.ocap;
-    lj.cap_units = J.n * elem / 8 + 1;
-    lj.sym16 = J.sym16;
-    return lossless_begin(L.ll, lj, st);
+    J.lj = subdomain_job(L, cfg, q_enc, J.n, elem, J.sym16, /*bins_filled=*/false);
+    return lossless_begin(L.ll, J.lj, st);
   };
   auto finish = [&](SubJob &J) -> int {
     Lane &L = g_cache.lane[J.lane];
@@ -2185,30 +2262,19 @@ int compress_impl(int D, int dtype, const uint64_t *shape, double tol_d, double 
   // At the start of iteration id the buffer of subdomain id + P is the one subdomain id - 1 used,
   // and finish(id - 1) ended with a synchronisation of its lane.
   const uint64_t P = nbufs > 0 ? (uint64_t)(nbufs - 1) : 0;
-  // One subdomain arriving from the host under a REL bound: its norm is reduced piece by piece on
-  // the lane's stream while the following pieces are still on the link (the norm pass is a pure
-  // reduction), so the decomposition starts when the last piece has landed instead of a whole norm
-  // pass later. MGH_HL_STREAM_NORM=0: norm after arrival (cross-check).
+  // One subdomain arriving from the host under a REL bound: its norm is reduced while it arrives
+  // (stream_in_with_norm), so the decomposition starts when the last piece has landed instead of a whole
+  // norm pass later; issue() waits for in_ready[0] and the fused call takes the norm from the hierarchy.
   bool first_fetched = false;
-  if (dd.num == 1 && !in_dev && ebtype == MGH_REL && env_get("MGH_HL_STREAM_NORM", 1) != 0) {
+  if (dd.num == 1 && norm_streams_in(in_dev, ebtype)) {
     if ((rc = get_hierarchy(&pre_h, &pre_owned, dtype, dd.subdomain_shape(0), cptr, dd.subdomain_offset(0), cfg, 0)) !=
         MGH_SUCCESS)
       return cleanup(rc);
     if (pre_owned) owned_alive.push_back(pre_h);
     if (mgh_sym16_supported(pre_h)) {  // (= the fused path will run, which takes the streamed norm)
-      hipStream_t lst = g_cache.lane[0].st;
-      if ((rc = mgh_norm_stream_begin(pre_h, lst)) != MGH_SUCCESS) return cleanup(rc);
-      const size_t bytes = total * elem, warm = (size_t)192 << 20;  // (what the level pass may still find cached)
-      mgh_hierarchy *const hh = pre_h;
-      const ChunkFn on_piece = [&, hh, lst](size_t off, size_t nb, hipEvent_t landed) -> int {
-        HL_HIP(hipStreamWaitEvent(lst, landed, 0));
-        return mgh_norm_stream_add(hh, (const char *)g_cache.in[0].p + off, nb / elem, s_d,
-                                   off + nb + warm < bytes ? 1 : 0, lst);
-      };
-      if ((rc = copy_any(g_cache.in[0].p, original, bytes, g_cache.copy_st, &on_piece)) != MGH_SUCCESS)
+      if ((rc = stream_in_with_norm(pre_h, g_cache.in[0].p, original, total * elem, elem, s_d, g_cache.lane[0].st)) !=
+          MGH_SUCCESS)
         return cleanup(rc);
-      if (hipEventRecord(g_cache.in_ready[0], g_cache.copy_st) != hipSuccess)
-        return cleanup(hl_fail(MGH_ERR_DEVICE, "hipEventRecord"));
       first_fetched = true;
     }
   }
@@ -2562,12 +2628,10 @@ int decompress_impl(const fmt::Header &hd, size_t meta_size, const void *compres
   HL_TRY(record_view_header(hd, rv_hd));
   const bool in_dev = is_device_pointer(compressed);
   Pretouch pretouch;  // (joined before the first byte of the output is written, and on every way out)
-  if (!prealloc) {
-    if (in_dev) HL_HIP(hipMalloc(out, total * elem));
-    else if (!(*out = host_alloc_large(total * elem))) return hl_fail(MGH_ERR_OUT_OF_MEMORY, "malloc");
-    // fresh host pages: faulted in beside the decoder instead of inside the device -> host copy
-    if (!in_dev) pretouch.start(*out, total * elem);
-  }
+  const OutSlot slot{out, in_dev, prealloc};
+  HL_TRY(slot.alloc(total * elem));
+  // fresh host pages: faulted in beside the decoder instead of inside the device -> host copy
+  if (!prealloc && !in_dev) pretouch.start(*out, total * elem);
   // auto_pin_host_buffers (CompressionHighLevel.hpp:470-497): stream and output registered for the call
   bool in_pinned_here = false, out_pinned_here = false;
   if (cfg.auto_pin_host_buffers) {
@@ -2593,11 +2657,7 @@ int decompress_impl(const fmt::Header &hd, size_t meta_size, const void *compres
     pretouch.join();
     if (in_pinned_here) (void)hipHostUnregister(const_cast<void *>(compressed));
     if (out_pinned_here) (void)hipHostUnregister(*out);
-    if (rc != MGH_SUCCESS && !prealloc) {
-      if (in_dev) (void)hipFree(*out); else std::free(*out);
-      *out = nullptr;
-    }
-    return rc;
+    return slot.fail(rc);
   };
   const uint64_t max_elems = dd.max_subdomain_elems();
   int rc;
@@ -2796,15 +2856,51 @@ int check_config(const mgh_config *cfg) {
   return MGH_SUCCESS;
 }
 
+// What every entry that takes an array checks, in this order. `given`: the caller's pre-allocated output.
+int size_call_args(int D, int dtype, const uint64_t *shape, int ebtype, const void *original, const mgh_config *config,
+                   void *const *given = nullptr) {
+  if (!shape || !original) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (D < 1 || D > MGH_MAX_DIM) return hl_fail(MGH_ERR_UNSUPPORTED_DIMENSION, "D must be 1..5");
+  if (dtype != MGH_FLOAT && dtype != MGH_DOUBLE) return hl_fail(MGH_ERR_UNSUPPORTED_DTYPE, "dtype");
+  if (ebtype != MGH_REL && ebtype != MGH_ABS) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "error_bound_type");
+  if (given && !*given) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "pre-allocated output is NULL");
+  const std::string bad = env_validate();  // MGH_* developer switches: a typo is an error
+  if (!bad.empty()) return hl_fail(MGH_ERR_INVALID_ARGUMENT, bad);
+  HL_TRY(check_config(config));
+  if (hipSetDevice(config->dev_id) != hipSuccess) return hl_fail(MGH_ERR_DEVICE, "hipSetDevice");
+  return MGH_SUCCESS;
+}
+
+// The K tolerances and K output slots of mgh_compress_ladder / _layers (`who` starts the refusals).
+int tolerance_list_args(const char *who, int ntol, const double *tols, void *const *slots, bool prealloc,
+                        bool strictly_decreasing) {
+  const std::string w(who);
+  if (ntol < 1 || ntol > kLadderMaxTols) return hl_fail(MGH_ERR_INVALID_ARGUMENT, w + "ntol must be in 1..64");
+  for (int k = 0; k < ntol; k++) {
+    if (!(tols[k] > 0) || !std::isfinite(tols[k]))
+      return hl_fail(MGH_ERR_INVALID_ARGUMENT, w + "every tolerance must be positive and finite");
+    if (strictly_decreasing && k > 0 && !(tols[k] < tols[k - 1]))
+      return hl_fail(MGH_ERR_INVALID_ARGUMENT, w + "the tolerances must be strictly decreasing");
+    if (prealloc && !slots[k]) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "pre-allocated output is NULL");
+  }
+  return MGH_SUCCESS;
+}
+
+// The session below keeps one array's coefficients: a configuration that decomposes the domain is refused.
+int one_subdomain_only(const char *who, const Decomposer &dd) {
+  if (dd.decomposed || dd.num != 1)
+    return hl_fail(MGH_ERR_INVALID_ARGUMENT,
+                   std::string(who) + "the configuration decomposes the domain (containers of one subdomain only)");
+  return MGH_SUCCESS;
+}
+
 // ---- sizes from histograms: mgh_estimate_sizes, mgh_compress_budget (size_plan.hpp) ---------------
 // ---- errors from round trips: mgh_achieved_errors, mgh_compress_target (target_plan.hpp) ----------
-// One array decomposed once, its coefficients kept on the device (lane 0's integer buffer, free
-// between calls) while tolerances are priced against them (price) or their reconstructions compared
-// with the input (achieved).
-struct SizeEstimator {
-  // what the decomposition is for: a size is a function of the histogram under Huffman alone; an
-  // achieved error does not depend on the lossless stage at all, and a ladder takes either
-  enum class Purpose { sizes, errors, ladder, layers };
+// ---- containers from them: mgh_compress_ladder, mgh_compress_layers, the last step of budget and target
+// The session of one array: decomposed once (begin), its coefficients kept on the device (lane 0's
+// integer buffer, free between calls) while tolerances are priced against them (price), their
+// reconstructions compared with the input (achieved), and containers written from them (write).
+struct CoefficientSession {
   int D = 0, dtype = 0, ebtype = 0;
   std::vector<uint64_t> shape_v;
   const void *d_in = nullptr;  // the input on the device: the caller's array, or its upload
@@ -2822,7 +2918,7 @@ struct SizeEstimator {
   std::vector<uint64_t> outl;
   huff::Codebook cb;
   bool res_in_q3 = false;  // write(layer): the coefficients the next layer reads are in lane 0's q3, not its q
-  ~SizeEstimator() {
+  ~CoefficientSession() {
     if (h && owned) mgh_hierarchy_destroy(h);
   }
 
@@ -2832,26 +2928,25 @@ struct SizeEstimator {
     return rc;
   }
 
-  // upload (host input), norm of a REL bound with the reduction compress_impl will use, decomposition
-  int begin(int D_, int dtype_, const uint64_t *shape, double s_, int ebtype_, const void *original,
-            const void *const *coords_in, const mgh_config &cfg_, Purpose purpose = Purpose::sizes) {
+  // an output of this array's calls: in the input's memory space
+  OutSlot out_slot(void **slot, bool prealloc) const { return OutSlot{slot, in_dev, prealloc}; }
+
+  // Upload (host input), norm of a REL bound with the reduction compress_impl uses, decomposition. `who`
+  // starts the refusals ("size estimates: "). huffman_only: the call prices -- a size is a function of the
+  // histogram under Huffman alone; an achieved error does not depend on the lossless stage at all, and
+  // a written container takes either.
+  int begin(const char *who, bool huffman_only, int D_, int dtype_, const uint64_t *shape, double s_, int ebtype_,
+            const void *original, const void *const *coords_in, const mgh_config &cfg_) {
     D = D_, dtype = dtype_, ebtype = ebtype_, s = s_, cfg = cfg_;
     elem = dtype == MGH_FLOAT ? 4 : 8;
     shape_v.assign(shape, shape + D);
-    if (purpose == Purpose::sizes && cfg.lossless != MGH_LOSSLESS_HUFFMAN)
-      return hl_fail(MGH_ERR_INVALID_ARGUMENT, "size estimates: lossless must be Huffman (a Zstd frame's size is no function of the histogram)");
+    if (huffman_only && cfg.lossless != MGH_LOSSLESS_HUFFMAN)
+      return hl_fail(MGH_ERR_INVALID_ARGUMENT,
+                     std::string(who) + "lossless must be Huffman (a Zstd frame's size is no function of the histogram)");
     HL_TRY(cache_prepare(cfg.dev_id));
     HL_TRY(trim_hierarchy_cache());
     HL_TRY(make_decomposer(dd, D, shape, elem, cfg));
-    if (dd.decomposed || dd.num != 1)
-      return hl_fail(MGH_ERR_INVALID_ARGUMENT,
-                     purpose == Purpose::sizes
-                         ? "size estimates: the configuration decomposes the domain (containers of one subdomain only)"
-                     : purpose == Purpose::errors
-                         ? "achieved errors: the configuration decomposes the domain (containers of one subdomain only)"
-                     : purpose == Purpose::ladder
-                         ? "compress_ladder: the configuration decomposes the domain (containers of one subdomain only)"
-                         : "compress_layers: the configuration decomposes the domain (containers of one subdomain only)");
+    HL_TRY(one_subdomain_only(who, dd));
     n = 1;
     for (int d = 0; d < D; d++) n *= shape[d];
     if (coords_in) {
@@ -2873,27 +2968,17 @@ struct SizeEstimator {
       HL_TRY(g_cache.in[0].ensure(bytes));
       d_in = g_cache.in[0].p;
       int rc;
-      if (ebtype == MGH_REL && env_get("MGH_HL_STREAM_NORM", 1) != 0 && mgh_sym16_supported(h)) {
-        // (compress_impl reduces the norm of such an input piece by piece while it arrives: the same
-        // pieces here, so that a sum of squares has the same partial sums)
-        if ((rc = mgh_norm_stream_begin(h, st)) != MGH_SUCCESS) return fail_drained(rc);
-        const size_t warm = (size_t)192 << 20;
-        mgh_hierarchy *const hh = h;
-        const double sd = s;
-        const size_t el = elem;
-        const ChunkFn on_piece = [&, hh, st, sd, el](size_t off, size_t nb, hipEvent_t landed) -> int {
-          HL_HIP(hipStreamWaitEvent(st, landed, 0));
-          return mgh_norm_stream_add(hh, (const char *)g_cache.in[0].p + off, nb / el, sd, off + nb + warm < bytes ? 1 : 0, st);
-        };
-        if ((rc = copy_any(g_cache.in[0].p, original, bytes, g_cache.copy_st, &on_piece)) != MGH_SUCCESS) return fail_drained(rc);
-        have_norm = true;
-      } else if ((rc = copy_any(g_cache.in[0].p, original, bytes, g_cache.copy_st)) != MGH_SUCCESS) {
-        return fail_drained(rc);
-      }
-      if (hipEventRecord(g_cache.in_ready[0], g_cache.copy_st) != hipSuccess ||
-          hipStreamWaitEvent(st, g_cache.in_ready[0], 0) != hipSuccess)
+      // (where compress_impl reduces the norm of such an input while it arrives, so does this)
+      const bool streamed = norm_streams_in(in_dev, ebtype) && mgh_sym16_supported(h);
+      if (streamed) rc = stream_in_with_norm(h, g_cache.in[0].p, original, bytes, elem, s, st);
+      else if ((rc = copy_any(g_cache.in[0].p, original, bytes, g_cache.copy_st)) == MGH_SUCCESS &&
+               hipEventRecord(g_cache.in_ready[0], g_cache.copy_st) != hipSuccess)
+        rc = hl_fail(MGH_ERR_DEVICE, "hipEventRecord");
+      if (rc != MGH_SUCCESS) return fail_drained(rc);
+      if (hipStreamWaitEvent(st, g_cache.in_ready[0], 0) != hipSuccess)
         return fail_drained(hl_fail(MGH_ERR_DEVICE, "hipEventRecord"));
-      if (have_norm && ebtype == MGH_REL && (rc = mgh_norm_stream_end(h, s, &norm, st)) != MGH_SUCCESS) return fail_drained(rc);
+      if (streamed && (rc = mgh_norm_stream_end(h, s, &norm, st)) != MGH_SUCCESS) return fail_drained(rc);
+      have_norm = have_norm || streamed;
     }
     int rc;
     if (!have_norm && (rc = mgh_norm(h, d_in, s, &norm, st)) != MGH_SUCCESS) return fail_drained(rc);
@@ -2921,26 +3006,13 @@ struct SizeEstimator {
   int write(double tol, void **compressed, size_t *compressed_size, bool prealloc, int layer = -1) {
     Lane &L = g_cache.lane[0];
     hipStream_t st = L.st;
-    // output buffer, same memory space as the input, sized as compress_impl sizes it
-    size_t cap;
-    if (!prealloc) {
-      cap = n * elem + (size_t)1e6;
-      if (in_dev) HL_HIP(hipMalloc(compressed, cap));
-      else if (!(*compressed = host_alloc_large(cap))) return hl_fail(MGH_ERR_OUT_OF_MEMORY, "malloc");
-    } else {
-      cap = *compressed_size;
-    }
-    auto cleanup = [&](int rc) {
-      if (rc == MGH_SUCCESS) return rc;
-      fail_drained(rc);
-      if (!prealloc) {
-        if (in_dev) (void)hipFree(*compressed); else std::free(*compressed);
-        *compressed = nullptr;
-      }
-      return rc;
-    };
+    const OutSlot slot = out_slot(compressed, prealloc);
     RecordSink sink;
-    sink.out = *compressed, sink.cap = cap, sink.out_dev = is_device_pointer(*compressed);
+    HL_TRY(writer_output(slot, n, elem, compressed_size, sink));
+    auto cleanup = [&](int rc) {
+      if (rc != MGH_SUCCESS) fail_drained(rc);
+      return slot.fail(rc);
+    };
     const uint64_t dict = cfg.huff_dict_size, chunk = cfg.huff_block_size;
     const bool sym16 = !cfg.reorder && lossless_sym16_ok(dict, chunk) && !qsym_refusal(n, dict);
     const uint64_t ocap = std::max<uint64_t>(1, (uint64_t)(cfg.estimate_outlier_ratio * (double)n));
@@ -2950,16 +3022,12 @@ struct SizeEstimator {
     if (layer >= 0 && (rc = L.q3.ensure(n * elem)) != MGH_SUCCESS) return cleanup(rc);
     const void *const coef = layer >= 0 && res_in_q3 ? L.q3.p : L.q.p;
     void *const residual = layer < 0 ? nullptr : res_in_q3 ? L.q.p : L.q3.p;
-    if ((rc = L.ocount.ensure(8)) != MGH_SUCCESS || (rc = L.oidx.ensure(ocap * 8)) != MGH_SUCCESS ||
-        (rc = L.oval.ensure(ocap * 8)) != MGH_SUCCESS || (rc = L.pin.ensure(64)) != MGH_SUCCESS)
-      return cleanup(rc);
-    L.ocap = std::max(L.ocap, ocap);  // (grow-only buffers: an earlier call may have left more)
+    if ((rc = ensure_lane_lists(L, ocap)) != MGH_SUCCESS) return cleanup(rc);
     fmt::Header hdr;
-    header_from(dd, dtype, ebtype, tol, s, ebtype == MGH_REL ? norm : 0.0, cptr, cfg, hdr);
-    const size_t meta_size = fmt::serialize_metadata(hdr).size();
-    if (meta_size > cap) return cleanup(hl_fail(MGH_ERR_OUTPUT_TOO_LARGE, "output buffer too small for the header"));
-    if ((rc = g_cache.hpin.ensure(64 + meta_size)) != MGH_SUCCESS) return cleanup(rc);
-    sink.byte_offset = meta_size;
+    size_t meta_size;
+    if ((rc = header_step(dd, dtype, ebtype, tol, s, ebtype == MGH_REL ? norm : 0.0, cptr, cfg, sink, hdr, meta_size)) !=
+        MGH_SUCCESS)
+      return cleanup(rc);
 
     LosslessJob lj;
     auto quantize = [&]() -> int {
@@ -2989,21 +3057,7 @@ struct SizeEstimator {
       }
       compress_stats().quantize_passes++;
       if (!fused_bins) compress_stats().histogram_launches++;
-      lj = LosslessJob();
-      lj.d_q = q_enc;
-      lj.n = n;
-      lj.dict = dict;
-      lj.chunk = chunk;
-      lj.lossless = cfg.lossless;
-      lj.zstd_level = cfg.zstd_compress_level;
-      lj.d_oidx = (const uint64_t *)L.oidx.p;
-      lj.d_oval = (const int64_t *)L.oval.p;
-      lj.ocount = 0;  // (read back together with the encoder's results)
-      lj.d_ocount = (const uint64_t *)L.ocount.p;
-      lj.ocap = L.ocap;
-      lj.cap_units = n * elem / 8 + 1;
-      lj.sym16 = sym16;
-      lj.bins_filled = fused_bins;
+      lj = subdomain_job(L, cfg, q_enc, n, elem, sym16, fused_bins);
       return lossless_begin(L.ll, lj, st);
     };
     if ((rc = quantize()) != MGH_SUCCESS) return cleanup(rc);
@@ -3072,18 +3126,6 @@ struct SizeEstimator {
   }
 };
 
-int size_call_args(int D, int dtype, const uint64_t *shape, int ebtype, const void *original, const mgh_config *config) {
-  if (!shape || !original) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "NULL argument");
-  if (D < 1 || D > MGH_MAX_DIM) return hl_fail(MGH_ERR_UNSUPPORTED_DIMENSION, "D must be 1..5");
-  if (dtype != MGH_FLOAT && dtype != MGH_DOUBLE) return hl_fail(MGH_ERR_UNSUPPORTED_DTYPE, "dtype");
-  if (ebtype != MGH_REL && ebtype != MGH_ABS) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "error_bound_type");
-  const std::string bad = env_validate();  // MGH_* developer switches: a typo is an error
-  if (!bad.empty()) return hl_fail(MGH_ERR_INVALID_ARGUMENT, bad);
-  HL_TRY(check_config(config));
-  if (hipSetDevice(config->dev_id) != hipSuccess) return hl_fail(MGH_ERR_DEVICE, "hipSetDevice");
-  return MGH_SUCCESS;
-}
-
 } // namespace
 
 extern "C" {
@@ -3118,27 +3160,15 @@ void mgh_config_default(mgh_config *c) {
 int mgh_compress(int D, int dtype, const uint64_t *shape, double tol, double s, int ebtype,
                  const void *original_data, void **compressed_data, size_t *compressed_size,
                  const void *const *coords, const mgh_config *config, int output_pre_allocated) {
-  if (!shape || !original_data || !compressed_data || !compressed_size)
-    return hl_fail(MGH_ERR_INVALID_ARGUMENT, "NULL argument");
-  if (D < 1 || D > MGH_MAX_DIM) return hl_fail(MGH_ERR_UNSUPPORTED_DIMENSION, "D must be 1..5");
-  if (dtype != MGH_FLOAT && dtype != MGH_DOUBLE) return hl_fail(MGH_ERR_UNSUPPORTED_DTYPE, "dtype");
-  if (ebtype != MGH_REL && ebtype != MGH_ABS) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "error_bound_type");
-  if (output_pre_allocated && !*compressed_data) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "pre-allocated output is NULL");
-  {
-    const std::string bad = env_validate();  // MGH_* developer switches: a typo is an error
-    if (!bad.empty()) return hl_fail(MGH_ERR_INVALID_ARGUMENT, bad);
-  }
-  HL_TRY(check_config(config));
-  if (hipSetDevice(config->dev_id) != hipSuccess) return hl_fail(MGH_ERR_DEVICE, "hipSetDevice");
-  try {
+  if (!compressed_data || !compressed_size) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "NULL argument");
+  HL_TRY(size_call_args(D, dtype, shape, ebtype, original_data, config, output_pre_allocated ? compressed_data : nullptr));
+  return hl_guarded([&]() -> int {
     if (dtype == MGH_FLOAT)
       return compress_impl<float>(D, dtype, shape, tol, s, ebtype, original_data, compressed_data,
                                   compressed_size, coords, *config, output_pre_allocated != 0);
     return compress_impl<double>(D, dtype, shape, tol, s, ebtype, original_data, compressed_data,
                                  compressed_size, coords, *config, output_pre_allocated != 0);
-  } catch (const std::exception &e) {
-    return hl_fail(MGH_ERR_DEVICE, e.what());
-  }
+  });
 }
 
 int mgh_estimate_sizes(int D, int dtype, const uint64_t *shape, int ntol, const double *tols, double s, int ebtype,
@@ -3147,13 +3177,11 @@ int mgh_estimate_sizes(int D, int dtype, const uint64_t *shape, int ntol, const 
   if (!tols || !out) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "NULL argument");
   if (ntol < 1 || ntol > kQhistMaxTols) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "ntol must be in 1..64");
   HL_TRY(size_call_args(D, dtype, shape, ebtype, original_data, config));
-  try {
-    SizeEstimator E;
-    HL_TRY(E.begin(D, dtype, shape, s, ebtype, original_data, coords, *config));
+  return hl_guarded([&]() -> int {
+    CoefficientSession E;
+    HL_TRY(E.begin("size estimates: ", true, D, dtype, shape, s, ebtype, original_data, coords, *config));
     return E.price(ntol, tols, out);
-  } catch (const std::exception &e) {
-    return hl_fail(MGH_ERR_DEVICE, e.what());
-  }
+  });
 }
 
 int mgh_compress_budget(int D, int dtype, const uint64_t *shape, size_t max_bytes, double tol_min, double tol_max,
@@ -3166,10 +3194,10 @@ int mgh_compress_budget(int D, int dtype, const uint64_t *shape, size_t max_byte
     return hl_fail(MGH_ERR_INVALID_ARGUMENT, "compress_budget: 0 < tol_min <= tol_max (finite), rounds in 1..8");
   HL_TRY(size_call_args(D, dtype, shape, ebtype, original_data, config));
   mgh_size_estimate used{};
-  try {
-    SizeEstimator E;
+  return hl_guarded([&]() -> int {
+    CoefficientSession E;
     compress_stats() = mgh_compress_stats{};
-    HL_TRY(E.begin(D, dtype, shape, s, ebtype, original_data, coords, *config));
+    HL_TRY(E.begin("size estimates: ", true, D, dtype, shape, s, ebtype, original_data, coords, *config));
     compress_stats().decompositions++;
     int rc = MGH_SUCCESS;
     std::vector<mgh_size_estimate> seen;  // every candidate priced, in order
@@ -3197,20 +3225,16 @@ int mgh_compress_budget(int D, int dtype, const uint64_t *shape, size_t max_byte
     for (const mgh_size_estimate &e : seen)
       if (e.tol == r.tol) used = e;
     if (estimate_used) *estimate_used = used;
-    // the container of tol_used from the coefficients the candidates were priced on (SizeEstimator::write)
+    // the container of tol_used from the coefficients the candidates were priced on (CoefficientSession::write)
     void *const given = *compressed_data;
     HL_TRY(E.write(*tol_used, compressed_data, compressed_size, output_pre_allocated != 0));
     if (*compressed_size > max_bytes) {  // (the bracket is an invariant of the record's layout: never expected)
-      if (!output_pre_allocated) {
-        if (is_device_pointer(*compressed_data)) (void)hipFree(*compressed_data); else std::free(*compressed_data);
-        *compressed_data = given;
-      }
+      E.out_slot(compressed_data, output_pre_allocated != 0).fail(MGH_ERR_FORMAT);
+      if (!output_pre_allocated) *compressed_data = given;  // (not NULL: what the caller passed in)
       return hl_fail(MGH_ERR_FORMAT, "compress_budget: the container left the estimate's bracket");
     }
     return MGH_SUCCESS;
-  } catch (const std::exception &e) {
-    return hl_fail(MGH_ERR_DEVICE, e.what());
-  }
+  });
 }
 
 int mgh_achieved_errors(int D, int dtype, const uint64_t *shape, int ntol, const double *tols, double s, int ebtype,
@@ -3219,13 +3243,11 @@ int mgh_achieved_errors(int D, int dtype, const uint64_t *shape, int ntol, const
   if (!tols || !out) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "NULL argument");
   if (ntol < 1 || ntol > kTargetMaxTols) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "achieved_errors: ntol must be in 1..64");
   HL_TRY(size_call_args(D, dtype, shape, ebtype, original_data, config));
-  try {
-    SizeEstimator E;
-    HL_TRY(E.begin(D, dtype, shape, s, ebtype, original_data, coords, *config, SizeEstimator::Purpose::errors));
+  return hl_guarded([&]() -> int {
+    CoefficientSession E;
+    HL_TRY(E.begin("achieved errors: ", false, D, dtype, shape, s, ebtype, original_data, coords, *config));
     return E.achieved(ntol, tols, out);
-  } catch (const std::exception &e) {
-    return hl_fail(MGH_ERR_DEVICE, e.what());
-  }
+  });
 }
 
 int mgh_compress_target(int D, int dtype, const uint64_t *shape, int metric, double target, double tol_min,
@@ -3242,10 +3264,10 @@ int mgh_compress_target(int D, int dtype, const uint64_t *shape, int metric, dou
   HL_TRY(size_call_args(D, dtype, shape, ebtype, original_data, config));
   mgh_error_stats used{};
   int evaluated = 0;
-  try {
-    SizeEstimator E;
+  return hl_guarded([&]() -> int {
+    CoefficientSession E;
     compress_stats() = mgh_compress_stats{};
-    HL_TRY(E.begin(D, dtype, shape, s, ebtype, original_data, coords, *config, SizeEstimator::Purpose::errors));
+    HL_TRY(E.begin("achieved errors: ", false, D, dtype, shape, s, ebtype, original_data, coords, *config));
     compress_stats().decompositions++;
     int rc = MGH_SUCCESS;
     std::vector<std::pair<double, mgh_error_stats>> seen;  // every candidate evaluated, in order
@@ -3267,52 +3289,36 @@ int mgh_compress_target(int D, int dtype, const uint64_t *shape, int metric, dou
       if (c.first == r.tol) used = c.second;
     if (stats_used) *stats_used = used;
     if (candidates) *candidates = evaluated;
-    // the container of tol_used from the coefficients the candidates share (SizeEstimator::write)
+    // the container of tol_used from the coefficients the candidates share (CoefficientSession::write)
     return E.write(*tol_used, compressed_data, compressed_size, output_pre_allocated != 0);
-  } catch (const std::exception &e) {
-    return hl_fail(MGH_ERR_DEVICE, e.what());
-  }
+  });
 }
 
 int mgh_compress_ladder(int D, int dtype, const uint64_t *shape, int ntol, const double *tols, double s, int ebtype,
                         const void *original_data, void **compressed_data, size_t *compressed_size,
                         const void *const *coords, const mgh_config *config, int output_pre_allocated) {
   if (!tols || !compressed_data || !compressed_size) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "NULL argument");
-  if (ntol < 1 || ntol > kLadderMaxTols) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "compress_ladder: ntol must be in 1..64");
-  for (int k = 0; k < ntol; k++) {
-    if (!(tols[k] > 0) || !std::isfinite(tols[k]))
-      return hl_fail(MGH_ERR_INVALID_ARGUMENT, "compress_ladder: every tolerance must be positive and finite");
-    if (output_pre_allocated && !compressed_data[k]) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "pre-allocated output is NULL");
-  }
+  HL_TRY(tolerance_list_args("compress_ladder: ", ntol, tols, compressed_data, output_pre_allocated != 0, false));
   HL_TRY(size_call_args(D, dtype, shape, ebtype, original_data, config));
   if (!output_pre_allocated)
     for (int k = 0; k < ntol; k++) compressed_data[k] = nullptr;
-  try {
-    SizeEstimator E;
+  return hl_guarded([&]() -> int {
+    CoefficientSession E;
     compress_stats() = mgh_compress_stats{};
-    HL_TRY(E.begin(D, dtype, shape, s, ebtype, original_data, coords, *config, SizeEstimator::Purpose::ladder));
+    HL_TRY(E.begin("compress_ladder: ", false, D, dtype, shape, s, ebtype, original_data, coords, *config));
     compress_stats().decompositions++;
     // (a failure at tolerance k leaves containers 0 .. k-1 the caller's; write() has freed its own)
     for (int k = 0; k < ntol; k++)
       HL_TRY(E.write(tols[k], &compressed_data[k], &compressed_size[k], output_pre_allocated != 0));
     return MGH_SUCCESS;
-  } catch (const std::exception &e) {
-    return hl_fail(MGH_ERR_DEVICE, e.what());
-  }
+  });
 }
 
 int mgh_compress_layers(int D, int dtype, const uint64_t *shape, int ntol, const double *tols, double s, int ebtype,
                         const void *original_data, void **compressed_data, size_t *compressed_size,
                         const void *const *coords, const mgh_config *config, int output_pre_allocated) {
   if (!tols || !compressed_data || !compressed_size) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "NULL argument");
-  if (ntol < 1 || ntol > kLadderMaxTols) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "compress_layers: ntol must be in 1..64");
-  for (int k = 0; k < ntol; k++) {
-    if (!(tols[k] > 0) || !std::isfinite(tols[k]))
-      return hl_fail(MGH_ERR_INVALID_ARGUMENT, "compress_layers: every tolerance must be positive and finite");
-    if (k > 0 && !(tols[k] < tols[k - 1]))
-      return hl_fail(MGH_ERR_INVALID_ARGUMENT, "compress_layers: the tolerances must be strictly decreasing");
-    if (output_pre_allocated && !compressed_data[k]) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "pre-allocated output is NULL");
-  }
+  HL_TRY(tolerance_list_args("compress_layers: ", ntol, tols, compressed_data, output_pre_allocated != 0, true));
   HL_TRY(size_call_args(D, dtype, shape, ebtype, original_data, config));
   {
     // what the layer writer does not take, before anything is allocated
@@ -3320,9 +3326,7 @@ int mgh_compress_layers(int D, int dtype, const uint64_t *shape, int ntol, const
     for (int d = 0; d < D; d++) n *= shape[d];
     Decomposer dd;
     HL_TRY(make_decomposer(dd, D, shape, dtype == MGH_FLOAT ? 4 : 8, *config));
-    if (dd.decomposed || dd.num != 1)
-      return hl_fail(MGH_ERR_INVALID_ARGUMENT,
-                     "compress_layers: the configuration decomposes the domain (containers of one subdomain only)");
+    HL_TRY(one_subdomain_only("compress_layers: ", dd));
     if (config->reorder)
       return hl_fail(MGH_ERR_INVALID_ARGUMENT, "compress_layers: reorder = 1 is not supported (the layers are reorder = 0 records)");
     if (!lossless_sym16_ok(config->huff_dict_size, config->huff_block_size))
@@ -3333,18 +3337,16 @@ int mgh_compress_layers(int D, int dtype, const uint64_t *shape, int ntol, const
   }
   if (!output_pre_allocated)
     for (int k = 0; k < ntol; k++) compressed_data[k] = nullptr;
-  try {
-    SizeEstimator E;
+  return hl_guarded([&]() -> int {
+    CoefficientSession E;
     compress_stats() = mgh_compress_stats{};
-    HL_TRY(E.begin(D, dtype, shape, s, ebtype, original_data, coords, *config, SizeEstimator::Purpose::layers));
+    HL_TRY(E.begin("compress_layers: ", false, D, dtype, shape, s, ebtype, original_data, coords, *config));
     compress_stats().decompositions++;
     // (a failure at layer k leaves containers 0 .. k-1 the caller's; write() has freed its own)
     for (int k = 0; k < ntol; k++)
       HL_TRY(E.write(tols[k], &compressed_data[k], &compressed_size[k], output_pre_allocated != 0, k));
     return MGH_SUCCESS;
-  } catch (const std::exception &e) {
-    return hl_fail(MGH_ERR_DEVICE, e.what());
-  }
+  });
 }
 
 int mgh_last_compress_stats(mgh_compress_stats *out) {
@@ -3471,15 +3473,13 @@ static int decompress_entry(const void *compressed_data, size_t compressed_size,
         return hl_fail(MGH_ERR_INVALID_ARGUMENT, "the window leaves the array");
   }
   const Window *win = win_lo ? &window : nullptr;
-  try {
+  return hl_guarded([&]() -> int {
     if (hd.is_double)
       return decompress_impl<double>(hd, meta_size, compressed_data, compressed_size, decompressed_data,
                                      *config, output_pre_allocated != 0, level, halvings, preview, win, vfy);
     return decompress_impl<float>(hd, meta_size, compressed_data, compressed_size, decompressed_data,
                                   *config, output_pre_allocated != 0, level, halvings, preview, win, vfy);
-  } catch (const std::exception &e) {
-    return hl_fail(MGH_ERR_DEVICE, e.what());
-  }
+  });
 }
 
 
@@ -3779,13 +3779,7 @@ int compress_multi_impl(int ndev, const int *devs, int D, int dtype, const uint6
     at += body_len[id];
   }
   free_parts();
-  if (!copied) {
-    if (!prealloc) {
-      if (in_dev) (void)hipFree(*compressed); else std::free(*compressed);
-      *compressed = nullptr;
-    }
-    return hl_fail(MGH_ERR_DEVICE, "assembling the container");
-  }
+  if (!copied) return OutSlot{compressed, in_dev, prealloc}.fail(hl_fail(MGH_ERR_DEVICE, "assembling the container"));
   *compressed_size = at;
   return MGH_SUCCESS;
 }
@@ -3883,7 +3877,7 @@ int mgh_compress_multi(int num_dev, const int *dev_ids, int D, int dtype, const 
   // memory of that device. A pre-allocated output must be of the same kind.
   if (output_pre_allocated && is_device_pointer(original_data) != is_device_pointer(*compressed_data))
     return hl_fail(MGH_ERR_INVALID_ARGUMENT, "mgh_compress_multi: input and pre-allocated output must both be host or both be device memory");
-  try {
+  return hl_guarded([&]() -> int {
     if (dtype == MGH_FLOAT)
       return compress_multi_impl<float>(num_dev, dev_ids, D, dtype, shape, tol, s, ebtype, original_data,
                                         compressed_data, compressed_size, coords, *config,
@@ -3891,9 +3885,7 @@ int mgh_compress_multi(int num_dev, const int *dev_ids, int D, int dtype, const 
     return compress_multi_impl<double>(num_dev, dev_ids, D, dtype, shape, tol, s, ebtype, original_data,
                                        compressed_data, compressed_size, coords, *config,
                                        output_pre_allocated != 0);
-  } catch (const std::exception &e) {
-    return hl_fail(MGH_ERR_DEVICE, e.what());
-  }
+  });
 }
 
 int mgh_decompress_multi(int num_dev, const int *dev_ids, const void *compressed_data,
@@ -3921,15 +3913,13 @@ int mgh_decompress_multi(int num_dev, const int *dev_ids, const void *compressed
     c.dev_id = dev_ids[0];
     return mgh_decompress(compressed_data, compressed_size, decompressed_data, &c, output_pre_allocated);
   }
-  try {
+  return hl_guarded([&]() -> int {
     if (hd.is_double)
       return decompress_multi_impl<double>(num_dev, dev_ids, hd, meta_size, compressed_data, compressed_size,
                                            decompressed_data, *config, output_pre_allocated != 0);
     return decompress_multi_impl<float>(num_dev, dev_ids, hd, meta_size, compressed_data, compressed_size,
                                         decompressed_data, *config, output_pre_allocated != 0);
-  } catch (const std::exception &e) {
-    return hl_fail(MGH_ERR_DEVICE, e.what());
-  }
+  });
 }
 
 }  // extern "C"
@@ -4227,7 +4217,7 @@ int mgh_compress_dist(void *nccl_comm, int rank, int nranks, int root, int D, in
   if (!g_rccl.load(nullptr)) return hl_fail(MGH_ERR_NO_DEVICE, "mgh_compress_dist: no RCCL (librccl.so.1) found");
   size_t dummy = 0;
   void *none = nullptr;
-  try {
+  return hl_guarded([&]() -> int {
     if (dtype == MGH_FLOAT)
       return compress_dist_impl<float>(nccl_comm, rank, nranks, root, D, dtype, local_shape, tol, s, ebtype, d_local_data,
                                        rank == root ? compressed_data : &none, rank == root ? compressed_size : &dummy,
@@ -4235,9 +4225,7 @@ int mgh_compress_dist(void *nccl_comm, int rank, int nranks, int root, int D, in
     return compress_dist_impl<double>(nccl_comm, rank, nranks, root, D, dtype, local_shape, tol, s, ebtype, d_local_data,
                                       rank == root ? compressed_data : &none, rank == root ? compressed_size : &dummy,
                                       coords, *config, rank == root && output_pre_allocated != 0);
-  } catch (const std::exception &e) {
-    return hl_fail(MGH_ERR_DEVICE, e.what());
-  }
+  });
 }
 
 int mgh_decompress_dist(void *nccl_comm, int rank, int nranks, int root, const void *compressed_data,
@@ -4254,7 +4242,7 @@ int mgh_decompress_dist(void *nccl_comm, int rank, int nranks, int root, const v
   if (!g_rccl.load(nullptr)) return hl_fail(MGH_ERR_NO_DEVICE, "mgh_decompress_dist: no RCCL (librccl.so.1) found");
   HL_TRY(cache_prepare(config->dev_id));
   hipStream_t st = g_cache.lane[0].st;
-  try {
+  return hl_guarded([&]() -> int {
     // the header travels first: its length, then its bytes
     if (nranks > 1 && rank == root && !is_device_pointer_on(compressed_data, config->dev_id))
       return hl_fail(MGH_ERR_INVALID_ARGUMENT, "mgh_decompress_dist: the container must be resident on the root's device");
@@ -4298,9 +4286,7 @@ int mgh_decompress_dist(void *nccl_comm, int rank, int nranks, int root, const v
                                           d_local_out, *config);
     return decompress_dist_impl<float>(nccl_comm, rank, nranks, root, hd, compressed_data, compressed_size, meta_size,
                                        d_local_out, *config);
-  } catch (const std::exception &e) {
-    return hl_fail(MGH_ERR_DEVICE, e.what());
-  }
+  });
 }
 
 }  // extern "C"
@@ -4579,12 +4565,9 @@ int mgh_lossless_compress(mgh_lossless_ctx *ctx, const int64_t *d_q, uint64_t n,
                           uint64_t *size_out, void *stream) {
   if (!ctx || !d_q || !payload_out || !size_out) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "NULL argument");
   if (hipSetDevice(ctx->dev) != hipSuccess) return hl_fail(MGH_ERR_DEVICE, "hipSetDevice");
-  try {
-    HL_TRY(lossless_compress(ctx, d_q, n, dict, chunk, lossless, zstd_level, d_oidx, d_oval, ocount,
-                             (hipStream_t)stream));
-  } catch (const std::exception &e) {
-    return hl_fail(MGH_ERR_DEVICE, e.what());
-  }
+  HL_TRY(hl_guarded([&] {
+    return lossless_compress(ctx, d_q, n, dict, chunk, lossless, zstd_level, d_oidx, d_oval, ocount, (hipStream_t)stream);
+  }));
   if (!ctx->on_host) {
     ctx->host.resize(ctx->lay.total);
     HL_TRY(record_write(ctx, ctx->host.data(), (hipStream_t)stream));
@@ -4602,13 +4585,11 @@ int mgh_lossless_compress_device(mgh_lossless_ctx *ctx, const int64_t *d_q, uint
   if (!ctx || !d_q || !d_record_out || !size_out) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "NULL argument");
   if (hipSetDevice(ctx->dev) != hipSuccess) return hl_fail(MGH_ERR_DEVICE, "hipSetDevice");
   if (!is_device_pointer(d_record_out)) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "d_record_out must be device memory");
-  try {
-    HL_TRY(lossless_compress(ctx, d_q, n, dict, chunk, MGH_LOSSLESS_HUFFMAN, 0, d_oidx, d_oval, ocount,
+  HL_TRY(hl_guarded([&] {
+    return lossless_compress(ctx, d_q, n, dict, chunk, MGH_LOSSLESS_HUFFMAN, 0, d_oidx, d_oval, ocount,
                              (hipStream_t)stream, nullptr, ~(uint64_t)0, 0, false, (uint8_t *)d_record_out,
-                             (size_t)capacity));
-  } catch (const std::exception &e) {
-    return hl_fail(MGH_ERR_DEVICE, e.what());
-  }
+                             (size_t)capacity);
+  }));
   if (ctx->overflow || ctx->record_size() > capacity)
     return hl_fail(MGH_ERR_OUTPUT_TOO_LARGE, "record does not fit the buffer");
   HL_TRY(record_write(ctx, d_record_out, (hipStream_t)stream));
@@ -4622,11 +4603,7 @@ int mgh_lossless_decompress(mgh_lossless_ctx *ctx, const uint8_t *payload, uint6
                             const int64_t **oval_out, uint64_t *ocount_out, void *stream) {
   if (!ctx || !payload || !d_q || !ocount_out) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "NULL argument");
   if (hipSetDevice(ctx->dev) != hipSuccess) return hl_fail(MGH_ERR_DEVICE, "hipSetDevice");
-  try {
-    HL_TRY(lossless_decompress(ctx, payload, size, lossless, d_q, n, ocount_out, (hipStream_t)stream));
-  } catch (const std::exception &e) {
-    return hl_fail(MGH_ERR_DEVICE, e.what());
-  }
+  HL_TRY(hl_guarded([&] { return lossless_decompress(ctx, payload, size, lossless, d_q, n, ocount_out, (hipStream_t)stream); }));
   if (oidx_out) *oidx_out = (const uint64_t *)ctx->oidx.p;
   if (oval_out) *oval_out = (const int64_t *)ctx->oval.p;
   return MGH_SUCCESS;
@@ -4638,12 +4615,10 @@ int mgh_lossless_decompress_prefix(mgh_lossless_ctx *ctx, const uint8_t *payload
   if (!ctx || !payload || !d_q || !ocount_out) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "NULL argument");
   if (n_prefix == 0) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "mgh_lossless_decompress_prefix: n_prefix is 0");
   if (hipSetDevice(ctx->dev) != hipSuccess) return hl_fail(MGH_ERR_DEVICE, "hipSetDevice");
-  try {
-    HL_TRY(lossless_decompress(ctx, payload, size, lossless, d_q, n, ocount_out, (hipStream_t)stream, nullptr, true,
-                               DecodeRange{n_prefix}));
-  } catch (const std::exception &e) {
-    return hl_fail(MGH_ERR_DEVICE, e.what());
-  }
+  HL_TRY(hl_guarded([&] {
+    return lossless_decompress(ctx, payload, size, lossless, d_q, n, ocount_out, (hipStream_t)stream, nullptr, true,
+                               DecodeRange{n_prefix});
+  }));
   if (oidx_out) *oidx_out = (const uint64_t *)ctx->oidx.p;
   if (oval_out) *oval_out = (const int64_t *)ctx->oval.p;
   return MGH_SUCCESS;
@@ -4656,12 +4631,10 @@ int mgh_lossless_decompress_range(mgh_lossless_ctx *ctx, const uint8_t *payload,
   if (count == 0 || first >= n || count > n - first)
     return hl_fail(MGH_ERR_INVALID_ARGUMENT, "mgh_lossless_decompress_range: first / count outside the record");
   if (hipSetDevice(ctx->dev) != hipSuccess) return hl_fail(MGH_ERR_DEVICE, "hipSetDevice");
-  try {
-    HL_TRY(lossless_decompress(ctx, payload, size, lossless, d_q, n, ocount_out, (hipStream_t)stream, nullptr, true,
-                               DecodeRange{first + count, ~(uint64_t)0, first}));
-  } catch (const std::exception &e) {
-    return hl_fail(MGH_ERR_DEVICE, e.what());
-  }
+  HL_TRY(hl_guarded([&] {
+    return lossless_decompress(ctx, payload, size, lossless, d_q, n, ocount_out, (hipStream_t)stream, nullptr, true,
+                               DecodeRange{first + count, ~(uint64_t)0, first});
+  }));
   if (oidx_out) *oidx_out = (const uint64_t *)ctx->oidx.p;
   if (oval_out) *oval_out = (const int64_t *)ctx->oval.p;
   return MGH_SUCCESS;
@@ -4860,22 +4833,16 @@ int progressive_refine(mgh_progressive *p, int to, void **out, bool prealloc) {
     }
   }
   // the array of to_level out, in the container's memory space
-  if (!prealloc) {
-    if (p->in_dev) HL_HIP(hipMalloc(out, out_bytes));
-    else if (!(*out = host_alloc_large(out_bytes))) return hl_fail(MGH_ERR_OUT_OF_MEMORY, "malloc");
-  }
+  const OutSlot slot{out, p->in_dev, prealloc};
+  HL_TRY(slot.alloc(out_bytes));
   int rc = raw_full ? copy_any(*out, p->rv.rec, out_bytes, st) : copy_any(*out, p->state[at].p, out_bytes, st);
   if (rc == MGH_SUCCESS && hipStreamSynchronize(st) != hipSuccess) rc = hl_fail(MGH_ERR_DEVICE, "sync");
   if (rc == MGH_SUCCESS && p->ll) rc = lossless_tag_check(p->ll);
-  if (rc != MGH_SUCCESS && !prealloc) {
-    if (p->in_dev) (void)hipFree(*out); else std::free(*out);
-    *out = nullptr;
-  }
   if (rc == MGH_SUCCESS) {
     p->si = at;
     p->level = to;
   }
-  return rc;
+  return slot.fail(rc);
 }
 
 // The current level prolonged to the full grid; reads the state, changes none of it (the level
@@ -4884,10 +4851,8 @@ int progressive_preview(mgh_progressive *p, void **out, bool prealloc) {
   hipStream_t st = p->st;
   const size_t out_bytes = p->n * p->elem;
   const bool raw_full = p->rv.raw && p->level == p->L;  // (a raw record IS the finest level: no state)
-  if (!prealloc) {
-    if (p->in_dev) HL_HIP(hipMalloc(out, out_bytes));
-    else if (!(*out = host_alloc_large(out_bytes))) return hl_fail(MGH_ERR_OUT_OF_MEMORY, "malloc");
-  }
+  const OutSlot slot{out, p->in_dev, prealloc};
+  HL_TRY(slot.alloc(out_bytes));
   int rc = MGH_SUCCESS;
   if (raw_full) {
     rc = copy_any(*out, p->rv.rec, out_bytes, st);
@@ -4899,11 +4864,7 @@ int progressive_preview(mgh_progressive *p, void **out, bool prealloc) {
     if (rc == MGH_SUCCESS) rc = copy_any(*out, p->full.p, out_bytes, st);
   }
   if (rc == MGH_SUCCESS && hipStreamSynchronize(st) != hipSuccess) rc = hl_fail(MGH_ERR_DEVICE, "sync");
-  if (rc != MGH_SUCCESS && !prealloc) {
-    if (p->in_dev) (void)hipFree(*out); else std::free(*out);
-    *out = nullptr;
-  }
-  return rc;
+  return slot.fail(rc);
 }
 
 // ... a window of it (mgh_prolong_window): the same reading of the state, window-sized work on the
@@ -4917,10 +4878,8 @@ int progressive_preview_window(mgh_progressive *p, const uint64_t *lo, const uin
     out_bytes *= ext[d];
   }
   const bool raw_full = p->rv.raw && p->level == p->L;  // (a raw record IS the finest level: no state)
-  if (!prealloc) {
-    if (p->in_dev) HL_HIP(hipMalloc(out, out_bytes));
-    else if (!(*out = host_alloc_large(out_bytes))) return hl_fail(MGH_ERR_OUT_OF_MEMORY, "malloc");
-  }
+  const OutSlot slot{out, p->in_dev, prealloc};
+  HL_TRY(slot.alloc(out_bytes));
   int rc = MGH_SUCCESS;
   const void *lvl = p->state[p->si].p;
   if (raw_full && is_device_pointer(p->rv.rec)) {
@@ -4935,11 +4894,7 @@ int progressive_preview_window(mgh_progressive *p, const uint64_t *lo, const uin
   if (rc == MGH_SUCCESS) rc = mgh_prolong_window(p->h, p->level, lvl, lo, ext, out_dev ? *out : p->win.p, st);
   if (rc == MGH_SUCCESS && !out_dev) rc = copy_any(*out, p->win.p, out_bytes, st);
   if (rc == MGH_SUCCESS && hipStreamSynchronize(st) != hipSuccess) rc = hl_fail(MGH_ERR_DEVICE, "sync");
-  if (rc != MGH_SUCCESS && !prealloc) {
-    if (p->in_dev) (void)hipFree(*out); else std::free(*out);
-    *out = nullptr;
-  }
-  return rc;
+  return slot.fail(rc);
 }
 }  // namespace
 
@@ -4962,12 +4917,7 @@ int mgh_progressive_open(mgh_progressive **out, const void *compressed_data, siz
   if (hipSetDevice(config->dev_id) != hipSuccess) return hl_fail(MGH_ERR_DEVICE, "hipSetDevice");
   mgh_progressive *p = new mgh_progressive();
   p->cfg = *config;
-  int rc;
-  try {
-    rc = progressive_open(p, compressed_data, compressed_size);
-  } catch (const std::exception &e) {
-    rc = hl_fail(MGH_ERR_DEVICE, e.what());
-  }
+  const int rc = hl_guarded([&] { return progressive_open(p, compressed_data, compressed_size); });
   if (rc != MGH_SUCCESS) {
     progressive_free(p);
     return rc;
@@ -4985,11 +4935,7 @@ int mgh_progressive_refine(mgh_progressive *p, int to_level, void **data, int ou
   if (to_level <= p->level)
     return hl_fail(MGH_ERR_INVALID_ARGUMENT, "mgh_progressive_refine: to_level must be above the current level");
   if (hipSetDevice(p->cfg.dev_id) != hipSuccess) return hl_fail(MGH_ERR_DEVICE, "hipSetDevice");
-  try {
-    return progressive_refine(p, to_level, data, output_pre_allocated != 0);
-  } catch (const std::exception &e) {
-    return hl_fail(MGH_ERR_DEVICE, e.what());
-  }
+  return hl_guarded([&] { return progressive_refine(p, to_level, data, output_pre_allocated != 0); });
 }
 
 int mgh_progressive_preview(mgh_progressive *p, void **data, int output_pre_allocated) {
@@ -4998,11 +4944,7 @@ int mgh_progressive_preview(mgh_progressive *p, void **data, int output_pre_allo
   if (p->level < 0)
     return hl_fail(MGH_ERR_INVALID_ARGUMENT, "mgh_progressive_preview: nothing refined yet (call mgh_progressive_refine first)");
   if (hipSetDevice(p->cfg.dev_id) != hipSuccess) return hl_fail(MGH_ERR_DEVICE, "hipSetDevice");
-  try {
-    return progressive_preview(p, data, output_pre_allocated != 0);
-  } catch (const std::exception &e) {
-    return hl_fail(MGH_ERR_DEVICE, e.what());
-  }
+  return hl_guarded([&] { return progressive_preview(p, data, output_pre_allocated != 0); });
 }
 
 int mgh_progressive_preview_window(mgh_progressive *p, const uint64_t *lo, const uint64_t *ext, void **data,
@@ -5013,11 +4955,7 @@ int mgh_progressive_preview_window(mgh_progressive *p, const uint64_t *lo, const
     return hl_fail(MGH_ERR_INVALID_ARGUMENT,
                    "mgh_progressive_preview_window: nothing refined yet (call mgh_progressive_refine first)");
   if (hipSetDevice(p->cfg.dev_id) != hipSuccess) return hl_fail(MGH_ERR_DEVICE, "hipSetDevice");
-  try {
-    return progressive_preview_window(p, lo, ext, data, output_pre_allocated != 0);
-  } catch (const std::exception &e) {
-    return hl_fail(MGH_ERR_DEVICE, e.what());
-  }
+  return hl_guarded([&] { return progressive_preview_window(p, lo, ext, data, output_pre_allocated != 0); });
 }
 
 void mgh_progressive_close(mgh_progressive *p) { progressive_free(p); }
@@ -5144,10 +5082,8 @@ int layers_add(mgh_layers *p, const void *data, size_t size) {
 int layers_data(mgh_layers *p, void **out, bool prealloc) {
   hipStream_t st = p->st;
   const size_t out_bytes = p->n * p->elem;
-  if (!prealloc) {
-    if (p->in_dev) HL_HIP(hipMalloc(out, out_bytes));
-    else if (!(*out = host_alloc_large(out_bytes))) return hl_fail(MGH_ERR_OUT_OF_MEMORY, "malloc");
-  }
+  const OutSlot slot{out, p->in_dev, prealloc};
+  HL_TRY(slot.alloc(out_bytes));
   int rc = MGH_SUCCESS;
   if (is_device_pointer(*out)) {
     rc = mgh_recompose(p->h, p->acc.p, *out, st);
@@ -5157,11 +5093,7 @@ int layers_data(mgh_layers *p, void **out, bool prealloc) {
     if (rc == MGH_SUCCESS) rc = copy_any(*out, p->out.p, out_bytes, st);
   }
   if (hipStreamSynchronize(st) != hipSuccess && rc == MGH_SUCCESS) rc = hl_fail(MGH_ERR_DEVICE, "sync");
-  if (rc != MGH_SUCCESS && !prealloc) {
-    if (p->in_dev) (void)hipFree(*out); else std::free(*out);
-    *out = nullptr;
-  }
-  return rc;
+  return slot.fail(rc);
 }
 }  // namespace
 
@@ -5183,12 +5115,7 @@ int mgh_layers_open(mgh_layers **out, const void *compressed_data, size_t compre
   if (hipSetDevice(config->dev_id) != hipSuccess) return hl_fail(MGH_ERR_DEVICE, "hipSetDevice");
   mgh_layers *p = new mgh_layers();
   p->cfg = *config;
-  int rc;
-  try {
-    rc = layers_add(p, compressed_data, compressed_size);
-  } catch (const std::exception &e) {
-    rc = hl_fail(MGH_ERR_DEVICE, e.what());
-  }
+  const int rc = hl_guarded([&] { return layers_add(p, compressed_data, compressed_size); });
   if (rc != MGH_SUCCESS) {
     layers_free(p);
     return rc;
@@ -5200,11 +5127,7 @@ int mgh_layers_open(mgh_layers **out, const void *compressed_data, size_t compre
 int mgh_layers_add(mgh_layers *p, const void *compressed_data, size_t compressed_size) {
   if (!p || !compressed_data) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "NULL argument");
   if (hipSetDevice(p->cfg.dev_id) != hipSuccess) return hl_fail(MGH_ERR_DEVICE, "hipSetDevice");
-  try {
-    return layers_add(p, compressed_data, compressed_size);
-  } catch (const std::exception &e) {
-    return hl_fail(MGH_ERR_DEVICE, e.what());
-  }
+  return hl_guarded([&] { return layers_add(p, compressed_data, compressed_size); });
 }
 
 int mgh_layers_count(const mgh_layers *p) { return p ? p->count : -1; }
@@ -5215,11 +5138,7 @@ int mgh_layers_data(mgh_layers *p, void **data, int output_pre_allocated) {
   if (!p || !data) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "NULL argument");
   if (output_pre_allocated && !*data) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "pre-allocated output is NULL");
   if (hipSetDevice(p->cfg.dev_id) != hipSuccess) return hl_fail(MGH_ERR_DEVICE, "hipSetDevice");
-  try {
-    return layers_data(p, data, output_pre_allocated != 0);
-  } catch (const std::exception &e) {
-    return hl_fail(MGH_ERR_DEVICE, e.what());
-  }
+  return hl_guarded([&] { return layers_data(p, data, output_pre_allocated != 0); });
 }
 
 void mgh_layers_close(mgh_layers *p) { layers_free(p); }

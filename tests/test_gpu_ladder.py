@@ -124,6 +124,25 @@ def test_ladder_containers_are_compress_containers(shape, dt, rel, s, dict_size,
     hl._hl().mgh_release_cache()
 
 
+def test_ladder_header_norm_is_compress_header_norm_over_several_ring_chunks():
+    """Pageable host input of 17.2 MB: two pieces of the 16 MB ring, so the norm of a REL bound with s = 0 is a
+    sum of squares over two partial sums in both entries into the writer. The ladder's header, norm included,
+    must be mgh_compress's byte for byte -- it is only while both entries split the input the same way."""
+    torch, mg, hl = _gpu()
+    u = smooth_field((129, 130, 257), F32)
+    assert u.nbytes > 16 << 20
+    cfg = _config(hl, 1024)
+    tols = [1e-2, 1e-3]
+    got = hl.compress_ladder(u, tols, 0.0, mg.REL, config=cfg)
+    for tol, g in zip(tols, got):
+        want = hl.compress(u, tol, 0.0, mg.REL, config=cfg)
+        gb, wb = _bytes(g), _bytes(want)
+        meta = hl.metadata_parse(wb)["metadata_size"]
+        assert gb[:meta] == wb[:meta]
+        _same_container(hl, g, want, u, cfg, zstd=False)
+    hl._hl().mgh_release_cache()
+
+
 def test_budget_and_target_write_from_their_one_decomposition():
     torch, mg, hl = _gpu()
     cfg = _config(hl, 1024)
