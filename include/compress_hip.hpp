@@ -269,6 +269,37 @@ inline compress_status_type decompress_layers(const std::vector<const void *> &c
   return detail::status(mgh_decompress_layers((int)compressed_data.size(), compressed_data.data(), compressed_size.data(),
                                               &c, &decompressed_data, output_pre_allocated ? 1 : 0));
 }
+// EXTENSION: mgh_compress_masked. compress of an array whose NaN / +-Inf (spec.flags & MGH_MASK_NONFINITE) and / or
+// elements equal to spec.fill_value (MGH_MASK_VALUE) do not count: [container of the filled array][mask record][footer].
+// The first masked_info().container_size bytes open in every reader; the bound holds at every valid position.
+inline compress_status_type compress_masked(DIM D, data_type dtype, std::vector<SIZE> shape, double tol, double s,
+                                            error_bound_type mode, const void *original_data, const mgh_mask_spec &spec,
+                                            void *&compressed_data, size_t &compressed_size,
+                                            std::vector<const Byte *> coords, HighLevelConfig config,
+                                            bool output_pre_allocated) {
+  if (shape.size() != D) return compress_status_type::Failure;
+  const mgh_config c = detail::to_c(config);
+  std::vector<const void *> cp(coords.begin(), coords.end());
+  return detail::status(mgh_compress_masked(D, (int)dtype, shape.data(), tol, s, (int)mode, original_data, &spec,
+                                            &compressed_data, &compressed_size, cp.empty() ? nullptr : cp.data(), &c,
+                                            output_pre_allocated ? 1 : 0));
+}
+// ... its reader (mgh_decompress_masked): spec.restore_value at every masked position. A plain container is a Failure.
+inline compress_status_type decompress_masked(const void *compressed_data, size_t compressed_size,
+                                              void *&decompressed_data, HighLevelConfig config,
+                                              bool output_pre_allocated) {
+  const mgh_config c = detail::to_c(config);
+  return detail::status(mgh_decompress_masked(compressed_data, compressed_size, &c, &decompressed_data,
+                                              output_pre_allocated ? 1 : 0));
+}
+// ... and what the buffer is (mgh_masked_info): masked = false for a plain container (info untouched); a footer
+// that fails a check is a Failure.
+inline compress_status_type masked_info(const void *compressed_data, size_t compressed_size, bool &masked,
+                                        struct mgh_masked_info &info) {
+  const int rc = mgh_masked_info(compressed_data, compressed_size, &info);
+  masked = rc == 1;
+  return rc < 0 ? detail::status(rc) : compress_status_type::Success;
+}
 // EXTENSION: mgh_achieved_errors. What verify(compress(tol)) would report for every tolerance of `tols`
 // (1..64), from one decomposition and without writing a container. Containers of one subdomain (Failure
 // otherwise; mgh_last_error() says so); any supported lossless_type.

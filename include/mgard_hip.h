@@ -542,6 +542,43 @@ int mgh_compare(int D, int dtype, const uint64_t *shape, const void *a, const ui
 int mgh_stream_calibrate(int dtype, const void *d_in, int64_t *d_out, void *d_side, uint64_t n,
                          int reps, double *ms_out, void *stream);
 
+/* ---- Missing-value masks (EXTENSION; the reference has nothing here) --------------------------------
+ * Arrays with NaN / +-Inf or a fill value (1e20, -9999) must not reach the decomposition: its Thomas
+ * solves are global along every dimension. These three streaming passes classify the elements, replace
+ * the masked ones by a deterministic fill, and put a value back at the masked positions afterwards.
+ * They need no hierarchy: D (1 ... MGH_MAX_DIM), shape[D] on the host, dtype, dense DEVICE arrays on the
+ * current device, ASYNCHRONOUS on `stream`. 1 ... 2^32 - 1 elements (MGH_ERR_INVALID_ARGUMENT beyond).
+ *
+ * The packed mask: ceil(n / 64) uint64_t, bit i % 64 of word i / 64 set when flat element i is masked;
+ * the unused high bits of the last word are zero.
+ *
+ * mgh_mask_scan: flags = MGH_MASK_NONFINITE (NaN, +-Inf) | MGH_MASK_VALUE (x == (T)fill_value); 0 and a
+ * NaN fill_value with MGH_MASK_VALUE are MGH_ERR_INVALID_ARGUMENT. Writes `words` and the device
+ * mgh_mask_stats: n, n_masked and the extremes of the VALID elements (vmin = vmax = 0 when there is
+ * none; -0.0 orders below +0.0). Count, minimum and maximum do not depend on the order of the
+ * reduction: the result is deterministic.
+ *
+ * mgh_mask_fill: out (may be data) = data with every masked element replaced. THE RULE IS PART OF THE
+ * INTERFACE -- it can be restated in NumPy to the bit: rows run along the last (fastest) dimension, of
+ * length nf; every row is cut into segments [k 1024, min((k + 1) 1024, nf)), restarting at every row; a
+ * masked element takes the value of the nearest valid element with a SMALLER index in its segment, if
+ * there is none of the nearest one with a LARGER index in its segment, and (T)c if the segment has no
+ * valid element. Valid elements are copied bit for bit; only copies and the one constant occur.
+ *
+ * mgh_mask_restore: data[i] = (T)value (which may be NaN) at every masked i; the rest is untouched. */
+#define MGH_MASK_NONFINITE 1
+#define MGH_MASK_VALUE 2
+typedef struct mgh_mask_stats {
+  uint64_t n, n_masked;
+  double vmin, vmax;
+} mgh_mask_stats;
+int mgh_mask_scan(int D, int dtype, const uint64_t *shape, const void *data, int flags, double fill_value,
+                  uint64_t *words, mgh_mask_stats *stats, void *stream);
+int mgh_mask_fill(int D, int dtype, const uint64_t *shape, const void *data, const uint64_t *words, double c,
+                  void *out, void *stream);
+int mgh_mask_restore(int D, int dtype, const uint64_t *shape, const uint64_t *words, double value, void *data,
+                     void *stream);
+
 #ifdef __cplusplus
 }
 #endif

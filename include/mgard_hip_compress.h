@@ -645,6 +645,56 @@ int mgh_decompress_layers(int nlayers, const void *const *compressed_data /* [nl
                           const size_t *compressed_size /* [nlayers] */, const mgh_config *config,
                           void **decompressed_data, int output_pre_allocated);
 
+/* ---- Arrays with missing values (EXTENSION; mgh_mask_* of mgard_hip.h) -------------------------------
+ * mgh_compress of an array whose NaN / +-Inf (MGH_MASK_NONFINITE) and / or whose elements equal to
+ * (T)fill_value (MGH_MASK_VALUE) do not count: scan -> c = (T)(0.5 vmin + 0.5 vmax), evaluated in double
+ * -> fill (mgh_mask_fill's rule) -> mgh_compress of the filled device array, with tol, s, the bound type,
+ * coords and config (its domain decomposition included) passed through unchanged -> mask record -> footer:
+ *   [ordinary container, C bytes][mask record, R bytes][48-byte footer]      (csrc/mask_plan.hpp)
+ * The first C bytes ARE the container mgh_compress writes for the filled array: every reader opens them
+ * without knowing about masks (stock MGARD-X, mgh_decompress_level, previews, the progressive reader,
+ * mgh_verify against the filled array). The footer is found from the end of the buffer.
+ * The error bound holds at every VALID position: valid elements enter the writer unchanged. The header's
+ * norm (REL) is the FILLED array's, because the header must describe the array the container holds: for
+ * s = inf it equals the absmax of the valid elements exactly (fills are copies of valid values or lie
+ * between vmin and vmax); for finite s it includes the filled points.
+ * Input: a host array (uploaded once, filled in place on the device) or a device array (filled into one
+ * temporary of the array's size). If the array plus that temporary do not fit config->max_memory_footprint
+ * the call is MGH_ERR_INVALID_ARGUMENT: masked arrays that must be streamed in parts are not supported.
+ * 1 ... 2^32 - 1 elements. The output lands in the input's memory space, allocated like mgh_compress's
+ * (plus the packed mask and the footer); MGH_ERR_OUTPUT_TOO_LARGE when a pre-allocated output cannot hold
+ * container + record + footer. Every masked position decodes to restore_value: +Inf and NaN are not told
+ * apart after the round trip. */
+typedef struct mgh_mask_spec {
+  int flags;            /* MGH_MASK_NONFINITE | MGH_MASK_VALUE */
+  double fill_value;    /* read with MGH_MASK_VALUE */
+  double restore_value; /* what mgh_decompress_masked stores at masked positions; may be NaN */
+} mgh_mask_spec;
+int mgh_compress_masked(int D, int dtype, const uint64_t *shape, double tol, double s, int error_bound_type,
+                        const void *original_data, const mgh_mask_spec *spec, void **compressed_data,
+                        size_t *compressed_size, const void *const *coords, const mgh_config *config,
+                        int output_pre_allocated);
+
+/* 1 and *info for a masked buffer, 0 for a buffer without the footer's magic, MGH_ERR_FORMAT for a footer
+ * that has the magic and fails a check (C + R + 48 == size, R against kind and against the n of the
+ * container's header, the record's CRC-32). Host work; of a device buffer the footer, the header and the
+ * record are copied first. kind: 0 packed words, 1 one record of the lossless stage, 2 nothing masked. */
+struct mgh_masked_info { /* (the tag only: the function has the name) */
+  uint64_t container_size, record_size, n_masked;
+  int kind;
+  double restore_value;
+};
+int mgh_masked_info(const void *compressed_data, size_t compressed_size, struct mgh_masked_info *info);
+
+/* mgh_decompress of the first C bytes, then the mask record, then mgh_mask_restore: the array with
+ * restore_value's bits at every masked position. Memory-space rules of mgh_decompress. A buffer without
+ * the footer is MGH_ERR_FORMAT (plain containers have mgh_decompress). */
+int mgh_decompress_masked(const void *compressed_data, size_t compressed_size, const mgh_config *config,
+                          void **decompressed_data, int output_pre_allocated);
+/* The mask alone: one byte per element, 0 or 1, into `mask` (host or device memory of the caller,
+ * n bytes; n from mgh_infer_shape). */
+int mgh_decompress_mask(const void *compressed_data, size_t compressed_size, const mgh_config *config, uint8_t *mask);
+
 #ifdef __cplusplus
 }
 #endif

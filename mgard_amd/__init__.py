@@ -39,6 +39,7 @@ SYMBOLS = [
     "mgh_prolong_window", "mgh_prolong_window_strided", "mgh_debug_prolong_window_ranges",
     "mgh_debug_prolong_window_plan",
     "mgh_compare",
+    "mgh_mask_scan", "mgh_mask_fill", "mgh_mask_restore",
 ]
 
 
@@ -167,6 +168,9 @@ def load_library():
     L.mgh_debug_prolong_window_plan.argtypes = [vp, C.c_int, u64p, u64p, C.c_int, C.POINTER(C.c_int)]
     L.mgh_stream_calibrate.argtypes = [C.c_int, vp, vp, vp, u64, C.c_int, C.POINTER(C.c_double), vp]
     L.mgh_compare.argtypes = [C.c_int, C.c_int, u64p, vp, u64p, vp, u64p, C.POINTER(ErrorStats), C.c_int, vp]
+    L.mgh_mask_scan.argtypes = [C.c_int, C.c_int, u64p, vp, C.c_int, C.c_double, vp, vp, vp]
+    L.mgh_mask_fill.argtypes = [C.c_int, C.c_int, u64p, vp, vp, C.c_double, vp, vp]
+    L.mgh_mask_restore.argtypes = [C.c_int, C.c_int, u64p, vp, C.c_double, vp, vp]
     _lib = L
     return L
 
@@ -243,6 +247,82 @@ def compare(a, b, device=None):
     _check(load_library().mgh_compare(len(shape), dts[0], (C.c_uint64 * max(len(shape), 1))(*shape), ptrs[0], lds[0],
                                       ptrs[1], lds[1], C.byref(out), int(device), stream))
     return out
+
+
+# ---- missing-value masks (mgh_mask_*) ---------------------------------------------------------------------
+MASK_NONFINITE, MASK_VALUE = 1, 2
+
+
+class MaskStats(C.Structure):
+    """mgh_mask_stats: element count, masked count, and the extremes of the valid elements (0, 0 when none)."""
+    _fields_ = [("n", C.c_uint64), ("n_masked", C.c_uint64), ("vmin", C.c_double), ("vmax", C.c_double)]
+
+    def __repr__(self):
+        return "MaskStats(n=%d, n_masked=%d, vmin=%r, vmax=%r)" % (self.n, self.n_masked, self.vmin, self.vmax)
+
+
+def _mask_array(data, what):
+    """(dtype code, shape array, D) of a contiguous float32 / float64 cuda tensor."""
+    import torch
+    if not (isinstance(data, torch.Tensor) and data.is_cuda and data.is_contiguous() and
+            data.dtype in (torch.float32, torch.float64)):
+        raise ValueError("%s: a contiguous float32 / float64 cuda tensor expected" % what)
+    shape = tuple(int(e) for e in data.shape) or (1,)
+    return FLOAT if data.dtype == torch.float32 else DOUBLE, (C.c_uint64 * len(shape))(*shape), len(shape)
+
+
+def _mask_words(words, n, what):
+    import torch
+    if not (isinstance(words, torch.Tensor) and words.is_cuda and words.is_contiguous() and words.dtype == torch.int64 and
+            words.numel() == (n + 63) // 64):
+        raise ValueError("%s: `words` must be the int64 cuda tensor of ceil(n / 64) words mask_scan returns" % what)
+    return C.c_void_p(words.data_ptr())
+
+
+def mask_flags(nonfinite=True, fill_value=None):
+    return (MASK_NONFINITE if nonfinite else 0) | (MASK_VALUE if fill_value is not None else 0)
+
+
+def mask_scan(data, nonfinite=True, fill_value=None):
+    """mgh_mask_scan of a cuda tensor: (words, stats). words: int64 cuda tensor of ceil(n / 64) words, bit i % 64 of
+    word i / 64 set when flat element i is NaN / +-Inf (`nonfinite`) or equals `fill_value` in the data's type;
+    stats: MaskStats over the valid elements."""
+    import torch
+    dt, shp, D = _mask_array(data, "mask_scan")
+    n = data.numel()
+    words = torch.empty((n + 63) // 64, dtype=torch.int64, device=data.device)
+    d_stats = torch.empty(4, dtype=torch.int64, device=data.device)
+    with torch.cuda.device(data.device):
+        _check(load_library().mgh_mask_scan(D, dt, shp, C.c_void_p(data.data_ptr()), mask_flags(nonfinite, fill_value),
+                                            0.0 if fill_value is None else float(fill_value),
+                                            C.c_void_p(words.data_ptr()), C.c_void_p(d_stats.data_ptr()), _stream()))
+    return words, MaskStats.from_buffer_copy(d_stats.cpu().numpy().tobytes())
+
+
+def mask_fill(data, words, c, out=None):
+    """mgh_mask_fill: `data` with every masked element replaced by the nearest valid element below it in its
+    segment of 1024 of its row, else the nearest above, else `c` (in the data's type). out may be data."""
+    import torch
+    dt, shp, D = _mask_array(data, "mask_fill")
+    if out is None:
+        out = torch.empty_like(data)
+    if not (isinstance(out, torch.Tensor) and out.is_cuda and out.is_contiguous() and out.dtype == data.dtype and
+            out.shape == data.shape):
+        raise ValueError("mask_fill: `out` must be a contiguous cuda tensor of the data's shape and type")
+    with torch.cuda.device(data.device):
+        _check(load_library().mgh_mask_fill(D, dt, shp, C.c_void_p(data.data_ptr()), _mask_words(words, data.numel(), "mask_fill"),
+                                            float(c), C.c_void_p(out.data_ptr()), _stream()))
+    return out
+
+
+def mask_restore(data, words, value):
+    """mgh_mask_restore, in place: `value` (in the data's type; may be NaN) at every masked position of `data`."""
+    import torch
+    dt, shp, D = _mask_array(data, "mask_restore")
+    with torch.cuda.device(data.device):
+        _check(load_library().mgh_mask_restore(D, dt, shp, _mask_words(words, data.numel(), "mask_restore"), float(value),
+                                               C.c_void_p(data.data_ptr()), _stream()))
+    return data
 
 
 class Hierarchy:

@@ -50,6 +50,7 @@
 #include "target_plan.hpp"
 #include "kernels_qround.hpp"
 #include "kernels_qsym.hpp"
+#include "kernels_mask.hpp"
 
 namespace {
 
@@ -4411,6 +4412,101 @@ int mgh_compare_device_(int D, int dtype, const uint64_t *shape, const void *d_a
                                  (mgh_error_stats *)d_scratch, st);
   return compare_launch<double>(D, shape, (const double *)d_a, stride_a, (const double *)d_b, stride_b,
                                 (mgh_error_stats *)d_scratch, st);
+}
+
+// ---- missing-value masks (kernels_mask.hpp) -------------------------------------------------------------
+namespace {
+// D, shape, dtype and the element count the three entries share (32-bit-free, but refused from 2^32 on
+// like mgh_quantize_roundtrip: one record of the lossless stage holds the mask)
+int mask_args(const char *who, int D, int dtype, const uint64_t *shape, uint64_t *n_out) {
+  const std::string w(who);
+  if (D < 1 || D > MGH_MAX_DIM) return fail(MGH_ERR_INVALID_ARGUMENT, w + ": D must be 1 .. MGH_MAX_DIM");
+  if (dtype != MGH_FLOAT && dtype != MGH_DOUBLE) return fail(MGH_ERR_INVALID_ARGUMENT, w + ": unknown dtype");
+  if (!shape) return fail(MGH_ERR_INVALID_ARGUMENT, w + ": NULL argument");
+  uint64_t n = 1;
+  for (int d = 0; d < D; d++) {
+    if (shape[d] == 0 || shape[d] > 0xffffffffull || n * shape[d] > 0xffffffffull)
+      return fail(MGH_ERR_INVALID_ARGUMENT, w + ": 1 .. 2^32 - 1 elements");
+    n *= shape[d];
+  }
+  *n_out = n;
+  return MGH_SUCCESS;
+}
+inline unsigned mask_blocks(uint64_t items) {
+  return (unsigned)std::min<uint64_t>(std::max<uint64_t>(items, 1), mgh::mask::kMaxBlocks);
+}
+}  // namespace
+
+int mgh_mask_scan(int D, int dtype, const uint64_t *shape, const void *data, int flags, double fill_value,
+                  uint64_t *words, mgh_mask_stats *stats, void *stream) {
+  uint64_t n = 0;
+  TRY(mask_args("mgh_mask_scan", D, dtype, shape, &n));
+  if (!data || !words || !stats) return fail(MGH_ERR_INVALID_ARGUMENT, "mgh_mask_scan: NULL argument");
+  if (flags == 0 || (flags & ~(MGH_MASK_NONFINITE | MGH_MASK_VALUE)))
+    return fail(MGH_ERR_INVALID_ARGUMENT, "mgh_mask_scan: flags must be MGH_MASK_NONFINITE, MGH_MASK_VALUE or both");
+  if ((flags & MGH_MASK_VALUE) && std::isnan(fill_value))
+    return fail(MGH_ERR_INVALID_ARGUMENT, "mgh_mask_scan: a NaN fill_value (MGH_MASK_NONFINITE masks NaN)");
+  hipStream_t st = (hipStream_t)stream;
+  const uint64_t nwords = mgh::mask_words(n);
+  unsigned long long *s = reinterpret_cast<unsigned long long *>(stats);
+  const unsigned blocks = mask_blocks((nwords + mgh::mask::kWaves * mgh::mask::kScanUnroll - 1) /
+                                      (mgh::mask::kWaves * mgh::mask::kScanUnroll));
+  mgh::mask::k_mask_stats_begin<<<1, 64, 0, st>>>(s);
+  if (dtype == MGH_FLOAT)
+    mgh::mask::k_mask_scan<float><<<blocks, mgh::mask::kThreads, 0, st>>>(
+        (const float *)data, n, nwords, flags, (float)fill_value, (unsigned long long *)words, s);
+  else
+    mgh::mask::k_mask_scan<double><<<blocks, mgh::mask::kThreads, 0, st>>>(
+        (const double *)data, n, nwords, flags, fill_value, (unsigned long long *)words, s);
+  mgh::mask::k_mask_stats_end<<<1, 64, 0, st>>>(s, n);
+  HIP_TRY(hipGetLastError());
+  return MGH_SUCCESS;
+}
+
+// (highlevel.hip: the constant as the bits of (T)c, so that what it derived in double is stored as it is)
+int mgh_mask_fill_bits_(int D, int dtype, const uint64_t *shape, const void *data, const uint64_t *words, uint64_t c_bits,
+                        void *out, void *stream) {
+  uint64_t n = 0;
+  TRY(mask_args("mgh_mask_fill", D, dtype, shape, &n));
+  if (!data || !words || !out) return fail(MGH_ERR_INVALID_ARGUMENT, "mgh_mask_fill: NULL argument");
+  const mgh::MaskSegments G = mgh::mask_segments(D, shape);
+  const unsigned blocks = mask_blocks((G.total + mgh::mask::kWaves - 1) / mgh::mask::kWaves);
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == MGH_FLOAT)
+    mgh::mask::k_mask_fill<uint32_t><<<blocks, mgh::mask::kThreads, 0, st>>>(
+        (const uint32_t *)data, (const unsigned long long *)words, mgh::mask_words(n), G, (uint32_t)c_bits, (uint32_t *)out);
+  else
+    mgh::mask::k_mask_fill<uint64_t><<<blocks, mgh::mask::kThreads, 0, st>>>(
+        (const uint64_t *)data, (const unsigned long long *)words, mgh::mask_words(n), G, c_bits, (uint64_t *)out);
+  HIP_TRY(hipGetLastError());
+  return MGH_SUCCESS;
+}
+
+int mgh_mask_fill(int D, int dtype, const uint64_t *shape, const void *data, const uint64_t *words, double c, void *out,
+                  void *stream) {
+  return mgh_mask_fill_bits_(D, dtype, shape, data, words, mgh::mask_value_bits(dtype == MGH_DOUBLE, c), out, stream);
+}
+
+// (highlevel.hip: the footer's restore_bits as they are)
+int mgh_mask_restore_bits_(int D, int dtype, const uint64_t *shape, const uint64_t *words, uint64_t value_bits, void *data,
+                           void *stream) {
+  uint64_t n = 0;
+  TRY(mask_args("mgh_mask_restore", D, dtype, shape, &n));
+  if (!words || !data) return fail(MGH_ERR_INVALID_ARGUMENT, "mgh_mask_restore: NULL argument");
+  const unsigned blocks = mask_blocks((n + mgh::mask::kThreads - 1) / mgh::mask::kThreads);
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == MGH_FLOAT)
+    mgh::mask::k_mask_restore<uint32_t><<<blocks, mgh::mask::kThreads, 0, st>>>(
+        (const unsigned long long *)words, n, (uint32_t)value_bits, (uint32_t *)data);
+  else
+    mgh::mask::k_mask_restore<uint64_t><<<blocks, mgh::mask::kThreads, 0, st>>>(
+        (const unsigned long long *)words, n, value_bits, (uint64_t *)data);
+  HIP_TRY(hipGetLastError());
+  return MGH_SUCCESS;
+}
+
+int mgh_mask_restore(int D, int dtype, const uint64_t *shape, const uint64_t *words, double value, void *data, void *stream) {
+  return mgh_mask_restore_bits_(D, dtype, shape, words, mgh::mask_value_bits(dtype == MGH_DOUBLE, value), data, stream);
 }
 
 } // extern "C"

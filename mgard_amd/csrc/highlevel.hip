@@ -41,8 +41,14 @@
 #include "domain_plan.hpp"
 #include "size_plan.hpp"
 #include "target_plan.hpp"
+#include "mask_plan.hpp"
 
 extern "C" void mgh_set_last_error_(const char *msg);  // capi.hip
+// (capi.hip: mgh_mask_fill / mgh_mask_restore with the value given as the bits of the data type)
+extern "C" int mgh_mask_fill_bits_(int D, int dtype, const uint64_t *shape, const void *data, const uint64_t *words,
+                                   uint64_t c_bits, void *out, void *stream);
+extern "C" int mgh_mask_restore_bits_(int D, int dtype, const uint64_t *shape, const uint64_t *words, uint64_t value_bits,
+                                      void *data, void *stream);
 // (capi.hip: the reduction of mgh_compare on two device arrays given by element strides, asynchronous)
 extern "C" size_t mgh_compare_scratch_bytes_(void);
 extern "C" void mgh_compare_release_(void);
@@ -1626,13 +1632,16 @@ struct HlCache {
   hipStream_t aux_st = nullptr;   // small device -> host reads that must not wait for the lanes
   PinBuf aux_pin;
   DevBuf vres;  // mgh_verify: one mgh_error_stats per subdomain, read back once at the end
+  // mgh_compress_masked / mgh_decompress_masked: the filled (or decoded) array; the packed mask with the scan's
+  // statistics behind it; the mask's bytes as symbols of the lossless stage
+  DevBuf mfill, mwords, msym;
   int dev = -1;
   // device bytes the cache holds now (they are reused, so they count as available to the next call)
   size_t held_bytes() const {
     size_t b = 0;
     for (auto &kv : hier) b += mgh_device_bytes(kv.second);
     for (auto &x : in) b += x.cap;
-    b += vres.cap;
+    b += vres.cap + mfill.cap + mwords.cap + msym.cap;
     for (auto &l : lane) {
       b += l.q.cap + l.q2.cap + l.q3.cap + l.oidx.cap + l.oval.cap + l.sub.cap + l.orig.cap + l.cmp.cap;
       if (l.ll) b += l.ll->units.cap + l.ll->oidx.cap + l.ll->oval.cap;
@@ -1651,6 +1660,9 @@ struct HlCache {
     hpin.release();
     aux_pin.release();
     vres.release();
+    mfill.release();
+    mwords.release();
+    msym.release();
     for (auto &l : lane) l.release();
     for (hipStream_t *s : {&copy_st, &aux_st}) {
       if (*s) (void)hipStreamDestroy(*s);
@@ -5156,6 +5168,325 @@ int mgh_decompress_layers(int nlayers, const void *const *compressed_data, const
   if (rc == MGH_SUCCESS) rc = mgh_layers_data(p, decompressed_data, output_pre_allocated);
   mgh_layers_close(p);
   return rc;
+}
+
+} // extern "C"
+
+// ---- arrays with missing values: mgh_compress_masked and its readers (mask_plan.hpp) ----------------------
+namespace {
+
+// the mask's bytes <-> symbols of the lossless stage (dictionary 256), and the mask as one byte per element
+__global__ void __launch_bounds__(256) k_mask_widen(const uint8_t *__restrict__ bytes, size_t nb, uint16_t *__restrict__ sym) {
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < nb; i += (size_t)gridDim.x * 256) sym[i] = bytes[i];
+}
+template <typename SYM>
+__global__ void __launch_bounds__(256) k_mask_narrow(const SYM *__restrict__ sym, size_t nb, uint8_t *__restrict__ bytes) {
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < nb; i += (size_t)gridDim.x * 256) bytes[i] = (uint8_t)sym[i];
+}
+__global__ void __launch_bounds__(256)
+k_mask_expand(const unsigned long long *__restrict__ words, size_t n, uint8_t *__restrict__ mask) {
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256)
+    mask[i] = (uint8_t)((words[i >> 6] >> (i & 63)) & 1);
+}
+inline unsigned mask_grid(size_t items) { return (unsigned)std::min<size_t>((items + 255) / 256, 2048); }
+
+int masked_shape_elems(const char *who, int D, const uint64_t *shape, uint64_t *n_out) {
+  uint64_t n = 1;
+  for (int d = 0; d < D; d++) {
+    if (shape[d] == 0 || shape[d] > 0xffffffffull || n * shape[d] > 0xffffffffull)
+      return hl_fail(MGH_ERR_INVALID_ARGUMENT, std::string(who) + ": 1 .. 2^32 - 1 elements");
+    n *= shape[d];
+  }
+  *n_out = n;
+  return MGH_SUCCESS;
+}
+
+int compress_masked_impl(int D, int dtype, const uint64_t *shape, double tol, double s, int ebtype, const void *original,
+                         const mgh_mask_spec &spec, void **compressed, size_t *csize, const void *const *coords,
+                         const mgh_config &cfg, bool prealloc) {
+  const bool is_double = dtype == MGH_DOUBLE;
+  const size_t elem = is_double ? 8 : 4;
+  uint64_t n = 0;
+  HL_TRY(masked_shape_elems("compress_masked", D, shape, &n));
+  if (spec.flags == 0 || (spec.flags & ~(MGH_MASK_NONFINITE | MGH_MASK_VALUE)))
+    return hl_fail(MGH_ERR_INVALID_ARGUMENT, "compress_masked: flags must be MGH_MASK_NONFINITE, MGH_MASK_VALUE or both");
+  if ((spec.flags & MGH_MASK_VALUE) && std::isnan(spec.fill_value))
+    return hl_fail(MGH_ERR_INVALID_ARGUMENT, "compress_masked: a NaN fill_value (MGH_MASK_NONFINITE masks NaN)");
+  const bool in_dev = is_device_pointer(original);
+  // the array on the device, and for a device-resident one its filled copy beside it
+  if ((in_dev ? 2 : 1) * (uint64_t)n * elem > cfg.max_memory_footprint)
+    return hl_fail(MGH_ERR_INVALID_ARGUMENT,
+                   "compress_masked: the array and its filled copy do not fit max_memory_footprint (masked arrays are "
+                   "not streamed in parts)");
+  HL_TRY(cache_prepare(cfg.dev_id));
+  HlCache &C = g_cache;
+  hipStream_t st = C.lane[0].st;
+  const uint64_t nw = mask_words(n), nb = mask_packed_bytes(n);
+  HL_TRY(C.mwords.ensure(nb + sizeof(mgh_mask_stats)));
+  uint64_t *d_words = (uint64_t *)C.mwords.p;
+  mgh_mask_stats *d_stats = (mgh_mask_stats *)((char *)C.mwords.p + nb);
+  const void *src = original;
+  if (!in_dev) {
+    HL_TRY(C.mfill.ensure(n * elem));
+    HL_TRY(copy_any(C.mfill.p, original, n * elem, st));
+    src = C.mfill.p;
+  }
+  HL_TRY(mgh_mask_scan(D, dtype, shape, src, spec.flags, spec.fill_value, d_words, d_stats, st));
+  mgh_mask_stats hs{};
+  HL_HIP(hipMemcpyAsync(&hs, d_stats, sizeof(hs), hipMemcpyDeviceToHost, st));
+  HL_HIP(hipStreamSynchronize(st));
+  const void *filled = src;  // (nothing masked: the array as it is, a device-resident one where it lies)
+  if (hs.n_masked) {
+    HL_TRY(C.mfill.ensure(n * elem));
+    const uint64_t c_bits = mask_value_bits(is_double, mask_fill_constant(hs.vmin, hs.vmax));
+    HL_TRY(mgh_mask_fill_bits_(D, dtype, shape, src, d_words, c_bits, C.mfill.p, st));
+    HL_HIP(hipStreamSynchronize(st));
+    filled = C.mfill.p;
+  }
+  // the output: mgh_compress's own capacity, and room for the packed mask and the footer behind it
+  const OutSlot slot{compressed, in_dev, prealloc};
+  size_t cap = 0, ccap = 0;
+  if (prealloc) {
+    cap = *csize;
+    if (cap <= kMaskFooterBytes) return hl_fail(MGH_ERR_OUTPUT_TOO_LARGE, "compress_masked: the output cannot hold the footer");
+    ccap = cap - kMaskFooterBytes;
+  } else {
+    ccap = n * elem + (size_t)1e6;
+    cap = ccap + nb + kMaskFooterBytes;
+    HL_TRY(slot.alloc(cap));
+  }
+  void *out = *compressed;
+  size_t container = ccap;
+  int rc = mgh_compress(D, dtype, shape, tol, s, ebtype, filled, &out, &container, coords, &cfg, 1);
+  if (rc != MGH_SUCCESS) return slot.fail(rc);
+  // the mask record: one record of the lossless stage where that is smaller than the packed words
+  MaskFooter f;
+  f.container = container;
+  f.n_masked = hs.n_masked;
+  f.restore_bits = mask_value_bits(is_double, spec.restore_value);
+  std::vector<uint8_t> rec;
+  mgh_lossless_ctx *ll = C.lane[0].ll;
+  uint64_t coded = 0;
+  if (hs.n_masked && mask_record_codable(cfg.huff_block_size)) {
+    if ((rc = C.msym.ensure(nb * 2)) != MGH_SUCCESS) return slot.fail(rc);
+    k_mask_widen<<<mask_grid(nb), 256, 0, st>>>((const uint8_t *)d_words, nb, (uint16_t *)C.msym.p);
+    if (hipGetLastError() != hipSuccess) return slot.fail(hl_fail(MGH_ERR_DEVICE, "compress_masked: k_mask_widen"));
+    // (a code stream of the packed words' size or more is of no interest: cap_units)
+    rc = lossless_compress(ll, (const int64_t *)C.msym.p, nb, kMaskDict, cfg.huff_block_size, cfg.lossless,
+                           cfg.zstd_compress_level, nullptr, nullptr, 0, st, nullptr, ~(uint64_t)0, nw + 1, /*sym16=*/true);
+    if (rc != MGH_SUCCESS) return slot.fail(rc);
+    if (!ll->overflow) coded = ll->record_size();
+  }
+  f.kind = mask_record_kind(n, hs.n_masked, coded);
+  auto device_fail = [&](const char *what) { return slot.fail(hl_fail(MGH_ERR_DEVICE, what)); };
+  if (f.kind == kMaskCoded) {
+    if (ll->on_host) {
+      rec = ll->host;
+    } else {
+      rec.resize(coded);
+      if ((rc = record_write(ll, rec.data(), st)) != MGH_SUCCESS) return slot.fail(rc);
+      if (hipStreamSynchronize(st) != hipSuccess) return device_fail("compress_masked: reading the mask record back");
+    }
+  } else if (f.kind == kMaskPacked) {
+    rec.resize(nb);
+    if (hipMemcpyAsync(rec.data(), d_words, nb, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess)
+      return device_fail("compress_masked: reading the packed mask back");
+  }
+  f.record = rec.size();
+  f.crc = fmt::crc32(rec.data(), rec.size());
+  if (container + rec.size() + kMaskFooterBytes > cap)
+    return slot.fail(hl_fail(MGH_ERR_OUTPUT_TOO_LARGE, "compress_masked: the output cannot hold container, mask record and footer"));
+  rec.resize(rec.size() + kMaskFooterBytes);
+  mask_footer_serialize(f, rec.data() + f.record);
+  if (is_device_pointer(out)) {
+    if (hipMemcpyAsync((char *)out + container, rec.data(), rec.size(), hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess)
+      return device_fail("compress_masked: writing mask record and footer");
+  } else {
+    std::memcpy((char *)out + container, rec.data(), rec.size());
+  }
+  *csize = container + rec.size();
+  return MGH_SUCCESS;
+}
+
+// A masked buffer opened: the footer, the header of the container in front of it, and the record on the host.
+struct MaskedView {
+  MaskFooter f;
+  fmt::Header hd;
+  uint64_t n = 0;
+  int dtype = MGH_FLOAT, lossless = MGH_LOSSLESS_HUFFMAN;
+  std::vector<uint8_t> rec;
+};
+
+// 1: a masked buffer that passed every check; 0: no footer's magic; negative: a status.
+int masked_open(const void *buf, size_t size, MaskedView &v) {
+  if (size < kMaskFooterBytes) return 0;
+  const bool in_dev = is_device_pointer(buf);
+  uint8_t tail[kMaskFooterBytes];
+  const uint8_t *p = (const uint8_t *)buf;
+  if (in_dev) HL_TRY(aux_read(tail, p + size - kMaskFooterBytes, kMaskFooterBytes));
+  else std::memcpy(tail, p + size - kMaskFooterBytes, kMaskFooterBytes);
+  if (!mask_footer_present(tail, size)) return 0;
+  if (const char *bad = mask_footer_parse(tail, size, v.f)) return hl_fail(MGH_ERR_FORMAT, bad);
+  size_t meta = 0;
+  HL_TRY(read_header(buf, (size_t)v.f.container, v.hd, meta));
+  if (v.hd.shape.empty() || v.hd.shape.size() > MGH_MAX_DIM) return hl_fail(MGH_ERR_FORMAT, "header: dimension");
+  v.n = 1;
+  for (uint64_t e : v.hd.shape) {
+    if (e == 0 || e > 0xffffffffull || v.n * e > 0xffffffffull) return hl_fail(MGH_ERR_FORMAT, "mask footer: an array of 2^32 elements or more");
+    v.n *= e;
+  }
+  v.dtype = v.hd.is_double ? MGH_DOUBLE : MGH_FLOAT;
+  v.lossless = v.hd.compressor == fmt::COMP_X_HUFFMAN_ZSTD ? MGH_LOSSLESS_HUFFMAN_ZSTD : MGH_LOSSLESS_HUFFMAN;
+  if (const char *bad = mask_footer_check_n(v.f, v.n, v.hd.is_double)) return hl_fail(MGH_ERR_FORMAT, bad);
+  v.rec.resize((size_t)v.f.record);
+  if (v.f.record) {
+    if (in_dev) HL_TRY(aux_read(v.rec.data(), p + v.f.container, (size_t)v.f.record));
+    else std::memcpy(v.rec.data(), p + v.f.container, (size_t)v.f.record);
+  }
+  if (const char *bad = mask_record_check_crc(v.f, v.rec.data())) return hl_fail(MGH_ERR_FORMAT, bad);
+  return 1;
+}
+
+// The packed mask of an opened buffer in the cache's device buffer, queued on `st`.
+int masked_words(const MaskedView &v, hipStream_t st, uint64_t **d_words_out) {
+  HlCache &C = g_cache;
+  const uint64_t nb = mask_packed_bytes(v.n);
+  HL_TRY(C.mwords.ensure(nb + sizeof(mgh_mask_stats)));
+  *d_words_out = (uint64_t *)C.mwords.p;
+  if (v.f.kind == kMaskNone) {
+    HL_HIP(hipMemsetAsync(C.mwords.p, 0, nb, st));
+  } else if (v.f.kind == kMaskPacked) {
+    HL_HIP(hipMemcpyAsync(C.mwords.p, v.rec.data(), nb, hipMemcpyHostToDevice, st));
+    HL_HIP(hipStreamSynchronize(st));  // (the record's host copy belongs to the caller)
+  } else {
+    HL_TRY(C.msym.ensure(nb * 8));
+    const mgh_decompress_stats kept = decompress_stats();  // (the statistics are the container's, not the mask's)
+    bool sym16 = true;
+    uint64_t ocount = 0;
+    const int rc = lossless_decompress(C.lane[0].ll, v.rec.data(), v.rec.size(), v.lossless, (int64_t *)C.msym.p, nb, &ocount,
+                                       st, &sym16);
+    decompress_stats() = kept;
+    HL_TRY(rc);
+    if (ocount) return hl_fail(MGH_ERR_FORMAT, "mask record: outliers in a record of bytes");
+    if (sym16) k_mask_narrow<uint16_t><<<mask_grid(nb), 256, 0, st>>>((const uint16_t *)C.msym.p, nb, (uint8_t *)C.mwords.p);
+    else k_mask_narrow<int64_t><<<mask_grid(nb), 256, 0, st>>>((const int64_t *)C.msym.p, nb, (uint8_t *)C.mwords.p);
+    HL_HIP(hipGetLastError());
+  }
+  return MGH_SUCCESS;
+}
+
+int masked_config(const mgh_config *config, mgh_config &cfg) {
+  if (config) cfg = *config;
+  else mgh_config_default(&cfg);
+  int ndev = mgh_device_count();
+  if (ndev <= 0) return hl_fail(MGH_ERR_NO_DEVICE, "no HIP device");
+  if (cfg.dev_id < 0 || cfg.dev_id >= ndev) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "dev_id");
+  if (hipSetDevice(cfg.dev_id) != hipSuccess) return hl_fail(MGH_ERR_DEVICE, "hipSetDevice");
+  return MGH_SUCCESS;
+}
+
+int decompress_masked_impl(const void *buf, size_t size, const mgh_config &cfg, void **out, bool prealloc) {
+  MaskedView v;
+  const int opened = masked_open(buf, size, v);
+  if (opened < 0) return opened;
+  if (opened == 0) return hl_fail(MGH_ERR_FORMAT, "decompress_masked: no mask footer (a plain container has mgh_decompress)");
+  const size_t bytes = (size_t)v.n * (v.hd.is_double ? 8 : 4);
+  const bool in_dev = is_device_pointer(buf);
+  const bool out_dev = prealloc ? is_device_pointer(*out) : in_dev;
+  HL_TRY(cache_prepare(cfg.dev_id));
+  HlCache &C = g_cache;
+  hipStream_t st = C.lane[0].st;
+  const OutSlot slot{out, in_dev, prealloc};
+  HL_TRY(slot.alloc(bytes));
+  // the restore pass runs on the device: a host output is reconstructed in a device buffer first
+  void *d_data = *out;
+  int rc = MGH_SUCCESS;
+  if (!out_dev) {
+    if ((rc = C.mfill.ensure(bytes)) != MGH_SUCCESS) return slot.fail(rc);
+    d_data = C.mfill.p;
+  }
+  void *dst = d_data;
+  if ((rc = mgh_decompress(buf, (size_t)v.f.container, &dst, &cfg, 1)) != MGH_SUCCESS) return slot.fail(rc);
+  if (v.f.kind != kMaskNone) {
+    uint64_t *d_words = nullptr;
+    if ((rc = masked_words(v, st, &d_words)) != MGH_SUCCESS) return slot.fail(rc);
+    rc = mgh_mask_restore_bits_((int)v.hd.shape.size(), v.dtype, v.hd.shape.data(), d_words, v.f.restore_bits, d_data, st);
+    if (rc != MGH_SUCCESS) return slot.fail(rc);
+  }
+  if (!out_dev && (rc = copy_any(*out, d_data, bytes, st)) != MGH_SUCCESS) return slot.fail(rc);
+  if (hipStreamSynchronize(st) != hipSuccess) return slot.fail(hl_fail(MGH_ERR_DEVICE, "decompress_masked: hipStreamSynchronize"));
+  return MGH_SUCCESS;
+}
+
+int decompress_mask_impl(const void *buf, size_t size, const mgh_config &cfg, uint8_t *mask) {
+  MaskedView v;
+  const int opened = masked_open(buf, size, v);
+  if (opened < 0) return opened;
+  if (opened == 0) return hl_fail(MGH_ERR_FORMAT, "decompress_mask: no mask footer");
+  HL_TRY(cache_prepare(cfg.dev_id));
+  HlCache &C = g_cache;
+  hipStream_t st = C.lane[0].st;
+  uint64_t *d_words = nullptr;
+  HL_TRY(masked_words(v, st, &d_words));
+  const bool out_dev = is_device_pointer(mask);
+  uint8_t *d_mask = mask;
+  if (!out_dev) {  // (the symbols have been narrowed into the words: their buffer is free)
+    HL_TRY(C.msym.ensure((size_t)v.n));
+    d_mask = (uint8_t *)C.msym.p;
+  }
+  k_mask_expand<<<mask_grid((size_t)v.n), 256, 0, st>>>((const unsigned long long *)d_words, (size_t)v.n, d_mask);
+  HL_HIP(hipGetLastError());
+  if (!out_dev) HL_TRY(copy_any(mask, d_mask, (size_t)v.n, st));
+  HL_HIP(hipStreamSynchronize(st));
+  return MGH_SUCCESS;
+}
+
+} // namespace
+
+extern "C" {
+
+int mgh_compress_masked(int D, int dtype, const uint64_t *shape, double tol, double s, int ebtype, const void *original_data,
+                        const mgh_mask_spec *spec, void **compressed_data, size_t *compressed_size,
+                        const void *const *coords, const mgh_config *config, int output_pre_allocated) {
+  if (!compressed_data || !compressed_size || !spec) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "NULL argument");
+  HL_TRY(size_call_args(D, dtype, shape, ebtype, original_data, config, output_pre_allocated ? compressed_data : nullptr));
+  return hl_guarded([&]() -> int {
+    return compress_masked_impl(D, dtype, shape, tol, s, ebtype, original_data, *spec, compressed_data, compressed_size,
+                                coords, *config, output_pre_allocated != 0);
+  });
+}
+
+int mgh_masked_info(const void *compressed_data, size_t compressed_size, struct mgh_masked_info *info) {
+  if (!compressed_data || !info) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "NULL argument");
+  return hl_guarded([&]() -> int {
+    MaskedView v;
+    const int opened = masked_open(compressed_data, compressed_size, v);
+    if (opened <= 0) return opened;
+    info->container_size = v.f.container;
+    info->record_size = v.f.record;
+    info->n_masked = v.f.n_masked;
+    info->kind = (int)v.f.kind;
+    info->restore_value = mask_bits_value(v.hd.is_double, v.f.restore_bits);
+    return 1;
+  });
+}
+
+int mgh_decompress_masked(const void *compressed_data, size_t compressed_size, const mgh_config *config,
+                          void **decompressed_data, int output_pre_allocated) {
+  if (!compressed_data || !decompressed_data) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (output_pre_allocated && !*decompressed_data) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "pre-allocated output is NULL");
+  mgh_config cfg;
+  HL_TRY(masked_config(config, cfg));
+  return hl_guarded([&] { return decompress_masked_impl(compressed_data, compressed_size, cfg, decompressed_data, output_pre_allocated != 0); });
+}
+
+int mgh_decompress_mask(const void *compressed_data, size_t compressed_size, const mgh_config *config, uint8_t *mask) {
+  if (!compressed_data || !mask) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "NULL argument");
+  mgh_config cfg;
+  HL_TRY(masked_config(config, cfg));
+  return hl_guarded([&] { return decompress_mask_impl(compressed_data, compressed_size, cfg, mask); });
 }
 
 } // extern "C"

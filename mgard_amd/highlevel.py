@@ -38,6 +38,7 @@ HL_SYMBOLS = [
     "mgh_compress_ladder", "mgh_last_compress_stats", "mgh_histogram_sym16",
     "mgh_compress_layers", "mgh_layers_open", "mgh_layers_add", "mgh_layers_count", "mgh_layers_tolerance",
     "mgh_layers_data", "mgh_layers_close", "mgh_decompress_layers",
+    "mgh_compress_masked", "mgh_masked_info", "mgh_decompress_masked", "mgh_decompress_mask",
 ]
 
 
@@ -111,6 +112,22 @@ class SizeEstimate(C.Structure):
     def __repr__(self):
         return "SizeEstimate(tol=%r, bytes_min=%d, bytes_max=%d, outliers=%d, code_bits=%d, raw=%d)" % (
             self.tol, self.bytes_min, self.bytes_max, self.outliers, self.code_bits, self.raw)
+
+
+class MaskSpec(C.Structure):
+    """mgh_mask_spec: which elements do not count, and what they decode to."""
+    _fields_ = [("flags", C.c_int), ("fill_value", C.c_double), ("restore_value", C.c_double)]
+
+
+class MaskedInfo(C.Structure):
+    """mgh_masked_info: the parts of a masked buffer -- [container][mask record][48-byte footer] -- and its
+    footer's fields. kind 0: packed words, 1: one record of the lossless stage, 2: nothing masked."""
+    _fields_ = [("container_size", C.c_uint64), ("record_size", C.c_uint64), ("n_masked", C.c_uint64),
+                ("kind", C.c_int), ("restore_value", C.c_double)]
+
+    def __repr__(self):
+        return "MaskedInfo(container_size=%d, record_size=%d, n_masked=%d, kind=%d, restore_value=%r)" % (
+            self.container_size, self.record_size, self.n_masked, self.kind, self.restore_value)
 
 
 class HeaderInfo(C.Structure):
@@ -237,6 +254,12 @@ def _hl():
                                         C.c_int]
     L.mgh_memcpy.argtypes = [vp, vp, C.c_size_t]
     L.mgh_huffman_codebook.argtypes = [vp, u64, vp, vp, vp, vp]
+    L.mgh_compress_masked.argtypes = [C.c_int, C.c_int, C.POINTER(u64), C.c_double, C.c_double, C.c_int, vp,
+                                      C.POINTER(MaskSpec), C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(vp),
+                                      C.POINTER(Config), C.c_int]
+    L.mgh_masked_info.argtypes = [vp, C.c_size_t, C.POINTER(MaskedInfo)]
+    L.mgh_decompress_masked.argtypes = [vp, C.c_size_t, C.POINTER(Config), C.POINTER(vp), C.c_int]
+    L.mgh_decompress_mask.argtypes = [vp, C.c_size_t, C.POINTER(Config), vp]
     _declared = True
     return L
 
@@ -552,6 +575,86 @@ def decompress_layers(bufs, config=None, out=None):
     _check(L.mgh_decompress_layers(k, (C.c_void_p * k)(*[p[0].value for p in ptrs]), (C.c_size_t * k)(*[p[1] for p in ptrs]),
                                    C.byref(cfg), C.byref(optr), 1))
     return out
+
+
+# ---- arrays with missing values -------------------------------------------------------------------------------
+def compress_masked(data, tol, s=INF, mode=REL, nonfinite=True, fill_value=None, restore_value=float("nan"), coords=None,
+                    config=None, out=None):
+    """mgh_compress_masked: compress(data) with the NaN / +-Inf (`nonfinite`) and / or the elements equal to
+    `fill_value` left out of the bound. Returns [container][mask record][48-byte footer]: buf[:C], with C =
+    masked_info(buf).container_size, is the ordinary container of the deterministically filled array and opens in
+    every reader; decompress_masked puts `restore_value` at the masked positions. The bound holds at every valid
+    position. Host array in, numpy buffer out; cuda tensor in, cuda buffer out. `out`: optional pre-allocated uint8
+    buffer of the same kind (its size is the capacity)."""
+    import torch
+    from . import mask_flags
+    L = _hl()
+    cfg = config if config is not None else Config()
+    ptr, dt, shape, keep = _as_ptr(data)
+    D = len(shape)
+    shp = (C.c_uint64 * D)(*shape)
+    cptr, ckeep = _coords_ptr(coords, dt, D)
+    on_device = isinstance(data, torch.Tensor) and data.is_cuda
+    n = int(np.prod(shape))
+    cap = n * (4 if dt == FLOAT else 8) + 1000000 + 8 * ((n + 63) // 64) + 48
+    if out is not None:
+        cap = int(out.numel()) if on_device else int(out.size)
+    elif on_device:
+        out = torch.empty(cap, dtype=torch.uint8, device=data.device)
+    else:
+        out = np.empty(cap, dtype=np.uint8)
+    optr = C.c_void_p(out.data_ptr()) if on_device else C.c_void_p(out.ctypes.data)
+    size = C.c_size_t(cap)
+    spec = MaskSpec(mask_flags(nonfinite, fill_value), 0.0 if fill_value is None else float(fill_value), float(restore_value))
+    _check(L.mgh_compress_masked(D, dt, shp, float(tol), float(s), int(mode), ptr, C.byref(spec), C.byref(optr),
+                                 C.byref(size), cptr, C.byref(cfg), 1))
+    del keep, ckeep
+    return out[:size.value]
+
+
+def masked_info(buf):
+    """mgh_masked_info: the MaskedInfo of a masked buffer, None for a buffer without the footer (a plain container);
+    MgardHipError for a footer that fails a check."""
+    p, n, _, keep = _container_ptr(buf)
+    info = MaskedInfo()
+    rc = _check(_hl().mgh_masked_info(p, n, C.byref(info)))
+    del keep
+    return info if rc == 1 else None
+
+
+def decompress_masked(buf, config=None, out=None):
+    """mgh_decompress_masked: the array of a masked buffer with restore_value at every masked position. A numpy array
+    (host buffer) or a cuda tensor; `out` as for decompress_layers. A plain container is refused: it has decompress."""
+    L = _hl()
+    cfg = config if config is not None else Config()
+    p, n, _, keep = _container_ptr(buf)
+    info = masked_info(keep)
+    if info is None:
+        _check(L.mgh_decompress_masked(p, n, C.byref(cfg), C.byref(C.c_void_p()), 0))  # (raises: no footer)
+    out, optr = _layers_out(keep[:info.container_size], out)
+    _check(L.mgh_decompress_masked(p, n, C.byref(cfg), C.byref(optr), 1))
+    return out
+
+
+def decompress_mask(buf, config=None):
+    """mgh_decompress_mask: the mask of a masked buffer as a bool array of the data's shape (numpy for a host buffer, a
+    cuda tensor for a device one)."""
+    import torch
+    L = _hl()
+    cfg = config if config is not None else Config()
+    p, n, on_dev, keep = _container_ptr(buf)
+    info = masked_info(keep)
+    if info is None:
+        raise MgardHipError("mgard_hip error -8: decompress_mask: no mask footer")
+    shape, _ = infer(keep[:info.container_size])
+    if on_dev:
+        mask = torch.empty(shape, dtype=torch.uint8, device=keep.device)
+        mp = C.c_void_p(mask.data_ptr())
+    else:
+        mask = np.empty(shape, dtype=np.uint8)
+        mp = C.c_void_p(mask.ctypes.data)
+    _check(L.mgh_decompress_mask(p, n, C.byref(cfg), mp))
+    return mask.bool() if on_dev else mask.astype(bool)
 
 
 class Layers:
