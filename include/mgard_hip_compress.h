@@ -579,6 +579,33 @@ int mgh_lossless_decompress_range(mgh_lossless_ctx *ctx, const uint8_t *payload,
                                   const uint64_t **d_outlier_idx_out, const int64_t **d_outlier_val_out,
                                   uint64_t *outlier_count_out, void *stream);
 
+/* ---- the same stage on 16-bit symbols (what mgh_compress moves through it when reorder = 0) ----
+ * mgh_lossless_compress_sym16 / mgh_lossless_compress_device_sym16: mgh_lossless_compress[_device] with
+ * the symbols as uint16_t (mgh_decompose_quantize_sym16, mgh_quantize_symbols); the record is the one
+ * written from the same values as int64, byte for byte. The single-pass encoder only, which stages a
+ * chunk's symbols and the code table in LDS: dict_size * 8 + chunk_size * 2 > 140 KiB is
+ * MGH_ERR_INVALID_ARGUMENT. */
+int mgh_lossless_compress_sym16(mgh_lossless_ctx *ctx, const uint16_t *d_symbols, uint64_t n,
+                                uint64_t dict_size, uint64_t chunk_size, int lossless, int zstd_level,
+                                const uint64_t *d_outlier_idx, const int64_t *d_outlier_val,
+                                uint64_t outlier_count, const uint8_t **h_payload_out,
+                                uint64_t *size_out, void *stream);
+int mgh_lossless_compress_device_sym16(mgh_lossless_ctx *ctx, const uint16_t *d_symbols, uint64_t n,
+                                       uint64_t dict_size, uint64_t chunk_size,
+                                       const uint64_t *d_outlier_idx, const int64_t *d_outlier_val,
+                                       uint64_t outlier_count, void *d_record_out, uint64_t capacity,
+                                       uint64_t *size_out, void *stream);
+/* Inverse into uint16_t symbols: first = 0, count = n decodes the whole record into d_symbols[0 .. n);
+ * anything else has the chunk-range semantics of mgh_lossless_decompress_range (count = 0 or a range
+ * that leaves [0, n) is an error). Nothing but 2-byte elements is ever written to d_symbols: a record
+ * that the decoder with a 16-bit output does not take -- chunk_size < 1024, a code longer than 32 bits,
+ * or MGH_HUFF_SERIAL_DECODE / MGH_HUFF_PAR_DECODE set -- is MGH_ERR_INVALID_ARGUMENT before anything is
+ * launched, and the context stays usable. */
+int mgh_lossless_decompress_sym16(mgh_lossless_ctx *ctx, const uint8_t *payload, uint64_t size, int lossless,
+                                  uint16_t *d_symbols, uint64_t n, uint64_t first, uint64_t count,
+                                  const uint64_t **d_outlier_idx_out, const int64_t **d_outlier_val_out,
+                                  uint64_t *outlier_count_out, void *stream);
+
 /* HOST only (like mgh_infer_level_shape): where the coefficients of `level` lie in a level-linearised
  * (reorder = 1) record -- integers [first_elem, first_elem + num_elems) with first_elem = N_{level-1}
  * (0 for level 0) and N_l = prod(level_shape(l)) -- and the Huffman chunks that hold them, by the

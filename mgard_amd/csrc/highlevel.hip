@@ -872,14 +872,16 @@ int record_upload(mgh_lossless_ctx *c, const uint8_t *p, bool on_dev, bool here,
 // record says is read by huffman_record.hpp (record_fixed, record_plan), which decoder takes it by
 // its decode_plan; this function fetches, uploads and launches.
 // sym16: decode to uint16_t symbols at d_q (the ring decoder only; *sym16 is cleared when another
-// decoder had to be used and d_q holds int64 values).
+// decoder had to be used and d_q holds int64 values). require16: d_q holds 16-bit elements and nothing
+// else -- a record the ring decoder does not take is refused (sym16_refusal) before anything is queued.
 // range (DecodeRange): a prefix or a range writes d_q[0 .. ) from the first integer of its first chunk
 // to the end of its last and nothing behind it, and of a record that has to be copied only what those
 // chunks need is moved; the decoders run on the chunk-table entries, synchronisation entries and code
 // units of the range alone. n_prefix == 0: a context with keep == 1 only (the reader's open).
 int lossless_decompress(mgh_lossless_ctx *c, const uint8_t *payload, uint64_t size, int lossless,
                         int64_t *d_q, uint64_t n, uint64_t *ocount_out, hipStream_t st,
-                        bool *sym16 = nullptr, bool sync_end = true, const DecodeRange &range = DecodeRange()) {
+                        bool *sym16 = nullptr, bool sync_end = true, const DecodeRange &range = DecodeRange(),
+                        bool require16 = false) {
   if (range.n_prefix == 0 && c->keep != 1) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "lossless_decompress: empty prefix");
   if (range.n_prefix != 0 && range.first >= std::min<uint64_t>(range.n_prefix, n))
     return hl_fail(MGH_ERR_INVALID_ARGUMENT, "lossless_decompress: empty range");
@@ -916,6 +918,8 @@ int lossless_decompress(mgh_lossless_ctx *c, const uint8_t *payload, uint64_t si
   if (const char *bad = record_plan(head.data(), head.size(), on_dev ? nullptr : p, psize, sw, R))
     return hl_fail(MGH_ERR_FORMAT, bad);
   const DecodePlan D = decode_plan(R, n, sw);
+  if (require16)
+    if (const char *bad = sym16_refusal(D)) return hl_fail(MGH_ERR_INVALID_ARGUMENT, bad);
   const PayloadLayout &L = R.L;
   const size_t nchunk = R.nchunk, ndec = R.ndec, cf = R.cf, ocount = R.ocount;
   const size_t n_out = ndec ? R.n_dec - cf * (size_t)R.chunk : 0;  // integers the call writes
@@ -961,12 +965,13 @@ int lossless_decompress(mgh_lossless_ctx *c, const uint8_t *payload, uint64_t si
     // two-level table from the decodebook (host, microseconds); 16 waves per workgroup when the
     // table leaves room
     const uint64_t *book = reinterpret_cast<const uint64_t *>(head.data() + L.decodebook);
-    const size_t lds_cap = 150 * 1024;
+    const size_t lds_cap = huff::kRingLdsCap;
+    static_assert(huff::kRingWaveLds == huff::kRingUnits * 64 * 8 + 64 * huff::kStageStride * 2, "decode_ring_lds per wave");
     // (kept in the context: the upload below is asynchronous and must not outlive its source)
     std::vector<uint32_t> &dt = c->h_dtable;
     if (!kept) {
       dt = huff::build_decode_table(book, book + 64, book + 128, R.dict, D.rtb,
-                                    (lds_cap - 8 * huff::decode_ring_lds(0, 1)) / 4 - (D.pair ? ((size_t)1 << D.rtb) : 0));
+                                    (lds_cap - huff::kRingMinWaves * huff::kRingWaveLds) / 4 - (D.pair ? ((size_t)1 << D.rtb) : 0));
       if (D.pair) dt = huff::make_pair_table(dt, D.rtb);
       HL_TRY(c->dtable.ensure(dt.size() * 4));
       // (out of pinned memory: a copy from pageable memory is staged synchronously, ~15 us)
@@ -974,7 +979,9 @@ int lossless_decompress(mgh_lossless_ctx *c, const uint8_t *payload, uint64_t si
       std::memcpy(c->dpin.p, dt.data(), dt.size() * 4);
       HL_HIP(hipMemcpyAsync(c->dtable.p, c->dpin.p, dt.size() * 4, hipMemcpyHostToDevice, st));
     }
-    const int waves = huff::decode_ring_lds(dt.size(), 16) <= lds_cap ? 16 : 8;
+    const int waves = huff::decode_ring_lds(dt.size(), 16) <= lds_cap ? 16 : huff::kRingMinWaves;
+    if (huff::decode_ring_lds(dt.size(), waves) > lds_cap)  // (decode_plan and build_decode_table keep the table inside)
+      return hl_fail(MGH_ERR_DEVICE, "lossless_decompress: decode table larger than the ring decoder's LDS");
     HL_TRY(hl_lds_limit(once_ring, 156 * 1024, huff::k_decode_ring<int64_t>, huff::k_decode_ring<uint16_t>));
     if (D.pair) HL_TRY(hl_lds_limit(once_pair, 156 * 1024, huff::k_decode_sync<int64_t>, huff::k_decode_sync<uint16_t>));
     // synchronisation points of the encoder, if the record has them: read where they lie in a
@@ -4571,14 +4578,18 @@ void mgh_lossless_destroy(mgh_lossless_ctx *c) {
   delete c;
 }
 
-int mgh_lossless_compress(mgh_lossless_ctx *ctx, const int64_t *d_q, uint64_t n, uint64_t dict,
-                          uint64_t chunk, int lossless, int zstd_level, const uint64_t *d_oidx,
-                          const int64_t *d_oval, uint64_t ocount, const uint8_t **payload_out,
-                          uint64_t *size_out, void *stream) {
+// mgh_lossless_compress[_sym16]: d_q holds int64 values, or (sym16) uint16_t symbols
+static int lossless_compress_to_host(mgh_lossless_ctx *ctx, const void *d_q, bool sym16, uint64_t n, uint64_t dict,
+                                     uint64_t chunk, int lossless, int zstd_level, const uint64_t *d_oidx,
+                                     const int64_t *d_oval, uint64_t ocount, const uint8_t **payload_out,
+                                     uint64_t *size_out, void *stream) {
   if (!ctx || !d_q || !payload_out || !size_out) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (sym16 && !lossless_sym16_ok(dict, chunk))
+    return hl_fail(MGH_ERR_INVALID_ARGUMENT, "lossless: 16-bit symbols need the single-pass encoder");
   if (hipSetDevice(ctx->dev) != hipSuccess) return hl_fail(MGH_ERR_DEVICE, "hipSetDevice");
   HL_TRY(hl_guarded([&] {
-    return lossless_compress(ctx, d_q, n, dict, chunk, lossless, zstd_level, d_oidx, d_oval, ocount, (hipStream_t)stream);
+    return lossless_compress(ctx, (const int64_t *)d_q, n, dict, chunk, lossless, zstd_level, d_oidx, d_oval, ocount,
+                             (hipStream_t)stream, nullptr, ~(uint64_t)0, 0, sym16);
   }));
   if (!ctx->on_host) {
     ctx->host.resize(ctx->lay.total);
@@ -4590,16 +4601,35 @@ int mgh_lossless_compress(mgh_lossless_ctx *ctx, const int64_t *d_q, uint64_t n,
   return MGH_SUCCESS;
 }
 
-int mgh_lossless_compress_device(mgh_lossless_ctx *ctx, const int64_t *d_q, uint64_t n, uint64_t dict,
-                                 uint64_t chunk, const uint64_t *d_oidx, const int64_t *d_oval,
-                                 uint64_t ocount, void *d_record_out, uint64_t capacity, uint64_t *size_out,
-                                 void *stream) {
+int mgh_lossless_compress(mgh_lossless_ctx *ctx, const int64_t *d_q, uint64_t n, uint64_t dict,
+                          uint64_t chunk, int lossless, int zstd_level, const uint64_t *d_oidx,
+                          const int64_t *d_oval, uint64_t ocount, const uint8_t **payload_out,
+                          uint64_t *size_out, void *stream) {
+  return lossless_compress_to_host(ctx, d_q, false, n, dict, chunk, lossless, zstd_level, d_oidx, d_oval, ocount,
+                                   payload_out, size_out, stream);
+}
+
+int mgh_lossless_compress_sym16(mgh_lossless_ctx *ctx, const uint16_t *d_symbols, uint64_t n, uint64_t dict,
+                                uint64_t chunk, int lossless, int zstd_level, const uint64_t *d_oidx,
+                                const int64_t *d_oval, uint64_t ocount, const uint8_t **payload_out,
+                                uint64_t *size_out, void *stream) {
+  return lossless_compress_to_host(ctx, d_symbols, true, n, dict, chunk, lossless, zstd_level, d_oidx, d_oval, ocount,
+                                   payload_out, size_out, stream);
+}
+
+// mgh_lossless_compress_device[_sym16]
+static int lossless_compress_to_device(mgh_lossless_ctx *ctx, const void *d_q, bool sym16, uint64_t n, uint64_t dict,
+                                       uint64_t chunk, const uint64_t *d_oidx, const int64_t *d_oval,
+                                       uint64_t ocount, void *d_record_out, uint64_t capacity, uint64_t *size_out,
+                                       void *stream) {
   if (!ctx || !d_q || !d_record_out || !size_out) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (sym16 && !lossless_sym16_ok(dict, chunk))
+    return hl_fail(MGH_ERR_INVALID_ARGUMENT, "lossless: 16-bit symbols need the single-pass encoder");
   if (hipSetDevice(ctx->dev) != hipSuccess) return hl_fail(MGH_ERR_DEVICE, "hipSetDevice");
   if (!is_device_pointer(d_record_out)) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "d_record_out must be device memory");
   HL_TRY(hl_guarded([&] {
-    return lossless_compress(ctx, d_q, n, dict, chunk, MGH_LOSSLESS_HUFFMAN, 0, d_oidx, d_oval, ocount,
-                             (hipStream_t)stream, nullptr, ~(uint64_t)0, 0, false, (uint8_t *)d_record_out,
+    return lossless_compress(ctx, (const int64_t *)d_q, n, dict, chunk, MGH_LOSSLESS_HUFFMAN, 0, d_oidx, d_oval, ocount,
+                             (hipStream_t)stream, nullptr, ~(uint64_t)0, 0, sym16, (uint8_t *)d_record_out,
                              (size_t)capacity);
   }));
   if (ctx->overflow || ctx->record_size() > capacity)
@@ -4608,6 +4638,22 @@ int mgh_lossless_compress_device(mgh_lossless_ctx *ctx, const int64_t *d_q, uint
   HL_HIP(hipStreamSynchronize((hipStream_t)stream));
   *size_out = ctx->record_size();
   return MGH_SUCCESS;
+}
+
+int mgh_lossless_compress_device(mgh_lossless_ctx *ctx, const int64_t *d_q, uint64_t n, uint64_t dict,
+                                 uint64_t chunk, const uint64_t *d_oidx, const int64_t *d_oval,
+                                 uint64_t ocount, void *d_record_out, uint64_t capacity, uint64_t *size_out,
+                                 void *stream) {
+  return lossless_compress_to_device(ctx, d_q, false, n, dict, chunk, d_oidx, d_oval, ocount, d_record_out, capacity,
+                                     size_out, stream);
+}
+
+int mgh_lossless_compress_device_sym16(mgh_lossless_ctx *ctx, const uint16_t *d_symbols, uint64_t n, uint64_t dict,
+                                       uint64_t chunk, const uint64_t *d_oidx, const int64_t *d_oval,
+                                       uint64_t ocount, void *d_record_out, uint64_t capacity, uint64_t *size_out,
+                                       void *stream) {
+  return lossless_compress_to_device(ctx, d_symbols, true, n, dict, chunk, d_oidx, d_oval, ocount, d_record_out,
+                                     capacity, size_out, stream);
 }
 
 int mgh_lossless_decompress(mgh_lossless_ctx *ctx, const uint8_t *payload, uint64_t size, int lossless,
@@ -4646,6 +4692,25 @@ int mgh_lossless_decompress_range(mgh_lossless_ctx *ctx, const uint8_t *payload,
   HL_TRY(hl_guarded([&] {
     return lossless_decompress(ctx, payload, size, lossless, d_q, n, ocount_out, (hipStream_t)stream, nullptr, true,
                                DecodeRange{first + count, ~(uint64_t)0, first});
+  }));
+  if (oidx_out) *oidx_out = (const uint64_t *)ctx->oidx.p;
+  if (oval_out) *oval_out = (const int64_t *)ctx->oval.p;
+  return MGH_SUCCESS;
+}
+
+int mgh_lossless_decompress_sym16(mgh_lossless_ctx *ctx, const uint8_t *payload, uint64_t size, int lossless,
+                                  uint16_t *d_symbols, uint64_t n, uint64_t first, uint64_t count,
+                                  const uint64_t **oidx_out, const int64_t **oval_out, uint64_t *ocount_out,
+                                  void *stream) {
+  if (!ctx || !payload || !d_symbols || !ocount_out) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (count == 0 || first >= n || count > n - first)
+    return hl_fail(MGH_ERR_INVALID_ARGUMENT, "mgh_lossless_decompress_sym16: first / count outside the record");
+  if (hipSetDevice(ctx->dev) != hipSuccess) return hl_fail(MGH_ERR_DEVICE, "hipSetDevice");
+  const DecodeRange range = first == 0 && count == n ? DecodeRange() : DecodeRange{first + count, ~(uint64_t)0, first};
+  HL_TRY(hl_guarded([&] {
+    bool sym16 = true;
+    return lossless_decompress(ctx, payload, size, lossless, (int64_t *)d_symbols, n, ocount_out, (hipStream_t)stream,
+                               &sym16, true, range, /*require16=*/true);
   }));
   if (oidx_out) *oidx_out = (const uint64_t *)ctx->oidx.p;
   if (oval_out) *oval_out = (const int64_t *)ctx->oval.p;

@@ -22,6 +22,9 @@ constexpr int kParWaves = 16;
 constexpr int kParBatch = 32;  // symbols a lane decodes between two write-outs
 constexpr int kEncRun = 40;      // symbols per thread the single-pass encoder keeps in registers (default chunk: 20480 = 40 x 512)
 constexpr int kEncThreads = 512;  // threads of an encoder workgroup (two workgroups per CU with 32-bit code entries)
+constexpr size_t kRingLdsCap = 150 * 1024;  // dynamic LDS a ring decoder's launch asks for at most
+constexpr size_t kRingWaveLds = 8 * 64 * 8 + 64 * 17 * 2;  // of which per wave: code-unit ring + write-out staging (decode_ring_lds)
+constexpr int kRingMinWaves = 8;  // waves of a ring decoder's workgroup when the table leaves no room for 16
 } // namespace huff
 
 // ---- offsets with natural alignment (Huffman.hpp:163-239) ---------------------------------------
@@ -221,7 +224,11 @@ inline DecodePlan decode_plan(const RecordPlan &R, uint64_t n, const DecodeSwitc
     // against 0.87, 9.1 bits (the benchmark's field at 1e-3) 0.97 against 0.79 -- pairs no longer fit
     // and the wider entries only cost. MGH_HUFF_PAIR: 0 never, 1 up to 6.5 bits per symbol (default),
     // 2 whenever the record has the points (cross-check).
-    D.pair = D.sync && (sw.pair == 2 || (sw.pair == 1 && (double)R.units * 64.0 <= 6.5 * (double)n));
+    // The pair table's root alone is 8 << rtb bytes and has to fit beside the rings of the smallest workgroup:
+    // 13 bits at most. MGH_HUFF_TB=14 decodes with single-symbol steps (its launch with pairs asked for
+    // 178 KiB of LDS and failed).
+    const bool pair_fits = ((size_t)8 << D.rtb) + huff::kRingMinWaves * huff::kRingWaveLds <= huff::kRingLdsCap;
+    D.pair = D.sync && pair_fits && (sw.pair == 2 || (sw.pair == 1 && (double)R.units * 64.0 <= 6.5 * (double)n));
     return D;
   }
   if (R.ndec <= R.cf) return D;  // (nothing to decode)
@@ -243,6 +250,13 @@ inline DecodePlan decode_plan(const RecordPlan &R, uint64_t n, const DecodeSwitc
   }
   D.tb = tb;
   return D;
+}
+
+// A caller whose output holds 16-bit symbols can be served by the ring decoder alone (k_decode_ring and
+// k_decode_sync have a uint16_t instantiation; the cross-check decoders write int64 values): what such
+// a caller is told about any other plan, nullptr when the plan is the ring decoder's.
+inline const char *sym16_refusal(const DecodePlan &D) {
+  return D.kind == DecodeKind::ring ? nullptr : "lossless: 16-bit symbols need the ring decoder for this record";
 }
 
 // A record whose code units arrive in pieces: with units [0, have) of the record on the device (all

@@ -39,6 +39,7 @@ HL_SYMBOLS = [
     "mgh_compress_layers", "mgh_layers_open", "mgh_layers_add", "mgh_layers_count", "mgh_layers_tolerance",
     "mgh_layers_data", "mgh_layers_close", "mgh_decompress_layers",
     "mgh_compress_masked", "mgh_masked_info", "mgh_decompress_masked", "mgh_decompress_mask",
+    "mgh_lossless_compress_sym16", "mgh_lossless_compress_device_sym16", "mgh_lossless_decompress_sym16",
 ]
 
 
@@ -225,6 +226,9 @@ def _hl():
                                                  C.POINTER(u64), vp]
     L.mgh_lossless_decompress_range.argtypes = [vp, vp, u64, C.c_int, vp, u64, u64, u64, C.POINTER(vp),
                                                 C.POINTER(vp), C.POINTER(u64), vp]
+    L.mgh_lossless_compress_sym16.argtypes = L.mgh_lossless_compress.argtypes
+    L.mgh_lossless_compress_device_sym16.argtypes = L.mgh_lossless_compress_device.argtypes
+    L.mgh_lossless_decompress_sym16.argtypes = L.mgh_lossless_decompress_range.argtypes
     L.mgh_infer_level_range.argtypes = [vp, C.c_size_t, vp, C.c_int, C.POINTER(u64), C.POINTER(u64),
                                         C.POINTER(u64), C.POINTER(u64)]
     L.mgh_progressive_open.argtypes = [C.POINTER(vp), vp, C.c_size_t, vp]
@@ -1228,13 +1232,25 @@ class Lossless:
         except Exception:
             pass
 
+    @staticmethod
+    def _is16(q):
+        """Whether q holds 16-bit symbols (torch.uint16 or int16: the same two bytes) rather than int64 values."""
+        import torch
+        if q.dtype in (torch.uint16, torch.int16):
+            return True
+        if q.dtype != torch.int64:
+            raise ValueError("symbols: expected an int64, uint16 or int16 tensor, got %s" % q.dtype)
+        return False
+
     def compress(self, q, dict_size=8192, chunk_size=20480, lossless=HUFFMAN, zstd_level=3,
                  outlier_idx=None, outlier_val=None):
-        """q: cuda int64 tensor of symbols in [0, dict_size). Returns the payload bytes."""
+        """q: cuda int64 tensor of symbols in [0, dict_size), or a cuda uint16 / int16 tensor of them
+        (mgh_lossless_compress_sym16: the same record). Returns the payload bytes."""
         import torch
         n_out = 0 if outlier_idx is None else int(outlier_idx.numel())
         pay, size = C.c_void_p(), C.c_uint64()
-        _check(_hl().mgh_lossless_compress(
+        fn = _hl().mgh_lossless_compress_sym16 if self._is16(q) else _hl().mgh_lossless_compress
+        _check(fn(
             self._c, C.c_void_p(q.data_ptr()), q.numel(), dict_size, chunk_size, lossless, zstd_level,
             C.c_void_p(outlier_idx.data_ptr()) if n_out else None,
             C.c_void_p(outlier_val.data_ptr()) if n_out else None, n_out, C.byref(pay), C.byref(size),
@@ -1243,18 +1259,19 @@ class Lossless:
 
     def compress_device(self, q, out, dict_size=8192, chunk_size=20480, outlier_idx=None, outlier_val=None):
         """The record written into `out` (cuda uint8 tensor or a view of one: any byte alignment).
-        Returns the record as a view of `out`."""
+        q as for compress. Returns the record as a view of `out`."""
         import torch
         n_out = 0 if outlier_idx is None else int(outlier_idx.numel())
         size = C.c_uint64()
-        _check(_hl().mgh_lossless_compress_device(
+        fn = _hl().mgh_lossless_compress_device_sym16 if self._is16(q) else _hl().mgh_lossless_compress_device
+        _check(fn(
             self._c, C.c_void_p(q.data_ptr()), q.numel(), dict_size, chunk_size,
             C.c_void_p(outlier_idx.data_ptr()) if n_out else None,
             C.c_void_p(outlier_val.data_ptr()) if n_out else None, n_out, C.c_void_p(out.data_ptr()),
             out.numel(), C.byref(size), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
         return out[:size.value]
 
-    def decompress(self, payload, n, lossless=HUFFMAN, prefix=None, out=None, first=None, count=None):
+    def decompress(self, payload, n, lossless=HUFFMAN, prefix=None, out=None, first=None, count=None, sym16=False):
         """payload: bytes, or a cuda uint8 tensor (decoded where it lies). Returns (q, outlier_idx,
         outlier_val) as cuda tensors.
         prefix: decode only the chunks that hold the first `prefix` integers
@@ -1263,15 +1280,20 @@ class Lossless:
         a prefix it need only hold what is written); default: a new one of n elements.
         first, count: decode only the chunks that hold integers [first, first + count)
         (mgh_lossless_decompress_range): q[0:] receives the integers from (first // chunk) * chunk to
-        the end of the last decoded chunk (or n), nothing behind them."""
+        the end of the last decoded chunk (or n), nothing behind them.
+        sym16: decode to 16-bit symbols (mgh_lossless_decompress_sym16) -- q and `out` are uint16
+        tensors (`out` may be int16); whole record or first / count, not prefix."""
         import torch
         if (first is None) != (count is None) or (first is not None and prefix is not None):
             raise ValueError("pass first and count together, and not with prefix")
+        if sym16 and prefix is not None:
+            raise ValueError("sym16: pass first and count, not prefix")
+        kinds = (torch.uint16, torch.int16) if sym16 else (torch.int64,)
         if out is None:
-            q = torch.empty(n, dtype=torch.int64, device="cuda")
+            q = torch.empty(n, dtype=kinds[0], device="cuda")
         else:
-            if not (out.is_cuda and out.dtype == torch.int64 and out.is_contiguous()):
-                raise ValueError("out: expected a contiguous cuda int64 tensor")
+            if not (out.is_cuda and out.dtype in kinds and out.is_contiguous()):
+                raise ValueError("out: expected a contiguous cuda %s tensor" % ("uint16" if sym16 else "int64"))
             if prefix is None and first is None and out.numel() < n:
                 raise ValueError("out: %d elements, the record holds %d" % (out.numel(), n))
             q = out
@@ -1285,7 +1307,12 @@ class Lossless:
         else:
             raw, nbytes = (C.c_uint8 * len(payload)).from_buffer_copy(payload), len(payload)
         oi, ov, cnt = C.c_void_p(), C.c_void_p(), C.c_uint64()
-        if first is not None:
+        if sym16:
+            lo, num = (0, n) if first is None else (int(first), int(count))
+            _check(_hl().mgh_lossless_decompress_sym16(
+                self._c, raw, nbytes, lossless, C.c_void_p(q.data_ptr()), n, lo, num, C.byref(oi),
+                C.byref(ov), C.byref(cnt), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        elif first is not None:
             _check(_hl().mgh_lossless_decompress_range(
                 self._c, raw, nbytes, lossless, C.c_void_p(q.data_ptr()), n, int(first), int(count), C.byref(oi),
                 C.byref(ov), C.byref(cnt), C.c_void_p(torch.cuda.current_stream().cuda_stream)))

@@ -6,6 +6,8 @@
 //   landed FILE N N_PREFIX FIRST C_DONE HAVE LAST   -> "landed C_HI" (chunks_landed on the record's table)
 //   decode DICT CHUNK N UNITS HAS_SYNC BOOK_MAX_LEN NDEC CF SERIAL PAR PAIR TB   (TB = "unset": switch not set)
 //                                   -> "decode kind=... sync= pair= tb= rtb= lds=" (decode_plan)
+//   decode16 (the same arguments)   -> "decode16 kind=... refused=0|1" (sym16_refusal of that plan: a caller
+//                                      whose output holds 16-bit symbols)
 // A record is handed to the parser the way lossless_decompress() does it, every span in a heap block
 // of exactly its size, so that AddressSanitizer sees a read past any of them: the first 24 bytes (or
 // fewer), then the bytes up to the code units, and -- a host record, ON_DEV = 0 -- the whole record.
@@ -105,7 +107,7 @@ int main() {
                   R.dict, R.chunk, R.nchunk, R.L.huffmeta, R.L.decodebook, R.L.ddata, R.ndec, R.cf, R.n_dec, R.tb0, R.tb_cnt,
                   R.dbsize, R.units, R.ocount, R.o_oc, R.o_oidx, R.o_oval, R.o_sync, (int)R.has_sync, R.units_lo,
                   R.units_need, R.book_max_len);
-    } else if (cmd == "decode") {
+    } else if (cmd == "decode" || cmd == "decode16") {
       RecordPlan R;
       uint64_t n = 0;
       int has_sync = 0, serial = 0, par = 0;
@@ -119,6 +121,10 @@ int main() {
       sw.par = par != 0;
       const DecodePlan D = decode_plan(R, n, sw);
       static const char *const kinds[] = {"none", "ring", "par", "serial"};
+      if (cmd == "decode16") {
+        std::printf("decode16 kind=%s refused=%d\n", kinds[(int)D.kind], sym16_refusal(D) != nullptr);
+        continue;
+      }
       std::printf("decode kind=%s sync=%d pair=%d tb=%d rtb=%d lds=%zu\n", kinds[(int)D.kind], (int)D.sync, (int)D.pair, D.tb,
                   D.rtb, D.lds);
     } else {

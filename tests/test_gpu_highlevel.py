@@ -7,7 +7,8 @@ import pytest
 
 import oracle
 from tests import payload as pl
-from tests.util import nonuniform_coords, reference_footprint as _reference_footprint, smooth_field
+from tests.util import (huffman_symbols as _symbols, nonuniform_coords, reference_footprint as _reference_footprint,
+                        smooth_field)
 
 pytestmark = pytest.mark.gpu
 
@@ -17,12 +18,6 @@ def _mods():
     import mgard_amd
     from mgard_amd import highlevel as hl
     return torch, mgard_amd, hl
-
-
-def _symbols(n, seed=3, width=6.0, dict_size=8192):
-    rng = np.random.default_rng(seed)
-    q = np.rint(rng.normal(0, width, n)).astype(np.int64) + dict_size // 2
-    return np.clip(q, 0, dict_size - 1)
 
 
 @pytest.mark.parametrize("lossless", ["HUFFMAN", "HUFFMAN_ZSTD"])

@@ -420,8 +420,11 @@ def _decode_model(dict_size, chunk, n, units, has_sync, book_max, ndec, cf, seri
     keys = (dict_size * 2 + 7) // 8 * 8 + 16 * 64 * 8
     if not serial and not par and 1024 <= chunk <= 2 ** 24 and dict_size <= 65536 and book_max <= 32:
         sync = has_sync and chunk <= 65535
-        return dict(kind="ring", sync=int(sync), tb=0, lds=0, rtb=max(8, min(14, 12 if tb is None else tb)),
-                    pair=int(sync and (pair == 2 or (pair == 1 and units * 64.0 <= 6.5 * n))))
+        rtb = max(8, min(14, 12 if tb is None else tb))
+        # (the pair table's root, 8 << rtb bytes, beside the rings of 8 waves in the launch's 150 KiB: 13 bits at most)
+        fits = (8 << rtb) + 8 * (8 * 64 * 8 + 64 * 17 * 2) <= 150 * 1024
+        return dict(kind="ring", sync=int(sync), tb=0, lds=0, rtb=rtb,
+                    pair=int(sync and fits and (pair == 2 or (pair == 1 and units * 64.0 <= 6.5 * n))))
     if ndec <= cf:
         return dict(kind="none", sync=0, pair=0, tb=0, rtb=0, lds=0)
     t = 15
@@ -464,8 +467,42 @@ def test_decoder_choice(dump):
     assert pick(serial=1, par=0, chunk=1024)["kind"] == "serial" and pick(serial=0, par=1, chunk=1024)["kind"] == "par"
     assert pick(tb=15, book_max=40, chunk=20480)["tb"] == 14 and pick(tb=15, book_max=20, chunk=512)["tb"] == 15
     assert pick(tb=15, book_max=20, chunk=20480)["rtb"] == 14 and pick(tb=8, book_max=20, chunk=20480)["rtb"] == 8
+    # (a root table of 14 bits leaves no room for pairs: that launch asked for more LDS than a workgroup has)
+    assert [pick(tb=t, book_max=20, chunk=20480)["pair"] for t in (12, 13, 14, 15)] == [1, 1, 0, 0]
     # (a value outside the switch's range is clamped, never taken for "not set")
     assert pick(tb=0, book_max=20, chunk=20480)["rtb"] == 8 and pick(tb=0, book_max=20, chunk=512)["tb"] == 8
+
+
+def test_sym16_output_takes_the_ring_decoder_or_nothing(dump):
+    """sym16_refusal: a caller whose output holds 16-bit symbols (mgh_lossless_decompress_sym16) is refused for
+    every plan that is not the ring decoder's -- the other decoders write int64 values -- and for none that is.
+    The plans: each condition of decode_plan's first branch on both sides of its edge."""
+    base = dict(dict_size=8192, chunk=20480, n=10 ** 6, units=10 ** 5, has_sync=1, book_max=20, ndec=49, cf=0, serial=0, par=0,
+                pair=1, tb=None)
+    cases = [base]
+    cases += [dict(base, chunk=c) for c in (1000, 1023, 1024, 1025, 65535, 65536, 2 ** 24, 2 ** 24 + 1)]
+    cases += [dict(base, book_max=b) for b in (1, 32, 33, 56)]
+    cases += [dict(base, serial=s, par=p, chunk=c) for s in (0, 1) for p in (0, 1) for c in (512, 1024)]
+    cases += [dict(base, has_sync=h, pair=p, tb=t) for h in (0, 1) for p in (0, 1, 2) for t in (None, 8, 14)]
+    cases += [dict(base, dict_size=d) for d in (2, 64, 16384)]
+    cases += [dict(base, ndec=n_, cf=c, book_max=b) for n_, c in ((0, 0), (3, 3)) for b in (20, 40)]  # nothing to decode
+    names = ("dict_size", "chunk", "n", "units", "has_sync", "book_max", "ndec", "cf", "serial", "par", "pair", "tb")
+    res = _run(dump, "".join("decode16 " + " ".join("unset" if c[k] is None else str(c[k]) for k in names) + "\n" for c in cases))
+    assert len(res) == len(cases)
+    seen = set()
+    for c, (kind, got) in zip(cases, res):
+        want = _decode_model(**c)["kind"]
+        assert kind == "decode16" and got == dict(kind=want, refused=int(want != "ring")), c
+        seen.add(want)
+    assert seen == {"ring", "par", "serial", "none"}
+    by = {tuple(sorted(c.items())): got["refused"] for c, (_, got) in zip(cases, res)}
+    pick = lambda **kw: by[tuple(sorted(dict(base, **kw).items()))]
+    # ... and the landmarks by name: the refusals the C ABI documents
+    assert pick() == 0 and [pick(chunk=c) for c in (1000, 1023, 1024, 65536)] == [1, 1, 0, 0]
+    assert [pick(book_max=b) for b in (32, 33)] == [0, 1]
+    assert pick(serial=1, par=0, chunk=1024) == 1 and pick(serial=0, par=1, chunk=1024) == 1
+    assert pick(has_sync=0, pair=1, tb=8) == 0 and pick(has_sync=1, pair=2, tb=14) == 0
+    assert pick(ndec=3, cf=3, book_max=40) == 1 and pick(ndec=3, cf=3, book_max=20) == 0
 
 
 def test_chunks_landed(dump, files):

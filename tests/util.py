@@ -43,6 +43,14 @@ def inside_field(shape, dtype=np.float32, seed=1):
     return np.ascontiguousarray(g.astype(dtype))
 
 
+def huffman_symbols(n, seed=3, width=6.0, dict_size=8192):
+    """Quantizer-like symbols for the lossless stage: a rounded normal of the given width about the middle of
+    the dictionary, clipped into [0, dict_size). int64."""
+    rng = np.random.default_rng(seed)
+    q = np.rint(rng.normal(0, width, n)).astype(np.int64) + dict_size // 2
+    return np.clip(q, 0, dict_size - 1)
+
+
 MAXDIM, BLOCK, VARIABLE = 0, 1, 2  # mgh_domain_decomposition
 
 
