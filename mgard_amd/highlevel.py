@@ -5,6 +5,15 @@ compress / decompress, the container header and the lossless stage, all through 
     v = mgard_amd.highlevel.decompress(buf)
 
 mirrors mgard_x::compress / decompress (reference include/compress_x.hpp:31-154).
+
+Streams. The container calls of the C ABI run on pipeline streams of their own, which are ordered against
+the NULL stream only (include/mgard_hip_compress.h, above mgh_pin_memory): work in flight on a NON-BLOCKING
+stream is not waited for, and torch's side streams are non-blocking. So every function here that is given a
+cuda tensor -- the array, the container, `out=`, `outs=` -- first synchronises the CURRENT stream of that
+tensor's device when it is not the device's default stream (_wait_for_current_stream): inside
+`with torch.cuda.stream(S)` a tensor that S is still producing is complete before the library reads it.
+Results are complete when a call returns, so a consumer on S needs nothing further. On the default stream
+nothing is synchronised here: the library's own ordering against the NULL stream holds.
 """
 import ctypes as C
 
@@ -331,12 +340,28 @@ def metadata_parse(data):
 
 
 # ---- whole-array compress / decompress -------------------------------------------------------
+def _wait_for_current_stream(*args):
+    """The stream contract of this module (see its docstring): for every cuda tensor among `args` (lists of
+    tensors are looked into; anything else is passed over), synchronise the current stream of the tensor's
+    device unless it is that device's default stream."""
+    import torch
+    done = set()
+    for a in args:
+        for t in (a if isinstance(a, (list, tuple)) else (a,)):
+            if isinstance(t, torch.Tensor) and t.is_cuda and t.device not in done:
+                done.add(t.device)
+                cur = torch.cuda.current_stream(t.device)
+                if cur != torch.cuda.default_stream(t.device):
+                    cur.synchronize()
+
+
 def _as_ptr(a):
     """(pointer, dtype code, shape, keepalive) of a numpy array or a cuda tensor."""
     import torch
     if isinstance(a, torch.Tensor):
         if not a.is_contiguous():
-            a = a.contiguous()
+            a = a.contiguous()  # (a copy on the current stream)
+        _wait_for_current_stream(a)
         dt = FLOAT if a.dtype == torch.float32 else DOUBLE if a.dtype == torch.float64 else None
         if dt is None:
             raise MgardHipError("float32 or float64 data expected")
@@ -357,6 +382,7 @@ def compress(data, tol, s=INF, mode=REL, coords=None, config=None, out_capacity=
     L = _hl()
     cfg = config if config is not None else Config()
     ptr, dt, shape, keep = _as_ptr(data)
+    _wait_for_current_stream(out)
     D = len(shape)
     shp = (C.c_uint64 * D)(*shape)
     cptr = None
@@ -512,6 +538,7 @@ def compress_ladder(data, tols, s=INF, mode=REL, coords=None, config=None, outs=
         outs = [torch.empty(cap, dtype=torch.uint8, device=data.device) if on_device else np.empty(cap, dtype=np.uint8)
                 for _ in range(k)]
     assert len(outs) == k, "one output buffer per tolerance"
+    _wait_for_current_stream(list(outs))
     optr = (C.c_void_p * max(k, 1))(*[o.data_ptr() if on_device else o.ctypes.data for o in outs])
     sizes = (C.c_size_t * max(k, 1))(*[int(o.numel()) if on_device else int(o.size) for o in outs])
     _check(getattr(L, _call)(D, dt, (C.c_uint64 * D)(*shape), k, (C.c_double * max(k, 1))(*tols), float(s),
@@ -535,6 +562,7 @@ def _container_ptr(buf):
     import torch
     if isinstance(buf, torch.Tensor) and buf.is_cuda:
         buf = buf.contiguous()
+        _wait_for_current_stream(buf)
         return C.c_void_p(buf.data_ptr()), int(buf.numel()), True, buf
     buf = np.ascontiguousarray(buf)
     return C.c_void_p(buf.ctypes.data), int(buf.size), False, buf
@@ -545,6 +573,7 @@ def _layers_out(buf0, out):
     array for a host one."""
     import torch
     shape, dt = infer(buf0)
+    _wait_for_current_stream(out)
     on_dev = isinstance(buf0, torch.Tensor) and buf0.is_cuda
     n = int(np.prod(shape))
     if on_dev:
@@ -595,6 +624,7 @@ def compress_masked(data, tol, s=INF, mode=REL, nonfinite=True, fill_value=None,
     L = _hl()
     cfg = config if config is not None else Config()
     ptr, dt, shape, keep = _as_ptr(data)
+    _wait_for_current_stream(out)
     D = len(shape)
     shp = (C.c_uint64 * D)(*shape)
     cptr, ckeep = _coords_ptr(coords, dt, D)
@@ -736,6 +766,7 @@ def infer(buf):
     import torch
     L = _hl()
     if isinstance(buf, torch.Tensor):
+        _wait_for_current_stream(buf)
         p, n = C.c_void_p(buf.data_ptr()), buf.numel()
     else:
         buf = np.ascontiguousarray(buf)
@@ -755,6 +786,7 @@ def infer_level(buf, level, config=None):
     L = _hl()
     cfg = config if config is not None else Config()
     if isinstance(buf, torch.Tensor):
+        _wait_for_current_stream(buf)
         p, n = C.c_void_p(buf.data_ptr()), buf.numel()
     else:
         buf = np.ascontiguousarray(buf)
@@ -776,6 +808,7 @@ def infer_level_nodes(buf, level, dim, config=None):
         raise ValueError("level must be >= 0 (infer_level(buf, None) gives l_target)")
     cfg = config if config is not None else Config()
     if isinstance(buf, torch.Tensor):
+        _wait_for_current_stream(buf)
         p, n = C.c_void_p(buf.data_ptr()), buf.numel()
     else:
         buf = np.ascontiguousarray(buf)
@@ -795,6 +828,7 @@ def infer_coarsened(buf, halvings, config=None):
     L = _hl()
     cfg = config if config is not None else Config()
     if isinstance(buf, torch.Tensor):
+        _wait_for_current_stream(buf)
         p, n = C.c_void_p(buf.data_ptr()), buf.numel()
     else:
         buf = np.ascontiguousarray(buf)
@@ -818,6 +852,7 @@ def infer_coarsened_nodes(buf, halvings, dim, config=None):
         raise ValueError("halvings must be >= 0 (infer_coarsened(buf, None) gives the largest number)")
     cfg = config if config is not None else Config()
     if isinstance(buf, torch.Tensor):
+        _wait_for_current_stream(buf)
         p, n = C.c_void_p(buf.data_ptr()), buf.numel()
     else:
         buf = np.ascontiguousarray(buf)
@@ -836,6 +871,7 @@ def infer_level_range(buf, level, config=None):
     L = _hl()
     cfg = config if config is not None else Config()
     if isinstance(buf, torch.Tensor):
+        _wait_for_current_stream(buf)
         p, n = C.c_void_p(buf.data_ptr()), buf.numel()
     else:
         buf = np.ascontiguousarray(buf)
@@ -862,6 +898,7 @@ class Progressive:
         self._on_dev = isinstance(buf, torch.Tensor) and buf.is_cuda
         if not self._on_dev:
             buf = np.ascontiguousarray(buf)
+        _wait_for_current_stream(buf)
         self._buf = buf
         self._dt = infer(buf)[1]
         p, n = (C.c_void_p(buf.data_ptr()), buf.numel()) if self._on_dev else (C.c_void_p(buf.ctypes.data), buf.size)
@@ -877,6 +914,7 @@ class Progressive:
         import torch
         if not self._p:
             raise MgardHipError("the reader is closed")
+        _wait_for_current_stream(self._buf, out)
         shape, _ = infer_level(self._buf, int(level), self._cfg)
         if self._on_dev:
             want = torch.float32 if self._dt == FLOAT else torch.float64
@@ -905,6 +943,7 @@ class Progressive:
         import torch
         if not self._p:
             raise MgardHipError("the reader is closed")
+        _wait_for_current_stream(self._buf, out)
         shape, _ = infer(self._buf)
         if window is not None:
             lo, ext = _window_args(window, len(shape))
@@ -994,6 +1033,7 @@ def verify(buf, original, config=None, coarsen=0):
     cfg = config if config is not None else Config()
     if isinstance(buf, torch.Tensor) and buf.is_cuda:
         buf = buf.contiguous()
+        _wait_for_current_stream(buf)
         p, n = C.c_void_p(buf.data_ptr()), buf.numel()
     else:
         buf = np.ascontiguousarray(buf)
@@ -1017,6 +1057,7 @@ def _decompress(buf, config, out, level, coarsen, full_grid, window=None):
     on_dev = isinstance(buf, torch.Tensor) and buf.is_cuda
     if not on_dev:
         buf = np.ascontiguousarray(buf)
+    _wait_for_current_stream(buf, out)
     if level is not None or coarsen is not None:
         if level is not None:
             shape, _ = infer_level(buf, int(level), cfg)
@@ -1105,6 +1146,7 @@ def compress_multi(data, tol, s=INF, mode=REL, devices=(0,), coords=None, config
     on_device = isinstance(data, torch.Tensor) and data.is_cuda
     if on_device:
         data = data.contiguous()
+        _wait_for_current_stream(data)
         np_dt = np.dtype(np.float32) if data.dtype == torch.float32 else np.dtype(np.float64)
         shape, nbytes, dptr = tuple(data.shape), data.numel() * data.element_size(), data.data_ptr()
     else:
@@ -1169,6 +1211,7 @@ def compress_dist(comm, rank, nranks, local, tol, s=INF, mode=REL, root=0, confi
         _check(L.mgh_dist_use_library(str(rccl_path).encode()))
     cfg = config if config is not None else Config()
     local = local.contiguous()
+    _wait_for_current_stream(local)
     dt = FLOAT if local.dtype == torch.float32 else DOUBLE
     shp = (C.c_uint64 * local.dim())(*local.shape)
     optr, size = C.c_void_p(), C.c_size_t(0)
@@ -1191,6 +1234,7 @@ def decompress_dist(comm, rank, nranks, container, local_shape, dtype, root=0, c
     cfg = config if config is not None else Config()
     dev = container.device if container is not None else device
     out = torch.empty(tuple(local_shape), dtype=dtype, device=dev)
+    _wait_for_current_stream(container)
     p = C.c_void_p(container.data_ptr()) if container is not None else None
     n = int(container.numel()) if container is not None else 0
     _check(L.mgh_decompress_dist(C.c_void_p(int(comm)), rank, nranks, root, p, n, C.c_void_p(out.data_ptr()),
