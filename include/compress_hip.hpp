@@ -300,6 +300,68 @@ inline compress_status_type masked_info(const void *compressed_data, size_t comp
   masked = rc == 1;
   return rc < 0 ? detail::status(rc) : compress_status_type::Success;
 }
+// EXTENSION: masked buffers in the reduced-resolution and preview readers (mgh_decompress_masked_level /
+// _coarsened / _preview / _preview_window). A node is masked when the element of the full array it stands on is
+// masked (sampling); masked positions hold spec.restore_value, every other position what the reader of the same
+// name without `masked_` writes for the container part. A plain container is a Failure.
+inline compress_status_type decompress_masked_level(const void *compressed_data, size_t compressed_size, int level,
+                                                    void *&decompressed_data, HighLevelConfig config,
+                                                    bool output_pre_allocated) {
+  const mgh_config c = detail::to_c(config);
+  return detail::status(mgh_decompress_masked_level(compressed_data, compressed_size, level, &decompressed_data, &c,
+                                                    output_pre_allocated ? 1 : 0));
+}
+inline compress_status_type decompress_masked_coarsened(const void *compressed_data, size_t compressed_size, int halvings,
+                                                        void *&decompressed_data, HighLevelConfig config,
+                                                        bool output_pre_allocated) {
+  const mgh_config c = detail::to_c(config);
+  return detail::status(mgh_decompress_masked_coarsened(compressed_data, compressed_size, halvings, &decompressed_data, &c,
+                                                        output_pre_allocated ? 1 : 0));
+}
+inline compress_status_type decompress_masked_preview(const void *compressed_data, size_t compressed_size, int halvings,
+                                                      void *&decompressed_data, HighLevelConfig config,
+                                                      bool output_pre_allocated) {
+  const mgh_config c = detail::to_c(config);
+  return detail::status(mgh_decompress_masked_preview(compressed_data, compressed_size, halvings, &decompressed_data, &c,
+                                                      output_pre_allocated ? 1 : 0));
+}
+inline compress_status_type decompress_masked_preview_window(const void *compressed_data, size_t compressed_size,
+                                                             int halvings, const std::vector<SIZE> &lo,
+                                                             const std::vector<SIZE> &ext, void *&decompressed_data,
+                                                             HighLevelConfig config, bool output_pre_allocated) {
+  if (lo.size() != ext.size()) return compress_status_type::Failure;
+  const mgh_config c = detail::to_c(config);
+  return detail::status(mgh_decompress_masked_preview_window(compressed_data, compressed_size, halvings, lo.data(),
+                                                             ext.data(), &decompressed_data, &c,
+                                                             output_pre_allocated ? 1 : 0));
+}
+// ... the sampled mask alone, one byte per element of the level array, the coarsened array or the window
+inline compress_status_type decompress_mask_level(const void *compressed_data, size_t compressed_size, int level,
+                                                  HighLevelConfig config, uint8_t *mask) {
+  const mgh_config c = detail::to_c(config);
+  return detail::status(mgh_decompress_mask_level(compressed_data, compressed_size, level, &c, mask));
+}
+inline compress_status_type decompress_mask_coarsened(const void *compressed_data, size_t compressed_size, int halvings,
+                                                      HighLevelConfig config, uint8_t *mask) {
+  const mgh_config c = detail::to_c(config);
+  return detail::status(mgh_decompress_mask_coarsened(compressed_data, compressed_size, halvings, &c, mask));
+}
+inline compress_status_type decompress_mask_window(const void *compressed_data, size_t compressed_size,
+                                                   const std::vector<SIZE> &lo, const std::vector<SIZE> &ext,
+                                                   HighLevelConfig config, uint8_t *mask) {
+  if (lo.size() != ext.size()) return compress_status_type::Failure;
+  const mgh_config c = detail::to_c(config);
+  return detail::status(mgh_decompress_mask_window(compressed_data, compressed_size, lo.data(), ext.data(), &c, mask));
+}
+// ... and mgh_verify_masked: verify against the user's own array, marks included; masked positions take part in
+// nothing (result.stats.n counts the valid ones, n_masked the others).
+inline compress_status_type verify_masked(const void *compressed_data, size_t compressed_size, const void *original_data,
+                                          size_t original_bytes, data_type dtype, int halvings, HighLevelConfig config,
+                                          mgh_verify_result &result, uint64_t &n_masked) {
+  const mgh_config c = detail::to_c(config);
+  return detail::status(mgh_verify_masked(compressed_data, compressed_size, original_data, original_bytes, (int)dtype,
+                                          halvings, &c, &result, &n_masked));
+}
 // EXTENSION: mgh_achieved_errors. What verify(compress(tol)) would report for every tolerance of `tols`
 // (1..64), from one decomposition and without writing a container. Containers of one subdomain (Failure
 // otherwise; mgh_last_error() says so); any supported lossless_type.

@@ -722,6 +722,56 @@ int mgh_decompress_masked(const void *compressed_data, size_t compressed_size, c
  * n bytes; n from mgh_infer_shape). */
 int mgh_decompress_mask(const void *compressed_data, size_t compressed_size, const mgh_config *config, uint8_t *mask);
 
+/* ---- Masked buffers in the reduced-resolution, preview and verify readers ------------------------------
+ * THE RULE (part of the contract):
+ *  - a node of a level array or of a coarsened array is masked when the element of the FULL array at that
+ *    node's index (mgh_infer_level_nodes, mgh_infer_coarsened_nodes) is masked. This is sampling: there is
+ *    no "any masked neighbour" rule;
+ *  - a position of a preview or of a preview window is masked when that position of the full array is;
+ *  - masked positions of any output hold restore_value's bits; every other position holds, bit for bit,
+ *    what the same reader writes for the container part (the first C bytes) alone.
+ * The container holds the FILLED array, so valid values near masked regions carry the influence of the
+ * fill: a coarse node next to land is a coarse node of the filled field. A preview carries no bound anyway.
+ * Each call is: the footer -> the plain reader on the first C bytes -> the mask record -> the sample of the
+ * packed mask through the node lists (mgh_mask_sample_; the window's lists are lo + i, and only its bits are
+ * gathered; the preview uses the full mask) -> mgh_mask_restore. Arguments, refusals and memory-space rules
+ * are those of the reader each one wraps (mgh_decompress_masked_level needs one subdomain, like
+ * mgh_decompress_level; the coarsened and preview readers take decomposed containers). A buffer without
+ * the footer is MGH_ERR_FORMAT. When nothing is masked (kind 2) the output is the plain reader's.
+ * Not built: the progressive reader with a mask; masked layers, ladders, budgets and targets; _multi and
+ * _dist; telling NaN from Inf. */
+int mgh_decompress_masked_level(const void *compressed_data, size_t compressed_size, int level, void **decompressed_data,
+                                const mgh_config *config, int output_pre_allocated);
+int mgh_decompress_masked_coarsened(const void *compressed_data, size_t compressed_size, int halvings,
+                                    void **decompressed_data, const mgh_config *config, int output_pre_allocated);
+int mgh_decompress_masked_preview(const void *compressed_data, size_t compressed_size, int halvings,
+                                  void **decompressed_data, const mgh_config *config, int output_pre_allocated);
+int mgh_decompress_masked_preview_window(const void *compressed_data, size_t compressed_size, int halvings,
+                                         const uint64_t *lo, const uint64_t *ext, void **decompressed_data,
+                                         const mgh_config *config, int output_pre_allocated);
+/* The sampled mask alone, one byte (0 or 1) per element of the level array, of the coarsened array or of the
+ * window [lo, lo + ext), into `mask` (host or device memory of the caller), like mgh_decompress_mask. */
+int mgh_decompress_mask_level(const void *compressed_data, size_t compressed_size, int level, const mgh_config *config,
+                              uint8_t *mask);
+int mgh_decompress_mask_coarsened(const void *compressed_data, size_t compressed_size, int halvings,
+                                  const mgh_config *config, uint8_t *mask);
+int mgh_decompress_mask_window(const void *compressed_data, size_t compressed_size, const uint64_t *lo,
+                               const uint64_t *ext, const mgh_config *config, uint8_t *mask);
+
+/* mgh_verify of a masked buffer against the user's OWN array, marks (NaN, +-Inf, fill values) included: it is
+ * mgh_verify on the container part with the masked compare kernel (mgh_compare_masked_) in place of the
+ * compare kernel -- per subdomain, its box is held against the full array's packed mask where it lies. Masked
+ * positions take part in nothing: stats.n counts the valid positions, *n_masked_out (may be NULL) the others.
+ * Nothing of the array's size is allocated beyond what mgh_verify allocates, plus the packed mask.
+ * The verdict: s = inf -- achieved = max_abs_err over the valid positions against the header's bound; s = 0
+ * -- achieved = sqrt(sum_sq_err / N) under normalize_coordinates (sqrt(sum_sq_err) without), N ALL elements
+ * of the array, masked ones included: the writer bounds the sum over the whole filled array, of which the
+ * valid positions are a part. within = 0 when an unmasked position is not finite. Any other s, and
+ * halvings > 0, as in mgh_verify (within = -1). A buffer without the footer is MGH_ERR_FORMAT. */
+int mgh_verify_masked(const void *compressed_data, size_t compressed_size, const void *original, size_t original_bytes,
+                      int original_dtype, int halvings, const mgh_config *config, mgh_verify_result *out,
+                      uint64_t *n_masked_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -41,6 +41,9 @@ SYMBOLS = [
     "mgh_compare",
     "mgh_mask_scan", "mgh_mask_fill", "mgh_mask_restore",
 ]
+# entry points of the library that no public header declares yet (trailing underscore): bound here for
+# mask_sample / compare_masked and their tests
+INTERNAL_SYMBOLS = ["mgh_mask_sample_", "mgh_compare_masked_"]
 
 
 class MgardHipError(RuntimeError):
@@ -171,6 +174,9 @@ def load_library():
     L.mgh_mask_scan.argtypes = [C.c_int, C.c_int, u64p, vp, C.c_int, C.c_double, vp, vp, vp]
     L.mgh_mask_fill.argtypes = [C.c_int, C.c_int, u64p, vp, vp, C.c_double, vp, vp]
     L.mgh_mask_restore.argtypes = [C.c_int, C.c_int, u64p, vp, C.c_double, vp, vp]
+    L.mgh_mask_sample_.argtypes = [C.c_int, u64p, vp, u64p, C.POINTER(vp), vp, vp, vp]
+    L.mgh_compare_masked_.argtypes = [C.c_int, C.c_int, u64p, vp, u64p, vp, u64p, vp, u64p, u64, C.POINTER(ErrorStats),
+                                     C.c_int, vp]
     _lib = L
     return L
 
@@ -323,6 +329,99 @@ def mask_restore(data, words, value):
         _check(load_library().mgh_mask_restore(D, dt, shp, _mask_words(words, data.numel(), "mask_restore"), float(value),
                                                C.c_void_p(data.data_ptr()), _stream()))
     return data
+
+
+def mask_sample(words, shape, idx_lists, out_shape=None):
+    """mgh_mask_sample_: (out_words, count) -- the packed mask of the dense array whose element (i_0 ...) is element
+    (idx_0[i_0] ...) of the array of `shape` that `words` is the packed mask of. idx_lists: one entry per dimension,
+    an int sequence, a cuda int32 / uint32 tensor, or None for the identity 0 .. out_shape[d] - 1 (out_shape is then
+    needed for that dimension; by default it is the lists' lengths, and shape[d] for None). An entry >= shape[d]
+    reads nothing and gives 0. count: the number of set output bits."""
+    import torch
+    shape = tuple(int(e) for e in shape)
+    D = len(shape)
+    if len(idx_lists) != D:
+        raise ValueError("mask_sample: one index list (or None) per dimension")
+    n = int(np.prod(shape, dtype=np.int64))
+    wp = _mask_words(words, n, "mask_sample")
+    keep, ptrs, lens = [], [], []
+    for d, lst in enumerate(idx_lists):
+        if lst is None:
+            ptrs.append(None)
+            lens.append(shape[d] if out_shape is None else int(out_shape[d]))
+            continue
+        if isinstance(lst, torch.Tensor):
+            if not (lst.is_cuda and lst.is_contiguous() and lst.dim() == 1 and lst.dtype in (torch.int32, getattr(torch, "uint32", torch.int32))):
+                raise ValueError("mask_sample: an index tensor must be a contiguous 1-D cuda int32 / uint32 tensor")
+            t = lst
+        else:
+            a = np.asarray(lst, dtype=np.int64).reshape(-1)
+            if a.size and (a.min() < 0 or a.max() > 0xffffffff):
+                raise ValueError("mask_sample: index outside 0 .. 2^32 - 1")
+            t = torch.from_numpy(a.astype(np.uint32).view(np.int32)).to(words.device)
+        keep.append(t)
+        ptrs.append(t.data_ptr())
+        lens.append(int(t.numel()))
+    if out_shape is not None and tuple(int(e) for e in out_shape) != tuple(lens):
+        raise ValueError("mask_sample: out_shape disagrees with the lengths of the lists")
+    n_out = int(np.prod(lens, dtype=np.int64))
+    out_words = torch.empty((n_out + 63) // 64, dtype=torch.int64, device=words.device)
+    d_count = torch.empty(1, dtype=torch.int64, device=words.device)
+    with torch.cuda.device(words.device):
+        _check(load_library().mgh_mask_sample_(D, (C.c_uint64 * D)(*shape), wp, (C.c_uint64 * D)(*lens),
+                                              (C.c_void_p * D)(*ptrs), C.c_void_p(out_words.data_ptr()),
+                                              C.c_void_p(d_count.data_ptr()), _stream()))
+    del keep
+    return out_words, int(d_count.item())
+
+
+def compare_masked(a, b, words, ld_m=None, bit0=0):
+    """mgh_compare_masked_: ErrorStats of the cuda tensor `a` (the reference) against `b` over the positions whose
+    bit of the packed mask `words` (int64 cuda tensor) is NOT set; `n` counts those positions. Element (i_0 ...) has
+    bit bit0 + its offset in an array of leading dimensions ld_m (None: dense, the arrays' shape) -- a box of a
+    larger array is held against that array's mask with ld_m = the array's shape and bit0 = the flat index of the
+    box's first element. Tensors with padded rows are read in place like compare's; other layouts through a copy."""
+    import torch
+    if tuple(a.shape) != tuple(b.shape):
+        raise ValueError("compare_masked: the arrays have different shapes")
+    if not all(isinstance(x, torch.Tensor) and x.is_cuda for x in (a, b, words)):
+        raise ValueError("compare_masked: a, b and words must be cuda tensors")
+    if not (words.is_contiguous() and words.dtype == torch.int64):
+        raise ValueError("compare_masked: `words` must be a contiguous int64 cuda tensor")
+    keep, ptrs, lds, dts = [], [], [], []
+    for x in (a, b):
+        ld = _leading_dims(x)
+        if ld is None and not x.is_contiguous():
+            x = x.contiguous()
+        dts.append({torch.float32: FLOAT, torch.float64: DOUBLE}.get(x.dtype))
+        ptrs.append(C.c_void_p(x.data_ptr()))
+        keep.append(x)
+        lds.append(None if ld is None or list(ld) == list(x.shape) else (C.c_uint64 * len(ld))(*ld))
+    if dts[0] is None or dts[0] != dts[1]:
+        raise ValueError("compare_masked: float32 or float64 arrays of one type expected")
+    shape = tuple(int(e) for e in a.shape)
+    D = len(shape)
+    ldm = None
+    if ld_m is not None:
+        if len(ld_m) != D:
+            raise ValueError("compare_masked: ld_m needs one entry per dimension")
+        ldm = (C.c_uint64 * D)(*[int(e) for e in ld_m])
+    # the last bit the view reaches must lie inside `words`
+    lead = [int(e) for e in ld_m] if ld_m is not None else list(shape)
+    last, run = int(bit0), 1
+    for d in range(D - 1, -1, -1):
+        last += (shape[d] - 1) * run
+        run *= lead[d]
+    if int(bit0) < 0 or (a.numel() and last >= 64 * words.numel()):
+        raise ValueError("compare_masked: the view of the mask leaves `words`")
+    out = ErrorStats()
+    device = a.device.index
+    with torch.cuda.device(device):
+        stream = _stream()
+    _check(load_library().mgh_compare_masked_(D, dts[0], (C.c_uint64 * max(D, 1))(*shape), ptrs[0], lds[0], ptrs[1], lds[1],
+                                             C.c_void_p(words.data_ptr()), ldm, int(bit0), C.byref(out), int(device), stream))
+    del keep
+    return out
 
 
 class Hierarchy:

@@ -4248,6 +4248,30 @@ int compare_launch(int D, const uint64_t *shape, const T *a, const uint64_t *str
   return MGH_SUCCESS;
 }
 
+// ... with a mask seen through the element strides str_m and bit0 (mgh_compare_masked_): always the row-wise
+// kernel, so that its sums are those of mgh_compare with leading dimensions
+template <typename T>
+int compare_masked_launch(int D, const uint64_t *shape, const T *a, const uint64_t *str_a, const T *b,
+                          const uint64_t *str_b, const uint64_t *words, const uint64_t *str_m, uint64_t bit0,
+                          mgh_error_stats *d_scratch, hipStream_t st) {
+  uint64_t n = 1;
+  for (int d = 0; d < D; d++) n *= shape[d];
+  const ComparePlan p = compare_plan(n, sizeof(T));
+  mgh_error_stats *partials = d_scratch + 1;
+  if (p.groups) {
+    uint64_t dense[MGH_MAX_DIM];
+    compact_strides(D, shape, dense);
+    const LdView Va = compare_view(D, shape, str_a ? str_a : dense), Vb = compare_view(D, shape, str_b ? str_b : dense),
+                 Vm = compare_view(D, shape, str_m ? str_m : dense);
+    k_compare_masked<T><<<(unsigned)p.groups, 256, 0, st>>>(a, Va, b, Vb, (const unsigned long long *)words, Vm, bit0, n,
+                                                             p.slab, partials);
+    HIP_TRY(hipGetLastError());
+  }
+  k_compare_final<<<1, 256, 0, st>>>(partials, (uint32_t)p.groups, d_scratch);
+  HIP_TRY(hipGetLastError());
+  return MGH_SUCCESS;
+}
+
 // Scratch of ONE call: taken from a per-device list of idle buffers (allocated when the list is empty)
 // and put back when the call returns, so two calls in flight -- on whatever streams and threads --
 // never share one, and the library holds as many buffers as calls have ever run at the same time,
@@ -4414,6 +4438,72 @@ int mgh_compare_device_(int D, int dtype, const uint64_t *shape, const void *d_a
                                 (mgh_error_stats *)d_scratch, st);
 }
 
+// mgh_compare with a packed mask (k_compare_masked): a position whose bit is set takes part in NOTHING. n is
+// the number of positions compared, i.e. the unmasked ones (the masked count is prod(shape) - n); nonfinite keeps
+// its meaning among them; argmax stays the flat index in the logical dense array.
+// The mask is a bit array seen through a view of its own, as a and b are: element (i_0 ...) of the logical array
+// has bit bit0 + sum_d i_d stride_d of `words`, the strides from ld_m in mgh_set_ld's convention (NULL: dense). So
+// a box of a larger array is compared against that array's mask with no gather: ld_m = the array's shape, bit0 =
+// the flat index of the box's first element. The caller guarantees that every bit of the view lies inside `words`.
+// a, b and words are DEVICE pointers (a host pointer is MGH_ERR_INVALID_ARGUMENT: the caller stages it, as
+// mgh_verify does); every extent is below 2^32. Determinism is mgh_compare's: no floating-point atomics, slabs
+// fixed by prod(shape). The reduction is the row-wise one of mgh_compare with leading dimensions whatever the
+// layout: with an all-zero mask every exact field equals mgh_compare's, and the sums equal, bit for bit, those of
+// mgh_compare called with leading dimensions. SYNCHRONOUS like mgh_compare.
+// INTERNAL for now (trailing underscore, in no public header; the Python layer and the tests call it): the public
+// face of the masked compare is mgh_verify_masked.
+int mgh_compare_masked_(int D, int dtype, const uint64_t *shape, const void *a, const uint64_t *ld_a, const void *b,
+                       const uint64_t *ld_b, const uint64_t *words, const uint64_t *ld_m, uint64_t bit0,
+                       mgh_error_stats *h_out, int device, void *stream) {
+  if (D < 1 || D > MGH_MAX_DIM) return fail(MGH_ERR_INVALID_ARGUMENT, "mgh_compare_masked_: D must be 1 .. MGH_MAX_DIM");
+  if (dtype != MGH_FLOAT && dtype != MGH_DOUBLE) return fail(MGH_ERR_INVALID_ARGUMENT, "mgh_compare_masked_: unknown dtype");
+  if (!shape || !a || !b || !words || !h_out) return fail(MGH_ERR_INVALID_ARGUMENT, "mgh_compare_masked_: NULL argument");
+  for (const uint64_t *ld : {ld_a, ld_b, ld_m})
+    for (int d = 1; ld && d < D; d++)
+      if (ld[d] < shape[d]) return fail(MGH_ERR_INVALID_ARGUMENT, "mgh_compare_masked_: ld[d] < shape[d]");
+  for (int d = 0; d < D; d++)
+    if (shape[d] == 0 || shape[d] > 0xffffffffull)
+      return fail(MGH_ERR_INVALID_ARGUMENT, "mgh_compare_masked_: an extent of 0, or of 2^32 or more");
+  if (device < 0 || device >= mgh_device_count()) return fail(MGH_ERR_INVALID_ARGUMENT, "mgh_compare_masked_: no such device");
+  HIP_TRY(hipSetDevice(device));
+  if (!compare_on_device(a) || !compare_on_device(b) || !compare_on_device(words))
+    return fail(MGH_ERR_INVALID_ARGUMENT, "mgh_compare_masked_: a, b and words must be device pointers (stage a host array first)");
+  hipStream_t st = (hipStream_t)stream;
+  CompareScratch scratch;
+  TRY(scratch.acquire(device));
+  scratch.st = st;
+  uint64_t sa[MGH_MAX_DIM], sb[MGH_MAX_DIM], sm[MGH_MAX_DIM];
+  if (ld_a) compact_strides(D, ld_a, sa);
+  if (ld_b) compact_strides(D, ld_b, sb);
+  if (ld_m) compact_strides(D, ld_m, sm);
+  const uint64_t *str_a = ld_a ? sa : nullptr, *str_b = ld_b ? sb : nullptr, *str_m = ld_m ? sm : nullptr;
+  mgh_error_stats *d_scratch = (mgh_error_stats *)scratch.p;
+  if (dtype == MGH_FLOAT)
+    TRY(compare_masked_launch<float>(D, shape, (const float *)a, str_a, (const float *)b, str_b, words, str_m, bit0, d_scratch, st));
+  else
+    TRY(compare_masked_launch<double>(D, shape, (const double *)a, str_a, (const double *)b, str_b, words, str_m, bit0, d_scratch, st));
+  HIP_TRY(hipMemcpyAsync(h_out, d_scratch, sizeof(*h_out), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  scratch.drained = true;
+  return MGH_SUCCESS;
+}
+
+// For highlevel.hip (mgh_verify_masked): mgh_compare_device_ with the mask given by element strides and bit0.
+int mgh_compare_masked_device_(int D, int dtype, const uint64_t *shape, const void *d_a, const uint64_t *stride_a,
+                               const void *d_b, const uint64_t *stride_b, const uint64_t *d_words, const uint64_t *stride_m,
+                               uint64_t bit0, void *d_scratch, void *stream) {
+  if (D < 1 || D > MGH_MAX_DIM || !shape || !d_a || !d_b || !d_words || !d_scratch || (dtype != MGH_FLOAT && dtype != MGH_DOUBLE))
+    return fail(MGH_ERR_INVALID_ARGUMENT, "mgh_compare_masked_device_: bad argument");
+  for (const uint64_t *str : {stride_a, stride_b, stride_m})
+    if (str && str[D - 1] != 1) return fail(MGH_ERR_INVALID_ARGUMENT, "mgh_compare_masked_device_: the fastest stride must be 1");
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == MGH_FLOAT)
+    return compare_masked_launch<float>(D, shape, (const float *)d_a, stride_a, (const float *)d_b, stride_b, d_words,
+                                        stride_m, bit0, (mgh_error_stats *)d_scratch, st);
+  return compare_masked_launch<double>(D, shape, (const double *)d_a, stride_a, (const double *)d_b, stride_b, d_words,
+                                       stride_m, bit0, (mgh_error_stats *)d_scratch, st);
+}
+
 // ---- missing-value masks (kernels_mask.hpp) -------------------------------------------------------------
 namespace {
 // D, shape, dtype and the element count the three entries share (32-bit-free, but refused from 2^32 on
@@ -4507,6 +4597,45 @@ int mgh_mask_restore_bits_(int D, int dtype, const uint64_t *shape, const uint64
 
 int mgh_mask_restore(int D, int dtype, const uint64_t *shape, const uint64_t *words, double value, void *data, void *stream) {
   return mgh_mask_restore_bits_(D, dtype, shape, words, mgh::mask_value_bits(dtype == MGH_DOUBLE, value), data, stream);
+}
+
+// The packed mask of a part of the array -- a level or coarsened grid through its node lists, a window through
+// lo + i (k_mask_sample). `words`: the packed mask of a dense array of `shape`. out_words: the packed mask of a
+// dense array of out_shape, ceil(prod(out_shape) / 64) words in the same bit order, the unused high bits of the
+// last word zero: output (i_0 ... i_{D-1}) is set when bit flat(idx_0[i_0], ..., idx_{D-1}[i_{D-1}]) of `words` is
+// set. THIS IS SAMPLING: a node is masked when the element of the full array it stands on is masked; masked
+// neighbours do not count.
+// d_idx: D pointers on the HOST to DEVICE arrays of out_shape[d] uint32 each; d_idx[d] == NULL (or d_idx == NULL,
+// for all) is the identity list 0 ... out_shape[d] - 1 and needs out_shape[d] <= shape[d]. An entry >= shape[d]
+// is the caller's error: nothing is read for it and its outputs are 0 -- a bad list cannot make the kernel fault.
+// d_count (device, may be NULL): the number of set output bits. ASYNCHRONOUS on `stream`, no allocation, no host
+// synchronisation; sizes as for the mgh_mask_* calls, for both shapes. Errors: MGH_ERR_INVALID_ARGUMENT with a
+// message, nothing launched.
+// INTERNAL for now (trailing underscore, in no public header; highlevel.hip, the Python layer and the tests call
+// it): the public faces of the sample are the mgh_decompress_masked_* / mgh_decompress_mask_* readers.
+int mgh_mask_sample_(int D, const uint64_t *shape, const uint64_t *words, const uint64_t *out_shape,
+                     const uint32_t *const *d_idx, uint64_t *out_words, uint64_t *d_count, void *stream) {
+  static_assert(mgh::kMaskMaxDim == MGH_MAX_DIM, "mask_plan.hpp: kMaskMaxDim");
+  uint64_t n = 0, n_out = 0;
+  TRY(mask_args("mgh_mask_sample_", D, MGH_FLOAT, shape, &n));
+  TRY(mask_args("mgh_mask_sample_", D, MGH_FLOAT, out_shape, &n_out));
+  if (!words || !out_words) return fail(MGH_ERR_INVALID_ARGUMENT, "mgh_mask_sample_: NULL argument");
+  mgh::mask::MaskSampleArgs A;
+  for (int k = 0; k < MGH_MAX_DIM; k++) {  // right-aligned, leading 1s
+    const int d = k - (MGH_MAX_DIM - D);
+    A.shape[k] = d >= 0 ? (uint32_t)shape[d] : 1u;
+    A.out_shape[k] = d >= 0 ? (uint32_t)out_shape[d] : 1u;
+    A.idx[k] = d >= 0 && d_idx ? d_idx[d] : nullptr;
+    if (!A.idx[k] && A.out_shape[k] > A.shape[k])
+      return fail(MGH_ERR_INVALID_ARGUMENT, "mgh_mask_sample_: the identity list (NULL) needs out_shape[d] <= shape[d]");
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const uint64_t nwords_out = mgh::mask_words(n_out);
+  if (d_count) HIP_TRY(hipMemsetAsync(d_count, 0, sizeof(uint64_t), st));
+  mgh::mask::k_mask_sample<<<mask_blocks((nwords_out + mgh::mask::kWaves - 1) / mgh::mask::kWaves), mgh::mask::kThreads, 0, st>>>(
+      (const unsigned long long *)words, A, n_out, nwords_out, (unsigned long long *)out_words, (unsigned long long *)d_count);
+  HIP_TRY(hipGetLastError());
+  return MGH_SUCCESS;
 }
 
 } // extern "C"

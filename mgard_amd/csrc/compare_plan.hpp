@@ -46,6 +46,11 @@ inline ComparePlan compare_plan(uint64_t n, size_t esz) {
   return p;
 }
 
+// mgh_compare_masked_: a wave holds `left` (1 .. 64) consecutive positions of a row against the mask bits
+// p, p + 1, ... They begin in word p / 64 at bit p % 64; the NEXT word is read only where they reach it, so
+// the last word of a mask is never stepped over.
+MGH_CMP_HD inline bool compare_mask_second_word(uint64_t p, uint32_t left) { return (p & 63) + left > 64; }
+
 // positions that take part in the maxima and sums
 MGH_CMP_HD inline uint64_t compare_finite(const mgh_error_stats &s) { return s.n - s.nonfinite; }
 

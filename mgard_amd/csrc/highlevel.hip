@@ -54,6 +54,13 @@ extern "C" size_t mgh_compare_scratch_bytes_(void);
 extern "C" void mgh_compare_release_(void);
 extern "C" int mgh_compare_device_(int D, int dtype, const uint64_t *shape, const void *d_a, const uint64_t *stride_a,
                                    const void *d_b, const uint64_t *stride_b, void *d_scratch, void *stream);
+// (capi.hip: the packed mask of a level grid, a coarsened grid or a window gathered out of the array's)
+extern "C" int mgh_mask_sample_(int D, const uint64_t *shape, const uint64_t *words, const uint64_t *out_shape,
+                                const uint32_t *const *d_idx, uint64_t *out_words, uint64_t *d_count, void *stream);
+// (capi.hip: ... with a packed mask seen through element strides and the bit of the first element)
+extern "C" int mgh_compare_masked_device_(int D, int dtype, const uint64_t *shape, const void *d_a, const uint64_t *stride_a,
+                                          const void *d_b, const uint64_t *stride_b, const uint64_t *d_words,
+                                          const uint64_t *stride_m, uint64_t bit0, void *d_scratch, void *stream);
 
 namespace {
 constexpr int kOutlierOverflow = -1000;  // internal: more outliers than the buffers hold
@@ -1642,13 +1649,15 @@ struct HlCache {
   // mgh_compress_masked / mgh_decompress_masked: the filled (or decoded) array; the packed mask with the scan's
   // statistics behind it; the mask's bytes as symbols of the lossless stage
   DevBuf mfill, mwords, msym;
+  // the masked readers at reduced resolution: the index lists of the sample, and the sampled packed mask
+  DevBuf midx, msamp;
   int dev = -1;
   // device bytes the cache holds now (they are reused, so they count as available to the next call)
   size_t held_bytes() const {
     size_t b = 0;
     for (auto &kv : hier) b += mgh_device_bytes(kv.second);
     for (auto &x : in) b += x.cap;
-    b += vres.cap + mfill.cap + mwords.cap + msym.cap;
+    b += vres.cap + mfill.cap + mwords.cap + msym.cap + midx.cap + msamp.cap;
     for (auto &l : lane) {
       b += l.q.cap + l.q2.cap + l.q3.cap + l.oidx.cap + l.oval.cap + l.sub.cap + l.orig.cap + l.cmp.cap;
       if (l.ll) b += l.ll->units.cap + l.ll->oidx.cap + l.ll->oval.cap;
@@ -1670,6 +1679,8 @@ struct HlCache {
     mfill.release();
     mwords.release();
     msym.release();
+    midx.release();
+    msamp.release();
     for (auto &l : lane) l.release();
     for (hipStream_t *s : {&copy_st, &aux_st}) {
       if (*s) (void)hipStreamDestroy(*s);
@@ -2527,6 +2538,8 @@ struct Window {
 // and the statistics of the whole array when the call is through.
 struct VerifyJob {
   const void *original = nullptr;
+  // mgh_verify_masked: the packed mask of the whole array on the device; a set position takes part in nothing
+  const uint64_t *d_words = nullptr;
   mgh_error_stats stats{};
   bool rel = false;  // the bound of the header
   double tol = 0, s = 0, norm = 0;
@@ -2810,20 +2823,21 @@ int decompress_impl(const fmt::Header &hd, size_t meta_size, const void *compres
     if (vfy) {
       const SubdomainPlan &P = plan[order[k]];
       const void *a = L.orig.p;
-      uint64_t astr[MGH_MAX_DIM];
-      if (vfy_in_place) {  // the box through its offset and the strides of the array
-        uint64_t run = 1, at = 0;
-        for (int d = dd.D - 1; d >= 0; d--) {
-          astr[d] = run;
-          at += P.off[d] * run;
-          run *= dshape[d];
-        }
-        a = (const char *)vfy->original + at * elem;
-      } else {
-        HL_TRY(copy_box(P.ext, P.off, dshape, elem, L.orig.p, vfy->original, nullptr, true, L.st));
+      // the box through its offset and the strides of the array: the original where it lies, and the mask
+      uint64_t astr[MGH_MAX_DIM], run = 1, at = 0;
+      for (int d = dd.D - 1; d >= 0; d--) {
+        astr[d] = run;
+        at += P.off[d] * run;
+        run *= dshape[d];
       }
-      HL_TRY(mgh_compare_device_(dd.D, dtype, P.ext.data(), a, vfy_in_place ? astr : nullptr, L.sub.p, nullptr, L.cmp.p,
-                                 L.st));
+      if (vfy_in_place) a = (const char *)vfy->original + at * elem;
+      else HL_TRY(copy_box(P.ext, P.off, dshape, elem, L.orig.p, vfy->original, nullptr, true, L.st));
+      if (vfy->d_words)
+        HL_TRY(mgh_compare_masked_device_(dd.D, dtype, P.ext.data(), a, vfy_in_place ? astr : nullptr, L.sub.p, nullptr,
+                                          vfy->d_words, astr, at, L.cmp.p, L.st));
+      else
+        HL_TRY(mgh_compare_device_(dd.D, dtype, P.ext.data(), a, vfy_in_place ? astr : nullptr, L.sub.p, nullptr, L.cmp.p,
+                                   L.st));
       HL_HIP(hipMemcpyAsync((char *)g_cache.vres.p + k * sizeof(mgh_error_stats), L.cmp.p, sizeof(mgh_error_stats),
                             hipMemcpyDeviceToDevice, L.st));
       return MGH_SUCCESS;
@@ -5508,6 +5522,181 @@ int decompress_mask_impl(const void *buf, size_t size, const mgh_config &cfg, ui
   return MGH_SUCCESS;
 }
 
+// ---- masked buffers in the reduced-resolution, preview and verify readers -----------------------------------
+// THE RULE: a node of a level or coarsened array is masked when the element of the full array at that node's
+// index is masked (sampling: masked neighbours do not count); a position of a preview or of a window is masked
+// when that position of the full array is. Masked positions hold restore_value's bits; every other position
+// holds, bit for bit, what the same reader writes for the container part alone -- near masked regions that
+// value carries the influence of the fill.
+struct MaskedRead {
+  int level = -1, halvings = -1;  // mgh_decompress_level / _coarsened, _preview(_window)
+  bool preview = false;
+  const uint64_t *lo = nullptr, *ext = nullptr;  // the window
+};
+
+// The shape of what the reader returns and, per dimension, the index in the full array of each of its positions
+// (sampled = false: the output is the full array and no list is made).
+int masked_read_lists(const MaskedView &v, const mgh_config &cfg, const MaskedRead &R, std::vector<uint64_t> &oshape,
+                      std::vector<std::vector<uint32_t>> &lists, bool &sampled) {
+  const int D = (int)v.hd.shape.size();
+  lists.assign(D, {});
+  sampled = true;
+  std::vector<uint64_t> idx;
+  if (R.level >= 0) {  // (refuses a decomposed container, as mgh_decompress_level does)
+    int L = 0;
+    HL_TRY(header_level_shape(v.hd, cfg, R.level, &L, &oshape));
+    for (int d = 0; d < D; d++) {
+      mgh::level_nodes(v.hd.shape[d], L - R.level, idx);
+      lists[d].assign(idx.begin(), idx.end());
+    }
+  } else if (R.lo) {
+    oshape.assign(R.ext, R.ext + D);
+    for (int d = 0; d < D; d++) {
+      if (R.ext[d] == 0 || R.lo[d] > v.hd.shape[d] || R.ext[d] > v.hd.shape[d] - R.lo[d])
+        return hl_fail(MGH_ERR_INVALID_ARGUMENT, "the window leaves the array");
+      for (uint64_t i = 0; i < R.ext[d]; i++) lists[d].push_back((uint32_t)(R.lo[d] + i));
+    }
+  } else if (R.preview) {
+    oshape = v.hd.shape;
+    sampled = false;
+  } else {  // the code that answers mgh_infer_coarsened_nodes
+    Decomposer dd;
+    HL_TRY(decomposer_from_header(v.hd, cfg, dd));
+    for (int d = 0; d < D; d++) {
+      StitchedLayout sl;
+      HL_TRY(hl_plan(stitched_layout(dd, cfg.max_larget_level, R.halvings, sl, d)));
+      lists[d].assign(sl.nodes[d].begin(), sl.nodes[d].end());
+      oshape = sl.shape;
+    }
+  }
+  for (int d = 0; d < D && sampled; d++)
+    if (lists[d].size() != oshape[d]) return hl_fail(MGH_ERR_FORMAT, "masked reader: node list and shape disagree");
+  return MGH_SUCCESS;
+}
+
+// The mask of the reader's output, packed, in the cache (queued on `st`): the full mask, or its sample through
+// the lists, which are uploaded into the cache's index buffer.
+int masked_read_words(const MaskedView &v, const std::vector<uint64_t> &oshape, const std::vector<std::vector<uint32_t>> &lists,
+                      bool sampled, hipStream_t st, uint64_t **d_words_out) {
+  HlCache &C = g_cache;
+  uint64_t *d_full = nullptr;
+  HL_TRY(masked_words(v, st, &d_full));
+  *d_words_out = d_full;
+  if (!sampled) return MGH_SUCCESS;
+  const int D = (int)oshape.size();
+  std::vector<uint32_t> all;
+  size_t at[MGH_MAX_DIM];
+  uint64_t n_out = 1;
+  for (int d = 0; d < D; d++) {
+    at[d] = all.size();
+    all.insert(all.end(), lists[d].begin(), lists[d].end());
+    n_out *= oshape[d];
+  }
+  HL_TRY(C.midx.ensure(all.size() * sizeof(uint32_t)));
+  HL_TRY(C.msamp.ensure(mask_packed_bytes(n_out)));
+  HL_HIP(hipMemcpyAsync(C.midx.p, all.data(), all.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+  HL_HIP(hipStreamSynchronize(st));  // (the lists' host copy ends with this call)
+  const uint32_t *d_idx[MGH_MAX_DIM];
+  for (int d = 0; d < D; d++) d_idx[d] = (const uint32_t *)C.midx.p + at[d];
+  HL_TRY(mgh_mask_sample_(D, v.hd.shape.data(), d_full, oshape.data(), d_idx, (uint64_t *)C.msamp.p, nullptr, st));
+  *d_words_out = (uint64_t *)C.msamp.p;
+  return MGH_SUCCESS;
+}
+
+int masked_open_or_refuse(const char *who, const void *buf, size_t size, MaskedView &v) {
+  const int opened = masked_open(buf, size, v);
+  if (opened < 0) return opened;
+  if (opened == 0) return hl_fail(MGH_ERR_FORMAT, std::string(who) + ": no mask footer (a plain container has the plain reader)");
+  return MGH_SUCCESS;
+}
+
+// masked_open -> the plain reader on the first C bytes into a device buffer -> the mask -> its sample -> restore
+int masked_read_impl(const void *buf, size_t size, const mgh_config &cfg, const MaskedRead &R, void **out, bool prealloc) {
+  MaskedView v;
+  HL_TRY(masked_open_or_refuse("masked reader", buf, size, v));
+  std::vector<uint64_t> oshape;
+  std::vector<std::vector<uint32_t>> lists;
+  bool sampled = false;
+  HL_TRY(masked_read_lists(v, cfg, R, oshape, lists, sampled));
+  size_t bytes = v.hd.is_double ? 8 : 4;
+  for (uint64_t e : oshape) bytes *= (size_t)e;
+  const bool in_dev = is_device_pointer(buf);
+  const bool out_dev = prealloc ? is_device_pointer(*out) : in_dev;
+  HL_TRY(cache_prepare(cfg.dev_id));
+  HlCache &C = g_cache;
+  hipStream_t st = C.lane[0].st;
+  const OutSlot slot{out, in_dev, prealloc};
+  HL_TRY(slot.alloc(bytes));
+  // the restore pass runs on the device: a host output is reconstructed in a device buffer first
+  void *d_data = *out;
+  int rc = MGH_SUCCESS;
+  if (!out_dev) {
+    if ((rc = C.mfill.ensure(bytes)) != MGH_SUCCESS) return slot.fail(rc);
+    d_data = C.mfill.p;
+  }
+  void *dst = d_data;
+  const size_t csize = (size_t)v.f.container;
+  if (R.level >= 0) rc = mgh_decompress_level(buf, csize, R.level, &dst, &cfg, 1);
+  else if (R.lo) rc = mgh_decompress_preview_window(buf, csize, R.halvings, R.lo, R.ext, &dst, &cfg, 1);
+  else if (R.preview) rc = mgh_decompress_preview(buf, csize, R.halvings, &dst, &cfg, 1);
+  else rc = mgh_decompress_coarsened(buf, csize, R.halvings, &dst, &cfg, 1);
+  if (rc != MGH_SUCCESS) return slot.fail(rc);
+  if (v.f.kind != kMaskNone) {
+    uint64_t *d_words = nullptr;
+    if ((rc = masked_read_words(v, oshape, lists, sampled, st, &d_words)) != MGH_SUCCESS) return slot.fail(rc);
+    rc = mgh_mask_restore_bits_((int)oshape.size(), v.dtype, oshape.data(), d_words, v.f.restore_bits, d_data, st);
+    if (rc != MGH_SUCCESS) return slot.fail(rc);
+  }
+  if (!out_dev && (rc = copy_any(*out, d_data, bytes, st)) != MGH_SUCCESS) return slot.fail(rc);
+  if (hipStreamSynchronize(st) != hipSuccess) return slot.fail(hl_fail(MGH_ERR_DEVICE, "masked reader: hipStreamSynchronize"));
+  return MGH_SUCCESS;
+}
+
+// ... and the sampled mask alone, one byte per output element
+int masked_read_mask_impl(const void *buf, size_t size, const mgh_config &cfg, const MaskedRead &R, uint8_t *mask) {
+  MaskedView v;
+  HL_TRY(masked_open_or_refuse("masked reader", buf, size, v));
+  std::vector<uint64_t> oshape;
+  std::vector<std::vector<uint32_t>> lists;
+  bool sampled = false;
+  HL_TRY(masked_read_lists(v, cfg, R, oshape, lists, sampled));
+  size_t n_out = 1;
+  for (uint64_t e : oshape) n_out *= (size_t)e;
+  HL_TRY(cache_prepare(cfg.dev_id));
+  HlCache &C = g_cache;
+  hipStream_t st = C.lane[0].st;
+  uint64_t *d_words = nullptr;
+  HL_TRY(masked_read_words(v, oshape, lists, sampled, st, &d_words));
+  const bool out_dev = is_device_pointer(mask);
+  uint8_t *d_mask = mask;
+  if (!out_dev) {  // (the symbols have been narrowed into the words: their buffer is free)
+    HL_TRY(C.msym.ensure(n_out));
+    d_mask = (uint8_t *)C.msym.p;
+  }
+  k_mask_expand<<<mask_grid(n_out), 256, 0, st>>>((const unsigned long long *)d_words, n_out, d_mask);
+  HL_HIP(hipGetLastError());
+  if (!out_dev) HL_TRY(copy_any(mask, d_mask, n_out, st));
+  HL_HIP(hipStreamSynchronize(st));
+  return MGH_SUCCESS;
+}
+
+int masked_read_entry(const void *buf, size_t size, const mgh_config *config, const MaskedRead &R, void **out, int prealloc) {
+  if (!buf || !out) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (prealloc && !*out) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "pre-allocated output is NULL");
+  mgh_config cfg;
+  HL_TRY(masked_config(config, cfg));
+  return hl_guarded([&] { return masked_read_impl(buf, size, cfg, R, out, prealloc != 0); });
+}
+
+int masked_read_mask_entry(const void *buf, size_t size, const mgh_config *config, const MaskedRead &R, uint8_t *mask) {
+  if (!buf || !mask) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "NULL argument");
+  mgh_config cfg;
+  HL_TRY(masked_config(config, cfg));
+  return hl_guarded([&] { return masked_read_mask_impl(buf, size, cfg, R, mask); });
+}
+
+const char *const kBadHalvings = "halvings outside 0 .. the smallest l_target of the subdomains";
+
 } // namespace
 
 extern "C" {
@@ -5552,6 +5741,115 @@ int mgh_decompress_mask(const void *compressed_data, size_t compressed_size, con
   mgh_config cfg;
   HL_TRY(masked_config(config, cfg));
   return hl_guarded([&] { return decompress_mask_impl(compressed_data, compressed_size, cfg, mask); });
+}
+
+int mgh_decompress_masked_level(const void *compressed_data, size_t compressed_size, int level, void **decompressed_data,
+                                const mgh_config *config, int output_pre_allocated) {
+  if (level < 0) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "level outside 0 .. l_target");
+  MaskedRead R;
+  R.level = level;
+  return masked_read_entry(compressed_data, compressed_size, config, R, decompressed_data, output_pre_allocated);
+}
+
+int mgh_decompress_masked_coarsened(const void *compressed_data, size_t compressed_size, int halvings, void **decompressed_data,
+                                    const mgh_config *config, int output_pre_allocated) {
+  if (halvings < 0) return hl_fail(MGH_ERR_INVALID_ARGUMENT, kBadHalvings);
+  MaskedRead R;
+  R.halvings = halvings;
+  return masked_read_entry(compressed_data, compressed_size, config, R, decompressed_data, output_pre_allocated);
+}
+
+int mgh_decompress_masked_preview(const void *compressed_data, size_t compressed_size, int halvings, void **decompressed_data,
+                                  const mgh_config *config, int output_pre_allocated) {
+  if (halvings < 0) return hl_fail(MGH_ERR_INVALID_ARGUMENT, kBadHalvings);
+  MaskedRead R;
+  R.halvings = halvings;
+  R.preview = true;
+  return masked_read_entry(compressed_data, compressed_size, config, R, decompressed_data, output_pre_allocated);
+}
+
+int mgh_decompress_masked_preview_window(const void *compressed_data, size_t compressed_size, int halvings, const uint64_t *lo,
+                                         const uint64_t *ext, void **decompressed_data, const mgh_config *config,
+                                         int output_pre_allocated) {
+  if (!lo || !ext) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (halvings < 0) return hl_fail(MGH_ERR_INVALID_ARGUMENT, kBadHalvings);
+  MaskedRead R;
+  R.halvings = halvings;
+  R.preview = true;
+  R.lo = lo;
+  R.ext = ext;
+  return masked_read_entry(compressed_data, compressed_size, config, R, decompressed_data, output_pre_allocated);
+}
+
+int mgh_decompress_mask_level(const void *compressed_data, size_t compressed_size, int level, const mgh_config *config,
+                              uint8_t *mask) {
+  if (level < 0) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "level outside 0 .. l_target");
+  MaskedRead R;
+  R.level = level;
+  return masked_read_mask_entry(compressed_data, compressed_size, config, R, mask);
+}
+
+int mgh_decompress_mask_coarsened(const void *compressed_data, size_t compressed_size, int halvings, const mgh_config *config,
+                                  uint8_t *mask) {
+  if (halvings < 0) return hl_fail(MGH_ERR_INVALID_ARGUMENT, kBadHalvings);
+  MaskedRead R;
+  R.halvings = halvings;
+  return masked_read_mask_entry(compressed_data, compressed_size, config, R, mask);
+}
+
+int mgh_decompress_mask_window(const void *compressed_data, size_t compressed_size, const uint64_t *lo, const uint64_t *ext,
+                               const mgh_config *config, uint8_t *mask) {
+  if (!lo || !ext) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "NULL argument");
+  MaskedRead R;
+  R.preview = true;
+  R.lo = lo;
+  R.ext = ext;
+  return masked_read_mask_entry(compressed_data, compressed_size, config, R, mask);
+}
+
+int mgh_verify_masked(const void *compressed_data, size_t compressed_size, const void *original, size_t original_bytes,
+                      int original_dtype, int halvings, const mgh_config *config, mgh_verify_result *out,
+                      uint64_t *n_masked_out) {
+  if (!compressed_data || !original || !out) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (original_dtype != MGH_FLOAT && original_dtype != MGH_DOUBLE)
+    return hl_fail(MGH_ERR_INVALID_ARGUMENT, "mgh_verify_masked: dtype");
+  if (halvings < 0) return hl_fail(MGH_ERR_INVALID_ARGUMENT, kBadHalvings);
+  mgh_config cfg;
+  HL_TRY(masked_config(config, cfg));
+  VerifyJob job;
+  job.original = original;
+  uint64_t n_total = 0;
+  HL_TRY(hl_guarded([&]() -> int {
+    MaskedView v;
+    HL_TRY(masked_open_or_refuse("mgh_verify_masked", compressed_data, compressed_size, v));
+    n_total = v.n;
+    compressed_size = (size_t)v.f.container;
+    // the packed mask, whole and complete on the device before the subdomains' lanes read it
+    HL_TRY(cache_prepare(cfg.dev_id));
+    uint64_t *d_words = nullptr;
+    HL_TRY(masked_words(v, g_cache.lane[0].st, &d_words));
+    HL_HIP(hipStreamSynchronize(g_cache.lane[0].st));
+    job.d_words = d_words;
+    return MGH_SUCCESS;
+  }));
+  void *none = nullptr;  // (there is no output: pre-allocated, and never looked at)
+  HL_TRY(decompress_entry(compressed_data, compressed_size, &none, &cfg, 1, original_bytes, original_dtype, -1, halvings, true,
+                          nullptr, nullptr, &job));
+  mgh_verify_result r{};
+  r.stats = job.stats;
+  r.bound = job.rel ? job.tol * job.norm : job.tol;
+  r.bound_kind = std::isinf(job.s) ? 0 : job.s == 0 ? 1 : -1;
+  // s = 0: the writer bounds the sum over ALL elements of the filled array, of which the valid positions are a
+  // part -- the divisor is the array's element count, masked ones included
+  r.achieved = r.bound_kind == 0   ? r.stats.max_abs_err
+               : r.bound_kind == 1 ? (cfg.normalize_coordinates ? std::sqrt(r.stats.sum_sq_err / (double)n_total)
+                                                                : std::sqrt(r.stats.sum_sq_err))
+                                   : 0.0;
+  if (halvings > 0 || r.bound_kind < 0) r.within = -1;  // (a preview carries no bound)
+  else r.within = r.stats.nonfinite == 0 && r.achieved <= r.bound ? 1 : 0;
+  *out = r;
+  if (n_masked_out) *n_masked_out = n_total - r.stats.n;
+  return MGH_SUCCESS;
 }
 
 } // extern "C"

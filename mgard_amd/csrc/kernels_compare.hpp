@@ -168,6 +168,43 @@ k_compare_ld(const T *__restrict__ a, LdView Va, const T *__restrict__ b, LdView
   compare_store_partial(acc, partials + blockIdx.x);
 }
 
+// k_compare_ld with a mask (mgh_compare_masked_, mgh_verify_masked): a position whose bit is set takes part in
+// nothing. The mask is a bit array seen through a view of its own: element (i_0 ...) has bit bit0 + the view's
+// offset, so a box of a larger array is held against that array's mask where it lies. The 64 positions a wave
+// takes at once are 64 consecutive bits: the one or two words that hold them are read at a wave-uniform
+// address, once for the 64 lanes, and shifted into place. Which lane takes which position, and in which order,
+// is k_compare_ld's: with an all-zero mask the two give the same bits.
+template <typename T>
+__global__ void __launch_bounds__(256)
+k_compare_masked(const T *__restrict__ a, LdView Va, const T *__restrict__ b, LdView Vb,
+                 const unsigned long long *__restrict__ words, LdView Vm, uint64_t bit0, uint64_t n, uint64_t slab,
+                 mgh_error_stats *partials) {
+  const uint64_t lo = (uint64_t)blockIdx.x * slab;
+  const uint64_t hi = lo + slab < n ? lo + slab : n;
+  const uint32_t nf = Va.ext[MGH_MAX_DIM - 1];
+  const int lane = threadIdx.x & 63;
+  CompareAcc<T> acc;
+  const uint64_t r0 = lo / nf, r1 = (hi - 1) / nf;
+  for (uint64_t row = r0 + (threadIdx.x >> 6); row <= r1; row += kCompareThreads / 64) {
+    const uint64_t base = row * nf;
+    const uint32_t c0 = row == r0 ? (uint32_t)(lo - base) : 0u;
+    const uint32_t c1 = row == r1 ? (uint32_t)(hi - base) : nf;
+    const T *pa = a + ld_row_offset(Va, row);
+    const T *pb = b + ld_row_offset(Vb, row);
+    const uint64_t mrow = bit0 + ld_row_offset(Vm, row);
+    for (uint32_t k0 = c0; k0 < c1; k0 += 64) {  // (k0 is the wave's)
+      const uint64_t p = mrow + k0;
+      const int sh = (int)(p & 63);
+      const uint32_t left = c1 - k0 < 64u ? c1 - k0 : 64u;
+      unsigned long long m = words[p >> 6] >> sh;
+      if (compare_mask_second_word(p, left)) m |= words[(p >> 6) + 1] << (64 - sh);  // (only where the bits reach it)
+      const uint32_t k = k0 + lane;
+      if (k < c1 && !((m >> lane) & 1)) acc.take(pa[k], pb[k], base + k);
+    }
+  }
+  compare_store_partial(acc, partials + blockIdx.x);
+}
+
 // The partials (their argmax already an index of the whole logical array) into one result: lane t
 // folds the contiguous run [t * per, (t + 1) * per), then lanes, then waves, always the lower
 // workgroups first.

@@ -8,6 +8,9 @@
 //                   bits, re-aligned to the segment's first element, in 16 words of LDS; a masked element finds
 //                   its source with count-leading / find-first on them. Only copies: nothing is computed.
 //   k_mask_restore  stores one value at every masked position.
+//   k_mask_sample   (mgh_mask_sample_) gathers the packed mask of a level grid, a coarsened grid or a window out of
+//                   the array's: one wave ballot is one output word. Sampling -- a node is masked when the element
+//                   it stands on is; valid values near masked regions still carry the fill's influence.
 // fill and restore move bit patterns (W = uint32_t / uint64_t), so NaN payloads and -0.0 survive.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -189,6 +192,49 @@ k_mask_restore(const unsigned long long *__restrict__ words, uint64_t n, W value
   const uint64_t stride = (uint64_t)gridDim.x * kThreads;
   for (uint64_t i = (uint64_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += stride)
     if ((words[i >> 6] >> (i & 63)) & 1) data[i] = value;
+}
+
+// mgh_mask_sample_: the packed mask of a dense array of A.out_shape whose element (i_0 ...) is the source's
+// element (idx_0[i_0] ...). Shapes and lists are right-aligned in kMaskMaxDim dimensions with leading 1s, so
+// every loop over them unrolls; a NULL list is the identity.
+struct MaskSampleArgs {
+  uint32_t shape[kMaskMaxDim], out_shape[kMaskMaxDim];
+  const uint32_t *idx[kMaskMaxDim];
+};
+
+// One wave owns one output word at a time: lane l unravels output element 64 w + l, maps its coordinates through
+// the lists (plain cached loads: the lists are small and every wave reads them) and reads the source bit; the
+// ballot is the word. An entry outside the source's shape is not read for and votes 0, as a lane past the end
+// does. count (may be NULL): masked outputs, one integer atomic per workgroup.
+__global__ void __launch_bounds__(kThreads)
+k_mask_sample(const unsigned long long *__restrict__ words, MaskSampleArgs A, uint64_t n_out, uint64_t nwords_out,
+              unsigned long long *__restrict__ out_words, unsigned long long *count) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const uint64_t wave = (uint64_t)blockIdx.x * kWaves + wv, nwaves = (uint64_t)gridDim.x * kWaves;
+  unsigned long long masked = 0;
+  // (the loop bounds are the wave's: every lane reaches the ballot)
+  for (uint64_t w = wave; w < nwords_out; w += nwaves) {
+    const uint64_t e = w * 64 + lane;
+    bool m = false;
+    if (e < n_out) {
+      uint64_t flat;
+      if (mask_sample_source(kMaskMaxDim, A.shape, A.out_shape, A.idx, (uint32_t)e, flat))
+        m = (words[flat >> 6] >> (flat & 63)) & 1;
+    }
+    const unsigned long long bits = __ballot(m);
+    if (lane == 0) {
+      out_words[w] = bits;
+      masked += (unsigned long long)__popcll(bits);
+    }
+  }
+  if (!count) return;  // (uniform: no barrier is skipped by a part of the workgroup)
+  __shared__ unsigned long long part[kWaves];
+  if (lane == 0) part[wv] = masked;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < kWaves; w++) masked += part[w];
+    if (masked) atomicAdd(count, masked);
+  }
 }
 
 } // namespace mask

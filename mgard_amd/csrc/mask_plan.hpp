@@ -175,4 +175,44 @@ MGH_MASK_HD inline void mask_segment_words(uint64_t start, uint64_t len, uint64_
   nwords = (int)(((uint64_t)shift + len + 63) / 64);
 }
 
+// ---- sampling a packed mask (mgh_mask_sample_) ---------------------------------------------------------------
+// Output element e of a dense array of `out_shape` is set when the element of the source array at the
+// coordinates (idx_0[i_0], ..., idx_{D-1}[i_{D-1}]) is set: a level or coarsened grid through its node lists, a
+// window through lo + i. Every count here is below 2^32 (the limit of the mgh_mask_* calls), so the arithmetic
+// is 32-bit; the kernel (kernels_mask.hpp: k_mask_sample) and tests/cpp/mask_sample_dump.cpp share it.
+constexpr int kMaskMaxDim = 5;  // (MGH_MAX_DIM)
+
+// coordinates of flat element e of a dense row-major array of `ext`
+MGH_MASK_HD inline void mask_unravel(int D, const uint32_t *ext, uint32_t e, uint32_t *coord) {
+  for (int d = D - 1; d > 0; d--) {
+    const uint32_t q = e / ext[d];
+    coord[d] = e - q * ext[d];
+    e = q;
+  }
+  coord[0] = e;
+}
+
+// flat index of `coord` in a dense row-major array of `shape`; false (and nothing to read) when a coordinate
+// lies outside it
+MGH_MASK_HD inline bool mask_flat_index(int D, const uint32_t *shape, const uint32_t *coord, uint64_t &flat) {
+  uint64_t f = 0;
+  bool inside = true;
+  for (int d = 0; d < D; d++) {
+    inside = inside && coord[d] < shape[d];
+    f = f * shape[d] + coord[d];
+  }
+  flat = f;
+  return inside;
+}
+
+// the source bit of output element e: lists[d] == nullptr is the identity list
+MGH_MASK_HD inline bool mask_sample_source(int D, const uint32_t *shape, const uint32_t *out_shape,
+                                           const uint32_t *const *lists, uint32_t e, uint64_t &flat) {
+  uint32_t c[kMaskMaxDim];
+  mask_unravel(D, out_shape, e, c);
+  for (int d = 0; d < D; d++)
+    if (lists[d]) c[d] = lists[d][c[d]];
+  return mask_flat_index(D, shape, c, flat);
+}
+
 } // namespace mgh

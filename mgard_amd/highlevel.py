@@ -48,6 +48,9 @@ HL_SYMBOLS = [
     "mgh_compress_layers", "mgh_layers_open", "mgh_layers_add", "mgh_layers_count", "mgh_layers_tolerance",
     "mgh_layers_data", "mgh_layers_close", "mgh_decompress_layers",
     "mgh_compress_masked", "mgh_masked_info", "mgh_decompress_masked", "mgh_decompress_mask",
+    "mgh_decompress_masked_level", "mgh_decompress_masked_coarsened", "mgh_decompress_masked_preview",
+    "mgh_decompress_masked_preview_window", "mgh_decompress_mask_level", "mgh_decompress_mask_coarsened",
+    "mgh_decompress_mask_window", "mgh_verify_masked",
     "mgh_lossless_compress_sym16", "mgh_lossless_compress_device_sym16", "mgh_lossless_decompress_sym16",
 ]
 
@@ -273,6 +276,15 @@ def _hl():
     L.mgh_masked_info.argtypes = [vp, C.c_size_t, C.POINTER(MaskedInfo)]
     L.mgh_decompress_masked.argtypes = [vp, C.c_size_t, C.POINTER(Config), C.POINTER(vp), C.c_int]
     L.mgh_decompress_mask.argtypes = [vp, C.c_size_t, C.POINTER(Config), vp]
+    for name in ("mgh_decompress_masked_level", "mgh_decompress_masked_coarsened", "mgh_decompress_masked_preview"):
+        getattr(L, name).argtypes = [vp, C.c_size_t, C.c_int, C.POINTER(vp), C.POINTER(Config), C.c_int]
+    L.mgh_decompress_masked_preview_window.argtypes = [vp, C.c_size_t, C.c_int, C.POINTER(u64), C.POINTER(u64),
+                                                       C.POINTER(vp), C.POINTER(Config), C.c_int]
+    L.mgh_decompress_mask_level.argtypes = [vp, C.c_size_t, C.c_int, C.POINTER(Config), vp]
+    L.mgh_decompress_mask_coarsened.argtypes = [vp, C.c_size_t, C.c_int, C.POINTER(Config), vp]
+    L.mgh_decompress_mask_window.argtypes = [vp, C.c_size_t, C.POINTER(u64), C.POINTER(u64), C.POINTER(Config), vp]
+    L.mgh_verify_masked.argtypes = [vp, C.c_size_t, vp, C.c_size_t, C.c_int, C.c_int, C.POINTER(Config),
+                                    C.POINTER(VerifyResult), C.POINTER(u64)]
     _declared = True
     return L
 
@@ -656,39 +668,143 @@ def masked_info(buf):
     return info if rc == 1 else None
 
 
-def decompress_masked(buf, config=None, out=None):
-    """mgh_decompress_masked: the array of a masked buffer with restore_value at every masked position. A numpy array
-    (host buffer) or a cuda tensor; `out` as for decompress_layers. A plain container is refused: it has decompress."""
-    L = _hl()
-    cfg = config if config is not None else Config()
-    p, n, _, keep = _container_ptr(buf)
-    info = masked_info(keep)
-    if info is None:
-        _check(L.mgh_decompress_masked(p, n, C.byref(cfg), C.byref(C.c_void_p()), 0))  # (raises: no footer)
-    out, optr = _layers_out(keep[:info.container_size], out)
-    _check(L.mgh_decompress_masked(p, n, C.byref(cfg), C.byref(optr), 1))
-    return out
-
-
-def decompress_mask(buf, config=None):
-    """mgh_decompress_mask: the mask of a masked buffer as a bool array of the data's shape (numpy for a host buffer, a
-    cuda tensor for a device one)."""
-    import torch
-    L = _hl()
-    cfg = config if config is not None else Config()
+def _masked_view(buf, cfg, level, coarsen, window, what):
+    """(pointer, size, on_device, keepalive, container part, shape of the view) of a masked buffer and one of the
+    views level / coarsen / window (at most one of them; none: the full array)."""
+    if sum(x is not None for x in (level, coarsen, window)) > 1:
+        raise ValueError("%s: pass at most one of `level`, `coarsen` and `window`" % what)
     p, n, on_dev, keep = _container_ptr(buf)
     info = masked_info(keep)
     if info is None:
-        raise MgardHipError("mgard_hip error -8: decompress_mask: no mask footer")
-    shape, _ = infer(keep[:info.container_size])
+        raise MgardHipError("mgard_hip error -8: %s: no mask footer (a plain container has the plain reader)" % what)
+    cont = keep[:info.container_size]
+    if level is not None:
+        shape, _ = infer_level(cont, int(level), cfg)
+    elif coarsen is not None:
+        if int(coarsen) < 0:
+            raise ValueError("coarsen must be >= 0")
+        shape, _ = infer_coarsened(cont, int(coarsen), cfg)
+    else:
+        shape = infer(cont)[0]
+    return p, n, on_dev, keep, cont, shape
+
+
+def _masked_out(cont, shape, out):
+    """`out`, or a new array of `shape`, for the array of the container `cont`, as (out, pointer): a cuda tensor for a
+    device container, a numpy array for a host one."""
+    import torch
+    _, dt = infer(cont)
+    _wait_for_current_stream(out)
+    n = int(np.prod(shape))
+    if isinstance(cont, torch.Tensor) and cont.is_cuda:
+        want = torch.float32 if dt == FLOAT else torch.float64
+        if out is None:
+            out = torch.empty(tuple(shape), dtype=want, device=cont.device)
+        if not (isinstance(out, torch.Tensor) and out.is_cuda and out.is_contiguous() and out.dtype == want and
+                out.device == cont.device and out.numel() == n):
+            raise ValueError("`out` must be a contiguous cuda tensor of the view's shape and the stream's type")
+        return out, C.c_void_p(out.data_ptr())
+    npdt = np.float32 if dt == FLOAT else np.float64
+    if out is None:
+        out = np.empty(tuple(shape), dtype=npdt)
+    if not (isinstance(out, np.ndarray) and out.flags.c_contiguous and out.flags.writeable and out.dtype == npdt and
+            out.size == n):
+        raise ValueError("`out` must be a writeable C-contiguous numpy array of the view's shape and type")
+    return out, C.c_void_p(out.ctypes.data)
+
+
+def decompress_masked(buf, config=None, out=None, level=None, coarsen=None):
+    """mgh_decompress_masked: the array of a masked buffer with restore_value at every masked position. A numpy array
+    (host buffer) or a cuda tensor; `out` as for decompress_layers. A plain container is refused: it has decompress.
+    `level` / `coarsen`: mgh_decompress_masked_level / _coarsened -- decompress(buf[:C], level=...) or (coarsen=...)
+    with restore_value at every node whose element of the FULL array is masked (sampling: masked neighbours do not
+    count). The valid nodes are those of the filled array's hierarchy: near masked regions they carry the fill's
+    influence."""
+    L = _hl()
+    cfg = config if config is not None else Config()
+    if level is None and coarsen is None:
+        p, n, _, keep = _container_ptr(buf)
+        info = masked_info(keep)
+        if info is None:
+            _check(L.mgh_decompress_masked(p, n, C.byref(cfg), C.byref(C.c_void_p()), 0))  # (raises: no footer)
+        out, optr = _layers_out(keep[:info.container_size], out)
+        _check(L.mgh_decompress_masked(p, n, C.byref(cfg), C.byref(optr), 1))
+        return out
+    p, n, _, keep, cont, shape = _masked_view(buf, cfg, level, coarsen, None, "decompress_masked")
+    out, optr = _masked_out(cont, shape, out)
+    if level is not None:
+        _check(L.mgh_decompress_masked_level(p, n, int(level), C.byref(optr), C.byref(cfg), 1))
+    else:
+        _check(L.mgh_decompress_masked_coarsened(p, n, int(coarsen), C.byref(optr), C.byref(cfg), 1))
+    del keep
+    return out
+
+
+def decompress_masked_preview(buf, coarsen, config=None, out=None, window=None):
+    """mgh_decompress_masked_preview(_window): decompress_preview(buf[:C], coarsen, window=window) with restore_value at
+    every position of the array (of the window) that is masked in the full array. A preview carries no bound."""
+    if coarsen is None:
+        raise ValueError("decompress_masked_preview needs `coarsen`")
+    if int(coarsen) < 0:
+        raise ValueError("coarsen must be >= 0")
+    L = _hl()
+    cfg = config if config is not None else Config()
+    p, n, _, keep, cont, shape = _masked_view(buf, cfg, None, None, None, "decompress_masked_preview")
+    if window is None:
+        out, optr = _masked_out(cont, shape, out)
+        _check(L.mgh_decompress_masked_preview(p, n, int(coarsen), C.byref(optr), C.byref(cfg), 1))
+    else:
+        wlo, wext = _window_args(window, len(shape))
+        out, optr = _masked_out(cont, tuple(int(e) for e in wext), out)
+        _check(L.mgh_decompress_masked_preview_window(p, n, int(coarsen), wlo, wext, C.byref(optr), C.byref(cfg), 1))
+    del keep
+    return out
+
+
+def decompress_mask(buf, config=None, level=None, coarsen=None, window=None):
+    """mgh_decompress_mask: the mask of a masked buffer as a bool array of the data's shape (numpy for a host buffer, a
+    cuda tensor for a device one). `level` / `coarsen` / window = (lo, ext): mgh_decompress_mask_level / _coarsened /
+    _window -- the mask sampled at the nodes of that level array or coarsened array, or the box of it."""
+    import torch
+    L = _hl()
+    cfg = config if config is not None else Config()
+    p, n, on_dev, keep, cont, shape = _masked_view(buf, cfg, level, coarsen, window, "decompress_mask")
+    if window is not None:
+        wlo, wext = _window_args(window, len(shape))
+        shape = tuple(int(e) for e in wext)
     if on_dev:
-        mask = torch.empty(shape, dtype=torch.uint8, device=keep.device)
+        mask = torch.empty(tuple(shape), dtype=torch.uint8, device=keep.device)
         mp = C.c_void_p(mask.data_ptr())
     else:
-        mask = np.empty(shape, dtype=np.uint8)
+        mask = np.empty(tuple(shape), dtype=np.uint8)
         mp = C.c_void_p(mask.ctypes.data)
-    _check(L.mgh_decompress_mask(p, n, C.byref(cfg), mp))
+    if level is not None:
+        _check(L.mgh_decompress_mask_level(p, n, int(level), C.byref(cfg), mp))
+    elif coarsen is not None:
+        _check(L.mgh_decompress_mask_coarsened(p, n, int(coarsen), C.byref(cfg), mp))
+    elif window is not None:
+        _check(L.mgh_decompress_mask_window(p, n, wlo, wext, C.byref(cfg), mp))
+    else:
+        _check(L.mgh_decompress_mask(p, n, C.byref(cfg), mp))
+    del keep
     return mask.bool() if on_dev else mask.astype(bool)
+
+
+def verify_masked(buf, original, config=None, coarsen=0):
+    """mgh_verify_masked: (VerifyResult, n_masked) of a masked buffer against `original`, the user's own array with its
+    NaN / +-Inf / fill values. Masked positions take part in nothing: stats.n counts the valid positions. s = inf:
+    achieved = max_abs_err over them; s = 0: sqrt(sum_sq_err / N) with N ALL elements (the writer's guarantee is over
+    the whole filled array). coarsen > 0 as in verify (within = -1)."""
+    L = _hl()
+    cfg = config if config is not None else Config()
+    p, n, _, keep = _container_ptr(buf)
+    optr, dt, shape, okeep = _as_ptr(original)
+    nbytes = int(np.prod(shape)) * (4 if dt == FLOAT else 8)
+    out = VerifyResult()
+    n_masked = C.c_uint64(0)
+    _check(L.mgh_verify_masked(p, n, optr, nbytes, dt, int(coarsen), C.byref(cfg), C.byref(out), C.byref(n_masked)))
+    del keep, okeep
+    return out, int(n_masked.value)
 
 
 class Layers:
