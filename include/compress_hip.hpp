@@ -362,6 +362,46 @@ inline compress_status_type verify_masked(const void *compressed_data, size_t co
   return detail::status(mgh_verify_masked(compressed_data, compressed_size, original_data, original_bytes, (int)dtype,
                                           halvings, &c, &result, &n_masked));
 }
+// EXTENSION: mgh_compress_pwrel. |x' - x| <= eps |x| at every element: the masked writer around y = log2|x| under an
+// ABS bound derived from eps, with the signs in a second bitmap: [masked buffer of y][flag record][footer]. +-0,
+// denormals and |x| < abs_floor decode to +0.0, NaN / +-Inf to NaN. An eps the data type cannot carry is a Failure.
+inline compress_status_type compress_pwrel(DIM D, data_type dtype, std::vector<SIZE> shape, double eps, double abs_floor,
+                                           const void *original_data, void *&compressed_data, size_t &compressed_size,
+                                           std::vector<const Byte *> coords, HighLevelConfig config,
+                                           bool output_pre_allocated) {
+  if (shape.size() != D) return compress_status_type::Failure;
+  const mgh_config c = detail::to_c(config);
+  std::vector<const void *> cp(coords.begin(), coords.end());
+  return detail::status(mgh_compress_pwrel(D, (int)dtype, shape.data(), eps, abs_floor, original_data, &compressed_data,
+                                           &compressed_size, cp.empty() ? nullptr : cp.data(), &c,
+                                           output_pre_allocated ? 1 : 0));
+}
+// ... its reader (mgh_decompress_pwrel). A plain container or a masked buffer is a Failure.
+inline compress_status_type decompress_pwrel(const void *compressed_data, size_t compressed_size, void *&decompressed_data,
+                                             HighLevelConfig config, bool output_pre_allocated) {
+  const mgh_config c = detail::to_c(config);
+  return detail::status(mgh_decompress_pwrel(compressed_data, compressed_size, &c, &decompressed_data,
+                                             output_pre_allocated ? 1 : 0));
+}
+// ... what the buffer is (mgh_pwrel_info): pwrel = false for any other buffer (info untouched); a footer that fails
+// a check is a Failure.
+inline compress_status_type pwrel_info(const void *compressed_data, size_t compressed_size, bool &pwrel,
+                                       struct mgh_pwrel_info &info) {
+  const int rc = mgh_pwrel_info(compressed_data, compressed_size, &info);
+  pwrel = rc == 1;
+  return rc < 0 ? detail::status(rc) : compress_status_type::Success;
+}
+// ... and mgh_verify_pwrel: the decoded array against the user's own; within = the bound holds at every valid
+// element, every class and sign came back, and nothing at or above the floor was zeroed.
+inline compress_status_type verify_pwrel(const void *compressed_data, size_t compressed_size, const void *original_data,
+                                         size_t original_bytes, data_type dtype, HighLevelConfig config,
+                                         mgh_pwrel_compare &result, bool &within) {
+  const mgh_config c = detail::to_c(config);
+  int w = 0;
+  const int rc = mgh_verify_pwrel(compressed_data, compressed_size, original_data, original_bytes, (int)dtype, &c, &result, &w);
+  within = w == 1;
+  return detail::status(rc);
+}
 // EXTENSION: mgh_achieved_errors. What verify(compress(tol)) would report for every tolerance of `tols`
 // (1..64), from one decomposition and without writing a container. Containers of one subdomain (Failure
 // otherwise; mgh_last_error() says so); any supported lossless_type.

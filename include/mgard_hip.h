@@ -579,6 +579,38 @@ int mgh_mask_fill(int D, int dtype, const uint64_t *shape, const void *data, con
 int mgh_mask_restore(int D, int dtype, const uint64_t *shape, const uint64_t *words, double value, void *data,
                      void *stream);
 
+/* ---- Pointwise relative error bound (EXTENSION; the reference has nothing here) ----------------------
+ * The result types of the three streaming passes behind mgh_compress_pwrel / mgh_decompress_pwrel /
+ * mgh_verify_pwrel (mgard_hip_compress.h; classes, tolerance and trailer: csrc/pwrel_plan.hpp). An element x of
+ * type T is, against floor_eff = max(abs_floor, smallest normal of T):
+ *   nonfinite (NaN, +-Inf): mask bit 1, flag bit 1, decodes to a quiet NaN;
+ *   zeroed (|x| < floor_eff: +-0, denormals, small values): mask bit 1, flag bit 0, decodes to +0.0;
+ *   valid (the rest): mask bit 0, flag bit = sign of x, decodes to +-exp2(y').
+ * Both bitmaps have the layout of the packed mask above. The passes themselves -- forward (one read of x:
+ * y = (T)log2((double)|x|), both bitmaps by wave ballots, mgh_pwrel_stats), inverse (in place over the decoded y',
+ * the magnitude clamped to [smallest normal, largest finite] of T) and compare (mgh_pwrel_compare of an original
+ * against a reconstruction) -- are exported with a trailing underscore and declared in no public header yet, like
+ * mgh_mask_sample_: a function declared here with a stream parameter must have its row in the stream-order
+ * table of the test suite, which a later change adds together with the declarations.
+ * mgh_pwrel_stats: ymin / ymax are the extremes of y over the VALID elements (0, 0 when there is none);
+ * n_nonfinite of the n_masked are non-finite; n_flag counts the set flag bits (non-finite and negative valid).
+ * mgh_pwrel_compare: max_rel_err = max |x' - x| / |x| in double over the valid positions whose x' is finite, at
+ * flat index argmax (the lowest on a tie; 0, 0 when there is none); max_zeroed_abs: the largest |x| among zeroed
+ * positions; n_class_mismatch: a zeroed position that is not +0.0 to the bit, a non-finite position that is not
+ * NaN, or a valid position that is not finite and non-zero; n_sign_mismatch: a valid position, finite and
+ * non-zero, with the other sign. */
+typedef struct mgh_pwrel_stats {
+  uint64_t n, n_masked, n_nonfinite, n_flag;
+  double ymin, ymax;
+} mgh_pwrel_stats;
+typedef struct mgh_pwrel_compare {
+  uint64_t n, n_valid, n_zeroed, n_nonfinite;
+  double max_rel_err;
+  uint64_t argmax;
+  double max_zeroed_abs;
+  uint64_t n_class_mismatch, n_sign_mismatch;
+} mgh_pwrel_compare;
+
 #ifdef __cplusplus
 }
 #endif

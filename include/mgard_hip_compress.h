@@ -772,6 +772,53 @@ int mgh_verify_masked(const void *compressed_data, size_t compressed_size, const
                       int original_dtype, int halvings, const mgh_config *config, mgh_verify_result *out,
                       uint64_t *n_masked_out);
 
+/* ---- Pointwise relative error bound (EXTENSION; the reference has nothing here) -----------------------
+ * |x' - x| <= eps |x| at EVERY element, where REL and ABS bound a norm over the whole array: the masked writer
+ * around the field y = log2|x|, compressed under an ABS, s = inf bound delta (csrc/pwrel_plan.hpp has the
+ * classes, the derivation of delta and the trailer; mgard_hip.h the result types):
+ *   forward pass (x is read once: y = (T)log2((double)|x|), the mask = non-finite or |x| < floor_eff, the flag
+ *   bits = non-finite or negative, the statistics) -> delta = log2(1 + eps) - ulp_T(max |y|) - 1.5 E2, E2 = 2^-23
+ *   (float) / 2^-52 (double) -> fill -> the masked writer on y (restore_value 0) -> flag record -> footer:
+ *   [masked buffer of y, M bytes][flag record, S bytes][56-byte footer]
+ * The first M bytes ARE what mgh_compress_masked writes for y: mgh_decompress_masked opens them (the filled y with
+ * 0 at the masked positions), and their own first C bytes are an ordinary container of the filled y. The last
+ * bytes are not the masked footer's magic: mgh_masked_info of the whole buffer returns 0.
+ * floor_eff = max(abs_floor, smallest normal of T): +-0, denormals and values below it decode to +0.0; NaN and
+ * +-Inf decode to a quiet NaN; every other element keeps its sign and meets the bound.
+ * eps must be finite with 0 < eps < 1 and abs_floor finite and >= 0 (MGH_ERR_INVALID_ARGUMENT). Where the roundings
+ * of the transform would take more than half of log2(1 + eps) -- float with |y| up to 128: eps below about 1e-5 --
+ * the call is MGH_ERR_INVALID_ARGUMENT with a message that says so: a looser bound is never delivered silently.
+ * coords and config (its domain decomposition included) pass through unchanged. Memory spaces, footprint
+ * (a host array is uploaded once and transformed in place; a device array is not modified and y is written beside
+ * it), element count and MGH_ERR_OUTPUT_TOO_LARGE as for mgh_compress_masked.
+ * Not built: reduced-resolution, preview and progressive readers of such buffers; ladders, budgets, targets and
+ * layers; _multi and _dist; telling NaN from Inf, or -0.0 from +0.0. */
+int mgh_compress_pwrel(int D, int dtype, const uint64_t *shape, double eps, double abs_floor, const void *original_data,
+                       void **compressed_data, size_t *compressed_size, const void *const *coords,
+                       const mgh_config *config, int output_pre_allocated);
+/* The footer -> mgh_decompress of the container part -> mask words and flag words -> the inverse pass: quiet NaN,
+ * +0.0, or +-exp2(y') with the magnitude clamped to [smallest normal, largest finite] of T. Memory-space rules of
+ * mgh_decompress. A buffer without the footer (a plain container, a masked buffer) is MGH_ERR_FORMAT. */
+int mgh_decompress_pwrel(const void *compressed_data, size_t compressed_size, const mgh_config *config,
+                         void **decompressed_data, int output_pre_allocated);
+/* 1 and *info for such a buffer, 0 for a buffer without the footer's magic, MGH_ERR_FORMAT for a footer that has
+ * the magic and fails a check (M + S + 56 == size, the masked buffer's own checks, S against kind and n,
+ * n_flag <= n, the flag record's CRC-32). delta is the tolerance in the container's header. Kinds: 0 packed
+ * words, 1 one record of the lossless stage, 2 no bit set. */
+struct mgh_pwrel_info { /* (the tag only: the function has the name) */
+  double eps, abs_floor, delta;
+  uint64_t n_masked, n_flag;
+  uint64_t container_size, masked_size, mask_record_size, flag_record_size;
+  int mask_kind, flag_kind;
+};
+int mgh_pwrel_info(const void *compressed_data, size_t compressed_size, struct mgh_pwrel_info *info);
+/* Decodes the whole array and holds it against the user's OWN array in one pass, with the footer's abs_floor
+ * (mgh_pwrel_compare, mgard_hip.h). *within (may be NULL) = 1 exactly when max_rel_err <= eps, there is no class
+ * and no sign mismatch, and the largest zeroed |x| lies below floor_eff; 0 otherwise. The original may be a host
+ * or a device array of the buffer's type and size (MGH_ERR_INVALID_ARGUMENT otherwise). */
+int mgh_verify_pwrel(const void *compressed_data, size_t compressed_size, const void *original, size_t original_bytes,
+                     int original_dtype, const mgh_config *config, mgh_pwrel_compare *out, int *within);
+
 #ifdef __cplusplus
 }
 #endif

@@ -44,6 +44,8 @@ SYMBOLS = [
 # entry points of the library that no public header declares yet (trailing underscore): bound here for
 # mask_sample / compare_masked and their tests
 INTERNAL_SYMBOLS = ["mgh_mask_sample_", "mgh_compare_masked_"]
+# ... and the three streaming passes of the pointwise relative bound (pwrel_forward / pwrel_inverse / compare_pwrel)
+PWREL_INTERNAL_SYMBOLS = ["mgh_pwrel_forward_", "mgh_pwrel_inverse_", "mgh_compare_pwrel_"]
 
 
 class MgardHipError(RuntimeError):
@@ -80,6 +82,29 @@ class ErrorStats(C.Structure):
 
     def __repr__(self):
         return "ErrorStats(%s)" % ", ".join("%s=%r" % (k, getattr(self, k)) for k, _ in self._fields_)
+
+
+class PwrelStats(C.Structure):
+    """mgh_pwrel_stats: element count, masked count (non-finite or below the floor), the non-finite among them, the
+    set flag bits (non-finite, and negative valid elements), and the extremes of y = log2|x| over the valid elements
+    (0, 0 when there is none)."""
+    _fields_ = [("n", C.c_uint64), ("n_masked", C.c_uint64), ("n_nonfinite", C.c_uint64), ("n_flag", C.c_uint64),
+                ("ymin", C.c_double), ("ymax", C.c_double)]
+
+    def __repr__(self):
+        return "PwrelStats(%s)" % ", ".join("%s=%r" % (k, getattr(self, k)) for k, _ in self._fields_)
+
+
+class PwrelCompare(C.Structure):
+    """mgh_pwrel_compare (include/mgard_hip.h): an original against a reconstruction under the pointwise relative
+    bound -- max |x' - x| / |x| over the valid positions and where, the counts of the three classes, the largest |x|
+    that was zeroed, and the positions whose class or sign did not come back."""
+    _fields_ = [("n", C.c_uint64), ("n_valid", C.c_uint64), ("n_zeroed", C.c_uint64), ("n_nonfinite", C.c_uint64),
+                ("max_rel_err", C.c_double), ("argmax", C.c_uint64), ("max_zeroed_abs", C.c_double),
+                ("n_class_mismatch", C.c_uint64), ("n_sign_mismatch", C.c_uint64)]
+
+    def __repr__(self):
+        return "PwrelCompare(%s)" % ", ".join("%s=%r" % (k, getattr(self, k)) for k, _ in self._fields_)
 
 
 def lib_path():
@@ -177,6 +202,9 @@ def load_library():
     L.mgh_mask_sample_.argtypes = [C.c_int, u64p, vp, u64p, C.POINTER(vp), vp, vp, vp]
     L.mgh_compare_masked_.argtypes = [C.c_int, C.c_int, u64p, vp, u64p, vp, u64p, vp, u64p, u64, C.POINTER(ErrorStats),
                                      C.c_int, vp]
+    L.mgh_pwrel_forward_.argtypes = [C.c_int, C.c_int, u64p, vp, C.c_double, vp, vp, vp, vp, vp]
+    L.mgh_pwrel_inverse_.argtypes = [C.c_int, C.c_int, u64p, vp, vp, vp, vp]
+    L.mgh_compare_pwrel_.argtypes = [C.c_int, C.c_int, u64p, vp, vp, C.c_double, C.POINTER(PwrelCompare), vp]
     _lib = L
     return L
 
@@ -329,6 +357,56 @@ def mask_restore(data, words, value):
         _check(load_library().mgh_mask_restore(D, dt, shp, _mask_words(words, data.numel(), "mask_restore"), float(value),
                                                C.c_void_p(data.data_ptr()), _stream()))
     return data
+
+
+# ---- pointwise relative error bound (mgh_pwrel_forward_ / mgh_pwrel_inverse_ / mgh_compare_pwrel_) -----------------
+def pwrel_forward(data, abs_floor=0.0, out=None):
+    """mgh_pwrel_forward_ of a cuda tensor: (y, mask_words, flag_words, stats). y = (T)log2((double)|x|) at valid
+    positions and 0 at the others (`out` may be `data`: in place); mask bit: NaN / +-Inf or |x| < max(abs_floor,
+    smallest normal); flag bit: NaN / +-Inf, or a negative valid element; stats: PwrelStats."""
+    import torch
+    dt, shp, D = _mask_array(data, "pwrel_forward")
+    n = data.numel()
+    if out is None:
+        out = torch.empty_like(data)
+    if not (isinstance(out, torch.Tensor) and out.is_cuda and out.is_contiguous() and out.dtype == data.dtype and
+            out.shape == data.shape):
+        raise ValueError("pwrel_forward: `out` must be a contiguous cuda tensor of the data's shape and type")
+    mwords = torch.empty((n + 63) // 64, dtype=torch.int64, device=data.device)
+    fwords = torch.empty((n + 63) // 64, dtype=torch.int64, device=data.device)
+    d_stats = torch.empty(6, dtype=torch.int64, device=data.device)
+    with torch.cuda.device(data.device):
+        _check(load_library().mgh_pwrel_forward_(D, dt, shp, C.c_void_p(data.data_ptr()), float(abs_floor),
+                                                 C.c_void_p(out.data_ptr()), C.c_void_p(mwords.data_ptr()),
+                                                 C.c_void_p(fwords.data_ptr()), C.c_void_p(d_stats.data_ptr()), _stream()))
+    return out, mwords, fwords, PwrelStats.from_buffer_copy(d_stats.cpu().numpy().tobytes())
+
+
+def pwrel_inverse(data, mask_words, flag_words):
+    """mgh_pwrel_inverse_, in place over y': quiet NaN where mask and flag are set, +0.0 where only the mask is, else
+    +-exp2(y') (the flag bit is the sign) with the magnitude clamped to [smallest normal, largest finite]."""
+    import torch
+    dt, shp, D = _mask_array(data, "pwrel_inverse")
+    with torch.cuda.device(data.device):
+        _check(load_library().mgh_pwrel_inverse_(D, dt, shp, _mask_words(mask_words, data.numel(), "pwrel_inverse"),
+                                                 _mask_words(flag_words, data.numel(), "pwrel_inverse"),
+                                                 C.c_void_p(data.data_ptr()), _stream()))
+    return data
+
+
+def compare_pwrel(original, reconstructed, abs_floor=0.0):
+    """mgh_compare_pwrel_: PwrelCompare of the cuda tensor `original` against `reconstructed` (same shape and type)."""
+    import torch
+    dt, shp, D = _mask_array(original, "compare_pwrel")
+    if not (isinstance(reconstructed, torch.Tensor) and reconstructed.is_cuda and reconstructed.is_contiguous() and
+            reconstructed.dtype == original.dtype and reconstructed.shape == original.shape and
+            reconstructed.device == original.device):
+        raise ValueError("compare_pwrel: `reconstructed` must be a contiguous cuda tensor of the original's shape and type")
+    out = PwrelCompare()
+    with torch.cuda.device(original.device):
+        _check(load_library().mgh_compare_pwrel_(D, dt, shp, C.c_void_p(original.data_ptr()),
+                                                 C.c_void_p(reconstructed.data_ptr()), float(abs_floor), C.byref(out), _stream()))
+    return out
 
 
 def mask_sample(words, shape, idx_lists, out_shape=None):

@@ -51,6 +51,7 @@
 #include "kernels_qround.hpp"
 #include "kernels_qsym.hpp"
 #include "kernels_mask.hpp"
+#include "kernels_pwrel.hpp"
 
 namespace {
 
@@ -4635,6 +4636,105 @@ int mgh_mask_sample_(int D, const uint64_t *shape, const uint64_t *words, const 
   mgh::mask::k_mask_sample<<<mask_blocks((nwords_out + mgh::mask::kWaves - 1) / mgh::mask::kWaves), mgh::mask::kThreads, 0, st>>>(
       (const unsigned long long *)words, A, n_out, nwords_out, (unsigned long long *)out_words, (unsigned long long *)d_count);
   HIP_TRY(hipGetLastError());
+  return MGH_SUCCESS;
+}
+
+// ---- pointwise relative error bound (kernels_pwrel.hpp; classes and tolerance: pwrel_plan.hpp) ------------
+// The three streaming passes of mgh_compress_pwrel and its readers (include/mgard_hip.h describes them beside
+// mgh_pwrel_stats / mgh_pwrel_compare). Like the mgh_mask_* calls: no hierarchy, dense DEVICE arrays on the current
+// device, 1 ... 2^32 - 1 elements, the stream last. INTERNAL for now (trailing underscore, in no public header; the
+// Python layer and the tests call them): the public faces are mgh_compress_pwrel, mgh_decompress_pwrel and
+// mgh_verify_pwrel.
+namespace {
+int pwrel_floor_arg(const char *who, double abs_floor) {
+  if (!(abs_floor >= 0.0) || std::isinf(abs_floor))
+    return fail(MGH_ERR_INVALID_ARGUMENT, std::string(who) + ": abs_floor must be finite and >= 0");
+  return MGH_SUCCESS;
+}
+}  // namespace
+
+// y_out (may be data) = (T)log2((double)|x|) at valid positions, 0 at the others; mask_words / flag_words:
+// ceil(n / 64) words each; *stats: a DEVICE mgh_pwrel_stats. ASYNCHRONOUS on `stream`.
+int mgh_pwrel_forward_(int D, int dtype, const uint64_t *shape, const void *data, double abs_floor, void *y_out,
+                       uint64_t *mask_words, uint64_t *flag_words, mgh_pwrel_stats *stats, void *stream) {
+  uint64_t n = 0;
+  TRY(mask_args("mgh_pwrel_forward", D, dtype, shape, &n));
+  if (!data || !y_out || !mask_words || !flag_words || !stats) return fail(MGH_ERR_INVALID_ARGUMENT, "mgh_pwrel_forward: NULL argument");
+  TRY(pwrel_floor_arg("mgh_pwrel_forward", abs_floor));
+  static_assert(sizeof(mgh_pwrel_stats) == 6 * sizeof(unsigned long long), "kernels_pwrel.hpp: the statistics' six words");
+  hipStream_t st = (hipStream_t)stream;
+  const uint64_t nwords = mgh::mask_words(n);
+  unsigned long long *s = reinterpret_cast<unsigned long long *>(stats);
+  const unsigned blocks = mask_blocks((nwords + mgh::mask::kWaves * mgh::mask::kScanUnroll - 1) /
+                                      (mgh::mask::kWaves * mgh::mask::kScanUnroll));
+  const double floor_eff = mgh::pwrel_floor_eff(dtype == MGH_DOUBLE, abs_floor);
+  mgh::pwrel::k_pwrel_stats_begin<<<1, 64, 0, st>>>(s);
+  if (dtype == MGH_FLOAT)
+    mgh::pwrel::k_pwrel_forward<float><<<blocks, mgh::mask::kThreads, 0, st>>>(
+        (const float *)data, n, nwords, floor_eff, (float *)y_out, (unsigned long long *)mask_words,
+        (unsigned long long *)flag_words, s);
+  else
+    mgh::pwrel::k_pwrel_forward<double><<<blocks, mgh::mask::kThreads, 0, st>>>(
+        (const double *)data, n, nwords, floor_eff, (double *)y_out, (unsigned long long *)mask_words,
+        (unsigned long long *)flag_words, s);
+  mgh::pwrel::k_pwrel_stats_end<<<1, 64, 0, st>>>(s, n);
+  HIP_TRY(hipGetLastError());
+  return MGH_SUCCESS;
+}
+
+// In place over the decoded y': quiet NaN / +0.0 at masked positions, +-exp2(y') clamped to the normal range of T
+// elsewhere. ASYNCHRONOUS on `stream`.
+int mgh_pwrel_inverse_(int D, int dtype, const uint64_t *shape, const uint64_t *mask_words, const uint64_t *flag_words,
+                       void *data_inout, void *stream) {
+  uint64_t n = 0;
+  TRY(mask_args("mgh_pwrel_inverse", D, dtype, shape, &n));
+  if (!mask_words || !flag_words || !data_inout) return fail(MGH_ERR_INVALID_ARGUMENT, "mgh_pwrel_inverse: NULL argument");
+  const unsigned blocks = mask_blocks((n + mgh::mask::kThreads - 1) / mgh::mask::kThreads);
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == MGH_FLOAT)
+    mgh::pwrel::k_pwrel_inverse<float><<<blocks, mgh::mask::kThreads, 0, st>>>(
+        (const unsigned long long *)mask_words, (const unsigned long long *)flag_words, n, (float *)data_inout);
+  else
+    mgh::pwrel::k_pwrel_inverse<double><<<blocks, mgh::mask::kThreads, 0, st>>>(
+        (const unsigned long long *)mask_words, (const unsigned long long *)flag_words, n, (double *)data_inout);
+  HIP_TRY(hipGetLastError());
+  return MGH_SUCCESS;
+}
+
+// mgh_pwrel_compare of an original against a reconstruction, both dense DEVICE arrays of the current device.
+// SYNCHRONOUS like mgh_compare: *out (host) is filled when the call returns; the scratch is mgh_compare's.
+int mgh_compare_pwrel_(int D, int dtype, const uint64_t *shape, const void *original, const void *reconstructed,
+                       double abs_floor, mgh_pwrel_compare *out, void *stream) {
+  uint64_t n = 0;
+  TRY(mask_args("mgh_compare_pwrel", D, dtype, shape, &n));
+  if (!original || !reconstructed || !out) return fail(MGH_ERR_INVALID_ARGUMENT, "mgh_compare_pwrel: NULL argument");
+  TRY(pwrel_floor_arg("mgh_compare_pwrel", abs_floor));
+  if (!compare_on_device(original) || !compare_on_device(reconstructed))
+    return fail(MGH_ERR_INVALID_ARGUMENT, "mgh_compare_pwrel: both arrays must be device pointers (stage a host array first)");
+  static_assert(sizeof(mgh_pwrel_compare) <= sizeof(mgh_error_stats), "the scratch of mgh_compare holds the partials");
+  int device = 0;
+  HIP_TRY(hipGetDevice(&device));
+  hipStream_t st = (hipStream_t)stream;
+  CompareScratch scratch;
+  TRY(scratch.acquire(device));
+  scratch.st = st;
+  mgh_pwrel_compare *d_out = (mgh_pwrel_compare *)scratch.p, *partials = d_out + 1;
+  const size_t esz = dtype == MGH_DOUBLE ? 8 : 4;
+  const mgh::ComparePlan p = mgh::compare_plan(n, esz);
+  const double floor_eff = mgh::pwrel_floor_eff(dtype == MGH_DOUBLE, abs_floor);
+  if (dtype == MGH_FLOAT)
+    mgh::pwrel::k_compare_pwrel<float><<<(unsigned)p.groups, 256, 0, st>>>((const float *)original, (const float *)reconstructed,
+                                                                          n, p.slab, floor_eff, partials);
+  else
+    mgh::pwrel::k_compare_pwrel<double><<<(unsigned)p.groups, 256, 0, st>>>((const double *)original,
+                                                                           (const double *)reconstructed, n, p.slab, floor_eff,
+                                                                           partials);
+  HIP_TRY(hipGetLastError());
+  mgh::pwrel::k_compare_pwrel_final<<<1, 256, 0, st>>>(partials, (uint32_t)p.groups, d_out);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(out, d_out, sizeof(*out), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  scratch.drained = true;
   return MGH_SUCCESS;
 }
 

@@ -42,6 +42,7 @@
 #include "size_plan.hpp"
 #include "target_plan.hpp"
 #include "mask_plan.hpp"
+#include "pwrel_plan.hpp"
 
 extern "C" void mgh_set_last_error_(const char *msg);  // capi.hip
 // (capi.hip: mgh_mask_fill / mgh_mask_restore with the value given as the bits of the data type)
@@ -5280,6 +5281,120 @@ int masked_shape_elems(const char *who, int D, const uint64_t *shape, uint64_t *
   return MGH_SUCCESS;
 }
 
+// The record of a packed bitmap of n bits, n_set of them set (the mask; the flag bits of the pointwise-relative
+// writer): one record of the lossless stage where that is smaller than the packed words (mask_record_kind).
+int bitmap_record(const char *who, const uint64_t *d_words, uint64_t n, uint64_t n_set, const mgh_config &cfg, hipStream_t st,
+                  uint32_t &kind, std::vector<uint8_t> &rec) {
+  HlCache &C = g_cache;
+  const uint64_t nw = mask_words(n), nb = mask_packed_bytes(n);
+  const std::string w(who);
+  mgh_lossless_ctx *ll = C.lane[0].ll;
+  uint64_t coded = 0;
+  rec.clear();
+  if (n_set && mask_record_codable(cfg.huff_block_size)) {
+    HL_TRY(C.msym.ensure(nb * 2));
+    k_mask_widen<<<mask_grid(nb), 256, 0, st>>>((const uint8_t *)d_words, nb, (uint16_t *)C.msym.p);
+    if (hipGetLastError() != hipSuccess) return hl_fail(MGH_ERR_DEVICE, w + ": k_mask_widen");
+    // (a code stream of the packed words' size or more is of no interest: cap_units)
+    HL_TRY(lossless_compress(ll, (const int64_t *)C.msym.p, nb, kMaskDict, cfg.huff_block_size, cfg.lossless,
+                             cfg.zstd_compress_level, nullptr, nullptr, 0, st, nullptr, ~(uint64_t)0, nw + 1, /*sym16=*/true));
+    if (!ll->overflow) coded = ll->record_size();
+  }
+  kind = mask_record_kind(n, n_set, coded);
+  if (kind == kMaskCoded) {
+    if (ll->on_host) {
+      rec = ll->host;
+    } else {
+      rec.resize(coded);
+      HL_TRY(record_write(ll, rec.data(), st));
+      if (hipStreamSynchronize(st) != hipSuccess) return hl_fail(MGH_ERR_DEVICE, w + ": reading the mask record back");
+    }
+  } else if (kind == kMaskPacked) {
+    rec.resize(nb);
+    if (hipMemcpyAsync(rec.data(), d_words, nb, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess)
+      return hl_fail(MGH_ERR_DEVICE, w + ": reading the packed mask back");
+  }
+  return MGH_SUCCESS;
+}
+
+// `tail` (host) behind the first `at` bytes of the output
+int write_behind(const char *who, void *out, size_t at, const std::vector<uint8_t> &tail, hipStream_t st) {
+  if (is_device_pointer(out)) {
+    if (hipMemcpyAsync((char *)out + at, tail.data(), tail.size(), hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess)
+      return hl_fail(MGH_ERR_DEVICE, std::string(who) + ": writing mask record and footer");
+  } else {
+    std::memcpy((char *)out + at, tail.data(), tail.size());
+  }
+  return MGH_SUCCESS;
+}
+
+// What the classifying pass of a writer left on the device: the array (`src`, device memory), its packed mask and
+// the statistics of the valid elements.
+struct MaskedScan {
+  const void *src = nullptr;
+  uint64_t n = 0, n_masked = 0;
+  double vmin = 0, vmax = 0;
+  uint64_t *d_words = nullptr;
+};
+
+// The masked writer behind its scan, shared by mgh_compress_masked and mgh_compress_pwrel: fill -> the output ->
+// mgh_compress of the filled array -> mask record -> footer. *csize: the bytes written (on entry the capacity of a
+// pre-allocated output). behind_min / behind_max: bytes the caller appends behind the masked buffer, at least and at
+// most (0, 0 for mgh_compress_masked): the first is kept free in a pre-allocated output, the second is added to an
+// allocated one. A failure has gone through slot.fail.
+int masked_write(const char *who, int D, int dtype, const uint64_t *shape, double tol, double s, int ebtype, const MaskedScan &S,
+                 double restore_value, const OutSlot &slot, size_t *csize, const void *const *coords, const mgh_config &cfg,
+                 size_t behind_min, size_t behind_max, size_t *cap_out) {
+  const bool is_double = dtype == MGH_DOUBLE;
+  const size_t elem = is_double ? 8 : 4;
+  const uint64_t n = S.n, nb = mask_packed_bytes(n);
+  const std::string w(who);
+  HlCache &C = g_cache;
+  hipStream_t st = C.lane[0].st;
+  const void *filled = S.src;  // (nothing masked: the array as it is, a device-resident one where it lies)
+  if (S.n_masked) {
+    HL_TRY(C.mfill.ensure(n * elem));
+    const uint64_t c_bits = mask_value_bits(is_double, mask_fill_constant(S.vmin, S.vmax));
+    HL_TRY(mgh_mask_fill_bits_(D, dtype, shape, S.src, S.d_words, c_bits, C.mfill.p, st));
+    HL_HIP(hipStreamSynchronize(st));
+    filled = C.mfill.p;
+  }
+  // the output: mgh_compress's own capacity, and room for the packed mask and the footer behind it
+  size_t cap = 0, ccap = 0;
+  if (slot.prealloc) {
+    cap = *csize;
+    if (cap <= kMaskFooterBytes + behind_min) return hl_fail(MGH_ERR_OUTPUT_TOO_LARGE, w + ": the output cannot hold the footer");
+    ccap = cap - kMaskFooterBytes - behind_min;
+  } else {
+    ccap = n * elem + (size_t)1e6;
+    cap = ccap + nb + kMaskFooterBytes + behind_max;
+    HL_TRY(slot.alloc(cap));
+  }
+  void *out = *slot.slot;
+  size_t container = ccap;
+  int rc = mgh_compress(D, dtype, shape, tol, s, ebtype, filled, &out, &container, coords, &cfg, 1);
+  if (rc != MGH_SUCCESS) return slot.fail(rc);
+  // the mask record: one record of the lossless stage where that is smaller than the packed words
+  MaskFooter f;
+  f.container = container;
+  f.n_masked = S.n_masked;
+  f.restore_bits = mask_value_bits(is_double, restore_value);
+  std::vector<uint8_t> rec;
+  if ((rc = bitmap_record(who, S.d_words, n, S.n_masked, cfg, st, f.kind, rec)) != MGH_SUCCESS) return slot.fail(rc);
+  f.record = rec.size();
+  f.crc = fmt::crc32(rec.data(), rec.size());
+  if (container + rec.size() + kMaskFooterBytes + behind_min > cap)
+    return slot.fail(hl_fail(MGH_ERR_OUTPUT_TOO_LARGE, w + ": the output cannot hold container, mask record and footer"));
+  rec.resize(rec.size() + kMaskFooterBytes);
+  mask_footer_serialize(f, rec.data() + f.record);
+  if ((rc = write_behind(who, out, container, rec, st)) != MGH_SUCCESS) return slot.fail(rc);
+  *csize = container + rec.size();
+  if (cap_out) *cap_out = cap;
+  return MGH_SUCCESS;
+}
+
 int compress_masked_impl(int D, int dtype, const uint64_t *shape, double tol, double s, int ebtype, const void *original,
                          const mgh_mask_spec &spec, void **compressed, size_t *csize, const void *const *coords,
                          const mgh_config &cfg, bool prealloc) {
@@ -5300,93 +5415,27 @@ int compress_masked_impl(int D, int dtype, const uint64_t *shape, double tol, do
   HL_TRY(cache_prepare(cfg.dev_id));
   HlCache &C = g_cache;
   hipStream_t st = C.lane[0].st;
-  const uint64_t nw = mask_words(n), nb = mask_packed_bytes(n);
+  const uint64_t nb = mask_packed_bytes(n);
   HL_TRY(C.mwords.ensure(nb + sizeof(mgh_mask_stats)));
-  uint64_t *d_words = (uint64_t *)C.mwords.p;
+  MaskedScan S;
+  S.n = n;
+  S.d_words = (uint64_t *)C.mwords.p;
   mgh_mask_stats *d_stats = (mgh_mask_stats *)((char *)C.mwords.p + nb);
-  const void *src = original;
+  S.src = original;
   if (!in_dev) {
     HL_TRY(C.mfill.ensure(n * elem));
     HL_TRY(copy_any(C.mfill.p, original, n * elem, st));
-    src = C.mfill.p;
+    S.src = C.mfill.p;
   }
-  HL_TRY(mgh_mask_scan(D, dtype, shape, src, spec.flags, spec.fill_value, d_words, d_stats, st));
+  HL_TRY(mgh_mask_scan(D, dtype, shape, S.src, spec.flags, spec.fill_value, S.d_words, d_stats, st));
   mgh_mask_stats hs{};
   HL_HIP(hipMemcpyAsync(&hs, d_stats, sizeof(hs), hipMemcpyDeviceToHost, st));
   HL_HIP(hipStreamSynchronize(st));
-  const void *filled = src;  // (nothing masked: the array as it is, a device-resident one where it lies)
-  if (hs.n_masked) {
-    HL_TRY(C.mfill.ensure(n * elem));
-    const uint64_t c_bits = mask_value_bits(is_double, mask_fill_constant(hs.vmin, hs.vmax));
-    HL_TRY(mgh_mask_fill_bits_(D, dtype, shape, src, d_words, c_bits, C.mfill.p, st));
-    HL_HIP(hipStreamSynchronize(st));
-    filled = C.mfill.p;
-  }
-  // the output: mgh_compress's own capacity, and room for the packed mask and the footer behind it
-  const OutSlot slot{compressed, in_dev, prealloc};
-  size_t cap = 0, ccap = 0;
-  if (prealloc) {
-    cap = *csize;
-    if (cap <= kMaskFooterBytes) return hl_fail(MGH_ERR_OUTPUT_TOO_LARGE, "compress_masked: the output cannot hold the footer");
-    ccap = cap - kMaskFooterBytes;
-  } else {
-    ccap = n * elem + (size_t)1e6;
-    cap = ccap + nb + kMaskFooterBytes;
-    HL_TRY(slot.alloc(cap));
-  }
-  void *out = *compressed;
-  size_t container = ccap;
-  int rc = mgh_compress(D, dtype, shape, tol, s, ebtype, filled, &out, &container, coords, &cfg, 1);
-  if (rc != MGH_SUCCESS) return slot.fail(rc);
-  // the mask record: one record of the lossless stage where that is smaller than the packed words
-  MaskFooter f;
-  f.container = container;
-  f.n_masked = hs.n_masked;
-  f.restore_bits = mask_value_bits(is_double, spec.restore_value);
-  std::vector<uint8_t> rec;
-  mgh_lossless_ctx *ll = C.lane[0].ll;
-  uint64_t coded = 0;
-  if (hs.n_masked && mask_record_codable(cfg.huff_block_size)) {
-    if ((rc = C.msym.ensure(nb * 2)) != MGH_SUCCESS) return slot.fail(rc);
-    k_mask_widen<<<mask_grid(nb), 256, 0, st>>>((const uint8_t *)d_words, nb, (uint16_t *)C.msym.p);
-    if (hipGetLastError() != hipSuccess) return slot.fail(hl_fail(MGH_ERR_DEVICE, "compress_masked: k_mask_widen"));
-    // (a code stream of the packed words' size or more is of no interest: cap_units)
-    rc = lossless_compress(ll, (const int64_t *)C.msym.p, nb, kMaskDict, cfg.huff_block_size, cfg.lossless,
-                           cfg.zstd_compress_level, nullptr, nullptr, 0, st, nullptr, ~(uint64_t)0, nw + 1, /*sym16=*/true);
-    if (rc != MGH_SUCCESS) return slot.fail(rc);
-    if (!ll->overflow) coded = ll->record_size();
-  }
-  f.kind = mask_record_kind(n, hs.n_masked, coded);
-  auto device_fail = [&](const char *what) { return slot.fail(hl_fail(MGH_ERR_DEVICE, what)); };
-  if (f.kind == kMaskCoded) {
-    if (ll->on_host) {
-      rec = ll->host;
-    } else {
-      rec.resize(coded);
-      if ((rc = record_write(ll, rec.data(), st)) != MGH_SUCCESS) return slot.fail(rc);
-      if (hipStreamSynchronize(st) != hipSuccess) return device_fail("compress_masked: reading the mask record back");
-    }
-  } else if (f.kind == kMaskPacked) {
-    rec.resize(nb);
-    if (hipMemcpyAsync(rec.data(), d_words, nb, hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipStreamSynchronize(st) != hipSuccess)
-      return device_fail("compress_masked: reading the packed mask back");
-  }
-  f.record = rec.size();
-  f.crc = fmt::crc32(rec.data(), rec.size());
-  if (container + rec.size() + kMaskFooterBytes > cap)
-    return slot.fail(hl_fail(MGH_ERR_OUTPUT_TOO_LARGE, "compress_masked: the output cannot hold container, mask record and footer"));
-  rec.resize(rec.size() + kMaskFooterBytes);
-  mask_footer_serialize(f, rec.data() + f.record);
-  if (is_device_pointer(out)) {
-    if (hipMemcpyAsync((char *)out + container, rec.data(), rec.size(), hipMemcpyHostToDevice, st) != hipSuccess ||
-        hipStreamSynchronize(st) != hipSuccess)
-      return device_fail("compress_masked: writing mask record and footer");
-  } else {
-    std::memcpy((char *)out + container, rec.data(), rec.size());
-  }
-  *csize = container + rec.size();
-  return MGH_SUCCESS;
+  S.n_masked = hs.n_masked;
+  S.vmin = hs.vmin;
+  S.vmax = hs.vmax;
+  return masked_write("compress_masked", D, dtype, shape, tol, s, ebtype, S, spec.restore_value, OutSlot{compressed, in_dev, prealloc},
+                      csize, coords, cfg, 0, 0, nullptr);
 }
 
 // A masked buffer opened: the footer, the header of the container in front of it, and the record on the host.
@@ -5428,32 +5477,39 @@ int masked_open(const void *buf, size_t size, MaskedView &v) {
   return 1;
 }
 
-// The packed mask of an opened buffer in the cache's device buffer, queued on `st`.
-int masked_words(const MaskedView &v, hipStream_t st, uint64_t **d_words_out) {
+// The packed bitmap of n bits that a record of `kind` holds (bitmap_record), into the device buffer `dst` of at least
+// 8 ceil(n / 64) bytes, queued on `st`.
+int bitmap_words(uint32_t kind, const std::vector<uint8_t> &rec, uint64_t n, int lossless, void *dst, hipStream_t st) {
   HlCache &C = g_cache;
-  const uint64_t nb = mask_packed_bytes(v.n);
-  HL_TRY(C.mwords.ensure(nb + sizeof(mgh_mask_stats)));
-  *d_words_out = (uint64_t *)C.mwords.p;
-  if (v.f.kind == kMaskNone) {
-    HL_HIP(hipMemsetAsync(C.mwords.p, 0, nb, st));
-  } else if (v.f.kind == kMaskPacked) {
-    HL_HIP(hipMemcpyAsync(C.mwords.p, v.rec.data(), nb, hipMemcpyHostToDevice, st));
+  const uint64_t nb = mask_packed_bytes(n);
+  if (kind == kMaskNone) {
+    HL_HIP(hipMemsetAsync(dst, 0, nb, st));
+  } else if (kind == kMaskPacked) {
+    HL_HIP(hipMemcpyAsync(dst, rec.data(), nb, hipMemcpyHostToDevice, st));
     HL_HIP(hipStreamSynchronize(st));  // (the record's host copy belongs to the caller)
   } else {
     HL_TRY(C.msym.ensure(nb * 8));
     const mgh_decompress_stats kept = decompress_stats();  // (the statistics are the container's, not the mask's)
     bool sym16 = true;
     uint64_t ocount = 0;
-    const int rc = lossless_decompress(C.lane[0].ll, v.rec.data(), v.rec.size(), v.lossless, (int64_t *)C.msym.p, nb, &ocount,
+    const int rc = lossless_decompress(C.lane[0].ll, rec.data(), rec.size(), lossless, (int64_t *)C.msym.p, nb, &ocount,
                                        st, &sym16);
     decompress_stats() = kept;
     HL_TRY(rc);
     if (ocount) return hl_fail(MGH_ERR_FORMAT, "mask record: outliers in a record of bytes");
-    if (sym16) k_mask_narrow<uint16_t><<<mask_grid(nb), 256, 0, st>>>((const uint16_t *)C.msym.p, nb, (uint8_t *)C.mwords.p);
-    else k_mask_narrow<int64_t><<<mask_grid(nb), 256, 0, st>>>((const int64_t *)C.msym.p, nb, (uint8_t *)C.mwords.p);
+    if (sym16) k_mask_narrow<uint16_t><<<mask_grid(nb), 256, 0, st>>>((const uint16_t *)C.msym.p, nb, (uint8_t *)dst);
+    else k_mask_narrow<int64_t><<<mask_grid(nb), 256, 0, st>>>((const int64_t *)C.msym.p, nb, (uint8_t *)dst);
     HL_HIP(hipGetLastError());
   }
   return MGH_SUCCESS;
+}
+
+// The packed mask of an opened buffer in the cache's device buffer, queued on `st`.
+int masked_words(const MaskedView &v, hipStream_t st, uint64_t **d_words_out) {
+  HlCache &C = g_cache;
+  HL_TRY(C.mwords.ensure(mask_packed_bytes(v.n) + sizeof(mgh_mask_stats)));
+  *d_words_out = (uint64_t *)C.mwords.p;
+  return bitmap_words(v.f.kind, v.rec, v.n, v.lossless, C.mwords.p, st);
 }
 
 int masked_config(const mgh_config *config, mgh_config &cfg) {
@@ -5850,6 +5906,260 @@ int mgh_verify_masked(const void *compressed_data, size_t compressed_size, const
   *out = r;
   if (n_masked_out) *n_masked_out = n_total - r.stats.n;
   return MGH_SUCCESS;
+}
+
+} // extern "C"
+
+// ---- pointwise relative error bound: mgh_compress_pwrel and its readers (pwrel_plan.hpp) -------------------
+// (capi.hip: the three streaming passes of kernels_pwrel.hpp)
+extern "C" int mgh_pwrel_forward_(int D, int dtype, const uint64_t *shape, const void *data, double abs_floor, void *y_out,
+                                  uint64_t *mask_words, uint64_t *flag_words, mgh_pwrel_stats *stats, void *stream);
+extern "C" int mgh_pwrel_inverse_(int D, int dtype, const uint64_t *shape, const uint64_t *mask_words,
+                                  const uint64_t *flag_words, void *data_inout, void *stream);
+extern "C" int mgh_compare_pwrel_(int D, int dtype, const uint64_t *shape, const void *original, const void *reconstructed,
+                                  double abs_floor, mgh_pwrel_compare *out, void *stream);
+
+namespace {
+
+// forward (the array is read once: it stands in for the masked writer's scan) -> statistics -> delta -> the masked
+// writer's tail on y (ABS, s = inf, delta; restore_value 0) -> flag record -> footer
+int compress_pwrel_impl(int D, int dtype, const uint64_t *shape, double eps, double abs_floor, const void *original,
+                        void **compressed, size_t *csize, const void *const *coords, const mgh_config &cfg, bool prealloc) {
+  const bool is_double = dtype == MGH_DOUBLE;
+  const size_t elem = is_double ? 8 : 4;
+  uint64_t n = 0;
+  HL_TRY(masked_shape_elems("compress_pwrel", D, shape, &n));
+  double delta = 0;
+  if (const char *bad = pwrel_abs_tolerance(is_double, eps, -1.0, &delta)) return hl_fail(MGH_ERR_INVALID_ARGUMENT, bad);
+  if (!(abs_floor >= 0.0) || std::isinf(abs_floor))
+    return hl_fail(MGH_ERR_INVALID_ARGUMENT, "compress_pwrel: abs_floor must be finite and >= 0");
+  const bool in_dev = is_device_pointer(original);
+  // the array on the device (a host array is uploaded once and transformed in place), and for a device-resident one,
+  // which is not modified, y beside it
+  if ((in_dev ? 2 : 1) * (uint64_t)n * elem > cfg.max_memory_footprint)
+    return hl_fail(MGH_ERR_INVALID_ARGUMENT,
+                   "compress_pwrel: the array and its transformed copy do not fit max_memory_footprint (such arrays are "
+                   "not streamed in parts)");
+  HL_TRY(cache_prepare(cfg.dev_id));
+  HlCache &C = g_cache;
+  hipStream_t st = C.lane[0].st;
+  const uint64_t nb = mask_packed_bytes(n);
+  HL_TRY(C.mwords.ensure(nb + sizeof(mgh_pwrel_stats)));
+  HL_TRY(C.msamp.ensure(nb));
+  HL_TRY(C.mfill.ensure(n * elem));
+  uint64_t *d_flags = (uint64_t *)C.msamp.p;
+  mgh_pwrel_stats *d_stats = (mgh_pwrel_stats *)((char *)C.mwords.p + nb);
+  const void *x = original;
+  if (!in_dev) {
+    HL_TRY(copy_any(C.mfill.p, original, n * elem, st));
+    x = C.mfill.p;
+  }
+  MaskedScan S;
+  S.n = n;
+  S.src = C.mfill.p;
+  S.d_words = (uint64_t *)C.mwords.p;
+  HL_TRY(mgh_pwrel_forward_(D, dtype, shape, x, abs_floor, C.mfill.p, S.d_words, d_flags, d_stats, st));
+  mgh_pwrel_stats hs{};
+  HL_HIP(hipMemcpyAsync(&hs, d_stats, sizeof(hs), hipMemcpyDeviceToHost, st));
+  HL_HIP(hipStreamSynchronize(st));
+  S.n_masked = hs.n_masked;
+  S.vmin = hs.ymin;
+  S.vmax = hs.ymax;
+  const double ybound = hs.n_masked >= n ? -1.0 : std::fmax(std::fabs(hs.ymin), std::fabs(hs.ymax));
+  if (const char *bad = pwrel_abs_tolerance(is_double, eps, ybound, &delta)) return hl_fail(MGH_ERR_INVALID_ARGUMENT, bad);
+  const OutSlot slot{compressed, in_dev, prealloc};
+  size_t masked = prealloc ? *csize : 0, cap = 0;
+  HL_TRY(masked_write("compress_pwrel", D, dtype, shape, delta, std::numeric_limits<double>::infinity(), MGH_ABS, S, 0.0, slot,
+                      &masked, coords, cfg, kPwrelFooterBytes, nb + kPwrelFooterBytes, &cap));
+  // the flag record, like the mask record, and the footer found from the end
+  PwrelFooter f;
+  f.masked = masked;
+  f.n_flag = hs.n_flag;
+  f.eps = eps;
+  f.abs_floor = abs_floor;
+  std::vector<uint8_t> rec;
+  int rc = bitmap_record("compress_pwrel", d_flags, n, hs.n_flag, cfg, st, f.kind, rec);
+  if (rc != MGH_SUCCESS) return slot.fail(rc);
+  f.record = rec.size();
+  f.crc = fmt::crc32(rec.data(), rec.size());
+  if (masked + rec.size() + kPwrelFooterBytes > cap)
+    return slot.fail(hl_fail(MGH_ERR_OUTPUT_TOO_LARGE, "compress_pwrel: the output cannot hold masked buffer, flag record and footer"));
+  rec.resize(rec.size() + kPwrelFooterBytes);
+  pwrel_footer_serialize(f, rec.data() + f.record);
+  if ((rc = write_behind("compress_pwrel", *compressed, masked, rec, st)) != MGH_SUCCESS) return slot.fail(rc);
+  *csize = masked + rec.size();
+  return MGH_SUCCESS;
+}
+
+// A pointwise-relative buffer opened: its footer, the masked buffer in front of it, and the flag record on the host.
+struct PwrelView {
+  PwrelFooter f;
+  MaskedView m;
+  std::vector<uint8_t> rec;
+};
+
+// 1: such a buffer that passed every check; 0: no footer's magic; negative: a status.
+int pwrel_open(const void *buf, size_t size, PwrelView &v) {
+  if (size < kPwrelFooterBytes) return 0;
+  const bool in_dev = is_device_pointer(buf);
+  uint8_t tail[kPwrelFooterBytes];
+  const uint8_t *p = (const uint8_t *)buf;
+  if (in_dev) HL_TRY(aux_read(tail, p + size - kPwrelFooterBytes, kPwrelFooterBytes));
+  else std::memcpy(tail, p + size - kPwrelFooterBytes, kPwrelFooterBytes);
+  if (!pwrel_footer_present(tail, size)) return 0;
+  if (const char *bad = pwrel_footer_parse(tail, size, v.f)) return hl_fail(MGH_ERR_FORMAT, bad);
+  const int opened = masked_open(buf, (size_t)v.f.masked, v.m);
+  if (opened < 0) return opened;
+  if (opened == 0) return hl_fail(MGH_ERR_FORMAT, "pwrel footer: the bytes in front of the flag record are no masked buffer");
+  if (v.m.f.restore_bits != 0) return hl_fail(MGH_ERR_FORMAT, "pwrel footer: the masked buffer's restore value is not +0.0");
+  if (const char *bad = pwrel_footer_check_n(v.f, v.m.n)) return hl_fail(MGH_ERR_FORMAT, bad);
+  v.rec.resize((size_t)v.f.record);
+  if (v.f.record) {
+    if (in_dev) HL_TRY(aux_read(v.rec.data(), p + v.f.masked, (size_t)v.f.record));
+    else std::memcpy(v.rec.data(), p + v.f.masked, (size_t)v.f.record);
+  }
+  if (const char *bad = pwrel_record_check_crc(v.f, v.rec.data())) return hl_fail(MGH_ERR_FORMAT, bad);
+  return 1;
+}
+
+int pwrel_open_or_refuse(const char *who, const void *buf, size_t size, PwrelView &v) {
+  const int opened = pwrel_open(buf, size, v);
+  if (opened < 0) return opened;
+  if (opened == 0)
+    return hl_fail(MGH_ERR_FORMAT, std::string(who) + ": no pointwise-relative footer (a plain container has mgh_decompress, a "
+                                                      "masked buffer mgh_decompress_masked)");
+  return MGH_SUCCESS;
+}
+
+// footer -> mgh_decompress of the container part -> mask words and flag words -> k_pwrel_inverse
+int decompress_pwrel_impl(const void *buf, size_t size, const mgh_config &cfg, void **out, bool prealloc) {
+  PwrelView v;
+  HL_TRY(pwrel_open_or_refuse("decompress_pwrel", buf, size, v));
+  const uint64_t n = v.m.n;
+  const size_t bytes = (size_t)n * (v.m.hd.is_double ? 8 : 4);
+  const bool in_dev = is_device_pointer(buf);
+  const bool out_dev = prealloc ? is_device_pointer(*out) : in_dev;
+  HL_TRY(cache_prepare(cfg.dev_id));
+  HlCache &C = g_cache;
+  hipStream_t st = C.lane[0].st;
+  const OutSlot slot{out, in_dev, prealloc};
+  HL_TRY(slot.alloc(bytes));
+  // the inverse pass runs on the device: a host output is reconstructed in a device buffer first
+  void *d_data = *out;
+  int rc = MGH_SUCCESS;
+  if (!out_dev) {
+    if ((rc = C.mfill.ensure(bytes)) != MGH_SUCCESS) return slot.fail(rc);
+    d_data = C.mfill.p;
+  }
+  void *dst = d_data;
+  if ((rc = mgh_decompress(buf, (size_t)v.m.f.container, &dst, &cfg, 1)) != MGH_SUCCESS) return slot.fail(rc);
+  uint64_t *d_words = nullptr;
+  if ((rc = masked_words(v.m, st, &d_words)) != MGH_SUCCESS) return slot.fail(rc);
+  // (the two records share the symbol buffer and the lossless context of the lane: one after the other)
+  if (hipStreamSynchronize(st) != hipSuccess) return slot.fail(hl_fail(MGH_ERR_DEVICE, "decompress_pwrel: hipStreamSynchronize"));
+  if ((rc = C.msamp.ensure(mask_packed_bytes(n))) != MGH_SUCCESS) return slot.fail(rc);
+  if ((rc = bitmap_words(v.f.kind, v.rec, n, v.m.lossless, C.msamp.p, st)) != MGH_SUCCESS) return slot.fail(rc);
+  rc = mgh_pwrel_inverse_((int)v.m.hd.shape.size(), v.m.dtype, v.m.hd.shape.data(), d_words, (const uint64_t *)C.msamp.p, d_data, st);
+  if (rc != MGH_SUCCESS) return slot.fail(rc);
+  if (!out_dev && (rc = copy_any(*out, d_data, bytes, st)) != MGH_SUCCESS) return slot.fail(rc);
+  if (hipStreamSynchronize(st) != hipSuccess) return slot.fail(hl_fail(MGH_ERR_DEVICE, "decompress_pwrel: hipStreamSynchronize"));
+  return MGH_SUCCESS;
+}
+
+struct DeviceTemp {
+  void *p = nullptr;
+  ~DeviceTemp() {
+    if (p) (void)hipFree(p);
+  }
+};
+
+// decode the whole array into a device buffer, then one pass of k_compare_pwrel against the original
+int verify_pwrel_impl(const void *buf, size_t size, const void *original, size_t original_bytes, int original_dtype,
+                      const mgh_config &cfg, mgh_pwrel_compare *out, int *within) {
+  PwrelView v;
+  HL_TRY(pwrel_open_or_refuse("mgh_verify_pwrel", buf, size, v));
+  const uint64_t n = v.m.n;
+  const size_t bytes = (size_t)n * (v.m.hd.is_double ? 8 : 4);
+  if (original_dtype != v.m.dtype) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "mgh_verify_pwrel: the original's dtype is not the buffer's");
+  if (original_bytes != bytes) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "mgh_verify_pwrel: original_bytes is not the array's size");
+  HL_TRY(cache_prepare(cfg.dev_id));
+  DeviceTemp recon, staged;
+  HL_HIP(hipMalloc(&recon.p, bytes));
+  void *dst = recon.p;
+  HL_TRY(decompress_pwrel_impl(buf, size, cfg, &dst, true));
+  hipStream_t st = g_cache.lane[0].st;
+  const void *d_orig = original;
+  if (!is_device_pointer(original)) {
+    HL_HIP(hipMalloc(&staged.p, bytes));
+    HL_TRY(copy_any(staged.p, original, bytes, st));
+    d_orig = staged.p;
+  }
+  mgh_pwrel_compare r{};
+  HL_TRY(mgh_compare_pwrel_((int)v.m.hd.shape.size(), v.m.dtype, v.m.hd.shape.data(), d_orig, recon.p, v.f.abs_floor, &r, st));
+  *out = r;
+  if (within)
+    *within = r.max_rel_err <= v.f.eps && r.n_class_mismatch == 0 && r.n_sign_mismatch == 0 &&
+                      r.max_zeroed_abs < pwrel_floor_eff(v.m.hd.is_double, v.f.abs_floor)
+                  ? 1
+                  : 0;
+  return MGH_SUCCESS;
+}
+
+} // namespace
+
+extern "C" {
+
+int mgh_compress_pwrel(int D, int dtype, const uint64_t *shape, double eps, double abs_floor, const void *original_data,
+                       void **compressed_data, size_t *compressed_size, const void *const *coords, const mgh_config *config,
+                       int output_pre_allocated) {
+  if (!compressed_data || !compressed_size) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "NULL argument");
+  HL_TRY(size_call_args(D, dtype, shape, MGH_ABS, original_data, config, output_pre_allocated ? compressed_data : nullptr));
+  return hl_guarded([&]() -> int {
+    return compress_pwrel_impl(D, dtype, shape, eps, abs_floor, original_data, compressed_data, compressed_size, coords, *config,
+                               output_pre_allocated != 0);
+  });
+}
+
+int mgh_pwrel_info(const void *compressed_data, size_t compressed_size, struct mgh_pwrel_info *info) {
+  if (!compressed_data || !info) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "NULL argument");
+  return hl_guarded([&]() -> int {
+    PwrelView v;
+    const int opened = pwrel_open(compressed_data, compressed_size, v);
+    if (opened <= 0) return opened;
+    info->eps = v.f.eps;
+    info->abs_floor = v.f.abs_floor;
+    info->delta = v.m.hd.tol;
+    info->n_masked = v.m.f.n_masked;
+    info->n_flag = v.f.n_flag;
+    info->container_size = v.m.f.container;
+    info->masked_size = v.f.masked;
+    info->mask_record_size = v.m.f.record;
+    info->flag_record_size = v.f.record;
+    info->mask_kind = (int)v.m.f.kind;
+    info->flag_kind = (int)v.f.kind;
+    return 1;
+  });
+}
+
+int mgh_decompress_pwrel(const void *compressed_data, size_t compressed_size, const mgh_config *config,
+                         void **decompressed_data, int output_pre_allocated) {
+  if (!compressed_data || !decompressed_data) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (output_pre_allocated && !*decompressed_data) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "pre-allocated output is NULL");
+  mgh_config cfg;
+  HL_TRY(masked_config(config, cfg));
+  return hl_guarded([&] { return decompress_pwrel_impl(compressed_data, compressed_size, cfg, decompressed_data, output_pre_allocated != 0); });
+}
+
+int mgh_verify_pwrel(const void *compressed_data, size_t compressed_size, const void *original, size_t original_bytes,
+                     int original_dtype, const mgh_config *config, mgh_pwrel_compare *out, int *within) {
+  if (!compressed_data || !original || !out) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (original_dtype != MGH_FLOAT && original_dtype != MGH_DOUBLE)
+    return hl_fail(MGH_ERR_INVALID_ARGUMENT, "mgh_verify_pwrel: dtype");
+  mgh_config cfg;
+  HL_TRY(masked_config(config, cfg));
+  return hl_guarded([&] {
+    return verify_pwrel_impl(compressed_data, compressed_size, original, original_bytes, original_dtype, cfg, out, within);
+  });
 }
 
 } // extern "C"

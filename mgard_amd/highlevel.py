@@ -51,6 +51,7 @@ HL_SYMBOLS = [
     "mgh_decompress_masked_level", "mgh_decompress_masked_coarsened", "mgh_decompress_masked_preview",
     "mgh_decompress_masked_preview_window", "mgh_decompress_mask_level", "mgh_decompress_mask_coarsened",
     "mgh_decompress_mask_window", "mgh_verify_masked",
+    "mgh_compress_pwrel", "mgh_decompress_pwrel", "mgh_pwrel_info", "mgh_verify_pwrel",
     "mgh_lossless_compress_sym16", "mgh_lossless_compress_device_sym16", "mgh_lossless_decompress_sym16",
 ]
 
@@ -141,6 +142,18 @@ class MaskedInfo(C.Structure):
     def __repr__(self):
         return "MaskedInfo(container_size=%d, record_size=%d, n_masked=%d, kind=%d, restore_value=%r)" % (
             self.container_size, self.record_size, self.n_masked, self.kind, self.restore_value)
+
+
+class PwrelInfo(C.Structure):
+    """mgh_pwrel_info: the parts of a pointwise-relative buffer -- [masked buffer of y = log2|x|][flag record][56-byte
+    footer] -- with the footer's eps and abs_floor, and delta, the ABS tolerance of y in the container's header."""
+    _fields_ = [("eps", C.c_double), ("abs_floor", C.c_double), ("delta", C.c_double), ("n_masked", C.c_uint64),
+                ("n_flag", C.c_uint64), ("container_size", C.c_uint64), ("masked_size", C.c_uint64),
+                ("mask_record_size", C.c_uint64), ("flag_record_size", C.c_uint64), ("mask_kind", C.c_int),
+                ("flag_kind", C.c_int)]
+
+    def __repr__(self):
+        return "PwrelInfo(%s)" % ", ".join("%s=%r" % (k, getattr(self, k)) for k, _ in self._fields_)
 
 
 class HeaderInfo(C.Structure):
@@ -285,6 +298,13 @@ def _hl():
     L.mgh_decompress_mask_window.argtypes = [vp, C.c_size_t, C.POINTER(u64), C.POINTER(u64), C.POINTER(Config), vp]
     L.mgh_verify_masked.argtypes = [vp, C.c_size_t, vp, C.c_size_t, C.c_int, C.c_int, C.POINTER(Config),
                                     C.POINTER(VerifyResult), C.POINTER(u64)]
+    from . import PwrelCompare
+    L.mgh_compress_pwrel.argtypes = [C.c_int, C.c_int, C.POINTER(u64), C.c_double, C.c_double, vp, C.POINTER(vp),
+                                     C.POINTER(C.c_size_t), C.POINTER(vp), C.POINTER(Config), C.c_int]
+    L.mgh_decompress_pwrel.argtypes = [vp, C.c_size_t, C.POINTER(Config), C.POINTER(vp), C.c_int]
+    L.mgh_pwrel_info.argtypes = [vp, C.c_size_t, C.POINTER(PwrelInfo)]
+    L.mgh_verify_pwrel.argtypes = [vp, C.c_size_t, vp, C.c_size_t, C.c_int, C.POINTER(Config), C.POINTER(PwrelCompare),
+                                   C.POINTER(C.c_int)]
     _declared = True
     return L
 
@@ -805,6 +825,79 @@ def verify_masked(buf, original, config=None, coarsen=0):
     _check(L.mgh_verify_masked(p, n, optr, nbytes, dt, int(coarsen), C.byref(cfg), C.byref(out), C.byref(n_masked)))
     del keep, okeep
     return out, int(n_masked.value)
+
+
+# ---- pointwise relative error bound ---------------------------------------------------------------------------
+def compress_pwrel(data, eps, abs_floor=0.0, coords=None, config=None, out=None):
+    """mgh_compress_pwrel: |x' - x| <= eps |x| at every element whose |x| >= max(abs_floor, smallest normal); +-0,
+    denormals and smaller values decode to +0.0, NaN / +-Inf to NaN. Returns [masked buffer of y = log2|x|][flag
+    record][56-byte footer]: buf[:pwrel_info(buf).masked_size] opens in decompress_masked, and its container part in
+    every reader, as y. 0 < eps < 1; an eps the data type cannot carry at the field's dynamic range raises. Host array
+    in, numpy buffer out; cuda tensor in, cuda buffer out. `out`: optional pre-allocated uint8 buffer of the same kind
+    (its size is the capacity)."""
+    import torch
+    L = _hl()
+    cfg = config if config is not None else Config()
+    ptr, dt, shape, keep = _as_ptr(data)
+    _wait_for_current_stream(out)
+    D = len(shape)
+    shp = (C.c_uint64 * D)(*shape)
+    cptr, ckeep = _coords_ptr(coords, dt, D)
+    on_device = isinstance(data, torch.Tensor) and data.is_cuda
+    n = int(np.prod(shape))
+    cap = n * (4 if dt == FLOAT else 8) + 1000000 + 16 * ((n + 63) // 64) + 48 + 56
+    if out is not None:
+        cap = int(out.numel()) if on_device else int(out.size)
+    elif on_device:
+        out = torch.empty(cap, dtype=torch.uint8, device=data.device)
+    else:
+        out = np.empty(cap, dtype=np.uint8)
+    optr = C.c_void_p(out.data_ptr()) if on_device else C.c_void_p(out.ctypes.data)
+    size = C.c_size_t(cap)
+    _check(L.mgh_compress_pwrel(D, dt, shp, float(eps), float(abs_floor), ptr, C.byref(optr), C.byref(size), cptr,
+                                C.byref(cfg), 1))
+    del keep, ckeep
+    return out[:size.value]
+
+
+def pwrel_info(buf):
+    """mgh_pwrel_info: the PwrelInfo of a pointwise-relative buffer, None for a buffer without its footer (a plain
+    container, a masked buffer); MgardHipError for a footer that fails a check."""
+    p, n, _, keep = _container_ptr(buf)
+    info = PwrelInfo()
+    rc = _check(_hl().mgh_pwrel_info(p, n, C.byref(info)))
+    del keep
+    return info if rc == 1 else None
+
+
+def decompress_pwrel(buf, config=None, out=None):
+    """mgh_decompress_pwrel: the array of a pointwise-relative buffer. A numpy array (host buffer) or a cuda tensor;
+    `out` as for decompress_layers. Any other buffer is refused."""
+    L = _hl()
+    cfg = config if config is not None else Config()
+    p, n, _, keep = _container_ptr(buf)
+    info = pwrel_info(keep)
+    if info is None:
+        _check(L.mgh_decompress_pwrel(p, n, C.byref(cfg), C.byref(C.c_void_p()), 0))  # (raises: no footer)
+    out, optr = _layers_out(keep[:info.container_size], out)
+    _check(L.mgh_decompress_pwrel(p, n, C.byref(cfg), C.byref(optr), 1))
+    return out
+
+
+def verify_pwrel(buf, original, config=None):
+    """mgh_verify_pwrel: (PwrelCompare, within) of a pointwise-relative buffer against `original`, the user's own array.
+    within: max_rel_err <= eps, no class or sign mismatch, and nothing at or above the floor zeroed."""
+    from . import PwrelCompare
+    L = _hl()
+    cfg = config if config is not None else Config()
+    p, n, _, keep = _container_ptr(buf)
+    optr, dt, shape, okeep = _as_ptr(original)
+    nbytes = int(np.prod(shape)) * (4 if dt == FLOAT else 8)
+    out = PwrelCompare()
+    within = C.c_int(0)
+    _check(L.mgh_verify_pwrel(p, n, optr, nbytes, dt, C.byref(cfg), C.byref(out), C.byref(within)))
+    del keep, okeep
+    return out, int(within.value)
 
 
 class Layers:

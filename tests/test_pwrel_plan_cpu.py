@@ -1,0 +1,201 @@
+"""CPU test of mgard_amd/csrc/pwrel_plan.hpp: the trailer of a pointwise-relative buffer (serialise, parse, every
+refusal), the classes of an element, and the tolerance delta -- against the same formula in Python, its refusals, and
+the inequality 2^(delta + E1) (1 + E2) <= 1 + eps it exists for, evaluated with `decimal` at 80 digits.
+
+tests/cpp/pwrel_plan_dump.cpp is compiled with g++ against the header alone (no HIP) and once more with
+-fsanitize=address,undefined as a stand-alone binary. The expectations are tests/pwrel_model.py."""
+import itertools
+import os
+import subprocess
+from decimal import Decimal, getcontext
+
+import numpy as np
+import pytest
+
+from tests import mask_model as mm
+from tests import pwrel_model as pm
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "mgard_amd", "csrc")
+SRC = os.path.join(ROOT, "tests", "cpp", "pwrel_plan_dump.cpp")
+EPS = (0.5, 1e-1, 1e-3, 1e-6, 1e-10)
+YBOUND = (0.0, 1.0, 127.0, 1023.0)
+
+
+def _build(tmp_path_factory, name, extra=()):
+    exe = str(tmp_path_factory.mktemp(name) / "pwrel_plan_dump")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", *extra, "-I", CSRC, SRC, "-o", exe])
+    return exe
+
+
+@pytest.fixture(scope="module")
+def dump(tmp_path_factory):
+    return _build(tmp_path_factory, "pwrel_plan")
+
+
+def _run(exe, text):
+    return subprocess.run([exe], input=text, capture_output=True, text=True, check=True, timeout=300).stdout.splitlines()
+
+
+def _hex(b):
+    return bytes(b).hex() or "-"
+
+
+def test_header_compiles_alone_without_hip(tmp_path):
+    src = tmp_path / "only.cpp"
+    src.write_text('#include "pwrel_plan.hpp"\n')
+    subprocess.check_call(["g++", "-std=c++17", "-fsyntax-only", "-Wall", "-Werror", "-I", CSRC, str(src)])
+
+
+# ---- footer ------------------------------------------------------------------------------------------------------
+N = 1000
+MASKED = bytes(range(100, 256)) + b"y" * 45                 # 201 bytes standing in for a masked buffer
+PACKED = bytes(np.random.default_rng(7).integers(0, 256, 8 * ((N + 63) // 64), dtype=np.uint8))
+CODED = b"\x04\x05\x06" * 13                                # 39 bytes < 128
+E, F = 1e-3, 1e-20
+
+
+def _buffer(record, kind, n_flag=17, eps=E, floor=F, masked=MASKED):
+    return masked + record + pm.footer(len(masked), record, n_flag, eps, floor, kind)
+
+
+def _open(dump, buf, n=N):
+    return _run(dump, "open %d %s\n" % (n, _hex(buf)))[0]
+
+
+def test_footer_serialises_as_the_restatement_and_round_trips(dump):
+    cases = [(201, 17, 1e-3, 1e-20, mm.PACKED, PACKED), (201, 3, 0.5, 0.0, mm.CODED, CODED),
+             (2 ** 40 + 5, 0, 1e-10, 2.5, mm.NONE, b""), (49, 2 ** 32 - 1, 0.999, 1e300, mm.PACKED, b"\xff" * 8)]
+    out = _run(dump, "".join("ser %d %d %s %s %d %s\n" % (m, nf, float(e).hex(), float(f).hex(), kind, _hex(rec))
+                             for m, nf, e, f, kind, rec in cases))
+    for line, (m, nf, e, f, kind, rec) in zip(out, cases):
+        want = pm.footer(m, rec, nf, e, f, kind)
+        assert len(want) == pm.FOOTER_BYTES and bytes.fromhex(line) == want
+        got = pm.parse_footer(want)
+        assert got == dict(masked=m, record=len(rec), n_flag=nf, eps=e, abs_floor=f, kind=kind, crc=got["crc"])
+    for rec, kind, nf in ((PACKED, mm.PACKED, 17), (CODED, mm.CODED, 17), (b"", mm.NONE, 0)):
+        f = _open(dump, _buffer(rec, kind, nf)).split()
+        assert f[0] == "ok" and [int(v) for v in f[1:4] + f[6:]] == [len(MASKED), len(rec), nf, kind]
+        assert [float.fromhex(v) for v in f[4:6]] == [E, F]
+
+
+def test_every_refusal(dump):
+    good = _buffer(PACKED, mm.PACKED)
+    assert _open(dump, good).startswith("ok ")
+    # truncated by one byte: the magic is no longer where a footer ends -- not such a buffer
+    assert _open(dump, good[:-1]) == "none"
+    assert _open(dump, good[1:]).startswith("bad ")       # ... and one byte short in front: M + S + 56 != size
+    assert _open(dump, b"") == "none" and _open(dump, good[-55:]) == "none"
+    # another magic: a masked buffer, a plain container
+    assert _open(dump, MASKED + mm.footer(len(MASKED), b"", 0, 0, mm.NONE)) == "none"
+    assert _open(dump, good[:-1] + b"2") == "none" and _open(dump, MASKED) == "none"
+    # sizes that do not add up
+    assert "not the buffer" in _open(dump, good[:50] + b"\x00" + good[50:])
+    assert "not the buffer" in _open(dump, MASKED + PACKED + pm.footer(len(MASKED) + 1, PACKED, 17, E, F, mm.PACKED))
+    assert _open(dump, MASKED + PACKED + pm.footer(2 ** 64 - 40, PACKED, 17, E, F, mm.PACKED)).startswith("bad ")
+    assert "no masked buffer" in _open(dump, _buffer(PACKED, mm.PACKED, masked=MASKED[:48]))
+    # kind against the record's size and n_flag, and against the n of the container's header
+    assert "kind 2" in _open(dump, _buffer(PACKED, mm.NONE, 0))
+    assert "kind 2" in _open(dump, _buffer(b"", mm.NONE, 5))
+    assert _open(dump, _buffer(b"", mm.PACKED)).startswith("bad ")
+    assert _open(dump, _buffer(PACKED, mm.PACKED, 0)).startswith("bad ")
+    assert "kind 0" in _open(dump, _buffer(PACKED[:-8], mm.PACKED))
+    assert "kind 0" in _open(dump, _buffer(PACKED, mm.PACKED), n=N + 64)
+    assert "kind 1" in _open(dump, _buffer(PACKED, mm.CODED))
+    assert "unknown kind" in _open(dump, _buffer(PACKED, 3))
+    assert "more flag bits" in _open(dump, _buffer(PACKED, mm.PACKED, N + 1))
+    assert _open(dump, _buffer(PACKED, mm.PACKED, N)).startswith("ok ")
+    # eps and the floor
+    for eps in (0.0, 1.0, -1.0, float("nan"), float("inf")):
+        assert "eps" in _open(dump, _buffer(PACKED, mm.PACKED, eps=eps))
+    for floor in (-1.0, float("nan"), float("inf")):
+        assert "abs_floor" in _open(dump, _buffer(PACKED, mm.PACKED, floor=floor))
+    # a flipped record byte fails the crc, wherever it is
+    for at in (0, len(PACKED) // 2, len(PACKED) - 1):
+        bad = bytearray(good)
+        bad[len(MASKED) + at] ^= 0x10
+        assert "CRC32" in _open(dump, bad)
+    bad = bytearray(good)
+    bad[3] ^= 0xff                                          # (the masked buffer is not this footer's business)
+    assert _open(dump, bad).startswith("ok ")
+
+
+# ---- classes -----------------------------------------------------------------------------------------------------
+def test_classes(dump):
+    rows = []
+    for dtype, floor in itertools.product((np.float32, np.float64), (0.0, 1e-20, 3.0)):
+        fl = float(dtype(floor))
+        xs = np.concatenate([pm.specials(dtype, fl), np.array([1.0, -2.5, 3.0, -3.0, 2.9999, 1e-30], dtype=dtype)])
+        want = pm.classify(xs, fl)
+        rows += [(int(dtype == np.float64), fl, float(x), int(w)) for x, w in zip(xs, want)]
+    out = _run(dump, "".join("cls %d %s %s\n" % (d, f.hex(), x.hex()) for d, f, x, _ in rows))
+    assert [int(o) for o in out] == [w for _, _, _, w in rows]
+    # a denormal, +-0 and a value below the floor are zeroed; the floor itself and the smallest normal are valid
+    f32 = np.finfo(np.float32)
+    assert list(pm.classify(np.array([0.0, -0.0, f32.smallest_subnormal, f32.tiny, -f32.max, np.nan, -np.inf], dtype=np.float32))) == \
+        [pm.ZEROED, pm.ZEROED, pm.ZEROED, pm.VALID, pm.VALID, pm.NONFINITE, pm.NONFINITE]
+
+
+# ---- tolerance ---------------------------------------------------------------------------------------------------
+def _tol(dump, rows):
+    out = _run(dump, "".join("tol %d %s %s\n" % (d, float(e).hex(), float(y).hex()) for d, e, y in rows))
+    return [float.fromhex(o.split()[1]) if o.startswith("ok ") else None for o in out], out
+
+
+CASES = [(d, e, y) for d in (0, 1) for e in EPS for y in YBOUND]
+
+
+def test_tolerance_is_the_formula(dump):
+    got, _ = _tol(dump, CASES + [(0, 1e-3, -1.0), (1, 1e-10, -1.0)])
+    want = [pm.abs_tolerance(np.float64 if d else np.float32, e, y) for d, e, y in CASES]
+    want += [pm.log2_1p(1e-3), pm.log2_1p(1e-10)]               # nothing valid: delta = log2(1 + eps)
+    assert got == want
+    accepted = [c for c, g in zip(CASES, got) if g is not None]
+    # every float64 case is accepted, and float32 wherever the rounding of y leaves half of log2(1 + eps)
+    assert all(c in accepted for c in CASES if c[0] == 1)
+    assert (0, 1e-3, 127.0) in accepted and (0, 1e-1, 1023.0) in accepted and (0, 1e-6, 1.0) in accepted
+    assert (0, 1e-6, 127.0) not in accepted and (0, 1e-10, 0.0) not in accepted
+
+
+def test_tolerance_keeps_the_bound(dump):
+    """2^(delta + E1) (1 + E2) <= 1 + eps, the side that binds, and 2^-(delta + E1) (1 - E2) >= 1 - eps."""
+    getcontext().prec = 80
+    got, _ = _tol(dump, CASES)
+    checked = 0
+    for (d, eps, yb), delta in zip(CASES, got):
+        if delta is None:
+            continue
+        dtype = np.float64 if d else np.float32
+        assert 0.5 * pm.log2_1p(eps) <= delta < pm.log2_1p(eps)
+        e1, e2 = Decimal(pm.ulp(dtype, yb)), Decimal(pm.e2(dtype))
+        up = Decimal(2) ** (Decimal(delta) + e1) * (1 + e2)
+        down = Decimal(2) ** -(Decimal(delta) + e1) * (1 - e2)
+        assert up <= 1 + Decimal(eps), (d, eps, yb)
+        assert down >= 1 - Decimal(eps), (d, eps, yb)
+        checked += 1
+    assert checked >= 30
+
+
+def test_tolerance_refusals(dump):
+    rows = [(d, e, 1.0) for d in (0, 1) for e in (0.0, 1.0, -1.0, float("nan"), float("inf"))]
+    got, out = _tol(dump, rows)
+    assert got == [None] * len(rows) and all("0 < eps < 1" in o for o in out)
+    # float32 cannot carry 1e-7 at any range (1.5 E2 alone is more), nor 1e-5 at |y| up to 127
+    got, out = _tol(dump, [(0, 1e-7, 0.0), (0, 1e-7, 127.0), (0, 1e-5, 127.0), (0, 1e-5, 1.0), (1, 1e-7, 1023.0)])
+    assert got[:3] == [None] * 3 and all("cannot carry" in o for o in out[:3])
+    assert got[3] is not None and got[4] is not None
+
+
+def test_program_is_clean_under_address_and_undefined_sanitizers(tmp_path_factory):
+    exe = _build(tmp_path_factory, "pwrel_plan_san", ("-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"))
+    good = _buffer(PACKED, mm.PACKED)
+    text = ""
+    for buf in (good, good[:-1], good[1:], b"", good[-56:], good[-55:], _buffer(b"", mm.NONE, 0), _buffer(CODED, mm.CODED),
+                MASKED + PACKED + pm.footer(2 ** 64 - 40, PACKED, 17, E, F, mm.PACKED)):
+        text += "open %d %s\n" % (N, _hex(buf))
+    text += "ser 201 17 %s %s 0 %s\nser 50 0 %s %s 2 -\n" % (E.hex(), F.hex(), _hex(PACKED), E.hex(), F.hex())
+    text += "".join("tol %d %s %s\n" % (d, float(e).hex(), float(y).hex()) for d, e, y in CASES)
+    text += "tol 0 nan 0x1p0\ntol 1 0x1p-10 -0x1p0\ncls 0 0x0p0 nan\ncls 1 0x1p-70 -0x1p-80\n"
+    p = subprocess.run([exe], input=text, capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0 and "runtime error" not in p.stderr and "Sanitizer" not in p.stderr, p.stderr[-4000:]
+    assert len(p.stdout.splitlines()) == text.count("\n")
