@@ -785,8 +785,10 @@ int mgh_verify_masked(const void *compressed_data, size_t compressed_size, const
  * bytes are not the masked footer's magic: mgh_masked_info of the whole buffer returns 0.
  * floor_eff = max(abs_floor, smallest normal of T): +-0, denormals and values below it decode to +0.0; NaN and
  * +-Inf decode to a quiet NaN; every other element keeps its sign and meets the bound.
- * eps must be finite with 0 < eps < 1 and abs_floor finite and >= 0 (MGH_ERR_INVALID_ARGUMENT). Where the roundings
- * of the transform would take more than half of log2(1 + eps) -- float with |y| up to 128: eps below about 1e-5 --
+ * eps must be finite with 0 < eps < 1 and abs_floor finite and >= 0 (MGH_ERR_INVALID_ARGUMENT). Where delta
+ * is below 64 ulp_T(max |y|) (the container's own rounding of y, measured: pwrel_plan.hpp) or the roundings of the
+ * transform would take more than half of log2(1 + eps) -- float with 64 <= |y| < 128: eps below about 3.5e-4, and
+ * 6.9e-4 where the largest finite value puts |y| at 128; double with 512 <= |y| < 1024: below about 5.2e-12 --
  * the call is MGH_ERR_INVALID_ARGUMENT with a message that says so: a looser bound is never delivered silently.
  * coords and config (its domain decomposition included) pass through unchanged. Memory spaces, footprint
  * (a host array is uploaded once and transformed in place; a device array is not modified and y is written beside

@@ -23,13 +23,38 @@
 //      (same table: exp2, maximum error 1 ulp), i.e. within 2^-52 relative, and rounding to float adds 2^-24.
 // So x' / x <= 2^{delta + E1} (1 + E2) <= 2^{delta + E1 + 1.5 E2} = 1 + eps, because log2(1 + E2) <= E2 / ln 2
 // < 1.5 E2: the upper side, which binds. The lower side, x' / x >= 2^{-(delta + E1)} (1 - E2) >= 1 / (1 + eps)
-// >= 1 - eps, follows for eps < 1 (1 - E2 >= 2^{-1.5 E2}). These are derived margins, not measured ones.
+// >= 1 - eps, follows for eps < 1 (1 - E2 >= 2^{-1.5 E2}). E1 and E2 are derived margins, not measured ones; the
+// smallest delta the container is trusted with (below) is MEASURED.
 // The inverse clamps |x'| to [smallest normal, largest finite] of T: a valid |x| lies in that range, so the clamp
 // moves x' towards x and keeps the bound.
 // delta is evaluated in double and rounded DOWN: log2(1 + eps) is log1p(eps) / ln 2 shrunk by 2^-50 relative (more
 // than the two roundings and the 1 ulp of log1p can add), and the result of the two subtractions is stepped down
-// two doubles. Where delta < 0.5 log2(1 + eps), the data type cannot carry eps at this field's dynamic range (float
-// with |y| up to 128: eps below about 1e-5) and the call is refused: a looser bound is never delivered silently.
+// two doubles.
+//
+// THE ROUNDING OF THE CONTAINER. |y' - y| <= delta is the container's guarantee in exact arithmetic. It decomposes,
+// quantizes, dequantizes and recomposes y in T, and that rounding is not in the derivation above: the round trip
+// without a quantizer already moves y by 1 to 3 ulp_T(ybound), and at a delta of a few ulps the error EXCEEDS delta.
+// There is no derivation of how much, so it was measured, on the CPU oracle (oracle.Hierarchy, which
+// tests/test_gpu_parity.py pins the GPU transform to bit for bit; tests/pwrel_model.py: oracle_y_errors), on
+// 2026-10-21: delta = m ulp_T(ybound) for every m in 1..64 and 72, 80, 96, 112, 128, 160, 192, 224, 256; float and
+// double; an all-valid smooth field and an all-valid field of magnitudes 10^U(-30, 30) / 10^U(-300, 300); shapes
+// 1000, 100001, 17x130, 513x513, 34x33x32, 65^3, 129^3, 5x6x7x9, 17^4, 5^5. excess = (max |y' - y| - delta) / ulp:
+//   m* = 24    the smallest m from which no case has an excess > 0 at any larger probed m. The last breach is
+//              double, 10^U, 5x6x7x9 at m = 23 (+6.25); the other cases stop between m = 1 (smooth 1-D, 2-D) and
+//              m = 19 (5^5). The largest excess anywhere is +19 ulp (double, 10^U, 5x6x7x9, m = 1 and 3); float: +18.
+//   e* = -2.0  the largest excess at any probed m >= m* (m = 27): not positive, so delta takes NO allowance for the
+//              container's rounding (K_alloc = 0: delta stays log2(1 + eps) - E1 - 1.5 E2). At m = 64 it is -43.
+//   K_min = 64 = 2 m* rounded up to a power of two; the factor 2 because the table is a sample, not a proof.
+// tests/test_pwrel_rounding_cpu.py has the per-case table and repeats the measurement at the threshold. On the GPU
+// (tests/test_gpu_pwrel.py) a container that quantizes gives the oracle's max |y' - y| to the bit, the breach at 1 and
+// 2 ulps included; a container that would be larger than the array is stored as it is (y' = y), which at a delta of
+// 64 ulps is every double field and every float field not smooth to about 12 bits -- the rough and tiny cases that
+// set m* among them. The rule does not count on that: it bounds what the container may be asked for.
+// REFUSALS. Where delta < kPwrelMinUlps ulp_T(ybound), or delta < 0.5 log2(1 + eps), the data type cannot carry
+// eps at this field's dynamic range and the call is refused: a looser bound is never delivered silently. The first
+// rule is the stricter one unless E1 < E2 / 42 (|y| below 1/32). Float: eps below about 3.5e-4 with 64 <= |y| < 128
+// (6.9e-4 where the largest finite value puts |y| at 128; 5.5e-6 with 1 <= |y| < 2). Double: below about 5.2e-12
+// with 512 <= |y| < 1024.
 //
 // A buffer:   [masked buffer of y, M bytes][flag record, S bytes][56-byte footer]
 // The first M bytes are what mgh_compress_masked writes for y with the mask nonfinite | zeroed, restore_value 0 (its
@@ -79,6 +104,9 @@ inline double pwrel_ulp(bool is_double, double v) {
 
 inline double pwrel_e2(bool is_double) { return is_double ? 0x1p-52 : 0x1p-23; }
 
+// K_min: the smallest delta handed to the container, in ulp_T(ybound) (measured: the header's comment)
+constexpr double kPwrelMinUlps = 64.0;
+
 // log2(1 + eps), not above the exact value
 inline double pwrel_log2_1p(double eps) { return std::log1p(eps) / 0.6931471805599453 * (1.0 - 0x1p-50); }
 
@@ -92,9 +120,10 @@ inline const char *pwrel_abs_tolerance(bool is_double, double eps, double ybound
     *delta = L;
     return nullptr;
   }
-  double d = L - pwrel_ulp(is_double, ybound) - 1.5 * pwrel_e2(is_double);
+  const double u = pwrel_ulp(is_double, ybound);
+  double d = L - u - 1.5 * pwrel_e2(is_double);
   d = std::nextafter(std::nextafter(d, -std::numeric_limits<double>::infinity()), -std::numeric_limits<double>::infinity());
-  if (d < 0.5 * L)
+  if (d < kPwrelMinUlps * u || d < 0.5 * L)
     return "pwrel: the data type cannot carry this eps at the field's dynamic range (the rounding of log2|x| and of "
            "exp2 would take more than half of log2(1 + eps)): use a larger eps, or float64 data";
   *delta = d;

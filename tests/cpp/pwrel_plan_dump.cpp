@@ -2,7 +2,8 @@
 // line of answer each. Built with g++ against the header alone.
 //   ser M n_flag EPS FLOOR kind HEXRECORD   (hex floats)  -> the 56 footer bytes in hex ("-" is the empty record)
 //   open n HEXBUFFER                        -> none | bad MESSAGE | ok M S n_flag EPS FLOOR kind
-//   tol is_double EPS YBOUND  (hex floats)  -> ok DELTA (hex float) | bad MESSAGE
+//   tol is_double EPS YBOUND  (hex floats)  -> ok DELTA (hex float) | bad MESSAGE   (refused: eps outside (0, 1), or
+//                                              DELTA below kPwrelMinUlps ulps of YBOUND or half of log2(1 + EPS))
 //   cls is_double FLOOR X     (hex floats)  -> 0 valid | 1 zeroed | 2 nonfinite
 #include <cinttypes>
 #include <cstdio>

@@ -85,17 +85,62 @@ def log2_1p(eps):
     return math.log1p(eps) / 0.6931471805599453 * (1.0 - 2.0 ** -50)
 
 
-def abs_tolerance(dtype, eps, yb):
-    """delta = log2(1 + eps) - ulp_T(ybound) - 1.5 E2 rounded down, or None where the call is refused. yb < 0: nothing
-    is valid and delta = log2(1 + eps)."""
+K_MIN = 64.0     # the smallest delta the container is handed, in ulp_T(ybound)
+
+
+def budget(dtype, eps, yb):
+    """B = log2(1 + eps) - ulp_T(ybound) - 1.5 E2 rounded down: what |y' - y| may use."""
+    d = log2_1p(eps) - ulp(dtype, yb) - 1.5 * e2(dtype)
+    return math.nextafter(math.nextafter(d, -math.inf), -math.inf)
+
+
+def abs_tolerance(dtype, eps, yb, k_min=K_MIN):
+    """delta = B, or None where the call is refused: delta < k_min ulp_T(ybound) (the container's own rounding, measured
+    in tests/test_pwrel_rounding_cpu.py) or delta < 0.5 log2(1 + eps). yb < 0: nothing is valid and delta =
+    log2(1 + eps). k_min=0 is the rule before the container's rounding was measured."""
     if not (math.isfinite(eps) and 0.0 < eps < 1.0):
         return None
     L = log2_1p(eps)
     if yb < 0:
         return L
-    d = L - ulp(dtype, yb) - 1.5 * e2(dtype)
-    d = math.nextafter(math.nextafter(d, -math.inf), -math.inf)
-    return None if d < 0.5 * L else d
+    d = budget(dtype, eps, yb)
+    return None if d < k_min * ulp(dtype, yb) or d < 0.5 * L else d
+
+
+def smallest_accepted_eps(dtype, yb, rel=0.01):
+    """An eps abs_tolerance accepts at this ybound, no more than `rel` above the smallest one it accepts (bisection;
+    acceptance is monotone in eps)."""
+    lo, hi = 2.0 ** -60, 0.5
+    assert abs_tolerance(dtype, lo, yb) is None and abs_tolerance(dtype, hi, yb) is not None
+    while hi > lo * (1.0 + rel):
+        mid = math.sqrt(lo * hi)
+        lo, hi = (lo, mid) if abs_tolerance(dtype, mid, yb) is not None else (mid, hi)
+    return hi
+
+
+# ---- the writer's path for y, through the CPU oracle ------------------------------------------------------------
+def oracle_y_errors(x, deltas, abs_floor=0.0):
+    """The container's part of the writer, restated with oracle.Hierarchy (which tests/test_gpu_parity.py pins the GPU
+    transform to, bit for bit): y = the filled T(log2|x|) -> decompose -> for every delta in `deltas`: quantize (ABS,
+    s = inf, norm 1, dictionary 8192) -> dequantize -> recompose. Everything runs in T; the differences are taken in
+    float64, where they are exact. Returns (ybound, [max |y' - y| over the VALID elements, one per delta]); a delta
+    of None leaves the quantizer out (decompose -> recompose alone)."""
+    import oracle
+    dt = x.dtype.type
+    mask, _ = bitmaps(x, abs_floor)
+    y = filled(x, abs_floor)
+    h = oracle.Hierarchy(x.shape, x.dtype)
+    c = h.decompose(y)
+    yd = y.astype(np.float64)
+    errs = []
+    for delta in deltas:
+        back = c
+        if delta is not None:
+            args = (oracle.ABS, dt(delta), dt(np.inf), dt(1))
+            q, oi, ov, _ = h.quantize(c, *args, dict_size=8192)
+            back = h.dequantize(q, *args, dict_size=8192, outlier_idx=oi, outlier_val=ov)
+        errs.append(float(np.max(np.abs(h.recompose(back).astype(np.float64) - yd)[~mask])))
+    return ybound(x, abs_floor), errs
 
 
 # ---- trailer -------------------------------------------------------------------------------------------------
@@ -157,12 +202,13 @@ def plant(x, abs_floor):
     return x
 
 
-def decades_field(shape, dtype, seed=0, abs_floor=0.0):
-    """Magnitudes 10^U(-30, 30) (float32) or 10^U(-300, 300) (float64) with random signs, the special values planted."""
+def decades_field(shape, dtype, seed=0, abs_floor=0.0, planted=True):
+    """Magnitudes 10^U(-30, 30) (float32) or 10^U(-300, 300) (float64) with random signs, the special values planted
+    (planted=False: every element is valid)."""
     rng = np.random.default_rng(seed)
     span = 30 if np.dtype(dtype) == np.float32 else 300
     x = (10.0 ** rng.uniform(-span, span, size=shape) * rng.choice([-1.0, 1.0], size=shape)).astype(dtype)
-    return plant(x, abs_floor)
+    return plant(x, abs_floor) if planted else x
 
 
 def smooth_field(shape, dtype, abs_floor=0.0, negative=True, planted=True):

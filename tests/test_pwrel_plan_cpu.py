@@ -1,10 +1,12 @@
 """CPU test of mgard_amd/csrc/pwrel_plan.hpp: the trailer of a pointwise-relative buffer (serialise, parse, every
-refusal), the classes of an element, and the tolerance delta -- against the same formula in Python, its refusals, and
+refusal), the classes of an element, and the tolerance delta -- against the same formula in Python, its refusals (the
+64 ulps the container's own rounding needs among them: tests/test_pwrel_rounding_cpu.py measures those), and
 the inequality 2^(delta + E1) (1 + E2) <= 1 + eps it exists for, evaluated with `decimal` at 80 digits.
 
 tests/cpp/pwrel_plan_dump.cpp is compiled with g++ against the header alone (no HIP) and once more with
 -fsanitize=address,undefined as a stand-alone binary. The expectations are tests/pwrel_model.py."""
 import itertools
+import math
 import os
 import subprocess
 from decimal import Decimal, getcontext
@@ -151,10 +153,20 @@ def test_tolerance_is_the_formula(dump):
     want += [pm.log2_1p(1e-3), pm.log2_1p(1e-10)]               # nothing valid: delta = log2(1 + eps)
     assert got == want
     accepted = [c for c, g in zip(CASES, got) if g is not None]
-    # every float64 case is accepted, and float32 wherever the rounding of y leaves half of log2(1 + eps)
+    # every float64 case is accepted, and float32 wherever delta is at least 64 ulps of the largest |y| (the container's
+    # own rounding, tests/test_pwrel_rounding_cpu.py) and half of log2(1 + eps)
     assert all(c in accepted for c in CASES if c[0] == 1)
-    assert (0, 1e-3, 127.0) in accepted and (0, 1e-1, 1023.0) in accepted and (0, 1e-6, 1.0) in accepted
+    assert (0, 1e-3, 127.0) in accepted and (0, 1e-1, 1023.0) in accepted and (0, 1e-6, 0.0) in accepted
     assert (0, 1e-6, 127.0) not in accepted and (0, 1e-10, 0.0) not in accepted
+    # 64 ulps: log2(1 + 1e-6) = 1.44e-6 is 12 ulps of 1.0 and log2(1 + 1e-3) = 1.44e-3 is 24 ulps of 1023
+    assert (0, 1e-6, 1.0) not in accepted and (0, 1e-3, 1023.0) not in accepted
+    # ... exactly 64: delta = log2(1 + eps) - E1 - 1.5 E2 against 64 ulp_T(ybound) on both sides of the limit
+    for d, yb in ((0, 1.0), (0, 127.0), (1, 1.0), (1, 1023.0)):
+        dtype = np.float64 if d else np.float32
+        u, e2 = pm.ulp(dtype, yb), pm.e2(dtype)
+        lo, hi = (math.expm1(((64 + 1 + k) * u + 1.5 * e2) * math.log(2.0)) for k in (-0.01, 0.01))
+        got, out = _tol(dump, [(d, lo, yb), (d, hi, yb)])
+        assert got[0] is None and "cannot carry" in out[0] and got[1] == pm.abs_tolerance(dtype, hi, yb) >= 64 * u
 
 
 def test_tolerance_keeps_the_bound(dump):
@@ -166,7 +178,7 @@ def test_tolerance_keeps_the_bound(dump):
         if delta is None:
             continue
         dtype = np.float64 if d else np.float32
-        assert 0.5 * pm.log2_1p(eps) <= delta < pm.log2_1p(eps)
+        assert 0.5 * pm.log2_1p(eps) <= delta < pm.log2_1p(eps) and delta >= 64 * pm.ulp(dtype, yb)
         e1, e2 = Decimal(pm.ulp(dtype, yb)), Decimal(pm.e2(dtype))
         up = Decimal(2) ** (Decimal(delta) + e1) * (1 + e2)
         down = Decimal(2) ** -(Decimal(delta) + e1) * (1 - e2)
@@ -182,6 +194,11 @@ def test_tolerance_refusals(dump):
     assert got == [None] * len(rows) and all("0 < eps < 1" in o for o in out)
     # float32 cannot carry 1e-7 at any range (1.5 E2 alone is more), nor 1e-5 at |y| up to 127
     got, out = _tol(dump, [(0, 1e-7, 0.0), (0, 1e-7, 127.0), (0, 1e-5, 127.0), (0, 1e-5, 1.0), (1, 1e-7, 1023.0)])
+    assert got[:3] == [None] * 3 and all("cannot carry" in o for o in out[:3])
+    assert got[3] is not None and got[4] is not None
+    # the figures of the documents: float32 at 64 <= |y| < 128 carries 4e-4 and not 3e-4 (the parent's rule carried
+    # 1.3e-5 there, where the container's rounding breaks the bound); float64 at 512 <= |y| < 1024, 1e-11 and not 1e-12
+    got, out = _tol(dump, [(0, 3e-4, 127.0), (0, 1.3e-5, 127.0), (1, 1e-12, 1023.0), (0, 4e-4, 127.0), (1, 1e-11, 1023.0)])
     assert got[:3] == [None] * 3 and all("cannot carry" in o for o in out[:3])
     assert got[3] is not None and got[4] is not None
 
