@@ -5318,26 +5318,68 @@ int bitmap_record(const char *who, const uint64_t *d_words, uint64_t n, uint64_t
   return MGH_SUCCESS;
 }
 
-// `tail` (host) behind the first `at` bytes of the output
-int write_behind(const char *who, void *out, size_t at, const std::vector<uint8_t> &tail, hipStream_t st) {
+// The record and the footer of a packed bitmap (the mask; the flag bits of the pointwise-relative writer) behind the
+// first `at` bytes of an output of `cap` bytes: bitmap_record -> the capacity -> the footer behind the record -> the
+// two into the output. footer(kind, the record's bytes, its CRC32, dst) serialises `footer_bytes` bytes; too_small
+// is the refusal's text behind `who`. *end: the bytes of the output in use.
+template <typename Footer>
+int write_trailer(const char *who, const char *too_small, void *out, size_t at, size_t cap, const uint64_t *d_words, uint64_t n,
+                  uint64_t n_set, const mgh_config &cfg, hipStream_t st, size_t footer_bytes, Footer footer, size_t *end) {
+  uint32_t kind = kMaskNone;
+  std::vector<uint8_t> rec;
+  HL_TRY(bitmap_record(who, d_words, n, n_set, cfg, st, kind, rec));
+  const size_t record = rec.size();
+  if (at + record + footer_bytes > cap) return hl_fail(MGH_ERR_OUTPUT_TOO_LARGE, std::string(who) + too_small);
+  rec.resize(record + footer_bytes);
+  footer(kind, record, fmt::crc32(rec.data(), record), rec.data() + record);
   if (is_device_pointer(out)) {
-    if (hipMemcpyAsync((char *)out + at, tail.data(), tail.size(), hipMemcpyHostToDevice, st) != hipSuccess ||
+    if (hipMemcpyAsync((char *)out + at, rec.data(), rec.size(), hipMemcpyHostToDevice, st) != hipSuccess ||
         hipStreamSynchronize(st) != hipSuccess)
       return hl_fail(MGH_ERR_DEVICE, std::string(who) + ": writing mask record and footer");
   } else {
-    std::memcpy((char *)out + at, tail.data(), tail.size());
+    std::memcpy((char *)out + at, rec.data(), rec.size());
   }
+  *end = at + rec.size();
   return MGH_SUCCESS;
 }
 
 // What the classifying pass of a writer left on the device: the array (`src`, device memory), its packed mask and
-// the statistics of the valid elements.
+// the statistics of the valid elements. in_dev: the caller's array is device memory.
 struct MaskedScan {
   const void *src = nullptr;
+  bool in_dev = false;
   uint64_t n = 0, n_masked = 0;
   double vmin = 0, vmax = 0;
   uint64_t *d_words = nullptr;
 };
+
+// The head of a writer, in front of its classifying pass: element count -> the caller's own argument check
+// (bad_arg: its refusal, or nullptr) -> footprint (the array on the device and a copy beside a device-resident one;
+// too_large: the refusal's text) -> the cache -> the mask words with the pass's statistics behind them -> a host
+// array uploaded into C.mfill. S.src is the array on the device; S.n_masked, S.vmin and S.vmax are the caller's to
+// fill from *d_stats once its pass has run.
+template <typename Stats>
+int scan_head(const char *who, const char *bad_arg, const char *too_large, int D, int dtype, const uint64_t *shape,
+              const void *original, const mgh_config &cfg, MaskedScan &S, Stats **d_stats) {
+  HL_TRY(masked_shape_elems(who, D, shape, &S.n));
+  if (bad_arg) return hl_fail(MGH_ERR_INVALID_ARGUMENT, bad_arg);
+  const size_t bytes = (size_t)S.n * (dtype == MGH_DOUBLE ? 8 : 4);
+  S.in_dev = is_device_pointer(original);
+  if ((S.in_dev ? 2 : 1) * (uint64_t)bytes > cfg.max_memory_footprint) return hl_fail(MGH_ERR_INVALID_ARGUMENT, too_large);
+  HL_TRY(cache_prepare(cfg.dev_id));
+  HlCache &C = g_cache;
+  const uint64_t nb = mask_packed_bytes(S.n);
+  HL_TRY(C.mwords.ensure(nb + sizeof(Stats)));
+  S.d_words = (uint64_t *)C.mwords.p;
+  *d_stats = (Stats *)((char *)C.mwords.p + nb);
+  S.src = original;
+  if (!S.in_dev) {
+    HL_TRY(C.mfill.ensure(bytes));
+    HL_TRY(copy_any(C.mfill.p, original, bytes, C.lane[0].st));
+    S.src = C.mfill.p;
+  }
+  return MGH_SUCCESS;
+}
 
 // The masked writer behind its scan, shared by mgh_compress_masked and mgh_compress_pwrel: fill -> the output ->
 // mgh_compress of the filled array -> mask record -> footer. *csize: the bytes written (on entry the capacity of a
@@ -5346,7 +5388,7 @@ struct MaskedScan {
 // allocated one. A failure has gone through slot.fail.
 int masked_write(const char *who, int D, int dtype, const uint64_t *shape, double tol, double s, int ebtype, const MaskedScan &S,
                  double restore_value, const OutSlot &slot, size_t *csize, const void *const *coords, const mgh_config &cfg,
-                 size_t behind_min, size_t behind_max, size_t *cap_out) {
+                 size_t behind_min, size_t behind_max) {
   const bool is_double = dtype == MGH_DOUBLE;
   const size_t elem = is_double ? 8 : 4;
   const uint64_t n = S.n, nb = mask_packed_bytes(n);
@@ -5381,52 +5423,33 @@ int masked_write(const char *who, int D, int dtype, const uint64_t *shape, doubl
   f.container = container;
   f.n_masked = S.n_masked;
   f.restore_bits = mask_value_bits(is_double, restore_value);
-  std::vector<uint8_t> rec;
-  if ((rc = bitmap_record(who, S.d_words, n, S.n_masked, cfg, st, f.kind, rec)) != MGH_SUCCESS) return slot.fail(rc);
-  f.record = rec.size();
-  f.crc = fmt::crc32(rec.data(), rec.size());
-  if (container + rec.size() + kMaskFooterBytes + behind_min > cap)
-    return slot.fail(hl_fail(MGH_ERR_OUTPUT_TOO_LARGE, w + ": the output cannot hold container, mask record and footer"));
-  rec.resize(rec.size() + kMaskFooterBytes);
-  mask_footer_serialize(f, rec.data() + f.record);
-  if ((rc = write_behind(who, out, container, rec, st)) != MGH_SUCCESS) return slot.fail(rc);
-  *csize = container + rec.size();
-  if (cap_out) *cap_out = cap;
-  return MGH_SUCCESS;
+  return slot.fail(write_trailer(who, ": the output cannot hold container, mask record and footer", out, container,
+                                 cap - behind_min, S.d_words, n, S.n_masked, cfg, st, kMaskFooterBytes,
+                                 [&](uint32_t kind, size_t record, uint32_t crc, uint8_t *dst) {
+                                   f.kind = kind;
+                                   f.record = record;
+                                   f.crc = crc;
+                                   mask_footer_serialize(f, dst);
+                                 },
+                                 csize));
 }
 
 int compress_masked_impl(int D, int dtype, const uint64_t *shape, double tol, double s, int ebtype, const void *original,
                          const mgh_mask_spec &spec, void **compressed, size_t *csize, const void *const *coords,
                          const mgh_config &cfg, bool prealloc) {
-  const bool is_double = dtype == MGH_DOUBLE;
-  const size_t elem = is_double ? 8 : 4;
-  uint64_t n = 0;
-  HL_TRY(masked_shape_elems("compress_masked", D, shape, &n));
+  const char *bad_arg = nullptr;
   if (spec.flags == 0 || (spec.flags & ~(MGH_MASK_NONFINITE | MGH_MASK_VALUE)))
-    return hl_fail(MGH_ERR_INVALID_ARGUMENT, "compress_masked: flags must be MGH_MASK_NONFINITE, MGH_MASK_VALUE or both");
-  if ((spec.flags & MGH_MASK_VALUE) && std::isnan(spec.fill_value))
-    return hl_fail(MGH_ERR_INVALID_ARGUMENT, "compress_masked: a NaN fill_value (MGH_MASK_NONFINITE masks NaN)");
-  const bool in_dev = is_device_pointer(original);
-  // the array on the device, and for a device-resident one its filled copy beside it
-  if ((in_dev ? 2 : 1) * (uint64_t)n * elem > cfg.max_memory_footprint)
-    return hl_fail(MGH_ERR_INVALID_ARGUMENT,
-                   "compress_masked: the array and its filled copy do not fit max_memory_footprint (masked arrays are "
-                   "not streamed in parts)");
-  HL_TRY(cache_prepare(cfg.dev_id));
-  HlCache &C = g_cache;
-  hipStream_t st = C.lane[0].st;
-  const uint64_t nb = mask_packed_bytes(n);
-  HL_TRY(C.mwords.ensure(nb + sizeof(mgh_mask_stats)));
+    bad_arg = "compress_masked: flags must be MGH_MASK_NONFINITE, MGH_MASK_VALUE or both";
+  else if ((spec.flags & MGH_MASK_VALUE) && std::isnan(spec.fill_value))
+    bad_arg = "compress_masked: a NaN fill_value (MGH_MASK_NONFINITE masks NaN)";
   MaskedScan S;
-  S.n = n;
-  S.d_words = (uint64_t *)C.mwords.p;
-  mgh_mask_stats *d_stats = (mgh_mask_stats *)((char *)C.mwords.p + nb);
-  S.src = original;
-  if (!in_dev) {
-    HL_TRY(C.mfill.ensure(n * elem));
-    HL_TRY(copy_any(C.mfill.p, original, n * elem, st));
-    S.src = C.mfill.p;
-  }
+  mgh_mask_stats *d_stats = nullptr;
+  // the array on the device, and for a device-resident one its filled copy beside it
+  HL_TRY(scan_head("compress_masked", bad_arg,
+                   "compress_masked: the array and its filled copy do not fit max_memory_footprint (masked arrays are "
+                   "not streamed in parts)",
+                   D, dtype, shape, original, cfg, S, &d_stats));
+  hipStream_t st = g_cache.lane[0].st;
   HL_TRY(mgh_mask_scan(D, dtype, shape, S.src, spec.flags, spec.fill_value, S.d_words, d_stats, st));
   mgh_mask_stats hs{};
   HL_HIP(hipMemcpyAsync(&hs, d_stats, sizeof(hs), hipMemcpyDeviceToHost, st));
@@ -5434,8 +5457,8 @@ int compress_masked_impl(int D, int dtype, const uint64_t *shape, double tol, do
   S.n_masked = hs.n_masked;
   S.vmin = hs.vmin;
   S.vmax = hs.vmax;
-  return masked_write("compress_masked", D, dtype, shape, tol, s, ebtype, S, spec.restore_value, OutSlot{compressed, in_dev, prealloc},
-                      csize, coords, cfg, 0, 0, nullptr);
+  return masked_write("compress_masked", D, dtype, shape, tol, s, ebtype, S, spec.restore_value, OutSlot{compressed, S.in_dev, prealloc},
+                      csize, coords, cfg, 0, 0);
 }
 
 // A masked buffer opened: the footer, the header of the container in front of it, and the record on the host.
@@ -5447,14 +5470,28 @@ struct MaskedView {
   std::vector<uint8_t> rec;
 };
 
+// Bytes [at, at + len) of a buffer in device memory (in_dev) or on the host, on the host.
+int host_piece(void *dst, const void *buf, bool in_dev, size_t at, size_t len) {
+  const uint8_t *p = (const uint8_t *)buf + at;
+  if (len && in_dev) return aux_read(dst, p, len);
+  if (len) std::memcpy(dst, p, len);
+  return MGH_SUCCESS;
+}
+
+// The rule of every reader that needs its footer: open(buf, size, v) < 0 is a status, 0 (no footer's magic) is
+// MGH_ERR_FORMAT with the reader's own text.
+template <typename Open, typename View>
+int open_or_refuse(Open open, const void *buf, size_t size, View &v, const std::string &no_footer) {
+  const int opened = open(buf, size, v);
+  return opened < 0 ? opened : opened == 0 ? hl_fail(MGH_ERR_FORMAT, no_footer) : MGH_SUCCESS;
+}
+
 // 1: a masked buffer that passed every check; 0: no footer's magic; negative: a status.
 int masked_open(const void *buf, size_t size, MaskedView &v) {
   if (size < kMaskFooterBytes) return 0;
   const bool in_dev = is_device_pointer(buf);
   uint8_t tail[kMaskFooterBytes];
-  const uint8_t *p = (const uint8_t *)buf;
-  if (in_dev) HL_TRY(aux_read(tail, p + size - kMaskFooterBytes, kMaskFooterBytes));
-  else std::memcpy(tail, p + size - kMaskFooterBytes, kMaskFooterBytes);
+  HL_TRY(host_piece(tail, buf, in_dev, size - kMaskFooterBytes, kMaskFooterBytes));
   if (!mask_footer_present(tail, size)) return 0;
   if (const char *bad = mask_footer_parse(tail, size, v.f)) return hl_fail(MGH_ERR_FORMAT, bad);
   size_t meta = 0;
@@ -5469,10 +5506,7 @@ int masked_open(const void *buf, size_t size, MaskedView &v) {
   v.lossless = v.hd.compressor == fmt::COMP_X_HUFFMAN_ZSTD ? MGH_LOSSLESS_HUFFMAN_ZSTD : MGH_LOSSLESS_HUFFMAN;
   if (const char *bad = mask_footer_check_n(v.f, v.n, v.hd.is_double)) return hl_fail(MGH_ERR_FORMAT, bad);
   v.rec.resize((size_t)v.f.record);
-  if (v.f.record) {
-    if (in_dev) HL_TRY(aux_read(v.rec.data(), p + v.f.container, (size_t)v.f.record));
-    else std::memcpy(v.rec.data(), p + v.f.container, (size_t)v.f.record);
-  }
+  HL_TRY(host_piece(v.rec.data(), buf, in_dev, (size_t)v.f.container, (size_t)v.f.record));
   if (const char *bad = mask_record_check_crc(v.f, v.rec.data())) return hl_fail(MGH_ERR_FORMAT, bad);
   return 1;
 }
@@ -5522,12 +5556,14 @@ int masked_config(const mgh_config *config, mgh_config &cfg) {
   return MGH_SUCCESS;
 }
 
-int decompress_masked_impl(const void *buf, size_t size, const mgh_config &cfg, void **out, bool prealloc) {
-  MaskedView v;
-  const int opened = masked_open(buf, size, v);
-  if (opened < 0) return opened;
-  if (opened == 0) return hl_fail(MGH_ERR_FORMAT, "decompress_masked: no mask footer (a plain container has mgh_decompress)");
-  const size_t bytes = (size_t)v.n * (v.hd.is_double ? 8 : 4);
+// A reader whose last pass runs on the device, around the plain reader of the container part. It owns the output
+// (allocated in the memory space of `buf` unless pre-allocated), the device buffer a host output is reconstructed in
+// (C.mfill), the copy out and the final synchronise; every failure behind the allocation goes through slot.fail.
+// decode(&dst): the plain reader with the pre-allocated device destination; post(d_data, st): the device passes
+// over its result, queued on `st`.
+template <typename Decode, typename Post>
+int staged_read(const char *who, const void *buf, size_t bytes, const mgh_config &cfg, void **out, bool prealloc, Decode decode,
+                Post post) {
   const bool in_dev = is_device_pointer(buf);
   const bool out_dev = prealloc ? is_device_pointer(*out) : in_dev;
   HL_TRY(cache_prepare(cfg.dev_id));
@@ -5535,7 +5571,6 @@ int decompress_masked_impl(const void *buf, size_t size, const mgh_config &cfg, 
   hipStream_t st = C.lane[0].st;
   const OutSlot slot{out, in_dev, prealloc};
   HL_TRY(slot.alloc(bytes));
-  // the restore pass runs on the device: a host output is reconstructed in a device buffer first
   void *d_data = *out;
   int rc = MGH_SUCCESS;
   if (!out_dev) {
@@ -5543,51 +5578,42 @@ int decompress_masked_impl(const void *buf, size_t size, const mgh_config &cfg, 
     d_data = C.mfill.p;
   }
   void *dst = d_data;
-  if ((rc = mgh_decompress(buf, (size_t)v.f.container, &dst, &cfg, 1)) != MGH_SUCCESS) return slot.fail(rc);
-  if (v.f.kind != kMaskNone) {
-    uint64_t *d_words = nullptr;
-    if ((rc = masked_words(v, st, &d_words)) != MGH_SUCCESS) return slot.fail(rc);
-    rc = mgh_mask_restore_bits_((int)v.hd.shape.size(), v.dtype, v.hd.shape.data(), d_words, v.f.restore_bits, d_data, st);
-    if (rc != MGH_SUCCESS) return slot.fail(rc);
-  }
+  if ((rc = decode(&dst)) != MGH_SUCCESS) return slot.fail(rc);
+  if ((rc = post(d_data, st)) != MGH_SUCCESS) return slot.fail(rc);
   if (!out_dev && (rc = copy_any(*out, d_data, bytes, st)) != MGH_SUCCESS) return slot.fail(rc);
-  if (hipStreamSynchronize(st) != hipSuccess) return slot.fail(hl_fail(MGH_ERR_DEVICE, "decompress_masked: hipStreamSynchronize"));
+  if (hipStreamSynchronize(st) != hipSuccess) return slot.fail(hl_fail(MGH_ERR_DEVICE, std::string(who) + ": hipStreamSynchronize"));
   return MGH_SUCCESS;
 }
 
-int decompress_mask_impl(const void *buf, size_t size, const mgh_config &cfg, uint8_t *mask) {
-  MaskedView v;
-  const int opened = masked_open(buf, size, v);
-  if (opened < 0) return opened;
-  if (opened == 0) return hl_fail(MGH_ERR_FORMAT, "decompress_mask: no mask footer");
-  HL_TRY(cache_prepare(cfg.dev_id));
+// n bits of packed words on the device as one byte each in `mask` (host or device memory), complete on return.
+int mask_bytes_out(const uint64_t *d_words, size_t n, uint8_t *mask, hipStream_t st) {
   HlCache &C = g_cache;
-  hipStream_t st = C.lane[0].st;
-  uint64_t *d_words = nullptr;
-  HL_TRY(masked_words(v, st, &d_words));
   const bool out_dev = is_device_pointer(mask);
   uint8_t *d_mask = mask;
   if (!out_dev) {  // (the symbols have been narrowed into the words: their buffer is free)
-    HL_TRY(C.msym.ensure((size_t)v.n));
+    HL_TRY(C.msym.ensure(n));
     d_mask = (uint8_t *)C.msym.p;
   }
-  k_mask_expand<<<mask_grid((size_t)v.n), 256, 0, st>>>((const unsigned long long *)d_words, (size_t)v.n, d_mask);
+  k_mask_expand<<<mask_grid(n), 256, 0, st>>>((const unsigned long long *)d_words, n, d_mask);
   HL_HIP(hipGetLastError());
-  if (!out_dev) HL_TRY(copy_any(mask, d_mask, (size_t)v.n, st));
+  if (!out_dev) HL_TRY(copy_any(mask, d_mask, n, st));
   HL_HIP(hipStreamSynchronize(st));
   return MGH_SUCCESS;
 }
 
-// ---- masked buffers in the reduced-resolution, preview and verify readers -----------------------------------
+// ---- masked buffers in the full, reduced-resolution, preview and verify readers ------------------------------
 // THE RULE: a node of a level or coarsened array is masked when the element of the full array at that node's
 // index is masked (sampling: masked neighbours do not count); a position of a preview or of a window is masked
 // when that position of the full array is. Masked positions hold restore_value's bits; every other position
 // holds, bit for bit, what the same reader writes for the container part alone -- near masked regions that
 // value carries the influence of the fill.
+enum class ReadKind { full, level, coarsened, preview, window };  // mgh_decompress, _level, _coarsened, _preview(_window)
 struct MaskedRead {
-  int level = -1, halvings = -1;  // mgh_decompress_level / _coarsened, _preview(_window)
-  bool preview = false;
+  ReadKind kind = ReadKind::full;
+  int level = -1, halvings = -1;
   const uint64_t *lo = nullptr, *ext = nullptr;  // the window
+  const char *who = "masked reader";             // ... in the messages, and the refusal of a buffer without the footer
+  const char *no_footer = "masked reader: no mask footer (a plain container has the plain reader)";
 };
 
 // The shape of what the reader returns and, per dimension, the index in the full array of each of its positions
@@ -5596,25 +5622,24 @@ int masked_read_lists(const MaskedView &v, const mgh_config &cfg, const MaskedRe
                       std::vector<std::vector<uint32_t>> &lists, bool &sampled) {
   const int D = (int)v.hd.shape.size();
   lists.assign(D, {});
-  sampled = true;
+  sampled = R.kind != ReadKind::full && R.kind != ReadKind::preview;
   std::vector<uint64_t> idx;
-  if (R.level >= 0) {  // (refuses a decomposed container, as mgh_decompress_level does)
+  if (!sampled) {  // (nothing asked of the header but its shape: a decomposed container is as good as any)
+    oshape = v.hd.shape;
+  } else if (R.kind == ReadKind::level) {  // (refuses a decomposed container, as mgh_decompress_level does)
     int L = 0;
     HL_TRY(header_level_shape(v.hd, cfg, R.level, &L, &oshape));
     for (int d = 0; d < D; d++) {
       mgh::level_nodes(v.hd.shape[d], L - R.level, idx);
       lists[d].assign(idx.begin(), idx.end());
     }
-  } else if (R.lo) {
+  } else if (R.kind == ReadKind::window) {
     oshape.assign(R.ext, R.ext + D);
     for (int d = 0; d < D; d++) {
       if (R.ext[d] == 0 || R.lo[d] > v.hd.shape[d] || R.ext[d] > v.hd.shape[d] - R.lo[d])
         return hl_fail(MGH_ERR_INVALID_ARGUMENT, "the window leaves the array");
       for (uint64_t i = 0; i < R.ext[d]; i++) lists[d].push_back((uint32_t)(R.lo[d] + i));
     }
-  } else if (R.preview) {
-    oshape = v.hd.shape;
-    sampled = false;
   } else {  // the code that answers mgh_infer_coarsened_nodes
     Decomposer dd;
     HL_TRY(decomposer_from_header(v.hd, cfg, dd));
@@ -5659,59 +5684,40 @@ int masked_read_words(const MaskedView &v, const std::vector<uint64_t> &oshape, 
   return MGH_SUCCESS;
 }
 
-int masked_open_or_refuse(const char *who, const void *buf, size_t size, MaskedView &v) {
-  const int opened = masked_open(buf, size, v);
-  if (opened < 0) return opened;
-  if (opened == 0) return hl_fail(MGH_ERR_FORMAT, std::string(who) + ": no mask footer (a plain container has the plain reader)");
-  return MGH_SUCCESS;
-}
-
 // masked_open -> the plain reader on the first C bytes into a device buffer -> the mask -> its sample -> restore
 int masked_read_impl(const void *buf, size_t size, const mgh_config &cfg, const MaskedRead &R, void **out, bool prealloc) {
   MaskedView v;
-  HL_TRY(masked_open_or_refuse("masked reader", buf, size, v));
+  HL_TRY(open_or_refuse(masked_open, buf, size, v, R.no_footer));
   std::vector<uint64_t> oshape;
   std::vector<std::vector<uint32_t>> lists;
   bool sampled = false;
   HL_TRY(masked_read_lists(v, cfg, R, oshape, lists, sampled));
   size_t bytes = v.hd.is_double ? 8 : 4;
   for (uint64_t e : oshape) bytes *= (size_t)e;
-  const bool in_dev = is_device_pointer(buf);
-  const bool out_dev = prealloc ? is_device_pointer(*out) : in_dev;
-  HL_TRY(cache_prepare(cfg.dev_id));
-  HlCache &C = g_cache;
-  hipStream_t st = C.lane[0].st;
-  const OutSlot slot{out, in_dev, prealloc};
-  HL_TRY(slot.alloc(bytes));
-  // the restore pass runs on the device: a host output is reconstructed in a device buffer first
-  void *d_data = *out;
-  int rc = MGH_SUCCESS;
-  if (!out_dev) {
-    if ((rc = C.mfill.ensure(bytes)) != MGH_SUCCESS) return slot.fail(rc);
-    d_data = C.mfill.p;
-  }
-  void *dst = d_data;
   const size_t csize = (size_t)v.f.container;
-  if (R.level >= 0) rc = mgh_decompress_level(buf, csize, R.level, &dst, &cfg, 1);
-  else if (R.lo) rc = mgh_decompress_preview_window(buf, csize, R.halvings, R.lo, R.ext, &dst, &cfg, 1);
-  else if (R.preview) rc = mgh_decompress_preview(buf, csize, R.halvings, &dst, &cfg, 1);
-  else rc = mgh_decompress_coarsened(buf, csize, R.halvings, &dst, &cfg, 1);
-  if (rc != MGH_SUCCESS) return slot.fail(rc);
-  if (v.f.kind != kMaskNone) {
-    uint64_t *d_words = nullptr;
-    if ((rc = masked_read_words(v, oshape, lists, sampled, st, &d_words)) != MGH_SUCCESS) return slot.fail(rc);
-    rc = mgh_mask_restore_bits_((int)oshape.size(), v.dtype, oshape.data(), d_words, v.f.restore_bits, d_data, st);
-    if (rc != MGH_SUCCESS) return slot.fail(rc);
-  }
-  if (!out_dev && (rc = copy_any(*out, d_data, bytes, st)) != MGH_SUCCESS) return slot.fail(rc);
-  if (hipStreamSynchronize(st) != hipSuccess) return slot.fail(hl_fail(MGH_ERR_DEVICE, "masked reader: hipStreamSynchronize"));
-  return MGH_SUCCESS;
+  return staged_read(
+      R.who, buf, bytes, cfg, out, prealloc,
+      [&](void **dst) {
+        switch (R.kind) {
+        case ReadKind::full: return mgh_decompress(buf, csize, dst, &cfg, 1);
+        case ReadKind::level: return mgh_decompress_level(buf, csize, R.level, dst, &cfg, 1);
+        case ReadKind::coarsened: return mgh_decompress_coarsened(buf, csize, R.halvings, dst, &cfg, 1);
+        case ReadKind::preview: return mgh_decompress_preview(buf, csize, R.halvings, dst, &cfg, 1);
+        default: return mgh_decompress_preview_window(buf, csize, R.halvings, R.lo, R.ext, dst, &cfg, 1);
+        }
+      },
+      [&](void *d_data, hipStream_t st) -> int {
+        if (v.f.kind == kMaskNone) return MGH_SUCCESS;
+        uint64_t *d_words = nullptr;
+        HL_TRY(masked_read_words(v, oshape, lists, sampled, st, &d_words));
+        return mgh_mask_restore_bits_((int)oshape.size(), v.dtype, oshape.data(), d_words, v.f.restore_bits, d_data, st);
+      });
 }
 
 // ... and the sampled mask alone, one byte per output element
 int masked_read_mask_impl(const void *buf, size_t size, const mgh_config &cfg, const MaskedRead &R, uint8_t *mask) {
   MaskedView v;
-  HL_TRY(masked_open_or_refuse("masked reader", buf, size, v));
+  HL_TRY(open_or_refuse(masked_open, buf, size, v, R.no_footer));
   std::vector<uint64_t> oshape;
   std::vector<std::vector<uint32_t>> lists;
   bool sampled = false;
@@ -5719,21 +5725,10 @@ int masked_read_mask_impl(const void *buf, size_t size, const mgh_config &cfg, c
   size_t n_out = 1;
   for (uint64_t e : oshape) n_out *= (size_t)e;
   HL_TRY(cache_prepare(cfg.dev_id));
-  HlCache &C = g_cache;
-  hipStream_t st = C.lane[0].st;
+  hipStream_t st = g_cache.lane[0].st;
   uint64_t *d_words = nullptr;
   HL_TRY(masked_read_words(v, oshape, lists, sampled, st, &d_words));
-  const bool out_dev = is_device_pointer(mask);
-  uint8_t *d_mask = mask;
-  if (!out_dev) {  // (the symbols have been narrowed into the words: their buffer is free)
-    HL_TRY(C.msym.ensure(n_out));
-    d_mask = (uint8_t *)C.msym.p;
-  }
-  k_mask_expand<<<mask_grid(n_out), 256, 0, st>>>((const unsigned long long *)d_words, n_out, d_mask);
-  HL_HIP(hipGetLastError());
-  if (!out_dev) HL_TRY(copy_any(mask, d_mask, n_out, st));
-  HL_HIP(hipStreamSynchronize(st));
-  return MGH_SUCCESS;
+  return mask_bytes_out(d_words, n_out, mask, st);
 }
 
 int masked_read_entry(const void *buf, size_t size, const mgh_config *config, const MaskedRead &R, void **out, int prealloc) {
@@ -5785,24 +5780,23 @@ int mgh_masked_info(const void *compressed_data, size_t compressed_size, struct 
 
 int mgh_decompress_masked(const void *compressed_data, size_t compressed_size, const mgh_config *config,
                           void **decompressed_data, int output_pre_allocated) {
-  if (!compressed_data || !decompressed_data) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "NULL argument");
-  if (output_pre_allocated && !*decompressed_data) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "pre-allocated output is NULL");
-  mgh_config cfg;
-  HL_TRY(masked_config(config, cfg));
-  return hl_guarded([&] { return decompress_masked_impl(compressed_data, compressed_size, cfg, decompressed_data, output_pre_allocated != 0); });
+  MaskedRead R;  // (the full array)
+  R.who = "decompress_masked";
+  R.no_footer = "decompress_masked: no mask footer (a plain container has mgh_decompress)";
+  return masked_read_entry(compressed_data, compressed_size, config, R, decompressed_data, output_pre_allocated);
 }
 
 int mgh_decompress_mask(const void *compressed_data, size_t compressed_size, const mgh_config *config, uint8_t *mask) {
-  if (!compressed_data || !mask) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "NULL argument");
-  mgh_config cfg;
-  HL_TRY(masked_config(config, cfg));
-  return hl_guarded([&] { return decompress_mask_impl(compressed_data, compressed_size, cfg, mask); });
+  MaskedRead R;  // (the full array)
+  R.no_footer = "decompress_mask: no mask footer";
+  return masked_read_mask_entry(compressed_data, compressed_size, config, R, mask);
 }
 
 int mgh_decompress_masked_level(const void *compressed_data, size_t compressed_size, int level, void **decompressed_data,
                                 const mgh_config *config, int output_pre_allocated) {
   if (level < 0) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "level outside 0 .. l_target");
   MaskedRead R;
+  R.kind = ReadKind::level;
   R.level = level;
   return masked_read_entry(compressed_data, compressed_size, config, R, decompressed_data, output_pre_allocated);
 }
@@ -5811,6 +5805,7 @@ int mgh_decompress_masked_coarsened(const void *compressed_data, size_t compress
                                     const mgh_config *config, int output_pre_allocated) {
   if (halvings < 0) return hl_fail(MGH_ERR_INVALID_ARGUMENT, kBadHalvings);
   MaskedRead R;
+  R.kind = ReadKind::coarsened;
   R.halvings = halvings;
   return masked_read_entry(compressed_data, compressed_size, config, R, decompressed_data, output_pre_allocated);
 }
@@ -5819,8 +5814,8 @@ int mgh_decompress_masked_preview(const void *compressed_data, size_t compressed
                                   const mgh_config *config, int output_pre_allocated) {
   if (halvings < 0) return hl_fail(MGH_ERR_INVALID_ARGUMENT, kBadHalvings);
   MaskedRead R;
+  R.kind = ReadKind::preview;
   R.halvings = halvings;
-  R.preview = true;
   return masked_read_entry(compressed_data, compressed_size, config, R, decompressed_data, output_pre_allocated);
 }
 
@@ -5830,8 +5825,8 @@ int mgh_decompress_masked_preview_window(const void *compressed_data, size_t com
   if (!lo || !ext) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "NULL argument");
   if (halvings < 0) return hl_fail(MGH_ERR_INVALID_ARGUMENT, kBadHalvings);
   MaskedRead R;
+  R.kind = ReadKind::window;
   R.halvings = halvings;
-  R.preview = true;
   R.lo = lo;
   R.ext = ext;
   return masked_read_entry(compressed_data, compressed_size, config, R, decompressed_data, output_pre_allocated);
@@ -5841,6 +5836,7 @@ int mgh_decompress_mask_level(const void *compressed_data, size_t compressed_siz
                               uint8_t *mask) {
   if (level < 0) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "level outside 0 .. l_target");
   MaskedRead R;
+  R.kind = ReadKind::level;
   R.level = level;
   return masked_read_mask_entry(compressed_data, compressed_size, config, R, mask);
 }
@@ -5849,6 +5845,7 @@ int mgh_decompress_mask_coarsened(const void *compressed_data, size_t compressed
                                   uint8_t *mask) {
   if (halvings < 0) return hl_fail(MGH_ERR_INVALID_ARGUMENT, kBadHalvings);
   MaskedRead R;
+  R.kind = ReadKind::coarsened;
   R.halvings = halvings;
   return masked_read_mask_entry(compressed_data, compressed_size, config, R, mask);
 }
@@ -5857,7 +5854,7 @@ int mgh_decompress_mask_window(const void *compressed_data, size_t compressed_si
                                const mgh_config *config, uint8_t *mask) {
   if (!lo || !ext) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "NULL argument");
   MaskedRead R;
-  R.preview = true;
+  R.kind = ReadKind::window;
   R.lo = lo;
   R.ext = ext;
   return masked_read_mask_entry(compressed_data, compressed_size, config, R, mask);
@@ -5877,7 +5874,8 @@ int mgh_verify_masked(const void *compressed_data, size_t compressed_size, const
   uint64_t n_total = 0;
   HL_TRY(hl_guarded([&]() -> int {
     MaskedView v;
-    HL_TRY(masked_open_or_refuse("mgh_verify_masked", compressed_data, compressed_size, v));
+    HL_TRY(open_or_refuse(masked_open, compressed_data, compressed_size, v,
+                          "mgh_verify_masked: no mask footer (a plain container has the plain reader)"));
     n_total = v.n;
     compressed_size = (size_t)v.f.container;
     // the packed mask, whole and complete on the device before the subdomains' lanes read it
@@ -5926,38 +5924,25 @@ namespace {
 int compress_pwrel_impl(int D, int dtype, const uint64_t *shape, double eps, double abs_floor, const void *original,
                         void **compressed, size_t *csize, const void *const *coords, const mgh_config &cfg, bool prealloc) {
   const bool is_double = dtype == MGH_DOUBLE;
-  const size_t elem = is_double ? 8 : 4;
-  uint64_t n = 0;
-  HL_TRY(masked_shape_elems("compress_pwrel", D, shape, &n));
   double delta = 0;
-  if (const char *bad = pwrel_abs_tolerance(is_double, eps, -1.0, &delta)) return hl_fail(MGH_ERR_INVALID_ARGUMENT, bad);
-  if (!(abs_floor >= 0.0) || std::isinf(abs_floor))
-    return hl_fail(MGH_ERR_INVALID_ARGUMENT, "compress_pwrel: abs_floor must be finite and >= 0");
-  const bool in_dev = is_device_pointer(original);
+  const char *bad_arg = pwrel_abs_tolerance(is_double, eps, -1.0, &delta);
+  if (!bad_arg && (!(abs_floor >= 0.0) || std::isinf(abs_floor))) bad_arg = "compress_pwrel: abs_floor must be finite and >= 0";
+  MaskedScan S;
+  mgh_pwrel_stats *d_stats = nullptr;
   // the array on the device (a host array is uploaded once and transformed in place), and for a device-resident one,
   // which is not modified, y beside it
-  if ((in_dev ? 2 : 1) * (uint64_t)n * elem > cfg.max_memory_footprint)
-    return hl_fail(MGH_ERR_INVALID_ARGUMENT,
+  HL_TRY(scan_head("compress_pwrel", bad_arg,
                    "compress_pwrel: the array and its transformed copy do not fit max_memory_footprint (such arrays are "
-                   "not streamed in parts)");
-  HL_TRY(cache_prepare(cfg.dev_id));
+                   "not streamed in parts)",
+                   D, dtype, shape, original, cfg, S, &d_stats));
   HlCache &C = g_cache;
   hipStream_t st = C.lane[0].st;
-  const uint64_t nb = mask_packed_bytes(n);
-  HL_TRY(C.mwords.ensure(nb + sizeof(mgh_pwrel_stats)));
+  const uint64_t n = S.n, nb = mask_packed_bytes(n);
   HL_TRY(C.msamp.ensure(nb));
-  HL_TRY(C.mfill.ensure(n * elem));
+  HL_TRY(C.mfill.ensure(n * (is_double ? 8 : 4)));
   uint64_t *d_flags = (uint64_t *)C.msamp.p;
-  mgh_pwrel_stats *d_stats = (mgh_pwrel_stats *)((char *)C.mwords.p + nb);
-  const void *x = original;
-  if (!in_dev) {
-    HL_TRY(copy_any(C.mfill.p, original, n * elem, st));
-    x = C.mfill.p;
-  }
-  MaskedScan S;
-  S.n = n;
+  const void *x = S.src;
   S.src = C.mfill.p;
-  S.d_words = (uint64_t *)C.mwords.p;
   HL_TRY(mgh_pwrel_forward_(D, dtype, shape, x, abs_floor, C.mfill.p, S.d_words, d_flags, d_stats, st));
   mgh_pwrel_stats hs{};
   HL_HIP(hipMemcpyAsync(&hs, d_stats, sizeof(hs), hipMemcpyDeviceToHost, st));
@@ -5967,28 +5952,27 @@ int compress_pwrel_impl(int D, int dtype, const uint64_t *shape, double eps, dou
   S.vmax = hs.ymax;
   const double ybound = hs.n_masked >= n ? -1.0 : std::fmax(std::fabs(hs.ymin), std::fabs(hs.ymax));
   if (const char *bad = pwrel_abs_tolerance(is_double, eps, ybound, &delta)) return hl_fail(MGH_ERR_INVALID_ARGUMENT, bad);
-  const OutSlot slot{compressed, in_dev, prealloc};
-  size_t masked = prealloc ? *csize : 0, cap = 0;
+  const OutSlot slot{compressed, S.in_dev, prealloc};
+  // the flag record, like the mask record, and the footer found from the end: at most the packed flag words and the
+  // footer, which an allocated output has behind whatever the masked buffer took
+  const size_t behind_max = nb + kPwrelFooterBytes, given = prealloc ? *csize : 0;
+  size_t masked = given;
   HL_TRY(masked_write("compress_pwrel", D, dtype, shape, delta, std::numeric_limits<double>::infinity(), MGH_ABS, S, 0.0, slot,
-                      &masked, coords, cfg, kPwrelFooterBytes, nb + kPwrelFooterBytes, &cap));
-  // the flag record, like the mask record, and the footer found from the end
+                      &masked, coords, cfg, kPwrelFooterBytes, behind_max));
   PwrelFooter f;
   f.masked = masked;
   f.n_flag = hs.n_flag;
   f.eps = eps;
   f.abs_floor = abs_floor;
-  std::vector<uint8_t> rec;
-  int rc = bitmap_record("compress_pwrel", d_flags, n, hs.n_flag, cfg, st, f.kind, rec);
-  if (rc != MGH_SUCCESS) return slot.fail(rc);
-  f.record = rec.size();
-  f.crc = fmt::crc32(rec.data(), rec.size());
-  if (masked + rec.size() + kPwrelFooterBytes > cap)
-    return slot.fail(hl_fail(MGH_ERR_OUTPUT_TOO_LARGE, "compress_pwrel: the output cannot hold masked buffer, flag record and footer"));
-  rec.resize(rec.size() + kPwrelFooterBytes);
-  pwrel_footer_serialize(f, rec.data() + f.record);
-  if ((rc = write_behind("compress_pwrel", *compressed, masked, rec, st)) != MGH_SUCCESS) return slot.fail(rc);
-  *csize = masked + rec.size();
-  return MGH_SUCCESS;
+  return slot.fail(write_trailer("compress_pwrel", ": the output cannot hold masked buffer, flag record and footer", *compressed,
+                                 masked, prealloc ? given : masked + behind_max, d_flags, n, hs.n_flag, cfg, st, kPwrelFooterBytes,
+                                 [&](uint32_t kind, size_t record, uint32_t crc, uint8_t *dst) {
+                                   f.kind = kind;
+                                   f.record = record;
+                                   f.crc = crc;
+                                   pwrel_footer_serialize(f, dst);
+                                 },
+                                 csize));
 }
 
 // A pointwise-relative buffer opened: its footer, the masked buffer in front of it, and the flag record on the host.
@@ -6003,67 +5987,41 @@ int pwrel_open(const void *buf, size_t size, PwrelView &v) {
   if (size < kPwrelFooterBytes) return 0;
   const bool in_dev = is_device_pointer(buf);
   uint8_t tail[kPwrelFooterBytes];
-  const uint8_t *p = (const uint8_t *)buf;
-  if (in_dev) HL_TRY(aux_read(tail, p + size - kPwrelFooterBytes, kPwrelFooterBytes));
-  else std::memcpy(tail, p + size - kPwrelFooterBytes, kPwrelFooterBytes);
+  HL_TRY(host_piece(tail, buf, in_dev, size - kPwrelFooterBytes, kPwrelFooterBytes));
   if (!pwrel_footer_present(tail, size)) return 0;
   if (const char *bad = pwrel_footer_parse(tail, size, v.f)) return hl_fail(MGH_ERR_FORMAT, bad);
-  const int opened = masked_open(buf, (size_t)v.f.masked, v.m);
-  if (opened < 0) return opened;
-  if (opened == 0) return hl_fail(MGH_ERR_FORMAT, "pwrel footer: the bytes in front of the flag record are no masked buffer");
+  HL_TRY(open_or_refuse(masked_open, buf, (size_t)v.f.masked, v.m,
+                        "pwrel footer: the bytes in front of the flag record are no masked buffer"));
   if (v.m.f.restore_bits != 0) return hl_fail(MGH_ERR_FORMAT, "pwrel footer: the masked buffer's restore value is not +0.0");
   if (const char *bad = pwrel_footer_check_n(v.f, v.m.n)) return hl_fail(MGH_ERR_FORMAT, bad);
   v.rec.resize((size_t)v.f.record);
-  if (v.f.record) {
-    if (in_dev) HL_TRY(aux_read(v.rec.data(), p + v.f.masked, (size_t)v.f.record));
-    else std::memcpy(v.rec.data(), p + v.f.masked, (size_t)v.f.record);
-  }
+  HL_TRY(host_piece(v.rec.data(), buf, in_dev, (size_t)v.f.masked, (size_t)v.f.record));
   if (const char *bad = pwrel_record_check_crc(v.f, v.rec.data())) return hl_fail(MGH_ERR_FORMAT, bad);
   return 1;
 }
 
-int pwrel_open_or_refuse(const char *who, const void *buf, size_t size, PwrelView &v) {
-  const int opened = pwrel_open(buf, size, v);
-  if (opened < 0) return opened;
-  if (opened == 0)
-    return hl_fail(MGH_ERR_FORMAT, std::string(who) + ": no pointwise-relative footer (a plain container has mgh_decompress, a "
-                                                      "masked buffer mgh_decompress_masked)");
-  return MGH_SUCCESS;
-}
+const char *const kNoPwrelFooter =
+    ": no pointwise-relative footer (a plain container has mgh_decompress, a masked buffer mgh_decompress_masked)";
 
 // footer -> mgh_decompress of the container part -> mask words and flag words -> k_pwrel_inverse
 int decompress_pwrel_impl(const void *buf, size_t size, const mgh_config &cfg, void **out, bool prealloc) {
   PwrelView v;
-  HL_TRY(pwrel_open_or_refuse("decompress_pwrel", buf, size, v));
+  HL_TRY(open_or_refuse(pwrel_open, buf, size, v, std::string("decompress_pwrel") + kNoPwrelFooter));
   const uint64_t n = v.m.n;
-  const size_t bytes = (size_t)n * (v.m.hd.is_double ? 8 : 4);
-  const bool in_dev = is_device_pointer(buf);
-  const bool out_dev = prealloc ? is_device_pointer(*out) : in_dev;
-  HL_TRY(cache_prepare(cfg.dev_id));
-  HlCache &C = g_cache;
-  hipStream_t st = C.lane[0].st;
-  const OutSlot slot{out, in_dev, prealloc};
-  HL_TRY(slot.alloc(bytes));
-  // the inverse pass runs on the device: a host output is reconstructed in a device buffer first
-  void *d_data = *out;
-  int rc = MGH_SUCCESS;
-  if (!out_dev) {
-    if ((rc = C.mfill.ensure(bytes)) != MGH_SUCCESS) return slot.fail(rc);
-    d_data = C.mfill.p;
-  }
-  void *dst = d_data;
-  if ((rc = mgh_decompress(buf, (size_t)v.m.f.container, &dst, &cfg, 1)) != MGH_SUCCESS) return slot.fail(rc);
-  uint64_t *d_words = nullptr;
-  if ((rc = masked_words(v.m, st, &d_words)) != MGH_SUCCESS) return slot.fail(rc);
-  // (the two records share the symbol buffer and the lossless context of the lane: one after the other)
-  if (hipStreamSynchronize(st) != hipSuccess) return slot.fail(hl_fail(MGH_ERR_DEVICE, "decompress_pwrel: hipStreamSynchronize"));
-  if ((rc = C.msamp.ensure(mask_packed_bytes(n))) != MGH_SUCCESS) return slot.fail(rc);
-  if ((rc = bitmap_words(v.f.kind, v.rec, n, v.m.lossless, C.msamp.p, st)) != MGH_SUCCESS) return slot.fail(rc);
-  rc = mgh_pwrel_inverse_((int)v.m.hd.shape.size(), v.m.dtype, v.m.hd.shape.data(), d_words, (const uint64_t *)C.msamp.p, d_data, st);
-  if (rc != MGH_SUCCESS) return slot.fail(rc);
-  if (!out_dev && (rc = copy_any(*out, d_data, bytes, st)) != MGH_SUCCESS) return slot.fail(rc);
-  if (hipStreamSynchronize(st) != hipSuccess) return slot.fail(hl_fail(MGH_ERR_DEVICE, "decompress_pwrel: hipStreamSynchronize"));
-  return MGH_SUCCESS;
+  return staged_read(
+      "decompress_pwrel", buf, (size_t)n * (v.m.hd.is_double ? 8 : 4), cfg, out, prealloc,
+      [&](void **dst) { return mgh_decompress(buf, (size_t)v.m.f.container, dst, &cfg, 1); },
+      [&](void *d_data, hipStream_t st) -> int {
+        HlCache &C = g_cache;
+        uint64_t *d_words = nullptr;
+        HL_TRY(masked_words(v.m, st, &d_words));
+        // (the two records share the symbol buffer and the lossless context of the lane: one after the other)
+        if (hipStreamSynchronize(st) != hipSuccess) return hl_fail(MGH_ERR_DEVICE, "decompress_pwrel: hipStreamSynchronize");
+        HL_TRY(C.msamp.ensure(mask_packed_bytes(n)));
+        HL_TRY(bitmap_words(v.f.kind, v.rec, n, v.m.lossless, C.msamp.p, st));
+        return mgh_pwrel_inverse_((int)v.m.hd.shape.size(), v.m.dtype, v.m.hd.shape.data(), d_words, (const uint64_t *)C.msamp.p,
+                                  d_data, st);
+      });
 }
 
 struct DeviceTemp {
@@ -6077,7 +6035,7 @@ struct DeviceTemp {
 int verify_pwrel_impl(const void *buf, size_t size, const void *original, size_t original_bytes, int original_dtype,
                       const mgh_config &cfg, mgh_pwrel_compare *out, int *within) {
   PwrelView v;
-  HL_TRY(pwrel_open_or_refuse("mgh_verify_pwrel", buf, size, v));
+  HL_TRY(open_or_refuse(pwrel_open, buf, size, v, std::string("mgh_verify_pwrel") + kNoPwrelFooter));
   const uint64_t n = v.m.n;
   const size_t bytes = (size_t)n * (v.m.hd.is_double ? 8 : 4);
   if (original_dtype != v.m.dtype) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "mgh_verify_pwrel: the original's dtype is not the buffer's");

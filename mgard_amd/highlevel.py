@@ -405,12 +405,25 @@ def _as_ptr(a):
     return C.c_void_p(a.ctypes.data), dt, a.shape, a
 
 
+def _writer_out(data, out, cap):
+    """(out, pointer, size word) of a writer's output: `out` where given (its size is the capacity), else a new uint8
+    buffer of `cap` bytes -- a numpy array for host `data`, a cuda tensor beside device `data`."""
+    import torch
+    on_device = isinstance(data, torch.Tensor) and data.is_cuda
+    if out is not None:
+        cap = int(out.numel()) if on_device else int(out.size)
+    elif on_device:
+        out = torch.empty(cap, dtype=torch.uint8, device=data.device)
+    else:
+        out = np.empty(cap, dtype=np.uint8)
+    return out, C.c_void_p(out.data_ptr() if on_device else out.ctypes.data), C.c_size_t(cap)
+
+
 def compress(data, tol, s=INF, mode=REL, coords=None, config=None, out_capacity=None, out=None):
     """mgard_x::compress. `data`: numpy array (host) or cuda tensor (device). Returns the
     compressed stream as a numpy uint8 array (host input) or a cuda uint8 tensor (device input).
     `out`: optional pre-allocated uint8 buffer of the same kind to write into (its size is the
     capacity)."""
-    import torch
     L = _hl()
     cfg = config if config is not None else Config()
     ptr, dt, shape, keep = _as_ptr(data)
@@ -427,19 +440,8 @@ def compress(data, tol, s=INF, mode=REL, coords=None, config=None, out_capacity=
             ckeep.append(c)
             arr[d] = c.ctypes.data
         cptr = arr
-    on_device = isinstance(data, torch.Tensor) and data.is_cuda
     nbytes = int(np.prod(shape)) * (4 if dt == FLOAT else 8)
-    cap = int(out_capacity) if out_capacity is not None else nbytes + 1000000
-    if out is not None:
-        cap = int(out.numel()) if on_device else int(out.size)
-        optr = C.c_void_p(out.data_ptr()) if on_device else C.c_void_p(out.ctypes.data)
-    elif on_device:
-        out = torch.empty(cap, dtype=torch.uint8, device=data.device)
-        optr = C.c_void_p(out.data_ptr())
-    else:
-        out = np.empty(cap, dtype=np.uint8)
-        optr = C.c_void_p(out.ctypes.data)
-    size = C.c_size_t(cap)
+    out, optr, size = _writer_out(data, out, int(out_capacity) if out_capacity is not None else nbytes + 1000000)
     _check(L.mgh_compress(D, dt, shp, float(tol), float(s), int(mode), ptr, C.byref(optr), C.byref(size),
                           cptr, C.byref(cfg), 1))
     return out[:size.value]
@@ -651,7 +653,6 @@ def compress_masked(data, tol, s=INF, mode=REL, nonfinite=True, fill_value=None,
     every reader; decompress_masked puts `restore_value` at the masked positions. The bound holds at every valid
     position. Host array in, numpy buffer out; cuda tensor in, cuda buffer out. `out`: optional pre-allocated uint8
     buffer of the same kind (its size is the capacity)."""
-    import torch
     from . import mask_flags
     L = _hl()
     cfg = config if config is not None else Config()
@@ -660,17 +661,8 @@ def compress_masked(data, tol, s=INF, mode=REL, nonfinite=True, fill_value=None,
     D = len(shape)
     shp = (C.c_uint64 * D)(*shape)
     cptr, ckeep = _coords_ptr(coords, dt, D)
-    on_device = isinstance(data, torch.Tensor) and data.is_cuda
     n = int(np.prod(shape))
-    cap = n * (4 if dt == FLOAT else 8) + 1000000 + 8 * ((n + 63) // 64) + 48
-    if out is not None:
-        cap = int(out.numel()) if on_device else int(out.size)
-    elif on_device:
-        out = torch.empty(cap, dtype=torch.uint8, device=data.device)
-    else:
-        out = np.empty(cap, dtype=np.uint8)
-    optr = C.c_void_p(out.data_ptr()) if on_device else C.c_void_p(out.ctypes.data)
-    size = C.c_size_t(cap)
+    out, optr, size = _writer_out(data, out, n * (4 if dt == FLOAT else 8) + 1000000 + 8 * ((n + 63) // 64) + 48)
     spec = MaskSpec(mask_flags(nonfinite, fill_value), 0.0 if fill_value is None else float(fill_value), float(restore_value))
     _check(L.mgh_compress_masked(D, dt, shp, float(tol), float(s), int(mode), ptr, C.byref(spec), C.byref(optr),
                                  C.byref(size), cptr, C.byref(cfg), 1))
@@ -686,6 +678,18 @@ def masked_info(buf):
     rc = _check(_hl().mgh_masked_info(p, n, C.byref(info)))
     del keep
     return info if rc == 1 else None
+
+
+def _footed_full(call, info_of, buf, cfg, out):
+    """The full array of a buffer with a footer (`info_of`: masked_info or pwrel_info; `call`: its C reader) into `out`
+    or a new array shaped by the container part. A buffer without the footer: the library's own refusal is raised."""
+    p, n, _, keep = _container_ptr(buf)
+    info = info_of(keep)
+    if info is None:
+        _check(call(p, n, C.byref(cfg), C.byref(C.c_void_p()), 0))  # (raises: no footer)
+    out, optr = _layers_out(keep[:info.container_size], out)
+    _check(call(p, n, C.byref(cfg), C.byref(optr), 1))
+    return out
 
 
 def _masked_view(buf, cfg, level, coarsen, window, what):
@@ -743,13 +747,7 @@ def decompress_masked(buf, config=None, out=None, level=None, coarsen=None):
     L = _hl()
     cfg = config if config is not None else Config()
     if level is None and coarsen is None:
-        p, n, _, keep = _container_ptr(buf)
-        info = masked_info(keep)
-        if info is None:
-            _check(L.mgh_decompress_masked(p, n, C.byref(cfg), C.byref(C.c_void_p()), 0))  # (raises: no footer)
-        out, optr = _layers_out(keep[:info.container_size], out)
-        _check(L.mgh_decompress_masked(p, n, C.byref(cfg), C.byref(optr), 1))
-        return out
+        return _footed_full(L.mgh_decompress_masked, masked_info, buf, cfg, out)
     p, n, _, keep, cont, shape = _masked_view(buf, cfg, level, coarsen, None, "decompress_masked")
     out, optr = _masked_out(cont, shape, out)
     if level is not None:
@@ -835,7 +833,6 @@ def compress_pwrel(data, eps, abs_floor=0.0, coords=None, config=None, out=None)
     every reader, as y. 0 < eps < 1; an eps the data type cannot carry at the field's dynamic range raises. Host array
     in, numpy buffer out; cuda tensor in, cuda buffer out. `out`: optional pre-allocated uint8 buffer of the same kind
     (its size is the capacity)."""
-    import torch
     L = _hl()
     cfg = config if config is not None else Config()
     ptr, dt, shape, keep = _as_ptr(data)
@@ -843,17 +840,8 @@ def compress_pwrel(data, eps, abs_floor=0.0, coords=None, config=None, out=None)
     D = len(shape)
     shp = (C.c_uint64 * D)(*shape)
     cptr, ckeep = _coords_ptr(coords, dt, D)
-    on_device = isinstance(data, torch.Tensor) and data.is_cuda
     n = int(np.prod(shape))
-    cap = n * (4 if dt == FLOAT else 8) + 1000000 + 16 * ((n + 63) // 64) + 48 + 56
-    if out is not None:
-        cap = int(out.numel()) if on_device else int(out.size)
-    elif on_device:
-        out = torch.empty(cap, dtype=torch.uint8, device=data.device)
-    else:
-        out = np.empty(cap, dtype=np.uint8)
-    optr = C.c_void_p(out.data_ptr()) if on_device else C.c_void_p(out.ctypes.data)
-    size = C.c_size_t(cap)
+    out, optr, size = _writer_out(data, out, n * (4 if dt == FLOAT else 8) + 1000000 + 16 * ((n + 63) // 64) + 48 + 56)
     _check(L.mgh_compress_pwrel(D, dt, shp, float(eps), float(abs_floor), ptr, C.byref(optr), C.byref(size), cptr,
                                 C.byref(cfg), 1))
     del keep, ckeep
@@ -873,15 +861,7 @@ def pwrel_info(buf):
 def decompress_pwrel(buf, config=None, out=None):
     """mgh_decompress_pwrel: the array of a pointwise-relative buffer. A numpy array (host buffer) or a cuda tensor;
     `out` as for decompress_layers. Any other buffer is refused."""
-    L = _hl()
-    cfg = config if config is not None else Config()
-    p, n, _, keep = _container_ptr(buf)
-    info = pwrel_info(keep)
-    if info is None:
-        _check(L.mgh_decompress_pwrel(p, n, C.byref(cfg), C.byref(C.c_void_p()), 0))  # (raises: no footer)
-    out, optr = _layers_out(keep[:info.container_size], out)
-    _check(L.mgh_decompress_pwrel(p, n, C.byref(cfg), C.byref(optr), 1))
-    return out
+    return _footed_full(_hl().mgh_decompress_pwrel, pwrel_info, buf, config if config is not None else Config(), out)
 
 
 def verify_pwrel(buf, original, config=None):

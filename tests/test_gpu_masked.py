@@ -144,6 +144,44 @@ def test_nothing_masked_is_kind_2_and_the_plain_container(shape, dtype):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("where", ["host", "device"])
+def test_full_readers_of_a_domain_decomposed_buffer(where):
+    """The full array and the full mask ask nothing of the container's header but its shape, so a container in
+    subdomains reads like any other; `level` is refused as mgh_decompress_level refuses it. The writer splits a host
+    array whose footprint estimate (tests/util.py: reference_footprint, 639408 bytes here) reaches the budget: halves of
+    33 along the first dimension. The mask is 10 % NaN, restored as -9999."""
+    import torch
+    import mgard_amd
+    from mgard_amd import highlevel as hl
+    from tests.util import reference_footprint
+    shape, dtype = (33, 20, 17), np.float32
+    data = inside_field(shape, dtype)
+    data[np.random.default_rng(7).random(shape) < 0.10] = NAN
+    mask = mm.classify(data, nonfinite=True, fill_value=None)
+    assert 0.05 * data.size < mask.sum() < 0.15 * data.size
+    budget = reference_footprint(shape, 4, dict_size=1024)
+    assert data.nbytes < budget
+    cfg = hl.Config(huff_dict_size=1024, max_memory_footprint=budget)
+    hbuf = hl.compress_masked(data, TOL, INF, mgard_amd.REL, config=cfg, restore_value=-9999.0)
+    C = int(hl.masked_info(hbuf).container_size)
+    m = hl.metadata_parse(hbuf[:C].tobytes())
+    assert m["domain_decomposed"] and (shape[m["dd_dim"]] - 1) // m["dd_size"] + 1 >= 2
+    buf = hbuf if where == "host" else torch.from_numpy(hbuf).cuda()
+    plain = _np(hl.decompress(buf[:C], config=cfg))
+    out = hl.decompress_masked(buf, config=cfg)
+    assert isinstance(out, np.ndarray) == (where == "host")
+    out = _np(out)
+    assert out.dtype == dtype and out.shape == shape
+    assert np.all(mm.int_view(out)[mask] == mm.int_view(np.array([-9999.0], dtype=dtype))[0])
+    assert np.array_equal(mm.int_view(out)[~mask], mm.int_view(plain)[~mask])
+    got_mask = hl.decompress_mask(buf, config=cfg)
+    assert got_mask.dtype in (np.bool_, torch.bool) and np.array_equal(_np(got_mask), mask)
+    for reader in (hl.decompress_masked, hl.decompress_mask):
+        with pytest.raises(mgard_amd.MgardHipError, match="domain-decomposed"):
+            reader(buf, config=cfg, level=0)
+
+
+@pytest.mark.gpu
 def test_kind_selection():
     """The lossless record of dictionary 256 carries 3136 bytes before its first code unit (24 + 16 chunks' table + 8
     + the decodebook's 8 (128 + 256) + 16), so at 35904 elements (4488 packed bytes) kind 1 can win only below 2.4
