@@ -468,6 +468,12 @@ int mgh_profile_read(mgh_hierarchy *h, const char **names, double *total_ms, uin
 #define MGH_IPK_PLAN_FIELDS 16
 int mgh_debug_ipk_plans_read(mgh_hierarchy *h, long long *out, int cap, int reset);
 
+/* Test aid (no reference counterpart): the solves in verified chunks (family Spec) recompute every
+ * chunk whose start did not meet the end of the chunk before it, and count those chunks. Waits for
+ * the device, then writes to *out the chunks repaired on this hierarchy since it was created or
+ * since the last read with reset != 0; 0 if no such solve has run yet. */
+int mgh_debug_spec_repairs_read(mgh_hierarchy *h, uint64_t *out, int reset);
+
 /* Test aid (no reference counterpart): while profiling is enabled on a hierarchy, every level that
  * goes through the planner of the fused level passes (mgard_amd/csrc/fused_plan.hpp) leaves one
  * record, the first 512 of them since the last reset. A record is MGH_FUSED_PLAN_FIELDS values: size

@@ -34,7 +34,7 @@ SYMBOLS = [
     "mgh_recompose_to_level", "mgh_dequantize_recompose_to_level",
     "mgh_dequantize_recompose_sym16_to_level", "mgh_level_nodes",
     "mgh_level_box_from_linear", "mgh_dequantize_recompose_linear_to_level",
-    "mgh_refine_level", "mgh_debug_ipk_plans_read", "mgh_debug_fused_plans_read",
+    "mgh_refine_level", "mgh_debug_ipk_plans_read", "mgh_debug_spec_repairs_read", "mgh_debug_fused_plans_read",
     "mgh_prolong", "mgh_debug_prolong_plan",
     "mgh_prolong_window", "mgh_prolong_window_strided", "mgh_debug_prolong_window_ranges",
     "mgh_debug_prolong_window_plan",
@@ -174,6 +174,7 @@ def load_library():
     L.mgh_profile_read.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(C.c_double), u64p,
                                    C.c_int, C.c_int]
     L.mgh_debug_ipk_plans_read.argtypes = [vp, i64p, C.c_int, C.c_int]
+    L.mgh_debug_spec_repairs_read.argtypes = [vp, u64p, C.c_int]
     L.mgh_debug_fused_plans_read.argtypes = [vp, i64p, C.c_int, C.c_int]
     L.mgh_outlier_restore.argtypes = [vp, u64, vp, vp, u64, vp]
     L.mgh_level_linearize.argtypes = [vp, vp, vp, C.c_int, vp, vp, u64, u64, vp]
@@ -1043,6 +1044,13 @@ class Hierarchy:
             r["m"] = (r.pop("m0"), r.pop("m1"), r.pop("m2"))
             out.append(r)
         return out
+
+    def spec_repairs(self, reset=True):
+        """Chunks that the solves in verified chunks (family Spec of ipk_plans) had to recompute on this
+        hierarchy since it was created or since the last read that reset the count. Waits for the device."""
+        n = C.c_uint64(0)
+        _check(load_library().mgh_debug_spec_repairs_read(self._h, C.byref(n), int(reset)))
+        return int(n.value)
 
     # ---- per-kernel timing (HIP events on the launch stream) ----
     def profile(self, enable=True, only=None):

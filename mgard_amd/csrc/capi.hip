@@ -4069,6 +4069,23 @@ int mgh_debug_ipk_plans_read(mgh_hierarchy *h, long long *out, int cap, int rese
   return n;
 }
 
+int mgh_debug_spec_repairs_read(mgh_hierarchy *h, uint64_t *out, int reset) {
+  if (!h || !out) return fail(MGH_ERR_INVALID_ARGUMENT, "null argument");
+  *out = 0;
+  return with_type(h, [&](auto t) {
+    auto *ds = DS<decltype(t)>(h);
+    if (!ds->spec_fixed) return (int)MGH_SUCCESS;  // (no solve in verified chunks so far)
+    // (the solves ran on a stream of the caller's: wait for the device, as mgh_profile_read does)
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipDeviceSynchronize());
+    unsigned long long v = 0;
+    HIP_TRY(hipMemcpy(&v, ds->spec_fixed, sizeof v, hipMemcpyDeviceToHost));
+    if (reset) HIP_TRY(hipMemset(ds->spec_fixed, 0, sizeof v));
+    *out = v;
+    return (int)MGH_SUCCESS;
+  });
+}
+
 int mgh_debug_fused_plans_read(mgh_hierarchy *h, long long *out, int cap, int reset) {
   if (!h || (cap > 0 && !out) || cap < 0) return fail(MGH_ERR_INVALID_ARGUMENT, "null argument");
   const int n = (int)h->fused_log.size();

@@ -1,7 +1,9 @@
 // Which kernel solves a tridiagonal (Thomas) system along one axis of a compact box, and with which
 // launch parameters: the ONE place where that choice is made. Host-only and free of HIP, so that
 // the choice can be compiled by a plain C++ compiler and pinned by the CPU suite
-// (tests/test_ipk_plan_cpu.py); capi.hip's ipk_launch makes the plan and dispatches on it.
+// (tests/test_ipk_plan_cpu.py; per family on small arrays: tests/ipk_family_cases.py and
+// tests/ipk_stream_cases.py, which the GPU suite holds against the plan log); capi.hip's ipk_launch
+// makes the plan and dispatches on it.
 // IpkKernel lists the families in the order in which ipk_plan() considers them.
 #pragma once
 #include <algorithm>
@@ -28,7 +30,7 @@ struct IpkTuning {
   uint32_t spec_max = 16384;  // MGH_IPK_SPEC_MAX: most pencils of a solve whose pencils do not fit LDS that still run in verified chunks
   int chunk = 1;    // MGH_IPK_CHUNK: the LDS-staged solve of contiguous pencils shares a tile's sweeps between the four waves (thomas_chunked: chunks verified against the sequential sweep)
   int chunk_k = 0;  // MGH_IPK_CHUNK_K: warm-up length of a chunk (0 = from the tables, chunk_warmup_need; small values make the verification fail and exercise the fall-back)
-  int chunk_need = 0;  // warm-up length that the Thomas tables of this hierarchy need (set with the tables)
+  int chunk_need = 0;  // warm-up length that the Thomas tables of this hierarchy need (set with the tables; stays 0 for D > 3)
   uint32_t w = 64;             // MGH_IPK_W: widest solver wave of the streaming Thomas solves
   size_t wpc = 8;              // MGH_IPK_WPC: most one-wave solver workgroups per CU the host plans with
   int kr16 = 1;                // MGH_IPK_KR16: 16 register-resident batches for float pencils of 512+ elements
@@ -200,7 +202,8 @@ inline IpkPlan ipk_plan(const IpkTuning &t, size_t elem_size, int axis, const ui
       const size_t tiles = ((size_t)npencil + 63) / 64;
       // (a level with fewer than two tiles per CU is served better by the LDS-staged kernels, whose
       // four waves per tile stream it in and out: 129^3, 261 tiles, 18.8 vs 16.1 us)
-      // (MGH_IPK_DMA_MIN: that threshold in tiles, 0 in the tests that run this kernel on small shapes)
+      // (MGH_IPK_DMA_MIN: that threshold in tiles, 0 in the tests that run this kernel on small shapes: the
+      // solves that get here, not the f- and c-solve of a fused level whose planes fit LDS -- tests/ipk_family_cases.py)
       // (round 6: short pencils -- four or more tiles per CU -- also when the level needs up to
       // MGH_IPK_DMA_ROUNDS rounds of resident workgroups: the 8 x 512^3 slab's 5168 tiles of
       // 257-element pencils, ipk_c 242 -> 213 us, ipk_r 204 -> 190 us against k_ipk_stream; long

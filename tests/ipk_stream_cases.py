@@ -35,7 +35,9 @@ CONTIG = dict(CU1, MGH_IPK_CHUNK="0", MGH_IPK_CONTIG="2")  # (not the chunked LD
 # environment -> members of IpkTuning (capi.hip: ipk_tuning_from_env), as tests/cpp/ipk_plan_dump.cpp names them
 SWITCH_MEMBER = {"MGH_IPK_PLAN_CU": "num_cu", "MGH_IPK_DMA": "dma", "MGH_IPK_DMA_MIN": "dma_min", "MGH_IPK_WPC": "wpc",
                  "MGH_IPK_W": "w", "MGH_IPK_KR16": "kr16", "MGH_IPK_CONTIG": "contig_rounds", "MGH_IPK_CHUNK": "chunk",
-                 "MGH_IPK_STREAM": "stream"}
+                 "MGH_IPK_STREAM": "stream", "MGH_IPK_SPEC": "spec", "MGH_IPK_SPEC_K": "spec_k",
+                 "MGH_IPK_SPEC_LONG": "spec_long", "MGH_IPK_SPEC_MAX": "spec_max", "MGH_IPK_CHUNK_K": "chunk_k",
+                 "MGH_IPK_DMA_ROUNDS": "dma_rounds"}
 NOT_THE_PLANNERS = ("MGH_FORCE_V1", "MGH_IPK_RANGE_MB")
 
 

@@ -913,21 +913,31 @@ def test_4d_long_march_class_with_odd_remainders():
                                    (12, 320, 9, 33)])
 def test_ipk_dma_on_small_shapes(shape, dt, monkeypatch):
     """k_ipk_dma (LDS-DMA front end of the strided Thomas solves) normally runs only on levels of
-    512+ tiles; MGH_IPK_DMA_MIN=0 puts every float level whose pencils are long enough (160+
-    elements) on it: LDS parts of 1 ... 97 rows (walked singly / in batches / none), the four-rows-
-    per-instruction DMA with its overlapping tail, tiles that straddle a plane or end the array
-    (one row per instruction), a last tile of a single pencil, AddND (+) and SubtractND (-) fused.
-    Decomposition and recomposition bit-identical to the oracle."""
+    512+ tiles; MGH_IPK_DMA_MIN=0 puts every float solve that reaches the planner with pencils long
+    enough (160+ elements) on it: LDS parts of 1 ... 97 rows (walked singly / in batches / none), the
+    four-rows-per-instruction DMA with its overlapping tail, a last tile of a single pencil, AddND (+)
+    and SubtractND (-) fused. On the fused route only the r-solve reaches the planner while a coarse
+    plane fits LDS, so the two shapes whose long pencils lie along axis 1 -- tiles that straddle a
+    plane, one row per instruction -- run with MGH_FORCE_V1=1. The plan log must show a Dma solve for
+    every shape (tests/ipk_family_cases.py pins the solves one by one). Decomposition and
+    recomposition bit-identical to the oracle."""
     torch, mg = _gpu()
     monkeypatch.setenv("MGH_IPK_DMA_MIN", "0")
+    if shape in ((40, 330, 70), (19, 321, 130)):  # (r-solves of 21 and 10 elements: Dma is their c-solve)
+        monkeypatch.setenv("MGH_FORCE_V1", "1")
     u = smooth_field(shape, dt, noise=3e-3)
     h = mg.Hierarchy(shape, dt)
+    h.profile(True)
     o = oracle.Hierarchy(shape, dt)
     ref = o.decompose(u)
     c = h.decompose(torch.from_numpy(u).cuda())
     assert_bit_equal(c.cpu().numpy(), ref, "decompose")
     back = h.recompose(c)
     assert_bit_equal(back.cpu().numpy(), o.recompose(ref), "recompose")
+    dma = [r for r in h.ipk_plans() if r["family"] == "Dma"]
+    assert dma, "no solve of %r ran k_ipk_dma" % (shape,)
+    if len(shape) == 3:
+        assert {r["axis"] for r in dma} == ({1} if shape[1] > shape[0] else {0})
     h.close()
 
 
@@ -1022,8 +1032,9 @@ def test_long_contiguous_pencils_are_solved_in_verified_chunks(shape, dt, nonuni
     from a wrong state a warm-up length in front of their first element; every chunk's start is then
     compared bit for bit with the end of the chunk before it and recomputed where they differ
     (kernels_ipk_spec.hpp). The result must be the sequential sweep's (IPKFunctor.h:111-149) whatever the
-    warm-up length: default, 2 and 9 (nearly every chunk fails the comparison and is repaired), and with
-    the one-lane-per-pencil kernel (MGH_IPK_SPEC=0)."""
+    warm-up length: default, 2 and 9 (meant to make chunks fail the comparison; that the repair then runs is
+    observed in tests/test_gpu_ipk_families.py through Hierarchy.spec_repairs, not here), and with the
+    one-lane-per-pencil kernel (MGH_IPK_SPEC=0)."""
     torch, mg = _gpu()
     for k, v in env.items():
         monkeypatch.setenv(k, v)
@@ -1053,21 +1064,37 @@ def test_tiles_in_lds_are_solved_in_verified_chunks(shape, dt, nonuniform, env, 
     length in front of it, every quarter's start is compared bit for bit with the end of the quarter
     before it, and a tile with a mismatch is loaded again and solved by one lane per pencil. The result
     must be the sequential sweep's (IPKFunctor.h:111-149) whatever the warm-up length: the one derived
-    from the tables, 3, 5 and 12 (most tiles fail the comparison and take the second pass), with the
-    kernels that do not chunk, and on the unfused path (MGH_FORCE_V1: one solve per axis at every level,
-    where the fused path solves f and c of the small levels in one plane kernel)."""
+    from the tables, 3, 5 and 12 (most tiles fail the comparison and take the second pass), and with the
+    kernels that do not chunk. The coarse planes of the 3-D shapes fit LDS, where the fused route solves f
+    and c in one plane kernel and never asks the planner: every 3-D row with MGH_IPK_CHUNK=1 runs with
+    MGH_FORCE_V1=1 (one solve per axis at every level); the 4-D shape gets there on the fused route, but only with MGH_IPK_CHUNK_K: a 4-D
+    hierarchy derives no warm-up length from its tables. Wherever MGH_IPK_CHUNK=1 the plan log must show
+    LdsContigChunked solves with the warm-up length asked for -- without MGH_IPK_CHUNK_K the 4-D shape
+    excepted, and 96 x 300 x 128 doubles, whose pencils of 65 are shorter than twice the 40 their tables need
+    (tests/ipk_family_cases.py has the double rows) -- and none with MGH_IPK_CHUNK=0."""
     torch, mg = _gpu()
     for k, v in env.items():
         monkeypatch.setenv(k, v)
+    if len(shape) == 3 and env["MGH_IPK_CHUNK"] == "1":
+        monkeypatch.setenv("MGH_FORCE_V1", "1")
     coords = nonuniform_coords(shape, dt) if nonuniform else None
     u = smooth_field(shape, dt, noise=1e-2)
     h = mg.Hierarchy(shape, dt, coords=coords)
+    h.profile(True)
     o = oracle.Hierarchy(shape, dt, coords=coords)
     ud = torch.from_numpy(u).cuda()
     c = h.decompose(ud)
     ref = o.decompose(u)
     assert_bit_equal(c.cpu().numpy(), ref, "decompose %r %r" % (shape, env))
     assert_bit_equal(h.recompose(c).cpu().numpy(), o.recompose(ref), "recompose %r %r" % (shape, env))
+    chunked = [r for r in h.ipk_plans() if r["family"] == "LdsContigChunked"]
+    if env["MGH_IPK_CHUNK"] == "0":
+        assert not chunked
+    elif "MGH_IPK_CHUNK_K" in env or (len(shape) == 3 and shape != (96, 300, 128)):
+        assert chunked, "no solve of %r ran the chunked kernel" % (shape,)
+        assert all(r["axis"] == 2 and r["n"] >= 64 and r["K"] <= r["n"] // 2 for r in chunked)
+        if "MGH_IPK_CHUNK_K" in env:
+            assert {r["K"] for r in chunked} == {int(env["MGH_IPK_CHUNK_K"])}
     h.close()
 
 

@@ -38,7 +38,8 @@ ROUTES = {
     "box": ((5, 5, 5), np.float32, False, {}),
     "thin": ((5000, 5, 7), np.float32, False, {}),
     "ipk-stream": (_IPK["shape"], np.float64, _IPK["nonuniform"], _IPK["env"]),
-    "ipk-dma": ((40, 330, 70), np.float32, False, {"MGH_IPK_DMA_MIN": "0"}),
+    # (the r-solve of the top level, 201 x 16 x 26, is a k_ipk_dma launch: test_the_ipk_dma_route_launches_k_ipk_dma)
+    "ipk-dma": ((400, 30, 50), np.float32, False, {"MGH_IPK_DMA_MIN": "0"}),
     "fused4": ((8, 66, 70, 129), np.float32, False, {}),
     "nd5": ((3, 4, 5, 6, 7), np.float64, False, {}),
 }
@@ -752,6 +753,21 @@ def _run_case(name, route, stream, monkeypatch):
 @pytest.mark.parametrize("name,route", PAIRS, ids=["%s-%s" % p for p in PAIRS])
 def test_entry_point_in_stream_order(name, route, monkeypatch):
     _run_case(name, route, _side_stream(), monkeypatch)
+
+
+def test_the_ipk_dma_route_launches_k_ipk_dma(monkeypatch):
+    """What the "ipk-dma" route is there for: the plan log of its hierarchy shows the r-solve of the top level as
+    a Dma solve, adding in decompose and subtracting in recompose. (On the fused route the f- and c-solve of a
+    box whose planes fit LDS never reach k_ipk_dma, whatever MGH_IPK_DMA_MIN says.)"""
+    c = Ctx("ipk-dma", _side_stream(), monkeypatch)
+    try:
+        c.h.profile(True)
+        _case_decompose(c)
+        _case_recompose(c)
+        dma = {(r["axis"], r["m"], r["add"]) for r in c.h.ipk_plans() if r["family"] == "Dma"}
+        assert dma == {(0, (201, 16, 26), +1), (0, (201, 16, 26), -1)}, dma
+    finally:
+        c.close()
 
 
 @pytest.mark.parametrize("name", [n for n, _, routes in CASE_TABLE if "fused3" in routes])

@@ -26,8 +26,9 @@ resident workgroups for w = 64 / 48 / 32 / 16: tiles of 65792 / 49344 / 32896 / 
 2 rounds. Not Spec (66049 > 64 pencils), chunk off, not Dma (axis 2), no KR = 16 (257 / 16 < 32), no
 KR = 8 (2 rounds < MGH_IPK_CONTIG = 4): k_ipk_lds_contig<float, false>, grid ceil(66049 / 48) = 1377
 of 256 threads, P = 48. The case is in tools/ipk_trace_case.py for the next recording.
-Not pinned by any row: the Thread family with nbatch > 1 (one call per box; the case
-thread_batches_4d of tools/ipk_trace_case.py is meant to record it).
+Not pinned by any row here: the Thread family with nbatch > 1 (one call per box; the case
+thread_batches_4d of tools/ipk_trace_case.py is meant to record it). tests/ipk_family_cases.py pins it
+on a small 4-D array ("thread-4d-batches"), on the CPU and through the plan log on the GPU.
 
 Shapes (`from`): 512^3 f32 and f64 (non-uniform), 1024^3 f32, the 8 x 512^3 4-D slab, 129^3, 257^3,
 16395 x 64 x 64, a 2^24-element 1-D array, 4194304 x 9, 100 x 100 x 6000, 64^4, 8 x 8 x 64^3; with
