@@ -269,6 +269,40 @@ inline compress_status_type decompress_layers(const std::vector<const void *> &c
   return detail::status(mgh_decompress_layers((int)compressed_data.size(), compressed_data.data(), compressed_size.data(),
                                               &c, &decompressed_data, output_pre_allocated ? 1 : 0));
 }
+// EXTENSION: mgh_compress_level_layers: compress_layers with level-linearised records (reorder = 1 whatever
+// config.reorder says), so that a reader takes level L of layer k from the head of that layer's record
+// (LevelLayersReader, decompress_level_layers). Layer 0 is compress(tols[0], reorder = 1)'s container.
+inline compress_status_type compress_level_layers(DIM D, data_type dtype, std::vector<SIZE> shape,
+                                                  const std::vector<double> &tols, double s, error_bound_type mode,
+                                                  const void *original_data, std::vector<void *> &compressed_data,
+                                                  std::vector<size_t> &compressed_size, std::vector<const Byte *> coords,
+                                                  HighLevelConfig config, bool output_pre_allocated) {
+  if (shape.size() != D) return compress_status_type::Failure;
+  if (output_pre_allocated && (compressed_data.size() != tols.size() || compressed_size.size() != tols.size()))
+    return compress_status_type::Failure;
+  if (!output_pre_allocated) {
+    compressed_data.assign(tols.size(), nullptr);
+    compressed_size.assign(tols.size(), 0);
+  }
+  const mgh_config c = detail::to_c(config);
+  std::vector<const void *> cp(coords.begin(), coords.end());
+  return detail::status(mgh_compress_level_layers(D, (int)dtype, shape.data(), (int)tols.size(), tols.data(), s, (int)mode,
+                                                  original_data, compressed_data.data(), compressed_size.data(),
+                                                  cp.empty() ? nullptr : cp.data(), &c, output_pre_allocated ? 1 : 0));
+}
+// ... and its one-shot reader (mgh_decompress_level_layers): level `level` of the array after layers
+// 0 .. size() - 1, every layer read up to that level. The output is dense in the level's shape
+// (mgh_infer_level_shape).
+inline compress_status_type decompress_level_layers(const std::vector<const void *> &compressed_data,
+                                                    const std::vector<size_t> &compressed_size, int level,
+                                                    void *&decompressed_data, HighLevelConfig config,
+                                                    bool output_pre_allocated) {
+  if (compressed_data.size() != compressed_size.size()) return compress_status_type::Failure;
+  const mgh_config c = detail::to_c(config);
+  return detail::status(mgh_decompress_level_layers((int)compressed_data.size(), compressed_data.data(),
+                                                    compressed_size.data(), level, &c, &decompressed_data,
+                                                    output_pre_allocated ? 1 : 0));
+}
 // EXTENSION: mgh_compress_masked. compress of an array whose NaN / +-Inf (spec.flags & MGH_MASK_NONFINITE) and / or
 // elements equal to spec.fill_value (MGH_MASK_VALUE) do not count: [container of the filled array][mask record][footer].
 // The first masked_info().container_size bytes open in every reader; the bound holds at every valid position.
@@ -559,9 +593,41 @@ public:
   compress_status_type data(void *&out, bool output_pre_allocated) {
     return detail::status(mgh_layers_data(p_, &out, output_pre_allocated ? 1 : 0));
   }
+  // (mgh_layers_data_level: the array of `level` of the hierarchy only)
+  compress_status_type data(int level, void *&out, bool output_pre_allocated) {
+    return detail::status(mgh_layers_data_level(p_, level, &out, output_pre_allocated ? 1 : 0));
+  }
 
 private:
   mgh_layers *p_ = nullptr;
+};
+// EXTENSION: the stateful reader of precision layers in level order (mgh_level_layers): layer 0 up to `level`
+// at construction, add() the next layer up to a level, extend() a layer deeper, data(level) whenever an
+// array is wanted. depth(k) never exceeds depth(k - 1); data needs level <= depth(0).
+class LevelLayersReader {
+public:
+  LevelLayersReader(const void *layer0, size_t size, int level, HighLevelConfig config = HighLevelConfig()) {
+    const mgh_config c = detail::to_c(config);
+    check(mgh_level_layers_open(&p_, layer0, size, &c, level), "LevelLayersReader");
+  }
+  ~LevelLayersReader() { mgh_level_layers_close(p_); }
+  LevelLayersReader(const LevelLayersReader &) = delete;
+  LevelLayersReader &operator=(const LevelLayersReader &) = delete;
+  int count() const { return mgh_level_layers_count(p_); }
+  int depth(int k) const { return mgh_level_layers_depth(p_, k); }
+  double tolerance(int k) const { return mgh_level_layers_tolerance(p_, k); }
+  compress_status_type add(const void *layer, size_t size, int level) {
+    return detail::status(mgh_level_layers_add(p_, layer, size, level));
+  }
+  compress_status_type extend(int k, const void *layer, size_t size, int level) {
+    return detail::status(mgh_level_layers_extend(p_, k, layer, size, level));
+  }
+  compress_status_type data(int level, void *&out, bool output_pre_allocated) {
+    return detail::status(mgh_level_layers_data(p_, level, &out, output_pre_allocated ? 1 : 0));
+  }
+
+private:
+  mgh_level_layers *p_ = nullptr;
 };
 inline compress_status_type decompress(const void *compressed_data, size_t compressed_size,
                                        void *&decompressed_data, std::vector<SIZE> &shape,

@@ -347,6 +347,8 @@ int mgh_dequantize_recompose_linear_to_level(mgh_hierarchy *h, int64_t *d_linear
                                              int prep_huffman, const uint64_t *d_outlier_idx,
                                              const int64_t *d_outlier_val, uint64_t outlier_count,
                                              int level, void *d_out, void *stream);
+/* (The three low-level calls of the precision layers in level order -- mgh_quantize_residual_linear,
+ * mgh_dequantize_add_linear, mgh_recompose_linear_to_level -- are declared in mgard_hip_level_layers.h.) */
 /* ONE LEVEL STEP of the same loop, for a caller that keeps the result of a coarser level and wants
  * the next one (DataRefactor::Recompose(data, start_level, stop_level, queue) with
  * start_level = level - 1, stop_level = level). level = 1 ... l_target.

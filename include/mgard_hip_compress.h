@@ -226,6 +226,24 @@ int mgh_compress_layers(int D, int dtype, const uint64_t *shape, int ntol, const
                         size_t *compressed_size /* [ntol] */, const void *const *coords, const mgh_config *config,
                         int output_pre_allocated);
 
+/* ---- Precision layers in LEVEL ORDER: refinable by tolerance AND by resolution (extension) -------------
+ * mgh_compress_layers with reorder = 1 records: the same chain q_k, r_{k+1}, the same arguments, outputs and
+ * failure at layer k, but every record is level-linearised WHATEVER config->reorder says, so that a reader
+ * takes level L of layer k from the head of that layer's record (mgh_level_layers_*). compressed_data[0]
+ * is the container mgh_compress(tols[0]) writes with config->reorder = 1 (up to the order of its outlier
+ * list); every layer is an ordinary container that mgh_decompress, mgh_decompress_level and
+ * mgh_progressive_* open. The quantizing step is mgh_quantize_residual_linear (int64 integers: the
+ * single-pass 16-bit encoder is not used, and its limits on huff_block_size do not apply).
+ * MGH_ERR_INVALID_ARGUMENT as for mgh_compress_layers, minus config->reorder: ntol, the tolerances, a
+ * configuration that decomposes the domain, huff_dict_size odd or outside 2..16384, arrays of 2^32 elements
+ * and more, and "compress_level_layers: layer k would be stored raw". Device memory: the coefficient array
+ * twice and the integers twice (8 bytes an element in a buffer of the pipeline and in one of the
+ * hierarchy). mgh_last_compress_stats: decompositions 1, records ntol. */
+int mgh_compress_level_layers(int D, int dtype, const uint64_t *shape, int ntol, const double *tols, double s,
+                              int error_bound_type, const void *original_data, void **compressed_data /* [ntol] */,
+                              size_t *compressed_size /* [ntol] */, const void *const *coords, const mgh_config *config,
+                              int output_pre_allocated);
+
 /* What the last WRITING call of the calling thread did (mgh_compress, mgh_compress_budget,
  * mgh_compress_target, mgh_compress_ladder, mgh_compress_layers; thread-local; zeros before the first call; a failed call
  * leaves what it had counted). */
@@ -671,6 +689,48 @@ void mgh_layers_close(mgh_layers *p);
 int mgh_decompress_layers(int nlayers, const void *const *compressed_data /* [nlayers] */,
                           const size_t *compressed_size /* [nlayers] */, const mgh_config *config,
                           void **decompressed_data, int output_pre_allocated);
+/* The coefficients the handle holds recomposed to `level` (0 .. l_target) only: mgh_recompose_to_level of
+ * the accumulator, the dense array of level_shape(level), placed as mgh_layers_data places its output. No
+ * fewer bytes were read for it (the layers are reorder = 0 records); it answers the question
+ * mgh_level_layers_data answers. */
+int mgh_layers_data_level(mgh_layers *p, int level, void **data, int output_pre_allocated);
+
+/* ---- Reader of precision layers in level order (EXTENSION; the containers of mgh_compress_level_layers) --
+ * A handle keeps the coefficients in LEVEL-LINEARISED order on the device (one array of the data's type), a
+ * decode buffer sized by the largest window decoded so far, and per layer its header and its DEPTH: the
+ * level up to which it has been added. With N_l = prod(level_shape(l)):
+ *   open(buf0, level)      layer 0 up to `level`: the ceil(N_level / huff_block_size) leading chunks of its
+ *                          record are decoded, the window [0, N_level) is stored.
+ *   add(buf, level)        the NEXT layer, level <= depth of the last one: a prefix decode, added.
+ *   extend(k, buf, level)  layer k deeper: depth[k] < level, and level <= depth[k - 1] for k > 0. Decodes
+ *                          from the chunk that holds N_depth[k] (that boundary chunk may be decoded a second
+ *                          time, nothing else is); the window [N_depth[k], N_level) is stored for k == 0 and
+ *                          added otherwise. The container must be the one recorded for layer k (header,
+ *                          tolerance, dictionary and chunk size).
+ *   data(level)            level <= depth[0]: mgh_recompose_linear_to_level of the head [0, N_level) into
+ *                          an array of level_shape(level) in the memory space of layer 0's container, or
+ *                          the caller's buffer. The handle stays as it was.
+ * Depths are non-increasing in k: a finer layer alone on a level would be a residual with nothing under
+ * it, so on every level the coefficients are the sum of a leading run of layers. MGH_ERR_INVALID_ARGUMENT,
+ * with the handle unchanged and before the coefficients are touched: a reorder = 0 container, a
+ * domain-decomposed one, a RAW record, a header that is not layer 0's (shape, data type, coordinates,
+ * bound type, s, norm), a tolerance that is not below the last layer's, a level outside the rules above.
+ * count (-1 for NULL), depth(k) (-1 for a bad k), tolerance(k) (0 for a bad k). The containers are not
+ * kept. mgh_last_decompress_stats: the chunks decoded and bytes moved by the last open / add / extend.
+ * mgh_decompress_level_layers: open, add ... add, data, close with every layer at `level`; nlayers 1..64. */
+typedef struct mgh_level_layers mgh_level_layers;
+int mgh_level_layers_open(mgh_level_layers **out, const void *compressed_data, size_t compressed_size,
+                          const mgh_config *config, int level);
+int mgh_level_layers_add(mgh_level_layers *p, const void *compressed_data, size_t compressed_size, int level);
+int mgh_level_layers_extend(mgh_level_layers *p, int k, const void *compressed_data, size_t compressed_size, int level);
+int mgh_level_layers_count(const mgh_level_layers *p);
+int mgh_level_layers_depth(const mgh_level_layers *p, int k);
+double mgh_level_layers_tolerance(const mgh_level_layers *p, int k);
+int mgh_level_layers_data(mgh_level_layers *p, int level, void **data, int output_pre_allocated);
+void mgh_level_layers_close(mgh_level_layers *p);
+int mgh_decompress_level_layers(int nlayers, const void *const *compressed_data /* [nlayers] */,
+                                const size_t *compressed_size /* [nlayers] */, int level, const mgh_config *config,
+                                void **decompressed_data, int output_pre_allocated);
 
 /* ---- Arrays with missing values (EXTENSION; mgh_mask_* of mgard_hip.h) -------------------------------
  * mgh_compress of an array whose NaN / +-Inf (MGH_MASK_NONFINITE) and / or whose elements equal to

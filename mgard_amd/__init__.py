@@ -41,6 +41,9 @@ SYMBOLS = [
     "mgh_compare",
     "mgh_mask_scan", "mgh_mask_fill", "mgh_mask_restore",
 ]
+# declared in include/mgard_hip_level_layers.h (which mgard_hip.h includes): the low-level calls of the precision
+# layers in level order
+LEVEL_LAYERS_SYMBOLS = ["mgh_quantize_residual_linear", "mgh_dequantize_add_linear", "mgh_recompose_linear_to_level"]
 # entry points of the library that no public header declares yet (trailing underscore): bound here for
 # mask_sample / compare_masked and their tests
 INTERNAL_SYMBOLS = ["mgh_mask_sample_", "mgh_compare_masked_"]
@@ -179,6 +182,11 @@ def load_library():
     L.mgh_outlier_restore.argtypes = [vp, u64, vp, vp, u64, vp]
     L.mgh_level_linearize.argtypes = [vp, vp, vp, C.c_int, vp, vp, u64, u64, vp]
     L.mgh_recompose_to_level.argtypes = [vp, vp, C.c_int, vp, vp]
+    L.mgh_recompose_linear_to_level.argtypes = [vp, vp, C.c_int, vp, vp]
+    L.mgh_quantize_residual_linear.argtypes = [vp, vp, C.c_int, C.c_double, C.c_double, C.c_double, u64, vp, vp, vp, vp,
+                                               u64, vp, vp]
+    L.mgh_dequantize_add_linear.argtypes = [vp, vp, u64, u64, C.c_int, C.c_double, C.c_double, C.c_double, u64, C.c_int,
+                                            vp, vp, u64, C.c_int, vp, vp]
     L.mgh_dequantize_recompose_to_level.argtypes = [vp, vp, C.c_int, C.c_double, C.c_double, C.c_double,
                                                     u64, C.c_int, vp, vp, u64, C.c_int, vp, vp]
     L.mgh_dequantize_recompose_sym16_to_level.argtypes = [vp, vp, C.c_int, C.c_double, C.c_double,
@@ -823,6 +831,55 @@ class Hierarchy:
             C.c_void_p(outlier_idx.data_ptr() if n else 0), C.c_void_p(outlier_val.data_ptr() if n else 0), n,
             int(first), C.c_void_p(acc.data_ptr()), _stream()))
         return acc
+
+    def quantize_residual_linear(self, coeff, ebtype, tol, s, norm, dict_size=8192, outlier_cap=None, out=None):
+        """mgh_quantize_residual_linear: (integers, outlier_idx, outlier_val, residual) -- the level-linearised
+        integers (flat int64) and the outlier pairs at linearised positions that quantize(prep_huffman=True) +
+        level_linearize(outlier_idx=...) give, and quantize_symbols_residual's residual in array order. `out`: a
+        dense tensor for the residual; it may be `coeff` itself."""
+        import torch
+        cap = self.total if outlier_cap is None else int(outlier_cap)
+        lin = torch.empty(self.total, dtype=torch.int64, device=coeff.device)
+        if out is None:
+            out = torch.empty(self.shape, dtype=self.torch_dtype, device=coeff.device)
+        assert out.is_cuda and out.is_contiguous() and out.numel() == self.total, "bad tensor"
+        assert out.dtype == self.torch_dtype and out.device.index == self.device, "bad tensor"
+        cnt, idx, val = self._outlier_bufs(cap)
+        _check(load_library().mgh_quantize_residual_linear(
+            self._h, self._chk(coeff), int(ebtype), tol, s, norm, int(dict_size), C.c_void_p(lin.data_ptr()),
+            C.c_void_p(cnt.data_ptr()), C.c_void_p(idx.data_ptr()), C.c_void_p(val.data_ptr()), cap,
+            C.c_void_p(out.data_ptr()), _stream()))
+        k = min(int(cnt.item()), cap)
+        return lin, idx[:k], val[:k], out
+
+    def dequantize_add_linear(self, window, first, acc, ebtype, tol, s, norm, dict_size=8192, prep_huffman=True,
+                              outlier_idx=None, outlier_val=None, store=False):
+        """mgh_dequantize_add_linear: `window` (contiguous int64, any view) holds the integers [first, first +
+        window.numel()) of the level-linearised array; `acc` (flat, total elements of the hierarchy's type) is the
+        whole accumulator in that order. Inside the window acc is stored (store=True) or added to; outside it
+        nothing is touched. The outliers of the window are written into `window`. Returns acc."""
+        import torch
+        assert window.is_cuda and window.dtype == torch.int64 and window.is_contiguous(), "bad tensor"
+        assert acc.is_cuda and acc.is_contiguous() and acc.numel() == self.total, "bad tensor"
+        assert acc.dtype == self.torch_dtype and acc.device.index == self.device, "bad tensor"
+        n = 0 if outlier_idx is None else int(outlier_idx.numel())
+        _check(load_library().mgh_dequantize_add_linear(
+            self._h, C.c_void_p(window.data_ptr()), int(first), int(window.numel()), int(ebtype), tol, s, norm,
+            int(dict_size), int(prep_huffman), C.c_void_p(outlier_idx.data_ptr() if n else 0),
+            C.c_void_p(outlier_val.data_ptr() if n else 0), n, int(store), C.c_void_p(acc.data_ptr()), _stream()))
+        return acc
+
+    def recompose_linear_to_level(self, acc, level, out=None):
+        """mgh_recompose_linear_to_level: the dense array of `level` from the head of a level-linearised coefficient
+        array (at least prod(level_shape(level)) elements are read, nothing behind them)."""
+        need = 1
+        for e in self.level_shape(level):
+            need *= int(e)
+        assert acc.is_cuda and acc.is_contiguous() and acc.dtype == self.torch_dtype and acc.numel() >= need, "bad tensor"
+        out = self._level_out(level, out, acc.device)
+        _check(load_library().mgh_recompose_linear_to_level(self._h, C.c_void_p(acc.data_ptr()), int(level),
+                                                            C.c_void_p(out.data_ptr()), _stream()))
+        return out
 
     def decompose_quantize_sym16(self, data, ebtype, tol, s, norm=0.0, dict_size=8192, outlier_cap=None):
         """mgh_decompose_quantize_sym16: (symbols uint16, outlier_idx, outlier_val, count, norm)."""

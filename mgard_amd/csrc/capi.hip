@@ -4,6 +4,7 @@
 // (reference include/mgard-x/DataRefactoring/MultiDimension/DataRefactoring.hpp:25-317)
 // over the HIP kernels in kernels_*.hpp.
 #include "../../include/mgard_hip.h"
+#include "../../include/mgard_hip_level_layers.h"
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -194,7 +195,9 @@ template <typename T> struct DeviceState {
   int t12_level = 0;               // t1 / t2 hold the sweeps of levels up to this one (0: not allocated)
   T *level_box = nullptr;          // compact coefficients of the corner box of a stop level (mgh_*_to_level; grown on demand)
   size_t level_box_elems = 0;
-  T *scratch_full = nullptr;       // lazily allocated full-size copy
+  T *lin_box = nullptr;            // mgh_recompose_linear_to_level: the compact box of the level out of the linearised head (grown on demand)
+  size_t lin_box_elems = 0;
+  T *scratch_full = nullptr;      // lazily allocated full-size copy
   // mgh_prolong_window: the window's part of two consecutive levels (grown on demand, sized by the
   // window), and on the shapes without a window kernel the full-grid array the window is cut from
   T *win[2] = {nullptr, nullptr};
@@ -492,6 +495,7 @@ template <typename T> void destroy_state(mgh_hierarchy *h) {
     (void)hipFree(ds->oh_val);
     (void)hipFree(ds->qbox);
     (void)hipFree(ds->level_box);
+    (void)hipFree(ds->lin_box);
     (void)hipFree(ds->spec_y);
     (void)hipFree(ds->spec_a);
     (void)hipFree(ds->spec_b);
@@ -3254,13 +3258,31 @@ int lin_box_units(const mgh_hierarchy *h, mgh::LinBox &B, int k, const uint32_t 
 
 // The compact corner box of `level` (dense in level_shape(level)) out of the first N_level integers
 // of a level-linearised array: k_box_from_linear, one wave per piece of a run of the stream.
-int box_from_linear(mgh_hierarchy *h, const int64_t *lin, int level, int64_t *box, hipStream_t st) {
+// E: int64_t for 8-byte elements (the integers; double coefficients), int32_t for 4-byte ones (float
+// coefficients) -- the permutation moves bits.
+template <typename E> int box_from_linear(mgh_hierarchy *h, const E *lin, int level, E *box, hipStream_t st) {
   mgh::LinMeta m{};
   mgh::LinBox B{};
   TRY(lin_box_begin(h, level, m, B));
   for (int j = 0; j <= level; j++) TRY(lin_box_units(h, B, j, m.lshape[j]));
   const unsigned grid = (unsigned)std::min<uint64_t>((B.unit0[level + 1] + 3) / 4, 256 * 32);
-  return launch(h, "box_from_linear", st, [&] { mgh::k_box_from_linear<<<grid, 256, 0, st>>>(m, B, lin, box); });
+  return launch(h, "box_from_linear", st, [&] { mgh::k_box_from_linear<E><<<grid, 256, 0, st>>>(m, B, lin, box); });
+}
+
+// mgh_recompose_linear_to_level: the compact box of `level` out of the head of a level-linearised
+// COEFFICIENT array (ds->lin_box, N_level elements), then the level loops of mgh_recompose_to_level on it
+// with the box's own dense strides -- level == l_target: the box is the whole array in array order, and
+// the body is mgh_recompose's.
+template <typename T>
+int recompose_linear_to_level_impl(mgh_hierarchy *h, const T *lin, int level, T *out, hipStream_t st) {
+  auto *ds = DS<T>(h);
+  using E = std::conditional_t<sizeof(T) == 8, int64_t, int32_t>;
+  TRY(grow(h, &ds->lin_box, &ds->lin_box_elems, (size_t)level_elems(h, level)));
+  TRY(box_from_linear<E>(h, reinterpret_cast<const E *>(lin), level, reinterpret_cast<E *>(ds->lin_box), st));
+  if (level == h->L) return recompose_impl<T>(h, ds->lin_box, dense_layout(h), out, dense_layout(h), st);
+  uint64_t ext[MGH_MAX_DIM];
+  for (int d = 0; d < h->D; d++) ext[d] = HH<T>(h)->level_shape[level][d];
+  return recompose_to_level_impl<T>(h, ds->lin_box, make_layout(h, ext, false), level, out, st);
 }
 
 // The shell of the compact box of `level` (dense in level_shape(level)) out of the level's own segment
@@ -3275,6 +3297,68 @@ int shell_from_linear(mgh_hierarchy *h, const int64_t *seg, int level, int64_t *
     TRY(lin_box_units(h, B, k, m.lshape[level - k], k == 1 && !fill_inner));
   const unsigned grid = (unsigned)std::min<uint64_t>((B.unit0[2] + 3) / 4, 256 * 32);
   return launch(h, "shell_from_linear", st, [&] { mgh::k_shell_from_linear<<<grid, 256, 0, st>>>(m, B, seg, box, inner); });
+}
+
+// ---- precision layers in level order -----------------------------------------
+// mgh_quantize_residual_linear: the four tables of the round trip, the int64 instance of the symbol
+// kernel into ds->qbox (array order, all of the array), then mgh_level_linearize's two kernels: the
+// integers into `lin`, the list's indices in place. The residual is dense, in array order.
+template <typename T>
+int quantize_residual_linear_impl(mgh_hierarchy *h, const T *coeff, Layout in, const Bound &b, double norm, uint64_t dict,
+                                  int64_t *lin, const QuantOut &qo, T *residual, hipStream_t st) {
+  auto *ds = DS<T>(h);
+  if (h->L + 1 > mgh::kLinMaxLevels + 1) return fail(MGH_ERR_INVALID_ARGUMENT, "too many levels");
+  unsigned grid;
+  TRY(stream_grid(h, kQsThreads, Vec16<T>::N, 0, 8, &grid));
+  TRY(ld_pack<T>(h, coeff, in, false, st));
+  QuantMeta qm;
+  TRY(upload_roundtrip_tables<T>(h, b, norm, qm, st));
+  const size_t total = h->total;
+  TRY(grow(h, &ds->qbox, &ds->qbox_elems, total));
+  HIP_TRY(hipMemsetAsync(qo.ocount, 0, sizeof(uint64_t), st));
+  TRY(launch(h, "quantize_residual_int64", st, [&] {
+    k_quantize_residual_int64<T><<<grid, kQsThreads, 0, st>>>(qm, total, coeff, ds->marks, ds->qr_tab, h->L + 1, (int)dict,
+                                                              ds->qbox, (unsigned long long *)qo.ocount, qo.oidx, qo.oval,
+                                                              (unsigned long long)qo.ocap, residual);
+  }));
+  mgh::LinMeta m{};
+  const int *marks = lin_meta(h, m);
+  const unsigned g1 = (unsigned)std::min<size_t>((total + 255) / 256, 256 * 32);
+  TRY(launch(h, "level_linearize", st, [&] {
+    mgh::k_level_linearize<int64_t, false><<<g1, 256, 0, st>>>(m, marks, total, ds->qbox, lin);
+  }));
+  if (!qo.ocap) return MGH_SUCCESS;
+  const unsigned g2 = (unsigned)std::max<size_t>(1, std::min<size_t>((std::min<size_t>(qo.ocap, total) + 255) / 256, 4096));
+  return launch(h, "linearize_indices", st, [&] {
+    mgh::k_linearize_indices<<<g2, 256, 0, st>>>(m, marks, total, qo.oidx, (const unsigned long long *)qo.ocount, 0ull,
+                                                 (unsigned long long)qo.ocap);
+  });
+}
+
+// mgh_dequantize_add_linear: the table of mgh_dequantize by its own upload, the outliers of the window
+// back into it, then one streaming launch of k_dequantize_add_linear over the window.
+template <typename T>
+int dequantize_add_linear_impl(mgh_hierarchy *h, int64_t *win, uint64_t first, uint64_t count, const QuantSpec &qs,
+                               bool store, T *acc, hipStream_t st) {
+  auto *ds = DS<T>(h);
+  const int nlev = h->L + 1;
+  if (nlev > kMaxLevels) return fail(MGH_ERR_INVALID_ARGUMENT, "too many levels");
+  LinOffsets off{};
+  for (int l = 0; l < nlev; l++) off.n[l] = (uint32_t)level_elems(h, l);
+  const size_t per_wg = (size_t)kQaThreads * Vec16<T>::N;
+  const unsigned grid = (unsigned)std::max<size_t>(1, std::min<size_t>((count + per_wg - 1) / per_wg, 8 * (size_t)h->num_cu));
+  TRY(upload_quantizers<T>(h, qs.ebtype, qs.tol, qs.s, qs.norm, false, st));
+  TRY(outliers_back(h, qs, "outlier_restore_window", st, k_outlier_restore_window, win, first, first + count));
+  const int64_t shift = qs.prep_huffman ? (int64_t)qs.dict_size / 2 : 0;
+  const int calc_vol = ds->qmeta.calc_vol;
+  return launch(h, "dequantize_add_linear", st, [&] {
+    if (store)
+      k_dequantize_add_linear<T, true><<<grid, kQaThreads, 0, st>>>(off, nlev, calc_vol, win, (uint32_t)first, (size_t)count,
+                                                                     ds->qz, shift, acc);
+    else
+      k_dequantize_add_linear<T, false><<<grid, kQaThreads, 0, st>>>(off, nlev, calc_vol, win, (uint32_t)first, (size_t)count,
+                                                                      ds->qz, shift, acc);
+  });
 }
 
 // ---- the reconstruction core ---------------------------------------------------------------------
@@ -3834,6 +3918,42 @@ int mgh_dequantize_add(mgh_hierarchy *h, int64_t *d_quantized, int error_bound_t
   });
 }
 
+int mgh_quantize_residual_linear(mgh_hierarchy *h, const void *d_coeff, int error_bound_type, double tol, double s,
+                                 double norm, uint64_t dict_size, int64_t *d_linear_out, uint64_t *d_outlier_count,
+                                 uint64_t *d_outlier_idx, int64_t *d_outlier_val, uint64_t outlier_capacity,
+                                 void *d_residual_out, void *stream) {
+  if (!h || !d_coeff || !d_linear_out || !d_residual_out) return fail(MGH_ERR_INVALID_ARGUMENT, "null argument");
+  const QuantOut qo{dict_size, 1, d_linear_out, nullptr, d_outlier_count, d_outlier_idx, d_outlier_val, outlier_capacity};
+  TRY(outlier_args(qo));
+  if (const char *bad = qsym_refusal(h->total, dict_size)) return fail(MGH_ERR_INVALID_ARGUMENT, bad);
+  HIP_TRY(hipSetDevice(h->device));
+  return with_type(h, [&](auto t) {
+    using T = decltype(t);
+    return quantize_residual_linear_impl<T>(h, (const T *)d_coeff, caller_layout(h, MGH_LD_IN), {error_bound_type, tol, s},
+                                            norm, dict_size, d_linear_out, qo, (T *)d_residual_out, (hipStream_t)stream);
+  });
+}
+
+int mgh_dequantize_add_linear(mgh_hierarchy *h, int64_t *d_linear_window, uint64_t first, uint64_t count,
+                              int error_bound_type, double tol, double s, double norm, uint64_t dict_size,
+                              int prep_huffman, const uint64_t *d_outlier_idx, const int64_t *d_outlier_val,
+                              uint64_t outlier_count, int store, void *d_acc_linear, void *stream) {
+  if (!h || !d_linear_window || !d_acc_linear) return fail(MGH_ERR_INVALID_ARGUMENT, "null argument");
+  if (prep_huffman && outlier_count && (!d_outlier_idx || !d_outlier_val))
+    return fail(MGH_ERR_INVALID_ARGUMENT, "null outlier list");
+  if (h->total == 0 || h->total >= ((uint64_t)1 << 32))
+    return fail(MGH_ERR_INVALID_ARGUMENT, "dequantize_add_linear: 1 .. 2^32 - 1 elements (32-bit index arithmetic)");
+  if (count == 0 || first >= h->total || count > h->total - first)
+    return fail(MGH_ERR_INVALID_ARGUMENT, "dequantize_add_linear: the window [first, first + count) leaves the array");
+  HIP_TRY(hipSetDevice(h->device));
+  const QuantSpec qs{error_bound_type, tol, s, norm, dict_size, prep_huffman, d_outlier_idx, d_outlier_val, outlier_count};
+  return with_type(h, [&](auto t) {
+    using T = decltype(t);
+    return dequantize_add_linear_impl<T>(h, d_linear_window, first, count, qs, store != 0, (T *)d_acc_linear,
+                                         (hipStream_t)stream);
+  });
+}
+
 int mgh_decompose_quantize_dn(mgh_hierarchy *h, const void *d_data, int error_bound_type,
                               double tol, double s, const void *d_norm, uint64_t num_subdomains,
                               uint64_t dict_size, int prep_huffman, int64_t *d_quantized,
@@ -3924,6 +4044,23 @@ int mgh_dequantize_recompose_linear_to_level(mgh_hierarchy *h, int64_t *d_linear
   TRY(level_arg(h, level));
   return reconstruct_entry(h, {ebtype, tol, s, norm, dict_size, prep_huffman, d_outlier_idx, d_outlier_val, outlier_count},
                            {IntSource::Linear, d_linear, nullptr}, {level, 0, nullptr, d_out, dense_layout(h)}, stream);
+}
+
+// The head of a level-linearised COEFFICIENT array (the accumulator of the level-ordered precision
+// layers) to the dense array of `level`: what mgh_recompose_to_level gives for the same coefficients
+// in array order, from the first N_level of them.
+int mgh_recompose_linear_to_level(mgh_hierarchy *h, const void *d_acc_linear, int level, void *d_out, void *stream) {
+  if (!h || !d_acc_linear || !d_out) return fail(MGH_ERR_INVALID_ARGUMENT, "null argument");
+  if (d_out == d_acc_linear) return fail(MGH_ERR_INVALID_ARGUMENT, "mgh_recompose_linear_to_level: d_out must not be d_acc_linear");
+  TRY(level_arg(h, level));
+  if (h->total >= ((uint64_t)1 << 32))
+    return fail(MGH_ERR_INVALID_ARGUMENT, "recompose_linear_to_level: at most 2^32 - 1 elements");
+  if (h->L + 1 > mgh::kLinMaxLevels + 1) return fail(MGH_ERR_INVALID_ARGUMENT, "too many levels");
+  HIP_TRY(hipSetDevice(h->device));
+  return with_type(h, [&](auto t) {
+    using T = decltype(t);
+    return recompose_linear_to_level_impl<T>(h, (const T *)d_acc_linear, level, (T *)d_out, (hipStream_t)stream);
+  });
 }
 
 // One level step: the dense nodal array of level - 1 and the level's own segment of a level-linearised

@@ -6,6 +6,7 @@
 //   self-describing container (format.hpp; Metadata.cpp:249-462).
 // Host code is C++; everything exported is extern "C" (include/mgard_hip_compress.h).
 #include "../../include/mgard_hip_compress.h"
+#include "../../include/mgard_hip_level_layers.h"
 
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
@@ -1967,12 +1968,12 @@ int encode_record(Lane &L, const LosslessJob &lj, const RecordSink &S, Again &&a
 // layer's "data" is no array a reader could take in its place): a record the RAW rule would store raw
 // ends the call instead, with nothing written.
 int write_record(Lane &L, uint64_t n, size_t elem, const void *dense_in, RecordSink &S, const fmt::Header *last_hdr,
-                 size_t meta_size, int no_raw_layer = -1) {
+                 size_t meta_size, int no_raw_layer = -1, const char *who = "compress_layers: ") {
   hipStream_t st = L.st;
   uint64_t csize = L.ll->record_size();
   const bool raw = (double)(n * elem) / (double)csize < 1.0;  // GPUPipelines.hpp:136-155
   if (raw && no_raw_layer >= 0)
-    return hl_fail(MGH_ERR_INVALID_ARGUMENT, "compress_layers: layer " + std::to_string(no_raw_layer) + " would be stored raw");
+    return hl_fail(MGH_ERR_INVALID_ARGUMENT, std::string(who) + "layer " + std::to_string(no_raw_layer) + " would be stored raw");
   if (raw) csize = n * elem;
   if (csize > S.cap - S.byte_offset || S.cap - S.byte_offset - csize < 8)
     return hl_fail(MGH_ERR_OUTPUT_TOO_LARGE, "Output too large");
@@ -3036,6 +3037,10 @@ struct CoefficientSession {
   // OTHER of two buffers (lane 0's q and q3). encode_record may run the step again (outlier overflow), and
   // that pass must read what the first read, so the two swap roles only when the record is written. A
   // record the RAW rule would store raw ends the call (write_record).
+  // layer >= 0 with cfg.reorder (mgh_compress_level_layers, which sets it whatever the caller's says): the
+  // quantizing step is mgh_quantize_residual_linear -- the level-linearised integers straight into the
+  // lane's second buffer, the list's indices linearised, the residual in array order with the same
+  // ping-pong.
   static constexpr bool kFusedSymbolHistogram = true;
   int write(double tol, void **compressed, size_t *compressed_size, bool prealloc, int layer = -1) {
     Lane &L = g_cache.lane[0];
@@ -3052,7 +3057,7 @@ struct CoefficientSession {
     const uint64_t ocap = std::max<uint64_t>(1, (uint64_t)(cfg.estimate_outlier_ratio * (double)n));
     int rc;
     if ((rc = L.q2.ensure(sym16 ? n * 2 : n * 8)) != MGH_SUCCESS) return cleanup(rc);
-    if (cfg.reorder && (rc = L.q3.ensure(n * 8)) != MGH_SUCCESS) return cleanup(rc);
+    if (cfg.reorder && layer < 0 && (rc = L.q3.ensure(n * 8)) != MGH_SUCCESS) return cleanup(rc);
     if (layer >= 0 && (rc = L.q3.ensure(n * elem)) != MGH_SUCCESS) return cleanup(rc);
     const void *const coef = layer >= 0 && res_in_q3 ? L.q3.p : L.q.p;
     void *const residual = layer < 0 ? nullptr : res_in_q3 ? L.q.p : L.q3.p;
@@ -3070,7 +3075,10 @@ struct CoefficientSession {
       if (!L.ll->prepared_n) HL_HIP(hipMemsetAsync(L.ocount.p, 0, 8, st));
       const bool fused_bins = sym16 && kFusedSymbolHistogram && L.ll->prepared_n != 0;
       const int64_t *q_enc = (const int64_t *)L.q2.p;
-      if (layer >= 0) {
+      if (layer >= 0 && cfg.reorder) {
+        HL_TRY(mgh_quantize_residual_linear(h, coef, ebtype, tol, s, norm, dict, (int64_t *)L.q2.p, (uint64_t *)L.ocount.p,
+                                            (uint64_t *)L.oidx.p, (int64_t *)L.oval.p, L.ocap, residual, st));
+      } else if (layer >= 0) {
         HL_TRY(mgh_quantize_symbols_residual(h, coef, ebtype, tol, s, norm, dict, (uint16_t *)L.q2.p,
                                              fused_bins ? (uint32_t *)L.ll->freq.p : nullptr, (uint64_t *)L.ocount.p,
                                              (uint64_t *)L.oidx.p, (int64_t *)L.oval.p, L.ocap, residual, st));
@@ -3096,7 +3104,9 @@ struct CoefficientSession {
     };
     if ((rc = quantize()) != MGH_SUCCESS) return cleanup(rc);
     if ((rc = encode_record(L, lj, sink, quantize)) != MGH_SUCCESS) return cleanup(rc);
-    if ((rc = write_record(L, n, elem, d_in, sink, &hdr, meta_size, layer)) != MGH_SUCCESS) return cleanup(rc);
+    if ((rc = write_record(L, n, elem, d_in, sink, &hdr, meta_size, layer,
+                           cfg.reorder ? "compress_level_layers: " : "compress_layers: ")) != MGH_SUCCESS)
+      return cleanup(rc);
     if (layer >= 0) res_in_q3 = !res_in_q3;
     *compressed_size = sink.byte_offset;
     return MGH_SUCCESS;
@@ -3375,6 +3385,38 @@ int mgh_compress_layers(int D, int dtype, const uint64_t *shape, int ntol, const
     CoefficientSession E;
     compress_stats() = mgh_compress_stats{};
     HL_TRY(E.begin("compress_layers: ", false, D, dtype, shape, s, ebtype, original_data, coords, *config));
+    compress_stats().decompositions++;
+    // (a failure at layer k leaves containers 0 .. k-1 the caller's; write() has freed its own)
+    for (int k = 0; k < ntol; k++)
+      HL_TRY(E.write(tols[k], &compressed_data[k], &compressed_size[k], output_pre_allocated != 0, k));
+    return MGH_SUCCESS;
+  });
+}
+
+int mgh_compress_level_layers(int D, int dtype, const uint64_t *shape, int ntol, const double *tols, double s, int ebtype,
+                              const void *original_data, void **compressed_data, size_t *compressed_size,
+                              const void *const *coords, const mgh_config *config, int output_pre_allocated) {
+  if (!tols || !compressed_data || !compressed_size) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "NULL argument");
+  HL_TRY(tolerance_list_args("compress_level_layers: ", ntol, tols, compressed_data, output_pre_allocated != 0, true));
+  HL_TRY(size_call_args(D, dtype, shape, ebtype, original_data, config));
+  mgh_config cfg = *config;
+  cfg.reorder = 1;  // (the records are level-linearised whatever the caller's configuration says)
+  {
+    // what the layer writer does not take, before anything is allocated
+    uint64_t n = 1;
+    for (int d = 0; d < D; d++) n *= shape[d];
+    Decomposer dd;
+    HL_TRY(make_decomposer(dd, D, shape, dtype == MGH_FLOAT ? 4 : 8, cfg));
+    HL_TRY(one_subdomain_only("compress_level_layers: ", dd));
+    if (const char *bad = qsym_refusal(n, cfg.huff_dict_size))
+      return hl_fail(MGH_ERR_INVALID_ARGUMENT, std::string("compress_level_layers: ") + bad);
+  }
+  if (!output_pre_allocated)
+    for (int k = 0; k < ntol; k++) compressed_data[k] = nullptr;
+  return hl_guarded([&]() -> int {
+    CoefficientSession E;
+    compress_stats() = mgh_compress_stats{};
+    HL_TRY(E.begin("compress_level_layers: ", false, D, dtype, shape, s, ebtype, original_data, coords, cfg));
     compress_stats().decompositions++;
     // (a failure at layer k leaves containers 0 .. k-1 the caller's; write() has freed its own)
     for (int k = 0; k < ntol; k++)
@@ -5171,17 +5213,28 @@ int layers_add(mgh_layers *p, const void *data, size_t size) {
 }
 
 // mgh_recompose of the accumulator into an array in the containers' memory space (or the caller's buffer).
-int layers_data(mgh_layers *p, void **out, bool prealloc) {
+// level >= 0 (mgh_layers_data_level): mgh_recompose_to_level, the dense array of that level -- the whole
+// accumulator is there either way, the call reads its corner box.
+int layers_data(mgh_layers *p, void **out, bool prealloc, int level = -1) {
   hipStream_t st = p->st;
-  const size_t out_bytes = p->n * p->elem;
+  size_t out_bytes = p->n * p->elem;
+  if (level >= 0) {
+    uint64_t shp[MGH_MAX_DIM];
+    HL_TRY(mgh_level_shape(p->h, level, shp));
+    out_bytes = p->elem;
+    for (size_t d = 0; d < p->hd.shape.size(); d++) out_bytes *= shp[d];
+  }
+  auto recompose = [&](void *dst) {
+    return level >= 0 ? mgh_recompose_to_level(p->h, p->acc.p, level, dst, st) : mgh_recompose(p->h, p->acc.p, dst, st);
+  };
   const OutSlot slot{out, p->in_dev, prealloc};
   HL_TRY(slot.alloc(out_bytes));
   int rc = MGH_SUCCESS;
   if (is_device_pointer(*out)) {
-    rc = mgh_recompose(p->h, p->acc.p, *out, st);
+    rc = recompose(*out);
   } else {
     rc = p->out.ensure(out_bytes);
-    if (rc == MGH_SUCCESS) rc = mgh_recompose(p->h, p->acc.p, p->out.p, st);
+    if (rc == MGH_SUCCESS) rc = recompose(p->out.p);
     if (rc == MGH_SUCCESS) rc = copy_any(*out, p->out.p, out_bytes, st);
   }
   if (hipStreamSynchronize(st) != hipSuccess && rc == MGH_SUCCESS) rc = hl_fail(MGH_ERR_DEVICE, "sync");
@@ -5247,6 +5300,259 @@ int mgh_decompress_layers(int nlayers, const void *const *compressed_data, const
   for (int k = 1; k < nlayers && rc == MGH_SUCCESS; k++) rc = mgh_layers_add(p, compressed_data[k], compressed_size[k]);
   if (rc == MGH_SUCCESS) rc = mgh_layers_data(p, decompressed_data, output_pre_allocated);
   mgh_layers_close(p);
+  return rc;
+}
+
+int mgh_layers_data_level(mgh_layers *p, int level, void **data, int output_pre_allocated) {
+  if (!p || !data) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (output_pre_allocated && !*data) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "pre-allocated output is NULL");
+  if (level < 0 || level > mgh_l_target(p->h))
+    return hl_fail(MGH_ERR_INVALID_ARGUMENT, "mgh_layers_data_level: level outside 0 .. l_target");
+  if (hipSetDevice(p->cfg.dev_id) != hipSuccess) return hl_fail(MGH_ERR_DEVICE, "hipSetDevice");
+  return hl_guarded([&] { return layers_data(p, data, output_pre_allocated != 0, level); });
+}
+
+} // extern "C"
+
+// ---- precision layers in level order: containers of mgh_compress_level_layers read by resolution AND by
+// tolerance. State between the calls: the accumulator in LEVEL-LINEARISED order (n elements), the header of
+// layer 0, and per layer its header and the level up to which it has been added (depth, non-increasing in
+// the layer's number: on every level the accumulator is the sum of a leading run of layers). A call decodes
+// the chunks that hold its window [N_from, N_level) of one record -- a prefix, or a range from the chunk
+// that holds N_from -- and streams that window into the accumulator (mgh_dequantize_add_linear); the decode
+// buffer grows to the largest window decoded. mgh_level_layers_data recomposes the head [0, N_level) of the
+// accumulator on a copy (mgh_recompose_linear_to_level).
+struct mgh_level_layers {
+  struct Layer {
+    fmt::Header hd;
+    int depth;
+  };
+  fmt::Header hd;  // of layer 0
+  mgh_config cfg;
+  bool in_dev = false;
+  int dtype = MGH_FLOAT;
+  size_t elem = 4;
+  uint64_t n = 0;
+  int L = 0;
+  std::vector<uint64_t> N;  // N[l] = prod(level_shape(l))
+  std::vector<Layer> layers;
+  mgh_hierarchy *h = nullptr;
+  mgh_lossless_ctx *ll = nullptr;
+  hipStream_t st = nullptr;
+  DevBuf acc;  // n elements: the coefficients, level-linearised
+  DevBuf q;    // the integers of the chunks of the window being added
+  DevBuf out;  // a level's array on its way to host memory
+};
+
+namespace {
+void level_layers_free(mgh_level_layers *p) {
+  if (!p) return;
+  (void)hipSetDevice(p->cfg.dev_id);
+  if (p->st) (void)hipStreamSynchronize(p->st);
+  for (DevBuf *b : {&p->acc, &p->q, &p->out}) b->release();
+  if (p->h) mgh_hierarchy_destroy(p->h);
+  if (p->ll) mgh_lossless_destroy(p->ll);
+  if (p->st) (void)hipStreamDestroy(p->st);
+  delete p;
+}
+
+// One window of one container into the accumulator. k == count: layer 0 opens the handle (count == 0),
+// every other one is added; k < count: layer k goes deeper. Every refusal comes before the accumulator is
+// touched.
+int level_layers_take(mgh_level_layers *p, int k, const void *data, size_t size, int level) {
+  const int count = (int)p->layers.size();
+  const bool first = count == 0, extend = k < count;
+  const std::string who = first ? "mgh_level_layers_open: " : extend ? "mgh_level_layers_extend: " : "mgh_level_layers_add: ";
+  std::unique_ptr<HostPrefix> prefix;
+  const bool in_dev = is_device_pointer(data);
+  if (in_dev) prefix.reset(new HostPrefix(data, size));
+  size_t meta_size = 0;
+  fmt::Header hd;
+  HL_TRY(read_header(data, size, hd, meta_size));
+  if (hd.shape.empty() || hd.shape.size() > MGH_MAX_DIM) return hl_fail(MGH_ERR_UNSUPPORTED_DIMENSION, "header: dimension");
+  if (!hd.quantized) return hl_fail(MGH_ERR_FORMAT, "not a compressed (quantized) stream");
+  RecordView rv;
+  HL_TRY(record_view_header(hd, rv));
+  if (hd.dd_method != fmt::DD_NOOP)
+    return hl_fail(MGH_ERR_INVALID_ARGUMENT, who + "the container is domain-decomposed (layers have one subdomain)");
+  if (!hd.reorder)
+    return hl_fail(MGH_ERR_INVALID_ARGUMENT, who + "a reorder = 0 container is no level-ordered layer (mgh_layers_* reads those)");
+  for (uint64_t e : hd.shape)
+    if (e < 3) return hl_fail(MGH_ERR_FORMAT, "header: extent below 3");
+  if (!first) {
+    if (const char *what = layers_mismatch(p->hd, hd)) return hl_fail(MGH_ERR_INVALID_ARGUMENT, who + what + " is not layer 0's");
+    if (!extend && !(hd.tol < p->layers.back().hd.tol))
+      return hl_fail(MGH_ERR_INVALID_ARGUMENT, who + "the tolerance is not below the last layer's");
+    if (extend) {
+      const fmt::Header &was = p->layers[k].hd;
+      if (!(hd.tol == was.tol) || hd.huff_dict_size != was.huff_dict_size || hd.huff_block_size != was.huff_block_size)
+        return hl_fail(MGH_ERR_INVALID_ARGUMENT, who + "the container is not the one recorded for layer " + std::to_string(k) +
+                                                     " (tolerance, dictionary or chunk size)");
+    }
+  }
+  int L = p->L;
+  std::vector<uint64_t> N = p->N;
+  if (first) {
+    HL_TRY(header_level_shape(hd, p->cfg, -1, &L, nullptr));
+    N.resize(L + 1);
+    for (int l = 0; l <= L; l++) {
+      std::vector<uint64_t> shp;
+      HL_TRY(header_level_shape(hd, p->cfg, l, nullptr, &shp));
+      N[l] = 1;
+      for (uint64_t e : shp) N[l] *= e;
+    }
+  }
+  // the level: layer 0 anywhere, a new layer no deeper than the one before it, a layer going deeper no
+  // deeper than the one before it either -- a finer layer alone on a level would be a residual of nothing
+  const int lo_level = extend ? p->layers[k].depth + 1 : 0;
+  const int hi_level = k > 0 ? p->layers[k - 1].depth : L;
+  if (level < lo_level || level > hi_level)
+    return hl_fail(MGH_ERR_INVALID_ARGUMENT, who + "level " + std::to_string(level) + " outside " + std::to_string(lo_level) +
+                                                 " .. " + std::to_string(hi_level) + " for layer " + std::to_string(k));
+  const uint64_t n = N[L];
+  const size_t elem = hd.is_double ? 8 : 4;
+  HL_TRY(record_view_at(data, size, meta_size, n * elem, rv));
+  if (rv.raw) return hl_fail(MGH_ERR_INVALID_ARGUMENT, who + "the record is stored raw (no layer is)");
+  if (first) {
+    p->hd = hd;
+    p->in_dev = in_dev;
+    p->dtype = hd.is_double ? MGH_DOUBLE : MGH_FLOAT;
+    p->elem = elem;
+    p->n = n;
+    p->L = L;
+    p->N = N;
+    std::vector<std::vector<double>> mirrored;
+    bool owned = true;
+    HL_TRY(get_hierarchy(&p->h, &owned, p->dtype, hd.shape, decoder_coords(hd, p->cfg, mirrored),
+                         std::vector<uint64_t>(hd.shape.size(), 0), p->cfg, 0, /*cached=*/false));
+    if (mgh_l_target(p->h) != L) return hl_fail(MGH_ERR_FORMAT, "header: the hierarchy of the subdomain is not the header's");
+    HL_HIP(hipStreamCreate(&p->st));
+    HL_TRY(mgh_lossless_create(&p->ll, p->cfg.dev_id));
+    HL_TRY(p->acc.ensure(n * elem));
+  }
+  // the window [lo, hi) of the level-linearised array, and the chunks that hold it
+  const uint64_t block = std::max<uint64_t>(hd.huff_block_size, 1);
+  const uint64_t lo = extend ? N[p->layers[k].depth] : 0, hi = N[level];
+  const uint64_t dec_first = lo / block * block, dec_end = std::min(n, ((hi - 1) / block + 1) * block);
+  HL_TRY(p->q.ensure((dec_end - dec_first) * 8));
+  mgh_decompress_stats &stats = decompress_stats();
+  stats = mgh_decompress_stats{};
+  stats.subdomains = 1;
+  auto in_type = [&](double v) { return hd.is_double ? v : (double)(float)v; };
+  uint64_t ocount = 0;
+  int rc = lossless_decompress(p->ll, rv.rec, rv.csize, rv.lossless, (int64_t *)p->q.p, n, &ocount, p->st, nullptr,
+                               /*sync_end=*/false, DecodeRange{/*n_prefix=*/hi, /*q_cap=*/dec_end - dec_first, /*first=*/lo});
+  if (rc == MGH_SUCCESS)
+    rc = mgh_dequantize_add_linear(p->h, (int64_t *)p->q.p + (lo - dec_first), lo, hi - lo, hd.rel ? MGH_REL : MGH_ABS,
+                                   in_type(hd.tol), in_type(hd.s), in_type(hd.norm), hd.huff_dict_size, 1,
+                                   (const uint64_t *)p->ll->oidx.p, (const int64_t *)p->ll->oval.p, ocount, k == 0 ? 1 : 0,
+                                   p->acc.p, p->st);
+  if (hipStreamSynchronize(p->st) != hipSuccess && rc == MGH_SUCCESS) rc = hl_fail(MGH_ERR_DEVICE, "sync");
+  if (rc == MGH_SUCCESS) rc = lossless_tag_check(p->ll);
+  HL_TRY(rc);
+  if (extend) p->layers[k].depth = level;
+  else p->layers.push_back({hd, level});
+  return MGH_SUCCESS;
+}
+
+// mgh_recompose_linear_to_level of the accumulator's head into an array in the containers' memory space
+// (or the caller's buffer); the accumulator stays.
+int level_layers_data(mgh_level_layers *p, int level, void **out, bool prealloc) {
+  hipStream_t st = p->st;
+  const size_t out_bytes = p->N[level] * p->elem;
+  const OutSlot slot{out, p->in_dev, prealloc};
+  HL_TRY(slot.alloc(out_bytes));
+  int rc = MGH_SUCCESS;
+  if (is_device_pointer(*out)) {
+    rc = mgh_recompose_linear_to_level(p->h, p->acc.p, level, *out, st);
+  } else {
+    rc = p->out.ensure(out_bytes);
+    if (rc == MGH_SUCCESS) rc = mgh_recompose_linear_to_level(p->h, p->acc.p, level, p->out.p, st);
+    if (rc == MGH_SUCCESS) rc = copy_any(*out, p->out.p, out_bytes, st);
+  }
+  if (hipStreamSynchronize(st) != hipSuccess && rc == MGH_SUCCESS) rc = hl_fail(MGH_ERR_DEVICE, "sync");
+  return slot.fail(rc);
+}
+}  // namespace
+
+extern "C" {
+
+int mgh_level_layers_open(mgh_level_layers **out, const void *compressed_data, size_t compressed_size,
+                          const mgh_config *config, int level) {
+  if (!out || !compressed_data) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "NULL argument");
+  *out = nullptr;
+  {
+    const std::string bad = env_validate();
+    if (!bad.empty()) return hl_fail(MGH_ERR_INVALID_ARGUMENT, bad);
+  }
+  mgh_config def;
+  if (!config) {
+    mgh_config_default(&def);
+    config = &def;
+  }
+  if (mgh_device_count() <= 0) return hl_fail(MGH_ERR_NO_DEVICE, "no HIP device");
+  if (hipSetDevice(config->dev_id) != hipSuccess) return hl_fail(MGH_ERR_DEVICE, "hipSetDevice");
+  mgh_level_layers *p = new mgh_level_layers();
+  p->cfg = *config;
+  const int rc = hl_guarded([&] { return level_layers_take(p, 0, compressed_data, compressed_size, level); });
+  if (rc != MGH_SUCCESS) {
+    level_layers_free(p);
+    return rc;
+  }
+  *out = p;
+  return MGH_SUCCESS;
+}
+
+int mgh_level_layers_add(mgh_level_layers *p, const void *compressed_data, size_t compressed_size, int level) {
+  if (!p || !compressed_data) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (p->layers.size() >= (size_t)kLadderMaxTols) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "mgh_level_layers_add: 64 layers at most");
+  if (hipSetDevice(p->cfg.dev_id) != hipSuccess) return hl_fail(MGH_ERR_DEVICE, "hipSetDevice");
+  return hl_guarded([&] { return level_layers_take(p, (int)p->layers.size(), compressed_data, compressed_size, level); });
+}
+
+int mgh_level_layers_extend(mgh_level_layers *p, int k, const void *compressed_data, size_t compressed_size, int level) {
+  if (!p || !compressed_data) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (k < 0 || k >= (int)p->layers.size())
+    return hl_fail(MGH_ERR_INVALID_ARGUMENT, "mgh_level_layers_extend: no layer " + std::to_string(k));
+  if (hipSetDevice(p->cfg.dev_id) != hipSuccess) return hl_fail(MGH_ERR_DEVICE, "hipSetDevice");
+  return hl_guarded([&] { return level_layers_take(p, k, compressed_data, compressed_size, level); });
+}
+
+int mgh_level_layers_count(const mgh_level_layers *p) { return p ? (int)p->layers.size() : -1; }
+
+int mgh_level_layers_depth(const mgh_level_layers *p, int k) {
+  return p && k >= 0 && k < (int)p->layers.size() ? p->layers[k].depth : -1;
+}
+
+double mgh_level_layers_tolerance(const mgh_level_layers *p, int k) {
+  return p && k >= 0 && k < (int)p->layers.size() ? p->layers[k].hd.tol : 0.0;
+}
+
+int mgh_level_layers_data(mgh_level_layers *p, int level, void **data, int output_pre_allocated) {
+  if (!p || !data) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (output_pre_allocated && !*data) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "pre-allocated output is NULL");
+  if (level < 0 || level > p->layers[0].depth)
+    return hl_fail(MGH_ERR_INVALID_ARGUMENT, "mgh_level_layers_data: level " + std::to_string(level) + " outside 0 .. " +
+                                                 std::to_string(p->layers[0].depth) + " (the depth of layer 0)");
+  if (hipSetDevice(p->cfg.dev_id) != hipSuccess) return hl_fail(MGH_ERR_DEVICE, "hipSetDevice");
+  return hl_guarded([&] { return level_layers_data(p, level, data, output_pre_allocated != 0); });
+}
+
+void mgh_level_layers_close(mgh_level_layers *p) { level_layers_free(p); }
+
+int mgh_decompress_level_layers(int nlayers, const void *const *compressed_data, const size_t *compressed_size, int level,
+                                const mgh_config *config, void **decompressed_data, int output_pre_allocated) {
+  if (!compressed_data || !compressed_size || !decompressed_data) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (nlayers < 1 || nlayers > kLadderMaxTols)
+    return hl_fail(MGH_ERR_INVALID_ARGUMENT, "decompress_level_layers: nlayers must be in 1..64");
+  for (int k = 0; k < nlayers; k++)
+    if (!compressed_data[k]) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (output_pre_allocated && !*decompressed_data) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "pre-allocated output is NULL");
+  mgh_level_layers *p = nullptr;
+  int rc = mgh_level_layers_open(&p, compressed_data[0], compressed_size[0], config, level);
+  for (int k = 1; k < nlayers && rc == MGH_SUCCESS; k++) rc = mgh_level_layers_add(p, compressed_data[k], compressed_size[k], level);
+  if (rc == MGH_SUCCESS) rc = mgh_level_layers_data(p, level, decompressed_data, output_pre_allocated);
+  mgh_level_layers_close(p);
   return rc;
 }
 

@@ -125,14 +125,19 @@ struct LinBox {
   uint64_t unit0[kLinMaxLevels + 2];    // first unit of level j (units: pieces of runs); [level + 1]: all
 };
 
-typedef int64_t lin_pair_t __attribute__((ext_vector_type(2), aligned(8)));
+// Two neighbours of the stream as one load. The permutation moves bits: E is int64_t for 8-byte elements
+// (the integers, double coefficients) and int32_t for 4-byte ones (float coefficients,
+// mgh_recompose_linear_to_level).
+template <typename E> struct LinPair;
+template <> struct LinPair<int64_t> { typedef int64_t type __attribute__((ext_vector_type(2), aligned(8))); };
+template <> struct LinPair<int32_t> { typedef int32_t type __attribute__((ext_vector_type(2), aligned(4))); };
 
 // One piece of a run of level j >= 1 (unit `ul` of that level) into a box with strides `bs`; `lj` is
 // where the level's own integers start (lin + N_{j-1} in the whole array, or a segment that holds the
 // level alone). All arguments but the lane are wave-uniform.
+template <typename E>
 __device__ __forceinline__ void lin_run_to_box(const LinMeta &m, int j, uint32_t ul, const uint64_t *bs,
-                                               const int64_t *__restrict__ lj, int64_t *__restrict__ box,
-                                               int lane) {
+                                               const E *__restrict__ lj, E *__restrict__ box, int lane) {
   const int D = m.D;
   const uint32_t *F = m.lshape[j];
   const uint32_t Ff = F[D - 1];
@@ -159,8 +164,8 @@ __device__ __forceinline__ void lin_run_to_box(const LinMeta &m, int j, uint32_t
     cstride *= F[d] / 2 + 1;
   }
   // (an all-coarse row starts at its first odd-f node, g = 1: one element on, one coarse node before it)
-  const int64_t *s = lj + (to - co);
-  int64_t *dst = box + off;
+  const E *s = lj + (to - co);
+  E *dst = box + off;
   if (mixed) {
     // the whole natural row: nodes 2k and 2k + 1 side by side in the stream
     const uint32_t e1 = min(Ff, e0 + kLevelBoxPiece);
@@ -168,7 +173,8 @@ __device__ __forceinline__ void lin_run_to_box(const LinMeta &m, int j, uint32_t
     for (uint32_t g = e0 + 2 * lane; g < e1; g += 128) {
       const uint32_t k = g / 2;
       if (g + 1 < e1) {
-        const lin_pair_t v = *reinterpret_cast<const lin_pair_t *>(s + g);
+        typedef typename LinPair<E>::type pair_t;
+        const pair_t v = *reinterpret_cast<const pair_t *>(s + g);
         dst[k] = v.x;
         dst[(even_last && g + 1 == Ff - 1) ? Ff / 2 : Cf + k] = v.y;
       } else {
@@ -183,8 +189,9 @@ __device__ __forceinline__ void lin_run_to_box(const LinMeta &m, int j, uint32_t
   }
 }
 
+template <typename E>
 __global__ void __launch_bounds__(256)
-k_box_from_linear(LinMeta m, LinBox B, const int64_t *__restrict__ lin, int64_t *__restrict__ box) {
+k_box_from_linear(LinMeta m, LinBox B, const E *__restrict__ lin, E *__restrict__ box) {
   const int lane = threadIdx.x & 63;
   const int D = m.D;
   const uint64_t units = B.unit0[B.level + 1];

@@ -33,6 +33,10 @@
 // (k_outlier_restore), as a pure stream (stream_levels) with its two tables in LDS. FIRST stores
 // k_dequantize's value (it is not added to zero: -0.0 stays -0.0); otherwise acc = acc + that value, one
 // IEEE add. 8 + esz bytes read (2 esz with the accumulator) and esz written per element, no atomics.
+//
+// The same two for the layers in LEVEL ORDER (reorder = 1 records; further down): k_quantize_residual_int64,
+// the symbol body with int64 output for the writer, and k_dequantize_add_linear, the reader's stream over a
+// window of the level-linearised array.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -43,10 +47,10 @@ namespace mgh {
 
 constexpr int kQsThreads = 256;
 
-template <typename T, bool HIST, bool RES>
+template <typename T, bool HIST, bool RES, typename SYM = uint16_t>
 __device__ __forceinline__ void quantize_symbols_body(const QuantMeta &m, size_t total, const T *v,
                                                       const int *__restrict__ marks, const T *__restrict__ tab, int nlev,
-                                                      int dict, uint16_t *__restrict__ sym, unsigned *__restrict__ freq,
+                                                      int dict, SYM *__restrict__ sym, unsigned *__restrict__ freq,
                                                       unsigned long long *outlier_count, uint64_t *__restrict__ outlier_idx,
                                                       int64_t *__restrict__ outlier_val, unsigned long long outlier_cap,
                                                       T *r_out /* RES only */) {
@@ -60,7 +64,7 @@ __device__ __forceinline__ void quantize_symbols_body(const QuantMeta &m, size_t
   const int64_t half = (int64_t)dict / 2;
   constexpr int VN = Vec16<T>::N;
   typedef T NV __attribute__((ext_vector_type(VN)));
-  typedef uint16_t SV __attribute__((ext_vector_type(VN)));
+  typedef SYM SV __attribute__((ext_vector_type(VN)));
   const bool vec_in = aligned16(v);
   const bool vec_out = (reinterpret_cast<uintptr_t>(sym) & (sizeof(SV) - 1)) == 0;
   const bool vec_res = RES && aligned16(r_out);
@@ -120,7 +124,7 @@ __device__ __forceinline__ void quantize_symbols_body(const QuantMeta &m, size_t
     SV s;
 #pragma unroll
     for (int u = 0; u < VN; u++) {
-      s[u] = (uint16_t)qd[u];
+      s[u] = (SYM)qd[u];
       if (HIST && u < cnt) {
         if (qd[u] == half) centre++;
         else atomicAdd(&qs_bins[(int)qd[u]], 1u);
@@ -157,6 +161,20 @@ k_quantize_symbols_residual(QuantMeta m, size_t total, const T *v, const int *__
                             int64_t *__restrict__ outlier_val, unsigned long long outlier_cap, T *r_out) {
   quantize_symbols_body<T, HIST, true>(m, total, v, marks, tab, nlev, dict, sym, freq, outlier_count, outlier_idx,
                                        outlier_val, outlier_cap, r_out);
+}
+
+// SYM = int64_t (mgh_quantize_residual_linear, the writer of a level-ordered layer): the same pass with
+// the integers stored as mgh_quantize(prep_huffman = 1) stores them -- the shifted value, 0 for an outlier
+// -- in array order; the launcher linearises them and the list's indices behind it (k_level_linearize,
+// k_linearize_indices).
+template <typename T>
+__global__ void __launch_bounds__(kQsThreads)
+k_quantize_residual_int64(QuantMeta m, size_t total, const T *v, const int *__restrict__ marks,
+                          const T *__restrict__ tab /* [4][nlev]: QTab */, int nlev, int dict, int64_t *__restrict__ q,
+                          unsigned long long *outlier_count, uint64_t *__restrict__ outlier_idx,
+                          int64_t *__restrict__ outlier_val, unsigned long long outlier_cap, T *r_out) {
+  quantize_symbols_body<T, false, true, int64_t>(m, total, v, marks, tab, nlev, dict, q, nullptr, outlier_count,
+                                                 outlier_idx, outlier_val, outlier_cap, r_out);
 }
 
 constexpr int kQaThreads = 256;
@@ -200,6 +218,93 @@ k_dequantize_add(QuantMeta m, size_t total, const int64_t *__restrict__ q, const
         const T add = value(q[k], level);
         acc[k] = FIRST ? add : acc[k] + add;
       });
+}
+
+// k_dequantize_add_linear: k_dequantize_add on a WINDOW of the level-linearised order (reorder = 1; the
+// reader of the level-ordered precision layers). q[0 .. count) are the integers at positions
+// [first, first + count) of the linearised array, outliers written back already (k_outlier_restore_window);
+// acc is the whole accumulator in the same order, of which only that window is read or written.
+//
+// In this order the level of a position needs no marks and no division: level l occupies [N_{l-1}, N_l)
+// with N_l = prod(level_shape(l)) (LinMeta::lshape; linearized_position, kernels_v1.hpp, puts a node of
+// level `level` at base = N_{level-1} plus its rank inside the level). The offsets N_0 < ... < N_L come by
+// value and are staged in LDS beside the two tables of mgh_dequantize. The numbering is the dequantizer's:
+// linearized_position takes `level` as the largest per-dimension mark of the node, level_of (kernels_v1.hpp,
+// what k_dequantize and LevelCursor index qz[] and vol[] with) is the same maximum over the same marks, and
+// both count 0 = coarsest (lshape[0] is the coarsest grid; upload_quantizers fills qz[l] for l = 0 .. L in
+// that order). With calc_vol == 0 (s = inf) k_dequantize reads entry 0 of the quantizers for every node and
+// no volume; so does this kernel.
+//
+// A pure stream: persistent workgroups, no atomics, no barrier behind the staging. Where q and acc + first
+// are 16-byte aligned a thread moves whole vectors (VN elements of T, VN / 2 pairs of integers) and takes
+// one level for the vector when its last element lies below the level's end, else one level per element;
+// the tail, or all of a misaligned window, goes element by element. STORE stores the value (never added to
+// zero: -0.0 stays -0.0); otherwise acc = acc + value, one IEEE add behind k_dequantize's two multiplies.
+struct LinOffsets {
+  uint32_t n[kMaxLevels];  // n[l] = N_l (the entry points refuse 2^32 elements and more)
+};
+
+template <typename T, bool STORE>
+__global__ void __launch_bounds__(kQaThreads)
+k_dequantize_add_linear(LinOffsets off, int nlev, int calc_vol, const int64_t *__restrict__ q, uint32_t first,
+                        size_t count, const T *__restrict__ tab /* [2][nlev]: quantizers, dequantize volumes */,
+                        int64_t shift, T *__restrict__ acc_all) {
+  __shared__ T s_tab[2][kMaxLevels];
+  __shared__ uint32_t s_off[kMaxLevels];
+  stage_tables<kQaThreads>(tab, nlev, s_tab);
+  for (int i = threadIdx.x; i < nlev; i += kQaThreads) s_off[i] = off.n[i];
+  __syncthreads();
+
+  const int top = nlev - 1;
+  // (most positions lie in the finest levels: from the top down, one comparison for the finest)
+  auto level_at = [&](uint32_t p) -> int {
+    int l = 0;
+    if (calc_vol) {
+      l = top;
+      while (l > 0 && p < s_off[l - 1]) l--;
+    }
+    return l;
+  };
+  auto value = [&](int64_t qd, int level) -> T {
+    const T volume = calc_vol ? s_tab[1][level] : (T)1;
+    return (s_tab[0][level] * volume) * (T)(qd - shift);
+  };
+  constexpr int VN = Vec16<T>::N;
+  typedef T NV __attribute__((ext_vector_type(VN)));
+  typedef int64_t Q2 __attribute__((ext_vector_type(2)));
+  T *acc = acc_all + first;  // acc[k] is position first + k, like q[k]
+  const size_t tid = (size_t)blockIdx.x * kQaThreads + threadIdx.x;
+  const size_t nth = (size_t)gridDim.x * kQaThreads;
+  size_t done = 0;
+  if (aligned16(q, acc)) {
+    const size_t nvec = count / VN;
+    for (size_t i = tid; i < nvec; i += nth) {
+      const uint32_t p0 = first + (uint32_t)(i * VN);
+      int64_t qd[VN];
+#pragma unroll
+      for (int u = 0; u < VN; u += 2) {
+        const Q2 two = reinterpret_cast<const Q2 *>(q)[i * (VN / 2) + u / 2];
+        qd[u] = two[0];
+        qd[u + 1] = two[1];
+      }
+      NV y;
+      if (!STORE) y = reinterpret_cast<NV *>(acc)[i];
+      const int l0 = level_at(p0);
+      // (the vector ends inside level l0: one level; else it straddles a boundary, element by element)
+      const bool one_level = !calc_vol || p0 + (VN - 1) < s_off[l0];
+#pragma unroll
+      for (int u = 0; u < VN; u++) {
+        const T add = value(qd[u], one_level ? l0 : level_at(p0 + u));
+        y[u] = STORE ? add : y[u] + add;
+      }
+      reinterpret_cast<NV *>(acc)[i] = y;
+    }
+    done = nvec * VN;
+  }
+  for (size_t k = done + tid; k < count; k += nth) {
+    const T add = value(q[k], level_at(first + (uint32_t)k));
+    acc[k] = STORE ? add : acc[k] + add;
+  }
 }
 
 }  // namespace mgh

@@ -46,7 +46,10 @@ HL_SYMBOLS = [
     "mgh_achieved_errors", "mgh_compress_target",
     "mgh_compress_ladder", "mgh_last_compress_stats", "mgh_histogram_sym16",
     "mgh_compress_layers", "mgh_layers_open", "mgh_layers_add", "mgh_layers_count", "mgh_layers_tolerance",
-    "mgh_layers_data", "mgh_layers_close", "mgh_decompress_layers",
+    "mgh_layers_data", "mgh_layers_close", "mgh_decompress_layers", "mgh_layers_data_level",
+    "mgh_compress_level_layers", "mgh_level_layers_open", "mgh_level_layers_add", "mgh_level_layers_extend",
+    "mgh_level_layers_count", "mgh_level_layers_depth", "mgh_level_layers_tolerance", "mgh_level_layers_data",
+    "mgh_level_layers_close", "mgh_decompress_level_layers",
     "mgh_compress_masked", "mgh_masked_info", "mgh_decompress_masked", "mgh_decompress_mask",
     "mgh_decompress_masked_level", "mgh_decompress_masked_coarsened", "mgh_decompress_masked_preview",
     "mgh_decompress_masked_preview_window", "mgh_decompress_mask_level", "mgh_decompress_mask_coarsened",
@@ -279,6 +282,20 @@ def _hl():
     L.mgh_layers_data.argtypes = [vp, C.POINTER(vp), C.c_int]
     L.mgh_layers_close.argtypes = [vp]
     L.mgh_layers_close.restype = None
+    L.mgh_layers_data_level.argtypes = [vp, C.c_int, C.POINTER(vp), C.c_int]
+    L.mgh_compress_level_layers.argtypes = L.mgh_compress_ladder.argtypes
+    L.mgh_level_layers_open.argtypes = [C.POINTER(vp), vp, C.c_size_t, vp, C.c_int]
+    L.mgh_level_layers_add.argtypes = [vp, vp, C.c_size_t, C.c_int]
+    L.mgh_level_layers_extend.argtypes = [vp, C.c_int, vp, C.c_size_t, C.c_int]
+    L.mgh_level_layers_count.argtypes = [vp]
+    L.mgh_level_layers_depth.argtypes = [vp, C.c_int]
+    L.mgh_level_layers_tolerance.argtypes = [vp, C.c_int]
+    L.mgh_level_layers_tolerance.restype = C.c_double
+    L.mgh_level_layers_data.argtypes = [vp, C.c_int, C.POINTER(vp), C.c_int]
+    L.mgh_level_layers_close.argtypes = [vp]
+    L.mgh_level_layers_close.restype = None
+    L.mgh_decompress_level_layers.argtypes = [C.c_int, C.POINTER(vp), C.POINTER(C.c_size_t), C.c_int, C.POINTER(Config),
+                                              C.POINTER(vp), C.c_int]
     L.mgh_decompress_layers.argtypes = [C.c_int, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(Config), C.POINTER(vp),
                                         C.c_int]
     L.mgh_memcpy.argtypes = [vp, vp, C.c_size_t]
@@ -602,11 +619,13 @@ def _container_ptr(buf):
     return C.c_void_p(buf.ctypes.data), int(buf.size), False, buf
 
 
-def _layers_out(buf0, out):
-    """The array layers of `buf0` reconstruct, as (out, pointer): a cuda tensor for a device container, a numpy
-    array for a host one."""
+def _layers_out(buf0, out, level=None, config=None):
+    """The array layers of `buf0` reconstruct (level = None) or its level `level`, as (out, pointer): a cuda tensor
+    for a device container, a numpy array for a host one."""
     import torch
     shape, dt = infer(buf0)
+    if level is not None:
+        shape = infer_level(buf0, level, config)[0]
     _wait_for_current_stream(out)
     on_dev = isinstance(buf0, torch.Tensor) and buf0.is_cuda
     n = int(np.prod(shape))
@@ -641,6 +660,40 @@ def decompress_layers(bufs, config=None, out=None):
     out, optr = _layers_out(bufs[0], out)
     _check(L.mgh_decompress_layers(k, (C.c_void_p * k)(*[p[0].value for p in ptrs]), (C.c_size_t * k)(*[p[1] for p in ptrs]),
                                    C.byref(cfg), C.byref(optr), 1))
+    return out
+
+
+def compress_level_layers(data, tols, s=INF, mode=REL, coords=None, config=None, outs=None):
+    """mgh_compress_level_layers: compress_layers with level-linearised (reorder = 1) records, whatever
+    config.reorder says -- a set that refines by tolerance AND by resolution: LevelLayers / decompress_level_layers
+    read level L of layer k from the head of that layer's record. bufs[0] is compress(data, tols[0], reorder = 1)'s
+    container; every layer is an ordinary container (decompress, decompress(level=), Progressive open it).
+    Refused: a configuration that decomposes the domain, a layer that would be stored raw."""
+    return compress_ladder(data, tols, s, mode, coords, config, outs, _call="mgh_compress_level_layers")
+
+
+def decompress_level_layers(bufs, level, config=None, out=None):
+    """mgh_decompress_level_layers: level `level` of the array after the layers `bufs` (compress_level_layers'
+    containers, from layer 0 on, in order), every layer read up to that level: per layer a prefix decode and one
+    stream over the head of the coefficients, then one recomposition of that head."""
+    L = _hl()
+    cfg = config if config is not None else Config()
+    bufs = list(bufs)
+    k = len(bufs)
+    ptrs = [_container_ptr(b) for b in bufs]
+    if k == 0:
+        raise ValueError("decompress_level_layers needs at least layer 0")
+    args = (k, (C.c_void_p * k)(*[p[0].value for p in ptrs]), (C.c_size_t * k)(*[p[1] for p in ptrs]), int(level), C.byref(cfg))
+    try:
+        known = int(level) >= 0 and infer_level(bufs[0], int(level), cfg)[0] is not None
+    except MgardHipError:
+        known = False
+    if not known:
+        # no such level, or no container that has levels: the call says which (it refuses before it allocates)
+        _check(L.mgh_decompress_level_layers(*args, C.byref(C.c_void_p()), 0))
+        raise MgardHipError("decompress_level_layers: the level's shape is unknown")
+    out, optr = _layers_out(bufs[0], out, int(level), cfg)
+    _check(L.mgh_decompress_level_layers(*args, C.byref(optr), 1))
     return out
 
 
@@ -918,8 +971,13 @@ class Layers:
         _check(_hl().mgh_layers_add(self._open(), p, n))
         return self
 
-    def data(self, out=None):
-        """mgh_layers_data: the recomposition of the coefficients as they stand; the reader goes on."""
+    def data(self, out=None, level=None):
+        """mgh_layers_data: the recomposition of the coefficients as they stand; the reader goes on. level = L:
+        mgh_layers_data_level, the array of that level of the hierarchy only (what LevelLayers.data(L) answers)."""
+        if level is not None:
+            out, optr = _layers_out(self._buf0, out, int(level), self._cfg)
+            _check(_hl().mgh_layers_data_level(self._open(), int(level), C.byref(optr), 1))
+            return out
         out, optr = _layers_out(self._buf0, out)
         _check(_hl().mgh_layers_data(self._open(), C.byref(optr), 1))
         return out
@@ -927,6 +985,77 @@ class Layers:
     def close(self):
         if self._p:
             _hl().mgh_layers_close(self._p)
+            self._p = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class LevelLayers:
+    """mgh_level_layers: the reader of precision layers in level order (compress_level_layers' containers) -- the
+    coefficients stay on the device in level-linearised order, and every layer is read up to a level of its own:
+
+        with LevelLayers(bufs[0], level=L - 2, config=cfg) as r:
+            quick = r.data(L - 2)                       # coarse grid, loose tolerance
+            r.add(bufs[1], L - 2)                       # ... a tighter tolerance on that grid
+            full = r.extend(0, bufs[0], L).data(L)      # ... the full grid at layer 0's tolerance
+
+    depth(k) never exceeds depth(k - 1); data(level) needs level <= depth(0). A call that breaks a rule raises and
+    leaves the reader as it was. The containers are read during the call only."""
+
+    def __init__(self, buf0, level, config=None):
+        self._p = C.c_void_p()
+        self._cfg = config if config is not None else Config()
+        self._buf0 = buf0
+        p, n, _, keep = _container_ptr(buf0)
+        _check(_hl().mgh_level_layers_open(C.byref(self._p), p, n, C.byref(self._cfg), int(level)))
+
+    def _open(self):
+        if not self._p:
+            raise MgardHipError("the reader is closed")
+        return self._p
+
+    @property
+    def count(self):
+        """Layers added so far, layer 0 included."""
+        return int(_hl().mgh_level_layers_count(self._open()))
+
+    def depth(self, k):
+        """The level up to which layer k has been added."""
+        return int(_hl().mgh_level_layers_depth(self._open(), int(k)))
+
+    def tolerance(self, k):
+        """The tolerance of layer k (its header's)."""
+        return float(_hl().mgh_level_layers_tolerance(self._open(), int(k)))
+
+    def add(self, buf, level):
+        p, n, _, keep = _container_ptr(buf)
+        _check(_hl().mgh_level_layers_add(self._open(), p, n, int(level)))
+        return self
+
+    def extend(self, k, buf, level):
+        p, n, _, keep = _container_ptr(buf)
+        _check(_hl().mgh_level_layers_extend(self._open(), int(k), p, n, int(level)))
+        return self
+
+    def data(self, level, out=None):
+        """mgh_level_layers_data: level `level` (<= depth(0)) of the coefficients as they stand; the reader goes on."""
+        out, optr = _layers_out(self._buf0, out, int(level), self._cfg)
+        _check(_hl().mgh_level_layers_data(self._open(), int(level), C.byref(optr), 1))
+        return out
+
+    def close(self):
+        if self._p:
+            _hl().mgh_level_layers_close(self._p)
             self._p = C.c_void_p()
 
     def __enter__(self):
