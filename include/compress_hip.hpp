@@ -417,6 +417,41 @@ inline compress_status_type decompress_pwrel(const void *compressed_data, size_t
   return detail::status(mgh_decompress_pwrel(compressed_data, compressed_size, &c, &decompressed_data,
                                              output_pre_allocated ? 1 : 0));
 }
+// ... and its readers at reduced resolution and in previews (mgh_decompress_pwrel_level / _coarsened / _preview /
+// _preview_window). A node takes its class and sign from the element of the full array it stands on (sampling); a
+// valid node is +-exp2 of what the reader of the same name without `pwrel_` writes for the container part. Such an
+// output carries no error bound. A plain container or a masked buffer is a Failure.
+inline compress_status_type decompress_pwrel_level(const void *compressed_data, size_t compressed_size, int level,
+                                                   void *&decompressed_data, HighLevelConfig config,
+                                                   bool output_pre_allocated) {
+  const mgh_config c = detail::to_c(config);
+  return detail::status(mgh_decompress_pwrel_level(compressed_data, compressed_size, level, &decompressed_data, &c,
+                                                   output_pre_allocated ? 1 : 0));
+}
+inline compress_status_type decompress_pwrel_coarsened(const void *compressed_data, size_t compressed_size, int halvings,
+                                                       void *&decompressed_data, HighLevelConfig config,
+                                                       bool output_pre_allocated) {
+  const mgh_config c = detail::to_c(config);
+  return detail::status(mgh_decompress_pwrel_coarsened(compressed_data, compressed_size, halvings, &decompressed_data, &c,
+                                                       output_pre_allocated ? 1 : 0));
+}
+inline compress_status_type decompress_pwrel_preview(const void *compressed_data, size_t compressed_size, int halvings,
+                                                     void *&decompressed_data, HighLevelConfig config,
+                                                     bool output_pre_allocated) {
+  const mgh_config c = detail::to_c(config);
+  return detail::status(mgh_decompress_pwrel_preview(compressed_data, compressed_size, halvings, &decompressed_data, &c,
+                                                     output_pre_allocated ? 1 : 0));
+}
+inline compress_status_type decompress_pwrel_preview_window(const void *compressed_data, size_t compressed_size,
+                                                            int halvings, const std::vector<SIZE> &lo,
+                                                            const std::vector<SIZE> &ext, void *&decompressed_data,
+                                                            HighLevelConfig config, bool output_pre_allocated) {
+  if (lo.size() != ext.size()) return compress_status_type::Failure;
+  const mgh_config c = detail::to_c(config);
+  return detail::status(mgh_decompress_pwrel_preview_window(compressed_data, compressed_size, halvings, lo.data(),
+                                                            ext.data(), &decompressed_data, &c,
+                                                            output_pre_allocated ? 1 : 0));
+}
 // ... what the buffer is (mgh_pwrel_info): pwrel = false for any other buffer (info untouched); a footer that fails
 // a check is a Failure.
 inline compress_status_type pwrel_info(const void *compressed_data, size_t compressed_size, bool &pwrel,

@@ -853,8 +853,8 @@ int mgh_verify_masked(const void *compressed_data, size_t compressed_size, const
  * coords and config (its domain decomposition included) pass through unchanged. Memory spaces, footprint
  * (a host array is uploaded once and transformed in place; a device array is not modified and y is written beside
  * it), element count and MGH_ERR_OUTPUT_TOO_LARGE as for mgh_compress_masked.
- * Not built: reduced-resolution, preview and progressive readers of such buffers; ladders, budgets, targets and
- * layers; _multi and _dist; telling NaN from Inf, or -0.0 from +0.0. */
+ * Not built: the progressive reader and verify of a view of such buffers; ladders, budgets, targets and layers;
+ * _multi and _dist; telling NaN from Inf, or -0.0 from +0.0. */
 int mgh_compress_pwrel(int D, int dtype, const uint64_t *shape, double eps, double abs_floor, const void *original_data,
                        void **compressed_data, size_t *compressed_size, const void *const *coords,
                        const mgh_config *config, int output_pre_allocated);
@@ -863,6 +863,33 @@ int mgh_compress_pwrel(int D, int dtype, const uint64_t *shape, double eps, doub
  * mgh_decompress. A buffer without the footer (a plain container, a masked buffer) is MGH_ERR_FORMAT. */
 int mgh_decompress_pwrel(const void *compressed_data, size_t compressed_size, const mgh_config *config,
                          void **decompressed_data, int output_pre_allocated);
+/* Such a buffer at reduced resolution and in previews. THE RULE (part of the contract):
+ *  - a node of a level array or of a coarsened array takes its CLASS AND SIGN from the element of the FULL array at
+ *    that node's index (mgh_infer_level_nodes, mgh_infer_coarsened_nodes). This is sampling, as for masks;
+ *  - a position of a preview or of a preview window takes them from that position of the full array;
+ *  - the class is read from the mask bit and the flag bit: both -> a quiet NaN; the mask bit alone -> +0.0;
+ *    otherwise +-T(exp2((double)y')), where y' is bit for bit what the reader of the same name without `pwrel_`
+ *    writes for the container part (the first C bytes) alone, the flag bit is the sign and the magnitude is clamped
+ *    to [smallest normal, largest finite] of T: the inverse pass of mgh_decompress_pwrel, unchanged.
+ * THE OUTPUT CARRIES NO ERROR BOUND: it is exp2 of a coarse or prolonged y, and near zeroed or non-finite elements it
+ * carries the influence of the fill. level = l_target, halvings = 0 and the preview at 0 halvings are bit for bit
+ * mgh_decompress_pwrel.
+ * Each call is: the footer -> the plain reader on the first C bytes -> the mask record and the flag record of the
+ * full array -> one pass over the view that reads both bits through the view's node lists (the window's lists are
+ * lo + i; the preview runs the full array's inverse pass). Arguments, refusals and memory-space rules are those of
+ * the reader each one wraps, as for the mgh_decompress_masked_* readers (_level needs one subdomain; the coarsened
+ * and preview readers take decomposed containers). A buffer without the footer is MGH_ERR_FORMAT.
+ * The classes and signs of a view alone are its masks: mgh_decompress_mask_level / _coarsened / _window on the first
+ * M bytes (the masked buffer) give the sampled mask bit. */
+int mgh_decompress_pwrel_level(const void *compressed_data, size_t compressed_size, int level, void **decompressed_data,
+                               const mgh_config *config, int output_pre_allocated);
+int mgh_decompress_pwrel_coarsened(const void *compressed_data, size_t compressed_size, int halvings,
+                                   void **decompressed_data, const mgh_config *config, int output_pre_allocated);
+int mgh_decompress_pwrel_preview(const void *compressed_data, size_t compressed_size, int halvings,
+                                 void **decompressed_data, const mgh_config *config, int output_pre_allocated);
+int mgh_decompress_pwrel_preview_window(const void *compressed_data, size_t compressed_size, int halvings,
+                                        const uint64_t *lo, const uint64_t *ext, void **decompressed_data,
+                                        const mgh_config *config, int output_pre_allocated);
 /* 1 and *info for such a buffer, 0 for a buffer without the footer's magic, MGH_ERR_FORMAT for a footer that has
  * the magic and fails a check (M + S + 56 == size, the masked buffer's own checks, S against kind and n,
  * n_flag <= n, the flag record's CRC-32). delta is the tolerance in the container's header. Kinds: 0 packed

@@ -49,6 +49,8 @@ LEVEL_LAYERS_SYMBOLS = ["mgh_quantize_residual_linear", "mgh_dequantize_add_line
 INTERNAL_SYMBOLS = ["mgh_mask_sample_", "mgh_compare_masked_"]
 # ... and the three streaming passes of the pointwise relative bound (pwrel_forward / pwrel_inverse / compare_pwrel)
 PWREL_INTERNAL_SYMBOLS = ["mgh_pwrel_forward_", "mgh_pwrel_inverse_", "mgh_compare_pwrel_"]
+# ... and the inverse pass over a level array, a coarsened array or a window (pwrel_inverse_sampled)
+PWREL_VIEW_INTERNAL_SYMBOLS = ["mgh_pwrel_inverse_sampled_"]
 
 
 class MgardHipError(RuntimeError):
@@ -213,6 +215,7 @@ def load_library():
                                      C.c_int, vp]
     L.mgh_pwrel_forward_.argtypes = [C.c_int, C.c_int, u64p, vp, C.c_double, vp, vp, vp, vp, vp]
     L.mgh_pwrel_inverse_.argtypes = [C.c_int, C.c_int, u64p, vp, vp, vp, vp]
+    L.mgh_pwrel_inverse_sampled_.argtypes = [C.c_int, C.c_int, u64p, vp, vp, u64p, C.POINTER(vp), vp, vp]
     L.mgh_compare_pwrel_.argtypes = [C.c_int, C.c_int, u64p, vp, vp, C.c_double, C.POINTER(PwrelCompare), vp]
     _lib = L
     return L
@@ -418,6 +421,35 @@ def compare_pwrel(original, reconstructed, abs_floor=0.0):
     return out
 
 
+def _sample_lists(idx_lists, shape, out_shape, device, what):
+    """(keepalive, pointers, lengths) of one index list per dimension as mgh_mask_sample_ takes them: an int sequence,
+    a cuda int32 / uint32 tensor, or None for the identity 0 .. out_shape[d] - 1."""
+    import torch
+    if len(idx_lists) != len(shape):
+        raise ValueError("%s: one index list (or None) per dimension" % what)
+    keep, ptrs, lens = [], [], []
+    for d, lst in enumerate(idx_lists):
+        if lst is None:
+            ptrs.append(None)
+            lens.append(shape[d] if out_shape is None else int(out_shape[d]))
+            continue
+        if isinstance(lst, torch.Tensor):
+            if not (lst.is_cuda and lst.is_contiguous() and lst.dim() == 1 and lst.dtype in (torch.int32, getattr(torch, "uint32", torch.int32))):
+                raise ValueError("%s: an index tensor must be a contiguous 1-D cuda int32 / uint32 tensor" % what)
+            t = lst
+        else:
+            a = np.asarray(lst, dtype=np.int64).reshape(-1)
+            if a.size and (a.min() < 0 or a.max() > 0xffffffff):
+                raise ValueError("%s: index outside 0 .. 2^32 - 1" % what)
+            t = torch.from_numpy(a.astype(np.uint32).view(np.int32)).to(device)
+        keep.append(t)
+        ptrs.append(t.data_ptr())
+        lens.append(int(t.numel()))
+    if out_shape is not None and tuple(int(e) for e in out_shape) != tuple(lens):
+        raise ValueError("%s: out_shape disagrees with the lengths of the lists" % what)
+    return keep, ptrs, lens
+
+
 def mask_sample(words, shape, idx_lists, out_shape=None):
     """mgh_mask_sample_: (out_words, count) -- the packed mask of the dense array whose element (i_0 ...) is element
     (idx_0[i_0] ...) of the array of `shape` that `words` is the packed mask of. idx_lists: one entry per dimension,
@@ -427,30 +459,9 @@ def mask_sample(words, shape, idx_lists, out_shape=None):
     import torch
     shape = tuple(int(e) for e in shape)
     D = len(shape)
-    if len(idx_lists) != D:
-        raise ValueError("mask_sample: one index list (or None) per dimension")
+    keep, ptrs, lens = _sample_lists(idx_lists, shape, out_shape, words.device, "mask_sample")
     n = int(np.prod(shape, dtype=np.int64))
     wp = _mask_words(words, n, "mask_sample")
-    keep, ptrs, lens = [], [], []
-    for d, lst in enumerate(idx_lists):
-        if lst is None:
-            ptrs.append(None)
-            lens.append(shape[d] if out_shape is None else int(out_shape[d]))
-            continue
-        if isinstance(lst, torch.Tensor):
-            if not (lst.is_cuda and lst.is_contiguous() and lst.dim() == 1 and lst.dtype in (torch.int32, getattr(torch, "uint32", torch.int32))):
-                raise ValueError("mask_sample: an index tensor must be a contiguous 1-D cuda int32 / uint32 tensor")
-            t = lst
-        else:
-            a = np.asarray(lst, dtype=np.int64).reshape(-1)
-            if a.size and (a.min() < 0 or a.max() > 0xffffffff):
-                raise ValueError("mask_sample: index outside 0 .. 2^32 - 1")
-            t = torch.from_numpy(a.astype(np.uint32).view(np.int32)).to(words.device)
-        keep.append(t)
-        ptrs.append(t.data_ptr())
-        lens.append(int(t.numel()))
-    if out_shape is not None and tuple(int(e) for e in out_shape) != tuple(lens):
-        raise ValueError("mask_sample: out_shape disagrees with the lengths of the lists")
     n_out = int(np.prod(lens, dtype=np.int64))
     out_words = torch.empty((n_out + 63) // 64, dtype=torch.int64, device=words.device)
     d_count = torch.empty(1, dtype=torch.int64, device=words.device)
@@ -460,6 +471,28 @@ def mask_sample(words, shape, idx_lists, out_shape=None):
                                               C.c_void_p(d_count.data_ptr()), _stream()))
     del keep
     return out_words, int(d_count.item())
+
+
+def pwrel_inverse_sampled(data, mask_words, flag_words, shape, idx_lists):
+    """mgh_pwrel_inverse_sampled_, in place over y' of a VIEW: pwrel_inverse with the two bits of element (i_0 ...) of
+    `data` taken from element (idx_0[i_0] ...) of the array of `shape` that mask_words / flag_words are the packed maps
+    of -- pwrel_inverse(data, mask_sample(mask_words, ...)[0], mask_sample(flag_words, ...)[0]) in one pass. idx_lists
+    as for mask_sample, with the data's shape as out_shape; an entry >= shape[d] reads nothing and gives a valid,
+    positive element."""
+    import torch
+    dt, oshp, D = _mask_array(data, "pwrel_inverse_sampled")
+    shape = tuple(int(e) for e in shape)
+    if len(shape) != D:
+        raise ValueError("pwrel_inverse_sampled: `shape` must have the data's number of dimensions")
+    keep, ptrs, lens = _sample_lists(idx_lists, shape, tuple(int(e) for e in oshp), data.device, "pwrel_inverse_sampled")
+    n = int(np.prod(shape, dtype=np.int64))
+    with torch.cuda.device(data.device):
+        _check(load_library().mgh_pwrel_inverse_sampled_(D, dt, (C.c_uint64 * D)(*shape),
+                                                         _mask_words(mask_words, n, "pwrel_inverse_sampled"),
+                                                         _mask_words(flag_words, n, "pwrel_inverse_sampled"), oshp,
+                                                         (C.c_void_p * D)(*ptrs), C.c_void_p(data.data_ptr()), _stream()))
+    del keep
+    return data
 
 
 def compare_masked(a, b, words, ld_m=None, bit0=0):

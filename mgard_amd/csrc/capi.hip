@@ -4680,6 +4680,24 @@ int mask_args(const char *who, int D, int dtype, const uint64_t *shape, uint64_t
 inline unsigned mask_blocks(uint64_t items) {
   return (unsigned)std::min<uint64_t>(std::max<uint64_t>(items, 1), mgh::mask::kMaxBlocks);
 }
+// The argument block of a sample (mgh_mask_sample_, mgh_pwrel_inverse_sampled_): both shapes within the sizes of the
+// mgh_mask_* calls, `pointers` (the call's arrays are there), shapes and lists right-aligned with leading 1s.
+int mask_sample_args(const char *who, int D, int dtype, const uint64_t *shape, const uint64_t *out_shape,
+                     const uint32_t *const *d_idx, bool pointers, mgh::mask::MaskSampleArgs &A, uint64_t *n, uint64_t *n_out) {
+  static_assert(mgh::kMaskMaxDim == MGH_MAX_DIM, "mask_plan.hpp: kMaskMaxDim");
+  TRY(mask_args(who, D, dtype, shape, n));
+  TRY(mask_args(who, D, dtype, out_shape, n_out));
+  if (!pointers) return fail(MGH_ERR_INVALID_ARGUMENT, std::string(who) + ": NULL argument");
+  for (int k = 0; k < MGH_MAX_DIM; k++) {
+    const int d = k - (MGH_MAX_DIM - D);
+    A.shape[k] = d >= 0 ? (uint32_t)shape[d] : 1u;
+    A.out_shape[k] = d >= 0 ? (uint32_t)out_shape[d] : 1u;
+    A.idx[k] = d >= 0 && d_idx ? d_idx[d] : nullptr;
+    if (!A.idx[k] && A.out_shape[k] > A.shape[k])
+      return fail(MGH_ERR_INVALID_ARGUMENT, std::string(who) + ": the identity list (NULL) needs out_shape[d] <= shape[d]");
+  }
+  return MGH_SUCCESS;
+}
 }  // namespace
 
 int mgh_mask_scan(int D, int dtype, const uint64_t *shape, const void *data, int flags, double fill_value,
@@ -4770,20 +4788,9 @@ int mgh_mask_restore(int D, int dtype, const uint64_t *shape, const uint64_t *wo
 // it): the public faces of the sample are the mgh_decompress_masked_* / mgh_decompress_mask_* readers.
 int mgh_mask_sample_(int D, const uint64_t *shape, const uint64_t *words, const uint64_t *out_shape,
                      const uint32_t *const *d_idx, uint64_t *out_words, uint64_t *d_count, void *stream) {
-  static_assert(mgh::kMaskMaxDim == MGH_MAX_DIM, "mask_plan.hpp: kMaskMaxDim");
   uint64_t n = 0, n_out = 0;
-  TRY(mask_args("mgh_mask_sample_", D, MGH_FLOAT, shape, &n));
-  TRY(mask_args("mgh_mask_sample_", D, MGH_FLOAT, out_shape, &n_out));
-  if (!words || !out_words) return fail(MGH_ERR_INVALID_ARGUMENT, "mgh_mask_sample_: NULL argument");
   mgh::mask::MaskSampleArgs A;
-  for (int k = 0; k < MGH_MAX_DIM; k++) {  // right-aligned, leading 1s
-    const int d = k - (MGH_MAX_DIM - D);
-    A.shape[k] = d >= 0 ? (uint32_t)shape[d] : 1u;
-    A.out_shape[k] = d >= 0 ? (uint32_t)out_shape[d] : 1u;
-    A.idx[k] = d >= 0 && d_idx ? d_idx[d] : nullptr;
-    if (!A.idx[k] && A.out_shape[k] > A.shape[k])
-      return fail(MGH_ERR_INVALID_ARGUMENT, "mgh_mask_sample_: the identity list (NULL) needs out_shape[d] <= shape[d]");
-  }
+  TRY(mask_sample_args("mgh_mask_sample_", D, MGH_FLOAT, shape, out_shape, d_idx, words && out_words, A, &n, &n_out));
   hipStream_t st = (hipStream_t)stream;
   const uint64_t nwords_out = mgh::mask_words(n_out);
   if (d_count) HIP_TRY(hipMemsetAsync(d_count, 0, sizeof(uint64_t), st));
@@ -4794,7 +4801,7 @@ int mgh_mask_sample_(int D, const uint64_t *shape, const uint64_t *words, const 
 }
 
 // ---- pointwise relative error bound (kernels_pwrel.hpp; classes and tolerance: pwrel_plan.hpp) ------------
-// The three streaming passes of mgh_compress_pwrel and its readers (include/mgard_hip.h describes them beside
+// The streaming passes of mgh_compress_pwrel and its readers (include/mgard_hip.h describes the first three beside
 // mgh_pwrel_stats / mgh_pwrel_compare). Like the mgh_mask_* calls: no hierarchy, dense DEVICE arrays on the current
 // device, 1 ... 2^32 - 1 elements, the stream last. INTERNAL for now (trailing underscore, in no public header; the
 // Python layer and the tests call them): the public faces are mgh_compress_pwrel, mgh_decompress_pwrel and
@@ -4851,6 +4858,36 @@ int mgh_pwrel_inverse_(int D, int dtype, const uint64_t *shape, const uint64_t *
   else
     mgh::pwrel::k_pwrel_inverse<double><<<blocks, mgh::mask::kThreads, 0, st>>>(
         (const unsigned long long *)mask_words, (const unsigned long long *)flag_words, n, (double *)data_inout);
+  HIP_TRY(hipGetLastError());
+  return MGH_SUCCESS;
+}
+
+// mgh_pwrel_inverse_ over a VIEW of the array -- a level or coarsened array through its node lists, a window through
+// lo + i -- in one pass (k_pwrel_inverse_sampled). data_inout: the dense y' of out_shape; mask_words / flag_words: the
+// packed maps of the FULL array of `shape`. Element (i_0 ...) of the view takes both bits from element
+// (idx_0[i_0] ...) of the full array: SAMPLING, as mgh_mask_sample_ does it, whose result for each map followed by
+// mgh_pwrel_inverse_ this call equals bit for bit, without the two sampled maps in between. d_idx, the sizes of both
+// shapes, the identity list and an entry >= shape[d] (nothing read, both bits clear: a valid, positive element) are
+// mgh_mask_sample_'s. ASYNCHRONOUS on `stream`, no allocation, no host synchronisation. INTERNAL like the others.
+int mgh_pwrel_inverse_sampled_(int D, int dtype, const uint64_t *shape, const uint64_t *mask_words, const uint64_t *flag_words,
+                               const uint64_t *out_shape, const uint32_t *const *d_idx, void *data_inout, void *stream) {
+  uint64_t n = 0, n_out = 0;
+  mgh::mask::MaskSampleArgs A;
+  TRY(mask_sample_args("mgh_pwrel_inverse_sampled_", D, dtype, shape, out_shape, d_idx, mask_words && flag_words && data_inout,
+                       A, &n, &n_out));
+  // a group of 2^lg lanes per row: the whole wave for rows of more than 32 elements, else the smallest that covers one
+  const uint32_t nf = A.out_shape[MGH_MAX_DIM - 1], rows = (uint32_t)(n_out / nf);
+  int lg = 6;
+  while (lg > 0 && (1u << (lg - 1)) >= nf) lg--;
+  const uint64_t rows_per_block = (uint64_t)mgh::mask::kWaves << (6 - lg);
+  const unsigned blocks = mask_blocks((rows + rows_per_block - 1) / rows_per_block);
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == MGH_FLOAT)
+    mgh::pwrel::k_pwrel_inverse_sampled<float><<<blocks, mgh::mask::kThreads, 0, st>>>(
+        (const unsigned long long *)mask_words, (const unsigned long long *)flag_words, A, rows, lg, (float *)data_inout);
+  else
+    mgh::pwrel::k_pwrel_inverse_sampled<double><<<blocks, mgh::mask::kThreads, 0, st>>>(
+        (const unsigned long long *)mask_words, (const unsigned long long *)flag_words, A, rows, lg, (double *)data_inout);
   HIP_TRY(hipGetLastError());
   return MGH_SUCCESS;
 }

@@ -5961,6 +5961,22 @@ int masked_read_lists(const MaskedView &v, const mgh_config &cfg, const MaskedRe
   return MGH_SUCCESS;
 }
 
+// The node lists in the cache's index buffer, complete on the device on return; d_idx[d]: the list of dimension d.
+int upload_lists(const std::vector<std::vector<uint32_t>> &lists, hipStream_t st, const uint32_t **d_idx) {
+  HlCache &C = g_cache;
+  std::vector<uint32_t> all;
+  size_t at[MGH_MAX_DIM];
+  for (size_t d = 0; d < lists.size(); d++) {
+    at[d] = all.size();
+    all.insert(all.end(), lists[d].begin(), lists[d].end());
+  }
+  HL_TRY(C.midx.ensure(all.size() * sizeof(uint32_t)));
+  HL_HIP(hipMemcpyAsync(C.midx.p, all.data(), all.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+  HL_HIP(hipStreamSynchronize(st));  // (the lists' host copy ends with this call)
+  for (size_t d = 0; d < lists.size(); d++) d_idx[d] = (const uint32_t *)C.midx.p + at[d];
+  return MGH_SUCCESS;
+}
+
 // The mask of the reader's output, packed, in the cache (queued on `st`): the full mask, or its sample through
 // the lists, which are uploaded into the cache's index buffer.
 int masked_read_words(const MaskedView &v, const std::vector<uint64_t> &oshape, const std::vector<std::vector<uint32_t>> &lists,
@@ -5971,23 +5987,25 @@ int masked_read_words(const MaskedView &v, const std::vector<uint64_t> &oshape, 
   *d_words_out = d_full;
   if (!sampled) return MGH_SUCCESS;
   const int D = (int)oshape.size();
-  std::vector<uint32_t> all;
-  size_t at[MGH_MAX_DIM];
   uint64_t n_out = 1;
-  for (int d = 0; d < D; d++) {
-    at[d] = all.size();
-    all.insert(all.end(), lists[d].begin(), lists[d].end());
-    n_out *= oshape[d];
-  }
-  HL_TRY(C.midx.ensure(all.size() * sizeof(uint32_t)));
+  for (int d = 0; d < D; d++) n_out *= oshape[d];
   HL_TRY(C.msamp.ensure(mask_packed_bytes(n_out)));
-  HL_HIP(hipMemcpyAsync(C.midx.p, all.data(), all.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-  HL_HIP(hipStreamSynchronize(st));  // (the lists' host copy ends with this call)
   const uint32_t *d_idx[MGH_MAX_DIM];
-  for (int d = 0; d < D; d++) d_idx[d] = (const uint32_t *)C.midx.p + at[d];
+  HL_TRY(upload_lists(lists, st, d_idx));
   HL_TRY(mgh_mask_sample_(D, v.hd.shape.data(), d_full, oshape.data(), d_idx, (uint64_t *)C.msamp.p, nullptr, st));
   *d_words_out = (uint64_t *)C.msamp.p;
   return MGH_SUCCESS;
+}
+
+// The plain reader of the view R on the container part, into the pre-allocated device destination *dst.
+int plain_read(const MaskedRead &R, const void *buf, size_t csize, const mgh_config &cfg, void **dst) {
+  switch (R.kind) {
+  case ReadKind::full: return mgh_decompress(buf, csize, dst, &cfg, 1);
+  case ReadKind::level: return mgh_decompress_level(buf, csize, R.level, dst, &cfg, 1);
+  case ReadKind::coarsened: return mgh_decompress_coarsened(buf, csize, R.halvings, dst, &cfg, 1);
+  case ReadKind::preview: return mgh_decompress_preview(buf, csize, R.halvings, dst, &cfg, 1);
+  default: return mgh_decompress_preview_window(buf, csize, R.halvings, R.lo, R.ext, dst, &cfg, 1);
+  }
 }
 
 // masked_open -> the plain reader on the first C bytes into a device buffer -> the mask -> its sample -> restore
@@ -6002,16 +6020,7 @@ int masked_read_impl(const void *buf, size_t size, const mgh_config &cfg, const 
   for (uint64_t e : oshape) bytes *= (size_t)e;
   const size_t csize = (size_t)v.f.container;
   return staged_read(
-      R.who, buf, bytes, cfg, out, prealloc,
-      [&](void **dst) {
-        switch (R.kind) {
-        case ReadKind::full: return mgh_decompress(buf, csize, dst, &cfg, 1);
-        case ReadKind::level: return mgh_decompress_level(buf, csize, R.level, dst, &cfg, 1);
-        case ReadKind::coarsened: return mgh_decompress_coarsened(buf, csize, R.halvings, dst, &cfg, 1);
-        case ReadKind::preview: return mgh_decompress_preview(buf, csize, R.halvings, dst, &cfg, 1);
-        default: return mgh_decompress_preview_window(buf, csize, R.halvings, R.lo, R.ext, dst, &cfg, 1);
-        }
-      },
+      R.who, buf, bytes, cfg, out, prealloc, [&](void **dst) { return plain_read(R, buf, csize, cfg, dst); },
       [&](void *d_data, hipStream_t st) -> int {
         if (v.f.kind == kMaskNone) return MGH_SUCCESS;
         uint64_t *d_words = nullptr;
@@ -6220,6 +6229,9 @@ extern "C" int mgh_pwrel_forward_(int D, int dtype, const uint64_t *shape, const
                                   uint64_t *mask_words, uint64_t *flag_words, mgh_pwrel_stats *stats, void *stream);
 extern "C" int mgh_pwrel_inverse_(int D, int dtype, const uint64_t *shape, const uint64_t *mask_words,
                                   const uint64_t *flag_words, void *data_inout, void *stream);
+extern "C" int mgh_pwrel_inverse_sampled_(int D, int dtype, const uint64_t *shape, const uint64_t *mask_words,
+                                          const uint64_t *flag_words, const uint64_t *out_shape, const uint32_t *const *d_idx,
+                                          void *data_inout, void *stream);
 extern "C" int mgh_compare_pwrel_(int D, int dtype, const uint64_t *shape, const void *original, const void *reconstructed,
                                   double abs_floor, mgh_pwrel_compare *out, void *stream);
 
@@ -6309,25 +6321,47 @@ int pwrel_open(const void *buf, size_t size, PwrelView &v) {
 const char *const kNoPwrelFooter =
     ": no pointwise-relative footer (a plain container has mgh_decompress, a masked buffer mgh_decompress_masked)";
 
-// footer -> mgh_decompress of the container part -> mask words and flag words -> k_pwrel_inverse
-int decompress_pwrel_impl(const void *buf, size_t size, const mgh_config &cfg, void **out, bool prealloc) {
+// THE RULE of the views: a node of a level or coarsened array takes its class and sign from the
+// element of the full array it stands on (sampling, as for masks), a position of a preview or of a window from that
+// position of the full array; the value is k_pwrel_inverse's of the y' the same plain reader writes for the
+// container part alone. Such an output carries no error bound.
+// footer -> the plain reader of the view on the container part -> mask words and flag words of the FULL array ->
+// k_pwrel_inverse (the full array, a preview) or k_pwrel_inverse_sampled through the view's node lists
+int pwrel_read_impl(const void *buf, size_t size, const mgh_config &cfg, const MaskedRead &R, void **out, bool prealloc) {
   PwrelView v;
-  HL_TRY(open_or_refuse(pwrel_open, buf, size, v, std::string("decompress_pwrel") + kNoPwrelFooter));
+  HL_TRY(open_or_refuse(pwrel_open, buf, size, v, std::string(R.who) + kNoPwrelFooter));
+  std::vector<uint64_t> oshape;
+  std::vector<std::vector<uint32_t>> lists;
+  bool sampled = false;
+  HL_TRY(masked_read_lists(v.m, cfg, R, oshape, lists, sampled));
+  size_t bytes = v.m.hd.is_double ? 8 : 4;
+  for (uint64_t e : oshape) bytes *= (size_t)e;
   const uint64_t n = v.m.n;
+  const int D = (int)v.m.hd.shape.size();
   return staged_read(
-      "decompress_pwrel", buf, (size_t)n * (v.m.hd.is_double ? 8 : 4), cfg, out, prealloc,
-      [&](void **dst) { return mgh_decompress(buf, (size_t)v.m.f.container, dst, &cfg, 1); },
+      R.who, buf, bytes, cfg, out, prealloc, [&](void **dst) { return plain_read(R, buf, (size_t)v.m.f.container, cfg, dst); },
       [&](void *d_data, hipStream_t st) -> int {
         HlCache &C = g_cache;
         uint64_t *d_words = nullptr;
         HL_TRY(masked_words(v.m, st, &d_words));
         // (the two records share the symbol buffer and the lossless context of the lane: one after the other)
-        if (hipStreamSynchronize(st) != hipSuccess) return hl_fail(MGH_ERR_DEVICE, "decompress_pwrel: hipStreamSynchronize");
+        if (hipStreamSynchronize(st) != hipSuccess) return hl_fail(MGH_ERR_DEVICE, std::string(R.who) + ": hipStreamSynchronize");
         HL_TRY(C.msamp.ensure(mask_packed_bytes(n)));
         HL_TRY(bitmap_words(v.f.kind, v.rec, n, v.m.lossless, C.msamp.p, st));
-        return mgh_pwrel_inverse_((int)v.m.hd.shape.size(), v.m.dtype, v.m.hd.shape.data(), d_words, (const uint64_t *)C.msamp.p,
-                                  d_data, st);
+        const uint64_t *d_flags = (const uint64_t *)C.msamp.p;
+        if (!sampled) return mgh_pwrel_inverse_(D, v.m.dtype, v.m.hd.shape.data(), d_words, d_flags, d_data, st);
+        const uint32_t *d_idx[MGH_MAX_DIM];
+        HL_TRY(upload_lists(lists, st, d_idx));
+        return mgh_pwrel_inverse_sampled_(D, v.m.dtype, v.m.hd.shape.data(), d_words, d_flags, oshape.data(), d_idx, d_data, st);
       });
+}
+
+int pwrel_read_entry(const void *buf, size_t size, const mgh_config *config, const MaskedRead &R, void **out, int prealloc) {
+  if (!buf || !out) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (prealloc && !*out) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "pre-allocated output is NULL");
+  mgh_config cfg;
+  HL_TRY(masked_config(config, cfg));
+  return hl_guarded([&] { return pwrel_read_impl(buf, size, cfg, R, out, prealloc != 0); });
 }
 
 struct DeviceTemp {
@@ -6350,7 +6384,9 @@ int verify_pwrel_impl(const void *buf, size_t size, const void *original, size_t
   DeviceTemp recon, staged;
   HL_HIP(hipMalloc(&recon.p, bytes));
   void *dst = recon.p;
-  HL_TRY(decompress_pwrel_impl(buf, size, cfg, &dst, true));
+  MaskedRead full;  // (the full array)
+  full.who = "mgh_verify_pwrel";
+  HL_TRY(pwrel_read_impl(buf, size, cfg, full, &dst, true));
   hipStream_t st = g_cache.lane[0].st;
   const void *d_orig = original;
   if (!is_device_pointer(original)) {
@@ -6407,11 +6443,53 @@ int mgh_pwrel_info(const void *compressed_data, size_t compressed_size, struct m
 
 int mgh_decompress_pwrel(const void *compressed_data, size_t compressed_size, const mgh_config *config,
                          void **decompressed_data, int output_pre_allocated) {
-  if (!compressed_data || !decompressed_data) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "NULL argument");
-  if (output_pre_allocated && !*decompressed_data) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "pre-allocated output is NULL");
-  mgh_config cfg;
-  HL_TRY(masked_config(config, cfg));
-  return hl_guarded([&] { return decompress_pwrel_impl(compressed_data, compressed_size, cfg, decompressed_data, output_pre_allocated != 0); });
+  MaskedRead R;  // (the full array)
+  R.who = "decompress_pwrel";
+  return pwrel_read_entry(compressed_data, compressed_size, config, R, decompressed_data, output_pre_allocated);
+}
+
+int mgh_decompress_pwrel_level(const void *compressed_data, size_t compressed_size, int level, void **decompressed_data,
+                               const mgh_config *config, int output_pre_allocated) {
+  if (level < 0) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "level outside 0 .. l_target");
+  MaskedRead R;
+  R.kind = ReadKind::level;
+  R.level = level;
+  R.who = "decompress_pwrel_level";
+  return pwrel_read_entry(compressed_data, compressed_size, config, R, decompressed_data, output_pre_allocated);
+}
+
+int mgh_decompress_pwrel_coarsened(const void *compressed_data, size_t compressed_size, int halvings, void **decompressed_data,
+                                   const mgh_config *config, int output_pre_allocated) {
+  if (halvings < 0) return hl_fail(MGH_ERR_INVALID_ARGUMENT, kBadHalvings);
+  MaskedRead R;
+  R.kind = ReadKind::coarsened;
+  R.halvings = halvings;
+  R.who = "decompress_pwrel_coarsened";
+  return pwrel_read_entry(compressed_data, compressed_size, config, R, decompressed_data, output_pre_allocated);
+}
+
+int mgh_decompress_pwrel_preview(const void *compressed_data, size_t compressed_size, int halvings, void **decompressed_data,
+                                 const mgh_config *config, int output_pre_allocated) {
+  if (halvings < 0) return hl_fail(MGH_ERR_INVALID_ARGUMENT, kBadHalvings);
+  MaskedRead R;
+  R.kind = ReadKind::preview;
+  R.halvings = halvings;
+  R.who = "decompress_pwrel_preview";
+  return pwrel_read_entry(compressed_data, compressed_size, config, R, decompressed_data, output_pre_allocated);
+}
+
+int mgh_decompress_pwrel_preview_window(const void *compressed_data, size_t compressed_size, int halvings, const uint64_t *lo,
+                                        const uint64_t *ext, void **decompressed_data, const mgh_config *config,
+                                        int output_pre_allocated) {
+  if (!lo || !ext) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (halvings < 0) return hl_fail(MGH_ERR_INVALID_ARGUMENT, kBadHalvings);
+  MaskedRead R;
+  R.kind = ReadKind::window;
+  R.halvings = halvings;
+  R.lo = lo;
+  R.ext = ext;
+  R.who = "decompress_pwrel_preview_window";
+  return pwrel_read_entry(compressed_data, compressed_size, config, R, decompressed_data, output_pre_allocated);
 }
 
 int mgh_verify_pwrel(const void *compressed_data, size_t compressed_size, const void *original, size_t original_bytes,

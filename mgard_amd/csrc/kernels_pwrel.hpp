@@ -1,5 +1,5 @@
-// Pointwise relative error bound: the three streaming kernels behind mgh_pwrel_forward_ / mgh_pwrel_inverse_ /
-// mgh_compare_pwrel_ (classes, tolerance and trailer: pwrel_plan.hpp).
+// Pointwise relative error bound: the streaming kernels behind mgh_pwrel_forward_ / mgh_pwrel_inverse_ /
+// mgh_pwrel_inverse_sampled_ / mgh_compare_pwrel_ (classes, tolerance and trailer: pwrel_plan.hpp).
 //   k_pwrel_forward   one pass over x: y = (T)log2((double)|x|) at valid positions (0 at masked ones, which the
 //                     fill overwrites), the mask word and the flag word of every 64 elements -- two wave ballots --
 //                     and the statistics: counts, and minimum / maximum of y over the valid elements as the ordered
@@ -12,6 +12,8 @@
 //                     kernels_compare.hpp: workgroup g reduces slab g (compare_plan.hpp) into one partial,
 //                     k_compare_pwrel_final folds the partials in ascending order. Maxima with the lowest index on
 //                     a tie, and counts: no floating-point sum, so the result does not depend on the order at all.
+//   k_pwrel_inverse_sampled  the same over a level array, a coarsened array or a window, with the two bits taken from
+//                     the full array's maps through the view's node lists (mgh_pwrel_inverse_sampled_).
 // Only vector stores: lane 0 of a wave stores the wave's two words.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -134,25 +136,60 @@ k_pwrel_forward(const T *x, uint64_t n, uint64_t nwords, double floor_eff, T *y,
   }
 }
 
+// What a position decodes to: the class from its mask bit m and its flag bit f, the value from y'.
+template <typename T>
+__device__ inline T pwrel_inverse_value(bool m, bool f, T y) {
+  const double lo = (double)std::numeric_limits<T>::min(), hi = (double)std::numeric_limits<T>::max();
+  if (m) return f ? std::numeric_limits<T>::quiet_NaN() : T(0);
+  double mag = exp2((double)y);
+  mag = mag < lo ? lo : mag;  // (comparisons, not fmin / fmax: a NaN stays one)
+  mag = mag > hi ? hi : mag;
+  return f ? -(T)mag : (T)mag;
+}
+
 template <typename T>
 __global__ void __launch_bounds__(kThreads)
 k_pwrel_inverse(const unsigned long long *__restrict__ mwords, const unsigned long long *__restrict__ fwords, uint64_t n,
                 T *__restrict__ data) {
-  const double lo = (double)std::numeric_limits<T>::min(), hi = (double)std::numeric_limits<T>::max();
   const uint64_t stride = (uint64_t)gridDim.x * kThreads;
   // (a wave's 64 elements share one word of each map: i / 64 is the wave's)
   for (uint64_t i = (uint64_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += stride) {
     const bool m = (mwords[i >> 6] >> (i & 63)) & 1, f = (fwords[i >> 6] >> (i & 63)) & 1;
-    T out;
-    if (m) {
-      out = f ? std::numeric_limits<T>::quiet_NaN() : T(0);
-    } else {
-      double mag = exp2((double)data[i]);
-      mag = mag < lo ? lo : mag;  // (comparisons, not fmin / fmax: a NaN stays one)
-      mag = mag > hi ? hi : mag;
-      out = f ? -(T)mag : (T)mag;
+    data[i] = pwrel_inverse_value<T>(m, f, m ? T(0) : data[i]);
+  }
+}
+
+// mgh_pwrel_inverse_sampled_: k_pwrel_inverse over the dense view y' of A.out_shape -- a level or coarsened array, a
+// window -- whose element (i_0 ...) takes its two bits from element (idx_0[i_0] ...) of the FULL array's maps
+// (mwords, fwords: the packed maps of an array of A.shape). It stands in for k_mask_sample twice and
+// k_pwrel_inverse: the bits are read in place, and no sampled map is stored.
+// Rows run along the last dimension (mask_plan.hpp: mask_row_begin). A group of 2^lg lanes owns a row at a time and
+// walks it with its lanes along the row, so the loads and stores of y' are contiguous; a wave holds 64 >> lg rows.
+// The host picks lg = 6 for rows of more than 32 elements and the smallest group that covers the row below that, so
+// that short rows (the coarse levels') do not leave most of a wave idle. The row is unravelled once, by the group's
+// lanes alike: an element costs no division. An entry outside A.shape reads nothing and counts as both bits clear.
+// Nothing is reduced and no lane waits for another: the result does not depend on the grid.
+template <typename T>
+__global__ void __launch_bounds__(kThreads)
+k_pwrel_inverse_sampled(const unsigned long long *__restrict__ mwords, const unsigned long long *__restrict__ fwords,
+                        mask::MaskSampleArgs A, uint32_t rows, int lg, T *__restrict__ data) {
+  constexpr int M = kMaskMaxDim;
+  const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const uint32_t group = 1u << lg, j0 = lane & (group - 1), per_wave = 64u >> lg;
+  const uint32_t nf = A.out_shape[M - 1];
+  const uint64_t wave = (uint64_t)blockIdx.x * kWaves + wv, nwaves = (uint64_t)gridDim.x * kWaves;
+  for (uint64_t r0 = wave * per_wave + (lane >> lg); r0 < rows; r0 += nwaves * per_wave) {
+    const MaskRow r = mask_row_begin(M, A.shape, A.out_shape, A.idx, (uint32_t)r0);
+    T *row = data + r0 * nf;
+    for (uint32_t j = j0; j < nf; j += group) {
+      uint64_t flat;
+      bool m = false, f = false;
+      if (mask_row_source(r, A.shape[M - 1], A.idx[M - 1], j, flat)) {
+        m = (mwords[flat >> 6] >> (flat & 63)) & 1;
+        f = (fwords[flat >> 6] >> (flat & 63)) & 1;
+      }
+      row[j] = pwrel_inverse_value<T>(m, f, row[j]);
     }
-    data[i] = out;
   }
 }
 

@@ -215,4 +215,50 @@ MGH_MASK_HD inline bool mask_sample_source(int D, const uint32_t *shape, const u
   return mask_flat_index(D, shape, c, flat);
 }
 
+// ---- the same source bit, walked by rows (mgh_pwrel_inverse_sampled_) ------------------------------------------
+// A row of the dense output runs along its last (fastest) dimension: out_shape[D - 1] elements, and
+// prod(out_shape[0 .. D - 2]) rows. The row is unravelled ONCE -- the only divisions -- into the part of the flat
+// source index its slow coordinates give, already multiplied by shape[D - 1]; an element of the row then costs one
+// list entry, one comparison and one addition. The kernel k_pwrel_inverse_sampled (kernels_pwrel.hpp) and
+// tests/cpp/mask_row_walk_dump.cpp share it; the CPU suite holds it against mask_sample_source.
+struct MaskRow {
+  uint64_t base = 0;    // flat source index of the row's element with source coordinate 0 in the last dimension
+  bool inside = false;  // every slow coordinate lies inside the source
+};
+
+MGH_MASK_HD inline uint32_t mask_row_count(int D, const uint32_t *out_shape) {
+  uint32_t rows = 1;
+  for (int d = 0; d + 1 < D; d++) rows *= out_shape[d];
+  return rows;
+}
+
+MGH_MASK_HD inline MaskRow mask_row_begin(int D, const uint32_t *shape, const uint32_t *out_shape,
+                                          const uint32_t *const *lists, uint32_t row) {
+  MaskRow r;
+  uint32_t c[kMaskMaxDim];
+  c[0] = 0;  // (D == 1: the one row has no slow coordinate)
+  for (int d = D - 2; d > 0; d--) {
+    const uint32_t q = row / out_shape[d];
+    c[d] = row - q * out_shape[d];
+    row = q;
+  }
+  if (D > 1) c[0] = row;
+  r.inside = true;
+  for (int d = 0; d + 1 < D; d++) {
+    const uint32_t s = lists[d] ? lists[d][c[d]] : c[d];
+    r.inside = r.inside && s < shape[d];
+    r.base = r.base * shape[d] + s;
+  }
+  r.base *= shape[D - 1];
+  return r;
+}
+
+// the source bit of element j of that row: false (and nothing to read) when a coordinate lies outside the source
+MGH_MASK_HD inline bool mask_row_source(const MaskRow &r, uint32_t shape_last, const uint32_t *list_last, uint32_t j,
+                                        uint64_t &flat) {
+  const uint32_t s = list_last ? list_last[j] : j;
+  flat = r.base + s;
+  return r.inside && s < shape_last;
+}
+
 } // namespace mgh

@@ -55,6 +55,8 @@ HL_SYMBOLS = [
     "mgh_decompress_masked_preview_window", "mgh_decompress_mask_level", "mgh_decompress_mask_coarsened",
     "mgh_decompress_mask_window", "mgh_verify_masked",
     "mgh_compress_pwrel", "mgh_decompress_pwrel", "mgh_pwrel_info", "mgh_verify_pwrel",
+    "mgh_decompress_pwrel_level", "mgh_decompress_pwrel_coarsened", "mgh_decompress_pwrel_preview",
+    "mgh_decompress_pwrel_preview_window",
     "mgh_lossless_compress_sym16", "mgh_lossless_compress_device_sym16", "mgh_lossless_decompress_sym16",
 ]
 
@@ -319,6 +321,10 @@ def _hl():
     L.mgh_compress_pwrel.argtypes = [C.c_int, C.c_int, C.POINTER(u64), C.c_double, C.c_double, vp, C.POINTER(vp),
                                      C.POINTER(C.c_size_t), C.POINTER(vp), C.POINTER(Config), C.c_int]
     L.mgh_decompress_pwrel.argtypes = [vp, C.c_size_t, C.POINTER(Config), C.POINTER(vp), C.c_int]
+    for name in ("mgh_decompress_pwrel_level", "mgh_decompress_pwrel_coarsened", "mgh_decompress_pwrel_preview"):
+        getattr(L, name).argtypes = [vp, C.c_size_t, C.c_int, C.POINTER(vp), C.POINTER(Config), C.c_int]
+    L.mgh_decompress_pwrel_preview_window.argtypes = [vp, C.c_size_t, C.c_int, C.POINTER(u64), C.POINTER(u64),
+                                                      C.POINTER(vp), C.POINTER(Config), C.c_int]
     L.mgh_pwrel_info.argtypes = [vp, C.c_size_t, C.POINTER(PwrelInfo)]
     L.mgh_verify_pwrel.argtypes = [vp, C.c_size_t, vp, C.c_size_t, C.c_int, C.POINTER(Config), C.POINTER(PwrelCompare),
                                    C.POINTER(C.c_int)]
@@ -911,10 +917,72 @@ def pwrel_info(buf):
     return info if rc == 1 else None
 
 
-def decompress_pwrel(buf, config=None, out=None):
+def _pwrel_view(buf, cfg, level, coarsen, what):
+    """(pointer, size, keepalive, container part, shape of the view) of a pointwise-relative buffer and one of the views
+    level / coarsen (at most one of them; none: the full array). Any other buffer: the library's own refusal."""
+    if level is not None and coarsen is not None:
+        raise ValueError("%s: pass at most one of `level` and `coarsen`" % what)
+    L = _hl()
+    p, n, _, keep = _container_ptr(buf)
+    info = pwrel_info(keep)
+    if info is None:  # (raises: no footer)
+        call = (L.mgh_decompress_pwrel_level if level is not None else
+                L.mgh_decompress_pwrel_coarsened if coarsen is not None else L.mgh_decompress_pwrel_preview)
+        _check(call(p, n, 0, C.byref(C.c_void_p()), C.byref(cfg), 0))
+        raise MgardHipError("%s: a buffer without the pointwise-relative footer was not refused" % what)
+    cont = keep[:info.container_size]
+    if level is not None:
+        shape, _ = infer_level(cont, int(level), cfg)
+    elif coarsen is not None:
+        if int(coarsen) < 0:
+            raise ValueError("coarsen must be >= 0")
+        shape, _ = infer_coarsened(cont, int(coarsen), cfg)
+    else:
+        shape = infer(cont)[0]
+    return p, n, keep, cont, shape
+
+
+def decompress_pwrel(buf, config=None, out=None, level=None, coarsen=None):
     """mgh_decompress_pwrel: the array of a pointwise-relative buffer. A numpy array (host buffer) or a cuda tensor;
-    `out` as for decompress_layers. Any other buffer is refused."""
-    return _footed_full(_hl().mgh_decompress_pwrel, pwrel_info, buf, config if config is not None else Config(), out)
+    `out` as for decompress_layers. Any other buffer is refused.
+    `level` / `coarsen`: mgh_decompress_pwrel_level / _coarsened -- every node takes its class and sign from the element
+    of the FULL array it stands on (sampling): NaN, +0.0, or +-exp2 of what decompress(buf[:C], level=...) or
+    (coarsen=...) gives for y. Such an array carries no error bound, and near zeroed or non-finite elements it carries
+    the fill's influence. level = l_target and coarsen = 0 are the full array, bit for bit."""
+    L = _hl()
+    cfg = config if config is not None else Config()
+    if level is None and coarsen is None:
+        return _footed_full(L.mgh_decompress_pwrel, pwrel_info, buf, cfg, out)
+    p, n, keep, cont, shape = _pwrel_view(buf, cfg, level, coarsen, "decompress_pwrel")
+    out, optr = _masked_out(cont, shape, out)
+    if level is not None:
+        _check(L.mgh_decompress_pwrel_level(p, n, int(level), C.byref(optr), C.byref(cfg), 1))
+    else:
+        _check(L.mgh_decompress_pwrel_coarsened(p, n, int(coarsen), C.byref(optr), C.byref(cfg), 1))
+    del keep
+    return out
+
+
+def decompress_pwrel_preview(buf, coarsen, config=None, out=None, window=None):
+    """mgh_decompress_pwrel_preview(_window): NaN, +0.0 or +-exp2 of decompress_preview(buf[:C], coarsen, window=window),
+    by the class and sign of every position of the array (of the window) in the full array. A preview carries no
+    bound; coarsen = 0 is decompress_pwrel."""
+    if coarsen is None:
+        raise ValueError("decompress_pwrel_preview needs `coarsen`")
+    if int(coarsen) < 0:
+        raise ValueError("coarsen must be >= 0")
+    L = _hl()
+    cfg = config if config is not None else Config()
+    p, n, keep, cont, shape = _pwrel_view(buf, cfg, None, None, "decompress_pwrel_preview")
+    if window is None:
+        out, optr = _masked_out(cont, shape, out)
+        _check(L.mgh_decompress_pwrel_preview(p, n, int(coarsen), C.byref(optr), C.byref(cfg), 1))
+    else:
+        wlo, wext = _window_args(window, len(shape))
+        out, optr = _masked_out(cont, tuple(int(e) for e in wext), out)
+        _check(L.mgh_decompress_pwrel_preview_window(p, n, int(coarsen), wlo, wext, C.byref(optr), C.byref(cfg), 1))
+    del keep
+    return out
 
 
 def verify_pwrel(buf, original, config=None):
