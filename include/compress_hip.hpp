@@ -471,6 +471,50 @@ inline compress_status_type verify_pwrel(const void *compressed_data, size_t com
   within = w == 1;
   return detail::status(rc);
 }
+// EXTENSION: mgh_compress_roi. The array within tol everywhere and within boxes[i].tol at every element of box i (up
+// to 16 disjoint boxes, every extent at least 3, s infinite): [container of compress(tol)][one residual record per
+// box][box table][footer]. The first bytes open in every plain reader as the unrefined base. A tol_i the data type
+// cannot carry is a Failure.
+inline compress_status_type compress_roi(DIM D, data_type dtype, std::vector<SIZE> shape, double tol, double s,
+                                         error_bound_type mode, const void *original_data,
+                                         const std::vector<mgh_roi_box> &boxes, void *&compressed_data,
+                                         size_t &compressed_size, std::vector<const Byte *> coords, HighLevelConfig config,
+                                         bool output_pre_allocated) {
+  if (shape.size() != D) return compress_status_type::Failure;
+  const mgh_config c = detail::to_c(config);
+  std::vector<const void *> cp(coords.begin(), coords.end());
+  return detail::status(mgh_compress_roi(D, (int)dtype, shape.data(), tol, s, (int)mode, original_data, (int)boxes.size(),
+                                         boxes.data(), &compressed_data, &compressed_size, cp.empty() ? nullptr : cp.data(),
+                                         &c, output_pre_allocated ? 1 : 0));
+}
+// ... its reader (mgh_decompress_roi). Any buffer without the box footer is a Failure.
+inline compress_status_type decompress_roi(const void *compressed_data, size_t compressed_size, void *&decompressed_data,
+                                           HighLevelConfig config, bool output_pre_allocated) {
+  const mgh_config c = detail::to_c(config);
+  return detail::status(mgh_decompress_roi(compressed_data, compressed_size, &decompressed_data, &c,
+                                           output_pre_allocated ? 1 : 0));
+}
+// ... what the buffer is (mgh_roi_info): roi = false for any other buffer (info untouched); a footer or table that
+// fails a check is a Failure.
+inline compress_status_type roi_info(const void *compressed_data, size_t compressed_size, bool &roi,
+                                     struct mgh_roi_info &info) {
+  const int rc = mgh_roi_info(compressed_data, compressed_size, &info);
+  roi = rc == 1;
+  return rc < 0 ? detail::status(rc) : compress_status_type::Success;
+}
+// ... and mgh_verify_roi: the decoded array against the user's own, over the whole array against the base bound and
+// over every box against that box's (per_box is resized to the number of boxes).
+inline compress_status_type verify_roi(const void *compressed_data, size_t compressed_size, const void *original_data,
+                                       size_t original_bytes, data_type dtype, HighLevelConfig config,
+                                       mgh_verify_result &whole, std::vector<mgh_verify_result> &per_box) {
+  struct mgh_roi_info info;
+  const int rc = mgh_roi_info(compressed_data, compressed_size, &info);
+  if (rc < 0) return detail::status(rc);
+  per_box.assign(rc == 1 ? (size_t)info.nbox : 1, mgh_verify_result{});
+  const mgh_config c = detail::to_c(config);
+  return detail::status(mgh_verify_roi(compressed_data, compressed_size, original_data, original_bytes, (int)dtype, &c,
+                                       &whole, per_box.data()));
+}
 // EXTENSION: mgh_achieved_errors. What verify(compress(tol)) would report for every tolerance of `tols`
 // (1..64), from one decomposition and without writing a container. Containers of one subdomain (Failure
 // otherwise; mgh_last_error() says so); any supported lossless_type.

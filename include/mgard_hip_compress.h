@@ -908,6 +908,63 @@ int mgh_pwrel_info(const void *compressed_data, size_t compressed_size, struct m
 int mgh_verify_pwrel(const void *compressed_data, size_t compressed_size, const void *original, size_t original_bytes,
                      int original_dtype, const mgh_config *config, mgh_pwrel_compare *out, int *within);
 
+/* ---- Region of interest (EXTENSION; the reference has nothing here) ------------------------------------
+ * A tighter POINTWISE bound inside up to 16 disjoint boxes of an array, without paying it everywhere
+ * (csrc/roi_plan.hpp has the rules of the boxes, the derivation of the bound and the trailer):
+ *   C0 = mgh_compress(x, tol), unchanged -> b = mgh_decompress(C0) on the device -> per box one pass: the dense
+ *   residual r_i = fl_T(x[box_i] - b[box_i]) with max |r_i|, max |x| and the count of non-finite values -> tolres_i
+ *   -> C_i = mgh_compress(r_i): ABS, s = inf, shape ext_i, no coordinates, the caller's lossless and huff_block_size
+ *   -> [C0][C_0] ... [C_{nbox-1}][box table, 120 nbox bytes][40-byte footer]
+ * The first C bytes ARE what mgh_compress(x, tol) writes (that call writes them; two calls agree byte for byte up to
+ * the order of the outlier pairs inside a record): every plain reader opens them as the unrefined base.
+ * With A = tol (ABS) or tol * the norm in C0's header (REL), and A_i = tol_i times the same factor, the decoded
+ * array is within A_i of x at every element of box i and within A everywhere:
+ *   |x'' - x| <= |r_i' - r_i| + ulp_T(max |r_i|) / 2 + ulp_T(max |x| + A_i) / 2, so
+ *   tolres_i = A_i - ulp_T(max |r_i|) / 2 - ulp_T(max |x| + A_i) / 2.
+ * Outside the boxes the output is bit for bit mgh_decompress of the first C bytes.
+ * MGH_ERR_INVALID_ARGUMENT, with a message: s not infinite (any other s bounds a norm, not a point); nbox outside
+ * 1 .. 16; a box that leaves the array, has an extent below 3 or meets another box; tol_i outside (0, tol); 2^32
+ * elements or more; an array that, with its decoded base beside it, does not fit max_memory_footprint (arrays with
+ * boxes are not streamed in parts); a non-finite value in a box (masked arrays with boxes are not built); and where
+ * tolres_i < A_i / 2 or tolres_i < 64 ulp_T(max |r_i|) -- the data type cannot carry tol_i there (the 64 ulps are
+ * the measured limit of the container path: pwrel_plan.hpp): a looser bound is never delivered silently.
+ * A box in which the base is exact (max |r_i| = 0) stores nothing: record size 0.
+ * coords and config pass through to C0 unchanged (it may be domain-decomposed). Memory spaces and
+ * MGH_ERR_OUTPUT_TOO_LARGE as for mgh_compress_masked. */
+typedef struct mgh_roi_box {
+  uint64_t lo[MGH_MAX_DIM], ext[MGH_MAX_DIM]; /* the first D entries of each */
+  double tol;
+} mgh_roi_box;
+int mgh_compress_roi(int D, int dtype, const uint64_t *shape, double tol, double s, int error_bound_type,
+                     const void *original_data, int nbox, const mgh_roi_box *boxes, void **compressed_data,
+                     size_t *compressed_size, const void *const *coords, const mgh_config *config,
+                     int output_pre_allocated);
+/* The footer and the table -> mgh_decompress of the first C bytes -> per box with a record: mgh_decompress of C_i
+ * into a device buffer and out[box_i] = fl_T(out[box_i] + r_i') in place. Memory-space rules of mgh_decompress.
+ * A buffer without the footer (a plain container, a masked or pointwise-relative buffer) is MGH_ERR_FORMAT. */
+int mgh_decompress_roi(const void *compressed_data, size_t compressed_size, void **decompressed_data,
+                       const mgh_config *config, int output_pre_allocated);
+/* 1 and *info for such a buffer, 0 for a buffer without the footer's magic, MGH_ERR_FORMAT for a footer that has
+ * the magic and fails a check (every size and offset against the buffer, the table's and the records' CRC-32, the
+ * boxes against the shape in C0's header). D is the array's; lo and ext hold D entries. */
+struct mgh_roi_info { /* (the tag only: the function has the name) */
+  uint64_t container_size;
+  int nbox, D;
+  struct {
+    uint64_t lo[MGH_MAX_DIM], ext[MGH_MAX_DIM];
+    double tol, tolres;
+    uint64_t record_size;
+  } box[16];
+};
+int mgh_roi_info(const void *compressed_data, size_t compressed_size, struct mgh_roi_info *info);
+/* Decodes the whole array into a device buffer and holds it against the user's OWN array with mgh_compare's
+ * reduction: *whole over the entire array against A (which, since A_i < A, covers the outside of the boxes), and
+ * per_box[i] (nbox entries; may be NULL) over box i, through the array's leading dimensions, against A_i;
+ * argmax is then the flat index inside the box. bound_kind = 0; within = 1 exactly when nothing is non-finite and
+ * max_abs_err <= bound. The original may be a host or a device array of the buffer's type and size. */
+int mgh_verify_roi(const void *compressed_data, size_t compressed_size, const void *original, size_t original_bytes,
+                   int original_dtype, const mgh_config *config, mgh_verify_result *whole, mgh_verify_result *per_box);
+
 #ifdef __cplusplus
 }
 #endif

@@ -51,6 +51,8 @@ INTERNAL_SYMBOLS = ["mgh_mask_sample_", "mgh_compare_masked_"]
 PWREL_INTERNAL_SYMBOLS = ["mgh_pwrel_forward_", "mgh_pwrel_inverse_", "mgh_compare_pwrel_"]
 # ... and the inverse pass over a level array, a coarsened array or a window (pwrel_inverse_sampled)
 PWREL_VIEW_INTERNAL_SYMBOLS = ["mgh_pwrel_inverse_sampled_"]
+# ... and the two streaming passes of the region of interest over a box of an array (box_residual / box_add)
+ROI_INTERNAL_SYMBOLS = ["mgh_box_scratch_bytes_", "mgh_box_residual_", "mgh_box_add_"]
 
 
 class MgardHipError(RuntimeError):
@@ -217,6 +219,10 @@ def load_library():
     L.mgh_pwrel_inverse_.argtypes = [C.c_int, C.c_int, u64p, vp, vp, vp, vp]
     L.mgh_pwrel_inverse_sampled_.argtypes = [C.c_int, C.c_int, u64p, vp, vp, u64p, C.POINTER(vp), vp, vp]
     L.mgh_compare_pwrel_.argtypes = [C.c_int, C.c_int, u64p, vp, vp, C.c_double, C.POINTER(PwrelCompare), vp]
+    L.mgh_box_scratch_bytes_.restype = C.c_size_t
+    L.mgh_box_scratch_bytes_.argtypes = []
+    L.mgh_box_residual_.argtypes = [C.c_int, C.c_int, u64p, u64p, u64p, vp, vp, vp, vp, vp]
+    L.mgh_box_add_.argtypes = [C.c_int, C.c_int, u64p, u64p, u64p, vp, vp, vp]
     _lib = L
     return L
 
@@ -419,6 +425,57 @@ def compare_pwrel(original, reconstructed, abs_floor=0.0):
         _check(load_library().mgh_compare_pwrel_(D, dt, shp, C.c_void_p(original.data_ptr()),
                                                  C.c_void_p(reconstructed.data_ptr()), float(abs_floor), C.byref(out), _stream()))
     return out
+
+
+# ---- region of interest (mgh_box_residual_ / mgh_box_add_) -----------------------------------------------------------
+class BoxStats(C.Structure):
+    """What mgh_box_residual_ reduces over a box: max |r| and max |x| over the finite values, and the number of
+    positions whose x or r is not finite."""
+    _fields_ = [("max_abs_r", C.c_double), ("max_abs_x", C.c_double), ("n_nonfinite", C.c_uint64), ("pad", C.c_uint64)]
+
+    def __repr__(self):
+        return "BoxStats(max_abs_r=%r, max_abs_x=%r, n_nonfinite=%d)" % (self.max_abs_r, self.max_abs_x, self.n_nonfinite)
+
+
+def _box_args(data, lo, ext, what):
+    dt, shp, D = _mask_array(data, what)
+    lo, ext = tuple(int(v) for v in lo), tuple(int(v) for v in ext)
+    if len(lo) != D or len(ext) != D:
+        raise ValueError("%s: `lo` and `ext` must have the data's number of dimensions" % what)
+    return dt, shp, D, (C.c_uint64 * D)(*lo), (C.c_uint64 * D)(*ext), ext
+
+
+def box_residual(x, b, lo, ext, sync=True):
+    """mgh_box_residual_ of two cuda tensors of the same shape and type: (r, stats). r: the dense tensor of `ext`,
+    fl(x[box] - b[box]) for the box lo .. lo + ext; stats: BoxStats. sync=False: stats is the cuda int64 tensor the
+    kernel leaves it in (four words: the struct's), and nothing waits for the stream."""
+    import torch
+    dt, shp, D, clo, cext, ext = _box_args(x, lo, ext, "box_residual")
+    if not (isinstance(b, torch.Tensor) and b.is_cuda and b.is_contiguous() and b.dtype == x.dtype and b.shape == x.shape and
+            b.device == x.device):
+        raise ValueError("box_residual: `b` must be a contiguous cuda tensor of x's shape and type")
+    with torch.cuda.device(x.device):
+        L = load_library()
+        r = torch.empty(ext, dtype=x.dtype, device=x.device)
+        scratch = torch.empty(int(L.mgh_box_scratch_bytes_()) // 8, dtype=torch.int64, device=x.device)
+        _check(L.mgh_box_residual_(D, dt, shp, clo, cext, C.c_void_p(x.data_ptr()), C.c_void_p(b.data_ptr()),
+                                   C.c_void_p(r.data_ptr()), C.c_void_p(scratch.data_ptr()), _stream()))
+    if not sync:
+        return r, scratch[:4]
+    return r, BoxStats.from_buffer_copy(scratch[:4].cpu().numpy().tobytes())
+
+
+def box_add(data, r, lo):
+    """mgh_box_add_, in place: data[box] = fl(data[box] + r) for the box lo .. lo + r.shape; nothing else is touched."""
+    import torch
+    if not (isinstance(r, torch.Tensor) and r.is_cuda and r.is_contiguous() and isinstance(data, torch.Tensor) and
+            r.dtype == data.dtype and r.device == data.device):
+        raise ValueError("box_add: `r` must be a contiguous cuda tensor of the data's type")
+    dt, shp, D, clo, cext, ext = _box_args(data, lo, tuple(r.shape) or (1,), "box_add")
+    with torch.cuda.device(data.device):
+        _check(load_library().mgh_box_add_(D, dt, shp, clo, cext, C.c_void_p(r.data_ptr()), C.c_void_p(data.data_ptr()),
+                                           _stream()))
+    return data
 
 
 def _sample_lists(idx_lists, shape, out_shape, device, what):

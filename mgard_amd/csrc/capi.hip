@@ -53,6 +53,7 @@
 #include "kernels_qsym.hpp"
 #include "kernels_mask.hpp"
 #include "kernels_pwrel.hpp"
+#include "kernels_roi.hpp"
 
 namespace {
 
@@ -4926,6 +4927,101 @@ int mgh_compare_pwrel_(int D, int dtype, const uint64_t *shape, const void *orig
   HIP_TRY(hipMemcpyAsync(out, d_out, sizeof(*out), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   scratch.drained = true;
+  return MGH_SUCCESS;
+}
+
+} // extern "C"
+
+// ---- region of interest (kernels_roi.hpp; the scheme and the bound: roi_plan.hpp) ---------------------------
+// The two streaming passes of mgh_compress_roi and mgh_decompress_roi over a box (lo, ext) of a dense DEVICE array
+// of `shape` on the current device, 1 ... 2^32 - 1 elements, every extent of the box at least 1. ASYNCHRONOUS on
+// `stream`, no allocation, no host synchronisation. INTERNAL for now (trailing underscore, in no public header;
+// highlevel.hip, the Python layer and the tests call them): the public faces are mgh_compress_roi, mgh_decompress_roi
+// and mgh_verify_roi.
+namespace {
+struct BoxLaunch {
+  mgh::LdView V;
+  uint64_t offset = 0;  // of the box's first element in the array
+  uint32_t nf = 1;
+  int lg = 6;
+  unsigned blocks = 1;
+};
+int box_args(const char *who, int D, int dtype, const uint64_t *shape, const uint64_t *lo, const uint64_t *ext, bool pointers,
+             BoxLaunch &B) {
+  const std::string w(who);
+  if (D < 1 || D > MGH_MAX_DIM) return fail(MGH_ERR_INVALID_ARGUMENT, w + ": D must be 1 .. MGH_MAX_DIM");
+  if (dtype != MGH_FLOAT && dtype != MGH_DOUBLE) return fail(MGH_ERR_INVALID_ARGUMENT, w + ": unknown dtype");
+  if (!shape || !lo || !ext || !pointers) return fail(MGH_ERR_INVALID_ARGUMENT, w + ": NULL argument");
+  uint64_t n = 1;
+  for (int d = 0; d < D; d++) {
+    if (shape[d] == 0 || shape[d] > 0xffffffffull || n * shape[d] > 0xffffffffull)
+      return fail(MGH_ERR_INVALID_ARGUMENT, w + ": 1 .. 2^32 - 1 elements");
+    n *= shape[d];
+    if (ext[d] == 0 || lo[d] >= shape[d] || ext[d] > shape[d] - lo[d])
+      return fail(MGH_ERR_INVALID_ARGUMENT, w + ": the box leaves the array");
+  }
+  uint64_t stride = 1;
+  B.V.rows = 1;
+  for (int k = MGH_MAX_DIM - 1; k >= 0; k--) {
+    const int d = k - (MGH_MAX_DIM - D);
+    B.V.ext[k] = d >= 0 ? (uint32_t)ext[d] : 1u;
+    B.V.stride[k] = d >= 0 ? stride : 0;
+    if (d >= 0) {
+      B.offset += lo[d] * stride;
+      stride *= shape[d];
+    }
+    if (k < MGH_MAX_DIM - 1) B.V.rows *= B.V.ext[k];
+  }
+  // a group of 2^lg lanes per row: the whole wave for rows of more than 32 elements, else the smallest that covers one
+  B.nf = B.V.ext[MGH_MAX_DIM - 1];
+  B.lg = 6;
+  while (B.lg > 0 && (1u << (B.lg - 1)) >= B.nf) B.lg--;
+  const uint64_t rows_per_block = (uint64_t)mgh::roi::kWaves << (6 - B.lg);
+  B.blocks = (unsigned)std::min<uint64_t>((B.V.rows + rows_per_block - 1) / rows_per_block, mgh::roi::kMaxBlocks);
+  return MGH_SUCCESS;
+}
+}  // namespace
+
+extern "C" {
+
+// the scratch of mgh_box_residual_: the statistics at its start, the workgroups' partials behind them
+size_t mgh_box_scratch_bytes_(void) { return (1 + (size_t)mgh::roi::kMaxBlocks) * sizeof(mgh::roi::BoxStats); }
+
+// r_out (dense, prod(ext) elements) = fl_T(x[box] - b[box]); d_scratch: mgh_box_scratch_bytes_() bytes of DEVICE
+// memory, at whose start the call leaves {double max |r|, double max |x|, u64 positions whose x or r is not finite,
+// u64 0}, the maxima over the finite values of the box. Deterministic: maxima and counts, no atomics.
+int mgh_box_residual_(int D, int dtype, const uint64_t *shape, const uint64_t *lo, const uint64_t *ext, const void *x,
+                      const void *b, void *r_out, void *d_scratch, void *stream) {
+  BoxLaunch B;
+  TRY(box_args("mgh_box_residual_", D, dtype, shape, lo, ext, x && b && r_out && d_scratch, B));
+  static_assert(sizeof(mgh::roi::BoxStats) == 32, "kernels_roi.hpp: the statistics' four words");
+  hipStream_t st = (hipStream_t)stream;
+  mgh::roi::BoxStats *out = (mgh::roi::BoxStats *)d_scratch, *partials = out + 1;
+  if (dtype == MGH_FLOAT)
+    mgh::roi::k_box_residual<float><<<B.blocks, mgh::roi::kThreads, 0, st>>>(
+        (const float *)x + B.offset, (const float *)b + B.offset, B.V, B.nf, B.lg, (float *)r_out, partials);
+  else
+    mgh::roi::k_box_residual<double><<<B.blocks, mgh::roi::kThreads, 0, st>>>(
+        (const double *)x + B.offset, (const double *)b + B.offset, B.V, B.nf, B.lg, (double *)r_out, partials);
+  HIP_TRY(hipGetLastError());
+  mgh::roi::k_box_stats_final<<<1, mgh::roi::kThreads, 0, st>>>(partials, B.blocks, out);
+  HIP_TRY(hipGetLastError());
+  return MGH_SUCCESS;
+}
+
+// data_inout[box] = fl_T(data_inout[box] + r), r dense of prod(ext) elements; nothing outside the box is touched.
+int mgh_box_add_(int D, int dtype, const uint64_t *shape, const uint64_t *lo, const uint64_t *ext, const void *r,
+                 void *data_inout, void *stream) {
+  BoxLaunch B;
+  TRY(box_args("mgh_box_add_", D, dtype, shape, lo, ext, r && data_inout, B));
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == MGH_FLOAT)
+    mgh::roi::k_box_add<float><<<B.blocks, mgh::roi::kThreads, 0, st>>>((float *)data_inout + B.offset, B.V, B.nf, B.lg,
+                                                                        (const float *)r);
+  else
+    mgh::roi::k_box_add<double><<<B.blocks, mgh::roi::kThreads, 0, st>>>((double *)data_inout + B.offset, B.V, B.nf, B.lg,
+                                                                         (const double *)r);
+  HIP_TRY(hipGetLastError());
   return MGH_SUCCESS;
 }
 

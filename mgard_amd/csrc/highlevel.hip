@@ -44,6 +44,7 @@
 #include "target_plan.hpp"
 #include "mask_plan.hpp"
 #include "pwrel_plan.hpp"
+#include "roi_plan.hpp"
 
 extern "C" void mgh_set_last_error_(const char *msg);  // capi.hip
 // (capi.hip: mgh_mask_fill / mgh_mask_restore with the value given as the bits of the data type)
@@ -6501,6 +6502,332 @@ int mgh_verify_pwrel(const void *compressed_data, size_t compressed_size, const 
   HL_TRY(masked_config(config, cfg));
   return hl_guarded([&] {
     return verify_pwrel_impl(compressed_data, compressed_size, original, original_bytes, original_dtype, cfg, out, within);
+  });
+}
+
+} // extern "C"
+
+// ---- region of interest: mgh_compress_roi and its readers (roi_plan.hpp) ------------------------------------
+// (capi.hip: the two streaming passes of kernels_roi.hpp)
+extern "C" size_t mgh_box_scratch_bytes_(void);
+extern "C" int mgh_box_residual_(int D, int dtype, const uint64_t *shape, const uint64_t *lo, const uint64_t *ext, const void *x,
+                                 const void *b, void *r_out, void *d_scratch, void *stream);
+extern "C" int mgh_box_add_(int D, int dtype, const uint64_t *shape, const uint64_t *lo, const uint64_t *ext, const void *r,
+                            void *data_inout, void *stream);
+
+namespace {
+
+struct RoiBoxStats {  // (kernels_roi.hpp: BoxStats)
+  double max_abs_r, max_abs_x;
+  uint64_t n_nonfinite, pad;
+};
+
+// the absolute bound a tolerance of the container `hd` stands for: mgh_verify's rule
+inline double roi_abs_factor(const fmt::Header &hd) { return hd.rel ? hd.norm : 1.0; }
+
+// C0 = mgh_compress(x, tol) into the output -> its header (the norm of a REL bound) -> b = mgh_decompress(C0) on
+// the device -> per box: residual and statistics in one pass -> tolres -> mgh_compress of the residual -> the
+// records, the table and the footer behind C0
+int compress_roi_impl(int D, int dtype, const uint64_t *shape, double tol, double s, int ebtype, const void *original,
+                      std::vector<RoiBox> &B, void **compressed, size_t *csize, const void *const *coords, const mgh_config &cfg,
+                      bool prealloc) {
+  const bool is_double = dtype == MGH_DOUBLE;
+  const size_t elem = is_double ? 8 : 4;
+  const int nbox = (int)B.size();
+  uint64_t n = 1, box_max = 0, box_sum = 0;
+  for (int d = 0; d < D; d++) n *= shape[d];
+  for (const RoiBox &b : B) {
+    box_max = std::max(box_max, roi_box_elems(b));
+    box_sum += roi_box_elems(b);
+  }
+  const size_t bytes = (size_t)n * elem;
+  if (const char *bad = roi_check_footprint(bytes, cfg.max_memory_footprint)) return hl_fail(MGH_ERR_INVALID_ARGUMENT, bad);
+  const bool in_dev = is_device_pointer(original);
+  HL_TRY(cache_prepare(cfg.dev_id));
+  HlCache &C = g_cache;
+  hipStream_t st = C.lane[0].st;
+  // the output: mgh_compress's own capacity for C0 and for every residual, the table and the footer
+  const size_t trailer = (size_t)nbox * kRoiEntryBytes + kRoiFooterBytes, slack = (size_t)1e6;
+  const OutSlot slot{compressed, in_dev, prealloc};
+  size_t cap = 0;
+  if (prealloc) {
+    cap = *csize;
+    if (cap <= trailer) return hl_fail(MGH_ERR_OUTPUT_TOO_LARGE, "compress_roi: the output cannot hold the box table and the footer");
+  } else {
+    cap = bytes + slack + box_sum * elem + (size_t)nbox * slack + trailer;
+    HL_TRY(slot.alloc(cap));
+  }
+  void *out = *slot.slot;
+  size_t container = prealloc ? cap - trailer : bytes + slack;
+  int rc = mgh_compress(D, dtype, shape, tol, s, ebtype, original, &out, &container, coords, &cfg, 1);
+  if (rc != MGH_SUCCESS) return slot.fail(rc);
+  fmt::Header hd;
+  size_t meta = 0;
+  if ((rc = read_header(out, container, hd, meta)) != MGH_SUCCESS) return slot.fail(rc);
+  const double factor = roi_abs_factor(hd);
+  // x on the device (a host array is uploaded once), b beside it, the residual of one box and the statistics
+  const void *x = original;
+  if (!in_dev) {
+    if ((rc = C.mfill.ensure(bytes)) != MGH_SUCCESS) return slot.fail(rc);
+    if ((rc = copy_any(C.mfill.p, original, bytes, st)) != MGH_SUCCESS) return slot.fail(rc);
+    x = C.mfill.p;
+  }
+  if ((rc = C.msamp.ensure(bytes)) != MGH_SUCCESS || (rc = C.msym.ensure((size_t)box_max * elem)) != MGH_SUCCESS ||
+      (rc = C.mwords.ensure(mgh_box_scratch_bytes_())) != MGH_SUCCESS)
+    return slot.fail(rc);
+  void *b = C.msamp.p;
+  if ((rc = mgh_decompress(out, container, &b, &cfg, 1)) != MGH_SUCCESS) return slot.fail(rc);
+  // the residual: the caller's configuration (lossless stage, dictionary, chunk) without its domain decomposition --
+  // a box is a small array of its own, cut only where the footprint asks (the default)
+  mgh_config rcfg = cfg;
+  rcfg.domain_decomposition = MGH_DD_MAXDIM;
+  rcfg.domain_decomposition_dim = 0;
+  rcfg.domain_decomposition_sizes = nullptr;
+  rcfg.num_domain_decomposition_sizes = 0;
+  std::vector<uint8_t> tail;
+  uint64_t at = container;
+  for (int i = 0; i < nbox; i++) {
+    RoiBox &bx = B[i];
+    const uint64_t *lo = bx.lo + (kRoiMaxDim - D), *ext = bx.ext + (kRoiMaxDim - D);
+    if ((rc = mgh_box_residual_(D, dtype, shape, lo, ext, x, b, C.msym.p, C.mwords.p, st)) != MGH_SUCCESS) return slot.fail(rc);
+    RoiBoxStats hs{};
+    if (hipMemcpyAsync(&hs, C.mwords.p, sizeof(hs), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+      return slot.fail(hl_fail(MGH_ERR_DEVICE, "compress_roi: reading the box statistics back"));
+    if (hs.n_nonfinite)
+      return slot.fail(hl_fail(MGH_ERR_INVALID_ARGUMENT,
+                               "compress_roi: a box holds a non-finite value (masked arrays with boxes are not built)"));
+    if (const char *bad = roi_tolres(is_double, bx.tol * factor, hs.max_abs_r, hs.max_abs_x, &bx.tolres))
+      return slot.fail(hl_fail(MGH_ERR_INVALID_ARGUMENT, std::string("compress_") + bad));
+    bx.offset = at;
+    bx.size = 0;
+    bx.crc = fmt::crc32(nullptr, 0);
+    if (hs.max_abs_r == 0) continue;  // the base is exact in the box: nothing is stored
+    void *rec = nullptr;  // (device memory: the residual's own space)
+    size_t rsize = 0;
+    rc = mgh_compress(D, dtype, ext, bx.tolres, std::numeric_limits<double>::infinity(), MGH_ABS, C.msym.p, &rec, &rsize, nullptr,
+                      &rcfg, 0);
+    if (rc != MGH_SUCCESS) return slot.fail(rc);
+    const size_t had = tail.size();
+    tail.resize(had + rsize);
+    rc = dev_to_host(tail.data() + had, rec, rsize);
+    (void)hipFree(rec);
+    if (rc != MGH_SUCCESS) return slot.fail(rc);
+    bx.size = rsize;
+    bx.crc = fmt::crc32(tail.data() + had, rsize);
+    at += rsize;
+  }
+  const std::vector<uint8_t> tf = roi_trailer_serialize(container, B);
+  tail.insert(tail.end(), tf.begin(), tf.end());
+  if (container + tail.size() > cap)
+    return slot.fail(hl_fail(MGH_ERR_OUTPUT_TOO_LARGE, "compress_roi: the output cannot hold container, box records, table and footer"));
+  if (is_device_pointer(out)) {
+    if (hipMemcpyAsync((char *)out + container, tail.data(), tail.size(), hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess)
+      return slot.fail(hl_fail(MGH_ERR_DEVICE, "compress_roi: writing box records, table and footer"));
+  } else {
+    std::memcpy((char *)out + container, tail.data(), tail.size());
+  }
+  *csize = container + tail.size();
+  return MGH_SUCCESS;
+}
+
+// A buffer with boxes opened: the footer, the table, and the header of the container in front of them.
+struct RoiView {
+  RoiFooter f;
+  std::vector<RoiBox> boxes;
+  fmt::Header hd;
+  uint64_t n = 0;
+  int dtype = MGH_FLOAT;
+  std::vector<std::vector<uint8_t>> recs;  // the records on the host, where their CRC-32 is checked
+};
+
+// 1: such a buffer that passed every check; 0: no footer's magic; negative: a status.
+int roi_open(const void *buf, size_t size, RoiView &v) {
+  if (size < kRoiFooterBytes) return 0;
+  const bool in_dev = is_device_pointer(buf);
+  uint8_t tail[kRoiFooterBytes];
+  HL_TRY(host_piece(tail, buf, in_dev, size - kRoiFooterBytes, kRoiFooterBytes));
+  if (!roi_footer_present(tail, size)) return 0;
+  if (const char *bad = roi_footer_parse(tail, size, v.f)) return hl_fail(MGH_ERR_FORMAT, bad);
+  std::vector<uint8_t> table((size_t)v.f.table_bytes);
+  HL_TRY(host_piece(table.data(), buf, in_dev, size - kRoiFooterBytes - table.size(), table.size()));
+  if (const char *bad = roi_table_parse(v.f, table.data(), size, v.boxes)) return hl_fail(MGH_ERR_FORMAT, bad);
+  size_t meta = 0;
+  HL_TRY(read_header(buf, (size_t)v.f.container, v.hd, meta));
+  if (v.hd.shape.empty() || v.hd.shape.size() > MGH_MAX_DIM) return hl_fail(MGH_ERR_FORMAT, "header: dimension");
+  v.n = 1;
+  for (uint64_t e : v.hd.shape) {
+    if (e == 0 || e > 0xffffffffull || v.n * e > 0xffffffffull) return hl_fail(MGH_ERR_FORMAT, "roi footer: an array of 2^32 elements or more");
+    v.n *= e;
+  }
+  v.dtype = v.hd.is_double ? MGH_DOUBLE : MGH_FLOAT;
+  if (const char *bad = roi_table_check_shape(v.boxes, (int)v.hd.shape.size(), v.hd.shape.data())) return hl_fail(MGH_ERR_FORMAT, bad);
+  v.recs.resize(v.boxes.size());
+  for (size_t i = 0; i < v.boxes.size(); i++) {
+    const RoiBox &b = v.boxes[i];
+    v.recs[i].resize((size_t)b.size);
+    HL_TRY(host_piece(v.recs[i].data(), buf, in_dev, (size_t)b.offset, (size_t)b.size));
+    if (const char *bad = roi_record_check_crc(b, v.recs[i].data())) return hl_fail(MGH_ERR_FORMAT, bad);
+  }
+  return 1;
+}
+
+const char *const kNoRoiFooter =
+    ": no box footer (a plain container has mgh_decompress, a masked buffer mgh_decompress_masked, a pointwise-relative "
+    "one mgh_decompress_pwrel)";
+
+// An opened buffer: the plain reader on the first C bytes -> per box with a record: its plain reader into the lane
+// buffer, k_box_add into the box
+int roi_read_view(const char *who, const RoiView &v, const void *buf, const mgh_config &cfg, void **out, bool prealloc) {
+  const int D = (int)v.hd.shape.size();
+  const size_t elem = v.hd.is_double ? 8 : 4, bytes = (size_t)v.n * elem;
+  return staged_read(
+      who, buf, bytes, cfg, out, prealloc, [&](void **dst) { return mgh_decompress(buf, (size_t)v.f.container, dst, &cfg, 1); },
+      [&](void *d_data, hipStream_t st) -> int {
+        HlCache &C = g_cache;
+        for (size_t i = 0; i < v.boxes.size(); i++) {
+          const RoiBox &b = v.boxes[i];
+          if (b.size == 0) continue;
+          const uint64_t *lo = b.lo + (kRoiMaxDim - D), *ext = b.ext + (kRoiMaxDim - D);
+          // (the lane buffer is read by the previous box's pass: one after the other)
+          if (hipStreamSynchronize(st) != hipSuccess) return hl_fail(MGH_ERR_DEVICE, std::string(who) + ": hipStreamSynchronize");
+          HL_TRY(C.msym.ensure((size_t)roi_box_elems(b) * elem));
+          // (the record's checked host copy: a record starts wherever the one before it ended, and the plain reader
+          // of a device buffer reads code units in place)
+          const void *rec = v.recs[i].data();
+          fmt::Header rh;
+          size_t meta = 0;
+          HL_TRY(read_header(rec, (size_t)b.size, rh, meta));
+          if (rh.is_double != v.hd.is_double || rh.shape.size() != (size_t)D || !std::equal(rh.shape.begin(), rh.shape.end(), ext))
+            return hl_fail(MGH_ERR_FORMAT, "roi record: the container does not hold the box's residual");
+          void *lane = C.msym.p;
+          HL_TRY(mgh_decompress(rec, (size_t)b.size, &lane, &cfg, 1));
+          HL_TRY(mgh_box_add_(D, v.dtype, v.hd.shape.data(), lo, ext, C.msym.p, d_data, st));
+        }
+        return MGH_SUCCESS;
+      });
+}
+
+int roi_read_impl(const char *who, const void *buf, size_t size, const mgh_config &cfg, void **out, bool prealloc) {
+  RoiView v;
+  HL_TRY(open_or_refuse(roi_open, buf, size, v, std::string(who) + kNoRoiFooter));
+  return roi_read_view(who, v, buf, cfg, out, prealloc);
+}
+
+// decode the whole array into a device buffer, then mgh_compare's reduction over the array and over every box
+int verify_roi_impl(const void *buf, size_t size, const void *original, size_t original_bytes, int original_dtype,
+                    const mgh_config &cfg, mgh_verify_result *whole, mgh_verify_result *per_box) {
+  RoiView v;
+  HL_TRY(open_or_refuse(roi_open, buf, size, v, std::string("mgh_verify_roi") + kNoRoiFooter));
+  const int D = (int)v.hd.shape.size();
+  const size_t elem = v.hd.is_double ? 8 : 4, bytes = (size_t)v.n * elem;
+  if (original_dtype != v.dtype) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "mgh_verify_roi: the original's dtype is not the buffer's");
+  if (original_bytes != bytes) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "mgh_verify_roi: original_bytes is not the array's size");
+  HL_TRY(cache_prepare(cfg.dev_id));
+  DeviceTemp recon, staged, scratch;
+  HL_HIP(hipMalloc(&recon.p, bytes));
+  HL_HIP(hipMalloc(&scratch.p, mgh_compare_scratch_bytes_()));
+  void *dst = recon.p;
+  HL_TRY(roi_read_view("mgh_verify_roi", v, buf, cfg, &dst, true));  // (the view opened above: the records are read once)
+  hipStream_t st = g_cache.lane[0].st;
+  const void *d_orig = original;
+  if (!is_device_pointer(original)) {
+    HL_HIP(hipMalloc(&staged.p, bytes));
+    HL_TRY(copy_any(staged.p, original, bytes, st));
+    d_orig = staged.p;
+  }
+  uint64_t str[MGH_MAX_DIM], run = 1;
+  for (int d = D - 1; d >= 0; d--) {
+    str[d] = run;
+    run *= v.hd.shape[d];
+  }
+  const double factor = roi_abs_factor(v.hd);
+  auto compare = [&](const uint64_t *ext, uint64_t at, bool strided, double bound, mgh_verify_result *res) -> int {
+    HL_TRY(mgh_compare_device_(D, v.dtype, ext, (const char *)d_orig + at * elem, strided ? str : nullptr,
+                               (const char *)recon.p + at * elem, strided ? str : nullptr, scratch.p, st));
+    mgh_verify_result r{};
+    HL_HIP(hipMemcpyAsync(&r.stats, scratch.p, sizeof(r.stats), hipMemcpyDeviceToHost, st));
+    HL_HIP(hipStreamSynchronize(st));
+    r.bound_kind = 0;
+    r.bound = bound;
+    r.achieved = r.stats.max_abs_err;
+    r.within = r.stats.nonfinite == 0 && r.achieved <= r.bound ? 1 : 0;
+    *res = r;
+    return MGH_SUCCESS;
+  };
+  HL_TRY(compare(v.hd.shape.data(), 0, false, v.hd.tol * factor, whole));
+  for (size_t i = 0; per_box && i < v.boxes.size(); i++) {
+    const RoiBox &b = v.boxes[i];
+    uint64_t at = 0;
+    for (int d = 0; d < D; d++) at += b.lo[kRoiMaxDim - D + d] * str[d];
+    HL_TRY(compare(b.ext + (kRoiMaxDim - D), at, true, b.tol * factor, per_box + i));
+  }
+  return MGH_SUCCESS;
+}
+
+} // namespace
+
+extern "C" {
+
+int mgh_compress_roi(int D, int dtype, const uint64_t *shape, double tol, double s, int ebtype, const void *original_data,
+                     int nbox, const mgh_roi_box *boxes, void **compressed_data, size_t *compressed_size,
+                     const void *const *coords, const mgh_config *config, int output_pre_allocated) {
+  if (!compressed_data || !compressed_size || !boxes || !shape || !original_data) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "NULL argument");
+  // the rules of the boxes (roi_plan.hpp) come before anything that needs a device
+  std::vector<RoiBox> B;
+  for (int i = 0; i < nbox && i < kRoiMaxBoxes && D >= 1 && D <= MGH_MAX_DIM; i++)
+    B.push_back(roi_box(D, boxes[i].lo, boxes[i].ext, boxes[i].tol));
+  if (const char *bad = roi_check_boxes(D, shape, tol, s, nbox, B.data())) return hl_fail(MGH_ERR_INVALID_ARGUMENT, bad);
+  HL_TRY(size_call_args(D, dtype, shape, ebtype, original_data, config, output_pre_allocated ? compressed_data : nullptr));
+  return hl_guarded([&]() -> int {
+    return compress_roi_impl(D, dtype, shape, tol, s, ebtype, original_data, B, compressed_data, compressed_size, coords,
+                             *config, output_pre_allocated != 0);
+  });
+}
+
+int mgh_decompress_roi(const void *compressed_data, size_t compressed_size, void **decompressed_data, const mgh_config *config,
+                       int output_pre_allocated) {
+  if (!compressed_data || !decompressed_data) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (output_pre_allocated && !*decompressed_data) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "pre-allocated output is NULL");
+  mgh_config cfg;
+  HL_TRY(masked_config(config, cfg));
+  return hl_guarded([&] {
+    return roi_read_impl("decompress_roi", compressed_data, compressed_size, cfg, decompressed_data, output_pre_allocated != 0);
+  });
+}
+
+int mgh_roi_info(const void *compressed_data, size_t compressed_size, struct mgh_roi_info *info) {
+  if (!compressed_data || !info) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "NULL argument");
+  return hl_guarded([&]() -> int {
+    RoiView v;
+    const int opened = roi_open(compressed_data, compressed_size, v);
+    if (opened <= 0) return opened;
+    const int D = (int)v.hd.shape.size();
+    std::memset(info, 0, sizeof(*info));
+    info->container_size = v.f.container;
+    info->nbox = (int)v.boxes.size();
+    info->D = D;
+    for (size_t i = 0; i < v.boxes.size(); i++) {
+      for (int d = 0; d < D; d++) {
+        info->box[i].lo[d] = v.boxes[i].lo[kRoiMaxDim - D + d];
+        info->box[i].ext[d] = v.boxes[i].ext[kRoiMaxDim - D + d];
+      }
+      info->box[i].tol = v.boxes[i].tol;
+      info->box[i].tolres = v.boxes[i].tolres;
+      info->box[i].record_size = v.boxes[i].size;
+    }
+    return 1;
+  });
+}
+
+int mgh_verify_roi(const void *compressed_data, size_t compressed_size, const void *original, size_t original_bytes,
+                   int original_dtype, const mgh_config *config, mgh_verify_result *whole, mgh_verify_result *per_box) {
+  if (!compressed_data || !original || !whole) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (original_dtype != MGH_FLOAT && original_dtype != MGH_DOUBLE) return hl_fail(MGH_ERR_INVALID_ARGUMENT, "mgh_verify_roi: dtype");
+  mgh_config cfg;
+  HL_TRY(masked_config(config, cfg));
+  return hl_guarded([&] {
+    return verify_roi_impl(compressed_data, compressed_size, original, original_bytes, original_dtype, cfg, whole, per_box);
   });
 }
 

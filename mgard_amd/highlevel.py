@@ -57,6 +57,7 @@ HL_SYMBOLS = [
     "mgh_compress_pwrel", "mgh_decompress_pwrel", "mgh_pwrel_info", "mgh_verify_pwrel",
     "mgh_decompress_pwrel_level", "mgh_decompress_pwrel_coarsened", "mgh_decompress_pwrel_preview",
     "mgh_decompress_pwrel_preview_window",
+    "mgh_compress_roi", "mgh_decompress_roi", "mgh_roi_info", "mgh_verify_roi",
     "mgh_lossless_compress_sym16", "mgh_lossless_compress_device_sym16", "mgh_lossless_decompress_sym16",
 ]
 
@@ -159,6 +160,30 @@ class PwrelInfo(C.Structure):
 
     def __repr__(self):
         return "PwrelInfo(%s)" % ", ".join("%s=%r" % (k, getattr(self, k)) for k, _ in self._fields_)
+
+
+class RoiBox(C.Structure):
+    """mgh_roi_box: a box lo .. lo + ext of an array (the first D entries of each) and its tolerance."""
+    _fields_ = [("lo", C.c_uint64 * MAX_DIM), ("ext", C.c_uint64 * MAX_DIM), ("tol", C.c_double)]
+
+
+class _RoiInfoBox(C.Structure):
+    _fields_ = [("lo", C.c_uint64 * MAX_DIM), ("ext", C.c_uint64 * MAX_DIM), ("tol", C.c_double), ("tolres", C.c_double),
+                ("record_size", C.c_uint64)]
+
+
+class RoiInfo(C.Structure):
+    """mgh_roi_info: the parts of a buffer with boxes -- [container][one record per box][box table][40-byte footer].
+    `boxes`: per box (lo, ext, tol, tolres, record_size), lo and ext as tuples of the array's dimension."""
+    _fields_ = [("container_size", C.c_uint64), ("nbox", C.c_int), ("D", C.c_int), ("box", _RoiInfoBox * 16)]
+
+    @property
+    def boxes(self):
+        return [(tuple(b.lo[:self.D]), tuple(b.ext[:self.D]), b.tol, b.tolres, int(b.record_size))
+                for b in self.box[:self.nbox]]
+
+    def __repr__(self):
+        return "RoiInfo(container_size=%d, boxes=%r)" % (self.container_size, self.boxes)
 
 
 class HeaderInfo(C.Structure):
@@ -326,6 +351,13 @@ def _hl():
     L.mgh_decompress_pwrel_preview_window.argtypes = [vp, C.c_size_t, C.c_int, C.POINTER(u64), C.POINTER(u64),
                                                       C.POINTER(vp), C.POINTER(Config), C.c_int]
     L.mgh_pwrel_info.argtypes = [vp, C.c_size_t, C.POINTER(PwrelInfo)]
+    L.mgh_compress_roi.argtypes = [C.c_int, C.c_int, C.POINTER(u64), C.c_double, C.c_double, C.c_int, vp, C.c_int,
+                                   C.POINTER(RoiBox), C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(vp),
+                                   C.POINTER(Config), C.c_int]
+    L.mgh_decompress_roi.argtypes = [vp, C.c_size_t, C.POINTER(vp), C.POINTER(Config), C.c_int]
+    L.mgh_roi_info.argtypes = [vp, C.c_size_t, C.POINTER(RoiInfo)]
+    L.mgh_verify_roi.argtypes = [vp, C.c_size_t, vp, C.c_size_t, C.c_int, C.POINTER(Config), C.POINTER(VerifyResult),
+                                 C.POINTER(VerifyResult)]
     L.mgh_verify_pwrel.argtypes = [vp, C.c_size_t, vp, C.c_size_t, C.c_int, C.POINTER(Config), C.POINTER(PwrelCompare),
                                    C.POINTER(C.c_int)]
     _declared = True
@@ -999,6 +1031,80 @@ def verify_pwrel(buf, original, config=None):
     _check(L.mgh_verify_pwrel(p, n, optr, nbytes, dt, C.byref(cfg), C.byref(out), C.byref(within)))
     del keep, okeep
     return out, int(within.value)
+
+
+# ---- region of interest: a tighter pointwise bound inside boxes ---------------------------------------------------
+def compress_roi(data, tol, boxes, s=INF, mode=REL, coords=None, config=None, out=None):
+    """mgh_compress_roi: `data` within `tol` (ABS, or REL: times the norm) everywhere and within tol_i inside every box
+    of boxes = [(lo, ext, tol_i), ...] -- up to 16 disjoint boxes, every extent at least 3, 0 < tol_i < tol, s infinite.
+    Returns [container][one record per box][box table][footer]: buf[:roi_info(buf).container_size] is, up to the order of
+    the outlier pairs inside a record, byte for byte compress(data, tol) and opens in every plain reader as the unrefined base. A tol_i the data type cannot carry
+    raises. Host array in, numpy buffer out; cuda tensor in, cuda buffer out. `out`: optional pre-allocated uint8
+    buffer of the same kind (its size is the capacity)."""
+    L = _hl()
+    cfg = config if config is not None else Config()
+    ptr, dt, shape, keep = _as_ptr(data)
+    _wait_for_current_stream(out)
+    D = len(shape)
+    shp = (C.c_uint64 * D)(*shape)
+    cptr, ckeep = _coords_ptr(coords, dt, D)
+    boxes = list(boxes)
+    cbox = (RoiBox * max(len(boxes), 1))()
+    elem, room = (4 if dt == FLOAT else 8), 0
+    for cb, (lo, ext, tol_i) in zip(cbox, boxes):
+        if len(lo) != D or len(ext) != D:
+            raise ValueError("compress_roi: `lo` and `ext` of a box must have the data's number of dimensions")
+        cb.lo[:D] = [int(v) for v in lo]
+        cb.ext[:D] = [int(v) for v in ext]
+        cb.tol = float(tol_i)
+        room += int(np.prod([int(v) for v in ext])) * elem + 1000000 + 120
+    n = int(np.prod(shape))
+    out, optr, size = _writer_out(data, out, n * elem + 1000000 + room + 40)
+    _check(L.mgh_compress_roi(D, dt, shp, float(tol), float(s), int(mode), ptr, len(boxes), cbox, C.byref(optr), C.byref(size),
+                              cptr, C.byref(cfg), 1))
+    del keep, ckeep
+    return out[:size.value]
+
+
+def roi_info(buf):
+    """mgh_roi_info: the RoiInfo of a buffer with boxes, None for a buffer without its footer (a plain container, a
+    masked or pointwise-relative buffer); MgardHipError for a footer or table that fails a check."""
+    p, n, _, keep = _container_ptr(buf)
+    info = RoiInfo()
+    rc = _check(_hl().mgh_roi_info(p, n, C.byref(info)))
+    del keep
+    return info if rc == 1 else None
+
+
+def decompress_roi(buf, config=None, out=None):
+    """mgh_decompress_roi: the array of a buffer with boxes -- decompress of its container part with every box's
+    decoded residual added in place. A numpy array (host buffer) or a cuda tensor; `out`: optional pre-allocated
+    array of the same kind. Any other buffer: the library's own refusal is raised."""
+    L = _hl()
+    cfg = config if config is not None else Config()
+    p, n, _, keep = _container_ptr(buf)
+    info = roi_info(keep)
+    if info is None:
+        _check(L.mgh_decompress_roi(p, n, C.byref(C.c_void_p()), C.byref(cfg), 0))  # (raises: no footer)
+    out, optr = _layers_out(keep[:info.container_size], out)
+    _check(L.mgh_decompress_roi(p, n, C.byref(optr), C.byref(cfg), 1))
+    return out
+
+
+def verify_roi(buf, original, config=None):
+    """mgh_verify_roi: (whole, per_box) of a buffer with boxes against `original`, the user's own array: a VerifyResult
+    over the entire array against the base bound, and one per box against that box's bound."""
+    L = _hl()
+    cfg = config if config is not None else Config()
+    p, n, _, keep = _container_ptr(buf)
+    info = roi_info(keep)
+    nbox = info.nbox if info is not None else 1
+    optr, dt, shape, okeep = _as_ptr(original)
+    nbytes = int(np.prod(shape)) * (4 if dt == FLOAT else 8)
+    whole, per_box = VerifyResult(), (VerifyResult * nbox)()
+    _check(L.mgh_verify_roi(p, n, optr, nbytes, dt, C.byref(cfg), C.byref(whole), per_box))
+    del keep, okeep
+    return whole, list(per_box)
 
 
 class Layers:
